@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the FlatIndex hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c3|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c3|c4] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no torchrun environment (WORLD_SIZE unset) starts the N ranks ITSELF: before anything touches
@@ -27,7 +27,11 @@ torch.distributed only launches the ranks, broadcasts the RCCL unique id and tak
 "single_process_sharded" is the other form of the same index: ONE vdb_flat_index over all N GPUs inside rank 0's process
 (vdb_flat_create_sharded -- the object the reference's single server process would hold), timed while the other ranks idle.
 
-Prints ONE JSON line on rank 0 (the driver contract) with
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`, `dtype`, `path_stats`);
+every side measurement below is null unless `--full` is given.  `--dump-outputs DIR` writes the arrays the last timed step
+returned (ids, distances, counts) as DIR/<name>.npy.
+
+Prints ONE JSON line on rank 0 (the driver contract); with --full it also carries
   "roofline"        the dominant kernel, HIP-event timed on its launch stream, on BOTH axes of SURVEY 8(d) with the
                     binding one named; "traffic" = PMC HBM bytes per launch of the profiled run the line cites;
   "f32_exact_tier"  the same index and queries through the f32-input MFMA tier only (the contract's f32 axis), results
@@ -63,6 +67,9 @@ CONFIGS = {
                workload="FlatIndex 1M x 1536 f32, Euclidean, batch=256, k=10, metadata eq filter as a device bitmask before top-k "
                         "(BASELINE configs[3])"),
 }
+SETTLE_STEPS = 200              # headline steps back to back in front of the W warm-up steps: the device needs 15-20 ms of work
+                                # to raise its clocks; 200 C2 steps are ~125 ms, about what the side legs of --full
+                                # put in front of the headline
 CHUNK = 125_000                 # generation granule: data is identical for every --gpus value
 PEAK_F32_MFMA_TFLOPS = 157.3    # /opt/skills/guides/MI355X_MICROARCH.md, dense f32-input MFMA
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # dense bf16 MFMA (not the 2:1-sparsity headline)
@@ -127,6 +134,14 @@ def host_rows(n_rows, dim, device, data=None):
         c0, c1 = c * chunk, min((c + 1) * chunk, n_rows)
         out[c0:c1] = gen_chunk(c, c1 - c0, dim, device, data).cpu().numpy()
     return out
+
+
+def dump_outputs(out_dir, ids, dists, counts):
+    """The arrays the caller of the timed path receives, as float64 (ids, counts: exact) and float32 (distances)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "ids.npy"), np.asarray(ids).astype(np.float64))
+    np.save(os.path.join(out_dir, "distances.npy"), np.asarray(dists, dtype=np.float32))
+    np.save(os.path.join(out_dir, "counts.npy"), np.asarray(counts).astype(np.float64))
 
 
 def free_port():
@@ -207,18 +222,33 @@ def run_c1(args, vdb, device):
     steps, warm = max(args.steps, 1), max(args.warmup, 1)
     h_mean, h_med, h_p99 = lat(host_call, warm, steps)
     stats = index.last_stats()
-    d_mean, d_med, d_p99 = lat(dev_call, warm, steps)
-    import oracle
-    oracle.lib()
-    t1 = time.perf_counter()
-    n_cpu = 0
-    while n_cpu < 20 or time.perf_counter() - t1 < min(args.cpu_seconds, 3.0):
-        oi, od = oracle.flat_search(cfg["metric"], rows, q, k)
-        n_cpu += 1
-    t_cpu = (time.perf_counter() - t1) / n_cpu
-    exact = bool(int(out_c.value) == len(oi) and np.array_equal(oi, out_i[:len(oi)]) and np.array_equal(od.view(np.uint32), out_d[:len(od)].view(np.uint32)))
-    exact_dev = bool(np.array_equal(d_i.cpu().numpy()[0].astype(np.uint64), oi) and np.array_equal(d_d.cpu().numpy()[0].view(np.uint32), od.view(np.uint32)))
-    alg_bytes = 4.0 * n * dim + 4.0 * dim
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out_i[None, :], out_d[None, :], np.array([out_c.value]))
+    dev_lat, roofline, cpu, recall = None, None, None, None
+    if args.full:
+        d_mean, d_med, d_p99 = lat(dev_call, warm, steps)
+        import oracle
+        oracle.lib()
+        t1 = time.perf_counter()
+        n_cpu = 0
+        while n_cpu < 20 or time.perf_counter() - t1 < min(args.cpu_seconds, 3.0):
+            oi, od = oracle.flat_search(cfg["metric"], rows, q, k)
+            n_cpu += 1
+        t_cpu = (time.perf_counter() - t1) / n_cpu
+        exact = bool(int(out_c.value) == len(oi) and np.array_equal(oi, out_i[:len(oi)]) and np.array_equal(od.view(np.uint32), out_d[:len(od)].view(np.uint32)))
+        exact_dev = bool(np.array_equal(d_i.cpu().numpy()[0].astype(np.uint64), oi) and np.array_equal(d_d.cpu().numpy()[0].view(np.uint32), od.view(np.uint32)))
+        alg_bytes = 4.0 * n * dim + 4.0 * dim
+        dev_lat = {"mean": round(1e6 * d_mean, 2), "median": round(1e6 * d_med, 2), "p99": round(1e6 * d_p99, 2)}
+        recall = float(oracle.recall(oi, out_i[:k]))
+        roofline = {"bound": "hbm", "achieved": round(alg_bytes / d_mean / 1e9, 2), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                    "frac": round(alg_bytes / d_mean / 1e9 / PEAK_HBM_GBS, 6), "traffic": None,
+                    "note": "5.12 MB per query: the call is bound by launch and synchronisation latency (five short kernels and one "
+                            "host sync), not by a roofline; the fraction is quoted on the device-resident call for completeness"}
+        cpu = {"value": round(1.0 / t_cpu, 2), "unit": "queries/s", "cores": 1, "kind": "port",
+               "us_per_search": round(1e6 * t_cpu, 1),
+               "sample": f"{n_cpu} searches of the same query, {n_cpu * t_cpu:.2f} s; oracle/flat_oracle.c",
+               "host_cpus": os.cpu_count(), "ids_and_distances_bit_identical": exact,
+               "device_resident_call_bit_identical": exact_dev}
     line = {
         "metric": f"QPS of single-query FlatIndex::search, {n}x{dim} f32 euclidean k={k} (one vdb_flat_search call per query; latency in config.us_per_search)",
         "value": round(1.0 / h_mean, 1), "unit": "queries/s", "n_gpus": 1, "steps": steps, "warmup": warm,
@@ -228,17 +258,8 @@ def run_c1(args, vdb, device):
         "config": {"workload": cfg["workload"], "name": "c1", "n_rows": n, "dim": dim, "batch": 1, "k": k, "distance": "euclidean",
                    "inputs": "value: host pointers in and out (vdb_flat_search, the literal Index::search drop-in); device_resident: queries and outputs in HBM",
                    "us_per_search": {"host_pointers": {"mean": round(1e6 * h_mean, 2), "median": round(1e6 * h_med, 2), "p99": round(1e6 * h_p99, 2)},
-                                     "device_resident": {"mean": round(1e6 * d_mean, 2), "median": round(1e6 * d_med, 2), "p99": round(1e6 * d_p99, 2)}}},
-        "recall_at_k": float(oracle.recall(oi, out_i[:k])), "path_stats": stats,
-        "roofline": {"bound": "hbm", "achieved": round(alg_bytes / d_mean / 1e9, 2), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                     "frac": round(alg_bytes / d_mean / 1e9 / PEAK_HBM_GBS, 6), "traffic": None,
-                     "note": "5.12 MB per query: the call is bound by launch and synchronisation latency (five short kernels and one "
-                             "host sync), not by a roofline; the fraction is quoted on the device-resident call for completeness"},
-        "cpu_baseline": {"value": round(1.0 / t_cpu, 2), "unit": "queries/s", "cores": 1, "kind": "port",
-                         "us_per_search": round(1e6 * t_cpu, 1),
-                         "sample": f"{n_cpu} searches of the same query, {n_cpu * t_cpu:.2f} s; oracle/flat_oracle.c",
-                         "host_cpus": os.cpu_count(), "ids_and_distances_bit_identical": exact,
-                         "device_resident_call_bit_identical": exact_dev},
+                                     "device_resident": dev_lat}},
+        "recall_at_k": recall, "path_stats": stats, "roofline": roofline, "cpu_baseline": cpu,
     }
     print(json.dumps(line), flush=True)
 
@@ -261,7 +282,12 @@ def main():
     ap.add_argument("--no-shadow", action="store_true", help="skip the side measurement with the opt-in bf16 shadow rows (vdb_flat_set_shadow)")
     ap.add_argument("--no-pipelined", action="store_true", help="skip the two-batches-in-flight side measurement (keeps a profile's per-kernel averages synchronous)")
     ap.add_argument("--no-single-process", action="store_true", help="skip the ONE-index-over-all-GPUs-in-one-process side measurement (vdb_flat_create_sharded)")
-    ap.add_argument("--lean", action="store_true", help="headline only: every side measurement off (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every side measurement (roofline and per-kernel times, f32 tier, pipelined, shadow rows, Gaussian rows, "
+                         "PCIe, after-idle, single-process, repeat rounds, CPU baseline and oracle parity); the --no-* options still apply")
+    ap.add_argument("--lean", action="store_true", help="with --full: the roofline only, every other side measurement off (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the ids, distances and counts the last timed step returned as DIR/<name>.npy")
     ap.add_argument("--data", default="uniform", choices=["uniform", "gauss"], help="distribution of the HEADLINE index")
     ap.add_argument("--screen", type=int, default=1, help="1: bf16 screening tier first (default); 0: f32 MFMA tier only")
     ap.add_argument("--no-wide", action="store_true", help="batches above 256 queries: 256-query passes instead of the 512-query filter kernel (A/B)")
@@ -271,7 +297,7 @@ def main():
     ap.add_argument("--rehearse-fallback", action="store_true", help="with the distributed path: behave as if the C-ABI shard group could not be created (the torch.distributed exchange)")
     ap.add_argument("--dry-launch", action="store_true", help="print this rank's RANK / WORLD_SIZE / LOCAL_RANK as a JSON line and exit (no GPU is touched)")
     args = ap.parse_args()
-    if args.lean:
+    if args.lean or not args.full:
         args.no_cpu = args.no_f32_tier = args.no_gauss = args.no_shadow = args.no_pipelined = args.no_single_process = True
 
     # ---- `--gpus N` outside torchrun: launch the N ranks (before any GPU call in this process)
@@ -478,15 +504,19 @@ def main():
         # (nothing between the last synchronous round and the headline's W + K steps: tools/clock_series.py shows that 5 ms of an
         # idle GPU in front of a 5 + 20-step measurement already cost 7 %, 20 ms cost 12 % -- the leg's summary is built afterwards)
     repeat_rounds = None
-    if distm and not args.lean:
+    if distm and args.full and not args.lean:
         # N > 1 has no two-in-flight form: three rounds of the same synchronous group search, reported, in front of the headline
         repeat_rounds = [round(1e3 * timed(step, 3, args.steps)[0] / max(args.steps, 1), 4) for _ in range(3)]
 
+    for _ in range(SETTLE_STEPS):                 # the clock state of a busy GPU, also when no side leg ran in front
+        step()
     elapsed, out = timed(step, args.warmup, args.steps)
     ms_per_step = 1e3 * elapsed / max(args.steps, 1)
     qps = B * args.steps / elapsed
     stats = index.last_stats()
     out = tuple(t.clone() for t in out)          # the search reuses its output tensors; keep this step's results
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *(t.cpu().numpy() for t in out))
     if not distm and not args.no_pipelined:
         pipe_last = bufs[(args.steps - 1) & 1]                      # the last pipelined batch's outputs (untouched since)
         mp_, ms_ = float(np.median(rp)), float(np.median(rs))
@@ -499,7 +529,7 @@ def main():
                              "interleaved rounds of --steps batches each (the headline `value` stays the contract's single W + K run)"}
 
     n_prof = max(3, min(args.steps, 10))
-    kern_ms = kernel_ms_of(index, step, n_prof, local_rows)
+    kern_ms = kernel_ms_of(index, step, n_prof, local_rows) if args.full else 0.0
     n_launch = launches_of(stats, local_rows)                   # filter-pass launches of one step
     b_launch = -(-B // n_launch)                                # queries served by one launch (one fetch of the rows)
     alg_flops = 2.0 * b_launch * local_rows * dim               # 2*B*N*d per launch
@@ -509,7 +539,7 @@ def main():
     # PMC pass under profiles/ (a line must not carry an older tree's counters)
     traffic, traffic_src = None, None
     tp = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tp) and not distm and args.config == "c2" and n_rows == CONFIGS["c2"]["rows"] and dim == 768:
+    if args.full and os.path.exists(tp) and not distm and args.config == "c2" and n_rows == CONFIGS["c2"]["rows"] and dim == 768:
         try:
             tj = json.load(open(tp))
             key = "hbm_bytes_per_launch_bf16_screen" if screened else "hbm_bytes_per_launch"
@@ -551,9 +581,11 @@ def main():
         r.update({"binding_axis": "hbm" if screened_ else "f32_mfma", "axes": axes, "kernel_ms": round(kms, 4)})
         return r
 
-    roofline = roofline_of(kern_ms, screened)
-    roofline["traffic"] = traffic
-    roofline["traffic_source"] = traffic_src
+    roofline = None
+    if args.full:
+        roofline = roofline_of(kern_ms, screened)
+        roofline["traffic"] = traffic
+        roofline["traffic_source"] = traffic_src
 
     # ---- the f32-exact tier (measured before the headline, see above)
     f32_tier = None
@@ -645,7 +677,7 @@ def main():
     # ---- the same W + K measurement on a GPU that was idle for 20 ms: what a caller sees whose batches do not arrive back to back
     # (the device drops its clocks within milliseconds of idling and takes longer than W steps to bring them back)
     after_idle = None
-    if not distm and not args.lean:
+    if not distm and args.full and not args.lean:
         torch.cuda.synchronize()
         time.sleep(0.02)
         el_i, _ = timed(step, args.warmup, args.steps)

@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 def _run(extra):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rehearse-distributed", "--rows", "300000", "--steps", "6", "--warmup", "2",
-                        "--cpu-seconds", "0"] + extra, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                        "--cpu-seconds", "0", "--full"] + extra, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     return line

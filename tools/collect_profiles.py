@@ -1,16 +1,17 @@
 #!/usr/bin/env python3
-"""Copy the newest rocprofv3 outputs under gpurun_out/ (tools/round_profile.sh) into profiles/ with a tag."""
+"""Copy the newest rocprofv3 outputs under $PROFILE_OUT (tools/round_profile.sh) into profiles/ with a tag."""
 import collections, csv, glob, json, os, shutil, sys
 tag = sys.argv[1]
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+src = os.environ["PROFILE_OUT"]                 # the directory tools/round_profile.sh wrote to
 def newest(pat):
     fs = glob.glob(os.path.join(root, pat)); fs.sort(key=os.path.getmtime); return fs[-1]
-shutil.copy(newest("gpurun_out/profS/*/*kernel_stats.csv"), os.path.join(root, f"profiles/{tag}_kernel_stats.csv"))
-cm = os.path.join(root, "gpurun_out/cert_margins.json")
+shutil.copy(newest(f"{src}/profS/*/*kernel_stats.csv"), os.path.join(root, f"profiles/{tag}_kernel_stats.csv"))
+cm = os.path.join(root, f"{src}/cert_margins.json")
 if os.path.exists(cm): shutil.copy(cm, os.path.join(root, f"profiles/{tag}_cert_margins.json"))
 out = {}
 for d in ("pmcA", "pmcB", "pmcF", "pmcW"):
-    cc = newest(f"gpurun_out/{d}/*/*counter_collection.csv"); kt = cc.replace("counter_collection", "kernel_trace")
+    cc = newest(f"{src}/{d}/*/*counter_collection.csv"); kt = cc.replace("counter_collection", "kernel_trace")
     trace = {r["Dispatch_Id"]: r for r in csv.DictReader(open(kt))}
     agg = collections.defaultdict(lambda: collections.defaultdict(float)); name = None
     for r in csv.DictReader(open(cc)):
@@ -39,18 +40,18 @@ tj[key + "_detail"] = {"fetch_size_raw_bytes": fetch, "write_size_bytes": write,
     "source": f"profiles/{tag}_pmc_fused.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes of bench.py --steps 3; FETCH doubled per the gfx950 correction)"}
 tj["workload"] = "bench.py default (1Mx768 f32, batch 256, k=10, 1 GPU)"
 json.dump(tj, open(tpath, "w"), indent=1)
-bench = open(os.path.join(root, "gpurun_out/bench_final.json")).read().strip().splitlines()[-1]
+bench = open(os.path.join(root, f"{src}/bench_final.json")).read().strip().splitlines()[-1]
 open(os.path.join(root, f"profiles/{tag}_bench_line.json"), "w").write(bench + "\n")
 # ---- config 3's shape (tools/round_profile.sh): kernel stats, bench line, FETCH / WRITE of the wide filter kernel per launch
 try:
-    shutil.copy(newest("gpurun_out/profS3/*/*kernel_stats.csv"), os.path.join(root, f"profiles/{tag}_c3_kernel_stats.csv"))
+    shutil.copy(newest(f"{src}/profS3/*/*kernel_stats.csv"), os.path.join(root, f"profiles/{tag}_c3_kernel_stats.csv"))
     for cfg in ("c3", "c1", "c4"):
-        f = os.path.join(root, f"gpurun_out/bench_{cfg}.json")
+        f = os.path.join(root, f"{src}/bench_{cfg}.json")
         if os.path.exists(f) and open(f).read().strip():
             open(os.path.join(root, f"profiles/{tag}_{cfg}_bench_line.json"), "w").write(open(f).read().strip().splitlines()[-1] + "\n")
     c3 = {}
     for d in ("pmcF3", "pmcW3"):
-        cc = newest(f"gpurun_out/{d}/*/*counter_collection.csv")
+        cc = newest(f"{src}/{d}/*/*counter_collection.csv")
         agg = collections.defaultdict(lambda: collections.defaultdict(float)); kname = None
         for r in csv.DictReader(open(cc)):
             if "fused_bf16" in r["Kernel_Name"]:
