@@ -184,6 +184,9 @@ int vdb_flat_distances_batch(vdb_flat_index *h, const float *queries, size_t nq,
  * (gathered from the row shards with an RCCL all-gather) into the global
  * top-k, ascending by (distance, id).  All pointers are device pointers on
  * `device`; parts are laid out [nparts][nq][k] with counts [nparts][nq].
+ * Any nparts * k (below 2^32): up to 2048 keys per query are sorted in LDS, above that every element is placed by
+ * binary searches in the other parts, which requires each part's first counts[part][q] entries to be ascending by
+ * (distance, id) -- as every search output is.  Ties between parts go to the lower part index; the result is the same.
  */
 int vdb_merge_topk_device(int device, const uint64_t *d_part_ids, const float *d_part_dists,
                           const uint32_t *d_part_counts, size_t nparts, size_t nq, size_t k,
@@ -221,7 +224,8 @@ int vdb_flat_search_batch_device_wait(vdb_flat_index *h, int ticket);
 
 /* The same merge reading the all-gathered exchange buffer in place.  Each part is `words_per_part` int32
  * words (even): ids int64[nq*k] | dists f32[nq*k] | counts i32[nq] | status i32 | pad.  *d_out_status (may be
- * NULL) receives the maximum status word over the parts, so one host read tells whether any shard failed. */
+ * NULL) receives the maximum status word over the parts, so one host read tells whether any shard failed.  The same
+ * range of nparts * k as vdb_merge_topk_device, and the same requirement above 2048 keys: every part ascending. */
 int vdb_merge_topk_packed_device(int device, const int32_t *d_packed, size_t nparts, size_t words_per_part,
                                  size_t nq, size_t k, uint64_t *d_out_ids, float *d_out_dists,
                                  uint32_t *d_out_counts, uint32_t *d_out_status, void *stream);
@@ -264,6 +268,17 @@ int vdb_flat_set_screen(vdb_flat_index *h, int mode);
  *  0: 256 queries per fetch (the kernel of batches up to 256), ceil(B / 256) reads.
  * No reference counterpart; results are identical either way, bit for bit. */
 int vdb_flat_set_wide(vdb_flat_index *h, int on);
+
+/* The screening tier's LARGE-k range (no reference counterpart; results are identical either way, bit for bit):
+ *  1 (default): 112 < k <= 1024 is served by the bf16 screening pass too -- a deeper filter threshold, up to 2048
+ *     candidates per query, and the certified re-rank of kernels_aux.hip (rerank_large_kernel) -- on indexes of at least
+ *     vdb_flat_large_k_min_rows(k) rows; uncertified queries go to the exact scan.  last_stats_ex()[8] = 1 when it ran,
+ *     [5] = the candidate depth;
+ *  0: k > 112 goes to the exact scan, as before the range existed.
+ * On a sharded handle it applies to every shard. */
+int vdb_flat_set_large_k(vdb_flat_index *h, int on);
+/* The smallest row count (of one handle or one shard) on which the large-k range serves k; 0 outside 112 < k <= 1024. */
+size_t vdb_flat_large_k_min_rows(size_t k);
 
 /*
  * Opt-in bf16 SHADOW of the rows for the screening pass (no reference counterpart; results are identical with and without

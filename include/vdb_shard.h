@@ -62,7 +62,7 @@ void vdb_shard_range(size_t n_rows, int rank, int world, size_t *lo, size_t *hi)
  * The sharded hot call.  COLLECTIVE: every rank calls it with the same queries, nq, dim and k and with the
  * vdb_flat_index of ITS row block (created on the group's device).  Arguments as vdb_flat_search_batch_device;
  * on return every rank holds the GLOBAL top-k: d_out_ids / d_out_dists [nq][k], d_out_counts [nq] = min(k, live
- * rows of all shards passing the mask).  nq * k * world <= ... see vdb_merge_topk_packed_device (world * k <= 2048).
+ * rows of all shards passing the mask).  Any world * k below 2^32 (the merge: vdb_merge_topk_packed_device).
  * `stream`: a hipStream_t of the group's device (NULL = the index's own stream).
  * Returns the worst status over all ranks; VDB_ERR_* raised by another rank's shard is reported here too.
  */

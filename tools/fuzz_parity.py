@@ -53,6 +53,7 @@ def main():
     ap.add_argument("--max-rows", type=int, default=300000)
     ap.add_argument("--shadow", action="store_true")
     ap.add_argument("--round3", action="store_true")
+    ap.add_argument("--large-k", action="store_true", help="add k in the screening tier's large-k range (113..1024) and above it")
     a = ap.parse_args()
     vdb = load_package()
     vdb.build()
@@ -70,7 +71,7 @@ def main():
         metric = int(rng.integers(0, 3))
         kind = str(rng.choice(kinds))
         nq = int(rng.choice([1, 2, 31, 32, 33, 100, 256, 257, 300] + ([7, 8, 9, 511, 512, 513, 700, 1024, 1100] if a.round3 else [])))
-        k = int(rng.choice([1, 2, 10, 10, 10, 30, 48, 49, 100, 112, 113, 150]))
+        k = int(rng.choice([1, 2, 10, 10, 10, 30, 48, 49, 100, 112, 113, 150] + ([200, 300, 300, 500, 1000, 1024, 1025] if a.large_k else [])))
         rows = make_data(rng, n, d, kind)
         if metric == 1:
             rows[np.linalg.norm(rows, axis=1) == 0] += 1.0      # a zero-norm row fails every Cosine search (tested elsewhere)

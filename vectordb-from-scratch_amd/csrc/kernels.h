@@ -269,6 +269,8 @@ struct RerankParams {
     uint32_t lds_row_stride, lds_chunk;                // filled by launch_rerank
 };
 void launch_rerank(const RerankParams& p, uint32_t nq, hipStream_t s);
+// the large-k re-rank of the screening tier: 112 < k <= 1024, up to 2048 candidates per query (kernels_aux.hip)
+void launch_rerank_large(const RerankParams& p, uint32_t nq, hipStream_t s);
 // exhaustive variant: EVERY candidate of the list (up to cand_stride, any order) is re-ranked, the best k are kept;
 // cert[q] = 1 unless the list was truncated upstream (the caller's overflow flag) or a NaN score was seen
 void launch_rerank_all(const RerankParams& p, uint32_t nq, hipStream_t s);

@@ -1310,6 +1310,188 @@ void launch_rerank(const RerankParams& p, uint32_t nq, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Large-k re-rank (screening tier, 112 < k <= 1024).  The same adaptive, certified re-rank as rerank_kernel
+// over up to RL_MAX = 2048 candidates sorted by ranking score.  The distances are computed in the reference's exact operation
+// order, up to RL_THREADS candidates per sweep (one per thread, rows staged through LDS in K slices as in rerank_kernel).  Only
+// the best k (<= 1024) (ordered distance, id) pairs are kept: each sweep writes its distances behind them and one bitonic sort
+// of the area cuts it back to k.  The certificate is cert_eval of rerank_kernel, unchanged: after each round every candidate not
+// yet re-ranked asks "would the result be certified if the re-rank stopped before me", and the first that says yes ends the
+// next round.  Once the list is exhausted the test is against the score of the last candidate (a truncated list) or the filter
+// threshold (the whole pool).  An uncertified query leaves its score cut in thr_next, like rerank_kernel.
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t RL_MAX = 2048, RL_KMAX = 1024, RL_THREADS = 512;
+constexpr uint32_t RL_AREA = 2048;                                // best k (<= 1024) + one sweep (<= 512), a power of two
+__global__ __launch_bounds__(RL_THREADS) void rerank_large_kernel(RerankParams p) {
+    extern __shared__ __attribute__((aligned(16))) float sRows[];   // query row + slice area of one sweep
+    __shared__ uint32_t sDist[RL_AREA];
+    __shared__ uint64_t sId[RL_AREA];
+    __shared__ uint32_t sRowIdx[RL_THREADS];
+    __shared__ uint32_t sAnyNan, sNanKey, sBad, sNext;
+    __shared__ CertConsts sCert;
+    const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint32_t k = p.k;                                       // <= RL_KMAX (the launcher refuses more)
+    const uint32_t cnt = p.cand_cnt[q] < p.kp ? p.cand_cnt[q] : p.kp;
+    const uint64_t* cand = p.cand + (size_t)q * p.cand_stride;
+    if (tid == 0) { sAnyNan = 0; sNanKey = 0; sBad = 0; sNext = 0; }
+    if (tid == RL_THREADS - 1) sCert = cert_consts(p, q, (double)p.qnorm[q]);
+    for (uint32_t i = tid; i < RL_AREA; i += RL_THREADS) { sDist[i] = 0xffffffffu; sId[i] = ~0ull; }
+    const uint32_t dimp = (p.dim + 3) & ~3u;
+    const uint32_t area = p.lds_chunk;
+    float* sQ = sRows;
+    float* sR = sRows + p.lds_row_stride;
+    const float* gq = p.qp + (size_t)q * p.ld;
+    for (uint32_t i = tid * 4; i < dimp; i += RL_THREADS * 4) *reinterpret_cast<float4*>(sQ + i) = *reinterpret_cast<const float4*>(gq + i);
+    __syncthreads();
+    const uint32_t nwaves = RL_THREADS / 64;
+    const float qn_f = p.qnorm[q];
+
+    uint32_t processed = 0, nbest = 0;                            // candidates re-ranked; pairs held in [0, nbest)
+    uint32_t target = cnt < p.kp_first ? cnt : p.kp_first;
+    uint32_t cert = 1;
+    bool cut_ok = false;
+    double cut_ek = 0.0;
+    while (true) {
+        // ---- one round: candidates [processed, target), RL_THREADS per sweep
+        while (processed < target) {
+            const uint32_t n = target - processed < RL_THREADS ? target - processed : RL_THREADS;
+            {
+                uint32_t row = 0xffffffffu;
+                if (tid < n) {
+                    const uint64_t key = cand[processed + tid];
+                    row = (uint32_t)key;
+                    if ((uint32_t)(key >> 32) == 0u) sNanKey = 1u;      // approximate score was NaN (benign race)
+                    const bool ok = row < p.n_rows && (p.rowmask ? ((p.rowmask[row >> 5] >> (row & 31)) & 1u) : true);
+                    if (!ok) { row = 0xffffffffu; sBad = 1u; }
+                }
+                sRowIdx[tid] = row;
+            }
+            __syncthreads();
+            uint32_t W = (area / n - 4u) & ~15u;
+            if (W > dimp) W = (dimp + 15u) & ~15u;
+            if (W < 16) W = 16;                                     // (the launcher sizes the area for 512 rows of 16 + 4)
+            const uint32_t Wp = W + ((W % 8 == 0) ? 4 : 0);
+            const uint32_t myrow = tid < n ? sRowIdx[tid] : 0xffffffffu;
+            float acc = 0.0f;
+            for (uint32_t k0 = 0; k0 < dimp; k0 += W) {
+                const uint32_t wlen = dimp - k0 < W ? dimp - k0 : W;
+                const uint32_t vpr = wlen / 4, bpr = (vpr + 63) / 64;
+                for (uint32_t u = wv; u < n * bpr; u += nwaves) {
+                    const uint32_t r = u / bpr, b = u % bpr, c4 = b * 64 + lane;
+                    const uint32_t row = sRowIdx[r];
+                    if (row != 0xffffffffu && c4 < vpr)
+                        __builtin_amdgcn_global_load_lds((rr_glb_t)(p.rows + (size_t)row * p.ld + k0 + 4 * c4),
+                                                         (rr_lds_t)(sR + (size_t)r * Wp + 256 * b), 16, 0, 0);
+                }
+                __syncthreads();
+                if (myrow != 0xffffffffu) {
+                    const uint32_t flen = (k0 + wlen > p.dim) ? p.dim - k0 : wlen;
+                    acc = p.metric == EUCLID ? fold_sqdiff_part(sQ + k0, sR + (size_t)tid * Wp, flen, acc)
+                                             : fold_dot_part(sQ + k0, sR + (size_t)tid * Wp, flen, acc);
+                }
+                __syncthreads();
+            }
+            if (tid < n) {
+                uint32_t od = 0xffffffffu;
+                uint64_t id = ~0ull;
+                if (myrow != 0xffffffffu) {
+                    const float dist = distance_from_fold(p.metric, acc, qn_f, p.nd[myrow]);
+                    if (dist != dist) sAnyNan = 1u;
+                    od = f32_to_ordered(dist);
+                    id = p.row_ids[myrow];
+                }
+                sDist[nbest + tid] = od;
+                sId[nbest + tid] = id;
+            }
+            __syncthreads();
+            // ---- bitonic sort of [0, P) ascending by (distance, id); unused slots hold the maximum; then keep the best k
+            uint32_t P = 64;
+            while (P < nbest + n) P <<= 1;
+            for (uint32_t size = 2; size <= P; size <<= 1)
+                for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+                    for (uint32_t t = tid; t < P / 2; t += RL_THREADS) {
+                        const uint32_t lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+                        const bool up = ((lo & size) == 0);
+                        const uint32_t da = sDist[lo], db = sDist[hi];
+                        const uint64_t ia = sId[lo], ib = sId[hi];
+                        const bool gt = da > db || (da == db && ia > ib);
+                        if (gt == up) { sDist[lo] = db; sDist[hi] = da; sId[lo] = ib; sId[hi] = ia; }
+                    }
+                    __syncthreads();
+                }
+            processed += n;
+            nbest = nbest + n < k ? nbest + n : k;
+            for (uint32_t i = nbest + tid; i < P; i += RL_THREADS) { sDist[i] = 0xffffffffu; sId[i] = ~0ull; }
+            __syncthreads();
+        }
+        // ---- certification / how much deeper to go (as rerank_kernel; ineligible candidates are counted by sBad)
+        const bool clean = !sNanKey && !sBad;
+        const uint32_t nout = nbest;                              // = min(processed, k) when clean
+        const bool can_test = clean && nout == k && nout > 0;
+        const double ek = can_test ? (double)ordered_to_f32(sDist[nout - 1]) : 0.0;
+        cut_ok = can_test; cut_ek = ek;
+        if (processed < cnt) {
+            if (tid == 0) sNext = 0xffffffffu;
+            __syncthreads();
+            if (can_test)
+                for (uint32_t i = processed + tid; i < cnt; i += RL_THREADS) {
+                    const float T = ordered_to_f32((uint32_t)(cand[i] >> 32));
+                    if (cert_eval(sCert, T, ek)) { atomicMin(&sNext, i); break; }   // (a thread's later candidates come after)
+                }
+            __syncthreads();
+            const uint32_t m = sNext;
+            __syncthreads();
+            if (can_test && m == processed) { cert = 1; break; }
+            if (!clean) { cert = 0; break; }
+            if (can_test && m != 0xffffffffu) target = m;
+            else if (can_test) target = cnt;
+            else target = processed + p.kp_step < cnt ? processed + p.kp_step : cnt;
+            continue;
+        }
+        {
+            bool have_T = false;
+            float T = 0.f;
+            if (cnt == p.kp) { T = ordered_to_f32((uint32_t)(cand[p.kp - 1] >> 32)); have_T = true; }
+            else if (p.thr && p.thr[q] < __uint_as_float(0x7f800000u)) { T = p.thr[q]; have_T = true; }
+            cert = 1;
+            if (have_T && !(can_test && cert_eval(sCert, T, ek))) cert = 0;
+        }
+        break;
+    }
+    const uint32_t nout = nbest;
+    for (uint32_t i = tid; i < k; i += RL_THREADS) {
+        const size_t o = (size_t)q * p.out_stride + i;
+        if (i < nout) { p.out_ids[o] = sId[i]; p.out_dists[o] = ordered_to_f32(sDist[i]); }
+        else { p.out_ids[o] = ~0ull; p.out_dists[o] = __uint_as_float(0x7fc00000u); }
+    }
+    if (tid == 0) {
+        p.out_counts[q] = nout;
+        if (sAnyNan) atomicOr(p.status, ST_NAN);
+        p.cert[q] = cert;
+        if (!cert) atomicOr(p.status + 1, 1u);
+        if (p.thr_next) {
+            float cut = __uint_as_float(0x7fc00000u);
+            if (!cert && cut_ok) cut = score_cut(p, q, cut_ek, (double)qn_f);
+            p.thr_next[q] = cut;
+        }
+        if (p.depth) p.depth[q] = processed;
+    }
+}
+void launch_rerank_large(const RerankParams& p, uint32_t nq, hipStream_t s) {
+    if (!nq || p.k == 0 || p.k > RL_KMAX) return;
+    RerankParams q = p;
+    if (q.kp > RL_MAX) q.kp = RL_MAX;
+    if (q.kp_first == 0 || q.kp_first > q.kp) q.kp_first = q.kp;
+    if (q.kp_step == 0) q.kp_step = 64;
+    const uint32_t dimp = (p.dim + 3) & ~3u;
+    q.lds_row_stride = dimp + 4;
+    // 160 KB of LDS: 24 KB of static sort area, the query row, and the slice area (dim <= 16384: at least 512 rows of 20 floats)
+    const size_t avail = (size_t)128 * 1024 / 4 - q.lds_row_stride;
+    q.lds_chunk = (uint32_t)avail;
+    const size_t lds = ((size_t)q.lds_row_stride + q.lds_chunk) * 4;
+    hipLaunchKernelGGL(rerank_large_kernel, dim3(nq), dim3(RL_THREADS), lds, s, q);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Compact re-run of uncertified queries by the next tier: gather their padded rows and norms into a
 // dense block, and scatter the block's results back to the batch positions.
 // ---------------------------------------------------------------------------------------------
@@ -1768,12 +1950,82 @@ __global__ __launch_bounds__(256) void merge_parts_kernel(const uint64_t* ids, c
     }
     if (tid == 0) out_counts[q] = nout;
 }
+// Above MERGE_MAX keys per query: a RANK merge, no LDS at all.  Every part is ascending by (ordered distance, id) -- as every
+// search output is -- so an element's place in the merged order is its index in its own part plus, for every other part, the
+// number of that part's elements before it (binary search; an equal (distance, id) pair counts as before it when its part
+// index is lower).  The places are distinct, the element placed below k writes itself there, and the output is the one the
+// bitonic sort gives: equal pairs are interchangeable.  One thread per (part, slot): blocks_per_q workgroups of 256 per query.
+__device__ __forceinline__ bool merge_before(uint32_t da, uint64_t ia, uint32_t db, uint64_t ib) {
+    return da < db || (da == db && ia < ib);
+}
+__global__ __launch_bounds__(256) void merge_rank_kernel(const uint64_t* ids, const float* dists, const uint32_t* counts,
+                                                         size_t ids_stride, size_t dists_stride, size_t counts_stride,
+                                                         const uint32_t* status, size_t status_stride, uint32_t nparts,
+                                                         uint32_t k, uint64_t* out_ids, float* out_dists, uint32_t* out_counts,
+                                                         uint32_t* out_status, uint32_t blocks_per_q) {
+    const uint32_t q = blockIdx.x / blocks_per_q;
+    const uint64_t i = (uint64_t)(blockIdx.x - q * blocks_per_q) * 256u + threadIdx.x;
+    if (q == 0 && i == 0 && out_status) {
+        uint32_t worst = 0;
+        for (uint32_t part = 0; part < nparts; ++part) { uint32_t v = status[part * status_stride]; worst = v > worst ? v : worst; }
+        *out_status = worst;
+    }
+    if (i >= (uint64_t)nparts * k) return;
+    uint64_t total = 0;
+    for (uint32_t part = 0; part < nparts; ++part) {
+        const uint32_t c = counts[part * counts_stride + q];
+        total += c < k ? c : k;
+    }
+    const uint32_t nout = total < k ? (uint32_t)total : k;
+    const uint32_t part = (uint32_t)(i / k), j = (uint32_t)(i - (uint64_t)part * k);
+    if (part == 0) {                                              // the first k threads write the empty tail and the count
+        if (j >= nout) { out_ids[(size_t)q * k + j] = ~0ull; out_dists[(size_t)q * k + j] = __uint_as_float(0x7fc00000u); }
+        if (j == 0) out_counts[q] = nout;
+    }
+    uint32_t cnt = counts[part * counts_stride + q];
+    if (cnt > k) cnt = k;
+    if (j >= cnt) return;
+    const float dist = dists[part * dists_stride + (size_t)q * k + j];
+    const uint32_t od = f32_to_ordered(dist);
+    const uint64_t id = ids[part * ids_stride + (size_t)q * k + j];
+    uint64_t rank = j;
+    for (uint32_t o = 0; o < nparts && rank < k; ++o) {
+        if (o == part) continue;
+        uint32_t c = counts[o * counts_stride + q];
+        if (c > k) c = k;
+        const uint64_t* oi = ids + o * ids_stride + (size_t)q * k;
+        const float* odp = dists + o * dists_stride + (size_t)q * k;
+        // first index whose element is NOT before ours (ties with a lower part index count as before)
+        uint32_t lo = 0, hi = c;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            const uint32_t dm = f32_to_ordered(odp[mid]);
+            const uint64_t im = oi[mid];
+            const bool before = merge_before(dm, im, od, id) || (o < part && dm == od && im == id);
+            if (before) lo = mid + 1; else hi = mid;
+        }
+        rank += lo;
+    }
+    if (rank < k) { out_ids[(size_t)q * k + rank] = id; out_dists[(size_t)q * k + rank] = ordered_to_f32(od); }
+}
+static void launch_merge(const uint64_t* ids, const float* dists, const uint32_t* counts, size_t ids_stride, size_t dists_stride,
+                         size_t counts_stride, const uint32_t* status, size_t status_stride, uint32_t nparts, uint32_t nq, uint32_t k,
+                         uint64_t* out_ids, float* out_dists, uint32_t* out_counts, uint32_t* out_status, hipStream_t s) {
+    if ((uint64_t)nparts * k <= MERGE_MAX)
+        hipLaunchKernelGGL(merge_parts_kernel, dim3(nq), dim3(256), 0, s, ids, dists, counts, ids_stride, dists_stride,
+                           counts_stride, status, status_stride, nparts, nq, k, out_ids, out_dists, out_counts, out_status);
+    else {
+        const uint32_t bpq = (uint32_t)(((uint64_t)nparts * k + 255) / 256);       // (the entry points keep nq * bpq below 2^31)
+        hipLaunchKernelGGL(merge_rank_kernel, dim3(nq * bpq), dim3(256), 0, s, ids, dists, counts, ids_stride, dists_stride,
+                           counts_stride, status, status_stride, nparts, k, out_ids, out_dists, out_counts, out_status, bpq);
+    }
+}
 void launch_merge_parts(const uint64_t* ids, const float* dists, const uint32_t* counts, uint32_t nparts,
                         uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_dists, uint32_t* out_counts,
                         hipStream_t s) {
     if (!nq || !k) return;
-    hipLaunchKernelGGL(merge_parts_kernel, dim3(nq), dim3(256), 0, s, ids, dists, counts, (size_t)nq * k, (size_t)nq * k,
-                       (size_t)nq, nullptr, (size_t)0, nparts, nq, k, out_ids, out_dists, out_counts, nullptr);
+    launch_merge(ids, dists, counts, (size_t)nq * k, (size_t)nq * k, (size_t)nq, nullptr, (size_t)0, nparts, nq, k, out_ids,
+                 out_dists, out_counts, nullptr, s);
 }
 // packed layout of one part (int32 words): ids int64[nq*k] | dists f32[nq*k] | counts i32[nq] | status i32 | pad
 void launch_merge_packed(const int32_t* packed, size_t words_per_part, uint32_t nparts, uint32_t nq, uint32_t k,
@@ -1781,11 +2033,10 @@ void launch_merge_packed(const int32_t* packed, size_t words_per_part, uint32_t 
                          hipStream_t s) {
     if (!nq || !k) return;
     const size_t nk = (size_t)nq * k;
-    hipLaunchKernelGGL(merge_parts_kernel, dim3(nq), dim3(256), 0, s, reinterpret_cast<const uint64_t*>(packed),
-                       reinterpret_cast<const float*>(packed + 2 * nk), reinterpret_cast<const uint32_t*>(packed + 3 * nk),
-                       words_per_part / 2, words_per_part, words_per_part,
-                       reinterpret_cast<const uint32_t*>(packed + 3 * nk + nq), words_per_part, nparts, nq, k, out_ids,
-                       out_dists, out_counts, out_status);
+    launch_merge(reinterpret_cast<const uint64_t*>(packed), reinterpret_cast<const float*>(packed + 2 * nk),
+                 reinterpret_cast<const uint32_t*>(packed + 3 * nk), words_per_part / 2, words_per_part, words_per_part,
+                 reinterpret_cast<const uint32_t*>(packed + 3 * nk + nq), words_per_part, nparts, nq, k, out_ids, out_dists,
+                 out_counts, out_status, s);
 }
 
 }  // namespace vdb

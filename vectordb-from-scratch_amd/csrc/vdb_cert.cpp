@@ -56,9 +56,38 @@ MarginPlan margin_plan(const Index* ix) {
 // certified.  The filter threshold is the kt-th smallest of the M = S/64 group minima of an S-row sample (at least
 // kt rows pass it); S = 2^s is sized so that about 2000 keys per query pass, and kt <= M/4 so that the kt smallest
 // minima come from (nearly) distinct groups.
+// Large-k plan (112 < k <= 1024): the pool is sized for the re-rank's depth, not the sample.  The filter pass
+// should let about P = 3 (k + 192) keys per query through -- the first re-rank round (k + k/8) and two more of the same size,
+// with room to spare -- and the threshold is the kt-th smallest of the M = S/64 group minima.  A group minimum lies above
+// the threshold with probability (1 - p)^64 when a fraction p of the rows lies below it, so the rank that lets p = P / n
+// through is  kt = M (1 - (1 - P/n)^64)  (for small p: kt ~ P S / n, the small-k rule).  The tier requires P / n <= 1/80:
+// kt stays below 0.553 M (the threshold is at most the 55th percentile of the group minima) and at most 1.25 % of the
+// (row, query) pairs take the filter's append path.  That is the row floor n >= 240 (k + 192):
+// 73 200 rows at k = 113, 118 080 at k = 300, 291 840 at k = 1024.
+uint64_t large_k_min_rows(size_t k) { return 240ull * ((uint64_t)k + 192u); }
+
+static Bf16Plan plan_large_k(const vdb_flat_index* ix, uint32_t n, size_t k) {
+    Bf16Plan pl;
+    if (!ix->large_k || k > LARGE_K_MAX || (uint64_t)n < large_k_min_rows(k) || n < BF16_MIN_ROWS) return pl;
+    uint64_t S = std::min<uint64_t>(65536u, std::max<uint64_t>(16384u, pow2_ceil((uint64_t)n / 16u)));
+    if (ix->kn.sample16) S = pow2_ceil(std::max(256u, ix->kn.sample16));
+    while (S > n) S /= 2;
+    const double M = (double)vdb::fused_bf16_sample_groups((uint32_t)S);
+    const double P = 3.0 * ((double)k + 192.0);
+    const double frac = 1.0 - std::pow(1.0 - std::min(1.0, P / (double)n), 64.0);
+    uint32_t kt = round_up((uint32_t)std::ceil(M * frac), 8u);
+    kt = std::min<uint32_t>(std::max<uint32_t>(kt, 16u), (uint32_t)M);
+    if (ix->kn.kt16) kt = std::min<uint32_t>(ix->kn.kt16, (uint32_t)M);
+    pl.kp = std::min<uint32_t>(2048u, round_up((uint32_t)std::ceil(P), 256u));   // candidates the select delivers
+    pl.S = (uint32_t)S; pl.kt = kt; pl.large = 1;
+    while ((1ull << pl.shift) < S) ++pl.shift;
+    return pl;
+}
+
 Bf16Plan plan_bf16(const vdb_flat_index* ix, uint32_t n, size_t k) {
     Bf16Plan pl;
-    if (n < BF16_MIN_ROWS || k > 112) return pl;
+    if (k > BF16_MAX_K) return plan_large_k(ix, n, k);
+    if (n < BF16_MIN_ROWS) return pl;
     // threshold rank: at least kt rows pass the filter, about kt * n / S are expected to (k = 10 at 1M rows: 16 -> ~244 keys per
     // query).  The re-rank certifies against the score of the first candidate it did NOT re-rank, so what the rank has to
     // provide is a pool a few times deeper than the first round (k + 38), not a margin: 16 instead of 32 halves the appends

@@ -562,13 +562,20 @@ int vdb_flat_search(vdb_flat_index* ix, const float* query, size_t dim, size_t k
     });
 }
 
+// the merge kernels index keys with 32 bits and launch up to nq * nparts*k / 256 workgroups
+static bool merge_fits(size_t nparts, size_t nq, size_t k) {
+    if (nparts && k > 0xffffffffull / nparts) return false;
+    const unsigned long long bpq = (nparts * k + 255) / 256;
+    return nq <= 0x7fffffffull && (!bpq || nq <= 0x7fffffffull / bpq);
+}
+
 int vdb_merge_topk_device(int device, const uint64_t* d_part_ids, const float* d_part_dists,
                           const uint32_t* d_part_counts, size_t nparts, size_t nq, size_t k, uint64_t* d_out_ids,
                           float* d_out_dists, uint32_t* d_out_counts, void* stream) {
     return guarded([&]() -> int {
     if (!d_part_ids || !d_part_dists || !d_part_counts || !d_out_ids || !d_out_dists || !d_out_counts)
         return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
-    if (nparts * k > 2048) return fail(VDB_ERR_INVALID_ARGUMENT, "nparts*k = %zu exceeds 2048", nparts * k);
+    if (!merge_fits(nparts, nq, k)) return fail(VDB_ERR_INVALID_ARGUMENT, "nq = %zu queries of nparts*k = %zu keys: too large", nq, nparts * k);
     HIP_TRY(hipSetDevice(device));
     vdb::launch_merge_parts(d_part_ids, d_part_dists, d_part_counts, (uint32_t)nparts, (uint32_t)nq, (uint32_t)k,
                             d_out_ids, d_out_dists, d_out_counts, (hipStream_t)stream);
@@ -641,7 +648,7 @@ int vdb_merge_topk_packed_device(int device, const int32_t* d_packed, size_t npa
     return guarded([&]() -> int {
     if (!d_packed || !d_out_ids || !d_out_dists || !d_out_counts)
         return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
-    if (nparts * k > 2048) return fail(VDB_ERR_INVALID_ARGUMENT, "nparts*k = %zu exceeds 2048", nparts * k);
+    if (!merge_fits(nparts, nq, k)) return fail(VDB_ERR_INVALID_ARGUMENT, "nq = %zu queries of nparts*k = %zu keys: too large", nq, nparts * k);
     if ((words_per_part & 1) || words_per_part < nq * (3 * k + 1) + 1)
         return fail(VDB_ERR_INVALID_ARGUMENT, "words_per_part must be even and >= nq*(3k+1)+1");
     HIP_TRY(hipSetDevice(device));
@@ -939,6 +946,19 @@ int vdb_flat_set_wide(vdb_flat_index* ix, int on) {
     ix->wide = on != 0;
     return VDB_OK;
     });
+}
+
+int vdb_flat_set_large_k(vdb_flat_index* ix, int on) {
+    return guarded([&]() -> int {
+    if (!ix || on < 0 || on > 1) return fail(VDB_ERR_INVALID_ARGUMENT, "on must be 0 or 1");
+    if (ix->multi) return multi_for_each(ix, [on](vdb_flat_index* c) { return vdb_flat_set_large_k(c, on); });
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->large_k = on != 0;
+    return VDB_OK;
+    });
+}
+size_t vdb_flat_large_k_min_rows(size_t k) {
+    return (k <= BF16_MAX_K || k > LARGE_K_MAX) ? 0 : (size_t)std::max<uint64_t>(large_k_min_rows(k), BF16_MIN_ROWS);
 }
 
 int vdb_flat_create_sharded(int metric, const int* devices, size_t n_devices, vdb_flat_index** out) {

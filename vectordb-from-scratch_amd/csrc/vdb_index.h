@@ -194,6 +194,7 @@ struct vdb_flat_index {
     hipEvent_t ev_order = nullptr;                          // orders the handle's stream before the null stream (search_batch_device_begin)
     int screen = 1;                                         // 1: bf16 screening tier first (default), 0: f32 MFMA tier only
     bool wide = true;                                       // batches above 256 queries: the 512-query filter kernel (vdb_flat_set_wide)
+    bool large_k = true;                                    // 112 < k <= 1024 on the screening tier (vdb_flat_set_large_k)
     uint64_t stats[16] = {0};                               // counters of the last COMPLETED search (copied from its context)
     bool profile = false; hipEvent_t ev0 = nullptr, ev1 = nullptr;
 
@@ -227,8 +228,10 @@ float c_acc_bf16(const Index* ix);
 struct MarginPlan { float m_e = 0, m_n = 0, m_b = 0, kappa = 0, beta_shrink = 0; };
 MarginPlan margin_plan(const Index* ix);
 constexpr uint32_t BF16_MIN_ROWS = 65536;
-struct Bf16Plan { uint32_t kp = 0, S = 0, shift = 0, kt = 0; };
+struct Bf16Plan { uint32_t kp = 0, S = 0, shift = 0, kt = 0, large = 0; };
+constexpr uint32_t BF16_MAX_K = 112, LARGE_K_MAX = 1024;   // k ranges of the screening tier's two re-ranks
 Bf16Plan plan_bf16(const Index* ix, uint32_t n, size_t k);
+uint64_t large_k_min_rows(size_t k);
 uint32_t pick_kp(size_t k);
 
 // ---- vdb_search.cpp: the tier scheduler

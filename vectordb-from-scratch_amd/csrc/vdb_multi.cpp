@@ -469,7 +469,6 @@ int search_locked(vdb_flat_index* P, const float* d_q, size_t nq, size_t dim, si
         HIP_TRY(hipStreamSynchronize(s0));
         return done(VDB_OK);
     }
-    if ((size_t)M->G * k > 2048) return done(fail(VDB_ERR_INVALID_ARGUMENT, "shards * k = %zu exceeds the merge capacity of 2048", (size_t)M->G * k));
     if (nq > 0x3fffffffull) return done(fail(VDB_ERR_INVALID_ARGUMENT, "batch too large"));
     if (M->exchange == VDB_EXCHANGE_RCCL) { int rc = ensure_comms(M); if (rc) return done(rc); M->stats[3] = (uint64_t)M->comm_world; }
     const size_t nk = nq * k;

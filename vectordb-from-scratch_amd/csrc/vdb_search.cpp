@@ -348,7 +348,12 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
                 if ((rc = W->w_depth.ensure(SUPER * 17))) return rc;      // depth[q], then 8 x 64-bit phase stamps per query
                 rp.depth = W->w_depth.p;
             }
-            vdb::launch_rerank(rp, nb, s);
+            if (pl.large) {
+                // 112 < k <= 1024: the large-k re-rank (first round k + k/8, at least k + 38; then as deep as the certificate asks)
+                rp.kp_first = round_up((uint32_t)k + std::max<uint32_t>(38u, (uint32_t)k / 8u), 16u); rp.kp_step = 64;
+                if (ix->kn.kp_first) rp.kp_first = ix->kn.kp_first;
+                vdb::launch_rerank_large(rp, nb, s);
+            } else vdb::launch_rerank(rp, nb, s);
             if (dump_depth) {
                 std::vector<uint32_t> dep((size_t)SUPER * 17);
                 HIP_TRY(hipMemcpyAsync(dep.data(), W->w_depth.p, dep.size() * 4, hipMemcpyDeviceToHost, s));
@@ -720,7 +725,8 @@ int search_part2(Index* ix, int* changed) {
         todo.push_back(q);
     }
     if (changed && !todo.empty()) *changed = 1;
-    if (kp16 && !todo.empty() && !no_rethr && !force_exact && !force_f32) {
+    // (the re-threshold pass re-ranks with rerank_all_kernel, k <= 112: an uncertified large-k query goes on to the exact scan)
+    if (kp16 && !todo.empty() && !no_rethr && !force_exact && !force_f32 && k <= BF16_MAX_K) {
         // ---- tier 0b: queries with a known score cut get one more HBM-bound pass with that cut as the threshold
         const uint32_t* h_ovf = ix->cur->h_flags + 4 + nq32;
         const float* h_cut = reinterpret_cast<const float*>(ix->cur->h_flags + 4 + 2 * (size_t)nq32);
@@ -760,7 +766,7 @@ int search_part2(Index* ix, int* changed) {
         vdb::launch_gather_queries(ix->cur->w_qp.p, ix->cur->w_qnorm.p, ld, ix->cur->w2_qidx.p, nf, nfp, ix->cur->w2_qp.p, ix->cur->w2_qnorm.p,
                                    ix->cur->w2_thr.p, s);
         if (kp == 0) {
-            // k too large for the f32 tier as well: straight to the exact scan (flags stay 0 = uncertified)
+            // k too large for the f32 tier (the large-k screening tier's uncertified queries): straight to the exact scan (flags stay 0)
         } else {
             if ((rc = pass_f32(ix, s, ix->cur->w2_qp.p, ix->cur->w2_qnorm.p, ix->cur->w2_thr.p, nf, k, kp, d_rowmask, ix->cur->w2_outi.p,
                                ix->cur->w2_outd.p, ix->cur->w2_outc.p, ix->cur->w2_flags.p, ix->cur->w2_flags.p + nf, d_status)))

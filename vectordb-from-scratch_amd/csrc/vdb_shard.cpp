@@ -262,7 +262,6 @@ int vdb_flat_search_batch_sharded(vdb_shard_group* g, vdb_flat_index* local, con
     // ---- argument checks that are identical on every rank come BEFORE any collective; nothing rank-LOCAL may return
     // between here and the last exchange (a rank that left early would leave the others blocked in ncclAllGather)
     if (nq == 0) return done(VDB_OK);
-    if ((size_t)g->world * k > 2048) return done(err(VDB_ERR_INVALID_ARGUMENT, "world * k exceeds the merge capacity of 2048"));
     if (nq > 0x3fffffffull) return done(err(VDB_ERR_INVALID_ARGUMENT, "batch too large"));
     if (g->poisoned) return done(err(VDB_ERR_DEVICE, "an earlier device failure left this rank out of step with its group: destroy the group"));
     int local_rc = VDB_OK;                                           // this rank's own failure, kept until the exchanges are over

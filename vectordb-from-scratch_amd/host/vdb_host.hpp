@@ -136,6 +136,7 @@ public:
     vdb_flat_index* handle() const { return h_; }
     // no reference counterpart: tier selection (results are identical either way)
     void set_screen(int mode) { check(vdb_flat_set_screen(h_, mode)); }
+    void set_large_k(int on) { check(vdb_flat_set_large_k(h_, on)); }
     void set_tiers(unsigned flags) { check(vdb_flat_set_tiers(h_, flags)); }
 
 private:

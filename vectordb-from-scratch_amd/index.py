@@ -301,6 +301,12 @@ class GpuFlatIndex(Index):
         if rc:
             _raise(rc)
 
+    def set_large_k(self, on=True):
+        """112 < k <= 1024 on the screening tier (default) or on the exact scan.  Results are identical."""
+        rc = self._L.vdb_flat_set_large_k(self._h, 1 if on else 0)
+        if rc:
+            _raise(rc)
+
     TIERS_NO_RETHRESHOLD, TIERS_FORCE_F32, TIERS_FORCE_EXACT, TIERS_NO_DIRECT = 1, 2, 4, 8
 
     def set_shadow(self, on=True):
