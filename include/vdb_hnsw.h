@@ -59,6 +59,18 @@ int vdb_hnsw_remove(vdb_hnsw_index *h, uint64_t id);
 int vdb_hnsw_search_batch(vdb_hnsw_index *h, const float *queries, size_t nq, size_t dim, size_t k, size_t ef,
                           uint64_t *out_ids, float *out_dists, size_t *out_counts);
 
+/* Pre-filtered search_knn: vdb_hnsw_search_batch with an id mask of the layout of vdb_flat_search_batch -- bit i (LSB-first in
+ * 64-bit words) set = id i eligible; ids >= mask_bits are not; id_mask is a host pointer, NULL = no filter (exactly
+ * vdb_hnsw_search_batch).  The greedy descent above layer 0 is unchanged; at layer 0 every visited node enters the candidate heap
+ * under the reference's rule (graph.rs:143-199) but only eligible ones enter the results, whose furthest element bounds the walk
+ * (hnswlib's filter rule: ineligible nodes are expanded like any other, the graph stays navigable).  out_counts[b] =
+ * min(k, eligible nodes found), every returned id eligible.  With every present id eligible the results are those of the
+ * unfiltered call, bit for bit.  When no present id is eligible nothing is walked and every count is 0; the dimension check and
+ * a zero-norm query under Cosine still fail as in the unfiltered call. */
+int vdb_hnsw_search_batch_masked(vdb_hnsw_index *h, const float *queries, size_t nq, size_t dim, size_t k, size_t ef,
+                                 const uint64_t *id_mask, size_t mask_bits, uint64_t *out_ids, float *out_dists,
+                                 size_t *out_counts);
+
 /* Test hook (results are identical either way): host_only = 1 sends every search through the host traversal instead of
  * the device-resident walk; host_threads > 0 fixes its worker-thread count (0 = automatic).  Not read from the environment. */
 int vdb_hnsw_set_traversal(vdb_hnsw_index *h, int host_only, size_t host_threads);

@@ -1,0 +1,233 @@
+"""Pre-filtered HNSW search (include/vdb_hnsw.h vdb_hnsw_search_batch_masked): the device-resident walk, the host traversal and
+the Python restatement of the filtered search_knn (tests/hnsw_filter_restatement.py, on the CPU restatement's graph) agree on
+ids, order and distance bits; an all-ones mask is the unfiltered search; recall against the exact filtered flat answer; the
+store, the server's "prefilter" extension and the C++ mirror on an HNSW index."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import oracle
+from conftest import ROOT, load_package
+from hnsw_filter_restatement import Walker, eligible_fn, mask_of
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def vdb():
+    v = load_package()
+    v.build()
+    return v
+
+
+def build_pair(vdb, metric, rows, m, efc, seed):
+    n = rows.shape[0]
+    g = vdb.GpuHnswIndex(vdb.DistanceMetric(metric), vdb.HnswParams.new(m, efc, 50), seed=seed)
+    g.build_batch((np.arange(n, dtype=np.uint64), rows))
+    o = oracle.HnswOracle(metric, m=m, ef_construction=efc, ef_search=50, seed=seed)
+    for i in range(n):
+        o.insert(i, rows[i])
+    return g, o
+
+
+def same(a, b):
+    (ai, ad, ac), (bi, bd, bc) = a, b
+    if not np.array_equal(ac, bc):
+        return False
+    return all(np.array_equal(ai[q, :ac[q]], bi[q, :bc[q]]) and
+               np.array_equal(ad[q, :ac[q]].view(np.uint32), bd[q, :bc[q]].view(np.uint32)) for q in range(ac.size))
+
+
+@pytest.mark.parametrize("metric", [0, 1, 2])
+@pytest.mark.parametrize("n,d,m,efc,ef", [(300, 8, 4, 32, 32), (1500, 48, 16, 200, 200)])
+def test_device_host_and_restatement_agree(vdb, metric, n, d, m, efc, ef):
+    rng = np.random.default_rng(100 + n + metric)
+    rows = rng.standard_normal((n, d)).astype(np.float32)             # Gaussian: no distance ties (the restatement uses heapq)
+    qs = rng.standard_normal((8, d)).astype(np.float32)
+    k = 10
+    g, o = build_pair(vdb, metric, rows, m, efc, seed=5)
+    w = Walker(o, metric, {i: rows[i] for i in range(n)})
+    for sel in (0.5, 0.1, 0.01):
+        elig = rng.random(n) < sel
+        mask, bits = mask_of(elig)
+        before = g.stats()
+        dev = g.search_batch_arrays(qs, k, ef, id_mask=mask, mask_bits=bits)
+        after = g.stats()
+        assert after["device_queries"] - before["device_queries"] + after["host_redone"] - before["host_redone"] == len(qs)
+        if sel >= 0.1:
+            assert after["host_redone"] == before["host_redone"], (sel, after)
+        g.set_traversal(True)
+        host = g.search_batch_arrays(qs, k, ef, id_mask=mask, mask_bits=bits)
+        g.set_traversal(False)
+        assert same(dev, host), sel
+        di, dd, dc = dev
+        for b in range(len(qs)):
+            wi, wd = w.search(qs[b], k, ef, eligible_fn(elig))
+            assert dc[b] == wi.size, (sel, b, dc[b], wi.size)
+            assert np.array_equal(di[b, :dc[b]], wi), (sel, b)
+            assert np.array_equal(dd[b, :dc[b]].view(np.uint32), wd.view(np.uint32)), (sel, b)
+            assert all(elig[int(i)] for i in di[b, :dc[b]])
+
+
+@pytest.fixture(scope="module")
+def small(vdb):
+    rng = np.random.default_rng(3)
+    n, d = 400, 16
+    rows = rng.standard_normal((n, d)).astype(np.float32)
+    g = vdb.GpuHnswIndex(vdb.DistanceMetric.Euclidean, vdb.HnswParams.new(8, 64, 50), seed=9)
+    g.build_batch((np.arange(n, dtype=np.uint64), rows))
+    return g, rows, rng.standard_normal((6, d)).astype(np.float32)
+
+
+def test_all_ones_mask_is_the_unfiltered_search(vdb, small):
+    g, rows, qs = small
+    n = rows.shape[0]
+    plain = g.search_batch_arrays(qs, 10, 60)
+    for bits in (n, n + 100):                                         # bits beyond the last id name nothing
+        mask, _ = mask_of(np.ones(bits, dtype=bool))
+        assert same(g.search_batch_arrays(qs, 10, 60, id_mask=mask, mask_bits=bits), plain)
+    g.set_traversal(True)
+    mask, _ = mask_of(np.ones(n, dtype=bool))
+    assert same(g.search_batch_arrays(qs, 10, 60, id_mask=mask, mask_bits=n), plain)
+    g.set_traversal(False)
+
+
+def test_empty_and_out_of_range_masks_return_nothing(vdb, small):
+    g, rows, qs = small
+    n = rows.shape[0]
+    out_of_range = np.zeros(n + 200, dtype=bool)
+    out_of_range[n:] = True
+    for elig in (np.zeros(n, dtype=bool), out_of_range):
+        mask, bits = mask_of(elig)
+        for host in (False, True):
+            g.set_traversal(host)
+            _, _, c = g.search_batch_arrays(qs, 10, 60, id_mask=mask, mask_bits=bits)
+            assert np.all(c == 0)
+    g.set_traversal(False)
+    mask, _ = mask_of(np.ones(n, dtype=bool))                         # mask_bits = 0: every id is beyond it
+    _, _, c = g.search_batch_arrays(qs, 10, 60, id_mask=mask, mask_bits=0)
+    assert np.all(c == 0)
+
+
+def test_removed_ids_are_never_returned(vdb):
+    rng = np.random.default_rng(4)
+    n, d = 300, 8
+    rows = rng.standard_normal((n, d)).astype(np.float32)
+    g = vdb.GpuHnswIndex(vdb.DistanceMetric.Euclidean, vdb.HnswParams.new(4, 32, 50), seed=2)
+    g.build_batch((np.arange(n, dtype=np.uint64), rows))
+    gone = np.arange(0, n, 3)
+    for i in gone:
+        g.remove(int(i))
+    qs = rng.standard_normal((5, d)).astype(np.float32)
+    only_gone = np.zeros(n, dtype=bool)
+    only_gone[gone] = True
+    mask, bits = mask_of(only_gone)
+    _, _, c = g.search_batch_arrays(qs, 5, 40, id_mask=mask, mask_bits=bits)
+    assert np.all(c == 0)
+    half = rng.random(n) < 0.5
+    mask, bits = mask_of(half)
+    dev = g.search_batch_arrays(qs, 5, 40, id_mask=mask, mask_bits=bits)
+    g.set_traversal(True)
+    host = g.search_batch_arrays(qs, 5, 40, id_mask=mask, mask_bits=bits)
+    g.set_traversal(False)
+    assert same(dev, host)
+    ids = dev[0]
+    for b in range(len(qs)):
+        for i in ids[b, :dev[2][b]]:
+            assert half[int(i)] and int(i) % 3 != 0
+
+
+def test_errors_match_the_unfiltered_call(vdb):
+    V = vdb.Vector
+    ix = vdb.GpuHnswIndex(vdb.DistanceMetric.Cosine, vdb.HnswParams.new(4, 32, 16))
+    ix.add(0, V([1.0, 0.0])); ix.add(1, V([0.0, 1.0]))
+    some, bits = mask_of(np.array([False, True]))
+    none, _ = mask_of(np.array([False, False]))
+    for mask in (some, none):                                          # the walk, and the empty mask that skips it
+        with pytest.raises(vdb.InvalidVector):
+            ix.search_batch_arrays(np.zeros((1, 2), np.float32), 1, 16, id_mask=mask, mask_bits=bits)
+        with pytest.raises(vdb.DimensionMismatch):
+            ix.search_batch_arrays(np.ones((1, 3), np.float32), 1, 16, id_mask=mask, mask_bits=bits)
+    i, _, c = ix.search_batch_arrays(np.array([[1.0, 0.1]], np.float32), 2, 16, id_mask=some, mask_bits=bits)
+    assert c[0] == 1 and i[0, 0] == 1
+
+
+@pytest.fixture(scope="module")
+def recall_shape(vdb):
+    # the reference's recall shape (tests/recall_test.rs:78-80): 5000 x 128 uniform, m = 16, ef_construction = 200
+    rng = np.random.default_rng(5000)
+    n, d, nq = 5000, 128, 64
+    rows = rng.random((n, d), dtype=np.float32)
+    qs = rng.random((nq, d), dtype=np.float32)
+    g = vdb.GpuHnswIndex(vdb.DistanceMetric.Euclidean, vdb.HnswParams.new(16, 200, 50), seed=n)
+    g.build_batch((np.arange(n, dtype=np.uint64), rows))
+    flat = vdb.GpuFlatIndex(vdb.DistanceMetric.Euclidean, keep_host_copy=False)
+    flat.add_bulk(rows)
+    return g, flat, rows, qs, rng
+
+
+@pytest.mark.parametrize("sel", [0.5, 0.1])
+def test_filtered_recall_at_the_reference_shape(vdb, recall_shape, sel):
+    g, flat, rows, qs, rng = recall_shape
+    n, k = rows.shape[0], 10
+    elig = rng.random(n) < sel
+    mask, bits = mask_of(elig)
+    before = g.stats()["host_redone"]
+    hi, hd, hc = g.search_batch_arrays(qs, k, 200, id_mask=mask, mask_bits=bits)
+    assert g.stats()["host_redone"] == before
+    ti, _, tc = flat.search_batch_arrays(qs, k, id_mask=mask, mask_bits=bits)       # the exact filtered answer
+    assert np.all(tc == k) and np.all(hc == k)
+    assert all(elig[int(i)] for i in hi.ravel())
+    assert np.all(hd[:, 1:] >= hd[:, :-1])
+    rec = np.mean([len(set(ti[b].tolist()) & set(hi[b].tolist())) / k for b in range(len(qs))])
+    # the reference's post-filter on the same queries (storage.rs:249-290): 3k results at ef = 50, the eligible ones kept
+    pi, _, pc = g.search_batch_arrays(qs, 3 * k, 50)
+    post = [[int(i) for i in pi[b, :pc[b]] if elig[int(i)]][:k] for b in range(len(qs))]
+    rec_post = np.mean([len(set(ti[b].tolist()) & set(post[b])) / k for b in range(len(qs))])
+    print(f"selectivity {sel}: pre-filtered recall@10 {rec:.4f}, post-filter recall@10 {rec_post:.4f}, "
+          f"post-filter mean count {np.mean([len(p) for p in post]):.2f}")
+    assert rec >= 0.85, rec
+    assert rec >= rec_post, (rec, rec_post)
+
+
+def test_store_and_server_prefilter_on_an_hnsw_index(vdb):
+    rng = np.random.default_rng(12)
+    n, d, k = 2000, 24, 10
+    rows = rng.standard_normal((n, d)).astype(np.float32)
+    qs = rng.standard_normal((4, d)).astype(np.float32)
+    ix = vdb.GpuHnswIndex(vdb.DistanceMetric.Euclidean, vdb.HnswParams.new(8, 64, 50), seed=1)
+    ix.build_batch((np.arange(n, dtype=np.uint64), rows))
+    store = vdb.VectorStore.with_index(ix)
+    buckets = np.array(["a", "b", "c", "d", "e"], dtype=object)[rng.integers(0, 5, n)]
+    store.attach_bulk_metadata(n, {"bucket": buckets})
+    flt = vdb.MetadataFilter.Eq("bucket", "c")
+    mask, bits = store.compile_filter(flt)
+    mi, md, mc = ix.search_batch_arrays(qs, k, 50, id_mask=mask, mask_bits=bits)
+    res = store.search_batch_prefiltered([(vdb.Vector(q), k) for q in qs], flt)
+    for b in range(len(qs)):
+        assert [int(r.id) for r in res[b]] == [int(i) for i in mi[b, :mc[b]]]
+        assert all(buckets[int(r.id)] == "c" for r in res[b]) and len(res[b]) == k
+        assert np.array_equal(np.array([r.distance for r in res[b]], np.float32).view(np.uint32), md[b, :mc[b]].view(np.uint32))
+    from starlette.testclient import TestClient
+    from vectordb_from_scratch_amd.server import AppState, create_app
+    client = TestClient(create_app(AppState(store)))
+    body = client.post("/search/batch", json={"queries": [{"vector": q.tolist(), "k": k} for q in qs],
+                                              "filter": {"op": "eq", "field": "bucket", "value": "c"}, "prefilter": True})
+    assert body.status_code == 200
+    for b, hits in enumerate(body.json()):
+        assert [int(x["id"]) for x in hits] == [int(i) for i in mi[b, :mc[b]]]
+
+
+def test_cpp_mirror_search_batch_masked(vdb):
+    lib = vdb.build()
+    libdir = os.path.dirname(lib)
+    src = os.path.join(ROOT, "tests", "cpp", "hnsw_filter_test.cpp")
+    exe = os.path.join(ROOT, "tests", "cpp", "hnsw_filter_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "include"),
+                           "-I", os.path.join(ROOT, "vectordb-from-scratch_amd", "host"), src, "-o", exe,
+                           "-L", libdir, "-lvdbflat", f"-Wl,-rpath,{libdir}", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr + out.stdout
+    assert "hnsw filter ok" in out.stdout

@@ -74,6 +74,29 @@ def main():
             for b in range(nq):
                 oi, od = o.search(q[b], k, ef)
                 ok &= bool(gc[b] == len(oi) and np.array_equal(gi[b, :gc[b]], oi) and np.array_equal(gd[b, :gc[b]].view(np.uint32), od.view(np.uint32)))
+        # pre-filtered search with a random id mask: the device walk equals the host traversal, results are eligible; an
+        # all-ones mask is the unfiltered search
+        bits = int(n * 2 + rng.integers(0, 100))
+        sel = float(rng.choice([1.0, 0.5, 0.1, 0.02, 0.0]))
+        elig = rng.random(bits) < sel
+        packed = np.zeros(((bits + 63) // 64) * 8, dtype=np.uint8)
+        pb = np.packbits(elig, bitorder="little")
+        packed[:pb.size] = pb
+        mask = packed.view(np.uint64)
+        k, ef = int(rng.integers(1, 30)), int(rng.choice([10, 50, 200]))
+        dev = g.search_batch_arrays(q, k, ef, id_mask=mask, mask_bits=bits)
+        g.set_traversal(True)
+        host = g.search_batch_arrays(q, k, ef, id_mask=mask, mask_bits=bits)
+        g.set_traversal(False)
+        for b in range(nq):
+            c = int(dev[2][b])
+            ok &= bool(c == host[2][b] and np.array_equal(dev[0][b, :c], host[0][b, :c]) and
+                       np.array_equal(dev[1][b, :c].view(np.uint32), host[1][b, :c].view(np.uint32)))
+            ok &= all(bool(elig[int(i)]) for i in dev[0][b, :c])
+        if sel == 1.0:
+            plain = g.search_batch_arrays(q, k, ef)
+            ok &= bool(np.array_equal(plain[2], dev[2]) and all(np.array_equal(plain[0][b, :plain[2][b]], dev[0][b, :dev[2][b]]) for b in range(nq)))
+        desc += f" mask sel={sel}"
         st = g.stats()
         dev_q += st["device_queries"]; host_q += st["host_redone"]
         print(("ok   " if ok else "FAIL ") + desc + f"  [device walks {st['device_queries']} host re-runs {st['host_redone']} host rounds {st['last_search_rounds']}]", flush=True)

@@ -18,7 +18,7 @@ SYMBOLS = [
     "vdb_flat_search_batch_device", "vdb_flat_search_batch_device_begin", "vdb_flat_search_batch_device_finish", "vdb_flat_search_batch_device_submit", "vdb_flat_search_batch_device_wait", "vdb_flat_distances_batch", "vdb_merge_topk_device", "vdb_merge_topk_packed_device", "vdb_flat_set_profile", "vdb_flat_last_stats", "vdb_flat_last_stats_ex", "vdb_flat_set_screen", "vdb_flat_set_wide", "vdb_flat_set_large_k", "vdb_flat_large_k_min_rows", "vdb_flat_set_shadow", "vdb_flat_set_sample_cache", "vdb_flat_set_tiers", "vdb_flat_debug_screen_scores", "vdb_flat_debug_rows", "vdb_flat_debug_row_info", "vdb_flat_debug_last_thresholds", "vdb_flat_debug_cert_probe", "vdb_last_error",
     "vdb_abi_version", "vdb_build_arch",
     # include/vdb_hnsw.h
-    "vdb_hnsw_create", "vdb_hnsw_destroy", "vdb_hnsw_add", "vdb_hnsw_add_bulk", "vdb_hnsw_remove", "vdb_hnsw_search_batch",
+    "vdb_hnsw_create", "vdb_hnsw_destroy", "vdb_hnsw_add", "vdb_hnsw_add_bulk", "vdb_hnsw_remove", "vdb_hnsw_search_batch", "vdb_hnsw_search_batch_masked",
     "vdb_hnsw_len", "vdb_hnsw_metric", "vdb_hnsw_get_vector", "vdb_hnsw_neighbors", "vdb_hnsw_node_level",
     "vdb_hnsw_entry_point", "vdb_hnsw_stats", "vdb_hnsw_set_traversal", "vdb_hnsw_set_build", "vdb_hnsw_build_stats", "vdb_hnsw_build_times",
     # include/vdb_shard.h
@@ -125,6 +125,7 @@ def lib():
     L.vdb_hnsw_add_bulk.argtypes = [vp, u64p, u64, fp, sz, sz]
     L.vdb_hnsw_remove.argtypes = [vp, u64]
     L.vdb_hnsw_search_batch.argtypes = [vp, fp, sz, sz, sz, sz, u64p, fp, szp]
+    L.vdb_hnsw_search_batch_masked.argtypes = [vp, fp, sz, sz, sz, sz, u64p, sz, u64p, fp, szp]
     L.vdb_hnsw_len.argtypes = [vp]
     L.vdb_hnsw_len.restype = sz
     L.vdb_hnsw_metric.argtypes = [vp]

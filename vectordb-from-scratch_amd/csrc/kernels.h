@@ -406,8 +406,17 @@ struct HnswSearchParams {
     const uint32_t* qrow; const uint32_t* qlevel;
     uint32_t* rec_row; float* rec_d; uint32_t* rec_cnt; uint32_t rec_cap; uint32_t rec_zero_mark;
     uint32_t chunk, stage_rows;                                          // set by launch_hnsw_search: staging chunk (elements), rows per staging buffer
+    // PRE-FILTERED search (id_mask != null; searches only): bit i of id_mask (LSB-first in 64-bit words) marks node id i eligible,
+    // ids >= mask_bits (<= n_ids) are not.  Layer 0 then admits every accepted neighbour to the candidate heap but only eligible
+    // ones to the results, and its visited set is a bitmap in HBM: vis_bits[q * vis_words ..], n_ids bits per query, zeroed by
+    // launch_hnsw_search.
+    const uint64_t* id_mask; uint32_t mask_bits;
+    uint32_t* vis_bits; uint32_t vis_words;
 };
 void launch_hnsw_search(const HnswSearchParams& p, uint32_t nq, hipStream_t s);
+// queries of one filtered launch: the HBM visited bitmaps of a launch stay within hnsw_filter_vis_bytes()
+uint32_t hnsw_filter_launch_queries(uint32_t n_ids);
+size_t hnsw_filter_vis_bytes(uint32_t n_ids, uint32_t nq);
 // incremental update of the graph mirror: n0 layer-0 records [id, row, level, up_off, ids[stride0], rows[stride0]] and nU
 // upper-list records [list index, ids[strideU], rows[strideU]] (uint32 words), scattered into the mirror arrays
 struct HnswScatterParams {

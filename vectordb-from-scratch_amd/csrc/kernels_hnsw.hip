@@ -23,6 +23,13 @@ constexpr uint32_t HT = 256;                  // threads per workgroup
 constexpr uint32_t CAND_CAP = 4096;
 constexpr uint32_t RES_CAP = 1024;            // ef + 1 <= RES_CAP
 constexpr uint32_t VIS_CAP = 16384;           // hash slots; at most 3/4 are used
+// The pre-filtered walk (p.id_mask) visits many more nodes at layer 0: until ef ELIGIBLE nodes are found every visited neighbour
+// enters the candidate heap.  Its layer-0 visited set is a bitmap in HBM (no cap), and the LDS the hash held goes to the heap; the
+// LDS hash stays for the greedy descent above layer 0 (ef = 1, a few hundred nodes), smaller.  Same LDS footprint as the plain walk.
+constexpr uint32_t CAND_CAP_F = 11264;
+constexpr uint32_t VIS_CAP_F = 2048;
+static_assert(CAND_CAP_F * 8 + VIS_CAP_F * 4 == CAND_CAP * 8 + VIS_CAP * 4, "one LDS plan for both walks");
+constexpr size_t FILTER_VIS_BYTES = (size_t)128 << 20;    // HBM visited bitmaps of one filtered launch at most
 // the rows of an expansion are staged in chunks of `chunk` elements (64..256, chosen on the host so that TWO chunk buffers fit
 // the LDS that the walk's own structures leave: hnsw_stage_plan); a staged row takes chunk + 4 floats
 constexpr uint32_t MAXP = 40;                 // neighbours per expansion at most (m_max0 + 1 <= 40, i.e. m <= 19)
@@ -130,15 +137,20 @@ template <int SIGN> __device__ __forceinline__ void wave_pop_discard(HNb* v, uin
 __device__ __forceinline__ uint32_t vis_hash(uint32_t x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; }
 }  // namespace
 
+// FILTERED: the pre-filtered search (p.id_mask set; kernels.h); the plain instantiation is the walk as it was.
+template <bool FILTERED>
 __global__ __launch_bounds__(HT) void hnsw_search_kernel(HnswSearchParams p) {
+    constexpr uint32_t CCAP = FILTERED ? CAND_CAP_F : CAND_CAP;
+    constexpr uint32_t VCAP = FILTERED ? VIS_CAP_F : VIS_CAP;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t ldq = (p.dim + 3) & ~3u;
     float* sQ = reinterpret_cast<float*>(smem);                                   // [ldq]
-    HNb* sCand = reinterpret_cast<HNb*>(sQ + ldq);                                // [CAND_CAP]
-    HNb* sRes = sCand + CAND_CAP;                                                 // [RES_CAP]
-    uint32_t* sVis = reinterpret_cast<uint32_t*>(sRes + RES_CAP);                 // [VIS_CAP]
-    float* sStage = reinterpret_cast<float*>(sVis + VIS_CAP);                     // [2][stage_rows][chunk + 4]
+    HNb* sCand = reinterpret_cast<HNb*>(sQ + ldq);                                // [CCAP]
+    HNb* sRes = sCand + CCAP;                                                     // [RES_CAP]
+    uint32_t* sVis = reinterpret_cast<uint32_t*>(sRes + RES_CAP);                 // [VCAP]
+    float* sStage = reinterpret_cast<float*>(sVis + VCAP);                        // [2][stage_rows][chunk + 4]
     __shared__ uint32_t sPendId[MAXP], sPendRow[MAXP];
+    __shared__ uint32_t sPendOk[FILTERED ? MAXP : 1];                             // FILTERED: the pending neighbour's mask bit
     __shared__ float sPendD[MAXP];
     __shared__ uint32_t sNP, sCont, sCur, sFail, sNVis, sZero, sNCand, sNRes, sRec;
     // the final stable sort's keys (ordered distance, position in the heap's backing array) live in the staging area, which is
@@ -153,6 +165,9 @@ __global__ __launch_bounds__(HT) void hnsw_search_kernel(HnswSearchParams p) {
     if (tid == 0) { sFail = 0; sZero = 0; sRec = 0; }
     const float qn = p.qrow ? p.nd[p.qrow[q]] : p.qnorm[q];
     const uint32_t ins_level = p.qlevel ? p.qlevel[q] : 0xffffffffu;    // 0xffffffff: a search (ef = 1 above layer 0)
+    // FILTERED: a node's mask bit, and this query's layer-0 visited bitmap
+    auto eligible = [&](uint32_t id) -> bool { return id < p.mask_bits && ((p.id_mask[id >> 6] >> (id & 63u)) & 1ull) != 0ull; };
+    uint32_t* const vis_g = FILTERED ? p.vis_bits + (size_t)q * p.vis_words : nullptr;
     __syncthreads();
 
     // distances of sPendRow[0..np) into sPendD, in the reference's operation order.
@@ -285,21 +300,26 @@ __global__ __launch_bounds__(HT) void hnsw_search_kernel(HnswSearchParams p) {
     for (int layer = (int)p.max_level; layer >= 0; --layer) {
         // search: ef = 1 above layer 0 (graph.rs:400-405); insert of a node of level L: ef = 1 above L, ef_construction at and below
         const uint32_t ef = p.qlevel ? ((uint32_t)layer > ins_level ? 1u : ef_final) : (layer >= 1 ? 1u : ef_final);
+        // the greedy descent above layer 0 is not filtered: it only finds the entry point
+        const bool filt = FILTERED && layer == 0;
         // ---- search_layer(query, [ep], ef, layer)   (graph.rs:143-199)
-        for (uint32_t i = tid; i < VIS_CAP; i += HT) sVis[i] = 0xffffffffu;
+        for (uint32_t i = tid; i < VCAP; i += HT) sVis[i] = 0xffffffffu;
         if (tid == 0) {
             sNCand = 0; sNRes = 0; sNVis = 1;
             sPendId[0] = ep; sPendRow[0] = p.row_of[ep];
         }
         __syncthreads();
-        if (tid == 0) sVis[vis_hash(ep) & (VIS_CAP - 1)] = ep;    // visited.insert(ep), after the clear has completed
+        if (tid == 0) {                                             // visited.insert(ep), after the clear has completed
+            if (filt) atomicOr(&vis_g[ep >> 5], 1u << (ep & 31u));
+            else sVis[vis_hash(ep) & (VCAP - 1)] = ep;
+        }
         __syncthreads();
         eval_pending(1);
         if (tid == 0) {
             uint32_t nc = 0, nr = 0;
             HNb x{sPendD[0], ep};
             h_push<-1>(sCand, nc, x);
-            h_push<+1>(sRes, nr, x);
+            if (!filt || eligible(ep)) h_push<+1>(sRes, nr, x);     // FILTERED: only eligible nodes are results
             sNCand = nc; sNRes = nr;
         }
         __syncthreads();
@@ -332,18 +352,27 @@ __global__ __launch_bounds__(HT) void hnsw_search_kernel(HnswSearchParams p) {
                     lst = p.nbrU + (size_t)li * p.strideU; lrow = p.nbrU_row + (size_t)li * p.strideU; stride = p.strideU;
                 }
                 if (stride > MAXP) { stride = MAXP; if (lane == 0) sFail = 1u; }
-                bool keep = false;
+                bool keep = false, ok = true;
                 uint32_t nid = 0xffffffffu, row = 0xffffffffu;
                 if (lane < stride) { nid = lst[lane]; row = lrow[lane]; }
                 if (nid != 0xffffffffu) {
-                    // visited.insert(nid): open addressing, CAS claims a slot; an equal key found = already visited
-                    uint32_t h = vis_hash(nid) & (VIS_CAP - 1);
                     bool fresh = false;
-                    for (uint32_t probe = 0; probe < VIS_CAP; ++probe) {
-                        const uint32_t old = atomicCAS(&sVis[h], 0xffffffffu, nid);
-                        if (old == 0xffffffffu) { fresh = true; break; }
-                        if (old == nid) break;
-                        h = (h + 1) & (VIS_CAP - 1);
+                    if (filt) {
+                        // visited.insert(nid) in the HBM bitmap; the neighbour's mask bit is read in the same pass
+                        if (nid < p.n_ids) {
+                            const uint32_t bit = 1u << (nid & 31u);
+                            fresh = (atomicOr(&vis_g[nid >> 5], bit) & bit) == 0u;
+                            ok = eligible(nid);
+                        } else sFail = 1u;                                   // (the mirror lists only ids below n_ids)
+                    } else {
+                        // visited.insert(nid): open addressing, CAS claims a slot; an equal key found = already visited
+                        uint32_t h = vis_hash(nid) & (VCAP - 1);
+                        for (uint32_t probe = 0; probe < VCAP; ++probe) {
+                            const uint32_t old = atomicCAS(&sVis[h], 0xffffffffu, nid);
+                            if (old == 0xffffffffu) { fresh = true; break; }
+                            if (old == nid) break;
+                            h = (h + 1) & (VCAP - 1);
+                        }
                     }
                     if (fresh) {
                         atomicAdd(&sNVis, 1u);
@@ -352,10 +381,10 @@ __global__ __launch_bounds__(HT) void hnsw_search_kernel(HnswSearchParams p) {
                 }
                 const unsigned long long m = __ballot(keep);
                 const uint32_t pos = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-                if (keep) { sPendId[pos] = nid; sPendRow[pos] = row; }
+                if (keep) { sPendId[pos] = nid; sPendRow[pos] = row; if (FILTERED) sPendOk[pos] = ok ? 1u : 0u; }
                 if (lane == 0) {
                     sNP = (uint32_t)__popcll(m);
-                    if (sNVis > (VIS_CAP / 4) * 3) sFail = 1u;
+                    if (!filt && sNVis > (VCAP / 4) * 3) sFail = 1u;
                 }
             }
             __syncthreads();
@@ -367,19 +396,23 @@ __global__ __launch_bounds__(HT) void hnsw_search_kernel(HnswSearchParams p) {
                 // lane i holds neighbour i (np <= 40): the loop below reads them with v_readlane and keeps the furthest result in a
                 // register -- two dependent LDS reads per neighbour, accepted or not, were half of this phase
                 const uint32_t my_d = lane < np ? __float_as_uint(sPendD[lane]) : 0u, my_id = lane < np ? sPendId[lane] : 0u;
+                const uint32_t my_ok = FILTERED && lane < np ? sPendOk[FILTERED ? lane : 0u] : 1u;
                 float furthest = nr ? __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(sRes[0].d))) : 3.40282347e+38f;
                 for (uint32_t i = 0; i < np; ++i) {
                     const float dd = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)my_d, (int)i));
                     if (dd < furthest || nr < ef) {
-                        if (nc >= CAND_CAP || nr >= RES_CAP) { if (lane == 0) sFail = 1u; break; }
+                        if (nc >= CCAP || nr >= RES_CAP) { if (lane == 0) sFail = 1u; break; }
                         const HNb x{dd, (uint32_t)__builtin_amdgcn_readlane((int)my_id, (int)i)};
                         wave_push<-1>(sCand, nc, x, lane);
-                        wave_push<+1>(sRes, nr, x, lane);
-                        if (nr > ef) {
-                            if (nr <= WAVE_POP_MAX) wave_pop_discard<+1>(sRes, nr, lane);
-                            else { if (lane == 0) (void)h_pop<+1>(sRes, nr); else --nr; }
+                        // FILTERED: every accepted neighbour is a candidate (the graph stays navigable), only eligible ones are results
+                        if (!filt || __builtin_amdgcn_readlane((int)my_ok, (int)i)) {
+                            wave_push<+1>(sRes, nr, x, lane);
+                            if (nr > ef) {
+                                if (nr <= WAVE_POP_MAX) wave_pop_discard<+1>(sRes, nr, lane);
+                                else { if (lane == 0) (void)h_pop<+1>(sRes, nr); else --nr; }
+                            }
+                            furthest = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(sRes[0].d)));
                         }
-                        furthest = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(sRes[0].d)));
                     }
                 }
                 if (lane == 0) { sNCand = nc; sNRes = nr; }
@@ -472,6 +505,11 @@ void launch_hnsw_scatter(const HnswScatterParams& p, hipStream_t s) {
     if (!(p.n0 + p.nU)) return;
     hipLaunchKernelGGL(hnsw_scatter_kernel, dim3(p.n0 + p.nU), dim3(64), 0, s, p);
 }
+uint32_t hnsw_filter_launch_queries(uint32_t n_ids) {
+    const size_t per_q = (size_t)((n_ids + 31u) / 32u) * 4u;
+    return (uint32_t)std::max<size_t>(1, std::min<size_t>(FILTER_VIS_BYTES / std::max<size_t>(per_q, 4), 0x7fffffffu));
+}
+size_t hnsw_filter_vis_bytes(uint32_t n_ids, uint32_t nq) { return (size_t)((n_ids + 31u) / 32u) * 4u * nq; }
 void launch_hnsw_search(const HnswSearchParams& p_in, uint32_t nq, hipStream_t s) {
     if (!nq) return;
     HnswSearchParams p = p_in;
@@ -480,7 +518,14 @@ void launch_hnsw_search(const HnswSearchParams& p_in, uint32_t nq, hipStream_t s
     size_t bytes = 0;
     p.chunk = hnsw_stage_plan(p.dim, p.stage_rows, &bytes);
     if (!p.chunk) return;                                                // unsupported shape: the caller checked hnsw_search_supported
-    hipLaunchKernelGGL(hnsw_search_kernel, dim3(nq), dim3(HT), bytes, s, p);
+    if (p.id_mask) {                                                     // the caller sized vis_bits: vis_words = ceil(n_ids / 32) words per query
+        p.vis_words = (p.n_ids + 31u) / 32u;
+        if (p.mask_bits > p.n_ids) p.mask_bits = p.n_ids;
+        (void)hipMemsetAsync(p.vis_bits, 0, hnsw_filter_vis_bytes(p.n_ids, nq), s);
+        hipLaunchKernelGGL(hnsw_search_kernel<true>, dim3(nq), dim3(HT), bytes, s, p);
+    } else {
+        hipLaunchKernelGGL(hnsw_search_kernel<false>, dim3(nq), dim3(HT), bytes, s, p);
+    }
 }
 
 }  // namespace vdb

@@ -148,6 +148,9 @@ struct vdb_hnsw_index {
     size_t out_cap = 0, out_nq_cap = 0;
     uint32_t mirror_ids = 0, stride0 = 0, strideU = 0, max_list = 0;
     uint64_t device_queries = 0, host_redone = 0;
+    // pre-filtered searches: the id mask on the device and the layer-0 visited bitmaps of one filtered launch
+    uint64_t* d_mask = nullptr; size_t mask_cap = 0;
+    uint32_t* d_vis = nullptr; size_t vis_cap = 0;
     // batched insert scans: two mapped host matrices [SCAN_CHUNK][scan_ld] the scan kernel writes, a stream and events
     float* h_scan[2] = {nullptr, nullptr}; float* d_scan[2] = {nullptr, nullptr}; size_t scan_ld = 0;
     hipStream_t scan_stream = nullptr; hipEvent_t scan_ev[2] = {nullptr, nullptr};
@@ -185,13 +188,18 @@ struct LayerSearch {
     std::vector<uint64_t> pending;
     int stage = 0;                                                // 0: entry points not yet requested, 1: requested, 2: main loop
     bool zero_norm = false;
+    // pre-filter (a search's layer 0 only): bit i of mask (LSB-first in 64-bit words) = id i may be a RESULT; every visited node is
+    // still a candidate, so the walk goes on through ineligible nodes.  nullptr: no filter.
+    const uint64_t* mask = nullptr; size_t mask_bits = 0;
 
-    void start(const Graph* g_, uint64_t ep, size_t ef_, size_t layer_) {
+    void start(const Graph* g_, uint64_t ep, size_t ef_, size_t layer_, const uint64_t* mask_ = nullptr, size_t mask_bits_ = 0) {
         g = g_; ef = ef_; layer = layer_;
         cand.clear(); res.clear(); visited.clear();
         pending.assign(1, ep);
         stage = 0; zero_norm = false;
+        mask = mask_; mask_bits = mask_bits_;
     }
+    bool eligible(uint64_t id) const { return !mask || (id < mask_bits && ((mask[id >> 6] >> (id & 63)) & 1ull)); }
     // The walk is a chain of dependent cache misses at a million nodes (node -> its list table -> the layer's list): the node
     // most likely to be expanded NEXT -- the top of the candidate heap -- is pulled towards the cache one level per call, while
     // the current expansion's distances are fetched and folded.
@@ -232,14 +240,16 @@ struct LayerSearch {
             if (stage == 1) {
                 visited.insert(n.id);
                 cand.push(n);
-                res.push(n);
+                if (eligible(n.id)) res.push(n);
             } else {
                 const float furthest = res.empty() ? F32_MAX : res.top().d;
                 if (n.d < furthest || res.size() < ef) {
                     if (n.id < g->nodes.size()) __builtin_prefetch(&g->nodes[n.id]);
                     cand.push(n);
-                    res.push(n);
-                    if (res.size() > ef) { Nb drop; res.pop(drop); }
+                    if (eligible(n.id)) {
+                        res.push(n);
+                        if (res.size() > ef) { Nb drop; res.pop(drop); }
+                    }
                 }
             }
         }
@@ -572,9 +582,10 @@ int vdb_hnsw_remove(vdb_hnsw_index* g, uint64_t id) {             // graph.rs:34
 namespace {
 
 // host traversal (one GPU launch per round for the candidate lists of every query): the path for what the device-resident
-// search does not take (m > 19, ef > 1022, overflowing queries, vdb_hnsw_set_traversal(h, 1, ..))
-int search_host(vdb_hnsw_index* g, const float* queries, size_t nq, size_t dim, size_t k, size_t ef,
-                uint64_t* out_ids, float* out_dists, size_t* out_counts) {
+// search does not take (m > 19, ef > 1022, overflowing queries, vdb_hnsw_set_traversal(h, 1, ..)); id_mask: the pre-filter of
+// layer 0 (LayerSearch::mask), nullptr = none
+int search_host(vdb_hnsw_index* g, const float* queries, size_t nq, size_t dim, size_t k, size_t ef, const uint64_t* id_mask,
+                size_t mask_bits, uint64_t* out_ids, float* out_dists, size_t* out_counts) {
     int rc;
     if ((rc = vdb_internal::pairs_begin(g->flat, queries, nq, dim))) return rc;
     const size_t ef_actual = std::max(ef ? ef : g->ef_search, k);
@@ -582,7 +593,7 @@ int search_host(vdb_hnsw_index* g, const float* queries, size_t nq, size_t dim, 
     std::vector<Q> qs(nq);
     for (Q& q : qs) {
         q.layer = g->max_level; q.ep = g->ep; q.done = false; q.off = q.n = 0;
-        q.ls.start(g, q.ep, q.layer >= 1 ? 1 : ef_actual, q.layer);
+        q.ls.start(g, q.ep, q.layer >= 1 ? 1 : ef_actual, q.layer, q.layer >= 1 ? nullptr : id_mask, mask_bits);
     }
     // The per-round host work (heap operations, neighbour scans of every in-flight query) is spread over worker
     // threads, each owning a contiguous block of queries; the GPU evaluates the round's pairs in ONE launch.
@@ -623,7 +634,7 @@ int search_host(vdb_hnsw_index* g, const float* queries, size_t nq, size_t dim, 
                 if (q.layer >= 1) {
                     if (!r.empty()) q.ep = r[0].id;
                     --q.layer;
-                    q.ls.start(g, q.ep, q.layer >= 1 ? 1 : ef_actual, q.layer);
+                    q.ls.start(g, q.ep, q.layer >= 1 ? 1 : ef_actual, q.layer, q.layer >= 1 ? nullptr : id_mask, mask_bits);
                 } else {
                     const size_t cnt = std::min(r.size(), k);
                     for (size_t i = 0; i < cnt; ++i) { out_ids[b * k + i] = r[i].id; out_dists[b * k + i] = r[i].d; }
@@ -680,8 +691,10 @@ int search_host(vdb_hnsw_index* g, const float* queries, size_t nq, size_t dim, 
 }
 
 void free_mirror(vdb_hnsw_index* g) {
-    for (uint32_t** p : {&g->d_row_of, &g->d_level, &g->d_nbr0, &g->d_cnt0, &g->d_up_off, &g->d_nbrU, &g->d_cntU, &g->d_nbr0_row, &g->d_nbrU_row, &g->d_out_counts, &g->d_fail})
+    for (uint32_t** p : {&g->d_row_of, &g->d_level, &g->d_nbr0, &g->d_cnt0, &g->d_up_off, &g->d_nbrU, &g->d_cntU, &g->d_nbr0_row, &g->d_nbrU_row, &g->d_out_counts, &g->d_fail, &g->d_vis})
         if (*p) { (void)hipFree(*p); *p = nullptr; }
+    if (g->d_mask) { (void)hipFree(g->d_mask); g->d_mask = nullptr; }
+    g->mask_cap = g->vis_cap = 0;
     if (g->d_out_ids) { (void)hipFree(g->d_out_ids); g->d_out_ids = nullptr; }
     if (g->d_out_dists) { (void)hipFree(g->d_out_dists); g->d_out_dists = nullptr; }
     g->out_cap = g->out_nq_cap = 0;
@@ -1037,10 +1050,10 @@ int build_speculative(Graph* g, const uint64_t* ids, uint64_t first_id, size_t n
     return VDB_OK;
 }
 
-// device-resident search of the whole batch in one launch; queries whose walk overflowed the kernel's LDS structures are
-// listed in `redo`
-int search_device(vdb_hnsw_index* g, const float* queries, size_t nq, size_t dim, size_t k, size_t ef_actual,
-                  uint64_t* out_ids, float* out_dists, size_t* out_counts, std::vector<uint32_t>& redo) {
+// device-resident search of the whole batch in one launch (pre-filtered: one per hnsw_filter_launch_queries queries); queries
+// whose walk overflowed the kernel's LDS structures are listed in `redo`
+int search_device(vdb_hnsw_index* g, const float* queries, size_t nq, size_t dim, size_t k, size_t ef_actual, const uint64_t* id_mask,
+                  size_t mask_bits, uint64_t* out_ids, float* out_dists, size_t* out_counts, std::vector<uint32_t>& redo) {
     int rc;
     if ((rc = vdb_internal::pairs_begin(g->flat, queries, nq, dim))) return rc;
     vdb_internal::DeviceView dv;
@@ -1067,8 +1080,38 @@ int search_device(vdb_hnsw_index* g, const float* queries, size_t nq, size_t dim
     hp.stride0 = g->stride0; hp.up_off = g->d_up_off; hp.nbrU = g->d_nbrU; hp.nbrU_row = g->d_nbrU_row; hp.cntU = g->d_cntU; hp.strideU = g->strideU;
     hp.entry_point = (uint32_t)g->ep; hp.max_level = (uint32_t)g->max_level; hp.ef = (uint32_t)ef_actual; hp.k = (uint32_t)k;
     hp.out_ids = g->d_out_ids; hp.out_dists = g->d_out_dists; hp.out_counts = g->d_out_counts; hp.fail = g->d_fail; hp.status = dv.status;
-    vdb::launch_hnsw_search(hp, (uint32_t)nq, s);
-    HN_TRY(hipGetLastError());
+    if (!id_mask) {
+        vdb::launch_hnsw_search(hp, (uint32_t)nq, s);
+        HN_TRY(hipGetLastError());
+    } else {
+        // the mask once per call, clamped to the mirror's ids (bits beyond it name no node); the visited bitmaps per launch
+        const uint32_t bits = (uint32_t)std::min<size_t>(mask_bits, g->mirror_ids);
+        const size_t words = std::max<size_t>((bits + 63) / 64, 1);
+        if (words > g->mask_cap) {
+            if (g->d_mask) (void)hipFree(g->d_mask);
+            g->d_mask = nullptr; g->mask_cap = 0;
+            HN_TRY(hipMalloc((void**)&g->d_mask, words * 8));
+            g->mask_cap = words;
+        }
+        if (bits) HN_TRY(hipMemcpyAsync(g->d_mask, id_mask, (size_t)(bits + 63) / 64 * 8, hipMemcpyHostToDevice, s));
+        const size_t per_launch = std::min<size_t>(nq, vdb::hnsw_filter_launch_queries(g->mirror_ids));
+        const size_t vis_bytes = vdb::hnsw_filter_vis_bytes(g->mirror_ids, (uint32_t)per_launch);
+        if (vis_bytes > g->vis_cap) {
+            if (g->d_vis) (void)hipFree(g->d_vis);
+            g->d_vis = nullptr; g->vis_cap = 0;
+            HN_TRY(hipMalloc((void**)&g->d_vis, vis_bytes));
+            g->vis_cap = vis_bytes;
+        }
+        hp.id_mask = g->d_mask; hp.mask_bits = bits; hp.vis_bits = g->d_vis;
+        for (size_t q0 = 0; q0 < nq; q0 += per_launch) {
+            const size_t n1 = std::min(per_launch, nq - q0);
+            vdb::HnswSearchParams hq = hp;
+            hq.qp = dv.qp + q0 * dv.ld; hq.qnorm = dv.qnorm + q0;
+            hq.out_ids = g->d_out_ids + q0 * k; hq.out_dists = g->d_out_dists + q0 * k; hq.out_counts = g->d_out_counts + q0; hq.fail = g->d_fail + q0;
+            vdb::launch_hnsw_search(hq, (uint32_t)n1, s);
+            HN_TRY(hipGetLastError());
+        }
+    }
     std::vector<uint32_t> cnt(nq), fail(nq);
     uint32_t status = 0;
     HN_TRY(hipMemcpyAsync(cnt.data(), g->d_out_counts, nq * 4, hipMemcpyDeviceToHost, s));
@@ -1089,12 +1132,29 @@ int search_device(vdb_hnsw_index* g, const float* queries, size_t nq, size_t dim
     return VDB_OK;
 }
 
+// Is any PRESENT node id eligible under the mask?  (Early out at the first one.)
+bool mask_admits_a_node(const vdb_hnsw_index* g, const uint64_t* id_mask, size_t mask_bits) {
+    const size_t nb = std::min(mask_bits, g->nodes.size());
+    for (size_t w = 0; w * 64 < nb; ++w) {
+        uint64_t x = id_mask[w];
+        if (nb - w * 64 < 64) x &= (1ull << (nb - w * 64)) - 1ull;
+        for (; x; x &= x - 1)
+            if (g->nodes[w * 64 + (size_t)__builtin_ctzll(x)].present) return true;
+    }
+    return false;
+}
+
 }  // namespace
 
 extern "C" {
 
 int vdb_hnsw_search_batch(vdb_hnsw_index* g, const float* queries, size_t nq, size_t dim, size_t k, size_t ef,
                           uint64_t* out_ids, float* out_dists, size_t* out_counts) {
+    return vdb_hnsw_search_batch_masked(g, queries, nq, dim, k, ef, nullptr, 0, out_ids, out_dists, out_counts);
+}
+
+int vdb_hnsw_search_batch_masked(vdb_hnsw_index* g, const float* queries, size_t nq, size_t dim, size_t k, size_t ef,
+                                 const uint64_t* id_mask, size_t mask_bits, uint64_t* out_ids, float* out_dists, size_t* out_counts) {
     return guarded([&]() -> int {
     if (!g || (nq && (!queries || !out_counts || (k && (!out_ids || !out_dists)))))
         return vdb_internal::set_error(VDB_ERR_INVALID_ARGUMENT, "null argument");
@@ -1104,13 +1164,28 @@ int vdb_hnsw_search_batch(vdb_hnsw_index* g, const float* queries, size_t nq, si
     if (nq == 0 || !g->has_ep) return VDB_OK;                     // graph.rs:392-395: empty graph -> Ok(vec![])
     if (dim != g->dim) return vdb_internal::set_dim_error(dim, g->dim);   // distance.rs:21-26 on the first evaluation
     const size_t ef_actual = std::max(ef ? ef : g->ef_search, k);
+    if (id_mask && !mask_admits_a_node(g, id_mask, mask_bits)) {
+        // nothing is eligible: the walk would traverse the whole reachable graph to return nothing.  It is skipped; the errors it
+        // would raise stay -- the dimension check above, and a zero-norm query under Cosine (its first distance, to the entry point)
+        int rc;
+        if ((rc = vdb_internal::pairs_begin(g->flat, queries, nq, dim))) return rc;
+        if (g->metric == vdb::COSINE) {
+            vdb_internal::DeviceView dv;
+            if ((rc = vdb_internal::device_view(g->flat, &dv))) return rc;
+            std::vector<float> qn(nq);
+            HN_TRY(hipMemcpyAsync(qn.data(), dv.qnorm, nq * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)dv.stream));
+            HN_TRY(hipStreamSynchronize((hipStream_t)dv.stream));
+            for (float x : qn) if (x == 0.0f) return zero_norm_error();
+        }
+        return VDB_OK;
+    }
     const bool on_device = !g->host_only && k > 0 && g->nodes.size() < 0xffffffffull &&
                            vdb::hnsw_search_supported((uint32_t)g->dim, (uint32_t)std::min<size_t>(ef_actual, 0xffffffu), (uint32_t)std::min<size_t>(k, 0xffffffu),
                                                       (uint32_t)std::max(g->m_max0, g->m) + 1);
-    if (!on_device) return search_host(g, queries, nq, dim, k, ef, out_ids, out_dists, out_counts);
+    if (!on_device) return search_host(g, queries, nq, dim, k, ef, id_mask, mask_bits, out_ids, out_dists, out_counts);
     int rc;
     std::vector<uint32_t> redo;
-    if ((rc = search_device(g, queries, nq, dim, k, ef_actual, out_ids, out_dists, out_counts, redo))) return rc;
+    if ((rc = search_device(g, queries, nq, dim, k, ef_actual, id_mask, mask_bits, out_ids, out_dists, out_counts, redo))) return rc;
     if (!redo.empty()) {                                            // the walks that did not fit the kernel's LDS structures
         g->host_redone += redo.size();
         std::vector<float> q2(redo.size() * dim);
@@ -1118,7 +1193,7 @@ int vdb_hnsw_search_batch(vdb_hnsw_index* g, const float* queries, size_t nq, si
         std::vector<uint64_t> i2(redo.size() * k);
         std::vector<float> d2(redo.size() * k);
         std::vector<size_t> c2(redo.size());
-        if ((rc = search_host(g, q2.data(), redo.size(), dim, k, ef, i2.data(), d2.data(), c2.data()))) return rc;
+        if ((rc = search_host(g, q2.data(), redo.size(), dim, k, ef, id_mask, mask_bits, i2.data(), d2.data(), c2.data()))) return rc;
         for (size_t j = 0; j < redo.size(); ++j) {
             memcpy(out_ids + (size_t)redo[j] * k, i2.data() + j * k, k * 8);
             memcpy(out_dists + (size_t)redo[j] * k, d2.data() + j * k, k * 4);

@@ -85,27 +85,35 @@ class GpuHnswIndex(Index):
         ids, ds, cnt = self.search_batch_arrays(q.data.reshape(1, -1), k, ef)
         return [(int(ids[0, i]), float(ds[0, i])) for i in range(int(cnt[0]))]
 
-    def search_batch_arrays(self, queries, k, ef=0):
+    def search_batch_arrays(self, queries, k, ef=0, id_mask=None, mask_bits=0):
         """queries [nq, dim] f32 -> (ids u64 [nq, k], dists f32 [nq, k], counts [nq]); every query of the batch walks
-        the graph in lockstep, one GPU launch per traversal round for all their candidate lists."""
+        the graph in lockstep, one GPU launch per traversal round for all their candidate lists.
+        id_mask / mask_bits: the pre-filter of GpuFlatIndex (bit i of the uint64 words = id i eligible, ids >= mask_bits are
+        not): only eligible ids are results, the walk still goes through the others (vdb_hnsw_search_batch_masked)."""
         qs = np.ascontiguousarray(queries, dtype=np.float32)
         nq, dim = qs.shape
         kk = max(int(k), 1)
         ids = np.zeros((nq, kk), dtype=np.uint64)
         ds = np.zeros((nq, kk), dtype=np.float32)
         cnt = np.zeros(nq, dtype=np.uintp)
-        rc = self._L.vdb_hnsw_search_batch(self._h, _fp(qs), nq, dim, int(k), int(ef), _u64p(ids), _fp(ds),
-                                           cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)))
+        mask_ptr = None
+        if id_mask is not None:
+            m = np.ascontiguousarray(id_mask, dtype=np.uint64)
+            if m.size * 64 < int(mask_bits):
+                raise ValueError(f"id_mask holds {m.size * 64} bits, mask_bits is {int(mask_bits)}")
+            mask_ptr = _u64p(m)
+        rc = self._L.vdb_hnsw_search_batch_masked(self._h, _fp(qs), nq, dim, int(k), int(ef), mask_ptr, int(mask_bits),
+                                                  _u64p(ids), _fp(ds), cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)))
         if rc:
             _raise(rc)
         return ids, ds, cnt
 
-    def search_batch(self, queries):
+    def search_batch(self, queries, id_mask=None, mask_bits=0):
         if not queries:
             return []
         qs = np.stack([(q.data if isinstance(q, Vector) else np.asarray(q, np.float32)) for q, _ in queries])
         kmax = max(k for _, k in queries)
-        ids, ds, cnt = self.search_batch_arrays(qs, kmax, 50)
+        ids, ds, cnt = self.search_batch_arrays(qs, kmax, 50, id_mask=id_mask, mask_bits=mask_bits)
         return [[(int(ids[b, i]), float(ds[b, i])) for i in range(min(int(cnt[b]), k))] for b, (_, k) in enumerate(queries)]
 
     def get_vector(self, id):                                    # mod.rs:65-67

@@ -197,20 +197,34 @@ public:
     }
     // all queries walk the graph in lockstep: one GPU launch per traversal round for all their candidate lists
     std::vector<std::vector<Neighbor>> search_batch(const std::vector<std::pair<Vector, size_t>>& qs) const override {
+        bool ragged = false;
+        for (auto& q : qs) ragged |= q.first.dimension() != qs[0].first.dimension();
+        if (ragged) return Index::search_batch(qs);                             // ragged batch: the sequential loop
+        return search_batch_masked(qs, nullptr, 0);
+    }
+    // pre-filter as a bitmask over ids (bit i set = id i eligible), as GpuFlatIndex::search_batch_masked: only eligible ids are
+    // results, the walk goes through the others
+    std::vector<std::vector<Neighbor>> search_batch_masked(const std::vector<std::pair<Vector, size_t>>& qs,
+                                                           const uint64_t* id_mask, size_t mask_bits) const {
         std::vector<std::vector<Neighbor>> out(qs.size());
         if (qs.empty()) return out;
         const size_t dim = qs[0].first.dimension();
+        bool ragged = false;
+        for (auto& q : qs) ragged |= q.first.dimension() != dim;
+        if (ragged) {                                                            // one call per query
+            for (size_t b = 0; b < qs.size(); ++b) out[b] = search_batch_masked({qs[b]}, id_mask, mask_bits)[0];
+            return out;
+        }
         size_t kmax = 1;
         std::vector<float> flat;
         for (auto& q : qs) {
-            if (q.first.dimension() != dim) return Index::search_batch(qs);     // ragged batch: the sequential loop
             flat.insert(flat.end(), q.first.as_slice().begin(), q.first.as_slice().end());
             kmax = std::max(kmax, q.second);
         }
         std::vector<uint64_t> ids(qs.size() * kmax);
         std::vector<float> ds(qs.size() * kmax);
         std::vector<size_t> cnt(qs.size());
-        check(vdb_hnsw_search_batch(h_, flat.data(), qs.size(), dim, kmax, 50, ids.data(), ds.data(), cnt.data()));
+        check(vdb_hnsw_search_batch_masked(h_, flat.data(), qs.size(), dim, kmax, 50, id_mask, mask_bits, ids.data(), ds.data(), cnt.data()));
         for (size_t b = 0; b < qs.size(); ++b)
             for (size_t i = 0; i < std::min(cnt[b], qs[b].second); ++i) out[b].emplace_back((size_t)ids[b * kmax + i], ds[b * kmax + i]);
         return out;
