@@ -46,9 +46,17 @@ int vdb_hnsw_create(int metric, size_t m, size_t ef_construction, size_t ef_sear
                     vdb_hnsw_index **out);
 void vdb_hnsw_destroy(vdb_hnsw_index *h);
 
-/* Index::add -> HnswGraph::insert (mod.rs:57-59, graph.rs:244-342).  `level` < 0: drawn from the seeded stream. */
+/* Index::add -> HnswGraph::insert (mod.rs:57-59, graph.rs:244-342).  `level` < 0: drawn from the seeded stream.
+ * An id the graph holds, or held before a vdb_hnsw_remove, may be added again; it does what the reference does
+ * (graph.rs:260-261 `self.nodes[id] = Some(node); self.count += 1`): the node is REPLACED by one with the new vector, the new
+ * level and new lists, vdb_hnsw_len counts the id once more, and every list of another node that names the id keeps naming it
+ * -- also above its new level, also a link a remove left behind -- and from then on leads to the new vector.  The entry point and
+ * max_level are only ever raised (graph.rs:336-339).  Such an insert is not a fast path: the device mirror is rebuilt and the
+ * lists that name the id are looked up by reading every list. */
 int vdb_hnsw_add(vdb_hnsw_index *h, uint64_t id, const float *v, size_t dim, long level);
-/* HnswIndex::build_batch (mod.rs:37-42): sequential inserts of rows [n][dim]; ids NULL: first_id + i. */
+/* HnswIndex::build_batch (mod.rs:37-42): sequential inserts of rows [n][dim]; ids NULL: first_id + i.  Ids seen before and an
+ * id named twice in one batch are inserted in their place in the sequence, each occurrence with ITS vector, as described at
+ * vdb_hnsw_add (the second occurrence replaces the first and counts again). */
 int vdb_hnsw_add_bulk(vdb_hnsw_index *h, const uint64_t *ids, uint64_t first_id, const float *rows, size_t n, size_t dim);
 /* Index::remove -> HnswGraph::remove (graph.rs:345-381): absent id is ok. */
 int vdb_hnsw_remove(vdb_hnsw_index *h, uint64_t id);

@@ -270,3 +270,207 @@ def test_frontier_only_build_reports_a_zero_norm_row_like_the_reference(vdb):
     for i, v in enumerate(nxt):
         o.insert(300 + i, v)
     assert_same_graph(g, o, np.concatenate([np.arange(120), np.arange(300, 340)]).astype(np.uint64))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# An id the graph has held before is inserted again (graph.rs:260-261: the node is replaced, len counts it again; the lists of
+# other nodes that name it keep naming it and lead to the new vector -- tests/test_hnsw_oracle.py pins the restatement's
+# behaviour on graphs small enough to check by hand).  Every case starts from a BULK build and one search, so that the device
+# mirror exists, is clean and is brought up to date incrementally from then on.
+# ---------------------------------------------------------------------------------------------------------------------------
+READD_SHAPE = dict(n=2000, d=16, m=6, efc=48)
+
+
+def readd_base(vdb, metric, seed, n=None):
+    n = n or READD_SHAPE["n"]
+    d, m, efc = READD_SHAPE["d"], READD_SHAPE["m"], READD_SHAPE["efc"]
+    rng = np.random.default_rng(seed)
+    rows = rng.standard_normal((n, d)).astype(np.float32)
+    g, o, ids = build_pair(vdb, metric, rows, m, efc, 50, seed=seed)
+    queries = rng.standard_normal((12, d)).astype(np.float32)
+    assert_same_results(g, o, queries, 10, 64)                         # the mirror is uploaded and clean
+    assert g.build_stats()["frontier_inserts"] == n
+    return g, o, [int(i) for i in ids], rows, queries, rng
+
+
+def in_links(o, ids, target):
+    """(owner, layer) of every list of ANOTHER node that names `target`, from the restatement."""
+    out = []
+    for i in ids:
+        if i == target:
+            continue
+        for l in range(o.level(i) + 1):
+            if target in o.neighbors(i, l):
+                out.append((i, l))
+    return out
+
+
+def check_both_walks(g, o, ids, queries, k=10, ef=64):
+    """graph, then the device-resident walk (nothing redone on the host) and the forced host traversal against the restatement"""
+    assert_same_graph(g, o, ids)
+    assert_same_results(g, o, queries, k, ef)
+    assert g.stats()["host_redone"] == 0, g.stats()
+    g.set_traversal(host_only=True)
+    assert_same_results(g, o, queries, k, ef)
+    g.set_traversal(host_only=False)
+
+
+def near(rng, vecs, count, scale=0.05):
+    vecs = np.asarray(vecs, dtype=np.float32)
+    return (vecs[rng.integers(0, len(vecs), count)] + scale * rng.standard_normal((count, vecs.shape[1]))).astype(np.float32)
+
+
+def grow_and_check(vdb, g, o, ids, rng, around, queries):
+    """One more fresh bulk (the speculative walks) and single adds close to `around` -- the old and new places of the re-added
+    ids, where the lists that name them are: with m this small the new back-links make those lists outgrow m and be pruned,
+    which is where a wrong cached edge distance would show (graph.rs:221-235 scores from the stored vectors)."""
+    nxt = max(ids) + 1
+    bulk = near(rng, around, 96)
+    g.build_batch((np.arange(nxt, nxt + 96, dtype=np.uint64), bulk))
+    for j, v in enumerate(bulk):
+        o.insert(nxt + j, v)
+    singles = near(rng, around, 24)
+    for j, v in enumerate(singles):
+        g.add(nxt + 96 + j, vdb.Vector(v))
+        o.insert(nxt + 96 + j, v)
+    ids = ids + list(range(nxt, nxt + 120))
+    check_both_walks(g, o, ids, np.concatenate([queries, bulk[:4], singles[:4]]))
+    return ids
+
+
+@pytest.mark.parametrize("metric", [0, 1, 2])
+def test_readd_present_ids_at_the_same_a_lower_and_a_higher_level(vdb, metric):
+    g, o, ids, rows, queries, rng = readd_base(vdb, metric, seed=40 + metric)
+    n = len(ids)
+    by_level = {lv: [i for i in ids if o.level(i) == lv] for lv in range(4)}
+    high = [i for i in ids if o.level(i) >= 2][:3]                     # re-added at level 0
+    low = by_level[0][:4]                                              # re-added at level 3
+    same = by_level[1][:2] + by_level[0][4:6]                          # re-added at the level they have
+    assert len(high) == 3 and len(low) == 4 and len(same) == 4
+    old_vecs, new_vecs = [], []
+
+    def readd(i, level):
+        v = near(rng, rows[rng.integers(0, n, 1)], 1, 0.3)[0]          # somewhere else in the data
+        old_vecs.append(rows[i]); new_vecs.append(v)
+        g.add(i, vdb.Vector(v), level=level)
+        o.insert(i, v, level)
+
+    for i in same:
+        readd(i, o.level(i))
+    check_both_walks(g, o, ids, np.concatenate([queries, np.array(new_vecs)]))
+    for i in high:
+        above = [(j, l) for j, l in in_links(o, ids, i) if l >= 1]
+        assert above, i                                                # lists above layer 0 name the id ...
+        readd(i, 0)
+        assert o.level(i) == 0 and [(j, l) for j, l in in_links(o, ids, i) if l >= 1] == above      # ... and still do, above its new level
+    check_both_walks(g, o, ids, np.concatenate([queries, np.array(new_vecs)]))
+    for i in low:                                                      # a search between the re-adds: the mirror is synced each time
+        readd(i, 3)
+        assert o.level(i) == 3 and o.neighbors(i, 1) and o.neighbors(i, 3) is not None      # three upper lists where it had none
+        assert_same_results(g, o, np.array(new_vecs[-2:]), 10, 64)
+    check_both_walks(g, o, ids, np.concatenate([queries, np.array(new_vecs)]))
+    assert g.len() == len(o) == n + 11                                 # graph.rs:261: every re-add counts again
+    assert g.build_stats()["frontier_inserts"] == n                    # (the re-adds took the path of their own)
+    grow_and_check(vdb, g, o, ids, rng, np.array(old_vecs + new_vecs), queries)
+
+
+@pytest.mark.parametrize("metric", [0, 1, 2])
+def test_readd_the_entry_point_at_level_0(vdb, metric):
+    """The entry point and max_level are only ever raised (graph.rs:336-339): the re-added node keeps the role with a level below
+    max_level, lists only itself, and every search from then on answers with it alone.  A graph of its own."""
+    g, o, ids, rows, queries, rng = readd_base(vdb, metric, seed=50 + metric, n=1500)
+    ep, top = o.entry_point()
+    assert top >= 1
+    v = near(rng, rows[7:8], 1)[0]
+    g.add(ep, vdb.Vector(v), level=0)
+    o.insert(ep, v, 0)
+    assert o.entry_point() == (ep, top) and o.level(ep) == 0 and o.neighbors(ep, 0) == [ep, ep]
+    check_both_walks(g, o, ids, queries)
+    gi, _, gc = g.search_batch_arrays(queries, 10, 64)
+    assert np.all(gc == 1) and np.all(gi[:, 0] == ep)
+    # a fresh bulk on top: its speculative walks start from that entry point, above its level
+    more = rng.standard_normal((128, rows.shape[1])).astype(np.float32)
+    nxt = len(ids)
+    g.build_batch((np.arange(nxt, nxt + 128, dtype=np.uint64), more))
+    for j, x in enumerate(more):
+        o.insert(nxt + j, x)
+    check_both_walks(g, o, ids + list(range(nxt, nxt + 128)), np.concatenate([queries, more[:6]]))
+
+
+@pytest.mark.parametrize("frontier_only", [True, False])
+def test_readded_ids_inside_a_bulk(vdb, frontier_only):
+    """Present ids and a removed id in the middle of a bulk of fresh ones, levels from the seeded stream: the batch is inserted
+    one vector after the other like the reference's build_batch (mod.rs:37-42)."""
+    g, o, ids, rows, queries, rng = readd_base(vdb, 0, seed=60)
+    n = len(ids)
+    g.set_build(frontier_only)
+    g.remove(55); o.remove(55)
+    assert in_links(o, ids, 55)                                        # a list still names the removed id
+    assert_same_results(g, o, queries, 10, 64)
+    present = [int(i) for i in rng.choice([i for i in ids if i != 55], 12, replace=False)]
+    batch_ids = list(range(n, n + 180))
+    for t, i in enumerate(present):
+        batch_ids.insert(5 + 14 * t, i)                                # runs of 5 .. 14 fresh ids between them, a long one at the end
+    batch_ids.insert(100, 55)
+    anchors = np.concatenate([rows[present], rows[[55]]])
+    batch = near(rng, anchors, len(batch_ids), 0.2)
+    before = g.build_stats()
+    g.build_batch((np.array(batch_ids, dtype=np.uint64), batch))
+    for i, v in zip(batch_ids, batch):
+        o.insert(i, v)
+    after = g.build_stats()
+    fresh = after["frontier_inserts"] - before["frontier_inserts"] + after["scan_inserts"] - before["scan_inserts"]
+    assert fresh == 180, (before, after)                               # the 13 others did not take a fresh id's path
+    ids = ids + list(range(n, n + 180))
+    assert g.len() == len(o) == n - 1 + len(batch_ids)
+    check_both_walks(g, o, ids, np.concatenate([queries, batch[:8]]))
+    g.set_build(True)
+    grow_and_check(vdb, g, o, ids, rng, np.concatenate([anchors, batch[[5, 19, 33, 100]]]), queries)
+
+
+@pytest.mark.parametrize("frontier_only", [True, False])
+def test_the_same_id_twice_in_one_bulk(vdb, frontier_only):
+    """The reference inserts the first vector, then replaces it with the second (graph.rs:260): both walks happen, with THEIR
+    vectors, and the id counts twice."""
+    g, o, ids, rows, queries, rng = readd_base(vdb, 0, seed=70, n=1200)
+    n = len(ids)
+    g.set_build(frontier_only)
+    batch_ids = list(range(n, n + 100))
+    batch_ids[60] = n + 10                                             # far apart
+    batch_ids[31] = n + 30                                             # back to back
+    batch_ids[99] = n + 98                                             # the last two
+    batch = near(rng, rows[:50], 100, 0.5)
+    g.build_batch((np.array(batch_ids, dtype=np.uint64), batch))
+    for i, v in zip(batch_ids, batch):
+        o.insert(i, v)
+    assert g.len() == len(o) == n + 100
+    ids = ids + sorted(set(batch_ids))
+    check_both_walks(g, o, ids, np.concatenate([queries, batch[[10, 60, 30, 31, 98, 99]]]))
+    gi, gd, _ = g.search_batch_arrays(batch[[60, 10]], 1, 64)
+    assert gi[0, 0] == n + 10 and gd[0, 0] == 0.0 and not (gi[1, 0] == n + 10 and gd[1, 0] == 0.0)     # the second vector is the stored one
+    g.set_build(True)
+    grow_and_check(vdb, g, o, ids, rng, batch[[10, 60, 30, 31, 98, 99]], queries)
+
+
+@pytest.mark.parametrize("metric", [0, 1, 2])
+def test_remove_search_readd(vdb, metric):
+    g, o, ids, rows, queries, rng = readd_base(vdb, metric, seed=80 + metric)
+    n = len(ids)
+    victims = list(range(100, 130))
+    for i in victims:
+        g.remove(i); o.remove(i)
+    dangling = [i for i in victims if in_links(o, ids, i)]
+    assert len(dangling) >= 5, dangling                                # remove cleans only the lists of the node's own neighbours
+    check_both_walks(g, o, ids, queries)                               # the mirror is rebuilt without them
+    new = near(rng, rows[rng.integers(0, n, len(victims))], len(victims), 0.3)
+    for t, i in enumerate(victims):
+        level = [-1, 0, 2][t % 3]                                      # from the seeded stream, or forced
+        g.add(i, vdb.Vector(new[t]), level=level)
+        o.insert(i, new[t], level)
+        if t % 10 == 0:
+            assert_same_results(g, o, new[t:t + 1], 10, 64)
+    assert g.len() == len(o) == n
+    for i in dangling:
+        assert in_links(o, ids, i)
+    check_both_walks(g, o, ids, np.concatenate([queries, new[:8]]))
+    grow_and_check(vdb, g, o, ids, rng, np.concatenate([rows[victims], new]), queries)

@@ -231,3 +231,43 @@ def test_cpp_mirror_search_batch_masked(vdb):
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr + out.stdout
     assert "hnsw filter ok" in out.stdout
+
+
+@pytest.mark.parametrize("metric", [0, 1, 2])
+def test_masked_search_over_a_graph_with_readded_ids(vdb, metric):
+    """Ids inserted again (graph.rs:260-261 replaces the node; lists of other nodes keep naming it, also above its new level, and
+    lead to the new vector): the pre-filtered device walk equals the host traversal, and with every id eligible both equal the
+    restatement's unfiltered search."""
+    rng = np.random.default_rng(300 + metric)
+    n, d, k, ef = 2000, 16, 10, 64
+    rows = rng.standard_normal((n, d)).astype(np.float32)
+    qs = rng.standard_normal((8, d)).astype(np.float32)
+    g, o = build_pair(vdb, metric, rows, 6, 48, seed=21 + metric)
+    g.search_batch_arrays(qs, k, ef)                                   # the mirror exists and is clean
+    high = [i for i in range(n) if o.level(i) >= 2][:3]
+    low = [i for i in range(n) if o.level(i) == 0][:3]
+    g.remove(low[2]); o.remove(low[2])
+    g.search_batch_arrays(qs, k, ef)
+    new = []
+    for i, level in [(high[0], 0), (high[1], 0), (high[2], 1), (low[0], 3), (low[1], 2), (low[2], 1)]:
+        v = (rows[rng.integers(0, n)] + 0.3 * rng.standard_normal(d)).astype(np.float32)
+        new.append(v)
+        g.add(i, vdb.Vector(v), level=level)
+        o.insert(i, v, level)
+    assert any(high[0] in o.neighbors(j, l) for j in range(n) if j != high[0] for l in range(1, o.level(j) + 1))
+    qs = np.concatenate([qs, np.array(new)])
+    for elig in (np.ones(n, dtype=bool), rng.random(n) < 0.3):
+        mask, bits = mask_of(elig)
+        before = g.stats()["host_redone"]
+        dev = g.search_batch_arrays(qs, k, ef, id_mask=mask, mask_bits=bits)
+        assert g.stats()["host_redone"] == before
+        g.set_traversal(True)
+        host = g.search_batch_arrays(qs, k, ef, id_mask=mask, mask_bits=bits)
+        g.set_traversal(False)
+        assert same(dev, host)
+        assert all(elig[int(i)] for b in range(len(qs)) for i in dev[0][b, :dev[2][b]])
+        if elig.all():
+            for b in range(len(qs)):
+                oi, od = o.search(qs[b], k, ef)
+                assert dev[2][b] == len(oi) and np.array_equal(dev[0][b, :len(oi)], oi)
+                assert np.array_equal(dev[1][b, :len(oi)].view(np.uint32), od.view(np.uint32))

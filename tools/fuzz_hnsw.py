@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Randomised differential test of the HNSW index: random sizes, dimensions, metrics, m / ef_construction / ef, data with
-duplicates, interleaved removals and re-inserts; the product's graph must equal the CPU restatement's (same seed) and
-every search result must be identical (ids, order, distance bits) -- through the device-resident search.
+duplicates, interleaved removals and re-inserts -- a share of the single adds and of a second bulk use ids that are present
+or were removed (graph.rs:260-261 replaces the node and counts it again), some with a forced level, and the second bulk may
+name an id twice; the product's graph must equal the CPU restatement's (same seed) and every search result must be identical
+(ids, order, distance bits) -- through the device-resident search.
 
     python tools/fuzz_hnsw.py [--cases N] [--seed S]
 """
@@ -47,7 +49,8 @@ def main():
         seed = int(rng.integers(1, 1 << 30))
         g = vdb.GpuHnswIndex(vdb.DistanceMetric(metric), vdb.HnswParams.new(m, efc, 50), seed=seed)
         o = oracle.HnswOracle(metric, m=m, ef_construction=efc, ef_search=50, seed=seed)
-        ids = rng.permutation(n * 2)[:n]
+        perm = rng.permutation(n * 2)
+        ids, spare = perm[:n], perm[n:]
         half = n // 2
         g.build_batch((ids[:half].astype(np.uint64), rows[:half]))
         for i in range(half):
@@ -55,12 +58,39 @@ def main():
         removed = set()
         for v in rng.choice(ids[:half], size=min(half, int(rng.integers(0, 40))), replace=False):
             g.remove(int(v)); o.remove(int(v)); removed.add(int(v))
-        for i in range(half, n):                                   # single adds after the removals
-            g.add(int(ids[i]), vdb.Vector(rows[i]))
-            o.insert(int(ids[i]), rows[i])
-        desc = f"case {case}: n={n} d={d} metric={metric} m={m} efc={efc} data={kind} removed={len(removed)}"
+        present, readds = set(int(x) for x in ids[:half]) - removed, 0
+
+        def seen_id():                                             # an id the graph has held before: removed (if any is left) or present
+            nonlocal readds
+            pool = sorted(removed) if removed and rng.random() < 0.5 else sorted(present)
+            readds += 1
+            return int(pool[int(rng.integers(0, len(pool)))])
+
+        def took(i):
+            removed.discard(i); present.add(i)
+
+        for i in range(half, n):                                   # single adds after the removals; one in ten re-uses an id
+            again = rng.random() < 0.1
+            nid = seen_id() if again else int(ids[i])
+            level = int(rng.integers(0, 4)) if again and rng.random() < 0.5 else -1
+            g.add(nid, vdb.Vector(rows[i]), level=level)
+            o.insert(nid, rows[i], level)
+            took(nid)
+        # a second bulk: fresh ids, ids seen before, now and then the same id twice; other vectors of the same data
+        nb = int(min(max(n // 4, 1), 96))
+        bulk_ids = []
+        for t in range(nb):
+            r = rng.random()
+            bulk_ids.append(seen_id() if r < 0.15 else (bulk_ids[int(rng.integers(0, t))] if r < 0.2 and t else int(spare[t])))
+        bulk_rows = rows[rng.integers(0, n, nb)] if kind == "dups" else rng.permutation(rows)[:nb] * np.float32(0.9)
+        bulk_rows = np.ascontiguousarray(bulk_rows, dtype=np.float32)
+        g.build_batch((np.array(bulk_ids, dtype=np.uint64), bulk_rows))
+        for nid, v in zip(bulk_ids, bulk_rows):
+            o.insert(nid, v)
+            took(nid)
+        desc = f"case {case}: n={n} d={d} metric={metric} m={m} efc={efc} data={kind} removed={len(removed)} re-adds={readds}"
         ok = g.len() == len(o) and g.entry_point() == o.entry_point()
-        for i in ids:
+        for i in list(ids) + [int(x) for x in spare[:nb]]:
             lv = o.level(int(i))
             ok &= g.level(int(i)) == lv
             for l in range(max(lv, -1) + 1):

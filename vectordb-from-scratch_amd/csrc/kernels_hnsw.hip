@@ -352,6 +352,9 @@ __global__ __launch_bounds__(HT) void hnsw_search_kernel(HnswSearchParams p) {
                     lst = p.nbrU + (size_t)li * p.strideU; lrow = p.nbrU_row + (size_t)li * p.strideU; stride = p.strideU;
                 }
                 if (stride > MAXP) { stride = MAXP; if (lane == 0) sFail = 1u; }
+                // graph.rs:170 `if layer < node.neighbors.len()`: a node met above its own level (re-added with a lower one while
+                // lists up here still name it, or an entry point re-added below max_level) has no list at this layer
+                if (layer >= 1 && p.level[cur] < (uint32_t)layer) stride = 0;
                 bool keep = false, ok = true;
                 uint32_t nid = 0xffffffffu, row = 0xffffffffu;
                 if (lane < stride) { nid = lst[lane]; row = lrow[lane]; }

@@ -12,7 +12,8 @@
 // the exact distances of 16 new vectors at once (scan_rows_kernel; 128 vectors per chunk, the next chunk's scan and its
 // transfer run while the host walks the current one), and the walks read them from pinned host memory -- no GPU round
 // trip per insert at all.  Prune distances (graph.rs:207-241) are never recomputed: every edge keeps the distance it was
-// created with (d(a,b) and d(b,a) are the same bits under all three metrics).
+// created with (d(a,b) and d(b,a) are the same bits under all three metrics).  The one event that changes a stored vector -- an
+// id inserted AGAIN (graph.rs:260 replaces the node) -- evaluates the kept distances of the edges that name the id anew (readd_row).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,6 +26,7 @@
 #include <mutex>
 #include <thread>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/vdb_flat.h"
@@ -171,6 +173,9 @@ struct vdb_hnsw_index {
     const Node* node(uint64_t id) const { return id < nodes.size() && nodes[id].present ? &nodes[id] : nullptr; }
     bool removed_any = false;                                     // no removal so far: every listed neighbour exists, the walks skip the presence check
     bool has(uint64_t id) const { return !removed_any || (id < row_of_id.size() && row_of_id[id] != 0xffffffffu); }
+    std::vector<uint8_t> was_removed;                             // ids that left through vdb_hnsw_remove: lists of other nodes may still name them
+    // an id the graph has held before -- present now, or removed: other nodes' lists may name it, so its insert is a re-add (readd_row)
+    bool seen_before(uint64_t id) const { return id < nodes.size() && (nodes[id].present || (id < was_removed.size() && was_removed[id])); }
 };
 
 namespace {
@@ -392,17 +397,9 @@ bool walks_supported(const Graph* g);
 int build_speculative(Graph* g, const uint64_t* ids, uint64_t first_id, size_t n, const std::vector<uint32_t>& rowv,
                       const std::vector<size_t>& lev, size_t* done);
 
-int add_rows(Graph* g, const uint64_t* ids, uint64_t first_id, const float* rows, size_t n, size_t dim, const long* levels, long level1) {
+// A batch of ids the graph has never held, each once (add_rows splits a batch at every other insert).
+int add_fresh_rows(Graph* g, const uint64_t* ids, uint64_t first_id, const float* rows, size_t n, size_t dim, const long* levels, long level1) {
     if (n == 0) return VDB_OK;
-    if (dim == 0) return vdb_internal::set_error(VDB_ERR_INVALID_ARGUMENT, "zero-dimensional vectors are not indexable");
-    if (g->count == 0 && !g->has_ep) g->dim = dim;
-    if (dim != g->dim) return vdb_internal::set_dim_error(g->dim, dim);
-    // The graph is a Vec indexed by id in the reference too (graph.rs:78, :249-251 resize_with(id + 1)), so a huge sparse id
-    // costs id + 1 slots there as here; the device mirror addresses nodes with 32 bits, so larger ids are refused up front
-    // (and an allocation failure of the resize is caught at the boundary instead of unwinding through it).
-    for (size_t i = 0; i < n; ++i)
-        if ((ids ? ids[i] : first_id + i) >= 0xfffffff0ull)
-            return vdb_internal::set_error(VDB_ERR_INVALID_ARGUMENT, "HNSW node ids must be below 2^32 - 16");
     int rc;
     if ((rc = vdb_flat_add_bulk(g->flat, ids, first_id, rows, n, dim))) return rc;
     // When insert number i fails (zero-norm Cosine pair), the reference has stored node i without links and has not seen
@@ -495,6 +492,93 @@ int add_rows(Graph* g, const uint64_t* ids, uint64_t first_id, const float* rows
     return VDB_OK;
 }
 
+// An id the graph has held before is inserted again (graph.rs:260-261: `self.nodes[id] = Some(node); self.count += 1`, whatever
+// was there).  The node gets new lists of its new level; every list of another node that names the id keeps naming it and now
+// leads to the NEW vector.  Rare, so it may be slow: no speculation, one GPU round trip per expansion of the walk, and
+//   - the mirror is rebuilt as a whole: lists that name the id carry its old device row (or none, after a remove), and the
+//     node's upper-list slot was sized for its old level;
+//   - the cached distance of every edge that names the id is evaluated again, new row against the owner's row, BEFORE the
+//     insert: its back-link loop prunes lists that hold such edges (graph.rs:221-235 scores from the stored vectors);
+//   - the walk may reach the id itself through such an edge: fetch() evaluates the new row against itself like any other pair.
+int readd_row(Graph* g, uint64_t id, const float* v, size_t dim, long level_in) {
+    int rc;
+    if ((rc = vdb_flat_add_bulk(g->flat, &id, 0, v, 1, dim))) return rc;                    // last-wins: the old row dies, a new one is appended
+    if ((rc = vdb_flat_flush(g->flat))) return rc;
+    const uint32_t row = vdb_internal::row_of(g->flat, id);
+    if (row == 0xffffffffu) return vdb_internal::set_error(VDB_ERR_INVALID_ARGUMENT, "row was not stored");
+    const size_t level = level_in >= 0 ? std::min<size_t>((size_t)level_in, g->max_layers - 1) : level_from_unit(g, next_unit(g));
+    g->mirror_full = true;
+    if (id < g->h_up_off.size()) g->h_up_off[id] = 0xffffffffu;
+    std::vector<uint32_t> ra, rb;
+    std::vector<float*> slot;
+    for (size_t o = 0; o < g->nodes.size(); ++o) {                                           // (no reverse index: every list is read)
+        Node& nd = g->nodes[o];
+        if (!nd.present || o == id) continue;                                                // the id's own old lists go with the old node
+        for (size_t l = 0; l < nd.nbr.size(); ++l)
+            for (size_t t = 0; t < nd.nbr[l].size(); ++t)
+                if (nd.nbr[l][t] == id) { ra.push_back(nd.row); rb.push_back(row); slot.push_back(&nd.nbr_d[l][t]); }
+    }
+    std::vector<float> dd(ra.size());
+    if (!ra.empty()) {
+        if ((rc = vdb_internal::rows_eval(g->flat, ra.data(), rb.data(), ra.size(), dd.data()))) return rc;
+        for (size_t t = 0; t < ra.size(); ++t) *slot[t] = dd[t];                             // (a zero-norm pair keeps its mark: f32::MAX at prune time)
+        g->stats[0] += ra.size(); g->stats[1]++;
+    }
+    auto fetch = [&](const std::vector<uint64_t>& pend, std::vector<float>& d, size_t) -> int {
+        ra.assign(pend.size(), row); rb.resize(pend.size());
+        for (size_t t = 0; t < pend.size(); ++t) rb[t] = g->row_of_id[pend[t]];
+        g->stats[0] += pend.size(); g->stats[1]++;
+        return vdb_internal::rows_eval(g->flat, ra.data(), rb.data(), pend.size(), d.data());
+    };
+    return insert_node(g, id, row, level, fetch);
+}
+
+int add_rows(Graph* g, const uint64_t* ids, uint64_t first_id, const float* rows, size_t n, size_t dim, const long* levels, long level1) {
+    if (n == 0) return VDB_OK;
+    if (dim == 0) return vdb_internal::set_error(VDB_ERR_INVALID_ARGUMENT, "zero-dimensional vectors are not indexable");
+    if (g->count == 0 && !g->has_ep) g->dim = dim;
+    if (dim != g->dim) return vdb_internal::set_dim_error(g->dim, dim);
+    // The graph is a Vec indexed by id in the reference too (graph.rs:78, :249-251 resize_with(id + 1)), so a huge sparse id
+    // costs id + 1 slots there as here; the device mirror addresses nodes with 32 bits, so larger ids are refused up front
+    // (and an allocation failure of the resize is caught at the boundary instead of unwinding through it).
+    auto id_of = [&](size_t i) { return ids ? ids[i] : first_id + i; };
+    bool plain = true;                                                                       // fresh ids, each once: the usual batch
+    for (size_t i = 0; i < n; ++i) {
+        if (id_of(i) >= 0xfffffff0ull)
+            return vdb_internal::set_error(VDB_ERR_INVALID_ARGUMENT, "HNSW node ids must be below 2^32 - 16");
+        if (g->seen_before(id_of(i))) plain = false;
+    }
+    if (plain && ids) {                                                                      // an id twice in the batch?  (ascending ids: no)
+        bool ascending = true;
+        for (size_t i = 1; i < n && ascending; ++i) ascending = ids[i] > ids[i - 1];
+        if (!ascending) {
+            std::vector<uint64_t> sorted(ids, ids + n);
+            std::sort(sorted.begin(), sorted.end());
+            plain = std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end();
+        }
+    }
+    if (plain) return add_fresh_rows(g, ids, first_id, rows, n, dim, levels, level1);
+    // The batch is split at every id the graph has held before and at the second occurrence of an id within it: the runs of
+    // fresh ids in between are built as usual, each such insert goes through readd_row with ITS vector -- the reference inserts
+    // one vector after the other (mod.rs:37-42), and returns at the first that fails.
+    int rc;
+    std::unordered_set<uint64_t> run;                                                       // the ids of the run being collected
+    size_t r0 = 0;
+    auto build_run = [&](size_t end) -> int {
+        const int r = end > r0 ? add_fresh_rows(g, ids ? ids + r0 : nullptr, first_id + r0, rows + r0 * dim, end - r0, dim, levels ? levels + r0 : nullptr, level1) : VDB_OK;
+        run.clear(); r0 = end;
+        return r;
+    };
+    for (size_t i = 0; i < n; ++i) {
+        const uint64_t id = id_of(i);
+        if (!g->seen_before(id) && !run.count(id)) { run.insert(id); continue; }
+        if ((rc = build_run(i))) return rc;
+        if ((rc = readd_row(g, id, rows + i * dim, dim, levels ? levels[i] : level1))) return rc;
+        r0 = i + 1;
+    }
+    return build_run(n);
+}
+
 void free_mirror(vdb_hnsw_index* g);
 
 }  // namespace
@@ -554,6 +638,8 @@ int vdb_hnsw_remove(vdb_hnsw_index* g, uint64_t id) {             // graph.rs:34
     g->nodes[id] = Node();
     if (id < g->row_of_id.size()) g->row_of_id[id] = 0xffffffffu;
     g->removed_any = true;
+    if (id >= g->was_removed.size()) g->was_removed.resize(g->nodes.size(), 0);
+    g->was_removed[id] = 1;
     for (size_t l = 0; l < gone.nbr.size(); ++l)
         for (uint64_t nid : gone.nbr[l]) {
             if (nid >= g->nodes.size() || !g->nodes[nid].present || l >= g->nodes[nid].nbr.size()) continue;
@@ -743,10 +829,12 @@ int sync_mirror(vdb_hnsw_index* g, hipStream_t s, size_t reserve_ids, size_t res
         uint32_t* r0 = g->h_stage;
         uint32_t* rU = g->h_stage + g->dirty.size() * w0;
         uint32_t cU = 0;
+        bool bad = false;                                              // a record that would be written outside the mirror
         for (size_t t = 0; t < g->dirty.size(); ++t) {
             const uint32_t id = g->dirty[t];
             const Node& nd = g->nodes[id];
             uint32_t* r = r0 + t * w0;
+            if (id >= g->cap_ids) bad = true;
             r[0] = id; r[1] = nd.present ? nd.row : 0xffffffffu; r[2] = nd.present ? nd.level : 0u;
             r[3] = nd.present && nd.level ? g->h_up_off[id] : 0u;
             for (uint32_t i = 0; i < stride0; ++i) {
@@ -758,6 +846,7 @@ int sync_mirror(vdb_hnsw_index* g, hipStream_t s, size_t reserve_ids, size_t res
                 for (size_t l = 1; l < nd.nbr.size(); ++l) {
                     uint32_t* u = rU + (size_t)cU++ * wU;
                     u[0] = g->h_up_off[id] + (uint32_t)(l - 1);
+                    if (u[0] >= g->n_upper_used || u[0] >= g->cap_upper) bad = true;
                     for (uint32_t i = 0; i < strideU; ++i) {
                         const bool in = i < nd.nbr[l].size();
                         u[1 + i] = in ? (uint32_t)nd.nbr[l][i] : 0xffffffffu;
@@ -766,6 +855,9 @@ int sync_mirror(vdb_hnsw_index* g, hipStream_t s, size_t reserve_ids, size_t res
                 }
             g->dirty_flag[id] = 0;
         }
+        // the scatter kernel writes where the records say: nothing is launched unless every node id is inside the mirror's id
+        // arrays and every upper-list slot inside the slots handed out so far (the next sync rebuilds the mirror as a whole)
+        if (bad) { g->mirror_full = true; return vdb_internal::set_error(VDB_ERR_DEVICE, "internal error: a mirror record lies outside the mirror"); }
         vdb::HnswScatterParams sp{g->d_stage, (uint32_t)g->dirty.size(), g->d_stage + g->dirty.size() * w0, cU,
                                   g->d_row_of, g->d_level, g->d_up_off, g->d_nbr0, g->d_nbr0_row, stride0, g->d_nbrU, g->d_nbrU_row, strideU};
         vdb::launch_hnsw_scatter(sp, s);
