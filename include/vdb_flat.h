@@ -133,6 +133,39 @@ int vdb_flat_reserve(vdb_flat_index *h, size_t rows, size_t dim);
 /* Push staged adds/removes to the device now (otherwise done lazily by the next search). */
 int vdb_flat_flush(vdb_flat_index *h);
 
+/*
+ * Take the device rows of removed and overwritten vectors back (no reference counterpart: a HashMap frees what it removes,
+ * src/flat_index.rs:43-46; search results are identical before and after, bit for bit).  remove() only clears a bit, and
+ * VectorStore::insert_with_metadata turns every upsert into remove(old) + add(next_id++) (src/storage.rs:157-166), so a
+ * long-lived store otherwise grows by a row per upsert and every search scans the dead rows too.
+ *
+ * vdb_flat_compact: staged adds are uploaded first; then the live rows and everything kept per row (norm, score coefficients,
+ * certificate margin, id, the bf16 shadow row) move down over the dead ones ON THE DEVICE, in place and in their old order,
+ * bit for bit (nothing is recomputed) -- the index then equals one that was given the surviving rows in the same order.
+ * Extra device memory: a bounce buffer of 32 MiB plus 4 bytes per 32 rows, allocated before the first row moves.
+ * *out_reclaimed (may be NULL) = device rows given back; 0, and no device work, when no row is dead.  shrink = 0 keeps the
+ * capacity, so later adds reuse the freed tail; shrink != 0 then re-allocates the store to the capacity a fresh index of
+ * that many rows would have -- THAT step holds the old and the new store at once.  Rows of another dimension are untouched.
+ * A mutation like add / remove: under the caller's write lock (routes.rs:141,:210,:300), refused while a submitted search
+ * is outstanding.  Failure: an error before the first row moved (allocation) leaves the index as it was; a HIP error after
+ * that leaves rows half moved, so the handle then refuses every search, flush and get_vector with VDB_ERR_DEVICE (single
+ * adds are still staged on the host, but can no longer be uploaded) -- destroy it.  On a sharded handle every shard compacts its own rows (concurrently); rows never change shards.
+ *
+ * vdb_flat_set_auto_compact(h, f): with 0 < f < 1 every flush -- and so the next search after a write -- compacts when more
+ * than f * (device rows) of the uploaded rows are dead (never while a submitted search is outstanding).  Default 0 = never.
+ *
+ * vdb_flat_store_stats: [0] device rows, live + dead, staged ones included   [1] live rows   [2] capacity in rows
+ *  [3] bytes of device memory the row store holds (rows, per-row columns, live mask, bf16 shadow)
+ *  [4] compactions run   [5] rows reclaimed in total   [6] host clock of the last compaction, ns (the whole call: upload of
+ *  the plan, the moves, renumbering the host's id -> row map)
+ *  [7] the last compaction's device part: bits 0-39 ns from the first enqueue to the synchronise after the last move,
+ *      bits 40-51 chunks that went through the bounce buffer, bits 52-63 chunks moved directly (both saturate at 4095).
+ * On a sharded handle: sums over the shards; [6] and the time in [7] are maxima.
+ */
+int vdb_flat_compact(vdb_flat_index *h, int shrink, size_t *out_reclaimed);
+int vdb_flat_set_auto_compact(vdb_flat_index *h, double dead_fraction);
+int vdb_flat_store_stats(const vdb_flat_index *h, uint64_t out[8]);
+
 /* Index::search(query, k)  src/index.rs:20, src/flat_index.rs:52-65.
  * out_ids/out_dists hold k entries; *out_count = min(k, len).  Ascending by
  * (distance, id): the reference's tie order is HashMap-random. */
@@ -333,12 +366,21 @@ int vdb_flat_set_tiers(vdb_flat_index *h, unsigned flags);
  */
 int vdb_flat_debug_screen_scores(vdb_flat_index *h, const float *queries, size_t nq, size_t dim, int raw,
                                  float *out_scores, float *out_qinfo, double *out_consts);
-size_t vdb_flat_debug_rows(const vdb_flat_index *h); /* device rows incl. tombstoned ones (row i = i-th row ever added since the last reset) */
+size_t vdb_flat_debug_rows(const vdb_flat_index *h); /* device rows incl. tombstoned ones (row i = i-th row added since the last reset or vdb_flat_compact: a compaction renumbers the rows) */
 int vdb_flat_debug_row_info(vdb_flat_index *h, float *out, size_t n_rows);
 /* the per-query filter thresholds of the screening tier as the LAST search on this handle derived them from its sample pass (first nq queries) */
 int vdb_flat_debug_last_thresholds(vdb_flat_index *h, float *out, size_t nq);
 int vdb_flat_debug_cert_probe(vdb_flat_index *h, const uint32_t *qi, const float *T, const float *ek, size_t n,
                               uint32_t *out);
+
+/* Diagnostics of vdb_flat_compact (tests).  vdb_flat_debug_compact_plan needs no handle and no device: for a live mask
+ * (bit r & 31 of word r >> 5 = row r alive; bits at and above n_rows clear) it returns the number of chunks the compaction
+ * moves and writes the first `cap` of them to out as [first source row, end source row, first destination row, mode]
+ * (mode 0 = moved directly, 1 = through the bounce buffer); bounce_rows = 0 means the default for rows of `ld` floats.
+ * vdb_flat_debug_set_compact_bounce: the bounce buffer of this handle in rows (rounded down to 32, at least 32; 0 = default),
+ * so that small indexes exercise many chunks.  Results are identical whatever the value. */
+size_t vdb_flat_debug_compact_plan(const uint32_t *live, size_t n_rows, size_t bounce_rows, size_t ld, uint32_t *out, size_t cap);
+int vdb_flat_debug_set_compact_bounce(vdb_flat_index *h, size_t rows);
 
 /* Thread-local message of the last failing call on this thread, plus the
  * DimensionMismatch pair (error.rs:12-13).  Any pointer may be NULL. */

@@ -91,6 +91,23 @@ void launch_count_zero_live(const float* nd, const uint32_t* livemask, uint32_t 
 void launch_build_rowmask(const uint64_t* row_ids, const uint32_t* livemask, const uint64_t* idmask,
                           uint64_t mask_bits, uint32_t n_rows, uint32_t* out_mask, hipStream_t s);
 
+// ---------------------------------------------------------------- row store compaction (kernels_compact.hip)
+// One chunk of vdb_flat_compact: the live rows of source rows [row_begin, row_end) move, with every per-row column, to
+// dst[dest(r) - dst_sub], dest(r) = prefix[r >> 5] + popc(live[r >> 5] & ((1 << (r & 31)) - 1)).  src == dst is the in-place
+// form (the host guarantees dest(row_end) <= row_begin); live == null is the identity form (row r -> r - dst_sub).
+struct CompactMoveParams {
+    const uint32_t* live; const uint32_t* prefix;      // old live mask and its exclusive per-word popcount prefix
+    uint32_t row_begin, row_end, dst_sub;
+    uint32_t ld, lanes_log2;                           // lanes per row: 2^lanes_log2 in [8, 64] (compact_lanes_log2)
+    const float* src_rows; float* dst_rows;
+    const uint16_t* src_rows16; uint16_t* dst_rows16;  // null without the bf16 shadow
+    const float* src_nd; float* dst_nd; const float* src_alpha; float* dst_alpha; const float* src_beta; float* dst_beta;
+    const float* src_margin; float* dst_margin;        // null under Cosine
+    const uint64_t* src_ids; uint64_t* dst_ids;
+};
+inline uint32_t compact_lanes_log2(uint32_t ld) { uint32_t l = 3; while (l < 6 && (1u << l) < (ld >> 2)) ++l; return l; }
+void launch_compact_move(const CompactMoveParams& p, uint32_t n_cu, hipStream_t s);
+
 // ---------------------------------------------------------------- query preparation
 struct QueryPrepParams {
     const float* q_in; uint32_t dim; uint32_t nq;      // [nq][dim] as handed over

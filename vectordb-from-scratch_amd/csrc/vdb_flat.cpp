@@ -305,6 +305,7 @@ int vdb_flat_get_vector(vdb_flat_index* ix, uint64_t id, float* out, size_t cap,
     }
     auto it = ix->id2row.find(id);
     if (it == ix->id2row.end()) return fail(VDB_ERR_NOT_FOUND, "Vector not found: %llu", (unsigned long long)id);
+    if (ix->store_broken) return fail(VDB_ERR_DEVICE, "the row store is inconsistent after a failed compaction: destroy the handle");
     if (dim) *dim = ix->dim;
     if (!out) return VDB_OK;
     size_t ncopy = std::min<size_t>(cap, ix->dim);
@@ -352,6 +353,76 @@ int vdb_flat_flush(vdb_flat_index* ix) {
     if (rc) return rc;
     if ((rc = flush(ix))) return rc;
     if (ix->metric == vdb::COSINE && ix->n_uploaded) return ensure_zero_count(ix);
+    return VDB_OK;
+    });
+}
+
+int vdb_flat_compact(vdb_flat_index* ix, int shrink, size_t* out_reclaimed) {
+    return guarded([&]() -> int {
+    if (!ix) return fail(VDB_ERR_INVALID_ARGUMENT, "null handle");
+    if (out_reclaimed) *out_reclaimed = 0;
+    if (ix->multi) {
+        std::mutex m;
+        size_t total = 0;
+        int rc = multi_for_each(ix, [&](vdb_flat_index* c) {
+            size_t got = 0;
+            int r = vdb_flat_compact(c, shrink, &got);
+            std::lock_guard<std::mutex> g(m);
+            total += got;
+            return r;
+        });
+        if (out_reclaimed) *out_reclaimed = total;
+        return rc;
+    }
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (in_flight(ix)) return refuse_in_flight();
+    int rc = set_device(ix);
+    if (rc) return rc;
+    return compact_store(ix, shrink != 0, out_reclaimed);
+    });
+}
+
+int vdb_flat_set_auto_compact(vdb_flat_index* ix, double dead_fraction) {
+    return guarded([&]() -> int {
+    if (!ix || !(dead_fraction >= 0.0 && dead_fraction < 1.0)) return fail(VDB_ERR_INVALID_ARGUMENT, "dead_fraction must be in [0, 1)");
+    if (ix->multi) return multi_for_each(ix, [dead_fraction](vdb_flat_index* c) { return vdb_flat_set_auto_compact(c, dead_fraction); });
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->auto_compact = dead_fraction;
+    return VDB_OK;
+    });
+}
+
+int vdb_flat_store_stats(const vdb_flat_index* ix, uint64_t out[8]) {
+    return guarded([&]() -> int {
+    if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (ix->multi) { multi_store_stats(ix, out); return VDB_OK; }
+    std::lock_guard<std::mutex> g(const_cast<vdb_flat_index*>(ix)->mu);
+    store_stats(ix, out);
+    return VDB_OK;
+    });
+}
+
+size_t vdb_flat_debug_compact_plan(const uint32_t* live, size_t n_rows, size_t bounce_rows, size_t ld, uint32_t* out, size_t cap) {
+    size_t n = 0;
+    (void)guarded([&]() -> int {
+    if (!live || n_rows > 0xfffffff0ull) return VDB_OK;
+    const uint32_t B = bounce_rows ? std::max<uint32_t>(32u, (uint32_t)std::min<size_t>(bounce_rows, 0xffffffe0u) & ~31u) : compact_bounce_rows((uint32_t)std::max<size_t>(ld, 1), false);
+    std::vector<uint32_t> prefix;
+    std::vector<CompactChunk> plan;
+    compact_plan(live, (uint32_t)n_rows, B, &prefix, &plan);
+    n = plan.size();
+    for (size_t i = 0; out && i < std::min(n, cap); ++i) { out[4 * i] = plan[i].a; out[4 * i + 1] = plan[i].b; out[4 * i + 2] = plan[i].dst; out[4 * i + 3] = plan[i].mode; }
+    return VDB_OK;
+    });
+    return n;
+}
+
+int vdb_flat_debug_set_compact_bounce(vdb_flat_index* ix, size_t rows) {
+    return guarded([&]() -> int {
+    if (!ix || rows > 0xffffffe0ull) return fail(VDB_ERR_INVALID_ARGUMENT, "bad argument");
+    if (ix->multi) return multi_for_each(ix, [rows](vdb_flat_index* c) { return vdb_flat_debug_set_compact_bounce(c, rows); });
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->bounce_rows_override = (uint32_t)rows;
     return VDB_OK;
     });
 }

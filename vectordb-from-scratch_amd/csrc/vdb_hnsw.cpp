@@ -592,6 +592,8 @@ int vdb_hnsw_create(int metric, size_t m, size_t ef_construction, size_t ef_sear
     *out = nullptr;
     if (m < 2) return vdb_internal::set_error(VDB_ERR_INVALID_ARGUMENT, "m must be >= 2");
     vdb_flat_index* flat = nullptr;
+    // (this private handle is never compacted -- no vdb_flat_compact, auto-compaction stays at its default 0: the graph mirror
+    // holds device row numbers in row_of_id / d_nbr0_row, and a compaction renumbers rows)
     int rc = vdb_flat_create(metric, device, &flat);
     if (rc) return rc;
     auto* g = new vdb_hnsw_index();

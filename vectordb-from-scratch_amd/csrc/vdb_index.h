@@ -180,6 +180,11 @@ struct vdb_flat_index {
     uint64_t* d_row_ids = nullptr; uint32_t* d_live = nullptr; uint32_t* d_scalars = nullptr;  // [0]=nd2max bits [1]=zero count [2],[3]=max bf16 rounding error of a row (abs^2, rel^2)
     uint32_t cap_rows = 0;
     bool zero_valid = false; uint32_t zero_live = 0;
+    // vdb_flat_compact (vdb_store.cpp compact_store): dead rows are taken back by an in-place stable compaction on the device
+    double auto_compact = 0.0;                              // vdb_flat_set_auto_compact: flush compacts above this dead fraction (0 = never)
+    uint32_t bounce_rows_override = 0;                      // vdb_flat_debug_set_compact_bounce (tests): bounce buffer in rows, 0 = compact_bounce_rows()
+    bool store_broken = false;                              // a compaction failed after its first row moved: every later call is refused
+    uint64_t n_compactions = 0, rows_reclaimed = 0, last_compact_ns = 0, last_device_ns = 0, last_chunks_direct = 0, last_chunks_bounce = 0;
     vdbi::DevBuf<uint32_t> d_idrank, d_rank2row; bool rank_valid = false;
 
     // search workspace: everything one search in flight owns.  Two of them, so that two batches can be in flight on two
@@ -219,6 +224,12 @@ void kill_row(Index* ix, uint32_t row);
 int remove_id(Index* ix, uint64_t id);
 int add_one(Index* ix, uint64_t id, const float* v, size_t dim);
 int flush(Index* ix);
+// the chunk plan of a compaction: source rows [a, b) whose live rows go to [dst, ...), directly (mode 0) or through the bounce buffer (mode 1)
+struct CompactChunk { uint32_t a, b, dst, mode; };
+void compact_plan(const uint32_t* live, uint32_t n_rows, uint32_t bounce_rows, std::vector<uint32_t>* prefix, std::vector<CompactChunk>* out);
+uint32_t compact_bounce_rows(uint32_t ld, bool shadow);
+int compact_store(Index* ix, bool shrink, size_t* out_reclaimed);
+void store_stats(const Index* ix, uint64_t out[8]);
 int ensure_zero_count(Index* ix);
 int ensure_ranks(Index* ix);
 
@@ -268,6 +279,7 @@ int multi_search_host(vdb_flat_index* P, const float* queries, size_t nq, size_t
 int multi_set_exchange(vdb_flat_index* P, int mode);
 size_t multi_shards(const vdb_flat_index* P);
 size_t multi_shard_len(const vdb_flat_index* P, size_t g);
+void multi_store_stats(const vdb_flat_index* P, uint64_t out[8]);
 void multi_stats(const vdb_flat_index* P, uint64_t out[8]);
 inline int refuse_multi(const char* what) { return fail(VDB_ERR_INVALID_ARGUMENT, "%s is not available on a sharded handle (vdb_flat_create_sharded)", what); }
 

@@ -642,6 +642,20 @@ int multi_set_exchange(vdb_flat_index* P, int mode) {
 
 size_t multi_shards(const vdb_flat_index* P) { return (size_t)P->multi->G; }
 size_t multi_shard_len(const vdb_flat_index* P, size_t g) { return g < (size_t)P->multi->G ? vdb_flat_len(P->multi->sh[g]) : 0; }
+// vdb_flat_store_stats of the parent: sums over the shards; [6] and the device time in [7] are maxima (the shards compact concurrently)
+void multi_store_stats(const vdb_flat_index* P, uint64_t out[8]) {
+    memset(out, 0, 8 * sizeof(uint64_t));
+    uint64_t dev_ns = 0, bounce = 0, direct = 0;
+    for (auto* c : P->multi->sh) {
+        uint64_t st[8] = {0};
+        (void)vdb_flat_store_stats(c, st);
+        for (int i = 0; i < 6; ++i) out[i] += st[i];
+        out[6] = std::max<uint64_t>(out[6], st[6]);
+        dev_ns = std::max<uint64_t>(dev_ns, st[7] & ((1ull << 40) - 1));
+        bounce += (st[7] >> 40) & 4095; direct += st[7] >> 52;
+    }
+    out[7] = dev_ns | (std::min<uint64_t>(bounce, 4095) << 40) | (std::min<uint64_t>(direct, 4095) << 52);
+}
 void multi_stats(const vdb_flat_index* P, uint64_t out[8]) { memcpy(out, P->multi->stats, sizeof(P->multi->stats)); }
 
 }  // namespace vdbi

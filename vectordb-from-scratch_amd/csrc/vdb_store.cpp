@@ -6,7 +6,8 @@
 //   nd       [cap]     f32   exact-order row norm  (vector.rs:35-37)
 //   alpha,beta [cap]   f32   ranking score = fma(dot, alpha, beta)
 //   row_ids  [cap]     u64   device row -> reference internal id
-//   live     [cap/32]  u32   tombstone bitmask (remove() clears a bit; rows are append-only)
+//   live     [cap/32]  u32   tombstone bitmask (remove() clears a bit; rows are appended, and only compact_store renumbers them)
+// Invariant kept by grow and by compact_store: rows, margin and the bf16 shadow read as zero over [n_uploaded, cap).
 #include <numeric>
 
 #include "vdb_index.h"
@@ -14,10 +15,8 @@
 namespace vdbi {
 
 // ------------------------------------------------------------------ device store management
-int grow(Index* ix, uint32_t need_rows) {
-    if (need_rows <= ix->cap_rows) return VDB_OK;
-    uint32_t cap = std::max<uint32_t>({need_rows, ix->cap_rows * 2u, 1024u});
-    cap = round_up(cap, 256);
+// Re-allocates the store with room for `cap` rows (>= n_uploaded) and carries the uploaded rows over; old and new exist at once.
+static int resize_store(Index* ix, uint32_t cap) {
     float *rows = nullptr, *nd = nullptr, *al = nullptr, *be = nullptr, *mg = nullptr;
     uint64_t* ids = nullptr;
     uint32_t* lv = nullptr;
@@ -63,6 +62,12 @@ int grow(Index* ix, uint32_t need_rows) {
     ix->cap_rows = cap;
     ix->live_dirty = true;
     return VDB_OK;
+}
+
+int grow(Index* ix, uint32_t need_rows) {
+    if (need_rows <= ix->cap_rows) return VDB_OK;
+    uint32_t cap = std::max<uint32_t>({need_rows, ix->cap_rows * 2u, 1024u});
+    return resize_store(ix, round_up(cap, 256));
 }
 
 void free_store(Index* ix) {
@@ -166,7 +171,8 @@ int add_one(Index* ix, uint64_t id, const float* v, size_t dim) {
     return VDB_OK;
 }
 
-int flush(Index* ix) {
+static int flush_upload(Index* ix) {
+    if (ix->store_broken) return fail(VDB_ERR_DEVICE, "the row store is inconsistent after a failed compaction: destroy the handle");
     hipStream_t s = ix->stream;
     uint32_t n = ix->n_rows();
     if (n > ix->n_uploaded) {
@@ -194,6 +200,188 @@ int flush(Index* ix) {
         HIP_TRY(hipStreamSynchronize(s));
         ix->live_dirty = false;
     }
+    return VDB_OK;
+}
+
+// ------------------------------------------------------------------ compaction (vdb_flat_compact)
+// The bounce buffer: 32 MiB of whole rows (every column of a row included), at least one 32-row word.  Large enough that one
+// launch gives each of the 256 CUs 128 KiB to move, 1 % of a 3 GB store, and -- read back at once -- well inside the 256 MiB cache.
+constexpr size_t COMPACT_BOUNCE_BYTES = (size_t)32 << 20;
+static size_t bounce_row_bytes(uint32_t ld, bool shadow) { return (size_t)ld * 4 + (shadow ? (size_t)ld * 2 : 0) + 8 + 4 * 4; }
+uint32_t compact_bounce_rows(uint32_t ld, bool shadow) {
+    const size_t rows = COMPACT_BOUNCE_BYTES / bounce_row_bytes(ld, shadow);
+    return (uint32_t)std::max<size_t>(32, rows & ~(size_t)31);
+}
+
+// The chunk plan.  prefix[w] = live rows below word w (nw + 1 entries), so dest(r) = prefix[r >> 5] + popc(live bits below r).
+// Chunks are runs of whole 32-row words, in source order, starting at the first word that holds a dead row (everything below
+// it stays where it is).  With gap = a - dest(a) dead rows below a chunk's first row a:
+//   direct  [a, b): b the last word boundary with live(a, b) <= gap, i.e. dest(b) <= a -- no row written by the launch is one
+//           it (or a later launch) still reads.  Taken when the gap is at least a quarter of the bounce buffer (below that a
+//           bounced chunk moves more rows per launch than a direct one could) or when it reaches the end of the store;
+//   bounce  [a, b): b the last word boundary with live(a, b) <= bounce_rows; gathered into the bounce buffer, then copied down.
+// Words without a live row are skipped (they only widen the gap).
+void compact_plan(const uint32_t* live, uint32_t n_rows, uint32_t bounce_rows, std::vector<uint32_t>* prefix, std::vector<CompactChunk>* out) {
+    const uint32_t nw = (n_rows + 31) / 32;
+    prefix->assign((size_t)nw + 1, 0u);
+    for (uint32_t w = 0; w < nw; ++w) (*prefix)[w + 1] = (*prefix)[w] + (uint32_t)__builtin_popcount(live[w]);
+    out->clear();
+    const uint32_t* P = prefix->data();
+    uint32_t aw = 0;
+    while (aw < nw && P[aw + 1] - P[aw] == std::min(32u, n_rows - aw * 32u)) ++aw;      // full words: nothing moves
+    while (aw < nw) {
+        if (live[aw] == 0) { ++aw; continue; }
+        const uint32_t a = aw * 32u, gap = a - P[aw];
+        auto last_within = [&](uint32_t budget) {      // the largest word index bw >= aw with live(aw, bw) <= budget
+            return (uint32_t)(std::upper_bound(P + aw, P + nw + 1, P[aw] + budget) - P) - 1u;
+        };
+        uint32_t bw = last_within(gap);
+        uint32_t mode = 0;
+        if (!(bw > aw && (bw == nw || gap >= bounce_rows / 4))) { bw = last_within(bounce_rows); mode = 1; }
+        out->push_back({a, std::min(bw * 32u, n_rows), P[aw], mode});
+        aw = bw;
+    }
+}
+
+void store_stats(const Index* ix, uint64_t out[8]) {
+    const uint64_t cap = ix->cap_rows;
+    out[0] = ix->n_rows(); out[1] = ix->n_live; out[2] = cap;
+    out[3] = ix->d_rows ? cap * ((uint64_t)ix->ld * 4 + 3 * 4 + (ix->d_margin ? 4 : 0) + 8) + cap / 8 + (ix->d_rows16 ? cap * ix->ld * 2 : 0) : 0;
+    out[4] = ix->n_compactions; out[5] = ix->rows_reclaimed; out[6] = ix->last_compact_ns;
+    // [7]: the last compaction's device part (bits 0-39, ns: plan uploaded .. last row moved and the stream synchronised) and its
+    // chunk counts, saturating at 4095 (bits 40-51 through the bounce buffer, bits 52-63 moved directly)
+    out[7] = std::min<uint64_t>(ix->last_device_ns, (1ull << 40) - 1) | (std::min<uint64_t>(ix->last_chunks_bounce, 4095) << 40) |
+             (std::min<uint64_t>(ix->last_chunks_direct, 4095) << 52);
+}
+
+int compact_store(Index* ix, bool shrink, size_t* out_reclaimed) {
+    if (out_reclaimed) *out_reclaimed = 0;
+    int rc;
+    if ((rc = flush_upload(ix))) return rc;             // staged rows go up first: the whole store is compacted, d_live is current
+    const auto t0 = std::chrono::steady_clock::now();
+    hipStream_t s = ix->stream;
+    const uint32_t n = ix->n_uploaded, n_live = ix->n_live, ld = ix->ld;
+    if (n > n_live) {                                   // (n_live > 0: removing the last row resets the store)
+        std::vector<uint32_t> prefix;
+        std::vector<CompactChunk> plan;
+        const bool shadow = ix->d_rows16 != nullptr;
+        const uint32_t B = ix->bounce_rows_override ? std::max(32u, ix->bounce_rows_override & ~31u) : compact_bounce_rows(ld, shadow);
+        compact_plan(ix->live.data(), n, B, &prefix, &plan);
+        uint64_t n_direct = 0, n_bounce = 0;
+        for (auto& c : plan) (c.mode ? n_bounce : n_direct)++;
+        // every allocation happens before the first row moves
+        uint32_t* d_prefix = nullptr;
+        char* d_bounce = nullptr;
+        HIP_TRY(hipMalloc((void**)&d_prefix, prefix.size() * 4));
+        if (n_bounce && hipMalloc((void**)&d_bounce, (size_t)B * bounce_row_bytes(ld, shadow)) != hipSuccess) {
+            (void)hipFree(d_prefix);
+            return fail(VDB_ERR_DEVICE, "hipMalloc of the compaction bounce buffer (%zu bytes) failed", (size_t)B * bounce_row_bytes(ld, shadow));
+        }
+        // bounce layout: f32 rows | bf16 rows | ids | nd | alpha | beta | margin, B rows each
+        float* b_rows = reinterpret_cast<float*>(d_bounce);
+        uint16_t* b_rows16 = reinterpret_cast<uint16_t*>(d_bounce + (size_t)B * ld * 4);
+        char* b_cols = d_bounce + (size_t)B * ld * 4 + (shadow ? (size_t)B * ld * 2 : 0);
+        uint64_t* b_ids = reinterpret_cast<uint64_t*>(b_cols);
+        float* b_nd = reinterpret_cast<float*>(b_cols + (size_t)B * 8);
+        float *b_alpha = b_nd + B, *b_beta = b_nd + 2 * (size_t)B, *b_margin = b_nd + 3 * (size_t)B;
+        bool moved = false;
+        auto run = [&]() -> hipError_t {
+            hipError_t e = hipMemcpyAsync(d_prefix, prefix.data(), prefix.size() * 4, hipMemcpyHostToDevice, s);
+            if (e != hipSuccess) return e;
+            vdb::CompactMoveParams mp{};
+            mp.ld = ld; mp.lanes_log2 = vdb::compact_lanes_log2(ld);
+            for (const CompactChunk& c : plan) {
+                const uint32_t cnt = prefix[(c.b + 31) / 32] - prefix[c.a / 32];
+                // source: the store, rows [a, b)
+                mp.live = ix->d_live; mp.prefix = d_prefix; mp.row_begin = c.a; mp.row_end = c.b;
+                mp.src_rows = ix->d_rows; mp.src_rows16 = ix->d_rows16; mp.src_nd = ix->d_nd; mp.src_alpha = ix->d_alpha; mp.src_beta = ix->d_beta;
+                mp.src_margin = ix->d_margin; mp.src_ids = ix->d_row_ids;
+                if (c.mode == 0) {
+                    mp.dst_sub = 0;
+                    mp.dst_rows = ix->d_rows; mp.dst_rows16 = ix->d_rows16; mp.dst_nd = ix->d_nd; mp.dst_alpha = ix->d_alpha; mp.dst_beta = ix->d_beta;
+                    mp.dst_margin = ix->d_margin; mp.dst_ids = ix->d_row_ids;
+                    moved = true;
+                    vdb::launch_compact_move(mp, (uint32_t)ix->n_cu, s);
+                } else {
+                    mp.dst_sub = c.dst;
+                    mp.dst_rows = b_rows; mp.dst_rows16 = shadow ? b_rows16 : nullptr; mp.dst_nd = b_nd; mp.dst_alpha = b_alpha; mp.dst_beta = b_beta;
+                    mp.dst_margin = ix->d_margin ? b_margin : nullptr; mp.dst_ids = b_ids;
+                    vdb::launch_compact_move(mp, (uint32_t)ix->n_cu, s);
+                    // the contiguous copy down: bounce rows [0, cnt) -> store rows [dst, dst + cnt)
+                    mp.live = nullptr; mp.prefix = nullptr; mp.row_begin = 0; mp.row_end = cnt; mp.dst_sub = 0;
+                    mp.src_rows = b_rows; mp.src_rows16 = shadow ? b_rows16 : nullptr; mp.src_nd = b_nd; mp.src_alpha = b_alpha; mp.src_beta = b_beta;
+                    mp.src_margin = ix->d_margin ? b_margin : nullptr; mp.src_ids = b_ids;
+                    mp.dst_rows = ix->d_rows + (size_t)c.dst * ld; mp.dst_rows16 = shadow ? ix->d_rows16 + (size_t)c.dst * ld : nullptr;
+                    mp.dst_nd = ix->d_nd + c.dst; mp.dst_alpha = ix->d_alpha + c.dst; mp.dst_beta = ix->d_beta + c.dst;
+                    mp.dst_margin = ix->d_margin ? ix->d_margin + c.dst : nullptr; mp.dst_ids = ix->d_row_ids + c.dst;
+                    moved = true;
+                    vdb::launch_compact_move(mp, (uint32_t)ix->n_cu, s);
+                }
+                if ((e = hipGetLastError()) != hipSuccess) return e;
+            }
+            // the freed tail reads as zero again (padding columns of later adds, rows staged past the last one by ragged tiles)
+            moved = true;
+            if ((e = hipMemsetAsync(ix->d_rows + (size_t)n_live * ld, 0, (size_t)(n - n_live) * ld * 4, s)) != hipSuccess) return e;
+            if (ix->d_margin && (e = hipMemsetAsync(ix->d_margin + n_live, 0, (size_t)(n - n_live) * 4, s)) != hipSuccess) return e;
+            if (shadow && (e = hipMemsetAsync(ix->d_rows16 + (size_t)n_live * ld, 0, (size_t)(n - n_live) * ld * 2, s)) != hipSuccess) return e;
+            if ((e = hipMemsetAsync(ix->d_live, 0, (size_t)ix->cap_rows / 8, s)) != hipSuccess) return e;
+            return hipStreamSynchronize(s);
+        };
+        const auto t_dev = std::chrono::steady_clock::now();
+        const hipError_t e = run();
+        ix->last_device_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_dev).count();
+        if (e != hipSuccess) (void)hipStreamSynchronize(s);
+        (void)hipFree(d_prefix);
+        if (d_bounce) (void)hipFree(d_bounce);
+        if (e != hipSuccess) {
+            if (moved) ix->store_broken = true;         // rows may be half moved: nothing is served from this handle any more
+            return fail(VDB_ERR_DEVICE, "HIP error %d (%s) during the compaction%s", (int)e, hipGetErrorString(e),
+                        moved ? "; the handle is unusable" : "; nothing was moved");
+        }
+        // host bookkeeping: the survivors in their old order (rows below the first dead one keep their number)
+        uint32_t d = 0;
+        while (d < n && ix->is_live(d)) ++d;
+        bool mono = true;
+        for (uint32_t r = 1; r < d && mono; ++r) mono = ix->row_ids[r] > ix->row_ids[r - 1];
+        for (uint32_t r = d; r < n; ++r)
+            if (ix->is_live(r)) {
+                const uint64_t id = ix->row_ids[r];
+                if (d && id <= ix->row_ids[d - 1]) mono = false;
+                ix->row_ids[d] = id;
+                ix->id2row[id] = d;
+                ++d;
+            }
+        ix->row_ids.resize(n_live);
+        ix->live.assign((n_live + 31) / 32, 0xffffffffu);
+        if (n_live & 31) ix->live.back() = (1u << (n_live & 31)) - 1u;
+        ix->n_uploaded = n_live;
+        ix->ids_monotone = mono;
+        ix->rank_valid = false;
+        ix->zero_valid = false;
+        ix->sample16_n = ix->sample16_S = 0;            // keyed by rows uploaded; row positions changed
+        ix->live_dirty = true;
+        ix->n_compactions++;
+        ix->rows_reclaimed += n - n_live;
+        ix->last_chunks_direct = n_direct; ix->last_chunks_bounce = n_bounce;
+        if (out_reclaimed) *out_reclaimed = n - n_live;
+        if ((rc = flush_upload(ix))) return rc;         // d_live: all ones over [0, n_live)
+        ix->last_compact_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+    }
+    if (shrink && ix->cap_rows) {
+        const uint32_t cap = round_up(std::max<uint32_t>(ix->n_uploaded, 1024u), 256);      // what grow picks for a fresh index of this many rows
+        if (cap < ix->cap_rows && (rc = resize_store(ix, cap))) return rc;
+        if ((rc = flush_upload(ix))) return rc;         // the new d_live
+    }
+    return VDB_OK;
+}
+
+int flush(Index* ix) {
+    int rc = flush_upload(ix);
+    if (rc) return rc;
+    // vdb_flat_set_auto_compact: never while another search of this handle is in flight (its kernels read the rows)
+    if (ix->auto_compact > 0.0 && ix->n_uploaded > ix->n_live && !in_flight(ix) &&
+        (double)(ix->n_uploaded - ix->n_live) > ix->auto_compact * (double)ix->n_uploaded)
+        return compact_store(ix, false, nullptr);
     return VDB_OK;
 }
 

@@ -133,6 +133,20 @@ public:
         check(vdb_flat_add_bulk(h_, nullptr, first_id, rows, n, dim));
         for (size_t i = 0; i < n; ++i) vectors_[first_id + i] = Vector(std::vector<float>(rows + i * dim, rows + (i + 1) * dim));
     }
+    // no reference counterpart (a HashMap frees what it removes, flat_index.rs:43-46): take the device rows of removed and
+    // overwritten vectors back; results are identical before and after.  A write, like add / remove.
+    size_t compact(bool shrink = false) {
+        size_t got = 0;
+        check(vdb_flat_compact(h_, shrink ? 1 : 0, &got));
+        return got;
+    }
+    void set_auto_compact(double dead_fraction) { check(vdb_flat_set_auto_compact(h_, dead_fraction)); }
+    // [0] device rows [1] live rows [2] capacity [3] bytes [4] compactions [5] rows reclaimed [6] ns of the last one [7] see vdb_flat.h
+    std::vector<uint64_t> store_stats() const {
+        std::vector<uint64_t> out(8, 0);
+        check(vdb_flat_store_stats(h_, out.data()));
+        return out;
+    }
     vdb_flat_index* handle() const { return h_; }
     // no reference counterpart: tier selection (results are identical either way)
     void set_screen(int mode) { check(vdb_flat_set_screen(h_, mode)); }

@@ -219,6 +219,54 @@ class GpuFlatIndex(Index):
         if rc:
             _raise(rc)
 
+    # ---- reclaiming removed rows (include/vdb_flat.h vdb_flat_compact; no reference counterpart, results identical)
+    def compact(self, shrink=False):
+        """Move the live device rows down over the removed / overwritten ones, on the device and in place; returns the
+        number of device rows given back.  shrink=True also re-allocates the store to a fresh index's capacity.
+        A mutation: call it where add / remove are called (the caller's write lock)."""
+        got = ctypes.c_size_t(0)
+        rc = self._L.vdb_flat_compact(self._h, 1 if shrink else 0, ctypes.byref(got))
+        if rc:
+            _raise(rc)
+        return int(got.value)
+
+    def set_auto_compact(self, fraction):
+        """fraction > 0: every flush (so the next search after a write) compacts when more than that share of the uploaded
+        rows is dead.  0 (default): never."""
+        rc = self._L.vdb_flat_set_auto_compact(self._h, float(fraction))
+        if rc:
+            _raise(rc)
+
+    def store_stats(self):
+        """[0] device rows (live + dead, staged included), [1] live rows, [2] capacity in rows, [3] device bytes of the row
+        store, [4] compactions run, [5] rows reclaimed in total, [6] ns of the last compaction (host clock, whole call),
+        [7] ns of its device part, [8] chunks it moved directly, [9] chunks it moved through the bounce buffer."""
+        out = (ctypes.c_uint64 * 8)()
+        rc = self._L.vdb_flat_store_stats(self._h, out)
+        if rc:
+            _raise(rc)
+        v = [int(x) for x in out]
+        return v[:7] + [v[7] & ((1 << 40) - 1), v[7] >> 52, (v[7] >> 40) & 4095]
+
+    def debug_set_compact_bounce(self, rows):
+        """Test hook: the compaction's bounce buffer in rows (0 = default), so that small indexes exercise many chunks."""
+        rc = self._L.vdb_flat_debug_set_compact_bounce(self._h, int(rows))
+        if rc:
+            _raise(rc)
+
+    @staticmethod
+    def debug_compact_plan(live_words, n_rows, bounce_rows=0, ld=32):
+        """The chunk plan of a compaction for a live mask (u32 words, bit r & 31 of word r >> 5): an [n, 4] u32 array of
+        (first source row, end source row, first destination row, mode 0 direct / 1 bounce).  Needs no device."""
+        L = _ffi.lib()
+        lw = np.ascontiguousarray(live_words, dtype=np.uint32)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        n = int(L.vdb_flat_debug_compact_plan(lw.ctypes.data_as(u32p), int(n_rows), int(bounce_rows), int(ld), None, 0))
+        out = np.zeros((n, 4), dtype=np.uint32)
+        if n:
+            L.vdb_flat_debug_compact_plan(lw.ctypes.data_as(u32p), int(n_rows), int(bounce_rows), int(ld), out.ctypes.data_as(u32p), n)
+        return out
+
     def search_batch_device(self, q_ptr, nq, dim, k, out_ids_ptr, out_dists_ptr, out_counts_ptr, stream=0,
                             mask_ptr=0, mask_bits=0):
         """Everything resident in HBM: raw device pointers (uint64 ids, f32 dists, u32 counts)."""

@@ -123,11 +123,15 @@ class VectorStore:
     """VectorStore<I: Index>  (storage.rs:83-95).  `VectorStore(metric)` builds the GPU flat index
     where the reference's `VectorStore::new` builds a FlatIndex (storage.rs:99-101)."""
 
-    def __init__(self, metric=None, index=None, device=0):
+    def __init__(self, metric=None, index=None, device=0, auto_compact=0.0):
+        """auto_compact: dead-row fraction above which the GPU flat index reclaims removed rows by itself
+        (GpuFlatIndex.set_auto_compact; 0 = never, compact() by hand)."""
         if index is None:
             index = GpuFlatIndex(DistanceMetric(metric), device=device)
         assert isinstance(index, Index)
         self._index = index
+        if auto_compact:
+            index.set_auto_compact(auto_compact)         # (an index without it raises AttributeError: nothing to pass it to)
         self._id_to_internal = {}
         self._internal_to_id = {}
         self._metadata = {}
@@ -192,6 +196,14 @@ class VectorStore:
         self._index.remove(internal)
         self._mark_present(internal, False)
         return v
+
+    def compact(self):
+        """Reclaim the index rows that upserts and deletes left behind (every upsert above is remove(old) + add(new), so a
+        flat index on the GPU keeps one dead device row per upsert until this runs).  Internal ids do not change, so no map
+        of the store does.  Returns the number of rows given back; 0 for an index that frees rows as it removes them.
+        No reference counterpart (a HashMap-backed FlatIndex has nothing to reclaim); a write, like insert / delete."""
+        compact = getattr(self._index, "compact", None)
+        return int(compact()) if compact is not None else 0
 
     # ---- reads
     def _internal_of(self, id):
