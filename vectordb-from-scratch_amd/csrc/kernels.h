@@ -79,8 +79,7 @@ void launch_row_stats(const RowStatsParams& p, hipStream_t s);
 // bf16 shadow of rows [row_begin, row_end): v_cvt_pk_bf16_f32 (RNE) of every element of the padded row -- the rounding the
 // f32-row screening kernels apply to their fragments in registers
 void launch_rows_to_bf16(const float* rows, uint16_t* rows16, uint32_t ld, uint32_t row_begin, uint32_t row_end, hipStream_t s);
-// compact bf16 copy of the S = 2^shift sample rows of the screening tier: out[j] = bf16(rows[sample_row(j)]), j < S, the
-// mapping of the sample kernels (position (j & 255) * (S >> 8) + (j >> 8), row = (position * n_rows) >> shift)
+// compact bf16 copy of the S = 2^shift sample rows of the screening tier: out[j] = bf16(rows[screen_sample_row(j)]), j < S
 void launch_sample_to_bf16(const float* rows, uint32_t ld, uint32_t n_rows, uint32_t n_sample, uint32_t shift, uint16_t* out, hipStream_t s);
 
 // count live rows whose norm is exactly zero (Cosine: distance.rs:51-55)
@@ -142,7 +141,7 @@ struct SelectParams {
     // gather mode (n_sub > 0): the query's keys live in n_sub sub-pools of capacity capl,
     // keys[(q*n_sub + s)*capl + j], j < sub_counts[q*n_sub + s]
     const uint32_t* sub_counts; uint32_t n_sub; uint32_t capl;
-    uint32_t wg_major;                                 // 1: sub-pool i = wg*4 + r of query q has its count at (wg*256 + q)*4 + r and its keys at that * capl (bf16 tier)
+    uint32_t wg_major;                                 // 1: sub-pool i = wg*4 + r of query q has its count at VDB_BF16_SUBPOOL_R(wg, q, r) and its keys at that * capl (bf16 tier)
     size_t blk_keys, blk_cnts;                         // wg_major, more than 256 queries in one launch: query q lives in block q >> 8, whose pools start blk_keys keys / blk_cnts counts after the previous block's
     uint32_t kk;                                       // how many smallest keys to keep (<= 2048)
     uint64_t* out_keys; uint32_t out_stride;           // sorted ascending, padded with EMPTY_KEY
@@ -194,7 +193,34 @@ void launch_fused_dma(const FusedParams& p, uint32_t n_super, hipStream_t s);
 // three-image ring, barrier in the middle of a stage (kernels_fused_dma3.hip)
 void launch_fused_dma3(const FusedParams& p, uint32_t n_super, hipStream_t s);
 
-// ---------------------------------------------------------------- bf16 screening tier (kernels_fused_bf16.hip)
+// ---------------------------------------------------------------- bf16 screening tier (fused_bf16_common.h)
+// CANDIDATE-POOL LAYOUT, workgroup-major: workgroup wg of a filter pass owns, for query q of the pass's 256-query block, the
+// four private sub-pools r = 2 * row half + lane half.  Sub-pool (wg, q, r) has its count at pool_cnt[index] and its keys at
+// pool[index * capl ..].  Workgroup-major, so that the few scattered appends of one workgroup fall into ONE 2 MB region
+// instead of one region per query (256 regions 2 MB apart: every append then missed the CU's address-translation cache in
+// front of the row stream), and its 1024 counts are one 4 KB block written in whole lines.  The filter kernels, the select's
+// gather (SelectParams::wg_major) and pool_to_dense all go through this one function: a writer and a reader that disagree
+// lose candidates silently.
+__host__ __device__ constexpr size_t fused_bf16_subpool(size_t wg, uint32_t q, uint32_t row_half, uint32_t lane_half) { return ((wg * 256 + q) * 2 + row_half) * 2 + lane_half; }
+// The same index from r = 2 * row half + lane half, for the readers (which walk r = 0..3) and the wide kernel (which derives r
+// on its rare path).  A macro whose R lands unparenthesised at the end of the sum, on purpose: the wide kernel sits at the
+// 256-VGPR limit, and every function form of this line -- forwarding to the one above included -- reordered its integer
+// arithmetic and with it the register allocation of the whole kernel (tools/isa_diff.py).  The static_assert ties the two.
+#define VDB_BF16_SUBPOOL_R(WG, Q, R) (((size_t)(WG) * 256 + (Q)) * 4 + R)
+static_assert(fused_bf16_subpool(7, 201, 1, 0) == VDB_BF16_SUBPOOL_R(7, 201, 2) && fused_bf16_subpool(7, 201, 1, 1) == VDB_BF16_SUBPOOL_R(7, 201, 3), "one layout");
+__host__ __device__ inline uint32_t fused_bf16_subpools_per_query(uint32_t n_wg) { return 4u * n_wg; }
+// SAMPLE INDEX -> DEVICE ROW.  The S = n_sample = 2^shift <= n_rows sample positions are spread evenly over the rows
+// ((pos * n) >> shift), and CONSECUTIVE positions go to DIFFERENT tiles (index j = tile*256 + tile-row sits at position
+// tile-row*tiles + tile): when near neighbours are stored next to each other (data ordered by cluster) their sample rows then
+// land in different groups, each contributes its own group minimum, and the threshold stays as tight as on shuffled data (with
+// consecutive positions in one tile a 500-row cluster was represented by 4 minima, the threshold came from far rows and
+// thousands of keys overflowed the pools).  sample_block != 0 (diagnostics): tiles of sample_block contiguous rows.  The
+// sample kernels and the compact sample copy (launch_sample_to_bf16) are only valid together if they all use this function.
+__host__ __device__ inline uint32_t screen_sample_row(uint32_t j, uint32_t n_sample, uint32_t shift, uint32_t n_rows, uint32_t sample_block = 0) {
+    if (sample_block) return (j >> 8) * sample_block + (j & 255u);
+    const uint32_t pos = (j & 255u) * (n_sample >> 8) + (j >> 8);
+    return (uint32_t)(((uint64_t)pos * n_rows) >> shift);
+}
 struct FusedBf16Params {
     const float* rows; uint32_t ld; uint32_t n_rows;
     const uint16_t* rows16;                            // bf16 shadow of `rows`, same pitch (kernels_fused_s16.hip; null unless vdb_flat_set_shadow and ld % 64 == 0)
@@ -208,24 +234,23 @@ struct FusedBf16Params {
     // "No score of this launch can be NaN" (fused_no_nan below): the index scalars (max |d|^2, smallest positive |d|^2 under
     // Cosine) and the largest query norm of the search as f32 bits (query_prep: status block word 2).  May be null (= unknown).
     const uint32_t* scalars; const uint32_t* qmax_bits;
-    // filter mode: keys with score <= thr[q] go to the private sub-pool
-    //   sub = ((wg*256 + q)*2 + row half)*2 + lane half ; keys at pool[sub*capl ..], count at pool_cnt[sub]  (workgroup-major)
+    // filter mode: keys with score <= thr[q] go to the lane's private sub-pool, fused_bf16_subpool(wg, q, row half, lane half)
     const float* thr;                                  // [256]
     uint64_t* pool; uint32_t* pool_cnt; uint32_t capl;
     uint32_t n_wg;                                     // row ranges = grid.x
     // the WIDE filter kernel (kernels_fused_bf16w.hip) serves two consecutive 256-query blocks per launch: qb / thr / qg cover
     // 512 queries, block b's pools start at pool + b * pool_block_stride (keys) and pool_cnt + b * cnt_block_stride
     size_t pool_block_stride, cnt_block_stride;
-    // sample mode: n_sample = 2^sample_shift <= n_rows, sample j -> row (j*n_rows) >> sample_shift; per query and
-    // group of 64 sample rows the smallest key
+    // sample mode: n_sample = 2^sample_shift <= n_rows, sample j -> screen_sample_row(j); per query and group of 64 sample
+    // rows the smallest key
     uint32_t n_sample, sample_shift, sample_block; uint64_t* minkeys; uint32_t minkey_stride;   // minkeys[q*minkey_stride + group]
     uint32_t ablate;                                   // diagnostics only (VDB_BF16_ABLATE): 1 skip LDS reads + MFMAs (unpipelined kernel only), 2 skip the row DMA, 4 skip the query DMA, 8 skip the epilogue, 16 (pipelined kernel) thresholds = -inf: nothing passes the filter
 };
 #ifdef VDB_DIAG
 void launch_fused_bf16(const FusedBf16Params& p, hipStream_t s);      // unpipelined filter pass (diagnostics build: A/B against bf16p)
 #endif
-void launch_sample_bf16(const FusedBf16Params& p, uint32_t n_cu, hipStream_t s);
-void launch_fused_bf16p(const FusedBf16Params& p, hipStream_t s);     // kernels_fused_bf16p.hip: the filter pass, software-pipelined (default)
+void launch_sample_bf16(const FusedBf16Params& p, hipStream_t s);
+void launch_fused_bf16p(const FusedBf16Params& p, hipStream_t s);     // the filter pass, software-pipelined (default)
 void launch_fused_bf16w(const FusedBf16Params& p, hipStream_t s);     // kernels_fused_bf16w.hip: the WIDE filter pass, 128 rows x 512 queries per workgroup (batches above 256 queries)
 uint32_t fused_bf16w_tile_rows();
 // With every row norm and query norm in [2^-40, 2^40] (zero allowed) no accumulator can overflow and no alpha / beta is
@@ -242,7 +267,6 @@ __device__ inline bool fused_no_nan(const uint32_t* scalars, const uint32_t* qma
 void launch_fused_s16(const FusedBf16Params& p, hipStream_t s);       // kernels_fused_s16.hip: the filter pass over p.rows16 (ld % 64 == 0)
 void launch_sample_s16(const FusedBf16Params& p, hipStream_t s);      // the sample pass over a COMPACT bf16 copy of the sample rows (p.rows16 = the copy)
 uint32_t fused_bf16_tile_rows();
-uint32_t fused_bf16_subpools_per_query(uint32_t n_wg);
 uint32_t fused_bf16_sample_groups(uint32_t n_sample);
 
 // compact re-run of uncertified queries: gather padded query rows / norms, scatter results back

@@ -264,8 +264,7 @@ __global__ __launch_bounds__(256) void sample_to_bf16_kernel(const float* __rest
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;     // 8 elements per thread
     if (i >= (size_t)n_sample * ld8) return;
     const uint32_t j = (uint32_t)(i / ld8), c8 = (uint32_t)(i % ld8);
-    const uint32_t pos = (j & 255u) * (n_sample >> 8) + (j >> 8);
-    const uint32_t row = (uint32_t)(((uint64_t)pos * n_rows) >> shift);
+    const uint32_t row = screen_sample_row(j, n_sample, shift, n_rows);
     const float4* src = reinterpret_cast<const float4*>(rows + (size_t)row * ld8 * 8) + 2 * c8;
     const float4 lo = src[0], hi = src[1];
     typedef __attribute__((ext_vector_type(2))) float f2;
@@ -393,7 +392,8 @@ void launch_query_prep(const QueryPrepParams& p, hipStream_t s) {
 // produce bit-identical scores and the sample's kk-th score is a valid inclusive
 // threshold there.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t sample_row(uint32_t j, uint32_t n_sample, uint32_t n_rows) {
+// (the f32 tier's sample: every (n / S)-th row -- not the screening tier's screen_sample_row)
+__device__ __forceinline__ uint32_t dense_sample_row(uint32_t j, uint32_t n_sample, uint32_t n_rows) {
     return n_sample >= n_rows ? j : (uint32_t)(((uint64_t)j * n_rows) / n_sample);
 }
 
@@ -405,7 +405,7 @@ __global__ __launch_bounds__(256) void dense_scores_kernel(DenseParams p) {
     if (tile >= ntiles) return;                       // whole wave exits together
     uint32_t sj = tile * 32 + c;
     if (sj >= p.n_sample) sj = p.n_sample - 1;
-    const uint32_t srow = sample_row(sj, p.n_sample, p.n_rows);
+    const uint32_t srow = dense_sample_row(sj, p.n_sample, p.n_rows);
     const float* ap = p.rows + (size_t)srow * p.ld + 4 * h;
     const float* bp = p.qp + (size_t)(blockIdx.y * 32 + c) * p.ld + 4 * h;
     f32x16 acc;
@@ -448,7 +448,7 @@ __global__ __launch_bounds__(256) void dense_scores_kernel(DenseParams p) {
     for (int r = 0; r < 16; ++r) {
         uint32_t j = tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
         if (j < p.n_sample) {
-            uint32_t row = sample_row(j, p.n_sample, p.n_rows);
+            uint32_t row = dense_sample_row(j, p.n_sample, p.n_rows);
             bool ok = p.rowmask ? ((p.rowmask[row >> 5] >> (row & 31)) & 1u) : true;
             float sc = fmaf(acc[r], p.alpha[row], p.beta[row]);
             out[j] = ok ? make_key(sc, row) : EMPTY_KEY;
@@ -517,7 +517,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(SelectParams p) {
         for (uint32_t i0 = 0; i0 < p.n_sub; i0 += SEL_THREADS) {
             const uint32_t i = i0 + tid;
             // (bf16 tier: counts workgroup-major like the keys -- four consecutive threads read one workgroup's 16 bytes)
-            uint32_t c = i < p.n_sub ? (p.wg_major ? wg_cnts[((size_t)(i >> 2) * 256u + ql) * 4u + (i & 3u)] : sc[i]) : 0u;
+            uint32_t c = i < p.n_sub ? (p.wg_major ? wg_cnts[VDB_BF16_SUBPOOL_R(i >> 2, ql, (i & 3u))] : sc[i]) : 0u;
             if (c > p.capl) { c = p.capl; over = true; }
             uint32_t incl = c;
             for (int o = 1; o < 64; o <<= 1) { uint32_t t = __shfl_up(incl, o); if ((int)lane >= o) incl += t; }
@@ -525,8 +525,8 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(SelectParams p) {
             if (lane == 63 && incl) wbase = atomicAdd(&sN, incl);
             wbase = __shfl(wbase, 63);
             uint32_t pos = wbase + incl - c;
-            // (bf16 tier: keys workgroup-major, sub-pool i = wg*4 + r of query q at ((wg*256 + q)*4 + r)*capl)
-            const uint64_t* src = p.wg_major ? wg_keys + (((size_t)(i >> 2) * 256u + ql) * 4u + (i & 3u)) * p.capl : base + (size_t)i * p.capl;
+            // (bf16 tier: keys workgroup-major as well, sub-pool i = wg*4 + r of query q)
+            const uint64_t* src = p.wg_major ? wg_keys + VDB_BF16_SUBPOOL_R(i >> 2, ql, (i & 3u)) * p.capl : base + (size_t)i * p.capl;
             for (uint32_t j0 = 0; j0 < c; j0 += 4) {
                 uint64_t k[4];
 #pragma unroll
@@ -925,9 +925,9 @@ __device__ __forceinline__ float score_cut(const RerankParams& p, uint32_t q, do
 __global__ __launch_bounds__(256) void pool_to_dense_kernel(const uint64_t* pool, const uint32_t* pool_cnt, uint32_t n_sub,
                                                             uint32_t capl, uint32_t n_rows, float* dense) {
     const uint32_t q = blockIdx.y, i = blockIdx.x;                 // sub-pool i = wg*4 + r of query q
-    uint32_t c = pool_cnt[((size_t)(i >> 2) * 256u + q) * 4u + (i & 3u)];
+    uint32_t c = pool_cnt[VDB_BF16_SUBPOOL_R(i >> 2, q, (i & 3u))];
     if (c > capl) c = capl;
-    const uint64_t* src = pool + (((size_t)(i >> 2) * 256u + q) * 4u + (i & 3u)) * capl;
+    const uint64_t* src = pool + VDB_BF16_SUBPOOL_R(i >> 2, q, (i & 3u)) * capl;
     for (uint32_t j = threadIdx.x; j < c; j += blockDim.x) {
         const uint64_t raw = src[j];
         const uint32_t row = (uint32_t)raw;

@@ -1,11 +1,5 @@
-// kernels_fused_bf16.hip -- the SCREENING tier of the search: ranking scores of every row against up to 256
-// queries on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16, 16x the f32-input MFMA rate), so that the pass
-// over the f32 rows is bound by HBM, not by arithmetic.  The scores only RANK rows; results stay the
-// reference's exact f32 distances (distance.rs:37-73) because
-//   * the candidates this kernel keeps are re-ranked with the reference's own f32 operation order, and
-//   * the re-rank certifies, from a rigorous bound on the bf16 rounding error (|dot_bf16 - dot| <=
-//     2^-8 |q||d| (1 + small), DESIGN.md "screening tier"), that no excluded row can enter the top k;
-//     a query that cannot be certified is re-done by the f32 MFMA tier and, failing that, the exact scan.
+// kernels_fused_bf16.hip -- the SAMPLE pass of the screening tier over the f32 rows (fused_bf16_common.h documents the
+// method), and, in the diagnostics build, the UNPIPELINED filter pass (VDB_FUSED_PIPE=0: A/B against kernels_fused_bf16p.hip).
 //
 // Rows stay f32 in HBM (the byte layout of persistence/mmap.rs:77-84).  A stage is 32 K-elements of
 // 256 rows (f32, 32 KB) and of 256 queries (bf16, prepared once per batch by query_prep, 16 KB), brought
@@ -20,53 +14,31 @@
 // complete in order, so "at most 6 outstanding" implies every piece of stage s has landed whatever other
 // loads or stores (pool appends) the wave issued since.
 //
-// The same kernel body runs in SAMPLE mode over S sample rows: instead of filtering by a threshold, every
-// lane keeps the smallest (score,row) key of the 64 rows it owns per query ("group minimum").  The kp-th
-// smallest of a query's group minima is an inclusive threshold that at least kp rows meet, and the
+// SAMPLE mode runs the same body over the S sample rows, one tile per workgroup: instead of filtering by a threshold,
+// every lane keeps the smallest (score,row) key of the 64 rows it owns per query ("group minimum").  The
 // instruction sequence per (row, query) is identical in both modes, so the scores agree bit for bit.
-// NOTE: the FILTER pass runs by default in its software-pipelined form, kernels_fused_bf16p.hip (same tile, same DMA
-// plan, same epilogue; one mid-stage barrier per stage); this file keeps the sample pass and the unpipelined filter
-// pass (VDB_FUSED_PIPE=0).
-#include "kernels.h"
-
-#include <type_traits>
+//
+// INSTANCES.  Release build: fused_bf16_kernel<true, false>, the sample pass, and nothing else.  Diagnostics build: also
+// <false, false> and <false, true>, the unpipelined filter pass without and with lower-bound scores.  The sample never
+// ranks by lower-bound scores (launch_sample_bf16 says why), so <true, true> does not exist.
+#include "fused_bf16_common.h"
 
 namespace vdb {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 constexpr int NW = 8, NT = NW * 64;
 constexpr int TR = 256;                          // rows per tile
 constexpr int TQ = 256;                          // queries per tile
-constexpr int A_ROWB = 128;                      // 32 f32 per row and stage
-constexpr int B_ROWB = 64;                       // 32 bf16 per query and stage
-constexpr int A_BYTES = TR * A_ROWB;             // 32 KB
-constexpr int B_BYTES = TQ * B_ROWB;             // 16 KB
+constexpr int A_BYTES = TR * A_ROWB;             // 32 KB: 32 f32 per row and stage
+constexpr int B_BYTES = TQ * B_ROWB;             // 16 KB: 32 bf16 per query and stage
 constexpr int STAGE_BYTES = A_BYTES + B_BYTES;   // 48 KB
 constexpr int MT = 4, QT = 2;                    // MFMA tiles per wave: 4 x 32 rows, 2 x 32 queries
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-    f32x2 v = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));   // v_cvt_pk_bf16_f32 (RNE)
-}
-__device__ __forceinline__ bf16x8 cvt8(const float4& lo, const float4& hi) {
-    u32x4 r = {pk_bf16(lo.x, lo.y), pk_bf16(lo.z, lo.w), pk_bf16(hi.x, hi.y), pk_bf16(hi.z, hi.w)};
-    return __builtin_bit_cast(bf16x8, r);
-}
 }  // namespace
 
-// MARGIN: lower-bound scores for Dot / Euclid, exactly as in kernels_fused_bf16p.hip (same two fmas per element, so the
-// sample's group minima and the filter pass agree bit for bit).
+// MARGIN (filter mode only): lower-bound scores for Dot / Euclid, one more fma per element on the plain score.
 template <bool SAMPLE, bool MARGIN>
 __global__ __launch_bounds__(NT, 2) void fused_bf16_kernel(FusedBf16Params p) {
+    static_assert(!(SAMPLE && MARGIN), "the sample pass ranks by the plain score");
     // three DISTINCT LDS objects, each access names its image at compile time (see kernels_fused_dma3.hip)
     __shared__ __attribute__((aligned(16))) char sImg0[STAGE_BYTES];
     __shared__ __attribute__((aligned(16))) char sImg1[STAGE_BYTES];
@@ -80,7 +52,7 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16_kernel(FusedBf16Params p) {
     // registers per lane (with those the sample instance spilled in its last stages, and every scratch reload is a
     // vmcnt(0) -- a drain of the DMA pipeline); each lane reads back only what it wrote
     __shared__ uint32_t sRow[SAMPLE ? 32 * 64 : 1];
-    __shared__ __attribute__((aligned(16))) float sMarg[MARGIN ? (SAMPLE ? TR : 2 * TR) : 4];
+    __shared__ __attribute__((aligned(16))) float sMarg[MARGIN ? 2 * TR : 4];
     __shared__ float sG[MARGIN ? TQ : 1];
 
     const uint32_t tid = threadIdx.x, lane = tid & 63;
@@ -117,14 +89,11 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16_kernel(FusedBf16Params p) {
     size_t sub_a = 0, sub_b = 0;
     float thr_a = 0.f, thr_b = 0.f;
     if (!SAMPLE) {
-        sub_a = (((size_t)blockIdx.x * TQ + q_a) * 2 + wr) * 2 + h;          // counts workgroup-major too (kernels_fused_bf16p.hip)
-        sub_b = (((size_t)blockIdx.x * TQ + q_b) * 2 + wr) * 2 + h;
-        // The pool KEYS are laid out workgroup-major -- slot ((wg*256 + q)*4 + row half*2 + lane half)*capl -- so that the
-        // few scattered appends of one workgroup fall into ONE 2 MB region instead of one region per query (256 regions
-        // 2 MB apart: every append then missed the CU's address-translation cache in front of the row stream); the
-        // select's gather knows both layouts (SelectParams::wg_major).
-        pool_a = p.pool + ((((size_t)blockIdx.x * TQ + q_a) * 2 + wr) * 2 + h) * p.capl;
-        pool_b = p.pool + ((((size_t)blockIdx.x * TQ + q_b) * 2 + wr) * 2 + h) * p.capl;
+        // the lane's two private sub-pools, counts and keys (kernels.h: candidate-pool layout)
+        sub_a = fused_bf16_subpool(blockIdx.x, q_a, wr, h);
+        sub_b = fused_bf16_subpool(blockIdx.x, q_b, wr, h);
+        pool_a = p.pool + fused_bf16_subpool(blockIdx.x, q_a, wr, h) * p.capl;
+        pool_b = p.pool + fused_bf16_subpool(blockIdx.x, q_b, wr, h) * p.capl;
         thr_a = p.thr[q_a];
         thr_b = p.thr[q_b];
         // consume the two loads here: a first use inside the stage loop would get a compiler-inserted vmcnt(0)
@@ -138,18 +107,7 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16_kernel(FusedBf16Params p) {
     }
     const uint32_t total = ntiles * KS;
     const uint32_t last_row = p.n_rows - 1;
-    // sample index -> device row.  The S sample positions are spread evenly over the rows ((pos * n) >> shift), and
-    // CONSECUTIVE positions go to DIFFERENT tiles (index j = tile*256 + tile-row sits at position tile-row*tiles + tile):
-    // when near neighbours are stored next to each other (data ordered by cluster) their sample rows then land in
-    // different groups, each contributes its own group minimum, and the threshold stays as tight as on shuffled data
-    // (with consecutive positions in one tile a 500-row cluster was represented by 4 minima, the threshold came from far
-    // rows and thousands of keys overflowed the pools).  Block mode (sample_block != 0, diagnostics): tiles of
-    // contiguous rows.
-    auto sample_row_of = [&](uint32_t j) -> uint32_t {
-        if (p.sample_block) return (j >> 8) * p.sample_block + (j & 255u);
-        const uint32_t pos = (j & 255u) * (p.n_sample >> 8) + (j >> 8);
-        return (uint32_t)(((uint64_t)pos * p.n_rows) >> p.sample_shift);
-    };
+    auto sample_row_of = [&](uint32_t j) -> uint32_t { return screen_sample_row(j, p.n_sample, p.sample_shift, p.n_rows, p.sample_block); };
     const char* __restrict__ rows_b = reinterpret_cast<const char*>(p.rows);
     const char* __restrict__ bbase = reinterpret_cast<const char*>(p.qb);
 
@@ -159,7 +117,6 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16_kernel(FusedBf16Params p) {
     // fragment reads below are bank-conflict free: data chunk x of row r sits at position x ^ ((r>>1)&7),
     // data chunk x of query r at position x ^ ((r>>2)&3); the filling lane fetches the permuted source chunk.
     const uint32_t a_pr = lane >> 3, a_pp = lane & 7;
-    const uint32_t b_pr = lane >> 2, b_pp = lane & 3;
     uint32_t a_chunk[4];                                                // source byte offset inside the 128-B stage
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -169,7 +126,6 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16_kernel(FusedBf16Params p) {
     // (the queries are stored by query_prep in exactly this image order, one 16 KB image per K stage: a wave's
     // query piece is 1 KB of CONTIGUOUS global memory -- 8 full 128-byte requests instead of 16 scattered 64-byte ones)
     const uint32_t ob[2] = {(2 * w) * 1024 + lane * 16, (2 * w + 1) * 1024 + lane * 16};
-    (void)b_pr; (void)b_pp;
     const char* aptr[4];                                                // row pieces of the tile being fetched
     auto tile_rows_of = [&](uint32_t t, uint32_t rt) -> uint32_t {      // device row of tile-row rt of local tile t
         if (SAMPLE) {
@@ -193,19 +149,6 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16_kernel(FusedBf16Params p) {
         if (SAMPLE) return rows_b + (size_t)sRow[(4 * w + j) * 64 + lane] * ld * 4 + a_chunk[j];
         return aptr[j];
     };
-    // The LDS-DMA is issued from inline asm, not through __builtin_amdgcn_global_load_lds: hipcc's waitcnt pass
-    // tracks the builtin as a pending LDS write and, at the loop header of the 3-stage ring, cannot bound how many
-    // vector-memory operations followed the fill of the image about to be read -- it then puts a vmcnt(0) in front
-    // of that stage's first ds_read, which drains the two-stage DMA pipeline.  All ordering between the DMA and the
-    // LDS reads is done by hand here (counted s_waitcnt + s_barrier at the top of each stage); compiler-inserted
-    // vmcnt waits for ordinary loads stay correct because not counting these instructions only makes them wait longer.
-#define VDB_DMA(GP, IMG, LOFF)                                                                         \
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"                     \
-                 :: "s"((uint32_t)(uintptr_t)(lds_ptr_t)((IMG) + (LOFF))), "v"((const void*)(GP)) : "memory", "m0")
-    // rows are read once per launch: non-temporal, so that they do not push the queries out of the L2
-#define VDB_DMA_NT(GP, IMG, LOFF)                                                                      \
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt"                  \
-                 :: "s"((uint32_t)(uintptr_t)(lds_ptr_t)((IMG) + (LOFF))), "v"((const void*)(GP)) : "memory", "m0")
 #define VDB_ISSUE(IMG, KSI)                                                                            \
     {                                                                                                  \
         const uint32_t la_ = (4 * w) * 1024;                                                           \
@@ -228,9 +171,6 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16_kernel(FusedBf16Params p) {
     // ---- row constants of a tile, one tile ahead, by LDS-DMA (4 bytes per lane): waves 0-3 fetch alpha and the mask
     // word of rows 64(w&3)..+63, waves 4-7 fetch beta.  Issued BEFORE the stage's row/query pieces, so the counted
     // wait at the top of the next stage covers them.
-#define VDB_DMA4(GP, LP)                                                                               \
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off"                        \
-                 :: "s"((uint32_t)(uintptr_t)(lds_ptr_t)(LP)), "v"((const void*)(GP)) : "memory", "m0")
     auto issue_consts = [&](uint32_t t) {
         const uint32_t par = t & 1u;
         const uint32_t cr = 64 * (w & 3);                              // first tile-row of this wave's chunk
@@ -281,10 +221,7 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16_kernel(FusedBf16Params p) {
         if (fks == KS) { fks = 0; ++ftile; if (ftile < ntiles) set_tile_ptrs(ftile); }
     }
 
-    // STEADY: the caller guarantees st + 2 < total, so the wait and the DMA issue are unconditional.  That is not a
-    // micro-optimisation: with a conditional issue hipcc's waitcnt pass sees a path on which nothing follows the
-    // previous fill of the image about to be read and puts a vmcnt(0) in front of the first ds_read of every
-    // third stage, which drains the two-stage DMA pipeline.
+    // STEADY: the caller guarantees st + 2 < total, so the wait and the DMA issue are unconditional (VDB_RING3).
     auto run_stage = [&](uint32_t st, auto buf_tag, auto steady_tag) {
         constexpr int BUF = decltype(buf_tag)::value;
         constexpr bool STEADY = decltype(steady_tag)::value;
@@ -361,7 +298,7 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16_kernel(FusedBf16Params p) {
             const float* be = sBeta + par * TR + wr * 128 + 4 * h;
             const float* mg = sMarg + (MARGIN ? par * TR + wr * 128 + 4 * h : 0);
             float ng_a = 0.f, ng_b = 0.f;
-            if (MARGIN) { ng_a = -sG[q_a]; ng_b = -sG[q_b]; }
+            if (!SAMPLE && MARGIN) { ng_a = -sG[q_a]; ng_b = -sG[q_b]; }
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 const uint32_t vbits = (uint32_t)(val[i >> 1] >> (32 * (i & 1) + 4 * h));
@@ -375,7 +312,7 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16_kernel(FusedBf16Params p) {
                     float sa2 = fmaf(acc[i][0][4 * j + 2], a4.z, b4.z), sa3 = fmaf(acc[i][0][4 * j + 3], a4.w, b4.w);
                     float sb0 = fmaf(acc[i][1][4 * j + 0], a4.x, b4.x), sb1 = fmaf(acc[i][1][4 * j + 1], a4.y, b4.y);
                     float sb2 = fmaf(acc[i][1][4 * j + 2], a4.z, b4.z), sb3 = fmaf(acc[i][1][4 * j + 3], a4.w, b4.w);
-                    if (MARGIN) {
+                    if (!SAMPLE && MARGIN) {
                         const float4 m4 = *reinterpret_cast<const float4*>(mg + i * 32 + 8 * j);
                         sa0 = fmaf(ng_a, m4.x, sa0); sa1 = fmaf(ng_a, m4.y, sa1); sa2 = fmaf(ng_a, m4.z, sa2); sa3 = fmaf(ng_a, m4.w, sa3);
                         sb0 = fmaf(ng_b, m4.x, sb0); sb1 = fmaf(ng_b, m4.y, sb1); sb2 = fmaf(ng_b, m4.z, sb2); sb3 = fmaf(ng_b, m4.w, sb3);
@@ -436,32 +373,15 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16_kernel(FusedBf16Params p) {
         if (ks == KS) { ks = 0; ++tile; }
     };
 
-    using B0 = std::integral_constant<int, 0>;
-    using B1 = std::integral_constant<int, 1>;
-    using B2 = std::integral_constant<int, 2>;
-    uint32_t st = 0;
-    for (; st + 4 < total; st += 3) {                                   // stage index mod 3 == image index
-        run_stage(st, B0{}, std::true_type{});
-        run_stage(st + 1, B1{}, std::true_type{});
-        run_stage(st + 2, B2{}, std::true_type{});
-    }
-    // the last one to four stages: conditional issue
-    if (st < total) { run_stage(st, B0{}, std::false_type{}); ++st; }
-    if (st < total) { run_stage(st, B1{}, std::false_type{}); ++st; }
-    if (st < total) { run_stage(st, B2{}, std::false_type{}); ++st; }
-    if (st < total) { run_stage(st, B0{}, std::false_type{}); ++st; }
+    VDB_RING3(run_stage, total, 4)
     if (!SAMPLE) {
         p.pool_cnt[sub_a] = pcnt_a;
         p.pool_cnt[sub_b] = pcnt_b;
     }
-#undef VDB_DMA
-#undef VDB_DMA_NT
-#undef VDB_DMA4
 #undef VDB_ISSUE
 }
 
 uint32_t fused_bf16_tile_rows() { return TR; }
-uint32_t fused_bf16_subpools_per_query(uint32_t n_wg) { return 4u * n_wg; }
 uint32_t fused_bf16_sample_groups(uint32_t n_sample) { return 4u * ((n_sample + TR - 1) / TR); }
 
 #ifdef VDB_DIAG
@@ -470,10 +390,9 @@ void launch_fused_bf16(const FusedBf16Params& p, hipStream_t s) {
     else hipLaunchKernelGGL((fused_bf16_kernel<false, false>), dim3(p.n_wg), dim3(NT), 0, s, p);
 }
 #endif
-void launch_sample_bf16(const FusedBf16Params& p, uint32_t n_cu, hipStream_t s) {
+void launch_sample_bf16(const FusedBf16Params& p, hipStream_t s) {
     const uint32_t stiles = (p.n_sample + TR - 1) / TR;
     if (!stiles) return;
-    (void)n_cu;
     // The sample ALWAYS ranks by the plain score, also when the filter pass ranks by lower-bound scores (p.margin): its
     // instance with the margin fma spills (scratch reloads drain the DMA pipeline), and it does not need it -- any
     // threshold is valid, and the select shifts this one by g_q * (smallest row margin of the index), after which every

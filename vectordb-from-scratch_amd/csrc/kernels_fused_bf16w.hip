@@ -1,8 +1,8 @@
 // kernels_fused_bf16w.hip -- the WIDE filter pass of the screening tier: 128 rows x 512 queries per workgroup.
 //
-// Same method, same stage loop and the same per-wave work as kernels_fused_bf16p.hip (which documents them): eight waves, each
-// 128 rows x 64 queries = 4 x 2 MFMA tiles of v_mfma_f32_32x32x16_bf16, f32 rows rounded to bf16 in registers, a 3-image
-// LDS-DMA ring with one mid-stage barrier per K stage, the threshold filter in the per-tile epilogue.  What changes is the
+// The method of fused_bf16_common.h and the stage loop of kernels_fused_bf16p.hip: eight waves, f32 rows rounded to bf16 in
+// registers, a 3-image LDS-DMA ring with one mid-stage barrier per K stage, the threshold filter in the per-tile epilogue.
+// What changes is the
 // SHAPE of the workgroup's tile: the eight waves sit side by side along the QUERY axis (wave w owns queries 64w .. 64w+63 of
 // 512) and all of them read the same 128 rows, where the 256 x 256 kernel has two row halves x four query quarters.  A stage
 // image is 16 KB of rows + 32 KB of queries (there: 32 + 16), so a fetched row tile serves 512 queries and a batch of B > 256
@@ -16,47 +16,21 @@
 // workgroup-major pools (FusedBf16Params::pool_block_stride), of which this kernel fills sub-pools 0 and 1 (lane halves) and
 // zeroes the counts of 2 and 3, so the select's gather, the re-rank and everything downstream are the 256-query code unchanged.
 // Scores are bit-identical to the other filter kernels' (same operands, same MFMA order per accumulator).
-#include "kernels.h"
-
-#include <type_traits>
+#include "fused_bf16_common.h"
 
 namespace vdb {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 constexpr int NW = 8, NT = NW * 64;
 constexpr int TR = 128;                          // rows per tile
 constexpr int TQ = 512;                          // queries per tile
 constexpr int QB = 256;                          // queries per block of the search (pools, query image)
-constexpr int A_ROWB = 128;                      // 32 f32 per row and stage
-constexpr int B_ROWB = 64;                       // 32 bf16 per query and stage
-constexpr int A_BYTES = TR * A_ROWB;             // 16 KB
-constexpr int B_BYTES = TQ * B_ROWB;             // 32 KB
+constexpr int A_BYTES = TR * A_ROWB;             // 16 KB: 32 f32 per row and stage
+constexpr int B_BYTES = TQ * B_ROWB;             // 32 KB: 32 bf16 per query and stage
 constexpr int BQ_BYTES = QB * B_ROWB;            // 16 KB: one block's query image of a K stage in global memory
 constexpr int STAGE_BYTES = A_BYTES + B_BYTES;   // 48 KB
 constexpr int MT = 2, QT = 4;                    // MFMA tiles per wave: 2 x 32 rows, 4 x 32 queries
 
-#ifdef VDB_DIAG
-constexpr bool kDiag = true;                     // ablate bits 32 / 64 below exist in the diagnostics build only
-#else
-constexpr bool kDiag = false;
-#endif
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-    f32x2 v = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));   // v_cvt_pk_bf16_f32 (RNE)
-}
-__device__ __forceinline__ bf16x8 cvt8(const float4& lo, const float4& hi) {
-    u32x4 r = {pk_bf16(lo.x, lo.y), pk_bf16(lo.z, lo.w), pk_bf16(hi.x, hi.y), pk_bf16(hi.z, hi.w)};
-    return __builtin_bit_cast(bf16x8, r);
-}
 }  // namespace
 
 // MARGIN (Dot / Euclid): the kernel ranks by the LOWER-BOUND score fma(-g_q, margin_row, score) -- see FusedBf16Params.
@@ -87,21 +61,17 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16w_kernel(FusedBf16Params p) {
     const uint32_t KS = ld / KSTAGE;
 
     // ---- the rows this workgroup covers
-    // (sample mode: exactly ONE tile per workgroup, grid = number of sample tiles.  A compile-time tile count lets
-    // the compiler drop the next-tile address state; with it the sample instance spilled registers to scratch, and
-    // every scratch reload put a vmcnt(0) -- a full drain of the DMA pipeline -- into the stage loop)
-    // WHOLE tiles, dealt round-robin: workgroup w takes tiles w, w + n_wg, ...  (see kernels_fused_bf16p.hip)
+    // WHOLE tiles, dealt round-robin: workgroup w takes tiles w, w + n_wg, ...
     const uint32_t nblk = (p.n_rows + TR - 1) / TR;
     const uint32_t r0 = blockIdx.x * TR, r1 = p.n_rows;
     const uint32_t ntiles = blockIdx.x < nblk ? (nblk - blockIdx.x + p.n_wg - 1) / p.n_wg : 0;
     const uint32_t TS = p.n_wg * TR;                                    // rows between consecutive tiles of this workgroup
-    // queries of this lane: one column in each of the wave's two 32-query MFMA tiles
     const uint32_t q_a = wq * 128 + c;                                  // the lane's queries: q_a + 32 j, j = 0..3 (one column in each of the wave's four 32-query MFMA tiles)
     // (query j of the lane = query a + 32 j: its count sits 128 j counts and its pool 128 j sub-pools further -- derived where they
     // are needed, in the rare path and at the end, instead of being held in registers across the stage loop: the kernel is at the
     // 256-VGPR limit, and a pointer spilled to scratch cost a vmcnt(0) -- a drain of the DMA ring -- at every append; the thresholds
     // live in LDS for the same reason)
-    // sub-pool r = 2 * row half + lane half of query q (inside its 256-query block), as in kernels_fused_bf16p.hip; recomputed from
+    // sub-pool r = 2 * row half + lane half of query q (inside its 256-query block: kernels.h, candidate-pool layout); recomputed from
     // the thread index wherever it is needed (the empty asm keeps hipcc from hoisting the result into a register held -- i.e.
     // spilled -- across the stage loop)
     auto sub_of = [&](uint32_t jq) -> size_t {
@@ -109,7 +79,7 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16w_kernel(FusedBf16Params p) {
         asm volatile("" : "+v"(t_));
         const uint32_t l_ = t_ & 63u, w_ = t_ >> 6;
         const uint32_t q_ = (w_ & 3u) * 128u + (l_ & 31u) + 32u * jq;
-        return ((size_t)blockIdx.x * QB + (q_ & 255u)) * 4 + 2 * (w_ >> 2) + (l_ >> 5);
+        return VDB_BF16_SUBPOOL_R(blockIdx.x, q_ & 255u, 2 * (w_ >> 2) + (l_ >> 5));
     };
     // the lane's four sub-pool counts, two 16-bit counters per register (saturating; a count above capl means overflow): four
     // registers' worth of counters were the ones the MARGIN instance spilled, and a scratch access on the append path drains the DMA ring
@@ -152,24 +122,6 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16w_kernel(FusedBf16Params p) {
         aptr1 = rows_b + (size_t)(row + 8) * ld * 4 + a_chunk1;
     };
     auto a_piece = [&](int j) -> const char* { return j ? aptr1 : aptr0; };
-    // The LDS-DMA is issued from inline asm, not through __builtin_amdgcn_global_load_lds: hipcc's waitcnt pass
-    // tracks the builtin as a pending LDS write and, at the loop header of the 3-stage ring, cannot bound how many
-    // vector-memory operations followed the fill of the image about to be read -- it then puts a vmcnt(0) in front
-    // of that stage's first ds_read, which drains the two-stage DMA pipeline.  All ordering between the DMA and the
-    // LDS reads is done by hand here (counted s_waitcnt + s_barrier at the top of each stage); compiler-inserted
-    // vmcnt waits for ordinary loads stay correct because not counting these instructions only makes them wait longer.
-#define VDB_DMA(GP, IMG, LOFF)                                                                         \
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"                     \
-                 :: "s"((uint32_t)(uintptr_t)(lds_ptr_t)((IMG) + (LOFF))), "v"((const void*)(GP)) : "memory", "m0")
-    // (the instruction's immediate offset applies to BOTH addresses -- the global source and the LDS destination M0 + offset +
-    // lane * 16 -- so the four query pieces of a wave share one source register AND one M0 value)
-#define VDB_DMA_OFF(GP, IMG, LOFF, IMM)                                                                 \
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off offset:%2"           \
-                 :: "s"((uint32_t)(uintptr_t)(lds_ptr_t)((IMG) + (LOFF))), "v"((const void*)(GP)), "i"(IMM) : "memory", "m0")
-    // rows are read once per launch: non-temporal, so that they do not push the queries out of the L2
-#define VDB_DMA_NT(GP, IMG, LOFF)                                                                      \
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt"                  \
-                 :: "s"((uint32_t)(uintptr_t)(lds_ptr_t)((IMG) + (LOFF))), "v"((const void*)(GP)) : "memory", "m0")
 #define VDB_ISSUE(IMG, KSI)                                                                            \
     {                                                                                                  \
         const uint32_t la_ = (2 * w) * 1024;                                                           \
@@ -191,9 +143,6 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16w_kernel(FusedBf16Params p) {
     // ---- row constants of a tile, one tile ahead, by LDS-DMA (4 bytes per lane): waves 0-1 fetch alpha and the mask word of
     // rows 64(w&1)..+63, waves 2-3 beta (and the margin).  Issued BEFORE the stage's row/query pieces, so the counted wait at
     // the top of the next stage covers them.
-#define VDB_DMA4(GP, LP)                                                                               \
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off"                        \
-                 :: "s"((uint32_t)(uintptr_t)(lds_ptr_t)(LP)), "v"((const void*)(GP)) : "memory", "m0")
     auto issue_consts = [&](uint32_t t) {
         if (w >= 4) return;
         const uint32_t par = t & 1u;
@@ -257,18 +206,6 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16w_kernel(FusedBf16Params p) {
     asm volatile("" ::: "memory");
 
     bf16x8 fa0[MT], fb0[QT];                                            // k-step 0 fragments of the stage to compute next
-#define VDB_LOAD_FRAGS(FA, FB, IMG, T_)                                                                \
-    {                                                                                                  \
-        _Pragma("unroll") for (int i_ = 0; i_ < MT; ++i_) {                                            \
-            const float4 lo_ = *reinterpret_cast<const float4*>((IMG) + a_row_off + i_ * 32 * A_ROWB + ra[T_]); \
-            const float4 hi_ = *reinterpret_cast<const float4*>((IMG) + a_row_off + i_ * 32 * A_ROWB + (ra[T_] ^ 16u)); \
-            FA[i_] = cvt8(lo_, hi_);                                                                   \
-        }                                                                                              \
-        _Pragma("unroll") for (int j_ = 0; j_ < QT; ++j_) {                                            \
-            const u32x4 raw_ = *reinterpret_cast<const u32x4*>((IMG) + b_row_off + j_ * 32 * B_ROWB + rb[T_]); \
-            FB[j_] = __builtin_bit_cast(bf16x8, raw_);                                                 \
-        }                                                                                              \
-    }
     VDB_LOAD_FRAGS(fa0, fb0, sImg0, 0)
 
     // STEADY: the caller guarantees st + 3 < total, so the wait and the DMA issue are unconditional.
@@ -281,11 +218,6 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16w_kernel(FusedBf16Params p) {
         // k-step 0 MFMAs with the fragment reads of k-step 1 between them, one row block at a time: the two ds_read_b128 of
         // a row fragment are issued, two MFMAs run, then the fragment is rounded to bf16 -- at most one f32 fragment (8
         // registers) is in flight, not four (reading all of them first spilled)
-#define VDB_READ_B(FB, IMG, T_)                                                                        \
-    _Pragma("unroll") for (int j_ = 0; j_ < QT; ++j_) {                                                \
-        const u32x4 raw_ = *reinterpret_cast<const u32x4*>((IMG) + b_row_off + j_ * 32 * B_ROWB + rb[T_]); \
-        FB[j_] = __builtin_bit_cast(bf16x8, raw_);                                                     \
-    }
 #define VDB_STEP(I_, FA_USE, FB_USE, FA_NEW, IMG_NEW, T_NEW, LOAD_, EX0, EX1, EX2)                     \
     {                                                                                                  \
         float4 lo_, hi_;                                                                               \
@@ -339,7 +271,6 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16w_kernel(FusedBf16Params p) {
 #undef VDB_PIECE_A
 #undef VDB_PIECE_B
 #undef VDB_STEP
-#undef VDB_READ_B
         if (do_dma) VDB_ADV
 
         if (ks == KS - 1 && !(p.ablate & 8u)) {
@@ -352,22 +283,19 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16w_kernel(FusedBf16Params p) {
             const unsigned long long val = __ballot(tr0 + rt_l < r1 && ((sMaskW[par * TR + rt_l] >> (rt_l & 31)) & 1u));   // tr0 is a multiple of 32
             const float* al = sAlpha + par * TR + wr * 64 + 4 * h;
             const float* be = sBeta + par * TR + wr * 64 + 4 * h;
-            // MARGIN: the filter is  lb = fma(-g_q, margin_row, score) <= thr.  Since margin_row <= mmax (the largest margin of
-            // this wave's 64 rows), lb <= thr implies score <= thr + g_q mmax =: thp -- so the COMMON path compares the plain
-            // score with a per-tile loosened threshold, and only the rare path computes lb and applies the exact test.  The
-            // slack covers the f32 rounding of thp and of lb, so no row with lb <= thr can fail the pre-test.
+            // MARGIN: the pre-test against a per-tile loosened threshold (fused_bf16_common.h), mmax over this wave's 64 rows
             const float* mg = sMarg + (MARGIN ? par * TR + wr * 64 : 0);
             float thr_q[QT], thp[QT], ng[QT];
 #pragma unroll
             for (int jq = 0; jq < QT; ++jq) { thr_q[jq] = sThr[q_a + 32 * jq]; thp[jq] = thr_q[jq]; ng[jq] = 0.f; }
             if (MARGIN) {
-                float mm = mg[lane];                                    // +inf margins (norm overflow) open the tile; NaN rows carry NaN scores anyway
-                for (int o = 32; o > 0; o >>= 1) mm = fmaxf(mm, __shfl_xor(mm, o));
+                float mm = mg[lane];
+                VDB_WAVE_MAX(mm)
 #pragma unroll
                 for (int jq = 0; jq < QT; ++jq) {
                     const float g = sG[q_a + 32 * jq];
                     ng[jq] = -g;
-                    thp[jq] = fmaf(g, mm, thr_q[jq]); thp[jq] += (fabsf(thr_q[jq]) + g * mm) * 6.0e-7f;
+                    VDB_LOOSEN(thp[jq], thr_q[jq], g, mm)
                 }
             }
             // Per row block i (32 rows x 4 queries per lane = 4 groups of 4 rows): the COMMON path is branch-free -- scores of the
@@ -375,32 +303,13 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16w_kernel(FusedBf16Params p) {
             // ends in ONE not-taken branch per query; one pair of LDS reads (alpha, beta of 4 rows) serves all four queries.  Hits
             // are rare (about 0.1 % of the elements), so the RARE path recomputes the block's scores for its query from the
             // accumulators -- nothing of the common path has to stay live for it -- and appends what passes the exact test.
-            // v_min_f32 drops a NaN operand and a NaN score must pass (flat_index.rs:62): the minimum test stands alone only when
-            // no score of the launch can be NaN (fused_no_nan: every norm within [2^-40, 2^40]); otherwise a NaN-propagating sum of
-            // each group is tested as well (inf - inf gives a false alarm, which the exact per-row test of the rare path sorts out).
+            // (The group test and the append are those of fused_bf16_common.h.)
 #define VDB_SCORES(I_, J_, Q_, S01, S23)                                                               \
     const float4 a4_ = *reinterpret_cast<const float4*>(al + (I_) * 32 + 8 * (J_));                    \
     const float4 b4_ = *reinterpret_cast<const float4*>(be + (I_) * 32 + 8 * (J_));                    \
     const f32x2 al01_ = {a4_.x, a4_.y}, al23_ = {a4_.z, a4_.w}, be01_ = {b4_.x, b4_.y}, be23_ = {b4_.z, b4_.w}; \
     const f32x2 p01_ = {acc[I_][Q_][4 * (J_) + 0], acc[I_][Q_][4 * (J_) + 1]}, p23_ = {acc[I_][Q_][4 * (J_) + 2], acc[I_][Q_][4 * (J_) + 3]}; \
     const f32x2 S01 = __builtin_elementwise_fma(p01_, al01_, be01_), S23 = __builtin_elementwise_fma(p23_, al23_, be23_);
-            // the append: one 4-bit hit mask per lane and group, then a loop over its set bits -- typically one lane, one iteration
-#define VDB_APPEND(I_, J_, S0, S1, S2, S3, THP, THR, NG, POOL, PCNT)                                   \
-    {                                                                                                  \
-        uint32_t hm_ = (!((S0) > (THP)) ? 1u : 0u) | (!((S1) > (THP)) ? 2u : 0u) | (!((S2) > (THP)) ? 4u : 0u) | (!((S3) > (THP)) ? 8u : 0u); \
-        hm_ &= (vbits >> (8 * (J_))) & 0xfu;                                                           \
-        while (hm_) {                                                                                  \
-            const uint32_t e_ = (uint32_t)__builtin_ctz(hm_);                                          \
-            hm_ &= hm_ - 1u;                                                                           \
-            float sc_ = e_ == 0 ? (S0) : e_ == 1 ? (S1) : e_ == 2 ? (S2) : (S3);                       \
-            if (MARGIN) {                                              /* the exact test, on the lower-bound score */ \
-                sc_ = fmaf((NG), mg[(I_) * 32 + 8 * (J_) + 4 * h + e_], sc_);                          \
-                if (sc_ > (THR)) continue;                                                             \
-            }                                                                                          \
-            if (!(kDiag && (p.ablate & 32u)) && PCNT < p.capl) POOL[PCNT] = make_raw_key(sc_, tr0 + rowb_ + 8 * (J_) + e_); /* diag 32: count only */ \
-            ++PCNT;                                                                                    \
-        }                                                                                              \
-    }
 #define VDB_RARE(I_, Q_)                                                                               \
     {                                                                                                  \
         uint64_t* const pool_q = p.pool + (size_t)(wq >> 1) * p.pool_block_stride + sub_of(Q_) * p.capl;   /* queries 128 wq .. + 127: block wq >> 1 */ \
@@ -411,7 +320,8 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16w_kernel(FusedBf16Params p) {
         _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_) {                                             \
             if (hit[Q_][j_] != 0ull) {         /* only the groups of four rows in which some lane has a hit (wave-uniform) */ \
                 VDB_SCORES(I_, j_, Q_, r01_, r23_)                                                     \
-                VDB_APPEND(I_, j_, r01_.x, r01_.y, r23_.x, r23_.y, thp[Q_], thr_q[Q_], ng[Q_], pool_q, cnt_) \
+                VDB_APPEND(r01_.x, r01_.y, r23_.x, r23_.y, vbits >> (8 * (j_)), thp[Q_], thr_q[Q_], ng[Q_], mg, (I_) * 32 + 8 * (j_) + 4 * h, \
+                           pool_q, cnt_, tr0 + rowb_ + 8 * (j_))                                       \
             }                                                                                          \
         }                                                                                              \
         if (cnt_ > 0xffffu) cnt_ = 0xffffu;                                                            \
@@ -433,8 +343,8 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16w_kernel(FusedBf16Params p) {
                     for (int jq = 0; jq < QT; ++jq) {
                         const f32x2 p01 = {acc[i][jq][4 * j + 0], acc[i][jq][4 * j + 1]}, p23 = {acc[i][jq][4 * j + 2], acc[i][jq][4 * j + 3]};
                         const f32x2 r01 = __builtin_elementwise_fma(p01, al01, be01), r23 = __builtin_elementwise_fma(p23, al23, be23);
-                        const f32x2 n_ = __builtin_elementwise_min(r01, r23);
-                        hit[jq][j] = __builtin_amdgcn_ballot_w64(!(fminf(n_.x, n_.y) > thp[jq]));
+                        const f32x2 n_ = VDB_MIN4(r01, r23);
+                        hit[jq][j] = VDB_HITS_MIN4(n_, thp[jq]);
                     }
                     // two groups in flight at a time: with all four the register allocator spills (the kernel sits at 256 VGPRs,
                     // and a scratch access in here costs a vmcnt(0), i.e. a drain of the DMA ring, per tile)
@@ -444,10 +354,10 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16w_kernel(FusedBf16Params p) {
                     asm volatile("" ::: "memory");                      // computing the sums always and selecting with v_cndmask
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        { VDB_SCORES(i, j, 0, u01, u23) const f32x2 u_ = u01 + u23; const float t_ = u_.x + u_.y; hit[0][j] |= __builtin_amdgcn_ballot_w64(t_ != t_); }
-                        { VDB_SCORES(i, j, 1, u01, u23) const f32x2 u_ = u01 + u23; const float t_ = u_.x + u_.y; hit[1][j] |= __builtin_amdgcn_ballot_w64(t_ != t_); }
-                        { VDB_SCORES(i, j, 2, u01, u23) const f32x2 u_ = u01 + u23; const float t_ = u_.x + u_.y; hit[2][j] |= __builtin_amdgcn_ballot_w64(t_ != t_); }
-                        { VDB_SCORES(i, j, 3, u01, u23) const f32x2 u_ = u01 + u23; const float t_ = u_.x + u_.y; hit[3][j] |= __builtin_amdgcn_ballot_w64(t_ != t_); }
+                        { VDB_SCORES(i, j, 0, u01, u23) const f32x2 u_ = VDB_SUM4(u01, u23); const float t_ = u_.x + u_.y; hit[0][j] |= VDB_HITS_NAN4(t_); }
+                        { VDB_SCORES(i, j, 1, u01, u23) const f32x2 u_ = VDB_SUM4(u01, u23); const float t_ = u_.x + u_.y; hit[1][j] |= VDB_HITS_NAN4(t_); }
+                        { VDB_SCORES(i, j, 2, u01, u23) const f32x2 u_ = VDB_SUM4(u01, u23); const float t_ = u_.x + u_.y; hit[2][j] |= VDB_HITS_NAN4(t_); }
+                        { VDB_SCORES(i, j, 3, u01, u23) const f32x2 u_ = VDB_SUM4(u01, u23); const float t_ = u_.x + u_.y; hit[3][j] |= VDB_HITS_NAN4(t_); }
                     }
                 }
                 if (__builtin_expect((hit[0][0] | hit[0][1] | hit[0][2] | hit[0][3]) != 0ull, 0)) VDB_RARE(i, 0)
@@ -456,7 +366,6 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16w_kernel(FusedBf16Params p) {
                 if (__builtin_expect((hit[3][0] | hit[3][1] | hit[3][2] | hit[3][3]) != 0ull, 0)) VDB_RARE(i, 3)
             }
 #undef VDB_RARE
-#undef VDB_APPEND
 #undef VDB_SCORES
 #pragma unroll
             for (int i = 0; i < MT; ++i)
@@ -469,30 +378,11 @@ __global__ __launch_bounds__(NT, 2) void fused_bf16w_kernel(FusedBf16Params p) {
         if (ks == KS) { ks = 0; ++tile; }
     };
 
-    using B0 = std::integral_constant<int, 0>;
-    using B1 = std::integral_constant<int, 1>;
-    using B2 = std::integral_constant<int, 2>;
-    uint32_t st = 0;
-    for (; st + 5 < total; st += 3) {                                   // stage index mod 3 == image index
-        run_stage(st, B0{}, std::true_type{});
-        run_stage(st + 1, B1{}, std::true_type{});
-        run_stage(st + 2, B2{}, std::true_type{});
-    }
-    // the last one to five stages: conditional issue
-    if (st < total) { run_stage(st, B0{}, std::false_type{}); ++st; }
-    if (st < total) { run_stage(st, B1{}, std::false_type{}); ++st; }
-    if (st < total) { run_stage(st, B2{}, std::false_type{}); ++st; }
-    if (st < total) { run_stage(st, B0{}, std::false_type{}); ++st; }
-    if (st < total) { run_stage(st, B1{}, std::false_type{}); ++st; }
+    VDB_RING3(run_stage, total, 5)
 #pragma unroll
     for (int j = 0; j < QT; ++j) p.pool_cnt[(size_t)(wq >> 1) * p.cnt_block_stride + sub_of(j)] = (pcnt_pk[j >> 1] >> (16 * (j & 1))) & 0xffffu;
-#undef VDB_DMA
-#undef VDB_DMA_NT
-#undef VDB_DMA_OFF
-#undef VDB_DMA4
 #undef VDB_ISSUE
 #undef VDB_ADV
-#undef VDB_LOAD_FRAGS
 }
 
 uint32_t fused_bf16w_tile_rows() { return TR; }

@@ -1,5 +1,5 @@
 // kernels_fused_s16.hip -- the FILTER pass of the screening tier over the bf16 SHADOW of the rows (vdb_flat_set_shadow):
-// the same scores as kernels_fused_bf16p.hip, bit for bit (the shadow holds exactly the v_cvt_pk_bf16_f32 roundings that
+// the method of fused_bf16_common.h and the scores of kernels_fused_bf16p.hip, bit for bit (the shadow holds exactly the v_cvt_pk_bf16_f32 roundings that
 // kernel makes in registers, and every accumulator sees the same MFMAs in the same order), from half the HBM bytes.
 //
 // Half the bytes halve the time the row stream leaves for everything else, so the shape is built around the matrix pipe
@@ -19,34 +19,18 @@
 // queries of u+1 -- issued at v = u-2 -- must have landed: whatever was issued after them is 8 + 4 pieces in either
 // parity (u even: Q(u+2) and R of v = u-1; u odd: R of v = u-2 and Q(u+2)), so the wait is vmcnt(12); the rows of the
 // next stage are older than that.  The half-stage after a tile start allows 4 more (the constants sit in the window).
-#include "kernels.h"
-
-#include <type_traits>
+#include "fused_bf16_common.h"
 
 namespace vdb {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 constexpr int NW = 4, NT = NW * 64;
 constexpr int TR = 256;                          // rows per tile
 constexpr int TQ = 256;                          // queries per tile
-constexpr int A_ROWB = 128;                      // 64 bf16 per row and row stage
-constexpr int B_ROWB = 64;                       // 32 bf16 per query and half-stage
-constexpr int A_BYTES = TR * A_ROWB;             // 32 KB
-constexpr int B_BYTES = TQ * B_ROWB;             // 16 KB
+constexpr int A_BYTES = TR * A_ROWB;             // 32 KB: 64 bf16 per row and row stage
+constexpr int B_BYTES = TQ * B_ROWB;             // 16 KB: 32 bf16 per query and half-stage
 constexpr int R_OFF = 0, Q_OFF = 3 * A_BYTES, IMG_BYTES = 3 * A_BYTES + 3 * B_BYTES;   // 144 KB
 constexpr int MT = 4, QT = 4;                    // MFMA tiles per wave: 4 x 32 rows, 4 x 32 queries
-
-#ifdef VDB_DIAG
-constexpr bool kDiag = true;
-#else
-constexpr bool kDiag = false;
-#endif
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 // The 256 accumulators of a wave live in a[0:255], named BY HAND.  Left to hipcc, a 4 x 4 block of f32x16 accumulators
 // that fills the AccVGPR file exactly is allocated with copies through VGPRs and scratch spills inside the stage loop (a
@@ -95,12 +79,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     const uint32_t r1 = SAMPLE ? p.n_sample : p.n_rows;
     const uint32_t ntiles = SAMPLE ? 1u : (blockIdx.x < nblk ? (nblk - blockIdx.x + p.n_wg - 1) / p.n_wg : 0);
     const uint32_t TS = SAMPLE ? TR : p.n_wg * TR;                      // rows between consecutive tiles of this workgroup
-    // sample index -> device row: positions spread evenly over the rows, consecutive positions in different tiles (see
-    // kernels_fused_bf16.hip)
-    auto sample_row_of = [&](uint32_t j) -> uint32_t {
-        const uint32_t pos = (j & 255u) * (p.n_sample >> 8) + (j >> 8);
-        return (uint32_t)(((uint64_t)pos * p.n_rows) >> p.sample_shift);
-    };
+    auto sample_row_of = [&](uint32_t j) -> uint32_t { return screen_sample_row(j, p.n_sample, p.sample_shift, p.n_rows); };
 
     uint32_t q_of[QT];
     uint64_t* pool[QT];
@@ -112,8 +91,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         q_of[j] = wq * 128 + 32 * j + c;
         sub[j] = 0; pool[j] = nullptr; thr[j] = 0.f; pcnt[j] = 0;
         if (SAMPLE) continue;
-        sub[j] = (((size_t)blockIdx.x * TQ + q_of[j]) * 2 + wr) * 2 + h;      // counts workgroup-major, like the keys
-        pool[j] = p.pool + ((((size_t)blockIdx.x * TQ + q_of[j]) * 2 + wr) * 2 + h) * p.capl;
+        sub[j] = fused_bf16_subpool(blockIdx.x, q_of[j], wr, h);
+        pool[j] = p.pool + fused_bf16_subpool(blockIdx.x, q_of[j], wr, h) * p.capl;
         thr[j] = p.thr[q_of[j]];
         if (kDiag && (p.ablate & 16u)) thr[j] = -__builtin_inff();
         asm volatile("" : "+v"(thr[j]));                                // consumed here: no ordinary load pending in the loop
@@ -178,9 +157,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                  :: "v"(FA), "v"(FB[0]), "v"(FB[1]), "v"(FB[2]), "v"(FB[3]),                          \
                     "n"(64 * (I)), "n"(64 * (I) + 15), "n"(64 * (I) + 16), "n"(64 * (I) + 31), "n"(64 * (I) + 32), "n"(64 * (I) + 47), \
                     "n"(64 * (I) + 48), "n"(64 * (I) + 63) : VDB_ALL_AGPRS)
-#define VDB_DMA4(GP, LP)                                                                               \
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off"                        \
-                 :: "s"((uint32_t)(uintptr_t)(lds_ptr_t)(LP)), "v"((const void*)(GP)) : "memory", "m0")
     // row constants of a tile, one tile ahead (4 bytes per lane): wave w fetches those of tile rows 64w..64w+63
     auto issue_consts = [&](uint32_t t) {
         const uint32_t par = t & 1u;
@@ -325,20 +301,18 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
             const float* al = sAlpha + par * TR + wr * 128 + 4 * h;
             const float* be = sBeta + par * TR + wr * 128 + 4 * h;
             const float* mg = sMarg + (MARGIN ? par * TR + wr * 128 : 0);
-            // MARGIN: common path on the plain score against a per-tile loosened threshold, exact lower-bound test on the rare
-            // path (see kernels_fused_bf16p.hip)
+            // MARGIN: the pre-test against a per-tile loosened threshold (fused_bf16_common.h), mmax over this wave's 128 rows
             float thp[QT], ng[QT];
 #pragma unroll
             for (int j = 0; j < QT; ++j) { thp[j] = thr[j]; ng[j] = 0.f; }
             if (MARGIN) {
                 float mm = fmaxf(mg[2 * lane], mg[2 * lane + 1]);
-                for (int o = 32; o > 0; o >>= 1) mm = fmaxf(mm, __shfl_xor(mm, o));
+                VDB_WAVE_MAX(mm)
 #pragma unroll
                 for (int j = 0; j < QT; ++j) {
                     const float g = sG[q_of[j]];
                     ng[j] = -g;
-                    thp[j] = fmaf(g, mm, thr[j]);
-                    thp[j] += (fabsf(thr[j]) + g * mm) * 6.0e-7f;
+                    VDB_LOOSEN(thp[j], thr[j], g, mm)
                 }
             }
             float best[QT];                                             // sample mode: running group minima
@@ -363,29 +337,15 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                                                    /* queries to the end of the epilogue and keeps 192 scores alive (spills) */ \
         } else {                                                                                       \
         const float tp = thp[J];                                                                       \
-        /* ONE compare for the four rows: their smallest score against the threshold; where a score of the launch could */ \
-        /* be NaN (fused_no_nan says no) a NaN-propagating sum is tested as well (kernels_fused_bf16p.hip) */ \
-        const f32x2 mn_ = __builtin_elementwise_min(s01, s23);                                         \
-        unsigned long long m = __builtin_amdgcn_ballot_w64(!(fminf(mn_.x, mn_.y) > tp));                \
+        /* the filter test and the append of fused_bf16_common.h */                                    \
+        const f32x2 mn_ = VDB_MIN4(s01, s23);                                                          \
+        unsigned long long m = VDB_HITS_MIN4(mn_, tp);                                                 \
         if (!(NN)) {                                           /* NN: compile-time copy of no_nan (the epilogue exists twice) */ \
-            const f32x2 u_ = s01 + s23; const float t_ = u_.x + u_.y;                                  \
-            m |= __builtin_amdgcn_ballot_w64(t_ != t_);                                                \
+            const f32x2 u_ = VDB_SUM4(s01, s23); const float t_ = u_.x + u_.y;                         \
+            m |= VDB_HITS_NAN4(t_);                                                                    \
         }                                                                                              \
-        if (__builtin_expect(m != 0ull, 0)) {                                                          \
-            uint32_t hm = (!(s0 > tp) ? 1u : 0u) | (!(s1 > tp) ? 2u : 0u) | (!(s2 > tp) ? 4u : 0u) | (!(s3 > tp) ? 8u : 0u); \
-            hm &= (vbits >> (8 * (G4))) & 0xfu;                                                        \
-            while (hm) {                                                                               \
-                const uint32_t e = (uint32_t)__builtin_ctz(hm);                                        \
-                hm &= hm - 1u;                                                                         \
-                float sc = e == 0 ? s0 : e == 1 ? s1 : e == 2 ? s2 : s3;                               \
-                if (MARGIN) {                                                                          \
-                    sc = fmaf(ng[J], mg[(I) * 32 + 8 * (G4) + 4 * h + e], sc);                         \
-                    if (sc > thr[J]) continue;                                                         \
-                }                                                                                      \
-                if (!(kDiag && (p.ablate & 32u)) && pcnt[J] < p.capl) pool[J][pcnt[J]] = make_raw_key(sc, tr0 + rt0 + e); \
-                ++pcnt[J];                                                                             \
-            }                                                                                          \
-        }                                                                                              \
+        if (__builtin_expect(m != 0ull, 0))                                                            \
+            VDB_APPEND(s0, s1, s2, s3, vbits >> (8 * (G4)), tp, thr[J], ng[J], mg, (I) * 32 + 8 * (G4) + 4 * h, pool[J], pcnt[J], tr0 + rt0) \
         }                                                                                              \
     }
 #define VDB_EPI_G(I, G4, NN)                                                                           \
@@ -437,7 +397,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 #undef VDB_DMA_SV
 #undef VDB_MFMA_DMA
 #undef VDB_MFMA4
-#undef VDB_DMA4
 #undef VDB_ISSUE_R
 #undef VDB_ISSUE_Q
 #undef VDB_RD

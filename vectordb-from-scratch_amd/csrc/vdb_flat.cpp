@@ -38,6 +38,9 @@ int fail_dim(size_t expected, size_t actual) {
     // same text as error.rs:12
     return fail(VDB_ERR_DIMENSION_MISMATCH, "Dimension mismatch: expected %zu, got %zu", expected, actual);
 }
+// (the texts are compared with the reference's by the tests)
+int fail_zero_vector() { return fail(VDB_ERR_INVALID_VECTOR, "Invalid vector: Cannot compute cosine distance with zero vector"); }
+int fail_nan() { return fail(VDB_ERR_NAN, "NaN distance (the reference panics here, flat_index.rs:62)"); }
 int guard_fail(const char* what) { return fail(VDB_ERR_DEVICE, "internal error: %s", what); }
 void last_error(std::string* msg, size_t* expected, size_t* actual) {
     if (msg) *msg = g_err;
@@ -708,7 +711,7 @@ int vdb_flat_distances_batch(vdb_flat_index* ix, const float* queries, size_t nq
     HIP_TRY(hipMemcpyAsync(&st, ix->cur->w_flags.p, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (st & vdb::ST_ZERO_QUERY)
-        return fail(VDB_ERR_INVALID_VECTOR, "Invalid vector: Cannot compute cosine distance with zero vector");
+        return fail_zero_vector();
     return VDB_OK;   // a NaN distance is returned as NaN (only the sort in FlatIndex::search panics on it)
     });
 }
@@ -1177,6 +1180,7 @@ int device_view(vdb_flat_index* ix, DeviceView* out) {
     return VDB_OK;
 }
 int set_error(int code, const char* msg) { return fail(code, "%s", msg); }
+int zero_vector_error() { return fail_zero_vector(); }
 int set_dim_error(size_t expected, size_t actual) { return fail_dim(expected, actual); }
 
 }  // namespace vdb_internal

@@ -283,7 +283,7 @@ template <class F> int guarded(F&& body) noexcept {
     } while (0)
 
 int zero_norm_error() {
-    return vdb_internal::set_error(VDB_ERR_INVALID_VECTOR, "Invalid vector: Cannot compute cosine distance with zero vector");
+    return vdb_internal::zero_vector_error();
 }
 
 // graph.rs:118-123

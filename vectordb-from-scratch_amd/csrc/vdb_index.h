@@ -28,6 +28,8 @@ namespace vdbi {
 // ---- thread-local last error (vdb_last_error) and the exception guard of every extern "C" body
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 int fail_dim(size_t expected, size_t actual);
+int fail_zero_vector();   // distance.rs:51-55: a zero-norm vector under Cosine fails the whole search
+int fail_nan();           // flat_index.rs:62: the reference panics on a NaN distance
 int guard_fail(const char* what);
 void last_error(std::string* msg, size_t* expected, size_t* actual);
 

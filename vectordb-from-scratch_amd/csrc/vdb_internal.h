@@ -29,6 +29,7 @@ struct DeviceView { const float* rows; uint32_t ld, dim; const float* nd; const 
 int device_view(vdb_flat_index* ix, DeviceView* out);
 // thread-local last-error state shared by every entry point of the library (vdb_last_error)
 int set_error(int code, const char* msg);
+int zero_vector_error();   // the reference's InvalidVector for a zero-norm Cosine operand
 int set_dim_error(size_t expected, size_t actual);
 
 }  // namespace vdb_internal

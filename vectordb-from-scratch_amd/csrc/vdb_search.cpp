@@ -21,6 +21,88 @@ void launch_filter_pass(Index* ix, vdb::FusedBf16Params& fp, hipStream_t s) {
     vdb::launch_fused_bf16p(fp, s);
 }
 
+// ------------------------------------------------------------------ parameter blocks shared by the tiers
+// grid of a screening pass: one workgroup per CU, at most one per row tile
+static uint32_t screen_grid(const Index* ix, uint32_t tile_rows) {
+    return std::min<uint32_t>((uint32_t)ix->n_cu, (ix->n_uploaded + tile_rows - 1) / tile_rows);
+}
+// A screening launch: everything that comes from the index and the pass-local workspace W.  The caller adds the query
+// block (screen_queries) and what its pass differs in.
+static vdb::FusedBf16Params screen_params(const Index* ix, const Workspace* W, const uint32_t* d_rowmask, const uint32_t* d_status,
+                                          uint32_t capl, uint32_t n_wg) {
+    vdb::FusedBf16Params fp{};
+    fp.rows = ix->d_rows; fp.ld = ix->ld; fp.n_rows = ix->n_uploaded;
+    fp.alpha = ix->d_alpha; fp.beta = ix->d_beta; fp.rowmask = d_rowmask ? d_rowmask : ix->d_live;
+    fp.margin = ix->d_margin;
+    fp.pool = W->w_pool.p; fp.pool_cnt = W->w_subcnt.p; fp.capl = capl; fp.n_wg = n_wg;
+    fp.scalars = ix->d_scalars; fp.qmax_bits = d_status + 2;
+    return fp;
+}
+// ... its queries: the 256-query block (512 for the wide kernel) that starts at q0 of the bf16 images / g_q / thresholds
+static void screen_queries(vdb::FusedBf16Params& fp, const Index* ix, const uint16_t* qb, const float* qg, const float* thr, uint32_t q0) {
+    fp.qb = qb + (size_t)q0 * ix->ld; fp.qg = ix->d_margin ? qg + q0 : nullptr; fp.thr = thr + q0;
+}
+// An exact re-rank of the candidate lists cand[q * kp ..] (cand_cnt[q] of them): everything but the query block, the
+// outputs and the certificate inputs of the tier.
+static vdb::RerankParams rerank_params(const Index* ix, const uint32_t* d_rowmask, uint32_t* d_status, size_t k, const uint64_t* cand,
+                                       uint32_t kp, const uint32_t* cand_cnt) {
+    vdb::RerankParams rp{};
+    rp.rows = ix->d_rows; rp.ld = ix->ld; rp.dim = ix->dim; rp.n_rows = ix->n_uploaded;
+    rp.nd = ix->d_nd; rp.row_ids = ix->d_row_ids; rp.rowmask = d_rowmask;
+    rp.cand = cand; rp.cand_stride = kp; rp.cand_cnt = cand_cnt; rp.kp = kp;
+    rp.metric = ix->metric; rp.k = (uint32_t)k; rp.nd2max_bits = ix->d_scalars;
+    rp.out_stride = (uint32_t)k; rp.status = d_status;
+    return rp;
+}
+// ... its queries (padded rows / norms of a block that starts at q0) and where their results and certificates go
+static void rerank_io(vdb::RerankParams& rp, const Index* ix, const float* qp, const float* qnorm, uint64_t* out_ids, float* out_dists,
+                      uint32_t* out_counts, uint32_t* cert, uint32_t q0) {
+    rp.qp = qp + (size_t)q0 * ix->ld; rp.qnorm = qnorm + q0;
+    rp.out_ids = out_ids + (size_t)q0 * rp.k; rp.out_dists = out_dists + (size_t)q0 * rp.k;
+    rp.out_counts = out_counts + q0; rp.cert = cert + q0;
+}
+
+// The compact re-run block of the queries `todo` (batch indices) that a tier could not certify: the w2_* buffers for
+// them, the index list on the device, their padded rows and norms gathered (thresholds: -inf in the padding).
+static int gather_compact(Index* ix, hipStream_t s, const std::vector<uint32_t>& todo, size_t k, bool zero_flags) {
+    int rc;
+    Workspace* W = ix->cur;
+    const uint32_t nf = (uint32_t)todo.size(), nfp = round_up(nf, SUPER), ld = ix->ld;
+    if ((rc = W->w2_qp.ensure((size_t)nfp * ld))) return rc;
+    if ((rc = W->w2_qnorm.ensure(nfp))) return rc;
+    if ((rc = W->w2_thr.ensure(nfp))) return rc;
+    if ((rc = W->w2_outi.ensure((size_t)nf * k))) return rc;
+    if ((rc = W->w2_outd.ensure((size_t)nf * k))) return rc;
+    if ((rc = W->w2_outc.ensure(nf))) return rc;
+    if ((rc = W->w2_flags.ensure(2 * (size_t)nf))) return rc;
+    if ((rc = W->w2_qidx.ensure(nf))) return rc;
+    HIP_TRY(hipMemcpyAsync(W->w2_qidx.p, todo.data(), (size_t)nf * 4, hipMemcpyHostToDevice, s));
+    if (zero_flags) HIP_TRY(hipMemsetAsync(W->w2_flags.p, 0, 2 * (size_t)nf * 4, s));
+    vdb::launch_gather_queries(W->w_qp.p, W->w_qnorm.p, ld, W->w2_qidx.p, nf, nfp, W->w2_qp.p, W->w2_qnorm.p, W->w2_thr.p, s);
+    return VDB_OK;
+}
+
+// diagnostics (kn.rr_depth): the re-rank depth each query of the block ended at and its phase stamps, printed
+static int dump_rerank_depth(Workspace* W, hipStream_t s, uint32_t nb, uint32_t kp_first) {
+    std::vector<uint32_t> dep((size_t)SUPER * 17);
+    HIP_TRY(hipMemcpyAsync(dep.data(), W->w_depth.p, dep.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    // phase stamps (s_memrealtime, 100 MHz): 0 start, 1 query row in LDS, 2 round 1 staged+folded, 3 sorted, 4 depth decided, 5 last round folded, 6 end
+    const uint64_t* st64 = reinterpret_cast<const uint64_t*>(dep.data() + SUPER);
+    uint64_t t0 = ~0ull;
+    for (uint32_t q = 0; q < nb; ++q) t0 = std::min(t0, st64[(size_t)q * 8]);
+    for (int ph = 0; ph < 7; ++ph) {
+        std::vector<double> v(nb);
+        for (uint32_t q = 0; q < nb; ++q) v[q] = (double)(st64[(size_t)q * 8 + ph] - t0) * 0.01;
+        std::sort(v.begin(), v.end());
+        fprintf(stderr, "[vdb] re-rank phase %d at us: min %.2f median %.2f p90 %.2f max %.2f\n", ph, v[0], v[nb / 2], v[(size_t)nb * 9 / 10], v[nb - 1]);
+    }
+    std::sort(dep.begin(), dep.begin() + nb);
+    fprintf(stderr, "[vdb] re-rank depth of %u queries: min %u  p25 %u  median %u  p75 %u  p95 %u  max %u  (first round %u)\n", nb,
+            dep[0], dep[nb / 4], dep[nb / 2], dep[(size_t)nb * 3 / 4], dep[(size_t)nb * 95 / 100], dep[nb - 1], kp_first);
+    return VDB_OK;
+}
+
 // ------------------------------------------------------------------ exact path for one query
 int exact_one(Index* ix, hipStream_t s, uint32_t q, size_t k, const uint32_t* d_rowmask, uint64_t* d_out_ids,
               float* d_out_dists, uint32_t* d_out_count) {
@@ -146,13 +228,9 @@ int pass_f32(Index* ix, hipStream_t s, const float* qp, const float* qnorm, floa
             mp.out_thr = nullptr; mp.ovf = d_ovf + q0; mp.summary = d_status + 1;
             vdb::launch_select(mp, nb, s);
         }
-        vdb::RerankParams rp{};
-        rp.rows = ix->d_rows; rp.ld = ld; rp.dim = ix->dim; rp.n_rows = n;
-        rp.qp = qp0; rp.qnorm = qnorm + q0; rp.nd = ix->d_nd; rp.row_ids = ix->d_row_ids;
-        rp.rowmask = d_rowmask; rp.cand = ix->cur->w_cand.p; rp.cand_stride = kp; rp.cand_cnt = d_cand_cnt; rp.kp = kp;
-        rp.metric = ix->metric; rp.k = (uint32_t)k; rp.eps_coef = eps; rp.nd2max_bits = ix->d_scalars;
-        rp.out_ids = d_out_ids + (size_t)q0 * k; rp.out_dists = d_out_dists + (size_t)q0 * k;
-        rp.out_counts = d_out_counts + q0; rp.out_stride = (uint32_t)k; rp.cert = d_cert + q0; rp.status = d_status;
+        vdb::RerankParams rp = rerank_params(ix, d_rowmask, d_status, k, ix->cur->w_cand.p, kp, d_cand_cnt);
+        rerank_io(rp, ix, qp, qnorm, d_out_ids, d_out_dists, d_out_counts, d_cert, q0);
+        rp.eps_coef = eps;
         rp.thr = small ? nullptr : thr + q0;
         vdb::launch_rerank(rp, nb, s);
     }
@@ -160,7 +238,7 @@ int pass_f32(Index* ix, hipStream_t s, const float* qp, const float* qnorm, floa
 }
 
 // ------------------------------------------------------------------ tier: bf16 screening + certified re-rank
-// Same structure, with the scores of the HBM-bound bf16 kernel (kernels_fused_bf16.hip): group minima of a row
+// Same structure, with the scores of the HBM-bound bf16 kernels (fused_bf16_common.h): group minima of a row
 // sample -> per-query threshold -> one pass over all rows keeping the keys under the threshold -> the kp smallest
 // keys -> exact re-rank, certified with the bf16 error bound.  Queries come from ix->cur->w_qp / w_qb / w_qnorm.
 int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& pl, const uint32_t* d_rowmask,
@@ -175,7 +253,7 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
     // the expected total, so that case stays on this tier instead of overflowing into the next.  The gather reads
     // counts and keys, never empty slots, so the capacity costs address space only (0.5 GB of workspace at 1M rows).
     const uint32_t capl = 256;
-    const uint32_t n_wg = std::min<uint32_t>((uint32_t)ix->n_cu, (n + vdb::fused_bf16_tile_rows() - 1) / vdb::fused_bf16_tile_rows());
+    const uint32_t n_wg = screen_grid(ix, vdb::fused_bf16_tile_rows());
     // Batches above 256 queries: the WIDE filter kernel (kernels_fused_bf16w.hip, 128 rows x 512 queries per workgroup) serves
     // two 256-query blocks per fetch of the rows -- BASELINE config 3 (B = 1024) reads its shard twice per batch instead of
     // four times.  Not over the opt-in bf16 shadow rows (their kernel has the one shape); vdb_flat_set_wide(h, 0) turns it off.
@@ -184,7 +262,7 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
                           && ix->kn.fused_pipe
 #endif
         ;
-    const uint32_t n_wg_w = std::min<uint32_t>((uint32_t)ix->n_cu, (n + vdb::fused_bf16w_tile_rows() - 1) / vdb::fused_bf16w_tile_rows());
+    const uint32_t n_wg_w = screen_grid(ix, vdb::fused_bf16w_tile_rows());
     const uint32_t n_sub = vdb::fused_bf16_subpools_per_query(std::max(n_wg, use_wide ? n_wg_w : 0u));   // (both kernels write the 4-sub-pool layout)
     const size_t pool_block = (size_t)SUPER * n_sub * capl, cnt_block = (size_t)SUPER * n_sub;
     // A batch above 256 queries takes several passes.  They are independent, so they ALTERNATE between
@@ -242,23 +320,23 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
     // thresholds: sample pass + threshold select per 256-query block.  A batch of several passes computes ALL of them first, on the
     // caller's stream: left to their own pass, the second stream's small kernels queue up behind the first pass's filter kernel
     // (which owns every CU for a millisecond) and the second filter pass starts late.
-    auto thresholds_of = [&](Workspace* W, hipStream_t st, uint32_t qb0) {
-        const uint32_t nb = std::min(SUPER, nq - qb0);
-        vdb::FusedBf16Params fp{};
-        fp.rows = ix->d_rows; fp.ld = ld; fp.n_rows = n;
-        fp.alpha = ix->d_alpha; fp.beta = ix->d_beta; fp.rowmask = d_rowmask ? d_rowmask : ix->d_live;
-        fp.margin = ix->d_margin;
-        fp.pool = W->w_pool.p; fp.pool_cnt = W->w_subcnt.p; fp.capl = capl; fp.n_wg = n_wg;
-        fp.scalars = ix->d_scalars; fp.qmax_bits = d_status + 2;
+    // a launch of this tier over pass-local buffers W: sample geometry and the diagnostics' ablation on top of screen_params
+    auto pass_params = [&](Workspace* W) {
+        vdb::FusedBf16Params fp = screen_params(ix, W, d_rowmask, d_status, capl, n_wg);
         fp.ablate = ix->kn.bf16_ablate;
         fp.n_sample = S; fp.sample_shift = pl.shift;
         fp.sample_block = ix->kn.sample_block ? (n / (S / 256u)) : 0u; fp.minkeys = W->w_dense.p; fp.minkey_stride = M;
-        fp.qb = ix->cur->w_qb.p + (size_t)qb0 * ld; fp.qg = ix->d_margin ? ix->cur->w_qg.p + qb0 : nullptr; fp.thr = ix->cur->w_thr.p + qb0;
+        return fp;
+    };
+    auto thresholds_of = [&](Workspace* W, hipStream_t st, uint32_t qb0) {
+        const uint32_t nb = std::min(SUPER, nq - qb0);
+        vdb::FusedBf16Params fp = pass_params(W);
+        screen_queries(fp, ix, ix->cur->w_qb.p, ix->cur->w_qg.p, ix->cur->w_thr.p, qb0);
         if (sample_copy) {
             vdb::FusedBf16Params sp16 = fp;
             sp16.rows16 = ix->d_sample16;
             vdb::launch_sample_s16(sp16, st);
-        } else vdb::launch_sample_bf16(fp, (uint32_t)ix->n_cu, st);
+        } else vdb::launch_sample_bf16(fp, st);
         vdb::SelectParams sp{};
         sp.keys = W->w_dense.p; sp.stride = M; sp.counts = nullptr; sp.n_fixed = M; sp.cap = M; sp.kk = KT;
         sp.out_stride = KT; sp.out_keys = W->w_samp.p; sp.out_cnt = W->w_cnt.p; sp.out_thr = ix->cur->w_thr.p + qb0; sp.ovf = nullptr;
@@ -280,20 +358,12 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
         Workspace* const W = Wv[pass & 1];                        // pass-local buffers
         const hipStream_t s = Sv[pass & 1];                       // (shadows the caller's stream inside the loop)
         uint32_t* d_cand_cnt = W->w_cnt.p + 2 * SUPER;
-        vdb::FusedBf16Params fp{};
-        fp.rows = ix->d_rows; fp.ld = ld; fp.n_rows = n;
-        fp.alpha = ix->d_alpha; fp.beta = ix->d_beta; fp.rowmask = d_rowmask ? d_rowmask : ix->d_live;
-        fp.margin = ix->d_margin;
-        fp.pool = W->w_pool.p; fp.pool_cnt = W->w_subcnt.p; fp.capl = capl; fp.n_wg = n_wg;
-        fp.scalars = ix->d_scalars; fp.qmax_bits = d_status + 2;
-        fp.ablate = ix->kn.bf16_ablate;
-        fp.n_sample = S; fp.sample_shift = pl.shift;
-        fp.sample_block = ix->kn.sample_block ? (n / (S / 256u)) : 0u; fp.minkeys = W->w_dense.p; fp.minkey_stride = M;
+        vdb::FusedBf16Params fp = pass_params(W);
         // ---- thresholds of the pass's blocks (unless they were all computed up front)
         if (!thr_first)
             for (uint32_t b = 0; b < n_blocks; ++b) thresholds_of(W, s, q0 + b * SUPER);
         // ---- ONE pass over the rows for all of them
-        fp.qb = ix->cur->w_qb.p + (size_t)q0 * ld; fp.qg = ix->d_margin ? ix->cur->w_qg.p + q0 : nullptr; fp.thr = ix->cur->w_thr.p + q0;
+        screen_queries(fp, ix, ix->cur->w_qb.p, ix->cur->w_qg.p, ix->cur->w_thr.p, q0);
         if (ix->profile) HIP_TRY(hipEventRecord(ix->ev0, s));
         if (wide) {
             fp.n_wg = n_wg_w; fp.pool_block_stride = pool_block; fp.cnt_block_stride = cnt_block;
@@ -330,13 +400,9 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
             mp.out_thr = nullptr; mp.ovf = d_ovf + qb0; mp.summary = d_status + 1;
             vdb::launch_select(mp, nb, s);
 
-            vdb::RerankParams rp{};
-            rp.rows = ix->d_rows; rp.ld = ld; rp.dim = ix->dim; rp.n_rows = n;
-            rp.qp = ix->cur->w_qp.p + (size_t)qb0 * ld; rp.qnorm = ix->cur->w_qnorm.p + qb0; rp.nd = ix->d_nd; rp.row_ids = ix->d_row_ids;
-            rp.rowmask = d_rowmask; rp.cand = W->w_cand.p; rp.cand_stride = kp; rp.cand_cnt = d_cand_cnt; rp.kp = kp;
-            rp.metric = ix->metric; rp.k = (uint32_t)k; rp.eps_coef = eps; rp.nd2max_bits = ix->d_scalars;
-            rp.out_ids = d_out_ids + (size_t)qb0 * k; rp.out_dists = d_out_dists + (size_t)qb0 * k;
-            rp.out_counts = d_out_counts + qb0; rp.out_stride = (uint32_t)k; rp.cert = d_cert + qb0; rp.status = d_status;
+            vdb::RerankParams rp = rerank_params(ix, d_rowmask, d_status, k, W->w_cand.p, kp, d_cand_cnt);
+            rerank_io(rp, ix, ix->cur->w_qp.p, ix->cur->w_qnorm.p, d_out_ids, d_out_dists, d_out_counts, d_cert, qb0);
+            rp.eps_coef = eps;
             rp.thr = ix->cur->w_thr.p + qb0;
             rp.qerr = ix->cur->w_qerr.p + qb0; rp.c_acc = c_acc_bf16(ix); rp.lb_scores = ix->d_margin ? 1u : 0u;
             rp.kp_first = round_up((uint32_t)k + 38u, 16u); rp.kp_step = 32;
@@ -354,24 +420,7 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
                 if (ix->kn.kp_first) rp.kp_first = ix->kn.kp_first;
                 vdb::launch_rerank_large(rp, nb, s);
             } else vdb::launch_rerank(rp, nb, s);
-            if (dump_depth) {
-                std::vector<uint32_t> dep((size_t)SUPER * 17);
-                HIP_TRY(hipMemcpyAsync(dep.data(), W->w_depth.p, dep.size() * 4, hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
-                // phase stamps (s_memrealtime, 100 MHz): 0 start, 1 query row in LDS, 2 round 1 staged+folded, 3 sorted, 4 depth decided, 5 last round folded, 6 end
-                const uint64_t* st64 = reinterpret_cast<const uint64_t*>(dep.data() + SUPER);
-                uint64_t t0 = ~0ull;
-                for (uint32_t q = 0; q < nb; ++q) t0 = std::min(t0, st64[(size_t)q * 8]);
-                for (int ph = 0; ph < 7; ++ph) {
-                    std::vector<double> v(nb);
-                    for (uint32_t q = 0; q < nb; ++q) v[q] = (double)(st64[(size_t)q * 8 + ph] - t0) * 0.01;
-                    std::sort(v.begin(), v.end());
-                    fprintf(stderr, "[vdb] re-rank phase %d at us: min %.2f median %.2f p90 %.2f max %.2f\n", ph, v[0], v[nb / 2], v[(size_t)nb * 9 / 10], v[nb - 1]);
-                }
-                std::sort(dep.begin(), dep.begin() + nb);
-                fprintf(stderr, "[vdb] re-rank depth of %u queries: min %u  p25 %u  median %u  p75 %u  p95 %u  max %u  (first round %u)\n", nb,
-                        dep[0], dep[nb / 4], dep[nb / 2], dep[(size_t)nb * 3 / 4], dep[(size_t)nb * 95 / 100], dep[nb - 1], rp.kp_first);
-            }
+            if (dump_depth && (rc = dump_rerank_depth(W, s, nb, rp.kp_first))) return rc;
         }
         q0 += n_blocks * SUPER;
     }
@@ -398,26 +447,17 @@ int pass_rethreshold(Index* ix, hipStream_t s, const std::vector<uint32_t>& todo
     const uint32_t nf = (uint32_t)todo.size(), nfp = round_up(nf, SUPER);
     constexpr uint32_t KMAX = 2048;                              // keys re-ranked per query at most (select capacity)
     const uint32_t capl = 256;
-    const uint32_t n_wg = std::min<uint32_t>((uint32_t)ix->n_cu, (n + vdb::fused_bf16_tile_rows() - 1) / vdb::fused_bf16_tile_rows());
+    const uint32_t n_wg = screen_grid(ix, vdb::fused_bf16_tile_rows());
     const uint32_t n_sub = vdb::fused_bf16_subpools_per_query(n_wg);
-    if ((rc = ix->cur->w2_qp.ensure((size_t)nfp * ld))) return rc;
-    if ((rc = ix->cur->w2_qnorm.ensure(nfp))) return rc;
-    if ((rc = ix->cur->w2_thr.ensure(nfp))) return rc;
     if ((rc = ix->cur->w2_qerr.ensure(nfp))) return rc;
     if ((rc = ix->cur->w2_qg.ensure(nfp))) return rc;
     if ((rc = ix->cur->w2_qb.ensure((size_t)nfp * ld))) return rc;
-    if ((rc = ix->cur->w2_outi.ensure((size_t)nf * k))) return rc;
-    if ((rc = ix->cur->w2_outd.ensure((size_t)nf * k))) return rc;
-    if ((rc = ix->cur->w2_outc.ensure(nf))) return rc;
-    if ((rc = ix->cur->w2_flags.ensure(2 * (size_t)nf))) return rc;
-    if ((rc = ix->cur->w2_qidx.ensure(nf))) return rc;
     if ((rc = ix->cur->w2_cand.ensure((size_t)SUPER * KMAX))) return rc;
     if ((rc = ix->cur->w_pool.ensure((size_t)SUPER * n_sub * capl))) return rc;
     if ((rc = ix->cur->w_subcnt.ensure((size_t)SUPER * n_sub))) return rc;
+    if ((rc = gather_compact(ix, s, todo, k, false))) return rc;             // (query_prep below zeroes the flags)
     uint32_t* d_cert2 = ix->cur->w2_flags.p;
     uint32_t* d_ovf2 = ix->cur->w2_flags.p + nf;
-    HIP_TRY(hipMemcpyAsync(ix->cur->w2_qidx.p, todo.data(), (size_t)nf * 4, hipMemcpyHostToDevice, s));
-    vdb::launch_gather_queries(ix->cur->w_qp.p, ix->cur->w_qnorm.p, ld, ix->cur->w2_qidx.p, nf, nfp, ix->cur->w2_qp.p, ix->cur->w2_qnorm.p, ix->cur->w2_thr.p, s);
     // bf16 image, |q - bf16(q)| and zeroed flags of the compact block (the rows are already padded: dim = ld)
     vdb::QueryPrepParams qp{ix->cur->w2_qp.p, ld, nf, ix->cur->w2_qp.p, ld, nfp, ix->cur->w2_qnorm.p, ix->cur->w2_thr.p, vdb::EUCLID, d_status,
                             ix->cur->w2_qb.p, ix->cur->w2_qerr.p, ix->d_margin ? ix->cur->w2_qg.p : nullptr, margin_plan(ix).kappa, d_cert2, d_ovf2};
@@ -426,12 +466,8 @@ int pass_rethreshold(Index* ix, hipStream_t s, const std::vector<uint32_t>& todo
     uint32_t* d_cand_cnt = ix->cur->w_cnt.p + 2 * SUPER;
     for (uint32_t q0 = 0; q0 < nf; q0 += SUPER) {
         const uint32_t nb = std::min(SUPER, nf - q0);
-        vdb::FusedBf16Params fp{};
-        fp.rows = ix->d_rows; fp.ld = ld; fp.n_rows = n; fp.qb = ix->cur->w2_qb.p + (size_t)q0 * ld;
-        fp.alpha = ix->d_alpha; fp.beta = ix->d_beta; fp.rowmask = d_rowmask ? d_rowmask : ix->d_live;
-        fp.margin = ix->d_margin; fp.qg = ix->d_margin ? ix->cur->w2_qg.p + q0 : nullptr;
-        fp.thr = ix->cur->w2_thr.p + q0; fp.pool = ix->cur->w_pool.p; fp.pool_cnt = ix->cur->w_subcnt.p; fp.capl = capl; fp.n_wg = n_wg;
-        fp.scalars = ix->d_scalars; fp.qmax_bits = d_status + 2;
+        vdb::FusedBf16Params fp = screen_params(ix, ix->cur, d_rowmask, d_status, capl, n_wg);
+        screen_queries(fp, ix, ix->cur->w2_qb.p, ix->cur->w2_qg.p, ix->cur->w2_thr.p, q0);
         launch_filter_pass(ix, fp, s);
         ix->cur->stats[3] += n;
         vdb::SelectParams mp{};
@@ -439,13 +475,8 @@ int pass_rethreshold(Index* ix, hipStream_t s, const std::vector<uint32_t>& todo
         mp.kk = KMAX; mp.out_keys = ix->cur->w2_cand.p; mp.out_stride = KMAX; mp.out_cnt = d_cand_cnt;
         mp.ovf = d_ovf2 + q0; mp.summary = nullptr; mp.flag_truncation = 1;
         vdb::launch_select(mp, nb, s);
-        vdb::RerankParams rp{};
-        rp.rows = ix->d_rows; rp.ld = ld; rp.dim = ix->dim; rp.n_rows = n;
-        rp.qp = ix->cur->w2_qp.p + (size_t)q0 * ld; rp.qnorm = ix->cur->w2_qnorm.p + q0; rp.nd = ix->d_nd; rp.row_ids = ix->d_row_ids;
-        rp.rowmask = d_rowmask; rp.cand = ix->cur->w2_cand.p; rp.cand_stride = KMAX; rp.cand_cnt = d_cand_cnt; rp.kp = KMAX;
-        rp.metric = ix->metric; rp.k = (uint32_t)k; rp.nd2max_bits = ix->d_scalars;
-        rp.out_ids = ix->cur->w2_outi.p + (size_t)q0 * k; rp.out_dists = ix->cur->w2_outd.p + (size_t)q0 * k;
-        rp.out_counts = ix->cur->w2_outc.p + q0; rp.out_stride = (uint32_t)k; rp.cert = d_cert2 + q0; rp.status = d_status;
+        vdb::RerankParams rp = rerank_params(ix, d_rowmask, d_status, k, ix->cur->w2_cand.p, KMAX, d_cand_cnt);
+        rerank_io(rp, ix, ix->cur->w2_qp.p, ix->cur->w2_qnorm.p, ix->cur->w2_outi.p, ix->cur->w2_outd.p, ix->cur->w2_outc.p, d_cert2, q0);
         vdb::launch_rerank_all(rp, nb, s);
     }
     HIP_TRY(hipGetLastError());
@@ -533,9 +564,8 @@ static int search_direct(Index* ix, hipStream_t s, const float* d_q, uint32_t nq
         HIP_TRY(hipMemsetAsync(W->w_dstat.p, 0, 16, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
-    if (status & vdb::ST_ZERO_QUERY)
-        return fail(VDB_ERR_INVALID_VECTOR, "Invalid vector: Cannot compute cosine distance with zero vector");
-    if (status & vdb::ST_NAN) return fail(VDB_ERR_NAN, "NaN distance (the reference panics here, flat_index.rs:62)");
+    if (status & vdb::ST_ZERO_QUERY) return fail_zero_vector();
+    if (status & vdb::ST_NAN) return fail_nan();
     return VDB_OK;
 }
 
@@ -574,7 +604,7 @@ int search_part1(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, c
     if (ix->metric == vdb::COSINE) {
         if ((rc = ensure_zero_count(ix))) return rc;
         if (ix->zero_live)   // distance.rs:51-55 aborts the whole search (flat_index.rs:57-60)
-            return fail(VDB_ERR_INVALID_VECTOR, "Invalid vector: Cannot compute cosine distance with zero vector");
+            return fail_zero_vector();
     }
     if (nq > 0x7fffffffull / 2 || k > 0x7fffffffull) return fail(VDB_ERR_INVALID_ARGUMENT, "batch too large");
     if (ix->dim > 16384) return fail(VDB_ERR_INVALID_ARGUMENT, "dimension %u exceeds the supported 16384", ix->dim);
@@ -652,7 +682,7 @@ int search_part1(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, c
         HIP_TRY(hipMemcpyAsync(ix->cur->h_flags, ix->cur->w_flags.p, 16, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         if (ix->cur->h_flags[0] & vdb::ST_ZERO_QUERY)
-            return fail(VDB_ERR_INVALID_VECTOR, "Invalid vector: Cannot compute cosine distance with zero vector");
+            return fail_zero_vector();
         for (uint32_t q = 0; q < nq32; ++q) {
             if ((rc = exact_one(ix, s, q, k, d_rowmask, d_out_ids + (size_t)q * k, d_out_dists + (size_t)q * k,
                                 d_out_counts + q)))
@@ -661,7 +691,7 @@ int search_part1(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, c
         ix->cur->stats[1] = nq32;
         HIP_TRY(hipMemcpyAsync(ix->cur->h_flags, ix->cur->w_flags.p, 16, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        if (ix->cur->h_flags[0] & vdb::ST_NAN) return fail(VDB_ERR_NAN, "NaN distance (the reference panics here, flat_index.rs:62)");
+        if (ix->cur->h_flags[0] & vdb::ST_NAN) return fail_nan();
         return VDB_OK;
     }
 
@@ -710,8 +740,7 @@ int search_part2(Index* ix, int* changed) {
     HIP_TRY(hipStreamSynchronize(s));
     ix->cur->stats[11] = since();                       // ... until the first tier's flags are on the host, ns
     uint32_t status = ix->cur->h_flags[0];
-    if (status & vdb::ST_ZERO_QUERY)
-        return fail(VDB_ERR_INVALID_VECTOR, "Invalid vector: Cannot compute cosine distance with zero vector");
+    if (status & vdb::ST_ZERO_QUERY) return fail_zero_vector();
     // vdb_flat_set_tiers: forced hand-over to the slower tiers (tests); every tier returns the same results
     const bool force_exact = (ix->tiers & VDB_TIERS_FORCE_EXACT) != 0;
     const bool force_f32 = (ix->tiers & VDB_TIERS_FORCE_F32) != 0;
@@ -751,20 +780,9 @@ int search_part2(Index* ix, int* changed) {
     }
     if (kp16 && !todo.empty()) {
         // ---- second tier: the uncertified queries as one compact block through the f32 MFMA pipeline
-        const uint32_t nf = (uint32_t)todo.size(), nfp = round_up(nf, SUPER);
+        const uint32_t nf = (uint32_t)todo.size();
         ix->cur->stats[9] = nf;
-        if ((rc = ix->cur->w2_qp.ensure((size_t)nfp * ld))) return rc;
-        if ((rc = ix->cur->w2_qnorm.ensure(nfp))) return rc;
-        if ((rc = ix->cur->w2_thr.ensure(nfp))) return rc;
-        if ((rc = ix->cur->w2_outi.ensure((size_t)nf * k))) return rc;
-        if ((rc = ix->cur->w2_outd.ensure((size_t)nf * k))) return rc;
-        if ((rc = ix->cur->w2_outc.ensure(nf))) return rc;
-        if ((rc = ix->cur->w2_flags.ensure(2 * (size_t)nf))) return rc;
-        if ((rc = ix->cur->w2_qidx.ensure(nf))) return rc;
-        HIP_TRY(hipMemcpyAsync(ix->cur->w2_qidx.p, todo.data(), (size_t)nf * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemsetAsync(ix->cur->w2_flags.p, 0, 2 * (size_t)nf * 4, s));
-        vdb::launch_gather_queries(ix->cur->w_qp.p, ix->cur->w_qnorm.p, ld, ix->cur->w2_qidx.p, nf, nfp, ix->cur->w2_qp.p, ix->cur->w2_qnorm.p,
-                                   ix->cur->w2_thr.p, s);
+        if ((rc = gather_compact(ix, s, todo, k, true))) return rc;
         if (kp == 0) {
             // k too large for the f32 tier (the large-k screening tier's uncertified queries): straight to the exact scan (flags stay 0)
         } else {
@@ -781,7 +799,7 @@ int search_part2(Index* ix, int* changed) {
         HIP_TRY(hipStreamSynchronize(s));
         status |= f2[2 * (size_t)nf];
         if (status & vdb::ST_ZERO_QUERY)
-            return fail(VDB_ERR_INVALID_VECTOR, "Invalid vector: Cannot compute cosine distance with zero vector");
+            return fail_zero_vector();
         std::vector<uint32_t> todo2;
         for (uint32_t j = 0; j < nf; ++j) {
             bool cert = f2[j] != 0, ovf = f2[nf + j] != 0;
@@ -849,7 +867,7 @@ int search_part2(Index* ix, int* changed) {
     // values may stay, a wild one must not outlive its search)
     ix->cur->status_dirty = st2 != 0 || ix->cur->stats[6] != 0 || ix->cur->stats[2] != 0 || ix->cur->h_flags[2] > 0x53800000u;
     if (st2 & vdb::ST_NAN)
-        return fail(VDB_ERR_NAN, "NaN distance (the reference panics here, flat_index.rs:62)");
+        return fail_nan();
     return VDB_OK;
 }
 
