@@ -52,7 +52,13 @@ void vdb_hnsw_destroy(vdb_hnsw_index *h);
  * level and new lists, vdb_hnsw_len counts the id once more, and every list of another node that names the id keeps naming it
  * -- also above its new level, also a link a remove left behind -- and from then on leads to the new vector.  The entry point and
  * max_level are only ever raised (graph.rs:336-339).  Such an insert is not a fast path: the device mirror is rebuilt and the
- * lists that name the id are looked up by reading every list. */
+ * lists that name the id are looked up by reading every list.
+ * IDS: a node id must be below 2^32 - 16.  The graph is an array indexed by id here as in the reference (graph.rs:78, :249-251:
+ * an id costs id + 1 slots), and the device mirror addresses nodes with 32 bits, 0xffffffff meaning "none".  An id at or above
+ * 2^32 - 16 is refused with VDB_ERR_INVALID_ARGUMENT by vdb_hnsw_add and by vdb_hnsw_add_bulk -- the whole batch, before any of
+ * it is inserted, also with ids == NULL, where the ids are first_id + i: the first of them is checked first, so a sum that
+ * wraps past 2^64 is never reached -- and is never truncated; the calls that only look an id up (remove, get_vector, neighbors, node_level) treat
+ * such an id as absent.  (The flat index of vdb_flat.h takes any uint64_t as an id.) */
 int vdb_hnsw_add(vdb_hnsw_index *h, uint64_t id, const float *v, size_t dim, long level);
 /* HnswIndex::build_batch (mod.rs:37-42): sequential inserts of rows [n][dim]; ids NULL: first_id + i.  Ids seen before and an
  * id named twice in one batch are inserted in their place in the sequence, each occurrence with ITS vector, as described at

@@ -31,9 +31,12 @@ def merge_topk_torch(ids, dists, counts, k):
     W, B, kk = ids.shape
     valid = torch.arange(kk, device=ids.device).view(1, 1, kk) < counts.view(W, B, 1)
     d = torch.where(valid, dists, torch.full_like(dists, float("inf"))).permute(1, 0, 2).reshape(B, W * kk)
-    i = torch.where(valid, ids, torch.full_like(ids, torch.iinfo(torch.int64).max)).permute(1, 0, 2).reshape(B, W * kk)
-    # stable two-key sort: by id first, then (stable) by distance
-    o1 = torch.sort(i, dim=1, stable=True).indices
+    # ids are uint64 held in int64 tensors: flipping the sign bit makes the signed sort below order them as unsigned.  Invalid
+    # slots take the all-ones id, but it is their infinite distance that keeps them last -- 2^64 - 1 is a legal id.
+    # (A VALID entry whose distance is +inf cannot be told from padding here; that limit is as old as this function.)
+    i = torch.where(valid, ids, torch.full_like(ids, -1)).permute(1, 0, 2).reshape(B, W * kk)
+    # stable two-key sort: by (unsigned) id first, then (stable) by distance
+    o1 = torch.sort(i ^ torch.iinfo(torch.int64).min, dim=1, stable=True).indices
     d1, i1 = torch.gather(d, 1, o1), torch.gather(i, 1, o1)
     o2 = torch.sort(d1, dim=1, stable=True).indices
     d2, i2 = torch.gather(d1, 1, o2), torch.gather(i1, 1, o2)

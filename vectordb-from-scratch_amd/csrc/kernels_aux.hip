@@ -1117,9 +1117,10 @@ __global__ __launch_bounds__(RR_THREADS) void rerank_kernel(RerankParams p) {
         }
 #undef VDB_CEX
         if (processed <= p.kp_first) { VDB_STAMP(3) }
-        // number of real candidates so far (ineligible ones sorted to the end with id ~0)
+        // number of real candidates so far: ineligible ones keep the padding distance 0xffffffff and sort to the end.  (The id
+        // cannot tell them apart: 2^64 - 1 is a legal id.  Only a NaN could order as 0xffffffff, and a NaN distance fails the search.)
         if (tid < RR_MAX) {
-            unsigned long long b0 = __ballot(tid < processed && sId[tid] != ~0ull);
+            unsigned long long b0 = __ballot(tid < processed && sDist[tid] != 0xffffffffu);
             if (lane == 0) sRealW[wv] = (uint32_t)__popcll(b0);
         }
         __syncthreads();
@@ -1266,7 +1267,8 @@ __global__ __launch_bounds__(RR_THREADS) void rerank_all_kernel(RerankParams p) 
     uint32_t nout = 0;
     {
         __shared__ uint32_t sCnt[RR_THREADS / 64];
-        const unsigned long long b0 = __ballot(tid < p.k && sId[tid < AREA ? tid : 0] != ~0ull);
+        // (counted by the padding distance, not by the id: 2^64 - 1 is a legal id)
+        const unsigned long long b0 = __ballot(tid < p.k && sDist[tid < AREA ? tid : 0] != 0xffffffffu);
         if (lane == 0) sCnt[wv] = (uint32_t)__popcll(b0);
         __syncthreads();
         for (uint32_t w8 = 0; w8 < RR_THREADS / 64; ++w8) nout += sCnt[w8];
