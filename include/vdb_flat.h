@@ -314,6 +314,41 @@ int vdb_flat_set_large_k(vdb_flat_index *h, int on);
 size_t vdb_flat_large_k_min_rows(size_t k);
 
 /*
+ * The SPARSE-FILTER route of pre-filtered searches (no reference counterpart; results are identical whatever the mode, bit for
+ * bit).  A search with an id mask normally costs one pass over every stored row, whatever the mask lets through.  On this route
+ * the eligible rows (live AND admitted by the mask) are gathered into a list on the device, the reference distance of every
+ * (query, eligible row) pair is computed in the reference's operation order (csrc/kernels_sparse.hip), and the k smallest by
+ * (distance, id) are written as the results: only the eligible rows are read.
+ *  0 (default): never -- every search runs as if this setting did not exist;
+ *  1: always -- every search that carries an id mask takes the route when k <= 2048 and at most 131072 rows are eligible
+ *     (also on indexes small enough for the direct path); otherwise it continues into the tiers unchanged;
+ *  2: automatic -- as 1, but only when the list is at most vdb_flat_sparse_limit(rows, padded dimension, dimension, nq) long,
+ *     and indexes of at most 16384 rows with batches of at most 8 queries keep their direct path.
+ * In modes 1 and 2 a masked search reads the eligible-row count back (4 bytes, one stream synchronisation) before it chooses.
+ * Searches without an id mask are never affected.  Errors are those of the exact scans under a row mask: the dimension checks
+ * and the zero-norm-row check under Cosine come first, a zero-norm query is an InvalidVector error, a NaN distance among the
+ * ELIGIBLE rows is VDB_ERR_NAN.  A search answered by the route is complete when _begin / _submit return.
+ * On a sharded handle the setting applies to every shard, and every shard decides from its own list.
+ */
+int vdb_flat_set_sparse_filter(vdb_flat_index *h, int mode);
+/* out[0] = 1 when the last search on the handle was answered by the route, [1] = eligible rows of the last masked search made
+ * with mode != 0, [2] = searches answered by the route since creation, [3] = 0 (reserved).  Sharded handle: [0] is the OR over
+ * the shards, [1] and [2] are sums. */
+int vdb_flat_sparse_stats(vdb_flat_index *h, uint64_t out[4]);
+/* The longest list of eligible rows that mode 2 sends to the route for an index (or shard) of n_rows rows of ld floats (the
+ * dimension rounded up to 32), queries of `dim` elements and a batch of nq: E * nq * dim <= C * n_rows * ld with the measured
+ * constant C, never above 131072 or n_rows.  0 for an empty index.  Needs no handle and no device. */
+size_t vdb_flat_sparse_limit(size_t n_rows, size_t ld, size_t dim, size_t nq);
+/* Diagnostics (tests).  vdb_flat_debug_eligible_rows flushes, builds the row mask and the eligible-row list exactly as a search
+ * on the route would -- id_mask in the layout of vdb_flat_search_batch, in device OR host memory -- and copies the first `cap`
+ * device rows (ascending) to out and the length of the list to *count; no distance is computed.  Not on a sharded handle.
+ * vdb_flat_debug_sparse_tile_rows / _queries: the tile of one workgroup of the scan kernel, in list positions and queries. */
+int vdb_flat_debug_eligible_rows(vdb_flat_index *h, const uint64_t *id_mask, size_t mask_bits, uint32_t *out, size_t cap,
+                                 size_t *count);
+size_t vdb_flat_debug_sparse_tile_rows(void);
+size_t vdb_flat_debug_sparse_tile_queries(void);
+
+/*
  * Opt-in bf16 SHADOW of the rows for the screening pass (no reference counterpart; results are identical with and without
  * it).  on = 1: the index keeps, next to the f32 rows, their bf16 roundings (+50 % device memory: 2 bytes per element on top
  * of 4) -- exactly the values the screening kernel otherwise produces in registers -- and the filter pass streams THOSE:

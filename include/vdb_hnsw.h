@@ -85,6 +85,16 @@ int vdb_hnsw_search_batch_masked(vdb_hnsw_index *h, const float *queries, size_t
                                  const uint64_t *id_mask, size_t mask_bits, uint64_t *out_ids, float *out_dists,
                                  size_t *out_counts);
 
+/* The brute-force route of very selective filters (default 0 = never: every masked search is walked, as described above).  With
+ * max_eligible > 0 a vdb_hnsw_search_batch_masked call whose mask leaves at most max_eligible PRESENT nodes eligible (and k <=
+ * 2048; max_eligible is capped at 131072) is not walked: the inner flat index scans exactly those nodes' vectors
+ * (vdb_flat_set_sparse_filter of vdb_flat.h) and returns the EXACT filtered k nearest neighbours, ascending by (distance, id),
+ * out_counts[b] = min(k, eligible present nodes).  These results are exact and therefore differ from the walk's approximate ones
+ * (they are what the walk converges to with a large ef); ids the graph has removed or replaced never appear.  Under Cosine a
+ * stored zero-norm vector fails the scan as it fails a flat search.  Above the limit, or without a mask, the walk runs as before.
+ * vdb_hnsw_stats()[1] counts such a search as one launch. */
+int vdb_hnsw_set_filter_scan(vdb_hnsw_index *h, size_t max_eligible);
+
 /* Test hook (results are identical either way): host_only = 1 sends every search through the host traversal instead of
  * the device-resident walk; host_threads > 0 fixes its worker-thread count (0 = automatic).  Not read from the environment. */
 int vdb_hnsw_set_traversal(vdb_hnsw_index *h, int host_only, size_t host_threads);

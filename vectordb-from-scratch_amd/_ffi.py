@@ -16,11 +16,12 @@ SYMBOLS = [
     "vdb_flat_load_vector_file", "vdb_flat_remove", "vdb_flat_get_vector", "vdb_flat_len", "vdb_flat_metric", "vdb_flat_dim",
     "vdb_flat_reserve", "vdb_flat_flush", "vdb_flat_compact", "vdb_flat_set_auto_compact", "vdb_flat_store_stats", "vdb_flat_search", "vdb_flat_search_batch",
     "vdb_flat_search_batch_device", "vdb_flat_search_batch_device_begin", "vdb_flat_search_batch_device_finish", "vdb_flat_search_batch_device_submit", "vdb_flat_search_batch_device_wait", "vdb_flat_distances_batch", "vdb_merge_topk_device", "vdb_merge_topk_packed_device", "vdb_flat_set_profile", "vdb_flat_last_stats", "vdb_flat_last_stats_ex", "vdb_flat_set_screen", "vdb_flat_set_wide", "vdb_flat_set_large_k", "vdb_flat_large_k_min_rows", "vdb_flat_set_shadow", "vdb_flat_set_sample_cache", "vdb_flat_set_tiers", "vdb_flat_debug_screen_scores", "vdb_flat_debug_rows", "vdb_flat_debug_row_info", "vdb_flat_debug_last_thresholds", "vdb_flat_debug_cert_probe", "vdb_flat_debug_compact_plan", "vdb_flat_debug_set_compact_bounce", "vdb_last_error",
+    "vdb_flat_set_sparse_filter", "vdb_flat_sparse_stats", "vdb_flat_sparse_limit", "vdb_flat_debug_eligible_rows", "vdb_flat_debug_sparse_tile_rows", "vdb_flat_debug_sparse_tile_queries",
     "vdb_abi_version", "vdb_build_arch",
     # include/vdb_hnsw.h
     "vdb_hnsw_create", "vdb_hnsw_destroy", "vdb_hnsw_add", "vdb_hnsw_add_bulk", "vdb_hnsw_remove", "vdb_hnsw_search_batch", "vdb_hnsw_search_batch_masked",
     "vdb_hnsw_len", "vdb_hnsw_metric", "vdb_hnsw_get_vector", "vdb_hnsw_neighbors", "vdb_hnsw_node_level",
-    "vdb_hnsw_entry_point", "vdb_hnsw_stats", "vdb_hnsw_set_traversal", "vdb_hnsw_set_build", "vdb_hnsw_build_stats", "vdb_hnsw_build_times",
+    "vdb_hnsw_entry_point", "vdb_hnsw_stats", "vdb_hnsw_set_traversal", "vdb_hnsw_set_build", "vdb_hnsw_build_stats", "vdb_hnsw_build_times", "vdb_hnsw_set_filter_scan",
     # include/vdb_shard.h
     "vdb_shard_unique_id", "vdb_shard_group_create", "vdb_shard_group_destroy", "vdb_shard_group_rank", "vdb_shard_group_world",
     "vdb_shard_range", "vdb_flat_search_batch_sharded", "vdb_shard_group_last_stats",
@@ -110,6 +111,15 @@ def lib():
     L.vdb_flat_set_screen.argtypes = [vp, c.c_int]
     L.vdb_flat_set_wide.argtypes = [vp, c.c_int]
     L.vdb_flat_set_large_k.argtypes = [vp, c.c_int]
+    L.vdb_flat_set_sparse_filter.argtypes = [vp, c.c_int]
+    L.vdb_flat_sparse_stats.argtypes = [vp, u64p]
+    L.vdb_flat_sparse_limit.argtypes = [sz, sz, sz, sz]
+    L.vdb_flat_sparse_limit.restype = sz
+    L.vdb_flat_debug_eligible_rows.argtypes = [vp, vp, sz, u32p, sz, szp]
+    L.vdb_flat_debug_sparse_tile_rows.argtypes = []
+    L.vdb_flat_debug_sparse_tile_rows.restype = sz
+    L.vdb_flat_debug_sparse_tile_queries.argtypes = []
+    L.vdb_flat_debug_sparse_tile_queries.restype = sz
     L.vdb_flat_large_k_min_rows.argtypes = [sz]
     L.vdb_flat_large_k_min_rows.restype = sz
     L.vdb_flat_set_tiers.argtypes = [vp, c.c_uint]
@@ -143,6 +153,7 @@ def lib():
     L.vdb_hnsw_entry_point.argtypes = [vp, u64p, szp]
     L.vdb_hnsw_stats.argtypes = [vp, u64p]
     L.vdb_hnsw_set_traversal.argtypes = [vp, c.c_int, sz]
+    L.vdb_hnsw_set_filter_scan.argtypes = [vp, sz]
     L.vdb_hnsw_set_build.argtypes = [vp, c.c_int]
     L.vdb_hnsw_build_stats.argtypes = [vp, u64p]
     L.vdb_hnsw_build_times.argtypes = [vp, c.POINTER(c.c_double)]

@@ -363,6 +363,26 @@ struct ExactMultiParams {
 };
 void launch_exact_multi(const ExactMultiParams& p, hipStream_t s);
 
+// ---------------------------------------------------------------- sparse-filter route (kernels_sparse.hip)
+// The ascending list of the rows whose bit is set in a search's row mask (bits at or above n_rows never count), in two steps
+// with the host in between: launch_sparse_count leaves E in *total (block_cnt / block_off: sparse_list_blocks(n_rows) words
+// each), the host reads it and sizes elig[], launch_sparse_scatter writes elig[0..E) (positions >= cap are dropped).
+uint32_t sparse_list_blocks(uint32_t n_rows);
+void launch_sparse_count(const uint32_t* rowmask, uint32_t n_rows, uint32_t* block_cnt, uint32_t* block_off, uint32_t* total, hipStream_t s);
+void launch_sparse_scatter(const uint32_t* rowmask, uint32_t n_rows, const uint32_t* block_off, uint32_t* elig, uint32_t cap, hipStream_t s);
+// The exact reference distance of every (query, eligible row) pair; one workgroup = SPARSE_TILE_R list positions x SPARSE_TILE_Q queries.
+constexpr uint32_t SPARSE_TILE_R = 64, SPARSE_TILE_Q = 64;
+struct SparseScanParams {
+    const float* rows; uint32_t ld; uint32_t dim; uint32_t n_rows;
+    const uint32_t* elig; uint32_t n_elig;             // device rows, ascending; an entry >= n_rows is skipped
+    const float* qp; const float* qnorm; uint32_t nq;  // prepared queries of this pass (query_prep), their exact-order norms
+    const float* nd; const uint32_t* idrank; int metric;
+    uint64_t* keys; uint32_t key_stride;               // keys[q * key_stride + j], j = position in elig; key = ordered(dist) << 32 | id rank.
+                                                       // key_stride = n_elig rounded up to SPARSE_TILE_R: the padding gets EMPTY_KEY
+    uint32_t* status;                                  // ST_NAN
+};
+void launch_sparse_scan(const SparseScanParams& p, hipStream_t s);
+
 struct EmitParams {                                    // sorted exact keys -> (id, dist) outputs
     const uint64_t* keys; uint32_t cnt_max; const uint32_t* cnt;
     const uint32_t* rank2row; const uint64_t* row_ids;

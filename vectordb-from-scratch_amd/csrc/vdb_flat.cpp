@@ -1035,6 +1035,80 @@ size_t vdb_flat_large_k_min_rows(size_t k) {
     return (k <= BF16_MAX_K || k > LARGE_K_MAX) ? 0 : (size_t)std::max<uint64_t>(large_k_min_rows(k), BF16_MIN_ROWS);
 }
 
+// ------------------------------------------------------------------ sparse-filter route (vdb_search.cpp search_sparse)
+int vdb_flat_set_sparse_filter(vdb_flat_index* ix, int mode) {
+    return guarded([&]() -> int {
+    if (!ix || mode < 0 || mode > 2) return fail(VDB_ERR_INVALID_ARGUMENT, "mode must be 0, 1 or 2");
+    if (ix->multi) return multi_for_each(ix, [mode](vdb_flat_index* c) { return vdb_flat_set_sparse_filter(c, mode); });
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->sparse_mode = mode;
+    return VDB_OK;
+    });
+}
+
+int vdb_flat_sparse_stats(vdb_flat_index* ix, uint64_t out[4]) {
+    return guarded([&]() -> int {
+    if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (ix->multi) {
+        std::mutex acc;                                            // (the shards are visited concurrently)
+        return multi_for_each(ix, [&](vdb_flat_index* c) -> int {
+            uint64_t v[4];
+            int rc = vdb_flat_sparse_stats(c, v);
+            if (rc) return rc;
+            std::lock_guard<std::mutex> a(acc);
+            out[0] |= v[0]; out[1] += v[1]; out[2] += v[2];
+            return VDB_OK;
+        });
+    }
+    std::lock_guard<std::mutex> g(ix->mu);
+    out[0] = ix->sparse_last; out[1] = ix->sparse_E; out[2] = ix->sparse_count;
+    return VDB_OK;
+    });
+}
+
+size_t vdb_flat_sparse_limit(size_t n_rows, size_t ld, size_t dim, size_t nq) { return sparse_limit(n_rows, ld, dim, nq); }
+size_t vdb_flat_debug_sparse_tile_rows(void) { return vdb::SPARSE_TILE_R; }
+size_t vdb_flat_debug_sparse_tile_queries(void) { return vdb::SPARSE_TILE_Q; }
+
+int vdb_flat_debug_eligible_rows(vdb_flat_index* ix, const uint64_t* id_mask, size_t mask_bits, uint32_t* out, size_t cap, size_t* count) {
+    return guarded([&]() -> int {
+    if (ix && ix->multi) return refuse_multi("vdb_flat_debug_eligible_rows");
+    if (!ix || !id_mask || !count || (cap && !out)) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (in_flight(ix)) return refuse_in_flight();
+    int rc;
+    if ((rc = set_device(ix))) return rc;
+    if ((rc = flush(ix))) return rc;
+    *count = 0;
+    const uint32_t n = ix->n_uploaded;
+    if (!n) return VDB_OK;
+    hipStream_t s = ix->stream;
+    // the mask may be handed over in host memory: it is copied to the device like vdb_flat_search_batch's
+    const uint64_t* d_mask = id_mask;
+    hipPointerAttribute_t at{};
+    const bool on_device = hipPointerGetAttributes(&at, id_mask) == hipSuccess && at.type == hipMemoryTypeDevice;
+    if (!on_device) {
+        (void)hipGetLastError();
+        const size_t words = (mask_bits + 63) / 64;
+        if ((rc = ix->cur->w_mask_ids.ensure(std::max<size_t>(words, 1)))) return rc;
+        if (words) HIP_TRY(hipMemcpyAsync(ix->cur->w_mask_ids.p, id_mask, words * 8, hipMemcpyHostToDevice, s));
+        d_mask = ix->cur->w_mask_ids.p;
+    }
+    if ((rc = ix->cur->w_rowmask.ensure((n + 31) / 32))) return rc;
+    vdb::launch_build_rowmask(ix->d_row_ids, (ix->n_live == n) ? nullptr : ix->d_live, d_mask, mask_bits, n, ix->cur->w_rowmask.p, s);
+    uint32_t E = 0;
+    if ((rc = eligible_count(ix, s, ix->cur->w_rowmask.p, &E))) return rc;
+    *count = E;
+    if (!E) return VDB_OK;
+    if ((rc = eligible_list(ix, s, ix->cur->w_rowmask.p, E))) return rc;
+    const size_t take = std::min<size_t>(cap, E);
+    if (take) HIP_TRY(hipMemcpyAsync(out, ix->cur->w_elig.p, take * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return VDB_OK;
+    });
+}
+
 int vdb_flat_create_sharded(int metric, const int* devices, size_t n_devices, vdb_flat_index** out) {
     return guarded([&]() -> int { return multi_create(metric, devices, n_devices, out); });
 }

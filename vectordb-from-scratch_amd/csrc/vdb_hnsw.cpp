@@ -157,6 +157,7 @@ struct vdb_hnsw_index {
     float* h_scan[2] = {nullptr, nullptr}; float* d_scan[2] = {nullptr, nullptr}; size_t scan_ld = 0;
     hipStream_t scan_stream = nullptr; hipEvent_t scan_ev[2] = {nullptr, nullptr};
     bool host_only = false; size_t host_threads = 0;              // vdb_hnsw_set_traversal
+    size_t filter_scan = 0;                                       // vdb_hnsw_set_filter_scan: masks leaving at most this many present nodes are scanned exactly (0 = never)
     // incremental mirror: capacity in node ids / pooled upper lists, the upper-list offset of every node, and the nodes whose
     // lists changed since the mirror was last brought up to date (inserts touch ~33 nodes each; a bulk build syncs per chunk)
     uint32_t cap_ids = 0, cap_upper = 0, n_upper_used = 0;
@@ -1238,6 +1239,25 @@ bool mask_admits_a_node(const vdb_hnsw_index* g, const uint64_t* id_mask, size_t
     return false;
 }
 
+// The mask with the graph's presence ANDed in (so that a row the inner flat index may still hold for an id the graph dropped can
+// never be returned), when it leaves at most `limit` present nodes eligible; false -- and `out` unspecified -- above the limit.
+bool present_mask_within(const vdb_hnsw_index* g, const uint64_t* id_mask, size_t mask_bits, size_t limit, std::vector<uint64_t>& out) {
+    const size_t nb = std::min(mask_bits, g->nodes.size());
+    out.assign((nb + 63) / 64, 0ull);
+    size_t cnt = 0;
+    for (size_t w = 0; w * 64 < nb; ++w) {
+        uint64_t x = id_mask[w];
+        if (nb - w * 64 < 64) x &= (1ull << (nb - w * 64)) - 1ull;
+        for (; x; x &= x - 1) {
+            const size_t b = (size_t)__builtin_ctzll(x);
+            if (!g->nodes[w * 64 + b].present) continue;
+            if (++cnt > limit) return false;
+            out[w] |= 1ull << b;
+        }
+    }
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1273,6 +1293,19 @@ int vdb_hnsw_search_batch_masked(vdb_hnsw_index* g, const float* queries, size_t
         }
         return VDB_OK;
     }
+    if (id_mask && g->filter_scan && k > 0 && k <= 2048) {
+        // vdb_hnsw_set_filter_scan: a mask this selective is answered by an exact scan of its eligible rows in the inner flat
+        // index (the sparse-filter route of vdb_flat.h) -- the walk would overflow its heap and be re-run on the host
+        std::vector<uint64_t> pm;
+        if (present_mask_within(g, id_mask, mask_bits, std::min<size_t>(g->filter_scan, 131072), pm)) {
+            int rc;
+            if ((rc = vdb_flat_set_sparse_filter(g->flat, 1))) return rc;
+            rc = vdb_flat_search_batch(g->flat, queries, nq, dim, nullptr, k, pm.data(), pm.size() * 64, k, out_ids, out_dists, out_counts);
+            (void)vdb_flat_set_sparse_filter(g->flat, 0);
+            g->stats[1]++;
+            return rc;
+        }
+    }
     const bool on_device = !g->host_only && k > 0 && g->nodes.size() < 0xffffffffull &&
                            vdb::hnsw_search_supported((uint32_t)g->dim, (uint32_t)std::min<size_t>(ef_actual, 0xffffffu), (uint32_t)std::min<size_t>(k, 0xffffffu),
                                                       (uint32_t)std::max(g->m_max0, g->m) + 1);
@@ -1304,6 +1337,15 @@ int vdb_hnsw_set_traversal(vdb_hnsw_index* g, int host_only, size_t host_threads
     std::lock_guard<std::mutex> lk(g->mu);
     g->host_only = host_only != 0;
     g->host_threads = std::min<size_t>(host_threads, 64);
+    return VDB_OK;
+    });
+}
+
+int vdb_hnsw_set_filter_scan(vdb_hnsw_index* g, size_t max_eligible) {
+    return guarded([&]() -> int {
+    if (!g) return vdb_internal::set_error(VDB_ERR_INVALID_ARGUMENT, "null handle");
+    std::lock_guard<std::mutex> lk(g->mu);
+    g->filter_scan = max_eligible;
     return VDB_OK;
     });
 }

@@ -81,6 +81,7 @@ constexpr uint32_t SMALL_N = 16384;     // at or below: dense scores of every ro
 constexpr uint32_t SUPER = 256;         // queries per pipeline pass
 constexpr uint32_t MAX_SELECT = 2048;   // select kernel capacity (kk)
 constexpr uint32_t DIRECT_MAX_Q = 8;    // the direct exact path of small indexes takes batches up to this many queries
+constexpr uint32_t SPARSE_MAX_E = 131072;   // sparse-filter route: eligible rows at most (one pass's key buffer: 256 x 131072 x 8 B = 256 MiB)
 
 }  // namespace vdbi
 
@@ -89,6 +90,7 @@ struct Workspace {
     uint32_t dbg_nq = 0; bool dbg_lb = false, dbg_f32 = false;             // vdb_flat_debug_screen_scores left this many prepared queries in the workspace
     vdbi::DevBuf<uint64_t> w_dense, w_samp, w_pool, w_cand, w_exact, w_exsel, w_mask_ids, w_outi;
     vdbi::DevBuf<uint32_t> w_cnt, w_rowmask, w_flags, w_outc, w_subcnt, w_depth;
+    vdbi::DevBuf<uint32_t> w_elig, w_eligblk;                     // sparse-filter route: the eligible-row list; block counts | block offsets | E
     vdbi::DevBuf<uint16_t> w_qb;                                  // bf16 copy of the padded queries (screening tier)
     // compact block of the queries the screening tier could not certify (re-run by the f32 tier)
     vdbi::DevBuf<float> w2_qp, w2_qnorm, w2_thr, w2_outd, w2_qerr, w2_qg;
@@ -121,7 +123,7 @@ struct Workspace {
         f(w_dense); f(w_samp); f(w_pool); f(w_cand); f(w_exact); f(w_exsel); f(w_mask_ids); f(w_outi);
         f(w_cnt); f(w_rowmask); f(w_flags); f(w_outc); f(w_subcnt); f(w_depth); f(w_qb);
         f(w2_qp); f(w2_qnorm); f(w2_thr); f(w2_outd); f(w2_qerr); f(w2_qg); f(w2_outi); f(w2_cand); f(w2_qb);
-        f(w2_outc); f(w2_flags); f(w2_qidx); f(w_dstat);
+        f(w2_outc); f(w2_flags); f(w2_qidx); f(w_dstat); f(w_elig); f(w_eligblk);
     }
 };
 
@@ -203,6 +205,9 @@ struct vdb_flat_index {
     bool wide = true;                                       // batches above 256 queries: the 512-query filter kernel (vdb_flat_set_wide)
     bool large_k = true;                                    // 112 < k <= 1024 on the screening tier (vdb_flat_set_large_k)
     uint64_t stats[16] = {0};                               // counters of the last COMPLETED search (copied from its context)
+    // vdb_flat_set_sparse_filter: 0 never (default), 1 always, 2 automatic -- masked searches scan only the eligible rows (search_sparse)
+    int sparse_mode = 0;
+    uint64_t sparse_last = 0, sparse_E = 0, sparse_count = 0;  // vdb_flat_sparse_stats [0] [1] [2]
     bool profile = false; hipEvent_t ev0 = nullptr, ev1 = nullptr;
 
     uint32_t n_rows() const { return (uint32_t)row_ids.size(); }
@@ -255,6 +260,9 @@ int search_part1(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, c
                  hipStream_t user_stream, bool allow_alt = false);
 int search_part2(Index* ix, int* changed);
 bool direct_eligible(const Index* ix, size_t n_rows, size_t nq, size_t k);
+size_t sparse_limit(size_t n_rows, size_t ld, size_t dim, size_t nq);
+int eligible_count(Index* ix, hipStream_t s, const uint32_t* d_rowmask, uint32_t* out_E);
+int eligible_list(Index* ix, hipStream_t s, const uint32_t* d_rowmask, uint32_t E);
 int ensure_host_io(Index* ix, size_t bytes);
 void publish_stats(Index* ix);
 bool in_flight(const Index* ix);

@@ -569,6 +569,98 @@ static int search_direct(Index* ix, hipStream_t s, const float* d_q, uint32_t nq
     return VDB_OK;
 }
 
+// ------------------------------------------------------------------ the sparse-filter route (vdb_flat_set_sparse_filter)
+// A masked search whose filter leaves few rows eligible reads ONLY those rows: the set bits of the row mask become an ascending
+// list of device rows (kernels_sparse.hip: popcount per block, one-workgroup scan, scatter -- the host reads E, 4 bytes, in
+// between), sparse_scan_kernel computes the reference distance of every (query, eligible row) pair, select_kernel in EMIT mode
+// writes the k smallest by (distance, id) as final results.  Exact by construction, like the direct path: no certificate.
+//
+// The automatic mode (2) takes the route when E * nq * dim <= C * n_rows * ld: the pair arithmetic of the scan against the one
+// HBM pass over the store that the tiers make.  C is a MEASUREMENT (tools/sparse_filter_bench.py), not an
+// estimate; until the grid has been measured it is 0 and mode 2 never sends a non-empty list to the route.
+constexpr double SPARSE_AUTO_C = 0.0;
+size_t sparse_limit(size_t n_rows, size_t ld, size_t dim, size_t nq) {
+    if (!n_rows) return 0;
+    const size_t cap = std::min<size_t>(n_rows, SPARSE_MAX_E);
+    const double per_row = (double)std::max<size_t>(nq, 1) * (double)std::max<size_t>(dim, 1);
+    const double e = SPARSE_AUTO_C * (double)n_rows * (double)std::max<size_t>(ld, 1) / per_row;
+    return e >= (double)cap ? cap : (size_t)e;
+}
+
+// E = set bits of the row mask below n_uploaded, read back to the host (one synchronisation)
+int eligible_count(Index* ix, hipStream_t s, const uint32_t* d_rowmask, uint32_t* out_E) {
+    int rc;
+    const uint32_t n = ix->n_uploaded, nb = vdb::sparse_list_blocks(n);
+    if ((rc = ix->cur->w_eligblk.ensure(2 * (size_t)nb + 4))) return rc;
+    uint32_t* blk = ix->cur->w_eligblk.p;
+    vdb::launch_sparse_count(d_rowmask, n, blk, blk + nb, blk + 2 * (size_t)nb, s);
+    HIP_TRY(hipGetLastError());
+    uint32_t E = 0;
+    HIP_TRY(hipMemcpyAsync(&E, blk + 2 * (size_t)nb, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (E > n) return fail(VDB_ERR_DEVICE, "eligible-row count %u exceeds the %u rows of the store", E, n);
+    *out_E = E;
+    return VDB_OK;
+}
+// ... and the list itself, w_elig[0..E), from the block offsets eligible_count left behind
+int eligible_list(Index* ix, hipStream_t s, const uint32_t* d_rowmask, uint32_t E) {
+    int rc;
+    const uint32_t n = ix->n_uploaded, nb = vdb::sparse_list_blocks(n);
+    if ((rc = ix->cur->w_elig.ensure(std::max<size_t>(E, 1)))) return rc;
+    vdb::launch_sparse_scatter(d_rowmask, n, ix->cur->w_eligblk.p + nb, ix->cur->w_elig.p, E, s);
+    HIP_TRY(hipGetLastError());
+    return VDB_OK;
+}
+
+static int search_sparse(Index* ix, hipStream_t s, const float* d_q, uint32_t nq, size_t dim, size_t k, uint32_t E,
+                         const uint32_t* d_rowmask, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts) {
+    int rc;
+    Workspace* W = ix->cur;
+    const uint32_t n = ix->n_uploaded, ld = ix->ld, bp_all = round_up(nq, SUPER);
+    // queries: the zero-padded block and the exact-order norms; query_prep raises ST_ZERO_QUERY (also when nothing is eligible)
+    if ((rc = W->w_qp.ensure((size_t)bp_all * ld))) return rc;
+    if ((rc = W->w_qnorm.ensure(bp_all))) return rc;
+    if ((rc = W->w_thr.ensure(bp_all))) return rc;
+    if ((rc = W->w_flags.ensure(4 + 3 * (size_t)nq))) return rc;
+    uint32_t* d_status = W->w_flags.p;
+    HIP_TRY(hipMemsetAsync(d_status, 0, 16, s));
+    W->status_dirty = true;                                        // (the tiers' bookkeeping: the block is cleared again before its next use)
+    vdb::QueryPrepParams qp{d_q, (uint32_t)dim, nq, W->w_qp.p, ld, bp_all, W->w_qnorm.p, W->w_thr.p, ix->metric, d_status,
+                            nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr};
+    vdb::launch_query_prep(qp, s);
+    if (E == 0) HIP_TRY(hipMemsetAsync(d_out_counts, 0, (size_t)nq * 4, s));
+    else {
+        if ((rc = ensure_ranks(ix))) return rc;
+        if ((rc = eligible_list(ix, s, d_rowmask, E))) return rc;
+        const uint32_t stride = round_up(E, vdb::SPARSE_TILE_R);
+        if ((rc = W->w_exact.ensure((size_t)std::min(nq, SUPER) * stride))) return rc;
+        if ((rc = W->w_exsel.ensure((size_t)SUPER * MAX_SELECT + 8))) return rc;
+        if ((rc = W->w_cnt.ensure(4 * SUPER + 16))) return rc;
+        for (uint32_t q0 = 0; q0 < nq; q0 += SUPER) {              // passes of SUPER queries: the key buffer stays bounded
+            const uint32_t nb = std::min(SUPER, nq - q0);
+            vdb::SparseScanParams sp{ix->d_rows, ld, ix->dim, n, W->w_elig.p, E, W->w_qp.p + (size_t)q0 * ld, W->w_qnorm.p + q0, nb,
+                                     ix->d_nd, ix->ids_monotone ? nullptr : ix->d_idrank.p, ix->metric, W->w_exact.p, stride, d_status};
+            vdb::launch_sparse_scan(sp, s);
+            vdb::SelectParams mp{};
+            mp.keys = W->w_exact.p; mp.stride = stride; mp.counts = nullptr; mp.n_fixed = stride; mp.cap = stride;
+            mp.kk = (uint32_t)k; mp.out_keys = W->w_exsel.p; mp.out_stride = MAX_SELECT; mp.out_cnt = W->w_cnt.p;
+            mp.emit_ids = d_out_ids + (size_t)q0 * k; mp.emit_dists = d_out_dists + (size_t)q0 * k; mp.emit_counts = d_out_counts + q0;
+            mp.emit_stride = (uint32_t)k;
+            mp.emit_rank2row = ix->ids_monotone ? nullptr : ix->d_rank2row.p; mp.emit_row_ids = ix->d_row_ids;
+            vdb::launch_select(mp, nb, s);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    uint32_t st[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(st, d_status, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    W->stats[1] = nq;                                              // answered by an exact scan
+    ix->sparse_last = 1; ++ix->sparse_count;
+    if (st[0] & vdb::ST_ZERO_QUERY) return fail_zero_vector();
+    if (st[0] & vdb::ST_NAN) return fail_nan();
+    return VDB_OK;
+}
+
 // Part 1: checks, workspace, and the FIRST tier enqueued on the stream -- no host synchronisation unless the search is
 // one of the cases answered completely here (empty store, k = 0, k too large for the MFMA tiers).
 int search_part1(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, const uint64_t* d_idmask,
@@ -576,6 +668,7 @@ int search_part1(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, c
                  hipStream_t user_stream, bool allow_alt) {
     int rc;
     ix->cur->ctx.pending = false;
+    ix->sparse_last = 0;
     if ((rc = set_device(ix))) return rc;
     if ((rc = flush(ix))) return rc;
     if (nq == 0) return VDB_OK;
@@ -614,6 +707,24 @@ int search_part1(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, c
     const uint32_t nq32 = (uint32_t)nq;
     const uint32_t bp_all = round_up(nq32, SUPER);
     const uint32_t kp = pick_kp(k);
+
+    // ---- sparse-filter route (off by default): a masked search scans only the rows its filter leaves eligible.  Mode 1 takes it
+    // whenever the select can hold k and the list fits; mode 2 also asks the measured cost limit and leaves small indexes to the
+    // direct path.  Answered completely here, like the direct path; otherwise the search goes on below as if nothing had happened.
+    if (ix->sparse_mode && d_idmask) {
+        if ((rc = ix->cur->w_rowmask.ensure((n + 31) / 32))) return rc;
+        vdb::launch_build_rowmask(ix->d_row_ids, (ix->n_live == n) ? nullptr : ix->d_live, d_idmask, mask_bits, n, ix->cur->w_rowmask.p, s);
+        uint32_t E = 0;
+        if ((rc = eligible_count(ix, s, ix->cur->w_rowmask.p, &E))) return rc;
+        ix->sparse_E = E;
+        bool take = k <= MAX_SELECT && E <= SPARSE_MAX_E;
+        if (ix->sparse_mode == 2) take = take && !direct_eligible(ix, n, nq, k) && E <= sparse_limit(n, ld, ix->dim, nq);
+        if (take) {
+            rc = search_sparse(ix, s, d_q, nq32, dim, k, E, ix->cur->w_rowmask.p, d_out_ids, d_out_dists, d_out_counts);
+            ix->cur->stats[10] = ix->cur->stats[11] = ix->cur->stats[12] = since();
+            return rc;
+        }
+    }
 
     // ---- small index, a few queries: the direct exact path (two kernels, answered completely here)
     if (direct_eligible(ix, n, nq, k)) {

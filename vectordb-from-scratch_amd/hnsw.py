@@ -154,6 +154,16 @@ class GpuHnswIndex(Index):
         if rc:
             _raise(rc)
 
+    def set_filter_scan(self, max_eligible):
+        """Masked searches whose mask leaves at most max_eligible present nodes are answered by an exact scan of those nodes
+        (exact results, so not the walk's approximate ones); 0 (default): every masked search is walked."""
+        max_eligible = int(max_eligible)
+        if max_eligible < 0:
+            raise ValueError("max_eligible must be >= 0")
+        rc = self._L.vdb_hnsw_set_filter_scan(self._h, max_eligible)
+        if rc:
+            _raise(rc)
+
     def stats(self):
         out = (ctypes.c_uint64 * 6)()
         self._L.vdb_hnsw_stats(self._h, out)

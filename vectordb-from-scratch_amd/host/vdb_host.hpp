@@ -151,6 +151,8 @@ public:
     // no reference counterpart: tier selection (results are identical either way)
     void set_screen(int mode) { check(vdb_flat_set_screen(h_, mode)); }
     void set_large_k(int on) { check(vdb_flat_set_large_k(h_, on)); }
+    // masked searches: 0 the tiers (default), 1 an exact scan of the eligible rows only, 2 automatic (results are identical)
+    void set_sparse_filter(int mode) { check(vdb_flat_set_sparse_filter(h_, mode)); }
     void set_tiers(unsigned flags) { check(vdb_flat_set_tiers(h_, flags)); }
 
 private:

@@ -355,6 +355,59 @@ class GpuFlatIndex(Index):
         if rc:
             _raise(rc)
 
+    # ---- the sparse-filter route of pre-filtered searches (include/vdb_flat.h vdb_flat_set_sparse_filter; results identical)
+    SPARSE_NEVER, SPARSE_ALWAYS, SPARSE_AUTO = 0, 1, 2
+
+    def set_sparse_filter(self, mode):
+        """Searches with an id mask: 0 (default) the tiers over every row, 1 an exact scan of the eligible rows only whenever
+        k <= 2048 and at most 131072 rows are eligible, 2 the same where sparse_limit() says it pays.  Results are identical."""
+        mode = int(mode)
+        if mode not in (0, 1, 2):
+            raise ValueError(f"sparse filter mode must be 0, 1 or 2, not {mode}")
+        rc = self._L.vdb_flat_set_sparse_filter(self._h, mode)
+        if rc:
+            _raise(rc)
+
+    def sparse_stats(self):
+        """[0] 1 when the last search was answered by the sparse-filter route, [1] eligible rows of the last masked search made
+        with a mode other than 0, [2] searches the route answered since creation, [3] 0."""
+        out = (ctypes.c_uint64 * 4)()
+        rc = self._L.vdb_flat_sparse_stats(self._h, out)
+        if rc:
+            _raise(rc)
+        return [int(x) for x in out]
+
+    @staticmethod
+    def sparse_limit(n_rows, ld, dim, nq):
+        """The longest eligible-row list mode 2 sends to the route for that shape (ld: dim rounded up to 32).  Needs no device."""
+        return int(_ffi.lib().vdb_flat_sparse_limit(int(n_rows), int(ld), int(dim), int(nq)))
+
+    @staticmethod
+    def sparse_tile():
+        """(list positions, queries) of one workgroup of the scan kernel."""
+        L = _ffi.lib()
+        return int(L.vdb_flat_debug_sparse_tile_rows()), int(L.vdb_flat_debug_sparse_tile_queries())
+
+    def debug_eligible_rows(self, mask, mask_bits):
+        """Test hook: the ascending device rows a masked search on the route would scan (u32 array); no distance is computed."""
+        m = np.ascontiguousarray(mask, dtype=np.uint64)
+        if m.size * 64 < int(mask_bits):
+            raise ValueError(f"mask holds {m.size * 64} bits, mask_bits is {int(mask_bits)}")
+        if m.size == 0:
+            m = np.zeros(1, dtype=np.uint64)
+        n = ctypes.c_size_t(0)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        rc = self._L.vdb_flat_debug_eligible_rows(self._h, ctypes.c_void_p(m.ctypes.data), int(mask_bits), None, 0, ctypes.byref(n))
+        if rc:
+            _raise(rc)
+        out = np.zeros(int(n.value), dtype=np.uint32)
+        if out.size:
+            rc = self._L.vdb_flat_debug_eligible_rows(self._h, ctypes.c_void_p(m.ctypes.data), int(mask_bits),
+                                                      out.ctypes.data_as(u32p), out.size, ctypes.byref(n))
+            if rc:
+                _raise(rc)
+        return out
+
     TIERS_NO_RETHRESHOLD, TIERS_FORCE_F32, TIERS_FORCE_EXACT, TIERS_NO_DIRECT = 1, 2, 4, 8
 
     def set_shadow(self, on=True):

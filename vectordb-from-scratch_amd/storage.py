@@ -205,6 +205,21 @@ class VectorStore:
         compact = getattr(self._index, "compact", None)
         return int(compact()) if compact is not None else 0
 
+    def set_sparse_filter(self, mode):
+        """How pre-filtered searches (search_batch_prefiltered, the server's "prefilter": true) treat a selective filter.
+        Flat index: 0 (default) every row is streamed, 1 only the eligible rows are scanned, 2 automatic
+        (GpuFlatIndex.set_sparse_filter).  HNSW index: mode != 0 answers filters that leave at most 131072 nodes with an exact scan
+        of those nodes instead of the walk (GpuHnswIndex.set_filter_scan).  An index without either setting ignores it."""
+        mode = int(mode)
+        if mode not in (0, 1, 2):
+            raise ValueError(f"sparse filter mode must be 0, 1 or 2, not {mode}")
+        flat = getattr(self._index, "set_sparse_filter", None)
+        scan = getattr(self._index, "set_filter_scan", None)
+        if flat is not None:
+            flat(mode)
+        elif scan is not None:
+            scan(131072 if mode else 0)
+
     # ---- reads
     def _internal_of(self, id):
         """String id -> internal id, for inserted rows and for bulk-attached rows alike (None: unknown)."""
