@@ -349,6 +349,58 @@ size_t vdb_flat_debug_sparse_tile_rows(void);
 size_t vdb_flat_debug_sparse_tile_queries(void);
 
 /*
+ * METADATA FILTERS COMPILED ON THE DEVICE (no reference counterpart: the reference evaluates MetadataFilter::matches row by row
+ * on the host, src/storage.rs:60-71, :272-287; search results are identical to those under the same mask built on the host, bit
+ * for bit).  A pre-filtered search needs the id bitmask of its filter.  Instead of building it on the host and uploading it with
+ * every request, the store keeps its metadata resident in HBM and the mask is computed there: one kernel launch, no transfer
+ * larger than the filter expression.
+ *
+ * vdb_meta_table: the metadata by INTERNAL id, on one device.  It belongs to the store, not to an index handle.  It holds
+ * columns, addressed by a small integer slot, of int32 dictionary codes (codes[id]; -1 = the row has no such field; an id never
+ * written reads as -1; columns grow independently and may be shorter than a mask), and a presence bitmap in the layout of id_mask.
+ * vdb_meta_set_codes / vdb_meta_set_present are WRITES (the caller's write lock, like add / remove, routes.rs:141,:210,:300): they
+ * are staged on the host and reach the device as dirty ranges in front of the next compile, the add / flush pattern of the index.
+ * A slot is known once vdb_meta_set_codes was called for it (n = 0 is enough).  Ids at or above 2^32: VDB_ERR_INVALID_ARGUMENT.
+ *
+ * vdb_meta_compile: `ops` is the filter as a POSTFIX program -- EQ slot code, NE slot code, EXISTS slot, CONST 0|1 push a
+ * verdict, AND / OR replace the two topmost by one.  Leaves are MetadataFilter::matches' (storage.rs:62-67): EQ is code == c, NE
+ * is code != c (a row without the field matches), EXISTS is code >= 0.  Whatever needs the dictionary (an unknown field or value)
+ * is resolved to CONST by the caller.  At most 1024 ops, evaluation stack at most 32 deep, exactly one value left, every slot
+ * known -- else VDB_ERR_INVALID_ARGUMENT before any device work.  On the table's stream and WITHOUT waiting for it: the staged
+ * ranges are uploaded, one kernel writes bit i = present(i) AND program(i) for every i < mask_bits (tail bits of the last word
+ * clear; mask_bits == 0 writes nothing) and counts the set bits.  *out is a mask from a pool inside the table (no allocation per
+ * request after warm-up) with an event marking its completion.  A read: may be called from several threads at once.
+ *
+ * vdb_meta_mask_ptr: the device pointer, for the d_id_mask of vdb_flat_search_batch_device / _begin / _submit, once the
+ * caller's stream is ordered behind the mask with vdb_meta_mask_wait_on (hipStreamWaitEvent, no host wait; stream NULL = the
+ * null stream).  vdb_meta_mask_bits: its mask_bits.  vdb_meta_mask_count: waits for the event, reads the number of set bits
+ * (8 bytes).  vdb_meta_mask_release: back to the pool -- after the last search that reads it has completed; the next compile may
+ * hand the same buffer out again.  vdb_meta_destroy frees the table and every mask it made.
+ *
+ * vdb_flat_search_batch_filtered: vdb_flat_search_batch (host queries, per-query ks, host outputs) under a compiled mask: the
+ * handle's stream is ordered behind the mask's event and nothing is uploaded for the filter; the same search code runs below it
+ * (tiers, sparse-filter route), so results are identical to the host-mask call, bit for bit.  Plain and sharded handles (the
+ * table must then be on devices[0]); a mask on another device or a null mask is VDB_ERR_INVALID_ARGUMENT.
+ */
+typedef struct vdb_meta_table vdb_meta_table;
+typedef struct vdb_meta_mask vdb_meta_mask;
+enum { VDB_META_EQ = 0, VDB_META_NE = 1, VDB_META_EXISTS = 2, VDB_META_CONST = 3, VDB_META_AND = 4, VDB_META_OR = 5 };
+typedef struct vdb_meta_op { uint32_t op; uint32_t slot; int32_t code; } vdb_meta_op; /* CONST: code = 0 | 1; AND / OR: both unused */
+int vdb_meta_create(int device, vdb_meta_table **out);
+void vdb_meta_destroy(vdb_meta_table *t);
+int vdb_meta_set_codes(vdb_meta_table *t, uint32_t slot, uint64_t first_id, const int32_t *codes, size_t n);
+int vdb_meta_set_present(vdb_meta_table *t, uint64_t first_id, size_t n, int on);
+int vdb_meta_compile(vdb_meta_table *t, const vdb_meta_op *ops, size_t n_ops, size_t mask_bits, vdb_meta_mask **out);
+const uint64_t *vdb_meta_mask_ptr(const vdb_meta_mask *m);
+size_t vdb_meta_mask_bits(const vdb_meta_mask *m);
+int vdb_meta_mask_count(vdb_meta_mask *m, uint64_t *eligible);
+int vdb_meta_mask_wait_on(vdb_meta_mask *m, void *stream);
+int vdb_meta_mask_release(vdb_meta_mask *m);
+int vdb_flat_search_batch_filtered(vdb_flat_index *h, const float *queries, size_t nq, size_t dim, const size_t *ks, size_t k,
+                                   const vdb_meta_mask *mask, size_t kstride, uint64_t *out_ids, float *out_dists,
+                                   size_t *out_counts);
+
+/*
  * Opt-in bf16 SHADOW of the rows for the screening pass (no reference counterpart; results are identical with and without
  * it).  on = 1: the index keeps, next to the f32 rows, their bf16 roundings (+50 % device memory: 2 bytes per element on top
  * of 4) -- exactly the values the screening kernel otherwise produces in registers -- and the filter pass streams THOSE:

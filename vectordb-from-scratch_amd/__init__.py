@@ -9,11 +9,11 @@ from . import _ffi
 from .build import build
 from .error import (DimensionMismatch, IndexError_, InvalidVector, NanDistance, VectorDbError,
                     VectorNotFound)
-from .index import GpuFlatIndex, Index
+from .index import CompiledMask, GpuFlatIndex, Index, MetaTable
 from .hnsw import GpuHnswIndex, HnswParams
 from .storage import BatchInsertItem, Metadata, MetadataFilter, SearchResult, VectorStore
 from .vector import DistanceMetric, Vector
 
-__all__ = ["build", "GpuFlatIndex", "GpuHnswIndex", "HnswParams", "Index", "VectorStore", "Vector", "DistanceMetric", "Metadata",
+__all__ = ["build", "GpuFlatIndex", "MetaTable", "CompiledMask", "GpuHnswIndex", "HnswParams", "Index", "VectorStore", "Vector", "DistanceMetric", "Metadata",
            "MetadataFilter", "SearchResult", "BatchInsertItem", "VectorDbError", "DimensionMismatch",
            "InvalidVector", "VectorNotFound", "IndexError_", "NanDistance"]

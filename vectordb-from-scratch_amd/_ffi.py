@@ -17,6 +17,8 @@ SYMBOLS = [
     "vdb_flat_reserve", "vdb_flat_flush", "vdb_flat_compact", "vdb_flat_set_auto_compact", "vdb_flat_store_stats", "vdb_flat_search", "vdb_flat_search_batch",
     "vdb_flat_search_batch_device", "vdb_flat_search_batch_device_begin", "vdb_flat_search_batch_device_finish", "vdb_flat_search_batch_device_submit", "vdb_flat_search_batch_device_wait", "vdb_flat_distances_batch", "vdb_merge_topk_device", "vdb_merge_topk_packed_device", "vdb_flat_set_profile", "vdb_flat_last_stats", "vdb_flat_last_stats_ex", "vdb_flat_set_screen", "vdb_flat_set_wide", "vdb_flat_set_large_k", "vdb_flat_large_k_min_rows", "vdb_flat_set_shadow", "vdb_flat_set_sample_cache", "vdb_flat_set_tiers", "vdb_flat_debug_screen_scores", "vdb_flat_debug_rows", "vdb_flat_debug_row_info", "vdb_flat_debug_last_thresholds", "vdb_flat_debug_cert_probe", "vdb_flat_debug_compact_plan", "vdb_flat_debug_set_compact_bounce", "vdb_last_error",
     "vdb_flat_set_sparse_filter", "vdb_flat_sparse_stats", "vdb_flat_sparse_limit", "vdb_flat_debug_eligible_rows", "vdb_flat_debug_sparse_tile_rows", "vdb_flat_debug_sparse_tile_queries",
+    "vdb_meta_create", "vdb_meta_destroy", "vdb_meta_set_codes", "vdb_meta_set_present", "vdb_meta_compile", "vdb_meta_mask_ptr", "vdb_meta_mask_bits",
+    "vdb_meta_mask_count", "vdb_meta_mask_wait_on", "vdb_meta_mask_release", "vdb_flat_search_batch_filtered",
     "vdb_abi_version", "vdb_build_arch",
     # include/vdb_hnsw.h
     "vdb_hnsw_create", "vdb_hnsw_destroy", "vdb_hnsw_add", "vdb_hnsw_add_bulk", "vdb_hnsw_remove", "vdb_hnsw_search_batch", "vdb_hnsw_search_batch_masked",
@@ -28,6 +30,11 @@ SYMBOLS = [
 ]
 
 _lib = None
+
+
+class MetaOp(ctypes.Structure):
+    """vdb_meta_op: one op of a filter program (include/vdb_flat.h)"""
+    _fields_ = [("op", ctypes.c_uint32), ("slot", ctypes.c_uint32), ("code", ctypes.c_int32)]
 
 
 def _preload_torch_hip():
@@ -132,6 +139,20 @@ def lib():
     L.vdb_flat_debug_row_info.argtypes = [vp, fp, sz]
     L.vdb_flat_debug_cert_probe.argtypes = [vp, u32p, fp, fp, sz, u32p]
     L.vdb_flat_set_profile.argtypes = [vp, c.c_int]
+    L.vdb_meta_create.argtypes = [c.c_int, c.POINTER(vp)]
+    L.vdb_meta_destroy.argtypes = [vp]
+    L.vdb_meta_destroy.restype = None
+    L.vdb_meta_set_codes.argtypes = [vp, c.c_uint32, u64, c.POINTER(c.c_int32), sz]
+    L.vdb_meta_set_present.argtypes = [vp, u64, sz, c.c_int]
+    L.vdb_meta_compile.argtypes = [vp, c.POINTER(MetaOp), sz, sz, c.POINTER(vp)]
+    L.vdb_meta_mask_ptr.argtypes = [vp]
+    L.vdb_meta_mask_ptr.restype = vp
+    L.vdb_meta_mask_bits.argtypes = [vp]
+    L.vdb_meta_mask_bits.restype = sz
+    L.vdb_meta_mask_count.argtypes = [vp, u64p]
+    L.vdb_meta_mask_wait_on.argtypes = [vp, vp]
+    L.vdb_meta_mask_release.argtypes = [vp]
+    L.vdb_flat_search_batch_filtered.argtypes = [vp, fp, sz, sz, szp, sz, vp, sz, u64p, fp, szp]
     L.vdb_last_error.argtypes = [c.c_char_p, sz, szp, szp]
     L.vdb_last_error.restype = None
     L.vdb_hnsw_create.argtypes = [c.c_int, sz, sz, sz, u64, c.c_int, c.POINTER(vp)]

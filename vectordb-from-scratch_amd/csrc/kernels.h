@@ -383,6 +383,21 @@ struct SparseScanParams {
 };
 void launch_sparse_scan(const SparseScanParams& p, hipStream_t s);
 
+// ---------------------------------------------------------------- metadata filters compiled on the device (kernels_filter.hip)
+// A MetadataFilter as a postfix program over the resident metadata columns (vdb_meta.cpp).  Every leaf carries its
+// column: codes[id] for id < len, -1 ("no such field") at and above len -- such an id reads no memory.
+enum : uint32_t { FOP_EQ = 0, FOP_NE = 1, FOP_EXISTS = 2, FOP_CONST = 3, FOP_AND = 4, FOP_OR = 5 };
+constexpr uint32_t FILTER_MAX_OPS = 1024, FILTER_MAX_DEPTH = 32;   // the evaluation stack is the bits of one 32-bit register
+struct FilterOp { const int32_t* codes; uint64_t len; uint32_t op; int32_t code; };   // FOP_CONST: code = 0 | 1
+struct FilterParams {
+    const FilterOp* ops; uint32_t n_ops;               // device memory; well-formed, n_ops <= FILTER_MAX_OPS, depth <= FILTER_MAX_DEPTH (the host checked)
+    const uint64_t* present; uint64_t present_words;   // presence bitmap by id; words at and above present_words read as 0
+    uint64_t mask_bits;                                // ids at and above contribute 0
+    uint64_t* mask;                                    // out: (mask_bits + 63) / 64 words, every one written
+    unsigned long long* count;                         // += popcount of the mask (zeroed by the caller on the same stream)
+};
+void launch_filter_compile(const FilterParams& p, uint32_t n_cu, hipStream_t s);   // mask_bits == 0: no launch
+
 struct EmitParams {                                    // sorted exact keys -> (id, dist) outputs
     const uint64_t* keys; uint32_t cnt_max; const uint32_t* cnt;
     const uint32_t* rank2row; const uint64_t* row_ids;

@@ -15,6 +15,7 @@
 #include <limits>
 
 #include "vdb_index.h"
+#include "vdb_meta.h"
 
 namespace vdbi {
 
@@ -546,12 +547,21 @@ int vdb_flat_search_batch_device_wait(vdb_flat_index* ix, int ticket) {
     });
 }
 
-int vdb_flat_search_batch(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks,
-                          size_t k, const uint64_t* id_mask, size_t mask_bits, size_t kstride, uint64_t* out_ids,
-                          float* out_dists, size_t* out_counts) {
+}  // extern "C"
+
+// vdb_flat_search_batch and vdb_flat_search_batch_filtered: the id mask comes from the host (id_mask, uploaded here) or is a
+// compiled one already in HBM (cm: the stream is ordered behind its event, nothing is uploaded); everything below is the same
+static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks,
+                             size_t k, const uint64_t* id_mask, size_t mask_bits, const vdb_meta_mask* cm, size_t kstride,
+                             uint64_t* out_ids, float* out_dists, size_t* out_counts) {
     return guarded([&]() -> int {
     if (!ix || (nq && (!queries || !out_counts))) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
-    if (ix->multi) return multi_search_host(ix, queries, nq, dim, ks, k, id_mask, mask_bits, kstride, out_ids, out_dists, out_counts);
+    if (cm) {
+        const int dev = ix->multi ? multi_home(ix) : ix->device;
+        if (cm->device != dev) return fail(VDB_ERR_INVALID_ARGUMENT, "the compiled mask lives on device %d, the index on device %d", cm->device, dev);
+        mask_bits = cm->bits;
+    }
+    if (ix->multi) return multi_search_host(ix, queries, nq, dim, ks, k, id_mask, mask_bits, kstride, out_ids, out_dists, out_counts, cm);
     size_t kmax = k;
     if (ks) {
         kmax = 0;
@@ -570,7 +580,7 @@ int vdb_flat_search_batch(vdb_flat_index* ix, const float* queries, size_t nq, s
     hipStream_t s = ix->stream;
     // Small index, a few queries (BASELINE configs[0]: Index::search itself, one query): queries and results go through MAPPED
     // host memory -- the two kernels of the direct path read and write it in place, nothing is copied by the runtime
-    if (direct_eligible(ix, ix->n_rows(), nq, kdev) && ix->misfits.empty() && dim == ix->dim && !id_mask) {
+    if (direct_eligible(ix, ix->n_rows(), nq, kdev) && ix->misfits.empty() && dim == ix->dim && !id_mask && !cm) {
         const size_t qb = nq * dim * sizeof(float), ib = nq * kdev * sizeof(uint64_t), db = nq * kdev * sizeof(float), cb = nq * sizeof(uint32_t);
         const size_t o_i = (qb + 15) & ~(size_t)15, o_d = o_i + ib, o_c = o_d + ((db + 15) & ~(size_t)15);
         if ((rc = ensure_host_io(ix, o_c + cb))) return rc;
@@ -602,6 +612,9 @@ int vdb_flat_search_batch(vdb_flat_index* ix, const float* queries, size_t nq, s
         if ((rc = ix->cur->w_mask_ids.ensure(std::max<size_t>(words, 1)))) return rc;
         if (words) HIP_TRY(hipMemcpyAsync(ix->cur->w_mask_ids.p, id_mask, words * 8, hipMemcpyHostToDevice, s));
         d_mask = ix->cur->w_mask_ids.p;
+    } else if (cm) {
+        HIP_TRY(hipStreamWaitEvent(s, cm->done, 0));
+        d_mask = cm->d_words;
     }
     rc = search_device(ix, ix->cur->w_qin.p, nq, dim, kdev, d_mask, mask_bits, ix->cur->w_outi.p, ix->cur->w_outd.p, ix->cur->w_outc.p,
                        nullptr);
@@ -626,6 +639,21 @@ int vdb_flat_search_batch(vdb_flat_index* ix, const float* queries, size_t nq, s
     }
     return VDB_OK;
     });
+}
+
+extern "C" {
+
+int vdb_flat_search_batch(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks,
+                          size_t k, const uint64_t* id_mask, size_t mask_bits, size_t kstride, uint64_t* out_ids,
+                          float* out_dists, size_t* out_counts) {
+    return search_batch_host(ix, queries, nq, dim, ks, k, id_mask, mask_bits, nullptr, kstride, out_ids, out_dists, out_counts);
+}
+
+int vdb_flat_search_batch_filtered(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k,
+                                   const vdb_meta_mask* mask, size_t kstride, uint64_t* out_ids, float* out_dists,
+                                   size_t* out_counts) {
+    if (!mask) return fail(VDB_ERR_INVALID_ARGUMENT, "null mask");
+    return search_batch_host(ix, queries, nq, dim, ks, k, nullptr, 0, mask, kstride, out_ids, out_dists, out_counts);
 }
 
 int vdb_flat_search(vdb_flat_index* ix, const float* query, size_t dim, size_t k, uint64_t* out_ids,

@@ -285,7 +285,9 @@ int multi_for_each(vdb_flat_index* P, const std::function<int(vdb_flat_index*)>&
 int multi_search_device(vdb_flat_index* P, const float* d_q, size_t nq, size_t dim, size_t k, const uint64_t* d_mask, size_t mask_bits,
                         uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, hipStream_t user_stream);
 int multi_search_host(vdb_flat_index* P, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k, const uint64_t* id_mask,
-                      size_t mask_bits, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts);
+                      size_t mask_bits, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts,
+                      const struct vdb_meta_mask* cm = nullptr);   // cm: a compiled mask on the home device instead of id_mask (vdb_meta.h)
+int multi_home(const vdb_flat_index* P);                           // devices[0]: where queries, masks and outputs live
 int multi_set_exchange(vdb_flat_index* P, int mode);
 size_t multi_shards(const vdb_flat_index* P);
 size_t multi_shard_len(const vdb_flat_index* P, size_t g);

@@ -28,6 +28,7 @@
 
 #include "../../include/vdb_shard.h"
 #include "vdb_index.h"
+#include "vdb_meta.h"
 #include "vdb_rccl.h"
 
 namespace vdbi {
@@ -586,7 +587,7 @@ int multi_search_device(vdb_flat_index* P, const float* d_q, size_t nq, size_t d
 }
 
 int multi_search_host(vdb_flat_index* P, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k, const uint64_t* id_mask,
-                      size_t mask_bits, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts) {
+                      size_t mask_bits, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts, const vdb_meta_mask* cm) {
     vdb_multi* M = P->multi;
     size_t kmax = k;
     if (ks) { kmax = 0; for (size_t b = 0; b < nq; ++b) kmax = std::max(kmax, ks[b]); }
@@ -610,6 +611,9 @@ int multi_search_host(vdb_flat_index* P, const float* queries, size_t nq, size_t
         if ((rc = M->w_mask.ensure(std::max<size_t>(words, 1)))) return rc;
         if (words) HIP_TRY(hipMemcpyAsync(M->w_mask.p, id_mask, words * 8, hipMemcpyHostToDevice, s));
         d_mask = M->w_mask.p;
+    } else if (cm) {                                                   // already on the home device: ordered in front of the wait below
+        HIP_TRY(hipStreamWaitEvent(s, cm->done, 0));
+        d_mask = cm->d_words;
     }
     HIP_TRY(hipStreamSynchronize(s));                                  // the shards' streams read the staged queries
     if ((rc = search_locked(P, M->w_qin.p, nq, dim, kdev, d_mask, mask_bits, M->w_outi.p, M->w_outd.p, M->w_outc.p, nullptr))) return rc;
@@ -630,6 +634,8 @@ int multi_search_host(vdb_flat_index* P, const float* queries, size_t nq, size_t
     }
     return VDB_OK;
 }
+
+int multi_home(const vdb_flat_index* P) { return P->multi->home; }
 
 int multi_set_exchange(vdb_flat_index* P, int mode) {
     vdb_multi* M = P->multi;

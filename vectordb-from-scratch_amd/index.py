@@ -67,6 +67,101 @@ def _u64p(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
 
 
+class CompiledMask:
+    """A filter compiled on the device (MetaTable.compile): the id bitmask in HBM plus the event behind which it is complete.
+    release() gives the buffer back to the table's pool -- after the last search that reads the mask has completed."""
+
+    def __init__(self, table, handle):
+        self._table, self._m = table, handle             # (the table is kept alive: it owns the buffer)
+
+    @property
+    def handle(self):
+        if not self._m:
+            raise ValueError("the compiled mask was released")
+        return self._m
+
+    @property
+    def ptr(self):
+        """device pointer of the mask words, for the mask_ptr of the search_batch_device* calls (after wait_on)"""
+        return int(self._table._L.vdb_meta_mask_ptr(self.handle) or 0)
+
+    @property
+    def bits(self):
+        return int(self._table._L.vdb_meta_mask_bits(self.handle))
+
+    def count(self):
+        """eligible ids (set bits); waits for the compile"""
+        n = ctypes.c_uint64(0)
+        rc = self._table._L.vdb_meta_mask_count(self.handle, ctypes.byref(n))
+        if rc:
+            _raise(rc)
+        return int(n.value)
+
+    def wait_on(self, stream=0):
+        """order `stream` (a hipStream_t as an integer, 0 = the null stream) behind the mask; the host does not wait"""
+        rc = self._table._L.vdb_meta_mask_wait_on(self.handle, ctypes.c_void_p(stream or None))
+        if rc:
+            _raise(rc)
+
+    def release(self):
+        m, self._m = self._m, None
+        if m and self._table._t:
+            rc = self._table._L.vdb_meta_mask_release(m)
+            if rc:
+                _raise(rc)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+
+
+class MetaTable:
+    """The store's metadata resident on one GPU (include/vdb_flat.h vdb_meta_table): int32 dictionary-code columns by slot
+    and a presence bitmap, both by internal id.  Writes are staged and uploaded by the next compile()."""
+
+    EQ, NE, EXISTS, CONST, AND, OR = range(6)
+    MAX_OPS, MAX_DEPTH = 1024, 32
+
+    def __init__(self, device=0):
+        self._L = _ffi.lib()
+        self._t = ctypes.c_void_p()
+        rc = self._L.vdb_meta_create(int(device), ctypes.byref(self._t))
+        if rc:
+            _raise(rc)
+        self.device = int(device)
+
+    def close(self):
+        t, self._t = getattr(self, "_t", None), None
+        if t:
+            self._L.vdb_meta_destroy(t)
+
+    __del__ = close
+
+    def set_codes(self, slot, first_id, codes):
+        c = np.ascontiguousarray(codes, dtype=np.int32)
+        rc = self._L.vdb_meta_set_codes(self._t, int(slot), int(first_id), c.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), c.size)
+        if rc:
+            _raise(rc)
+
+    def set_present(self, first_id, n, on):
+        rc = self._L.vdb_meta_set_present(self._t, int(first_id), int(n), 1 if on else 0)
+        if rc:
+            _raise(rc)
+
+    def compile(self, program, mask_bits):
+        """program: a sequence of (op, slot, code) in postfix order.  Returns a CompiledMask without waiting for the device."""
+        ops = (_ffi.MetaOp * max(len(program), 1))()
+        for i, (op, slot, code) in enumerate(program):
+            ops[i].op, ops[i].slot, ops[i].code = int(op), int(slot), int(code)
+        m = ctypes.c_void_p()
+        rc = self._L.vdb_meta_compile(self._t, ops, len(program), int(mask_bits), ctypes.byref(m))
+        if rc:
+            _raise(rc)
+        return CompiledMask(self, m)
+
+
 class GpuFlatIndex(Index):
     """Drop-in for FlatIndex (src/flat_index.rs) backed by the MI355X engine."""
 
@@ -137,22 +232,25 @@ class GpuFlatIndex(Index):
         return int(self._L.vdb_flat_len(self._h))
 
     # ---- batched hot call (overrides the provided loop)
-    def search_batch(self, queries, id_mask=None, mask_bits=0):
-        """queries: sequence of (Vector, k).  Returns a list of [(id, distance), ...] per query."""
+    def search_batch(self, queries, id_mask=None, mask_bits=0, compiled_mask=None):
+        """queries: sequence of (Vector, k).  Returns a list of [(id, distance), ...] per query.
+        compiled_mask: a CompiledMask (MetaTable.compile) instead of id_mask / mask_bits; results are identical."""
         if len(queries) == 0:
             return []
         dims = {q.dimension() for q, _ in queries}
         if len(dims) != 1:
             # a ragged batch: the reference handles each query on its own (storage.rs:306-309)
-            return [self.search_batch([(q, k)], id_mask, mask_bits)[0] for q, k in queries]
+            return [self.search_batch([(q, k)], id_mask, mask_bits, compiled_mask)[0] for q, k in queries]
         qs = np.stack([q.data for q, _ in queries]).astype(np.float32, copy=False)
         ks = np.array([int(k) for _, k in queries], dtype=np.uintp)
-        ids, dists, counts = self.search_batch_arrays(qs, ks, id_mask=id_mask, mask_bits=mask_bits)
+        ids, dists, counts = self.search_batch_arrays(qs, ks, id_mask=id_mask, mask_bits=mask_bits, compiled_mask=compiled_mask)
         return [[(int(ids[b, i]), np.float32(dists[b, i])) for i in range(int(counts[b]))] for b in range(len(queries))]
 
-    def search_batch_arrays(self, queries, k, id_mask=None, mask_bits=0):
+    def search_batch_arrays(self, queries, k, id_mask=None, mask_bits=0, compiled_mask=None):
         """numpy in/out form: queries [nq, dim] f32, k an int or a per-query array.
         Returns (ids u64 [nq,kmax], dists f32 [nq,kmax], counts [nq])."""
+        if compiled_mask is not None and id_mask is not None:
+            raise ValueError("pass id_mask or compiled_mask, not both")
         qs = np.ascontiguousarray(queries, dtype=np.float32)
         nq, dim = qs.shape
         if np.isscalar(k):
@@ -169,9 +267,14 @@ class GpuFlatIndex(Index):
         if id_mask is not None:
             m = np.ascontiguousarray(id_mask, dtype=np.uint64)
             mask_ptr = _u64p(m)
-        rc = self._L.vdb_flat_search_batch(self._h, _fp(qs), nq, dim, ks_ptr, kscalar, mask_ptr, int(mask_bits),
-                                           kstride, _u64p(out_ids), _fp(out_d),
-                                           counts.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)))
+        if compiled_mask is not None:
+            rc = self._L.vdb_flat_search_batch_filtered(self._h, _fp(qs), nq, dim, ks_ptr, kscalar, compiled_mask.handle,
+                                                        kstride, _u64p(out_ids), _fp(out_d),
+                                                        counts.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)))
+        else:
+            rc = self._L.vdb_flat_search_batch(self._h, _fp(qs), nq, dim, ks_ptr, kscalar, mask_ptr, int(mask_bits),
+                                               kstride, _u64p(out_ids), _fp(out_d),
+                                               counts.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)))
         if rc:
             _raise(rc)
         return out_ids, out_d, counts

@@ -7,7 +7,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .error import DimensionMismatch, VectorNotFound
-from .index import GpuFlatIndex, Index
+from .index import GpuFlatIndex, Index, MetaTable
 from .vector import DistanceMetric, Vector
 
 
@@ -142,6 +142,10 @@ class VectorStore:
         self._cols = {}
         self._present = np.zeros(1024, dtype=bool)
         self._bulk = []                                  # attach_bulk_metadata ranges: (first internal id, n, ids or None)
+        # set_device_filter: the same columns resident on the index's GPU (a slot per field, in order of first appearance) and
+        # filters compiled there; None = off, the default
+        self._slots = {}
+        self._table = None
 
     @classmethod
     def with_index(cls, index):                      # storage.rs:118-127
@@ -174,7 +178,10 @@ class VectorStore:
         self._metadata[internal] = metadata
         self._mark_present(internal, True)
         for key, value in metadata.fields().items():
-            self._cols.setdefault(key, _Column()).set(internal, value)
+            col = self._column(key)
+            col.set(internal, value)
+            if self._table is not None:
+                self._table.set_codes(self._slots[key], internal, col.codes[internal:internal + 1])
         if old is not None:
             self._mark_present(old, False)
 
@@ -274,6 +281,16 @@ class VectorStore:
             new[:self._present.size] = self._present
             self._present = new
         self._present[internal] = on
+        if self._table is not None:
+            self._table.set_present(internal, 1, on)
+
+    def _column(self, key):
+        """The column of field `key`, created (with the next slot) when the field appears for the first time."""
+        col = self._cols.get(key)
+        if col is None:
+            col = self._cols[key] = _Column()
+            self._slots[key] = len(self._slots)
+        return col
 
     def attach_bulk_metadata(self, n, columns, ids=None):
         """Register n rows that are ALREADY in the index under the next n internal ids (a bulk device load, a mapped
@@ -300,9 +317,14 @@ class VectorStore:
         for key, values in columns.items():
             if len(values) != n:
                 raise ValueError(f"column {key!r} must have n entries")
-            self._cols.setdefault(key, _Column()).set_range(start, values)
+            col = self._column(key)
+            col.set_range(start, values)
+            if self._table is not None:
+                self._table.set_codes(self._slots[key], start, col.codes[start:start + n])
         self._mark_present(start + n - 1, False)                 # grow once
         self._present[start:start + n] = True
+        if self._table is not None and n:
+            self._table.set_present(start, n, True)
         self._bulk.append((start, n, new_ids, None if new_ids is None else {sid: start + j for j, sid in enumerate(new_ids)}))
         self._next_id += n
         if self._dimension is None and hasattr(self._index, "dim"):
@@ -427,10 +449,99 @@ class VectorStore:
         packed[:pb.size] = pb
         return packed.view(np.uint64), bits
 
+    # ---- the same mask compiled on the device from resident columns (include/vdb_flat.h vdb_meta_table)
+    def set_device_filter(self, on=True):
+        """on: keep the metadata columns and the presence bitmap resident on the index's GPU, forward every later insert /
+        upsert / delete / bulk attach to them, and let search_batch_prefiltered compile its filter there (one kernel launch,
+        nothing uploaded but the filter expression) instead of in numpy.  off (the default): free them.  Results are identical
+        either way.  A store whose index is not a GpuFlatIndex ignores the setting (an HNSW index consumes its mask on the host)."""
+        if not isinstance(self._index, GpuFlatIndex):
+            return
+        if not on:
+            table, self._table = self._table, None
+            if table is not None:
+                table.close()
+            return
+        if self._table is not None:
+            return
+        table = MetaTable(self._index._device)
+        n = self._next_id
+        for key, col in self._cols.items():
+            table.set_codes(self._slots[key], 0, col.codes[:min(n, col.codes.size)])
+        pres = self._present[:n]
+        edges = np.flatnonzero(np.diff(np.concatenate(([False], pres, [False])).astype(np.int8)))   # the runs of present ids
+        for a, b in zip(edges[0::2], edges[1::2]):
+            table.set_present(int(a), int(b - a), True)
+        self._table = table
+
+    def device_filter(self):
+        return self._table is not None
+
+    def filter_program(self, flt):
+        """The filter as the postfix program vdb_meta_compile takes: a list of (op, slot, code), or None when it needs more
+        than MetaTable.MAX_OPS ops or an evaluation stack deeper than MetaTable.MAX_DEPTH.  Everything that needs the
+        dictionary is resolved here, exactly as _eval_filter does: a field nobody has and a value no row has become CONST
+        (Eq / Exists 0, Ne 1), And([]) is CONST 1, Or([]) CONST 0, n-ary And / Or are left folds of the binary op."""
+        T = MetaTable
+        prog = []
+        depth = peak = 0
+        # iterative post-order walk (a filter may nest deeper than Python's recursion limit likes): ("visit", f) | ("emit", op)
+        todo = [("visit", flt)]
+        while todo:
+            what, f = todo.pop()
+            if what == "emit":
+                prog.append((f, 0, 0))
+                depth -= 1
+            elif f.op in ("eq", "ne", "exists"):
+                col = self._cols.get(f.field)
+                c = None
+                if col is not None and f.op != "exists":
+                    c = col.code(f.value) if f.value is not None else None
+                if col is None or (f.op != "exists" and c is None):
+                    prog.append((T.CONST, 0, 1 if f.op == "ne" else 0))
+                elif f.op == "exists":
+                    prog.append((T.EXISTS, self._slots[f.field], 0))
+                else:
+                    prog.append((T.EQ if f.op == "eq" else T.NE, self._slots[f.field], c))
+                depth += 1
+            elif f.op in ("and", "or"):
+                if not f.filters:
+                    prog.append((T.CONST, 0, 1 if f.op == "and" else 0))
+                    depth += 1
+                else:
+                    op = T.AND if f.op == "and" else T.OR
+                    steps = [("visit", f.filters[0])]
+                    for g in f.filters[1:]:
+                        steps += [("visit", g), ("emit", op)]
+                    todo.extend(reversed(steps))
+            else:
+                raise ValueError(f.op)
+            peak = max(peak, depth)
+            if len(prog) > T.MAX_OPS or peak > T.MAX_DEPTH:
+                return None
+        return prog
+
+    def compile_filter_device(self, flt):
+        """compile_filter on the device: a CompiledMask over max(next internal id, 1) bits, equal to compile_filter's word for
+        word.  The call does not wait for the device; release() the mask after the last search that uses it.  None when the
+        filter does not fit the program limits (filter_program)."""
+        if self._table is None:
+            raise ValueError("the device filter is off: set_device_filter(True) first")
+        prog = self.filter_program(flt)
+        if prog is None:
+            return None
+        return self._table.compile(prog, max(self._next_id, 1))
+
     def search_batch_prefiltered(self, queries, flt):
         if self.is_empty():
             return [[] for _ in queries]
         for q, _ in queries:
             self._check_dim(q)
+        cm = self.compile_filter_device(flt) if self._table is not None else None
+        if cm is not None:
+            try:
+                return [self._map(r) for r in self._index.search_batch(list(queries), compiled_mask=cm)]
+            finally:
+                cm.release()
         mask, bits = self.compile_filter(flt)
         return [self._map(r) for r in self._index.search_batch(list(queries), id_mask=mask, mask_bits=bits)]
