@@ -280,7 +280,8 @@ int vdb_flat_last_stats(const vdb_flat_index *h, uint64_t out[8]);
  *  [9] queries the screening tier could not certify and handed to the f32 MFMA tier
  *  [10] [11] [12] host clock of the call, ns: first tier enqueued / its flags on the host / return
  *  [13] queries answered by the re-threshold pass (a second screening pass whose thresholds are the score cuts that the
- *       k-th exact distances of the first pass imply; every key under the cut is re-ranked)
+ *       k-th exact distances of the first pass imply; every key under the cut is re-ranked), for every k the screening
+ *       tier serves: k <= 112 and the large-k range 112 < k <= 1024
  *  [14] 1 when the screening pass read the bf16 shadow rows (vdb_flat_set_shadow)
  *  [15] 1 when the library is the DIAGNOSTICS build (-DVDB_DIAG) and one of its environment knobs is set: such a run
  *       is not covered by the exactness guarantee.  Always 0 in the release library, which reads no environment.
@@ -305,8 +306,10 @@ int vdb_flat_set_wide(vdb_flat_index *h, int on);
 /* The screening tier's LARGE-k range (no reference counterpart; results are identical either way, bit for bit):
  *  1 (default): 112 < k <= 1024 is served by the bf16 screening pass too -- a deeper filter threshold, up to 2048
  *     candidates per query, and the certified re-rank of kernels_aux.hip (rerank_large_kernel) -- on indexes of at least
- *     vdb_flat_large_k_min_rows(k) rows; uncertified queries go to the exact scan.  last_stats_ex()[8] = 1 when it ran,
- *     [5] = the candidate depth;
+ *     vdb_flat_large_k_min_rows(k) rows; an uncertified query takes the re-threshold pass (one more filter pass under the
+ *     score cut of its k-th exact distance, every key under the cut re-ranked: last_stats_ex()[13]) and goes to the exact
+ *     scan only when more than 2048 keys lie under the cut or a candidate pool overflowed.  last_stats_ex()[8] = 1 when the
+ *     range ran, [5] = the candidate depth;
  *  0: k > 112 goes to the exact scan, as before the range existed.
  * On a sharded handle it applies to every shard. */
 int vdb_flat_set_large_k(vdb_flat_index *h, int on);
@@ -425,10 +428,13 @@ int vdb_flat_set_sample_cache(vdb_flat_index *h, int on);
 /* Test hook (no reference counterpart; results are identical whatever the flags): force the hand-over of queries to
  * the slower tiers so that every tier can be compared with every other on the same index.  Not read from the
  * environment -- the release library has no getenv on any path. */
-#define VDB_TIERS_NO_RETHRESHOLD 1u /* skip the re-threshold pass: uncertified queries go straight to the f32 MFMA tier */
+#define VDB_TIERS_NO_RETHRESHOLD 1u /* skip the re-threshold pass: uncertified queries go straight to the f32 MFMA tier (k <= 112) or the exact scan */
 #define VDB_TIERS_FORCE_F32 2u      /* hand EVERY query the screening tier answered to the f32 MFMA tier as well */
 #define VDB_TIERS_FORCE_EXACT 4u    /* hand every query to the exact scan */
 #define VDB_TIERS_NO_DIRECT 8u      /* small indexes (<= 16384 rows), batches of <= 8 queries: the tiered pipeline instead of the direct exact scan */
+#define VDB_TIERS_FORCE_RETHRESHOLD 16u /* hand every query the screening tier answered to the re-threshold pass as well (small and large k); a query
+                                         * without a finite score cut or with a pool overflow goes on as an uncertified one does.  Ignored together
+                                         * with FORCE_F32, FORCE_EXACT or NO_RETHRESHOLD */
 int vdb_flat_set_tiers(vdb_flat_index *h, unsigned flags);
 
 /*

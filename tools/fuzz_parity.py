@@ -61,6 +61,7 @@ def main():
     kinds = ["uniform", "gauss", "unit", "clustered", "dups", "scales"]
     t0 = time.time()
     tiers = {"screen": 0, "rethr": 0, "f32q": 0, "exact": 0, "ovf": 0}
+    large = {"cases": 0, "queries": 0, "screen": 0, "uncertified": 0, "rethr": 0, "exact": 0, "ovf": 0}   # 112 < k <= 1024 only
     for case in range(a.cases):
         n = int(rng.integers(16385, a.max_rows))
         if a.round3 and rng.random() < 0.3:
@@ -153,11 +154,14 @@ def main():
             gi, gd, gc = a1
             ok &= bool(gc[b] == len(oi) and np.array_equal(gi[b, :gc[b]], oi) and np.array_equal(gd[b, :gc[b]].view(np.uint32), od.view(np.uint32)))
         tiers["screen"] += st["bf16_screen"]; tiers["rethr"] += st["rethreshold_queries"]; tiers["f32q"] += st["f32_tier_queries"]; tiers["exact"] += st["exact_queries"]; tiers["ovf"] += st["pool_overflows"]
+        if 112 < k <= 1024:
+            large["cases"] += 1; large["queries"] += nq; large["screen"] += st["bf16_screen"]; large["uncertified"] += st["uncertified"]
+            large["rethr"] += st["rethreshold_queries"]; large["exact"] += st["exact_queries"]; large["ovf"] += st["pool_overflows"]
         print(("ok   " if ok else "FAIL ") + desc + f"  [screen={st['bf16_screen']} rethr={st['rethreshold_queries']} f32q={st['f32_tier_queries']} exact={st['exact_queries']} ovf={st['pool_overflows']}]", flush=True)
         if not ok:
             sys.exit(1)
         del ix
-    print(f"ALL {a.cases} CASES OK in {time.time() - t0:.0f} s; tier usage {tiers}", flush=True)
+    print(f"ALL {a.cases} CASES OK in {time.time() - t0:.0f} s; tier usage {tiers}; large k (113..1024) {large}", flush=True)
 
 
 if __name__ == "__main__":

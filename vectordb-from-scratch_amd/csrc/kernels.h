@@ -293,6 +293,8 @@ struct RerankParams {
     uint32_t* depth;                                   // may be null: candidates re-ranked per query (diagnostics)
     float* thr_next;                                   // may be null: for an UNCERTIFIED query the score cut above which no row can
                                                        // enter the top k (from the k-th exact distance found so far); NaN: no cut known
+    uint32_t cut_always;                               // 1 (VDB_TIERS_FORCE_RETHRESHOLD): thr_next gets the cut of EVERY query that has one
+                                                       // (a k-th exact distance, no NaN / ineligible candidate), certified or not
     int metric;
     uint32_t k;                                        // results wanted per query
     float eps_coef; const uint32_t* nd2max_bits;       // certification bound inputs (max row norm^2, f32 bits)
@@ -315,6 +317,8 @@ void launch_rerank_large(const RerankParams& p, uint32_t nq, hipStream_t s);
 // exhaustive variant: EVERY candidate of the list (up to cand_stride, any order) is re-ranked, the best k are kept;
 // cert[q] = 1 unless the list was truncated upstream (the caller's overflow flag) or a NaN score was seen
 void launch_rerank_all(const RerankParams& p, uint32_t nq, hipStream_t s);
+// the same for 112 < k <= 1024: up to 2048 keys per query through the sweep and sort area of the large-k re-rank
+void launch_rerank_all_large(const RerankParams& p, uint32_t nq, hipStream_t s);
 
 // ---------------------------------------------------------------- direct exact scan of a SMALL index for a few queries
 // Index::search as it stands (flat_index.rs:52-65) for indexes of at most 16384 rows and batches of at most 8 queries -- the shape

@@ -1179,7 +1179,7 @@ __global__ __launch_bounds__(RR_THREADS) void rerank_kernel(RerankParams p) {
         if (!cert) atomicOr(p.status + 1, 1u);             // summary word of the status block: some query needs the next tier
         if (p.thr_next) {
             float cut = __uint_as_float(0x7fc00000u);             // NaN: no cut known
-            if (!cert && cut_ok) cut = score_cut(p, q, cut_ek, (double)qn_f);
+            if ((!cert || p.cut_always) && cut_ok) cut = score_cut(p, q, cut_ek, (double)qn_f);
             p.thr_next[q] = cut;
         }
         if (p.depth) p.depth[q] = processed;
@@ -1323,7 +1323,11 @@ void launch_rerank(const RerankParams& p, uint32_t nq, hipStream_t s) {
 // ---------------------------------------------------------------------------------------------
 constexpr uint32_t RL_MAX = 2048, RL_KMAX = 1024, RL_THREADS = 512;
 constexpr uint32_t RL_AREA = 2048;                                // best k (<= 1024) + one sweep (<= 512), a power of two
-__global__ __launch_bounds__(RL_THREADS) void rerank_large_kernel(RerankParams p) {
+// ALL = true is the EXHAUSTIVE form (the re-threshold pass at large k, launch_rerank_all_large): the same sweep over every key of
+// the list in one round, in any order; a key whose row is out of range or masked out is skipped, no certificate is evaluated
+// (the list is complete by construction: cert = 1 unless a NaN score was seen; a truncated list is flagged by the select).
+template <bool ALL>
+__device__ __forceinline__ void rerank_large_body(const RerankParams& p) {
     extern __shared__ __attribute__((aligned(16))) float sRows[];   // query row + slice area of one sweep
     __shared__ uint32_t sDist[RL_AREA];
     __shared__ uint64_t sId[RL_AREA];
@@ -1335,7 +1339,7 @@ __global__ __launch_bounds__(RL_THREADS) void rerank_large_kernel(RerankParams p
     const uint32_t cnt = p.cand_cnt[q] < p.kp ? p.cand_cnt[q] : p.kp;
     const uint64_t* cand = p.cand + (size_t)q * p.cand_stride;
     if (tid == 0) { sAnyNan = 0; sNanKey = 0; sBad = 0; sNext = 0; }
-    if (tid == RL_THREADS - 1) sCert = cert_consts(p, q, (double)p.qnorm[q]);
+    if (!ALL && tid == RL_THREADS - 1) sCert = cert_consts(p, q, (double)p.qnorm[q]);
     for (uint32_t i = tid; i < RL_AREA; i += RL_THREADS) { sDist[i] = 0xffffffffu; sId[i] = ~0ull; }
     const uint32_t dimp = (p.dim + 3) & ~3u;
     const uint32_t area = p.lds_chunk;
@@ -1426,6 +1430,7 @@ __global__ __launch_bounds__(RL_THREADS) void rerank_large_kernel(RerankParams p
             __syncthreads();
         }
         // ---- certification / how much deeper to go (as rerank_kernel; ineligible candidates are counted by sBad)
+        if (ALL) { cert = sNanKey ? 0u : 1u; break; }             // one round took the whole list: nothing to certify
         const bool clean = !sNanKey && !sBad;
         const uint32_t nout = nbest;                              // = min(processed, k) when clean
         const bool can_test = clean && nout == k && nout > 0;
@@ -1459,7 +1464,17 @@ __global__ __launch_bounds__(RL_THREADS) void rerank_large_kernel(RerankParams p
         }
         break;
     }
-    const uint32_t nout = nbest;
+    uint32_t nout = nbest;
+    if (ALL) {
+        // skipped keys left padding pairs behind the real ones (sorted to the end): count the output by the padding distance,
+        // never by the id -- 2^64 - 1 is a legal id
+        if (tid == 0) sNext = 0;
+        __syncthreads();
+        for (uint32_t i = tid; i < nbest; i += RL_THREADS)
+            if (sDist[i] != 0xffffffffu && (i + 1 == nbest || sDist[i + 1] == 0xffffffffu)) sNext = i + 1;
+        __syncthreads();
+        nout = sNext;
+    }
     for (uint32_t i = tid; i < k; i += RL_THREADS) {
         const size_t o = (size_t)q * p.out_stride + i;
         if (i < nout) { p.out_ids[o] = sId[i]; p.out_dists[o] = ordered_to_f32(sDist[i]); }
@@ -1469,15 +1484,19 @@ __global__ __launch_bounds__(RL_THREADS) void rerank_large_kernel(RerankParams p
         p.out_counts[q] = nout;
         if (sAnyNan) atomicOr(p.status, ST_NAN);
         p.cert[q] = cert;
-        if (!cert) atomicOr(p.status + 1, 1u);
-        if (p.thr_next) {
-            float cut = __uint_as_float(0x7fc00000u);
-            if (!cert && cut_ok) cut = score_cut(p, q, cut_ek, (double)qn_f);
-            p.thr_next[q] = cut;
+        if (!ALL) {
+            if (!cert) atomicOr(p.status + 1, 1u);
+            if (p.thr_next) {
+                float cut = __uint_as_float(0x7fc00000u);
+                if ((!cert || p.cut_always) && cut_ok) cut = score_cut(p, q, cut_ek, (double)qn_f);
+                p.thr_next[q] = cut;
+            }
+            if (p.depth) p.depth[q] = processed;
         }
-        if (p.depth) p.depth[q] = processed;
     }
 }
+__global__ __launch_bounds__(RL_THREADS) void rerank_large_kernel(RerankParams p) { rerank_large_body<false>(p); }
+__global__ __launch_bounds__(RL_THREADS) void rerank_all_large_kernel(RerankParams p) { rerank_large_body<true>(p); }
 void launch_rerank_large(const RerankParams& p, uint32_t nq, hipStream_t s) {
     if (!nq || p.k == 0 || p.k > RL_KMAX) return;
     RerankParams q = p;
@@ -1491,6 +1510,18 @@ void launch_rerank_large(const RerankParams& p, uint32_t nq, hipStream_t s) {
     q.lds_chunk = (uint32_t)avail;
     const size_t lds = ((size_t)q.lds_row_stride + q.lds_chunk) * 4;
     hipLaunchKernelGGL(rerank_large_kernel, dim3(nq), dim3(RL_THREADS), lds, s, q);
+}
+// the exhaustive form (the re-threshold pass): every key of the list in ONE round, the same LDS plan
+void launch_rerank_all_large(const RerankParams& p, uint32_t nq, hipStream_t s) {
+    if (!nq || p.k == 0 || p.k > RL_KMAX) return;
+    RerankParams q = p;
+    q.kp = std::min(p.cand_stride, RL_MAX);
+    q.kp_first = q.kp; q.kp_step = 0;
+    const uint32_t dimp = (p.dim + 3) & ~3u;
+    q.lds_row_stride = dimp + 4;
+    q.lds_chunk = (uint32_t)((size_t)128 * 1024 / 4 - q.lds_row_stride);
+    const size_t lds = ((size_t)q.lds_row_stride + q.lds_chunk) * 4;
+    hipLaunchKernelGGL(rerank_all_large_kernel, dim3(nq), dim3(RL_THREADS), lds, s, q);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -461,7 +461,7 @@ int vdb_flat_search_batch_device_begin(vdb_flat_index* ix, const float* d_querie
         hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
         // (a forced hand-over to the slower tiers -- vdb_flat_set_tiers, tests -- rewrites the outputs in _finish whatever the
         // first tier certified: the word says "pending" then, so that a caller exchanging partial results exchanges again)
-        if (ix->cur->ctx.pending && (ix->tiers & (VDB_TIERS_FORCE_EXACT | VDB_TIERS_FORCE_F32))) {
+        if (ix->cur->ctx.pending && (ix->tiers & (VDB_TIERS_FORCE_EXACT | VDB_TIERS_FORCE_F32 | VDB_TIERS_FORCE_RETHRESHOLD))) {
             if (hipMemsetD32Async((hipDeviceptr_t)d_code, VDB_PENDING_HOST, 1, s) != hipSuccess) rc = fail(VDB_ERR_DEVICE, "hipMemsetD32Async failed");
         } else if (ix->cur->ctx.pending) vdb::launch_write_code(ix->cur->w_flags.p, d_code, s);
         else if (hipMemsetAsync(d_code, 0, 4, s) != hipSuccess) rc = fail(VDB_ERR_DEVICE, "hipMemsetAsync failed");
@@ -1022,7 +1022,7 @@ int vdb_flat_set_shadow(vdb_flat_index* ix, int on) {
 
 int vdb_flat_set_tiers(vdb_flat_index* ix, unsigned flags) {
     return guarded([&]() -> int {
-    if (!ix || (flags & ~15u)) return fail(VDB_ERR_INVALID_ARGUMENT, "flags must be a combination of VDB_TIERS_*");
+    if (!ix || (flags & ~31u)) return fail(VDB_ERR_INVALID_ARGUMENT, "flags must be a combination of VDB_TIERS_*");
     if (ix->multi) return multi_for_each(ix, [flags](vdb_flat_index* c) { return vdb_flat_set_tiers(c, flags); });
     std::lock_guard<std::mutex> g(ix->mu);
     ix->tiers = flags;

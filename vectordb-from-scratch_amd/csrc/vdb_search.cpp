@@ -237,6 +237,12 @@ int pass_f32(Index* ix, hipStream_t s, const float* qp, const float* qnorm, floa
     return VDB_OK;
 }
 
+// VDB_TIERS_FORCE_RETHRESHOLD in effect: ignored together with FORCE_EXACT / FORCE_F32, and when the pass itself is switched off
+static bool force_rethreshold(const Index* ix) {
+    return (ix->tiers & VDB_TIERS_FORCE_RETHRESHOLD) &&
+           !(ix->tiers & (VDB_TIERS_FORCE_EXACT | VDB_TIERS_FORCE_F32 | VDB_TIERS_NO_RETHRESHOLD));
+}
+
 // ------------------------------------------------------------------ tier: bf16 screening + certified re-rank
 // Same structure, with the scores of the HBM-bound bf16 kernels (fused_bf16_common.h): group minima of a row
 // sample -> per-query threshold -> one pass over all rows keeping the keys under the threshold -> the kp smallest
@@ -407,6 +413,7 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
             rp.qerr = ix->cur->w_qerr.p + qb0; rp.c_acc = c_acc_bf16(ix); rp.lb_scores = ix->d_margin ? 1u : 0u;
             rp.kp_first = round_up((uint32_t)k + 38u, 16u); rp.kp_step = 32;
             rp.thr_next = d_thr_next ? d_thr_next + qb0 : nullptr;
+            rp.cut_always = force_rethreshold(ix) ? 1u : 0u;
             // diagnostics build: the first re-rank round overridden, the depth each query ended at printed
             if (ix->kn.kp_first) rp.kp_first = ix->kn.kp_first;
             const bool dump_depth = ix->kn.rr_depth;
@@ -436,8 +443,9 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
 // For queries the screening tier re-ranked to its depth limit without a certificate, the k-th exact distance found so
 // far still bounds the answer: rerank_kernel turned it into a score cut above which no row can enter the top k.  The
 // queries are gathered into a compact block, the HBM-bound filter pass runs once more with those cuts as thresholds,
-// and EVERY key that passes (up to 2048 per query) is re-ranked exactly.  Exact by construction; a query whose list does
-// not fit (pool overflow, more than 2048 keys) keeps its flag and goes on to the next tier.
+// and EVERY key that passes (up to 2048 per query) is re-ranked exactly: by rerank_all_kernel for k <= 112, by the exhaustive
+// form of the large-k re-rank above that (k <= 1024).  Exact by construction; a query whose list does not fit (pool overflow,
+// more than 2048 keys) keeps its flag and goes on to the next tier.
 // todo: batch indices; cuts: their score cuts.  On return flags2 (host) holds cert / overflow per compact query.
 int pass_rethreshold(Index* ix, hipStream_t s, const std::vector<uint32_t>& todo, const std::vector<float>& cuts, size_t k,
                      const uint32_t* d_rowmask, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
@@ -477,7 +485,8 @@ int pass_rethreshold(Index* ix, hipStream_t s, const std::vector<uint32_t>& todo
         vdb::launch_select(mp, nb, s);
         vdb::RerankParams rp = rerank_params(ix, d_rowmask, d_status, k, ix->cur->w2_cand.p, KMAX, d_cand_cnt);
         rerank_io(rp, ix, ix->cur->w2_qp.p, ix->cur->w2_qnorm.p, ix->cur->w2_outi.p, ix->cur->w2_outd.p, ix->cur->w2_outc.p, d_cert2, q0);
-        vdb::launch_rerank_all(rp, nb, s);
+        if (k <= BF16_MAX_K) vdb::launch_rerank_all(rp, nb, s);
+        else vdb::launch_rerank_all_large(rp, nb, s);
     }
     HIP_TRY(hipGetLastError());
     flags2.assign(2 * (size_t)nf, 0u);
@@ -856,17 +865,17 @@ int search_part2(Index* ix, int* changed) {
     const bool force_exact = (ix->tiers & VDB_TIERS_FORCE_EXACT) != 0;
     const bool force_f32 = (ix->tiers & VDB_TIERS_FORCE_F32) != 0;
     const bool no_rethr = (ix->tiers & VDB_TIERS_NO_RETHRESHOLD) != 0;
+    const bool force_rethr = kp16 && force_rethreshold(ix);       // every query with a cut takes the re-threshold pass as well
     std::vector<uint32_t> todo;
     for (uint32_t q = 0; q < nq32; ++q) {
         bool cert = ix->cur->h_flags[4 + q] != 0, ovf = ix->cur->h_flags[4 + nq32 + q] != 0;
         if (ovf) ++ix->cur->stats[2];
         if (!cert) ++ix->cur->stats[6];
-        if (cert && !ovf && !force_exact && !(kp16 && force_f32)) continue;
+        if (cert && !ovf && !force_exact && !(kp16 && force_f32) && !force_rethr) continue;
         todo.push_back(q);
     }
     if (changed && !todo.empty()) *changed = 1;
-    // (the re-threshold pass re-ranks with rerank_all_kernel, k <= 112: an uncertified large-k query goes on to the exact scan)
-    if (kp16 && !todo.empty() && !no_rethr && !force_exact && !force_f32 && k <= BF16_MAX_K) {
+    if (kp16 && !todo.empty() && !no_rethr && !force_exact && !force_f32) {
         // ---- tier 0b: queries with a known score cut get one more HBM-bound pass with that cut as the threshold
         const uint32_t* h_ovf = ix->cur->h_flags + 4 + nq32;
         const float* h_cut = reinterpret_cast<const float*>(ix->cur->h_flags + 4 + 2 * (size_t)nq32);

@@ -512,6 +512,7 @@ class GpuFlatIndex(Index):
         return out
 
     TIERS_NO_RETHRESHOLD, TIERS_FORCE_F32, TIERS_FORCE_EXACT, TIERS_NO_DIRECT = 1, 2, 4, 8
+    TIERS_FORCE_RETHRESHOLD = 16
 
     def set_shadow(self, on=True):
         """Opt-in bf16 shadow of the rows for the screening pass (include/vdb_flat.h: +50 % device memory, half the HBM bytes
