@@ -10,7 +10,7 @@
  * traversal asks for (graph.rs:155, :182, :224) is evaluated on the MI355X, in the reference's exact f32 operation
  * order (distance.rs:37-73).  Searches run DEVICE-RESIDENT by default (kernels_hnsw.hip): the graph is mirrored in HBM
  * and one workgroup per query walks it, with the reference's priority queues in LDS -- one launch per batch; what does
- * not fit that kernel (m > 19, ef > 1022, a walk that overflows its LDS structures, vdb_hnsw_set_traversal) is traversed on
+ * not fit that kernel (m > 19, ef > 1023, a walk that overflows its LDS structures, vdb_hnsw_set_traversal) is traversed on
  * the host with the candidate lists of ALL in-flight queries evaluated in one launch per traversal round.  Both give
  * the reference's results; there is no CPU distance path.
  *

@@ -8,7 +8,17 @@ of any object with entry_point() / neighbors(id, layer) -- oracle.HnswOracle or 
   - output: the results sorted by distance, truncated to k.
 
 Python's heapq stands in for Rust's BinaryHeap: the order of EQUAL distances may differ, so callers use data without ties
-(Gaussian rows).  eligible = None is the unfiltered search_knn."""
+(Gaussian rows).  eligible = None is the unfiltered search_knn.
+
+`peaks` (a dict handed to search) also receives the two quantities the device walk's capacities are stated in
+(kernels_hnsw.hip), exactly and over EVERY layer searched, the greedy descent included:
+
+  "pushed"         the largest length of `candidates` immediately after a push.  The kernel fails a walk that would push with
+                   CAND_CAP (CAND_CAP_F when filtered) entries in the heap, so a walk fails on that cap iff this exceeds it.
+                   ("candidates", the older key, is len + 1 once per expansion at layer 0: an upper bound, not this number.)
+  "layer_visited"  the final len(visited) of each layer searched, in search order (max_level first, layer 0 last).  The
+                   kernel clears and recounts its visited set per layer; the plain walk fails iff one of these exceeds 3/4 of
+                   VIS_CAP."""
 import heapq
 
 import numpy as np
@@ -34,6 +44,7 @@ class Walker:
         visited = {ep}
         d0 = dist(ep)
         cand = [(d0, ep)]                                       # min-heap: closest candidate first
+        peaks["pushed"] = max(peaks.get("pushed", 0), 1)
         res = []                                                # max-heap by (distance, id) as (-d, -id)
         if eligible is None or eligible(ep):
             heapq.heappush(res, (-d0, -ep))
@@ -52,24 +63,31 @@ class Walker:
                 furthest = -res[0][0] if res else F32_MAX
                 if d < furthest or len(res) < ef:
                     heapq.heappush(cand, (d, nid))
+                    if len(cand) > peaks["pushed"]:
+                        peaks["pushed"] = len(cand)
                     if eligible is None or eligible(nid):
                         heapq.heappush(res, (-d, -nid))
                         if len(res) > ef:
                             heapq.heappop(res)
             peaks["candidates"] = max(peaks["candidates"], len(cand) + 1)
         peaks["visited"] = max(peaks["visited"], len(visited))
+        peaks.setdefault("layer_visited", []).append(len(visited))
         out = sorted(((-nd, -ni) for nd, ni in res), key=lambda t: t[0])
         return [i for _, i in out], [d for d, _ in out]
 
     def search(self, query, k, ef, eligible=None, peaks=None):
-        """-> (ids u64 array, dists f32 array); peaks (a dict) receives the layer-0 visited count and candidate-heap peak."""
+        """-> (ids u64 array, dists f32 array); peaks (a dict) receives the layer-0 visited count and candidate-heap peak
+        ("visited", "candidates") and the exact per-walk counters "pushed" and "layer_visited" (module docstring)."""
         peaks = {"visited": 0, "candidates": 0} if peaks is None else peaks
-        peaks.setdefault("visited", 0); peaks.setdefault("candidates", 0)
+        peaks.setdefault("visited", 0); peaks.setdefault("candidates", 0); peaks.setdefault("pushed", 0)
+        peaks["layer_visited"] = []                             # of THIS search; the three peaks accumulate over a reused dict
         ep, max_level = self.g.entry_point()
         if ep is None:
             return np.zeros(0, np.uint64), np.zeros(0, np.float32)
         for layer in range(max_level, 0, -1):
-            ids, _ = self.search_layer(query, ep, 1, layer, None, {"visited": 0, "candidates": 0})
+            upper = {"visited": 0, "candidates": 0, "pushed": peaks["pushed"], "layer_visited": peaks["layer_visited"]}
+            ids, _ = self.search_layer(query, ep, 1, layer, None, upper)
+            peaks["pushed"] = upper["pushed"]
             if ids:
                 ep = ids[0]
         ids, ds = self.search_layer(query, ep, max(ef, k), 0, eligible, peaks)

@@ -35,7 +35,7 @@ def main():
         d = int(rng.choice([1, 2, 7, 16, 33, 64, 128, 300]))
         metric = int(rng.integers(0, 3))
         m = int(rng.choice([2, 4, 8, 16, 19, 24]))
-        efc = int(rng.choice([8, 32, 100, 200]))
+        efc = int(rng.choice([8, 32, 100, 200, 520]))            # 520: the insert walks' result heap beyond the wave pop (514)
         kind = str(rng.choice(["uniform", "gauss", "dups"]))
         if kind == "uniform":
             rows = rng.random((n, d), dtype=np.float32)
@@ -99,7 +99,7 @@ def main():
         q = rng.standard_normal((nq, d)).astype(np.float32) if kind == "gauss" else rng.random((nq, d), dtype=np.float32)
         if metric == 1:
             q[np.linalg.norm(q, axis=1) == 0] += 1.0
-        for (k, ef) in [(10, 100), (1, 16), (int(rng.integers(1, 60)), int(rng.choice([10, 50, 300])))]:
+        for (k, ef) in [(10, 100), (1, 16), (int(rng.integers(1, 60)), int(rng.choice([10, 50, 300, 513, 514, 1022])))]:   # 513 / 514: the last wave pop, the first single-lane pop
             gi, gd, gc = g.search_batch_arrays(q, k, ef)
             for b in range(nq):
                 oi, od = o.search(q[b], k, ef)

@@ -671,7 +671,7 @@ int vdb_hnsw_remove(vdb_hnsw_index* g, uint64_t id) {             // graph.rs:34
 namespace {
 
 // host traversal (one GPU launch per round for the candidate lists of every query): the path for what the device-resident
-// search does not take (m > 19, ef > 1022, overflowing queries, vdb_hnsw_set_traversal(h, 1, ..)); id_mask: the pre-filter of
+// search does not take (m > 19, ef > 1023, overflowing queries, vdb_hnsw_set_traversal(h, 1, ..)); id_mask: the pre-filter of
 // layer 0 (LayerSearch::mask), nullptr = none
 int search_host(vdb_hnsw_index* g, const float* queries, size_t nq, size_t dim, size_t k, size_t ef, const uint64_t* id_mask,
                 size_t mask_bits, uint64_t* out_ids, float* out_dists, size_t* out_counts) {
