@@ -386,7 +386,10 @@ size_t vdb_flat_debug_sparse_tile_queries(void);
  * table must then be on devices[0]); a mask on another device or a null mask is VDB_ERR_INVALID_ARGUMENT.
  */
 typedef struct vdb_meta_table vdb_meta_table;
+#ifndef VDB_META_MASK_DECLARED                  /* (vdb_hnsw.h declares the same type: either header may come first) */
+#define VDB_META_MASK_DECLARED
 typedef struct vdb_meta_mask vdb_meta_mask;
+#endif
 enum { VDB_META_EQ = 0, VDB_META_NE = 1, VDB_META_EXISTS = 2, VDB_META_CONST = 3, VDB_META_AND = 4, VDB_META_OR = 5 };
 typedef struct vdb_meta_op { uint32_t op; uint32_t slot; int32_t code; } vdb_meta_op; /* CONST: code = 0 | 1; AND / OR: both unused */
 int vdb_meta_create(int device, vdb_meta_table **out);

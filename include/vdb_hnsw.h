@@ -85,6 +85,28 @@ int vdb_hnsw_search_batch_masked(vdb_hnsw_index *h, const float *queries, size_t
                                  const uint64_t *id_mask, size_t mask_bits, uint64_t *out_ids, float *out_dists,
                                  size_t *out_counts);
 
+#ifndef VDB_META_MASK_DECLARED                  /* (vdb_flat.h declares the same type: either header may come first) */
+#define VDB_META_MASK_DECLARED
+typedef struct vdb_meta_mask vdb_meta_mask;
+#endif
+
+/* vdb_hnsw_search_batch_masked with the mask taken from a filter compiled on the device (vdb_meta_compile of vdb_flat.h): id_mask
+ * = the compiled mask's words, mask_bits = its bits.  Ids, order, distance bits and counts are those of the masked call on every
+ * route (device walk, host traversal, the filter scan below), and vdb_hnsw_stats counts the call the same way.  Nothing is built
+ * or uploaded by the host: one small kernel behind the mask's event ANDs it with the graph's presence and counts what is left
+ * (8 bytes read back); the walk reads that mask where it is, the filter scan hands it to the inner flat index as a device mask,
+ * and only a host traversal (vdb_hnsw_set_traversal, m > 19, ef > 1023, a walk that overflowed) copies its words back, once.
+ * A null mask, or a mask on another device than the index's, is VDB_ERR_INVALID_ARGUMENT before any device work.  The mask must
+ * stay unreleased until the call returns. */
+int vdb_hnsw_search_batch_filtered(vdb_hnsw_index *h, const float *queries, size_t nq, size_t dim, size_t k, size_t ef,
+                                   const vdb_meta_mask *mask, uint64_t *out_ids, float *out_dists, size_t *out_counts);
+
+/* Test hook: the first half of vdb_hnsw_search_batch_filtered alone -- the compiled mask ANDed with the graph's presence over
+ * min(the mask's bits, node ids of the graph) bits.  Copies the ceil(bits / 64) words to out_words (at most cap_words; more is
+ * VDB_ERR_INVALID_ARGUMENT), their number to *out_nwords and the number of set bits to *out_count.  No search is performed. */
+int vdb_hnsw_debug_present_mask(vdb_hnsw_index *h, const vdb_meta_mask *mask, uint64_t *out_words, size_t cap_words,
+                                size_t *out_nwords, uint64_t *out_count);
+
 /* The brute-force route of very selective filters (default 0 = never: every masked search is walked, as described above).  With
  * max_eligible > 0 a vdb_hnsw_search_batch_masked call whose mask leaves at most max_eligible PRESENT nodes eligible (and k <=
  * 2048; max_eligible is capped at 131072) is not walked: the inner flat index scans exactly those nodes' vectors

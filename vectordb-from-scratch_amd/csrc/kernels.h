@@ -505,6 +505,16 @@ struct HnswScatterParams {
     uint32_t* nbrU; uint32_t* nbrU_row; uint32_t strideU;
 };
 void launch_hnsw_scatter(const HnswScatterParams& p, hipStream_t s);
+// a compiled filter mask ANDed with the graph's presence (vdb_hnsw_search_batch_filtered): out[w] for w < ceil(bits / 64), bit i
+// set when i < bits (= min(the mask's bits, n_ids), the caller's clamp), bit i of src is set (src holds src_words words) and
+// row_of[i] != 0xffffffff; *count += the set bits (a 64-bit word the caller zeroes on the same stream).  bits = 0 launches nothing.
+struct HnswPresentMaskParams {
+    const uint64_t* src; uint64_t src_words;
+    const uint32_t* row_of; uint32_t n_ids;
+    uint32_t bits;
+    uint64_t* out; unsigned long long* count;
+};
+void launch_hnsw_present_mask(const HnswPresentMaskParams& p, hipStream_t s);
 bool hnsw_search_supported(uint32_t dim, uint32_t ef, uint32_t k, uint32_t max_list);
 
 void launch_merge_packed(const int32_t* packed, size_t words_per_part, uint32_t nparts, uint32_t nq, uint32_t k,

@@ -484,6 +484,35 @@ __global__ __launch_bounds__(64) void hnsw_scatter_kernel(HnswScatterParams p) {
     }
 }
 
+// A compiled filter mask (kernels_filter.hip) ANDed with the graph's presence, and the number of nodes it leaves eligible: the
+// shape of filter_compile_kernel -- one lane per id, one wave per 64-bit output word, the wave's __ballot IS the word (wave64),
+// written by lane 0 with an ordinary store, so the tail bits of the last word are clear.  The source word (one address for the
+// whole wave) is read only below src_words, row_of[id] (consecutive lanes, consecutive words) only below n_ids; the workgroups
+// stride over the words and add their popcounts to *count with one atomic each (the caller zeroed it on the same stream).
+constexpr uint32_t PM_THREADS = 256, PM_WAVES = PM_THREADS / 64;
+
+__global__ __launch_bounds__(PM_THREADS) void hnsw_present_mask_kernel(HnswPresentMaskParams p, uint64_t n_words) {
+    __shared__ uint32_t sCnt[PM_WAVES];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t found = 0;                                                  // set bits of this wave's words (the same in every lane)
+    for (uint64_t w = (uint64_t)blockIdx.x * PM_WAVES + wave; w < n_words; w += (uint64_t)gridDim.x * PM_WAVES) {
+        const uint64_t id = w * 64u + lane;
+        const uint64_t src = w < p.src_words ? p.src[w] : 0ull;
+        uint32_t row = 0xffffffffu;
+        if (id < p.n_ids) row = p.row_of[id];
+        const uint64_t word = __ballot(id < p.bits && ((src >> lane) & 1ull) && row != 0xffffffffu);
+        if (lane == 0) p.out[w] = word;
+        found += (uint32_t)__popcll(word);
+    }
+    if (lane == 0) sCnt[wave] = found;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long total = 0;
+        for (uint32_t i = 0; i < PM_WAVES; ++i) total += sCnt[i];
+        if (total) atomicAdd(p.count, total);
+    }
+}
+
 // Two staging buffers of stage_rows x (chunk + 4) floats in what the walk's own structures leave of the 160 KB: the largest chunk
 // of 256 / 192 / 128 / 64 elements that fits (m = 16 at 768 dimensions: 33 rows x 192), not larger than the rows; 0 = does not fit.
 static uint32_t hnsw_stage_plan(uint32_t dim, uint32_t stage_rows, size_t* bytes) {
@@ -507,6 +536,13 @@ bool hnsw_search_supported(uint32_t dim, uint32_t ef, uint32_t k, uint32_t max_l
 void launch_hnsw_scatter(const HnswScatterParams& p, hipStream_t s) {
     if (!(p.n0 + p.nU)) return;
     hipLaunchKernelGGL(hnsw_scatter_kernel, dim3(p.n0 + p.nU), dim3(64), 0, s, p);
+}
+void launch_hnsw_present_mask(const HnswPresentMaskParams& p, hipStream_t s) {
+    const uint64_t n_words = ((uint64_t)p.bits + 63) / 64;
+    if (n_words == 0) return;                                            // nothing to write: the count stays at the caller's 0
+    const uint64_t want = (n_words + PM_WAVES - 1) / PM_WAVES;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(want, 2048);      // 8 workgroups per CU of a 256-CU part; they stride
+    hipLaunchKernelGGL(hnsw_present_mask_kernel, dim3(grid), dim3(PM_THREADS), 0, s, p, n_words);
 }
 uint32_t hnsw_filter_launch_queries(uint32_t n_ids) {
     const size_t per_q = (size_t)((n_ids + 31u) / 32u) * 4u;

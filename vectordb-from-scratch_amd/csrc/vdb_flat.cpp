@@ -550,10 +550,11 @@ int vdb_flat_search_batch_device_wait(vdb_flat_index* ix, int ticket) {
 }  // extern "C"
 
 // vdb_flat_search_batch and vdb_flat_search_batch_filtered: the id mask comes from the host (id_mask, uploaded here) or is a
-// compiled one already in HBM (cm: the stream is ordered behind its event, nothing is uploaded); everything below is the same
+// compiled one already in HBM (cm: the stream is ordered behind its event, nothing is uploaded); everything below is the same.
+// dm (vdb_internal::search_batch_device_mask): mask_bits bits at a device address, written on the handle's own stream.
 static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks,
                              size_t k, const uint64_t* id_mask, size_t mask_bits, const vdb_meta_mask* cm, size_t kstride,
-                             uint64_t* out_ids, float* out_dists, size_t* out_counts) {
+                             uint64_t* out_ids, float* out_dists, size_t* out_counts, const uint64_t* dm = nullptr) {
     return guarded([&]() -> int {
     if (!ix || (nq && (!queries || !out_counts))) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
     if (cm) {
@@ -561,7 +562,10 @@ static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq
         if (cm->device != dev) return fail(VDB_ERR_INVALID_ARGUMENT, "the compiled mask lives on device %d, the index on device %d", cm->device, dev);
         mask_bits = cm->bits;
     }
-    if (ix->multi) return multi_search_host(ix, queries, nq, dim, ks, k, id_mask, mask_bits, kstride, out_ids, out_dists, out_counts, cm);
+    if (ix->multi) {
+        if (dm) return refuse_multi("a search under a raw device mask");
+        return multi_search_host(ix, queries, nq, dim, ks, k, id_mask, mask_bits, kstride, out_ids, out_dists, out_counts, cm);
+    }
     size_t kmax = k;
     if (ks) {
         kmax = 0;
@@ -580,7 +584,7 @@ static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq
     hipStream_t s = ix->stream;
     // Small index, a few queries (BASELINE configs[0]: Index::search itself, one query): queries and results go through MAPPED
     // host memory -- the two kernels of the direct path read and write it in place, nothing is copied by the runtime
-    if (direct_eligible(ix, ix->n_rows(), nq, kdev) && ix->misfits.empty() && dim == ix->dim && !id_mask && !cm) {
+    if (direct_eligible(ix, ix->n_rows(), nq, kdev) && ix->misfits.empty() && dim == ix->dim && !id_mask && !cm && !dm) {
         const size_t qb = nq * dim * sizeof(float), ib = nq * kdev * sizeof(uint64_t), db = nq * kdev * sizeof(float), cb = nq * sizeof(uint32_t);
         const size_t o_i = (qb + 15) & ~(size_t)15, o_d = o_i + ib, o_c = o_d + ((db + 15) & ~(size_t)15);
         if ((rc = ensure_host_io(ix, o_c + cb))) return rc;
@@ -615,6 +619,8 @@ static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq
     } else if (cm) {
         HIP_TRY(hipStreamWaitEvent(s, cm->done, 0));
         d_mask = cm->d_words;
+    } else if (dm) {
+        d_mask = dm;
     }
     rc = search_device(ix, ix->cur->w_qin.p, nq, dim, kdev, d_mask, mask_bits, ix->cur->w_outi.p, ix->cur->w_outd.p, ix->cur->w_outc.p,
                        nullptr);
@@ -1280,6 +1286,11 @@ int device_view(vdb_flat_index* ix, DeviceView* out) {
     out->rows = ix->d_rows; out->ld = ix->ld; out->dim = ix->dim; out->nd = ix->d_nd; out->qp = ix->cur->w_qp.p; out->qnorm = ix->cur->w_qnorm.p;
     out->metric = ix->metric; out->stream = (void*)ix->stream; out->status = ix->cur->w_flags.p;
     return VDB_OK;
+}
+int search_batch_device_mask(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, size_t k, const uint64_t* d_mask,
+                             size_t mask_bits, uint64_t* out_ids, float* out_dists, size_t* out_counts) {
+    if (!d_mask) return fail(VDB_ERR_INVALID_ARGUMENT, "null mask");
+    return search_batch_host(ix, queries, nq, dim, nullptr, k, nullptr, mask_bits, nullptr, k, out_ids, out_dists, out_counts, d_mask);
 }
 int set_error(int code, const char* msg) { return fail(code, "%s", msg); }
 int zero_vector_error() { return fail_zero_vector(); }

@@ -21,6 +21,7 @@
 #include <cfloat>
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -32,6 +33,7 @@
 #include "../../include/vdb_flat.h"
 #include "../../include/vdb_hnsw.h"
 #include "vdb_internal.h"
+#include "vdb_meta.h"
 #include "kernels.h"
 
 namespace {
@@ -132,7 +134,7 @@ inline bool is_zero_norm_mark(float d) { uint32_t b; memcpy(&b, &d, 4); return b
 
 struct vdb_hnsw_index {
     vdb_flat_index* flat = nullptr;
-    int metric = 0;
+    int metric = 0, device = 0;
     size_t m = 16, m_max0 = 32, ef_construction = 200, ef_search = 50, max_layers = 16;
     double ml = 0;
     uint64_t rng = 0;
@@ -152,6 +154,7 @@ struct vdb_hnsw_index {
     uint64_t device_queries = 0, host_redone = 0;
     // pre-filtered searches: the id mask on the device and the layer-0 visited bitmaps of one filtered launch
     uint64_t* d_mask = nullptr; size_t mask_cap = 0;
+    unsigned long long* d_eligible = nullptr;                     // vdb_hnsw_search_batch_filtered: present nodes the compiled mask admits
     uint32_t* d_vis = nullptr; size_t vis_cap = 0;
     // batched insert scans: two mapped host matrices [SCAN_CHUNK][scan_ld] the scan kernel writes, a stream and events
     float* h_scan[2] = {nullptr, nullptr}; float* d_scan[2] = {nullptr, nullptr}; size_t scan_ld = 0;
@@ -598,7 +601,7 @@ int vdb_hnsw_create(int metric, size_t m, size_t ef_construction, size_t ef_sear
     int rc = vdb_flat_create(metric, device, &flat);
     if (rc) return rc;
     auto* g = new vdb_hnsw_index();
-    g->flat = flat; g->metric = metric; g->m = m; g->m_max0 = 2 * m; g->ef_construction = ef_construction;
+    g->flat = flat; g->metric = metric; g->device = device; g->m = m; g->m_max0 = 2 * m; g->ef_construction = ef_construction;
     g->ef_search = ef_search; g->ml = 1.0 / std::log((double)m); g->rng = seed;              // graph.rs:49-59
     *out = g;
     return VDB_OK;
@@ -783,6 +786,7 @@ void free_mirror(vdb_hnsw_index* g) {
     for (uint32_t** p : {&g->d_row_of, &g->d_level, &g->d_nbr0, &g->d_cnt0, &g->d_up_off, &g->d_nbrU, &g->d_cntU, &g->d_nbr0_row, &g->d_nbrU_row, &g->d_out_counts, &g->d_fail, &g->d_vis})
         if (*p) { (void)hipFree(*p); *p = nullptr; }
     if (g->d_mask) { (void)hipFree(g->d_mask); g->d_mask = nullptr; }
+    if (g->d_eligible) { (void)hipFree(g->d_eligible); g->d_eligible = nullptr; }
     g->mask_cap = g->vis_cap = 0;
     if (g->d_out_ids) { (void)hipFree(g->d_out_ids); g->d_out_ids = nullptr; }
     if (g->d_out_dists) { (void)hipFree(g->d_out_dists); g->d_out_dists = nullptr; }
@@ -1145,12 +1149,24 @@ int build_speculative(Graph* g, const uint64_t* ids, uint64_t first_id, size_t n
     return VDB_OK;
 }
 
+// g->d_mask with room for `words` 64-bit words (at least one)
+int ensure_mask(vdb_hnsw_index* g, size_t words) {
+    if (words > g->mask_cap) {
+        if (g->d_mask) (void)hipFree(g->d_mask);
+        g->d_mask = nullptr; g->mask_cap = 0;
+        HN_TRY(hipMalloc((void**)&g->d_mask, words * 8));
+        g->mask_cap = words;
+    }
+    return VDB_OK;
+}
+
 // device-resident search of the whole batch in one launch (pre-filtered: one per hnsw_filter_launch_queries queries); queries
-// whose walk overflowed the kernel's LDS structures are listed in `redo`
+// whose walk overflowed the kernel's LDS structures are listed in `redo`.  resident: the mask is not id_mask but what
+// present_mask_device left in g->d_mask (mask_bits bits, already clamped to the mirror's ids) behind a pairs_begin of these queries
 int search_device(vdb_hnsw_index* g, const float* queries, size_t nq, size_t dim, size_t k, size_t ef_actual, const uint64_t* id_mask,
-                  size_t mask_bits, uint64_t* out_ids, float* out_dists, size_t* out_counts, std::vector<uint32_t>& redo) {
+                  size_t mask_bits, bool resident, uint64_t* out_ids, float* out_dists, size_t* out_counts, std::vector<uint32_t>& redo) {
     int rc;
-    if ((rc = vdb_internal::pairs_begin(g->flat, queries, nq, dim))) return rc;
+    if (!resident && (rc = vdb_internal::pairs_begin(g->flat, queries, nq, dim))) return rc;
     vdb_internal::DeviceView dv;
     if ((rc = vdb_internal::device_view(g->flat, &dv))) return rc;
     hipStream_t s = (hipStream_t)dv.stream;
@@ -1175,20 +1191,14 @@ int search_device(vdb_hnsw_index* g, const float* queries, size_t nq, size_t dim
     hp.stride0 = g->stride0; hp.up_off = g->d_up_off; hp.nbrU = g->d_nbrU; hp.nbrU_row = g->d_nbrU_row; hp.cntU = g->d_cntU; hp.strideU = g->strideU;
     hp.entry_point = (uint32_t)g->ep; hp.max_level = (uint32_t)g->max_level; hp.ef = (uint32_t)ef_actual; hp.k = (uint32_t)k;
     hp.out_ids = g->d_out_ids; hp.out_dists = g->d_out_dists; hp.out_counts = g->d_out_counts; hp.fail = g->d_fail; hp.status = dv.status;
-    if (!id_mask) {
+    if (!id_mask && !resident) {
         vdb::launch_hnsw_search(hp, (uint32_t)nq, s);
         HN_TRY(hipGetLastError());
     } else {
         // the mask once per call, clamped to the mirror's ids (bits beyond it name no node); the visited bitmaps per launch
         const uint32_t bits = (uint32_t)std::min<size_t>(mask_bits, g->mirror_ids);
-        const size_t words = std::max<size_t>((bits + 63) / 64, 1);
-        if (words > g->mask_cap) {
-            if (g->d_mask) (void)hipFree(g->d_mask);
-            g->d_mask = nullptr; g->mask_cap = 0;
-            HN_TRY(hipMalloc((void**)&g->d_mask, words * 8));
-            g->mask_cap = words;
-        }
-        if (bits) HN_TRY(hipMemcpyAsync(g->d_mask, id_mask, (size_t)(bits + 63) / 64 * 8, hipMemcpyHostToDevice, s));
+        if ((rc = ensure_mask(g, std::max<size_t>((bits + 63) / 64, 1)))) return rc;
+        if (bits && !resident) HN_TRY(hipMemcpyAsync(g->d_mask, id_mask, (size_t)(bits + 63) / 64 * 8, hipMemcpyHostToDevice, s));
         const size_t per_launch = std::min<size_t>(nq, vdb::hnsw_filter_launch_queries(g->mirror_ids));
         const size_t vis_bytes = vdb::hnsw_filter_vis_bytes(g->mirror_ids, (uint32_t)per_launch);
         if (vis_bytes > g->vis_cap) {
@@ -1258,6 +1268,135 @@ bool present_mask_within(const vdb_hnsw_index* g, const uint64_t* id_mask, size_
     return true;
 }
 
+// Steps 1-4 of a search under a compiled mask: the queries prepared and the mirror up to date, then -- behind the mask's event,
+// on the inner flat index's stream -- g->d_mask = the mask ANDed with the graph's presence (d_row_of[id] != 0xffffffff is "the
+// graph holds id") over *bits = min(the mask's bits, mirror ids) bits, and *eligible = its set bits (8 bytes read back, one
+// synchronisation: what the flat sparse-filter route pays to choose its route).
+// pairs_begin comes first because the route is not known before the count is: the walk and the "nothing eligible" early-out use
+// the prepared queries (search_device is told not to prepare them again).  The filter scan does not -- the inner flat search
+// uploads the queries itself, so there they go up twice -- and a host traversal prepares them again in search_host; both are one
+// small copy and one small kernel against a scan or a traversal, not a bug.
+int present_mask_device(vdb_hnsw_index* g, const vdb_meta_mask* cm, const float* queries, size_t nq, size_t dim, size_t* bits, uint64_t* eligible) {
+    int rc;
+    if ((rc = vdb_internal::pairs_begin(g->flat, queries, nq, dim))) return rc;
+    vdb_internal::DeviceView dv;
+    if ((rc = vdb_internal::device_view(g->flat, &dv))) return rc;
+    hipStream_t s = (hipStream_t)dv.stream;
+    if ((rc = upload_mirror(g, s))) return rc;
+    HN_TRY(hipStreamWaitEvent(s, cm->done, 0));
+    const uint32_t nb = (uint32_t)std::min<size_t>(cm->bits, g->mirror_ids);
+    if ((rc = ensure_mask(g, std::max<size_t>(((size_t)nb + 63) / 64, 1)))) return rc;
+    if (!g->d_eligible) HN_TRY(hipMalloc((void**)&g->d_eligible, 8));
+    HN_TRY(hipMemsetAsync(g->d_eligible, 0, 8, s));
+    vdb::HnswPresentMaskParams pp{cm->d_words, (uint64_t)((cm->bits + 63) / 64), g->d_row_of, g->mirror_ids, nb, g->d_mask, g->d_eligible};
+    vdb::launch_hnsw_present_mask(pp, s);
+    HN_TRY(hipGetLastError());
+    unsigned long long cnt = 0;
+    HN_TRY(hipMemcpyAsync(&cnt, g->d_eligible, 8, hipMemcpyDeviceToHost, s));
+    HN_TRY(hipStreamSynchronize(s));
+    *bits = nb; *eligible = cnt;
+    return VDB_OK;
+}
+
+int compiled_mask_refused(const vdb_hnsw_index* g, const vdb_meta_mask* cm) {
+    if (!cm) return vdb_internal::set_error(VDB_ERR_INVALID_ARGUMENT, "null mask");
+    if (cm->device != g->device) {
+        char msg[128];
+        snprintf(msg, sizeof(msg), "the compiled mask lives on device %d, the index on device %d", cm->device, g->device);
+        return vdb_internal::set_error(VDB_ERR_INVALID_ARGUMENT, msg);
+    }
+    return VDB_OK;
+}
+
+// vdb_hnsw_search_batch_masked (the mask in host memory: id_mask / mask_bits, or none) and vdb_hnsw_search_batch_filtered (cm: a
+// compiled mask in HBM) -- one body, the two differ only in where the mask comes from.
+// Under cm the mask every route reads is NOT the compiled one but the compiled one ANDed with the graph's presence
+// (present_mask_device).  That changes no result: the device walk and the host traversal test eligibility only of nodes they
+// reach through the graph -- the entry point and listed neighbours that passed the presence check -- and those are present, so
+// the bit they read is the raw mask's; bits beyond the node ids name no node.  The filter scan ANDs the presence in on the
+// host path too (present_mask_within), and "nothing is eligible" is the same question asked of the count.
+int search_batch_common(vdb_hnsw_index* g, const float* queries, size_t nq, size_t dim, size_t k, size_t ef, const uint64_t* id_mask,
+                        size_t mask_bits, const vdb_meta_mask* cm, uint64_t* out_ids, float* out_dists, size_t* out_counts) {
+    std::lock_guard<std::mutex> lk(g->mu);
+    for (size_t b = 0; b < nq; ++b) out_counts[b] = 0;
+    g->stats[2] = g->stats[3] = 0;
+    if (nq == 0 || !g->has_ep) return VDB_OK;                     // graph.rs:392-395: empty graph -> Ok(vec![])
+    if (dim != g->dim) return vdb_internal::set_dim_error(dim, g->dim);   // distance.rs:21-26 on the first evaluation
+    const size_t ef_actual = std::max(ef ? ef : g->ef_search, k);
+    int rc;
+    uint64_t eligible = 0;                                        // cm: present nodes the mask admits (mask_bits: the bits of g->d_mask)
+    if (cm && (rc = present_mask_device(g, cm, queries, nq, dim, &mask_bits, &eligible))) return rc;
+    // the host traversal reads its mask from host memory: under cm the words of g->d_mask come back once, when it first runs
+    std::vector<uint64_t> hmask;
+    auto host_mask = [&]() -> int {
+        if (!cm || id_mask) return VDB_OK;
+        const size_t words = (mask_bits + 63) / 64;
+        hmask.assign(std::max<size_t>(words, 1), 0ull);
+        if (words) {
+            vdb_internal::DeviceView dv;
+            int rc2;
+            if ((rc2 = vdb_internal::device_view(g->flat, &dv))) return rc2;
+            HN_TRY(hipMemcpyAsync(hmask.data(), g->d_mask, words * 8, hipMemcpyDeviceToHost, (hipStream_t)dv.stream));
+            HN_TRY(hipStreamSynchronize((hipStream_t)dv.stream));
+        }
+        id_mask = hmask.data();
+        return VDB_OK;
+    };
+    if (cm ? eligible == 0 : (id_mask && !mask_admits_a_node(g, id_mask, mask_bits))) {
+        // nothing is eligible: the walk would traverse the whole reachable graph to return nothing.  It is skipped; the errors it
+        // would raise stay -- the dimension check above, and a zero-norm query under Cosine (its first distance, to the entry point)
+        if (!cm && (rc = vdb_internal::pairs_begin(g->flat, queries, nq, dim))) return rc;
+        if (g->metric == vdb::COSINE) {
+            vdb_internal::DeviceView dv;
+            if ((rc = vdb_internal::device_view(g->flat, &dv))) return rc;
+            std::vector<float> qn(nq);
+            HN_TRY(hipMemcpyAsync(qn.data(), dv.qnorm, nq * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)dv.stream));
+            HN_TRY(hipStreamSynchronize((hipStream_t)dv.stream));
+            for (float x : qn) if (x == 0.0f) return zero_norm_error();
+        }
+        return VDB_OK;
+    }
+    if ((id_mask || cm) && g->filter_scan && k > 0 && k <= 2048) {
+        // vdb_hnsw_set_filter_scan: a mask this selective is answered by an exact scan of its eligible rows in the inner flat
+        // index (the sparse-filter route of vdb_flat.h) -- the walk would overflow its heap and be re-run on the host
+        const size_t limit = std::min<size_t>(g->filter_scan, 131072);
+        std::vector<uint64_t> pm;
+        if (cm ? eligible <= limit : present_mask_within(g, id_mask, mask_bits, limit, pm)) {
+            if ((rc = vdb_flat_set_sparse_filter(g->flat, 1))) return rc;
+            if (cm) rc = vdb_internal::search_batch_device_mask(g->flat, queries, nq, dim, k, g->d_mask, mask_bits, out_ids, out_dists, out_counts);
+            else rc = vdb_flat_search_batch(g->flat, queries, nq, dim, nullptr, k, pm.data(), pm.size() * 64, k, out_ids, out_dists, out_counts);
+            (void)vdb_flat_set_sparse_filter(g->flat, 0);
+            g->stats[1]++;
+            return rc;
+        }
+    }
+    const bool on_device = !g->host_only && k > 0 && g->nodes.size() < 0xffffffffull &&
+                           vdb::hnsw_search_supported((uint32_t)g->dim, (uint32_t)std::min<size_t>(ef_actual, 0xffffffu), (uint32_t)std::min<size_t>(k, 0xffffffu),
+                                                      (uint32_t)std::max(g->m_max0, g->m) + 1);
+    if (!on_device) {
+        if ((rc = host_mask())) return rc;
+        return search_host(g, queries, nq, dim, k, ef, id_mask, mask_bits, out_ids, out_dists, out_counts);
+    }
+    std::vector<uint32_t> redo;
+    if ((rc = search_device(g, queries, nq, dim, k, ef_actual, id_mask, mask_bits, cm != nullptr, out_ids, out_dists, out_counts, redo))) return rc;
+    if (!redo.empty()) {                                            // the walks that did not fit the kernel's LDS structures
+        g->host_redone += redo.size();
+        std::vector<float> q2(redo.size() * dim);
+        for (size_t j = 0; j < redo.size(); ++j) memcpy(q2.data() + j * dim, queries + (size_t)redo[j] * dim, dim * sizeof(float));
+        std::vector<uint64_t> i2(redo.size() * k);
+        std::vector<float> d2(redo.size() * k);
+        std::vector<size_t> c2(redo.size());
+        if ((rc = host_mask())) return rc;
+        if ((rc = search_host(g, q2.data(), redo.size(), dim, k, ef, id_mask, mask_bits, i2.data(), d2.data(), c2.data()))) return rc;
+        for (size_t j = 0; j < redo.size(); ++j) {
+            memcpy(out_ids + (size_t)redo[j] * k, i2.data() + j * k, k * 8);
+            memcpy(out_dists + (size_t)redo[j] * k, d2.data() + j * k, k * 4);
+            out_counts[redo[j]] = c2[j];
+        }
+    }
+    return VDB_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1272,61 +1411,40 @@ int vdb_hnsw_search_batch_masked(vdb_hnsw_index* g, const float* queries, size_t
     return guarded([&]() -> int {
     if (!g || (nq && (!queries || !out_counts || (k && (!out_ids || !out_dists)))))
         return vdb_internal::set_error(VDB_ERR_INVALID_ARGUMENT, "null argument");
-    std::lock_guard<std::mutex> lk(g->mu);
-    for (size_t b = 0; b < nq; ++b) out_counts[b] = 0;
-    g->stats[2] = g->stats[3] = 0;
-    if (nq == 0 || !g->has_ep) return VDB_OK;                     // graph.rs:392-395: empty graph -> Ok(vec![])
-    if (dim != g->dim) return vdb_internal::set_dim_error(dim, g->dim);   // distance.rs:21-26 on the first evaluation
-    const size_t ef_actual = std::max(ef ? ef : g->ef_search, k);
-    if (id_mask && !mask_admits_a_node(g, id_mask, mask_bits)) {
-        // nothing is eligible: the walk would traverse the whole reachable graph to return nothing.  It is skipped; the errors it
-        // would raise stay -- the dimension check above, and a zero-norm query under Cosine (its first distance, to the entry point)
-        int rc;
-        if ((rc = vdb_internal::pairs_begin(g->flat, queries, nq, dim))) return rc;
-        if (g->metric == vdb::COSINE) {
-            vdb_internal::DeviceView dv;
-            if ((rc = vdb_internal::device_view(g->flat, &dv))) return rc;
-            std::vector<float> qn(nq);
-            HN_TRY(hipMemcpyAsync(qn.data(), dv.qnorm, nq * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)dv.stream));
-            HN_TRY(hipStreamSynchronize((hipStream_t)dv.stream));
-            for (float x : qn) if (x == 0.0f) return zero_norm_error();
-        }
-        return VDB_OK;
-    }
-    if (id_mask && g->filter_scan && k > 0 && k <= 2048) {
-        // vdb_hnsw_set_filter_scan: a mask this selective is answered by an exact scan of its eligible rows in the inner flat
-        // index (the sparse-filter route of vdb_flat.h) -- the walk would overflow its heap and be re-run on the host
-        std::vector<uint64_t> pm;
-        if (present_mask_within(g, id_mask, mask_bits, std::min<size_t>(g->filter_scan, 131072), pm)) {
-            int rc;
-            if ((rc = vdb_flat_set_sparse_filter(g->flat, 1))) return rc;
-            rc = vdb_flat_search_batch(g->flat, queries, nq, dim, nullptr, k, pm.data(), pm.size() * 64, k, out_ids, out_dists, out_counts);
-            (void)vdb_flat_set_sparse_filter(g->flat, 0);
-            g->stats[1]++;
-            return rc;
-        }
-    }
-    const bool on_device = !g->host_only && k > 0 && g->nodes.size() < 0xffffffffull &&
-                           vdb::hnsw_search_supported((uint32_t)g->dim, (uint32_t)std::min<size_t>(ef_actual, 0xffffffu), (uint32_t)std::min<size_t>(k, 0xffffffu),
-                                                      (uint32_t)std::max(g->m_max0, g->m) + 1);
-    if (!on_device) return search_host(g, queries, nq, dim, k, ef, id_mask, mask_bits, out_ids, out_dists, out_counts);
+    return search_batch_common(g, queries, nq, dim, k, ef, id_mask, mask_bits, nullptr, out_ids, out_dists, out_counts);
+    });
+}
+
+int vdb_hnsw_search_batch_filtered(vdb_hnsw_index* g, const float* queries, size_t nq, size_t dim, size_t k, size_t ef,
+                                   const vdb_meta_mask* mask, uint64_t* out_ids, float* out_dists, size_t* out_counts) {
+    return guarded([&]() -> int {
+    if (!g || (nq && (!queries || !out_counts || (k && (!out_ids || !out_dists)))))
+        return vdb_internal::set_error(VDB_ERR_INVALID_ARGUMENT, "null argument");
     int rc;
-    std::vector<uint32_t> redo;
-    if ((rc = search_device(g, queries, nq, dim, k, ef_actual, id_mask, mask_bits, out_ids, out_dists, out_counts, redo))) return rc;
-    if (!redo.empty()) {                                            // the walks that did not fit the kernel's LDS structures
-        g->host_redone += redo.size();
-        std::vector<float> q2(redo.size() * dim);
-        for (size_t j = 0; j < redo.size(); ++j) memcpy(q2.data() + j * dim, queries + (size_t)redo[j] * dim, dim * sizeof(float));
-        std::vector<uint64_t> i2(redo.size() * k);
-        std::vector<float> d2(redo.size() * k);
-        std::vector<size_t> c2(redo.size());
-        if ((rc = search_host(g, q2.data(), redo.size(), dim, k, ef, id_mask, mask_bits, i2.data(), d2.data(), c2.data()))) return rc;
-        for (size_t j = 0; j < redo.size(); ++j) {
-            memcpy(out_ids + (size_t)redo[j] * k, i2.data() + j * k, k * 8);
-            memcpy(out_dists + (size_t)redo[j] * k, d2.data() + j * k, k * 4);
-            out_counts[redo[j]] = c2[j];
-        }
+    if ((rc = compiled_mask_refused(g, mask))) return rc;
+    return search_batch_common(g, queries, nq, dim, k, ef, nullptr, 0, mask, out_ids, out_dists, out_counts);
+    });
+}
+
+int vdb_hnsw_debug_present_mask(vdb_hnsw_index* g, const vdb_meta_mask* mask, uint64_t* out_words, size_t cap_words, size_t* out_nwords,
+                                uint64_t* out_count) {
+    return guarded([&]() -> int {
+    if (!g || !out_nwords || !out_count || (cap_words && !out_words)) return vdb_internal::set_error(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    int rc;
+    if ((rc = compiled_mask_refused(g, mask))) return rc;
+    std::lock_guard<std::mutex> lk(g->mu);
+    size_t bits = 0;
+    uint64_t eligible = 0;
+    if ((rc = present_mask_device(g, mask, nullptr, 0, g->dim, &bits, &eligible))) return rc;
+    const size_t words = (bits + 63) / 64;
+    if (words > cap_words) return vdb_internal::set_error(VDB_ERR_INVALID_ARGUMENT, "out_words is too small for the mask");
+    if (words) {
+        vdb_internal::DeviceView dv;
+        if ((rc = vdb_internal::device_view(g->flat, &dv))) return rc;
+        HN_TRY(hipMemcpyAsync(out_words, g->d_mask, words * 8, hipMemcpyDeviceToHost, (hipStream_t)dv.stream));
+        HN_TRY(hipStreamSynchronize((hipStream_t)dv.stream));
     }
+    *out_nwords = words; *out_count = eligible;
     return VDB_OK;
     });
 }

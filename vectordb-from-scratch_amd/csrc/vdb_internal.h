@@ -27,6 +27,10 @@ uint32_t n_rows(vdb_flat_index* ix);
 // device pointers of the row store and of the query block prepared by pairs_begin (valid until the next call on the handle)
 struct DeviceView { const float* rows; uint32_t ld, dim; const float* nd; const float* qp; const float* qnorm; int metric; void* stream; uint32_t* status; };
 int device_view(vdb_flat_index* ix, DeviceView* out);
+// vdb_flat_search_batch (one k for the batch, kstride = k) under an id mask that is ALREADY on the device: mask_bits bits at
+// d_mask, written on the handle's own stream (DeviceView::stream), so nothing is uploaded and nothing waited for
+int search_batch_device_mask(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, size_t k, const uint64_t* d_mask,
+                             size_t mask_bits, uint64_t* out_ids, float* out_dists, size_t* out_counts);
 // thread-local last-error state shared by every entry point of the library (vdb_last_error)
 int set_error(int code, const char* msg);
 int zero_vector_error();   // the reference's InvalidVector for a zero-norm Cosine operand

@@ -37,6 +37,7 @@ class GpuHnswIndex(Index):
                                      self.params.ef_search, int(seed), int(device), ctypes.byref(self._h))
         if rc:
             _raise(rc)
+        self._device = int(device)
         self._vectors = {}
 
     @classmethod
@@ -85,17 +86,28 @@ class GpuHnswIndex(Index):
         ids, ds, cnt = self.search_batch_arrays(q.data.reshape(1, -1), k, ef)
         return [(int(ids[0, i]), float(ds[0, i])) for i in range(int(cnt[0]))]
 
-    def search_batch_arrays(self, queries, k, ef=0, id_mask=None, mask_bits=0):
+    def search_batch_arrays(self, queries, k, ef=0, id_mask=None, mask_bits=0, compiled_mask=None):
         """queries [nq, dim] f32 -> (ids u64 [nq, k], dists f32 [nq, k], counts [nq]); every query of the batch walks
         the graph in lockstep, one GPU launch per traversal round for all their candidate lists.
         id_mask / mask_bits: the pre-filter of GpuFlatIndex (bit i of the uint64 words = id i eligible, ids >= mask_bits are
-        not): only eligible ids are results, the walk still goes through the others (vdb_hnsw_search_batch_masked)."""
+        not): only eligible ids are results, the walk still goes through the others (vdb_hnsw_search_batch_masked).
+        compiled_mask: a CompiledMask (MetaTable.compile) on the index's device instead of id_mask / mask_bits; results are
+        identical, nothing is uploaded (vdb_hnsw_search_batch_filtered)."""
+        if compiled_mask is not None and id_mask is not None:
+            raise ValueError("pass id_mask or compiled_mask, not both")
         qs = np.ascontiguousarray(queries, dtype=np.float32)
         nq, dim = qs.shape
         kk = max(int(k), 1)
         ids = np.zeros((nq, kk), dtype=np.uint64)
         ds = np.zeros((nq, kk), dtype=np.float32)
         cnt = np.zeros(nq, dtype=np.uintp)
+        cntp = cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t))
+        if compiled_mask is not None:
+            rc = self._L.vdb_hnsw_search_batch_filtered(self._h, _fp(qs), nq, dim, int(k), int(ef), compiled_mask.handle,
+                                                        _u64p(ids), _fp(ds), cntp)
+            if rc:
+                _raise(rc)
+            return ids, ds, cnt
         mask_ptr = None
         if id_mask is not None:
             m = np.ascontiguousarray(id_mask, dtype=np.uint64)
@@ -103,17 +115,19 @@ class GpuHnswIndex(Index):
                 raise ValueError(f"id_mask holds {m.size * 64} bits, mask_bits is {int(mask_bits)}")
             mask_ptr = _u64p(m)
         rc = self._L.vdb_hnsw_search_batch_masked(self._h, _fp(qs), nq, dim, int(k), int(ef), mask_ptr, int(mask_bits),
-                                                  _u64p(ids), _fp(ds), cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)))
+                                                  _u64p(ids), _fp(ds), cntp)
         if rc:
             _raise(rc)
         return ids, ds, cnt
 
-    def search_batch(self, queries, id_mask=None, mask_bits=0):
+    def search_batch(self, queries, id_mask=None, mask_bits=0, compiled_mask=None):
+        if compiled_mask is not None and id_mask is not None:
+            raise ValueError("pass id_mask or compiled_mask, not both")
         if not queries:
             return []
         qs = np.stack([(q.data if isinstance(q, Vector) else np.asarray(q, np.float32)) for q, _ in queries])
         kmax = max(k for _, k in queries)
-        ids, ds, cnt = self.search_batch_arrays(qs, kmax, 50, id_mask=id_mask, mask_bits=mask_bits)
+        ids, ds, cnt = self.search_batch_arrays(qs, kmax, 50, id_mask=id_mask, mask_bits=mask_bits, compiled_mask=compiled_mask)
         return [[(int(ids[b, i]), float(ds[b, i])) for i in range(min(int(cnt[b]), k))] for b, (_, k) in enumerate(queries)]
 
     def get_vector(self, id):                                    # mod.rs:65-67
@@ -163,6 +177,17 @@ class GpuHnswIndex(Index):
         rc = self._L.vdb_hnsw_set_filter_scan(self._h, max_eligible)
         if rc:
             _raise(rc)
+
+    def debug_present_mask(self, cm):
+        """Test hook: the compiled mask ANDed with the graph's presence, as a filtered search computes it on the device:
+        (uint64 words over min(cm.bits, node ids) bits, number of set bits).  No search runs."""
+        handle = cm.handle                               # (raises for a released mask and for one whose table was closed)
+        words = np.zeros(cm.bits // 64 + 1, dtype=np.uint64)
+        n, count = ctypes.c_size_t(0), ctypes.c_uint64(0)
+        rc = self._L.vdb_hnsw_debug_present_mask(self._h, handle, _u64p(words), words.size, ctypes.byref(n), ctypes.byref(count))
+        if rc:
+            _raise(rc)
+        return words[:n.value].copy(), int(count.value)
 
     def stats(self):
         out = (ctypes.c_uint64 * 6)()

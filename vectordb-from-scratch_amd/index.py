@@ -78,6 +78,8 @@ class CompiledMask:
     def handle(self):
         if not self._m:
             raise ValueError("the compiled mask was released")
+        if not self._table._t:                           # (a closed table has freed every mask it handed out)
+            raise ValueError("the compiled mask's table was closed")
         return self._m
 
     @property

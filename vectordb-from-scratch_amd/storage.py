@@ -7,6 +7,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .error import DimensionMismatch, VectorNotFound
+from .hnsw import GpuHnswIndex
 from .index import GpuFlatIndex, Index, MetaTable
 from .vector import DistanceMetric, Vector
 
@@ -454,8 +455,10 @@ class VectorStore:
         """on: keep the metadata columns and the presence bitmap resident on the index's GPU, forward every later insert /
         upsert / delete / bulk attach to them, and let search_batch_prefiltered compile its filter there (one kernel launch,
         nothing uploaded but the filter expression) instead of in numpy.  off (the default): free them.  Results are identical
-        either way.  A store whose index is not a GpuFlatIndex ignores the setting (an HNSW index consumes its mask on the host)."""
-        if not isinstance(self._index, GpuFlatIndex):
+        either way.  A GpuFlatIndex searches under the compiled mask where it is; a GpuHnswIndex ANDs it with the graph's presence
+        on the device and walks (or, with set_sparse_filter, scans) under that (vdb_hnsw_search_batch_filtered).  A store over any
+        other index ignores the setting."""
+        if not isinstance(self._index, (GpuFlatIndex, GpuHnswIndex)):
             return
         if not on:
             table, self._table = self._table, None
