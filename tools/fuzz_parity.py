@@ -21,8 +21,10 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from bench import load_package  # noqa: E402
 import oracle  # noqa: E402
+from value_families import fuzz_rows  # noqa: E402
 
 
 def make_data(rng, n, d, kind):
@@ -43,6 +45,8 @@ def make_data(rng, n, d, kind):
     if kind == "scales":                          # norms spread over two orders of magnitude
         x = rng.standard_normal((n, d)).astype(np.float32)
         return x * np.exp(rng.uniform(-2.3, 2.3, (n, 1))).astype(np.float32)
+    if kind in ("overflow", "subnormal"):         # tests/value_families.py: squares and sums that overflow; the bottom of f32
+        return fuzz_rows(rng, n, d, kind)
     raise ValueError(kind)
 
 
@@ -58,7 +62,7 @@ def main():
     vdb = load_package()
     vdb.build()
     rng = np.random.default_rng(a.seed)
-    kinds = ["uniform", "gauss", "unit", "clustered", "dups", "scales"]
+    kinds = ["uniform", "gauss", "unit", "clustered", "dups", "scales", "overflow", "subnormal"]
     t0 = time.time()
     tiers = {"screen": 0, "rethr": 0, "f32q": 0, "exact": 0, "ovf": 0}
     large = {"cases": 0, "queries": 0, "screen": 0, "uncertified": 0, "rethr": 0, "exact": 0, "ovf": 0}   # 112 < k <= 1024 only
@@ -76,7 +80,7 @@ def main():
         rows = make_data(rng, n, d, kind)
         if metric == 1:
             rows[np.linalg.norm(rows, axis=1) == 0] += 1.0      # a zero-norm row fails every Cosine search (tested elsewhere)
-        queries = make_data(rng, nq, d, kind if kind not in ("clustered", "dups") else "gauss")
+        queries = make_data(rng, nq, d, kind if kind not in ("clustered", "dups", "overflow") else "gauss")   # (overflow on both sides: inf / inf)
         if kind in ("clustered", "dups") and nq > 1:
             queries[: nq // 2] = rows[rng.integers(0, n, nq // 2)] + (1e-3 * rng.standard_normal((nq // 2, d))).astype(np.float32)
         if metric == 1:

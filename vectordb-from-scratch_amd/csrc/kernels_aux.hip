@@ -1923,6 +1923,9 @@ void launch_write_code(const uint32_t* flags, int32_t* code, hipStream_t s) {
 constexpr uint32_t MERGE_MAX = 2048;
 // part p's arrays start at ids + p*ids_stride, dists + p*dists_stride, counts + p*counts_stride (element units),
 // so both the plain [nparts][nq][k] layout and the packed all-gather buffer of sharded.py can be merged in place
+// The merge orders as the reference compares (partial_cmp: -0.0 == +0.0, so between the two the id decides), while
+// f32_to_ordered puts -0.0 one step before +0.0: compare with the sign of a zero taken off, carry the bits as they are.
+__device__ __forceinline__ uint32_t merge_zero_sign_off(uint32_t od) { return od == 0x7fffffffu ? 0x80000000u : od; }
 __global__ __launch_bounds__(256) void merge_parts_kernel(const uint64_t* ids, const float* dists,
                                                           const uint32_t* counts, size_t ids_stride,
                                                           size_t dists_stride, size_t counts_stride,
@@ -1969,7 +1972,8 @@ __global__ __launch_bounds__(256) void merge_parts_kernel(const uint64_t* ids, c
                 bool up = ((lo & size) == 0);
                 uint32_t da = sD[lo], db = sD[hi];
                 uint64_t ia = sI[lo], ib = sI[hi];
-                bool gt = da > db || (da == db && ia > ib);
+                const uint32_t ca = merge_zero_sign_off(da), cb = merge_zero_sign_off(db);
+                bool gt = ca > cb || (ca == cb && ia > ib);
                 if (gt == up) { sD[lo] = db; sD[hi] = da; sI[lo] = ib; sI[hi] = ia; }
             }
             __syncthreads();
@@ -1989,7 +1993,7 @@ __global__ __launch_bounds__(256) void merge_parts_kernel(const uint64_t* ids, c
 // index is lower).  The places are distinct, the element placed below k writes itself there, and the output is the one the
 // bitonic sort gives: equal pairs are interchangeable.  One thread per (part, slot): blocks_per_q workgroups of 256 per query.
 __device__ __forceinline__ bool merge_before(uint32_t da, uint64_t ia, uint32_t db, uint64_t ib) {
-    return da < db || (da == db && ia < ib);
+    return da < db || (da == db && ia < ib);                      // (both already through merge_zero_sign_off)
 }
 __global__ __launch_bounds__(256) void merge_rank_kernel(const uint64_t* ids, const float* dists, const uint32_t* counts,
                                                          size_t ids_stride, size_t dists_stride, size_t counts_stride,
@@ -2019,7 +2023,7 @@ __global__ __launch_bounds__(256) void merge_rank_kernel(const uint64_t* ids, co
     if (cnt > k) cnt = k;
     if (j >= cnt) return;
     const float dist = dists[part * dists_stride + (size_t)q * k + j];
-    const uint32_t od = f32_to_ordered(dist);
+    const uint32_t od = merge_zero_sign_off(f32_to_ordered(dist));
     const uint64_t id = ids[part * ids_stride + (size_t)q * k + j];
     uint64_t rank = j;
     for (uint32_t o = 0; o < nparts && rank < k; ++o) {
@@ -2032,14 +2036,14 @@ __global__ __launch_bounds__(256) void merge_rank_kernel(const uint64_t* ids, co
         uint32_t lo = 0, hi = c;
         while (lo < hi) {
             const uint32_t mid = (lo + hi) >> 1;
-            const uint32_t dm = f32_to_ordered(odp[mid]);
+            const uint32_t dm = merge_zero_sign_off(f32_to_ordered(odp[mid]));
             const uint64_t im = oi[mid];
             const bool before = merge_before(dm, im, od, id) || (o < part && dm == od && im == id);
             if (before) lo = mid + 1; else hi = mid;
         }
         rank += lo;
     }
-    if (rank < k) { out_ids[(size_t)q * k + rank] = id; out_dists[(size_t)q * k + rank] = ordered_to_f32(od); }
+    if (rank < k) { out_ids[(size_t)q * k + rank] = id; out_dists[(size_t)q * k + rank] = dist; }
 }
 static void launch_merge(const uint64_t* ids, const float* dists, const uint32_t* counts, size_t ids_stride, size_t dists_stride,
                          size_t counts_stride, const uint32_t* status, size_t status_stride, uint32_t nparts, uint32_t nq, uint32_t k,
