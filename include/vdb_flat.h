@@ -80,8 +80,9 @@ void vdb_flat_destroy(vdb_flat_index *h);
  * two ranks on one device).
  *
  * Not available on a sharded handle: the two-half / ticket forms of the device search (begin/finish, submit/wait),
- * vdb_flat_distances_batch, the vdb_flat_debug_* probes and vdb_flat_search_batch_sharded (that one is the
- * process-per-GPU form of the same exchange, vdb_shard.h); they return VDB_ERR_INVALID_ARGUMENT.
+ * vdb_flat_distances_batch, the range searches (vdb_flat_range_search_batch, vdb_flat_range_search_batch_device), the
+ * vdb_flat_debug_* probes and vdb_flat_search_batch_sharded (that one is the process-per-GPU form of the same exchange,
+ * vdb_shard.h); they return VDB_ERR_INVALID_ARGUMENT.
  */
 int vdb_flat_create_sharded(int metric, const int *devices, size_t n_devices, vdb_flat_index **out);
 /* number of shards of the handle (1 for a plain vdb_flat_create handle) */
@@ -350,6 +351,46 @@ int vdb_flat_debug_eligible_rows(vdb_flat_index *h, const uint64_t *id_mask, siz
                                  size_t *count);
 size_t vdb_flat_debug_sparse_tile_rows(void);
 size_t vdb_flat_debug_sparse_tile_queries(void);
+
+/*
+ * EXACT RANGE SEARCH: every neighbour within a radius (no reference counterpart: Index::search, flat_index.rs:52-65, only
+ * answers "the k nearest").  For query q and radius r the result is the set of eligible rows (live, admitted by the optional id
+ * mask) whose reference distance d -- DistanceMetric::distance in the reference's own f32 operation order, distance.rs:20-73 --
+ * satisfies the IEEE comparison d <= r: a row at exactly r is in, -0.0 equals +0.0.  Results are ascending by (distance,
+ * unsigned id); the first min(total, max_results) of that order are written and `total`, the number of rows within the radius,
+ * is reported whether they fit or not.  This is the prefix with d <= r of what vdb_flat_search_batch returns for k = len, bit
+ * for bit, on every route:
+ *  - large indexes (screening tier on, at least 65536 rows): the radius becomes a score cut -- the inverse of the screening
+ *    tier's certificate: every row scoring above the cut is PROVEN to lie strictly beyond r, so rows at the radius score at or
+ *    below it -- the HBM-bound bf16 filter pass runs once under the cuts, and EVERY key that passes (up to 2048 per query) is
+ *    evaluated exactly.  No sample pass, no certificate to wait for: the list is complete by construction;
+ *  - everything else (small indexes, vdb_flat_set_screen(0), a query with more than 2048 keys under its cut, an overflowed
+ *    pool, a radius without a finite cut: +-inf, >= 2 under Cosine, a tiny query norm): an exact scan that keeps the rows with
+ *    d <= r, eight queries per pass over the rows;
+ *  - more than 32768 rows within the radius: the full exact scan of that query for its first max_results.
+ * radii: one radius per query, or NULL to use `radius` for all.  out_ids / out_dists: [nq][max_results], unused slots are not
+ * written by the host form (the device form pads them with id ~0 and a NaN distance).  out_counts[b] = entries written,
+ * out_totals[b] (may be NULL) = rows within the radius.
+ * Errors, in the order of the searches: an empty index gives counts and totals 0 before any check; dimension mismatch; under
+ * Cosine one live zero-norm row fails the call, masked or not, and a zero-norm query is VDB_ERR_INVALID_VECTOR; a NaN distance
+ * at an eligible row is VDB_ERR_NAN.  A NaN radius, max_results == 0 or max_results > 2048 is VDB_ERR_INVALID_ARGUMENT before
+ * any device work.  Locking, workspaces and tickets as vdb_flat_search_batch / _device: concurrent callers are serialised by
+ * the handle, the host-pointer form is refused while a submitted search is in flight, staged adds are flushed first.
+ * Not available on a sharded handle (totals across shards need another exchange layout).
+ */
+int vdb_flat_range_search_batch(vdb_flat_index *h, const float *queries, size_t nq, size_t dim,
+                                const float *radii, float radius, const uint64_t *id_mask, size_t mask_bits,
+                                size_t max_results, uint64_t *out_ids, float *out_dists,
+                                size_t *out_counts, uint64_t *out_totals);
+/* queries, radii (required), mask and outputs in this device's HBM; d_out_counts uint32[nq], d_out_totals uint64[nq] or NULL */
+int vdb_flat_range_search_batch_device(vdb_flat_index *h, const float *d_queries, size_t nq, size_t dim,
+                                       const float *d_radii, const uint64_t *d_id_mask, size_t mask_bits,
+                                       size_t max_results, uint64_t *d_out_ids, float *d_out_dists,
+                                       uint32_t *d_out_counts, uint64_t *d_out_totals, void *stream);
+/* counters of the last range search: [0] queries answered by the screened route  [1] by the exact range scan
+ * [2] by the dense fallback (more than 32768 rows within the radius)  [3] rows streamed by filter passes
+ * [4] keys re-ranked  [5] queries whose pool or select overflowed  [6] queries without a finite score cut  [7] 0 */
+int vdb_flat_range_stats(const vdb_flat_index *h, uint64_t out[8]);
 
 /*
  * METADATA FILTERS COMPILED ON THE DEVICE (no reference counterpart: the reference evaluates MetadataFilter::matches row by row

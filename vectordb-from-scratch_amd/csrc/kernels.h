@@ -367,6 +367,52 @@ struct ExactMultiParams {
 };
 void launch_exact_multi(const ExactMultiParams& p, hipStream_t s);
 
+// ---------------------------------------------------------------- exact range search (kernels_range.hip)
+// thr[q] = score_cut(radii[q]) from the constants of the re-rank's certificate (cert: metric, ld, qnorm, qerr, c_acc, eps_coef,
+// nd2max_bits, lb_scores -- what rerank_kernel hands to score_cut); -inf for an empty answer (r < 0 under Euclid / Cosine) and
+// for a query without a finite cut, which gets nocut[q] = 1
+struct RangeCutParams {
+    RerankParams cert;
+    const float* radii; uint32_t nq;
+    float* thr; uint32_t* nocut;
+};
+void launch_range_cut(const RangeCutParams& p, hipStream_t s);
+// the tail of the screened route: every key of cand[q * cand_stride ..] (cand_cnt[q] of them, any order) evaluated exactly, the
+// rows with d <= radii[q] sorted by (distance, id); out_*[q * max_results ..] padded with (~0, NaN)
+struct RangeRerankParams {
+    const float* rows; uint32_t ld; uint32_t dim; uint32_t n_rows;
+    const float* qp; const float* qnorm; const float* nd;
+    const uint64_t* row_ids; const uint32_t* rowmask;  // rowmask may be null
+    const uint64_t* cand; uint32_t cand_stride; const uint32_t* cand_cnt;   // cand_stride <= 2048
+    const float* radii; int metric; uint32_t max_results;
+    uint64_t* out_ids; float* out_dists; uint32_t* out_counts; uint64_t* out_totals;   // out_totals may be null
+    uint32_t* complete;                                // [nq]: 0 = a NaN-score key was in the list (the exact range scan answers)
+    uint32_t* n_keys;                                  // [nq]: keys evaluated
+    uint32_t* status;                                  // ST_NAN
+    uint32_t lds_row_stride, lds_chunk;                // filled by launch_range_rerank
+};
+void launch_range_rerank(const RangeRerankParams& p, uint32_t nq, hipStream_t s);
+// The exact range scan: ExactMultiParams with the bound of query j taken from radii[qidx[j]] (d <= radius is kept)
+struct RangeScanParams {
+    const float* rows; uint32_t ld; uint32_t dim; uint32_t n_rows;
+    const float* qp; const float* qnorm;               // padded query block and norms of the whole batch
+    const float* nd; const uint32_t* rowmask; const uint32_t* idrank;
+    int metric;
+    uint32_t nqf; uint32_t qidx[8];
+    const float* radii;                                // [batch]
+    uint64_t* keys; uint32_t cap; uint32_t* cnt;       // keys[j*cap + slot], cnt[j] = ALL survivors (may exceed cap)
+    uint32_t* status;
+};
+void launch_range_scan(const RangeScanParams& p, hipStream_t s);
+// its sorted survivors as results: query j reads keys + j*key_stride, cnt[j] (selected) and survivors[j] (the total)
+struct RangeEmitParams {
+    const uint64_t* keys; uint32_t key_stride; const uint32_t* cnt; const uint32_t* survivors;
+    const uint32_t* rank2row; const uint64_t* row_ids; uint32_t n_rows;
+    uint64_t* out_ids; float* out_dists; uint32_t* out_counts; uint64_t* out_totals; uint32_t max_results;
+    uint32_t nqf; uint32_t qidx[8];
+};
+void launch_range_emit(const RangeEmitParams& p, hipStream_t s);
+
 // ---------------------------------------------------------------- sparse-filter route (kernels_sparse.hip)
 // The ascending list of the rows whose bit is set in a search's row mask (bits at or above n_rows never count), in two steps
 // with the host in between: launch_sparse_count leaves E in *total (block_cnt / block_off: sparse_list_blocks(n_rows) words

@@ -671,6 +671,84 @@ int vdb_flat_search(vdb_flat_index* ix, const float* query, size_t dim, size_t k
 }
 
 // the merge kernels index keys with 32 bits and launch up to nq * nparts*k / 256 workgroups
+// ---- exact range search (vdb_search.cpp range_search_device)
+int vdb_flat_range_search_batch_device(vdb_flat_index* ix, const float* d_queries, size_t nq, size_t dim, const float* d_radii,
+                                       const uint64_t* d_id_mask, size_t mask_bits, size_t max_results, uint64_t* d_out_ids,
+                                       float* d_out_dists, uint32_t* d_out_counts, uint64_t* d_out_totals, void* stream) {
+    return guarded([&]() -> int {
+    if (!ix || (nq && (!d_queries || !d_radii || !d_out_counts || !d_out_ids || !d_out_dists)))
+        return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (ix->multi) return refuse_multi("vdb_flat_range_search_batch_device");
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (ix->begin_locked) return fail(VDB_ERR_INVALID_ARGUMENT, "a search is pending between begin and finish");
+    return range_search_device(ix, d_queries, nq, dim, d_radii, d_id_mask, mask_bits, max_results, d_out_ids, d_out_dists,
+                               d_out_counts, d_out_totals, (hipStream_t)stream);
+    });
+}
+
+int vdb_flat_range_search_batch(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const float* radii, float radius,
+                                const uint64_t* id_mask, size_t mask_bits, size_t max_results, uint64_t* out_ids, float* out_dists,
+                                size_t* out_counts, uint64_t* out_totals) {
+    return guarded([&]() -> int {
+    if (!ix || (nq && (!queries || !out_counts || !out_ids || !out_dists))) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (ix->multi) return refuse_multi("vdb_flat_range_search_batch");
+    if (max_results == 0 || max_results > MAX_SELECT)
+        return fail(VDB_ERR_INVALID_ARGUMENT, "max_results %zu outside [1, %u]", max_results, MAX_SELECT);
+    std::vector<float> rad(nq, radius);
+    if (radii) std::copy(radii, radii + nq, rad.begin());
+    for (size_t b = 0; b < nq; ++b)
+        if (rad[b] != rad[b]) return fail(VDB_ERR_INVALID_ARGUMENT, "the radius of query %zu is NaN", b);
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (ix->begin_locked) return fail(VDB_ERR_INVALID_ARGUMENT, "a search is pending between begin and finish");
+    if (in_flight(ix)) return refuse_in_flight();
+    int rc = set_device(ix);
+    if (rc) return rc;
+    if (nq == 0) return VDB_OK;
+    Workspace* W = &ix->wsv[0];
+    hipStream_t s = ix->stream;
+    if ((rc = W->w_qin.ensure(nq * std::max<size_t>(dim, 1)))) return rc;
+    if ((rc = W->w_radii.ensure(nq))) return rc;
+    if ((rc = W->w_outi.ensure(nq * max_results))) return rc;
+    if ((rc = W->w_outd.ensure(nq * max_results))) return rc;
+    if ((rc = W->w_outc.ensure(nq))) return rc;
+    if ((rc = W->w_totals.ensure(nq))) return rc;
+    if (dim) HIP_TRY(hipMemcpyAsync(W->w_qin.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(W->w_radii.p, rad.data(), nq * sizeof(float), hipMemcpyHostToDevice, s));
+    const uint64_t* d_mask = nullptr;
+    if (id_mask) {
+        const size_t words = (mask_bits + 63) / 64;
+        if ((rc = W->w_mask_ids.ensure(std::max<size_t>(words, 1)))) return rc;
+        if (words) HIP_TRY(hipMemcpyAsync(W->w_mask_ids.p, id_mask, words * 8, hipMemcpyHostToDevice, s));
+        d_mask = W->w_mask_ids.p;
+    }
+    rc = range_search_device(ix, W->w_qin.p, nq, dim, W->w_radii.p, d_mask, mask_bits, max_results, W->w_outi.p, W->w_outd.p,
+                             W->w_outc.p, W->w_totals.p, nullptr);
+    if (rc) return rc;
+    std::vector<uint32_t> cnt(nq);
+    std::vector<uint64_t> ids(nq * max_results), tot(nq);
+    std::vector<float> ds(nq * max_results);
+    HIP_TRY(hipMemcpyAsync(cnt.data(), W->w_outc.p, nq * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(tot.data(), W->w_totals.p, nq * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(ids.data(), W->w_outi.p, nq * max_results * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(ds.data(), W->w_outd.p, nq * max_results * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t b = 0; b < nq; ++b) {
+        const size_t c = std::min<size_t>(cnt[b], max_results);
+        out_counts[b] = c;
+        if (out_totals) out_totals[b] = tot[b];
+        for (size_t i = 0; i < c; ++i) { out_ids[b * max_results + i] = ids[b * max_results + i]; out_dists[b * max_results + i] = ds[b * max_results + i]; }
+    }
+    return VDB_OK;
+    });
+}
+
+int vdb_flat_range_stats(const vdb_flat_index* ix, uint64_t out[8]) {
+    if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (ix->multi) return refuse_multi("vdb_flat_range_stats");
+    memcpy(out, ix->range_stats, sizeof(ix->range_stats));
+    return VDB_OK;
+}
+
 static bool merge_fits(size_t nparts, size_t nq, size_t k) {
     if (nparts && k > 0xffffffffull / nparts) return false;
     const unsigned long long bpq = (nparts * k + 255) / 256;

@@ -91,6 +91,7 @@ struct Workspace {
     vdbi::DevBuf<uint64_t> w_dense, w_samp, w_pool, w_cand, w_exact, w_exsel, w_mask_ids, w_outi;
     vdbi::DevBuf<uint32_t> w_cnt, w_rowmask, w_flags, w_outc, w_subcnt, w_depth;
     vdbi::DevBuf<uint32_t> w_elig, w_eligblk;                     // sparse-filter route: the eligible-row list; block counts | block offsets | E
+    vdbi::DevBuf<float> w_radii; vdbi::DevBuf<uint64_t> w_totals; // range search, host-pointer form: radii in, totals out
     vdbi::DevBuf<uint16_t> w_qb;                                  // bf16 copy of the padded queries (screening tier)
     // compact block of the queries the screening tier could not certify (re-run by the f32 tier)
     vdbi::DevBuf<float> w2_qp, w2_qnorm, w2_thr, w2_outd, w2_qerr, w2_qg;
@@ -123,7 +124,7 @@ struct Workspace {
         f(w_dense); f(w_samp); f(w_pool); f(w_cand); f(w_exact); f(w_exsel); f(w_mask_ids); f(w_outi);
         f(w_cnt); f(w_rowmask); f(w_flags); f(w_outc); f(w_subcnt); f(w_depth); f(w_qb);
         f(w2_qp); f(w2_qnorm); f(w2_thr); f(w2_outd); f(w2_qerr); f(w2_qg); f(w2_outi); f(w2_cand); f(w2_qb);
-        f(w2_outc); f(w2_flags); f(w2_qidx); f(w_dstat); f(w_elig); f(w_eligblk);
+        f(w2_outc); f(w2_flags); f(w2_qidx); f(w_dstat); f(w_elig); f(w_eligblk); f(w_radii); f(w_totals);
     }
 };
 
@@ -208,6 +209,7 @@ struct vdb_flat_index {
     // vdb_flat_set_sparse_filter: 0 never (default), 1 always, 2 automatic -- masked searches scan only the eligible rows (search_sparse)
     int sparse_mode = 0;
     uint64_t sparse_last = 0, sparse_E = 0, sparse_count = 0;  // vdb_flat_sparse_stats [0] [1] [2]
+    uint64_t range_stats[8] = {0};                          // vdb_flat_range_stats: counters of the last range search
     bool profile = false; hipEvent_t ev0 = nullptr, ev1 = nullptr;
 
     uint32_t n_rows() const { return (uint32_t)row_ids.size(); }
@@ -270,6 +272,9 @@ int refuse_in_flight();
 int search_device(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, const uint64_t* d_idmask,
                   size_t mask_bits, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                   hipStream_t user_stream);
+int range_search_device(Index* ix, const float* d_q, size_t nq, size_t dim, const float* d_radii, const uint64_t* d_idmask,
+                        size_t mask_bits, size_t max_results, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
+                        uint64_t* d_out_totals, hipStream_t user_stream);
 
 // ---- vdb_multi.cpp: one index over several GPUs in one process (the parent handle dispatches here)
 int multi_create(int metric, const int* devices, size_t n, vdb_flat_index** out);

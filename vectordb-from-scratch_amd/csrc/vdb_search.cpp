@@ -991,6 +991,224 @@ int search_part2(Index* ix, int* changed) {
     return VDB_OK;
 }
 
+// ------------------------------------------------------------------ the exact range search
+// Every eligible row with reference distance d <= radius, ascending by (distance, id): the first min(total, max_results) and
+// the total per query.  No reference counterpart; the machinery is the re-threshold pass's with the radius in the place of the
+// k-th exact distance:
+//   1. screened route (screening tier on, n >= BF16_MIN_ROWS): query_prep, range_cut_kernel (threshold = score_cut(radius): every
+//      row scoring above it lies strictly beyond the radius), the bf16 filter pass per 256 queries, the select of up to 2048 keys
+//      with truncation flagged, range_rerank_kernel -- every key evaluated exactly.  No sample pass.
+//   2. exact range scan, eight queries per pass over the rows: everything route 1 does not serve or could not finish (pool or
+//      select overflow, no finite cut, a NaN-score key).
+//   3. dense fallback: more than 32768 survivors -> exact_one for the first max_results (all within the radius); the total is
+//      route 2's counter.
+// (the caller checked the radii: none is NaN)
+static int range_search_run(Index* ix, const float* d_q, size_t nq, size_t dim, const float* d_radii,
+                            const uint64_t* d_idmask, size_t mask_bits, size_t max_results, uint64_t* d_out_ids, float* d_out_dists,
+                            uint32_t* d_out_counts, uint64_t* d_out_totals, hipStream_t s, uint64_t* st) {
+    int rc;
+    Workspace* W = ix->cur;
+    const size_t total_rows = ix->n_live + ix->misfits.size();
+    if (total_rows == 0) {                                         // as the searches: an empty store answers before any check
+        HIP_TRY(hipMemsetAsync(d_out_counts, 0, nq * 4, s));
+        if (d_out_totals) HIP_TRY(hipMemsetAsync(d_out_totals, 0, nq * 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return VDB_OK;
+    }
+    if (ix->n_live && ix->dim != dim) return fail_dim(dim, ix->dim);
+    for (auto& kv : ix->misfits)
+        if (kv.second.size() != dim) return fail_dim(dim, kv.second.size());
+    if (!ix->misfits.empty()) return fail(VDB_ERR_INVALID_ARGUMENT, "zero-dimensional vectors are not searchable");
+    if (ix->metric == vdb::COSINE) {
+        if ((rc = ensure_zero_count(ix))) return rc;
+        if (ix->zero_live) return fail_zero_vector();
+    }
+    if (nq > 0x7fffffffull / 2) return fail(VDB_ERR_INVALID_ARGUMENT, "batch too large");
+    if (ix->dim > 16384) return fail(VDB_ERR_INVALID_ARGUMENT, "dimension %u exceeds the supported 16384", ix->dim);
+
+    const uint32_t n = ix->n_uploaded, ld = ix->ld, nq32 = (uint32_t)nq, bp_all = round_up(nq32, SUPER);
+    const uint32_t mr = (uint32_t)max_results;
+    const bool screened = ix->screen && n >= BF16_MIN_ROWS;
+    constexpr uint32_t KMAX = MAX_SELECT;                          // keys evaluated per query at most (select capacity)
+
+    // ---- workspace.  Flags: status block | overflow | no cut | complete | keys evaluated, per query; all zeroed here
+    if ((rc = W->w_qp.ensure((size_t)bp_all * ld))) return rc;
+    if ((rc = W->w_qnorm.ensure(bp_all))) return rc;
+    if ((rc = W->w_thr.ensure(bp_all))) return rc;
+    if ((rc = W->w_flags.ensure(4 + 4 * (size_t)nq32))) return rc;
+    if ((rc = W->w_cnt.ensure(4 * SUPER + 16))) return rc;
+    uint32_t* d_status = W->w_flags.p;
+    uint32_t* d_ovf = d_status + 4;
+    uint32_t* d_nocut = d_ovf + nq32;
+    uint32_t* d_complete = d_nocut + nq32;
+    uint32_t* d_nkeys = d_complete + nq32;
+    HIP_TRY(hipMemsetAsync(W->w_flags.p, 0, (4 + 4 * (size_t)nq32) * 4, s));
+    W->status_dirty = true;                                        // (the tiers' bookkeeping: the block is cleared again before its next use)
+
+    // ---- eligibility mask: tombstones, optionally AND the caller's id filter
+    const uint32_t* d_rowmask = (ix->n_live == n) ? nullptr : ix->d_live;
+    if (d_idmask) {
+        if ((rc = W->w_rowmask.ensure((n + 31) / 32))) return rc;
+        vdb::launch_build_rowmask(ix->d_row_ids, d_rowmask, d_idmask, mask_bits, n, W->w_rowmask.p, s);
+        d_rowmask = W->w_rowmask.p;
+    }
+
+    // ---- queries: zero-padded copy, exact-order norms; for the screened route the bf16 image, |q - bf16(q)| and g_q as a search prepares them
+    if (screened) {
+        if ((rc = W->w_qb.ensure((size_t)bp_all * ld))) return rc;
+        if ((rc = W->w_qerr.ensure(bp_all))) return rc;
+        if ((rc = W->w_qg.ensure(bp_all))) return rc;
+    }
+    {
+        vdb::QueryPrepParams qp{d_q, (uint32_t)dim, nq32, W->w_qp.p, ld, bp_all, W->w_qnorm.p, W->w_thr.p, ix->metric, d_status,
+                                screened ? W->w_qb.p : nullptr, W->w_qerr.p, (screened && ix->d_margin) ? W->w_qg.p : nullptr,
+                                margin_plan(ix).kappa, nullptr, nullptr};
+        vdb::launch_query_prep(qp, s);
+    }
+
+    std::vector<uint32_t> todo;                                    // batch indices for the exact range scan
+    if (screened) {
+        const uint32_t capl = 256;
+        const uint32_t n_wg = screen_grid(ix, vdb::fused_bf16_tile_rows());
+        const uint32_t n_sub = vdb::fused_bf16_subpools_per_query(n_wg);
+        if ((rc = W->w2_cand.ensure((size_t)SUPER * KMAX))) return rc;
+        if ((rc = W->w_pool.ensure((size_t)SUPER * n_sub * capl))) return rc;
+        if ((rc = W->w_subcnt.ensure((size_t)SUPER * n_sub))) return rc;
+        // thresholds: score_cut(radius) from the constants the re-rank hands to score_cut (pass_bf16)
+        vdb::RangeCutParams cp{};
+        cp.cert = rerank_params(ix, d_rowmask, d_status, mr, nullptr, KMAX, nullptr);
+        cp.cert.qnorm = W->w_qnorm.p; cp.cert.eps_coef = eps_coef(ix);
+        cp.cert.qerr = W->w_qerr.p; cp.cert.c_acc = c_acc_bf16(ix); cp.cert.lb_scores = ix->d_margin ? 1u : 0u;
+        cp.radii = d_radii; cp.nq = nq32; cp.thr = W->w_thr.p; cp.nocut = d_nocut;
+        vdb::launch_range_cut(cp, s);
+        uint32_t* d_cand_cnt = W->w_cnt.p + 2 * SUPER;
+        for (uint32_t q0 = 0; q0 < nq32; q0 += SUPER) {
+            const uint32_t nb = std::min(SUPER, nq32 - q0);
+            vdb::FusedBf16Params fp = screen_params(ix, W, d_rowmask, d_status, capl, n_wg);
+            screen_queries(fp, ix, W->w_qb.p, W->w_qg.p, W->w_thr.p, q0);
+            launch_filter_pass(ix, fp, s);
+            st[3] += n;
+            vdb::SelectParams mp{};
+            mp.keys = W->w_pool.p; mp.sub_counts = W->w_subcnt.p; mp.n_sub = n_sub; mp.capl = capl; mp.wg_major = 1;
+            mp.kk = KMAX; mp.out_keys = W->w2_cand.p; mp.out_stride = KMAX; mp.out_cnt = d_cand_cnt;
+            mp.ovf = d_ovf + q0; mp.summary = nullptr; mp.flag_truncation = 1;
+            vdb::launch_select(mp, nb, s);
+            vdb::RangeRerankParams rp{};
+            rp.rows = ix->d_rows; rp.ld = ld; rp.dim = ix->dim; rp.n_rows = n;
+            rp.qp = W->w_qp.p + (size_t)q0 * ld; rp.qnorm = W->w_qnorm.p + q0; rp.nd = ix->d_nd;
+            rp.row_ids = ix->d_row_ids; rp.rowmask = d_rowmask;
+            rp.cand = W->w2_cand.p; rp.cand_stride = KMAX; rp.cand_cnt = d_cand_cnt;
+            rp.radii = d_radii + q0; rp.metric = ix->metric; rp.max_results = mr;
+            rp.out_ids = d_out_ids + (size_t)q0 * mr; rp.out_dists = d_out_dists + (size_t)q0 * mr;
+            rp.out_counts = d_out_counts + q0; rp.out_totals = d_out_totals ? d_out_totals + q0 : nullptr;
+            rp.complete = d_complete + q0; rp.n_keys = d_nkeys + q0; rp.status = d_status;
+            vdb::launch_range_rerank(rp, nb, s);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    std::vector<uint32_t> hf(4 + 4 * (size_t)nq32);
+    HIP_TRY(hipMemcpyAsync(hf.data(), W->w_flags.p, hf.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (hf[0] & vdb::ST_ZERO_QUERY) return fail_zero_vector();
+    if (screened) {
+        const uint32_t* ovf = hf.data() + 4; const uint32_t* nocut = ovf + nq32; const uint32_t* complete = nocut + nq32;
+        const uint32_t* nkeys = complete + nq32;
+        for (uint32_t q = 0; q < nq32; ++q) {
+            if (nocut[q]) ++st[6];
+            else { if (ovf[q]) ++st[5]; st[4] += nkeys[q]; }
+            if (nocut[q] || ovf[q] || !complete[q]) todo.push_back(q);
+        }
+    } else {
+        todo.resize(nq32);
+        for (uint32_t q = 0; q < nq32; ++q) todo[q] = q;
+    }
+
+    // ---- exact range scan of the queries left; the dense fallback for those with more survivors than the key buffer holds
+    uint32_t n_dense = 0;
+    if (!todo.empty()) {
+        const uint32_t cap = 32768;
+        if ((rc = ensure_ranks(ix))) return rc;
+        if ((rc = W->w_exact.ensure(std::max<size_t>((size_t)8 * cap, n)))) return rc;
+        if ((rc = W->w_exsel.ensure((size_t)8 * MAX_SELECT + 8))) return rc;
+        uint32_t* d_cnt8 = W->w_cnt.p + 3 * SUPER;                  // [8] survivors per query, [8..16) select counts
+        std::vector<uint32_t> dense;
+        for (size_t g0 = 0; g0 < todo.size(); g0 += 8) {
+            const uint32_t nqf = (uint32_t)std::min<size_t>(8, todo.size() - g0);
+            HIP_TRY(hipMemsetAsync(d_cnt8, 0, 16 * 4, s));
+            vdb::RangeScanParams ep{};
+            ep.rows = ix->d_rows; ep.ld = ld; ep.dim = ix->dim; ep.n_rows = n; ep.qp = W->w_qp.p; ep.qnorm = W->w_qnorm.p;
+            ep.nd = ix->d_nd; ep.rowmask = d_rowmask; ep.idrank = ix->ids_monotone ? nullptr : ix->d_idrank.p;
+            ep.metric = ix->metric; ep.nqf = nqf;
+            for (uint32_t j = 0; j < nqf; ++j) ep.qidx[j] = todo[g0 + j];
+            ep.radii = d_radii;
+            ep.keys = W->w_exact.p; ep.cap = cap; ep.cnt = d_cnt8; ep.status = d_status;
+            vdb::launch_range_scan(ep, s);
+            uint32_t h_cnt[8];
+            HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt8, nqf * 4, hipMemcpyDeviceToHost, s));
+            vdb::SelectParams sp{};
+            sp.keys = W->w_exact.p; sp.stride = cap; sp.counts = d_cnt8; sp.n_fixed = 0; sp.cap = cap; sp.kk = mr;
+            sp.out_keys = W->w_exsel.p; sp.out_stride = MAX_SELECT; sp.out_cnt = d_cnt8 + 8;
+            vdb::launch_select(sp, nqf, s);
+            vdb::RangeEmitParams em{};
+            em.keys = W->w_exsel.p; em.key_stride = MAX_SELECT; em.cnt = d_cnt8 + 8; em.survivors = d_cnt8;
+            em.rank2row = ix->ids_monotone ? nullptr : ix->d_rank2row.p; em.row_ids = ix->d_row_ids; em.n_rows = n;
+            em.out_ids = d_out_ids; em.out_dists = d_out_dists; em.out_counts = d_out_counts; em.out_totals = d_out_totals;
+            em.max_results = mr; em.nqf = nqf;
+            for (uint32_t j = 0; j < nqf; ++j) em.qidx[j] = todo[g0 + j];
+            vdb::launch_range_emit(em, s);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(s));
+            for (uint32_t j = 0; j < nqf; ++j)
+                if (h_cnt[j] > cap) dense.push_back(todo[g0 + j]);
+        }
+        // (every one of the first max_results <= 2048 lies within the radius: more than 32768 rows do)
+        for (uint32_t q : dense)
+            if ((rc = exact_one(ix, s, q, mr, d_rowmask, d_out_ids + (size_t)q * mr, d_out_dists + (size_t)q * mr, d_out_counts + q)))
+                return rc;
+        n_dense = (uint32_t)dense.size();
+    }
+    st[0] = nq32 - todo.size(); st[1] = todo.size() - n_dense; st[2] = n_dense;
+    uint32_t status = hf[0];
+    if (!todo.empty()) {
+        uint32_t st4[4] = {0, 0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(st4, W->w_flags.p, 16, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        status |= st4[0];
+    }
+    if (status & vdb::ST_ZERO_QUERY) return fail_zero_vector();
+    if (status & vdb::ST_NAN) return fail_nan();
+    return VDB_OK;
+}
+
+int range_search_device(Index* ix, const float* d_q, size_t nq, size_t dim, const float* d_radii, const uint64_t* d_idmask,
+                        size_t mask_bits, size_t max_results, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
+                        uint64_t* d_out_totals, hipStream_t user_stream) {
+    int rc;
+    if (max_results == 0 || max_results > MAX_SELECT)
+        return fail(VDB_ERR_INVALID_ARGUMENT, "max_results %zu outside [1, %u]", max_results, MAX_SELECT);
+    // a synchronous call takes a context no submitted search is using, like search_device
+    Workspace* W = ix->wsv[0].busy ? &ix->wsv[1] : &ix->wsv[0];
+    if (W->busy) return fail(VDB_ERR_INVALID_ARGUMENT, "two submitted searches are in flight on this handle: wait for one first");
+    if ((rc = set_device(ix))) return rc;
+    hipStream_t s = user_stream ? user_stream : W->stream;
+    // the radii on the host: a NaN radius is refused before anything is launched
+    std::vector<float> h_radii(nq);
+    if (nq) {
+        HIP_TRY(hipMemcpyAsync(h_radii.data(), d_radii, nq * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    for (size_t b = 0; b < nq; ++b)
+        if (h_radii[b] != h_radii[b]) return fail(VDB_ERR_INVALID_ARGUMENT, "the radius of query %zu is NaN", b);
+    ix->cur = W;
+    uint64_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    rc = flush(ix);
+    if (!rc && nq) rc = range_search_run(ix, d_q, nq, dim, d_radii, d_idmask, mask_bits, max_results, d_out_ids, d_out_dists,
+                                         d_out_counts, d_out_totals, s, st);
+    memcpy(ix->range_stats, st, sizeof(st));
+    ix->cur = &ix->wsv[0];
+    return rc;
+}
+
 void publish_stats(Index* ix) { memcpy(ix->stats, ix->cur->stats, sizeof(ix->stats)); }
 
 // searches submitted and not yet waited for (vdb_flat_search_batch_device_submit): the row store must not change under them

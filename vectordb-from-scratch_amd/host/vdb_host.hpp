@@ -127,6 +127,21 @@ public:
             for (size_t i = 0; i < cnt[b]; ++i) out[b].emplace_back((size_t)ids[b * kmax + i], ds[b * kmax + i]);
         return out;
     }
+    // no reference counterpart: every eligible row with distance d <= radius, ascending by (distance, id), at most max_results
+    // (1..2048) of them; *total (may be null) = rows within the radius
+    std::vector<Neighbor> range_search(const Vector& q, float radius, size_t max_results, const uint64_t* id_mask = nullptr,
+                                       size_t mask_bits = 0, uint64_t* total = nullptr) const {
+        std::vector<uint64_t> ids(std::max<size_t>(max_results, 1));
+        std::vector<float> ds(ids.size());
+        size_t cnt = 0;
+        uint64_t tot = 0;
+        check(vdb_flat_range_search_batch(h_, q.as_slice().data(), 1, q.dimension(), nullptr, radius, id_mask, mask_bits, max_results,
+                                          ids.data(), ds.data(), &cnt, &tot));
+        if (total) *total = tot;
+        std::vector<Neighbor> out;
+        for (size_t i = 0; i < cnt; ++i) out.emplace_back((size_t)ids[i], ds[i]);
+        return out;
+    }
     DistanceMetric metric() const override { return metric_; }
     size_t len() const override { return vdb_flat_len(h_); }
     void add_bulk(const float* rows, size_t n, size_t dim, uint64_t first_id) {
@@ -379,6 +394,15 @@ public:
         auto res = index_->search_batch(fetch);
         for (size_t b = 0; b < qs.size(); ++b) out[b] = post_filter(res[b], qs[b].second, f);
         return out;
+    }
+    // no reference counterpart: everything within `radius` of q, nearest first, at most `limit`; with a filter, under its mask
+    std::vector<SearchResult> search_within(const Vector& q, float radius, size_t limit, const MetadataFilter* f = nullptr) const {
+        if (is_empty()) return {};
+        check_dim(q);
+        if (!f) return map(index_->range_search(q, radius, limit));
+        size_t bits = 0;
+        const std::vector<uint64_t> mask = compile_filter(*f, &bits);
+        return map(index_->range_search(q, radius, limit, mask.data(), bits));
     }
     // the MetadataFilter compiled to a bitmask over internal ids (device pre-filter, BASELINE config 4)
     std::vector<uint64_t> compile_filter(const MetadataFilter& f, size_t* bits) const {

@@ -419,6 +419,60 @@ class GpuFlatIndex(Index):
         if rc:
             _raise(rc)
 
+    # ---- exact range search (include/vdb_flat.h vdb_flat_range_search_batch; no reference counterpart)
+    MAX_RANGE_RESULTS = 2048
+
+    def range_search_batch(self, queries, radius, max_results, id_mask=None, mask_bits=0):
+        """Every eligible row whose reference distance d satisfies d <= radius, ascending by (distance, id).
+        queries [nq, dim] f32; radius a scalar or a per-query array; max_results in [1, 2048].
+        Returns (ids u64 [nq, max_results], dists f32 [nq, max_results], counts [nq], totals u64 [nq]): counts[b] =
+        min(totals[b], max_results) entries of row b are written, totals[b] rows lie within the radius."""
+        qs = np.ascontiguousarray(queries, dtype=np.float32)
+        nq, dim = qs.shape
+        mr = int(max_results)
+        if np.isscalar(radius):
+            rad_ptr, rscalar = None, float(radius)
+        else:
+            rad = np.ascontiguousarray(radius, dtype=np.float32)
+            if rad.shape != (nq,):
+                raise ValueError(f"radius must be a scalar or hold one value per query ({nq}), not {rad.shape}")
+            rad_ptr, rscalar = _fp(rad), 0.0
+        out_ids = np.zeros((nq, max(mr, 1)), dtype=np.uint64)
+        out_d = np.zeros((nq, max(mr, 1)), dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uintp)
+        totals = np.zeros(nq, dtype=np.uint64)
+        mask_ptr = None
+        if id_mask is not None:
+            m = np.ascontiguousarray(id_mask, dtype=np.uint64)
+            mask_ptr = _u64p(m)
+        rc = self._L.vdb_flat_range_search_batch(self._h, _fp(qs), nq, dim, rad_ptr, ctypes.c_float(rscalar), mask_ptr, int(mask_bits),
+                                                 mr, _u64p(out_ids), _fp(out_d),
+                                                 counts.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)), _u64p(totals))
+        if rc:
+            _raise(rc)
+        return out_ids, out_d, counts, totals
+
+    def range_search_batch_device(self, q_ptr, nq, dim, radii_ptr, max_results, out_ids_ptr, out_dists_ptr, out_counts_ptr,
+                                  out_totals_ptr=0, stream=0, mask_ptr=0, mask_bits=0):
+        """Everything resident in HBM: raw device pointers (f32 radii [nq], uint64 ids and f32 dists [nq, max_results], u32
+        counts, u64 totals or 0).  Unused output slots hold id 2^64 - 1 and a NaN distance."""
+        rc = self._L.vdb_flat_range_search_batch_device(
+            self._h, ctypes.c_void_p(q_ptr), int(nq), int(dim), ctypes.c_void_p(radii_ptr), ctypes.c_void_p(mask_ptr or None),
+            int(mask_bits), int(max_results), ctypes.c_void_p(out_ids_ptr), ctypes.c_void_p(out_dists_ptr),
+            ctypes.c_void_p(out_counts_ptr), ctypes.c_void_p(out_totals_ptr or None), ctypes.c_void_p(stream or None))
+        if rc:
+            _raise(rc)
+
+    def range_stats(self):
+        """Counters of the last range search: [0] queries answered by the screened route, [1] by the exact range scan, [2] by
+        the dense fallback, [3] rows streamed by filter passes, [4] keys re-ranked, [5] queries whose pool or select
+        overflowed, [6] queries without a finite score cut, [7] 0."""
+        out = (ctypes.c_uint64 * 8)()
+        rc = self._L.vdb_flat_range_stats(self._h, out)
+        if rc:
+            _raise(rc)
+        return [int(x) for x in out]
+
     def distances_batch(self, queries, id_lists):
         """Exact reference distances of query b to the stored ids id_lists[b] (HNSW candidate lists)."""
         qs = np.ascontiguousarray(queries, dtype=np.float32)

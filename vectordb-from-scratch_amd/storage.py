@@ -535,6 +535,20 @@ class VectorStore:
             return None
         return self._table.compile(prog, max(self._next_id, 1))
 
+    # ---- exact range search (GpuFlatIndex.range_search_batch; no reference counterpart)
+    def search_within(self, query, radius, limit, flt=None):
+        """Every stored vector whose distance d to `query` satisfies d <= radius, nearest first (ties by internal id), at most
+        `limit` (1..2048) of them.  With flt the filter is applied BEFORE the radius, under the mask of compile_filter, like
+        search_batch_prefiltered."""
+        if not isinstance(self._index, GpuFlatIndex):
+            raise ValueError("search_within needs a GpuFlatIndex")
+        if self.is_empty():
+            return []
+        self._check_dim(query)
+        mask, bits = self.compile_filter(flt) if flt is not None else (None, 0)
+        ids, dists, counts, _ = self._index.range_search_batch(query.data[None, :], float(radius), int(limit), id_mask=mask, mask_bits=bits)
+        return self._map([(int(ids[0, i]), dists[0, i]) for i in range(int(counts[0]))])
+
     def search_batch_prefiltered(self, queries, flt):
         if self.is_empty():
             return [[] for _ in queries]
