@@ -7,6 +7,9 @@
 Two compiles of the same source differ only in the __hip_cuid_ symbol, so "identical" below means the instruction
 stream, the registers, the scratch and the LDS of a kernel are unchanged.  Kernels are matched by demangled name;
 --rename OLD=NEW rewrites a substring of the OLD file's names first (a template parameter that was dropped).
+The number of a function within its file is taken out of every block label, with or without the .L prefix: the loop
+comments of the assembly ("Loop: Header=BB31_3") carry it too, and a kernel added or removed earlier in the file shifts it
+for every later kernel, which would otherwise all report DIFFERS.
 Exit status 1 if any kernel differs or is missing on either side.
 """
 import argparse
@@ -30,7 +33,7 @@ def kernels(path, renames):
             d = d.replace(old, new)
         body = re.search(r"^%s:[^\n]*\n(.*?)^\.Lfunc_end\d+:" % re.escape(mangled), text, re.M | re.S).group(1)
         desc = re.search(r"\.amdhsa_kernel\s+%s\n(.*?)\.end_amdhsa_kernel" % re.escape(mangled), text, re.S).group(1)
-        norm = lambda s: re.sub(r"\.LBB\d+_", ".LBB_", s.replace(mangled, "KERNEL"))
+        norm = lambda s: re.sub(r"BB\d+_", "BB_", s.replace(mangled, "KERNEL"))
         res = {k: re.search(r"\.amdhsa_%s\s+(\S+)" % k, desc).group(1) for k in RES}
         out[d] = (norm(body).split("\n"), norm(desc).split("\n"), res)
     return out

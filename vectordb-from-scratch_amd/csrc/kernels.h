@@ -352,20 +352,23 @@ struct ExactScanParams {
 };
 void launch_exact_scan(const ExactScanParams& p, hipStream_t s);
 
-// Bounded exact scan for up to 8 uncertified queries in ONE pass over the rows: a row is kept for query j
-// only if its exact distance is <= bound_j, the k-th exact distance the re-rank already produced (an upper
-// bound of the true k-th distance), so the survivors are a handful of keys per query.
-struct ExactMultiParams {
+// The bounded exact scan: ONE pass over the rows for up to 8 queries; a row is kept for query j only if its exact distance
+// passes the query's bound, so the survivors are a handful of keys per query.  The bound is one of
+//   radii != null (the exact range scan):  d <= radii[qidx[j]]
+//   radii == null (the kNN fallback):      !(d > bound_j), bound_j = the k-th exact distance the re-rank already produced (an
+//                                          upper bound of the true k-th distance), +inf where prev_counts says there is none
+struct BoundedScanParams {
     const float* rows; uint32_t ld; uint32_t dim; uint32_t n_rows;
     const float* qp; const float* qnorm;               // padded query block and norms of the whole batch
     const float* nd; const uint32_t* rowmask; const uint32_t* idrank;
     int metric;
     uint32_t nqf; uint32_t qidx[8];                    // batch indices of the queries of this pass
-    const float* prev_dists; const uint32_t* prev_counts; uint32_t k;   // re-rank outputs: bound = dists[q*k + k-1] if counts[q] == k
-    uint64_t* keys; uint32_t cap; uint32_t* cnt;       // keys[j*cap + slot], cnt[j] (may exceed cap: overflow)
-    uint32_t* status;
+    const float* radii;                                // range: [batch]; null for the kNN fallback, which reads instead
+    const float* prev_dists; const uint32_t* prev_counts; uint32_t k;   // the re-rank outputs: bound = dists[q*k + k-1] if counts[q] == k
+    uint64_t* keys; uint32_t cap; uint32_t* cnt;       // keys[j*cap + slot], cnt[j] = ALL survivors (may exceed cap: overflow)
+    uint32_t* status;                                  // ST_NAN
 };
-void launch_exact_multi(const ExactMultiParams& p, hipStream_t s);
+void launch_bounded_scan(const BoundedScanParams& p, hipStream_t s);
 
 // ---------------------------------------------------------------- exact range search (kernels_range.hip)
 // thr[q] = score_cut(radii[q]) from the constants of the re-rank's certificate (cert: metric, ld, qnorm, qerr, c_acc, eps_coef,
@@ -392,26 +395,6 @@ struct RangeRerankParams {
     uint32_t lds_row_stride, lds_chunk;                // filled by launch_range_rerank
 };
 void launch_range_rerank(const RangeRerankParams& p, uint32_t nq, hipStream_t s);
-// The exact range scan: ExactMultiParams with the bound of query j taken from radii[qidx[j]] (d <= radius is kept)
-struct RangeScanParams {
-    const float* rows; uint32_t ld; uint32_t dim; uint32_t n_rows;
-    const float* qp; const float* qnorm;               // padded query block and norms of the whole batch
-    const float* nd; const uint32_t* rowmask; const uint32_t* idrank;
-    int metric;
-    uint32_t nqf; uint32_t qidx[8];
-    const float* radii;                                // [batch]
-    uint64_t* keys; uint32_t cap; uint32_t* cnt;       // keys[j*cap + slot], cnt[j] = ALL survivors (may exceed cap)
-    uint32_t* status;
-};
-void launch_range_scan(const RangeScanParams& p, hipStream_t s);
-// its sorted survivors as results: query j reads keys + j*key_stride, cnt[j] (selected) and survivors[j] (the total)
-struct RangeEmitParams {
-    const uint64_t* keys; uint32_t key_stride; const uint32_t* cnt; const uint32_t* survivors;
-    const uint32_t* rank2row; const uint64_t* row_ids; uint32_t n_rows;
-    uint64_t* out_ids; float* out_dists; uint32_t* out_counts; uint64_t* out_totals; uint32_t max_results;
-    uint32_t nqf; uint32_t qidx[8];
-};
-void launch_range_emit(const RangeEmitParams& p, hipStream_t s);
 
 // ---------------------------------------------------------------- sparse-filter route (kernels_sparse.hip)
 // The ascending list of the rows whose bit is set in a search's row mask (bits at or above n_rows never count), in two steps
@@ -448,17 +431,20 @@ struct FilterParams {
 };
 void launch_filter_compile(const FilterParams& p, uint32_t n_cu, hipStream_t s);   // mask_bits == 0: no launch
 
+// A rank or row at or beyond n_rows is written as padding (~0, NaN), never dereferenced.
 struct EmitParams {                                    // sorted exact keys -> (id, dist) outputs
     const uint64_t* keys; uint32_t cnt_max; const uint32_t* cnt;
     const uint32_t* rank2row; const uint64_t* row_ids;
     uint64_t* out_ids; float* out_dists; uint32_t* out_count; uint32_t k;
     uint32_t accumulate;                               // 1: *out_count += n (chunked large k), 0: *out_count = n
+    uint32_t n_rows;
 };
-// emit for several queries at once: query j (= blockIdx.y) reads keys + j*key_stride, cnt[j] and writes
-// to out_*[qidx[j]*k ..] / out_count[qidx[j]]
+// emit for several queries at once: query j (= blockIdx.y) reads keys + j*key_stride, cnt[j] (selected) and writes
+// to out_*[qidx[j]*k ..] / out_count[qidx[j]]; with out_totals, out_totals[qidx[j]] = survivors[j] (the range scan's total)
 struct EmitMultiParams {
     const uint64_t* keys; uint32_t key_stride; const uint32_t* cnt;
-    const uint32_t* rank2row; const uint64_t* row_ids;
+    const uint32_t* survivors; uint64_t* out_totals;   // both may be null
+    const uint32_t* rank2row; const uint64_t* row_ids; uint32_t n_rows;
     uint64_t* out_ids; float* out_dists; uint32_t* out_count; uint32_t k;
     uint32_t nqf; uint32_t qidx[8];
 };

@@ -699,8 +699,6 @@ void launch_cert_probe(const RerankParams& p, const uint32_t* qi, const float* T
     hipLaunchKernelGGL(cert_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, s, p, qi, T, ek, n, out);
 }
 
-typedef __attribute__((address_space(3))) void* rr_lds_t;
-typedef const __attribute__((address_space(1))) void* rr_glb_t;
 constexpr uint32_t RR_MAX = 512;        // candidates per query at most (= RR_THREADS: one thread per candidate)
 constexpr uint32_t RR_THREADS = 512;
 
@@ -961,32 +959,17 @@ __global__ __launch_bounds__(RR_THREADS) void rerank_all_kernel(RerankParams p) 
     const float* gq = p.qp + (size_t)q * p.ld;
     for (uint32_t i = tid * 4; i < dimp; i += RR_THREADS * 4) *reinterpret_cast<float4*>(sQ + i) = *reinterpret_cast<const float4*>(gq + i);
     __syncthreads();
-    const uint32_t vpr = dimp / 4, bpr = (vpr + 63) / 64, nwaves = RR_THREADS / 64;
     const float qn_f = p.qnorm[q];
     for (uint32_t c0 = 0; c0 < cnt; c0 += chunk) {
         const uint32_t nthis = (cnt - c0 < chunk) ? cnt - c0 : chunk;
+        float dist;
+        uint32_t row;
+        const bool have = stage_chunk_distances<RR_THREADS>(cand + c0, nthis, p.rows, p.ld, p.dim, p.n_rows, p.rowmask, p.nd, p.metric, qn_f,
+                                                            sQ, sR, ldp, sRowIdx, &sNanKey, &dist, &row);
         if (tid < nthis) {
-            const uint64_t key = cand[c0 + tid];
-            uint32_t row = (uint32_t)key;
-            if ((uint32_t)(key >> 32) == 0u) sNanKey = 1u;
-            const bool ok = row < p.n_rows && (p.rowmask ? ((p.rowmask[row >> 5] >> (row & 31)) & 1u) : true);
-            sRowIdx[tid] = ok ? row : 0xffffffffu;
-        }
-        __syncthreads();
-        for (uint32_t u = wv; u < nthis * bpr; u += nwaves) {
-            const uint32_t r = u / bpr, b = u % bpr, c4 = b * 64 + lane;
-            const uint32_t row = sRowIdx[r];
-            if (row != 0xffffffffu && c4 < vpr)
-                __builtin_amdgcn_global_load_lds((rr_glb_t)(p.rows + (size_t)row * p.ld + 4 * c4),
-                                                 (rr_lds_t)(sR + (size_t)r * ldp + 256 * b), 16, 0, 0);
-        }
-        __syncthreads();
-        if (tid < nthis) {
-            const uint32_t row = sRowIdx[tid];
             uint32_t od = 0xffffffffu;
             uint64_t id = ~0ull;
-            if (row != 0xffffffffu) {
-                const float dist = exact_distance(p.metric, sQ, sR + (size_t)tid * ldp, p.dim, qn_f, p.nd[row]);
+            if (have) {
                 if (dist != dist) sAnyNan = 1u;
                 od = f32_to_ordered(dist);
                 id = p.row_ids[row];
@@ -995,19 +978,7 @@ __global__ __launch_bounds__(RR_THREADS) void rerank_all_kernel(RerankParams p) 
             sId[p.k + tid] = id;
         }
         __syncthreads();
-        for (uint32_t size = 2; size <= AREA; size <<= 1)
-            for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-                if (tid < AREA / 2) {
-                    uint32_t lo = 2 * tid - (tid & (stride - 1));
-                    uint32_t hi = lo + stride;
-                    bool up = ((lo & size) == 0);
-                    uint32_t da = sDist[lo], db = sDist[hi];
-                    uint64_t ia = sId[lo], ib = sId[hi];
-                    bool gt = da > db || (da == db && ia > ib);
-                    if (gt == up) { sDist[lo] = db; sDist[hi] = da; sId[lo] = ib; sId[hi] = ia; }
-                }
-                __syncthreads();
-            }
+        bitonic_sort_pairs<RR_THREADS>(sDist, sId, AREA, tid);
         if (tid >= p.k && tid < AREA) { sDist[tid] = 0xffffffffu; sId[tid] = ~0ull; }      // keep the best k only
         __syncthreads();
     }
@@ -1034,8 +1005,7 @@ __global__ __launch_bounds__(RR_THREADS) void rerank_all_kernel(RerankParams p) 
 void launch_rerank_all(const RerankParams& p, uint32_t nq, hipStream_t s) {
     if (!nq) return;
     RerankParams q = p;
-    uint32_t dimp = (p.dim + 3) & ~3u;
-    q.lds_row_stride = dimp + ((dimp % 8 == 0) ? 4 : 0);
+    q.lds_row_stride = rerank_row_stride(p.dim);
     uint32_t chunk = (uint32_t)std::min<size_t>(64, (150 * 1024) / ((size_t)q.lds_row_stride * 4));
     chunk = chunk > 1 ? chunk - 1 : 1;
     q.lds_chunk = chunk;
@@ -1159,18 +1129,7 @@ __device__ __forceinline__ void rerank_large_body(const RerankParams& p) {
             // ---- bitonic sort of [0, P) ascending by (distance, id); unused slots hold the maximum; then keep the best k
             uint32_t P = 64;
             while (P < nbest + n) P <<= 1;
-            for (uint32_t size = 2; size <= P; size <<= 1)
-                for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-                    for (uint32_t t = tid; t < P / 2; t += RL_THREADS) {
-                        const uint32_t lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-                        const bool up = ((lo & size) == 0);
-                        const uint32_t da = sDist[lo], db = sDist[hi];
-                        const uint64_t ia = sId[lo], ib = sId[hi];
-                        const bool gt = da > db || (da == db && ia > ib);
-                        if (gt == up) { sDist[lo] = db; sDist[hi] = da; sId[lo] = ib; sId[hi] = ia; }
-                    }
-                    __syncthreads();
-                }
+            bitonic_sort_pairs<RL_THREADS>(sDist, sId, P, tid);
             processed += n;
             nbest = nbest + n < k ? nbest + n : k;
             for (uint32_t i = nbest + tid; i < P; i += RL_THREADS) { sDist[i] = 0xffffffffu; sId[i] = ~0ull; }
@@ -1406,84 +1365,62 @@ void launch_small_scan(const SmallScanParams& p, hipStream_t s) {
     hipLaunchKernelGGL(small_scan_kernel, dim3((p.n_rows + 255) / 256, p.nq), dim3(256), (size_t)((p.dim + 3) & ~3u) * sizeof(float), s, p);
 }
 
-// One pass over the rows for up to 8 queries: one thread per row, the row is read once (16 floats at a
-// time) and folded against every query in the reference's order (independent chains -> ILP).
-__global__ __launch_bounds__(256) void exact_multi_kernel(ExactMultiParams p) {
+// The bounded exact scan (BoundedScanParams): one pass over the rows for up to 8 queries, one thread per row, the row folded
+// against every query by fold_multi.  A row is kept for query j when its distance passes the query's bound; cnt[j] counts ALL
+// survivors, also those past the key buffer.  The two keep rules differ for a NaN distance and are kept as they are:
+//   RANGE  (the exact range scan)   dist <= radii[qi]: a row at exactly the radius is in, a NaN distance is out
+//   !RANGE (the kNN fallback)       !(dist > bound), bound = the k-th exact distance the re-rank found, +inf without one: ties
+//                                   with the bound are kept, and so is a NaN distance
+template <bool RANGE>
+__global__ __launch_bounds__(256) void bounded_scan_kernel(BoundedScanParams p) {
     const uint32_t row = blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= p.n_rows) return;
     if (p.rowmask && !((p.rowmask[row >> 5] >> (row & 31)) & 1u)) return;
-    const float* x = p.rows + (size_t)row * p.ld;
     float s[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s[j] = 0.0f;
-    const uint32_t d = p.dim;
-    uint32_t i = 0;
-    for (; i + 16 <= d; i += 16) {
-        float4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(x + i + 4 * u);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if (j < (int)p.nqf) {                                           // wave-uniform
-                const float* q = p.qp + (size_t)p.qidx[j] * p.ld + i;       // uniform address: scalar loads
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float4 a = *reinterpret_cast<const float4*>(q + 4 * u);
-                    if (p.metric == EUCLID) {
-                        float t;
-                        t = __fsub_rn(a.x, v[u].x); s[j] = __fadd_rn(s[j], __fmul_rn(t, t));
-                        t = __fsub_rn(a.y, v[u].y); s[j] = __fadd_rn(s[j], __fmul_rn(t, t));
-                        t = __fsub_rn(a.z, v[u].z); s[j] = __fadd_rn(s[j], __fmul_rn(t, t));
-                        t = __fsub_rn(a.w, v[u].w); s[j] = __fadd_rn(s[j], __fmul_rn(t, t));
-                    } else {
-                        s[j] = __fadd_rn(s[j], __fmul_rn(a.x, v[u].x));
-                        s[j] = __fadd_rn(s[j], __fmul_rn(a.y, v[u].y));
-                        s[j] = __fadd_rn(s[j], __fmul_rn(a.z, v[u].z));
-                        s[j] = __fadd_rn(s[j], __fmul_rn(a.w, v[u].w));
-                    }
-                }
-            }
-        }
-    }
-    for (; i < d; ++i) {
-        const float xv = x[i];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if (j < (int)p.nqf) {
-                const float a = p.qp[(size_t)p.qidx[j] * p.ld + i];
-                if (p.metric == EUCLID) { float t = __fsub_rn(a, xv); s[j] = __fadd_rn(s[j], __fmul_rn(t, t)); }
-                else s[j] = __fadd_rn(s[j], __fmul_rn(a, xv));
-            }
-        }
-    }
+    fold_multi<8>(p.metric, p.rows + (size_t)row * p.ld, p.dim, p.qp, p.ld, p.qidx, p.nqf, s);
     const float xn = p.nd[row];
     const uint32_t rk = p.idrank ? p.idrank[row] : row;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         if (j < (int)p.nqf) {
             const uint32_t qi = p.qidx[j];
-            float dist;
-            if (p.metric == EUCLID) dist = __builtin_sqrtf(s[j]);
-            else if (p.metric == DOT) dist = -s[j];
-            else {
-                float sim = __fdiv_rn(s[j], __fmul_rn(p.qnorm[qi], xn));
-                if (sim < -1.0f) sim = -1.0f;
-                if (sim > 1.0f) sim = 1.0f;
-                dist = __fsub_rn(1.0f, sim);
-            }
+            const float dist = distance_from_fold(p.metric, s[j], p.qnorm[qi], xn);
             if (dist != dist) atomicOr(p.status, ST_NAN);
-            const float bound = (p.prev_counts[qi] == p.k) ? p.prev_dists[(size_t)qi * p.k + p.k - 1]
-                                                           : __uint_as_float(0x7f800000u);
-            if (!(dist > bound)) {                                          // ties with the bound are kept
+            bool keep;
+            if (RANGE) keep = dist <= p.radii[qi];
+            else {
+                const float bound = (p.prev_counts[qi] == p.k) ? p.prev_dists[(size_t)qi * p.k + p.k - 1]
+                                                               : __uint_as_float(0x7f800000u);
+                keep = !(dist > bound);
+            }
+            if (keep) {
                 const uint32_t slot = atomicAdd(&p.cnt[j], 1u);
                 if (slot < p.cap) p.keys[(size_t)j * p.cap + slot] = ((uint64_t)f32_to_ordered(dist) << 32) | rk;
             }
         }
     }
 }
-void launch_exact_multi(const ExactMultiParams& p, hipStream_t s) {
+void launch_bounded_scan(const BoundedScanParams& p, hipStream_t s) {
     if (!p.n_rows || !p.nqf) return;
-    hipLaunchKernelGGL(exact_multi_kernel, dim3((p.n_rows + 255) / 256), dim3(256), 0, s, p);
+    const dim3 grid((p.n_rows + 255) / 256), block(256);
+    if (p.radii) hipLaunchKernelGGL(bounded_scan_kernel<true>, grid, block, 0, s, p);
+    else hipLaunchKernelGGL(bounded_scan_kernel<false>, grid, block, 0, s, p);
+}
+
+// slot i of a query's output from its sorted keys: the row's id and the distance of the key, or the padding (~0, NaN) for a slot
+// at or beyond cnt -- and for a key whose rank or row is at or beyond n_rows, which is never dereferenced
+__device__ __forceinline__ void emit_slot(const uint64_t* keys, uint32_t i, uint32_t cnt, const uint32_t* rank2row,
+                                          const uint64_t* row_ids, uint32_t n_rows, uint64_t* out_id, float* out_dist) {
+    const uint64_t key = i < cnt ? keys[i] : EMPTY_KEY;
+    const uint32_t rk = (uint32_t)key;
+    const uint32_t row = (rk < n_rows && rank2row) ? rank2row[rk] : rk;
+    if (i < cnt && row < n_rows) {
+        *out_id = row_ids[row];
+        *out_dist = ordered_to_f32((uint32_t)(key >> 32));
+    } else {
+        *out_id = ~0ull;
+        *out_dist = __uint_as_float(0x7fc00000u);
+    }
 }
 
 __global__ __launch_bounds__(256) void emit_multi_kernel(EmitMultiParams p) {
@@ -1492,19 +1429,13 @@ __global__ __launch_bounds__(256) void emit_multi_kernel(EmitMultiParams p) {
     const uint32_t qi = p.qidx[j];
     uint32_t cnt = p.cnt[j];
     if (cnt > p.k) cnt = p.k;
-    if (i == 0) p.out_count[qi] = cnt;
+    if (i == 0) {
+        p.out_count[qi] = cnt;
+        if (p.out_totals) p.out_totals[qi] = p.survivors[j];
+    }
     if (i >= p.k) return;
     const size_t o = (size_t)qi * p.k + i;
-    if (i < cnt) {
-        uint64_t key = p.keys[(size_t)j * p.key_stride + i];
-        uint32_t rk = (uint32_t)key;
-        uint32_t row = p.rank2row ? p.rank2row[rk] : rk;
-        p.out_ids[o] = p.row_ids[row];
-        p.out_dists[o] = ordered_to_f32((uint32_t)(key >> 32));
-    } else {
-        p.out_ids[o] = ~0ull;
-        p.out_dists[o] = __uint_as_float(0x7fc00000u);
-    }
+    emit_slot(p.keys + (size_t)j * p.key_stride, i, cnt, p.rank2row, p.row_ids, p.n_rows, p.out_ids + o, p.out_dists + o);
 }
 void launch_emit_multi(const EmitMultiParams& p, hipStream_t s) {
     if (!p.k || !p.nqf) return;
@@ -1517,16 +1448,7 @@ __global__ __launch_bounds__(256) void emit_kernel(EmitParams p) {
     if (cnt > p.k) cnt = p.k;
     if (i == 0) *p.out_count = (p.accumulate ? *p.out_count : 0u) + cnt;
     if (i >= p.k) return;
-    if (i < cnt) {
-        uint64_t key = p.keys[i];
-        uint32_t rk = (uint32_t)key;
-        uint32_t row = p.rank2row ? p.rank2row[rk] : rk;
-        p.out_ids[i] = p.row_ids[row];
-        p.out_dists[i] = ordered_to_f32((uint32_t)(key >> 32));
-    } else {
-        p.out_ids[i] = ~0ull;
-        p.out_dists[i] = __uint_as_float(0x7fc00000u);
-    }
+    emit_slot(p.keys, i, cnt, p.rank2row, p.row_ids, p.n_rows, p.out_ids + i, p.out_dists + i);
 }
 void launch_emit(const EmitParams& p, hipStream_t s) {
     if (!p.k) return;
@@ -1582,74 +1504,22 @@ void launch_pair_eval(const PairEvalParams& p, hipStream_t s) {
     hipLaunchKernelGGL(pair_eval_kernel, dim3((p.n + 255) / 256), dim3(256), 0, s, p);
 }
 
-// One pass over rows [0, n_scan) for up to 16 query rows: one thread per row, the row read once (16 floats at a time)
-// and folded against every query in the reference's order (independent chains -> ILP); the query elements come through
-// scalar loads (uniform addresses).  The all-pairs scan the batched HNSW build amortises over a chunk of inserts.
+// One pass over rows [0, n_scan) for up to 16 query rows, themselves stored rows: one thread per row, folded against every
+// query row by fold_multi.  The all-pairs scan the batched HNSW build amortises over a chunk of inserts.
 template <int NQ>
 __global__ __launch_bounds__(256) void scan_rows_kernel(ScanRowsParams p) {
     const uint32_t row = blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= p.n_scan) return;
-    const float* x = p.rows + (size_t)row * p.ld;
     float s[NQ];
-#pragma unroll
-    for (int j = 0; j < NQ; ++j) s[j] = 0.0f;
-    const uint32_t d = p.dim;
-    uint32_t i = 0;
-    for (; i + 16 <= d; i += 16) {
-        float4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(x + i + 4 * u);
-#pragma unroll
-        for (int j = 0; j < NQ; ++j) {
-            if (j < (int)p.nq) {                                            // wave-uniform
-                const float* q = p.rows + (size_t)p.qrow[j] * p.ld + i;     // uniform address: scalar loads
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float4 a = *reinterpret_cast<const float4*>(q + 4 * u);
-                    if (p.metric == EUCLID) {
-                        float t;
-                        t = __fsub_rn(a.x, v[u].x); s[j] = __fadd_rn(s[j], __fmul_rn(t, t));
-                        t = __fsub_rn(a.y, v[u].y); s[j] = __fadd_rn(s[j], __fmul_rn(t, t));
-                        t = __fsub_rn(a.z, v[u].z); s[j] = __fadd_rn(s[j], __fmul_rn(t, t));
-                        t = __fsub_rn(a.w, v[u].w); s[j] = __fadd_rn(s[j], __fmul_rn(t, t));
-                    } else {
-                        s[j] = __fadd_rn(s[j], __fmul_rn(a.x, v[u].x));
-                        s[j] = __fadd_rn(s[j], __fmul_rn(a.y, v[u].y));
-                        s[j] = __fadd_rn(s[j], __fmul_rn(a.z, v[u].z));
-                        s[j] = __fadd_rn(s[j], __fmul_rn(a.w, v[u].w));
-                    }
-                }
-            }
-        }
-    }
-    for (; i < d; ++i) {
-        const float xv = x[i];
-#pragma unroll
-        for (int j = 0; j < NQ; ++j) {
-            if (j < (int)p.nq) {
-                const float a = p.rows[(size_t)p.qrow[j] * p.ld + i];
-                if (p.metric == EUCLID) { float t = __fsub_rn(a, xv); s[j] = __fadd_rn(s[j], __fmul_rn(t, t)); }
-                else s[j] = __fadd_rn(s[j], __fmul_rn(a, xv));
-            }
-        }
-    }
+    fold_multi<NQ>(p.metric, p.rows + (size_t)row * p.ld, p.dim, p.rows, p.ld, p.qrow, p.nq, s);
     const float xn = p.nd[row];
 #pragma unroll
     for (int j = 0; j < NQ; ++j) {
         if (j < (int)p.nq) {
+            const float qn = p.metric == COSINE ? p.nd[p.qrow[j]] : 0.0f;
             float dist;
-            if (p.metric == EUCLID) dist = __builtin_sqrtf(s[j]);
-            else if (p.metric == DOT) dist = -s[j];
-            else {
-                const float qn = p.nd[p.qrow[j]];
-                if (qn == 0.0f || xn == 0.0f) dist = __uint_as_float(p.mark);
-                else {
-                    float sim = __fdiv_rn(s[j], __fmul_rn(qn, xn));          // norm1 * norm2 with the QUERY's norm first (distance.rs:58)
-                    if (sim < -1.0f) sim = -1.0f;
-                    if (sim > 1.0f) sim = 1.0f;
-                    dist = __fsub_rn(1.0f, sim);
-                }
-            }
+            if (p.metric == COSINE && (qn == 0.0f || xn == 0.0f)) dist = __uint_as_float(p.mark);
+            else dist = distance_from_fold(p.metric, s[j], qn, xn);
             p.out[(size_t)j * p.ldm + row] = dist;
         }
     }

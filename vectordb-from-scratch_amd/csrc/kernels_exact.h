@@ -148,14 +148,137 @@ __device__ __forceinline__ float distance_from_fold(int metric, float s, float q
 // qn / xn are the exact-order norms of query and row (only read under Cosine).
 __device__ __forceinline__ float exact_distance(int metric, const float* __restrict__ q,
                                                 const float* __restrict__ x, uint32_t d, float qn, float xn) {
-    if (metric == EUCLID) return __builtin_sqrtf(fold_sqdiff(q, x, d));
-    float dot = fold_dot(q, x, d);
-    if (metric == DOT) return -dot;
-    float den = __fmul_rn(qn, xn);                 // norm1 * norm2   distance.rs:58
-    float sim = __fdiv_rn(dot, den);
-    if (sim < -1.0f) sim = -1.0f;                  // f32::clamp keeps NaN
-    if (sim > 1.0f) sim = 1.0f;
-    return __fsub_rn(1.0f, sim);
+    if (metric == EUCLID) return distance_from_fold(EUCLID, fold_sqdiff(q, x, d), qn, xn);
+    return distance_from_fold(metric, fold_dot(q, x, d), qn, xn);
+}
+
+// The same folds for ONE row against up to NQ queries at once (the bounded scans of the searches, the row scan of the HNSW
+// build): one thread per row, the row read once, 16 floats at a time, and folded against every query in the reference's order --
+// NQ independent chains.  Query j is the row qbase + qidx[j] * pitch; qidx is an array INSIDE the kernel's parameter struct and
+// nq is wave-uniform, so every query address is a uniform expression of kernel parameters and the query elements come through
+// scalar loads.  s[j] ends as fold_sqdiff / fold_dot of (query j, x); s[j] for j >= nq stays 0.
+// (NIDX is the length of the index array, deduced: scan_rows_kernel<4> and <8> pass the 16-entry qrow of their parameter struct.)
+template <int NQ, int NIDX>
+__device__ __forceinline__ void fold_multi(int metric, const float* x, uint32_t d, const float* qbase, uint32_t pitch,
+                                           const uint32_t (&qidx)[NIDX], uint32_t nq, float (&s)[NQ]) {
+    static_assert(NQ <= NIDX, "one index per query");
+    // The sums are folded in a local array and copied to s at the end.  Folding into s directly compiled, in every includer, to
+    // a different block layout of the j < nq guards with 6 to 10 more VGPRs than the loop written out in the kernel had
+    // (bounded_scan_kernel 32 -> 40, scan_rows_kernel<4> 28 -> 34, <8> 30 -> 40): the body is optimised before it is inlined, and
+    // until then s is memory that x and qbase may alias.  With the local array the arithmetic and load counts and the VGPRs are
+    // the written-out loop's (32, 30, 32, 52).
+    float acc[NQ];
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) acc[j] = 0.0f;
+    uint32_t i = 0;
+    for (; i + 16 <= d; i += 16) {
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(x + i + 4 * u);
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {
+            if (j < (int)nq) {                                              // wave-uniform
+                const float* q = qbase + (size_t)qidx[j] * pitch + i;       // uniform address: scalar loads
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const float4 a = *reinterpret_cast<const float4*>(q + 4 * u);
+                    if (metric == EUCLID) {
+                        float t;
+                        t = __fsub_rn(a.x, v[u].x); acc[j] = __fadd_rn(acc[j], __fmul_rn(t, t));
+                        t = __fsub_rn(a.y, v[u].y); acc[j] = __fadd_rn(acc[j], __fmul_rn(t, t));
+                        t = __fsub_rn(a.z, v[u].z); acc[j] = __fadd_rn(acc[j], __fmul_rn(t, t));
+                        t = __fsub_rn(a.w, v[u].w); acc[j] = __fadd_rn(acc[j], __fmul_rn(t, t));
+                    } else {
+                        acc[j] = __fadd_rn(acc[j], __fmul_rn(a.x, v[u].x));
+                        acc[j] = __fadd_rn(acc[j], __fmul_rn(a.y, v[u].y));
+                        acc[j] = __fadd_rn(acc[j], __fmul_rn(a.z, v[u].z));
+                        acc[j] = __fadd_rn(acc[j], __fmul_rn(a.w, v[u].w));
+                    }
+                }
+            }
+        }
+    }
+    for (; i < d; ++i) {
+        const float xv = x[i];
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {
+            if (j < (int)nq) {
+                const float a = qbase[(size_t)qidx[j] * pitch + i];
+                if (metric == EUCLID) { float t = __fsub_rn(a, xv); acc[j] = __fadd_rn(acc[j], __fmul_rn(t, t)); }
+                else acc[j] = __fadd_rn(acc[j], __fmul_rn(a, xv));
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) s[j] = acc[j];
+}
+
+// ---------------------------------------------------------------------------------------------
+// What the exhaustive re-ranks share (rerank_all_kernel, rerank_large_body, range_rerank_kernel): the LDS plan of a staged row,
+// the staging of a chunk of candidate rows with their exact distances, and the sort of (ordered distance, id) pairs.
+// ---------------------------------------------------------------------------------------------
+typedef __attribute__((address_space(3))) void* rr_lds_t;
+typedef const __attribute__((address_space(1))) void* rr_glb_t;
+constexpr uint32_t NO_ROW = 0xffffffffu;                          // sRowIdx entry of a key that is skipped
+
+// floats between two rows staged in LDS: the padded dimension, plus 4 where it is a multiple of 8 (bank spread of the float4 reads)
+__host__ __device__ inline uint32_t rerank_row_stride(uint32_t dim) {
+    const uint32_t dimp = (dim + 3) & ~3u;
+    return dimp + ((dimp % 8 == 0) ? 4 : 0);
+}
+
+// One chunk of a candidate list, by a workgroup of THREADS threads (nthis <= THREADS keys at keys[0 .. nthis)): thread t < nthis
+// reads key t, raises *sNanKey for a NaN-score key (score word 0) and puts the key's row into sRowIdx[t] -- NO_ROW if the row is
+// at or beyond n_rows or masked out, BEFORE any address is formed from it; the waves then stage the valid rows into
+// sR[t * ldp ..] with global_load_lds, 16 bytes per lane; thread t gets exact_distance(sQ, its row).  Returns false for a
+// thread without a key or with a skipped one (*dist, *row untouched).  Every thread of the workgroup must call it: it holds
+// two barriers; the caller places the one that ends the chunk.
+template <uint32_t THREADS>
+__device__ __forceinline__ bool stage_chunk_distances(const uint64_t* __restrict__ keys, uint32_t nthis, const float* __restrict__ rows,
+                                                      uint32_t ld, uint32_t dim, uint32_t n_rows, const uint32_t* __restrict__ rowmask,
+                                                      const float* __restrict__ nd, int metric, float qn, const float* sQ, float* sR,
+                                                      uint32_t ldp, uint32_t* sRowIdx, uint32_t* sNanKey, float* dist, uint32_t* row_out) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint32_t vpr = ((dim + 3) & ~3u) / 4, bpr = (vpr + 63) / 64;
+    if (tid < nthis) {
+        const uint64_t key = keys[tid];
+        const uint32_t row = (uint32_t)key;
+        if ((uint32_t)(key >> 32) == 0u) *sNanKey = 1u;
+        const bool ok = row < n_rows && (rowmask ? ((rowmask[row >> 5] >> (row & 31)) & 1u) : true);
+        sRowIdx[tid] = ok ? row : NO_ROW;
+    }
+    __syncthreads();
+    for (uint32_t u = wv; u < nthis * bpr; u += THREADS / 64) {
+        const uint32_t r = u / bpr, b = u % bpr, c4 = b * 64 + lane;
+        const uint32_t row = sRowIdx[r];
+        if (row != NO_ROW && c4 < vpr)
+            __builtin_amdgcn_global_load_lds((rr_glb_t)(rows + (size_t)row * ld + 4 * c4), (rr_lds_t)(sR + (size_t)r * ldp + 256 * b), 16, 0, 0);
+    }
+    __syncthreads();
+    if (tid >= nthis) return false;
+    const uint32_t row = sRowIdx[tid];
+    if (row == NO_ROW) return false;
+    *dist = exact_distance(metric, sQ, sR + (size_t)tid * ldp, dim, qn, nd[row]);
+    *row_out = row;
+    return true;
+}
+
+// Bitonic sort of the pairs (sDist[i], sId[i]), i < P (a power of two >= 2, unused slots hold the maximum), ascending by
+// (ordered distance, id), by a workgroup of THREADS threads.  Ends with a barrier.
+template <uint32_t THREADS>
+__device__ __forceinline__ void bitonic_sort_pairs(uint32_t* sDist, uint64_t* sId, uint32_t P, uint32_t tid) {
+    for (uint32_t size = 2; size <= P; size <<= 1)
+        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+            for (uint32_t t = tid; t < P / 2; t += THREADS) {
+                const uint32_t lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+                const bool up = ((lo & size) == 0);
+                const uint32_t da = sDist[lo], db = sDist[hi];
+                const uint64_t ia = sId[lo], ib = sId[hi];
+                const bool gt = da > db || (da == db && ia > ib);
+                if (gt == up) { sDist[lo] = db; sDist[hi] = da; sId[lo] = ib; sId[hi] = ia; }
+            }
+            __syncthreads();
+        }
 }
 
 // The certification test: every row not re-ranked has ranking score >= T; is the k-th exact distance ek below the

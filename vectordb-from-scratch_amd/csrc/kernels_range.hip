@@ -4,8 +4,9 @@
 // oracle's full ranking, bit for bit.
 //   range_cut_kernel      radius -> filter threshold of the bf16 screening pass: score_cut, the inverse of the certificate
 //   range_rerank_kernel   the tail of the screened route: every key that passed the filter evaluated exactly, kept if d <= r, sorted
-//   range_scan_kernel     the exact range scan: exact_multi_kernel's pass over the rows with the radius as the bound
-//   range_emit_kernel     its sorted survivors as results, with the total
+// The exact range scan and its emit are not here: they are the kNN fallback's kernels (kernels_aux.hip) -- bounded_scan_kernel<true>,
+// the one pass over the rows with the radius as the bound, and emit_multi_kernel with the total.  range_rerank_kernel stages and
+// sorts with the helpers of kernels_exact.h that rerank_all_kernel uses.
 // gfx950 only.  Built with -ffp-contract=off like every translation unit that computes a reference distance.
 #include "kernels.h"
 #include "kernels_exact.h"
@@ -51,15 +52,13 @@ void launch_range_cut(const RangeCutParams& p, hipStream_t s) {
 
 // ---------------------------------------------------------------------------------------------
 // The tail of the screened route, one workgroup per query.  EVERY key the select delivered (up to 2048, any order) is evaluated
-// with exact_distance, rows staged through LDS chunk by chunk as rerank_all_kernel stages them; the keys with d <= r go to a
-// sort area of 2048 (ordered distance, id) pairs, which one bitonic network orders.  The first min(total, max_results) are
+// with exact_distance, rows staged through LDS chunk by chunk (stage_chunk_distances, shared with rerank_all_kernel); the keys
+// with d <= r go to a sort area of 2048 (ordered distance, id) pairs, which one bitonic network orders (bitonic_sort_pairs).  The first min(total, max_results) are
 // written, the rest of the query's output row is padded (id ~0, NaN distance).  complete[q] = 0 when a NaN-score key was in the
 // list (as rerank_all_kernel: the exact range scan answers); a truncated list is flagged by the select (overflow).
 // Everything that comes from device memory is treated as untrusted: the key count is clamped to the list's stride and the sort
 // area, a row index is compared with n_rows before any address is formed, a sort slot is compared with the area before the store.
 // ---------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void* rg_lds_t;
-typedef const __attribute__((address_space(1))) void* rg_glb_t;
 constexpr uint32_t RG_THREADS = 512, RG_AREA = 2048;
 constexpr size_t RG_LDS_PLAN = 150 * 1024;                       // the plan of launch_rerank_all: sort area + row slices stay within it
 constexpr size_t RG_STATIC = RG_AREA * 12 + RG_THREADS * 4 + 64; // sDist + sId + sRowIdx + flags
@@ -70,7 +69,7 @@ __global__ __launch_bounds__(RG_THREADS) void range_rerank_kernel(RangeRerankPar
     __shared__ uint64_t sId[RG_AREA];
     __shared__ uint32_t sRowIdx[RG_THREADS];
     __shared__ uint32_t sAnyNan, sNanKey, sKept;
-    const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint32_t q = blockIdx.x, tid = threadIdx.x;
     uint32_t cnt = p.cand_cnt[q] < p.cand_stride ? p.cand_cnt[q] : p.cand_stride;
     if (cnt > RG_AREA) cnt = RG_AREA;
     const uint64_t* cand = p.cand + (size_t)q * p.cand_stride;
@@ -84,36 +83,18 @@ __global__ __launch_bounds__(RG_THREADS) void range_rerank_kernel(RangeRerankPar
     const float* gq = p.qp + (size_t)q * p.ld;
     for (uint32_t i = tid * 4; i < dimp; i += RG_THREADS * 4) *reinterpret_cast<float4*>(sQ + i) = *reinterpret_cast<const float4*>(gq + i);
     __syncthreads();
-    const uint32_t vpr = dimp / 4, bpr = (vpr + 63) / 64, nwaves = RG_THREADS / 64;
     const float qn_f = p.qnorm[q];
     const float r = p.radii[q];
     for (uint32_t c0 = 0; c0 < cnt; c0 += chunk) {
         const uint32_t nthis = (cnt - c0 < chunk) ? cnt - c0 : chunk;
-        if (tid < nthis) {
-            const uint64_t key = cand[c0 + tid];
-            const uint32_t row = (uint32_t)key;
-            if ((uint32_t)(key >> 32) == 0u) sNanKey = 1u;
-            const bool ok = row < p.n_rows && (p.rowmask ? ((p.rowmask[row >> 5] >> (row & 31)) & 1u) : true);
-            sRowIdx[tid] = ok ? row : 0xffffffffu;
-        }
-        __syncthreads();
-        for (uint32_t u = wv; u < nthis * bpr; u += nwaves) {
-            const uint32_t rr = u / bpr, b = u % bpr, c4 = b * 64 + lane;
-            const uint32_t row = sRowIdx[rr];
-            if (row != 0xffffffffu && c4 < vpr)
-                __builtin_amdgcn_global_load_lds((rg_glb_t)(p.rows + (size_t)row * p.ld + 4 * c4),
-                                                 (rg_lds_t)(sR + (size_t)rr * ldp + 256 * b), 16, 0, 0);
-        }
-        __syncthreads();
-        if (tid < nthis) {
-            const uint32_t row = sRowIdx[tid];
-            if (row != 0xffffffffu) {
-                const float dist = exact_distance(p.metric, sQ, sR + (size_t)tid * ldp, p.dim, qn_f, p.nd[row]);
-                if (dist != dist) sAnyNan = 1u;
-                else if (dist <= r) {
-                    const uint32_t slot = atomicAdd(&sKept, 1u);
-                    if (slot < RG_AREA) { sDist[slot] = f32_to_ordered(dist); sId[slot] = p.row_ids[row]; }
-                }
+        float dist;
+        uint32_t row;
+        if (stage_chunk_distances<RG_THREADS>(cand + c0, nthis, p.rows, p.ld, p.dim, p.n_rows, p.rowmask, p.nd, p.metric, qn_f, sQ, sR, ldp,
+                                              sRowIdx, &sNanKey, &dist, &row)) {
+            if (dist != dist) sAnyNan = 1u;
+            else if (dist <= r) {
+                const uint32_t slot = atomicAdd(&sKept, 1u);
+                if (slot < RG_AREA) { sDist[slot] = f32_to_ordered(dist); sId[slot] = p.row_ids[row]; }
             }
         }
         __syncthreads();
@@ -121,19 +102,7 @@ __global__ __launch_bounds__(RG_THREADS) void range_rerank_kernel(RangeRerankPar
     const uint32_t total = sKept < RG_AREA ? sKept : RG_AREA;
     uint32_t n2 = 2;
     while (n2 < total) n2 <<= 1;                                   // (<= RG_AREA: total is clamped)
-    for (uint32_t size = 2; size <= n2; size <<= 1)
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            for (uint32_t t = tid; t < n2 / 2; t += RG_THREADS) {
-                const uint32_t lo = 2 * t - (t & (stride - 1));
-                const uint32_t hi = lo + stride;
-                const bool up = ((lo & size) == 0);
-                const uint32_t da = sDist[lo], db = sDist[hi];
-                const uint64_t ia = sId[lo], ib = sId[hi];
-                const bool gt = da > db || (da == db && ia > ib);
-                if (gt == up) { sDist[lo] = db; sDist[hi] = da; sId[lo] = ib; sId[hi] = ia; }
-            }
-            __syncthreads();
-        }
+    bitonic_sort_pairs<RG_THREADS>(sDist, sId, n2, tid);
     const uint32_t nout = total < p.max_results ? total : p.max_results;
     for (uint32_t i = tid; i < p.max_results; i += RG_THREADS) {
         const size_t o = (size_t)q * p.max_results + i;
@@ -151,8 +120,7 @@ __global__ __launch_bounds__(RG_THREADS) void range_rerank_kernel(RangeRerankPar
 void launch_range_rerank(const RangeRerankParams& p, uint32_t nq, hipStream_t s) {
     if (!nq) return;
     RangeRerankParams q = p;
-    const uint32_t dimp = (p.dim + 3) & ~3u;
-    q.lds_row_stride = dimp + ((dimp % 8 == 0) ? 4 : 0);
+    q.lds_row_stride = rerank_row_stride(p.dim);
     // rows of the slice area: what the plan leaves beside the sort area, at least the query row and one candidate row (dim <= 16384)
     const size_t row_bytes = (size_t)q.lds_row_stride * 4;
     size_t rows_fit = (RG_LDS_PLAN - RG_STATIC) / row_bytes;
@@ -160,116 +128,6 @@ void launch_range_rerank(const RangeRerankParams& p, uint32_t nq, hipStream_t s)
     q.lds_chunk = (uint32_t)std::min<size_t>(RG_THREADS, rows_fit - 1);
     const size_t lds = (size_t)(q.lds_chunk + 1) * row_bytes;
     hipLaunchKernelGGL(range_rerank_kernel, dim3(nq), dim3(RG_THREADS), lds, s, q);
-}
-
-// ---------------------------------------------------------------------------------------------
-// The exact range scan: one pass over the rows for up to 8 queries, exact_multi_kernel's loop and arithmetic (one thread per row,
-// the row read once, 16 floats at a time, folded against every query in the reference's order), the bound taken from the radius
-// array.  A row is kept for query j when d <= radii[qidx[j]]; cnt[j] counts ALL survivors, also those past the key buffer.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void range_scan_kernel(RangeScanParams p) {
-    const uint32_t row = blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= p.n_rows) return;
-    if (p.rowmask && !((p.rowmask[row >> 5] >> (row & 31)) & 1u)) return;
-    const float* x = p.rows + (size_t)row * p.ld;
-    float s[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s[j] = 0.0f;
-    const uint32_t d = p.dim;
-    uint32_t i = 0;
-    for (; i + 16 <= d; i += 16) {
-        float4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(x + i + 4 * u);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if (j < (int)p.nqf) {                                           // wave-uniform
-                const float* q = p.qp + (size_t)p.qidx[j] * p.ld + i;       // uniform address: scalar loads
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float4 a = *reinterpret_cast<const float4*>(q + 4 * u);
-                    if (p.metric == EUCLID) {
-                        float t;
-                        t = __fsub_rn(a.x, v[u].x); s[j] = __fadd_rn(s[j], __fmul_rn(t, t));
-                        t = __fsub_rn(a.y, v[u].y); s[j] = __fadd_rn(s[j], __fmul_rn(t, t));
-                        t = __fsub_rn(a.z, v[u].z); s[j] = __fadd_rn(s[j], __fmul_rn(t, t));
-                        t = __fsub_rn(a.w, v[u].w); s[j] = __fadd_rn(s[j], __fmul_rn(t, t));
-                    } else {
-                        s[j] = __fadd_rn(s[j], __fmul_rn(a.x, v[u].x));
-                        s[j] = __fadd_rn(s[j], __fmul_rn(a.y, v[u].y));
-                        s[j] = __fadd_rn(s[j], __fmul_rn(a.z, v[u].z));
-                        s[j] = __fadd_rn(s[j], __fmul_rn(a.w, v[u].w));
-                    }
-                }
-            }
-        }
-    }
-    for (; i < d; ++i) {
-        const float xv = x[i];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if (j < (int)p.nqf) {
-                const float a = p.qp[(size_t)p.qidx[j] * p.ld + i];
-                if (p.metric == EUCLID) { float t = __fsub_rn(a, xv); s[j] = __fadd_rn(s[j], __fmul_rn(t, t)); }
-                else s[j] = __fadd_rn(s[j], __fmul_rn(a, xv));
-            }
-        }
-    }
-    const float xn = p.nd[row];
-    const uint32_t rk = p.idrank ? p.idrank[row] : row;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        if (j < (int)p.nqf) {
-            const uint32_t qi = p.qidx[j];
-            float dist;
-            if (p.metric == EUCLID) dist = __builtin_sqrtf(s[j]);
-            else if (p.metric == DOT) dist = -s[j];
-            else {
-                float sim = __fdiv_rn(s[j], __fmul_rn(p.qnorm[qi], xn));
-                if (sim < -1.0f) sim = -1.0f;
-                if (sim > 1.0f) sim = 1.0f;
-                dist = __fsub_rn(1.0f, sim);
-            }
-            if (dist != dist) atomicOr(p.status, ST_NAN);
-            if (dist <= p.radii[qi]) {                                      // a row at exactly the radius is in
-                const uint32_t slot = atomicAdd(&p.cnt[j], 1u);
-                if (slot < p.cap) p.keys[(size_t)j * p.cap + slot] = ((uint64_t)f32_to_ordered(dist) << 32) | rk;
-            }
-        }
-    }
-}
-void launch_range_scan(const RangeScanParams& p, hipStream_t s) {
-    if (!p.n_rows || !p.nqf) return;
-    hipLaunchKernelGGL(range_scan_kernel, dim3((p.n_rows + 255) / 256), dim3(256), 0, s, p);
-}
-
-// the sorted survivors of query j (= blockIdx.y) as results of batch query qidx[j]: emit_multi_kernel plus the total
-__global__ __launch_bounds__(256) void range_emit_kernel(RangeEmitParams p) {
-    const uint32_t j = blockIdx.y;
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t qi = p.qidx[j];
-    uint32_t cnt = p.cnt[j];
-    if (cnt > p.max_results) cnt = p.max_results;
-    if (i == 0) {
-        p.out_counts[qi] = cnt;
-        if (p.out_totals) p.out_totals[qi] = p.survivors[j];
-    }
-    if (i >= p.max_results) return;
-    const size_t o = (size_t)qi * p.max_results + i;
-    const uint64_t key = i < cnt ? p.keys[(size_t)j * p.key_stride + i] : EMPTY_KEY;
-    const uint32_t rk = (uint32_t)key;
-    const uint32_t row = (rk < p.n_rows && p.rank2row) ? p.rank2row[rk] : rk;
-    if (i < cnt && row < p.n_rows) {
-        p.out_ids[o] = p.row_ids[row];
-        p.out_dists[o] = ordered_to_f32((uint32_t)(key >> 32));
-    } else {
-        p.out_ids[o] = ~0ull;
-        p.out_dists[o] = __uint_as_float(0x7fc00000u);
-    }
-}
-void launch_range_emit(const RangeEmitParams& p, hipStream_t s) {
-    if (!p.max_results || !p.nqf) return;
-    hipLaunchKernelGGL(range_emit_kernel, dim3((p.max_results + 255) / 256, p.nqf), dim3(256), 0, s, p);
 }
 
 }  // namespace vdb

@@ -129,10 +129,60 @@ int exact_one(Index* ix, hipStream_t s, uint32_t q, size_t k, const uint32_t* d_
         sp.lo_excl = done ? last : nullptr; sp.out_last = last;
         vdb::launch_select(sp, 1, s);
         vdb::EmitParams em{ix->cur->w_exsel.p, MAX_SELECT, cnt, ix->ids_monotone ? nullptr : ix->d_rank2row.p,
-                           ix->d_row_ids, d_out_ids + done, d_out_dists + done, d_out_count, kk, done ? 1u : 0u};
+                           ix->d_row_ids, d_out_ids + done, d_out_dists + done, d_out_count, kk, done ? 1u : 0u, n};
         vdb::launch_emit(em, s);
     }
     HIP_TRY(hipGetLastError());
+    return VDB_OK;
+}
+
+// ------------------------------------------------------------------ the bounded exact scan, eight queries per pass over the rows
+// The queries of `todo` (batch indices into the workspace's prepared queries) through launch_bounded_scan: a row survives for a
+// query only if its exact distance passes the query's bound -- d_radii[q] if d_radii is given (the range scan), else the k-th
+// exact distance the re-rank left in d_out_dists / d_out_counts (the kNN fallback).  The kk smallest survivors of query q go to
+// d_out_*[q * kk ..], the survivor count to d_out_totals[q] if given.  `dense` receives the queries with more survivors than
+// the key buffer holds (e.g. every row ties with the bound): their outputs are not valid, the caller runs exact_one for them.
+constexpr uint32_t SCAN_CAP = 32768;                               // keys per query of a bounded pass
+static int bounded_scan_queries(Index* ix, hipStream_t s, const std::vector<uint32_t>& todo, uint32_t kk, const float* d_radii,
+                                const uint32_t* d_rowmask, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
+                                uint64_t* d_out_totals, uint32_t* d_status, std::vector<uint32_t>& dense) {
+    int rc;
+    Workspace* W = ix->cur;
+    const uint32_t n = ix->n_uploaded;
+    if ((rc = ensure_ranks(ix))) return rc;
+    if ((rc = W->w_exact.ensure(std::max<size_t>((size_t)8 * SCAN_CAP, n)))) return rc;
+    if ((rc = W->w_exsel.ensure((size_t)8 * MAX_SELECT + 8))) return rc;
+    uint32_t* d_cnt8 = W->w_cnt.p + 3 * SUPER;                     // [8] survivors per query, [8..16) select counts
+    for (size_t g0 = 0; g0 < todo.size(); g0 += 8) {
+        const uint32_t nqf = (uint32_t)std::min<size_t>(8, todo.size() - g0);
+        HIP_TRY(hipMemsetAsync(d_cnt8, 0, 16 * 4, s));
+        vdb::BoundedScanParams ep{};
+        ep.rows = ix->d_rows; ep.ld = ix->ld; ep.dim = ix->dim; ep.n_rows = n; ep.qp = W->w_qp.p; ep.qnorm = W->w_qnorm.p;
+        ep.nd = ix->d_nd; ep.rowmask = d_rowmask; ep.idrank = ix->ids_monotone ? nullptr : ix->d_idrank.p;
+        ep.metric = ix->metric; ep.nqf = nqf;
+        for (uint32_t j = 0; j < nqf; ++j) ep.qidx[j] = todo[g0 + j];
+        if (d_radii) ep.radii = d_radii;
+        else { ep.prev_dists = d_out_dists; ep.prev_counts = d_out_counts; ep.k = kk; }
+        ep.keys = W->w_exact.p; ep.cap = SCAN_CAP; ep.cnt = d_cnt8; ep.status = d_status;
+        vdb::launch_bounded_scan(ep, s);
+        uint32_t h_cnt[8];
+        HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt8, nqf * 4, hipMemcpyDeviceToHost, s));
+        vdb::SelectParams sp{};
+        sp.keys = W->w_exact.p; sp.stride = SCAN_CAP; sp.counts = d_cnt8; sp.n_fixed = 0; sp.cap = SCAN_CAP; sp.kk = kk;
+        sp.out_keys = W->w_exsel.p; sp.out_stride = MAX_SELECT; sp.out_cnt = d_cnt8 + 8;
+        vdb::launch_select(sp, nqf, s);
+        vdb::EmitMultiParams em{};
+        em.keys = W->w_exsel.p; em.key_stride = MAX_SELECT; em.cnt = d_cnt8 + 8;
+        em.survivors = d_cnt8; em.out_totals = d_out_totals;
+        em.rank2row = ix->ids_monotone ? nullptr : ix->d_rank2row.p; em.row_ids = ix->d_row_ids; em.n_rows = n;
+        em.out_ids = d_out_ids; em.out_dists = d_out_dists; em.out_count = d_out_counts; em.k = kk; em.nqf = nqf;
+        for (uint32_t j = 0; j < nqf; ++j) em.qidx[j] = todo[g0 + j];
+        vdb::launch_emit_multi(em, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));
+        for (uint32_t j = 0; j < nqf; ++j)
+            if (h_cnt[j] > SCAN_CAP) dense.push_back(todo[g0 + j]);
+    }
     return VDB_OK;
 }
 
@@ -853,7 +903,6 @@ int search_part2(Index* ix, int* changed) {
     hipStream_t s = c.s;
     const uint32_t* d_rowmask = c.d_rowmask;
     uint64_t* d_out_ids = c.d_out_ids; float* d_out_dists = c.d_out_dists; uint32_t* d_out_counts = c.d_out_counts;
-    const uint32_t n = ix->n_uploaded, ld = ix->ld;
     uint32_t* d_status = ix->cur->w_flags.p;
     const auto t_entry = c.t_entry;
     auto since = [&]() { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_entry).count(); };
@@ -935,40 +984,10 @@ int search_part2(Index* ix, int* changed) {
     uint32_t n_fallback = 0;
     n_fallback = (uint32_t)todo.size();
     if (!todo.empty()) {
-        const uint32_t cap = 32768;
-        if ((rc = ensure_ranks(ix))) return rc;
-        if ((rc = ix->cur->w_exact.ensure(std::max<size_t>((size_t)8 * cap, n)))) return rc;
-        if ((rc = ix->cur->w_exsel.ensure((size_t)8 * MAX_SELECT + 8))) return rc;
-        uint32_t* d_cnt8 = ix->cur->w_cnt.p + 3 * SUPER;            // [8] survivors per query, [8..16) select counts
         std::vector<uint32_t> dense;                             // queries whose bounded pass overflowed
-        for (size_t g0 = 0; g0 < todo.size(); g0 += 8) {
-            const uint32_t nqf = (uint32_t)std::min<size_t>(8, todo.size() - g0);
-            HIP_TRY(hipMemsetAsync(d_cnt8, 0, 16 * 4, s));
-            vdb::ExactMultiParams ep{};
-            ep.rows = ix->d_rows; ep.ld = ld; ep.dim = ix->dim; ep.n_rows = n; ep.qp = ix->cur->w_qp.p; ep.qnorm = ix->cur->w_qnorm.p;
-            ep.nd = ix->d_nd; ep.rowmask = d_rowmask; ep.idrank = ix->ids_monotone ? nullptr : ix->d_idrank.p;
-            ep.metric = ix->metric; ep.nqf = nqf;
-            for (uint32_t j = 0; j < nqf; ++j) ep.qidx[j] = todo[g0 + j];
-            ep.prev_dists = d_out_dists; ep.prev_counts = d_out_counts; ep.k = (uint32_t)k;
-            ep.keys = ix->cur->w_exact.p; ep.cap = cap; ep.cnt = d_cnt8; ep.status = d_status;
-            vdb::launch_exact_multi(ep, s);
-            uint32_t h_cnt[8];
-            HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt8, nqf * 4, hipMemcpyDeviceToHost, s));
-            vdb::SelectParams sp{};
-            sp.keys = ix->cur->w_exact.p; sp.stride = cap; sp.counts = d_cnt8; sp.n_fixed = 0; sp.cap = cap; sp.kk = (uint32_t)k;
-            sp.out_keys = ix->cur->w_exsel.p; sp.out_stride = MAX_SELECT; sp.out_cnt = d_cnt8 + 8;
-            vdb::launch_select(sp, nqf, s);
-            vdb::EmitMultiParams em{};
-            em.keys = ix->cur->w_exsel.p; em.key_stride = MAX_SELECT; em.cnt = d_cnt8 + 8;
-            em.rank2row = ix->ids_monotone ? nullptr : ix->d_rank2row.p; em.row_ids = ix->d_row_ids;
-            em.out_ids = d_out_ids; em.out_dists = d_out_dists; em.out_count = d_out_counts; em.k = (uint32_t)k; em.nqf = nqf;
-            for (uint32_t j = 0; j < nqf; ++j) em.qidx[j] = todo[g0 + j];
-            vdb::launch_emit_multi(em, s);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(s));
-            for (uint32_t j = 0; j < nqf; ++j)
-                if (h_cnt[j] > cap) dense.push_back(todo[g0 + j]);   // e.g. every row ties with the bound
-        }
+        if ((rc = bounded_scan_queries(ix, s, todo, (uint32_t)k, nullptr, d_rowmask, d_out_ids, d_out_dists, d_out_counts, nullptr,
+                                       d_status, dense)))
+            return rc;
         for (uint32_t q : dense)
             if ((rc = exact_one(ix, s, q, k, d_rowmask, d_out_ids + (size_t)q * k, d_out_dists + (size_t)q * k,
                                 d_out_counts + q)))
@@ -1126,41 +1145,10 @@ static int range_search_run(Index* ix, const float* d_q, size_t nq, size_t dim, 
     // ---- exact range scan of the queries left; the dense fallback for those with more survivors than the key buffer holds
     uint32_t n_dense = 0;
     if (!todo.empty()) {
-        const uint32_t cap = 32768;
-        if ((rc = ensure_ranks(ix))) return rc;
-        if ((rc = W->w_exact.ensure(std::max<size_t>((size_t)8 * cap, n)))) return rc;
-        if ((rc = W->w_exsel.ensure((size_t)8 * MAX_SELECT + 8))) return rc;
-        uint32_t* d_cnt8 = W->w_cnt.p + 3 * SUPER;                  // [8] survivors per query, [8..16) select counts
         std::vector<uint32_t> dense;
-        for (size_t g0 = 0; g0 < todo.size(); g0 += 8) {
-            const uint32_t nqf = (uint32_t)std::min<size_t>(8, todo.size() - g0);
-            HIP_TRY(hipMemsetAsync(d_cnt8, 0, 16 * 4, s));
-            vdb::RangeScanParams ep{};
-            ep.rows = ix->d_rows; ep.ld = ld; ep.dim = ix->dim; ep.n_rows = n; ep.qp = W->w_qp.p; ep.qnorm = W->w_qnorm.p;
-            ep.nd = ix->d_nd; ep.rowmask = d_rowmask; ep.idrank = ix->ids_monotone ? nullptr : ix->d_idrank.p;
-            ep.metric = ix->metric; ep.nqf = nqf;
-            for (uint32_t j = 0; j < nqf; ++j) ep.qidx[j] = todo[g0 + j];
-            ep.radii = d_radii;
-            ep.keys = W->w_exact.p; ep.cap = cap; ep.cnt = d_cnt8; ep.status = d_status;
-            vdb::launch_range_scan(ep, s);
-            uint32_t h_cnt[8];
-            HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt8, nqf * 4, hipMemcpyDeviceToHost, s));
-            vdb::SelectParams sp{};
-            sp.keys = W->w_exact.p; sp.stride = cap; sp.counts = d_cnt8; sp.n_fixed = 0; sp.cap = cap; sp.kk = mr;
-            sp.out_keys = W->w_exsel.p; sp.out_stride = MAX_SELECT; sp.out_cnt = d_cnt8 + 8;
-            vdb::launch_select(sp, nqf, s);
-            vdb::RangeEmitParams em{};
-            em.keys = W->w_exsel.p; em.key_stride = MAX_SELECT; em.cnt = d_cnt8 + 8; em.survivors = d_cnt8;
-            em.rank2row = ix->ids_monotone ? nullptr : ix->d_rank2row.p; em.row_ids = ix->d_row_ids; em.n_rows = n;
-            em.out_ids = d_out_ids; em.out_dists = d_out_dists; em.out_counts = d_out_counts; em.out_totals = d_out_totals;
-            em.max_results = mr; em.nqf = nqf;
-            for (uint32_t j = 0; j < nqf; ++j) em.qidx[j] = todo[g0 + j];
-            vdb::launch_range_emit(em, s);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(s));
-            for (uint32_t j = 0; j < nqf; ++j)
-                if (h_cnt[j] > cap) dense.push_back(todo[g0 + j]);
-        }
+        if ((rc = bounded_scan_queries(ix, s, todo, mr, d_radii, d_rowmask, d_out_ids, d_out_dists, d_out_counts, d_out_totals,
+                                       d_status, dense)))
+            return rc;
         // (every one of the first max_results <= 2048 lies within the radius: more than 32768 rows do)
         for (uint32_t q : dense)
             if ((rc = exact_one(ix, s, q, mr, d_rowmask, d_out_ids + (size_t)q * mr, d_out_dists + (size_t)q * mr, d_out_counts + q)))
