@@ -42,7 +42,6 @@ int fail_dim(size_t expected, size_t actual) {
 // (the texts are compared with the reference's by the tests)
 int fail_zero_vector() { return fail(VDB_ERR_INVALID_VECTOR, "Invalid vector: Cannot compute cosine distance with zero vector"); }
 int fail_nan() { return fail(VDB_ERR_NAN, "NaN distance (the reference panics here, flat_index.rs:62)"); }
-int guard_fail(const char* what) { return fail(VDB_ERR_DEVICE, "internal error: %s", what); }
 void last_error(std::string* msg, size_t* expected, size_t* actual) {
     if (msg) *msg = g_err;
     if (expected) *expected = g_expected;
@@ -83,7 +82,7 @@ int vdb_flat_create(int metric, int device, vdb_flat_index** out) {
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(VDB_ERR_DEVICE, "device %d is %s; the kernels are built for gfx950 only", device, prop.gcnArchName);
-    auto* ix = new vdb_flat_index();
+    auto ix = std::make_unique<vdb_flat_index>();
     ix->metric = metric;
     ix->device = device;
     ix->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -100,53 +99,31 @@ int vdb_flat_create(int metric, int device, vdb_flat_index** out) {
         if (const char* e = getenv("VDB_FUSED_PIPE")) { kn.fused_pipe = strcmp(e, "0") != 0; kn.any = true; }
     }
 #endif
-    if (hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete ix;
-        return fail(VDB_ERR_DEVICE, "hipStreamCreate failed");
-    }
-    if (hipMalloc((void**)&ix->d_scalars, 32) != hipSuccess || hipMemset(ix->d_scalars, 0, 32) != hipSuccess) {
-        (void)hipStreamDestroy(ix->stream);
-        delete ix;
-        return fail(VDB_ERR_DEVICE, "hipMalloc failed");
-    }
-    ix->wsv = new Workspace[2];
+    int rc;
+    if ((rc = ix->stream.create(hipStreamNonBlocking)) || (rc = ix->stream_alt.create(hipStreamNonBlocking))) return rc;
+    if ((rc = ix->d_scalars.ensure(8))) return rc;
+    HIP_TRY(hipMemset(ix->d_scalars, 0, 32));
+    ix->wsv.reset(new Workspace[2]);
     ix->cur = &ix->wsv[0];
     ix->wsv[0].stream = ix->stream;
-    if (hipStreamCreateWithFlags(&ix->wsv[1].stream, hipStreamNonBlocking) != hipSuccess) {
-        (void)hipFree(ix->d_scalars);
-        (void)hipStreamDestroy(ix->stream);
-        delete[] ix->wsv;
-        delete ix;
-        return fail(VDB_ERR_DEVICE, "hipStreamCreate failed");
-    }
-    *out = ix;
+    ix->wsv[1].stream = ix->stream_alt;
+    *out = ix.release();
     return VDB_OK;
     });
+}
+
+// Only what ordering requires: nothing is freed under a kernel that still runs.  The members free themselves afterwards,
+// the streams (declared first) last.
+vdb_flat_index::~vdb_flat_index() {
+    if (!stream) return;
+    (void)hipSetDevice(device);
+    (void)hipStreamSynchronize(stream);
+    (void)hipStreamSynchronize(stream_alt);
 }
 
 void vdb_flat_destroy(vdb_flat_index* ix) {
     if (!ix) return;
     if (ix->multi) { multi_destroy(ix); return; }
-    (void)hipSetDevice(ix->device);
-    (void)hipStreamSynchronize(ix->stream);
-    free_store(ix);
-    if (ix->d_scalars) (void)hipFree(ix->d_scalars);
-    ix->d_idrank.release(); ix->d_rank2row.release();
-    for (int w = 0; ix->wsv && w < 2; ++w) {
-        Workspace& W = ix->wsv[w];
-        W.for_each_buffer([](auto& buf) { buf.release(); });
-        if (W.h_flags) (void)hipHostFree(W.h_flags);
-        if (W.h_dstat) (void)hipHostFree(W.h_dstat);
-        if (W.h_io) (void)hipHostFree(W.h_io);
-        if (w == 1 && W.stream) { (void)hipStreamSynchronize(W.stream); (void)hipStreamDestroy(W.stream); }
-    }
-    delete[] ix->wsv;
-    if (ix->h_pairs) (void)hipHostFree(ix->h_pairs);
-    if (ix->h_pout) (void)hipHostFree(ix->h_pout);
-    if (ix->ev0) { (void)hipEventDestroy(ix->ev0); (void)hipEventDestroy(ix->ev1); }
-    if (ix->ev_order) (void)hipEventDestroy(ix->ev_order);
-    for (int t = 0; t < 2; ++t) if (ix->ev_pass[t]) (void)hipEventDestroy(ix->ev_pass[t]);
-    (void)hipStreamDestroy(ix->stream);
     delete ix;
 }
 
@@ -469,7 +446,7 @@ int vdb_flat_search_batch_device_begin(vdb_flat_index* ix, const float* d_querie
     if (rc == VDB_OK && !stream) {
         // the work went to the handle's own (non-blocking) stream: whatever the caller enqueues next on the null stream
         // -- the exchange -- must wait for it
-        if (!ix->ev_order && hipEventCreateWithFlags(&ix->ev_order, hipEventDisableTiming) != hipSuccess) rc = fail(VDB_ERR_DEVICE, "hipEventCreate failed");
+        rc = ix->ev_order.create(hipEventDisableTiming);
         if (rc == VDB_OK && (hipEventRecord(ix->ev_order, ix->stream) != hipSuccess || hipStreamWaitEvent(nullptr, ix->ev_order, 0) != hipSuccess))
             rc = fail(VDB_ERR_DEVICE, "stream ordering failed");
     }
@@ -590,8 +567,8 @@ static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq
         if ((rc = ensure_host_io(ix, o_c + cb))) return rc;
         Workspace* W = ix->cur;
         memcpy(W->h_io, queries, qb);
-        rc = search_device(ix, reinterpret_cast<const float*>(W->d_h_io), nq, dim, kdev, nullptr, 0, reinterpret_cast<uint64_t*>(W->d_h_io + o_i),
-                           reinterpret_cast<float*>(W->d_h_io + o_d), reinterpret_cast<uint32_t*>(W->d_h_io + o_c), nullptr);
+        rc = search_device(ix, reinterpret_cast<const float*>(W->h_io.d), nq, dim, kdev, nullptr, 0, reinterpret_cast<uint64_t*>(W->h_io.d + o_i),
+                           reinterpret_cast<float*>(W->h_io.d + o_d), reinterpret_cast<uint32_t*>(W->h_io.d + o_c), nullptr);
         if (rc) return rc;
         W = &ix->wsv[0];                                           // (search_device leaves ix->cur at workspace 0, the one it used)
         const uint64_t* h_ids = reinterpret_cast<const uint64_t*>(W->h_io + o_i);
@@ -852,10 +829,7 @@ int vdb_flat_set_profile(vdb_flat_index* ix, int on) {
     std::lock_guard<std::mutex> g(ix->mu);
     int rc = set_device(ix);
     if (rc) return rc;
-    if (on && !ix->ev0) {
-        HIP_TRY(hipEventCreate(&ix->ev0));
-        HIP_TRY(hipEventCreate(&ix->ev1));
-    }
+    if (on && ((rc = ix->ev0.create(hipEventDefault)) || (rc = ix->ev1.create(hipEventDefault)))) return rc;
     ix->profile = on != 0;
     return VDB_OK;
     });
@@ -1069,8 +1043,7 @@ int vdb_flat_set_sample_cache(vdb_flat_index* ix, int on) {
     if (!on && ix->d_sample16) {
         HIP_TRY(hipSetDevice(ix->device));
         HIP_TRY(hipDeviceSynchronize());
-        (void)hipFree(ix->d_sample16);
-        ix->d_sample16 = nullptr; ix->sample16_cap = 0; ix->sample16_n = ix->sample16_S = 0;
+        ix->d_sample16.release(); ix->sample16_n = ix->sample16_S = 0;
     }
     return VDB_OK;
     });
@@ -1086,18 +1059,18 @@ int vdb_flat_set_shadow(vdb_flat_index* ix, int on) {
     int rc;
     if ((rc = flush(ix))) return rc;
     if (!on) {
-        if (ix->d_rows16) { HIP_TRY(hipStreamSynchronize(ix->stream)); (void)hipFree(ix->d_rows16); }
-        ix->d_rows16 = nullptr; ix->shadow = false;
+        if (ix->d_rows16) { HIP_TRY(hipStreamSynchronize(ix->stream)); ix->d_rows16.release(); }
+        ix->shadow = false;
         return VDB_OK;
     }
     if (!ix->d_rows16 && ix->cap_rows) {
-        uint16_t* r16 = nullptr;
-        HIP_TRY(hipMalloc((void**)&r16, (size_t)ix->cap_rows * ix->ld * 2));
+        DevBuf<uint16_t> r16;
+        HIP_TRY(r16.alloc((size_t)ix->cap_rows * ix->ld));
         hipError_t e = hipMemsetAsync(r16, 0, (size_t)ix->cap_rows * ix->ld * 2, ix->stream);
         if (e == hipSuccess) { vdb::launch_rows_to_bf16(ix->d_rows, r16, ix->ld, 0, ix->n_uploaded, ix->stream); e = hipGetLastError(); }
         if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);
-        if (e != hipSuccess) { (void)hipFree(r16); return fail(VDB_ERR_DEVICE, "building the bf16 shadow failed: %s", hipGetErrorString(e)); }
-        ix->d_rows16 = r16;                                       // only a COMPLETE shadow is ever visible to a search
+        if (e != hipSuccess) return fail(VDB_ERR_DEVICE, "building the bf16 shadow failed: %s", hipGetErrorString(e));
+        ix->d_rows16 = std::move(r16);                                   // only a COMPLETE shadow is ever visible to a search
     }
     ix->shadow = true;
     return VDB_OK;
@@ -1250,21 +1223,9 @@ int vdb_flat_shard_stats(const vdb_flat_index* ix, uint64_t out[8]) {
 namespace vdb_internal {
 
 static int ensure_pair_buffers(vdb_flat_index* ix, size_t n_pairs, size_t n_out) {
-    if (n_pairs > ix->h_pairs_cap) {
-        if (ix->h_pairs) (void)hipHostFree(ix->h_pairs);
-        ix->h_pairs = nullptr; ix->h_pairs_cap = 0;
-        size_t cap = std::max<size_t>(n_pairs + n_pairs / 2, 4096);
-        HIP_TRY(hipHostMalloc((void**)&ix->h_pairs, cap * 2 * sizeof(uint32_t), hipHostMallocMapped));
-        ix->h_pairs_cap = cap;
-    }
-    if (n_out > ix->h_pout_cap) {
-        if (ix->h_pout) (void)hipHostFree(ix->h_pout);
-        ix->h_pout = nullptr; ix->h_pout_cap = 0;
-        size_t cap = std::max<size_t>(n_out + n_out / 2, 4096);
-        HIP_TRY(hipHostMalloc((void**)&ix->h_pout, cap * sizeof(float), hipHostMallocMapped));
-        ix->h_pout_cap = cap;
-    }
-    return VDB_OK;
+    int rc;
+    if ((rc = ix->h_pairs.ensure(2 * std::max<size_t>(n_pairs, 4096)))) return rc;
+    return ix->h_pout.ensure(std::max<size_t>(n_out, 4096));
 }
 
 int pairs_begin(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim) {
@@ -1304,9 +1265,7 @@ static int run_pair_eval(vdb_flat_index* ix, int mode, const uint32_t* a, const 
     if (n > 0xfffffff0ull) return fail(VDB_ERR_INVALID_ARGUMENT, "too many pairs");
     if (mode == 1 && (rc = flush(ix))) return rc;
     if ((rc = ensure_pair_buffers(ix, mode == 2 ? 1 : n, n))) return rc;
-    uint32_t *d_pairs = nullptr; float* d_out = nullptr;
-    HIP_TRY(hipHostGetDevicePointer((void**)&d_pairs, ix->h_pairs, 0));
-    HIP_TRY(hipHostGetDevicePointer((void**)&d_out, ix->h_pout, 0));
+    uint32_t* d_pairs = ix->h_pairs.d; float* d_out = ix->h_pout.d;
     if (mode != 2) {
         memcpy(ix->h_pairs, a, n * sizeof(uint32_t));
         memcpy(ix->h_pairs + n, b, n * sizeof(uint32_t));
@@ -1321,7 +1280,7 @@ static int run_pair_eval(vdb_flat_index* ix, int mode, const uint32_t* a, const 
     // a round trip, and a 1M-row build makes a million of them.  (Bounded: after 2 ms the stream is synchronised after all.)
     constexpr uint32_t SENTINEL = 0xffc0fee1u;
     const bool poll = mode == 1 && n <= 256;
-    volatile uint32_t* hw = reinterpret_cast<volatile uint32_t*>(ix->h_pout);
+    volatile uint32_t* hw = reinterpret_cast<volatile uint32_t*>(ix->h_pout.h);
     if (poll) for (size_t i = 0; i < n; ++i) hw[i] = SENTINEL;
     vdb::launch_pair_eval(pp, ix->stream);
     HIP_TRY(hipGetLastError());

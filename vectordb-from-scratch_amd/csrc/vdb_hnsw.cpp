@@ -32,6 +32,7 @@
 
 #include "../../include/vdb_flat.h"
 #include "../../include/vdb_hnsw.h"
+#include "vdb_device.h"
 #include "vdb_internal.h"
 #include "vdb_meta.h"
 #include "kernels.h"
@@ -144,21 +145,20 @@ struct vdb_hnsw_index {
     size_t count = 0, dim = 0;
     std::mutex mu;
     uint64_t stats[4] = {0, 0, 0, 0};
+    vdbi::Stream scan_stream;                                     // of the insert scans and walks; declared before every buffer, so destroyed after them
     // the graph mirrored in HBM for the device-resident search (kernels_hnsw.hip); rebuilt when the graph changed
     uint64_t graph_version = 1, mirror_version = 0;
-    uint32_t *d_row_of = nullptr, *d_level = nullptr, *d_nbr0 = nullptr, *d_cnt0 = nullptr, *d_up_off = nullptr, *d_nbrU = nullptr, *d_cntU = nullptr;
-    uint32_t *d_nbr0_row = nullptr, *d_nbrU_row = nullptr;
-    uint64_t* d_out_ids = nullptr; float* d_out_dists = nullptr; uint32_t *d_out_counts = nullptr, *d_fail = nullptr;
-    size_t out_cap = 0, out_nq_cap = 0;
+    vdbi::DevBuf<uint32_t> d_row_of, d_level, d_nbr0, d_up_off, d_nbrU, d_nbr0_row, d_nbrU_row;
+    vdbi::DevBuf<uint64_t> d_out_ids; vdbi::DevBuf<float> d_out_dists; vdbi::DevBuf<uint32_t> d_out_counts, d_fail;
     uint32_t mirror_ids = 0, stride0 = 0, strideU = 0, max_list = 0;
     uint64_t device_queries = 0, host_redone = 0;
     // pre-filtered searches: the id mask on the device and the layer-0 visited bitmaps of one filtered launch
-    uint64_t* d_mask = nullptr; size_t mask_cap = 0;
-    unsigned long long* d_eligible = nullptr;                     // vdb_hnsw_search_batch_filtered: present nodes the compiled mask admits
-    uint32_t* d_vis = nullptr; size_t vis_cap = 0;
+    vdbi::DevBuf<uint64_t> d_mask;
+    vdbi::DevBuf<unsigned long long> d_eligible;                  // vdb_hnsw_search_batch_filtered: present nodes the compiled mask admits
+    vdbi::DevBuf<uint32_t> d_vis;
     // batched insert scans: two mapped host matrices [SCAN_CHUNK][scan_ld] the scan kernel writes, a stream and events
-    float* h_scan[2] = {nullptr, nullptr}; float* d_scan[2] = {nullptr, nullptr}; size_t scan_ld = 0;
-    hipStream_t scan_stream = nullptr; hipEvent_t scan_ev[2] = {nullptr, nullptr};
+    vdbi::HostBuf<float> h_scan[2]; size_t scan_ld = 0;
+    vdbi::Event scan_ev[2];
     bool host_only = false; size_t host_threads = 0;              // vdb_hnsw_set_traversal
     size_t filter_scan = 0;                                       // vdb_hnsw_set_filter_scan: masks leaving at most this many present nodes are scanned exactly (0 = never)
     // incremental mirror: capacity in node ids / pooled upper lists, the upper-list offset of every node, and the nodes whose
@@ -166,11 +166,11 @@ struct vdb_hnsw_index {
     uint32_t cap_ids = 0, cap_upper = 0, n_upper_used = 0;
     std::vector<uint32_t> h_up_off; std::vector<uint8_t> dirty_flag; std::vector<uint32_t> dirty;
     bool mirror_full = true;                                      // the next sync rebuilds the whole mirror
-    uint32_t* h_stage = nullptr; uint32_t* d_stage = nullptr; size_t stage_words = 0;      // mapped staging of the scatter records
+    vdbi::HostBuf<uint32_t> h_stage;                              // mapped staging of the scatter records
     // speculative insert walks: per walk of a chunk its query row / level (host -> device) and its record (device -> host), mapped
-    uint32_t *h_wq = nullptr, *d_wq = nullptr;                    // [2][WALKS]: rows, levels
-    uint32_t *h_rec_row = nullptr, *d_rec_row = nullptr, *h_rec_cnt = nullptr, *d_rec_cnt = nullptr;
-    float *h_rec_d = nullptr, *d_rec_d = nullptr;
+    vdbi::HostBuf<uint32_t> h_wq;                                 // [2][WALKS]: rows, levels
+    vdbi::HostBuf<uint32_t> h_rec_row, h_rec_cnt;
+    vdbi::HostBuf<float> h_rec_d;
     bool spec_build = true;                                       // vdb_hnsw_set_build: 0 = the row-scan build of round 2 (A/B, tests)
     uint64_t bstats[8] = {0};                                     // vdb_hnsw_build_stats
     double btimes[4] = {0, 0, 0, 0};                              // vdb_hnsw_build_times
@@ -272,19 +272,7 @@ struct LayerSearch {
     }
 };
 
-// No C++ exception may cross the C ABI (std::bad_alloc from nodes.resize(id + 1) on a sparse id, vector growth in a search).
-template <class F> int guarded(F&& body) noexcept {
-    try { return body(); }
-    catch (const std::bad_alloc&) { return vdb_internal::set_error(VDB_ERR_DEVICE, "internal error: out of host memory"); }
-    catch (const std::exception& e) { return vdb_internal::set_error(VDB_ERR_DEVICE, e.what()); }
-    catch (...) { return vdb_internal::set_error(VDB_ERR_DEVICE, "internal error: unknown C++ exception"); }
-}
-
-#define HN_TRY(expr)                                                                                       \
-    do {                                                                                                   \
-        hipError_t e_ = (expr);                                                                            \
-        if (e_ != hipSuccess) return vdb_internal::set_error(VDB_ERR_DEVICE, hipGetErrorString(e_));       \
-    } while (0)
+using vdbi::guarded;     // (std::bad_alloc from nodes.resize(id + 1) on a sparse id, vector growth in a search)
 
 int zero_norm_error() {
     return vdb_internal::zero_vector_error();
@@ -443,19 +431,11 @@ int add_fresh_rows(Graph* g, const uint64_t* ids, uint64_t first_id, const float
     // before the host walks chunk c, so the passes over the rows and their transfer hide behind the sequential walks.
     constexpr size_t CHUNK = 128;
     const size_t need_ld = ((size_t)rowv[n - 1] + 1023) & ~(size_t)1023;
-    if (!g->scan_stream) {
-        HN_TRY(hipStreamCreateWithFlags(&g->scan_stream, hipStreamNonBlocking));
-        HN_TRY(hipEventCreateWithFlags(&g->scan_ev[0], hipEventDisableTiming));
-        HN_TRY(hipEventCreateWithFlags(&g->scan_ev[1], hipEventDisableTiming));
-    }
+    if ((rc = g->scan_stream.create(hipStreamNonBlocking)) || (rc = g->scan_ev[0].create(hipEventDisableTiming)) || (rc = g->scan_ev[1].create(hipEventDisableTiming))) return rc;
     if (need_ld > g->scan_ld) {
         const size_t ld_new = std::max(need_ld, g->scan_ld + g->scan_ld / 2);
-        for (int t = 0; t < 2; ++t) {
-            if (g->h_scan[t]) (void)hipHostFree(g->h_scan[t]);
-            g->h_scan[t] = nullptr;
-            HN_TRY(hipHostMalloc((void**)&g->h_scan[t], CHUNK * ld_new * sizeof(float), hipHostMallocMapped));
-            HN_TRY(hipHostGetDevicePointer((void**)&g->d_scan[t], g->h_scan[t], 0));
-        }
+        g->scan_ld = 0;
+        for (int t = 0; t < 2; ++t) HIP_TRY(g->h_scan[t].alloc(CHUNK * ld_new));
         g->scan_ld = ld_new;
     }
     const size_t n_chunks = (n + CHUNK - 1) / CHUNK;
@@ -467,12 +447,12 @@ int add_fresh_rows(Graph* g, const uint64_t* ids, uint64_t first_id, const float
             sp.rows = dv.rows; sp.ld = dv.ld; sp.dim = dv.dim; sp.nd = dv.nd; sp.metric = dv.metric; sp.mark = vdb_internal::ZERO_NORM_MARK;
             sp.nq = (uint32_t)std::min<size_t>(16, nc - q0);
             for (uint32_t j = 0; j < sp.nq; ++j) sp.qrow[j] = rowv[c0 + q0 + j];
-            sp.n_scan = n_scan; sp.out = g->d_scan[c & 1] + q0 * g->scan_ld; sp.ldm = g->scan_ld;
+            sp.n_scan = n_scan; sp.out = g->h_scan[c & 1].d + q0 * g->scan_ld; sp.ldm = g->scan_ld;
             vdb::launch_scan_rows(sp, g->scan_stream);
             g->stats[0] += (uint64_t)sp.nq * n_scan; g->stats[1]++;
         }
-        HN_TRY(hipGetLastError());
-        HN_TRY(hipEventRecord(g->scan_ev[c & 1], g->scan_stream));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(g->scan_ev[c & 1], g->scan_stream));
         return VDB_OK;
     };
     auto drain = [&]() { (void)hipStreamSynchronize(g->scan_stream); };
@@ -583,8 +563,6 @@ int add_rows(Graph* g, const uint64_t* ids, uint64_t first_id, const float* rows
     return build_run(n);
 }
 
-void free_mirror(vdb_hnsw_index* g);
-
 }  // namespace
 
 extern "C" {
@@ -610,11 +588,10 @@ int vdb_hnsw_create(int metric, size_t m, size_t ef_construction, size_t ef_sear
 
 void vdb_hnsw_destroy(vdb_hnsw_index* g) {
     if (!g) return;
-    free_mirror(g);
-    if (g->scan_stream) { (void)hipStreamSynchronize(g->scan_stream); (void)hipStreamDestroy(g->scan_stream); }
-    for (int t = 0; t < 2; ++t) { if (g->h_scan[t]) (void)hipHostFree(g->h_scan[t]); if (g->scan_ev[t]) (void)hipEventDestroy(g->scan_ev[t]); }
-    vdb_flat_destroy(g->flat);
-    delete g;
+    if (g->scan_stream) (void)hipStreamSynchronize(g->scan_stream);
+    vdb_flat_index* flat = g->flat;
+    delete g;                                                     // the mirror, the scratch buffers, then the scan stream
+    vdb_flat_destroy(flat);
 }
 
 int vdb_hnsw_add(vdb_hnsw_index* g, uint64_t id, const float* v, size_t dim, long level) {
@@ -782,21 +759,6 @@ int search_host(vdb_hnsw_index* g, const float* queries, size_t nq, size_t dim, 
     return VDB_OK;
 }
 
-void free_mirror(vdb_hnsw_index* g) {
-    for (uint32_t** p : {&g->d_row_of, &g->d_level, &g->d_nbr0, &g->d_cnt0, &g->d_up_off, &g->d_nbrU, &g->d_cntU, &g->d_nbr0_row, &g->d_nbrU_row, &g->d_out_counts, &g->d_fail, &g->d_vis})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
-    if (g->d_mask) { (void)hipFree(g->d_mask); g->d_mask = nullptr; }
-    if (g->d_eligible) { (void)hipFree(g->d_eligible); g->d_eligible = nullptr; }
-    g->mask_cap = g->vis_cap = 0;
-    if (g->d_out_ids) { (void)hipFree(g->d_out_ids); g->d_out_ids = nullptr; }
-    if (g->d_out_dists) { (void)hipFree(g->d_out_dists); g->d_out_dists = nullptr; }
-    g->out_cap = g->out_nq_cap = 0;
-    g->mirror_version = 0;
-    g->mirror_full = true; g->cap_ids = g->cap_upper = 0;
-    for (void* hp : {(void*)g->h_stage, (void*)g->h_wq, (void*)g->h_rec_cnt, (void*)g->h_rec_row, (void*)g->h_rec_d}) if (hp) (void)hipHostFree(hp);
-    g->h_stage = nullptr; g->stage_words = 0; g->h_wq = nullptr; g->h_rec_cnt = nullptr; g->h_rec_row = nullptr; g->h_rec_d = nullptr;
-}
-
 // Mirrors the graph into HBM (kernels.h HnswSearchParams): per node id its device row (0xffffffff = absent), level,
 // layer-0 list (stride m_max0) and the offset of its upper-layer lists (stride m) in a pooled array; every list entry carries
 // the device row of the neighbour beside its id.  A FULL rebuild allocates capacity beyond the present graph (reserve_*); after
@@ -825,14 +787,8 @@ int sync_mirror(vdb_hnsw_index* g, hipStream_t s, size_t reserve_ids, size_t res
         for (uint32_t id : g->dirty) if (g->nodes[id].present) nU += g->nodes[id].level;
         const size_t w0 = 4 + 2 * (size_t)stride0, wU = 1 + 2 * (size_t)strideU;
         const size_t words = g->dirty.size() * w0 + nU * wU;
-        if (words > g->stage_words) {
-            if (g->h_stage) (void)hipHostFree(g->h_stage);
-            g->h_stage = g->d_stage = nullptr; g->stage_words = 0;
-            const size_t cap = words + words / 2 + 4096;
-            HN_TRY(hipHostMalloc((void**)&g->h_stage, cap * 4, hipHostMallocMapped));
-            HN_TRY(hipHostGetDevicePointer((void**)&g->d_stage, g->h_stage, 0));
-            g->stage_words = cap;
-        }
+        int rc;
+        if ((rc = g->h_stage.ensure(words))) return rc;
         uint32_t* r0 = g->h_stage;
         uint32_t* rU = g->h_stage + g->dirty.size() * w0;
         uint32_t cU = 0;
@@ -865,11 +821,11 @@ int sync_mirror(vdb_hnsw_index* g, hipStream_t s, size_t reserve_ids, size_t res
         // the scatter kernel writes where the records say: nothing is launched unless every node id is inside the mirror's id
         // arrays and every upper-list slot inside the slots handed out so far (the next sync rebuilds the mirror as a whole)
         if (bad) { g->mirror_full = true; return vdb_internal::set_error(VDB_ERR_DEVICE, "internal error: a mirror record lies outside the mirror"); }
-        vdb::HnswScatterParams sp{g->d_stage, (uint32_t)g->dirty.size(), g->d_stage + g->dirty.size() * w0, cU,
+        vdb::HnswScatterParams sp{g->h_stage.d, (uint32_t)g->dirty.size(), g->h_stage.d + g->dirty.size() * w0, cU,
                                   g->d_row_of, g->d_level, g->d_up_off, g->d_nbr0, g->d_nbr0_row, stride0, g->d_nbrU, g->d_nbrU_row, strideU};
         vdb::launch_hnsw_scatter(sp, s);
-        HN_TRY(hipGetLastError());
-        HN_TRY(hipStreamSynchronize(s));                               // the staging memory is reused by the next sync
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));                               // the staging memory is reused by the next sync
         g->dirty.clear();
         g->mirror_ids = n;
         g->mirror_version = g->graph_version;
@@ -899,19 +855,25 @@ int sync_mirror(vdb_hnsw_index* g, hipStream_t s, size_t reserve_ids, size_t res
         off += nd.level;
     }
     g->n_upper_used = off;
-    for (uint32_t** p : {&g->d_row_of, &g->d_level, &g->d_nbr0, &g->d_cnt0, &g->d_up_off, &g->d_nbrU, &g->d_cntU, &g->d_nbr0_row, &g->d_nbrU_row})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
-    auto up = [&](uint32_t** dst, const std::vector<uint32_t>& v) -> int {
-        HN_TRY(hipMalloc((void**)dst, std::max<size_t>(v.size(), 1) * 4));
-        if (!v.empty()) HN_TRY(hipMemcpyAsync(*dst, v.data(), v.size() * 4, hipMemcpyHostToDevice, s));
+    // built in locals and swapped in, together with the capacities and strides that describe it, once every array is there: a
+    // failure leaves the old mirror whole (and due for this rebuild again: h_up_off already describes the new one)
+    g->mirror_full = true;
+    vdbi::DevBuf<uint32_t> b_row_of, b_level, b_nbr0, b_up_off, b_nbrU, b_nbr0_row, b_nbrU_row;
+    auto up = [&](vdbi::DevBuf<uint32_t>& dst, const std::vector<uint32_t>& v) -> int {
+        HIP_TRY(dst.alloc(std::max<size_t>(v.size(), 1)));
+        if (!v.empty()) HIP_TRY(hipMemcpyAsync(dst, v.data(), v.size() * 4, hipMemcpyHostToDevice, s));
         return VDB_OK;
     };
     int rc;
-    if ((rc = up(&g->d_row_of, row_of)) || (rc = up(&g->d_level, level)) || (rc = up(&g->d_nbr0, nbr0)) ||
-        (rc = up(&g->d_up_off, up_off)) || (rc = up(&g->d_nbrU, nbrU)) ||
-        (rc = up(&g->d_nbr0_row, nbr0_row)) || (rc = up(&g->d_nbrU_row, nbrU_row)))
+    if ((rc = up(b_row_of, row_of)) || (rc = up(b_level, level)) || (rc = up(b_nbr0, nbr0)) ||
+        (rc = up(b_up_off, up_off)) || (rc = up(b_nbrU, nbrU)) ||
+        (rc = up(b_nbr0_row, nbr0_row)) || (rc = up(b_nbrU_row, nbrU_row))) {
+        (void)hipStreamSynchronize(s);                                 // (a copy may still read a staging vector)
         return rc;
-    HN_TRY(hipStreamSynchronize(s));                                   // the staging vectors go out of scope
+    }
+    HIP_TRY(hipStreamSynchronize(s));                                   // the staging vectors go out of scope
+    g->d_row_of = std::move(b_row_of); g->d_level = std::move(b_level); g->d_nbr0 = std::move(b_nbr0); g->d_up_off = std::move(b_up_off);
+    g->d_nbrU = std::move(b_nbrU); g->d_nbr0_row = std::move(b_nbr0_row); g->d_nbrU_row = std::move(b_nbrU_row);
     g->cap_ids = cap_ids; g->cap_upper = cap_up;
     g->mirror_ids = n; g->stride0 = stride0; g->strideU = strideU; g->max_list = std::max(stride0, strideU);
     g->mirror_version = g->graph_version;
@@ -960,32 +922,12 @@ int build_speculative(Graph* g, const uint64_t* ids, uint64_t first_id, size_t n
     vdb_internal::DeviceView dv;
     if ((rc = vdb_internal::device_view(g->flat, &dv))) return rc;
     hipStream_t s = (hipStream_t)dv.stream;
-    if (!g->h_wq) {                                              // two sets of everything a walk launch touches: block b + 1 is walked while b is replayed
-        HN_TRY(hipHostMalloc((void**)&g->h_wq, 2 * 2 * WALKS * 4, hipHostMallocMapped));
-        HN_TRY(hipHostGetDevicePointer((void**)&g->d_wq, g->h_wq, 0));
-        HN_TRY(hipHostMalloc((void**)&g->h_rec_cnt, 2 * WALKS * 4, hipHostMallocMapped));
-        HN_TRY(hipHostGetDevicePointer((void**)&g->d_rec_cnt, g->h_rec_cnt, 0));
-        HN_TRY(hipHostMalloc((void**)&g->h_rec_row, (size_t)2 * WALKS * REC_CAP * 4, hipHostMallocMapped));
-        HN_TRY(hipHostGetDevicePointer((void**)&g->d_rec_row, g->h_rec_row, 0));
-        HN_TRY(hipHostMalloc((void**)&g->h_rec_d, (size_t)2 * WALKS * REC_CAP * 4, hipHostMallocMapped));
-        HN_TRY(hipHostGetDevicePointer((void**)&g->d_rec_d, g->h_rec_d, 0));
-    }
-    if (!g->scan_stream) {
-        HN_TRY(hipStreamCreateWithFlags(&g->scan_stream, hipStreamNonBlocking));
-        HN_TRY(hipEventCreateWithFlags(&g->scan_ev[0], hipEventDisableTiming));
-        HN_TRY(hipEventCreateWithFlags(&g->scan_ev[1], hipEventDisableTiming));
-    }
+    // two sets of everything a walk launch touches: block b + 1 is walked while b is replayed
+    if ((rc = g->h_wq.ensure(2 * 2 * WALKS)) || (rc = g->h_rec_cnt.ensure(2 * WALKS)) ||
+        (rc = g->h_rec_row.ensure((size_t)2 * WALKS * REC_CAP)) || (rc = g->h_rec_d.ensure((size_t)2 * WALKS * REC_CAP))) return rc;
+    if ((rc = g->scan_stream.create(hipStreamNonBlocking)) || (rc = g->scan_ev[0].create(hipEventDisableTiming)) || (rc = g->scan_ev[1].create(hipEventDisableTiming))) return rc;
     const hipStream_t sw = g->scan_stream;
-    if (!g->d_fail || g->out_nq_cap < WALKS) {
-        if (g->d_fail) (void)hipFree(g->d_fail);
-        if (g->d_out_counts) (void)hipFree(g->d_out_counts);
-        g->d_fail = g->d_out_counts = nullptr;
-        HN_TRY(hipMalloc((void**)&g->d_fail, WALKS * 4));
-        HN_TRY(hipMalloc((void**)&g->d_out_counts, WALKS * 4));
-        if (g->d_out_ids) { (void)hipFree(g->d_out_ids); g->d_out_ids = nullptr; }
-        if (g->d_out_dists) { (void)hipFree(g->d_out_dists); g->d_out_dists = nullptr; }
-        g->out_cap = 0; g->out_nq_cap = WALKS;
-    }
+    if ((rc = g->d_fail.ensure(WALKS)) || (rc = g->d_out_counts.ensure(WALKS))) return rc;
     // room in the mirror for the whole batch: ids up to the largest of the batch, upper lists for its levels
     size_t max_id = 0, up_need = 0;
     for (size_t i = 0; i < n; ++i) { max_id = std::max<size_t>(max_id, ids ? ids[i] : first_id + i); up_need += lev[i]; }
@@ -1031,14 +973,14 @@ int build_speculative(Graph* g, const uint64_t* ids, uint64_t first_id, size_t n
             hp.stride0 = g->stride0; hp.up_off = g->d_up_off; hp.nbrU = g->d_nbrU; hp.nbrU_row = g->d_nbrU_row; hp.cntU = nullptr; hp.strideU = g->strideU;
             hp.entry_point = (uint32_t)g->ep; hp.max_level = (uint32_t)g->max_level; hp.ef = (uint32_t)g->ef_construction; hp.k = 0;
             hp.out_ids = nullptr; hp.out_dists = nullptr; hp.out_counts = g->d_out_counts; hp.fail = g->d_fail; hp.status = dv.status;
-            hp.qrow = g->d_wq + (size_t)par * 2 * WALKS; hp.qlevel = hp.qrow + WALKS;
-            hp.rec_row = g->d_rec_row + (size_t)par * WALKS * REC_CAP; hp.rec_d = g->d_rec_d + (size_t)par * WALKS * REC_CAP;
-            hp.rec_cnt = g->d_rec_cnt + (size_t)par * WALKS; hp.rec_cap = REC_CAP; hp.rec_zero_mark = vdb_internal::ZERO_NORM_MARK;
+            hp.qrow = g->h_wq.d + (size_t)par * 2 * WALKS; hp.qlevel = hp.qrow + WALKS;
+            hp.rec_row = g->h_rec_row.d + (size_t)par * WALKS * REC_CAP; hp.rec_d = g->h_rec_d.d + (size_t)par * WALKS * REC_CAP;
+            hp.rec_cnt = g->h_rec_cnt.d + (size_t)par * WALKS; hp.rec_cap = REC_CAP; hp.rec_zero_mark = vdb_internal::ZERO_NORM_MARK;
             vdb::launch_hnsw_search(hp, (uint32_t)nc, sw);
-            HN_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             g->stats[1]++;
         }
-        HN_TRY(hipEventRecord(g->scan_ev[par], sw));
+        HIP_TRY(hipEventRecord(g->scan_ev[par], sw));
         return VDB_OK;
     };
     auto clock = [] { return std::chrono::steady_clock::now(); };
@@ -1056,7 +998,7 @@ int build_speculative(Graph* g, const uint64_t* ids, uint64_t first_id, size_t n
         const size_t p0 = b ? c0 - WALKS : 0, pn = b ? WALKS : 0;       // the block before this one (of this call)
         // ---- this block's walks (launched a block ago) are done; the next block's start on the graph as it is now
         const auto t_block = clock();
-        HN_TRY(hipEventSynchronize(g->scan_ev[par]));
+        HIP_TRY(hipEventSynchronize(g->scan_ev[par]));
         const auto t_walked = clock();
         if (b + 1 < n_blocks) {
             if ((rc = sync_mirror(g, s, max_id + 1, up_have + up_need))) return rc;
@@ -1149,17 +1091,6 @@ int build_speculative(Graph* g, const uint64_t* ids, uint64_t first_id, size_t n
     return VDB_OK;
 }
 
-// g->d_mask with room for `words` 64-bit words (at least one)
-int ensure_mask(vdb_hnsw_index* g, size_t words) {
-    if (words > g->mask_cap) {
-        if (g->d_mask) (void)hipFree(g->d_mask);
-        g->d_mask = nullptr; g->mask_cap = 0;
-        HN_TRY(hipMalloc((void**)&g->d_mask, words * 8));
-        g->mask_cap = words;
-    }
-    return VDB_OK;
-}
-
 // device-resident search of the whole batch in one launch (pre-filtered: one per hnsw_filter_launch_queries queries); queries
 // whose walk overflowed the kernel's LDS structures are listed in `redo`.  resident: the mask is not id_mask but what
 // present_mask_device left in g->d_mask (mask_bits bits, already clamped to the mirror's ids) behind a pairs_begin of these queries
@@ -1172,41 +1103,25 @@ int search_device(vdb_hnsw_index* g, const float* queries, size_t nq, size_t dim
     hipStream_t s = (hipStream_t)dv.stream;
     if ((rc = upload_mirror(g, s))) return rc;
     const size_t need = nq * std::max<size_t>(k, 1);
-    if (need > g->out_cap || nq > g->out_nq_cap) {
-        if (g->d_out_ids) (void)hipFree(g->d_out_ids);
-        if (g->d_out_dists) (void)hipFree(g->d_out_dists);
-        if (g->d_out_counts) (void)hipFree(g->d_out_counts);
-        if (g->d_fail) (void)hipFree(g->d_fail);
-        g->d_out_ids = nullptr; g->d_out_dists = nullptr; g->d_out_counts = g->d_fail = nullptr; g->out_cap = g->out_nq_cap = 0;
-        HN_TRY(hipMalloc((void**)&g->d_out_ids, need * 8));
-        HN_TRY(hipMalloc((void**)&g->d_out_dists, need * 4));
-        HN_TRY(hipMalloc((void**)&g->d_out_counts, nq * 4));
-        HN_TRY(hipMalloc((void**)&g->d_fail, nq * 4));
-        g->out_cap = need; g->out_nq_cap = nq;
-    }
-    HN_TRY(hipMemsetAsync(dv.status, 0, 16, s));
+    if ((rc = g->d_out_ids.ensure(need)) || (rc = g->d_out_dists.ensure(need)) || (rc = g->d_out_counts.ensure(nq)) || (rc = g->d_fail.ensure(nq))) return rc;
+    HIP_TRY(hipMemsetAsync(dv.status, 0, 16, s));
     vdb::HnswSearchParams hp{};
     hp.rows = dv.rows; hp.ld = dv.ld; hp.dim = dv.dim; hp.nd = dv.nd; hp.metric = dv.metric; hp.qp = dv.qp; hp.qnorm = dv.qnorm;
-    hp.row_of = g->d_row_of; hp.level = g->d_level; hp.n_ids = g->mirror_ids; hp.nbr0 = g->d_nbr0; hp.nbr0_row = g->d_nbr0_row; hp.cnt0 = g->d_cnt0;
-    hp.stride0 = g->stride0; hp.up_off = g->d_up_off; hp.nbrU = g->d_nbrU; hp.nbrU_row = g->d_nbrU_row; hp.cntU = g->d_cntU; hp.strideU = g->strideU;
+    hp.row_of = g->d_row_of; hp.level = g->d_level; hp.n_ids = g->mirror_ids; hp.nbr0 = g->d_nbr0; hp.nbr0_row = g->d_nbr0_row; hp.cnt0 = nullptr;
+    hp.stride0 = g->stride0; hp.up_off = g->d_up_off; hp.nbrU = g->d_nbrU; hp.nbrU_row = g->d_nbrU_row; hp.cntU = nullptr; hp.strideU = g->strideU;
     hp.entry_point = (uint32_t)g->ep; hp.max_level = (uint32_t)g->max_level; hp.ef = (uint32_t)ef_actual; hp.k = (uint32_t)k;
     hp.out_ids = g->d_out_ids; hp.out_dists = g->d_out_dists; hp.out_counts = g->d_out_counts; hp.fail = g->d_fail; hp.status = dv.status;
     if (!id_mask && !resident) {
         vdb::launch_hnsw_search(hp, (uint32_t)nq, s);
-        HN_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     } else {
         // the mask once per call, clamped to the mirror's ids (bits beyond it name no node); the visited bitmaps per launch
         const uint32_t bits = (uint32_t)std::min<size_t>(mask_bits, g->mirror_ids);
-        if ((rc = ensure_mask(g, std::max<size_t>((bits + 63) / 64, 1)))) return rc;
-        if (bits && !resident) HN_TRY(hipMemcpyAsync(g->d_mask, id_mask, (size_t)(bits + 63) / 64 * 8, hipMemcpyHostToDevice, s));
+        if ((rc = g->d_mask.ensure(std::max<size_t>((bits + 63) / 64, 1)))) return rc;
+        if (bits && !resident) HIP_TRY(hipMemcpyAsync(g->d_mask, id_mask, (size_t)(bits + 63) / 64 * 8, hipMemcpyHostToDevice, s));
         const size_t per_launch = std::min<size_t>(nq, vdb::hnsw_filter_launch_queries(g->mirror_ids));
         const size_t vis_bytes = vdb::hnsw_filter_vis_bytes(g->mirror_ids, (uint32_t)per_launch);
-        if (vis_bytes > g->vis_cap) {
-            if (g->d_vis) (void)hipFree(g->d_vis);
-            g->d_vis = nullptr; g->vis_cap = 0;
-            HN_TRY(hipMalloc((void**)&g->d_vis, vis_bytes));
-            g->vis_cap = vis_bytes;
-        }
+        if ((rc = g->d_vis.ensure((vis_bytes + 3) / 4))) return rc;
         hp.id_mask = g->d_mask; hp.mask_bits = bits; hp.vis_bits = g->d_vis;
         for (size_t q0 = 0; q0 < nq; q0 += per_launch) {
             const size_t n1 = std::min(per_launch, nq - q0);
@@ -1214,19 +1129,19 @@ int search_device(vdb_hnsw_index* g, const float* queries, size_t nq, size_t dim
             hq.qp = dv.qp + q0 * dv.ld; hq.qnorm = dv.qnorm + q0;
             hq.out_ids = g->d_out_ids + q0 * k; hq.out_dists = g->d_out_dists + q0 * k; hq.out_counts = g->d_out_counts + q0; hq.fail = g->d_fail + q0;
             vdb::launch_hnsw_search(hq, (uint32_t)n1, s);
-            HN_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
     }
     std::vector<uint32_t> cnt(nq), fail(nq);
     uint32_t status = 0;
-    HN_TRY(hipMemcpyAsync(cnt.data(), g->d_out_counts, nq * 4, hipMemcpyDeviceToHost, s));
-    HN_TRY(hipMemcpyAsync(fail.data(), g->d_fail, nq * 4, hipMemcpyDeviceToHost, s));
-    HN_TRY(hipMemcpyAsync(&status, dv.status, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(cnt.data(), g->d_out_counts, nq * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(fail.data(), g->d_fail, nq * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&status, dv.status, 4, hipMemcpyDeviceToHost, s));
     if (k) {
-        HN_TRY(hipMemcpyAsync(out_ids, g->d_out_ids, nq * k * 8, hipMemcpyDeviceToHost, s));
-        HN_TRY(hipMemcpyAsync(out_dists, g->d_out_dists, nq * k * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_ids, g->d_out_ids, nq * k * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_dists, g->d_out_dists, nq * k * 4, hipMemcpyDeviceToHost, s));
     }
-    HN_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipStreamSynchronize(s));
     g->stats[1]++;
     if (status & 2u) return zero_norm_error();                     // ST_ZERO_QUERY
     for (size_t b = 0; b < nq; ++b) {
@@ -1283,17 +1198,17 @@ int present_mask_device(vdb_hnsw_index* g, const vdb_meta_mask* cm, const float*
     if ((rc = vdb_internal::device_view(g->flat, &dv))) return rc;
     hipStream_t s = (hipStream_t)dv.stream;
     if ((rc = upload_mirror(g, s))) return rc;
-    HN_TRY(hipStreamWaitEvent(s, cm->done, 0));
+    HIP_TRY(hipStreamWaitEvent(s, cm->done, 0));
     const uint32_t nb = (uint32_t)std::min<size_t>(cm->bits, g->mirror_ids);
-    if ((rc = ensure_mask(g, std::max<size_t>(((size_t)nb + 63) / 64, 1)))) return rc;
-    if (!g->d_eligible) HN_TRY(hipMalloc((void**)&g->d_eligible, 8));
-    HN_TRY(hipMemsetAsync(g->d_eligible, 0, 8, s));
+    if ((rc = g->d_mask.ensure(std::max<size_t>(((size_t)nb + 63) / 64, 1)))) return rc;
+    if ((rc = g->d_eligible.ensure(1))) return rc;
+    HIP_TRY(hipMemsetAsync(g->d_eligible, 0, 8, s));
     vdb::HnswPresentMaskParams pp{cm->d_words, (uint64_t)((cm->bits + 63) / 64), g->d_row_of, g->mirror_ids, nb, g->d_mask, g->d_eligible};
     vdb::launch_hnsw_present_mask(pp, s);
-    HN_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     unsigned long long cnt = 0;
-    HN_TRY(hipMemcpyAsync(&cnt, g->d_eligible, 8, hipMemcpyDeviceToHost, s));
-    HN_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpyAsync(&cnt, g->d_eligible, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     *bits = nb; *eligible = cnt;
     return VDB_OK;
 }
@@ -1336,8 +1251,8 @@ int search_batch_common(vdb_hnsw_index* g, const float* queries, size_t nq, size
             vdb_internal::DeviceView dv;
             int rc2;
             if ((rc2 = vdb_internal::device_view(g->flat, &dv))) return rc2;
-            HN_TRY(hipMemcpyAsync(hmask.data(), g->d_mask, words * 8, hipMemcpyDeviceToHost, (hipStream_t)dv.stream));
-            HN_TRY(hipStreamSynchronize((hipStream_t)dv.stream));
+            HIP_TRY(hipMemcpyAsync(hmask.data(), g->d_mask, words * 8, hipMemcpyDeviceToHost, (hipStream_t)dv.stream));
+            HIP_TRY(hipStreamSynchronize((hipStream_t)dv.stream));
         }
         id_mask = hmask.data();
         return VDB_OK;
@@ -1350,8 +1265,8 @@ int search_batch_common(vdb_hnsw_index* g, const float* queries, size_t nq, size
             vdb_internal::DeviceView dv;
             if ((rc = vdb_internal::device_view(g->flat, &dv))) return rc;
             std::vector<float> qn(nq);
-            HN_TRY(hipMemcpyAsync(qn.data(), dv.qnorm, nq * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)dv.stream));
-            HN_TRY(hipStreamSynchronize((hipStream_t)dv.stream));
+            HIP_TRY(hipMemcpyAsync(qn.data(), dv.qnorm, nq * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)dv.stream));
+            HIP_TRY(hipStreamSynchronize((hipStream_t)dv.stream));
             for (float x : qn) if (x == 0.0f) return zero_norm_error();
         }
         return VDB_OK;
@@ -1441,8 +1356,8 @@ int vdb_hnsw_debug_present_mask(vdb_hnsw_index* g, const vdb_meta_mask* mask, ui
     if (words) {
         vdb_internal::DeviceView dv;
         if ((rc = vdb_internal::device_view(g->flat, &dv))) return rc;
-        HN_TRY(hipMemcpyAsync(out_words, g->d_mask, words * 8, hipMemcpyDeviceToHost, (hipStream_t)dv.stream));
-        HN_TRY(hipStreamSynchronize((hipStream_t)dv.stream));
+        HIP_TRY(hipMemcpyAsync(out_words, g->d_mask, words * 8, hipMemcpyDeviceToHost, (hipStream_t)dv.stream));
+        HIP_TRY(hipStreamSynchronize((hipStream_t)dv.stream));
     }
     *out_nwords = words; *out_count = eligible;
     return VDB_OK;

@@ -13,6 +13,7 @@
 #include <functional>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -21,54 +22,17 @@
 
 #include "../../include/vdb_flat.h"
 #include "kernels.h"
+#include "vdb_device.h"
 #include "vdb_internal.h"
 
 namespace vdbi {
 
-// ---- thread-local last error (vdb_last_error) and the exception guard of every extern "C" body
+// ---- thread-local last error (vdb_last_error); the exception guard of every extern "C" body is in vdb_device.h
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 int fail_dim(size_t expected, size_t actual);
 int fail_zero_vector();   // distance.rs:51-55: a zero-norm vector under Cosine fails the whole search
 int fail_nan();           // flat_index.rs:62: the reference panics on a NaN distance
-int guard_fail(const char* what);
 void last_error(std::string* msg, size_t* expected, size_t* actual);
-
-// No C++ exception may cross the C ABI (ctypes, a Rust FFI caller: undefined behaviour or abort).  Every extern "C" entry
-// point that can allocate runs its body through this.
-template <class F> int guarded(F&& body) noexcept {
-    try { return body(); }
-    catch (const std::bad_alloc&) { return guard_fail("out of host memory"); }
-    catch (const std::exception& e) { return guard_fail(e.what()); }
-    catch (...) { return guard_fail("unknown C++ exception"); }
-}
-
-#define HIP_TRY(expr)                                                                           \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return ::vdbi::fail(VDB_ERR_DEVICE, "HIP error %d (%s) at %s:%d: %s", (int)e_,      \
-                                hipGetErrorString(e_), __FILE__, __LINE__, #expr);              \
-    } while (0)
-
-template <typename T> struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    int ensure(size_t want) {
-        if (want <= n) return VDB_OK;
-        size_t cap = std::max(want, n + n / 2);
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        HIP_TRY(hipMalloc((void**)&p, cap * sizeof(T)));
-        n = cap;
-        return VDB_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
 
 inline uint32_t round_up(uint32_t x, uint32_t m) { return (x + m - 1) / m * m; }
 inline uint32_t pow2_ceil(uint64_t x) {
@@ -98,12 +62,12 @@ struct Workspace {
     vdbi::DevBuf<uint64_t> w2_outi, w2_cand;
     vdbi::DevBuf<uint16_t> w2_qb;
     vdbi::DevBuf<uint32_t> w2_outc, w2_flags, w2_qidx;
-    uint32_t* h_flags = nullptr; size_t h_flags_n = 0;
+    vdbi::HostBuf<uint32_t> h_flags{hipHostMallocDefault};
     // the direct path of small indexes (search_direct): a device status word known to be zero between searches, and MAPPED host
     // memory -- the kernels write results and status straight into it (h_io: the host-pointer entry point's queries and outputs)
     vdbi::DevBuf<uint32_t> w_dstat; bool dstat_ready = false;
-    uint32_t* h_dstat = nullptr; uint32_t* d_h_dstat = nullptr;       // [16] host view / device view
-    char* h_io = nullptr; char* d_h_io = nullptr; size_t h_io_bytes = 0;
+    vdbi::HostBuf<uint32_t> h_dstat;                                  // [16] host view / device view
+    vdbi::HostBuf<char> h_io;
     bool status_dirty = true; uint32_t* status_buf = nullptr;   // device status block known to be zero?
     // a search between its two halves (search_part1 enqueues the first tier, search_part2 reads its flags and runs
     // the fallback tiers): vdb_flat_search_batch_device_begin / _finish keep the handle locked in between
@@ -117,15 +81,8 @@ struct Workspace {
         std::chrono::steady_clock::time_point t_entry;
     } ctx;
     uint64_t stats[16] = {0};
-    hipStream_t stream = nullptr;                           // this context's own stream (used when the caller passes none)
+    hipStream_t stream = nullptr;                           // this context's stream, owned by the handle (used when the caller passes none)
     bool busy = false;                                      // submitted, not yet waited for
-    template <class F> void for_each_buffer(F&& f) {
-        f(w_qp); f(w_qnorm); f(w_thr); f(w_qin); f(w_outd); f(w_qerr); f(w_qg); f(w_dbg);
-        f(w_dense); f(w_samp); f(w_pool); f(w_cand); f(w_exact); f(w_exsel); f(w_mask_ids); f(w_outi);
-        f(w_cnt); f(w_rowmask); f(w_flags); f(w_outc); f(w_subcnt); f(w_depth); f(w_qb);
-        f(w2_qp); f(w2_qnorm); f(w2_thr); f(w2_outd); f(w2_qerr); f(w2_qg); f(w2_outi); f(w2_cand); f(w2_qb);
-        f(w2_outc); f(w2_flags); f(w2_qidx); f(w_dstat); f(w_elig); f(w_eligblk); f(w_radii); f(w_totals);
-    }
 };
 
 // Diagnostic knobs: ablation switches, A/B kernel variants, scaled certificates, sample-size overrides.  Several of them
@@ -153,7 +110,7 @@ struct vdb_flat_index {
     vdb_multi* multi = nullptr;           // non-null: this handle is the PARENT of a sharded index and owns nothing below but mu / stats
     vdb_knobs kn;
     uint32_t tiers = 0;                   // vdb_flat_set_tiers: VDB_TIERS_* bits (tier hand-over forced; results identical)
-    hipStream_t stream = nullptr;
+    vdbi::Stream stream, stream_alt;      // of the two workspaces; declared before every buffer, so destroyed after them
     int n_cu = 256;
     std::mutex mu;
 
@@ -175,14 +132,14 @@ struct vdb_flat_index {
     // compact bf16 copy of the screening tier's S sample rows (kernels_fused_s16.hip SAMPLE mode): +S*ld*2 bytes (3 % of a 1M-row
     // index), rebuilt when rows were added; the sample pass then streams 100 MB of contiguous bf16 instead of gathering 200 MB of
     // f32 rows.  Thresholds are identical (same roundings, same MFMA order).  vdb_flat_set_sample_cache(h, 0) turns it off.
-    uint16_t* d_sample16 = nullptr; size_t sample16_cap = 0;            // capacity in elements
+    vdbi::DevBuf<uint16_t> d_sample16;
     uint32_t sample16_n = 0, sample16_S = 0;                            // what the copy was built for (rows uploaded, sample size)
     bool sample_cache = true;
-    uint16_t* d_rows16 = nullptr;         // opt-in bf16 shadow of d_rows [cap_rows][ld] (vdb_flat_set_shadow), else null
+    vdbi::DevBuf<uint16_t> d_rows16;      // opt-in bf16 shadow of d_rows [cap_rows][ld] (vdb_flat_set_shadow), else null
     bool shadow = false;
-    float* d_rows = nullptr; float* d_nd = nullptr; float* d_alpha = nullptr; float* d_beta = nullptr;
-    float* d_margin = nullptr;            // [cap] per-row error margin of the screening tier's lower-bound scores (Dot / Euclid; null under Cosine)
-    uint64_t* d_row_ids = nullptr; uint32_t* d_live = nullptr; uint32_t* d_scalars = nullptr;  // [0]=nd2max bits [1]=zero count [2],[3]=max bf16 rounding error of a row (abs^2, rel^2)
+    vdbi::DevBuf<float> d_rows, d_nd, d_alpha, d_beta;
+    vdbi::DevBuf<float> d_margin;         // [cap] per-row error margin of the screening tier's lower-bound scores (Dot / Euclid; null under Cosine)
+    vdbi::DevBuf<uint64_t> d_row_ids; vdbi::DevBuf<uint32_t> d_live, d_scalars;  // [0]=nd2max bits [1]=zero count [2],[3]=max bf16 rounding error of a row (abs^2, rel^2)
     uint32_t cap_rows = 0;
     bool zero_valid = false; uint32_t zero_live = 0;
     // vdb_flat_compact (vdb_store.cpp compact_store): dead rows are taken back by an in-place stable compaction on the device
@@ -195,13 +152,13 @@ struct vdb_flat_index {
     // search workspace: everything one search in flight owns.  Two of them, so that two batches can be in flight on two
     // streams (vdb_flat_search_batch_device_submit / _wait); every synchronous entry point uses the first.
     struct Workspace* cur = nullptr;                        // the context the search code below works in (set under the handle mutex)
-    struct Workspace* wsv = nullptr;                        // [2]
+    std::unique_ptr<Workspace[]> wsv;                       // [2]
     // mapped host memory for the pair hooks (vdb_internal.h): the kernel reads the pairs and writes the distances in place
-    uint32_t* h_pairs = nullptr; float* h_pout = nullptr; size_t h_pairs_cap = 0, h_pout_cap = 0;
+    vdbi::HostBuf<uint32_t> h_pairs; vdbi::HostBuf<float> h_pout;
     uint32_t pairs_nq = 0;
     bool begin_locked = false;
-    hipEvent_t ev_pass[2] = {nullptr, nullptr};             // fork / join of the alternating passes of a large batch (pass_bf16)
-    hipEvent_t ev_order = nullptr;                          // orders the handle's stream before the null stream (search_batch_device_begin)
+    vdbi::Event ev_pass[2];                                 // fork / join of the alternating passes of a large batch (pass_bf16)
+    vdbi::Event ev_order;                                   // orders the handle's stream before the null stream (search_batch_device_begin)
     int screen = 1;                                         // 1: bf16 screening tier first (default), 0: f32 MFMA tier only
     bool wide = true;                                       // batches above 256 queries: the 512-query filter kernel (vdb_flat_set_wide)
     bool large_k = true;                                    // 112 < k <= 1024 on the screening tier (vdb_flat_set_large_k)
@@ -210,10 +167,11 @@ struct vdb_flat_index {
     int sparse_mode = 0;
     uint64_t sparse_last = 0, sparse_E = 0, sparse_count = 0;  // vdb_flat_sparse_stats [0] [1] [2]
     uint64_t range_stats[8] = {0};                          // vdb_flat_range_stats: counters of the last range search
-    bool profile = false; hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool profile = false; vdbi::Event ev0, ev1;
 
     uint32_t n_rows() const { return (uint32_t)row_ids.size(); }
     bool is_live(uint32_t r) const { return (live[r >> 5] >> (r & 31)) & 1u; }
+    ~vdb_flat_index();                    // vdb_flat.cpp: waits for the streams; the members free themselves
 };
 
 namespace vdbi {

@@ -23,8 +23,8 @@ static_assert(VDB_META_EQ == (int)vdb::FOP_EQ && VDB_META_NE == (int)vdb::FOP_NE
 // a host array with its device copy; [lo, hi) is what the device has not seen yet
 template <typename T> struct Staged {
     std::vector<T> h;
-    T* d = nullptr;
-    size_t cap = 0, lo = SIZE_MAX, hi = 0;
+    DevBuf<T> d;
+    size_t lo = SIZE_MAX, hi = 0;
     T fill{};
     void grow(size_t n) {                                           // the new tail reads as `fill` on both sides
         if (n <= h.size()) return;
@@ -33,29 +33,24 @@ template <typename T> struct Staged {
     }
     void touch(size_t a, size_t b) { lo = std::min(lo, a); hi = std::max(hi, b); }
     int upload(hipStream_t s) {
-        if (h.size() > cap) {
-            const size_t want = std::max<size_t>(std::max(h.size(), cap * 2), 1024);
-            T* nd = nullptr;
-            HIP_TRY(hipMalloc((void**)&nd, want * sizeof(T)));
-            if (d) {                                                // an earlier compile may still read the old copy
-                (void)hipStreamSynchronize(s);
-                (void)hipFree(d);
-            }
-            d = nd; cap = want;
+        if (h.size() > d.n) {
+            DevBuf<T> nd;
+            HIP_TRY(nd.alloc(std::max<size_t>(std::max(h.size(), d.n * 2), 1024)));
+            if (d) (void)hipStreamSynchronize(s);                   // an earlier compile may still read the old copy
+            d = std::move(nd);
             touch(0, h.size());
         }
         if (lo < hi) HIP_TRY(hipMemcpyAsync(d + lo, h.data() + lo, (hi - lo) * sizeof(T), hipMemcpyHostToDevice, s));
         lo = SIZE_MAX; hi = 0;
         return VDB_OK;
     }
-    void release() { if (d) (void)hipFree(d); d = nullptr; cap = 0; }
 };
 
 }  // namespace
 
 struct vdb_meta_table {
     int device = 0, n_cu = 256;
-    hipStream_t stream = nullptr;
+    Stream stream;                                                  // declared first: destroyed after every buffer below
     std::mutex mu;                                                  // compiles are reads of the caller and may come from several threads
     std::vector<std::unique_ptr<Staged<int32_t>>> cols;             // by slot; null = slot never written
     Staged<uint64_t> present;
@@ -65,28 +60,18 @@ struct vdb_meta_table {
 
 namespace {
 
-void free_mask(vdb_meta_mask* m) {
-    if (m->d_words) (void)hipFree(m->d_words);
-    if (m->d_block) (void)hipFree(m->d_block);
-    if (m->h_block) (void)hipHostFree(m->h_block);
-    if (m->done) (void)hipEventDestroy(m->done);
-}
-
 // a mask of at least `words` words from the pool (the most recently released one that is large enough, else any released one,
 // regrown), or a new one
 int take_mask(vdb_meta_table* t, size_t words, vdb_meta_mask** out) {
     vdb_meta_mask* m = nullptr;
     for (size_t i = t->free_masks.size(); i-- > 0 && !m;)
-        if (t->free_masks[i]->cap_words >= words) { m = t->free_masks[i]; t->free_masks.erase(t->free_masks.begin() + (ptrdiff_t)i); }
+        if (t->free_masks[i]->d_words.n >= words) { m = t->free_masks[i]; t->free_masks.erase(t->free_masks.begin() + (ptrdiff_t)i); }
     if (!m && !t->free_masks.empty()) { m = t->free_masks.back(); t->free_masks.pop_back(); }
     if (!m) {
         auto nm = std::make_unique<vdb_meta_mask>();
         nm->table = t; nm->device = t->device;
-        if (hipMalloc((void**)&nm->d_block, BLOCK_BYTES) != hipSuccess || hipHostMalloc((void**)&nm->h_block, BLOCK_BYTES) != hipSuccess ||
-            hipEventCreateWithFlags(&nm->done, hipEventDisableTiming) != hipSuccess) {
-            free_mask(nm.get());
+        if (nm->d_block.alloc(BLOCK_BYTES) != hipSuccess || nm->h_block.alloc(BLOCK_BYTES) != hipSuccess || nm->done.create(hipEventDisableTiming))
             return fail(VDB_ERR_DEVICE, "allocating a filter mask failed");
-        }
         memset(nm->h_block, 0, BLOCK_BYTES);
         m = nm.get();
         t->masks.push_back(std::move(nm));
@@ -95,12 +80,9 @@ int take_mask(vdb_meta_table* t, size_t words, vdb_meta_mask** out) {
         // the mask was released before anybody waited for it)
         HIP_TRY(hipEventSynchronize(m->done));
     }
-    if (m->cap_words < words) {
-        if (m->d_words) (void)hipFree(m->d_words);
-        m->d_words = nullptr; m->cap_words = 0;
-        const size_t want = std::max<size_t>(words + words / 2, 64);
-        if (hipMalloc((void**)&m->d_words, want * 8) != hipSuccess) { t->free_masks.push_back(m); return fail(VDB_ERR_DEVICE, "hipMalloc of a filter mask failed"); }
-        m->cap_words = want;
+    if (m->d_words.n < words && m->d_words.alloc(std::max<size_t>(words + words / 2, 64)) != hipSuccess) {
+        t->free_masks.push_back(m);
+        return fail(VDB_ERR_DEVICE, "allocating the words of a filter mask failed");
     }
     *out = m;
     return VDB_OK;
@@ -126,7 +108,8 @@ int vdb_meta_create(int device, vdb_meta_table** out) {
     t->device = device;
     t->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     t->present.fill = 0;
-    HIP_TRY(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+    int rc;
+    if ((rc = t->stream.create(hipStreamNonBlocking))) return rc;
     *out = t.release();
     return VDB_OK;
     });
@@ -136,10 +119,6 @@ void vdb_meta_destroy(vdb_meta_table* t) {
     if (!t) return;
     (void)hipSetDevice(t->device);
     (void)hipStreamSynchronize(t->stream);
-    for (auto& c : t->cols) if (c) c->release();
-    t->present.release();
-    for (auto& m : t->masks) free_mask(m.get());
-    (void)hipStreamDestroy(t->stream);
     delete t;
 }
 
@@ -235,7 +214,7 @@ int vdb_meta_compile(vdb_meta_table* t, const vdb_meta_op* ops, size_t n_ops, si
         p.ops = reinterpret_cast<const vdb::FilterOp*>(m->d_block + BLOCK_HEADER); p.n_ops = (uint32_t)n_ops;
         p.present = t->present.d; p.present_words = t->present.d ? t->present.h.size() : 0;
         p.mask_bits = mask_bits; p.mask = m->d_words;
-        p.count = reinterpret_cast<unsigned long long*>(m->d_block);
+        p.count = reinterpret_cast<unsigned long long*>(m->d_block.p);
         vdb::launch_filter_compile(p, (uint32_t)t->n_cu, s);
         e = hipGetLastError();
     }

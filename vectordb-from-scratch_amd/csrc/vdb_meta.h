@@ -6,14 +6,16 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "vdb_device.h"
+
 struct vdb_meta_table;
 
 struct vdb_meta_mask {
     vdb_meta_table* table = nullptr;
     int device = 0;
-    uint64_t* d_words = nullptr; size_t cap_words = 0;     // the mask, in the layout of id_mask
+    vdbi::DevBuf<uint64_t> d_words;                         // the mask, in the layout of id_mask
     size_t bits = 0;
     // one device block and its pinned host image: [0] the eligible count (uploaded as 0), then the program
-    char* d_block = nullptr; char* h_block = nullptr;
-    hipEvent_t done = nullptr;                              // recorded on the table's stream behind the kernel
+    vdbi::DevBuf<char> d_block; vdbi::HostBuf<char> h_block{hipHostMallocDefault};
+    vdbi::Event done;                                       // recorded on the table's stream behind the kernel
 };

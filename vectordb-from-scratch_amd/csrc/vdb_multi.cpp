@@ -137,17 +137,17 @@ struct vdb_multi {
     std::vector<void*> comm;                   // in-process RCCL communicators, created at the first RCCL exchange
     int comm_world = 0;
     struct PerShard {
-        hipStream_t stream = nullptr;
-        hipEvent_t ev_done = nullptr;
-        float* d_q = nullptr; size_t q_cap = 0;                 // the queries on this shard's device (shards off the home device)
-        uint64_t* d_mask = nullptr; size_t mask_cap = 0;        // the id mask, likewise
-        int32_t* d_pack = nullptr; size_t pack_words = 0;       // this shard's packed partial results
-        int32_t* d_gath = nullptr; size_t gath_words = 0;       // [G][words]: RCCL receive buffer (every shard) / peer target (shard 0)
+        vdbi::Stream stream;
+        vdbi::Event ev_done;
+        vdbi::DevBuf<float> d_q;                                // the queries on this shard's device (shards off the home device)
+        vdbi::DevBuf<uint64_t> d_mask;                          // the id mask, likewise
+        vdbi::DevBuf<int32_t> d_pack;                           // this shard's packed partial results
+        vdbi::DevBuf<int32_t> d_gath;                           // [G][words]: RCCL receive buffer (every shard) / peer target (shard 0)
         int rc = VDB_OK; bool begun = false; int changed = 0;
         std::string msg; size_t e_exp = 0, e_act = 0;
     };
     std::vector<PerShard> ps;
-    uint32_t* d_status = nullptr; uint32_t* h_status = nullptr;     // devices[0]
+    vdbi::DevBuf<uint32_t> d_status; vdbi::HostBuf<uint32_t> h_status{hipHostMallocDefault};     // devices[0]
     // host-pointer entry point: staging on devices[0]
     vdbi::DevBuf<float> w_qin, w_outd; vdbi::DevBuf<uint64_t> w_outi, w_mask; vdbi::DevBuf<uint32_t> w_outc;
     uint64_t stats[8] = {0};
@@ -194,18 +194,6 @@ int ensure_comms(vdb_multi* M) {
     M->comm.swap(comm);
     M->comm_world = cnt;
     HIP_TRY(hipSetDevice(M->home));
-    return VDB_OK;
-}
-
-// (re)allocates a device buffer of the shard on ITS device; the caller restores the current device
-template <class T> int ensure_on(int device, T*& p, size_t& cap, size_t want) {
-    if (want <= cap) return VDB_OK;
-    HIP_TRY(hipSetDevice(device));
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    const size_t n = want + want / 2;
-    HIP_TRY(hipMalloc((void**)&p, n * sizeof(T)));
-    cap = n;
     return VDB_OK;
 }
 
@@ -287,8 +275,7 @@ int multi_create(int metric, const int* devices, size_t n, vdb_flat_index** out)
         int rc = vdb_flat_create(metric, devices[g], &c);
         if (rc) return bail(rc);
         M->sh.push_back(c);
-        if (hipSetDevice(devices[g]) != hipSuccess || hipStreamCreateWithFlags(&M->ps[g].stream, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&M->ps[g].ev_done, hipEventDisableTiming) != hipSuccess)
+        if (hipSetDevice(devices[g]) != hipSuccess || M->ps[g].stream.create(hipStreamNonBlocking) || M->ps[g].ev_done.create(hipEventDisableTiming))
             return bail(fail(VDB_ERR_DEVICE, "stream / event creation failed on device %d", devices[g]));
     }
     // direct xGMI copies between the home device and the others where the topology allows (otherwise the runtime stages them)
@@ -306,8 +293,7 @@ int multi_create(int metric, const int* devices, size_t n, vdb_flat_index** out)
             if (e != hipSuccess) (void)hipGetLastError();
         }
     }
-    if (hipSetDevice(M->home) != hipSuccess || hipMalloc((void**)&M->d_status, 16) != hipSuccess ||
-        hipHostMalloc((void**)&M->h_status, 16, hipHostMallocDefault) != hipSuccess)
+    if (hipSetDevice(M->home) != hipSuccess || M->d_status.alloc(4) != hipSuccess || M->h_status.alloc(4) != hipSuccess)
         return bail(fail(VDB_ERR_DEVICE, "allocation failed on device %d", M->home));
     M->gang.start(M->G, [M](int g) { (void)hipSetDevice(M->dev[g]); });
     *out = P;
@@ -324,19 +310,12 @@ void multi_destroy(vdb_flat_index* P) {
             (void)hipSetDevice(M->dev[g]);
             if (p.stream) (void)hipStreamSynchronize(p.stream);
             if (r && g < M->comm.size() && M->comm[g]) (void)r->comm_destroy(M->comm[g]);
-            if (p.d_q) (void)hipFree(p.d_q);
-            if (p.d_mask) (void)hipFree(p.d_mask);
-            if (p.d_pack) (void)hipFree(p.d_pack);
-            if (p.d_gath) (void)hipFree(p.d_gath);
-            if (p.ev_done) (void)hipEventDestroy(p.ev_done);
-            if (p.stream) (void)hipStreamDestroy(p.stream);
+            p.d_q.release(); p.d_mask.release(); p.d_pack.release(); p.d_gath.release();
+            p.ev_done.destroy(); p.stream.destroy();
         }
         for (auto* c : M->sh) vdb_flat_destroy(c);
         (void)hipSetDevice(M->home);
-        if (M->d_status) (void)hipFree(M->d_status);
-        if (M->h_status) (void)hipHostFree(M->h_status);
-        M->w_qin.release(); M->w_outd.release(); M->w_outi.release(); M->w_mask.release(); M->w_outc.release();
-        delete M;
+        delete M;                                  // the status words and the staging of the host entry point, on devices[0]
     }
     delete P;
     (void)hipGetLastError();                   // teardown is best effort: leave no stale error behind for the thread's next call
@@ -386,8 +365,8 @@ int multi_add_bulk(vdb_flat_index* P, const uint64_t* ids, uint64_t first_id, co
             // rows resident on the home device: staged through a buffer on the shard's device, 64 Mi floats at a time
             rc = VDB_OK;
             const size_t chunk_rows = std::max<size_t>(1, ((size_t)64 << 20) / std::max<size_t>(dim, 1));
-            float* tmp = nullptr;
-            if (hipSetDevice(M->dev[g]) != hipSuccess || hipMalloc((void**)&tmp, std::min(chunk_rows, hi - lo) * dim * 4) != hipSuccess)
+            DevBuf<float> tmp;
+            if (hipSetDevice(M->dev[g]) != hipSuccess || tmp.alloc(std::min(chunk_rows, hi - lo) * dim) != hipSuccess)
                 rc = fail(VDB_ERR_DEVICE, "staging allocation failed on device %d", M->dev[g]);
             for (size_t a = lo; a < hi && rc == VDB_OK; a += chunk_rows) {
                 const size_t cnt = std::min(chunk_rows, hi - a);
@@ -396,7 +375,6 @@ int multi_add_bulk(vdb_flat_index* P, const uint64_t* ids, uint64_t first_id, co
                     rc = fail(VDB_ERR_DEVICE, "peer copy of rows to device %d failed", M->dev[g]);
                 else rc = vdb_flat_add_bulk_device(M->sh[g], ids ? ids + a : nullptr, first_id + a, tmp, cnt, dim);
             }
-            if (tmp) (void)hipFree(tmp);
         }
         if (rc) capture_error(M->ps[g], rc);
     });
@@ -479,12 +457,18 @@ int search_locked(vdb_flat_index* P, const float* d_q, size_t nq, size_t dim, si
     for (int g = 0; g < M->G; ++g) {
         auto& p = M->ps[g];
         int rc;
-        if ((rc = ensure_on(M->dev[g], p.d_pack, p.pack_words, words))) return done(rc);
+        // a shard's buffers live on ITS device: it is made current only when one of them grows (the home device is restored below)
+        auto grow = [&](auto& buf, size_t want) -> int {
+            if (want <= buf.n) return VDB_OK;
+            HIP_TRY(hipSetDevice(M->dev[g]));
+            return buf.ensure(want);
+        };
+        if ((rc = grow(p.d_pack, words))) return done(rc);
         if (M->exchange == VDB_EXCHANGE_RCCL || g == 0)
-            if ((rc = ensure_on(M->dev[g], p.d_gath, p.gath_words, words * (size_t)M->G))) return done(rc);
+            if ((rc = grow(p.d_gath, words * (size_t)M->G))) return done(rc);
         if (M->dev[g] != M->home) {
-            if ((rc = ensure_on(M->dev[g], p.d_q, p.q_cap, nq * std::max<size_t>(dim, 1)))) return done(rc);
-            if (mask_words && (rc = ensure_on(M->dev[g], p.d_mask, p.mask_cap, mask_words))) return done(rc);
+            if ((rc = grow(p.d_q, nq * std::max<size_t>(dim, 1)))) return done(rc);
+            if (mask_words && (rc = grow(p.d_mask, mask_words))) return done(rc);
         }
         p.rc = VDB_OK; p.begun = false; p.changed = 0; p.msg.clear();
     }
@@ -524,7 +508,7 @@ int search_locked(vdb_flat_index* P, const float* d_q, size_t nq, size_t dim, si
             mk = mask_words ? p.d_mask : nullptr;
         }
         if (p.rc == VDB_OK) {
-            uint64_t* p_ids = reinterpret_cast<uint64_t*>(p.d_pack);
+            uint64_t* p_ids = reinterpret_cast<uint64_t*>(p.d_pack.p);
             float* p_dists = reinterpret_cast<float*>(p.d_pack + 2 * nk);
             uint32_t* p_counts = reinterpret_cast<uint32_t*>(p.d_pack + 3 * nk);
             int32_t* p_code = p.d_pack + 3 * nk + nq;

@@ -350,10 +350,9 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
         if (o->busy) sample_copy = false;
         else {
             const size_t need = (size_t)S * ld;
-            if (ix->sample16_cap < need) {
-                if (ix->d_sample16) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(ix->d_sample16); ix->d_sample16 = nullptr; ix->sample16_cap = 0; }
-                if (hipMalloc((void**)&ix->d_sample16, need * 2) == hipSuccess) ix->sample16_cap = need;
-                else { (void)hipGetLastError(); ix->d_sample16 = nullptr; sample_copy = false; }   // no memory for the optional copy: f32 gather
+            if (ix->d_sample16.n < need) {
+                if (ix->d_sample16) HIP_TRY(hipDeviceSynchronize());
+                if (ix->d_sample16.alloc(need) != hipSuccess) { (void)hipGetLastError(); sample_copy = false; }   // no memory for the optional copy: f32 gather
             }
             if (sample_copy) {
                 vdb::launch_sample_to_bf16(ix->d_rows, ld, n, S, pl.shift, ix->d_sample16, s);
@@ -364,10 +363,7 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
         }
     }
     if (alt) {                                                   // the other stream starts behind query_prep and the row mask
-        if (!ix->ev_pass[0]) {
-            HIP_TRY(hipEventCreateWithFlags(&ix->ev_pass[0], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&ix->ev_pass[1], hipEventDisableTiming));
-        }
+        if ((rc = ix->ev_pass[0].create(hipEventDisableTiming)) || (rc = ix->ev_pass[1].create(hipEventDisableTiming))) return rc;
         HIP_TRY(hipEventRecord(ix->ev_pass[0], s));
         HIP_TRY(hipStreamWaitEvent(Sv[1], ix->ev_pass[0], 0));
     }
@@ -572,15 +568,7 @@ bool direct_eligible(const Index* ix, size_t n_rows, size_t nq, size_t k) {
 }
 
 int ensure_host_io(Index* ix, size_t bytes) {
-    Workspace* W = ix->cur;
-    if (bytes <= W->h_io_bytes) return VDB_OK;
-    if (W->h_io) (void)hipHostFree(W->h_io);
-    W->h_io = W->d_h_io = nullptr; W->h_io_bytes = 0;
-    const size_t cap = std::max<size_t>(bytes + bytes / 2, 1u << 16);
-    HIP_TRY(hipHostMalloc((void**)&W->h_io, cap, hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void**)&W->d_h_io, W->h_io, 0));
-    W->h_io_bytes = cap;
-    return VDB_OK;
+    return ix->cur->h_io.ensure(std::max<size_t>(bytes, 1u << 16));
 }
 
 static int search_direct(Index* ix, hipStream_t s, const float* d_q, uint32_t nq, size_t k, const uint32_t* d_rowmask,
@@ -597,10 +585,7 @@ static int search_direct(Index* ix, hipStream_t s, const float* d_q, uint32_t nq
     if ((rc = W->w_cnt.ensure(4 * SUPER + 16))) return rc;
     if (!W->dstat_ready) {
         if ((rc = W->w_dstat.ensure(4))) return rc;
-        if (!W->h_dstat) {
-            HIP_TRY(hipHostMalloc((void**)&W->h_dstat, 16 * sizeof(uint32_t), hipHostMallocMapped));
-            HIP_TRY(hipHostGetDevicePointer((void**)&W->d_h_dstat, W->h_dstat, 0));
-        }
+        if ((rc = W->h_dstat.ensure(16))) return rc;
         HIP_TRY(hipMemsetAsync(W->w_dstat.p, 0, 16, s));
         W->dstat_ready = true;
     }
@@ -612,7 +597,7 @@ static int search_direct(Index* ix, hipStream_t s, const float* d_q, uint32_t nq
     mp.kk = (uint32_t)k; mp.out_keys = W->w_exsel.p; mp.out_stride = MAX_SELECT; mp.out_cnt = W->w_cnt.p;
     mp.emit_ids = d_out_ids; mp.emit_dists = d_out_dists; mp.emit_counts = d_out_counts; mp.emit_stride = (uint32_t)k;
     mp.emit_rank2row = ix->ids_monotone ? nullptr : ix->d_rank2row.p; mp.emit_row_ids = ix->d_row_ids;
-    mp.emit_status_in = W->w_dstat.p; mp.emit_status = W->d_h_dstat;
+    mp.emit_status_in = W->w_dstat.p; mp.emit_status = W->h_dstat.d;
     vdb::launch_select(mp, nq, s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
@@ -803,14 +788,7 @@ int search_part1(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, c
     if ((rc = ix->cur->w_qnorm.ensure(bp_all))) return rc;
     if ((rc = ix->cur->w_thr.ensure(bp_all))) return rc;
     if ((rc = ix->cur->w_flags.ensure(4 + 3 * (size_t)nq32))) return rc;      // status block | cert | overflow | score cut per query
-    if (ix->cur->h_flags_n < 4 + 3 * (size_t)nq32) {
-        if (ix->cur->h_flags) (void)hipHostFree(ix->cur->h_flags);
-        ix->cur->h_flags = nullptr;
-        ix->cur->h_flags_n = 0;
-        size_t want = 4 + 3 * (size_t)nq32 + 1024;
-        HIP_TRY(hipHostMalloc((void**)&ix->cur->h_flags, want * 4, hipHostMallocDefault));
-        ix->cur->h_flags_n = want;
-    }
+    if ((rc = ix->cur->h_flags.ensure(4 + 3 * (size_t)nq32))) return rc;
     uint32_t* d_status = ix->cur->w_flags.p;        // [0] status bits
     uint32_t* d_cert = ix->cur->w_flags.p + 4;      // [nq]
     uint32_t* d_ovf = d_cert + nq32;           // [nq]

@@ -15,6 +15,7 @@
 #include "../../include/vdb_flat.h"
 #include "../../include/vdb_shard.h"
 #include "kernels.h"
+#include "vdb_device.h"
 #include "vdb_internal.h"
 #include "vdb_rccl.h"
 
@@ -23,6 +24,7 @@ namespace {
 using vdb_rccl::NcclId;
 using vdb_rccl::Rccl;
 using namespace vdb_rccl;
+using vdbi::guarded;
 Rccl g_rccl;
 std::once_flag g_rccl_once;
 
@@ -72,31 +74,19 @@ int nccl_fail(const char* what, int rc) {
     return err(VDB_ERR_DEVICE, buf);
 }
 
-#define SH_TRY(expr)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) { char b_[256]; snprintf(b_, sizeof(b_), "HIP error %d (%s): %s", (int)e_, hipGetErrorString(e_), #expr); return err(VDB_ERR_DEVICE, b_); } \
-    } while (0)
-
 constexpr uint32_t CODE_ERR_BASE = 1000;     // status word of a rank whose local search failed: 1000 + vdb_status (survives the MAX with VDB_PENDING_HOST)
-
-template <class F> int guarded(F&& body) noexcept {
-    try { return body(); }
-    catch (const std::bad_alloc&) { return err(VDB_ERR_DEVICE, "internal error: out of host memory"); }
-    catch (...) { return err(VDB_ERR_DEVICE, "internal error: C++ exception"); }
-}
 
 }  // namespace
 
 struct vdb_shard_group {
     int rank = 0, world = 1, device = 0, comm_world = 1;
     void* comm = nullptr;
-    hipStream_t stream = nullptr;             // used when the caller passes no stream
-    int32_t* d_pack = nullptr; int32_t* d_gath = nullptr; size_t pack_words = 0;
-    uint32_t* d_status = nullptr; uint32_t* h_status = nullptr;
+    vdbi::Stream stream;                      // used when the caller passes no stream
+    vdbi::DevBuf<int32_t> d_pack, d_gath;     // d_pack.n words per rank, the same on every rank
+    vdbi::DevBuf<uint32_t> d_status; vdbi::HostBuf<uint32_t> h_status{hipHostMallocDefault};
     // fixed-size exchange made at create time: one word per rank.  A rank-LOCAL failure that would otherwise keep a rank out
     // of a collective (growing the packed buffers) is first agreed on through these, which cannot fail to exist.
-    int32_t* d_vote = nullptr; int32_t* d_votes = nullptr; int32_t* h_votes = nullptr;
+    vdbi::DevBuf<int32_t> d_vote, d_votes; vdbi::HostBuf<int32_t> h_votes{hipHostMallocDefault};
     bool poisoned = false;                    // a local device failure left this rank unable to follow the protocol: every later call fails at once
     std::mutex mu;
     uint64_t stats[4] = {0, 0, 0, 0};
@@ -104,11 +94,7 @@ struct vdb_shard_group {
 
 namespace {
 
-void drop_buffers(vdb_shard_group* g) {
-    if (g->d_pack) (void)hipFree(g->d_pack);
-    if (g->d_gath) (void)hipFree(g->d_gath);
-    g->d_pack = g->d_gath = nullptr; g->pack_words = 0;
-}
+void drop_buffers(vdb_shard_group* g) { g->d_pack.release(); g->d_gath.release(); }
 
 // Growing the packed buffers is a rank-LOCAL allocation, and a rank that returned on its failure would leave the others
 // blocked in exchange 1 for ever.  So growth is agreed on: every rank tries, then ONE all-gather of a word per rank (buffers
@@ -116,11 +102,11 @@ void drop_buffers(vdb_shard_group* g) {
 // -- capacities stay identical on all ranks (`words` is, and so is the growth rule), which is what makes "does this call
 // grow?" a rank-identical decision in the first place.
 int ensure_buffers(vdb_shard_group* g, size_t words, hipStream_t s) {
-    if (words <= g->pack_words) return VDB_OK;
+    if (words <= g->d_pack.n) return VDB_OK;
     drop_buffers(g);
     const size_t cap = words + words / 2;
     int32_t vote = 0;
-    if (hipMalloc((void**)&g->d_pack, cap * 4) != hipSuccess || hipMalloc((void**)&g->d_gath, cap * 4 * (size_t)g->world) != hipSuccess) {
+    if (g->d_pack.alloc(cap) != hipSuccess || g->d_gath.alloc(cap * (size_t)g->world) != hipSuccess) {
         (void)hipGetLastError();
         vote = 1;
     }
@@ -140,7 +126,6 @@ int ensure_buffers(vdb_shard_group* g, size_t words, hipStream_t s) {
         snprintf(b_, sizeof(b_), "rank %d could not allocate the exchange buffers (%zu bytes per rank); no rank searched", bad, cap * 4);
         return err(VDB_ERR_DEVICE, b_);
     }
-    g->pack_words = cap;
     return VDB_OK;
 }
 
@@ -191,14 +176,14 @@ int vdb_shard_group_create(const unsigned char id[VDB_SHARD_UNIQUE_ID_BYTES], in
     *out = nullptr;
     if (world < 1 || rank < 0 || rank >= world) return err(VDB_ERR_INVALID_ARGUMENT, "rank / world out of range");
     if (world > 1 && !id) return err(VDB_ERR_INVALID_ARGUMENT, "a unique id is required for world > 1");
-    SH_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     auto* g = new vdb_shard_group();
     g->rank = rank; g->world = world; g->device = device; g->comm_world = 1;
     auto fail_with = [&](int rc) { vdb_shard_group_destroy(g); return rc; };
-    if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) return fail_with(err(VDB_ERR_DEVICE, "hipStreamCreate failed"));
-    if (hipMalloc((void**)&g->d_status, 16) != hipSuccess || hipHostMalloc((void**)&g->h_status, 16, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc((void**)&g->d_vote, 16) != hipSuccess || hipMalloc((void**)&g->d_votes, (size_t)world * 4 + 16) != hipSuccess ||
-        hipHostMalloc((void**)&g->h_votes, (size_t)world * 4 + 16, hipHostMallocDefault) != hipSuccess)
+    int rc0 = g->stream.create(hipStreamNonBlocking);
+    if (rc0) return fail_with(rc0);
+    if (g->d_status.alloc(4) != hipSuccess || g->h_status.alloc(4) != hipSuccess || g->d_vote.alloc(4) != hipSuccess ||
+        g->d_votes.alloc((size_t)world + 4) != hipSuccess || g->h_votes.alloc((size_t)world + 4) != hipSuccess)
         return fail_with(err(VDB_ERR_DEVICE, "allocation failed"));
     if (world > 1 || id) {                                         // (world == 1 WITH an id: a single-rank communicator, full exchange path)
         const Rccl* r = rccl();
@@ -224,14 +209,6 @@ void vdb_shard_group_destroy(vdb_shard_group* g) {
     (void)hipSetDevice(g->device);
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     if (g->comm) { const Rccl* r = rccl(); if (r) (void)r->comm_destroy(g->comm); }
-    if (g->d_pack) (void)hipFree(g->d_pack);
-    if (g->d_gath) (void)hipFree(g->d_gath);
-    if (g->d_status) (void)hipFree(g->d_status);
-    if (g->h_status) (void)hipHostFree(g->h_status);
-    if (g->d_vote) (void)hipFree(g->d_vote);
-    if (g->d_votes) (void)hipFree(g->d_votes);
-    if (g->h_votes) (void)hipHostFree(g->h_votes);
-    if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
 }
 
@@ -277,8 +254,8 @@ int vdb_flat_search_batch_sharded(vdb_shard_group* g, vdb_flat_index* local, con
     hip_note(hipSetDevice(g->device), "hipSetDevice");
     hipStream_t s = stream ? (hipStream_t)stream : g->stream;
     if (k == 0) {                                                  // (k is the same on every rank: no rank enters a collective)
-        SH_TRY(hipMemsetAsync(d_out_counts, 0, nq * 4, s));
-        SH_TRY(hipStreamSynchronize(s));
+        HIP_TRY(hipMemsetAsync(d_out_counts, 0, nq * 4, s));
+        HIP_TRY(hipStreamSynchronize(s));
         return done(VDB_OK);
     }
     const size_t nk = nq * k;
@@ -287,7 +264,7 @@ int vdb_flat_search_batch_sharded(vdb_shard_group* g, vdb_flat_index* local, con
     int rc;
     if ((rc = ensure_buffers(g, words, s))) return done(rc);         // agreed on by all ranks (see there): every rank returns here, or none
     // the local search writes straight into the packed buffer: ids | dists | counts | status word
-    uint64_t* p_ids = reinterpret_cast<uint64_t*>(g->d_pack);
+    uint64_t* p_ids = reinterpret_cast<uint64_t*>(g->d_pack.p);
     float* p_dists = reinterpret_cast<float*>(g->d_pack + 2 * nk);
     uint32_t* p_counts = reinterpret_cast<uint32_t*>(g->d_pack + 3 * nk);
     int32_t* p_code = g->d_pack + 3 * nk + nq;

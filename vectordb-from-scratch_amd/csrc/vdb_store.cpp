@@ -17,25 +17,26 @@ namespace vdbi {
 // ------------------------------------------------------------------ device store management
 // Re-allocates the store with room for `cap` rows (>= n_uploaded) and carries the uploaded rows over; old and new exist at once.
 static int resize_store(Index* ix, uint32_t cap) {
-    float *rows = nullptr, *nd = nullptr, *al = nullptr, *be = nullptr, *mg = nullptr;
-    uint64_t* ids = nullptr;
-    uint32_t* lv = nullptr;
+    // built in locals and moved into the handle at the end: a failure anywhere frees every new array and leaves the old store in place
+    DevBuf<float> rows, nd, al, be, mg;
+    DevBuf<uint64_t> ids;
+    DevBuf<uint32_t> lv;
+    DevBuf<uint16_t> r16;
     size_t row_bytes = (size_t)ix->ld * sizeof(float);
-    HIP_TRY(hipMalloc((void**)&rows, (size_t)cap * row_bytes));
-    HIP_TRY(hipMalloc((void**)&nd, (size_t)cap * 4));
-    HIP_TRY(hipMalloc((void**)&al, (size_t)cap * 4));
-    HIP_TRY(hipMalloc((void**)&be, (size_t)cap * 4));
-    if (ix->metric != vdb::COSINE) HIP_TRY(hipMalloc((void**)&mg, (size_t)cap * 4));
-    HIP_TRY(hipMalloc((void**)&ids, (size_t)cap * 8));
-    HIP_TRY(hipMalloc((void**)&lv, (size_t)cap / 8));
+    HIP_TRY(rows.alloc((size_t)cap * ix->ld));
+    HIP_TRY(nd.alloc(cap));
+    HIP_TRY(al.alloc(cap));
+    HIP_TRY(be.alloc(cap));
+    if (ix->metric != vdb::COSINE) HIP_TRY(mg.alloc(cap));
+    HIP_TRY(ids.alloc(cap));
+    HIP_TRY(lv.alloc((size_t)cap / 32));
     hipStream_t s = ix->stream;
     uint32_t old = ix->n_uploaded;
-    uint16_t* r16 = nullptr;
     if (ix->shadow) {
-        HIP_TRY(hipMalloc((void**)&r16, (size_t)cap * ix->ld * 2));
+        HIP_TRY(r16.alloc((size_t)cap * ix->ld));
         if (old && ix->d_rows16) HIP_TRY(hipMemcpyAsync(r16, ix->d_rows16, (size_t)old * ix->ld * 2, hipMemcpyDeviceToDevice, s));
         else if (old) vdb::launch_rows_to_bf16(ix->d_rows, r16, ix->ld, 0, old, s);     // no shadow yet: from the f32 rows, never left unset
-        HIP_TRY(hipMemsetAsync((char*)r16 + (size_t)old * ix->ld * 2, 0, (size_t)(cap - old) * ix->ld * 2, s));
+        HIP_TRY(hipMemsetAsync((char*)r16.p + (size_t)old * ix->ld * 2, 0, (size_t)(cap - old) * ix->ld * 2, s));
     }
     if (old) {
         HIP_TRY(hipMemcpyAsync(rows, ix->d_rows, (size_t)old * row_bytes, hipMemcpyDeviceToDevice, s));
@@ -47,18 +48,13 @@ static int resize_store(Index* ix, uint32_t cap) {
     }
     if (mg) HIP_TRY(hipMemsetAsync(mg + old, 0, (size_t)(cap - old) * 4, s));   // rows past the last one are staged by the kernels (ragged tile)
     // zero the rest of the row block: the [dim, ld) padding columns must read as 0
-    HIP_TRY(hipMemsetAsync((char*)rows + (size_t)old * row_bytes, 0, (size_t)(cap - old) * row_bytes, s));
+    HIP_TRY(hipMemsetAsync((char*)rows.p + (size_t)old * row_bytes, 0, (size_t)(cap - old) * row_bytes, s));
     HIP_TRY(hipMemsetAsync(lv, 0, (size_t)cap / 8, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (ix->d_rows) {
-        (void)hipFree(ix->d_rows); (void)hipFree(ix->d_nd); (void)hipFree(ix->d_alpha);
-        (void)hipFree(ix->d_beta); (void)hipFree(ix->d_row_ids); (void)hipFree(ix->d_live);
-        if (ix->d_margin) (void)hipFree(ix->d_margin);
-    }
-    if (ix->d_rows16) (void)hipFree(ix->d_rows16);
-    ix->d_rows16 = r16;
-    ix->d_margin = mg;
-    ix->d_rows = rows; ix->d_nd = nd; ix->d_alpha = al; ix->d_beta = be; ix->d_row_ids = ids; ix->d_live = lv;
+    ix->d_rows16 = std::move(r16);
+    ix->d_margin = std::move(mg);
+    ix->d_rows = std::move(rows); ix->d_nd = std::move(nd); ix->d_alpha = std::move(al); ix->d_beta = std::move(be);
+    ix->d_row_ids = std::move(ids); ix->d_live = std::move(lv);
     ix->cap_rows = cap;
     ix->live_dirty = true;
     return VDB_OK;
@@ -71,18 +67,10 @@ int grow(Index* ix, uint32_t need_rows) {
 }
 
 void free_store(Index* ix) {
-    if (ix->d_rows) {
-        (void)hipFree(ix->d_rows); (void)hipFree(ix->d_nd); (void)hipFree(ix->d_alpha);
-        (void)hipFree(ix->d_beta); (void)hipFree(ix->d_row_ids); (void)hipFree(ix->d_live);
-        if (ix->d_margin) (void)hipFree(ix->d_margin);
-    }
-    if (ix->d_rows16) (void)hipFree(ix->d_rows16);
-    ix->d_rows16 = nullptr;
-    if (ix->d_sample16) (void)hipFree(ix->d_sample16);
-    ix->d_sample16 = nullptr; ix->sample16_cap = 0; ix->sample16_n = ix->sample16_S = 0;
-    ix->d_margin = nullptr;
-    ix->d_rows = ix->d_nd = ix->d_alpha = ix->d_beta = nullptr;
-    ix->d_row_ids = nullptr; ix->d_live = nullptr;
+    ix->d_rows.release(); ix->d_nd.release(); ix->d_alpha.release(); ix->d_beta.release(); ix->d_margin.release();
+    ix->d_row_ids.release(); ix->d_live.release();
+    ix->d_rows16.release();
+    ix->d_sample16.release(); ix->sample16_n = ix->sample16_S = 0;
     ix->cap_rows = 0;
 }
 
@@ -270,17 +258,16 @@ int compact_store(Index* ix, bool shrink, size_t* out_reclaimed) {
         uint64_t n_direct = 0, n_bounce = 0;
         for (auto& c : plan) (c.mode ? n_bounce : n_direct)++;
         // every allocation happens before the first row moves
-        uint32_t* d_prefix = nullptr;
-        char* d_bounce = nullptr;
-        HIP_TRY(hipMalloc((void**)&d_prefix, prefix.size() * 4));
-        if (n_bounce && hipMalloc((void**)&d_bounce, (size_t)B * bounce_row_bytes(ld, shadow)) != hipSuccess) {
-            (void)hipFree(d_prefix);
-            return fail(VDB_ERR_DEVICE, "hipMalloc of the compaction bounce buffer (%zu bytes) failed", (size_t)B * bounce_row_bytes(ld, shadow));
+        DevBuf<uint32_t> d_prefix;
+        DevBuf<char> d_bounce;
+        HIP_TRY(d_prefix.alloc(prefix.size()));
+        if (n_bounce && d_bounce.alloc((size_t)B * bounce_row_bytes(ld, shadow)) != hipSuccess) {
+            return fail(VDB_ERR_DEVICE, "allocating the compaction bounce buffer (%zu bytes) failed", (size_t)B * bounce_row_bytes(ld, shadow));
         }
         // bounce layout: f32 rows | bf16 rows | ids | nd | alpha | beta | margin, B rows each
-        float* b_rows = reinterpret_cast<float*>(d_bounce);
-        uint16_t* b_rows16 = reinterpret_cast<uint16_t*>(d_bounce + (size_t)B * ld * 4);
-        char* b_cols = d_bounce + (size_t)B * ld * 4 + (shadow ? (size_t)B * ld * 2 : 0);
+        float* b_rows = reinterpret_cast<float*>(d_bounce.p);
+        uint16_t* b_rows16 = reinterpret_cast<uint16_t*>(d_bounce.p + (size_t)B * ld * 4);
+        char* b_cols = d_bounce.p + (size_t)B * ld * 4 + (shadow ? (size_t)B * ld * 2 : 0);
         uint64_t* b_ids = reinterpret_cast<uint64_t*>(b_cols);
         float* b_nd = reinterpret_cast<float*>(b_cols + (size_t)B * 8);
         float *b_alpha = b_nd + B, *b_beta = b_nd + 2 * (size_t)B, *b_margin = b_nd + 3 * (size_t)B;
@@ -331,8 +318,6 @@ int compact_store(Index* ix, bool shrink, size_t* out_reclaimed) {
         const hipError_t e = run();
         ix->last_device_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_dev).count();
         if (e != hipSuccess) (void)hipStreamSynchronize(s);
-        (void)hipFree(d_prefix);
-        if (d_bounce) (void)hipFree(d_bounce);
         if (e != hipSuccess) {
             if (moved) ix->store_broken = true;         // rows may be half moved: nothing is served from this handle any more
             return fail(VDB_ERR_DEVICE, "HIP error %d (%s) during the compaction%s", (int)e, hipGetErrorString(e),
