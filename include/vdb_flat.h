@@ -448,6 +448,44 @@ int vdb_flat_search_batch_filtered(vdb_flat_index *h, const float *queries, size
                                    size_t *out_counts);
 
 /*
+ * SEARCH BY STORED ID: "what is near item x?" (no reference counterpart: Index::search, src/index.rs / src/flat_index.rs:52-65,
+ * takes a vector; a caller would get_vector, search with k + 1 and drop the item on the host).  One sentence defines the call: for
+ * query id x and count k the result is what vdb_flat_search_batch returns for the STORED VECTOR of x with k + 1 under the same
+ * mask, with the entry whose id equals x removed if it is there, cut to k -- ids, order, distance bits, counts and errors.
+ * Dropping the last of the k + 1 when x is absent is exact: the top k of "eligible rows without x" is the top k + 1 of "eligible
+ * rows", minus x, cut to k.  The vectors never leave HBM: the row numbers of the ids go up, a kernel gathers the rows into the
+ * query block, the search runs, a second kernel strikes x from each list, the results come down (csrc/kernels_by_id.hip).
+ *  - The strike is by 64-bit id EQUALITY among the first `count` entries of a list: never by position ("drop the first hit" is
+ *    wrong -- under Dot the row itself is often not among the k + 1 best, and under any metric a duplicate with a lower id sorts in
+ *    front of it), never by distance, and no id value is a flag: 2^64 - 1 is a legal stored id and a legal query id.
+ *  - out_counts[b] = min(k_b, eligible rows - [x eligible]).  A query id that the mask makes ineligible is still a valid query:
+ *    it is then simply not in its list.
+ *  - ks: one search with max(ks) + 1 and one strike; each query's answer is the first k_b entries of its struck list (the prefix
+ *    property of vdb_flat_search_batch).  k is clamped to len before the 1 is added, so k = SIZE_MAX cannot wrap.
+ *  - A query id that is not stored -- never added, or removed -- fails the whole batch with VDB_ERR_NOT_FOUND; staged adds and
+ *    removes are flushed first; the message names the first such id; no device search is run.
+ *  - A query id whose row has another dimension than the index (vdb_flat_add keeps such rows on the host) fails with
+ *    VDB_ERR_DIMENSION_MISMATCH, exactly as searching with that vector would.
+ *  - The same query id may appear several times in one batch.
+ *  - Zero-norm rows under Cosine (VDB_ERR_INVALID_VECTOR) and NaN distances (VDB_ERR_NAN) are the errors of the equivalent search.
+ *  - nq is unbounded, as in vdb_flat_search_batch.  Because the search runs with k + 1, k = 112 is served by the large-k range
+ *    (vdb_flat_set_large_k) and k = 1024 by the exact scan: the tier boundaries lie one lower than for a search by vector.
+ *  - Locking and tickets as vdb_flat_search_batch: refused while a submitted search is outstanding.
+ * On a sharded handle the row of x lives on one shard: that shard gathers its queries on its own device, the block goes to
+ * devices[0] device-to-device, the sharded search runs with k + 1 and the strike runs on devices[0]; an id on no shard is
+ * VDB_ERR_NOT_FOUND.  _filtered is the same call under a compiled mask (vdb_flat_search_batch_filtered).
+ * vdb_flat_by_id_stats describes the last call on the handle: [0] queries, [1] queries whose own id was found and struck,
+ * [2] queries cut at k instead, [3] 0.
+ */
+int vdb_flat_search_batch_by_id(vdb_flat_index *h, const uint64_t *query_ids, size_t nq, const size_t *ks, size_t k,
+                                const uint64_t *id_mask, size_t mask_bits, size_t kstride,
+                                uint64_t *out_ids, float *out_dists, size_t *out_counts);
+int vdb_flat_search_batch_by_id_filtered(vdb_flat_index *h, const uint64_t *query_ids, size_t nq, const size_t *ks, size_t k,
+                                         const vdb_meta_mask *mask, size_t kstride,
+                                         uint64_t *out_ids, float *out_dists, size_t *out_counts);
+int vdb_flat_by_id_stats(const vdb_flat_index *h, uint64_t out[4]);
+
+/*
  * Opt-in bf16 SHADOW of the rows for the screening pass (no reference counterpart; results are identical with and without
  * it).  on = 1: the index keeps, next to the f32 rows, their bf16 roundings (+50 % device memory: 2 bytes per element on top
  * of 4) -- exactly the values the screening kernel otherwise produces in registers -- and the filter pass streams THOSE:

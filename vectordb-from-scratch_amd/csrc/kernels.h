@@ -552,4 +552,18 @@ bool hnsw_search_supported(uint32_t dim, uint32_t ef, uint32_t k, uint32_t max_l
 void launch_merge_packed(const int32_t* packed, size_t words_per_part, uint32_t nparts, uint32_t nq, uint32_t k,
                          uint64_t* out_ids, float* out_dists, uint32_t* out_counts, uint32_t* out_status, hipStream_t s);
 
+// ---------------------------------------------------------------- search by stored id (kernels_by_id.hip)
+// out[b * dim .. + dim) = rows[row[b] * ld .. + dim) for b < nq: the stored rows become the dense query block (row[b] < n_rows)
+void launch_gather_rows(const float* rows, uint32_t ld, uint32_t dim, uint32_t n_rows, const uint32_t* row, uint32_t nq, float* out,
+                        hipStream_t s);
+// Query b's result list ids / dists [b * kdev ..], counts[b] entries: the entry whose id equals self_id[b] is removed and the gap
+// closed in order (counts[b] - 1 entries remain, stats[0] += 1); when the id is not among them and counts[b] > k, counts[b] = k
+// (stats[1] += 1).  Nothing at or past counts[b] is written.
+struct StrikeSelfParams {
+    uint64_t* ids; float* dists; uint32_t* counts; uint32_t kdev;
+    const uint64_t* self_id; uint32_t k;
+    uint32_t* stats;                                                       // [2], zeroed by the caller
+};
+void launch_strike_self(const StrikeSelfParams& p, uint32_t nq, hipStream_t s);
+
 }  // namespace vdb

@@ -526,14 +526,42 @@ int vdb_flat_search_batch_device_wait(vdb_flat_index* ix, int ticket) {
 
 }  // extern "C"
 
+// The device rows of the query ids of a search by stored id, after the flush.  An id that is not stored fails the batch
+// (VDB_ERR_NOT_FOUND names the first); an id whose vector could not be searched with -- a row of another dimension -- fails it
+// exactly as the search with that vector would.
+static int resolve_query_ids(vdb_flat_index* ix, const uint64_t* ids, size_t nq, std::vector<uint32_t>* rows) {
+    rows->assign(nq, 0xffffffffu);
+    for (size_t b = 0; b < nq; ++b) {
+        auto it = ix->id2row.find(ids[b]);
+        if (it != ix->id2row.end()) (*rows)[b] = it->second;
+        else if (!ix->misfits.count(ids[b])) return fail(VDB_ERR_NOT_FOUND, "Vector not found: %llu", (unsigned long long)ids[b]);
+    }
+    size_t checked = ~(size_t)0;
+    for (size_t b = 0; b < nq; ++b) {
+        const size_t d = (*rows)[b] == 0xffffffffu ? ix->misfits.find(ids[b])->second.size() : ix->dim;
+        if (d == checked) continue;
+        int rc = query_dim_check(ix, d);
+        if (rc) return rc;
+        checked = d;
+    }
+    // (every check passed: no row of another dimension is stored at all, so every query id has a device row)
+    for (size_t b = 0; b < nq; ++b)
+        if ((*rows)[b] >= ix->n_uploaded) return fail(VDB_ERR_DEVICE, "internal error: row %u of id %llu is not on the device", (*rows)[b], (unsigned long long)ids[b]);
+    return VDB_OK;
+}
+
 // vdb_flat_search_batch and vdb_flat_search_batch_filtered: the id mask comes from the host (id_mask, uploaded here) or is a
 // compiled one already in HBM (cm: the stream is ordered behind its event, nothing is uploaded); everything below is the same.
 // dm (vdb_internal::search_batch_device_mask): mask_bits bits at a device address, written on the handle's own stream.
+// by (vdb_flat_search_batch_by_id; `queries` and `dim` are then unused): the queries are the STORED vectors of these ids.  Their
+// device rows are gathered into the query block on the device, the search runs with one result more, and the entry whose id
+// equals the query's own is struck from each list on the device before the usual copy-out.
 static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks,
                              size_t k, const uint64_t* id_mask, size_t mask_bits, const vdb_meta_mask* cm, size_t kstride,
-                             uint64_t* out_ids, float* out_dists, size_t* out_counts, const uint64_t* dm = nullptr) {
+                             uint64_t* out_ids, float* out_dists, size_t* out_counts, const uint64_t* dm = nullptr,
+                             const uint64_t* by = nullptr) {
     return guarded([&]() -> int {
-    if (!ix || (nq && (!queries || !out_counts))) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (!ix || (nq && ((!queries && !by) || !out_counts))) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
     if (cm) {
         const int dev = ix->multi ? multi_home(ix) : ix->device;
         if (cm->device != dev) return fail(VDB_ERR_INVALID_ARGUMENT, "the compiled mask lives on device %d, the index on device %d", cm->device, dev);
@@ -541,6 +569,7 @@ static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq
     }
     if (ix->multi) {
         if (dm) return refuse_multi("a search under a raw device mask");
+        if (by) return multi_search_by_id(ix, by, nq, ks, k, id_mask, mask_bits, kstride, out_ids, out_dists, out_counts, cm);
         return multi_search_host(ix, queries, nq, dim, ks, k, id_mask, mask_bits, kstride, out_ids, out_dists, out_counts, cm);
     }
     size_t kmax = k;
@@ -554,14 +583,25 @@ static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq
     if (in_flight(ix)) return refuse_in_flight();
     int rc = set_device(ix);
     if (rc) return rc;
+    if (by) memset(ix->by_id_stats, 0, sizeof(ix->by_id_stats));
     if (nq == 0) return VDB_OK;
+    std::vector<uint32_t> self_rows;
+    if (by) {
+        // staged adds and removes first: an id resolves to what the search below sees
+        if (nq > 0x7fffffffull / 2) return fail(VDB_ERR_INVALID_ARGUMENT, "batch too large");
+        if ((rc = flush(ix))) return rc;
+        if ((rc = resolve_query_ids(ix, by, nq, &self_rows))) return rc;
+        dim = ix->dim;
+    }
     // Index::search returns at most len results; clamp before sizing device buffers
     size_t len = ix->n_live + ix->misfits.size();
     size_t kdev = std::min(kmax, std::max<size_t>(len, 1));
+    const size_t kcut = kdev;                                      // by id: what is left of a list after the strike, at most
+    if (by) kdev = std::min(kdev + 1, len);                        // (k was clamped to len first: k = SIZE_MAX cannot wrap)
     hipStream_t s = ix->stream;
     // Small index, a few queries (BASELINE configs[0]: Index::search itself, one query): queries and results go through MAPPED
     // host memory -- the two kernels of the direct path read and write it in place, nothing is copied by the runtime
-    if (direct_eligible(ix, ix->n_rows(), nq, kdev) && ix->misfits.empty() && dim == ix->dim && !id_mask && !cm && !dm) {
+    if (direct_eligible(ix, ix->n_rows(), nq, kdev) && ix->misfits.empty() && dim == ix->dim && !id_mask && !cm && !dm && !by) {
         const size_t qb = nq * dim * sizeof(float), ib = nq * kdev * sizeof(uint64_t), db = nq * kdev * sizeof(float), cb = nq * sizeof(uint32_t);
         const size_t o_i = (qb + 15) & ~(size_t)15, o_d = o_i + ib, o_c = o_d + ((db + 15) & ~(size_t)15);
         if ((rc = ensure_host_io(ix, o_c + cb))) return rc;
@@ -586,7 +626,17 @@ static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq
     if ((rc = ix->cur->w_outi.ensure(nq * std::max<size_t>(kdev, 1)))) return rc;
     if ((rc = ix->cur->w_outd.ensure(nq * std::max<size_t>(kdev, 1)))) return rc;
     if ((rc = ix->cur->w_outc.ensure(nq))) return rc;
-    if (dim) HIP_TRY(hipMemcpyAsync(ix->cur->w_qin.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
+    if (by) {
+        // only the row numbers and the ids go up; the vectors never leave HBM
+        if ((rc = ix->cur->w_selfrow.ensure(nq))) return rc;
+        if ((rc = ix->cur->w_selfid.ensure(nq))) return rc;
+        if ((rc = ix->cur->w_bystat.ensure(2))) return rc;
+        HIP_TRY(hipMemcpyAsync(ix->cur->w_selfrow.p, self_rows.data(), nq * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(ix->cur->w_selfid.p, by, nq * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(ix->cur->w_bystat.p, 0, 8, s));
+        vdb::launch_gather_rows(ix->d_rows, ix->ld, ix->dim, ix->n_uploaded, ix->cur->w_selfrow.p, (uint32_t)nq, ix->cur->w_qin.p, s);
+        HIP_TRY(hipGetLastError());
+    } else if (dim) HIP_TRY(hipMemcpyAsync(ix->cur->w_qin.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
     const uint64_t* d_mask = nullptr;
     if (id_mask) {
         size_t words = (mask_bits + 63) / 64;
@@ -602,6 +652,14 @@ static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq
     rc = search_device(ix, ix->cur->w_qin.p, nq, dim, kdev, d_mask, mask_bits, ix->cur->w_outi.p, ix->cur->w_outd.p, ix->cur->w_outc.p,
                        nullptr);
     if (rc) return rc;
+    uint32_t by_stat[2] = {0, 0};
+    if (by) {
+        vdb::StrikeSelfParams sp{ix->cur->w_outi.p, ix->cur->w_outd.p, ix->cur->w_outc.p, (uint32_t)kdev, ix->cur->w_selfid.p, (uint32_t)kcut,
+                                 ix->cur->w_bystat.p};
+        vdb::launch_strike_self(sp, (uint32_t)nq, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(by_stat, ix->cur->w_bystat.p, 8, hipMemcpyDeviceToHost, s));
+    }
     std::vector<uint32_t> cnt(nq);
     std::vector<uint64_t> ids(nq * std::max<size_t>(kdev, 1));
     std::vector<float> ds(nq * std::max<size_t>(kdev, 1));
@@ -611,6 +669,7 @@ static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq
         HIP_TRY(hipMemcpyAsync(ds.data(), ix->cur->w_outd.p, nq * kdev * 4, hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(hipStreamSynchronize(s));
+    if (by) { ix->by_id_stats[0] = nq; ix->by_id_stats[1] = by_stat[0]; ix->by_id_stats[2] = by_stat[1]; }
     for (size_t b = 0; b < nq; ++b) {
         size_t kb = ks ? ks[b] : k;
         size_t c = std::min<size_t>(cnt[b], kb);   // per-query k: a prefix of the batch-wide result
@@ -637,6 +696,31 @@ int vdb_flat_search_batch_filtered(vdb_flat_index* ix, const float* queries, siz
                                    size_t* out_counts) {
     if (!mask) return fail(VDB_ERR_INVALID_ARGUMENT, "null mask");
     return search_batch_host(ix, queries, nq, dim, ks, k, nullptr, 0, mask, kstride, out_ids, out_dists, out_counts);
+}
+
+// ---- search by stored id (no reference counterpart; search_batch_host with `by`)
+static const uint64_t kNoIds = 0;                                   // an empty batch may come without an id array
+int vdb_flat_search_batch_by_id(vdb_flat_index* ix, const uint64_t* query_ids, size_t nq, const size_t* ks, size_t k,
+                                const uint64_t* id_mask, size_t mask_bits, size_t kstride, uint64_t* out_ids, float* out_dists,
+                                size_t* out_counts) {
+    if (nq && !query_ids) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    return search_batch_host(ix, nullptr, nq, 0, ks, k, id_mask, mask_bits, nullptr, kstride, out_ids, out_dists, out_counts, nullptr,
+                             query_ids ? query_ids : &kNoIds);
+}
+
+int vdb_flat_search_batch_by_id_filtered(vdb_flat_index* ix, const uint64_t* query_ids, size_t nq, const size_t* ks, size_t k,
+                                         const vdb_meta_mask* mask, size_t kstride, uint64_t* out_ids, float* out_dists,
+                                         size_t* out_counts) {
+    if (!mask) return fail(VDB_ERR_INVALID_ARGUMENT, "null mask");
+    if (nq && !query_ids) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    return search_batch_host(ix, nullptr, nq, 0, ks, k, nullptr, 0, mask, kstride, out_ids, out_dists, out_counts, nullptr,
+                             query_ids ? query_ids : &kNoIds);
+}
+
+int vdb_flat_by_id_stats(const vdb_flat_index* ix, uint64_t out[4]) {
+    if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    memcpy(out, ix->by_id_stats, sizeof(ix->by_id_stats));
+    return VDB_OK;
 }
 
 int vdb_flat_search(vdb_flat_index* ix, const float* query, size_t dim, size_t k, uint64_t* out_ids,

@@ -56,6 +56,7 @@ struct Workspace {
     vdbi::DevBuf<uint32_t> w_cnt, w_rowmask, w_flags, w_outc, w_subcnt, w_depth;
     vdbi::DevBuf<uint32_t> w_elig, w_eligblk;                     // sparse-filter route: the eligible-row list; block counts | block offsets | E
     vdbi::DevBuf<float> w_radii; vdbi::DevBuf<uint64_t> w_totals; // range search, host-pointer form: radii in, totals out
+    vdbi::DevBuf<uint32_t> w_selfrow, w_bystat; vdbi::DevBuf<uint64_t> w_selfid;   // search by stored id: device rows and ids of the queries, struck | cut counters
     vdbi::DevBuf<uint16_t> w_qb;                                  // bf16 copy of the padded queries (screening tier)
     // compact block of the queries the screening tier could not certify (re-run by the f32 tier)
     vdbi::DevBuf<float> w2_qp, w2_qnorm, w2_thr, w2_outd, w2_qerr, w2_qg;
@@ -167,6 +168,7 @@ struct vdb_flat_index {
     int sparse_mode = 0;
     uint64_t sparse_last = 0, sparse_E = 0, sparse_count = 0;  // vdb_flat_sparse_stats [0] [1] [2]
     uint64_t range_stats[8] = {0};                          // vdb_flat_range_stats: counters of the last range search
+    uint64_t by_id_stats[4] = {0};                          // vdb_flat_by_id_stats: counters of the last search by stored id (also on a sharded parent)
     bool profile = false; vdbi::Event ev0, ev1;
 
     uint32_t n_rows() const { return (uint32_t)row_ids.size(); }
@@ -230,6 +232,9 @@ int refuse_in_flight();
 int search_device(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, const uint64_t* d_idmask,
                   size_t mask_bits, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                   hipStream_t user_stream);
+// what search_part1 answers for a query of `dim` elements before any device work: VDB_OK, or the dimension error of the first
+// stored row that differs (distance.rs:21-26) -- the check a search by stored id makes for the vector its id names
+int query_dim_check(const Index* ix, size_t dim);
 int range_search_device(Index* ix, const float* d_q, size_t nq, size_t dim, const float* d_radii, const uint64_t* d_idmask,
                         size_t mask_bits, size_t max_results, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                         uint64_t* d_out_totals, hipStream_t user_stream);
@@ -250,6 +255,11 @@ int multi_search_device(vdb_flat_index* P, const float* d_q, size_t nq, size_t d
 int multi_search_host(vdb_flat_index* P, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k, const uint64_t* id_mask,
                       size_t mask_bits, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts,
                       const struct vdb_meta_mask* cm = nullptr);   // cm: a compiled mask on the home device instead of id_mask (vdb_meta.h)
+// vdb_flat_search_batch_by_id on a sharded handle: every shard gathers the rows of ITS query ids on its own device, the blocks
+// meet on devices[0] device-to-device, the ordinary sharded search runs with k + 1 and the strike runs on devices[0]
+int multi_search_by_id(vdb_flat_index* P, const uint64_t* query_ids, size_t nq, const size_t* ks, size_t k, const uint64_t* id_mask,
+                       size_t mask_bits, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts,
+                       const struct vdb_meta_mask* cm);
 int multi_home(const vdb_flat_index* P);                           // devices[0]: where queries, masks and outputs live
 int multi_set_exchange(vdb_flat_index* P, int mode);
 size_t multi_shards(const vdb_flat_index* P);

@@ -143,6 +143,7 @@ struct vdb_multi {
         vdbi::DevBuf<uint64_t> d_mask;                          // the id mask, likewise
         vdbi::DevBuf<int32_t> d_pack;                           // this shard's packed partial results
         vdbi::DevBuf<int32_t> d_gath;                           // [G][words]: RCCL receive buffer (every shard) / peer target (shard 0)
+        vdbi::DevBuf<uint32_t> d_grow; vdbi::DevBuf<float> d_gq; // search by stored id: this shard's query rows, and their vectors gathered (shards off the home device)
         int rc = VDB_OK; bool begun = false; int changed = 0;
         std::string msg; size_t e_exp = 0, e_act = 0;
     };
@@ -150,6 +151,8 @@ struct vdb_multi {
     vdbi::DevBuf<uint32_t> d_status; vdbi::HostBuf<uint32_t> h_status{hipHostMallocDefault};     // devices[0]
     // host-pointer entry point: staging on devices[0]
     vdbi::DevBuf<float> w_qin, w_outd; vdbi::DevBuf<uint64_t> w_outi, w_mask; vdbi::DevBuf<uint32_t> w_outc;
+    // search by stored id: the shards' gathered blocks side by side, each query's place in them, the query ids, struck | cut counters
+    vdbi::DevBuf<float> w_gstage; vdbi::DevBuf<uint32_t> w_place, w_bystat; vdbi::DevBuf<uint64_t> w_selfid;
     uint64_t stats[8] = {0};
     vdbi::Gang gang;
 };
@@ -310,7 +313,7 @@ void multi_destroy(vdb_flat_index* P) {
             (void)hipSetDevice(M->dev[g]);
             if (p.stream) (void)hipStreamSynchronize(p.stream);
             if (r && g < M->comm.size() && M->comm[g]) (void)r->comm_destroy(M->comm[g]);
-            p.d_q.release(); p.d_mask.release(); p.d_pack.release(); p.d_gath.release();
+            p.d_q.release(); p.d_mask.release(); p.d_pack.release(); p.d_gath.release(); p.d_grow.release(); p.d_gq.release();
             p.ev_done.destroy(); p.stream.destroy();
         }
         for (auto* c : M->sh) vdb_flat_destroy(c);
@@ -570,6 +573,67 @@ int multi_search_device(vdb_flat_index* P, const float* d_q, size_t nq, size_t d
     return search_locked(P, d_q, nq, dim, k, d_mask, mask_bits, d_out_ids, d_out_dists, d_out_counts, user_stream);
 }
 
+namespace {
+
+// The second half of the host-pointer searches, under the parent's lock: the query block [nq][dim] is already in (or on its way
+// into, on the home stream) M->w_qin; the mask is staged, the sharded search runs with kdev results per query and the first k_b of
+// each list are copied out.  by (search by stored id): kdev is one more than kcut, and the entry whose id equals by[b] is struck
+// from list b on the home device in between.
+int finish_host(vdb_flat_index* P, size_t nq, size_t dim, const size_t* ks, size_t k, size_t kdev, const uint64_t* id_mask, size_t mask_bits,
+                const vdb_meta_mask* cm, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts, const uint64_t* by = nullptr,
+                size_t kcut = 0) {
+    vdb_multi* M = P->multi;
+    hipStream_t s = M->ps[0].stream;
+    int rc;
+    if ((rc = M->w_outi.ensure(nq * std::max<size_t>(kdev, 1)))) return rc;
+    if ((rc = M->w_outd.ensure(nq * std::max<size_t>(kdev, 1)))) return rc;
+    if ((rc = M->w_outc.ensure(nq))) return rc;
+    const uint64_t* d_mask = nullptr;
+    if (id_mask) {
+        const size_t words = (mask_bits + 63) / 64;
+        if ((rc = M->w_mask.ensure(std::max<size_t>(words, 1)))) return rc;
+        if (words) HIP_TRY(hipMemcpyAsync(M->w_mask.p, id_mask, words * 8, hipMemcpyHostToDevice, s));
+        d_mask = M->w_mask.p;
+    } else if (cm) {                                                   // already on the home device: ordered in front of the wait below
+        HIP_TRY(hipStreamWaitEvent(s, cm->done, 0));
+        d_mask = cm->d_words;
+    }
+    if (by) {
+        if ((rc = M->w_selfid.ensure(nq))) return rc;
+        if ((rc = M->w_bystat.ensure(2))) return rc;
+        HIP_TRY(hipMemcpyAsync(M->w_selfid.p, by, nq * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(M->w_bystat.p, 0, 8, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));                                  // the shards' streams read the staged queries
+    if ((rc = search_locked(P, M->w_qin.p, nq, dim, kdev, d_mask, mask_bits, M->w_outi.p, M->w_outd.p, M->w_outc.p, nullptr))) return rc;
+    uint32_t by_stat[2] = {0, 0};
+    if (by) {
+        vdb::StrikeSelfParams sp{M->w_outi.p, M->w_outd.p, M->w_outc.p, (uint32_t)kdev, M->w_selfid.p, (uint32_t)kcut, M->w_bystat.p};
+        vdb::launch_strike_self(sp, (uint32_t)nq, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(by_stat, M->w_bystat.p, 8, hipMemcpyDeviceToHost, s));
+    }
+    std::vector<uint32_t> cnt(nq);
+    std::vector<uint64_t> ids(nq * std::max<size_t>(kdev, 1));
+    std::vector<float> ds(nq * std::max<size_t>(kdev, 1));
+    HIP_TRY(hipMemcpyAsync(cnt.data(), M->w_outc.p, nq * 4, hipMemcpyDeviceToHost, s));
+    if (kdev) {
+        HIP_TRY(hipMemcpyAsync(ids.data(), M->w_outi.p, nq * kdev * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(ds.data(), M->w_outd.p, nq * kdev * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if (by) { P->by_id_stats[0] = nq; P->by_id_stats[1] = by_stat[0]; P->by_id_stats[2] = by_stat[1]; }
+    for (size_t b = 0; b < nq; ++b) {
+        const size_t kb = ks ? ks[b] : k;
+        const size_t c = std::min<size_t>(cnt[b], kb);                 // per-query k: a prefix of the batch-wide result
+        out_counts[b] = c;
+        for (size_t i = 0; i < c; ++i) { out_ids[b * kstride + i] = ids[b * kdev + i]; out_dists[b * kstride + i] = ds[b * kdev + i]; }
+    }
+    return VDB_OK;
+}
+
+}  // namespace
+
 int multi_search_host(vdb_flat_index* P, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k, const uint64_t* id_mask,
                       size_t mask_bits, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts, const vdb_meta_mask* cm) {
     vdb_multi* M = P->multi;
@@ -585,38 +649,105 @@ int multi_search_host(vdb_flat_index* P, const float* queries, size_t nq, size_t
     hipStream_t s = M->ps[0].stream;
     int rc;
     if ((rc = M->w_qin.ensure(nq * std::max<size_t>(dim, 1)))) return rc;
-    if ((rc = M->w_outi.ensure(nq * std::max<size_t>(kdev, 1)))) return rc;
-    if ((rc = M->w_outd.ensure(nq * std::max<size_t>(kdev, 1)))) return rc;
-    if ((rc = M->w_outc.ensure(nq))) return rc;
     if (dim) HIP_TRY(hipMemcpyAsync(M->w_qin.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
-    const uint64_t* d_mask = nullptr;
-    if (id_mask) {
-        const size_t words = (mask_bits + 63) / 64;
-        if ((rc = M->w_mask.ensure(std::max<size_t>(words, 1)))) return rc;
-        if (words) HIP_TRY(hipMemcpyAsync(M->w_mask.p, id_mask, words * 8, hipMemcpyHostToDevice, s));
-        d_mask = M->w_mask.p;
-    } else if (cm) {                                                   // already on the home device: ordered in front of the wait below
-        HIP_TRY(hipStreamWaitEvent(s, cm->done, 0));
-        d_mask = cm->d_words;
-    }
-    HIP_TRY(hipStreamSynchronize(s));                                  // the shards' streams read the staged queries
-    if ((rc = search_locked(P, M->w_qin.p, nq, dim, kdev, d_mask, mask_bits, M->w_outi.p, M->w_outd.p, M->w_outc.p, nullptr))) return rc;
-    std::vector<uint32_t> cnt(nq);
-    std::vector<uint64_t> ids(nq * std::max<size_t>(kdev, 1));
-    std::vector<float> ds(nq * std::max<size_t>(kdev, 1));
-    HIP_TRY(hipMemcpyAsync(cnt.data(), M->w_outc.p, nq * 4, hipMemcpyDeviceToHost, s));
-    if (kdev) {
-        HIP_TRY(hipMemcpyAsync(ids.data(), M->w_outi.p, nq * kdev * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(ds.data(), M->w_outd.p, nq * kdev * 4, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
+    return finish_host(P, nq, dim, ks, k, kdev, id_mask, mask_bits, cm, kstride, out_ids, out_dists, out_counts);
+}
+
+// Search by stored id.  The row of an id lives on one shard: every shard gathers the rows of ITS query ids on its own device
+// (kernels_by_id.hip) and sends the block to devices[0] device-to-device, where one more gather puts every vector at its query's
+// place in the home query block.  No vector byte passes through host memory: row numbers and ids go up, results come down.
+int multi_search_by_id(vdb_flat_index* P, const uint64_t* query_ids, size_t nq, const size_t* ks, size_t k, const uint64_t* id_mask,
+                       size_t mask_bits, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts, const vdb_meta_mask* cm) {
+    vdb_multi* M = P->multi;
+    size_t kmax = k;
+    if (ks) { kmax = 0; for (size_t b = 0; b < nq; ++b) kmax = std::max(kmax, ks[b]); }
+    if (kmax > kstride) return fail(VDB_ERR_INVALID_ARGUMENT, "kstride %zu smaller than the largest k %zu", kstride, kmax);
+    if (kmax && nq && (!out_ids || !out_dists)) return fail(VDB_ERR_INVALID_ARGUMENT, "null output");
+    std::lock_guard<std::mutex> lk(P->mu);
+    memset(P->by_id_stats, 0, sizeof(P->by_id_stats));
+    if (nq == 0) return VDB_OK;
+    if (nq > 0x3fffffffull) return fail(VDB_ERR_INVALID_ARGUMENT, "batch too large");
+    int rc;
+    // staged adds and removes first: an id resolves to what the search below sees
+    for (auto* c : M->sh) if ((rc = vdb_flat_flush(c))) return rc;
+    HIP_TRY(hipSetDevice(M->home));
+    // id -> (shard, row); an id on no shard fails the batch
+    std::vector<int> shard_of(nq, -1);
+    std::vector<uint32_t> row_of(nq, 0xffffffffu);
+    std::vector<size_t> qdim(nq, 0);
     for (size_t b = 0; b < nq; ++b) {
-        const size_t kb = ks ? ks[b] : k;
-        const size_t c = std::min<size_t>(cnt[b], kb);                 // per-query k: a prefix of the batch-wide result
-        out_counts[b] = c;
-        for (size_t i = 0; i < c; ++i) { out_ids[b * kstride + i] = ids[b * kdev + i]; out_dists[b * kstride + i] = ds[b * kdev + i]; }
+        for (int g = 0; g < M->G && shard_of[b] < 0; ++g) {
+            Index* c = M->sh[g];
+            std::lock_guard<std::mutex> cg(c->mu);
+            auto it = c->id2row.find(query_ids[b]);
+            if (it != c->id2row.end()) { shard_of[b] = g; row_of[b] = it->second; qdim[b] = c->dim; continue; }
+            auto m = c->misfits.find(query_ids[b]);
+            if (m != c->misfits.end()) { shard_of[b] = g; qdim[b] = m->second.size(); }
+        }
+        if (shard_of[b] < 0) return fail(VDB_ERR_NOT_FOUND, "Vector not found: %llu", (unsigned long long)query_ids[b]);
     }
-    return VDB_OK;
+    // a vector that could not be searched with fails the batch as that search would: the first shard (lowest index) that objects
+    size_t checked = ~(size_t)0;
+    for (size_t b = 0; b < nq; ++b) {
+        if (qdim[b] == checked) continue;
+        for (auto* c : M->sh) {
+            std::lock_guard<std::mutex> cg(c->mu);
+            if ((rc = query_dim_check(c, qdim[b]))) return rc;
+        }
+        checked = qdim[b];
+    }
+    const size_t dim = qdim[0];                                        // (every check passed: one dimension, every query id has a device row)
+    // the shards' blocks lie side by side in the staging buffer, shard 0's first
+    std::vector<std::vector<uint32_t>> rows_g((size_t)M->G);
+    std::vector<size_t> off_g((size_t)M->G + 1, 0);
+    std::vector<uint32_t> place(nq);
+    for (size_t b = 0; b < nq; ++b) {
+        if (row_of[b] == 0xffffffffu) return fail(VDB_ERR_DEVICE, "internal error: id %llu has no device row", (unsigned long long)query_ids[b]);
+        ++off_g[(size_t)shard_of[b] + 1];
+    }
+    for (int g = 0; g < M->G; ++g) { rows_g[g].reserve(off_g[g + 1]); off_g[g + 1] += off_g[g]; }
+    for (size_t b = 0; b < nq; ++b) {
+        const int g = shard_of[b];
+        place[b] = (uint32_t)(off_g[g] + rows_g[g].size());
+        rows_g[g].push_back(row_of[b]);
+    }
+    const size_t len = multi_len(P);
+    const size_t kcut = std::min(kmax, std::max<size_t>(len, 1));      // k is clamped to len BEFORE the + 1: k = SIZE_MAX cannot wrap
+    const size_t kdev = std::min(kcut + 1, len);
+    hipStream_t s = M->ps[0].stream;
+    if ((rc = M->w_qin.ensure(nq * dim))) return rc;
+    if ((rc = M->w_gstage.ensure(nq * dim))) return rc;
+    if ((rc = M->w_place.ensure(nq))) return rc;
+    for (auto& p : M->ps) { p.rc = VDB_OK; p.msg.clear(); }
+    M->gang.run([&](int g) {
+        auto& p = M->ps[g];
+        const size_t n_g = rows_g[g].size();
+        if (!n_g) return;
+        Index* c = M->sh[g];
+        float* stage = M->w_gstage.p + off_g[g] * dim;
+        const bool at_home = M->dev[g] == M->home;
+        int r = VDB_OK;
+        if (hipSetDevice(M->dev[g]) != hipSuccess) r = fail(VDB_ERR_DEVICE, "hipSetDevice(%d) failed", M->dev[g]);
+        if (!r) r = p.d_grow.ensure(n_g);
+        if (!r && !at_home) r = p.d_gq.ensure(n_g * dim);
+        if (!r) {
+            hipError_t e = hipMemcpyAsync(p.d_grow.p, rows_g[g].data(), n_g * 4, hipMemcpyHostToDevice, p.stream);
+            if (e == hipSuccess) {
+                vdb::launch_gather_rows(c->d_rows, c->ld, c->dim, c->n_uploaded, p.d_grow.p, (uint32_t)n_g, at_home ? stage : p.d_gq.p, p.stream);
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess && !at_home) e = hipMemcpyPeerAsync(stage, M->home, p.d_gq.p, M->dev[g], n_g * dim * 4, p.stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(p.stream);
+            if (e != hipSuccess) r = fail(VDB_ERR_DEVICE, "gathering the query rows on device %d failed: %s", M->dev[g], hipGetErrorString(e));
+        }
+        if (r) capture_error(p, r);
+    });
+    HIP_TRY(hipSetDevice(M->home));
+    if ((rc = first_error(M))) return rc;
+    HIP_TRY(hipMemcpyAsync(M->w_place.p, place.data(), nq * 4, hipMemcpyHostToDevice, s));
+    vdb::launch_gather_rows(M->w_gstage.p, (uint32_t)dim, (uint32_t)dim, (uint32_t)nq, M->w_place.p, (uint32_t)nq, M->w_qin.p, s);
+    HIP_TRY(hipGetLastError());
+    return finish_host(P, nq, dim, ks, k, kdev, id_mask, mask_bits, cm, kstride, out_ids, out_dists, out_counts, query_ids, kcut);
 }
 
 int multi_home(const vdb_flat_index* P) { return P->multi->home; }

@@ -705,6 +705,18 @@ static int search_sparse(Index* ix, hipStream_t s, const float* d_q, uint32_t nq
     return VDB_OK;
 }
 
+// distance.rs:21-26: the first row whose dimension differs from the query's fails the search
+int query_dim_check(const Index* ix, size_t dim) {
+    if (ix->n_live && ix->dim != dim) return fail_dim(dim, ix->dim);
+    for (auto& kv : ix->misfits)
+        if (kv.second.size() != dim) return fail_dim(dim, kv.second.size());
+    if (!ix->misfits.empty()) {
+        // every stored row has the query's dimension but none is on the device (zero-length rows)
+        return fail(VDB_ERR_INVALID_ARGUMENT, "zero-dimensional vectors are not searchable");
+    }
+    return VDB_OK;
+}
+
 // Part 1: checks, workspace, and the FIRST tier enqueued on the stream -- no host synchronisation unless the search is
 // one of the cases answered completely here (empty store, k = 0, k too large for the MFMA tiers).
 int search_part1(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, const uint64_t* d_idmask,
@@ -730,14 +742,7 @@ int search_part1(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, c
         HIP_TRY(hipStreamSynchronize(s));
         return VDB_OK;
     }
-    // distance.rs:21-26: the first row whose dimension differs from the query's fails the search
-    if (ix->n_live && ix->dim != dim) return fail_dim(dim, ix->dim);
-    for (auto& kv : ix->misfits)
-        if (kv.second.size() != dim) return fail_dim(dim, kv.second.size());
-    if (!ix->misfits.empty()) {
-        // every stored row has the query's dimension but none is on the device (zero-length rows)
-        return fail(VDB_ERR_INVALID_ARGUMENT, "zero-dimensional vectors are not searchable");
-    }
+    if ((rc = query_dim_check(ix, dim))) return rc;
     if (ix->metric == vdb::COSINE) {
         if ((rc = ensure_zero_count(ix))) return rc;
         if (ix->zero_live)   // distance.rs:51-55 aborts the whole search (flat_index.rs:57-60)

@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from . import _ffi
-from .error import DimensionMismatch, IndexError_, InvalidVector, NanDistance
+from .error import DimensionMismatch, IndexError_, InvalidVector, NanDistance, VectorNotFound
 from .vector import DistanceMetric, Vector
 
 
@@ -280,6 +280,54 @@ class GpuFlatIndex(Index):
         if rc:
             _raise(rc)
         return out_ids, out_d, counts
+
+    # ---- search by stored id (include/vdb_flat.h vdb_flat_search_batch_by_id; no reference counterpart)
+    def search_batch_by_id(self, ids, k, id_mask=None, mask_bits=0, compiled_mask=None):
+        """The nearest neighbours of STORED vectors, the vector itself left out: for query id x, what search_batch_arrays
+        returns for the stored vector of x with k + 1, the entry whose id equals x removed if it is there, cut to k.  The
+        vectors never leave the device.  ids: u64 array of stored ids (repeats allowed); k an int or a per-query array.
+        Returns the arrays of search_batch_arrays.  An id that is not stored raises VectorNotFound for the whole batch."""
+        if compiled_mask is not None and id_mask is not None:
+            raise ValueError("pass id_mask or compiled_mask, not both")
+        qid = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        nq = qid.size
+        if np.isscalar(k):
+            ks_ptr, kscalar, kmax = None, int(k), int(k)
+        else:
+            ks = np.ascontiguousarray(k, dtype=np.uintp)
+            if ks.shape != (nq,):
+                raise ValueError(f"k must be a scalar or hold one value per query id ({nq}), not {ks.shape}")
+            ks_ptr = ks.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t))
+            kscalar, kmax = 0, int(ks.max()) if ks.size else 0
+        kstride = max(kmax, 1)
+        out_ids = np.zeros((nq, kstride), dtype=np.uint64)
+        out_d = np.zeros((nq, kstride), dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uintp)
+        cp = counts.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t))
+        if compiled_mask is not None:
+            rc = self._L.vdb_flat_search_batch_by_id_filtered(self._h, _u64p(qid), nq, ks_ptr, kscalar, compiled_mask.handle,
+                                                              kstride, _u64p(out_ids), _fp(out_d), cp)
+        else:
+            mask_ptr = None
+            if id_mask is not None:
+                m = np.ascontiguousarray(id_mask, dtype=np.uint64)
+                mask_ptr = _u64p(m)
+            rc = self._L.vdb_flat_search_batch_by_id(self._h, _u64p(qid), nq, ks_ptr, kscalar, mask_ptr, int(mask_bits),
+                                                     kstride, _u64p(out_ids), _fp(out_d), cp)
+        if rc == _ffi.ERR_NOT_FOUND:
+            raise VectorNotFound(int(_ffi.last_error()[0].rsplit(": ", 1)[-1]))
+        if rc:
+            _raise(rc)
+        return out_ids, out_d, counts
+
+    def by_id_stats(self):
+        """The last search_batch_by_id: [0] queries, [1] queries whose own id was found in their list and struck, [2] queries
+        whose list was cut at k instead, [3] 0."""
+        out = (ctypes.c_uint64 * 4)()
+        rc = self._L.vdb_flat_by_id_stats(self._h, out)
+        if rc:
+            _raise(rc)
+        return [int(x) for x in out]
 
     # ---- bulk build and device-resident entry points
     def add_bulk(self, rows, ids=None, first_id=0):

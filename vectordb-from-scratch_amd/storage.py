@@ -549,6 +549,37 @@ class VectorStore:
         ids, dists, counts, _ = self._index.range_search_batch(query.data[None, :], float(radius), int(limit), id_mask=mask, mask_bits=bits)
         return self._map([(int(ids[0, i]), dists[0, i]) for i in range(int(counts[0]))])
 
+    # ---- "what is near item X?" (GpuFlatIndex.search_batch_by_id; no reference counterpart)
+    def search_similar(self, id, k, flt=None):
+        """The k stored vectors nearest to the stored vector `id`, that vector itself left out, nearest first."""
+        return self.search_similar_batch([id], k, flt)[0]
+
+    def search_similar_batch(self, ids, k, flt=None):
+        """search_similar for several ids in one device call; the vectors never leave the GPU.  An unknown id raises
+        VectorNotFound.  flt is a PRE-filter (the mask of compile_filter, or the device filter when set_device_filter is on),
+        as in search_batch_prefiltered: a filtered-out id may still be asked about, it is simply in nobody's answer."""
+        if not isinstance(self._index, GpuFlatIndex):
+            raise ValueError("search_similar needs a GpuFlatIndex")
+        internal = []
+        for id in ids:
+            i = self._internal_of(id)
+            if i is None:
+                raise VectorNotFound(id)
+            internal.append(i)
+        if not internal:
+            return []
+        q = np.asarray(internal, dtype=np.uint64)
+        cm = self.compile_filter_device(flt) if flt is not None and self._table is not None else None
+        if cm is not None:
+            try:
+                out_ids, dists, counts = self._index.search_batch_by_id(q, int(k), compiled_mask=cm)
+            finally:
+                cm.release()
+        else:
+            mask, bits = self.compile_filter(flt) if flt is not None else (None, 0)
+            out_ids, dists, counts = self._index.search_batch_by_id(q, int(k), id_mask=mask, mask_bits=bits)
+        return [self._map([(int(out_ids[b, i]), dists[b, i]) for i in range(int(counts[b]))]) for b in range(len(internal))]
+
     def search_batch_prefiltered(self, queries, flt):
         if self.is_empty():
             return [[] for _ in queries]
