@@ -486,6 +486,46 @@ int vdb_flat_search_batch_by_id_filtered(vdb_flat_index *h, const uint64_t *quer
 int vdb_flat_by_id_stats(const vdb_flat_index *h, uint64_t out[4]);
 
 /*
+ * ONE NEAREST ROW PER GROUP: the k nearest documents, videos, products of a store of chunked items, each represented by its nearest
+ * row (no reference counterpart: a caller of Index::search over-fetches by a guessed factor and dedupes on the host, the failure of
+ * the 3x post-filter of storage.rs:249-290).  One sentence defines the call: for query q, count k, column `slot` of `table` and an
+ * optional id mask, take the FULL ranking of the eligible rows -- what vdb_flat_search_batch returns under that mask with k = len,
+ * ascending by (distance, unsigned id) -- walk it from the front, keep a row iff its group code is -1 or no earlier row of the
+ * ranking has the same code, stop after k kept rows: ids, order, distance bits, counts and errors.
+ *  - Group code of id i: codes[i] of the column as vdb_meta_compile reads it; -1 when the row has no such field or i lies at or
+ *    beyond the column's length.
+ *  - ROWS WITH CODE -1 ARE NEVER COLLAPSED: each is its own group.  A caller who wants them gone ANDs an EXISTS on the slot into
+ *    the filter; the opposite default could not be undone.
+ *  - The representative of a group is its first row in the ranking; exact duplicates at one distance are decided by the lower id.  A
+ *    mask that removes the representative makes the group's next eligible row the representative.
+ *  - out_counts[b] = min(k_b, distinct groups among the eligible rows, each -1 row counting as one).  out_codes (may be NULL)
+ *    receives the group code of every returned row, in the layout of out_ids.
+ *  - ks: the answer for k_b is the first k_b entries of the answer for max(ks).
+ * The result is exact and does not depend on how it was reached.  Stage A searches the batch at depth
+ * vdb_flat_distinct_depth(kmax, len, 0) = min(len, min(1024, max(4 kmax, 32))) and collapses every list on the device; a query that
+ * kept kmax rows, or whose list came back short, is complete.  Stage B searches the others at vdb_flat_distinct_depth(kmax, len, 1)
+ * = min(len, 1024).  Stage C, for a query whose 1024 nearest rows hold fewer than kmax groups, repeats: a mask without the groups
+ * already answered is written on the device, the query is searched under it, the new groups are appended -- at most kmax rounds.
+ * Errors, all before any device search: a null table or a slot never written, k or max(ks) above 1024, a table (or compiled mask) on
+ * another device than the handle's (devices[0] of a sharded handle), an index that has EVER held an id at or above 2^32 (the table
+ * cannot describe such ids): VDB_ERR_INVALID_ARGUMENT.  An empty index or k = 0 gives counts 0 before any of these.  Everything else
+ * is the error of the equivalent search.  Staged adds and the table's staged column writes are flushed first; the handle's stream
+ * is ordered behind the table's by an event.  Locking and tickets as vdb_flat_search_batch; the table stays locked for the call.
+ * Plain and sharded handles (the collapse and the exclusion masks run on devices[0]).
+ * vdb_flat_distinct_stats describes the last call: [0] queries, [1] completed by stage A, [2] by stage B, [3] by exclusion rounds,
+ * [4] exclusion searches run, [5] depth of stage A, [6] depth of stage B, [7] rows returned in total.
+ * vdb_flat_distinct_depth needs no handle and no device; any other stage gives 0.
+ */
+int vdb_flat_search_batch_distinct(vdb_flat_index *h, const float *queries, size_t nq, size_t dim, const size_t *ks, size_t k,
+                                   vdb_meta_table *table, uint32_t slot, const uint64_t *id_mask, size_t mask_bits, size_t kstride,
+                                   uint64_t *out_ids, float *out_dists, int32_t *out_codes, size_t *out_counts);
+int vdb_flat_search_batch_distinct_filtered(vdb_flat_index *h, const float *queries, size_t nq, size_t dim, const size_t *ks, size_t k,
+                                            vdb_meta_table *table, uint32_t slot, const vdb_meta_mask *mask, size_t kstride,
+                                            uint64_t *out_ids, float *out_dists, int32_t *out_codes, size_t *out_counts);
+int vdb_flat_distinct_stats(const vdb_flat_index *h, uint64_t out[8]);
+size_t vdb_flat_distinct_depth(size_t k, size_t len, int stage);
+
+/*
  * Opt-in bf16 SHADOW of the rows for the screening pass (no reference counterpart; results are identical with and without
  * it).  on = 1: the index keeps, next to the f32 rows, their bf16 roundings (+50 % device memory: 2 bytes per element on top
  * of 4) -- exactly the values the screening kernel otherwise produces in registers -- and the filter pass streams THOSE:

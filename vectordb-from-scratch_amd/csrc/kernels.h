@@ -566,4 +566,28 @@ struct StrikeSelfParams {
 };
 void launch_strike_self(const StrikeSelfParams& p, uint32_t nq, hipStream_t s);
 
+// ---------------------------------------------------------------- one nearest row per group (kernels_distinct.hip)
+constexpr uint32_t DISTINCT_MAX_LIST = 1024;                               // entries of one list, and rows of one answer, at most
+// List j -- ids / dists [j * stride ..], counts[j] entries, ascending by (distance, id) -- collapsed by the group code of its ids
+// (codes[id] when id < codes_len, else -1) into answer row dest[j] (j when dest is null; >= n_answers: nothing is done): entry i is
+// kept iff its code is -1 or no earlier entry of the list has it.  The first k kept go to out_* [b * kstride ..] behind the
+// kept[b] rows already there (append) or from slot 0; the rest of the row is padded (~0, NaN, -1).  kept[b] = rows in the answer,
+// complete[b] = 1 when that is k, or counts[j] < depth, or exhaustive (the depth covered every row of the index).
+struct DistinctFirstParams {
+    const uint64_t* ids; const float* dists; const uint32_t* counts; uint32_t stride, depth, exhaustive;
+    const int32_t* codes; uint64_t codes_len;
+    const uint32_t* dest; uint32_t n_answers;
+    uint32_t k, kstride, append;
+    uint64_t* out_ids; float* out_dists; int32_t* out_codes; uint32_t* kept; uint32_t* complete;
+};
+void launch_distinct_first(const DistinctFirstParams& p, uint32_t n_lists, hipStream_t s);
+// mask[0, ceil(bits / 64)) = src (all ones when null) over [0, bits), minus every id whose code is among the kept[answer] codes
+// of answer row `answer` (out_codes), minus every kept id of that row whose code is -1; bits at or beyond `bits` are clear
+struct ExcludeGroupsParams {
+    const uint64_t* src; uint64_t bits; uint64_t* mask;
+    const int32_t* codes; uint64_t codes_len;
+    const uint64_t* out_ids; const int32_t* out_codes; const uint32_t* kept; uint32_t kstride, answer;
+};
+void launch_exclude_groups(const ExcludeGroupsParams& p, uint32_t n_cu, hipStream_t s);
+
 }  // namespace vdb

@@ -202,6 +202,7 @@ int vdb_flat_add_bulk_device(vdb_flat_index* ix, const uint64_t* ids, uint64_t f
         uint32_t row = first + (uint32_t)i;
         if (row && id <= ix->row_ids.back()) ix->ids_monotone = false;
         ix->row_ids.push_back(id);
+        ix->id_bound = std::max(ix->id_bound, id == ~0ull ? id : id + 1);
         if ((row >> 5) >= ix->live.size()) ix->live.push_back(0u);
         ix->live[row >> 5] |= 1u << (row & 31);
         ++ix->n_live;
@@ -720,6 +721,91 @@ int vdb_flat_search_batch_by_id_filtered(vdb_flat_index* ix, const uint64_t* que
 int vdb_flat_by_id_stats(const vdb_flat_index* ix, uint64_t out[4]) {
     if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
     memcpy(out, ix->by_id_stats, sizeof(ix->by_id_stats));
+    return VDB_OK;
+}
+
+// ---- one nearest row per group (no reference counterpart; vdb_search.cpp distinct_drive)
+size_t vdb_flat_distinct_depth(size_t k, size_t len, int stage) {
+    const size_t cap = vdb::DISTINCT_MAX_LIST;
+    if (stage == 0) return std::min(len, std::min(cap, std::max(k > cap / 4 ? cap : 4 * k, (size_t)32)));
+    if (stage == 1) return std::min(len, cap);
+    return 0;
+}
+
+static int search_distinct_host(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k,
+                                vdb_meta_table* table, uint32_t slot, const uint64_t* id_mask, size_t mask_bits, const vdb_meta_mask* cm,
+                                size_t kstride, uint64_t* out_ids, float* out_dists, int32_t* out_codes, size_t* out_counts) {
+    return guarded([&]() -> int {
+    if (!ix || (nq && (!queries || !out_counts))) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    size_t kmax = k;
+    if (ks) {
+        kmax = 0;
+        for (size_t b = 0; b < nq; ++b) kmax = std::max(kmax, ks[b]);
+    }
+    if (kmax > kstride) return fail(VDB_ERR_INVALID_ARGUMENT, "kstride %zu smaller than the largest k %zu", kstride, kmax);
+    if (kmax && nq && (!out_ids || !out_dists)) return fail(VDB_ERR_INVALID_ARGUMENT, "null output");
+    std::lock_guard<std::mutex> g(ix->mu);                         // (a sharded parent's lock too: the shards are searched under it)
+    if (!ix->multi && in_flight(ix)) return refuse_in_flight();
+    memset(ix->distinct_stats, 0, sizeof(ix->distinct_stats));
+    ix->distinct_stats[0] = nq;
+    if (nq == 0) return VDB_OK;
+    const int dev = ix->multi ? multi_home(ix) : ix->device;
+    const size_t len = ix->multi ? multi_len(ix) : ix->n_live + ix->misfits.size();
+    if (len == 0 || kmax == 0) {                                   // storage.rs:218-220: empty store -> Ok(vec![]) before any check
+        for (size_t b = 0; b < nq; ++b) out_counts[b] = 0;
+        return VDB_OK;
+    }
+    // every refusal below comes before any device search
+    int tdev = 0, rc;
+    if ((rc = meta_column_check(table, slot, &tdev))) return rc;
+    if (kmax > vdb::DISTINCT_MAX_LIST) return fail(VDB_ERR_INVALID_ARGUMENT, "a search by group returns at most %u rows per query, not %zu", vdb::DISTINCT_MAX_LIST, kmax);
+    if (tdev != dev) return fail(VDB_ERR_INVALID_ARGUMENT, "the metadata table lives on device %d, the index on device %d", tdev, dev);
+    const uint64_t id_bound = ix->multi ? multi_id_bound(ix) : ix->id_bound;
+    if (id_bound > (1ull << 32)) return fail(VDB_ERR_INVALID_ARGUMENT, "the index has held an id at or above 2^32: a metadata table cannot describe it");
+    if (cm) {
+        if (cm->device != dev) return fail(VDB_ERR_INVALID_ARGUMENT, "the compiled mask lives on device %d, the index on device %d", cm->device, dev);
+        mask_bits = cm->bits;
+    }
+    if (nq > 0x3fffffffull) return fail(VDB_ERR_INVALID_ARGUMENT, "batch too large");
+    HIP_TRY(hipSetDevice(dev));
+    // staged adds first, then the table's staged column writes; the handle's stream waits for those by an event
+    if ((rc = ix->multi ? multi_flush_nolock(ix) : flush(ix))) return rc;
+    hipStream_t s = ix->multi ? multi_home_stream(ix) : (hipStream_t)ix->stream;
+    MetaColumn col;
+    if ((rc = meta_column_acquire(table, slot, s, &col))) return rc;
+    struct Release { vdb_meta_table* t; ~Release() { meta_column_release(t); } } release{table};
+    DistinctArgs a{queries, nq, dim, ks, k, kmax, len, col.d_codes, col.len, id_mask, mask_bits, cm, id_bound, (uint32_t)ix->n_cu,
+                   kstride, out_ids, out_dists, out_codes, out_counts};
+    DistinctSearch search;
+    if (ix->multi)
+        search = [&](const float* d_q, size_t n, size_t depth, const uint64_t* d_mask, size_t bits, uint64_t* oi, float* od, uint32_t* oc) {
+            return multi_search_nolock(ix, d_q, n, dim, depth, d_mask, bits, oi, od, oc);
+        };
+    else
+        search = [&](const float* d_q, size_t n, size_t depth, const uint64_t* d_mask, size_t bits, uint64_t* oi, float* od, uint32_t* oc) {
+            return search_device(ix, d_q, n, dim, depth, d_mask, bits, oi, od, oc, nullptr);
+        };
+    return distinct_drive(ix, s, search, a);
+    });
+}
+
+int vdb_flat_search_batch_distinct(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k,
+                                   vdb_meta_table* table, uint32_t slot, const uint64_t* id_mask, size_t mask_bits, size_t kstride,
+                                   uint64_t* out_ids, float* out_dists, int32_t* out_codes, size_t* out_counts) {
+    return search_distinct_host(ix, queries, nq, dim, ks, k, table, slot, id_mask, mask_bits, nullptr, kstride, out_ids, out_dists, out_codes,
+                                out_counts);
+}
+
+int vdb_flat_search_batch_distinct_filtered(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k,
+                                            vdb_meta_table* table, uint32_t slot, const vdb_meta_mask* mask, size_t kstride,
+                                            uint64_t* out_ids, float* out_dists, int32_t* out_codes, size_t* out_counts) {
+    if (!mask) return fail(VDB_ERR_INVALID_ARGUMENT, "null mask");
+    return search_distinct_host(ix, queries, nq, dim, ks, k, table, slot, nullptr, 0, mask, kstride, out_ids, out_dists, out_codes, out_counts);
+}
+
+int vdb_flat_distinct_stats(const vdb_flat_index* ix, uint64_t out[8]) {
+    if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    memcpy(out, ix->distinct_stats, sizeof(ix->distinct_stats));
     return VDB_OK;
 }
 

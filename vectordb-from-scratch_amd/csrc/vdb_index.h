@@ -86,6 +86,15 @@ struct Workspace {
     bool busy = false;                                      // submitted, not yet waited for
 };
 
+// What one search by group owns on the device (vdb_search.cpp distinct_drive): the query block, the ranked lists
+// of the search in hand, the answers, and -- only once an exclusion round runs -- the mask of that round.
+struct DistinctWs {
+    vdbi::DevBuf<float> q, q2, ld, ad;                            // queries | the incomplete ones, dense | list and answer distances
+    vdbi::DevBuf<uint64_t> li, ai, mask_in, xmask;                // list and answer ids | the caller's host mask | the exclusion mask
+    vdbi::DevBuf<int32_t> ac;                                     // answer codes
+    vdbi::DevBuf<uint32_t> lc, kept, complete, sel;               // list counts | rows per answer | completeness flags | the incomplete queries
+};
+
 // Diagnostic knobs: ablation switches, A/B kernel variants, scaled certificates, sample-size overrides.  Several of them
 // VOID the exact-result guarantee, so they exist only in the diagnostics build (-DVDB_DIAG -> libvdbflat_diag.so,
 // `make diag`), where vdb_flat_create reads them from the environment ONCE into the handle.  In the release library
@@ -169,6 +178,9 @@ struct vdb_flat_index {
     uint64_t sparse_last = 0, sparse_E = 0, sparse_count = 0;  // vdb_flat_sparse_stats [0] [1] [2]
     uint64_t range_stats[8] = {0};                          // vdb_flat_range_stats: counters of the last range search
     uint64_t by_id_stats[4] = {0};                          // vdb_flat_by_id_stats: counters of the last search by stored id (also on a sharded parent)
+    uint64_t distinct_stats[8] = {0};                       // vdb_flat_distinct_stats: counters of the last search by group (also on a sharded parent)
+    DistinctWs dws;                                         // its device buffers (a sharded parent's live on devices[0])
+    uint64_t id_bound = 0;                                  // 1 + the largest id ever added (saturating), raised at add time only: never lowered by a remove
     bool profile = false; vdbi::Event ev0, ev1;
 
     uint32_t n_rows() const { return (uint32_t)row_ids.size(); }
@@ -239,6 +251,20 @@ int range_search_device(Index* ix, const float* d_q, size_t nq, size_t dim, cons
                         size_t mask_bits, size_t max_results, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                         uint64_t* d_out_totals, hipStream_t user_stream);
 
+// One nearest row per group (vdb_flat_search_batch_distinct).  The driver is the same on a plain and on a sharded handle: H owns
+// the buffers and the counters, s is the stream its kernels run on (the home device is current), `search` is the handle's ordinary
+// device-pointer search -- outputs complete when it returns -- and everything in DistinctArgs has passed the entry point's checks.
+struct DistinctArgs {
+    const float* queries; size_t nq, dim; const size_t* ks; size_t k, kmax, len;
+    const int32_t* d_codes; size_t codes_len;
+    const uint64_t* id_mask; size_t mask_bits; const struct vdb_meta_mask* cm;
+    uint64_t id_bound; uint32_t n_cu;
+    size_t kstride; uint64_t* out_ids; float* out_dists; int32_t* out_codes; size_t* out_counts;
+};
+using DistinctSearch = std::function<int(const float* d_q, size_t nq, size_t depth, const uint64_t* d_mask, size_t mask_bits,
+                                         uint64_t* d_ids, float* d_dists, uint32_t* d_counts)>;
+int distinct_drive(Index* H, hipStream_t s, const DistinctSearch& search, const DistinctArgs& a);
+
 // ---- vdb_multi.cpp: one index over several GPUs in one process (the parent handle dispatches here)
 int multi_create(int metric, const int* devices, size_t n, vdb_flat_index** out);
 void multi_destroy(vdb_flat_index* P);
@@ -260,6 +286,14 @@ int multi_search_host(vdb_flat_index* P, const float* queries, size_t nq, size_t
 int multi_search_by_id(vdb_flat_index* P, const uint64_t* query_ids, size_t nq, const size_t* ks, size_t k, const uint64_t* id_mask,
                        size_t mask_bits, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts,
                        const struct vdb_meta_mask* cm);
+// vdb_flat_search_batch_distinct on a sharded handle (the caller holds the parent's lock): the shards' staged adds flushed; the
+// stream of devices[0] that distinct_drive's kernels run on; the sharded search behind a host wait for that stream (the shards'
+// streams read what it wrote); the largest id bound of the shards
+int multi_flush_nolock(vdb_flat_index* P);
+hipStream_t multi_home_stream(const vdb_flat_index* P);
+int multi_search_nolock(vdb_flat_index* P, const float* d_q, size_t nq, size_t dim, size_t k, const uint64_t* d_mask, size_t mask_bits,
+                        uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts);
+uint64_t multi_id_bound(const vdb_flat_index* P);
 int multi_home(const vdb_flat_index* P);                           // devices[0]: where queries, masks and outputs live
 int multi_set_exchange(vdb_flat_index* P, int mode);
 size_t multi_shards(const vdb_flat_index* P);

@@ -56,9 +56,17 @@ struct vdb_meta_table {
     Staged<uint64_t> present;
     std::vector<std::unique_ptr<vdb_meta_mask>> masks;              // every mask ever handed out (owned here)
     std::vector<vdb_meta_mask*> free_masks;                         // released ones, most recently released last
+    Event col_ready;                                                // meta_column_acquire: recorded behind the uploads a grouping search waits for
 };
 
 namespace {
+
+// what was written since the last upload reaches the device, on the table's stream (the caller holds the table's lock)
+int upload_staged(vdb_meta_table* t, hipStream_t s) {
+    int rc;
+    for (auto& c : t->cols) if (c && (rc = c->upload(s))) return rc;
+    return t->present.upload(s);
+}
 
 // a mask of at least `words` words from the pool (the most recently released one that is large enough, else any released one,
 // regrown), or a new one
@@ -193,8 +201,7 @@ int vdb_meta_compile(vdb_meta_table* t, const vdb_meta_op* ops, size_t n_ops, si
     hipStream_t s = t->stream;
     // 2. what was written since the last compile
     int rc;
-    for (auto& c : t->cols) if (c && (rc = c->upload(s))) return rc;
-    if ((rc = t->present.upload(s))) return rc;
+    if ((rc = upload_staged(t, s))) return rc;
     // 3. the mask, its program (the leaves take their column's address and length now), the zeroed count, one launch
     const size_t words = (mask_bits + 63) / 64;
     vdb_meta_mask* m = nullptr;
@@ -263,3 +270,31 @@ int vdb_meta_mask_release(vdb_meta_mask* m) {
 }
 
 }  // extern "C"
+
+namespace vdbi {
+
+int meta_column_check(vdb_meta_table* t, uint32_t slot, int* device) {
+    if (!t) return fail(VDB_ERR_INVALID_ARGUMENT, "null table");
+    std::lock_guard<std::mutex> g(t->mu);
+    if (slot >= t->cols.size() || !t->cols[slot]) return fail(VDB_ERR_INVALID_ARGUMENT, "slot %u was never written", slot);
+    *device = t->device;
+    return VDB_OK;
+}
+
+int meta_column_acquire(vdb_meta_table* t, uint32_t slot, hipStream_t waiter, MetaColumn* out) {
+    std::unique_lock<std::mutex> g(t->mu);
+    if (slot >= t->cols.size() || !t->cols[slot]) return fail(VDB_ERR_INVALID_ARGUMENT, "slot %u was never written", slot);
+    int rc;
+    if ((rc = upload_staged(t, t->stream))) return rc;
+    if ((rc = t->col_ready.create(hipEventDisableTiming))) return rc;
+    HIP_TRY(hipEventRecord(t->col_ready, t->stream));
+    HIP_TRY(hipStreamWaitEvent(waiter, t->col_ready, 0));
+    out->d_codes = t->cols[slot]->d;
+    out->len = t->cols[slot]->d ? t->cols[slot]->h.size() : 0;
+    g.release();                                                    // stays locked: meta_column_release
+    return VDB_OK;
+}
+
+void meta_column_release(vdb_meta_table* t) { t->mu.unlock(); }
+
+}  // namespace vdbi

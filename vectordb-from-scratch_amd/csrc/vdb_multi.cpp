@@ -750,6 +750,30 @@ int multi_search_by_id(vdb_flat_index* P, const uint64_t* query_ids, size_t nq, 
     return finish_host(P, nq, dim, ks, k, kdev, id_mask, mask_bits, cm, kstride, out_ids, out_dists, out_counts, query_ids, kcut);
 }
 
+// ---- one nearest row per group: the driver is vdb_search.cpp's distinct_drive; a sharded handle only lends it these
+int multi_flush_nolock(vdb_flat_index* P) {
+    for (auto* c : P->multi->sh) { int rc = vdb_flat_flush(c); if (rc) return rc; }
+    HIP_TRY(hipSetDevice(P->multi->home));
+    return VDB_OK;
+}
+
+hipStream_t multi_home_stream(const vdb_flat_index* P) { return P->multi->ps[0].stream; }
+
+int multi_search_nolock(vdb_flat_index* P, const float* d_q, size_t nq, size_t dim, size_t k, const uint64_t* d_mask, size_t mask_bits,
+                        uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts) {
+    HIP_TRY(hipSetDevice(P->multi->home));
+    HIP_TRY(hipStreamSynchronize(P->multi->ps[0].stream));             // the shards' streams read the queries and the mask
+    int rc = search_locked(P, d_q, nq, dim, k, d_mask, mask_bits, d_out_ids, d_out_dists, d_out_counts, nullptr);
+    (void)hipSetDevice(P->multi->home);
+    return rc;
+}
+
+uint64_t multi_id_bound(const vdb_flat_index* P) {
+    uint64_t m = 0;
+    for (auto* c : P->multi->sh) { std::lock_guard<std::mutex> cg(c->mu); m = std::max(m, c->id_bound); }
+    return m;
+}
+
 int multi_home(const vdb_flat_index* P) { return P->multi->home; }
 
 int multi_set_exchange(vdb_flat_index* P, int mode) {

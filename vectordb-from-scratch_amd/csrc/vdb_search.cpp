@@ -7,6 +7,7 @@
 #include <limits>
 
 #include "vdb_index.h"
+#include "vdb_meta.h"
 
 namespace vdbi {
 
@@ -1185,6 +1186,131 @@ void publish_stats(Index* ix) { memcpy(ix->stats, ix->cur->stats, sizeof(ix->sta
 // searches submitted and not yet waited for (vdb_flat_search_batch_device_submit): the row store must not change under them
 bool in_flight(const Index* ix) { return ix->wsv && (ix->wsv[0].busy || ix->wsv[1].busy); }
 int refuse_in_flight() { return fail(VDB_ERR_INVALID_ARGUMENT, "a submitted search is still in flight on this handle: wait for it first"); }
+
+// ---------------------------------------------------------------------------------------------
+// One nearest row per group (vdb_flat_search_batch_distinct).  The answer of a query is defined on its FULL
+// ranking; a search returns a prefix of it, so the driver only decides how deep it has to look, in three stages that are all exact:
+//   A  one search of the whole batch at depth dA, each list collapsed on the device (distinct_first_kernel).  The collapse of a
+//      prefix is a prefix of the collapse of the ranking: a query whose list kept k rows, or came back short, is complete.
+//   B  the incomplete queries, gathered into a dense block, at depth dB = min(len, 1024), collapsed from scratch into their places.
+//   C  a query still incomplete has one group owning its whole list.  Exclusion rounds: a mask without the groups (and the
+//      group-less rows) already answered, one search of that query under it, the list appended.  The ranking under "mask minus
+//      those rows" is the ranking with those rows deleted, and a deleted row could only have been dropped by the walk, so the
+//      concatenation is the walk of the full ranking.  Every round adds a group or comes back short: at most k rounds.
+// One host read of the flags per stage and per round; ids, distances and codes stay on the device until the end.
+// ---------------------------------------------------------------------------------------------
+int distinct_drive(Index* H, hipStream_t s, const DistinctSearch& search, const DistinctArgs& a) {
+    DistinctWs& W = H->dws;
+    uint64_t* st = H->distinct_stats;
+    const size_t nq = a.nq, dim = a.dim, kmax = a.kmax;
+    const size_t dA = vdb_flat_distinct_depth(kmax, a.len, 0), dB = vdb_flat_distinct_depth(kmax, a.len, 1);
+    st[0] = nq; st[5] = dA; st[6] = dB;
+    int rc;
+    if ((rc = W.q.ensure(nq * std::max<size_t>(dim, 1))) || (rc = W.li.ensure(nq * dA)) || (rc = W.ld.ensure(nq * dA)) || (rc = W.lc.ensure(nq)) ||
+        (rc = W.ai.ensure(nq * kmax)) || (rc = W.ad.ensure(nq * kmax)) || (rc = W.ac.ensure(nq * kmax)) || (rc = W.kept.ensure(nq)) ||
+        (rc = W.complete.ensure(nq)) || (rc = W.sel.ensure(nq)))
+        return rc;
+    if (dim) HIP_TRY(hipMemcpyAsync(W.q.p, a.queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
+    const uint64_t* d_mask = nullptr;
+    size_t mask_bits = a.mask_bits;
+    if (a.id_mask) {
+        const size_t words = (mask_bits + 63) / 64;
+        if ((rc = W.mask_in.ensure(std::max<size_t>(words, 1)))) return rc;
+        if (words) HIP_TRY(hipMemcpyAsync(W.mask_in.p, a.id_mask, words * 8, hipMemcpyHostToDevice, s));
+        d_mask = W.mask_in.p;
+    } else if (a.cm) {
+        HIP_TRY(hipStreamWaitEvent(s, a.cm->done, 0));
+        d_mask = a.cm->d_words;
+    }
+    vdb::DistinctFirstParams fp{};
+    fp.ids = W.li.p; fp.dists = W.ld.p; fp.counts = W.lc.p;
+    fp.codes = a.d_codes; fp.codes_len = a.codes_len; fp.n_answers = (uint32_t)nq; fp.k = (uint32_t)kmax; fp.kstride = (uint32_t)kmax;
+    fp.out_ids = W.ai.p; fp.out_dists = W.ad.p; fp.out_codes = W.ac.p; fp.kept = W.kept.p; fp.complete = W.complete.p;
+    std::vector<uint32_t> flag(nq), pending;
+    // the incomplete queries after a collapse (one host read of the flags)
+    auto read_pending = [&]() -> int {
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(flag.data(), W.complete.p, nq * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        pending.clear();
+        for (size_t b = 0; b < nq; ++b) if (!flag[b]) pending.push_back((uint32_t)b);
+        return VDB_OK;
+    };
+
+    // ---- stage A
+    if ((rc = search(W.q.p, nq, dA, d_mask, mask_bits, W.li.p, W.ld.p, W.lc.p))) return rc;
+    fp.stride = fp.depth = (uint32_t)dA; fp.exhaustive = dA >= a.len; fp.dest = nullptr; fp.append = 0;
+    vdb::launch_distinct_first(fp, (uint32_t)nq, s);
+    if ((rc = read_pending())) return rc;
+    st[1] = nq - pending.size();
+
+    // ---- stage B
+    if (!pending.empty()) HIP_TRY(hipMemcpyAsync(W.sel.p, pending.data(), pending.size() * 4, hipMemcpyHostToDevice, s));
+    const std::vector<uint32_t> sel = pending;                     // W.sel[j] = sel[j] from here on
+    if (!pending.empty() && dB > dA) {
+        const size_t nB = pending.size();
+        if ((rc = W.q2.ensure(nB * std::max<size_t>(dim, 1))) || (rc = W.li.ensure(nB * dB)) || (rc = W.ld.ensure(nB * dB))) return rc;
+        vdb::launch_gather_rows(W.q.p, (uint32_t)dim, (uint32_t)dim, (uint32_t)nq, W.sel.p, (uint32_t)nB, W.q2.p, s);
+        HIP_TRY(hipGetLastError());
+        if ((rc = search(W.q2.p, nB, dB, d_mask, mask_bits, W.li.p, W.ld.p, W.lc.p))) return rc;
+        fp.ids = W.li.p; fp.dists = W.ld.p;
+        fp.stride = fp.depth = (uint32_t)dB; fp.exhaustive = dB >= a.len; fp.dest = W.sel.p; fp.append = 0;
+        vdb::launch_distinct_first(fp, (uint32_t)nB, s);
+        if ((rc = read_pending())) return rc;
+        st[2] = nB - pending.size();
+    }
+
+    // ---- stage C
+    if (!pending.empty()) {
+        const uint64_t xbits = d_mask ? (uint64_t)mask_bits : a.id_bound;
+        if ((rc = W.xmask.ensure(std::max<size_t>((xbits + 63) / 64, 1))) || (rc = W.li.ensure(dB)) || (rc = W.ld.ensure(dB))) return rc;
+        fp.ids = W.li.p; fp.dists = W.ld.p;
+        fp.stride = fp.depth = (uint32_t)dB; fp.exhaustive = dB >= a.len; fp.append = 1;
+        vdb::ExcludeGroupsParams xp{d_mask, xbits, W.xmask.p, a.d_codes, a.codes_len, W.ai.p, W.ac.p, W.kept.p, (uint32_t)kmax, 0};
+        size_t j = 0;
+        for (uint32_t b : pending) {
+            while (sel[j] != b) ++j;                               // (pending is a subsequence of sel)
+            xp.answer = b;
+            fp.dest = W.sel.p + j;
+            uint32_t done = 0;
+            for (size_t round = 0; !done; ++round) {
+                if (round > kmax) return fail(VDB_ERR_DEVICE, "internal error: query %u needed more than %zu exclusion rounds", b, kmax);
+                vdb::launch_exclude_groups(xp, a.n_cu, s);
+                HIP_TRY(hipGetLastError());
+                if ((rc = search(W.q.p + (size_t)b * dim, 1, dB, W.xmask.p, (size_t)xbits, W.li.p, W.ld.p, W.lc.p))) return rc;
+                ++st[4];
+                vdb::launch_distinct_first(fp, 1, s);
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipMemcpyAsync(&done, W.complete.p + b, 4, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+            }
+            ++st[3];
+        }
+    }
+
+    // ---- the answers come down; per-query k: a prefix of the batch-wide answer
+    std::vector<uint32_t> cnt(nq);
+    std::vector<uint64_t> ids(nq * kmax);
+    std::vector<float> ds(nq * kmax);
+    std::vector<int32_t> cs(nq * kmax);
+    HIP_TRY(hipMemcpyAsync(cnt.data(), W.kept.p, nq * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(ids.data(), W.ai.p, nq * kmax * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(ds.data(), W.ad.p, nq * kmax * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(cs.data(), W.ac.p, nq * kmax * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t b = 0; b < nq; ++b) {
+        const size_t kb = a.ks ? a.ks[b] : a.k;
+        const size_t c = std::min<size_t>(std::min<size_t>(cnt[b], kmax), kb);
+        a.out_counts[b] = c;
+        st[7] += c;
+        for (size_t i = 0; i < c; ++i) {
+            a.out_ids[b * a.kstride + i] = ids[b * kmax + i];
+            a.out_dists[b * a.kstride + i] = ds[b * kmax + i];
+            if (a.out_codes) a.out_codes[b * a.kstride + i] = cs[b * kmax + i];
+        }
+    }
+    return VDB_OK;
+}
 
 int search_device(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, const uint64_t* d_idmask,
                   size_t mask_bits, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,

@@ -95,6 +95,7 @@ void append_row(Index* ix, uint64_t id, const float* v) {
     uint32_t row = ix->n_rows();
     if (row && id <= ix->row_ids.back()) ix->ids_monotone = false;
     ix->row_ids.push_back(id);
+    ix->id_bound = std::max(ix->id_bound, id == ~0ull ? id : id + 1);
     if ((row >> 5) >= ix->live.size()) ix->live.push_back(0u);
     ix->live[row >> 5] |= 1u << (row & 31);
     ++ix->n_live;
@@ -154,6 +155,7 @@ int add_one(Index* ix, uint64_t id, const float* v, size_t dim) {
         append_row(ix, id, v);
     } else {
         ix->misfits[id] = std::vector<float>(v, v + dim);
+        ix->id_bound = std::max(ix->id_bound, id == ~0ull ? id : id + 1);
         if (ix->n_live == 0) promote_misfits(ix);
     }
     return VDB_OK;

@@ -142,6 +142,22 @@ public:
         for (size_t i = 0; i < cnt; ++i) out.emplace_back((size_t)ids[i], ds[i]);
         return out;
     }
+    // no reference counterpart: the k nearest GROUPS, each by its nearest row -- the full ranking walked from the front, a row kept
+    // iff its code in column `slot` of `table` is -1 (such a row is its own group) or no earlier row has the same code.  codes
+    // (may be null) receives the group code of every returned row.
+    std::vector<Neighbor> search_distinct(const Vector& q, size_t k, vdb_meta_table* table, uint32_t slot, const uint64_t* id_mask = nullptr,
+                                          size_t mask_bits = 0, std::vector<int32_t>* codes = nullptr) const {
+        std::vector<uint64_t> ids(std::max<size_t>(k, 1));
+        std::vector<float> ds(ids.size());
+        std::vector<int32_t> cs(ids.size());
+        size_t cnt = 0;
+        check(vdb_flat_search_batch_distinct(h_, q.as_slice().data(), 1, q.dimension(), nullptr, k, table, slot, id_mask, mask_bits, ids.size(),
+                                             ids.data(), ds.data(), cs.data(), &cnt));
+        std::vector<Neighbor> out;
+        for (size_t i = 0; i < cnt; ++i) out.emplace_back((size_t)ids[i], ds[i]);
+        if (codes) codes->assign(cs.begin(), cs.begin() + (ptrdiff_t)cnt);
+        return out;
+    }
     DistanceMetric metric() const override { return metric_; }
     size_t len() const override { return vdb_flat_len(h_); }
     void add_bulk(const float* rows, size_t n, size_t dim, uint64_t first_id) {

@@ -329,6 +329,62 @@ class GpuFlatIndex(Index):
             _raise(rc)
         return [int(x) for x in out]
 
+    # ---- one nearest row per group (include/vdb_flat.h vdb_flat_search_batch_distinct; no reference counterpart)
+    def search_batch_distinct(self, queries, k, table, slot, id_mask=None, mask_bits=0, compiled_mask=None):
+        """The k nearest GROUPS, each represented by its nearest row: the full ranking of the eligible rows walked from the
+        front, a row kept iff its code in column `slot` of `table` (a MetaTable) is -1 or no earlier row has the same code.
+        Rows with code -1 (no such field) are never collapsed.  Exact, however deep one group reaches.  k an int or a
+        per-query array.  Returns (ids, dists, codes, counts); codes is the int32 group code of every returned row."""
+        if compiled_mask is not None and id_mask is not None:
+            raise ValueError("pass id_mask or compiled_mask, not both")
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError("queries must be a 2-d array")
+        nq, dim = q.shape
+        if np.isscalar(k):
+            ks_ptr, kscalar, kmax = None, int(k), int(k)
+        else:
+            ks = np.ascontiguousarray(k, dtype=np.uintp)
+            if ks.shape != (nq,):
+                raise ValueError(f"k must be a scalar or hold one value per query ({nq}), not {ks.shape}")
+            ks_ptr = ks.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t))
+            kscalar, kmax = 0, int(ks.max()) if ks.size else 0
+        kstride = max(kmax, 1)
+        out_ids = np.zeros((nq, kstride), dtype=np.uint64)
+        out_d = np.zeros((nq, kstride), dtype=np.float32)
+        out_c = np.full((nq, kstride), -1, dtype=np.int32)
+        counts = np.zeros(nq, dtype=np.uintp)
+        cp = counts.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t))
+        ccp = out_c.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        t = table._t if table is not None else None
+        if compiled_mask is not None:
+            rc = self._L.vdb_flat_search_batch_distinct_filtered(self._h, _fp(q), nq, dim, ks_ptr, kscalar, t, int(slot), compiled_mask.handle,
+                                                                 kstride, _u64p(out_ids), _fp(out_d), ccp, cp)
+        else:
+            mask_ptr = None
+            if id_mask is not None:
+                m = np.ascontiguousarray(id_mask, dtype=np.uint64)
+                mask_ptr = _u64p(m)
+            rc = self._L.vdb_flat_search_batch_distinct(self._h, _fp(q), nq, dim, ks_ptr, kscalar, t, int(slot), mask_ptr, int(mask_bits),
+                                                        kstride, _u64p(out_ids), _fp(out_d), ccp, cp)
+        if rc:
+            _raise(rc)
+        return out_ids, out_d, out_c, counts
+
+    def distinct_stats(self):
+        """The last search_batch_distinct: [0] queries, [1] completed by stage A, [2] by stage B, [3] by exclusion rounds,
+        [4] exclusion searches run, [5] depth of stage A, [6] depth of stage B, [7] rows returned in total."""
+        out = (ctypes.c_uint64 * 8)()
+        rc = self._L.vdb_flat_distinct_stats(self._h, out)
+        if rc:
+            _raise(rc)
+        return [int(x) for x in out]
+
+    @staticmethod
+    def distinct_depth(k, length, stage):
+        """Rows per query the stage-A (0) / stage-B (1) search of search_batch_distinct asks for; needs no device."""
+        return int(_ffi.lib().vdb_flat_distinct_depth(int(k), int(length), int(stage)))
+
     # ---- bulk build and device-resident entry points
     def add_bulk(self, rows, ids=None, first_id=0):
         rows = np.ascontiguousarray(rows, dtype=np.float32)

@@ -580,6 +580,39 @@ class VectorStore:
             out_ids, dists, counts = self._index.search_batch_by_id(q, int(k), id_mask=mask, mask_bits=bits)
         return [self._map([(int(out_ids[b, i]), dists[b, i]) for i in range(int(counts[b]))]) for b in range(len(internal))]
 
+    # ---- "the k nearest documents" (GpuFlatIndex.search_batch_distinct; no reference counterpart)
+    def search_distinct(self, query, k, field, flt=None):
+        """The k nearest GROUPS of rows that share a value of metadata field `field`, each represented by its nearest row,
+        nearest first.  A row without the field is its own group (And an Exists(field) into flt to drop such rows)."""
+        return self.search_distinct_batch([query], k, field, flt)[0]
+
+    def search_distinct_batch(self, queries, k, field, flt=None):
+        """search_distinct for several queries in one device call.  Needs the device table (set_device_filter(True)): the
+        collapse reads the field's resident column.  flt is a PRE-filter, compiled on the device when it fits the program
+        limits, else by compile_filter.  A field no row has leaves every row its own group: the plain search."""
+        if not isinstance(self._index, GpuFlatIndex):
+            raise ValueError("search_distinct needs a GpuFlatIndex")
+        if self._table is None:
+            raise ValueError("the device filter is off: set_device_filter(True) first")
+        queries = list(queries)
+        if self.is_empty() or not queries:
+            return [[] for _ in queries]
+        for q in queries:
+            self._check_dim(q)
+        qs = np.stack([q.data for q in queries]).astype(np.float32)
+        cm = self.compile_filter_device(flt) if flt is not None else None
+        mask, bits = self.compile_filter(flt) if flt is not None and cm is None else (None, 0)
+        try:
+            if field not in self._cols:
+                out_ids, dists, counts = self._index.search_batch_arrays(qs, int(k), id_mask=mask, mask_bits=bits, compiled_mask=cm)
+            else:
+                out_ids, dists, _, counts = self._index.search_batch_distinct(qs, int(k), self._table, self._slots[field], id_mask=mask,
+                                                                              mask_bits=bits, compiled_mask=cm)
+        finally:
+            if cm is not None:
+                cm.release()
+        return [self._map([(int(out_ids[b, i]), dists[b, i]) for i in range(int(counts[b]))]) for b in range(len(queries))]
+
     def search_batch_prefiltered(self, queries, flt):
         if self.is_empty():
             return [[] for _ in queries]
