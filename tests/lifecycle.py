@@ -1,0 +1,1914 @@
+"""Stateful lifecycle tests of the flat index: a model, a schedule generator and a runner (no GPU, no import of the product).
+
+A TRACE is plain data: {"seed", "profile", "metric", "d", "ops": [tuple, ...]}.  Every vector, id permutation, mask and query is
+derived from (trace seed, the key an op carries), so a trace can be printed, pasted into a test as a literal and replayed with
+run(trace, adapter).  run() applies every op to the adapter and to the MODEL and compares after every read: ids, order, counts and
+distance bits (range totals and group codes too), or the error the model predicts.
+
+THE MODEL (Model) is the append log of test_gpu_compact generalised: every row ever appended, its id, whether it is alive, plus an
+int32 group code and a presence bit per id.  Its answers are oracle.flat_search over the log with the dead rows switched off
+(live=), shaped by the helpers of range_data / by_id_data / distinct_data.  THE REFERENCE ADAPTER (RefIndex) keeps the same rows
+but answers by another path: the survivors rebuilt as a fresh contiguous block, masked rows taken out of the block, every search
+asked with its own k.  tests/test_lifecycle_cpu.py runs the pinned schedules against it, and against its MUTANTS: one stale-state
+defect each, modelled on a flag of the engine; the pinned set must catch every one of them.
+
+Store level: StoreSim states VectorStore's semantics (upsert = remove + add under the next internal id, post-filter with 3x
+over-fetch, pre-filter as an id mask) over anything with the index interface: over a Model it is the store's model, over a
+RefIndex the store's reference adapter."""
+from collections import Counter
+
+import numpy as np
+
+import by_id_data as bd
+import distinct_data as dd
+import oracle
+import range_data as rd
+
+F32, U64, I32 = np.float32, np.uint64, np.int32
+EUCLID, COSINE, DOT = 0, 1, 2
+ID_LIMIT = 1 << 20                     # ids stay below: meta table and masks stay small, distinct is never refused
+SMALL_N, DIRECT_MAX_Q, BF16_MIN_ROWS = 16384, 8, 65536
+BATCHES, KS = (1, 8, 9, 40), (1, 10, 113, 300)
+NO_DIRECT = 8                          # GpuFlatIndex.TIERS_NO_DIRECT
+MUTATIONS = ("add", "bulk", "upsert", "readd", "remove", "remove_absent", "compact", "compact_shrink", "auto_compact", "codes", "reset")
+READS = ("search", "masked", "sparse", "range", "by_id", "distinct")
+SPARSE_SHARE = 0.02                    # eligible share of a "sparse" read's mask
+
+
+class Predicted(Exception):
+    """an error the model (or the reference adapter) answers a read with: kind and, for VectorNotFound, the id it names"""
+
+    def __init__(self, kind, id=None):
+        super().__init__(kind, id)
+        self.kind, self.id = kind, id
+
+
+class Mismatch(AssertionError):
+    pass
+
+
+# ---------------------------------------------------------------------------------------------------------------- derived data
+def rng_of(seed, key, salt=0):
+    return np.random.default_rng([int(seed), int(key), int(salt)])
+
+
+def vectors(seed, key, n, d, dup=0.0):
+    """n gaussian rows; a share `dup` of them exact copies of other rows of the block"""
+    rng = rng_of(seed, key)
+    rows = rng.standard_normal((n, d)).astype(F32)
+    m = int(n * dup)
+    if m and n > 1:
+        dst = rng.choice(n, m, replace=False)
+        rows[dst] = rows[rng.integers(0, n, m)]
+    return rows
+
+
+def bulk_ids(seed, key, n, base, perm):
+    ids = np.arange(n, dtype=np.int64)
+    if perm:
+        ids = rng_of(seed, key, 1).permutation(n)
+    return (ids + int(base)).astype(U64)
+
+
+def lists_of(gi, gd, gc):
+    """(ids, dists, counts) arrays -> one (ids u64[c], distance bits u32[c]) per query"""
+    return [(np.array(gi[b, :int(c)], dtype=U64), np.array(gd[b, :int(c)], dtype=F32).view(np.uint32)) for b, c in enumerate(gc)]
+
+
+def k_of(ks, b):
+    return int(ks) if np.isscalar(ks) else int(ks[b])
+
+
+def mask_ok(mask, id_codes, present):
+    """bool by id: ("host", ok) as it is, ("compiled", code): present and group code != code (a missing code matches, like Ne)"""
+    if mask is None:
+        return None
+    if mask[0] == "host":
+        return np.asarray(mask[1], dtype=bool)
+    return present & (id_codes != I32(mask[1]))
+
+
+def ok_of_ids(ok, ids):
+    out = np.zeros(len(ids), dtype=bool)
+    inside = ids < U64(len(ok))
+    out[inside] = ok[ids[inside].astype(np.int64)]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- the row log
+class Log:
+    """Every row ever appended, in order, with its id and whether it is still alive; a group code and a presence bit per id.
+    Also what decides the engine's routes and re-allocations, counted from the ops alone: the capacity (1024 rows, doubling), the
+    rows appended since the last read (staged), crossings of SMALL_N."""
+
+    def __init__(self, metric, sharded=False):
+        self.metric, self.sharded = int(metric), bool(sharded)
+        self.rows = np.zeros((0, 0), dtype=F32)
+        self.ids = np.zeros(0, dtype=U64)
+        self.alive = np.zeros(0, dtype=bool)
+        self.misfits = {}
+        self.codes = np.full(ID_LIMIT, -1, dtype=I32)
+        self.present = np.zeros(ID_LIMIT, dtype=bool)
+        self.id_bound = 0
+        self.cap, self.auto, self.staged, self.last_d, self.epoch = 0, 0.0, 0, 0, 0
+        self.counts = dict(doublings=0, shrinks=0, up=0, down=0, dim_resets=0, auto_compactions=0, compact_with_staged=0)
+
+    # -- sizes
+    @property
+    def d(self):
+        return self.rows.shape[1]
+
+    def n_rows(self):
+        return self.ids.size
+
+    def n_live(self):
+        return int(self.alive.sum())
+
+    def live_ids(self):
+        return np.sort(self.ids[self.alive])
+
+    def _resized(self, before):
+        n = self.n_rows()
+        if before <= SMALL_N < n:
+            self.counts["up"] += 1
+        if n <= SMALL_N < before:
+            self.counts["down"] += 1
+        if n > self.cap:
+            self.on_grow()
+            self.cap = max(self.cap, 1024)
+            while self.cap < n:
+                self.cap *= 2
+                self.counts["doublings"] += 1
+
+    def on_grow(self):
+        pass
+
+    # -- mutations
+    def _kill(self, ids):
+        ids = np.asarray(ids, dtype=U64)
+        self.epoch += 1
+        self.alive &= ~np.isin(self.ids, ids)
+        self.present[ids[ids < U64(ID_LIMIT)].astype(np.int64)] = False
+        if self.misfits:
+            for i in ids.tolist():
+                self.misfits.pop(int(i), None)
+        if self.ids.size and not self.alive.any():                     # the last row is gone: the store starts over
+            before, self.staged = self.n_rows(), 0
+            self.rows, self.ids, self.alive = np.zeros((0, 0), dtype=F32), np.zeros(0, dtype=U64), np.zeros(0, dtype=bool)
+            self.cap = 0
+            self.on_reset()
+            self._resized(before)
+
+    def on_reset(self):
+        pass
+
+    def add_bulk(self, rows, ids):
+        self._append(rows, ids)
+
+    def _append(self, rows, ids):
+        rows, ids = np.ascontiguousarray(rows, dtype=F32), np.asarray(ids, dtype=U64)
+        self._kill(ids)
+        if not self.ids.size:
+            if self.last_d not in (0, rows.shape[1]):
+                self.counts["dim_resets"] += 1
+            self.rows = np.zeros((0, rows.shape[1]), dtype=F32)
+        self.last_d = rows.shape[1]
+        self.epoch += 1
+        before = self.n_rows()
+        self.rows = np.concatenate([self.rows, self.stored(rows, before)])
+        self.ids = np.concatenate([self.ids, ids])
+        self.alive = np.concatenate([self.alive, np.ones(ids.size, dtype=bool)])
+        self.present[ids[ids < U64(ID_LIMIT)].astype(np.int64)] = True
+        self.id_bound = max(self.id_bound, int(ids.max()) + 1)
+        self.staged += ids.size
+        self._resized(before)
+
+    def stored(self, rows, first):
+        return rows
+
+    def add(self, id, v):
+        v = np.asarray(v, dtype=F32)
+        self._kill([id])                                               # an add overwrites; the last row gone resets the store
+        if self.ids.size and v.size != self.d:
+            self.misfits[int(id)] = int(v.size)                        # a row of another dimension: kept aside, fails the searches
+            self.id_bound = max(self.id_bound, int(id) + 1)
+            return
+        self._append(v[None, :], [id])
+
+    def remove(self, ids):
+        self._kill(np.atleast_1d(np.asarray(ids, dtype=U64)))
+
+    def compact(self, shrink=False):
+        """the staged rows are uploaded first, then the survivors move down; returns the rows given back"""
+        if self.staged and not self.alive.all():
+            self.counts["compact_with_staged"] += 1
+        self.staged = 0
+        self.epoch += 1
+        dead = int((~self.alive).sum())
+        before = self.n_rows()
+        if dead:
+            self.on_compact(shrink)
+            self.rows, self.ids = self.rows[self.alive], self.ids[self.alive]
+            self.alive = np.ones(self.ids.size, dtype=bool)
+        if shrink and self.ids.size:
+            cap = (self.ids.size + 1023) // 1024 * 1024
+            if cap < self.cap:
+                self.counts["shrinks"] += 1
+            self.cap = cap
+        self._resized(before)
+        return dead
+
+    def on_compact(self, shrink):
+        pass
+
+    def set_auto_compact(self, f):
+        self.auto = float(f)
+
+    def set_codes(self, first, codes):
+        codes = np.asarray(codes, dtype=I32)
+        self.codes[int(first):int(first) + codes.size] = codes
+
+    def set(self, name, value):
+        pass
+
+    def flush(self):
+        self.uploaded()
+
+    def uploaded(self):
+        """what every read and flush() does first: the staged rows reach the device, auto-compaction may run"""
+        self.staged = 0
+        n = self.n_rows()
+        if self.auto > 0 and n and (n - self.n_live()) > self.auto * n:
+            self.counts["auto_compactions"] += 1
+            self.compact()
+
+    # -- what a read answers with before it searches
+    def zero_live(self):
+        return self.metric == COSINE and self.ids.size and bool((self.alive & ~self.rows.any(axis=1)).any())
+
+    def refusal(self, kind, ids=None):
+        if kind == "range" and self.sharded:
+            raise Predicted("Refused")
+        if kind == "by_id":
+            live = set(self.ids[self.alive].tolist()) | set(self.misfits)
+            for i in np.asarray(ids, dtype=U64).tolist():
+                if i not in live:
+                    raise Predicted("VectorNotFound", int(i))
+        if not self.ids.size and not self.misfits:
+            return True                                                # an empty store answers every query with nothing
+        if self.misfits:
+            raise Predicted("DimensionMismatch")
+        if self.zero_live():
+            raise Predicted("InvalidVector")
+        return False
+
+
+# ---------------------------------------------------------------------------------------------------------------- the model
+class Model(Log):
+    """Expected answers from oracle.flat_search over the log with live= and nothing else.  With an index attached (driving())
+    every mutation goes to the index too: the form tests/test_gpu_compact.py uses."""
+
+    vdb = ix = None
+
+    @classmethod
+    def driving(cls, vdb, metric, rows, ix=None, **kw):
+        m = cls(metric)
+        m.vdb = vdb
+        m.ix = ix or vdb.GpuFlatIndex(vdb.DistanceMetric(metric), keep_host_copy=False, **kw)
+        m.add_bulk(rows, np.arange(rows.shape[0], dtype=U64))
+        return m
+
+    def add_bulk(self, rows, ids):
+        ids = np.asarray(ids, dtype=U64)
+        if self.ix is not None:
+            self.ix.add_bulk(rows, ids=ids)
+        super().add_bulk(rows, ids)
+
+    def add(self, id, v):
+        if self.ix is not None:
+            self.ix.add(int(id), self.vdb.Vector(v))
+        super().add(id, v)
+
+    def remove(self, ids):
+        if self.ix is not None:
+            for i in np.atleast_1d(ids):
+                self.ix.remove(int(i))
+        super().remove(ids)
+
+    def compact(self, shrink=False):
+        got = self.ix.compact(shrink=shrink) if self.ix is not None else None
+        dead = super().compact(shrink)
+        return dead if got is None else got
+
+    def survivors(self):
+        return np.ascontiguousarray(self.rows[self.alive]), np.ascontiguousarray(self.ids[self.alive])
+
+    def fresh(self, **kw):
+        rows, ids = self.survivors()
+        ix = self.vdb.GpuFlatIndex(self.vdb.DistanceMetric(self.metric), keep_host_copy=False, **kw)
+        ix.add_bulk(rows, ids=ids)
+        return ix
+
+    def check(self, q, k, qsel=None, got=None, **kw):
+        rows, ids = self.survivors()
+        gi, gd, gc = got if got is not None else self.ix.search_batch_arrays(q, k, **kw)
+        for b in (range(q.shape[0]) if qsel is None else qsel):
+            oi, od = oracle.flat_search(self.metric, rows, q[b], k, ids=ids)
+            assert gc[b] == len(oi), (b, gc[b], len(oi))
+            assert np.array_equal(gi[b, :gc[b]], oi), (b, gi[b, :gc[b]], oi)
+            assert np.array_equal(gd[b, :gc[b]].view(np.uint32), od.view(np.uint32)), (b, gd[b, :gc[b]], od)
+        return gi, gd, gc
+
+    # -- reads: the adapter interface, answered by the oracle
+    def _live(self, mask):
+        ok = mask_ok(mask, self.codes, self.present)
+        live = self.alive if ok is None else self.alive & ok_of_ids(ok, self.ids)
+        return live.astype(np.uint8)
+
+    def ranking(self, q, live, k=None):
+        """the oracle's ranking of one query over the log (full when k is None; the full ones are kept until the next mutation)"""
+        if k is not None:
+            return oracle.flat_search(self.metric, self.rows, q, k, ids=self.ids, live=live)
+        memo = self.__dict__.setdefault("_memo", {})
+        if memo.get("epoch") != self.epoch:
+            memo.clear()
+            memo["epoch"] = self.epoch
+        key = (q.tobytes(), live.tobytes())
+        if key not in memo:
+            memo[key] = oracle.flat_search(self.metric, self.rows, q, self.n_rows(), ids=self.ids, live=live)
+        return memo[key]
+
+    def search(self, q, ks, mask=None):
+        empty = self.refusal("search")
+        self.uploaded()
+        if empty:
+            return {"lists": [(np.zeros(0, U64), np.zeros(0, np.uint32))] * len(q)}
+        live = self._live(mask)
+        out = []
+        for b in range(len(q)):
+            oi, od = self.ranking(q[b], live, k_of(ks, b))
+            out.append((oi, od.view(np.uint32)))
+        return {"lists": out}
+
+    def range(self, q, radii, max_results, mask=None):
+        empty = self.refusal("range")
+        self.uploaded()
+        if empty:
+            return {"lists": [(np.zeros(0, U64), np.zeros(0, np.uint32))] * len(q), "totals": [0] * len(q)}
+        live = self._live(mask)
+        out, totals = [], []
+        for b in range(len(q)):
+            oi, od, c, total = rd.cut(self.ranking(q[b], live), radii[b], max_results)
+            out.append((oi, od.view(np.uint32)))
+            totals.append(total)
+        return {"lists": out, "totals": totals}
+
+    def by_id(self, ids, ks, mask=None):
+        ids = np.asarray(ids, dtype=U64)
+        self.refusal("by_id", ids)
+        self.uploaded()
+        live = self._live(mask)
+        at = {int(i): r for r, i in enumerate(self.ids.tolist()) if self.alive[r]}
+        sel = [at[int(i)] for i in ids]
+        k = ks if np.isscalar(ks) else list(ks)
+        want = bd.expected(self.metric, self.rows, sel, k, ids=self.ids, live=live)
+        ans = {"lists": [(oi, od.view(np.uint32)) for oi, od, _, _ in want]}
+        if np.isscalar(ks):                                          # (with per-query k the engine strikes in lists of max(k) + 1: other counts, same answers)
+            ans.update(struck=sum(1 for w in want if w[2]), cut=sum(1 for w in want if w[3]))
+        return ans
+
+    def distinct(self, q, ks, mask=None):
+        empty = self.refusal("distinct")
+        self.uploaded()
+        if empty:
+            return {"lists": [(np.zeros(0, U64), np.zeros(0, np.uint32))] * len(q), "codes": [np.zeros(0, I32)] * len(q)}
+        live = self._live(mask)
+        out, codes, stages = [], [], []
+        for b in range(len(q)):
+            rank = self.ranking(q[b], live)
+            ei, ed, ec = dd.expected(rank, self.codes, k_of(ks, b))
+            out.append((ei, ed.view(np.uint32)))
+            codes.append(ec)
+            if np.isscalar(ks) and mask is None:                     # the stage that completes the query (distinct_data.stage_of)
+                stages.append(dd.stage_of(rank, self.codes, int(ks), self.n_live()))
+        ans = {"lists": out, "codes": codes}
+        if stages:
+            ans["stages"] = [stages.count(x) for x in "ABC"]
+        return ans
+
+
+# ---------------------------------------------------------------------------------------------------------------- the reference adapter
+class RefIndex(Log):
+    """The same rows, answered by another path: the survivors as a fresh contiguous block (Model.fresh() without a GPU), masked
+    rows removed from the block instead of switched off, every search asked with its own k."""
+
+    def seen(self):
+        """(rows, ids, alive) as the reads see them: the hook of most mutants"""
+        return self.rows, self.ids, self.alive
+
+    def block(self, mask):
+        rows, ids, alive = self.seen()
+        keep = alive.copy()
+        ok = mask_ok(mask, self.codes, self.present)
+        if ok is not None:
+            keep &= ok_of_ids(ok, ids)
+        return np.ascontiguousarray(rows[keep]), np.ascontiguousarray(ids[keep])
+
+    def knn(self, rows, ids, q, k):
+        return oracle.flat_search(self.metric, rows, q, k, ids=ids)
+
+    def search(self, q, ks, mask=None):
+        empty = self.refusal("search")
+        self.uploaded()
+        rows, ids = self.block(mask)
+        if empty:
+            rows = np.zeros((0, q.shape[1]), dtype=F32)
+        out = []
+        for b in range(len(q)):
+            oi, od = self.knn(rows, ids, q[b], k_of(ks, b)) if len(rows) else (np.zeros(0, U64), np.zeros(0, F32))
+            out.append((oi, od.view(np.uint32)))
+        return {"lists": out}
+
+    def range_total(self, q, r, mask, total):
+        return total
+
+    def range(self, q, radii, max_results, mask=None):
+        empty = self.refusal("range")
+        self.uploaded()
+        rows, ids = self.block(mask)
+        out, totals = [], []
+        for b in range(len(q)):
+            if empty or not len(rows):
+                out.append((np.zeros(0, U64), np.zeros(0, np.uint32)))
+                totals.append(0)
+                continue
+            oi, od, c, total = rd.cut(self.knn(rows, ids, q[b], len(rows)), radii[b], max_results)
+            out.append((oi, od.view(np.uint32)))
+            totals.append(self.range_total(q[b], radii[b], mask, total))
+        return {"lists": out, "totals": totals}
+
+    def vector_of(self, id):
+        rows, ids, alive = self.seen()
+        at = np.nonzero(alive & (ids == U64(id)))[0]
+        if not at.size:
+            raise Predicted("VectorNotFound", int(id))
+        return rows[at[-1]]
+
+    def by_id(self, ids, ks, mask=None):
+        ids = np.asarray(ids, dtype=U64)
+        self.refusal("by_id", ids)
+        self.uploaded()
+        rows, bids = self.block(mask)
+        out, struck, cut = [], 0, 0
+        for b, own in enumerate(ids):
+            k = k_of(ks, b)
+            oi, od = self.knn(rows, bids, self.vector_of(own), k + 1) if len(rows) else (np.zeros(0, U64), np.zeros(0, F32))
+            oi, od, hit, _cut = bd.strike(oi, od, own, k)
+            struck += bool(hit)
+            cut += bool(_cut)
+            out.append((oi, od.view(np.uint32)))
+        return {"lists": out, "struck": struck, "cut": cut} if np.isscalar(ks) else {"lists": out}
+
+    def codes_seen(self):
+        return self.codes
+
+    def distinct(self, q, ks, mask=None):
+        empty = self.refusal("distinct")
+        self.uploaded()
+        rows, ids = self.block(mask)
+        out, codes = [], []
+        for b in range(len(q)):
+            if empty or not len(rows):
+                out.append((np.zeros(0, U64), np.zeros(0, np.uint32)))
+                codes.append(np.zeros(0, I32))
+                continue
+            ei, ed, ec = dd.expected(self.knn(rows, ids, q[b], len(rows)), self.codes_seen(), k_of(ks, b))
+            out.append((ei, ed.view(np.uint32)))
+            codes.append(ec)
+        return {"lists": out, "codes": codes}
+
+
+# ---------------------------------------------------------------------------------------------------------------- mutants
+class LostRemove(RefIndex):
+    """1. a remove is not seen by reads until the next add (live_dirty lost)"""
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.unseen = np.zeros(0, dtype=bool)
+
+    def remove(self, ids):
+        before = self.alive.copy()
+        super().remove(ids)
+        if self.alive.size == before.size:
+            u = np.zeros(before.size, dtype=bool)
+            u[:self.unseen.size] = self.unseen[:before.size]
+            self.unseen = u | (before & ~self.alive)
+
+    def _append(self, rows, ids):
+        self.unseen = np.zeros(0, dtype=bool)
+        super()._append(rows, ids)
+
+    def on_compact(self, shrink):
+        self.unseen = np.zeros(0, dtype=bool)
+
+    def seen(self):
+        alive = self.alive.copy()
+        n = min(alive.size, self.unseen.size)
+        alive[:n] |= self.unseen[:n]
+        return self.rows, self.ids, alive
+
+
+class StagedInvisibleOnce(RefIndex):
+    """2. rows staged since the last read are invisible to the NEXT read only (n_uploaded / pending)"""
+
+    def seen(self):
+        alive = self.alive.copy()
+        if self.staged:
+            alive[self.n_rows() - self.staged:] = False
+        return self.rows, self.ids, alive
+
+    def search(self, *a, **kw):
+        return self._late(super().search, *a, **kw)
+
+    def range(self, *a, **kw):
+        return self._late(super().range, *a, **kw)
+
+    def by_id(self, *a, **kw):
+        return self._late(super().by_id, *a, **kw)
+
+    def distinct(self, *a, **kw):
+        return self._late(super().distinct, *a, **kw)
+
+    def uploaded(self):
+        pass
+
+    def flush(self):
+        Log.uploaded(self)
+
+    def _late(self, read, *a, **kw):
+        try:
+            return read(*a, **kw)
+        finally:
+            Log.uploaded(self)
+
+
+class IdsNotMoved(RefIndex):
+    """3. after a compaction the id column is not moved with the rows beyond the first dead one"""
+
+    def on_compact(self, shrink):
+        self._old_ids = self.ids.copy()
+
+    def compact(self, shrink=False):
+        self._old_ids = None
+        dead = super().compact(shrink)
+        if self._old_ids is not None:
+            self.ids = self._old_ids[:self.ids.size].copy()
+        return dead
+
+
+class GrowForgetsTombstones(RefIndex):
+    """4. a capacity doubling forgets the tombstones of old rows"""
+
+    def on_grow(self):
+        if self.cap:
+            self._revive = True
+
+    def _append(self, rows, ids):
+        self._revive = False
+        n = self.n_rows()
+        super()._append(rows, ids)
+        if self._revive and self.n_rows() > n:
+            self.alive[:n] = True
+
+
+class SampleKeyCollision(RefIndex):
+    """5. shrink-compaction followed by adds back to the same row count serves the row block from before: a copy of the rows
+    keyed only by the row count (sample16_n), which an ordinary compaction drops and a shrinking one forgets to"""
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.copy = {}
+
+    def on_compact(self, shrink):
+        if not shrink:
+            self.copy = {}
+
+    def on_reset(self):
+        self.copy = {}
+
+    def seen(self):
+        n = self.n_rows()
+        held = self.copy.get(n)
+        if held is None or held.shape != self.rows.shape:
+            held = self.copy[n] = self.rows.copy()
+        return held, self.ids, self.alive
+
+
+class TiesByPosition(RefIndex):
+    """6. ties are broken by row position instead of id once ids are non-monotone (rank_valid)"""
+
+    def knn(self, rows, ids, q, k):
+        oi, od = oracle.flat_search(self.metric, rows, q, k)
+        return ids[oi.astype(np.int64)], od
+
+
+class StaleZeroFlag(RefIndex):
+    """7. a removed zero-norm row still fails Cosine searches, and an added one does not yet (zero_valid): the flag a read uses
+    is the one the read before it computed"""
+
+    flag = False
+
+    def zero_live(self):
+        now, was = super().zero_live(), self.flag
+        self.flag = now
+        return was
+
+    def block(self, mask):
+        rows, ids = super().block(mask)
+        keep = rows.any(axis=1) if self.metric == COSINE and len(rows) else np.ones(len(rows), dtype=bool)
+        return np.ascontiguousarray(rows[keep]), np.ascontiguousarray(ids[keep])
+
+
+class ByIdGathersOldRow(RefIndex):
+    """8. search by id gathers the row the id had before its upsert"""
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.before = {}
+
+    def _append(self, rows, ids):
+        live = {int(i): r for r, i in enumerate(self.ids.tolist()) if self.alive[r]}
+        for j, i in enumerate(np.asarray(ids, dtype=U64).tolist()):
+            if i in live and self.rows.shape[1] == np.shape(rows)[1]:
+                self.before[i] = self.rows[live[i]].copy()
+        super()._append(rows, ids)
+
+    def add(self, id, v):
+        at = np.nonzero(self.alive & (self.ids == U64(id)))[0]
+        if at.size and self.d == np.size(v):
+            self.before[int(id)] = self.rows[at[-1]].copy()
+        super().add(id, v)
+
+    def on_reset(self):
+        self.before = {}
+
+    def vector_of(self, id):
+        v = super().vector_of(id)
+        return self.before.get(int(id), v)
+
+
+class TotalCountsDead(RefIndex):
+    """9. the range total counts dead rows"""
+
+    def range_total(self, q, r, mask, total):
+        rows, ids, alive = self.seen()
+        dead = np.ascontiguousarray(rows[~alive])
+        if not len(dead):
+            return total
+        _, od = oracle.flat_search(self.metric, dead, q, len(dead))
+        with np.errstate(invalid="ignore"):
+            return total + int((od <= F32(r)).sum())
+
+
+class CodesLostAfterDistinct(RefIndex):
+    """10. a group-code write made after a distinct search never reaches the column (Staged range lost)"""
+
+    column = None
+
+    def distinct(self, *a, **kw):
+        out = super().distinct(*a, **kw)
+        if self.column is None:
+            self.column = self.codes.copy()
+        return out
+
+    def codes_seen(self):
+        return self.codes if self.column is None else self.column
+
+
+class RefillKeepsNorms(RefIndex):
+    """12. remove-everything-then-refill keeps the per-row norms of the old rows"""
+
+    old = np.zeros(0)
+
+    def _kill(self, ids):
+        norms = np.sqrt((self.rows.astype(np.float64) ** 2).sum(axis=1)) if self.ids.size else None
+        super()._kill(ids)
+        if norms is not None and not self.ids.size:
+            self.old = norms
+
+    def stored(self, rows, first):
+        n = max(0, min(len(rows), self.old.size - first))
+        if not n:
+            return rows
+        rows = rows.copy()
+        now = np.sqrt((rows[:n].astype(np.float64) ** 2).sum(axis=1))
+        scale = np.where(now > 0, self.old[first:first + n] / np.where(now > 0, now, 1.0), 1.0)
+        rows[:n] = (rows[:n] * scale[:, None]).astype(F32)
+        return rows
+
+
+INDEX_MUTANTS = {1: LostRemove, 2: StagedInvisibleOnce, 3: IdsNotMoved, 4: GrowForgetsTombstones, 5: SampleKeyCollision,
+                 6: TiesByPosition, 7: StaleZeroFlag, 8: ByIdGathersOldRow, 9: TotalCountsDead, 10: CodesLostAfterDistinct,
+                 12: RefillKeepsNorms}
+
+
+# ---------------------------------------------------------------------------------------------------------------- the store
+def flt_of(vdb, spec):
+    """a filter as plain data -> MetadataFilter: ("eq" | "ne", field, value), ("exists", field), ("and" | "or", [specs])"""
+    if spec is None:
+        return None
+    F = vdb.MetadataFilter
+    if spec[0] in ("and", "or"):
+        return (F.And if spec[0] == "and" else F.Or)([flt_of(vdb, s) for s in spec[1]])
+    return {"eq": F.Eq, "ne": F.Ne, "exists": F.Exists}[spec[0]](*spec[1:])
+
+
+class StoreSim:
+    """VectorStore's semantics over anything with the index interface: string id -> (internal id, Metadata), an upsert removes the
+    old internal id and adds the row under the next one, filters by MetadataFilter.matches over the live entries (never by any
+    column).  stale_presence: mutant 11, the presence bit of a superseded internal id stays set, so a pre-filtered search still
+    finds the old version."""
+
+    GROUP_FIELD = "grp"
+
+    def __init__(self, vdb, index, stale_presence=False):
+        self.vdb, self.index, self.stale = vdb, index, stale_presence
+        self.entries, self.next, self.table = {}, 0, False           # sid -> (internal, Metadata)
+        self.group_code = {}
+        self.ghosts = {}                                             # internal -> (sid, Metadata) of superseded versions (mutant 11)
+
+    def insert(self, sid, v, fields):
+        old = self.entries.get(sid)
+        if old is not None:
+            if self.stale:
+                self.ghosts[old[0]] = (sid, old[1], self.index.rows[np.nonzero(self.index.ids == U64(old[0]))[0][-1]].copy())
+            self.index.remove(old[0])
+        internal, self.next = self.next, self.next + 1
+        self.index.add(internal, v)
+        self.entries[sid] = (internal, self.vdb.Metadata(dict(fields)))
+        g = dict(fields).get(self.GROUP_FIELD)
+        self.index.set_codes(internal, [-1 if g is None else self.group_code.setdefault(g, len(self.group_code))])
+
+    def delete(self, sid):
+        e = self.entries.pop(sid, None)
+        if e is None:
+            raise Predicted("VectorNotFound", sid)
+        self.index.remove(e[0])
+
+    def compact(self):
+        return self.index.compact()
+
+    def set(self, name, value):
+        if name == "device_filter":
+            self.table = bool(value)
+        self.index.set(name, value)
+
+    def _ok(self, spec):
+        """eligibility by internal id of a pre-filter"""
+        if spec is None:
+            return None
+        flt = flt_of(self.vdb, spec)
+        ok = np.zeros(max(self.next, 1), dtype=bool)
+        for sid, (internal, meta) in self.entries.items():
+            ok[internal] = flt.matches(meta)
+        return ok
+
+    def _mask(self, spec):
+        ok = self._ok(spec)
+        return None if ok is None else ("host", ok)
+
+    def _named(self, lists):
+        name = {internal: sid for sid, (internal, _) in self.entries.items()}
+        for internal, (sid, _, _) in self.ghosts.items():
+            name.setdefault(internal, sid)
+        return [[(name.get(int(i), f"?{int(i)}"), int(b)) for i, b in zip(*l)] for l in lists]
+
+    def _empty(self):
+        return not self.entries
+
+    def _pre(self, read, *args, spec=None):
+        """a pre-filtered read; mutant 11 adds the superseded versions that match the filter back for its duration"""
+        mask = self._mask(spec)
+        back = []
+        if self.stale and spec is not None and self.ghosts:
+            flt = flt_of(self.vdb, spec)
+            back = [(i, g) for i, g in self.ghosts.items() if flt.matches(g[1])]
+            for i, g in back:
+                self.index.add(i, g[2])
+                mask[1][i] = True
+        try:
+            return read(*args, mask)
+        finally:
+            for i, _ in back:
+                self.index.remove(i)
+
+    def search(self, q, k):
+        return [] if self._empty() else self._named(self.index.search(q[None, :], int(k))["lists"])[0]
+
+    def search_with_filter(self, q, k, spec):
+        if self._empty():
+            return []
+        flt = flt_of(self.vdb, spec)
+        meta = {internal: (sid, m) for sid, (internal, m) in self.entries.items()}
+        fetch = min(max(3 * k, k), len(self.entries))
+        ids, bits = self.index.search(q[None, :], fetch)["lists"][0]
+        out = [(meta[int(i)][0], int(b)) for i, b in zip(ids, bits) if flt.matches(meta[int(i)][1])]
+        return out[:k]
+
+    def search_batch_prefiltered(self, q, ks, spec):
+        return [[] for _ in q] if self._empty() else self._named(self._pre(self.index.search, q, ks, spec=spec)["lists"])
+
+    def search_within(self, q, radius, limit, spec):
+        if self._empty():
+            return []
+        return self._named(self._pre(self.index.range, q[None, :], [radius], limit, spec=spec)["lists"])[0]
+
+    def search_similar_batch(self, sids, k, spec):
+        ids = []
+        for sid in sids:
+            if sid not in self.entries:
+                raise Predicted("VectorNotFound", sid)
+            ids.append(self.entries[sid][0])
+        return self._named(self._pre(self.index.by_id, np.array(ids, dtype=U64), int(k), spec=spec)["lists"])
+
+    def search_distinct_batch(self, q, k, spec):
+        if not self.table:
+            raise Predicted("NeedsTable")
+        return [[] for _ in q] if self._empty() else self._named(self._pre(self.index.distinct, q, int(k), spec=spec)["lists"])
+
+
+# ---------------------------------------------------------------------------------------------------------------- the runner
+READ_OPS = READS
+STORE_READS = ("s_search", "s_with_filter", "s_prefiltered", "s_within", "s_similar", "s_distinct")
+
+
+def is_read(op):
+    return op[0] in READ_OPS or op[0] in STORE_READS
+
+
+def queries(seed, key, log, B, d):
+    """gaussian queries, most of them next to a stored (alive or removed) row, so that exact duplicates meet in the answers"""
+    rng = rng_of(seed, key, 2)
+    q = rng.standard_normal((B, d)).astype(F32)
+    if log.n_rows() and log.d == d:
+        near = rng.random(B) < 0.7
+        at = rng.integers(0, log.n_rows(), B)
+        q[near] = log.rows[at[near]] + F32(0.05) * q[near]
+        if log.metric == COSINE:
+            q[~q.any(axis=1)] = F32(1.0)
+    return np.ascontiguousarray(q, dtype=F32)
+
+
+def mask_of(seed, op_mask, log):
+    """the mask of a read as plain data -> None | ("host", ok by id) | ("compiled", code)"""
+    if op_mask is None:
+        return None
+    how, key, share = op_mask
+    if how == "compiled":
+        return ("compiled", int(key))
+    return ("host", rng_of(seed, key, 3).random(max(log.id_bound, 1)) < share)
+
+
+def ks_of(k):
+    return int(k) if np.isscalar(k) else np.array(k, dtype=np.uintp)
+
+
+def materialise(trace, op, model):
+    """a read op -> (method name, positional arguments) for model and adapter alike"""
+    seed, kind = trace["seed"], op[0]
+    d = model.d or trace["d"]
+    if kind in ("search", "masked", "sparse"):
+        _, B, k, qkey, m = op
+        return "search", (queries(seed, qkey, model, B, d), ks_of(k), mask_of(seed, m, model))
+    if kind == "distinct":
+        _, B, k, qkey, m = op
+        return "distinct", (queries(seed, qkey, model, B, d), ks_of(k), mask_of(seed, m, model))
+    if kind == "range":
+        _, B, qkey, rank, maxr, m = op
+        q = queries(seed, qkey, model, B, d)
+        mask = mask_of(seed, m, model)
+        radii = np.ones(B, dtype=F32)
+        if model.ids.size and not model.misfits and not model.zero_live():
+            live = model._live(mask)
+            for b in range(B):
+                r = model.ranking(q[b], live)
+                if len(r[0]):
+                    radii[b] = rd.radius_at(r, min(int(rank), len(r[0])))
+        return "range", (q, radii, int(maxr), mask)
+    if kind == "by_id":
+        _, B, k, skey, absent, m = op
+        rng = rng_of(seed, skey, 4)
+        live = model.live_ids()
+        ids = live[rng.integers(0, live.size, B)] if live.size else np.zeros(B, dtype=U64)
+        if live.size:                                                # half of them among the ids written last (added, upserted, re-added)
+            last = model.ids[model.alive][-48:]
+            recent = rng.random(B) < 0.5
+            ids[recent] = last[rng.integers(0, last.size, B)][recent]
+            ids[0] = last[-1]                                        # and always the very last one
+        if absent or not live.size:
+            gone = np.setdiff1d(model.ids, live)
+            ids[int(rng.integers(0, B))] = gone[int(rng.integers(0, gone.size))] if gone.size else U64(ID_LIMIT - 1)
+        return "by_id", (ids, ks_of(k), mask_of(seed, m, model))
+    raise ValueError(kind)
+
+
+def capture(call):
+    try:
+        return call()
+    except Predicted as e:
+        return {"error": (e.kind, e.id)}
+
+
+def diff(want, got):
+    """None, or what differs between two answers"""
+    if "error" in want or "error" in got:
+        return None if want.get("error") == got.get("error") else f"expected {want.get('error', 'an answer')}, got {got.get('error', 'an answer')}"
+    if len(want["lists"]) != len(got["lists"]):
+        return f"{len(want['lists'])} queries expected, {len(got['lists'])} answered"
+    for b, (w, g) in enumerate(zip(want["lists"], got["lists"])):
+        if len(w[0]) != len(g[0]):
+            return f"query {b}: count {len(g[0])}, expected {len(w[0])}"
+        if not np.array_equal(w[0], g[0]):
+            at = int(np.nonzero(np.asarray(w[0]) != np.asarray(g[0]))[0][0])
+            return f"query {b}: id {g[0][at]} at rank {at}, expected {w[0][at]}"
+        if not np.array_equal(w[1], g[1]):
+            at = int(np.nonzero(np.asarray(w[1]) != np.asarray(g[1]))[0][0])
+            return f"query {b}: distance bits {g[1][at]:#x} at rank {at}, expected {w[1][at]:#x}"
+    if "totals" in want and [int(t) for t in want["totals"]] != [int(t) for t in got["totals"]]:
+        return f"range totals {list(map(int, got['totals']))}, expected {list(map(int, want['totals']))}"
+    if "codes" in want and "codes" in got:
+        for b, (w, g) in enumerate(zip(want["codes"], got["codes"])):
+            if not np.array_equal(w, g):
+                return f"query {b}: group codes {g}, expected {w}"
+    for key in ("struck", "cut", "stages"):                          # the engine's own counters of the read, where both sides have them
+        if key in want and key in got and want[key] != got[key]:
+            return f"{key} {got[key]}, expected {want[key]}"
+    return None
+
+
+def resolve(trace, op, log):
+    """one non-read op of an index-level trace -> the concrete calls [(method, args)] it stands for, given the model's state
+    (a duplicate of a stored row, remove_many and reset name no vector and no id themselves)"""
+    seed, kind = trace["seed"], op[0]
+    d = log.d or trace["d"]
+    if kind in ("add", "upsert", "readd"):
+        _, id, key, dup_of = op
+        v = vectors(seed, key, 1, d)[0]
+        at = np.nonzero(log.alive & (log.ids == U64(dup_of)))[0] if dup_of >= 0 else ()
+        return [("add", (int(id), log.rows[at[-1]].copy() if len(at) else v))]
+    if kind == "zero":
+        return [("add", (int(op[1]), np.zeros(d, dtype=F32)))]
+    if kind == "misfit":
+        return [("add", (int(op[1]), np.ones(int(op[2]), dtype=F32)))]
+    if kind in ("bulk", "reset"):
+        _, n, d, base, perm, key, dup = op
+        calls = [("remove", (log.live_ids(),))] if kind == "reset" and log.n_live() else []
+        return calls + [("add_bulk", (vectors(seed, key, n, d, dup), bulk_ids(seed, key, n, base, perm)))]
+    if kind in ("remove", "remove_absent"):
+        return [("remove", (np.array([op[1]], dtype=U64),))]
+    if kind == "remove_many":
+        _, count, key = op
+        live = log.live_ids()
+        take = rng_of(seed, key, 5).permutation(live.size)[:max(0, min(int(count), live.size - 1))]
+        return [("remove", (live[np.sort(take)],))] if take.size else []
+    if kind in ("compact", "compact_shrink"):
+        return [("compact", (kind == "compact_shrink",))]
+    if kind == "auto_compact":
+        return [("set_auto_compact", (float(op[1]),))]
+    if kind == "codes":
+        _, first, n, key, groups = op
+        return [("set_codes", (int(first), rng_of(seed, key, 6).integers(-1, groups, n).astype(I32)))]
+    if kind == "set":
+        return [("set", (op[1], op[2]))]
+    if kind == "flush":
+        return [("flush", ())]
+    raise ValueError(kind)
+
+
+def apply_mutation(trace, op, log):
+    for name, args in resolve(trace, op, log):
+        getattr(log, name)(*args)
+
+
+def run(trace, adapter, expected=None, on_read=None):
+    """Apply the trace to the adapter and to a fresh model; compare after every read (and the error of every mutation).
+    expected: a list with one slot per op that keeps the reads' arguments and the model's answers between runs of one trace.
+    on_read(step, op, model, args, got): called after every matching read.  Returns the model."""
+    store = trace.get("store", False)
+    model = StoreSim(adapter.vdb, Model(trace["metric"])) if store else Model(trace["metric"], sharded=getattr(adapter, "sharded", False))
+    log = model_log(model)
+    ops = trace["ops"]
+    for step, op in enumerate(ops):
+        what = None
+        if not is_read(op):
+            for name, args in (resolve_store(trace, op) if store else resolve(trace, op, log)):
+                want = capture(lambda: getattr(model, name)(*args) and None or {})
+                got = capture(lambda: getattr(adapter, name)(*args) and None or {})
+                if want.get("error") != got.get("error"):
+                    what = f"{name}: expected {want.get('error', 'no error')}, got {got.get('error', 'no error')}"
+                    break
+        else:
+            if expected is not None and expected[step] is not None:
+                name, args, want = expected[step]
+                if "error" not in want and not (name == "range" and log.sharded):
+                    log.uploaded()                                   # (a refused read uploads nothing: as on the uncached path)
+            else:
+                name, args = materialise_store(trace, op, model) if store else materialise(trace, op, model)
+                want = capture(lambda: getattr(model, name)(*args))
+                if expected is not None and not log.sharded:
+                    expected[step] = (name, args, want)
+            if name == "range" and log.sharded:
+                want = {"error": ("Refused", None)}
+            got = capture(lambda: getattr(adapter, name)(*args))
+            if store:
+                want, got = as_answer(want), as_answer(got)
+            what = diff(want, got)
+            if what is None and on_read is not None:
+                on_read(step, op, model, args, got)
+        if what is not None:
+            head = {k: v for k, v in trace.items() if k != "ops"}
+            head["ops"] = list(ops[:step + 1])
+            raise Mismatch(f"seed {trace['seed']}, profile {trace.get('profile')}, step {step} {op}: {what}\n"
+                           f"replay with lifecycle.run(TRACE, adapter), TRACE = {head!r}")
+    return model
+
+
+def model_log(model):
+    return model.index if isinstance(model, StoreSim) else model
+
+
+def as_answer(x):
+    """a store answer (a list of (sid, bits), or a list of such lists) in the form diff() compares"""
+    if isinstance(x, dict):
+        return x
+    if x and isinstance(x[0], tuple) or not x:
+        x = [x]
+    return {"lists": [([s for s, _ in l], [b for _, b in l]) for l in x]}
+
+
+def shrink(trace, make_adapter, log=None):
+    """Drop ops greedily while the failure persists; make_adapter() gives a fresh adapter for every attempt.  Returns the
+    smallest failing trace found (the failing read stays last)."""
+    def fails(ops):
+        t = dict(trace, ops=ops)
+        try:
+            run(t, make_adapter())
+        except Mismatch as e:
+            return int(str(e).split("step ")[1].split(" ")[0]) + 1
+        except Exception:
+            return 0                                                 # another failure than the one being shrunk: not this trace
+        return 0
+    ops = list(trace["ops"])
+    n = fails(ops)
+    if not n:
+        return None
+    ops = ops[:n]
+    chunk = max(1, len(ops) // 4)
+    while chunk >= 1:
+        i = len(ops) - 1 - chunk
+        while i >= 0:
+            cand = ops[:i] + ops[i + chunk:]
+            n = fails(cand)
+            if n:
+                ops = cand[:n]
+                if log:
+                    log(f"  {len(ops)} ops")
+            i -= chunk
+        chunk //= 2
+    return dict(trace, ops=ops)
+
+
+# ---------------------------------------------------------------------------------------------------------------- store traces
+def store_vector(trace, key):
+    return vectors(trace["seed"], key, 1, trace["d"])[0]
+
+
+def doc_fields(trace, j, key):
+    """the metadata of version `key` of document j: a group (absent for every 7th document), a parity that changes between versions"""
+    f = {"par": str(int(rng_of(trace["seed"], key, 7).integers(0, 3))), "ver": str(key % 5)}
+    if j % 7:
+        f["grp"] = f"g{j % trace.get('groups', 40)}"
+    return f
+
+
+def resolve_store(trace, op):
+    kind = op[0]
+    if kind == "s_insert":
+        _, j, key, dup_of = op
+        return [("insert", (f"doc{j}", store_vector(trace, key if dup_of < 0 else dup_of), doc_fields(trace, j, key)))]
+    if kind == "s_insert_many":                                      # every 9th document of the run shares one vector
+        _, first, n, key = op
+        return [("insert", (f"doc{j}", store_vector(trace, key * 100003 + (j if j % 9 else first)), doc_fields(trace, j, key * 100003 + j)))
+                for j in range(first, first + n)]
+    if kind in ("s_delete", "s_delete_absent"):
+        return [("delete", (f"doc{op[1]}",))]
+    if kind == "s_compact":
+        return [("compact", ())]
+    if kind == "set":
+        return [("set", (op[1], op[2]))]
+    raise ValueError(kind)
+
+
+def materialise_store(trace, op, model):
+    seed, kind, log = trace["seed"], op[0], model.index
+    d = trace["d"]
+    if kind == "s_search":
+        return "search", (queries(seed, op[2], log, 1, d)[0], int(op[1]))
+    if kind == "s_with_filter":
+        return "search_with_filter", (queries(seed, op[2], log, 1, d)[0], int(op[1]), op[3])
+    if kind == "s_prefiltered":
+        _, B, k, qkey, spec = op
+        return "search_batch_prefiltered", (queries(seed, qkey, log, B, d), ks_of(k), spec)
+    if kind == "s_within":
+        _, qkey, rank, limit, spec = op
+        q = queries(seed, qkey, log, 1, d)[0]
+        r = F32(1.0)
+        if model.entries:
+            ok = model._ok(spec)
+            live = log._live(None if ok is None else ("host", ok))
+            rank_ = log.ranking(q, live)
+            if len(rank_[0]):
+                r = rd.radius_at(rank_, min(int(rank), len(rank_[0])))
+        return "search_within", (q, r, int(limit), spec)
+    if kind == "s_similar":
+        _, B, k, skey, spec, absent = op
+        rng = rng_of(seed, skey, 4)
+        names = sorted(model.entries)
+        sids = [names[int(i)] for i in rng.integers(0, len(names), B)] if names else ["doc0"] * B
+        if absent or not names:
+            sids[int(rng.integers(0, B))] = "nobody"
+        return "search_similar_batch", (sids, int(k), spec)
+    if kind == "s_distinct":
+        _, B, k, qkey, spec = op
+        return "search_distinct_batch", (queries(seed, qkey, log, B, d), int(k), spec)
+    raise ValueError(kind)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the generator
+PROFILES = {
+    # d, the dimension after the reset, which error episodes it holds
+    "even":   dict(d=64, d2=40, zero=True, misfit=False),
+    "odd":    dict(d=40, d2=64, zero=True, misfit=False),
+    "misfit": dict(d=40, d2=64, zero=True, misfit=True),
+    "auto":   dict(d=64, d2=40, zero=True, misfit=False, auto=0.3),
+}
+
+# name, seed, profile, metric, what it is for
+PINNED = (
+    ("even-euclid", 11, "even", EUCLID, "ld % 64 == 0; grows 1024 -> 32768 rows of capacity, shrinks, collides the row count, resets to d = 40"),
+    ("even-cosine", 12, "even", COSINE, "the same with a zero-norm episode: InvalidVector while the row lives, answers again once it is gone"),
+    ("even-dot", 13, "even", DOT, "the same under Dot: negative radii, by-id lists that are cut rather than struck"),
+    ("odd-euclid", 21, "odd", EUCLID, "ld % 64 != 0 (d = 40), reset to d = 64"),
+    ("odd-cosine", 22, "odd", COSINE, "d = 40 with the zero-norm episode"),
+    ("odd-dot", 23, "odd", DOT, "d = 40 under Dot"),
+    ("misfit-euclid", 31, "misfit", EUCLID, "a row of another dimension comes and goes: DimensionMismatch from every read in between"),
+    ("misfit-cosine", 32, "misfit", COSINE, "both error episodes in one life"),
+    ("misfit-dot", 33, "misfit", DOT, "the misfit episode under Dot"),
+    ("auto-euclid", 41, "auto", EUCLID, "auto-compaction on for most of the life: reads compact before they search"),
+    ("auto-cosine", 42, "auto", COSINE, "auto-compaction with the zero-norm episode"),
+    ("auto-dot", 43, "auto", DOT, "auto-compaction under Dot"),
+)
+
+
+class _Gen:
+    def __init__(self, seed, profile, metric):
+        self.p = dict(PROFILES[profile])
+        self.trace = {"seed": int(seed), "profile": profile, "metric": int(metric), "d": self.p["d"], "ops": []}
+        self.rng = np.random.default_rng([int(seed), 99])
+        self.m = Model(metric)
+        self.key = 0
+        self.next_id = 0
+        self.groups = 30
+        self.last_mut = None
+        self.pairs = set()
+        self.turn = int(seed)
+        self.distinct_seen = False
+
+    def k(self):
+        self.key += 1
+        return self.key
+
+    def emit(self, op):
+        self.trace["ops"].append(op)
+        if is_read(op):
+            read_begins(self.trace, op, self.m)
+            if self.last_mut:
+                self.pairs.add((self.last_mut, op[0]))
+                self.last_mut = None
+        else:
+            apply_mutation(self.trace, op, self.m)
+            if op[0] in MUTATIONS or op[0] == "remove_many":
+                self.last_mut = "remove" if op[0] == "remove_many" else op[0]
+
+    # -- ids
+    def fresh_ids(self, n):
+        base, self.next_id = self.next_id, self.next_id + n
+        assert self.next_id < ID_LIMIT - 1
+        return base
+
+    def live_id(self):
+        live = self.m.live_ids()
+        return int(live[int(self.rng.integers(0, live.size))])
+
+    def dead_id(self):
+        gone = np.setdiff1d(self.m.ids, self.m.live_ids())
+        return int(gone[int(self.rng.integers(0, gone.size))]) if gone.size else None
+
+    # -- reads
+    def draw_k(self, B):
+        r = self.rng.random()
+        if r < 0.15 and B > 1:
+            return tuple(int(x) for x in self.rng.choice(KS, B))
+        return int(self.rng.choice(KS, p=(0.2, 0.45, 0.2, 0.15)))
+
+    def draw_B(self):
+        big = self.m.n_rows() > 9000
+        return int(self.rng.choice(BATCHES, p=(0.4, 0.3, 0.25, 0.05) if big else (0.25, 0.3, 0.25, 0.2)))
+
+    def draw_mask(self, allow_none=True, compiled=True):
+        r = self.rng.random()
+        if allow_none and r < 0.6:
+            return None
+        if r < 0.8 or not compiled:
+            return ("host", self.k(), float(self.rng.choice((0.5, 0.9))))
+        return ("compiled", int(self.rng.integers(0, self.groups)), 0.0)
+
+    def read(self, kind=None, absent=False):
+        if kind is None:
+            after = self.last_mut
+            want = [r for r in READS if after and (after, r) not in self.pairs]
+            self.turn += 1
+            kind = want[self.turn % len(want)] if want else READS[self.turn % len(READS)]
+        B = self.draw_B()
+        if kind == "search":
+            self.emit(("search", B, self.draw_k(B), self.k(), None))
+        elif kind == "masked":
+            self.emit(("masked", B, self.draw_k(B), self.k(), self.draw_mask(False)))
+        elif kind == "sparse":
+            self.emit(("sparse", B, self.draw_k(B), self.k(), ("host", self.k(), SPARSE_SHARE)))
+        elif kind == "range":
+            rank = int(self.rng.choice((3, 40, 600, 2500)))
+            self.emit(("range", B, self.k(), rank, int(self.rng.choice((8, 256, 2048))),
+                       self.draw_mask(compiled=False) if self.rng.random() < 0.4 else None))   # (the range call takes a host mask only)
+        elif kind == "by_id":
+            self.emit(("by_id", B, self.draw_k(B), self.k(), bool(absent), None if self.rng.random() < 0.7 else self.draw_mask(False)))
+        elif kind == "distinct":
+            self.emit(("distinct", B, self.draw_k(B), self.k(), self.draw_mask() if self.rng.random() < 0.4 else None))
+
+    # -- mutations
+    def mutate(self, kind):
+        rng, d = self.rng, self.m.d
+        if kind == "add":
+            dup = self.live_id() if rng.random() < 0.3 else -1
+            self.emit(("add", self.fresh_ids(1), self.k(), dup))
+        elif kind == "upsert":
+            self.emit(("upsert", self.live_id(), self.k(), -1))
+        elif kind == "readd":
+            i = self.dead_id()
+            if i is None:
+                return self.mutate("upsert")
+            self.emit(("readd", i, self.k(), -1))
+        elif kind == "remove":
+            if self.m.n_live() < 50:
+                return self.mutate("add")
+            if rng.random() < 0.5:
+                self.emit(("remove", self.live_id()))
+            else:
+                self.emit(("remove_many", int(rng.integers(5, max(6, self.m.n_live() // 12))), self.k()))
+        elif kind == "remove_absent":
+            i = self.dead_id()
+            self.emit(("remove_absent", i if i is not None and rng.random() < 0.5 else ID_LIMIT - 2 - int(rng.integers(0, 1000))))
+        elif kind == "bulk":
+            n = int(rng.integers(40, 400))
+            if rng.random() < 0.3 and self.m.n_live() > n:                   # a bulk over ids that are live: an upsert of a range
+                base = int(self.m.live_ids()[0])
+            else:
+                base = self.fresh_ids(n)
+            self.emit(("bulk", n, d, base, int(rng.random() < 0.6), self.k(), 0.15))
+        elif kind in ("compact", "compact_shrink"):
+            self.emit((kind,))
+        elif kind == "auto_compact":
+            self.emit(("auto_compact", float(rng.choice((0.0, 0.1, 0.3, 0.6)))))
+        elif kind == "codes":
+            n = int(rng.integers(1, 600))
+            first = int(rng.integers(0, max(1, self.m.id_bound)))
+            self.emit(("codes", first, min(n, ID_LIMIT - first), self.k(), int(rng.choice((6, self.groups, 150)))))
+
+    def toggle(self):
+        rng = self.rng
+        name = str(rng.choice(("shadow", "sample_cache", "screen", "tiers", "sparse_filter", "large_k", "bounce", "flush")))
+        if name == "flush":
+            self.emit(("flush",))
+        elif name == "tiers":
+            self.emit(("set", "tiers", int(rng.choice((0, NO_DIRECT)))))
+        elif name == "sparse_filter":
+            self.emit(("set", "sparse_filter", int(rng.choice((0, 1, 1, 2)))))
+        elif name == "bounce":
+            self.emit(("set", "bounce", int(rng.choice((0, 64, 512)))))
+        else:
+            self.emit(("set", name, int(rng.integers(0, 2))))
+
+    def mix(self, steps, kinds=None):
+        kinds = kinds or ("add", "add", "upsert", "upsert", "readd", "remove", "remove", "remove_absent", "bulk", "compact",
+                          "compact_shrink", "auto_compact", "codes", "codes")
+        for _ in range(steps):
+            r = self.rng.random()
+            if r < 0.15:
+                self.toggle()
+                continue
+            self.turn += 1
+            missing = [m for m in kinds if any((m, rd_) not in self.pairs for rd_ in READS)]
+            kind = missing[self.turn % len(missing)] if missing and r < 0.75 else str(self.rng.choice(kinds))
+            self.mutate(kind)
+            if self.rng.random() < 0.85:
+                self.read()
+                if self.rng.random() < 0.25:
+                    self.read()
+
+    def bulk(self, n, d=None, perm=1):
+        self.emit(("bulk", n, d or self.m.d or self.p["d"], self.fresh_ids(n), perm, self.k(), 0.15))
+
+    def build(self):
+        p, rng = self.p, self.rng
+        sparse0 = int(rng.choice((1, 2)))
+        self.emit(("set", "sparse_filter", sparse0))
+        self.emit(("set", "shadow", 1))
+        self.emit(("set", "bounce", 64))
+        self.bulk(int(rng.integers(600, 900)), p["d"])
+        self.emit(("codes", 0, 3000, self.k(), 6))                  # few groups: stage A is too shallow for most k
+        self.read("distinct")
+        # one read for each route a small index has, whatever the draws below bring: the direct path, dense scores, the exact scan
+        # (k beyond the candidate depth), the sparse route, distinct stage B (113 groups are not among the first 452 ranks), by-id
+        # lists that are cut (the own id masked out)
+        self.emit(("set", "tiers", 0))
+        self.emit(("set", "sparse_filter", 1))
+        self.emit(("search", 8, 10, self.k(), None))
+        self.emit(("search", 9, 10, self.k(), None))
+        self.emit(("search", 9, 300, self.k(), None))
+        self.emit(("sparse", 9, 10, self.k(), ("host", self.k(), SPARSE_SHARE)))
+        self.emit(("distinct", 8, 113, self.k(), None))
+        self.emit(("by_id", 40, 10, self.k(), False, ("host", self.k(), 0.5)))
+        self.emit(("set", "sparse_filter", sparse0))
+        self.mix(28)
+        if p.get("auto"):
+            self.emit(("auto_compact", p["auto"]))
+            self.read()
+        # grow through the doublings, a few reads on every level, single adds in between so that rows are staged when reads arrive
+        for n in (1300, 2500, 4500):
+            self.mutate("remove")                                   # dead rows in the store when it is re-allocated ...
+            self.bulk(n)
+            self.read("search")                                     # ... and a read right behind the doubling
+            self.mix(4)
+        self.emit(("set", "shadow", 1))                             # the store is re-allocated with the bf16 shadow in place
+        self.bulk(SMALL_N - 300 - self.m.n_rows())                  # just below SMALL_N: the dense path at its largest
+        self.mutate("add")
+        self.read("search")
+        self.bulk(1000)                                             # across SMALL_N upward
+        self.mutate("add")
+        self.read("search")
+        self.emit(("set", "tiers", 0))
+        self.emit(("search", 9, 10, self.k(), None))                # the fused f32 pass
+        self.mix(7)
+        self.emit(("set", "tiers", 0))
+        self.read("masked")
+        # back down: most rows go, rows are staged, the compaction takes them along
+        self.emit(("auto_compact", 0.0))
+        self.emit(("set", "bounce", 64))                            # wide gaps, a small buffer: chunks move directly
+        self.emit(("remove_many", self.m.n_live() - 2600, self.k()))
+        self.read()
+        self.mutate("add")
+        self.mutate("upsert")
+        self.emit(("compact",))
+        self.read()
+        self.mix(6)
+        # the row count collides: a read at n rows, a shrinking compaction, adds back to exactly n rows, a read
+        self.emit(("compact",))
+        self.read("search")
+        n = self.m.n_rows()
+        self.emit(("remove_many", 700, self.k()))
+        self.emit(("set", "bounce", 0))                             # scattered dead rows, the default buffer: through the bounce buffer
+        self.emit(("compact_shrink",))
+        self.bulk(n - self.m.n_rows())
+        self.read()
+        self.read("search")
+        self.mix(6)
+        if p.get("auto"):
+            self.emit(("auto_compact", p["auto"]))
+        else:
+            self.emit(("auto_compact", 0.25))
+        self.emit(("remove_many", int(self.m.n_live() * 0.45), self.k()))
+        self.read()
+        if not p.get("auto"):
+            self.emit(("auto_compact", 0.0))
+        if p["zero"] and self.trace["metric"] == COSINE:
+            z = self.fresh_ids(1)
+            self.emit(("zero", z))
+            self.read("search")
+            self.read("by_id")
+            self.emit(("remove", z))
+            self.read("range")
+            self.read("search")
+        if p["misfit"]:
+            z = self.fresh_ids(1)
+            self.emit(("misfit", z, p["d"] + 3))
+            self.read("distinct")
+            self.read("search")
+            self.emit(("remove", z))
+            self.read("by_id")
+        self.read("by_id", absent=True)
+        self.mix(5)
+        # everything goes; the refill has another dimension
+        self.emit(("remove_many", max(0, self.m.n_live() - 300), self.k()))
+        n = int(rng.integers(700, 1000))
+        self.emit(("reset", n, p["d2"], self.fresh_ids(n), 1, self.k(), 0.15))
+        self.read(READS[self.trace["seed"] % len(READS)])          # (the pinned seeds take every kind here)
+        self.mix(22)
+        self.bulk(1500)
+        self.read()
+        return self.trace
+
+
+LARGE_ROWS = 75_000      # above BF16_MIN_ROWS = 65536 and above the large-k floor 240 (113 + 192) = 73200 rows
+
+# The issue holds the schedules to 20 000 rows AND asks for the bf16 screen and both range routes, which start at 65 536 rows
+# (32 768 survivors for the dense range fallback).  These three short schedules settle it: d = 64, few reads, small batches.
+LARGE_PINNED = (
+    ("large-euclid", 61, EUCLID, "the screening tier's state: grows past 65 536 rows with the shadow on, toggles shadow / sample cache / "
+                                 "screen, shrink-compacts and refills to the same row count, reads plain, large-k and range"),
+    ("large-cosine", 62, COSINE, "the same under Cosine"),
+    ("large-dot", 63, DOT, "the same under Dot"),
+)
+
+
+def large_schedule(seed, metric):
+    g = _Gen(seed, "even", metric)
+    g.trace["profile"] = "large"
+    e, k = g.emit, g.k
+
+    def reads():                                                     # plain (bf16 screen), large k on the screening tier, both range routes
+        e(("search", 9, 10, k(), None))
+        e(("search", 1, 113, k(), None))
+        e(("range", 8, k(), 40, 256, None))                          # the screened route: the candidates of a tight radius
+        e(("range", 1, k(), 40_000, 2048, None))                     # more than 32 768 survivors: the dense fallback
+    e(("set", "shadow", 1))
+    e(("set", "sparse_filter", 1))
+    g.bulk(900, 64)
+    e(("codes", 0, 3000, k(), 6))
+    for n in (20_000, 30_000, LARGE_ROWS - 50_900 - 1200):           # re-allocations with the shadow in place, across 65 536 rows
+        g.bulk(n)
+        e(("search", 1, 10, k(), None))                              # (a bulk is staged like a single add: the read uploads it, the store grows)
+    g.mutate("add")
+    reads()
+    e(("by_id", 8, 10, k(), False, None))
+    e(("distinct", 8, 10, k(), None))
+    e(("masked", 8, 10, k(), ("host", k(), 0.5)))
+    e(("sparse", 8, 10, k(), ("host", k(), SPARSE_SHARE)))
+    for name, value in (("sample_cache", 0), ("sample_cache", 1), ("shadow", 0), ("screen", 0), ("screen", 1), ("shadow", 1), ("large_k", 0),
+                        ("large_k", 1)):
+        e(("set", name, value))
+        g.mutate(("upsert", "add", "remove")[value + (name == "shadow")])
+        e(("search", 9, 10, k(), None))
+        e(("search", 1, 113, k(), None))
+        if name in ("screen", "shadow"):
+            e(("range", 8, k(), 40, 256, None))
+    # the row count collides above the floor: reads at n rows, a shrinking compaction, adds back to exactly n rows, the reads again
+    e(("compact",))
+    reads()
+    n = g.m.n_rows()
+    e(("remove_many", 900, k()))
+    e(("compact_shrink",))
+    g.bulk(n - g.m.n_rows())
+    reads()
+    e(("by_id", 8, 10, k(), False, None))
+    g.mutate("upsert")
+    g.mutate("remove")
+    reads()
+    # back below the floor through removes and a compaction with rows staged, and up again
+    e(("remove_many", g.m.n_live() - 60_000, k()))
+    g.mutate("add")
+    e(("compact",))
+    e(("search", 9, 10, k(), None))
+    e(("range", 8, k(), 40, 256, None))
+    g.bulk(LARGE_ROWS - g.m.n_rows())
+    reads()
+    return g.trace
+
+
+def schedule(seed, profile, metric=EUCLID):
+    """a trace of about 200 ops: see _Gen.build for the phases, PROFILES for what differs between profiles"""
+    return _Gen(seed, profile, metric).build()
+
+
+def pinned(name):
+    for n, seed, profile, metric, _ in PINNED:
+        if n == name:
+            return schedule(seed, profile, metric)
+    for n, seed, metric, _ in LARGE_PINNED:
+        if n == name:
+            return large_schedule(seed, metric)
+    raise KeyError(name)
+
+
+# ---------------------------------------------------------------------------------------------------------------- store schedules
+STORE_PINNED = (
+    ("store-euclid-late", 51, EUCLID, dict(table_at="mid", auto=0.0), "device filter switched on mid-life"),
+    ("store-cosine-late", 52, COSINE, dict(table_at="mid", auto=0.4), "device filter mid-life, auto-compaction"),
+    ("store-dot-early", 53, DOT, dict(table_at="start", auto=0.0), "device filter from the start"),
+    ("store-euclid-early", 54, EUCLID, dict(table_at="start", auto=0.4), "device filter from the start, auto-compaction"),
+)
+STORE_FILTERS = (("eq", "par", "1"), ("ne", "par", "0"), ("exists", "grp"), ("and", [("exists", "grp"), ("ne", "ver", "2")]),
+                 ("or", [("eq", "par", "2"), ("eq", "grp", "g3")]), ("eq", "grp", "g5"))
+
+
+def store_schedule(seed, metric, table_at="mid", auto=0.0, steps=110):
+    rng = np.random.default_rng([int(seed), 98])
+    trace = {"seed": int(seed), "profile": "store", "metric": int(metric), "d": 40, "store": True, "groups": 40, "auto": float(auto),
+             "table_at": table_at, "ops": []}
+    ops = trace["ops"]
+    docs, gone, key = set(), set(), [0]
+
+    def k():
+        key[0] += 1
+        return key[0]
+
+    def flt(none_ok=True):
+        return None if none_ok and rng.random() < 0.3 else STORE_FILTERS[int(rng.integers(0, len(STORE_FILTERS)))]
+
+    def read(i):
+        kind = STORE_READS[i % len(STORE_READS)]
+        kk = int(rng.choice((1, 10, 113)))
+        if kind == "s_search":
+            ops.append((kind, kk, k()))
+        elif kind == "s_with_filter":
+            ops.append((kind, max(kk, 10), k(), STORE_FILTERS[int(rng.integers(0, 3))]))   # (a post-filter: unselective ones, or 3 k rows hold no match)
+        elif kind == "s_prefiltered":
+            B = int(rng.choice(BATCHES))
+            ops.append((kind, B, tuple(int(x) for x in rng.choice(KS[:3], B)) if rng.random() < 0.3 else kk, k(), flt(False)))
+        elif kind == "s_within":
+            ops.append((kind, k(), int(rng.choice((3, 40, 400))), int(rng.choice((8, 256))), flt()))
+        elif kind == "s_similar":
+            ops.append((kind, int(rng.choice(BATCHES)), kk, k(), flt(), bool(rng.random() < 0.1)))
+        else:
+            ops.append((kind, int(rng.choice((1, 8, 9))), kk, k(), flt()))
+
+    if table_at == "start":
+        ops.append(("set", "device_filter", 1))
+    ops.append(("set", "sparse_filter", int(rng.choice((1, 2)))))
+    ops.append(("s_insert_many", 0, 900, k()))
+    docs.update(range(900))
+    turn = int(seed)
+    for step in range(steps):
+        if table_at == "mid" and step == steps // 3:
+            ops.append(("set", "device_filter", 1))
+        if step == steps // 2:                                       # by construction, whatever the draws bring: a compaction by hand
+            ops.append(("s_insert", 0, k(), -1))                     # (an upsert: at least one dead row)
+            ops.append(("s_compact",))                               # over the upserts so far, and a by-id read that names an unknown id
+            ops.append(("s_similar", 8, 10, k(), None, True))
+        r = rng.random()
+        live = sorted(docs)
+        if r < 0.25:
+            ops.append(("s_insert", len(docs) + len(gone) + 1000 + step, k(), -1))
+            docs.add(ops[-1][1])
+        elif r < 0.55:                                               # an upsert, sometimes of a copy of another version's vector
+            ops.append(("s_insert", int(rng.choice(live)), k(), key[0] - 3 if rng.random() < 0.3 and key[0] > 3 else -1))
+        elif r < 0.62 and gone:
+            j = int(rng.choice(sorted(gone)))
+            ops.append(("s_insert", j, k(), -1))
+            gone.discard(j)
+            docs.add(j)
+        elif r < 0.8 and len(live) > 50:
+            j = int(rng.choice(live))
+            ops.append(("s_delete", j))
+            docs.discard(j)
+            gone.add(j)
+        elif r < 0.85:
+            ops.append(("s_delete_absent", 10 ** 7 + step))
+        elif r < 0.9:
+            ops.append(("s_compact",))
+        elif r < 0.95:
+            first = max(docs | gone) + 1 if rng.random() < 0.5 else int(rng.choice(live))
+            n = int(rng.integers(100, 1300))
+            ops.append(("s_insert_many", first, n, k()))
+            for j in range(first, first + n):
+                docs.add(j)
+                gone.discard(j)
+        else:
+            ops.append(("set", "sparse_filter", int(rng.choice((0, 1, 2)))))
+        turn += 1
+        read(turn)
+        if rng.random() < 0.2:
+            turn += 1
+            read(turn)
+    return trace
+
+
+def store_pinned(name):
+    for n, seed, metric, kw, _ in STORE_PINNED:
+        if n == name:
+            return store_schedule(seed, metric, **kw)
+    raise KeyError(name)
+
+
+# ---------------------------------------------------------------------------------------------------------------- coverage
+def read_begins(trace, op, model):
+    """What every read does to the model's state, without the oracle: True when the model refuses it (then nothing is uploaded,
+    exactly as Model.search & co. raise before they upload), else the staged rows are uploaded and auto-compaction may run."""
+    try:
+        ids = materialise(trace, op, model)[1][0] if op[0] == "by_id" else None
+        model.refusal({"masked": "search", "sparse": "search"}.get(op[0], op[0]), ids)
+    except Predicted:
+        return True
+    model.uploaded()
+    return False
+
+
+def coverage(trace):
+    """What a trace reaches, from the trace alone: {"pairs": (mutation, first read after it), "counts": the Log's counters,
+    "reads": kinds in order, "errors": how many reads expect an error}.  Error reads are predicted without the oracle."""
+    m = Model(trace["metric"])
+    pairs, reads, errors, last = set(), [], 0, None
+    for op in trace["ops"]:
+        if is_read(op):
+            reads.append(op[0])
+            if last:
+                pairs.add((last, op[0]))
+                last = None
+            errors += read_begins(trace, op, m)
+        else:
+            apply_mutation(trace, op, m)
+            if op[0] in MUTATIONS or op[0] == "remove_many":
+                last = "remove" if op[0] == "remove_many" else op[0]
+    return {"pairs": pairs, "counts": dict(m.counts), "reads": reads, "errors": errors}
+
+
+_SLOTS = {}
+
+
+def slots(name, trace):
+    """the `expected` list of run() for a pinned trace: computed by the first run, shared by every later one"""
+    return _SLOTS.setdefault(name, [None] * len(trace["ops"]))
+
+
+# ---------------------------------------------------------------------------------------------------------------- adapters over the engine
+class EngineErrors:
+    """the engine's exceptions -> the kinds the model predicts"""
+
+    def guarded(self, call):
+        v = self.vdb
+        try:
+            return call()
+        except v.VectorNotFound as e:
+            raise Predicted("VectorNotFound", e.id)
+        except v.DimensionMismatch:
+            raise Predicted("DimensionMismatch")
+        except v.InvalidVector:
+            raise Predicted("InvalidVector")
+        except v.VectorDbError as e:
+            if "sharded" in str(e):
+                raise Predicted("Refused")
+            raise
+        except ValueError as e:
+            if "device filter is off" in str(e):
+                raise Predicted("NeedsTable")
+            raise
+
+
+class GpuIndexAdapter(EngineErrors):
+    """GpuFlatIndex (devices=None) or one sharded handle (devices=[0, 0, 0]) plus a MetaTable: column 0 holds the group codes,
+    the presence bitmap follows add / remove.  Accumulates the engine's own counters over the run (self.seen) and notes the
+    route of every plain search (self.route)."""
+
+    def __init__(self, vdb, metric, devices=None):
+        self.vdb, self.sharded = vdb, devices is not None
+        self.ix = vdb.GpuFlatIndex(vdb.DistanceMetric(metric), keep_host_copy=False, devices=devices)
+        self.table = vdb.MetaTable(0)
+        self.id_bound = 0
+        self.settings = dict(shadow=0, tiers=0, sparse_filter=0, screen=1, large_k=1, sample_cache=1)
+        self.seen = Counter()
+        self.route, self.raw = None, None
+        self._compactions, self._cap = 0, 0
+
+    def close(self):
+        self.table.close()
+
+    # -- mutations
+    def _after_write(self):
+        st = self.ix.store_stats()
+        if st[4] != self._compactions:                               # a compaction ran (by hand or automatic): its chunk counts
+            self._compactions = st[4]
+            self.seen["compactions"] += 1
+            self.seen["chunks_direct"] += st[8]
+            self.seen["chunks_bounce"] += st[9]
+        if st[2] != self._cap:
+            if self._cap and st[2] > self._cap:
+                self.seen["grown"] += 1
+                self.seen["grown_with_shadow"] += self.settings["shadow"]
+            if st[2] and st[2] < self._cap:
+                self.seen["shrunk"] += 1
+            self._cap = st[2]
+
+    def add(self, id, v):
+        self.ix.add(int(id), self.vdb.Vector(v))
+        self.table.set_present(int(id), 1, True)
+        self.id_bound = max(self.id_bound, int(id) + 1)
+
+    def add_bulk(self, rows, ids):
+        ids = np.ascontiguousarray(ids, dtype=U64)
+        self.ix.add_bulk(rows, ids=ids)
+        lo, hi = int(ids.min()), int(ids.max())
+        if hi - lo + 1 == ids.size:
+            self.table.set_present(lo, ids.size, True)
+        else:
+            for i in ids.tolist():
+                self.table.set_present(i, 1, True)
+        self.id_bound = max(self.id_bound, hi + 1)
+        self._after_write()
+
+    def remove(self, ids):
+        for i in np.atleast_1d(ids).tolist():
+            self.ix.remove(int(i))
+            if i < ID_LIMIT:
+                self.table.set_present(int(i), 1, False)
+
+    def compact(self, shrink=False):
+        got = self.ix.compact(shrink=shrink)
+        self._after_write()
+        return got
+
+    def set_auto_compact(self, f):
+        self.ix.set_auto_compact(f)
+
+    def set_codes(self, first, codes):
+        self.table.set_codes(0, int(first), codes)
+
+    def set(self, name, value):
+        ix = self.ix
+        {"shadow": lambda: ix.set_shadow(bool(value)), "sample_cache": lambda: ix.set_sample_cache(bool(value)),
+         "screen": lambda: ix.set_screen(int(value)), "tiers": lambda: ix.set_tiers(int(value)),
+         "sparse_filter": lambda: ix.set_sparse_filter(int(value)), "large_k": lambda: ix.set_large_k(bool(value)),
+         "bounce": lambda: ix.debug_set_compact_bounce(int(value))}[name]()
+        self.settings[name] = int(value)
+
+    def flush(self):
+        self.ix.flush()
+        self._after_write()
+
+    # -- reads
+    def _masked(self, mask, call):
+        """call(**mask keywords) under None | ("host", ok by id) | ("compiled", code): Ne(column 0, code) compiled on the device"""
+        if mask is None:
+            return call()
+        if mask[0] == "host":
+            words, bits = dd.id_mask(mask[1])
+            return call(id_mask=words, mask_bits=bits)
+        cm = self.table.compile([(self.table.NE, 0, int(mask[1]))], max(self.id_bound, 1))
+        try:
+            return call(compiled_mask=cm)
+        finally:
+            cm.release()
+
+    def _read(self, call):
+        try:
+            return self.guarded(call)
+        finally:
+            self._after_write()
+
+    def search(self, q, ks, mask=None):
+        self.route = None
+        gi, gd, gc = self._read(lambda: self._masked(mask, lambda **kw: self.ix.search_batch_arrays(q, ks, **kw)))
+        self.raw = (gi, gd, gc)
+        if mask is not None and self.settings["sparse_filter"]:
+            sp = self.ix.sparse_stats()
+            self.seen["sparse_route"] += sp[0]
+            self.route = "sparse" if sp[0] else None
+        if self.route is None and not self.sharded:
+            st = self.ix.last_stats()
+            nq = len(q)
+            if st["bf16_screen"]:
+                self.route = "bf16"
+                self.seen["bf16_shadow_rows"] += st["shadow_rows"]   # the engine's word that the pass read the bf16 shadow
+                self.seen["bf16_plain_rows"] += 1 - st["shadow_rows"]
+                self.seen["bf16_large_k"] += int(st["kprime"] > 512)
+            elif st["exact_queries"] == nq and not st["rows_scanned"] and not st["mfma_queries"] and not st["sample_rows"]:
+                small = self.ix.store_stats()[0] <= SMALL_N
+                self.route = "direct" if small and nq <= DIRECT_MAX_Q and not self.settings["tiers"] & NO_DIRECT else "exact"
+            elif st["exact_queries"] == nq:
+                self.route = "exact"
+            elif st["rows_scanned"]:
+                self.route = "fused"
+            else:
+                self.route = "dense"
+            self.seen["route_" + self.route] += 1
+        return {"lists": lists_of(gi, gd, gc)}
+
+    def range(self, q, radii, max_results, mask=None):
+        gi, gd, gc, totals = self._read(lambda: self._masked(mask, lambda **kw: self.ix.range_search_batch(q, np.asarray(radii, dtype=F32), max_results, **kw)))
+        st = self.ix.range_stats()
+        self.seen["range_screened"] += st[0]
+        self.seen["range_exact"] += st[1]
+        self.seen["range_dense"] += st[2]
+        return {"lists": lists_of(gi, gd, gc), "totals": [int(t) for t in totals]}
+
+    def by_id(self, ids, ks, mask=None):
+        gi, gd, gc = self._read(lambda: self._masked(mask, lambda **kw: self.ix.search_batch_by_id(ids, ks, **kw)))
+        st = self.ix.by_id_stats()
+        self.seen["by_id_struck"] += st[1]
+        self.seen["by_id_cut"] += st[2]
+        return {"lists": lists_of(gi, gd, gc), "struck": st[1], "cut": st[2]}
+
+    def distinct(self, q, ks, mask=None):
+        gi, gd, gcodes, gc = self._read(lambda: self._masked(mask, lambda **kw: self.ix.search_batch_distinct(q, ks, self.table, 0, **kw)))
+        st = self.ix.distinct_stats()
+        for j, key in enumerate(("distinct_a", "distinct_b", "distinct_c")):
+            self.seen[key] += st[1 + j]
+        return {"lists": lists_of(gi, gd, gc), "codes": [np.array(gcodes[b, :int(c)]) for b, c in enumerate(gc)], "stages": st[1:4]}
+
+
+def predicted_route(log, settings, op, args):
+    """The route a plain, unmasked search with one k is MEANT to take, from the sizes alone (None: not predicted): the direct
+    path (at most SMALL_N rows, at most DIRECT_MAX_Q queries), dense scores of a small index, the fused f32 pass above
+    SMALL_N, the exact scan for k beyond the tiers' candidate depth."""
+    if op[0] != "search" or not np.isscalar(args[1]) or not log.ids.size:
+        return None
+    n, nq, k = log.n_rows(), len(args[0]), int(args[1])
+    if n >= BF16_MIN_ROWS:                                           # the screening tier: k <= 112 always, larger k from 240 (k + 192) rows
+        if not settings["screen"]:
+            return "fused" if k <= 10 else None
+        if k <= 112 or (settings["large_k"] and n >= 240 * (k + 192)):
+            return "bf16"
+        return "exact"
+    if n <= SMALL_N and nq <= DIRECT_MAX_Q and not settings["tiers"] & NO_DIRECT:
+        return "direct"
+    if k == 300:
+        return "exact"
+    if k <= 10:
+        return "dense" if n <= SMALL_N else "fused"
+    return None
+
+
+class GpuStoreAdapter(EngineErrors):
+    """VectorStore over a GpuFlatIndex, driven by the store traces"""
+
+    def __init__(self, vdb, metric, auto_compact=0.0):
+        self.vdb = vdb
+        self.store = vdb.VectorStore(vdb.DistanceMetric(metric), auto_compact=auto_compact)
+        self.seen = Counter()
+
+    def close(self):
+        self.store.set_device_filter(False)
+
+    def insert(self, sid, v, fields):
+        self.store.insert_with_metadata(sid, self.vdb.Vector(v), self.vdb.Metadata(dict(fields)))
+
+    def delete(self, sid):
+        self.guarded(lambda: self.store.delete(sid))
+
+    def compact(self):
+        self.store.compact()
+
+    def set(self, name, value):
+        if name == "device_filter":
+            self.store.set_device_filter(bool(value))
+        else:
+            self.store.set_sparse_filter(int(value))
+
+    def _out(self, results):
+        return [(r.id, int(np.float32(r.distance).view(np.uint32))) for r in results]
+
+    def _note(self):
+        ix = self.store.index()
+        self.seen["sparse_route"] = ix.sparse_stats()[2]
+        self.seen["compactions"] = ix.store_stats()[4]
+
+    def _read(self, call):
+        try:
+            return self.guarded(call)
+        finally:
+            self._note()
+
+    def search(self, q, k):
+        return self._out(self._read(lambda: self.store.search(self.vdb.Vector(q), k)))
+
+    def search_with_filter(self, q, k, spec):
+        return self._out(self._read(lambda: self.store.search_with_filter(self.vdb.Vector(q), k, flt_of(self.vdb, spec))))
+
+    def search_batch_prefiltered(self, q, ks, spec):
+        qs = [(self.vdb.Vector(q[b]), k_of(ks, b)) for b in range(len(q))]
+        self.seen["prefiltered_compiled" if self.store.device_filter() else "prefiltered_host"] += 1
+        return [self._out(r) for r in self._read(lambda: self.store.search_batch_prefiltered(qs, flt_of(self.vdb, spec)))]
+
+    def search_within(self, q, radius, limit, spec):
+        return self._out(self._read(lambda: self.store.search_within(self.vdb.Vector(q), radius, limit, flt_of(self.vdb, spec))))
+
+    def search_similar_batch(self, sids, k, spec):
+        out = [self._out(r) for r in self._read(lambda: self.store.search_similar_batch(sids, k, flt_of(self.vdb, spec)))]
+        st = self.store.index().by_id_stats()
+        self.seen["by_id_struck"] += st[1]
+        self.seen["by_id_cut"] += st[2]
+        return out
+
+    def search_distinct_batch(self, q, k, spec):
+        qs = [self.vdb.Vector(x) for x in q]
+        out = [self._out(r) for r in self._read(lambda: self.store.search_distinct_batch(qs, k, StoreSim.GROUP_FIELD, flt_of(self.vdb, spec)))]
+        self.seen["distinct"] += 1
+        return out

@@ -5,6 +5,7 @@ moved, not recomputed; the index goes on living afterwards."""
 import numpy as np
 import pytest
 
+import lifecycle
 import oracle
 from conftest import load_package
 from test_compact_cpu import pack
@@ -19,64 +20,10 @@ def vdb():
     return v
 
 
-class Model:
-    """What the device store must hold: every row ever appended, in order, with its id and whether it is still alive."""
-
-    def __init__(self, vdb, metric, rows, ix=None, **kw):
-        self.vdb, self.metric = vdb, metric
-        self.ix = ix or vdb.GpuFlatIndex(vdb.DistanceMetric(metric), keep_host_copy=False, **kw)
-        self.rows = np.zeros((0, rows.shape[1]), dtype=np.float32)
-        self.ids = np.zeros(0, dtype=np.uint64)
-        self.alive = np.zeros(0, dtype=bool)
-        self.add_bulk(rows, np.arange(rows.shape[0], dtype=np.uint64))
-
-    def _kill(self, ids):
-        self.alive &= ~np.isin(self.ids, np.asarray(ids, dtype=np.uint64))
-
-    def add_bulk(self, rows, ids):
-        ids = np.asarray(ids, dtype=np.uint64)
-        self.ix.add_bulk(rows, ids=ids)
-        self._kill(ids)
-        self.rows = np.concatenate([self.rows, rows])
-        self.ids = np.concatenate([self.ids, ids])
-        self.alive = np.concatenate([self.alive, np.ones(ids.size, dtype=bool)])
-
-    def add(self, id, v):
-        self.ix.add(int(id), self.vdb.Vector(v))
-        self._kill([id])
-        self.rows = np.concatenate([self.rows, v[None]])
-        self.ids = np.concatenate([self.ids, np.array([id], dtype=np.uint64)])
-        self.alive = np.concatenate([self.alive, [True]])
-
-    def remove(self, ids):
-        for i in ids:
-            self.ix.remove(int(i))
-        self._kill(ids)
-
-    def compact(self, **kw):
-        got = self.ix.compact(**kw)
-        self.rows, self.ids = self.rows[self.alive], self.ids[self.alive]
-        self.alive = np.ones(self.ids.size, dtype=bool)
-        return got
-
-    def survivors(self):
-        return np.ascontiguousarray(self.rows[self.alive]), np.ascontiguousarray(self.ids[self.alive])
-
-    def fresh(self, **kw):
-        rows, ids = self.survivors()
-        ix = self.vdb.GpuFlatIndex(self.vdb.DistanceMetric(self.metric), keep_host_copy=False, **kw)
-        ix.add_bulk(rows, ids=ids)
-        return ix
-
-    def check(self, q, k, qsel=None, got=None, **kw):
-        rows, ids = self.survivors()
-        gi, gd, gc = got if got is not None else self.ix.search_batch_arrays(q, k, **kw)
-        for b in (range(q.shape[0]) if qsel is None else qsel):
-            oi, od = oracle.flat_search(self.metric, rows, q[b], k, ids=ids)
-            assert gc[b] == len(oi), (b, gc[b], len(oi))
-            assert np.array_equal(gi[b, :gc[b]], oi), (b, gi[b, :gc[b]], oi)
-            assert np.array_equal(gd[b, :gc[b]].view(np.uint32), od.view(np.uint32)), (b, gd[b, :gc[b]], od)
-        return gi, gd, gc
+def Model(vdb, metric, rows, ix=None, **kw):
+    """What the device store must hold (lifecycle.Model: every row ever appended, in order, with its id and whether it is still
+    alive), driving an index: every mutation of the model goes to the index too."""
+    return lifecycle.Model.driving(vdb, metric, rows, ix=ix, **kw)
 
 
 def same(a, b):

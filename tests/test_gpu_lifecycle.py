@@ -1,0 +1,146 @@
+"""Stateful lifecycle tests on the GPU (tests/lifecycle.py; tests/test_lifecycle_cpu.py proves on the CPU that these schedules
+catch stale state): long seeded schedules of interleaved mutations and reads through a GpuFlatIndex, through one sharded
+handle and through VectorStore, every read compared bit for bit with the model -- ids, order, counts, distance bits, range
+totals, group codes, the by-id struck / cut counters and the distinct stage counters, or the predicted error.
+
+After each schedule the engine's own counters, accumulated over the run, must show that the routes were taken: the direct
+path, dense scores of a small index, the fused f32 pass, the exact scan, the exact range scan, the sparse route, distinct stages A
+and B, by-id struck and cut, compaction chunks moved directly and through the bounce buffer, a re-allocation with the shadow on.
+The route of every plain search is also compared with the one its sizes are meant to take (lifecycle.predicted_route).
+
+The bf16 screening tier, its sample copy and shadow rows, the screened range route and the dense range fallback start at
+65 536 rows (32 768 survivors), above the 20 000 rows the twelve schedules are held to: three short schedules of 75 000 rows
+(test_large_lifecycle) reach them and assert last_stats()["bf16_screen"], ["shadow_rows"], range_stats()[0] and [2].
+
+What the counters can and cannot tell: the direct path and the exact scan both report exact_queries == nq and nothing else,
+so "direct" against "exact" is told apart by the sizes only (the same rule predicted_route uses); what the route check does
+prove is direct / exact against dense / fused / bf16.  grown_with_shadow is the adapter's own memory of set_shadow at a
+capacity change; that the shadow is READ is the engine's shadow_rows flag, asserted in test_large_lifecycle.  On the sharded
+runs every range read is refused, so more than 15 % of their reads expect an error (10-18 % refusals plus the episodes).
+
+Twin equality: on a sample of plain searches the answer equals that of a fresh index bulk-loaded with the survivors, so a
+failure says whether the model or the life before the read is at fault."""
+import numpy as np
+import pytest
+
+import lifecycle as lc
+from conftest import load_package
+
+pytestmark = pytest.mark.gpu
+
+NAMES = [p[0] for p in lc.PINNED]
+LARGE_NAMES = [p[0] for p in lc.LARGE_PINNED]
+STORE_NAMES = [p[0] for p in lc.STORE_PINNED]
+_TRACES = {}
+
+
+@pytest.fixture(scope="module")
+def vdb():
+    v = load_package()
+    v.build()
+    return v
+
+
+def trace_of(name):
+    if name not in _TRACES:
+        _TRACES[name] = lc.store_pinned(name) if name in STORE_NAMES else lc.pinned(name)
+    return _TRACES[name]
+
+
+def same(a, b):
+    return np.array_equal(a[2], b[2]) and np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32))
+
+
+def life(vdb, name, devices=None):
+    """one pinned schedule through an index adapter; returns the adapter's counters and what the model meant to reach"""
+    t = trace_of(name)
+    ad = lc.GpuIndexAdapter(vdb, t["metric"], devices=devices)
+    meant, n_search, off_route = lc.Counter(), [0], []
+
+    def on_read(step, op, model, args, got):
+        if "error" in got:
+            meant["error_" + got["error"][0]] += 1
+            return
+        if "stages" in got:
+            meant["distinct_reads"] += 1
+        want = lc.predicted_route(model, ad.settings, op, args)
+        if want is not None and not ad.sharded:
+            if ad.route != want:
+                off_route.append((step, op, ad.route, want, ad.ix.last_stats()))
+            meant["route_" + want] += 1
+        if op[0] == "search":
+            n_search[0] += 1
+            if n_search[0] % 6 == 0:                                 # twin equality, on every sixth plain search
+                rows, ids = model.survivors()
+                twin = vdb.GpuFlatIndex(vdb.DistanceMetric(t["metric"]), keep_host_copy=False)
+                twin.add_bulk(rows, ids=ids)
+                assert same(ad.raw, twin.search_batch_arrays(args[0], args[1])), (name, step, op)
+                meant["twins"] += 1
+    try:
+        lc.run(t, ad, expected=lc.slots(name, t), on_read=on_read)
+    finally:
+        ad.close()
+    print(name, "sharded" if devices else "plain", dict(ad.seen), dict(meant))
+    assert not off_route, off_route                                  # every predicted route was the one taken
+    return ad.seen, meant
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_index_lifecycle(vdb, name):
+    seen, meant = life(vdb, name)
+    for route in ("direct", "dense", "fused", "exact"):
+        assert meant["route_" + route] > 0 and seen["route_" + route] >= meant["route_" + route], (route, seen, meant)
+    assert seen["range_exact"] > 0 and seen["sparse_route"] > 0, seen
+    assert seen["distinct_a"] > 0 and seen["distinct_b"] > 0, seen
+    assert seen["by_id_struck"] > 0 and seen["by_id_cut"] > 0, seen
+    assert seen["chunks_direct"] > 0 and seen["chunks_bounce"] > 0 and seen["compactions"] >= 4, seen
+    assert seen["grown"] >= 3 and seen["grown_with_shadow"] >= 1 and seen["shrunk"] >= 1, seen
+    assert meant["twins"] >= 2, meant
+    t = trace_of(name)
+    if t["metric"] == lc.COSINE:
+        assert meant["error_InvalidVector"] >= 2, meant
+    if any(op[0] == "misfit" for op in t["ops"]):
+        assert meant["error_DimensionMismatch"] >= 2, meant
+    assert meant["error_VectorNotFound"] >= 1, meant
+
+
+@pytest.mark.parametrize("name", LARGE_NAMES)
+def test_large_lifecycle(vdb, name):
+    """75 000 rows of d = 64: the bf16 screening tier with and without the shadow rows (the engine's own shadow_rows flag), with
+    and without its sample copy, large k on it, the screened range route and the dense range fallback -- before and after a
+    shrinking compaction refilled to the same row count.  Above the 20 000 rows the other schedules are held to: these routes
+    start at 65 536 rows."""
+    seen, meant = life(vdb, name)
+    assert meant["route_bf16"] >= 10 and seen["route_bf16"] >= meant["route_bf16"], (seen, meant)
+    assert seen["bf16_shadow_rows"] > 0 and seen["bf16_plain_rows"] > 0 and seen["bf16_large_k"] > 0, seen
+    assert meant["route_fused"] > 0 and meant["route_exact"] > 0, meant          # set_screen(0); large k with set_large_k(0)
+    assert seen["range_screened"] > 0 and seen["range_dense"] > 0 and seen["range_exact"] > 0, seen
+    assert seen["grown_with_shadow"] >= 2 and seen["shrunk"] >= 1 and seen["compactions"] >= 3, seen
+    assert seen["by_id_struck"] > 0 and seen["distinct_a"] > 0 and seen["sparse_route"] > 0 and meant["twins"] >= 2, (seen, meant)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_sharded_lifecycle(vdb, name):
+    seen, meant = life(vdb, name, devices=[0, 0, 0])
+    t = trace_of(name)
+    assert meant["error_Refused"] == sum(1 for op in t["ops"] if op[0] == "range") > 0, meant    # every range read, refused
+    assert seen["range_exact"] == 0 and seen["sparse_route"] > 0, seen
+    assert seen["distinct_a"] > 0 and seen["distinct_b"] > 0, seen
+    assert seen["by_id_struck"] > 0 and seen["by_id_cut"] > 0, seen
+    assert seen["compactions"] >= 4 and meant["twins"] >= 2, (seen, meant)
+
+
+@pytest.mark.parametrize("name", STORE_NAMES)
+def test_store_lifecycle(vdb, name):
+    t = trace_of(name)
+    ad = lc.GpuStoreAdapter(vdb, t["metric"], auto_compact=t["auto"])
+    kinds = lc.Counter()
+    lc.run(t, ad, expected=lc.slots(name, t), on_read=lambda step, op, model, args, got: kinds.update([(op[0], "error" in got)]))
+    print(name, dict(ad.seen), dict(kinds))
+    seen = ad.seen
+    assert seen["prefiltered_compiled"] > 0 and seen["distinct"] > 0, seen
+    assert (seen["prefiltered_host"] > 0) == (t["table_at"] == "mid"), seen
+    assert seen["sparse_route"] > 0 and seen["by_id_struck"] + seen["by_id_cut"] > 0, seen
+    assert seen["compactions"] > 0, seen
+    assert all(kinds[(k, False)] > 0 for k in lc.STORE_READS), kinds
+    assert any(e for (_, e) in kinds), kinds                                                   # a predicted error was met

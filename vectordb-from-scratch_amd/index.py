@@ -322,7 +322,8 @@ class GpuFlatIndex(Index):
 
     def by_id_stats(self):
         """The last search_batch_by_id: [0] queries, [1] queries whose own id was found in their list and struck, [2] queries
-        whose list was cut at k instead, [3] 0."""
+        whose list was cut instead, [3] 0.  The lists are those the device searched: max(k) + 1 entries for every query, so with a
+        per-query k a query counts as struck when its own id lies anywhere among its max(k) + 1 nearest."""
         out = (ctypes.c_uint64 * 4)()
         rc = self._L.vdb_flat_by_id_stats(self._h, out)
         if rc:
