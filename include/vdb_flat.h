@@ -80,7 +80,8 @@ void vdb_flat_destroy(vdb_flat_index *h);
  * two ranks on one device).
  *
  * Not available on a sharded handle: the two-half / ticket forms of the device search (begin/finish, submit/wait),
- * vdb_flat_distances_batch, the range searches (vdb_flat_range_search_batch, vdb_flat_range_search_batch_device), the
+ * vdb_flat_distances_batch, the range searches (vdb_flat_range_search_batch, vdb_flat_range_search_batch_device), the grouped
+ * searches (vdb_flat_search_batch_grouped, vdb_flat_search_batch_grouped_filtered, vdb_flat_grouped_stats), the
  * vdb_flat_debug_* probes and vdb_flat_search_batch_sharded (that one is the process-per-GPU form of the same exchange,
  * vdb_shard.h); they return VDB_ERR_INVALID_ARGUMENT.
  */
@@ -524,6 +525,52 @@ int vdb_flat_search_batch_distinct_filtered(vdb_flat_index *h, const float *quer
                                             uint64_t *out_ids, float *out_dists, int32_t *out_codes, size_t *out_counts);
 int vdb_flat_distinct_stats(const vdb_flat_index *h, uint64_t out[8]);
 size_t vdb_flat_distinct_depth(size_t k, size_t len, int stage);
+
+/*
+ * ONE BATCH, A FILTER PER QUERY (no reference counterpart: search_batch_with_filter, src/storage.rs:313-322, takes one filter for
+ * the batch, while every request of POST /search carries its own, routes.rs:30-35).  One sentence defines the call: the answer for
+ * query b is what vdb_flat_search_batch returns for that query ALONE with k_b under mask group_of[b] -- under no mask for
+ * VDB_GROUP_NONE: ids, order, distance bits and count, on every route.
+ *  - id_masks: n_masks masks of (mask_bits + 63) / 64 words each, one after the other, host memory; layout and eligibility are those
+ *    of vdb_flat_search_batch (LSB first, an id at or beyond mask_bits is ineligible, 64-bit ids compared as unsigned).  The
+ *    _filtered form takes compiled masks (vdb_meta_compile), each with its own length, all on the handle's device; the handle's
+ *    stream is ordered behind the event of every referenced mask and nothing is uploaded.
+ *  - group_of[b]: the mask of query b, or VDB_GROUP_NONE.  A mask no query references is never read.
+ *  - ks: the answer for k_b is the first k_b entries of the answer for max(ks).
+ * The queries that share a mask form a group, and the groups are answered in ONE launch chain, not one per mask (csrc/
+ * kernels_grouped.hip): one kernel writes the row mask of every referenced group (a row's id and live bit are read
+ * once for all of them), the eligible-row counts E_g of all groups come back in one copy, the host permutes the queries so that a
+ * group's are contiguous and plans a table of tiles -- 64 list positions x 64 queries of ONE group -- per pass of 256 queries, one
+ * launch writes all eligible-row lists, and per pass one scan (the tile of the sparse-filter route, the reference's operation order)
+ * and one select in EMIT mode answer the queries; one launch puts the results back into the caller's order.  Exact by construction.
+ * A group with E_g = 0 has counts 0.  Two capacity limits, not tuning: a group with E_g > 131072, and every group when k (clamped to
+ * the index's length) exceeds 2048, is answered by one ordinary masked search of its queries; the unfiltered queries by one ordinary
+ * search.  The route never consults vdb_flat_set_sparse_filter.
+ * Errors, in this order: an empty index or k = 0 gives counts 0 before any check; VDB_ERR_INVALID_ARGUMENT before any device work
+ * for a NULL group_of, an index >= n_masks that is not VDB_GROUP_NONE, n_masks > 1024, n_masks > 0 with a NULL mask array or a NULL
+ * entry among the referenced masks, a compiled mask on another device; the dimension mismatch of a search; under Cosine one live
+ * zero-norm row fails the call, masked or not; a zero-norm query anywhere in the batch gives VDB_ERR_INVALID_VECTOR (before any NaN);
+ * a NaN distance at a row eligible FOR THAT QUERY'S MASK gives VDB_ERR_NAN -- a NaN row only other groups admit does not.
+ * Locking and tickets as vdb_flat_search_batch: refused while a submitted search is outstanding; staged adds are flushed first.
+ * Not available on a sharded handle.
+ * vdb_flat_grouped_stats describes the last call: [0] queries, [1] masks referenced, [2] queries answered by the grouped scan, [3] by
+ * a per-group ordinary search, [4] unfiltered queries, [5] eligible rows summed over the scanned groups, [6] tiles launched, [7] passes.
+ * vdb_flat_debug_group_plan needs no handle and no device: the plan for group_of and the eligible-row counts elig[n_masks] at
+ * k <= 2048.  perm[i] = the caller's index of permuted query i (scanned groups first, then the groups with nothing eligible, the
+ * groups beyond the capacity, the unfiltered queries; a group's queries contiguous and in the caller's order); tiles[t] = {group,
+ * first list position, first permuted query, queries}; pass of a tile = first permuted query / 256.  Returns the number of tiles
+ * (at most cap are written; perm and tiles may be NULL), (size_t)-1 for a bad group index.
+ */
+#define VDB_GROUP_NONE 0xffffffffu      /* this query is searched without a filter */
+int vdb_flat_search_batch_grouped(vdb_flat_index *h, const float *queries, size_t nq, size_t dim, const size_t *ks, size_t k,
+                                  const uint64_t *id_masks, size_t n_masks, size_t mask_bits, const uint32_t *group_of,
+                                  size_t kstride, uint64_t *out_ids, float *out_dists, size_t *out_counts);
+int vdb_flat_search_batch_grouped_filtered(vdb_flat_index *h, const float *queries, size_t nq, size_t dim, const size_t *ks, size_t k,
+                                           const vdb_meta_mask *const *masks, size_t n_masks, const uint32_t *group_of,
+                                           size_t kstride, uint64_t *out_ids, float *out_dists, size_t *out_counts);
+int vdb_flat_grouped_stats(const vdb_flat_index *h, uint64_t out[8]);
+size_t vdb_flat_debug_group_plan(const uint32_t *group_of, size_t nq, const uint32_t *elig, size_t n_masks, uint32_t *perm,
+                                 uint32_t *tiles, size_t cap);
 
 /*
  * Opt-in bf16 SHADOW of the rows for the screening pass (no reference counterpart; results are identical with and without

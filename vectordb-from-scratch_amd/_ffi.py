@@ -19,6 +19,7 @@ SYMBOLS = [
     "vdb_flat_range_search_batch", "vdb_flat_range_search_batch_device", "vdb_flat_range_stats",
     "vdb_flat_search_batch_by_id", "vdb_flat_search_batch_by_id_filtered", "vdb_flat_by_id_stats",
     "vdb_flat_search_batch_distinct", "vdb_flat_search_batch_distinct_filtered", "vdb_flat_distinct_stats", "vdb_flat_distinct_depth",
+    "vdb_flat_search_batch_grouped", "vdb_flat_search_batch_grouped_filtered", "vdb_flat_grouped_stats", "vdb_flat_debug_group_plan",
     "vdb_flat_set_sparse_filter", "vdb_flat_sparse_stats", "vdb_flat_sparse_limit", "vdb_flat_debug_eligible_rows", "vdb_flat_debug_sparse_tile_rows", "vdb_flat_debug_sparse_tile_queries",
     "vdb_meta_create", "vdb_meta_destroy", "vdb_meta_set_codes", "vdb_meta_set_present", "vdb_meta_compile", "vdb_meta_mask_ptr", "vdb_meta_mask_bits",
     "vdb_meta_mask_count", "vdb_meta_mask_wait_on", "vdb_meta_mask_release", "vdb_flat_search_batch_filtered",
@@ -169,6 +170,11 @@ def lib():
     L.vdb_flat_distinct_stats.argtypes = [vp, u64p]
     L.vdb_flat_distinct_depth.argtypes = [sz, sz, c.c_int]
     L.vdb_flat_distinct_depth.restype = sz
+    L.vdb_flat_search_batch_grouped.argtypes = [vp, fp, sz, sz, szp, sz, u64p, sz, sz, u32p, sz, u64p, fp, szp]
+    L.vdb_flat_search_batch_grouped_filtered.argtypes = [vp, fp, sz, sz, szp, sz, c.POINTER(vp), sz, u32p, sz, u64p, fp, szp]
+    L.vdb_flat_grouped_stats.argtypes = [vp, u64p]
+    L.vdb_flat_debug_group_plan.argtypes = [u32p, sz, u32p, sz, u32p, u32p, sz]
+    L.vdb_flat_debug_group_plan.restype = sz
     L.vdb_last_error.argtypes = [c.c_char_p, sz, szp, szp]
     L.vdb_last_error.restype = None
     L.vdb_hnsw_create.argtypes = [c.c_int, sz, sz, sz, u64, c.c_int, c.POINTER(vp)]

@@ -416,6 +416,32 @@ struct SparseScanParams {
 };
 void launch_sparse_scan(const SparseScanParams& p, hipStream_t s);
 
+// ---------------------------------------------------------------- grouped route (kernels_grouped.hip)
+// One batch, a filter per query: the queries that share an id mask are a group, and every group gets the scan above.
+struct GroupedMask { const uint64_t* words; uint64_t bits; };          // an id mask in the layout of launch_build_rowmask's
+// rowmasks[g][w] = live AND mask_g gathered through row_ids, (n_rows + 31) / 32 words per group; row_ids and the live word are
+// read once for all groups
+void launch_grouped_rowmasks(const uint64_t* row_ids, const uint32_t* livemask, const GroupedMask* masks, uint32_t n_groups, uint32_t n_rows,
+                             uint32_t* rowmasks, hipStream_t s);
+// launch_sparse_count for every group: block_cnt / block_off [n_groups][sparse_list_blocks(n_rows)], totals[g] = E_g
+void launch_grouped_count(const uint32_t* rowmasks, uint32_t n_groups, uint32_t n_rows, uint32_t* block_cnt, uint32_t* block_off,
+                          uint32_t* totals, hipStream_t s);
+// launch_sparse_scatter for every group: glist[g] = {offset, length} of group g's list inside lists[0..lists_cap); length 0 = no list
+void launch_grouped_scatter(const uint32_t* rowmasks, uint32_t n_groups, uint32_t n_rows, const uint32_t* block_off, const uint32_t* glist,
+                            uint32_t* lists, uint32_t lists_cap, hipStream_t s);
+// The scan of one pass over a tile table.  scan: as launch_sparse_scan sees a pass, with elig / n_elig = ALL lists and their total
+// length, qp / qnorm / nq = the permuted queries of the pass, key_stride = the pass's longest list rounded up to SPARSE_TILE_R.
+// tiles[i] = {group, first list position (a multiple of SPARSE_TILE_R), first permuted query (batch-wide: q_base is the pass's
+// first), queries (<= SPARSE_TILE_Q)}.  Key positions of a query past its group's rounded list length are NOT written: the
+// select reads counts.
+struct GroupedScanParams {
+    SparseScanParams scan;
+    const uint32_t* tiles; uint32_t n_tiles;
+    const uint32_t* glist; uint32_t n_groups;
+    uint32_t q_base;
+};
+void launch_grouped_scan(const GroupedScanParams& p, hipStream_t s);
+
 // ---------------------------------------------------------------- metadata filters compiled on the device (kernels_filter.hip)
 // A MetadataFilter as a postfix program over the resident metadata columns (vdb_meta.cpp).  Every leaf carries its
 // column: codes[id] for id < len, -1 ("no such field") at and above len -- such an id reads no memory.

@@ -809,6 +809,147 @@ int vdb_flat_distinct_stats(const vdb_flat_index* ix, uint64_t out[8]) {
     return VDB_OK;
 }
 
+}  // extern "C"
+
+// ---- one batch, a filter per query (no reference counterpart; vdb_search.cpp search_grouped).  The masks come from
+// the host (id_masks: n_masks x words, the referenced ones uploaded here) or are compiled ones already in HBM (cms).
+static int search_grouped_host(vdb_flat_index* ix, const char* what, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k,
+                               const uint64_t* id_masks, const vdb_meta_mask* const* cms, bool compiled, size_t n_masks, size_t mask_bits,
+                               const uint32_t* group_of, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts) {
+    return guarded([&]() -> int {
+    if (!ix || (nq && (!queries || !out_counts))) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (ix->multi) return refuse_multi(what);
+    size_t kmax = k;
+    if (ks) {
+        kmax = 0;
+        for (size_t b = 0; b < nq; ++b) kmax = std::max(kmax, ks[b]);
+    }
+    if (kmax > kstride) return fail(VDB_ERR_INVALID_ARGUMENT, "kstride %zu smaller than the largest k %zu", kstride, kmax);
+    if (kmax && nq && (!out_ids || !out_dists)) return fail(VDB_ERR_INVALID_ARGUMENT, "null output");
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (in_flight(ix)) return refuse_in_flight();
+    memset(ix->grouped_stats, 0, sizeof(ix->grouped_stats));
+    ix->grouped_stats[0] = nq;
+    if (nq == 0) return VDB_OK;
+    const size_t len = ix->n_live + ix->misfits.size();
+    if (len == 0 || kmax == 0) {                                   // storage.rs:218-220: empty store -> Ok(vec![]) before any check
+        for (size_t b = 0; b < nq; ++b) out_counts[b] = 0;
+        return VDB_OK;
+    }
+    // ---- argument errors, before any device work
+    if (!group_of) return fail(VDB_ERR_INVALID_ARGUMENT, "null group_of");
+    for (size_t b = 0; b < nq; ++b)
+        if (group_of[b] != VDB_GROUP_NONE && group_of[b] >= n_masks)
+            return fail(VDB_ERR_INVALID_ARGUMENT, "query %zu names mask %u of %zu", b, group_of[b], n_masks);
+    if (n_masks > 1024) return fail(VDB_ERR_INVALID_ARGUMENT, "%zu masks: a grouped search takes at most 1024", n_masks);
+    if (n_masks && (compiled ? !cms : !id_masks)) return fail(VDB_ERR_INVALID_ARGUMENT, "null mask array");
+    // the referenced masks, in the order of their indices: slot[b] = the query's place among them
+    std::vector<uint32_t> place(n_masks, VDB_GROUP_NONE), ref, slot(nq);
+    for (size_t b = 0; b < nq; ++b)
+        if (group_of[b] != VDB_GROUP_NONE) place[group_of[b]] = 0;
+    for (size_t m = 0; m < n_masks; ++m)
+        if (place[m] == 0) { place[m] = (uint32_t)ref.size(); ref.push_back((uint32_t)m); }
+    for (size_t b = 0; b < nq; ++b) slot[b] = group_of[b] == VDB_GROUP_NONE ? VDB_GROUP_NONE : place[group_of[b]];
+    const size_t R = ref.size();
+    if (compiled)
+        for (uint32_t m : ref) {
+            if (!cms[m]) return fail(VDB_ERR_INVALID_ARGUMENT, "mask %u is null", m);
+            if (cms[m]->device != ix->device)
+                return fail(VDB_ERR_INVALID_ARGUMENT, "the compiled mask lives on device %d, the index on device %d", cms[m]->device, ix->device);
+        }
+    if (nq > 0x3fffffffull) return fail(VDB_ERR_INVALID_ARGUMENT, "batch too large");
+    ix->grouped_stats[1] = R;
+    int rc = set_device(ix);
+    if (rc) return rc;
+    ix->cur = &ix->wsv[0];
+    if ((rc = flush(ix))) return rc;                               // staged adds first
+    const size_t kdev = std::min(kmax, std::max<size_t>(len, 1));  // Index::search returns at most len results
+    hipStream_t s = ix->stream;
+    GroupedWs& G = ix->gws;
+    if ((rc = G.q.ensure(nq * std::max<size_t>(dim, 1))) || (rc = G.oi.ensure(nq * kdev)) || (rc = G.od.ensure(nq * kdev)) || (rc = G.oc.ensure(nq)) ||
+        (rc = G.desc.ensure(std::max<size_t>(R, 1))))
+        return rc;
+    if (dim) HIP_TRY(hipMemcpyAsync(G.q.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
+    std::vector<vdb::GroupedMask> desc(R);
+    if (compiled) {
+        for (size_t r = 0; r < R; ++r) {
+            const vdb_meta_mask* cm = cms[ref[r]];
+            HIP_TRY(hipStreamWaitEvent(s, cm->done, 0));
+            desc[r] = vdb::GroupedMask{cm->d_words, cm->bits};
+        }
+    } else {
+        const size_t words = (mask_bits + 63) / 64;
+        if ((rc = G.masks.ensure(std::max<size_t>(R * words, 1)))) return rc;
+        for (size_t r = 0; r < R; ++r) {
+            if (words) HIP_TRY(hipMemcpyAsync(G.masks.p + r * words, id_masks + (size_t)ref[r] * words, words * 8, hipMemcpyHostToDevice, s));
+            desc[r] = vdb::GroupedMask{G.masks.p + r * words, mask_bits};
+        }
+    }
+    if (R) HIP_TRY(hipMemcpyAsync(G.desc.p, desc.data(), R * sizeof(vdb::GroupedMask), hipMemcpyHostToDevice, s));
+    GroupedArgs a{G.q.p, nq, dim, kdev, slot.data(), G.desc.p, desc.data(), R, G.oi.p, G.od.p, G.oc.p};
+    if ((rc = search_grouped(ix, s, a))) {
+        (void)hipStreamSynchronize(s);                             // (desc and the plan are host vectors of this frame)
+        return rc;
+    }
+    std::vector<uint32_t> cnt(nq);
+    std::vector<uint64_t> ids(nq * kdev);
+    std::vector<float> ds(nq * kdev);
+    HIP_TRY(hipMemcpyAsync(cnt.data(), G.oc.p, nq * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(ids.data(), G.oi.p, nq * kdev * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(ds.data(), G.od.p, nq * kdev * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t b = 0; b < nq; ++b) {
+        const size_t kb = ks ? ks[b] : k;
+        const size_t c = std::min<size_t>(cnt[b], kb);             // per-query k: a prefix of the batch-wide result
+        out_counts[b] = c;
+        for (size_t i = 0; i < c; ++i) { out_ids[b * kstride + i] = ids[b * kdev + i]; out_dists[b * kstride + i] = ds[b * kdev + i]; }
+    }
+    return VDB_OK;
+    });
+}
+
+extern "C" {
+
+int vdb_flat_search_batch_grouped(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k,
+                                  const uint64_t* id_masks, size_t n_masks, size_t mask_bits, const uint32_t* group_of, size_t kstride,
+                                  uint64_t* out_ids, float* out_dists, size_t* out_counts) {
+    return search_grouped_host(ix, "vdb_flat_search_batch_grouped", queries, nq, dim, ks, k, id_masks, nullptr, false, n_masks, mask_bits, group_of,
+                               kstride, out_ids, out_dists, out_counts);
+}
+
+int vdb_flat_search_batch_grouped_filtered(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k,
+                                           const vdb_meta_mask* const* masks, size_t n_masks, const uint32_t* group_of, size_t kstride,
+                                           uint64_t* out_ids, float* out_dists, size_t* out_counts) {
+    return search_grouped_host(ix, "vdb_flat_search_batch_grouped_filtered", queries, nq, dim, ks, k, nullptr, masks, true, n_masks, 0, group_of,
+                               kstride, out_ids, out_dists, out_counts);
+}
+
+int vdb_flat_grouped_stats(const vdb_flat_index* ix, uint64_t out[8]) {
+    return guarded([&]() -> int {
+    if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (ix->multi) return refuse_multi("vdb_flat_grouped_stats");
+    memcpy(out, ix->grouped_stats, sizeof(ix->grouped_stats));
+    return VDB_OK;
+    });
+}
+
+size_t vdb_flat_debug_group_plan(const uint32_t* group_of, size_t nq, const uint32_t* elig, size_t n_masks, uint32_t* perm, uint32_t* tiles,
+                                 size_t cap) {
+    size_t n = 0;
+    (void)guarded([&]() -> int {
+    if ((nq && !group_of) || (n_masks && !elig) || nq > 0x3fffffffull) { n = ~(size_t)0; return VDB_OK; }
+    GroupPlan plan;
+    if (!group_plan(group_of, nq, elig, n_masks, true, &plan)) { n = ~(size_t)0; return VDB_OK; }
+    n = plan.tiles.size();
+    for (size_t i = 0; perm && i < nq; ++i) perm[i] = plan.perm[i];
+    for (size_t i = 0; tiles && i < std::min(n, cap); ++i) {
+        tiles[4 * i] = plan.tiles[i].group; tiles[4 * i + 1] = plan.tiles[i].j0; tiles[4 * i + 2] = plan.tiles[i].q0; tiles[4 * i + 3] = plan.tiles[i].nq;
+    }
+    return VDB_OK;
+    });
+    return n;
+}
+
 int vdb_flat_search(vdb_flat_index* ix, const float* query, size_t dim, size_t k, uint64_t* out_ids,
                     float* out_dists, size_t* out_count) {
     return guarded([&]() -> int {

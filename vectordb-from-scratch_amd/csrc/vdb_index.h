@@ -95,6 +95,16 @@ struct DistinctWs {
     vdbi::DevBuf<uint32_t> lc, kept, complete, sel;               // list counts | rows per answer | completeness flags | the incomplete queries
 };
 
+// What one grouped search owns on the device (vdb_search.cpp search_grouped) beside the search workspace: the
+// caller's queries and masks, the row masks and lists of all groups, the plan, and the results -- permuted as the passes emit
+// them (s*) and in the caller's order (o*).
+struct GroupedWs {
+    vdbi::DevBuf<float> q, q2, sd, od;                            // queries | the gathered block of an ordinary sub-search | distances
+    vdbi::DevBuf<uint64_t> masks, si, oi;                         // host-form masks of the referenced groups, side by side | ids
+    vdbi::DevBuf<vdb::GroupedMask> desc;                          // where each referenced group's mask is and how many bits it has
+    vdbi::DevBuf<uint32_t> rowmask, blk, lists, plan, sel, sc, oc;   // [R][words] | block counts, offsets, totals | lists | perm, key counts, glist, tiles | sub-search queries | counts
+};
+
 // Diagnostic knobs: ablation switches, A/B kernel variants, scaled certificates, sample-size overrides.  Several of them
 // VOID the exact-result guarantee, so they exist only in the diagnostics build (-DVDB_DIAG -> libvdbflat_diag.so,
 // `make diag`), where vdb_flat_create reads them from the environment ONCE into the handle.  In the release library
@@ -180,6 +190,8 @@ struct vdb_flat_index {
     uint64_t by_id_stats[4] = {0};                          // vdb_flat_by_id_stats: counters of the last search by stored id (also on a sharded parent)
     uint64_t distinct_stats[8] = {0};                       // vdb_flat_distinct_stats: counters of the last search by group (also on a sharded parent)
     DistinctWs dws;                                         // its device buffers (a sharded parent's live on devices[0])
+    uint64_t grouped_stats[8] = {0};                        // vdb_flat_grouped_stats: counters of the last grouped search
+    GroupedWs gws;                                          // its device buffers
     uint64_t id_bound = 0;                                  // 1 + the largest id ever added (saturating), raised at add time only: never lowered by a remove
     bool profile = false; vdbi::Event ev0, ev1;
 
@@ -264,6 +276,28 @@ struct DistinctArgs {
 using DistinctSearch = std::function<int(const float* d_q, size_t nq, size_t depth, const uint64_t* d_mask, size_t mask_bits,
                                          uint64_t* d_ids, float* d_dists, uint32_t* d_counts)>;
 int distinct_drive(Index* H, hipStream_t s, const DistinctSearch& search, const DistinctArgs& a);
+
+// One batch, a filter per query (vdb_flat_search_batch_grouped).  The plan is host arithmetic alone: the
+// permutation that makes every group's queries contiguous (scanned groups first, then the groups nothing is eligible for, the
+// groups beyond the scan's capacity, the unfiltered queries), and per pass of SUPER permuted queries the tile table of the scan.
+struct GroupTile { uint32_t group, j0, q0, nq; };                  // 64 list positions from j0 x nq <= 64 permuted queries from q0, ONE group
+struct GroupPass { uint32_t q0, nq, tile0, n_tiles, stride; };     // permuted queries [q0, q0 + nq), tiles [tile0, tile0 + n_tiles), longest list rounded up to 64
+struct GroupPlan {
+    std::vector<uint32_t> perm;                                    // perm[i] = the caller's index of permuted query i
+    std::vector<GroupTile> tiles; std::vector<GroupPass> passes;
+    uint32_t n_scan = 0, n_empty = 0, n_over = 0, n_none = 0;      // queries of each kind, in the order of perm
+};
+// elig[g] = E_g; can_scan = false sends every non-empty group to the ordinary search (k beyond the select).  false: a group index
+// that is neither below n_masks nor VDB_GROUP_NONE
+bool group_plan(const uint32_t* group_of, size_t nq, const uint32_t* elig, size_t n_masks, bool can_scan, GroupPlan* out);
+// Everything below has passed the entry point's checks.  slot[b]: the query's place among the R referenced masks (desc / h_desc:
+// on the device and on the host) or VDB_GROUP_NONE; outputs [nq][k] on the device, complete when it returns.
+struct GroupedArgs {
+    const float* d_q; size_t nq, dim, k;
+    const uint32_t* slot; const vdb::GroupedMask* d_desc; const vdb::GroupedMask* h_desc; size_t n_ref;
+    uint64_t* d_out_ids; float* d_out_dists; uint32_t* d_out_counts;
+};
+int search_grouped(Index* ix, hipStream_t s, const GroupedArgs& a);
 
 // ---- vdb_multi.cpp: one index over several GPUs in one process (the parent handle dispatches here)
 int multi_create(int metric, const int* devices, size_t n, vdb_flat_index** out);

@@ -1328,4 +1328,191 @@ int search_device(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, 
     return rc;
 }
 
+// ---------------------------------------------------------------------------------------------
+// One batch, a filter per query (vdb_flat_search_batch_grouped).  The answer of a query is what the ordinary search
+// returns for it alone under its mask; the queries that share a mask form a group, and the groups whose eligible rows fit get the
+// sparse-filter route's scan in ONE launch chain: row masks of all groups, their counts (one host read: every E_g and the
+// status of query_prep), the plan, all lists, then per pass of SUPER permuted queries one scan over the tile table and one
+// select in EMIT mode, and one scatter back into the caller's order.  Exact by construction, like search_sparse: no certificate.
+// ---------------------------------------------------------------------------------------------
+bool group_plan(const uint32_t* group_of, size_t nq, const uint32_t* elig, size_t n_masks, bool can_scan, GroupPlan* out) {
+    out->perm.clear(); out->tiles.clear(); out->passes.clear();
+    out->n_scan = out->n_empty = out->n_over = out->n_none = 0;
+    // kind of a query: 0 scanned, 1 nothing eligible, 2 beyond the scan's capacity, 3 unfiltered
+    auto kind = [&](uint32_t g) -> int {
+        if (g == VDB_GROUP_NONE) return 3;
+        return elig[g] == 0 ? 1 : (can_scan && elig[g] <= SPARSE_MAX_E) ? 0 : 2;
+    };
+    std::vector<uint32_t> cnt(n_masks + 1, 0);                     // queries per group (the last: unfiltered)
+    for (size_t b = 0; b < nq; ++b) {
+        const uint32_t g = group_of[b];
+        if (g != VDB_GROUP_NONE && g >= n_masks) return false;
+        ++cnt[g == VDB_GROUP_NONE ? n_masks : g];
+    }
+    // a counting sort by (kind, group): stable, so a group's queries keep the caller's order
+    std::vector<uint32_t> start(n_masks + 1, 0);
+    uint32_t at = 0;
+    for (int kd = 0; kd < 4; ++kd)
+        for (size_t g = 0; g <= n_masks; ++g) {
+            if (!cnt[g] || kind(g == n_masks ? VDB_GROUP_NONE : (uint32_t)g) != kd) continue;
+            start[g] = at; at += cnt[g];
+            (kd == 0 ? out->n_scan : kd == 1 ? out->n_empty : kd == 2 ? out->n_over : out->n_none) += cnt[g];
+        }
+    out->perm.resize(nq);
+    std::vector<uint32_t> fill(start);
+    for (size_t b = 0; b < nq; ++b) out->perm[fill[group_of[b] == VDB_GROUP_NONE ? n_masks : group_of[b]]++] = (uint32_t)b;
+    // tiles: the scanned groups in the order of the permutation, cut at the pass boundaries
+    for (uint32_t p0 = 0; p0 < out->n_scan; p0 += SUPER) out->passes.push_back(GroupPass{p0, std::min(SUPER, out->n_scan - p0), 0, 0, 0});
+    for (size_t g = 0; g < n_masks; ++g) {
+        if (!cnt[g] || kind((uint32_t)g) != 0) continue;
+        const uint32_t a = start[g], b = a + cnt[g], E = elig[g];
+        for (uint32_t q = a; q < b;) {
+            GroupPass& P = out->passes[q / SUPER];
+            const uint32_t nqt = std::min(std::min(b, P.q0 + P.nq) - q, vdb::SPARSE_TILE_Q);
+            if (!P.n_tiles) P.tile0 = (uint32_t)out->tiles.size();
+            for (uint32_t j0 = 0; j0 < E; j0 += vdb::SPARSE_TILE_R) out->tiles.push_back(GroupTile{(uint32_t)g, j0, q, nqt});
+            P.n_tiles = (uint32_t)out->tiles.size() - P.tile0;
+            P.stride = std::max(P.stride, round_up(E, vdb::SPARSE_TILE_R));
+            q += nqt;
+        }
+    }
+    return true;
+}
+
+// an ordinary search of the queries `idx` (caller's indices) under one mask or none, its results put into their places
+static int grouped_ordinary(Index* ix, hipStream_t s, const GroupedArgs& a, const std::vector<uint32_t>& idx, const vdb::GroupedMask* mask) {
+    int rc;
+    GroupedWs& G = ix->gws;
+    const size_t m = idx.size(), k = a.k;
+    if (!m) return VDB_OK;
+    if ((rc = G.sel.ensure(m)) || (rc = G.q2.ensure(m * std::max<size_t>(a.dim, 1))) || (rc = G.si.ensure(m * k)) || (rc = G.sd.ensure(m * k)) ||
+        (rc = G.sc.ensure(m)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(G.sel.p, idx.data(), m * 4, hipMemcpyHostToDevice, s));
+    vdb::launch_gather_rows(a.d_q, (uint32_t)a.dim, (uint32_t)a.dim, (uint32_t)a.nq, G.sel.p, (uint32_t)m, G.q2.p, s);
+    HIP_TRY(hipGetLastError());
+    if ((rc = search_device(ix, G.q2.p, m, a.dim, k, mask ? mask->words : nullptr, mask ? (size_t)mask->bits : 0, G.si.p, G.sd.p, G.sc.p, nullptr)))
+        return rc;
+    vdb::launch_scatter_results(G.si.p, G.sd.p, G.sc.p, G.sel.p, (uint32_t)m, (uint32_t)k, a.d_out_ids, a.d_out_dists, a.d_out_counts, s);
+    HIP_TRY(hipGetLastError());
+    return VDB_OK;
+}
+
+int search_grouped(Index* ix, hipStream_t s, const GroupedArgs& a) {
+    int rc;
+    GroupedWs& G = ix->gws;
+    uint64_t* st = ix->grouped_stats;
+    const size_t nq = a.nq, k = a.k, R = a.n_ref;
+    const uint32_t nq32 = (uint32_t)nq;
+    // the checks of a search, in its order (search_part1): dimension, a live zero-norm row under Cosine
+    if ((rc = query_dim_check(ix, a.dim))) return rc;
+    if (ix->metric == vdb::COSINE) {
+        if ((rc = ensure_zero_count(ix))) return rc;
+        if (ix->zero_live) return fail_zero_vector();
+    }
+    if (ix->dim > 16384) return fail(VDB_ERR_INVALID_ARGUMENT, "dimension %u exceeds the supported 16384", ix->dim);
+    ix->cur = &ix->wsv[0];
+    Workspace* W = ix->cur;
+    const uint32_t n = ix->n_uploaded, ld = ix->ld, bp_all = round_up(nq32, SUPER);
+    const uint32_t n_words = (n + 31) / 32, nb = vdb::sparse_list_blocks(n);
+
+    // ---- row masks and counts of all referenced groups; the queries prepared (the whole batch: a zero-norm query anywhere fails
+    // the call before any distance is looked at)
+    HIP_TRY(hipMemsetAsync(a.d_out_counts, 0, nq * 4, s));
+    if ((rc = W->w_qp.ensure((size_t)bp_all * ld)) || (rc = W->w_qnorm.ensure(bp_all)) || (rc = W->w_thr.ensure(bp_all)) ||
+        (rc = W->w_flags.ensure(4 + 3 * (size_t)nq32)))
+        return rc;
+    uint32_t* d_status = W->w_flags.p;
+    HIP_TRY(hipMemsetAsync(d_status, 0, 16, s));
+    W->status_dirty = true;                                        // (the tiers' bookkeeping: the block is cleared again before its next use)
+    vdb::QueryPrepParams qp{a.d_q, (uint32_t)a.dim, nq32, W->w_qp.p, ld, bp_all, W->w_qnorm.p, W->w_thr.p, ix->metric, d_status,
+                            nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr};
+    vdb::launch_query_prep(qp, s);
+    uint32_t* d_blk = nullptr;                                     // [R][nb] counts | [R][nb] offsets | [R] totals
+    if (R) {
+        if ((rc = G.rowmask.ensure(R * std::max<size_t>(n_words, 1))) || (rc = G.blk.ensure(2 * R * (size_t)nb + R))) return rc;
+        d_blk = G.blk.p;
+        vdb::launch_grouped_rowmasks(ix->d_row_ids, (ix->n_live == n) ? nullptr : ix->d_live, a.d_desc, (uint32_t)R, n, G.rowmask.p, s);
+        vdb::launch_grouped_count(G.rowmask.p, (uint32_t)R, n, d_blk, d_blk + R * (size_t)nb, d_blk + 2 * R * (size_t)nb, s);
+    }
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> elig(R + 4, 0);                          // E of every referenced group | the status block
+    if (R) HIP_TRY(hipMemcpyAsync(elig.data(), d_blk + 2 * R * (size_t)nb, R * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(elig.data() + R, d_status, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (elig[R] & vdb::ST_ZERO_QUERY) return fail_zero_vector();
+    for (size_t g = 0; g < R; ++g)
+        if (elig[g] > n) return fail(VDB_ERR_DEVICE, "eligible-row count %u exceeds the %u rows of the store", elig[g], n);
+
+    // ---- the plan
+    GroupPlan plan;
+    if (!group_plan(a.slot, nq, elig.data(), R, k <= MAX_SELECT, &plan)) return fail(VDB_ERR_DEVICE, "internal error: a query's group is not among the referenced masks");
+    st[2] = plan.n_scan; st[3] = plan.n_over; st[4] = plan.n_none; st[6] = plan.tiles.size(); st[7] = plan.passes.size();
+
+    if (plan.n_scan) {
+        // one block for the device: permutation | key count per permuted query | {list offset, length} per group | tiles
+        const uint32_t ns = plan.n_scan, nt = (uint32_t)plan.tiles.size();
+        std::vector<uint32_t> hp((size_t)2 * ns + 2 * R + 4 * (size_t)nt, 0);
+        uint32_t* h_kcnt = hp.data() + ns; uint32_t* h_glist = h_kcnt + ns; uint32_t* h_tiles = h_glist + 2 * R;
+        uint64_t lists_len = 0;
+        for (uint32_t i = 0; i < ns; ++i) { hp[i] = plan.perm[i]; h_kcnt[i] = round_up(elig[a.slot[plan.perm[i]]], vdb::SPARSE_TILE_R); }
+        for (uint32_t i = 0; i < ns;) {                             // (group by group: the scanned queries are sorted by group)
+            const uint32_t g = a.slot[plan.perm[i]];
+            h_glist[2 * g] = (uint32_t)lists_len; h_glist[2 * g + 1] = elig[g];
+            lists_len += elig[g]; st[5] += elig[g];
+            while (i < ns && a.slot[plan.perm[i]] == g) ++i;
+        }
+        if (lists_len > 0xfffffff0ull) return fail(VDB_ERR_INVALID_ARGUMENT, "the eligible-row lists of the batch hold %llu rows: too many for one call", (unsigned long long)lists_len);
+        memcpy(h_tiles, plan.tiles.data(), (size_t)nt * 16);
+        size_t key_rows = 0;
+        for (const GroupPass& P : plan.passes) key_rows = std::max(key_rows, (size_t)P.nq * P.stride);
+        if ((rc = ensure_ranks(ix))) return rc;
+        if ((rc = G.plan.ensure(hp.size())) || (rc = G.lists.ensure(lists_len)) || (rc = W->w2_qp.ensure((size_t)ns * ld)) ||
+            (rc = W->w2_qnorm.ensure(ns)) || (rc = W->w2_thr.ensure(ns)) || (rc = G.si.ensure((size_t)ns * k)) || (rc = G.sd.ensure((size_t)ns * k)) ||
+            (rc = G.sc.ensure(ns)) || (rc = W->w_exact.ensure(key_rows)) || (rc = W->w_exsel.ensure((size_t)SUPER * MAX_SELECT + 8)) ||
+            (rc = W->w_cnt.ensure(4 * SUPER + 16)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(G.plan.p, hp.data(), hp.size() * 4, hipMemcpyHostToDevice, s));
+        const uint32_t* d_perm = G.plan.p; const uint32_t* d_kcnt = d_perm + ns; const uint32_t* d_glist = d_kcnt + ns;
+        const uint32_t* d_tiles = d_glist + 2 * R;
+        vdb::launch_grouped_scatter(G.rowmask.p, (uint32_t)R, n, d_blk + R * (size_t)nb, d_glist, G.lists.p, (uint32_t)lists_len, s);
+        vdb::launch_gather_queries(W->w_qp.p, W->w_qnorm.p, ld, d_perm, ns, ns, W->w2_qp.p, W->w2_qnorm.p, W->w2_thr.p, s);
+        for (const GroupPass& P : plan.passes) {
+            vdb::GroupedScanParams gp{};
+            gp.scan = vdb::SparseScanParams{ix->d_rows, ld, ix->dim, n, G.lists.p, (uint32_t)lists_len, W->w2_qp.p + (size_t)P.q0 * ld,
+                                            W->w2_qnorm.p + P.q0, P.nq, ix->d_nd, ix->ids_monotone ? nullptr : ix->d_idrank.p, ix->metric,
+                                            W->w_exact.p, P.stride, d_status};
+            gp.tiles = d_tiles + 4 * (size_t)P.tile0; gp.n_tiles = P.n_tiles; gp.glist = d_glist; gp.n_groups = (uint32_t)R; gp.q_base = P.q0;
+            vdb::launch_grouped_scan(gp, s);
+            vdb::SelectParams mp{};
+            mp.keys = W->w_exact.p; mp.stride = P.stride; mp.counts = d_kcnt + P.q0; mp.n_fixed = P.stride; mp.cap = P.stride;
+            mp.kk = (uint32_t)k; mp.out_keys = W->w_exsel.p; mp.out_stride = MAX_SELECT; mp.out_cnt = W->w_cnt.p;
+            mp.emit_ids = G.si.p + (size_t)P.q0 * k; mp.emit_dists = G.sd.p + (size_t)P.q0 * k; mp.emit_counts = G.sc.p + P.q0;
+            mp.emit_stride = (uint32_t)k;
+            mp.emit_rank2row = ix->ids_monotone ? nullptr : ix->d_rank2row.p; mp.emit_row_ids = ix->d_row_ids;
+            vdb::launch_select(mp, P.nq, s);
+        }
+        vdb::launch_scatter_results(G.si.p, G.sd.p, G.sc.p, d_perm, ns, (uint32_t)k, a.d_out_ids, a.d_out_dists, a.d_out_counts, s);
+        HIP_TRY(hipGetLastError());
+        uint32_t st4[4] = {0, 0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(st4, d_status, 16, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (st4[0] & vdb::ST_NAN) return fail_nan();
+    }
+
+    // ---- the queries not on the route, by the existing code: one ordinary masked search per group beyond the scan's capacity,
+    // one unmasked search for all unfiltered queries
+    std::vector<uint32_t> idx;
+    for (uint32_t i = plan.n_scan + plan.n_empty; i < plan.n_scan + plan.n_empty + plan.n_over;) {
+        const uint32_t g = a.slot[plan.perm[i]];
+        idx.clear();
+        for (; i < plan.n_scan + plan.n_empty + plan.n_over && a.slot[plan.perm[i]] == g; ++i) idx.push_back(plan.perm[i]);
+        if ((rc = grouped_ordinary(ix, s, a, idx, &a.h_desc[g]))) return rc;
+    }
+    idx.assign(plan.perm.begin() + (nq - plan.n_none), plan.perm.end());
+    if ((rc = grouped_ordinary(ix, s, a, idx, nullptr))) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return VDB_OK;
+}
+
 }  // namespace vdbi

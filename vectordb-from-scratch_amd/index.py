@@ -164,10 +164,14 @@ class MetaTable:
         return CompiledMask(self, m)
 
 
+GROUP_NONE = 0xFFFFFFFF                              # search_batch_grouped: this query is searched without a filter
+
+
 class GpuFlatIndex(Index):
     """Drop-in for FlatIndex (src/flat_index.rs) backed by the MI355X engine."""
 
     EXCHANGE_RCCL, EXCHANGE_PEER = 0, 1
+    GROUP_NONE = GROUP_NONE                              # search_batch_grouped: this query is searched without a filter
 
     def __init__(self, metric, device=0, keep_host_copy=True, devices=None):
         """devices=[d0, d1, ...]: ONE index whose rows are sharded over these GPUs inside this process
@@ -385,6 +389,86 @@ class GpuFlatIndex(Index):
     def distinct_depth(k, length, stage):
         """Rows per query the stage-A (0) / stage-B (1) search of search_batch_distinct asks for; needs no device."""
         return int(_ffi.lib().vdb_flat_distinct_depth(int(k), int(length), int(stage)))
+
+    # ---- one batch, a filter per query (include/vdb_flat.h vdb_flat_search_batch_grouped; no reference counterpart)
+    def search_batch_grouped(self, queries, k, group_of, id_masks=None, mask_bits=0, compiled_masks=None, ks=None):
+        """One batch, a filter per query: the answer for query b is what search_batch_arrays returns for that query alone under
+        mask group_of[b] (GROUP_NONE: under no mask) -- ids, order, distance bits and count.  group_of: one mask index per query.
+        id_masks: u64 array [n_masks, (mask_bits + 63) // 64]; or compiled_masks: a sequence of CompiledMask (entries no query
+        references may be None).  ks: a per-query k (k is then ignored).  The queries that share a mask are answered together, all
+        groups in one launch chain.  Returns the arrays of search_batch_arrays."""
+        if compiled_masks is not None and id_masks is not None:
+            raise ValueError("pass id_masks or compiled_masks, not both")
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError("queries must be a 2-d array")
+        nq, dim = q.shape
+        if ks is None:
+            ks_ptr, kscalar, kmax = None, int(k), int(k)
+        else:
+            ks = np.ascontiguousarray(ks, dtype=np.uintp)
+            if ks.shape != (nq,):
+                raise ValueError(f"ks must hold one value per query ({nq}), not {ks.shape}")
+            ks_ptr = ks.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t))
+            kscalar, kmax = 0, int(ks.max()) if ks.size else 0
+        gp = None
+        if group_of is not None:
+            go = np.ascontiguousarray(group_of, dtype=np.uint32).reshape(-1)
+            if go.shape != (nq,):
+                raise ValueError(f"group_of must hold one value per query ({nq}), not {go.shape}")
+            gp = go.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+        kstride = max(kmax, 1)
+        out_ids = np.zeros((nq, kstride), dtype=np.uint64)
+        out_d = np.zeros((nq, kstride), dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uintp)
+        cp = counts.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t))
+        if compiled_masks is not None:
+            n_masks = len(compiled_masks)
+            arr = (ctypes.c_void_p * max(n_masks, 1))(*[m.handle if m is not None else None for m in compiled_masks])
+            rc = self._L.vdb_flat_search_batch_grouped_filtered(self._h, _fp(q), nq, dim, ks_ptr, kscalar, arr if n_masks else None, n_masks,
+                                                                gp, kstride, _u64p(out_ids), _fp(out_d), cp)
+        else:
+            mask_ptr, n_masks = None, 0
+            if id_masks is not None:
+                m = np.ascontiguousarray(id_masks, dtype=np.uint64)
+                words = (int(mask_bits) + 63) // 64
+                if m.ndim != 2 or m.shape[1] != words:
+                    raise ValueError(f"id_masks must be [n_masks, {words}] for {mask_bits} bits, not {m.shape}")
+                n_masks = m.shape[0]
+                mask_ptr = _u64p(m) if m.size else None
+            rc = self._L.vdb_flat_search_batch_grouped(self._h, _fp(q), nq, dim, ks_ptr, kscalar, mask_ptr, n_masks, int(mask_bits), gp,
+                                                       kstride, _u64p(out_ids), _fp(out_d), cp)
+        if rc:
+            _raise(rc)
+        return out_ids, out_d, counts
+
+    def grouped_stats(self):
+        """The last search_batch_grouped: [0] queries, [1] masks referenced, [2] queries answered by the grouped scan, [3] by a
+        per-group ordinary search, [4] unfiltered queries, [5] eligible rows summed over the scanned groups, [6] tiles launched,
+        [7] passes."""
+        out = (ctypes.c_uint64 * 8)()
+        rc = self._L.vdb_flat_grouped_stats(self._h, out)
+        if rc:
+            _raise(rc)
+        return [int(x) for x in out]
+
+    @staticmethod
+    def debug_group_plan(group_of, elig):
+        """The plan of a grouped search for these group indices and eligible-row counts (k <= 2048); needs no device.
+        Returns (perm u32 [nq], tiles u32 [n_tiles, 4] = group, first list position, first permuted query, queries), or None
+        for a group index that is neither below len(elig) nor GROUP_NONE."""
+        go = np.ascontiguousarray(group_of, dtype=np.uint32).reshape(-1)
+        el = np.ascontiguousarray(elig, dtype=np.uint32).reshape(-1)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        L = _ffi.lib()
+        gp, ep = go.ctypes.data_as(u32p) if go.size else None, el.ctypes.data_as(u32p) if el.size else None
+        n = L.vdb_flat_debug_group_plan(gp, go.size, ep, el.size, None, None, 0)
+        if n == ctypes.c_size_t(-1).value:
+            return None
+        perm = np.zeros(go.size, dtype=np.uint32)
+        tiles = np.zeros((n, 4), dtype=np.uint32)
+        L.vdb_flat_debug_group_plan(gp, go.size, ep, el.size, perm.ctypes.data_as(u32p), tiles.ctypes.data_as(u32p), n)
+        return perm, tiles
 
     # ---- bulk build and device-resident entry points
     def add_bulk(self, rows, ids=None, first_id=0):

@@ -8,7 +8,7 @@ import numpy as np
 
 from .error import DimensionMismatch, VectorNotFound
 from .hnsw import GpuHnswIndex
-from .index import GpuFlatIndex, Index, MetaTable
+from .index import GROUP_NONE, GpuFlatIndex, Index, MetaTable
 from .vector import DistanceMetric, Vector
 
 
@@ -626,3 +626,78 @@ class VectorStore:
                 cm.release()
         mask, bits = self.compile_filter(flt)
         return [self._map(r) for r in self._index.search_batch(list(queries), id_mask=mask, mask_bits=bits)]
+
+    # ---- one batch, a filter per query (GpuFlatIndex.search_batch_grouped; no reference counterpart)
+    @staticmethod
+    def _filter_key(flt):
+        """A hashable key equal for structurally equal filters (same ops, fields, values, order of children)."""
+        done = []                                                  # keys of finished subtrees, a stack
+        todo = [("visit", flt)]
+        while todo:
+            what, f = todo.pop()
+            if what == "visit" and f.op in ("and", "or"):
+                todo.append(("fold", f))
+                todo.extend(("visit", g) for g in reversed(f.filters))
+            elif what == "visit":
+                v = f.value
+                try:
+                    hash(v)
+                except TypeError:
+                    v = repr(v)
+                done.append((f.op, f.field, type(v).__name__, v))
+            else:
+                n = len(f.filters)
+                kids = tuple(done[len(done) - n:]) if n else ()
+                del done[len(done) - n:]
+                done.append((f.op, kids))
+        return done[0]
+
+    def search_batch_with_filters(self, queries, filters):
+        """search_batch_prefiltered with a filter PER QUERY: queries holds (Vector, k) pairs, filters[i] is the MetadataFilter of
+        query i or None (no filter).  Structurally equal filters share one mask; all queries go to the device as ONE batch
+        (GpuFlatIndex.search_batch_grouped).  The masks are compiled on the device when the device table is on and every
+        program fits its limits, else by compile_filter.  Results equal search_batch_prefiltered([q], f) query by query."""
+        if not isinstance(self._index, GpuFlatIndex):
+            raise ValueError("search_batch_with_filters needs a GpuFlatIndex")
+        queries, filters = list(queries), list(filters)
+        if len(filters) != len(queries):
+            raise ValueError(f"{len(queries)} queries but {len(filters)} filters")
+        if self.is_empty() or not queries:
+            return [[] for _ in queries]
+        for q, _ in queries:
+            self._check_dim(q)
+        group_of, distinct, seen = [], [], {}
+        for f in filters:
+            if f is None:
+                group_of.append(GROUP_NONE)
+                continue
+            key = self._filter_key(f)
+            if key not in seen:
+                seen[key] = len(distinct)
+                distinct.append(f)
+            group_of.append(seen[key])
+        qs = np.stack([q.data for q, _ in queries]).astype(np.float32, copy=False)
+        ks = np.array([int(k) for _, k in queries], dtype=np.uintp)
+        go = np.asarray(group_of, dtype=np.uint32)
+        compiled = []
+        try:
+            if self._table is not None:
+                for f in distinct:
+                    cm = self.compile_filter_device(f)
+                    if cm is None:                                 # one program beyond the limits: every mask from the host
+                        break
+                    compiled.append(cm)
+            if distinct and len(compiled) == len(distinct):
+                ids, dists, counts = self._index.search_batch_grouped(qs, 0, go, compiled_masks=compiled, ks=ks)
+            elif not distinct:
+                ids, dists, counts = self._index.search_batch_grouped(qs, 0, go, ks=ks)
+            else:
+                bits = max(self._next_id, 1)
+                masks = np.zeros((len(distinct), (bits + 63) // 64), dtype=np.uint64)
+                for i, f in enumerate(distinct):
+                    masks[i] = self.compile_filter(f)[0]
+                ids, dists, counts = self._index.search_batch_grouped(qs, 0, go, id_masks=masks, mask_bits=bits, ks=ks)
+        finally:
+            for cm in compiled:
+                cm.release()
+        return [self._map([(int(ids[b, i]), dists[b, i]) for i in range(int(counts[b]))]) for b in range(len(queries))]
