@@ -416,6 +416,23 @@ int vdb_flat_range_stats(const vdb_flat_index *h, uint64_t out[8]);
  * clear; mask_bits == 0 writes nothing) and counts the set bits.  *out is a mask from a pool inside the table (no allocation per
  * request after warm-up) with an event marking its completion.  A read: may be called from several threads at once.
  *
+ * NUMERIC LEAVES (no reference counterpart: the reference's filter has Eq / Ne / Exists / And / Or only, src/storage.rs:45-58).
+ * LT / LE / GT / GE compare the NUMBER of the row's string with a binary64 constant.  A string is numeric iff all of it matches
+ * [+-]?([0-9]+(\.[0-9]*)?|\.[0-9]+)([eE][+-]?[0-9]+)? in ASCII and its correctly rounded binary64 value is finite; that value is
+ * its number (so integers above 2^53 compare by their roundings).  Values stay strings and rows gain no storage: the number of a
+ * row is a lookup by its dictionary code.  vdb_meta_set_numbers writes that table for column `slot`: values[i] is the number of
+ * code first_code + i, NaN = "no number".  A WRITE like vdb_meta_set_codes: staged, uploaded as a dirty range in front of the
+ * next compile; the table grows independently of the codes, a new tail reads as NaN, n = 0 is allowed, first_code + n above 2^31
+ * is VDB_ERR_INVALID_ARGUMENT.  A slot without a table has one of length 0.  It does not make a slot known.
+ * vdb_meta_compile_num is vdb_meta_compile with constants: for LT / LE / GT / GE, `slot` is the column (it must be known, as for
+ * EQ) and `code` an index into consts.  The leaf is true iff the row's code c satisfies 0 <= c < the table's length and
+ * table[c] OP consts[code] holds as an IEEE comparison (-0 == +0; a NaN entry fails all four; the constant may be +-inf).  A row
+ * without the field, with a non-numeric string, or whose code lies outside the table matches none of the four -- whatever int32
+ * the column holds, no memory outside the table is read.  n_consts > 1024, a constant index at or beyond n_consts, a NaN
+ * constant and a null consts with n_consts > 0 are VDB_ERR_INVALID_ARGUMENT before any device work; everything else (limits,
+ * pool, event, count, locking) is vdb_meta_compile's, which is this call with n_consts = 0 and therefore refuses a numeric op.
+ * Opcodes 6..15 are unknown.
+ *
  * vdb_meta_mask_ptr: the device pointer, for the d_id_mask of vdb_flat_search_batch_device / _begin / _submit, once the
  * caller's stream is ordered behind the mask with vdb_meta_mask_wait_on (hipStreamWaitEvent, no host wait; stream NULL = the
  * null stream).  vdb_meta_mask_bits: its mask_bits.  vdb_meta_mask_count: waits for the event, reads the number of set bits
@@ -432,13 +449,17 @@ typedef struct vdb_meta_table vdb_meta_table;
 #define VDB_META_MASK_DECLARED
 typedef struct vdb_meta_mask vdb_meta_mask;
 #endif
-enum { VDB_META_EQ = 0, VDB_META_NE = 1, VDB_META_EXISTS = 2, VDB_META_CONST = 3, VDB_META_AND = 4, VDB_META_OR = 5 };
-typedef struct vdb_meta_op { uint32_t op; uint32_t slot; int32_t code; } vdb_meta_op; /* CONST: code = 0 | 1; AND / OR: both unused */
+enum { VDB_META_EQ = 0, VDB_META_NE = 1, VDB_META_EXISTS = 2, VDB_META_CONST = 3, VDB_META_AND = 4, VDB_META_OR = 5,
+       VDB_META_LT = 16, VDB_META_LE = 17, VDB_META_GT = 18, VDB_META_GE = 19 };
+typedef struct vdb_meta_op { uint32_t op; uint32_t slot; int32_t code; } vdb_meta_op; /* CONST: code = 0 | 1; AND / OR: both unused; LT..GE: code = constant index */
 int vdb_meta_create(int device, vdb_meta_table **out);
 void vdb_meta_destroy(vdb_meta_table *t);
 int vdb_meta_set_codes(vdb_meta_table *t, uint32_t slot, uint64_t first_id, const int32_t *codes, size_t n);
 int vdb_meta_set_present(vdb_meta_table *t, uint64_t first_id, size_t n, int on);
+int vdb_meta_set_numbers(vdb_meta_table *t, uint32_t slot, uint32_t first_code, const double *values, size_t n);
 int vdb_meta_compile(vdb_meta_table *t, const vdb_meta_op *ops, size_t n_ops, size_t mask_bits, vdb_meta_mask **out);
+int vdb_meta_compile_num(vdb_meta_table *t, const vdb_meta_op *ops, size_t n_ops, const double *consts, size_t n_consts, size_t mask_bits,
+                         vdb_meta_mask **out);
 const uint64_t *vdb_meta_mask_ptr(const vdb_meta_mask *m);
 size_t vdb_meta_mask_bits(const vdb_meta_mask *m);
 int vdb_meta_mask_count(vdb_meta_mask *m, uint64_t *eligible);

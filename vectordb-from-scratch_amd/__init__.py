@@ -11,9 +11,9 @@ from .error import (DimensionMismatch, IndexError_, InvalidVector, NanDistance, 
                     VectorNotFound)
 from .index import CompiledMask, GpuFlatIndex, Index, MetaTable
 from .hnsw import GpuHnswIndex, HnswParams
-from .storage import BatchInsertItem, Metadata, MetadataFilter, SearchResult, VectorStore
+from .storage import BatchInsertItem, Metadata, MetadataFilter, SearchResult, VectorStore, num
 from .vector import DistanceMetric, Vector
 
 __all__ = ["build", "GpuFlatIndex", "MetaTable", "CompiledMask", "GpuHnswIndex", "HnswParams", "Index", "VectorStore", "Vector", "DistanceMetric", "Metadata",
-           "MetadataFilter", "SearchResult", "BatchInsertItem", "VectorDbError", "DimensionMismatch",
+           "MetadataFilter", "num", "SearchResult", "BatchInsertItem", "VectorDbError", "DimensionMismatch",
            "InvalidVector", "VectorNotFound", "IndexError_", "NanDistance"]

@@ -21,7 +21,7 @@ SYMBOLS = [
     "vdb_flat_search_batch_distinct", "vdb_flat_search_batch_distinct_filtered", "vdb_flat_distinct_stats", "vdb_flat_distinct_depth",
     "vdb_flat_search_batch_grouped", "vdb_flat_search_batch_grouped_filtered", "vdb_flat_grouped_stats", "vdb_flat_debug_group_plan",
     "vdb_flat_set_sparse_filter", "vdb_flat_sparse_stats", "vdb_flat_sparse_limit", "vdb_flat_debug_eligible_rows", "vdb_flat_debug_sparse_tile_rows", "vdb_flat_debug_sparse_tile_queries",
-    "vdb_meta_create", "vdb_meta_destroy", "vdb_meta_set_codes", "vdb_meta_set_present", "vdb_meta_compile", "vdb_meta_mask_ptr", "vdb_meta_mask_bits",
+    "vdb_meta_create", "vdb_meta_destroy", "vdb_meta_set_codes", "vdb_meta_set_present", "vdb_meta_set_numbers", "vdb_meta_compile", "vdb_meta_compile_num", "vdb_meta_mask_ptr", "vdb_meta_mask_bits",
     "vdb_meta_mask_count", "vdb_meta_mask_wait_on", "vdb_meta_mask_release", "vdb_flat_search_batch_filtered",
     "vdb_abi_version", "vdb_build_arch",
     # include/vdb_hnsw.h
@@ -152,7 +152,9 @@ def lib():
     L.vdb_meta_destroy.restype = None
     L.vdb_meta_set_codes.argtypes = [vp, c.c_uint32, u64, c.POINTER(c.c_int32), sz]
     L.vdb_meta_set_present.argtypes = [vp, u64, sz, c.c_int]
+    L.vdb_meta_set_numbers.argtypes = [vp, c.c_uint32, c.c_uint32, c.POINTER(c.c_double), sz]
     L.vdb_meta_compile.argtypes = [vp, c.POINTER(MetaOp), sz, sz, c.POINTER(vp)]
+    L.vdb_meta_compile_num.argtypes = [vp, c.POINTER(MetaOp), sz, c.POINTER(c.c_double), sz, sz, c.POINTER(vp)]
     L.vdb_meta_mask_ptr.argtypes = [vp]
     L.vdb_meta_mask_ptr.restype = vp
     L.vdb_meta_mask_bits.argtypes = [vp]

@@ -445,11 +445,16 @@ void launch_grouped_scan(const GroupedScanParams& p, hipStream_t s);
 // ---------------------------------------------------------------- metadata filters compiled on the device (kernels_filter.hip)
 // A MetadataFilter as a postfix program over the resident metadata columns (vdb_meta.cpp).  Every leaf carries its
 // column: codes[id] for id < len, -1 ("no such field") at and above len -- such an id reads no memory.
-enum : uint32_t { FOP_EQ = 0, FOP_NE = 1, FOP_EXISTS = 2, FOP_CONST = 3, FOP_AND = 4, FOP_OR = 5 };
+// A numeric leaf (FOP_LT .. FOP_GE) compares the NUMBER of the row's string with a constant: v = lut[codes[id]], the column's
+// f64 table by dictionary code; a code that is negative or at / beyond lut_len, and a NaN entry, mean "no number" and match
+// nothing.  Its lut, lut_len and constant live in a second array, nums[op.code], so that FilterOp stays 24 bytes.
+enum : uint32_t { FOP_EQ = 0, FOP_NE = 1, FOP_EXISTS = 2, FOP_CONST = 3, FOP_AND = 4, FOP_OR = 5, FOP_LT = 16, FOP_LE = 17, FOP_GT = 18, FOP_GE = 19 };
 constexpr uint32_t FILTER_MAX_OPS = 1024, FILTER_MAX_DEPTH = 32;   // the evaluation stack is the bits of one 32-bit register
-struct FilterOp { const int32_t* codes; uint64_t len; uint32_t op; int32_t code; };   // FOP_CONST: code = 0 | 1
+struct FilterOp { const int32_t* codes; uint64_t len; uint32_t op; int32_t code; };   // FOP_CONST: code = 0 | 1; numeric: code = index into nums
+struct FilterNum { const double* lut; uint64_t lut_len; double c; };                  // c is never NaN (the host checked)
 struct FilterParams {
     const FilterOp* ops; uint32_t n_ops;               // device memory; well-formed, n_ops <= FILTER_MAX_OPS, depth <= FILTER_MAX_DEPTH (the host checked)
+    uint32_t n_nums; const FilterNum* nums;            // device memory; one per numeric leaf, n_nums <= n_ops; every numeric op's code < n_nums
     const uint64_t* present; uint64_t present_words;   // presence bitmap by id; words at and above present_words read as 0
     uint64_t mask_bits;                                // ids at and above contribute 0
     uint64_t* mask;                                    // out: (mask_bits + 63) / 64 words, every one written

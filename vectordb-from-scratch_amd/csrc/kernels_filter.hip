@@ -10,18 +10,27 @@
 //     id < mask_bits; every other lane sees -1 without touching memory;
 //   - the workgroups stride over the words; no workgroup waits for another.  The eligible count is one atomic add per workgroup.
 // Leaf semantics are MetadataFilter::matches' (storage.rs:60-71): Eq code == c, Ne code != c (a row without the field
-// matches), Exists code >= 0.
+// matches), Exists code >= 0.  A numeric leaf (Lt / Le / Gt / Ge) reads the same code and then the column's f64
+// table: v = lut[c] only when 0 <= c < lut_len -- a column may hold ANY int32, so this check stands in front of every lut
+// access -- else NaN; the verdict is the plain IEEE comparison with the leaf's constant, which NaN fails four times out of
+// four.  A numeric leaf's lut, length and constant sit in a second LDS array behind the ops (nums[op.code]), so a program
+// without one keeps its 24 bytes of LDS per op.
 // gfx950 only.
 #include "kernels.h"
 
 namespace vdb {
+
+static_assert(sizeof(FilterOp) == 24 && sizeof(FilterNum) == 24 && FILTER_MAX_OPS * (sizeof(FilterOp) + sizeof(FilterNum)) <= 64 * 1024,
+              "the longest program, all numeric leaves, fits the default dynamic LDS of a launch");
 
 constexpr uint32_t FLT_THREADS = 256, FLT_WAVES = FLT_THREADS / 64;
 
 __global__ __launch_bounds__(FLT_THREADS) void filter_compile_kernel(FilterParams p, uint64_t n_words) {
     extern __shared__ FilterOp sOps[];
     __shared__ uint32_t sCnt[FLT_WAVES];
+    FilterNum* sNums = reinterpret_cast<FilterNum*>(sOps + p.n_ops);       // (both records are 24 bytes, 8-byte aligned)
     for (uint32_t i = threadIdx.x; i < p.n_ops; i += FLT_THREADS) sOps[i] = p.ops[i];
+    for (uint32_t i = threadIdx.x; i < p.n_nums; i += FLT_THREADS) sNums[i] = p.nums[i];
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint32_t found = 0;                                                    // set bits of this wave's words (the same in every lane)
@@ -40,8 +49,16 @@ __global__ __launch_bounds__(FLT_THREADS) void filter_compile_kernel(FilterParam
                 st = (st << 1) | (op.code ? 1u : 0u);
             } else if (op.op == FOP_AND) {
                 st = (st >> 1) & (st | ~1u);
-            } else {
+            } else if (op.op == FOP_OR) {
                 st = (st >> 1) | (st & 1u);
+            } else {                                                       // FOP_LT .. FOP_GE
+                const FilterNum x = sNums[op.code];                        // uniform address again
+                int32_t c = -1;
+                if (in_range && id < op.len) c = op.codes[id];
+                double v = __builtin_nan("");
+                if (c >= 0 && (uint64_t)(uint32_t)c < x.lut_len) v = x.lut[c];
+                const bool r = op.op == FOP_LT ? v < x.c : (op.op == FOP_LE ? v <= x.c : (op.op == FOP_GT ? v > x.c : v >= x.c));
+                st = (st << 1) | (r ? 1u : 0u);
             }
         }
         uint64_t word = __ballot(in_range && (st & 1u));
@@ -63,7 +80,7 @@ void launch_filter_compile(const FilterParams& p, uint32_t n_cu, hipStream_t s) 
     if (n_words == 0) return;
     const uint64_t want = (n_words + FLT_WAVES - 1) / FLT_WAVES;
     const uint32_t grid = (uint32_t)(want < (uint64_t)n_cu * 8 ? want : (uint64_t)n_cu * 8);
-    hipLaunchKernelGGL(filter_compile_kernel, dim3(grid), dim3(FLT_THREADS), p.n_ops * sizeof(FilterOp), s, p, n_words);
+    hipLaunchKernelGGL(filter_compile_kernel, dim3(grid), dim3(FLT_THREADS), p.n_ops * sizeof(FilterOp) + p.n_nums * sizeof(FilterNum), s, p, n_words);
 }
 
 }  // namespace vdb

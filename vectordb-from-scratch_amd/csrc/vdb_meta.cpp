@@ -5,6 +5,7 @@
 // uploads + ONE kernel (kernels_filter.hip) on the table's stream; the host never waits for it.
 #include "vdb_meta.h"
 
+#include <limits>
 #include <memory>
 
 #include "vdb_index.h"
@@ -14,11 +15,16 @@ using namespace vdbi;
 namespace {
 
 constexpr size_t BLOCK_HEADER = 16;                                 // the eligible count (8 bytes) + padding, in front of the program
-constexpr size_t BLOCK_BYTES = BLOCK_HEADER + vdb::FILTER_MAX_OPS * sizeof(vdb::FilterOp);
+// (a numeric leaf's FilterNum follows the ops of ITS program directly, so one copy uploads both)
+constexpr size_t BLOCK_BYTES = BLOCK_HEADER + vdb::FILTER_MAX_OPS * (sizeof(vdb::FilterOp) + sizeof(vdb::FilterNum));
 constexpr uint64_t MAX_IDS = 1ull << 32;
+constexpr uint64_t MAX_CODES = 1ull << 31;                          // dictionary codes are non-negative int32
 constexpr uint32_t MAX_SLOTS = 65536;
+constexpr size_t MAX_CONSTS = 1024;
 static_assert(VDB_META_EQ == (int)vdb::FOP_EQ && VDB_META_NE == (int)vdb::FOP_NE && VDB_META_EXISTS == (int)vdb::FOP_EXISTS && VDB_META_CONST == (int)vdb::FOP_CONST &&
-              VDB_META_AND == (int)vdb::FOP_AND && VDB_META_OR == (int)vdb::FOP_OR, "the ABI's opcodes are the kernel's");
+              VDB_META_AND == (int)vdb::FOP_AND && VDB_META_OR == (int)vdb::FOP_OR && VDB_META_LT == (int)vdb::FOP_LT && VDB_META_LE == (int)vdb::FOP_LE &&
+              VDB_META_GT == (int)vdb::FOP_GT && VDB_META_GE == (int)vdb::FOP_GE, "the ABI's opcodes are the kernel's");
+static_assert(sizeof(vdb::FilterOp) % alignof(vdb::FilterNum) == 0 && BLOCK_HEADER % alignof(vdb::FilterNum) == 0, "FilterNum behind the ops is aligned");
 
 // a host array with its device copy; [lo, hi) is what the device has not seen yet
 template <typename T> struct Staged {
@@ -53,6 +59,7 @@ struct vdb_meta_table {
     Stream stream;                                                  // declared first: destroyed after every buffer below
     std::mutex mu;                                                  // compiles are reads of the caller and may come from several threads
     std::vector<std::unique_ptr<Staged<int32_t>>> cols;             // by slot; null = slot never written
+    std::vector<std::unique_ptr<Staged<double>>> luts;              // by slot: the number of each dictionary code, NaN = none; null = no LUT (length 0)
     Staged<uint64_t> present;
     std::vector<std::unique_ptr<vdb_meta_mask>> masks;              // every mask ever handed out (owned here)
     std::vector<vdb_meta_mask*> free_masks;                         // released ones, most recently released last
@@ -65,6 +72,7 @@ namespace {
 int upload_staged(vdb_meta_table* t, hipStream_t s) {
     int rc;
     for (auto& c : t->cols) if (c && (rc = c->upload(s))) return rc;
+    for (auto& l : t->luts) if (l && (rc = l->upload(s))) return rc;
     return t->present.upload(s);
 }
 
@@ -147,6 +155,23 @@ int vdb_meta_set_codes(vdb_meta_table* t, uint32_t slot, uint64_t first_id, cons
     });
 }
 
+int vdb_meta_set_numbers(vdb_meta_table* t, uint32_t slot, uint32_t first_code, const double* values, size_t n) {
+    return guarded([&]() -> int {
+    if (!t || (n && !values)) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (slot >= MAX_SLOTS) return fail(VDB_ERR_INVALID_ARGUMENT, "slot %u out of range (%u)", slot, MAX_SLOTS);
+    if (first_code > MAX_CODES || n > MAX_CODES - first_code) return fail(VDB_ERR_INVALID_ARGUMENT, "dictionary codes must be below 2^31");
+    std::lock_guard<std::mutex> g(t->mu);
+    if (t->luts.size() <= slot) t->luts.resize(slot + 1);
+    if (!t->luts[slot]) { t->luts[slot] = std::make_unique<Staged<double>>(); t->luts[slot]->fill = std::numeric_limits<double>::quiet_NaN(); }
+    if (n == 0) return VDB_OK;
+    auto& l = *t->luts[slot];
+    l.grow((size_t)first_code + n);
+    memcpy(l.h.data() + first_code, values, n * sizeof(double));
+    l.touch(first_code, (size_t)first_code + n);
+    return VDB_OK;
+    });
+}
+
 int vdb_meta_set_present(vdb_meta_table* t, uint64_t first_id, size_t n, int on) {
     return guarded([&]() -> int {
     if (!t) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
@@ -168,17 +193,30 @@ int vdb_meta_set_present(vdb_meta_table* t, uint64_t first_id, size_t n, int on)
 }
 
 int vdb_meta_compile(vdb_meta_table* t, const vdb_meta_op* ops, size_t n_ops, size_t mask_bits, vdb_meta_mask** out) {
+    return vdb_meta_compile_num(t, ops, n_ops, nullptr, 0, mask_bits, out);     // no constants: a numeric op is refused
+}
+
+int vdb_meta_compile_num(vdb_meta_table* t, const vdb_meta_op* ops, size_t n_ops, const double* consts, size_t n_consts, size_t mask_bits,
+                         vdb_meta_mask** out) {
     return guarded([&]() -> int {
-    if (!t || !out || (n_ops && !ops)) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (!t || !out || (n_ops && !ops) || (n_consts && !consts)) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
     if (mask_bits > MAX_IDS) return fail(VDB_ERR_INVALID_ARGUMENT, "mask_bits must be at most 2^32");
     if (n_ops == 0 || n_ops > vdb::FILTER_MAX_OPS) return fail(VDB_ERR_INVALID_ARGUMENT, "a filter program has 1 to %u ops, not %zu", vdb::FILTER_MAX_OPS, n_ops);
+    if (n_consts > MAX_CONSTS) return fail(VDB_ERR_INVALID_ARGUMENT, "a filter program has at most %zu constants, not %zu", MAX_CONSTS, n_consts);
+    for (size_t i = 0; i < n_consts; ++i)
+        if (consts[i] != consts[i]) return fail(VDB_ERR_INVALID_ARGUMENT, "constant %zu is NaN", i);
     std::lock_guard<std::mutex> g(t->mu);
-    // 1. the program: well-formed postfix, stack depth within the register, every slot known
+    // 1. the program: well-formed postfix, stack depth within the register, every slot known, every constant index in range
     uint32_t depth = 0;
+    size_t n_nums = 0;
     for (size_t i = 0; i < n_ops; ++i) {
         const vdb_meta_op& o = ops[i];
         switch (o.op) {
+        case VDB_META_LT: case VDB_META_LE: case VDB_META_GT: case VDB_META_GE:
+            if (o.code < 0 || (size_t)o.code >= n_consts) return fail(VDB_ERR_INVALID_ARGUMENT, "op %zu names constant %d of %zu", i, o.code, n_consts);
+            ++n_nums;
+            [[fallthrough]];
         case VDB_META_EQ: case VDB_META_NE: case VDB_META_EXISTS:
             if (o.slot >= t->cols.size() || !t->cols[o.slot]) return fail(VDB_ERR_INVALID_ARGUMENT, "op %zu names slot %u, which was never written", i, o.slot);
             ++depth;
@@ -208,17 +246,26 @@ int vdb_meta_compile(vdb_meta_table* t, const vdb_meta_op* ops, size_t n_ops, si
     if ((rc = take_mask(t, std::max<size_t>(words, 1), &m))) return rc;   // (never a null pointer: to a search that means "no filter")
     m->bits = mask_bits;
     auto* hops = reinterpret_cast<vdb::FilterOp*>(m->h_block + BLOCK_HEADER);
+    auto* hnums = reinterpret_cast<vdb::FilterNum*>(hops + n_ops);  // one per numeric leaf, in program order, right behind the ops
+    size_t k = 0;
     for (size_t i = 0; i < n_ops; ++i) {
         const vdb_meta_op& o = ops[i];
         vdb::FilterOp f{nullptr, 0, (uint32_t)o.op, o.code};
-        if (o.op <= VDB_META_EXISTS) { f.codes = t->cols[o.slot]->d; f.len = t->cols[o.slot]->h.size(); }
+        const bool numeric = o.op >= VDB_META_LT;
+        if (o.op <= VDB_META_EXISTS || numeric) { f.codes = t->cols[o.slot]->d; f.len = t->cols[o.slot]->h.size(); }
+        if (numeric) {
+            const Staged<double>* l = o.slot < t->luts.size() ? t->luts[o.slot].get() : nullptr;
+            hnums[k] = vdb::FilterNum{l ? l->d.p : nullptr, l && l->d ? l->h.size() : 0, consts[o.code]};   // (no LUT: length 0, every leaf false)
+            f.code = (int32_t)k++;
+        }
         hops[i] = f;
     }
-    const size_t up = BLOCK_HEADER + n_ops * sizeof(vdb::FilterOp);
+    const size_t up = BLOCK_HEADER + n_ops * sizeof(vdb::FilterOp) + n_nums * sizeof(vdb::FilterNum);
     hipError_t e = hipMemcpyAsync(m->d_block, m->h_block, up, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
         vdb::FilterParams p{};
         p.ops = reinterpret_cast<const vdb::FilterOp*>(m->d_block + BLOCK_HEADER); p.n_ops = (uint32_t)n_ops;
+        p.nums = reinterpret_cast<const vdb::FilterNum*>(p.ops + n_ops); p.n_nums = (uint32_t)n_nums;
         p.present = t->present.d; p.present_words = t->present.d ? t->present.h.size() : 0;
         p.mask_bits = mask_bits; p.mask = m->d_words;
         p.count = reinterpret_cast<unsigned long long*>(m->d_block.p);

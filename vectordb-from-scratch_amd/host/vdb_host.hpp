@@ -11,7 +11,10 @@
 // Header-only; link with libvdbflat.so.
 #pragma once
 #include <algorithm>
+#include <clocale>
+#include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <map>
 #include <memory>
 #include <optional>
@@ -312,10 +315,53 @@ private:
     std::map<std::string, std::string> fields_;
 };
 
-struct MetadataFilter {                                                         // storage.rs:45-71
-    enum Op { Eq, Ne, Exists, And, Or } op;
+// The number of a metadata string (no reference counterpart; what MetadataFilter::lt / le / gt / ge compare).  `s` is numeric
+// iff ALL of it matches the ASCII grammar [+-]?([0-9]+(\.[0-9]*)?|\.[0-9]+)([eE][+-]?[0-9]+)? -- checked by hand here, so no
+// whitespace, "inf", "nan", hex or locale digits get through to the conversion -- and its correctly rounded binary64 value is
+// finite ("1e400" is not numeric; "1E-400" is 0).  The conversion is strtod in the "C" locale, whatever the process has set.
+inline bool parse_number(const std::string& s, double* out) {
+    const char* p = s.c_str();                                                   // (an embedded NUL ends the walk early: p != end below)
+    const char* const end = p + s.size();
+    auto digits = [&]() { size_t n = 0; while (*p >= '0' && *p <= '9') { ++p; ++n; } return n; };
+    if (*p == '+' || *p == '-') ++p;
+    if (digits()) {
+        if (*p == '.') { ++p; digits(); }
+    } else {
+        if (*p != '.') return false;
+        ++p;
+        if (!digits()) return false;
+    }
+    if (*p == 'e' || *p == 'E') {
+        ++p;
+        if (*p == '+' || *p == '-') ++p;
+        if (!digits()) return false;
+    }
+    if (p != end) return false;
+    static const locale_t c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
+    if (c_locale == (locale_t)0) return false;
+    const double v = strtod_l(s.c_str(), nullptr, c_locale);
+    if (!std::isfinite(v)) return false;
+    *out = v;
+    return true;
+}
+
+struct MetadataFilter {                                                         // storage.rs:45-71, plus the four numeric comparisons
+    enum Op { Eq, Ne, Exists, And, Or, Lt, Le, Gt, Ge } op;
     std::string field, value;
     std::vector<MetadataFilter> filters;
+    double number = 0;                                                          // Lt .. Ge: the constant, never NaN
+    // the row has the field, its string is numeric (parse_number) and number(string) OP v holds as an IEEE comparison; a NaN
+    // constant is refused
+    static MetadataFilter numeric(Op op, std::string f, double v) {
+        if (v != v) throw std::invalid_argument("a numeric filter's value must not be NaN");
+        MetadataFilter r{op, std::move(f), "", {}};
+        r.number = v;
+        return r;
+    }
+    static MetadataFilter lt(std::string f, double v) { return numeric(Lt, std::move(f), v); }
+    static MetadataFilter le(std::string f, double v) { return numeric(Le, std::move(f), v); }
+    static MetadataFilter gt(std::string f, double v) { return numeric(Gt, std::move(f), v); }
+    static MetadataFilter ge(std::string f, double v) { return numeric(Ge, std::move(f), v); }
     static MetadataFilter eq(std::string f, std::string v) { return {Eq, std::move(f), std::move(v), {}}; }
     static MetadataFilter ne(std::string f, std::string v) { return {Ne, std::move(f), std::move(v), {}}; }
     static MetadataFilter exists(std::string f) { return {Exists, std::move(f), "", {}}; }
@@ -329,6 +375,11 @@ struct MetadataFilter {                                                         
         case Exists: return v != nullptr;
         case And: return std::all_of(filters.begin(), filters.end(), [&](const MetadataFilter& f) { return f.matches(m); });
         case Or: return std::any_of(filters.begin(), filters.end(), [&](const MetadataFilter& f) { return f.matches(m); });
+        case Lt: case Le: case Gt: case Ge: {
+            double x;
+            if (!v || !parse_number(*v, &x)) return false;
+            return op == Lt ? x < number : (op == Le ? x <= number : (op == Gt ? x > number : x >= number));
+        }
         }
         return false;
     }

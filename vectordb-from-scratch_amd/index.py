@@ -124,7 +124,8 @@ class MetaTable:
     and a presence bitmap, both by internal id.  Writes are staged and uploaded by the next compile()."""
 
     EQ, NE, EXISTS, CONST, AND, OR = range(6)
-    MAX_OPS, MAX_DEPTH = 1024, 32
+    LT, LE, GT, GE = 16, 17, 18, 19
+    MAX_OPS, MAX_DEPTH, MAX_CONSTS = 1024, 32, 1024
 
     def __init__(self, device=0):
         self._L = _ffi.lib()
@@ -152,13 +153,30 @@ class MetaTable:
         if rc:
             _raise(rc)
 
-    def compile(self, program, mask_bits):
-        """program: a sequence of (op, slot, code) in postfix order.  Returns a CompiledMask without waiting for the device."""
+    def set_numbers(self, slot, first_code, values):
+        """The numeric LUT of column `slot`: values[i] is the number of dictionary code first_code + i, NaN = the code's string
+        has no number (vdb_meta_set_numbers).  What LT / LE / GT / GE leaves on that column compare."""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        if not 0 <= int(first_code) < 1 << 32:
+            raise ValueError("first_code must fit 32 bits")
+        rc = self._L.vdb_meta_set_numbers(self._t, int(slot), int(first_code), v.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), v.size)
+        if rc:
+            _raise(rc)
+
+    def compile(self, program, mask_bits, consts=None):
+        """program: a sequence of (op, slot, code) in postfix order; consts: the f64 constants its LT / LE / GT / GE leaves
+        index with `code` (None: vdb_meta_compile, which refuses such leaves).  Returns a CompiledMask without waiting for the
+        device."""
         ops = (_ffi.MetaOp * max(len(program), 1))()
         for i, (op, slot, code) in enumerate(program):
             ops[i].op, ops[i].slot, ops[i].code = int(op), int(slot), int(code)
         m = ctypes.c_void_p()
-        rc = self._L.vdb_meta_compile(self._t, ops, len(program), int(mask_bits), ctypes.byref(m))
+        if consts is None:
+            rc = self._L.vdb_meta_compile(self._t, ops, len(program), int(mask_bits), ctypes.byref(m))
+        else:
+            cs = np.ascontiguousarray(consts, dtype=np.float64)
+            rc = self._L.vdb_meta_compile_num(self._t, ops, len(program), cs.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), cs.size,
+                                              int(mask_bits), ctypes.byref(m))
         if rc:
             _raise(rc)
         return CompiledMask(self, m)

@@ -105,7 +105,7 @@ class _Guard:
 
 
 def filter_from_json(obj):
-    """serde(tag = "op", rename_all = "snake_case")  (storage.rs:45-58)."""
+    """serde(tag = "op", rename_all = "snake_case")  (storage.rs:45-58), plus {"op": "lt" | "le" | "gt" | "ge", "field", "value": number}."""
     op = obj.get("op")
     if op == "eq":
         return MetadataFilter.Eq(obj["field"], obj["value"])
@@ -113,6 +113,11 @@ def filter_from_json(obj):
         return MetadataFilter.Ne(obj["field"], obj["value"])
     if op == "exists":
         return MetadataFilter.Exists(obj["field"])
+    if op in ("lt", "le", "gt", "ge"):                     # numeric comparisons (no reference counterpart): value is a JSON number
+        value = obj["value"]
+        if isinstance(value, bool) or not isinstance(value, (int, float)):
+            raise ValueError(f"filter op {op!r} takes a number, not {value!r}")
+        return {"lt": MetadataFilter.Lt, "le": MetadataFilter.Le, "gt": MetadataFilter.Gt, "ge": MetadataFilter.Ge}[op](obj["field"], value)
     if op in ("and", "or"):
         subs = [filter_from_json(f) for f in obj["filters"]]
         return MetadataFilter.And(subs) if op == "and" else MetadataFilter.Or(subs)

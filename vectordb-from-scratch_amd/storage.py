@@ -2,6 +2,9 @@
 id maps, metadata, dimension enforcement, the metadata filter, and the batch drivers that call the
 index.  Same names, argument meaning and error behaviour as the reference; `search_batch` hands the
 whole batch to the index in one call (the hook SURVEY.md 8(b) describes)."""
+import math
+import re
+import struct
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -32,9 +35,60 @@ class Metadata:                                      # storage.rs:19-42
         return self._fields
 
 
+_NUMERIC = re.compile(r"[+-]?(?:[0-9]+(?:\.[0-9]*)?|\.[0-9]+)(?:[eE][+-]?[0-9]+)?")
+NUMERIC_OPS = ("lt", "le", "gt", "ge")
+
+
+def num(s):
+    """The number of a metadata string, or None.  Metadata values stay strings (storage.rs:19-22); `s` is numeric iff ALL of it
+    matches the ASCII grammar [+-]?([0-9]+(\\.[0-9]*)?|\\.[0-9]+)([eE][+-]?[0-9]+)? -- no whitespace, `_`, inf / nan, hex or
+    non-ASCII digits -- and its correctly rounded binary64 value is finite; that value is its number.  So "1e400" has none,
+    "1E-400" is 0.0, "-0" is -0.0, and an integer above 2^53 has the number it rounds to."""
+    if not isinstance(s, str) or _NUMERIC.fullmatch(s) is None:
+        return None
+    v = float(s)                                     # (correctly rounded; the grammar is a subset of what float() takes)
+    return v if math.isfinite(v) else None
+
+
+def _bits(value):
+    """the bit pattern of a binary64: what tells -0.0 from 0.0"""
+    return struct.unpack("<Q", struct.pack("<d", value))[0]
+
+
 class MetadataFilter:                                # storage.rs:45-71
     def __init__(self, op, field=None, value=None, filters=None):
         self.op, self.field, self.value, self.filters = op, field, value, filters or []
+
+    # ---- numeric comparisons (no reference counterpart): the row has the field, its string is numeric (num), and
+    # num(string) OP value holds as an IEEE comparison (-0.0 equals 0.0; value may be +-inf).  A row without the field or with
+    # a non-numeric string matches none of the four.
+    @staticmethod
+    def _numeric(op, field, value):
+        if isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"{op}: the value must be a number, not a bool")
+        try:
+            value = float(value)
+        except (TypeError, OverflowError) as e:
+            raise ValueError(f"{op}: the value must be a number ({e})") from None
+        if value != value:
+            raise ValueError(f"{op}: the value must not be NaN")
+        return MetadataFilter(op, field, value)
+
+    @staticmethod
+    def Lt(field, value):
+        return MetadataFilter._numeric("lt", field, value)
+
+    @staticmethod
+    def Le(field, value):
+        return MetadataFilter._numeric("le", field, value)
+
+    @staticmethod
+    def Gt(field, value):
+        return MetadataFilter._numeric("gt", field, value)
+
+    @staticmethod
+    def Ge(field, value):
+        return MetadataFilter._numeric("ge", field, value)
 
     @staticmethod
     def Eq(field, value):
@@ -63,6 +117,12 @@ class MetadataFilter:                                # storage.rs:45-71
             return metadata.get(self.field) != self.value
         if self.op == "exists":
             return metadata.get(self.field) is not None
+        if self.op in NUMERIC_OPS:
+            s = metadata.get(self.field)
+            v = num(str(s)) if s is not None else None   # (str: the one encoding of _Column.code)
+            if v is None:
+                return False
+            return {"lt": v < self.value, "le": v <= self.value, "gt": v > self.value, "ge": v >= self.value}[self.op]
         if self.op == "and":
             return all(f.matches(metadata) for f in self.filters)
         if self.op == "or":
@@ -85,6 +145,16 @@ class _Column:
     def __init__(self):
         self.codes = np.full(1024, -1, dtype=np.int32)
         self.values, self.code_of = [], {}
+        self._nums = np.full(64, np.nan)                 # num(values[c]) by code, NaN = none; always at least one NaN behind the last code
+
+    @property
+    def nums(self):
+        """f64, parallel to `values`: the number of each dictionary value (num), NaN where it has none"""
+        return self._nums[:len(self.values)]
+
+    def numbers_of(self, n):
+        """num() of the field for internal ids below n: NaN for a row without the field or with a non-numeric string"""
+        return self._nums[:len(self.values) + 1][self.view(n)]      # (code -1 indexes the NaN behind the last code)
 
     def _grow(self, n):
         if n > self.codes.size:
@@ -98,6 +168,12 @@ class _Column:
         if c is None and create:
             c = self.code_of[value] = len(self.values)
             self.values.append(value)
+            if c + 2 > self._nums.size:
+                new = np.full(2 * self._nums.size, np.nan)
+                new[:c] = self._nums[:c]
+                self._nums = new
+            v = num(value)
+            self._nums[c] = np.nan if v is None else v
         return c
 
     def set(self, internal, value):
@@ -147,6 +223,7 @@ class VectorStore:
         # filters compiled there; None = off, the default
         self._slots = {}
         self._table = None
+        self._lut_sent = {}                              # field -> dictionary codes whose numbers the table has (MetaTable.set_numbers)
 
     @classmethod
     def with_index(cls, index):                      # storage.rs:118-127
@@ -183,6 +260,7 @@ class VectorStore:
             col.set(internal, value)
             if self._table is not None:
                 self._table.set_codes(self._slots[key], internal, col.codes[internal:internal + 1])
+                self._forward_numbers(key, col)
         if old is not None:
             self._mark_present(old, False)
 
@@ -293,6 +371,14 @@ class VectorStore:
             self._slots[key] = len(self._slots)
         return col
 
+    def _forward_numbers(self, key, col):
+        """The numbers of the dictionary codes the device table has not seen yet (the LUT numeric leaves read), when the
+        column's dictionary grew."""
+        sent = self._lut_sent.get(key, 0)
+        if len(col.values) > sent:
+            self._table.set_numbers(self._slots[key], sent, col.nums[sent:])
+            self._lut_sent[key] = len(col.values)
+
     def attach_bulk_metadata(self, n, columns, ids=None):
         """Register n rows that are ALREADY in the index under the next n internal ids (a bulk device load, a mapped
         vector file: persistence/mmap.rs has no id or metadata column) together with their metadata columns
@@ -322,6 +408,7 @@ class VectorStore:
             col.set_range(start, values)
             if self._table is not None:
                 self._table.set_codes(self._slots[key], start, col.codes[start:start + n])
+                self._forward_numbers(key, col)
         self._mark_present(start + n - 1, False)                 # grow once
         self._present[start:start + n] = True
         if self._table is not None and n:
@@ -428,6 +515,12 @@ class VectorStore:
             if flt.op == "eq":
                 return (codes == c) if c is not None else np.zeros(n, dtype=bool)
             return (codes != c) if c is not None else np.ones(n, dtype=bool)      # Ne: a missing field matches (storage.rs:65)
+        if flt.op in NUMERIC_OPS:
+            col = self._cols.get(flt.field)
+            if col is None:                                       # nobody has the field
+                return np.zeros(n, dtype=bool)
+            v = col.numbers_of(n)                                 # NaN (no field, no number) fails all four comparisons
+            return {"lt": np.less, "le": np.less_equal, "gt": np.greater, "ge": np.greater_equal}[flt.op](v, flt.value)
         if flt.op in ("and", "or"):
             acc = np.full(n, flt.op == "and", dtype=bool)          # all([]) is true, any([]) is false, like Rust's iterators
             for f in flt.filters:
@@ -462,6 +555,7 @@ class VectorStore:
             return
         if not on:
             table, self._table = self._table, None
+            self._lut_sent = {}
             if table is not None:
                 table.close()
             return
@@ -471,6 +565,8 @@ class VectorStore:
         n = self._next_id
         for key, col in self._cols.items():
             table.set_codes(self._slots[key], 0, col.codes[:min(n, col.codes.size)])
+            table.set_numbers(self._slots[key], 0, col.nums)
+            self._lut_sent[key] = len(col.values)
         pres = self._present[:n]
         edges = np.flatnonzero(np.diff(np.concatenate(([False], pres, [False])).astype(np.int8)))   # the runs of present ids
         for a, b in zip(edges[0::2], edges[1::2]):
@@ -480,13 +576,18 @@ class VectorStore:
     def device_filter(self):
         return self._table is not None
 
-    def filter_program(self, flt):
+    def filter_program(self, flt, with_consts=False):
         """The filter as the postfix program vdb_meta_compile takes: a list of (op, slot, code), or None when it needs more
         than MetaTable.MAX_OPS ops or an evaluation stack deeper than MetaTable.MAX_DEPTH.  Everything that needs the
         dictionary is resolved here, exactly as _eval_filter does: a field nobody has and a value no row has become CONST
-        (Eq / Exists 0, Ne 1), And([]) is CONST 1, Or([]) CONST 0, n-ary And / Or are left folds of the binary op."""
+        (Eq / Exists 0, Ne 1), And([]) is CONST 1, Or([]) CONST 0, n-ary And / Or are left folds of the binary op.
+        with_consts=True: (program, consts), what vdb_meta_compile_num takes -- a numeric leaf is (LT | LE | GT | GE, slot,
+        index into consts), equal constants (by bit pattern) share an index, a field nobody has is CONST 0, and more than
+        MetaTable.MAX_CONSTS distinct constants give None.  Without it the constants are dropped: a program with numeric leaves
+        is then good for counting its ops only."""
         T = MetaTable
         prog = []
+        consts, const_of = [], {}
         depth = peak = 0
         # iterative post-order walk (a filter may nest deeper than Python's recursion limit likes): ("visit", f) | ("emit", op)
         todo = [("visit", flt)]
@@ -517,12 +618,23 @@ class VectorStore:
                     for g in f.filters[1:]:
                         steps += [("visit", g), ("emit", op)]
                     todo.extend(reversed(steps))
+            elif f.op in NUMERIC_OPS:                               # (behind the reference's five: they walk the code they always did)
+                if f.field not in self._cols:
+                    prog.append((T.CONST, 0, 0))
+                else:
+                    j = const_of.setdefault(_bits(f.value), len(consts))
+                    if j == len(consts):
+                        consts.append(f.value)
+                        if len(consts) > T.MAX_CONSTS:
+                            return None
+                    prog.append(({"lt": T.LT, "le": T.LE, "gt": T.GT, "ge": T.GE}[f.op], self._slots[f.field], j))
+                depth += 1
             else:
                 raise ValueError(f.op)
             peak = max(peak, depth)
             if len(prog) > T.MAX_OPS or peak > T.MAX_DEPTH:
                 return None
-        return prog
+        return (prog, consts) if with_consts else prog
 
     def compile_filter_device(self, flt):
         """compile_filter on the device: a CompiledMask over max(next internal id, 1) bits, equal to compile_filter's word for
@@ -530,10 +642,11 @@ class VectorStore:
         filter does not fit the program limits (filter_program)."""
         if self._table is None:
             raise ValueError("the device filter is off: set_device_filter(True) first")
-        prog = self.filter_program(flt)
+        prog = self.filter_program(flt, with_consts=True)
         if prog is None:
             return None
-        return self._table.compile(prog, max(self._next_id, 1))
+        prog, consts = prog
+        return self._table.compile(prog, max(self._next_id, 1), consts if consts else None)
 
     # ---- exact range search (GpuFlatIndex.range_search_batch; no reference counterpart)
     def search_within(self, query, radius, limit, flt=None):
@@ -639,7 +752,7 @@ class VectorStore:
                 todo.append(("fold", f))
                 todo.extend(("visit", g) for g in reversed(f.filters))
             elif what == "visit":
-                v = f.value
+                v = _bits(f.value) if f.op in NUMERIC_OPS else f.value     # (-0.0 == 0.0 and hash alike: told apart by their bits)
                 try:
                     hash(v)
                 except TypeError:
