@@ -508,6 +508,55 @@ int vdb_flat_search_batch_by_id_filtered(vdb_flat_index *h, const uint64_t *quer
 int vdb_flat_by_id_stats(const vdb_flat_index *h, uint64_t out[4]);
 
 /*
+ * RECOMMEND FROM POSITIVE AND NEGATIVE STORED IDS: "more like these, less like those" (no reference counterpart; a caller would
+ * get_vector every example, fold them on the host, upload, search with k + m and strike the examples on the host).  One sentence
+ * defines the call: for request b with positives p_1..p_np (np >= 1) and negatives n_1..n_nn (nn >= 0), all stored ids, and count
+ * k_b, the result is what vdb_flat_search_batch returns for the vector q_b with k_b + np + nn under the same mask, with every entry
+ * whose id is among the examples removed, cut to k_b -- ids, order, distance bits, counts and errors.
+ * q_b is computed per element j in f32 without contraction (the library is built with -ffp-contract=off):
+ *  - positive fold: sp = p_1[j]; for i = 2..np: sp = sp + p_i[j].  A LEFT fold in list order, started from the first row and not
+ *    from 0: -0.0 survives, and np = 1 is the stored row itself.
+ *  - positive average: ap = sp when np == 1, else ap = sp * rp with rp = 1.0f / (float)np computed once on the host: a multiply,
+ *    never a division on the device.
+ *  - query: nn == 0: q[j] = ap; otherwise an is built from the negatives in the same way and q[j] = ap + (ap - an).
+ * The order of the adds and the multiply are observable in the distance bits, so they are part of the contract.  The vectors never
+ * leave HBM: the lists go up, fold_examples_kernel writes the query block from the stored rows, the search runs, strike_set_kernel
+ * removes the examples from each list, the results come down (csrc/kernels_recommend.hip).
+ *  - Request b owns example_ids[offsets[b] .. offsets[b + 1]); the first n_pos[b] of them are positives, the rest negatives.
+ *  - Recommend with ([x], []) is vdb_flat_search_batch_by_id([x]) bit for bit.
+ *  - Removing the m = np + nn examples from the top k + m and cutting to k is exact, for the same reason by-id's + 1 is: the top k
+ *    of "eligible rows without the examples" is the top k + m of "eligible rows", minus the examples, cut to k.
+ *  - An example that the mask makes ineligible is still a valid example: it is folded, and it is simply in nobody's list.
+ *  - The same id may appear several times in a request, on either side or on both: it is folded as often as it is listed.  The
+ *    strike is by SET (64-bit id equality); the over-fetch is by COUNT m, which is at least the size of the set.
+ *  - No id value is a flag: 2^64 - 1 is a legal example and a legal neighbour.
+ *  - ks: ONE search at depth min(min(max ks, len) + max_b m_b, len) and one strike; the answer for k_b is the first k_b entries of
+ *    the struck list.  k is clamped to len before m is added, as by-id does, so k = SIZE_MAX cannot wrap.
+ * VDB_ERR_INVALID_ARGUMENT before any device work: a null array (nq > 0), offsets[0] != 0, decreasing offsets, n_pos[b] == 0,
+ * n_pos[b] above the request's length, more than VDB_RECOMMEND_MAX_EXAMPLES examples in a request, offsets[nq] > 2^20.  After
+ * those, in by-id's order: staged adds and removes are flushed; an example that is not stored -- never added, or removed -- fails
+ * the whole batch with VDB_ERR_NOT_FOUND, the message naming the first such id in array order; an example whose row has another
+ * dimension than the index fails with VDB_ERR_DIMENSION_MISMATCH; everything else is the error of the equivalent search: a fold that
+ * comes out all zero under Cosine (p and -p) is VDB_ERR_INVALID_VECTOR, a fold that overflows gives what searching with that vector
+ * gives (VDB_ERR_NAN where a distance is NaN).  Locking and tickets as vdb_flat_search_batch_by_id.
+ * On a sharded handle every shard gathers the rows of ITS examples on its own device, the blocks go to devices[0] device-to-device
+ * and the fold runs there over the staged rows: the fold order is the request's list order wherever the rows live.  _filtered is
+ * the same call under a compiled mask (vdb_flat_search_batch_filtered).
+ * vdb_flat_recommend_stats describes the last call on the handle: [0] requests, [1] example rows folded (the sum of m_b),
+ * [2] entries struck in total (those in front of the cut of the batch-wide list), [3] the depth the search ran at.
+ */
+#define VDB_RECOMMEND_MAX_EXAMPLES 64   /* per request, positives + negatives */
+int vdb_flat_recommend_batch(vdb_flat_index *h, const uint64_t *example_ids, const size_t *offsets /* [nq + 1] */,
+                             const uint32_t *n_pos /* [nq] */, size_t nq, const size_t *ks, size_t k,
+                             const uint64_t *id_mask, size_t mask_bits, size_t kstride,
+                             uint64_t *out_ids, float *out_dists, size_t *out_counts);
+int vdb_flat_recommend_batch_filtered(vdb_flat_index *h, const uint64_t *example_ids, const size_t *offsets /* [nq + 1] */,
+                                      const uint32_t *n_pos /* [nq] */, size_t nq, const size_t *ks, size_t k,
+                                      const vdb_meta_mask *mask, size_t kstride,
+                                      uint64_t *out_ids, float *out_dists, size_t *out_counts);
+int vdb_flat_recommend_stats(const vdb_flat_index *h, uint64_t out[4]);
+
+/*
  * ONE NEAREST ROW PER GROUP: the k nearest documents, videos, products of a store of chunked items, each represented by its nearest
  * row (no reference counterpart: a caller of Index::search over-fetches by a guessed factor and dedupes on the host, the failure of
  * the 3x post-filter of storage.rs:249-290).  One sentence defines the call: for query q, count k, column `slot` of `table` and an

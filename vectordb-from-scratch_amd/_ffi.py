@@ -18,6 +18,7 @@ SYMBOLS = [
     "vdb_flat_search_batch_device", "vdb_flat_search_batch_device_begin", "vdb_flat_search_batch_device_finish", "vdb_flat_search_batch_device_submit", "vdb_flat_search_batch_device_wait", "vdb_flat_distances_batch", "vdb_merge_topk_device", "vdb_merge_topk_packed_device", "vdb_flat_set_profile", "vdb_flat_last_stats", "vdb_flat_last_stats_ex", "vdb_flat_set_screen", "vdb_flat_set_wide", "vdb_flat_set_large_k", "vdb_flat_large_k_min_rows", "vdb_flat_set_shadow", "vdb_flat_set_sample_cache", "vdb_flat_set_tiers", "vdb_flat_debug_screen_scores", "vdb_flat_debug_rows", "vdb_flat_debug_row_info", "vdb_flat_debug_last_thresholds", "vdb_flat_debug_cert_probe", "vdb_flat_debug_compact_plan", "vdb_flat_debug_set_compact_bounce", "vdb_last_error",
     "vdb_flat_range_search_batch", "vdb_flat_range_search_batch_device", "vdb_flat_range_stats",
     "vdb_flat_search_batch_by_id", "vdb_flat_search_batch_by_id_filtered", "vdb_flat_by_id_stats",
+    "vdb_flat_recommend_batch", "vdb_flat_recommend_batch_filtered", "vdb_flat_recommend_stats",
     "vdb_flat_search_batch_distinct", "vdb_flat_search_batch_distinct_filtered", "vdb_flat_distinct_stats", "vdb_flat_distinct_depth",
     "vdb_flat_search_batch_grouped", "vdb_flat_search_batch_grouped_filtered", "vdb_flat_grouped_stats", "vdb_flat_debug_group_plan",
     "vdb_flat_set_sparse_filter", "vdb_flat_sparse_stats", "vdb_flat_sparse_limit", "vdb_flat_debug_eligible_rows", "vdb_flat_debug_sparse_tile_rows", "vdb_flat_debug_sparse_tile_queries",
@@ -166,6 +167,9 @@ def lib():
     L.vdb_flat_search_batch_by_id.argtypes = [vp, u64p, sz, szp, sz, u64p, sz, sz, u64p, fp, szp]
     L.vdb_flat_search_batch_by_id_filtered.argtypes = [vp, u64p, sz, szp, sz, vp, sz, u64p, fp, szp]
     L.vdb_flat_by_id_stats.argtypes = [vp, u64p]
+    L.vdb_flat_recommend_batch.argtypes = [vp, u64p, szp, c.POINTER(c.c_uint32), sz, szp, sz, u64p, sz, sz, u64p, fp, szp]
+    L.vdb_flat_recommend_batch_filtered.argtypes = [vp, u64p, szp, c.POINTER(c.c_uint32), sz, szp, sz, vp, sz, u64p, fp, szp]
+    L.vdb_flat_recommend_stats.argtypes = [vp, u64p]
     i32p = c.POINTER(c.c_int32)
     L.vdb_flat_search_batch_distinct.argtypes = [vp, fp, sz, sz, szp, sz, vp, c.c_uint32, u64p, sz, sz, u64p, fp, i32p, szp]
     L.vdb_flat_search_batch_distinct_filtered.argtypes = [vp, fp, sz, sz, szp, sz, vp, c.c_uint32, vp, sz, u64p, fp, i32p, szp]

@@ -621,4 +621,27 @@ struct ExcludeGroupsParams {
 };
 void launch_exclude_groups(const ExcludeGroupsParams& p, uint32_t n_cu, hipStream_t s);
 
+// ---------------------------------------------------------------- recommend from stored examples (kernels_recommend.hip)
+constexpr uint32_t RECOMMEND_MAX_EXAMPLES = 64;                            // per request, positives + negatives (VDB_RECOMMEND_MAX_EXAMPLES)
+// The requests of one call on the device: request b owns entries [offs[b], offs[b + 1]) of rows / ids, the first n_pos[b] of
+// them positives, the rest negatives; recip[2 b] = 1.0f / positives, recip[2 b + 1] = 1.0f / negatives (unused when there are none)
+struct RecommendLists {
+    const uint32_t* offs; const uint32_t* n_pos; const float* recip;
+    const uint32_t* rows;                                                  // row numbers in the block the fold reads
+    const uint64_t* ids;                                                   // the stored ids of the same entries
+};
+// out[b * dim .. + dim) = the query of request b (include/vdb_flat.h: left fold in list order, multiply by the reciprocal,
+// ap + (ap - an)) from rows[row * ld .. + dim), row < n_rows
+void launch_fold_examples(const float* rows, uint32_t ld, uint32_t dim, uint32_t n_rows, const RecommendLists& L, uint32_t nq,
+                          float* out, hipStream_t s);
+// Request b's result list ids / dists [b * kdev ..], counts[b] entries: every entry whose id is among ex_ids[offs[b], offs[b + 1])
+// is removed and the gaps closed in order; counts[b] = min(entries kept, kcut).  stats[0] += the removed entries that stood in
+// front of the kcut-th kept one.  Nothing at or past counts[b] (as it was), or at or past kcut, is written.
+struct StrikeSetParams {
+    uint64_t* ids; float* dists; uint32_t* counts; uint32_t kdev;
+    const uint32_t* offs; const uint64_t* ex_ids; uint32_t kcut;
+    uint32_t* stats;                                                       // [1], zeroed by the caller
+};
+void launch_strike_set(const StrikeSetParams& p, uint32_t nq, hipStream_t s);
+
 }  // namespace vdb

@@ -551,16 +551,72 @@ static int resolve_query_ids(vdb_flat_index* ix, const uint64_t* ids, size_t nq,
     return VDB_OK;
 }
 
+static_assert(vdb::RECOMMEND_MAX_EXAMPLES == VDB_RECOMMEND_MAX_EXAMPLES, "the kernels' LDS set and the public limit");
+// The argument checks of vdb_flat_recommend_batch, before any lock or device work; fills r->total and r->mmax.
+static int recommend_check(RecommendReq* r, size_t nq) {
+    r->total = r->mmax = 0;
+    if (nq == 0) return VDB_OK;
+    if (!r->offsets || !r->n_pos) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (r->offsets[0] != 0) return fail(VDB_ERR_INVALID_ARGUMENT, "offsets[0] is %zu, not 0", r->offsets[0]);
+    for (size_t b = 0; b < nq; ++b) {
+        if (r->offsets[b + 1] < r->offsets[b]) return fail(VDB_ERR_INVALID_ARGUMENT, "offsets decrease at request %zu", b);
+        const size_t m = r->offsets[b + 1] - r->offsets[b];
+        if (m > VDB_RECOMMEND_MAX_EXAMPLES) return fail(VDB_ERR_INVALID_ARGUMENT, "request %zu has %zu examples, more than %d", b, m, VDB_RECOMMEND_MAX_EXAMPLES);
+        if (r->n_pos[b] == 0) return fail(VDB_ERR_INVALID_ARGUMENT, "request %zu has no positive example", b);
+        if (r->n_pos[b] > m) return fail(VDB_ERR_INVALID_ARGUMENT, "request %zu: %u positives among %zu examples", b, r->n_pos[b], m);
+        r->mmax = std::max(r->mmax, m);
+    }
+    r->total = r->offsets[nq];
+    if (r->total > ((size_t)1 << 20)) return fail(VDB_ERR_INVALID_ARGUMENT, "%zu examples in one call, more than 2^20", r->total);
+    if (!r->ids) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    return VDB_OK;
+}
+
+int vdbi::recommend_stage(RecommendWs& W, const RecommendReq& r, size_t nq, const uint32_t* rows, hipStream_t s, vdb::RecommendLists* L) {
+    // offsets [nq + 1] | n_pos [nq] | reciprocals [nq][2] | row numbers [total]
+    const size_t o_np = nq + 1, o_rc = o_np + nq, o_row = o_rc + 2 * nq, words = o_row + r.total;
+    std::vector<uint32_t> meta(words);
+    for (size_t b = 0; b <= nq; ++b) meta[b] = (uint32_t)r.offsets[b];
+    for (size_t b = 0; b < nq; ++b) {
+        const uint32_t np = r.n_pos[b], nn = (uint32_t)(r.offsets[b + 1] - r.offsets[b]) - np;
+        const float rc[2] = {1.0f / (float)np, nn ? 1.0f / (float)nn : 0.0f};   // f32, once, here: the kernel multiplies
+        meta[o_np + b] = np;
+        memcpy(&meta[o_rc + 2 * b], rc, sizeof(rc));
+    }
+    memcpy(meta.data() + o_row, rows, r.total * 4);
+    int rc;
+    if ((rc = W.meta.ensure(words))) return rc;
+    if ((rc = W.ids.ensure(r.total))) return rc;
+    if ((rc = W.stat.ensure(1))) return rc;
+    HIP_TRY(hipMemcpyAsync(W.meta.p, meta.data(), words * 4, hipMemcpyHostToDevice, s));   // (pageable: the copy has left `meta` when this returns)
+    HIP_TRY(hipMemcpyAsync(W.ids.p, r.ids, r.total * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(W.stat.p, 0, 4, s));
+    *L = vdb::RecommendLists{W.meta.p, W.meta.p + o_np, reinterpret_cast<const float*>(W.meta.p + o_rc), W.meta.p + o_row, W.ids.p};
+    return VDB_OK;
+}
+
+int vdbi::recommend_strike(RecommendWs& W, const vdb::RecommendLists& L, size_t nq, uint64_t* d_ids, float* d_dists, uint32_t* d_counts,
+                           size_t kdev, size_t kcut, hipStream_t s, uint32_t* struck) {
+    vdb::StrikeSetParams sp{d_ids, d_dists, d_counts, (uint32_t)kdev, L.offs, L.ids, (uint32_t)kcut, W.stat.p};
+    vdb::launch_strike_set(sp, (uint32_t)nq, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(struck, W.stat.p, 4, hipMemcpyDeviceToHost, s));
+    return VDB_OK;
+}
+
 // vdb_flat_search_batch and vdb_flat_search_batch_filtered: the id mask comes from the host (id_mask, uploaded here) or is a
 // compiled one already in HBM (cm: the stream is ordered behind its event, nothing is uploaded); everything below is the same.
 // dm (vdb_internal::search_batch_device_mask): mask_bits bits at a device address, written on the handle's own stream.
 // by (vdb_flat_search_batch_by_id; `queries` and `dim` are then unused): the queries are the STORED vectors of these ids.  Their
 // device rows are gathered into the query block on the device, the search runs with one result more, and the entry whose id
 // equals the query's own is struck from each list on the device before the usual copy-out.
+// rec (vdb_flat_recommend_batch; `by` is then rec->ids): the queries are FOLDS of stored vectors.  All examples resolve to device
+// rows as by-id's queries do, the fold kernel writes the query block straight from d_rows, the search runs with as many results
+// more as the longest request has examples, and the set strike removes every example from its request's list.
 static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks,
                              size_t k, const uint64_t* id_mask, size_t mask_bits, const vdb_meta_mask* cm, size_t kstride,
                              uint64_t* out_ids, float* out_dists, size_t* out_counts, const uint64_t* dm = nullptr,
-                             const uint64_t* by = nullptr) {
+                             const uint64_t* by = nullptr, const RecommendReq* rec = nullptr) {
     return guarded([&]() -> int {
     if (!ix || (nq && ((!queries && !by) || !out_counts))) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
     if (cm) {
@@ -570,7 +626,7 @@ static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq
     }
     if (ix->multi) {
         if (dm) return refuse_multi("a search under a raw device mask");
-        if (by) return multi_search_by_id(ix, by, nq, ks, k, id_mask, mask_bits, kstride, out_ids, out_dists, out_counts, cm);
+        if (by) return multi_search_by_id(ix, by, nq, ks, k, id_mask, mask_bits, kstride, out_ids, out_dists, out_counts, cm, rec);
         return multi_search_host(ix, queries, nq, dim, ks, k, id_mask, mask_bits, kstride, out_ids, out_dists, out_counts, cm);
     }
     size_t kmax = k;
@@ -584,21 +640,22 @@ static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq
     if (in_flight(ix)) return refuse_in_flight();
     int rc = set_device(ix);
     if (rc) return rc;
-    if (by) memset(ix->by_id_stats, 0, sizeof(ix->by_id_stats));
+    if (rec) memset(ix->recommend_stats, 0, sizeof(ix->recommend_stats));
+    else if (by) memset(ix->by_id_stats, 0, sizeof(ix->by_id_stats));
     if (nq == 0) return VDB_OK;
     std::vector<uint32_t> self_rows;
     if (by) {
         // staged adds and removes first: an id resolves to what the search below sees
         if (nq > 0x7fffffffull / 2) return fail(VDB_ERR_INVALID_ARGUMENT, "batch too large");
         if ((rc = flush(ix))) return rc;
-        if ((rc = resolve_query_ids(ix, by, nq, &self_rows))) return rc;
+        if ((rc = resolve_query_ids(ix, by, rec ? rec->total : nq, &self_rows))) return rc;
         dim = ix->dim;
     }
     // Index::search returns at most len results; clamp before sizing device buffers
     size_t len = ix->n_live + ix->misfits.size();
     size_t kdev = std::min(kmax, std::max<size_t>(len, 1));
     const size_t kcut = kdev;                                      // by id: what is left of a list after the strike, at most
-    if (by) kdev = std::min(kdev + 1, len);                        // (k was clamped to len first: k = SIZE_MAX cannot wrap)
+    if (by) kdev = std::min(kdev + (rec ? rec->mmax : 1), len);    // (k was clamped to len first: k = SIZE_MAX cannot wrap)
     hipStream_t s = ix->stream;
     // Small index, a few queries (BASELINE configs[0]: Index::search itself, one query): queries and results go through MAPPED
     // host memory -- the two kernels of the direct path read and write it in place, nothing is copied by the runtime
@@ -627,7 +684,13 @@ static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq
     if ((rc = ix->cur->w_outi.ensure(nq * std::max<size_t>(kdev, 1)))) return rc;
     if ((rc = ix->cur->w_outd.ensure(nq * std::max<size_t>(kdev, 1)))) return rc;
     if ((rc = ix->cur->w_outc.ensure(nq))) return rc;
-    if (by) {
+    vdb::RecommendLists rl{};
+    if (rec) {
+        // only the lists go up; the fold reads the examples where they are stored
+        if ((rc = recommend_stage(ix->cur->w_rec, *rec, nq, self_rows.data(), s, &rl))) return rc;
+        vdb::launch_fold_examples(ix->d_rows, ix->ld, ix->dim, ix->n_uploaded, rl, (uint32_t)nq, ix->cur->w_qin.p, s);
+        HIP_TRY(hipGetLastError());
+    } else if (by) {
         // only the row numbers and the ids go up; the vectors never leave HBM
         if ((rc = ix->cur->w_selfrow.ensure(nq))) return rc;
         if ((rc = ix->cur->w_selfid.ensure(nq))) return rc;
@@ -654,7 +717,9 @@ static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq
                        nullptr);
     if (rc) return rc;
     uint32_t by_stat[2] = {0, 0};
-    if (by) {
+    if (rec) {
+        if ((rc = recommend_strike(ix->cur->w_rec, rl, nq, ix->cur->w_outi.p, ix->cur->w_outd.p, ix->cur->w_outc.p, kdev, kcut, s, by_stat))) return rc;
+    } else if (by) {
         vdb::StrikeSelfParams sp{ix->cur->w_outi.p, ix->cur->w_outd.p, ix->cur->w_outc.p, (uint32_t)kdev, ix->cur->w_selfid.p, (uint32_t)kcut,
                                  ix->cur->w_bystat.p};
         vdb::launch_strike_self(sp, (uint32_t)nq, s);
@@ -670,7 +735,8 @@ static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq
         HIP_TRY(hipMemcpyAsync(ds.data(), ix->cur->w_outd.p, nq * kdev * 4, hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(hipStreamSynchronize(s));
-    if (by) { ix->by_id_stats[0] = nq; ix->by_id_stats[1] = by_stat[0]; ix->by_id_stats[2] = by_stat[1]; }
+    if (rec) { ix->recommend_stats[0] = nq; ix->recommend_stats[1] = rec->total; ix->recommend_stats[2] = by_stat[0]; ix->recommend_stats[3] = kdev; }
+    else if (by) { ix->by_id_stats[0] = nq; ix->by_id_stats[1] = by_stat[0]; ix->by_id_stats[2] = by_stat[1]; }
     for (size_t b = 0; b < nq; ++b) {
         size_t kb = ks ? ks[b] : k;
         size_t c = std::min<size_t>(cnt[b], kb);   // per-query k: a prefix of the batch-wide result
@@ -721,6 +787,34 @@ int vdb_flat_search_batch_by_id_filtered(vdb_flat_index* ix, const uint64_t* que
 int vdb_flat_by_id_stats(const vdb_flat_index* ix, uint64_t out[4]) {
     if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
     memcpy(out, ix->by_id_stats, sizeof(ix->by_id_stats));
+    return VDB_OK;
+}
+
+// ---- recommend from positive and negative stored ids (no reference counterpart; search_batch_host with `rec`)
+int vdb_flat_recommend_batch(vdb_flat_index* ix, const uint64_t* example_ids, const size_t* offsets, const uint32_t* n_pos, size_t nq,
+                             const size_t* ks, size_t k, const uint64_t* id_mask, size_t mask_bits, size_t kstride, uint64_t* out_ids,
+                             float* out_dists, size_t* out_counts) {
+    RecommendReq r{example_ids, offsets, n_pos};
+    int rc = recommend_check(&r, nq);
+    if (rc) return rc;
+    return search_batch_host(ix, nullptr, nq, 0, ks, k, id_mask, mask_bits, nullptr, kstride, out_ids, out_dists, out_counts, nullptr,
+                             example_ids ? example_ids : &kNoIds, &r);
+}
+
+int vdb_flat_recommend_batch_filtered(vdb_flat_index* ix, const uint64_t* example_ids, const size_t* offsets, const uint32_t* n_pos,
+                                      size_t nq, const size_t* ks, size_t k, const vdb_meta_mask* mask, size_t kstride,
+                                      uint64_t* out_ids, float* out_dists, size_t* out_counts) {
+    if (!mask) return fail(VDB_ERR_INVALID_ARGUMENT, "null mask");
+    RecommendReq r{example_ids, offsets, n_pos};
+    int rc = recommend_check(&r, nq);
+    if (rc) return rc;
+    return search_batch_host(ix, nullptr, nq, 0, ks, k, nullptr, 0, mask, kstride, out_ids, out_dists, out_counts, nullptr,
+                             example_ids ? example_ids : &kNoIds, &r);
+}
+
+int vdb_flat_recommend_stats(const vdb_flat_index* ix, uint64_t out[4]) {
+    if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    memcpy(out, ix->recommend_stats, sizeof(ix->recommend_stats));
     return VDB_OK;
 }
 

@@ -49,6 +49,17 @@ constexpr uint32_t SPARSE_MAX_E = 131072;   // sparse-filter route: eligible row
 
 }  // namespace vdbi
 
+// What one recommend call owns on the device (vdb_flat_recommend_batch) beside the search workspace; a sharded
+// parent's live on devices[0].  RecommendReq is the call as the caller passed it, checked by recommend_check.
+struct RecommendWs {
+    vdbi::DevBuf<uint32_t> meta, stat;                            // offsets [nq + 1] | n_pos [nq] | reciprocals [nq][2] | row numbers [total] ; struck entries
+    vdbi::DevBuf<uint64_t> ids;                                   // the example ids [total]
+};
+struct RecommendReq {
+    const uint64_t* ids; const size_t* offsets; const uint32_t* n_pos;
+    size_t total = 0, mmax = 0;                                   // offsets[nq]; the longest request (recommend_check)
+};
+
 struct Workspace {
     vdbi::DevBuf<float> w_qp, w_qnorm, w_thr, w_qin, w_outd, w_qerr, w_qg, w_dbg;
     uint32_t dbg_nq = 0; bool dbg_lb = false, dbg_f32 = false;             // vdb_flat_debug_screen_scores left this many prepared queries in the workspace
@@ -57,6 +68,7 @@ struct Workspace {
     vdbi::DevBuf<uint32_t> w_elig, w_eligblk;                     // sparse-filter route: the eligible-row list; block counts | block offsets | E
     vdbi::DevBuf<float> w_radii; vdbi::DevBuf<uint64_t> w_totals; // range search, host-pointer form: radii in, totals out
     vdbi::DevBuf<uint32_t> w_selfrow, w_bystat; vdbi::DevBuf<uint64_t> w_selfid;   // search by stored id: device rows and ids of the queries, struck | cut counters
+    RecommendWs w_rec;                                            // recommend: the requests' lists
     vdbi::DevBuf<uint16_t> w_qb;                                  // bf16 copy of the padded queries (screening tier)
     // compact block of the queries the screening tier could not certify (re-run by the f32 tier)
     vdbi::DevBuf<float> w2_qp, w2_qnorm, w2_thr, w2_outd, w2_qerr, w2_qg;
@@ -188,6 +200,7 @@ struct vdb_flat_index {
     uint64_t sparse_last = 0, sparse_E = 0, sparse_count = 0;  // vdb_flat_sparse_stats [0] [1] [2]
     uint64_t range_stats[8] = {0};                          // vdb_flat_range_stats: counters of the last range search
     uint64_t by_id_stats[4] = {0};                          // vdb_flat_by_id_stats: counters of the last search by stored id (also on a sharded parent)
+    uint64_t recommend_stats[4] = {0};                      // vdb_flat_recommend_stats: counters of the last recommend call (also on a sharded parent)
     uint64_t distinct_stats[8] = {0};                       // vdb_flat_distinct_stats: counters of the last search by group (also on a sharded parent)
     DistinctWs dws;                                         // its device buffers (a sharded parent's live on devices[0])
     uint64_t grouped_stats[8] = {0};                        // vdb_flat_grouped_stats: counters of the last grouped search
@@ -259,6 +272,13 @@ int search_device(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, 
 // what search_part1 answers for a query of `dim` elements before any device work: VDB_OK, or the dimension error of the first
 // stored row that differs (distance.rs:21-26) -- the check a search by stored id makes for the vector its id names
 int query_dim_check(const Index* ix, size_t dim);
+// ---- vdb_flat.cpp: the device side of a recommend call, the same on a plain handle and on the home device of a sharded one.
+// recommend_stage packs the checked request with the row number of every example (in the block the fold will read) and sends it
+// up on s in two copies; *L then names the lists on the device.  recommend_strike runs the set strike over the search's lists and
+// enqueues the read of the struck counter into *struck (valid after the caller's synchronisation).
+int recommend_stage(RecommendWs& W, const RecommendReq& r, size_t nq, const uint32_t* rows, hipStream_t s, vdb::RecommendLists* L);
+int recommend_strike(RecommendWs& W, const vdb::RecommendLists& L, size_t nq, uint64_t* d_ids, float* d_dists, uint32_t* d_counts,
+                     size_t kdev, size_t kcut, hipStream_t s, uint32_t* struck);
 int range_search_device(Index* ix, const float* d_q, size_t nq, size_t dim, const float* d_radii, const uint64_t* d_idmask,
                         size_t mask_bits, size_t max_results, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                         uint64_t* d_out_totals, hipStream_t user_stream);
@@ -316,10 +336,12 @@ int multi_search_host(vdb_flat_index* P, const float* queries, size_t nq, size_t
                       size_t mask_bits, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts,
                       const struct vdb_meta_mask* cm = nullptr);   // cm: a compiled mask on the home device instead of id_mask (vdb_meta.h)
 // vdb_flat_search_batch_by_id on a sharded handle: every shard gathers the rows of ITS query ids on its own device, the blocks
-// meet on devices[0] device-to-device, the ordinary sharded search runs with k + 1 and the strike runs on devices[0]
+// meet on devices[0] device-to-device, the ordinary sharded search runs with k + 1 and the strike runs on devices[0].
+// rec (vdb_flat_recommend_batch; query_ids is then rec->ids): one staged row per EXAMPLE, folded on devices[0] in list order into
+// the nq queries; the search runs with k + the longest request and the set strike replaces the self strike
 int multi_search_by_id(vdb_flat_index* P, const uint64_t* query_ids, size_t nq, const size_t* ks, size_t k, const uint64_t* id_mask,
                        size_t mask_bits, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts,
-                       const struct vdb_meta_mask* cm);
+                       const struct vdb_meta_mask* cm, const RecommendReq* rec = nullptr);
 // vdb_flat_search_batch_distinct on a sharded handle (the caller holds the parent's lock): the shards' staged adds flushed; the
 // stream of devices[0] that distinct_drive's kernels run on; the sharded search behind a host wait for that stream (the shards'
 // streams read what it wrote); the largest id bound of the shards

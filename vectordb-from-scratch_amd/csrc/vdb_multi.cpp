@@ -153,6 +153,7 @@ struct vdb_multi {
     vdbi::DevBuf<float> w_qin, w_outd; vdbi::DevBuf<uint64_t> w_outi, w_mask; vdbi::DevBuf<uint32_t> w_outc;
     // search by stored id: the shards' gathered blocks side by side, each query's place in them, the query ids, struck | cut counters
     vdbi::DevBuf<float> w_gstage; vdbi::DevBuf<uint32_t> w_place, w_bystat; vdbi::DevBuf<uint64_t> w_selfid;
+    RecommendWs w_rec;                                          // recommend: the requests' lists; their row numbers are places in w_gstage
     uint64_t stats[8] = {0};
     vdbi::Gang gang;
 };
@@ -578,10 +579,11 @@ namespace {
 // The second half of the host-pointer searches, under the parent's lock: the query block [nq][dim] is already in (or on its way
 // into, on the home stream) M->w_qin; the mask is staged, the sharded search runs with kdev results per query and the first k_b of
 // each list are copied out.  by (search by stored id): kdev is one more than kcut, and the entry whose id equals by[b] is struck
-// from list b on the home device in between.
+// from list b on the home device in between.  rec / rl (recommend; by is null): the lists are already staged on the home device,
+// kdev is kcut + the longest request, and the set strike removes every example of request b from list b.
 int finish_host(vdb_flat_index* P, size_t nq, size_t dim, const size_t* ks, size_t k, size_t kdev, const uint64_t* id_mask, size_t mask_bits,
                 const vdb_meta_mask* cm, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts, const uint64_t* by = nullptr,
-                size_t kcut = 0) {
+                size_t kcut = 0, const RecommendReq* rec = nullptr, const vdb::RecommendLists* rl = nullptr) {
     vdb_multi* M = P->multi;
     hipStream_t s = M->ps[0].stream;
     int rc;
@@ -607,7 +609,9 @@ int finish_host(vdb_flat_index* P, size_t nq, size_t dim, const size_t* ks, size
     HIP_TRY(hipStreamSynchronize(s));                                  // the shards' streams read the staged queries
     if ((rc = search_locked(P, M->w_qin.p, nq, dim, kdev, d_mask, mask_bits, M->w_outi.p, M->w_outd.p, M->w_outc.p, nullptr))) return rc;
     uint32_t by_stat[2] = {0, 0};
-    if (by) {
+    if (rec) {
+        if ((rc = recommend_strike(M->w_rec, *rl, nq, M->w_outi.p, M->w_outd.p, M->w_outc.p, kdev, kcut, s, by_stat))) return rc;
+    } else if (by) {
         vdb::StrikeSelfParams sp{M->w_outi.p, M->w_outd.p, M->w_outc.p, (uint32_t)kdev, M->w_selfid.p, (uint32_t)kcut, M->w_bystat.p};
         vdb::launch_strike_self(sp, (uint32_t)nq, s);
         HIP_TRY(hipGetLastError());
@@ -622,7 +626,8 @@ int finish_host(vdb_flat_index* P, size_t nq, size_t dim, const size_t* ks, size
         HIP_TRY(hipMemcpyAsync(ds.data(), M->w_outd.p, nq * kdev * 4, hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(hipStreamSynchronize(s));
-    if (by) { P->by_id_stats[0] = nq; P->by_id_stats[1] = by_stat[0]; P->by_id_stats[2] = by_stat[1]; }
+    if (rec) { P->recommend_stats[0] = nq; P->recommend_stats[1] = rec->total; P->recommend_stats[2] = by_stat[0]; P->recommend_stats[3] = kdev; }
+    else if (by) { P->by_id_stats[0] = nq; P->by_id_stats[1] = by_stat[0]; P->by_id_stats[2] = by_stat[1]; }
     for (size_t b = 0; b < nq; ++b) {
         const size_t kb = ks ? ks[b] : k;
         const size_t c = std::min<size_t>(cnt[b], kb);                 // per-query k: a prefix of the batch-wide result
@@ -656,15 +661,21 @@ int multi_search_host(vdb_flat_index* P, const float* queries, size_t nq, size_t
 // Search by stored id.  The row of an id lives on one shard: every shard gathers the rows of ITS query ids on its own device
 // (kernels_by_id.hip) and sends the block to devices[0] device-to-device, where one more gather puts every vector at its query's
 // place in the home query block.  No vector byte passes through host memory: row numbers and ids go up, results come down.
+// Recommend (rec) stages one row per EXAMPLE in the same way -- the ne = rec->total ids of all requests, in array order -- and
+// instead of the last gather the fold kernel runs on devices[0] over the stage (ld = dim, each example's place as its row number):
+// the fold order is the request's list order wherever the rows live.
 int multi_search_by_id(vdb_flat_index* P, const uint64_t* query_ids, size_t nq, const size_t* ks, size_t k, const uint64_t* id_mask,
-                       size_t mask_bits, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts, const vdb_meta_mask* cm) {
+                       size_t mask_bits, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts, const vdb_meta_mask* cm,
+                       const RecommendReq* rec) {
     vdb_multi* M = P->multi;
+    const size_t ne = rec ? rec->total : nq;                           // staged rows: one per query id, or one per example
     size_t kmax = k;
     if (ks) { kmax = 0; for (size_t b = 0; b < nq; ++b) kmax = std::max(kmax, ks[b]); }
     if (kmax > kstride) return fail(VDB_ERR_INVALID_ARGUMENT, "kstride %zu smaller than the largest k %zu", kstride, kmax);
     if (kmax && nq && (!out_ids || !out_dists)) return fail(VDB_ERR_INVALID_ARGUMENT, "null output");
     std::lock_guard<std::mutex> lk(P->mu);
-    memset(P->by_id_stats, 0, sizeof(P->by_id_stats));
+    if (rec) memset(P->recommend_stats, 0, sizeof(P->recommend_stats));
+    else memset(P->by_id_stats, 0, sizeof(P->by_id_stats));
     if (nq == 0) return VDB_OK;
     if (nq > 0x3fffffffull) return fail(VDB_ERR_INVALID_ARGUMENT, "batch too large");
     int rc;
@@ -672,10 +683,10 @@ int multi_search_by_id(vdb_flat_index* P, const uint64_t* query_ids, size_t nq, 
     for (auto* c : M->sh) if ((rc = vdb_flat_flush(c))) return rc;
     HIP_TRY(hipSetDevice(M->home));
     // id -> (shard, row); an id on no shard fails the batch
-    std::vector<int> shard_of(nq, -1);
-    std::vector<uint32_t> row_of(nq, 0xffffffffu);
-    std::vector<size_t> qdim(nq, 0);
-    for (size_t b = 0; b < nq; ++b) {
+    std::vector<int> shard_of(ne, -1);
+    std::vector<uint32_t> row_of(ne, 0xffffffffu);
+    std::vector<size_t> qdim(ne, 0);
+    for (size_t b = 0; b < ne; ++b) {
         for (int g = 0; g < M->G && shard_of[b] < 0; ++g) {
             Index* c = M->sh[g];
             std::lock_guard<std::mutex> cg(c->mu);
@@ -688,7 +699,7 @@ int multi_search_by_id(vdb_flat_index* P, const uint64_t* query_ids, size_t nq, 
     }
     // a vector that could not be searched with fails the batch as that search would: the first shard (lowest index) that objects
     size_t checked = ~(size_t)0;
-    for (size_t b = 0; b < nq; ++b) {
+    for (size_t b = 0; b < ne; ++b) {
         if (qdim[b] == checked) continue;
         for (auto* c : M->sh) {
             std::lock_guard<std::mutex> cg(c->mu);
@@ -700,24 +711,24 @@ int multi_search_by_id(vdb_flat_index* P, const uint64_t* query_ids, size_t nq, 
     // the shards' blocks lie side by side in the staging buffer, shard 0's first
     std::vector<std::vector<uint32_t>> rows_g((size_t)M->G);
     std::vector<size_t> off_g((size_t)M->G + 1, 0);
-    std::vector<uint32_t> place(nq);
-    for (size_t b = 0; b < nq; ++b) {
+    std::vector<uint32_t> place(ne);
+    for (size_t b = 0; b < ne; ++b) {
         if (row_of[b] == 0xffffffffu) return fail(VDB_ERR_DEVICE, "internal error: id %llu has no device row", (unsigned long long)query_ids[b]);
         ++off_g[(size_t)shard_of[b] + 1];
     }
     for (int g = 0; g < M->G; ++g) { rows_g[g].reserve(off_g[g + 1]); off_g[g + 1] += off_g[g]; }
-    for (size_t b = 0; b < nq; ++b) {
+    for (size_t b = 0; b < ne; ++b) {
         const int g = shard_of[b];
         place[b] = (uint32_t)(off_g[g] + rows_g[g].size());
         rows_g[g].push_back(row_of[b]);
     }
     const size_t len = multi_len(P);
     const size_t kcut = std::min(kmax, std::max<size_t>(len, 1));      // k is clamped to len BEFORE the + 1: k = SIZE_MAX cannot wrap
-    const size_t kdev = std::min(kcut + 1, len);
+    const size_t kdev = std::min(kcut + (rec ? rec->mmax : 1), len);
     hipStream_t s = M->ps[0].stream;
     if ((rc = M->w_qin.ensure(nq * dim))) return rc;
-    if ((rc = M->w_gstage.ensure(nq * dim))) return rc;
-    if ((rc = M->w_place.ensure(nq))) return rc;
+    if ((rc = M->w_gstage.ensure(ne * dim))) return rc;
+    if (!rec && (rc = M->w_place.ensure(nq))) return rc;
     for (auto& p : M->ps) { p.rc = VDB_OK; p.msg.clear(); }
     M->gang.run([&](int g) {
         auto& p = M->ps[g];
@@ -744,6 +755,13 @@ int multi_search_by_id(vdb_flat_index* P, const uint64_t* query_ids, size_t nq, 
     });
     HIP_TRY(hipSetDevice(M->home));
     if ((rc = first_error(M))) return rc;
+    if (rec) {
+        vdb::RecommendLists rl{};
+        if ((rc = recommend_stage(M->w_rec, *rec, nq, place.data(), s, &rl))) return rc;
+        vdb::launch_fold_examples(M->w_gstage.p, (uint32_t)dim, (uint32_t)dim, (uint32_t)ne, rl, (uint32_t)nq, M->w_qin.p, s);
+        HIP_TRY(hipGetLastError());
+        return finish_host(P, nq, dim, ks, k, kdev, id_mask, mask_bits, cm, kstride, out_ids, out_dists, out_counts, nullptr, kcut, rec, &rl);
+    }
     HIP_TRY(hipMemcpyAsync(M->w_place.p, place.data(), nq * 4, hipMemcpyHostToDevice, s));
     vdb::launch_gather_rows(M->w_gstage.p, (uint32_t)dim, (uint32_t)dim, (uint32_t)nq, M->w_place.p, (uint32_t)nq, M->w_qin.p, s);
     HIP_TRY(hipGetLastError());

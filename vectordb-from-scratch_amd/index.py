@@ -352,6 +352,66 @@ class GpuFlatIndex(Index):
             _raise(rc)
         return [int(x) for x in out]
 
+    # ---- recommend from positive and negative stored ids (include/vdb_flat.h vdb_flat_recommend_batch; no reference counterpart)
+    def recommend_batch(self, positive, negative, k, id_mask=None, mask_bits=0, compiled_mask=None):
+        """"More like these, less like those": request b is the average ap of the stored vectors positive[b] (at least one id)
+        and, when negative[b] is not empty, ap + (ap - an) with the average an of those; the answer is what
+        search_batch_arrays returns for that vector with k + the number of examples, every example removed, cut to k.  The
+        fold runs on the device in f32, left to right in list order (include/vdb_flat.h has the exact arithmetic); the
+        vectors never leave it.  positive, negative: sequences of id sequences of the same length (negative None: no
+        negatives at all); k an int or a per-request array.  Returns the arrays of search_batch_arrays.  An id that is not
+        stored raises VectorNotFound for the whole batch."""
+        if compiled_mask is not None and id_mask is not None:
+            raise ValueError("pass id_mask or compiled_mask, not both")
+        nq = len(positive)
+        if negative is None:
+            negative = [()] * nq
+        if len(negative) != nq:
+            raise ValueError(f"{nq} positive lists but {len(negative)} negative lists")
+        pos = [np.asarray(p, dtype=np.uint64).reshape(-1) for p in positive]
+        neg = [np.asarray(x, dtype=np.uint64).reshape(-1) for x in negative]
+        ex = np.ascontiguousarray(np.concatenate([a for pn in zip(pos, neg) for a in pn] + [np.zeros(0, dtype=np.uint64)]))
+        offsets = np.zeros(nq + 1, dtype=np.uintp)
+        offsets[1:] = np.cumsum([p.size + x.size for p, x in zip(pos, neg)], dtype=np.uintp)
+        n_pos = np.asarray([p.size for p in pos], dtype=np.uint32)
+        if np.isscalar(k):
+            ks_ptr, kscalar, kmax = None, int(k), int(k)
+        else:
+            ks = np.ascontiguousarray(k, dtype=np.uintp)
+            if ks.shape != (nq,):
+                raise ValueError(f"k must be a scalar or hold one value per request ({nq}), not {ks.shape}")
+            ks_ptr = ks.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t))
+            kscalar, kmax = 0, int(ks.max()) if ks.size else 0
+        kstride = max(kmax, 1)
+        out_ids = np.zeros((nq, kstride), dtype=np.uint64)
+        out_d = np.zeros((nq, kstride), dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uintp)
+        szp = ctypes.POINTER(ctypes.c_size_t)
+        head = (self._h, _u64p(ex), offsets.ctypes.data_as(szp), n_pos.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), nq, ks_ptr, kscalar)
+        tail = (kstride, _u64p(out_ids), _fp(out_d), counts.ctypes.data_as(szp))
+        if compiled_mask is not None:
+            rc = self._L.vdb_flat_recommend_batch_filtered(*head, compiled_mask.handle, *tail)
+        else:
+            mask_ptr = None
+            if id_mask is not None:
+                m = np.ascontiguousarray(id_mask, dtype=np.uint64)
+                mask_ptr = _u64p(m)
+            rc = self._L.vdb_flat_recommend_batch(*head, mask_ptr, int(mask_bits), *tail)
+        if rc == _ffi.ERR_NOT_FOUND:
+            raise VectorNotFound(int(_ffi.last_error()[0].rsplit(": ", 1)[-1]))
+        if rc:
+            _raise(rc)
+        return out_ids, out_d, counts
+
+    def recommend_stats(self):
+        """The last recommend_batch: [0] requests, [1] example rows folded, [2] entries struck in total (those in front of the
+        cut of the batch-wide list), [3] the depth the search ran at: min(max(k), len) + the longest request, at most len."""
+        out = (ctypes.c_uint64 * 4)()
+        rc = self._L.vdb_flat_recommend_stats(self._h, out)
+        if rc:
+            _raise(rc)
+        return [int(x) for x in out]
+
     # ---- one nearest row per group (include/vdb_flat.h vdb_flat_search_batch_distinct; no reference counterpart)
     def search_batch_distinct(self, queries, k, table, slot, id_mask=None, mask_bits=0, compiled_mask=None):
         """The k nearest GROUPS, each represented by its nearest row: the full ranking of the eligible rows walked from the

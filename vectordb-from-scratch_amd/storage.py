@@ -693,6 +693,45 @@ class VectorStore:
             out_ids, dists, counts = self._index.search_batch_by_id(q, int(k), id_mask=mask, mask_bits=bits)
         return [self._map([(int(out_ids[b, i]), dists[b, i]) for i in range(int(counts[b]))]) for b in range(len(internal))]
 
+    # ---- "more like these, less like those" (GpuFlatIndex.recommend_batch; no reference counterpart)
+    def recommend(self, positive, negative, k, flt=None):
+        """The k stored vectors nearest to the average of the stored vectors `positive`, pushed away from the average of
+        `negative` (may be empty), the examples themselves left out, nearest first."""
+        return self.recommend_batch([(positive, negative)], k, flt)[0]
+
+    def recommend_batch(self, requests, k, flt=None):
+        """recommend for several (positive ids, negative ids) pairs in one device call; the vectors never leave the GPU.  An
+        unknown id raises VectorNotFound.  flt is a PRE-filter, as in search_similar_batch: a filtered-out id may still be an
+        example, it is simply in nobody's answer."""
+        if not isinstance(self._index, GpuFlatIndex):
+            raise ValueError("recommend needs a GpuFlatIndex")
+
+        def internal(ids):
+            out = []
+            for id in ids:
+                i = self._internal_of(id)
+                if i is None:
+                    raise VectorNotFound(id)
+                out.append(i)
+            return out
+
+        pos, neg = [], []
+        for p, n in requests:
+            pos.append(internal(p))
+            neg.append(internal(n))
+        if not pos:
+            return []
+        cm = self.compile_filter_device(flt) if flt is not None and self._table is not None else None
+        if cm is not None:
+            try:
+                out_ids, dists, counts = self._index.recommend_batch(pos, neg, int(k), compiled_mask=cm)
+            finally:
+                cm.release()
+        else:
+            mask, bits = self.compile_filter(flt) if flt is not None else (None, 0)
+            out_ids, dists, counts = self._index.recommend_batch(pos, neg, int(k), id_mask=mask, mask_bits=bits)
+        return [self._map([(int(out_ids[b, i]), dists[b, i]) for i in range(int(counts[b]))]) for b in range(len(pos))]
+
     # ---- "the k nearest documents" (GpuFlatIndex.search_batch_distinct; no reference counterpart)
     def search_distinct(self, query, k, field, flt=None):
         """The k nearest GROUPS of rows that share a value of metadata field `field`, each represented by its nearest row,
