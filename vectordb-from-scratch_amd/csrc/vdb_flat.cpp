@@ -174,11 +174,7 @@ int vdb_flat_add_bulk_device(vdb_flat_index* ix, const uint64_t* ids, uint64_t f
     int rc = set_device(ix);
     if (rc) return rc;
     if (ix->n_rows() + n > 0xfffffff0ull) return fail(VDB_ERR_INVALID_ARGUMENT, "more than 2^32 rows per index");
-    if (ix->n_live == 0 && ix->misfits.empty()) {
-        if (ix->dim != dim) reset_rows(ix);
-        ix->dim = (uint32_t)dim;
-        ix->ld = round_up(ix->dim, vdb::KSTAGE);
-    }
+    adopt_dim(ix, dim);
     if (dim != ix->dim) return fail_dim(ix->dim, dim);   // the device bulk path requires the index dimension
     // overwrite semantics for ids already present
     for (size_t i = 0; i < n; ++i) {
@@ -313,11 +309,7 @@ int vdb_flat_reserve(vdb_flat_index* ix, size_t rows, size_t dim) {
     if (in_flight(ix)) return refuse_in_flight();
     int rc = set_device(ix);
     if (rc) return rc;
-    if (ix->n_live == 0 && ix->misfits.empty()) {
-        if (ix->dim != dim) reset_rows(ix);
-        ix->dim = (uint32_t)dim;
-        ix->ld = round_up(ix->dim, vdb::KSTAGE);
-    }
+    adopt_dim(ix, dim);
     if (dim != ix->dim) return fail_dim(ix->dim, dim);
     if (rows > 0xfffffff0ull) return fail(VDB_ERR_INVALID_ARGUMENT, "more than 2^32 rows per index");
     if ((rc = flush(ix))) return rc;
@@ -595,54 +587,82 @@ int vdbi::recommend_stage(RecommendWs& W, const RecommendReq& r, size_t nq, cons
     return VDB_OK;
 }
 
-int vdbi::recommend_strike(RecommendWs& W, const vdb::RecommendLists& L, size_t nq, uint64_t* d_ids, float* d_dists, uint32_t* d_counts,
-                           size_t kdev, size_t kcut, hipStream_t s, uint32_t* struck) {
-    vdb::StrikeSetParams sp{d_ids, d_dists, d_counts, (uint32_t)kdev, L.offs, L.ids, (uint32_t)kcut, W.stat.p};
-    vdb::launch_strike_set(sp, (uint32_t)nq, s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(struck, W.stat.p, 4, hipMemcpyDeviceToHost, s));
+int vdbi::strike_stage(StrikeBufs B, const HostSearch& r, hipStream_t s) {
+    if (r.rec) return VDB_OK;                                      // (recommend_stage has sent the lists and zeroed the counter)
+    int rc;
+    if ((rc = B.selfid.ensure(r.nq))) return rc;
+    if ((rc = B.bystat.ensure(2))) return rc;
+    HIP_TRY(hipMemcpyAsync(B.selfid.p, r.by, r.nq * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(B.bystat.p, 0, 8, s));
+    return VDB_OK;
+}
+
+int vdbi::strike_copy_out(Index* H, const HostSearch& r, StrikeBufs B, const vdb::RecommendLists& L, const Lists& found, size_t kcut, hipStream_t s) {
+    uint64_t* d_ids = const_cast<uint64_t*>(found.ids);            // (the search's own output buffers: the strike rewrites them in place)
+    float* d_dists = const_cast<float*>(found.dists);
+    uint32_t* d_counts = const_cast<uint32_t*>(found.counts);
+    uint32_t stat[2] = {0, 0};                                     // struck | cut, valid after the copy-out's synchronisation
+    if (r.rec) {
+        vdb::StrikeSetParams sp{d_ids, d_dists, d_counts, (uint32_t)found.stride, L.offs, L.ids, (uint32_t)kcut, B.rec.stat.p};
+        vdb::launch_strike_set(sp, (uint32_t)r.nq, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(stat, B.rec.stat.p, 4, hipMemcpyDeviceToHost, s));
+    } else {
+        vdb::StrikeSelfParams sp{d_ids, d_dists, d_counts, (uint32_t)found.stride, B.selfid.p, (uint32_t)kcut, B.bystat.p};
+        vdb::launch_strike_self(sp, (uint32_t)r.nq, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(stat, B.bystat.p, 8, hipMemcpyDeviceToHost, s));
+    }
+    int rc = copy_out(found, r, s);
+    if (rc) return rc;
+    if (r.rec) { H->recommend_stats[0] = r.nq; H->recommend_stats[1] = r.rec->total; H->recommend_stats[2] = stat[0]; H->recommend_stats[3] = found.stride; }
+    else { H->by_id_stats[0] = r.nq; H->by_id_stats[1] = stat[0]; H->by_id_stats[2] = stat[1]; }
+    return VDB_OK;
+}
+
+vdbi::MaskSrc vdbi::mask_src(const HostSearch& r) {
+    return MaskSrc{r.id_mask, r.mask_bits, r.cm ? r.cm->d_words.p : nullptr, r.cm ? (hipEvent_t)r.cm->done : nullptr, r.dm};
+}
+
+// A compiled mask serves a search on the device it lives on.
+static int compiled_mask_check(const vdb_meta_mask* cm, int dev) {
+    if (cm->device != dev) return fail(VDB_ERR_INVALID_ARGUMENT, "the compiled mask lives on device %d, the index on device %d", cm->device, dev);
     return VDB_OK;
 }
 
 // vdb_flat_search_batch and vdb_flat_search_batch_filtered: the id mask comes from the host (id_mask, uploaded here) or is a
 // compiled one already in HBM (cm: the stream is ordered behind its event, nothing is uploaded); everything below is the same.
-// dm (vdb_internal::search_batch_device_mask): mask_bits bits at a device address, written on the handle's own stream.
-// by (vdb_flat_search_batch_by_id; `queries` and `dim` are then unused): the queries are the STORED vectors of these ids.  Their
+// r.dm (vdb_internal::search_batch_device_mask): mask_bits bits at a device address, written on the handle's own stream.
+// r.by (vdb_flat_search_batch_by_id; `queries` and `dim` are then unused): the queries are the STORED vectors of these ids.  Their
 // device rows are gathered into the query block on the device, the search runs with one result more, and the entry whose id
 // equals the query's own is struck from each list on the device before the usual copy-out.
-// rec (vdb_flat_recommend_batch; `by` is then rec->ids): the queries are FOLDS of stored vectors.  All examples resolve to device
+// r.rec (vdb_flat_recommend_batch; `by` is then rec->ids): the queries are FOLDS of stored vectors.  All examples resolve to device
 // rows as by-id's queries do, the fold kernel writes the query block straight from d_rows, the search runs with as many results
 // more as the longest request has examples, and the set strike removes every example from its request's list.
-static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks,
-                             size_t k, const uint64_t* id_mask, size_t mask_bits, const vdb_meta_mask* cm, size_t kstride,
-                             uint64_t* out_ids, float* out_dists, size_t* out_counts, const uint64_t* dm = nullptr,
-                             const uint64_t* by = nullptr, const RecommendReq* rec = nullptr) {
+static int search_batch_host(vdb_flat_index* ix, HostSearch r) {
     return guarded([&]() -> int {
-    if (!ix || (nq && ((!queries && !by) || !out_counts))) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
-    if (cm) {
-        const int dev = ix->multi ? multi_home(ix) : ix->device;
-        if (cm->device != dev) return fail(VDB_ERR_INVALID_ARGUMENT, "the compiled mask lives on device %d, the index on device %d", cm->device, dev);
-        mask_bits = cm->bits;
+    const size_t nq = r.nq;
+    const uint64_t* const by = r.by;
+    const RecommendReq* const rec = r.rec;
+    if (!ix || (nq && ((!r.queries && !by) || !r.counts))) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    int rc;
+    if (r.cm) {
+        if ((rc = compiled_mask_check(r.cm, ix->multi ? multi_home(ix) : ix->device))) return rc;
+        r.mask_bits = r.cm->bits;
     }
     if (ix->multi) {
-        if (dm) return refuse_multi("a search under a raw device mask");
-        if (by) return multi_search_by_id(ix, by, nq, ks, k, id_mask, mask_bits, kstride, out_ids, out_dists, out_counts, cm, rec);
-        return multi_search_host(ix, queries, nq, dim, ks, k, id_mask, mask_bits, kstride, out_ids, out_dists, out_counts, cm);
+        if (r.dm) return refuse_multi("a search under a raw device mask");
+        return by ? multi_search_by_id(ix, r) : multi_search_host(ix, r);
     }
-    size_t kmax = k;
-    if (ks) {
-        kmax = 0;
-        for (size_t b = 0; b < nq; ++b) kmax = std::max(kmax, ks[b]);
-    }
-    if (kmax > kstride) return fail(VDB_ERR_INVALID_ARGUMENT, "kstride %zu smaller than the largest k %zu", kstride, kmax);
-    if (kmax && nq && (!out_ids || !out_dists)) return fail(VDB_ERR_INVALID_ARGUMENT, "null output");
+    size_t kmax;
+    if ((rc = batch_shape(r, &kmax))) return rc;
     std::lock_guard<std::mutex> g(ix->mu);
     if (in_flight(ix)) return refuse_in_flight();
-    int rc = set_device(ix);
-    if (rc) return rc;
+    if ((rc = set_device(ix))) return rc;
     if (rec) memset(ix->recommend_stats, 0, sizeof(ix->recommend_stats));
     else if (by) memset(ix->by_id_stats, 0, sizeof(ix->by_id_stats));
     if (nq == 0) return VDB_OK;
+    size_t dim = r.dim;
     std::vector<uint32_t> self_rows;
     if (by) {
         // staged adds and removes first: an id resolves to what the search below sees
@@ -659,95 +679,65 @@ static int search_batch_host(vdb_flat_index* ix, const float* queries, size_t nq
     hipStream_t s = ix->stream;
     // Small index, a few queries (BASELINE configs[0]: Index::search itself, one query): queries and results go through MAPPED
     // host memory -- the two kernels of the direct path read and write it in place, nothing is copied by the runtime
-    if (direct_eligible(ix, ix->n_rows(), nq, kdev) && ix->misfits.empty() && dim == ix->dim && !id_mask && !cm && !dm && !by) {
+    if (direct_eligible(ix, ix->n_rows(), nq, kdev) && ix->misfits.empty() && dim == ix->dim && !r.id_mask && !r.cm && !r.dm && !by) {
         const size_t qb = nq * dim * sizeof(float), ib = nq * kdev * sizeof(uint64_t), db = nq * kdev * sizeof(float), cb = nq * sizeof(uint32_t);
         const size_t o_i = (qb + 15) & ~(size_t)15, o_d = o_i + ib, o_c = o_d + ((db + 15) & ~(size_t)15);
         if ((rc = ensure_host_io(ix, o_c + cb))) return rc;
         Workspace* W = ix->cur;
-        memcpy(W->h_io, queries, qb);
+        memcpy(W->h_io, r.queries, qb);
         rc = search_device(ix, reinterpret_cast<const float*>(W->h_io.d), nq, dim, kdev, nullptr, 0, reinterpret_cast<uint64_t*>(W->h_io.d + o_i),
                            reinterpret_cast<float*>(W->h_io.d + o_d), reinterpret_cast<uint32_t*>(W->h_io.d + o_c), nullptr);
         if (rc) return rc;
         W = &ix->wsv[0];                                           // (search_device leaves ix->cur at workspace 0, the one it used)
-        const uint64_t* h_ids = reinterpret_cast<const uint64_t*>(W->h_io + o_i);
-        const float* h_ds = reinterpret_cast<const float*>(W->h_io + o_d);
-        const uint32_t* h_cnt = reinterpret_cast<const uint32_t*>(W->h_io + o_c);
-        for (size_t b = 0; b < nq; ++b) {
-            const size_t kb = ks ? ks[b] : k;
-            const size_t c = std::min<size_t>(h_cnt[b], kb);       // per-query k: a prefix of the batch-wide result
-            out_counts[b] = c;
-            for (size_t i = 0; i < c; ++i) { out_ids[b * kstride + i] = h_ids[b * kdev + i]; out_dists[b * kstride + i] = h_ds[b * kdev + i]; }
-        }
+        emit_lists(Lists{reinterpret_cast<const uint64_t*>(W->h_io + o_i), reinterpret_cast<const float*>(W->h_io + o_d),
+                         reinterpret_cast<const uint32_t*>(W->h_io + o_c), nullptr, kdev}, r);
         return VDB_OK;
     }
-    if ((rc = ix->cur->w_qin.ensure(nq * std::max<size_t>(dim, 1)))) return rc;
-    if ((rc = ix->cur->w_outi.ensure(nq * std::max<size_t>(kdev, 1)))) return rc;
-    if ((rc = ix->cur->w_outd.ensure(nq * std::max<size_t>(kdev, 1)))) return rc;
-    if ((rc = ix->cur->w_outc.ensure(nq))) return rc;
+    Workspace* W = ix->cur;
+    if ((rc = W->w_qin.ensure(nq * std::max<size_t>(dim, 1)))) return rc;
+    if ((rc = W->w_outi.ensure(nq * std::max<size_t>(kdev, 1)))) return rc;
+    if ((rc = W->w_outd.ensure(nq * std::max<size_t>(kdev, 1)))) return rc;
+    if ((rc = W->w_outc.ensure(nq))) return rc;
     vdb::RecommendLists rl{};
+    const StrikeBufs strike{W->w_selfid, W->w_bystat, W->w_rec};
     if (rec) {
         // only the lists go up; the fold reads the examples where they are stored
-        if ((rc = recommend_stage(ix->cur->w_rec, *rec, nq, self_rows.data(), s, &rl))) return rc;
-        vdb::launch_fold_examples(ix->d_rows, ix->ld, ix->dim, ix->n_uploaded, rl, (uint32_t)nq, ix->cur->w_qin.p, s);
+        if ((rc = recommend_stage(W->w_rec, *rec, nq, self_rows.data(), s, &rl))) return rc;
+        vdb::launch_fold_examples(ix->d_rows, ix->ld, ix->dim, ix->n_uploaded, rl, (uint32_t)nq, W->w_qin.p, s);
         HIP_TRY(hipGetLastError());
     } else if (by) {
         // only the row numbers and the ids go up; the vectors never leave HBM
-        if ((rc = ix->cur->w_selfrow.ensure(nq))) return rc;
-        if ((rc = ix->cur->w_selfid.ensure(nq))) return rc;
-        if ((rc = ix->cur->w_bystat.ensure(2))) return rc;
-        HIP_TRY(hipMemcpyAsync(ix->cur->w_selfrow.p, self_rows.data(), nq * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(ix->cur->w_selfid.p, by, nq * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemsetAsync(ix->cur->w_bystat.p, 0, 8, s));
-        vdb::launch_gather_rows(ix->d_rows, ix->ld, ix->dim, ix->n_uploaded, ix->cur->w_selfrow.p, (uint32_t)nq, ix->cur->w_qin.p, s);
+        if ((rc = W->w_selfrow.ensure(nq))) return rc;
+        HIP_TRY(hipMemcpyAsync(W->w_selfrow.p, self_rows.data(), nq * 4, hipMemcpyHostToDevice, s));
+        if ((rc = strike_stage(strike, r, s))) return rc;
+        vdb::launch_gather_rows(ix->d_rows, ix->ld, ix->dim, ix->n_uploaded, W->w_selfrow.p, (uint32_t)nq, W->w_qin.p, s);
         HIP_TRY(hipGetLastError());
-    } else if (dim) HIP_TRY(hipMemcpyAsync(ix->cur->w_qin.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
-    const uint64_t* d_mask = nullptr;
-    if (id_mask) {
-        size_t words = (mask_bits + 63) / 64;
-        if ((rc = ix->cur->w_mask_ids.ensure(std::max<size_t>(words, 1)))) return rc;
-        if (words) HIP_TRY(hipMemcpyAsync(ix->cur->w_mask_ids.p, id_mask, words * 8, hipMemcpyHostToDevice, s));
-        d_mask = ix->cur->w_mask_ids.p;
-    } else if (cm) {
-        HIP_TRY(hipStreamWaitEvent(s, cm->done, 0));
-        d_mask = cm->d_words;
-    } else if (dm) {
-        d_mask = dm;
-    }
-    rc = search_device(ix, ix->cur->w_qin.p, nq, dim, kdev, d_mask, mask_bits, ix->cur->w_outi.p, ix->cur->w_outd.p, ix->cur->w_outc.p,
-                       nullptr);
-    if (rc) return rc;
-    uint32_t by_stat[2] = {0, 0};
-    if (rec) {
-        if ((rc = recommend_strike(ix->cur->w_rec, rl, nq, ix->cur->w_outi.p, ix->cur->w_outd.p, ix->cur->w_outc.p, kdev, kcut, s, by_stat))) return rc;
-    } else if (by) {
-        vdb::StrikeSelfParams sp{ix->cur->w_outi.p, ix->cur->w_outd.p, ix->cur->w_outc.p, (uint32_t)kdev, ix->cur->w_selfid.p, (uint32_t)kcut,
-                                 ix->cur->w_bystat.p};
-        vdb::launch_strike_self(sp, (uint32_t)nq, s);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(by_stat, ix->cur->w_bystat.p, 8, hipMemcpyDeviceToHost, s));
-    }
-    std::vector<uint32_t> cnt(nq);
-    std::vector<uint64_t> ids(nq * std::max<size_t>(kdev, 1));
-    std::vector<float> ds(nq * std::max<size_t>(kdev, 1));
-    HIP_TRY(hipMemcpyAsync(cnt.data(), ix->cur->w_outc.p, nq * 4, hipMemcpyDeviceToHost, s));
-    if (kdev) {
-        HIP_TRY(hipMemcpyAsync(ids.data(), ix->cur->w_outi.p, nq * kdev * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(ds.data(), ix->cur->w_outd.p, nq * kdev * 4, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    if (rec) { ix->recommend_stats[0] = nq; ix->recommend_stats[1] = rec->total; ix->recommend_stats[2] = by_stat[0]; ix->recommend_stats[3] = kdev; }
-    else if (by) { ix->by_id_stats[0] = nq; ix->by_id_stats[1] = by_stat[0]; ix->by_id_stats[2] = by_stat[1]; }
-    for (size_t b = 0; b < nq; ++b) {
-        size_t kb = ks ? ks[b] : k;
-        size_t c = std::min<size_t>(cnt[b], kb);   // per-query k: a prefix of the batch-wide result
-        out_counts[b] = c;
-        for (size_t i = 0; i < c; ++i) {
-            out_ids[b * kstride + i] = ids[b * kdev + i];
-            out_dists[b * kstride + i] = ds[b * kdev + i];
-        }
-    }
-    return VDB_OK;
+    } else if (dim) HIP_TRY(hipMemcpyAsync(W->w_qin.p, r.queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
+    const uint64_t* d_mask;
+    if ((rc = stage_mask(W->w_mask_ids, mask_src(r), s, &d_mask))) return rc;
+    if ((rc = search_device(ix, W->w_qin.p, nq, dim, kdev, d_mask, r.mask_bits, W->w_outi.p, W->w_outd.p, W->w_outc.p, nullptr))) return rc;
+    const Lists found{W->w_outi.p, W->w_outd.p, W->w_outc.p, nullptr, kdev};
+    if (by) return strike_copy_out(ix, r, strike, rl, found, kcut, s);
+    return copy_out(found, r, s);
     });
+}
+
+// What every host-pointer shim fills the same way; then the mask in the form the shim got it, and the stored ids the queries
+// come from (an empty batch may come without an id array).
+static HostSearch host_search(const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k, size_t kstride, uint64_t* out_ids,
+                              float* out_dists, size_t* out_counts) {
+    HostSearch r;
+    r.nq = nq; r.ks = ks; r.k = k; r.kstride = kstride;
+    r.ids = out_ids; r.dists = out_dists; r.counts = out_counts;
+    r.queries = queries; r.dim = dim;
+    return r;
+}
+static HostSearch under(HostSearch r, const uint64_t* id_mask, size_t mask_bits) { r.id_mask = id_mask; r.mask_bits = mask_bits; return r; }
+static HostSearch under(HostSearch r, const vdb_meta_mask* cm) { r.cm = cm; return r; }
+static HostSearch of_ids(HostSearch r, const uint64_t* ids, const RecommendReq* rec = nullptr) {
+    static const uint64_t none = 0;
+    r.by = ids ? ids : &none; r.rec = rec;
+    return r;
 }
 
 extern "C" {
@@ -755,24 +745,22 @@ extern "C" {
 int vdb_flat_search_batch(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks,
                           size_t k, const uint64_t* id_mask, size_t mask_bits, size_t kstride, uint64_t* out_ids,
                           float* out_dists, size_t* out_counts) {
-    return search_batch_host(ix, queries, nq, dim, ks, k, id_mask, mask_bits, nullptr, kstride, out_ids, out_dists, out_counts);
+    return search_batch_host(ix, under(host_search(queries, nq, dim, ks, k, kstride, out_ids, out_dists, out_counts), id_mask, mask_bits));
 }
 
 int vdb_flat_search_batch_filtered(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k,
                                    const vdb_meta_mask* mask, size_t kstride, uint64_t* out_ids, float* out_dists,
                                    size_t* out_counts) {
     if (!mask) return fail(VDB_ERR_INVALID_ARGUMENT, "null mask");
-    return search_batch_host(ix, queries, nq, dim, ks, k, nullptr, 0, mask, kstride, out_ids, out_dists, out_counts);
+    return search_batch_host(ix, under(host_search(queries, nq, dim, ks, k, kstride, out_ids, out_dists, out_counts), mask));
 }
 
-// ---- search by stored id (no reference counterpart; search_batch_host with `by`)
-static const uint64_t kNoIds = 0;                                   // an empty batch may come without an id array
+// ---- search by stored id (no reference counterpart; search_batch_host with r.by)
 int vdb_flat_search_batch_by_id(vdb_flat_index* ix, const uint64_t* query_ids, size_t nq, const size_t* ks, size_t k,
                                 const uint64_t* id_mask, size_t mask_bits, size_t kstride, uint64_t* out_ids, float* out_dists,
                                 size_t* out_counts) {
     if (nq && !query_ids) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
-    return search_batch_host(ix, nullptr, nq, 0, ks, k, id_mask, mask_bits, nullptr, kstride, out_ids, out_dists, out_counts, nullptr,
-                             query_ids ? query_ids : &kNoIds);
+    return search_batch_host(ix, under(of_ids(host_search(nullptr, nq, 0, ks, k, kstride, out_ids, out_dists, out_counts), query_ids), id_mask, mask_bits));
 }
 
 int vdb_flat_search_batch_by_id_filtered(vdb_flat_index* ix, const uint64_t* query_ids, size_t nq, const size_t* ks, size_t k,
@@ -780,8 +768,7 @@ int vdb_flat_search_batch_by_id_filtered(vdb_flat_index* ix, const uint64_t* que
                                          size_t* out_counts) {
     if (!mask) return fail(VDB_ERR_INVALID_ARGUMENT, "null mask");
     if (nq && !query_ids) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
-    return search_batch_host(ix, nullptr, nq, 0, ks, k, nullptr, 0, mask, kstride, out_ids, out_dists, out_counts, nullptr,
-                             query_ids ? query_ids : &kNoIds);
+    return search_batch_host(ix, under(of_ids(host_search(nullptr, nq, 0, ks, k, kstride, out_ids, out_dists, out_counts), query_ids), mask));
 }
 
 int vdb_flat_by_id_stats(const vdb_flat_index* ix, uint64_t out[4]) {
@@ -790,26 +777,24 @@ int vdb_flat_by_id_stats(const vdb_flat_index* ix, uint64_t out[4]) {
     return VDB_OK;
 }
 
-// ---- recommend from positive and negative stored ids (no reference counterpart; search_batch_host with `rec`)
+// ---- recommend from positive and negative stored ids (no reference counterpart; search_batch_host with r.rec)
 int vdb_flat_recommend_batch(vdb_flat_index* ix, const uint64_t* example_ids, const size_t* offsets, const uint32_t* n_pos, size_t nq,
                              const size_t* ks, size_t k, const uint64_t* id_mask, size_t mask_bits, size_t kstride, uint64_t* out_ids,
                              float* out_dists, size_t* out_counts) {
-    RecommendReq r{example_ids, offsets, n_pos};
-    int rc = recommend_check(&r, nq);
+    RecommendReq rec{example_ids, offsets, n_pos};
+    int rc = recommend_check(&rec, nq);
     if (rc) return rc;
-    return search_batch_host(ix, nullptr, nq, 0, ks, k, id_mask, mask_bits, nullptr, kstride, out_ids, out_dists, out_counts, nullptr,
-                             example_ids ? example_ids : &kNoIds, &r);
+    return search_batch_host(ix, under(of_ids(host_search(nullptr, nq, 0, ks, k, kstride, out_ids, out_dists, out_counts), example_ids, &rec), id_mask, mask_bits));
 }
 
 int vdb_flat_recommend_batch_filtered(vdb_flat_index* ix, const uint64_t* example_ids, const size_t* offsets, const uint32_t* n_pos,
                                       size_t nq, const size_t* ks, size_t k, const vdb_meta_mask* mask, size_t kstride,
                                       uint64_t* out_ids, float* out_dists, size_t* out_counts) {
     if (!mask) return fail(VDB_ERR_INVALID_ARGUMENT, "null mask");
-    RecommendReq r{example_ids, offsets, n_pos};
-    int rc = recommend_check(&r, nq);
+    RecommendReq rec{example_ids, offsets, n_pos};
+    int rc = recommend_check(&rec, nq);
     if (rc) return rc;
-    return search_batch_host(ix, nullptr, nq, 0, ks, k, nullptr, 0, mask, kstride, out_ids, out_dists, out_counts, nullptr,
-                             example_ids ? example_ids : &kNoIds, &r);
+    return search_batch_host(ix, under(of_ids(host_search(nullptr, nq, 0, ks, k, kstride, out_ids, out_dists, out_counts), example_ids, &rec), mask));
 }
 
 int vdb_flat_recommend_stats(const vdb_flat_index* ix, uint64_t out[4]) {
@@ -826,18 +811,13 @@ size_t vdb_flat_distinct_depth(size_t k, size_t len, int stage) {
     return 0;
 }
 
-static int search_distinct_host(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k,
-                                vdb_meta_table* table, uint32_t slot, const uint64_t* id_mask, size_t mask_bits, const vdb_meta_mask* cm,
-                                size_t kstride, uint64_t* out_ids, float* out_dists, int32_t* out_codes, size_t* out_counts) {
+static int search_distinct_host(vdb_flat_index* ix, HostSearch r, vdb_meta_table* table, uint32_t slot) {
     return guarded([&]() -> int {
-    if (!ix || (nq && (!queries || !out_counts))) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
-    size_t kmax = k;
-    if (ks) {
-        kmax = 0;
-        for (size_t b = 0; b < nq; ++b) kmax = std::max(kmax, ks[b]);
-    }
-    if (kmax > kstride) return fail(VDB_ERR_INVALID_ARGUMENT, "kstride %zu smaller than the largest k %zu", kstride, kmax);
-    if (kmax && nq && (!out_ids || !out_dists)) return fail(VDB_ERR_INVALID_ARGUMENT, "null output");
+    const size_t nq = r.nq, dim = r.dim;
+    if (!ix || (nq && (!r.queries || !r.counts))) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    size_t kmax;
+    int rc;
+    if ((rc = batch_shape(r, &kmax))) return rc;
     std::lock_guard<std::mutex> g(ix->mu);                         // (a sharded parent's lock too: the shards are searched under it)
     if (!ix->multi && in_flight(ix)) return refuse_in_flight();
     memset(ix->distinct_stats, 0, sizeof(ix->distinct_stats));
@@ -846,19 +826,19 @@ static int search_distinct_host(vdb_flat_index* ix, const float* queries, size_t
     const int dev = ix->multi ? multi_home(ix) : ix->device;
     const size_t len = ix->multi ? multi_len(ix) : ix->n_live + ix->misfits.size();
     if (len == 0 || kmax == 0) {                                   // storage.rs:218-220: empty store -> Ok(vec![]) before any check
-        for (size_t b = 0; b < nq; ++b) out_counts[b] = 0;
+        for (size_t b = 0; b < nq; ++b) r.counts[b] = 0;
         return VDB_OK;
     }
     // every refusal below comes before any device search
-    int tdev = 0, rc;
+    int tdev = 0;
     if ((rc = meta_column_check(table, slot, &tdev))) return rc;
     if (kmax > vdb::DISTINCT_MAX_LIST) return fail(VDB_ERR_INVALID_ARGUMENT, "a search by group returns at most %u rows per query, not %zu", vdb::DISTINCT_MAX_LIST, kmax);
     if (tdev != dev) return fail(VDB_ERR_INVALID_ARGUMENT, "the metadata table lives on device %d, the index on device %d", tdev, dev);
     const uint64_t id_bound = ix->multi ? multi_id_bound(ix) : ix->id_bound;
     if (id_bound > (1ull << 32)) return fail(VDB_ERR_INVALID_ARGUMENT, "the index has held an id at or above 2^32: a metadata table cannot describe it");
-    if (cm) {
-        if (cm->device != dev) return fail(VDB_ERR_INVALID_ARGUMENT, "the compiled mask lives on device %d, the index on device %d", cm->device, dev);
-        mask_bits = cm->bits;
+    if (r.cm) {
+        if ((rc = compiled_mask_check(r.cm, dev))) return rc;
+        r.mask_bits = r.cm->bits;
     }
     if (nq > 0x3fffffffull) return fail(VDB_ERR_INVALID_ARGUMENT, "batch too large");
     HIP_TRY(hipSetDevice(dev));
@@ -868,8 +848,7 @@ static int search_distinct_host(vdb_flat_index* ix, const float* queries, size_t
     MetaColumn col;
     if ((rc = meta_column_acquire(table, slot, s, &col))) return rc;
     struct Release { vdb_meta_table* t; ~Release() { meta_column_release(t); } } release{table};
-    DistinctArgs a{queries, nq, dim, ks, k, kmax, len, col.d_codes, col.len, id_mask, mask_bits, cm, id_bound, (uint32_t)ix->n_cu,
-                   kstride, out_ids, out_dists, out_codes, out_counts};
+    DistinctArgs a{r, kmax, len, col.d_codes, col.len, id_bound, (uint32_t)ix->n_cu};
     DistinctSearch search;
     if (ix->multi)
         search = [&](const float* d_q, size_t n, size_t depth, const uint64_t* d_mask, size_t bits, uint64_t* oi, float* od, uint32_t* oc) {
@@ -886,15 +865,18 @@ static int search_distinct_host(vdb_flat_index* ix, const float* queries, size_t
 int vdb_flat_search_batch_distinct(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k,
                                    vdb_meta_table* table, uint32_t slot, const uint64_t* id_mask, size_t mask_bits, size_t kstride,
                                    uint64_t* out_ids, float* out_dists, int32_t* out_codes, size_t* out_counts) {
-    return search_distinct_host(ix, queries, nq, dim, ks, k, table, slot, id_mask, mask_bits, nullptr, kstride, out_ids, out_dists, out_codes,
-                                out_counts);
+    HostSearch r = under(host_search(queries, nq, dim, ks, k, kstride, out_ids, out_dists, out_counts), id_mask, mask_bits);
+    r.codes = out_codes;
+    return search_distinct_host(ix, r, table, slot);
 }
 
 int vdb_flat_search_batch_distinct_filtered(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k,
                                             vdb_meta_table* table, uint32_t slot, const vdb_meta_mask* mask, size_t kstride,
                                             uint64_t* out_ids, float* out_dists, int32_t* out_codes, size_t* out_counts) {
     if (!mask) return fail(VDB_ERR_INVALID_ARGUMENT, "null mask");
-    return search_distinct_host(ix, queries, nq, dim, ks, k, table, slot, nullptr, 0, mask, kstride, out_ids, out_dists, out_codes, out_counts);
+    HostSearch r = under(host_search(queries, nq, dim, ks, k, kstride, out_ids, out_dists, out_counts), mask);
+    r.codes = out_codes;
+    return search_distinct_host(ix, r, table, slot);
 }
 
 int vdb_flat_distinct_stats(const vdb_flat_index* ix, uint64_t out[8]) {
@@ -907,19 +889,15 @@ int vdb_flat_distinct_stats(const vdb_flat_index* ix, uint64_t out[8]) {
 
 // ---- one batch, a filter per query (no reference counterpart; vdb_search.cpp search_grouped).  The masks come from
 // the host (id_masks: n_masks x words, the referenced ones uploaded here) or are compiled ones already in HBM (cms).
-static int search_grouped_host(vdb_flat_index* ix, const char* what, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k,
-                               const uint64_t* id_masks, const vdb_meta_mask* const* cms, bool compiled, size_t n_masks, size_t mask_bits,
-                               const uint32_t* group_of, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts) {
+static int search_grouped_host(vdb_flat_index* ix, const char* what, const HostSearch& r, const uint64_t* id_masks,
+                               const vdb_meta_mask* const* cms, bool compiled, size_t n_masks, const uint32_t* group_of) {
     return guarded([&]() -> int {
-    if (!ix || (nq && (!queries || !out_counts))) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    const size_t nq = r.nq, dim = r.dim, mask_bits = r.mask_bits;
+    if (!ix || (nq && (!r.queries || !r.counts))) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
     if (ix->multi) return refuse_multi(what);
-    size_t kmax = k;
-    if (ks) {
-        kmax = 0;
-        for (size_t b = 0; b < nq; ++b) kmax = std::max(kmax, ks[b]);
-    }
-    if (kmax > kstride) return fail(VDB_ERR_INVALID_ARGUMENT, "kstride %zu smaller than the largest k %zu", kstride, kmax);
-    if (kmax && nq && (!out_ids || !out_dists)) return fail(VDB_ERR_INVALID_ARGUMENT, "null output");
+    size_t kmax;
+    int rc;
+    if ((rc = batch_shape(r, &kmax))) return rc;
     std::lock_guard<std::mutex> g(ix->mu);
     if (in_flight(ix)) return refuse_in_flight();
     memset(ix->grouped_stats, 0, sizeof(ix->grouped_stats));
@@ -927,7 +905,7 @@ static int search_grouped_host(vdb_flat_index* ix, const char* what, const float
     if (nq == 0) return VDB_OK;
     const size_t len = ix->n_live + ix->misfits.size();
     if (len == 0 || kmax == 0) {                                   // storage.rs:218-220: empty store -> Ok(vec![]) before any check
-        for (size_t b = 0; b < nq; ++b) out_counts[b] = 0;
+        for (size_t b = 0; b < nq; ++b) r.counts[b] = 0;
         return VDB_OK;
     }
     // ---- argument errors, before any device work
@@ -948,13 +926,11 @@ static int search_grouped_host(vdb_flat_index* ix, const char* what, const float
     if (compiled)
         for (uint32_t m : ref) {
             if (!cms[m]) return fail(VDB_ERR_INVALID_ARGUMENT, "mask %u is null", m);
-            if (cms[m]->device != ix->device)
-                return fail(VDB_ERR_INVALID_ARGUMENT, "the compiled mask lives on device %d, the index on device %d", cms[m]->device, ix->device);
+            if ((rc = compiled_mask_check(cms[m], ix->device))) return rc;
         }
     if (nq > 0x3fffffffull) return fail(VDB_ERR_INVALID_ARGUMENT, "batch too large");
     ix->grouped_stats[1] = R;
-    int rc = set_device(ix);
-    if (rc) return rc;
+    if ((rc = set_device(ix))) return rc;
     ix->cur = &ix->wsv[0];
     if ((rc = flush(ix))) return rc;                               // staged adds first
     const size_t kdev = std::min(kmax, std::max<size_t>(len, 1));  // Index::search returns at most len results
@@ -963,20 +939,21 @@ static int search_grouped_host(vdb_flat_index* ix, const char* what, const float
     if ((rc = G.q.ensure(nq * std::max<size_t>(dim, 1))) || (rc = G.oi.ensure(nq * kdev)) || (rc = G.od.ensure(nq * kdev)) || (rc = G.oc.ensure(nq)) ||
         (rc = G.desc.ensure(std::max<size_t>(R, 1))))
         return rc;
-    if (dim) HIP_TRY(hipMemcpyAsync(G.q.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
+    if (dim) HIP_TRY(hipMemcpyAsync(G.q.p, r.queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
     std::vector<vdb::GroupedMask> desc(R);
     if (compiled) {
-        for (size_t r = 0; r < R; ++r) {
-            const vdb_meta_mask* cm = cms[ref[r]];
+        for (size_t j = 0; j < R; ++j) {
+            const vdb_meta_mask* cm = cms[ref[j]];
             HIP_TRY(hipStreamWaitEvent(s, cm->done, 0));
-            desc[r] = vdb::GroupedMask{cm->d_words, cm->bits};
+            desc[j] = vdb::GroupedMask{cm->d_words, cm->bits};
         }
     } else {
+        // (R masks side by side in ONE buffer: not the single-mask stager of vdb_hostio.h)
         const size_t words = (mask_bits + 63) / 64;
         if ((rc = G.masks.ensure(std::max<size_t>(R * words, 1)))) return rc;
-        for (size_t r = 0; r < R; ++r) {
-            if (words) HIP_TRY(hipMemcpyAsync(G.masks.p + r * words, id_masks + (size_t)ref[r] * words, words * 8, hipMemcpyHostToDevice, s));
-            desc[r] = vdb::GroupedMask{G.masks.p + r * words, mask_bits};
+        for (size_t j = 0; j < R; ++j) {
+            if (words) HIP_TRY(hipMemcpyAsync(G.masks.p + j * words, id_masks + (size_t)ref[j] * words, words * 8, hipMemcpyHostToDevice, s));
+            desc[j] = vdb::GroupedMask{G.masks.p + j * words, mask_bits};
         }
     }
     if (R) HIP_TRY(hipMemcpyAsync(G.desc.p, desc.data(), R * sizeof(vdb::GroupedMask), hipMemcpyHostToDevice, s));
@@ -985,20 +962,7 @@ static int search_grouped_host(vdb_flat_index* ix, const char* what, const float
         (void)hipStreamSynchronize(s);                             // (desc and the plan are host vectors of this frame)
         return rc;
     }
-    std::vector<uint32_t> cnt(nq);
-    std::vector<uint64_t> ids(nq * kdev);
-    std::vector<float> ds(nq * kdev);
-    HIP_TRY(hipMemcpyAsync(cnt.data(), G.oc.p, nq * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(ids.data(), G.oi.p, nq * kdev * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(ds.data(), G.od.p, nq * kdev * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (size_t b = 0; b < nq; ++b) {
-        const size_t kb = ks ? ks[b] : k;
-        const size_t c = std::min<size_t>(cnt[b], kb);             // per-query k: a prefix of the batch-wide result
-        out_counts[b] = c;
-        for (size_t i = 0; i < c; ++i) { out_ids[b * kstride + i] = ids[b * kdev + i]; out_dists[b * kstride + i] = ds[b * kdev + i]; }
-    }
-    return VDB_OK;
+    return copy_out(Lists{G.oi.p, G.od.p, G.oc.p, nullptr, kdev}, r, s);
     });
 }
 
@@ -1007,15 +971,16 @@ extern "C" {
 int vdb_flat_search_batch_grouped(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k,
                                   const uint64_t* id_masks, size_t n_masks, size_t mask_bits, const uint32_t* group_of, size_t kstride,
                                   uint64_t* out_ids, float* out_dists, size_t* out_counts) {
-    return search_grouped_host(ix, "vdb_flat_search_batch_grouped", queries, nq, dim, ks, k, id_masks, nullptr, false, n_masks, mask_bits, group_of,
-                               kstride, out_ids, out_dists, out_counts);
+    // (mask_bits: of every one of the n_masks host masks)
+    return search_grouped_host(ix, "vdb_flat_search_batch_grouped", under(host_search(queries, nq, dim, ks, k, kstride, out_ids, out_dists, out_counts), nullptr, mask_bits),
+                               id_masks, nullptr, false, n_masks, group_of);
 }
 
 int vdb_flat_search_batch_grouped_filtered(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k,
                                            const vdb_meta_mask* const* masks, size_t n_masks, const uint32_t* group_of, size_t kstride,
                                            uint64_t* out_ids, float* out_dists, size_t* out_counts) {
-    return search_grouped_host(ix, "vdb_flat_search_batch_grouped_filtered", queries, nq, dim, ks, k, nullptr, masks, true, n_masks, 0, group_of,
-                               kstride, out_ids, out_dists, out_counts);
+    return search_grouped_host(ix, "vdb_flat_search_batch_grouped_filtered", host_search(queries, nq, dim, ks, k, kstride, out_ids, out_dists, out_counts),
+                               nullptr, masks, true, n_masks, group_of);
 }
 
 int vdb_flat_grouped_stats(const vdb_flat_index* ix, uint64_t out[8]) {
@@ -1096,30 +1061,19 @@ int vdb_flat_range_search_batch(vdb_flat_index* ix, const float* queries, size_t
     if ((rc = W->w_totals.ensure(nq))) return rc;
     if (dim) HIP_TRY(hipMemcpyAsync(W->w_qin.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(W->w_radii.p, rad.data(), nq * sizeof(float), hipMemcpyHostToDevice, s));
-    const uint64_t* d_mask = nullptr;
-    if (id_mask) {
-        const size_t words = (mask_bits + 63) / 64;
-        if ((rc = W->w_mask_ids.ensure(std::max<size_t>(words, 1)))) return rc;
-        if (words) HIP_TRY(hipMemcpyAsync(W->w_mask_ids.p, id_mask, words * 8, hipMemcpyHostToDevice, s));
-        d_mask = W->w_mask_ids.p;
-    }
+    const uint64_t* d_mask;
+    if ((rc = stage_mask(W->w_mask_ids, MaskSrc{id_mask, mask_bits}, s, &d_mask))) return rc;
     rc = range_search_device(ix, W->w_qin.p, nq, dim, W->w_radii.p, d_mask, mask_bits, max_results, W->w_outi.p, W->w_outd.p,
                              W->w_outc.p, W->w_totals.p, nullptr);
     if (rc) return rc;
-    std::vector<uint32_t> cnt(nq);
-    std::vector<uint64_t> ids(nq * max_results), tot(nq);
-    std::vector<float> ds(nq * max_results);
-    HIP_TRY(hipMemcpyAsync(cnt.data(), W->w_outc.p, nq * 4, hipMemcpyDeviceToHost, s));
+    // every list has room for max_results entries: the caller's stride is the device's.  The totals come down with the lists.
+    std::vector<uint64_t> tot(nq);
     HIP_TRY(hipMemcpyAsync(tot.data(), W->w_totals.p, nq * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(ids.data(), W->w_outi.p, nq * max_results * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(ds.data(), W->w_outd.p, nq * max_results * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (size_t b = 0; b < nq; ++b) {
-        const size_t c = std::min<size_t>(cnt[b], max_results);
-        out_counts[b] = c;
-        if (out_totals) out_totals[b] = tot[b];
-        for (size_t i = 0; i < c; ++i) { out_ids[b * max_results + i] = ids[b * max_results + i]; out_dists[b * max_results + i] = ds[b * max_results + i]; }
-    }
+    Batch out;
+    out.nq = nq; out.k = out.kstride = max_results;
+    out.ids = out_ids; out.dists = out_dists; out.counts = out_counts;
+    if ((rc = copy_out(Lists{W->w_outi.p, W->w_outd.p, W->w_outc.p, nullptr, max_results}, out, s))) return rc;
+    if (out_totals) std::copy(tot.begin(), tot.end(), out_totals);
     return VDB_OK;
     });
 }
@@ -1580,10 +1534,7 @@ int vdb_flat_debug_eligible_rows(vdb_flat_index* ix, const uint64_t* id_mask, si
     const bool on_device = hipPointerGetAttributes(&at, id_mask) == hipSuccess && at.type == hipMemoryTypeDevice;
     if (!on_device) {
         (void)hipGetLastError();
-        const size_t words = (mask_bits + 63) / 64;
-        if ((rc = ix->cur->w_mask_ids.ensure(std::max<size_t>(words, 1)))) return rc;
-        if (words) HIP_TRY(hipMemcpyAsync(ix->cur->w_mask_ids.p, id_mask, words * 8, hipMemcpyHostToDevice, s));
-        d_mask = ix->cur->w_mask_ids.p;
+        if ((rc = stage_mask(ix->cur->w_mask_ids, MaskSrc{id_mask, mask_bits}, s, &d_mask))) return rc;
     }
     if ((rc = ix->cur->w_rowmask.ensure((n + 31) / 32))) return rc;
     vdb::launch_build_rowmask(ix->d_row_ids, (ix->n_live == n) ? nullptr : ix->d_live, d_mask, mask_bits, n, ix->cur->w_rowmask.p, s);
@@ -1635,7 +1586,7 @@ static int ensure_pair_buffers(vdb_flat_index* ix, size_t n_pairs, size_t n_out)
 
 int pairs_begin(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim) {
     std::lock_guard<std::mutex> g(ix->mu);
-    if (ix->wsv && (ix->wsv[0].busy || ix->wsv[1].busy)) return fail(VDB_ERR_INVALID_ARGUMENT, "a submitted search is still in flight on this handle");
+    if (in_flight(ix)) return fail(VDB_ERR_INVALID_ARGUMENT, "a submitted search is still in flight on this handle");
     int rc;
     if ((rc = set_device(ix))) return rc;
     if ((rc = flush(ix))) return rc;
@@ -1663,7 +1614,7 @@ int pairs_begin(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim)
 
 static int run_pair_eval(vdb_flat_index* ix, int mode, const uint32_t* a, const uint32_t* b, uint32_t q0, size_t n, float* out) {
     std::lock_guard<std::mutex> g(ix->mu);
-    if (ix->wsv && (ix->wsv[0].busy || ix->wsv[1].busy)) return fail(VDB_ERR_INVALID_ARGUMENT, "a submitted search is still in flight on this handle");
+    if (in_flight(ix)) return fail(VDB_ERR_INVALID_ARGUMENT, "a submitted search is still in flight on this handle");
     int rc;
     if ((rc = set_device(ix))) return rc;
     if (n == 0) return VDB_OK;
@@ -1732,7 +1683,9 @@ int device_view(vdb_flat_index* ix, DeviceView* out) {
 int search_batch_device_mask(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, size_t k, const uint64_t* d_mask,
                              size_t mask_bits, uint64_t* out_ids, float* out_dists, size_t* out_counts) {
     if (!d_mask) return fail(VDB_ERR_INVALID_ARGUMENT, "null mask");
-    return search_batch_host(ix, queries, nq, dim, nullptr, k, nullptr, mask_bits, nullptr, k, out_ids, out_dists, out_counts, d_mask);
+    HostSearch r = under(host_search(queries, nq, dim, nullptr, k, k, out_ids, out_dists, out_counts), nullptr, mask_bits);
+    r.dm = d_mask;
+    return search_batch_host(ix, r);
 }
 int set_error(int code, const char* msg) { return fail(code, "%s", msg); }
 int zero_vector_error() { return fail_zero_vector(); }

@@ -4,6 +4,8 @@
 //   vdb_cert.cpp     the coefficients of the "certified top-k" bounds and the tier plans
 //   vdb_search.cpp   the tier scheduler: screening pass, re-threshold pass, f32 MFMA tier, exact scan
 //   vdb_multi.cpp    ONE index over several GPUs in one process (vdb_flat_create_sharded)
+// vdb_hostio.h holds the steps every host-pointer batch search shares (shape check, mask staging, copy-out); HostSearch below is
+// the request those entry points hand on.
 // Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -23,6 +25,7 @@
 #include "../../include/vdb_flat.h"
 #include "kernels.h"
 #include "vdb_device.h"
+#include "vdb_hostio.h"
 #include "vdb_internal.h"
 
 namespace vdbi {
@@ -58,6 +61,17 @@ struct RecommendWs {
 struct RecommendReq {
     const uint64_t* ids; const size_t* offsets; const uint32_t* n_pos;
     size_t total = 0, mmax = 0;                                   // offsets[nq]; the longest request (recommend_check)
+};
+
+// A host-pointer batch search as its entry point received it (the extern "C" shims fill it): the batch and its outputs (Batch),
+// the queries -- vectors [nq][dim], or the stored vectors of `by` (then queries is null and dim unused), or folds of stored
+// vectors (rec, checked by recommend_check; by is then rec->ids) -- and the id mask in the form it came in.
+struct HostSearch : vdbi::Batch {
+    const float* queries = nullptr; size_t dim = 0;
+    const uint64_t* by = nullptr; const RecommendReq* rec = nullptr;
+    const uint64_t* id_mask = nullptr; size_t mask_bits = 0;      // mask_bits bits in host memory
+    const struct vdb_meta_mask* cm = nullptr;                     // a compiled mask (vdb_meta.h); mask_bits becomes its size
+    const uint64_t* dm = nullptr;                                 // mask_bits bits already on the device (vdb_internal::search_batch_device_mask)
 };
 
 struct Workspace {
@@ -226,6 +240,7 @@ inline int set_device(const Index* ix) {
 int grow(Index* ix, uint32_t need_rows);
 void free_store(Index* ix);
 void reset_rows(Index* ix);
+void adopt_dim(Index* ix, size_t dim);   // a store without rows takes the dimension of what comes next
 void kill_row(Index* ix, uint32_t row);
 int remove_id(Index* ix, uint64_t id);
 int add_one(Index* ix, uint64_t id, const float* v, size_t dim);
@@ -274,11 +289,17 @@ int search_device(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, 
 int query_dim_check(const Index* ix, size_t dim);
 // ---- vdb_flat.cpp: the device side of a recommend call, the same on a plain handle and on the home device of a sharded one.
 // recommend_stage packs the checked request with the row number of every example (in the block the fold will read) and sends it
-// up on s in two copies; *L then names the lists on the device.  recommend_strike runs the set strike over the search's lists and
-// enqueues the read of the struck counter into *struck (valid after the caller's synchronisation).
+// up on s in two copies; *L then names the lists on the device.
 int recommend_stage(RecommendWs& W, const RecommendReq& r, size_t nq, const uint32_t* rows, hipStream_t s, vdb::RecommendLists* L);
-int recommend_strike(RecommendWs& W, const vdb::RecommendLists& L, size_t nq, uint64_t* d_ids, float* d_dists, uint32_t* d_counts,
-                     size_t kdev, size_t kcut, hipStream_t s, uint32_t* struck);
+// The strike of a search by stored id or of a recommend call, on s, around the device search: strike_stage sends the query ids up
+// and zeroes the counters (a recommend's lists L and counter are staged by recommend_stage already); strike_copy_out runs the self
+// strike or the set strike over the search's lists `found`, cutting them to kcut, reads the struck counters with the copy-out and
+// writes H->by_id_stats / H->recommend_stats.  The buffers are the plain handle's workspace's or the sharded parent's.
+struct StrikeBufs { vdbi::DevBuf<uint64_t>& selfid; vdbi::DevBuf<uint32_t>& bystat; RecommendWs& rec; };
+int strike_stage(StrikeBufs B, const HostSearch& r, hipStream_t s);
+int strike_copy_out(Index* H, const HostSearch& r, StrikeBufs B, const vdb::RecommendLists& L, const Lists& found, size_t kcut, hipStream_t s);
+// the mask of a request whose compiled mask, if any, has passed the device check
+MaskSrc mask_src(const HostSearch& r);
 int range_search_device(Index* ix, const float* d_q, size_t nq, size_t dim, const float* d_radii, const uint64_t* d_idmask,
                         size_t mask_bits, size_t max_results, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                         uint64_t* d_out_totals, hipStream_t user_stream);
@@ -287,11 +308,9 @@ int range_search_device(Index* ix, const float* d_q, size_t nq, size_t dim, cons
 // the buffers and the counters, s is the stream its kernels run on (the home device is current), `search` is the handle's ordinary
 // device-pointer search -- outputs complete when it returns -- and everything in DistinctArgs has passed the entry point's checks.
 struct DistinctArgs {
-    const float* queries; size_t nq, dim; const size_t* ks; size_t k, kmax, len;
+    const HostSearch& r; size_t kmax, len;
     const int32_t* d_codes; size_t codes_len;
-    const uint64_t* id_mask; size_t mask_bits; const struct vdb_meta_mask* cm;
     uint64_t id_bound; uint32_t n_cu;
-    size_t kstride; uint64_t* out_ids; float* out_dists; int32_t* out_codes; size_t* out_counts;
 };
 using DistinctSearch = std::function<int(const float* d_q, size_t nq, size_t depth, const uint64_t* d_mask, size_t mask_bits,
                                          uint64_t* d_ids, float* d_dists, uint32_t* d_counts)>;
@@ -332,16 +351,13 @@ int multi_reserve(vdb_flat_index* P, size_t rows, size_t dim);
 int multi_for_each(vdb_flat_index* P, const std::function<int(vdb_flat_index*)>& f);
 int multi_search_device(vdb_flat_index* P, const float* d_q, size_t nq, size_t dim, size_t k, const uint64_t* d_mask, size_t mask_bits,
                         uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, hipStream_t user_stream);
-int multi_search_host(vdb_flat_index* P, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k, const uint64_t* id_mask,
-                      size_t mask_bits, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts,
-                      const struct vdb_meta_mask* cm = nullptr);   // cm: a compiled mask on the home device instead of id_mask (vdb_meta.h)
-// vdb_flat_search_batch_by_id on a sharded handle: every shard gathers the rows of ITS query ids on its own device, the blocks
-// meet on devices[0] device-to-device, the ordinary sharded search runs with k + 1 and the strike runs on devices[0].
-// rec (vdb_flat_recommend_batch; query_ids is then rec->ids): one staged row per EXAMPLE, folded on devices[0] in list order into
-// the nq queries; the search runs with k + the longest request and the set strike replaces the self strike
-int multi_search_by_id(vdb_flat_index* P, const uint64_t* query_ids, size_t nq, const size_t* ks, size_t k, const uint64_t* id_mask,
-                       size_t mask_bits, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts,
-                       const struct vdb_meta_mask* cm, const RecommendReq* rec = nullptr);
+// the host-pointer searches on a sharded handle; a compiled mask of r lives on the home device
+int multi_search_host(vdb_flat_index* P, const HostSearch& r);
+// vdb_flat_search_batch_by_id on a sharded handle (r.by): every shard gathers the rows of ITS query ids on its own device, the
+// blocks meet on devices[0] device-to-device, the ordinary sharded search runs with k + 1 and the strike runs on devices[0].
+// r.rec (vdb_flat_recommend_batch): one staged row per EXAMPLE, folded on devices[0] in list order into the nq queries; the
+// search runs with k + the longest request and the set strike replaces the self strike
+int multi_search_by_id(vdb_flat_index* P, const HostSearch& r);
 // vdb_flat_search_batch_distinct on a sharded handle (the caller holds the parent's lock): the shards' staged adds flushed; the
 // stream of devices[0] that distinct_drive's kernels run on; the sharded search behind a host wait for that stream (the shards'
 // streams read what it wrote); the largest id bound of the shards

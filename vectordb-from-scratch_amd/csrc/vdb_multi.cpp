@@ -28,7 +28,6 @@
 
 #include "../../include/vdb_shard.h"
 #include "vdb_index.h"
-#include "vdb_meta.h"
 #include "vdb_rccl.h"
 
 namespace vdbi {
@@ -578,84 +577,45 @@ namespace {
 
 // The second half of the host-pointer searches, under the parent's lock: the query block [nq][dim] is already in (or on its way
 // into, on the home stream) M->w_qin; the mask is staged, the sharded search runs with kdev results per query and the first k_b of
-// each list are copied out.  by (search by stored id): kdev is one more than kcut, and the entry whose id equals by[b] is struck
-// from list b on the home device in between.  rec / rl (recommend; by is null): the lists are already staged on the home device,
-// kdev is kcut + the longest request, and the set strike removes every example of request b from list b.
-int finish_host(vdb_flat_index* P, size_t nq, size_t dim, const size_t* ks, size_t k, size_t kdev, const uint64_t* id_mask, size_t mask_bits,
-                const vdb_meta_mask* cm, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts, const uint64_t* by = nullptr,
-                size_t kcut = 0, const RecommendReq* rec = nullptr, const vdb::RecommendLists* rl = nullptr) {
+// each list are copied out.  r.by (search by stored id): kdev is one more than kcut, and the entry whose id equals by[b] is struck
+// from list b on the home device in between.  r.rec / rl (recommend): the lists are already staged on the home device, kdev is
+// kcut + the longest request, and the set strike removes every example of request b from list b.
+int finish_host(vdb_flat_index* P, const HostSearch& r, size_t dim, size_t kdev, size_t kcut = 0, const vdb::RecommendLists& rl = {}) {
     vdb_multi* M = P->multi;
     hipStream_t s = M->ps[0].stream;
+    const size_t nq = r.nq;
     int rc;
     if ((rc = M->w_outi.ensure(nq * std::max<size_t>(kdev, 1)))) return rc;
     if ((rc = M->w_outd.ensure(nq * std::max<size_t>(kdev, 1)))) return rc;
     if ((rc = M->w_outc.ensure(nq))) return rc;
-    const uint64_t* d_mask = nullptr;
-    if (id_mask) {
-        const size_t words = (mask_bits + 63) / 64;
-        if ((rc = M->w_mask.ensure(std::max<size_t>(words, 1)))) return rc;
-        if (words) HIP_TRY(hipMemcpyAsync(M->w_mask.p, id_mask, words * 8, hipMemcpyHostToDevice, s));
-        d_mask = M->w_mask.p;
-    } else if (cm) {                                                   // already on the home device: ordered in front of the wait below
-        HIP_TRY(hipStreamWaitEvent(s, cm->done, 0));
-        d_mask = cm->d_words;
-    }
-    if (by) {
-        if ((rc = M->w_selfid.ensure(nq))) return rc;
-        if ((rc = M->w_bystat.ensure(2))) return rc;
-        HIP_TRY(hipMemcpyAsync(M->w_selfid.p, by, nq * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemsetAsync(M->w_bystat.p, 0, 8, s));
-    }
+    const uint64_t* d_mask;                                            // (a compiled mask is on the home device already)
+    if ((rc = stage_mask(M->w_mask, mask_src(r), s, &d_mask))) return rc;
+    const StrikeBufs strike{M->w_selfid, M->w_bystat, M->w_rec};
+    if (r.by && (rc = strike_stage(strike, r, s))) return rc;
     HIP_TRY(hipStreamSynchronize(s));                                  // the shards' streams read the staged queries
-    if ((rc = search_locked(P, M->w_qin.p, nq, dim, kdev, d_mask, mask_bits, M->w_outi.p, M->w_outd.p, M->w_outc.p, nullptr))) return rc;
-    uint32_t by_stat[2] = {0, 0};
-    if (rec) {
-        if ((rc = recommend_strike(M->w_rec, *rl, nq, M->w_outi.p, M->w_outd.p, M->w_outc.p, kdev, kcut, s, by_stat))) return rc;
-    } else if (by) {
-        vdb::StrikeSelfParams sp{M->w_outi.p, M->w_outd.p, M->w_outc.p, (uint32_t)kdev, M->w_selfid.p, (uint32_t)kcut, M->w_bystat.p};
-        vdb::launch_strike_self(sp, (uint32_t)nq, s);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(by_stat, M->w_bystat.p, 8, hipMemcpyDeviceToHost, s));
-    }
-    std::vector<uint32_t> cnt(nq);
-    std::vector<uint64_t> ids(nq * std::max<size_t>(kdev, 1));
-    std::vector<float> ds(nq * std::max<size_t>(kdev, 1));
-    HIP_TRY(hipMemcpyAsync(cnt.data(), M->w_outc.p, nq * 4, hipMemcpyDeviceToHost, s));
-    if (kdev) {
-        HIP_TRY(hipMemcpyAsync(ids.data(), M->w_outi.p, nq * kdev * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(ds.data(), M->w_outd.p, nq * kdev * 4, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    if (rec) { P->recommend_stats[0] = nq; P->recommend_stats[1] = rec->total; P->recommend_stats[2] = by_stat[0]; P->recommend_stats[3] = kdev; }
-    else if (by) { P->by_id_stats[0] = nq; P->by_id_stats[1] = by_stat[0]; P->by_id_stats[2] = by_stat[1]; }
-    for (size_t b = 0; b < nq; ++b) {
-        const size_t kb = ks ? ks[b] : k;
-        const size_t c = std::min<size_t>(cnt[b], kb);                 // per-query k: a prefix of the batch-wide result
-        out_counts[b] = c;
-        for (size_t i = 0; i < c; ++i) { out_ids[b * kstride + i] = ids[b * kdev + i]; out_dists[b * kstride + i] = ds[b * kdev + i]; }
-    }
-    return VDB_OK;
+    if ((rc = search_locked(P, M->w_qin.p, nq, dim, kdev, d_mask, r.mask_bits, M->w_outi.p, M->w_outd.p, M->w_outc.p, nullptr))) return rc;
+    const Lists found{M->w_outi.p, M->w_outd.p, M->w_outc.p, nullptr, kdev};
+    if (r.by) return strike_copy_out(P, r, strike, rl, found, kcut, s);
+    return copy_out(found, r, s);
 }
 
 }  // namespace
 
-int multi_search_host(vdb_flat_index* P, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k, const uint64_t* id_mask,
-                      size_t mask_bits, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts, const vdb_meta_mask* cm) {
+int multi_search_host(vdb_flat_index* P, const HostSearch& r) {
     vdb_multi* M = P->multi;
-    size_t kmax = k;
-    if (ks) { kmax = 0; for (size_t b = 0; b < nq; ++b) kmax = std::max(kmax, ks[b]); }
-    if (kmax > kstride) return fail(VDB_ERR_INVALID_ARGUMENT, "kstride %zu smaller than the largest k %zu", kstride, kmax);
-    if (kmax && nq && (!out_ids || !out_dists)) return fail(VDB_ERR_INVALID_ARGUMENT, "null output");
+    const size_t nq = r.nq, dim = r.dim;
+    size_t kmax;
+    int rc;
+    if ((rc = batch_shape(r, &kmax))) return rc;
     std::lock_guard<std::mutex> lk(P->mu);
     if (nq == 0) return VDB_OK;
     HIP_TRY(hipSetDevice(M->home));
     const size_t len = multi_len(P);
     const size_t kdev = std::min(kmax, std::max<size_t>(len, 1));      // Index::search returns at most len results
     hipStream_t s = M->ps[0].stream;
-    int rc;
     if ((rc = M->w_qin.ensure(nq * std::max<size_t>(dim, 1)))) return rc;
-    if (dim) HIP_TRY(hipMemcpyAsync(M->w_qin.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
-    return finish_host(P, nq, dim, ks, k, kdev, id_mask, mask_bits, cm, kstride, out_ids, out_dists, out_counts);
+    if (dim) HIP_TRY(hipMemcpyAsync(M->w_qin.p, r.queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
+    return finish_host(P, r, dim, kdev);
 }
 
 // Search by stored id.  The row of an id lives on one shard: every shard gathers the rows of ITS query ids on its own device
@@ -664,21 +624,20 @@ int multi_search_host(vdb_flat_index* P, const float* queries, size_t nq, size_t
 // Recommend (rec) stages one row per EXAMPLE in the same way -- the ne = rec->total ids of all requests, in array order -- and
 // instead of the last gather the fold kernel runs on devices[0] over the stage (ld = dim, each example's place as its row number):
 // the fold order is the request's list order wherever the rows live.
-int multi_search_by_id(vdb_flat_index* P, const uint64_t* query_ids, size_t nq, const size_t* ks, size_t k, const uint64_t* id_mask,
-                       size_t mask_bits, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts, const vdb_meta_mask* cm,
-                       const RecommendReq* rec) {
+int multi_search_by_id(vdb_flat_index* P, const HostSearch& r) {
     vdb_multi* M = P->multi;
+    const uint64_t* const query_ids = r.by;
+    const RecommendReq* const rec = r.rec;
+    const size_t nq = r.nq;
     const size_t ne = rec ? rec->total : nq;                           // staged rows: one per query id, or one per example
-    size_t kmax = k;
-    if (ks) { kmax = 0; for (size_t b = 0; b < nq; ++b) kmax = std::max(kmax, ks[b]); }
-    if (kmax > kstride) return fail(VDB_ERR_INVALID_ARGUMENT, "kstride %zu smaller than the largest k %zu", kstride, kmax);
-    if (kmax && nq && (!out_ids || !out_dists)) return fail(VDB_ERR_INVALID_ARGUMENT, "null output");
+    size_t kmax;
+    int rc;
+    if ((rc = batch_shape(r, &kmax))) return rc;
     std::lock_guard<std::mutex> lk(P->mu);
     if (rec) memset(P->recommend_stats, 0, sizeof(P->recommend_stats));
     else memset(P->by_id_stats, 0, sizeof(P->by_id_stats));
     if (nq == 0) return VDB_OK;
     if (nq > 0x3fffffffull) return fail(VDB_ERR_INVALID_ARGUMENT, "batch too large");
-    int rc;
     // staged adds and removes first: an id resolves to what the search below sees
     for (auto* c : M->sh) if ((rc = vdb_flat_flush(c))) return rc;
     HIP_TRY(hipSetDevice(M->home));
@@ -760,12 +719,12 @@ int multi_search_by_id(vdb_flat_index* P, const uint64_t* query_ids, size_t nq, 
         if ((rc = recommend_stage(M->w_rec, *rec, nq, place.data(), s, &rl))) return rc;
         vdb::launch_fold_examples(M->w_gstage.p, (uint32_t)dim, (uint32_t)dim, (uint32_t)ne, rl, (uint32_t)nq, M->w_qin.p, s);
         HIP_TRY(hipGetLastError());
-        return finish_host(P, nq, dim, ks, k, kdev, id_mask, mask_bits, cm, kstride, out_ids, out_dists, out_counts, nullptr, kcut, rec, &rl);
+        return finish_host(P, r, dim, kdev, kcut, rl);
     }
     HIP_TRY(hipMemcpyAsync(M->w_place.p, place.data(), nq * 4, hipMemcpyHostToDevice, s));
     vdb::launch_gather_rows(M->w_gstage.p, (uint32_t)dim, (uint32_t)dim, (uint32_t)nq, M->w_place.p, (uint32_t)nq, M->w_qin.p, s);
     HIP_TRY(hipGetLastError());
-    return finish_host(P, nq, dim, ks, k, kdev, id_mask, mask_bits, cm, kstride, out_ids, out_dists, out_counts, query_ids, kcut);
+    return finish_host(P, r, dim, kdev, kcut);
 }
 
 // ---- one nearest row per group: the driver is vdb_search.cpp's distinct_drive; a sharded handle only lends it these

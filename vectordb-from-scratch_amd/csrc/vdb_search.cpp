@@ -7,7 +7,6 @@
 #include <limits>
 
 #include "vdb_index.h"
-#include "vdb_meta.h"
 
 namespace vdbi {
 
@@ -1202,7 +1201,7 @@ int refuse_in_flight() { return fail(VDB_ERR_INVALID_ARGUMENT, "a submitted sear
 int distinct_drive(Index* H, hipStream_t s, const DistinctSearch& search, const DistinctArgs& a) {
     DistinctWs& W = H->dws;
     uint64_t* st = H->distinct_stats;
-    const size_t nq = a.nq, dim = a.dim, kmax = a.kmax;
+    const size_t nq = a.r.nq, dim = a.r.dim, kmax = a.kmax;
     const size_t dA = vdb_flat_distinct_depth(kmax, a.len, 0), dB = vdb_flat_distinct_depth(kmax, a.len, 1);
     st[0] = nq; st[5] = dA; st[6] = dB;
     int rc;
@@ -1210,18 +1209,10 @@ int distinct_drive(Index* H, hipStream_t s, const DistinctSearch& search, const 
         (rc = W.ai.ensure(nq * kmax)) || (rc = W.ad.ensure(nq * kmax)) || (rc = W.ac.ensure(nq * kmax)) || (rc = W.kept.ensure(nq)) ||
         (rc = W.complete.ensure(nq)) || (rc = W.sel.ensure(nq)))
         return rc;
-    if (dim) HIP_TRY(hipMemcpyAsync(W.q.p, a.queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
-    const uint64_t* d_mask = nullptr;
-    size_t mask_bits = a.mask_bits;
-    if (a.id_mask) {
-        const size_t words = (mask_bits + 63) / 64;
-        if ((rc = W.mask_in.ensure(std::max<size_t>(words, 1)))) return rc;
-        if (words) HIP_TRY(hipMemcpyAsync(W.mask_in.p, a.id_mask, words * 8, hipMemcpyHostToDevice, s));
-        d_mask = W.mask_in.p;
-    } else if (a.cm) {
-        HIP_TRY(hipStreamWaitEvent(s, a.cm->done, 0));
-        d_mask = a.cm->d_words;
-    }
+    if (dim) HIP_TRY(hipMemcpyAsync(W.q.p, a.r.queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
+    const uint64_t* d_mask;
+    const size_t mask_bits = a.r.mask_bits;
+    if ((rc = stage_mask(W.mask_in, mask_src(a.r), s, &d_mask))) return rc;
     vdb::DistinctFirstParams fp{};
     fp.ids = W.li.p; fp.dists = W.ld.p; fp.counts = W.lc.p;
     fp.codes = a.d_codes; fp.codes_len = a.codes_len; fp.n_answers = (uint32_t)nq; fp.k = (uint32_t)kmax; fp.kstride = (uint32_t)kmax;
@@ -1288,27 +1279,10 @@ int distinct_drive(Index* H, hipStream_t s, const DistinctSearch& search, const 
         }
     }
 
-    // ---- the answers come down; per-query k: a prefix of the batch-wide answer
-    std::vector<uint32_t> cnt(nq);
-    std::vector<uint64_t> ids(nq * kmax);
-    std::vector<float> ds(nq * kmax);
-    std::vector<int32_t> cs(nq * kmax);
-    HIP_TRY(hipMemcpyAsync(cnt.data(), W.kept.p, nq * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(ids.data(), W.ai.p, nq * kmax * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(ds.data(), W.ad.p, nq * kmax * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(cs.data(), W.ac.p, nq * kmax * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (size_t b = 0; b < nq; ++b) {
-        const size_t kb = a.ks ? a.ks[b] : a.k;
-        const size_t c = std::min<size_t>(std::min<size_t>(cnt[b], kmax), kb);
-        a.out_counts[b] = c;
-        st[7] += c;
-        for (size_t i = 0; i < c; ++i) {
-            a.out_ids[b * a.kstride + i] = ids[b * kmax + i];
-            a.out_dists[b * a.kstride + i] = ds[b * kmax + i];
-            if (a.out_codes) a.out_codes[b * a.kstride + i] = cs[b * kmax + i];
-        }
-    }
+    // ---- the answers come down (a kept count is clamped to the answers' stride)
+    size_t emitted = 0;
+    if ((rc = copy_out(Lists{W.ai.p, W.ad.p, W.kept.p, W.ac.p, kmax}, a.r, s, &emitted))) return rc;
+    st[7] += emitted;
     return VDB_OK;
 }
 

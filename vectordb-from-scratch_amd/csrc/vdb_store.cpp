@@ -83,6 +83,14 @@ void reset_rows(Index* ix) {
     if (ix->d_scalars) (void)hipMemsetAsync(ix->d_scalars, 0, 32, ix->stream);
 }
 
+// A fresh index takes the dimension of what it is given (add, bulk add, reserve); rows of a store emptied by removes go first.
+void adopt_dim(Index* ix, size_t dim) {
+    if (ix->n_live != 0 || !ix->misfits.empty()) return;
+    if (ix->dim != dim) reset_rows(ix);
+    ix->dim = (uint32_t)dim;
+    ix->ld = round_up(ix->dim, vdb::KSTAGE);
+}
+
 void kill_row(Index* ix, uint32_t row) {
     ix->live[row >> 5] &= ~(1u << (row & 31));
     --ix->n_live;
@@ -146,11 +154,7 @@ int remove_id(Index* ix, uint64_t id) {
 
 int add_one(Index* ix, uint64_t id, const float* v, size_t dim) {
     remove_id(ix, id);   // HashMap::insert overwrites (flat_index.rs:39)
-    if (ix->n_live == 0 && ix->misfits.empty() && dim > 0) {
-        if (ix->dim != dim) { reset_rows(ix); }
-        ix->dim = (uint32_t)dim;
-        ix->ld = round_up(ix->dim, vdb::KSTAGE);
-    }
+    if (dim > 0) adopt_dim(ix, dim);
     if (dim == ix->dim && dim > 0) {
         append_row(ix, id, v);
     } else {
