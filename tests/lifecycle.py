@@ -14,7 +14,21 @@ defect each, modelled on a flag of the engine; the pinned set must catch every o
 
 Store level: StoreSim states VectorStore's semantics (upsert = remove + add under the next internal id, post-filter with 3x
 over-fetch, pre-filter as an id mask) over anything with the index interface: over a Model it is the store's model, over a
-RefIndex the store's reference adapter."""
+RefIndex the store's reference adapter.
+
+GROUPED, RECOMMEND AND NUMERIC-FILTER READS have schedules of their own (NEW_PINNED, NEW_STORE_PINNED; _Gen9), because the
+older schedules are dealt from one rng stream each and must stay op for op what they are (test_the_old_schedules_do_not_move).
+  * grouped (B, k, query key, G, mask form, binding key): the model answers query b as Model.search of that query alone under
+    mask group_of[b]; the reference adapter takes each group's eligible rows out of the survivors block and answers the group's
+    queries in one call.  grouped_counters() predicts grouped_stats [0]-[5] from k, the live count and E_g.
+  * recommend (B, k, example key, absent, mask): the model is recommend_data's fold, one search of k_b + m_b, the set strike, the
+    cut; the reference adapter folds with its own loop over vector_of(id) and searches ONE depth for the batch.  recommend_stats
+    [1]-[3] are compared.
+  * mask kind ("numeric", leaf, const key) wherever ("compiled", code) is accepted, and the mutation numbers =
+    MetaTable.set_numbers(0, first code, values): the LUT of column 0, absent at first, overwritten in crossing ranges, grown
+    past its device capacity twice (Log.table_uploaded counts the regrows by vdb_meta.cpp's growth rule).
+  * store level ("numeric": True in the trace): the fields ts and price, numeric filters in the pool, the reads s_recommend and
+    s_with_filters, the device filter switched off and on again."""
 from collections import Counter
 
 import numpy as np
@@ -23,6 +37,7 @@ import by_id_data as bd
 import distinct_data as dd
 import oracle
 import range_data as rd
+import recommend_data as rcd
 
 F32, U64, I32 = np.float32, np.uint64, np.int32
 EUCLID, COSINE, DOT = 0, 1, 2
@@ -33,6 +48,15 @@ NO_DIRECT = 8                          # GpuFlatIndex.TIERS_NO_DIRECT
 MUTATIONS = ("add", "bulk", "upsert", "readd", "remove", "remove_absent", "compact", "compact_shrink", "auto_compact", "codes", "reset")
 READS = ("search", "masked", "sparse", "range", "by_id", "distinct")
 SPARSE_SHARE = 0.02                    # eligible share of a "sparse" read's mask
+# the read kinds, the mutation and the mask kind of the grouped / recommend / numeric schedules (NEW_PINNED).  The old traces never
+# hold them: READS and MUTATIONS stay what the twelve + three + four old schedules were dealt from.
+NEW_READS = ("grouped", "recommend", "numeric")
+READS9, MUTATIONS12 = READS + NEW_READS, MUTATIONS + ("numbers",)
+NUMERIC_CARRIERS = ("numeric", "masked", "by_id", "distinct", "grouped", "recommend")
+GROUP_NONE = 0xFFFFFFFF                # VDB_GROUP_NONE
+GROUPED_MAX_K = 2048                   # a grouped search with k (clamped to the live count) above: one ordinary masked search per group
+GROUPED_BIG_K = 2100
+LEAVES = ("lt", "le", "gt", "ge", "and")   # ("numeric", leaf, const, code): Lt / Le / Gt / Ge on column 0, And([Ne(0, code), Ge(0, const)])
 
 
 class Predicted(Exception):
@@ -79,13 +103,28 @@ def k_of(ks, b):
     return int(ks) if np.isscalar(ks) else int(ks[b])
 
 
-def mask_ok(mask, id_codes, present):
-    """bool by id: ("host", ok) as it is, ("compiled", code): present and group code != code (a missing code matches, like Ne)"""
+def mask_ok(mask, id_codes, present, numbers=None):
+    """bool by id: ("host", ok) as it is, ("compiled", code): present and group code != code (a missing code matches, like Ne),
+    ("numeric", leaf, const, code): present and numbers[code of the id] OP const -- NaN, which fails every comparison, for code
+    -1, for a code at or beyond the LUT's length and for an entry set to NaN; "and": And([Ne(code), Ge(const)])"""
     if mask is None:
         return None
     if mask[0] == "host":
         return np.asarray(mask[1], dtype=bool)
+    if mask[0] == "numeric":
+        _, leaf, const, code = mask
+        lut = np.zeros(0) if numbers is None else numbers
+        has = (id_codes >= 0) & (id_codes < lut.size)
+        v = np.full(id_codes.size, np.nan)
+        v[has] = lut[id_codes[has]]
+        with np.errstate(invalid="ignore"):
+            ok = {"lt": v < const, "le": v <= const, "gt": v > const, "ge": v >= const, "and": (id_codes != I32(code)) & (v >= const)}[leaf]
+        return present & ok
     return present & (id_codes != I32(mask[1]))
+
+
+def on_table(mask):
+    return mask is not None and mask[0] in ("compiled", "numeric")
 
 
 def ok_of_ids(ok, ids):
@@ -111,7 +150,10 @@ class Log:
         self.present = np.zeros(ID_LIMIT, dtype=bool)
         self.id_bound = 0
         self.cap, self.auto, self.staged, self.last_d, self.epoch = 0, 0.0, 0, 0, 0
-        self.counts = dict(doublings=0, shrinks=0, up=0, down=0, dim_resets=0, auto_compactions=0, compact_with_staged=0)
+        self.counts = dict(doublings=0, shrinks=0, up=0, down=0, dim_resets=0, auto_compactions=0, compact_with_staged=0, regrows=0)
+        # the numeric LUT of column 0 by dictionary code (MetaTable.set_numbers); its device array as vdb_meta.cpp's Staged grows it:
+        # at the next upload (a compile, a distinct search), to max(length, twice the old capacity, 1024) -- a REGROW when there was one
+        self.numbers, self.lut_cap, self.lut_dirty, self.col_len = np.zeros(0), 0, None, 0
 
     # -- sizes
     @property
@@ -227,6 +269,38 @@ class Log:
     def set_codes(self, first, codes):
         codes = np.asarray(codes, dtype=I32)
         self.codes[int(first):int(first) + codes.size] = codes
+        self.col_len = max(self.col_len, int(first) + codes.size)
+
+    def set_numbers(self, first, values):
+        values = np.asarray(values, dtype=np.float64)
+        first, end = int(first), int(first) + values.size
+        if end > self.numbers.size:
+            self.numbers = np.concatenate([self.numbers, np.full(end - self.numbers.size, np.nan)])
+        self.numbers[first:end] = values
+        lo, hi = self.lut_dirty or (first, end)
+        self.lut_dirty = (min(lo, first), max(hi, end))
+        self.epoch += 1
+
+    def table_uploaded(self):
+        """what a compile (and a distinct search) does to the table first: the staged LUT writes reach the device"""
+        if self.numbers.size > self.lut_cap:
+            if self.lut_cap:
+                self.counts["regrows"] += 1
+                self.on_regrow()
+            self.lut_cap = max(self.numbers.size, 2 * self.lut_cap, 1024)
+        self.lut_dirty = None
+
+    def on_regrow(self):
+        pass
+
+    def numbers_seen(self):
+        return self.numbers
+
+    def ok_by_id(self, mask):
+        """mask_ok over this log's columns; a mask compiled on the table uploads the table's staged writes first"""
+        if on_table(mask):
+            self.table_uploaded()
+        return mask_ok(mask, self.codes, self.present, self.numbers_seen())
 
     def set(self, name, value):
         pass
@@ -247,7 +321,7 @@ class Log:
         return self.metric == COSINE and self.ids.size and bool((self.alive & ~self.rows.any(axis=1)).any())
 
     def refusal(self, kind, ids=None):
-        if kind == "range" and self.sharded:
+        if kind in ("range", "grouped") and self.sharded:
             raise Predicted("Refused")
         if kind == "by_id":
             live = set(self.ids[self.alive].tolist()) | set(self.misfits)
@@ -321,7 +395,7 @@ class Model(Log):
 
     # -- reads: the adapter interface, answered by the oracle
     def _live(self, mask):
-        ok = mask_ok(mask, self.codes, self.present)
+        ok = self.ok_by_id(mask)
         live = self.alive if ok is None else self.alive & ok_of_ids(ok, self.ids)
         return live.astype(np.uint8)
 
@@ -396,6 +470,58 @@ class Model(Log):
             ans["stages"] = [stages.count(x) for x in "ABC"]
         return ans
 
+    def grouped(self, q, ks, group_of, masks):
+        """include/vdb_flat.h: "the answer for query b is what vdb_flat_search_batch returns for that query ALONE with k_b under
+        mask group_of[b]".  gstats: what grouped_stats [0], [1], [2], [3], [4], [5] must read (grouped_counters)."""
+        empty = self.refusal("grouped")
+        self.uploaded()
+        if empty:
+            return {"lists": [(np.zeros(0, U64), np.zeros(0, np.uint32))] * len(q), "gstats": [len(q), 0, 0, 0, 0, 0]}
+        lives = {g: self._live(masks[g]) for g in sorted({int(g) for g in group_of if g != GROUP_NONE})}
+        lives[GROUP_NONE] = self._live(None)
+        out = []
+        for b in range(len(q)):
+            oi, od = self.ranking(q[b], lives[int(group_of[b])], k_of(ks, b))
+            out.append((oi, od.view(np.uint32)))
+        elig = {g: int(l.sum()) for g, l in lives.items() if g != GROUP_NONE}
+        return {"lists": out, "gstats": grouped_counters(ks, group_of, elig, self.n_live())}
+
+    def recommend(self, pos, neg, ks, mask=None):
+        """recommend_data.expected over the log with live=: the fold of recommend_data, the search with k_b + m_b under the mask,
+        the set strike, the cut.  rstats: recommend_stats [1], [2], [3] (recommend_data.stats); cut: the requests whose list was
+        longer than k_b after the strike (not an engine counter: the caps of the schedules use it)."""
+        flat = np.array([i for p, n in zip(pos, neg) for i in list(p) + list(n)], dtype=U64)
+        self.refusal("by_id", flat)
+        self.uploaded()
+        live = self._live(mask)
+        at = {int(i): r for r, i in enumerate(self.ids.tolist()) if self.alive[r]}
+        requests = [(tuple(at[int(i)] for i in p), tuple(at[int(i)] for i in n)) for p, n in zip(pos, neg)]
+        n = len(self.rows)
+        depths = [min(k_of(ks, b), n) + len(p) + len(ng) for b, (p, ng) in enumerate(requests)]
+        res = oracle.search_batch(self.metric, self.rows, rcd.queries(self.rows, requests), depths, ids=self.ids, live=live)
+        out, cut = [], 0
+        for b, ((oi, od), (p, ng)) in enumerate(zip(res, requests)):
+            keep = ~np.isin(oi, self.ids[list(p) + list(ng)])
+            cut += int(keep.sum()) > k_of(ks, b)
+            ei, ed = rcd.strike(oi, od, self.ids[list(p) + list(ng)], k_of(ks, b))
+            out.append((ei, ed.view(np.uint32)))
+        k = int(ks) if np.isscalar(ks) else [int(x) for x in ks]
+        st = rcd.stats(self.metric, self.rows, requests, k, self.n_live(), ids=self.ids, live=live)
+        return {"lists": out, "rstats": st[1:4], "cut": cut}
+
+
+def grouped_counters(ks, group_of, elig, n_live):
+    """grouped_stats [0], [1], [2], [3], [4], [5] of one call, from k, the live count and the eligible rows E_g of every referenced
+    mask (vdb_search.cpp group_plan / search_grouped).  The rule for E_g = 0: such a group is NEITHER scanned NOR sent to the
+    per-group search -- its queries keep the counts 0 the output starts with and appear in no counter but [0]; so [5] sums E_g
+    over the groups with 0 < E_g <= 131072 when k <= 2048, and is 0 when k > 2048 (then every group with E_g > 0 counts in [3]).
+    E_g > 131072 needs more rows than these schedules hold (at most 20 000): that capacity limit is out of their reach."""
+    kmax = int(ks) if np.isscalar(ks) else max(int(x) for x in ks)
+    scan = min(kmax, max(n_live, 1)) <= GROUPED_MAX_K
+    some = [int(g) for g in group_of if g != GROUP_NONE and elig[int(g)] > 0]
+    return [len(group_of), len(elig), len(some) if scan else 0, 0 if scan else len(some), sum(1 for g in group_of if g == GROUP_NONE),
+            sum(elig[g] for g in set(some)) if scan else 0]
+
 
 # ---------------------------------------------------------------------------------------------------------------- the reference adapter
 class RefIndex(Log):
@@ -409,7 +535,7 @@ class RefIndex(Log):
     def block(self, mask):
         rows, ids, alive = self.seen()
         keep = alive.copy()
-        ok = mask_ok(mask, self.codes, self.present)
+        ok = self.ok_by_id(mask)
         if ok is not None:
             keep &= ok_of_ids(ok, ids)
         return np.ascontiguousarray(rows[keep]), np.ascontiguousarray(ids[keep])
@@ -486,6 +612,91 @@ class RefIndex(Log):
             out.append((ei, ed.view(np.uint32)))
             codes.append(ec)
         return {"lists": out, "codes": codes}
+
+    # -- grouped: per group, the group's eligible rows taken out of the survivors block, all its queries in one knn_batch call
+    def knn_batch(self, rows, ids, q, ks):
+        return oracle.search_batch(self.metric, rows, q, ks, ids=ids)
+
+    def view_before_upload(self):
+        """(rows, ids, alive) as the unfiltered queries and the k > 2048 fallback of a grouped read see them, taken BEFORE the
+        read uploads the staged rows; None: as every other query sees them (hook of GroupedSideSkipsFlush)"""
+        return None
+
+    def group_keeps(self, masks, refs, view):
+        """bool by row of `view` for every referenced mask: alive and eligible (hook of the grouped mutants)"""
+        rows, ids, alive = view
+        return [alive & ok_of_ids(self.ok_by_id(masks[g]), ids) for g in refs]
+
+    def grouped(self, q, ks, group_of, masks):
+        empty = self.refusal("grouped")
+        early = self.view_before_upload()
+        self.uploaded()
+        nq = len(q)
+        out = [(np.zeros(0, U64), np.zeros(0, np.uint32))] * nq
+        if empty:
+            return {"lists": out, "gstats": [nq, 0, 0, 0, 0, 0]}
+        view = self.seen()
+        refs = sorted({int(g) for g in group_of if g != GROUP_NONE})
+        keeps = dict(zip(refs, self.group_keeps(masks, refs, view)))
+        kmax = int(ks) if np.isscalar(ks) else max(int(x) for x in ks)
+        fallback = min(kmax, max(self.n_live(), 1)) > GROUPED_MAX_K
+        for g in refs + [GROUP_NONE]:
+            members = [b for b in range(nq) if int(group_of[b]) == g]
+            side = early is not None and (g == GROUP_NONE or fallback)
+            rows, ids, alive = early if side else view
+            if g == GROUP_NONE:
+                keep = alive
+            elif side:
+                keep = alive & ok_of_ids(self.ok_by_id(masks[g]), ids)
+            else:
+                keep = keeps[g]
+            if not members or not keep.any():
+                continue
+            block, bids = np.ascontiguousarray(rows[keep]), np.ascontiguousarray(ids[keep])
+            for b, (oi, od) in zip(members, self.knn_batch(block, bids, q[members], [k_of(ks, b) for b in members])):
+                out[b] = (oi, od.view(np.uint32))
+        elig = {g: int(keeps[g].sum()) for g in refs}
+        return {"lists": out, "gstats": grouped_counters(ks, group_of, elig, self.n_live())}
+
+    # -- recommend: its own fold over vector_of(id), f32, left to right, one multiply by F32(1) / F32(n); the survivors block
+    def average(self, ids, first=0):
+        with np.errstate(over="ignore", invalid="ignore"):
+            s = self.example_of(ids[0], first).astype(F32, copy=True)
+            for j, i in enumerate(ids[1:]):
+                s = s + self.example_of(i, first + 1 + j)
+            return s if len(ids) == 1 else s * (F32(1) / F32(len(ids)))
+
+    def example_of(self, id, position):
+        """the stored vector of an example; position: its place in the request (positives first)"""
+        return self.vector_of(id)
+
+    def resolve_before_upload(self, flat):
+        pass
+
+    def struck_ids(self, pos, neg):
+        return np.array(list(pos) + list(neg), dtype=U64)
+
+    def recommend(self, pos, neg, ks, mask=None):
+        flat = np.array([i for p, n in zip(pos, neg) for i in list(p) + list(n)], dtype=U64)
+        self.refusal("by_id", flat)
+        self.resolve_before_upload(flat)
+        self.uploaded()
+        rows, bids = self.block(mask)
+        out, struck_total = [], 0
+        kmax = int(ks) if np.isscalar(ks) else max(int(x) for x in ks)
+        kcut = min(kmax, max(self.n_live(), 1))
+        mmax = max(len(p) + len(n) for p, n in zip(pos, neg))
+        for b, (p, n) in enumerate(zip(pos, neg)):
+            ap = self.average(list(p))
+            with np.errstate(over="ignore", invalid="ignore"):
+                fold = ap if not len(n) else ap + (ap - self.average(list(n), len(p)))
+            k, m = k_of(ks, b), len(p) + len(n)
+            oi, od = self.knn(rows, bids, fold, kcut + mmax) if len(rows) else (np.zeros(0, U64), np.zeros(0, F32))
+            oi, od = oi[:min(kcut + mmax, self.n_live())], od[:min(kcut + mmax, self.n_live())]
+            hit = np.isin(oi, self.struck_ids(p, n))
+            struck_total += int((hit & (np.cumsum(~hit) - ~hit < kcut)).sum())      # (the examples in front of the cut of the batch-wide list)
+            out.append((oi[~hit][:k], od[~hit][:k].view(np.uint32)))
+        return {"lists": out, "rstats": [len(flat), struck_total, min(kcut + mmax, self.n_live())]}
 
 
 # ---------------------------------------------------------------------------------------------------------------- mutants
@@ -707,6 +918,117 @@ class RefillKeepsNorms(RefIndex):
         return rows
 
 
+class GroupedIgnoresLive(RefIndex):
+    """13. grouped: the row mask is mask_g[row_ids] alone, without the live bit -- a removed row stays eligible until a compaction"""
+
+    def group_keeps(self, masks, refs, view):
+        rows, ids, alive = view
+        return [ok_of_ids(self.ok_by_id(masks[g]), ids) for g in refs]
+
+
+class GroupedSideSkipsFlush(RefIndex):
+    """14. grouped: the unfiltered queries and the k > 2048 fallback skip the flush -- rows staged since the last read are
+    invisible to those queries only"""
+
+    def view_before_upload(self):
+        rows, ids, alive = self.seen()
+        alive = alive.copy()
+        if self.staged:
+            alive[self.n_rows() - self.staged:] = False
+        return rows, ids, alive
+
+
+class GroupedKeepsRowMasks(RefIndex):
+    """15. grouped: the row masks of the previous grouped read are kept when the row count and the number of referenced masks
+    are unchanged (a workspace keyed by its sizes, like 5)"""
+
+    held = None
+
+    def group_keeps(self, masks, refs, view):
+        key = (len(view[1]), len(refs))
+        if self.held is None or self.held[0] != key:
+            self.held = (key, super().group_keeps(masks, refs, view))
+        return self.held[1]
+
+
+class RecommendResolvesEarly(RefIndex):
+    """16. recommend: the examples' row numbers are resolved before the compaction the same read triggers -- the fold takes
+    whatever sits at the old row numbers"""
+
+    def resolve_before_upload(self, flat):
+        self.early = {int(i): r for r, i in enumerate(self.ids.tolist()) if self.alive[r]}
+
+    def example_of(self, id, position):
+        return self.rows[min(self.early[int(id)], self.n_rows() - 1)]
+
+
+class RecommendFoldsOldRow(ByIdGathersOldRow):
+    """17. recommend: every example but the first of a request is the row its id had before the upsert (8 does not see this:
+    search by id is right, and so is the request ([x], []))"""
+
+    def vector_of(self, id):
+        return RefIndex.vector_of(self, id)
+
+    def example_of(self, id, position):
+        v = RefIndex.vector_of(self, id)
+        return self.before.get(int(id), v) if position else v
+
+
+class RecommendStrikesOnce(RefIndex):
+    """18. recommend: the strike goes by the position of an id's first listing, and a second listing of the same id takes the
+    strike back -- an id listed twice is returned as a neighbour"""
+
+    def struck_ids(self, pos, neg):
+        listed = Counter(int(i) for i in list(pos) + list(neg))
+        return np.array([i for i, c in listed.items() if c == 1], dtype=U64)
+
+
+class RegrowDropsLut(RefIndex):
+    """19. a regrow of the LUT's device array drops the entries the device had: they read NaN until they are set again"""
+
+    def on_regrow(self):
+        lo, hi = self.lut_dirty or (0, 0)
+        kept = self.numbers[lo:hi].copy()
+        self.numbers[:] = np.nan
+        self.numbers[lo:hi] = kept
+
+
+class LutDirtyLastCall(RefIndex):
+    """20. the LUT's dirty range covers only the last set_numbers call before a compile: an earlier, disjoint call is lost
+    (until a regrow sends the whole array)"""
+
+    dev, last = np.zeros(0), None
+
+    def set_numbers(self, first, values):
+        super().set_numbers(first, values)
+        self.last = (int(first), np.array(values, dtype=np.float64))
+
+    def table_uploaded(self):
+        whole = self.numbers.size > self.lut_cap
+        super().table_uploaded()
+        if whole:
+            self.dev = self.numbers.copy()
+        elif self.last is not None:
+            first, values = self.last
+            self.dev = np.concatenate([self.dev, np.full(self.numbers.size - self.dev.size, np.nan)])
+            self.dev[first:first + values.size] = values
+        self.last = None
+
+    def numbers_seen(self):
+        return self.dev
+
+
+class CodesGrowResetsLut(RefIndex):
+    """21. a growing code column resets the LUT's length to 0"""
+
+    def set_codes(self, first, codes):
+        if self.col_len and int(first) + len(codes) > self.col_len:
+            self.numbers = np.zeros(0)
+        super().set_codes(first, codes)
+
+
+NEW_INDEX_MUTANTS = {13: GroupedIgnoresLive, 14: GroupedSideSkipsFlush, 15: GroupedKeepsRowMasks, 16: RecommendResolvesEarly,
+                     17: RecommendFoldsOldRow, 18: RecommendStrikesOnce, 19: RegrowDropsLut, 20: LutDirtyLastCall, 21: CodesGrowResetsLut}
 INDEX_MUTANTS = {1: LostRemove, 2: StagedInvisibleOnce, 3: IdsNotMoved, 4: GrowForgetsTombstones, 5: SampleKeyCollision,
                  6: TiesByPosition, 7: StaleZeroFlag, 8: ByIdGathersOldRow, 9: TotalCountsDead, 10: CodesLostAfterDistinct,
                  12: RefillKeepsNorms}
@@ -714,25 +1036,50 @@ INDEX_MUTANTS = {1: LostRemove, 2: StagedInvisibleOnce, 3: IdsNotMoved, 4: GrowF
 
 # ---------------------------------------------------------------------------------------------------------------- the store
 def flt_of(vdb, spec):
-    """a filter as plain data -> MetadataFilter: ("eq" | "ne", field, value), ("exists", field), ("and" | "or", [specs])"""
+    """a filter as plain data -> MetadataFilter: ("eq" | "ne", field, value), ("exists", field), ("and" | "or", [specs]),
+    ("lt" | "le" | "gt" | "ge", field, number -- or "-inf" / "inf", which a trace can print)"""
     if spec is None:
         return None
     F = vdb.MetadataFilter
     if spec[0] in ("and", "or"):
         return (F.And if spec[0] == "and" else F.Or)([flt_of(vdb, s) for s in spec[1]])
-    return {"eq": F.Eq, "ne": F.Ne, "exists": F.Exists}[spec[0]](*spec[1:])
+    return {"eq": F.Eq, "ne": F.Ne, "exists": F.Exists, "lt": F.Lt, "le": F.Le, "gt": F.Gt, "ge": F.Ge}[spec[0]](*spec[1:])
+
+
+def spec_matches(spec, fields, number_of):
+    """MetadataFilter.matches restated over a filter as plain data, with the numbers of the numeric leaves looked up by
+    number_of(field, string) -> float or None: what the store mutants of the LUT change"""
+    op = spec[0]
+    if op == "and":
+        return all(spec_matches(s, fields, number_of) for s in spec[1])
+    if op == "or":
+        return any(spec_matches(s, fields, number_of) for s in spec[1])
+    have = fields.get(spec[1])
+    if op == "exists":
+        return have is not None
+    if op == "eq":
+        return have is not None and have == spec[2]
+    if op == "ne":
+        return have != spec[2]
+    v = number_of(spec[1], have) if have is not None else None
+    c = float(spec[2])
+    return v is not None and {"lt": v < c, "le": v <= c, "gt": v > c, "ge": v >= c}[op]
 
 
 class StoreSim:
     """VectorStore's semantics over anything with the index interface: string id -> (internal id, Metadata), an upsert removes the
     old internal id and adds the row under the next one, filters by MetadataFilter.matches over the live entries (never by any
     column).  stale_presence: mutant 11, the presence bit of a superseded internal id stays set, so a pre-filtered search still
-    finds the old version."""
+    finds the old version.  lut: the two store mutants of the device table's numeric LUT -- "stale_sent" (22: _lut_sent survives
+    set_device_filter(False) / (True), so the new table never receives the numbers of the dictionary values the old one had) and
+    "bulk_only" (23: the numbers of new dictionary values are forwarded on a bulk attach only, not on single inserts).  Both
+    show while the device filter is on and nowhere else: a numeric leaf then sees no number for such a value."""
 
     GROUP_FIELD = "grp"
 
-    def __init__(self, vdb, index, stale_presence=False):
-        self.vdb, self.index, self.stale = vdb, index, stale_presence
+    def __init__(self, vdb, index, stale_presence=False, lut=None):
+        self.vdb, self.index, self.stale, self.lut = vdb, index, stale_presence, lut
+        self.words, self.known, self.was_on = {}, {}, False          # field -> every value ever stored | those the table has numbers for
         self.entries, self.next, self.table = {}, 0, False           # sid -> (internal, Metadata)
         self.group_code = {}
         self.ghosts = {}                                             # internal -> (sid, Metadata) of superseded versions (mutant 11)
@@ -746,6 +1093,10 @@ class StoreSim:
         internal, self.next = self.next, self.next + 1
         self.index.add(internal, v)
         self.entries[sid] = (internal, self.vdb.Metadata(dict(fields)))
+        for f, value in dict(fields).items():
+            self.words.setdefault(f, set()).add(value)
+            if self.table and self.lut != "bulk_only":
+                self.known.setdefault(f, set()).add(value)
         g = dict(fields).get(self.GROUP_FIELD)
         self.index.set_codes(internal, [-1 if g is None else self.group_code.setdefault(g, len(self.group_code))])
 
@@ -760,6 +1111,10 @@ class StoreSim:
 
     def set(self, name, value):
         if name == "device_filter":
+            if value and not self.table:                             # a new table takes every column's numbers
+                stale = self.lut == "stale_sent" and self.was_on
+                self.known = {f: set() if stale else set(w) for f, w in self.words.items()}
+                self.was_on = True
             self.table = bool(value)
         self.index.set(name, value)
 
@@ -769,6 +1124,12 @@ class StoreSim:
             return None
         flt = flt_of(self.vdb, spec)
         ok = np.zeros(max(self.next, 1), dtype=bool)
+        if self.lut and self.table:
+            num = self.vdb.storage.num
+            number_of = lambda f, s: num(s) if s in self.known.get(f, ()) else None
+            for sid, (internal, meta) in self.entries.items():
+                ok[internal] = spec_matches(spec, meta.fields(), number_of)
+            return ok
         for sid, (internal, meta) in self.entries.items():
             ok[internal] = flt.matches(meta)
         return ok
@@ -836,14 +1197,30 @@ class StoreSim:
             raise Predicted("NeedsTable")
         return [[] for _ in q] if self._empty() else self._named(self._pre(self.index.distinct, q, int(k), spec=spec)["lists"])
 
+    def search_batch_with_filters(self, q, ks, specs):
+        """in the reference's terms: search_batch_prefiltered query by query, each under its own filter (None: the plain search)"""
+        return [self.search_batch_prefiltered(q[b:b + 1], [k_of(ks, b)], spec)[0] for b, spec in enumerate(specs)]
+
+    def recommend_batch(self, requests, k, spec):
+        """the host composition: names -> internal ids (an unknown name: VectorNotFound), the index's recommend under the pre-filter"""
+        pos, neg = [], []
+        for p, n in requests:
+            for sid in list(p) + list(n):
+                if sid not in self.entries:
+                    raise Predicted("VectorNotFound", sid)
+            pos.append([self.entries[s][0] for s in p])
+            neg.append([self.entries[s][0] for s in n])
+        return self._named(self._pre(lambda p_, n_, k_, m_: self.index.recommend(p_, n_, k_, m_), pos, neg, int(k), spec=spec)["lists"])
+
 
 # ---------------------------------------------------------------------------------------------------------------- the runner
 READ_OPS = READS
 STORE_READS = ("s_search", "s_with_filter", "s_prefiltered", "s_within", "s_similar", "s_distinct")
+NEW_STORE_READS = ("s_recommend", "s_with_filters")                 # (schedules with "numeric": True only)
 
 
 def is_read(op):
-    return op[0] in READ_OPS or op[0] in STORE_READS
+    return op[0] in READ_OPS or op[0] in NEW_READS or op[0] in STORE_READS or op[0] in NEW_STORE_READS
 
 
 def queries(seed, key, log, B, d):
@@ -860,12 +1237,24 @@ def queries(seed, key, log, B, d):
 
 
 def mask_of(seed, op_mask, log):
-    """the mask of a read as plain data -> None | ("host", ok by id) | ("compiled", code)"""
+    """the mask of a read as plain data -> None | ("host", ok by id) | ("compiled", code) | ("numeric", leaf, const, code).
+    In a trace a numeric mask is ("numeric", leaf, const key): the constant is one of the numbers set at that moment, from the
+    middle four fifths of them, so that ties at equality occur and most masks keep a share of the rows; one draw in ten is
+    -inf (Gt, Ge) or +inf (Lt, Le): every number passes, NaN does not.  With no number set yet it is 0.0 (and the mask admits
+    nothing; the comparison no number passes, Lt(-inf), stands in grouped reads: grouped_masks)."""
     if op_mask is None:
         return None
     how, key, share = op_mask
     if how == "compiled":
         return ("compiled", int(key))
+    if how == "numeric":
+        rng = rng_of(seed, share, 8)
+        have = np.sort(log.numbers[np.isfinite(log.numbers)])
+        r, at, code = rng.random(), rng.random(), int(rng.integers(0, 30))
+        const = float(have[int((0.1 + 0.8 * at) * have.size)]) if have.size else 0.0
+        if r < 0.1:                                                  # (the infinity every number passes: a read must return a row)
+            const = float("inf") if key in ("lt", "le") else float("-inf")
+        return ("numeric", str(key), const, code)
     return ("host", rng_of(seed, key, 3).random(max(log.id_bound, 1)) < share)
 
 
@@ -909,7 +1298,86 @@ def materialise(trace, op, model):
             gone = np.setdiff1d(model.ids, live)
             ids[int(rng.integers(0, B))] = gone[int(rng.integers(0, gone.size))] if gone.size else U64(ID_LIMIT - 1)
         return "by_id", (ids, ks_of(k), mask_of(seed, m, model))
+    if kind == "numeric":
+        _, B, k, qkey, m = op
+        return "search", (queries(seed, qkey, model, B, d), ks_of(k), mask_of(seed, m, model))
+    if kind == "grouped":
+        _, B, k, qkey, G, form, gkey = op
+        return "grouped", (queries(seed, qkey, model, B, d), ks_of(k)) + grouped_masks(seed, gkey, model, B, G, form)
+    if kind == "recommend":
+        _, B, k, ekey, absent, m = op
+        pos, neg = requests_of(seed, ekey, model, B, absent)
+        return "recommend", (pos, neg, ks_of(k), mask_of(seed, m, model))
     raise ValueError(kind)
+
+
+def grouped_masks(seed, gkey, log, B, G, form):
+    """(group_of u32 [B], masks) of a grouped read.  G masks, all host masks (form "host": eligible shares from SPARSE_SHARE, 0.5,
+    0.9) or all compiled on the table ("compiled": Ne leaves; "numeric": numeric leaves among them).  One read in four holds a mask
+    with no eligible live row (a host mask that admits the removed ids only; compiled: a numeric leaf no number passes), one in
+    four a mask no query references (the last one).  group_of is drawn per query, VDB_GROUP_NONE included; from B = 8 on two
+    queries share a group and one is unfiltered."""
+    rng = rng_of(seed, gkey, 9)
+    bound = max(log.id_bound, 1)
+    masks = []
+    for g in range(G):
+        if form == "host":
+            masks.append(("host", rng.random(bound) < float(rng.choice((SPARSE_SHARE, 0.5, 0.9)))))
+        elif form == "numeric" and rng.random() < 0.6:
+            masks.append(mask_of(seed, ("numeric", str(rng.choice(LEAVES)), int(rng.integers(0, 1 << 30))), log))
+        else:
+            masks.append(("compiled", int(rng.integers(0, 30))))
+    barren, spare = rng.random() < 0.25, rng.random() < 0.25 and G > 1
+    if barren:
+        if form == "host":
+            ok = np.ones(bound, dtype=bool)
+            live = log.live_ids()
+            ok[live[live < U64(bound)].astype(np.int64)] = False
+            masks[0] = ("host", ok)
+        else:
+            masks[0] = ("numeric", "lt", float("-inf"), 0)
+    used = G - 1 if spare else G
+    group_of = rng.integers(0, used + 1, B).astype(np.int64)
+    group_of[rng.random(B) < 0.15] = used
+    if B >= 8:
+        group_of[0] = group_of[1] = int(rng.integers(0, used))
+        group_of[2] = used
+    group_of = np.where(group_of == used, GROUP_NONE, group_of).astype(np.uint32)
+    return group_of, masks
+
+
+def requests_of(seed, ekey, log, B, absent):
+    """(positives, negatives) of a recommend read: per request 1 to 8 positives and 0 to 4 negatives from the live ids, half of
+    them among the 48 ids written last, an id repeated within a request one time in five; one request of the batch is ([x], []);
+    the very last id is the last example of the longest request (not the first of a fold: RecommendFoldsOldRow); `absent` puts a removed (or never stored) id at a random place."""
+    rng = rng_of(seed, ekey, 10)
+    live = log.live_ids()
+    last = log.ids[log.alive][-48:]
+
+    def draw(n):
+        if not live.size:
+            return [0] * n
+        ids = live[rng.integers(0, live.size, n)]
+        recent = rng.random(n) < 0.5
+        ids[recent] = last[rng.integers(0, last.size, n)][recent]
+        return [int(i) for i in ids]
+    reqs = []
+    for b in range(B):
+        ex = draw(int(rng.integers(1, 9)) + int(rng.integers(0, 5)))
+        npos = max(1, len(ex) - int(rng.integers(0, min(5, len(ex)))))
+        if len(ex) > 1 and rng.random() < 0.2:
+            ex[int(rng.integers(1, len(ex)))] = ex[int(rng.integers(0, len(ex)))]
+        reqs.append([ex[:npos], ex[npos:]])
+    reqs[int(rng.integers(0, B))] = [draw(1), []]
+    b = int(np.argmax([len(p) + len(n) for p, n in reqs]))             # the very last id: the last example of the longest request
+    if live.size:
+        reqs[b][1 if reqs[b][1] else 0][-1] = int(last[-1])
+    if absent or not live.size:
+        gone = np.setdiff1d(log.ids, live)
+        b = int(rng.integers(0, B))
+        side = reqs[b][int(rng.integers(0, 2)) if reqs[b][1] else 0]
+        side[int(rng.integers(0, len(side)))] = int(gone[int(rng.integers(0, gone.size))]) if gone.size else ID_LIMIT - 1
+    return [p for p, _ in reqs], [n for _, n in reqs]
 
 
 def capture(call):
@@ -940,7 +1408,7 @@ def diff(want, got):
         for b, (w, g) in enumerate(zip(want["codes"], got["codes"])):
             if not np.array_equal(w, g):
                 return f"query {b}: group codes {g}, expected {w}"
-    for key in ("struck", "cut", "stages"):                          # the engine's own counters of the read, where both sides have them
+    for key in ("struck", "cut", "stages", "gstats", "rstats"):      # the engine's own counters of the read, where both sides have them
         if key in want and key in got and want[key] != got[key]:
             return f"{key} {got[key]}, expected {want[key]}"
     return None
@@ -982,6 +1450,17 @@ def resolve(trace, op, log):
         return [("set", (op[1], op[2]))]
     if kind == "flush":
         return [("flush", ())]
+    if kind == "numbers":                                            # gaussians; NaN ("no number"), +0.0, -0.0 and exact duplicates among them
+        _, first, n, key = op
+        rng = rng_of(seed, key, 11)
+        v = rng.standard_normal(n)
+        r = rng.random(n)
+        copy = r < 0.15
+        v[copy] = v[rng.integers(0, n, n)][copy]
+        v[(r >= 0.15) & (r < 0.2)] = 0.0
+        v[(r >= 0.2) & (r < 0.25)] = -0.0
+        v[(r >= 0.25) & (r < 0.35)] = np.nan
+        return [("set_numbers", (int(first), v))]
     raise ValueError(kind)
 
 
@@ -1010,15 +1489,17 @@ def run(trace, adapter, expected=None, on_read=None):
         else:
             if expected is not None and expected[step] is not None:
                 name, args, want = expected[step]
-                if "error" not in want and not (name == "range" and log.sharded):
+                if "error" not in want and not (name in ("range", "grouped") and log.sharded):
                     log.uploaded()                                   # (a refused read uploads nothing: as on the uncached path)
             else:
                 name, args = materialise_store(trace, op, model) if store else materialise(trace, op, model)
                 want = capture(lambda: getattr(model, name)(*args))
                 if expected is not None and not log.sharded:
                     expected[step] = (name, args, want)
-            if name == "range" and log.sharded:
+            if name in ("range", "grouped") and log.sharded:
                 want = {"error": ("Refused", None)}
+            if not store and compiles(name, args):
+                log.table_uploaded()                                 # (the adapter compiles before it calls: also when the read fails)
             got = capture(lambda: getattr(adapter, name)(*args))
             if store:
                 want, got = as_answer(want), as_answer(got)
@@ -1031,6 +1512,12 @@ def run(trace, adapter, expected=None, on_read=None):
             raise Mismatch(f"seed {trace['seed']}, profile {trace.get('profile')}, step {step} {op}: {what}\n"
                            f"replay with lifecycle.run(TRACE, adapter), TRACE = {head!r}")
     return model
+
+
+def compiles(name, args):
+    """does this read compile a mask on the table (the table's staged writes are uploaded then)"""
+    masks = args[3] if name == "grouped" else [args[-1]]
+    return any(on_table(m) for m in masks)
 
 
 def model_log(model):
@@ -1088,7 +1575,16 @@ def doc_fields(trace, j, key):
     f = {"par": str(int(rng_of(trace["seed"], key, 7).integers(0, 3))), "ver": str(key % 5)}
     if j % 7:
         f["grp"] = f"g{j % trace.get('groups', 40)}"
+    if trace.get("numeric"):
+        # ts: a decimal string of its own for nearly every version (the dictionary grows on almost every insert), now and then
+        # one of the hard ones of tests/golden/numeric_strings.tsv; price: about 20 values, absent for every fifth document
+        f["ts"] = TS_SPECIAL[key // 13 % len(TS_SPECIAL)] if key % 13 == 0 else str(key * 7919 % 1000003)
+        if j % 5:
+            f["price"] = f"{(key * 31 + j) % 20}.5"
     return f
+
+
+TS_SPECIAL = ("-0", "1e400", "n/a", "007", "9007199254740993")
 
 
 def resolve_store(trace, op):
@@ -1141,6 +1637,21 @@ def materialise_store(trace, op, model):
     if kind == "s_distinct":
         _, B, k, qkey, spec = op
         return "search_distinct_batch", (queries(seed, qkey, log, B, d), int(k), spec)
+    if kind == "s_with_filters":                                     # a filter per query: some None, some structurally equal
+        _, B, k, qkey, fkey = op
+        rng = rng_of(seed, fkey, 12)
+        pool = [NUMERIC_STORE_FILTERS[int(i)] for i in rng.integers(0, len(NUMERIC_STORE_FILTERS), 3)]
+        specs = [None if rng.random() < 0.25 else pool[int(rng.integers(0, 3))] for _ in range(B)]
+        return "search_batch_with_filters", (queries(seed, qkey, log, B, d), ks_of(k), specs)
+    if kind == "s_recommend":
+        _, B, k, rkey, spec, absent = op
+        rng = rng_of(seed, rkey, 13)
+        names = sorted(model.entries)
+        pick = lambda n: [names[int(i)] for i in rng.integers(0, len(names), n)] if names else ["doc0"] * n
+        reqs = [(pick(int(rng.integers(1, 5))), pick(int(rng.integers(0, 3)))) for _ in range(B)]
+        if absent or not names:
+            reqs[int(rng.integers(0, B))][0][0] = "nobody"
+        return "recommend_batch", (reqs, int(k), spec)
     raise ValueError(kind)
 
 
@@ -1197,7 +1708,7 @@ class _Gen:
                 self.last_mut = None
         else:
             apply_mutation(self.trace, op, self.m)
-            if op[0] in MUTATIONS or op[0] == "remove_many":
+            if op[0] in MUTATIONS12 or op[0] == "remove_many":
                 self.last_mut = "remove" if op[0] == "remove_many" else op[0]
 
     # -- ids
@@ -1494,9 +2005,269 @@ def large_schedule(seed, metric):
     return g.trace
 
 
+# ---------------------------------------------------------------------------------------------------------------- grouped, recommend, numeric
+# Schedules of their own for the three read paths added after 266122c: the old traces are dealt from one rng stream each, so a
+# new read kind in _Gen.read() would re-deal all of them.  The trace key "numbers" marks a schedule that holds them.
+PROFILES["nine"] = dict(d=64, d2=40, zero=True, misfit=False)
+PROFILES["nine-auto"] = dict(d=40, d2=64, zero=True, misfit=True, auto=0.3)
+
+NEW_PINNED = (
+    ("nine-euclid", 71, "nine", EUCLID, "all nine read kinds, the LUT set late and regrown twice; d = 64, reset to d = 40"),
+    ("nine-cosine", 72, "nine", COSINE, "the same with the zero-norm episode: grouped and recommend fail while the row lives"),
+    ("nine-dot", 73, "nine", DOT, "the same under Dot"),
+    ("nine-auto-euclid", 81, "nine-auto", EUCLID, "d = 40, reset to d = 64, auto-compaction on: recommend compacts before it folds; a misfit episode"),
+    ("nine-auto-cosine", 82, "nine-auto", COSINE, "auto-compaction with both error episodes"),
+    ("nine-auto-dot", 83, "nine-auto", DOT, "auto-compaction under Dot"),
+)
+
+
+def carries_numeric(op):
+    return op[0] == "grouped" and op[5] == "numeric" or op[0] != "grouped" and is_read(op) and op[-1] is not None and op[-1][0] == "numeric"
+
+
+class _Gen9(_Gen):
+    def __init__(self, seed, profile, metric):
+        super().__init__(seed, profile, metric)
+        self.trace["numbers"] = True
+        self.used = Counter()
+
+    def emit(self, op):
+        if is_read(op):
+            self.used[op[0]] += 1
+        super().emit(op)
+
+    def lut(self):
+        return self.m.numbers.size
+
+    def numeric_mask(self):
+        return ("numeric", str(self.rng.choice(LEAVES)), self.k())
+
+    def draw_mask9(self, after_numbers, none=0.6):
+        r = self.rng.random()
+        if after_numbers or (self.lut() and r > 0.75):
+            return self.numeric_mask()
+        if r < none:
+            return None
+        return self.draw_mask(False)
+
+    def draw_grouped_k(self, B):
+        if self.m.n_live() > GROUPED_MAX_K and self.rng.random() < 0.125:
+            return GROUPED_BIG_K
+        return self.draw_k(B)
+
+    def read(self, kind=None, absent=False):
+        after_numbers = self.last_mut == "numbers"
+        if kind is None:                                             # a kind this mutation has not been followed by yet; the least used one
+            after = self.last_mut
+            want = [r for r in (NUMERIC_CARRIERS if after == "numbers" else NEW_READS) if after and (after, r) not in self.pairs]
+            least = min(self.used[r] for r in READS9)
+            want = [r for r in want if self.used[r] <= least + 2]    # (no kind runs away: every kind keeps its 8 % of the reads)
+            kind = min(want or READS9, key=lambda r: (self.used[r], READS9.index(r)))
+        if kind in ("search", "sparse", "range"):
+            return super().read(kind)
+        B = self.draw_B()
+        if kind == "masked":
+            self.emit(("masked", B, self.draw_k(B), self.k(), self.numeric_mask() if after_numbers else self.draw_mask(False)))
+        elif kind == "numeric":
+            self.emit(("numeric", B, self.draw_k(B), self.k(), self.numeric_mask()))
+        elif kind == "by_id":
+            self.emit(("by_id", B, self.draw_k(B), self.k(), bool(absent), self.draw_mask9(after_numbers, 0.7)))
+        elif kind == "distinct":
+            self.emit(("distinct", B, self.draw_k(B), self.k(), self.draw_mask9(after_numbers, 0.6)))
+        elif kind == "grouped":
+            r = self.rng.random()
+            form = "numeric" if after_numbers or (self.lut() and r < 0.3) else "host" if r < 0.8 else "compiled"
+            k, qkey, G = self.draw_grouped_k(B), self.k(), int(self.rng.integers(1, 7))
+            for _ in range(20):                                      # a binding key under which some query has a row to return (a cap on the inputs)
+                op = ("grouped", B, k, qkey, G, form, self.k())
+                group_of, masks = materialise(self.trace, op, self.m)[1][2:]
+                if any(g == GROUP_NONE or self.m._live(masks[int(g)]).any() for g in group_of):
+                    break
+            self.emit(op)
+        elif kind == "recommend":                                    # an example key under which the read strikes or cuts an entry (a cap on the inputs)
+            k, mask = self.draw_k(B), self.draw_mask9(after_numbers, 0.6)
+            for _ in range(20):
+                op = ("recommend", B, k, self.k(), bool(absent), mask)
+                got = capture(lambda: self.m.recommend(*materialise(self.trace, op, self.m)[1]))
+                if "error" in got or got["rstats"][1] or got["cut"]:
+                    break
+                if _ == 4:                                           # (B = 1 names the last id whatever the key: a copy of a row with a lower id
+                    k = 10                                           # stands behind the cut of k = 1)
+            self.emit(op)
+
+    def mutate(self, kind):
+        rng = self.rng
+        if kind == "numbers":
+            L = self.lut()
+            if not L:
+                return self.emit(("numbers", 0, self.groups + 1, self.k()))
+            first = int(rng.integers(0, L))
+            self.emit(("numbers", first, int(rng.integers(1, L - first + 1)), self.k()))
+            if rng.random() < 0.5:                                   # a second call before the next compile: disjoint, or across the first
+                lo = int(rng.integers(0, max(1, first)))
+                self.emit(("numbers", lo, int(rng.integers(1, max(2, (first if rng.random() < 0.6 else L) - lo))), self.k()))
+        elif kind == "codes":                                        # codes from a range wider than the LUT: some have no number
+            n = int(rng.integers(1, 3000))
+            first = int(rng.integers(0, max(1, self.m.id_bound)))
+            self.emit(("codes", first, min(n, ID_LIMIT - first), self.k(), max(6, int(1.15 * self.lut()))))
+        else:
+            super().mutate(kind)
+
+    def grouped_all(self, B, k, G):
+        """a grouped read of G host masks whose binding key leaves no mask unreferenced and none without a live row: R = G"""
+        live = self.m.live_ids().astype(np.int64)
+        while True:
+            key = self.k()
+            group_of, masks = grouped_masks(self.trace["seed"], key, self.m, B, G, "host")
+            if len(set(group_of.tolist()) - {GROUP_NONE}) == G and all(m[1][live].any() for m in masks):
+                return self.emit(("grouped", B, k, self.k(), G, "host", key))
+
+    def codes_all(self):
+        self.emit(("codes", 0, self.m.id_bound, self.k(), max(self.groups, int(1.15 * self.lut()))))
+
+    def extend_lut(self, to):
+        """the LUT grows past its device capacity: overwrite a range, then the new tail; the next compile regrows the array"""
+        L = self.lut()
+        self.emit(("numbers", L // 2, L - L // 2, self.k()))
+        self.emit(("numbers", L, to - L, self.k()))
+        self.read("numeric")
+        self.codes_all()
+        self.read("masked")
+
+    def mix(self, steps, kinds=None):
+        kinds = kinds or ("add", "add", "upsert", "upsert", "readd", "remove", "remove", "remove_absent", "bulk", "compact",
+                          "compact_shrink", "auto_compact", "codes", "codes", "numbers", "numbers")
+        for _ in range(steps):
+            r = self.rng.random()
+            if r < 0.1:
+                self.toggle()
+                continue
+            self.turn += 1
+            missing = [m for m in kinds if any((m, rd_) not in self.pairs for rd_ in NEW_READS)]
+            kind = missing[self.turn % len(missing)] if missing and r < 0.75 else str(self.rng.choice(kinds))
+            self.mutate(kind)
+            self.read()
+            if self.rng.random() < 0.2:
+                self.read()
+
+    def build(self):
+        p, rng, e, k = self.p, self.rng, self.emit, self.k
+        e(("set", "sparse_filter", int(rng.choice((1, 2)))))
+        e(("set", "shadow", 1))
+        e(("set", "bounce", 64))
+        self.bulk(int(rng.integers(600, 900)), p["d"])
+        e(("codes", 0, 3000, k(), self.groups))
+        # no LUT yet: every numeric leaf is false, the Ne masks and the unfiltered queries of the same batch answer
+        e(("grouped", 9, 10, k(), 4, "numeric", k()))
+        self.mutate("numbers")
+        self.read("numeric")
+        e(("numbers", 0, 10, k()))                                   # two disjoint writes, then one across both, before the next compile
+        e(("numbers", 20, self.groups - 19, k()))
+        self.read("numeric")
+        e(("numbers", 3, 4, k()))
+        e(("numbers", 5, 20, k()))
+        e(("numbers", 0, 4, k()))
+        self.read("masked")
+        # two grouped reads of two masks each with a remove in between: the row count and the number of masks stay, the masks and
+        # the live bits do not
+        self.grouped_all(9, 113, 2)
+        e(("remove_many", 60, k()))
+        self.grouped_all(9, 113, 2)
+        self.mutate("upsert")                                        # the upserted id is the last example of a longer request
+        e(("recommend", 8, 10, k(), False, None))
+        self.mutate("numbers")
+        self.read("grouped")
+        self.mutate("numbers")
+        self.read("recommend")
+        for kind in NEW_READS:                                       # (ids to re-add are rare later: a compaction forgets them)
+            self.mutate("readd")
+            self.read(kind)
+        self.mix(22)
+        if p.get("auto"):
+            e(("auto_compact", p["auto"]))
+            self.read()
+        # grow through the doublings; a grouped read with unfiltered queries right behind a staged bulk, the LUT regrown on the way
+        for n, lut, form in ((1300, 1300, "host"), (2500, 2600, "compiled"), (4500, 0, "numeric")):
+            self.mutate("remove")
+            self.bulk(n)
+            e(("grouped", 9, 300, k(), 2, form, k()))
+            if lut:
+                self.extend_lut(lut)
+            self.mix(2)
+        e(("set", "shadow", 1))
+        self.bulk(SMALL_N - 300 - self.m.n_rows())
+        self.codes_all()
+        self.mutate("add")
+        self.read()
+        self.bulk(1000)                                              # across SMALL_N upward
+        self.mutate("add")
+        self.grouped_all(8, GROUPED_BIG_K, 3)                        # k > 2048: one ordinary masked search per group, rows staged
+        self.read()
+        self.mix(4)
+        # back down: most rows go, rows are staged, the compaction takes them along
+        e(("auto_compact", 0.0))
+        e(("set", "bounce", 64))
+        e(("remove_many", self.m.n_live() - 2600, k()))
+        self.read()
+        self.mutate("add")
+        self.mutate("upsert")
+        e(("compact",))
+        self.read()
+        e(("compact_shrink",))
+        self.read("grouped")
+        self.mix(4)
+        # the row count collides under grouped reads of the same number of masks
+        e(("compact",))
+        self.grouped_all(9, 10, 3)
+        n = self.m.n_rows()
+        e(("remove_many", 700, k()))
+        e(("set", "bounce", 0))
+        e(("compact_shrink",))
+        self.bulk(n - self.m.n_rows())
+        self.grouped_all(9, 10, 3)
+        self.read()
+        self.mix(4)
+        # auto-compaction inside a recommend read: the examples resolve to the rows AFTER it
+        e(("auto_compact", p.get("auto") or 0.25))
+        e(("remove_many", int(self.m.n_live() * 0.45), k()))
+        e(("recommend", 9, 10, k(), False, None))
+        if not p.get("auto"):
+            e(("auto_compact", 0.0))
+        if p["zero"] and self.trace["metric"] == COSINE:
+            z = self.fresh_ids(1)
+            e(("zero", z))
+            self.read("grouped")
+            self.read("recommend")
+            e(("remove", z))
+            self.read("numeric")
+        if p["misfit"]:
+            z = self.fresh_ids(1)
+            e(("misfit", z, p["d"] + 3))
+            self.read("recommend")
+            self.read("grouped")
+            e(("remove", z))
+            self.read("numeric")
+        self.read("recommend", absent=True)
+        self.mix(3)
+        # everything goes; the refill has another dimension
+        e(("remove_many", max(0, self.m.n_live() - 300), k()))
+        n = int(rng.integers(700, 1000))
+        e(("codes", 0, self.next_id + n, k(), max(self.groups, int(1.15 * self.lut()))))   # (the codes of the ids to come: the read behind the reset finds numbers)
+        e(("reset", n, p["d2"], self.fresh_ids(n), 1, k(), 0.15))
+        self.read(NEW_READS[self.trace["seed"] % 3])          # (the pinned seeds take every new kind here)
+        self.mix(18)
+        for m, r in [(m, r) for m in MUTATIONS12 for r in NEW_READS if m != "reset"]:   # what the draws left out, while the trace is short
+            if (m, r) not in self.pairs and len(self.trace["ops"]) < 236:
+                self.mutate(m)
+                self.read(r)
+        self.bulk(1500)
+        self.read()
+        return self.trace
+
+
 def schedule(seed, profile, metric=EUCLID):
     """a trace of about 200 ops: see _Gen.build for the phases, PROFILES for what differs between profiles"""
-    return _Gen(seed, profile, metric).build()
+    return (_Gen9 if profile in ("nine", "nine-auto") else _Gen)(seed, profile, metric).build()
 
 
 def pinned(name):
@@ -1506,6 +2277,9 @@ def pinned(name):
     for n, seed, metric, _ in LARGE_PINNED:
         if n == name:
             return large_schedule(seed, metric)
+    for n, seed, profile, metric, _ in NEW_PINNED:
+        if n == name:
+            return _Gen9(seed, profile, metric).build()
     raise KeyError(name)
 
 
@@ -1516,14 +2290,30 @@ STORE_PINNED = (
     ("store-dot-early", 53, DOT, dict(table_at="start", auto=0.0), "device filter from the start"),
     ("store-euclid-early", 54, EUCLID, dict(table_at="start", auto=0.4), "device filter from the start, auto-compaction"),
 )
+NEW_STORE_PINNED = (
+    ("store-numeric-early", 55, EUCLID, dict(table_at="start", auto=0.0), "numeric fields, device filter from the start"),
+    ("store-numeric-late", 56, COSINE, dict(table_at="mid", auto=0.4), "numeric fields, device filter mid-life, auto-compaction"),
+    ("store-numeric-again", 57, DOT, dict(table_at="start", auto=0.0, again=True), "device filter on, off mid-life and on again: the new table takes every number"),
+)
 STORE_FILTERS = (("eq", "par", "1"), ("ne", "par", "0"), ("exists", "grp"), ("and", [("exists", "grp"), ("ne", "ver", "2")]),
                  ("or", [("eq", "par", "2"), ("eq", "grp", "g3")]), ("eq", "grp", "g5"))
 
 
-def store_schedule(seed, metric, table_at="mid", auto=0.0, steps=110):
+NUMERIC_STORE_FILTERS = STORE_FILTERS + (
+    ("lt", "price", 7.5), ("and", [("ge", "ts", 200000), ("lt", "ts", 700000)]), ("or", [("eq", "grp", "g3"), ("gt", "price", 12.5)]),
+    ("gt", "ts", "-inf"), ("le", "price", 3.5))
+
+
+def store_schedule(seed, metric, table_at="mid", auto=0.0, steps=110, numeric=False, again=False):
+    """numeric: the schedules of the numeric fields (doc_fields: ts, price), the filter pool NUMERIC_STORE_FILTERS and the two
+    store reads s_recommend and s_with_filters; again: the device filter goes off and on again at two thirds of the life.
+    Without them the trace is, draw for draw, the one STORE_PINNED was dealt."""
     rng = np.random.default_rng([int(seed), 98])
     trace = {"seed": int(seed), "profile": "store", "metric": int(metric), "d": 40, "store": True, "groups": 40, "auto": float(auto),
              "table_at": table_at, "ops": []}
+    READS_, FILTERS_ = (STORE_READS + NEW_STORE_READS, NUMERIC_STORE_FILTERS) if numeric else (STORE_READS, STORE_FILTERS)
+    if numeric:
+        trace["numeric"] = True
     ops = trace["ops"]
     docs, gone, key = set(), set(), [0]
 
@@ -1532,10 +2322,10 @@ def store_schedule(seed, metric, table_at="mid", auto=0.0, steps=110):
         return key[0]
 
     def flt(none_ok=True):
-        return None if none_ok and rng.random() < 0.3 else STORE_FILTERS[int(rng.integers(0, len(STORE_FILTERS)))]
+        return None if none_ok and rng.random() < 0.3 else FILTERS_[int(rng.integers(0, len(FILTERS_)))]
 
     def read(i):
-        kind = STORE_READS[i % len(STORE_READS)]
+        kind = READS_[i % len(READS_)]
         kk = int(rng.choice((1, 10, 113)))
         if kind == "s_search":
             ops.append((kind, kk, k()))
@@ -1548,6 +2338,11 @@ def store_schedule(seed, metric, table_at="mid", auto=0.0, steps=110):
             ops.append((kind, k(), int(rng.choice((3, 40, 400))), int(rng.choice((8, 256))), flt()))
         elif kind == "s_similar":
             ops.append((kind, int(rng.choice(BATCHES)), kk, k(), flt(), bool(rng.random() < 0.1)))
+        elif kind == "s_recommend":
+            ops.append((kind, int(rng.choice(BATCHES)), max(kk, 10), k(), flt(), bool(rng.random() < 0.1)))
+        elif kind == "s_with_filters":
+            B = int(rng.choice(BATCHES))
+            ops.append((kind, B, tuple(int(x) for x in rng.choice(KS[:3], B)) if rng.random() < 0.5 else kk, k(), k()))
         else:
             ops.append((kind, int(rng.choice((1, 8, 9))), kk, k(), flt()))
 
@@ -1560,6 +2355,13 @@ def store_schedule(seed, metric, table_at="mid", auto=0.0, steps=110):
     for step in range(steps):
         if table_at == "mid" and step == steps // 3:
             ops.append(("set", "device_filter", 1))
+        if again and step == 2 * steps // 3:                         # off and on again: a new table, every column and LUT sent anew
+            ops.append(("set", "device_filter", 0))
+            ops.append(("s_insert", 1, k(), -1))
+            docs.add(1)
+            gone.discard(1)
+            ops.append(("set", "device_filter", 1))
+            ops.append(("s_prefiltered", 8, 10, k(), ("lt", "price", 7.5)))
         if step == steps // 2:                                       # by construction, whatever the draws bring: a compaction by hand
             ops.append(("s_insert", 0, k(), -1))                     # (an upsert: at least one dead row)
             ops.append(("s_compact",))                               # over the upserts so far, and a by-id read that names an unknown id
@@ -1606,6 +2408,9 @@ def store_pinned(name):
     for n, seed, metric, kw, _ in STORE_PINNED:
         if n == name:
             return store_schedule(seed, metric, **kw)
+    for n, seed, metric, kw, _ in NEW_STORE_PINNED:
+        if n == name:
+            return store_schedule(seed, metric, numeric=True, **kw)
     raise KeyError(name)
 
 
@@ -1613,9 +2418,16 @@ def store_pinned(name):
 def read_begins(trace, op, model):
     """What every read does to the model's state, without the oracle: True when the model refuses it (then nothing is uploaded,
     exactly as Model.search & co. raise before they upload), else the staged rows are uploaded and auto-compaction may run."""
+    if op[0] == "grouped" and model.sharded:
+        return True
+    if (op[5] != "host") if op[0] == "grouped" else (op[0] != "range" and op[-1] is not None and op[-1][0] in ("compiled", "numeric")):
+        model.table_uploaded()                                       # (the mask is compiled before the read is called)
     try:
         ids = materialise(trace, op, model)[1][0] if op[0] == "by_id" else None
-        model.refusal({"masked": "search", "sparse": "search"}.get(op[0], op[0]), ids)
+        if op[0] == "recommend":
+            pos, neg = requests_of(trace["seed"], op[3], model, op[1], op[4])
+            ids = [i for p, n in zip(pos, neg) for i in p + n]
+        model.refusal({"masked": "search", "sparse": "search", "numeric": "search", "recommend": "by_id"}.get(op[0], op[0]), ids)
     except Predicted:
         return True
     model.uploaded()
@@ -1636,7 +2448,7 @@ def coverage(trace):
             errors += read_begins(trace, op, m)
         else:
             apply_mutation(trace, op, m)
-            if op[0] in MUTATIONS or op[0] == "remove_many":
+            if op[0] in MUTATIONS12 or op[0] == "remove_many":
                 last = "remove" if op[0] == "remove_many" else op[0]
     return {"pairs": pairs, "counts": dict(m.counts), "reads": reads, "errors": errors}
 
@@ -1761,11 +2573,62 @@ class GpuIndexAdapter(EngineErrors):
         if mask[0] == "host":
             words, bits = dd.id_mask(mask[1])
             return call(id_mask=words, mask_bits=bits)
-        cm = self.table.compile([(self.table.NE, 0, int(mask[1]))], max(self.id_bound, 1))
+        cm = self._compile(mask)
         try:
             return call(compiled_mask=cm)
         finally:
             cm.release()
+
+    def _compile(self, mask):
+        """("compiled", code): Ne(column 0, code); ("numeric", leaf, const, code): Lt / Le / Gt / Ge(column 0, const), or
+        And([Ne(column 0, code), Ge(column 0, const)]) -- one program that reads the code column and the LUT"""
+        T, bits = self.table, max(self.id_bound, 1)
+        if mask[0] == "compiled":
+            return T.compile([(T.NE, 0, int(mask[1]))], bits)
+        _, leaf, const, code = mask
+        self.seen["numeric_compiles"] += 1
+        if leaf == "and":
+            return T.compile([(T.NE, 0, int(code)), (T.GE, 0, 0), (T.AND, 0, 0)], bits, consts=[const])
+        return T.compile([({"lt": T.LT, "le": T.LE, "gt": T.GT, "ge": T.GE}[leaf], 0, 0)], bits, consts=[const])
+
+    def set_numbers(self, first, values):
+        self.table.set_numbers(0, int(first), values)
+
+    def twin(self, model):
+        """a fresh index bulk-loaded with the model's survivors and a fresh table with its codes, presence bits and numbers"""
+        t = GpuIndexAdapter(self.vdb, model.metric)
+        rows, ids = model.survivors()
+        t.add_bulk(rows, ids)
+        t.set_codes(0, model.codes[:max(model.col_len, 1)])
+        if model.numbers.size:
+            t.set_numbers(0, model.numbers)
+        return t
+
+    def grouped(self, q, ks, group_of, masks):
+        k, kw = (int(ks), {}) if np.isscalar(ks) else (0, {"ks": ks})
+        cms = []
+        try:
+            if masks[0][0] == "host":
+                bits = len(masks[0][1])
+                kw.update(id_masks=np.stack([dd.id_mask(m[1])[0][:(bits + 63) // 64] for m in masks]), mask_bits=bits)
+            else:
+                cms = [self._compile(m) for m in masks]
+                kw.update(compiled_masks=cms)
+            gi, gd, gc = self._read(lambda: self.ix.search_batch_grouped(q, k, group_of, **kw))
+        finally:
+            for cm in cms:
+                cm.release()
+        st = self.ix.grouped_stats()
+        for j, key in ((2, "grouped_scan"), (3, "grouped_fallback"), (4, "grouped_unfiltered"), (6, "grouped_tiles")):
+            self.seen[key] += st[j]
+        return {"lists": lists_of(gi, gd, gc), "gstats": st[:6]}
+
+    def recommend(self, pos, neg, ks, mask=None):
+        gi, gd, gc = self._read(lambda: self._masked(mask, lambda **kw: self.ix.recommend_batch(pos, neg, ks, **kw)))
+        st = self.ix.recommend_stats()
+        self.seen["recommend_examples"] += st[1]
+        self.seen["recommend_struck"] += st[2]
+        return {"lists": lists_of(gi, gd, gc), "rstats": st[1:4]}
 
     def _read(self, call):
         try:
@@ -1869,6 +2732,7 @@ class GpuStoreAdapter(EngineErrors):
     def set(self, name, value):
         if name == "device_filter":
             self.store.set_device_filter(bool(value))
+            self.seen["table_switched_on"] += bool(value)
         else:
             self.store.set_sparse_filter(int(value))
 
@@ -1895,6 +2759,7 @@ class GpuStoreAdapter(EngineErrors):
     def search_batch_prefiltered(self, q, ks, spec):
         qs = [(self.vdb.Vector(q[b]), k_of(ks, b)) for b in range(len(q))]
         self.seen["prefiltered_compiled" if self.store.device_filter() else "prefiltered_host"] += 1
+        self.seen["prefiltered_compiled_on_a_second_table"] += self.store.device_filter() and self.seen["table_switched_on"] >= 2
         return [self._out(r) for r in self._read(lambda: self.store.search_batch_prefiltered(qs, flt_of(self.vdb, spec)))]
 
     def search_within(self, q, radius, limit, spec):
@@ -1905,6 +2770,19 @@ class GpuStoreAdapter(EngineErrors):
         st = self.store.index().by_id_stats()
         self.seen["by_id_struck"] += st[1]
         self.seen["by_id_cut"] += st[2]
+        return out
+
+    def search_batch_with_filters(self, q, ks, specs):
+        qs = [(self.vdb.Vector(q[b]), k_of(ks, b)) for b in range(len(q))]
+        out = [self._out(r) for r in self._read(lambda: self.store.search_batch_with_filters(qs, [flt_of(self.vdb, s) for s in specs]))]
+        st = self.store.index().grouped_stats()
+        self.seen["grouped_scan"] += st[2]
+        self.seen["grouped_unfiltered"] += st[4]
+        return out
+
+    def recommend_batch(self, requests, k, spec):
+        out = [self._out(r) for r in self._read(lambda: self.store.recommend_batch(requests, k, flt_of(self.vdb, spec)))]
+        self.seen["recommend_examples"] += self.store.index().recommend_stats()[1]
         return out
 
     def search_distinct_batch(self, q, k, spec):

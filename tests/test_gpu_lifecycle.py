@@ -19,7 +19,13 @@ capacity change; that the shadow is READ is the engine's shadow_rows flag, asser
 runs every range read is refused, so more than 15 % of their reads expect an error (10-18 % refusals plus the episodes).
 
 Twin equality: on a sample of plain searches the answer equals that of a fresh index bulk-loaded with the survivors, so a
-failure says whether the model or the life before the read is at fault."""
+failure says whether the model or the life before the read is at fault.
+
+Grouped, recommend and numeric-filter reads (lifecycle.NEW_PINNED, NEW_STORE_PINNED): six index schedules of all nine read
+kinds through a plain handle (grouped_stats [0]-[5] and recommend_stats [1]-[3] compared with the model read by read; the
+grouped scan, the per-group fallback of k > 2048, unfiltered queries, folded examples, struck entries and numeric compiles
+must all have been counted; twins with a fresh MetaTable on every fourth grouped / recommend read) and through a sharded
+handle (every grouped read refused), three store schedules with numeric fields.  E_g > 131072 is out of reach at 20 000 rows."""
 import numpy as np
 import pytest
 
@@ -31,6 +37,8 @@ pytestmark = pytest.mark.gpu
 NAMES = [p[0] for p in lc.PINNED]
 LARGE_NAMES = [p[0] for p in lc.LARGE_PINNED]
 STORE_NAMES = [p[0] for p in lc.STORE_PINNED]
+NEW_NAMES = [p[0] for p in lc.NEW_PINNED]
+NEW_STORE_NAMES = [p[0] for p in lc.NEW_STORE_PINNED]
 _TRACES = {}
 
 
@@ -128,6 +136,92 @@ def test_sharded_lifecycle(vdb, name):
     assert seen["distinct_a"] > 0 and seen["distinct_b"] > 0, seen
     assert seen["by_id_struck"] > 0 and seen["by_id_cut"] > 0, seen
     assert seen["compactions"] >= 4 and meant["twins"] >= 2, (seen, meant)
+
+
+def life9(vdb, name, devices=None):
+    """one schedule of the nine read kinds (lifecycle.NEW_PINNED) through an index adapter: every read against the model, the
+    counters grouped_stats [0]-[5] and recommend_stats [1]-[3] with it (lifecycle.diff: "gstats", "rstats"); on a plain handle
+    every fourth grouped and every fourth recommend read again on a twin -- a fresh index bulk-loaded with the survivors, a fresh
+    MetaTable with the model's codes, presence bits and numbers.  Returns the adapter's counters, what was met, the model."""
+    t = trace_of(name)
+    ad = lc.GpuIndexAdapter(vdb, t["metric"], devices=devices)
+    meant, nth = lc.Counter(), lc.Counter()
+
+    def on_read(step, op, model, args, got):
+        if "error" in got:
+            meant[(op[0], got["error"][0])] += 1
+            return
+        meant[(op[0], "answered")] += 1
+        meant["numeric_answered"] += lc.carries_numeric(op)
+        if op[0] in ("grouped", "recommend") and not ad.sharded:
+            nth[op[0]] += 1
+            if nth[op[0]] % 4 == 0:
+                twin = ad.twin(model)
+                try:
+                    again = getattr(twin, op[0])(*args)
+                finally:
+                    twin.close()
+                what = lc.diff(got, again)
+                assert what is None, (name, step, op, "the twin answers otherwise", what)
+                meant["twins_" + op[0]] += 1
+    try:
+        model = lc.run(t, ad, expected=lc.slots(name, t), on_read=on_read)
+    finally:
+        ad.close()
+    print(name, "sharded" if devices else "plain", dict(ad.seen), dict(meant), model.counts)
+    return ad.seen, meant, model
+
+
+@pytest.mark.parametrize("name", NEW_NAMES)
+def test_index_lifecycle_nine(vdb, name):
+    """grouped, recommend and numeric-masked reads in a long life of the index: doublings with the shadow on, a shrinking
+    compaction that collides the row count, a reset to another dimension, auto-compaction inside the read, the zero-norm and
+    misfit episodes, the LUT regrown twice between compiles, codes beyond the LUT.  E_g > 131072 is not reached (20 000 rows)."""
+    seen, meant, model = life9(vdb, name)
+    assert seen["grouped_scan"] > 0 and seen["grouped_fallback"] > 0 and seen["grouped_unfiltered"] > 0 and seen["grouped_tiles"] > 0, seen
+    assert seen["recommend_examples"] > 0 and seen["recommend_struck"] > 0 and seen["numeric_compiles"] > 0, seen
+    assert model.counts["regrows"] >= 2, model.counts
+    assert meant["twins_grouped"] >= 1 and meant["twins_recommend"] >= 1, meant
+    assert all(meant[(kind, "answered")] > 0 for kind in lc.READS9) and meant["numeric_answered"] > 0, meant
+    t = trace_of(name)
+    if t["metric"] == lc.COSINE:
+        assert meant[("grouped", "InvalidVector")] >= 1 and meant[("recommend", "InvalidVector")] >= 1, meant
+    if any(op[0] == "misfit" for op in t["ops"]):
+        assert meant[("grouped", "DimensionMismatch")] >= 1 and meant[("recommend", "DimensionMismatch")] >= 1, meant
+    assert meant[("recommend", "VectorNotFound")] >= 1, meant
+
+
+@pytest.mark.parametrize("name", NEW_NAMES)
+def test_sharded_lifecycle_nine(vdb, name):
+    """the same schedules through one sharded handle: every grouped read is refused (as every range read is), recommend --
+    examples gathered per shard -- and the numeric-masked reads are answered, recommend_stats as on the plain handle"""
+    seen, meant, model = life9(vdb, name, devices=[0, 0, 0])
+    t = trace_of(name)
+    assert meant[("grouped", "Refused")] == sum(1 for op in t["ops"] if op[0] == "grouped") > 0, meant
+    assert meant[("grouped", "answered")] == 0 and seen["grouped_scan"] + seen["grouped_fallback"] == 0, (seen, meant)
+    assert meant[("recommend", "answered")] > 0 and meant[("numeric", "answered")] > 0 and meant["numeric_answered"] > 0, meant
+    assert seen["recommend_examples"] > 0 and seen["recommend_struck"] > 0 and seen["numeric_compiles"] > 0, seen
+
+
+@pytest.mark.parametrize("name", NEW_STORE_NAMES)
+def test_store_lifecycle_with_numeric_fields(vdb, name):
+    """VectorStore with the numeric fields ts and price: recommend_batch and search_batch_with_filters beside the six older
+    reads, numeric filters compiled on the device table while the dictionary of ts grows on nearly every insert; in one schedule
+    the device filter goes off and on again, and the new table must hold every number the old one had"""
+    t = lc.store_pinned(name)
+    ad = lc.GpuStoreAdapter(vdb, t["metric"], auto_compact=t["auto"])
+    kinds = lc.Counter()
+    try:
+        lc.run(t, ad, expected=lc.slots(name, t), on_read=lambda step, op, model, args, got: kinds.update([(op[0], "error" in got)]))
+    finally:
+        ad.close()
+    print(name, dict(ad.seen), dict(kinds))
+    seen = ad.seen
+    assert all(kinds[(k, False)] > 0 for k in lc.STORE_READS + lc.NEW_STORE_READS), kinds
+    assert any(e for (_, e) in kinds), kinds                                                   # a predicted error was met
+    assert seen["prefiltered_compiled"] > 0 and seen["grouped_scan"] > 0 and seen["grouped_unfiltered"] > 0 and seen["recommend_examples"] > 0, seen
+    if name == "store-numeric-again":                                                          # compiled before AND after the table was rebuilt
+        assert seen["table_switched_on"] == 2 and 0 < seen["prefiltered_compiled_on_a_second_table"] < seen["prefiltered_compiled"], seen
 
 
 @pytest.mark.parametrize("name", STORE_NAMES)

@@ -6,7 +6,15 @@
     reset with another dimension, an auto-compaction and a compaction with staged rows;
   * the caps on the inputs: at most 15 % of the reads expect an error, no read kind is below 8 % of the reads, every answered
     read returns a row for some query.  (Counted on the traces, i.e. for a plain handle.  A sharded handle refuses every range
-    read on top of that, 10-18 % of the reads, so the 15 % cap does NOT hold for the sharded runs of the same schedules.)"""
+    read on top of that, 10-18 % of the reads, so the 15 % cap does NOT hold for the sharded runs of the same schedules.)
+
+The grouped, recommend and numeric-filter reads (six index schedules NEW_PINNED, three store schedules NEW_STORE_PINNED) get
+the same proofs further down: the 19 older traces have not moved (digests), the reference adapter passes, mutants 13-21 fall on
+every new index schedule and 22 / 23 on the store schedules they apply to, every (mutation, first read) pair of the three new
+read kinds with all twelve mutations, (numbers, r) for every r that can carry a numeric mask, two LUT regrows per schedule,
+and the caps: the old three, at most a quarter of the grouped per-query answers empty, 80 % of the numeric masks keeping
+5-95 % of the live rows, every recommend read striking or cutting an entry.  (A sharded handle refuses every grouped read too:
+with the range reads that is about a fifth of the reads of these schedules.)"""
 from collections import Counter
 
 import pytest
@@ -172,6 +180,214 @@ def test_caps_on_the_inputs():
     cosine = [p[0] for p in lc.PINNED if p[3] == lc.COSINE]
     assert cosine and all(any(op[0] == "zero" for op in trace_of(n)["ops"]) for n in cosine)
     assert any(op[0] == "misfit" for n in NAMES for op in trace_of(n)["ops"])
+
+
+# ------------------------------------------------------------------ grouped, recommend and numeric-filter reads (lifecycle.NEW_PINNED)
+# The old schedules are dealt from one rng stream each: a digest of repr(trace), computed on the commit before the new read kinds
+# came, says that none of them moved.
+OLD_DIGESTS = {
+    "even-euclid": "e3c25ab8794da1d6", "even-cosine": "61506c2cffa0b9a1", "even-dot": "638fe53dbd8255aa",
+    "odd-euclid": "7545cbbbcc320b2c", "odd-cosine": "03901372ac228caf", "odd-dot": "3ab466341078dfe6",
+    "misfit-euclid": "45c935e1dcec2e98", "misfit-cosine": "4766466f5468b25a", "misfit-dot": "89f09b990182f93a",
+    "auto-euclid": "a1d30fa684078625", "auto-cosine": "db042d76e808a0e0", "auto-dot": "d6501246ae78ff2e",
+    "large-euclid": "19f8ab73d25a6c64", "large-cosine": "ce8b5e3e9f7eeba7", "large-dot": "83bed28f1a60e808",
+    "store-euclid-late": "74cb6a156f810aa7", "store-cosine-late": "05c2015431d3966e", "store-dot-early": "6dd6e11382a16081",
+    "store-euclid-early": "65aa23185b83342d",
+}
+NEW_NAMES = [p[0] for p in lc.NEW_PINNED]
+
+
+def test_the_old_schedules_do_not_move():
+    import hashlib
+    assert sorted(OLD_DIGESTS) == sorted(NAMES + LARGE_NAMES + STORE_NAMES) and len(OLD_DIGESTS) == 19
+    got = {name: hashlib.sha256(repr(trace_of(name)).encode()).hexdigest()[:16] for name in OLD_DIGESTS}
+    assert got == OLD_DIGESTS, {n: d for n, d in got.items() if d != OLD_DIGESTS[n]}
+    assert lc.READS == ("search", "masked", "sparse", "range", "by_id", "distinct") and len(lc.STORE_READS) == 6 and len(lc.STORE_FILTERS) == 6
+    assert not any(op[0] in lc.NEW_READS or op[0] == "numbers" for n in NAMES + LARGE_NAMES for op in trace_of(n)["ops"])
+
+
+@pytest.mark.parametrize("name", NEW_NAMES)
+def test_reference_adapter_passes_the_nine_read_kinds(name):
+    """the reference adapter passes, and the caps on the answers hold with the model alone: every answered read returns a row
+    for some query; at most a quarter of the per-query answers of the grouped reads are empty; at least 80 % of the reads under
+    a numeric mask keep between 5 % and 95 % of the live rows; every recommend read strikes an entry, or cuts one, for some request"""
+    t = trace_of(name)
+    empty, seen, idle = [], Counter(), []
+
+    def answered(step, op, model, args, got):
+        if "error" in got:
+            return
+        if not any(len(l[0]) for l in got["lists"]):
+            empty.append((step, op))
+        want = lc.slots(name, t)[step][2]
+        if op[0] == "grouped":
+            seen["grouped_answers"] += len(want["lists"])
+            seen["grouped_empty"] += sum(1 for l in want["lists"] if not len(l[0]))
+            for j, key in ((2, "scan"), (3, "fallback"), (4, "unfiltered")):
+                seen[key] += want["gstats"][j]
+        elif op[0] == "recommend" and not want["rstats"][1] and not want["cut"]:
+            idle.append((step, op))
+        if lc.carries_numeric(op) and op[0] != "grouped":
+            ok = lc.mask_ok(args[-1], model.codes, model.present, model.numbers)
+            share = int((model.alive & lc.ok_of_ids(ok, model.ids)).sum()) / model.n_live()
+            seen["numeric_reads"] += 1
+            seen["numeric_mid"] += 0.05 <= share <= 0.95
+    lc.run(t, lc.RefIndex(t["metric"]), expected=lc.slots(name, t), on_read=answered)
+    print(name, dict(seen))
+    assert not empty, empty
+    assert not idle, idle
+    assert 4 * seen["grouped_empty"] <= seen["grouped_answers"], seen
+    assert seen["numeric_reads"] >= 8 and seen["numeric_mid"] >= 0.8 * seen["numeric_reads"], seen
+    assert seen["scan"] > 0 and seen["fallback"] > 0 and seen["unfiltered"] > 0, seen      # what the GPU runs must see the engine count
+
+
+@pytest.mark.parametrize("name", NEW_NAMES[:2])
+def test_reference_adapter_refuses_grouped_when_sharded(name):
+    t = trace_of(name)
+    seen = Counter()
+    lc.run(t, lc.RefIndex(t["metric"], sharded=True), expected=lc.slots(name, t), on_read=lambda s, op, m, a, got: seen.update([(op[0], "error" in got)]))
+    for kind in ("range", "grouped"):
+        assert seen[(kind, True)] == sum(1 for op in t["ops"] if op[0] == kind) and not seen[(kind, False)]
+    assert seen[("recommend", False)] > 0 and seen[("numeric", False)] > 0
+
+
+# the schedules a new mutant must fall on: all six -- each holds the interleaving the mutant needs by construction (_Gen9.build)
+NEW_APPLIES = {number: NEW_NAMES for number in lc.NEW_INDEX_MUTANTS}
+
+
+@pytest.mark.parametrize("number", sorted(lc.NEW_INDEX_MUTANTS))
+def test_new_index_mutant_is_caught(number):
+    mutant = lc.NEW_INDEX_MUTANTS[number]
+    caught = caught_by(lambda t: mutant(t["metric"]), NEW_NAMES)
+    print(number, mutant.__name__, len(caught), "of", len(NEW_NAMES), caught)
+    assert sorted(caught) == sorted(NEW_APPLIES[number]), sorted(set(NEW_APPLIES[number]) - set(caught))
+    kinds = {13: ("grouped",), 14: ("grouped",), 15: ("grouped",), 16: ("recommend",), 17: ("recommend",), 18: ("recommend",)}.get(number)
+    if kinds:                                                        # a grouped defect falls on a grouped read, a recommend defect on a recommend read
+        assert all(any(f"('{k}'," in v for k in kinds) for v in caught.values()), caught
+    else:                                                            # a LUT defect on a read under a numeric mask
+        assert all("'numeric'" in v for v in caught.values()), caught
+
+
+def test_coverage_of_the_nine_read_kinds():
+    covs = {name: lc.coverage(trace_of(name)) for name in NEW_NAMES}
+    pairs = set().union(*(c["pairs"] for c in covs.values()))
+    missing = [(m, r) for m in lc.MUTATIONS12 for r in lc.NEW_READS if (m, r) not in pairs]
+    assert not missing, missing
+    after_numbers = set()                                            # (numbers, r) with the numeric mask IN that read
+    for name in NEW_NAMES:
+        ops = trace_of(name)["ops"]
+        for a, b in zip(ops, ops[1:]):
+            if a[0] == "numbers" and lc.is_read(b) and lc.carries_numeric(b):
+                after_numbers.add(b[0])
+    assert after_numbers == set(lc.NUMERIC_CARRIERS), after_numbers
+    for name, c in covs.items():
+        n = c["counts"]
+        assert n["up"] >= 1 and n["down"] >= 1, (name, n)
+        assert n["doublings"] >= 3 and n["shrinks"] >= 1 and n["dim_resets"] >= 1, (name, n)
+        assert n["auto_compactions"] >= 1 and n["compact_with_staged"] >= 1 and n["regrows"] >= 2, (name, n)
+        assert 150 <= len(trace_of(name)["ops"]) <= 250, (name, len(trace_of(name)["ops"]))
+        assert trace_of(name)["numbers"] is True
+
+
+def test_sizes_and_caps_of_the_nine_read_kinds():
+    """the limits of the twelve old schedules; at most 15 % of the reads expect an error (counted on the traces, i.e. for a plain
+    handle: a sharded handle refuses every range AND every grouped read on top, about a fifth of the reads), no kind below 8 %"""
+    for name in NEW_NAMES:
+        t = trace_of(name)
+        m = lc.Model(t["metric"])
+        peak, low, dims, codes_past_lut = 0, 10 ** 9, set(), 0
+        for op in t["ops"]:
+            if lc.is_read(op):
+                peak, low = max(peak, m.n_rows()), min(low, m.n_live())
+                dims.add(m.d)
+                if m.numbers.size and lc.carries_numeric(op):
+                    codes_past_lut += bool((m.codes[m.ids[m.alive].astype("int64")] >= m.numbers.size).any())
+                m.uploaded()
+            else:
+                lc.apply_mutation(t, op, m)
+            assert m.id_bound <= lc.ID_LIMIT
+        assert lc.SMALL_N < peak <= 20_000 and low <= 1000, (name, peak, low)
+        assert dims == {40, 64} and codes_past_lut >= 3, (name, dims, codes_past_lut)
+        c = lc.coverage(t)
+        reads = Counter(c["reads"])
+        total = sum(reads.values())
+        assert c["errors"] <= 0.15 * total, (name, c["errors"], total)
+        assert set(reads) == set(lc.READS9) and min(reads.values()) >= 0.08 * total, (name, reads)
+        ops = t["ops"]
+        assert {op[1] for op in ops if op[0] in lc.NEW_READS} == set(lc.BATCHES), name
+        ks = [op[2] for op in ops if op[0] in lc.NEW_READS]
+        assert {k for k in ks if isinstance(k, int)} == set(lc.KS) | {lc.GROUPED_BIG_K} and any(isinstance(k, tuple) for k in ks), name
+        forms = Counter(op[5] for op in ops if op[0] == "grouped")
+        assert set(forms) == {"host", "compiled", "numeric"} and len({op[4] for op in ops if op[0] == "grouped"}) >= 3, (name, forms)
+        assert any(op[0] == "recommend" and op[4] for op in ops), name                       # an absent example: VectorNotFound
+    assert {op[4] for n in NEW_NAMES for op in trace_of(n)["ops"] if op[0] == "grouped"} == {1, 2, 3, 4, 5, 6}   # G, over the set
+    cosine = [p[0] for p in lc.NEW_PINNED if p[3] == lc.COSINE]
+    assert cosine and all(any(op[0] == "zero" for op in trace_of(n)["ops"]) for n in cosine)
+    assert any(op[0] == "misfit" for n in NEW_NAMES for op in trace_of(n)["ops"])
+
+
+def test_a_new_failure_shrinks():
+    t = trace_of(NEW_NAMES[0])
+    make = lambda: lc.RecommendFoldsOldRow(t["metric"])
+    small = lc.shrink(t, make)
+    assert small is not None and len(small["ops"]) <= 6, small and small["ops"]   # a bulk, an upsert, the recommend read (and little more)
+    assert small["ops"][-1][0] == "recommend"
+    with pytest.raises(lc.Mismatch):
+        lc.run(small, make())
+    lc.run(small, lc.RefIndex(t["metric"]))
+
+
+NEW_STORE_NAMES = [p[0] for p in lc.NEW_STORE_PINNED]
+
+
+def new_store_trace(name):
+    if name not in _TRACES:
+        _TRACES[name] = lc.store_pinned(name)
+    return _TRACES[name]
+
+
+@pytest.mark.parametrize("name", NEW_STORE_NAMES)
+def test_store_reference_passes_with_numeric_fields(name):
+    """StoreSim over RefIndex passes the store schedules of the numeric fields: s_with_filters stated as search_batch_prefiltered
+    query by query, s_recommend as the host composition; every read kind keeps its 8 %, every answered read returns a row"""
+    import ast
+    vdb = load_package()
+    t = new_store_trace(name)
+    assert ast.literal_eval(repr(t)) == t and t["numeric"] is True                 # plain data, "-inf" included
+    empty, kinds = [], Counter()
+
+    def answered(step, op, model, args, got):
+        kinds[op[0]] += 1
+        if "error" not in got and not any(len(l[0]) for l in got["lists"]):
+            empty.append((step, op))
+    lc.run(t, lc.StoreSim(vdb, lc.RefIndex(t["metric"])), expected=lc.slots(name, t), on_read=answered)
+    assert not empty, empty
+    assert set(kinds) == set(lc.STORE_READS + lc.NEW_STORE_READS) and min(kinds.values()) >= 0.08 * sum(kinds.values()), kinds
+    fields = [f for call in (c for op in t["ops"] if not lc.is_read(op) for c in lc.resolve_store(t, op)) if call[0] == "insert" for f in [call[1][2]]]
+    ts = [f["ts"] for f in fields]
+    assert len(set(ts)) >= 0.9 * len(ts) and set(lc.TS_SPECIAL) <= set(ts), (len(set(ts)), len(ts))   # the dictionary grows on nearly every insert
+    assert 15 <= len({f["price"] for f in fields if "price" in f}) <= 20 and 0.15 < sum("price" not in f for f in fields) / len(fields) < 0.25
+    used = {repr(op[4]) for op in t["ops"] if op[0] in ("s_prefiltered", "s_similar", "s_recommend", "s_distinct", "s_within")}
+    assert used >= {repr(f) for f in lc.NUMERIC_STORE_FILTERS[len(lc.STORE_FILTERS):]}, used          # every numeric filter of the pool is drawn
+    switches = [op[2] for op in t["ops"] if op[:2] == ("set", "device_filter")]
+    assert switches == {"store-numeric-early": [1], "store-numeric-late": [1], "store-numeric-again": [1, 0, 1]}[name]
+
+
+@pytest.mark.parametrize("lut,applies", [("stale_sent", ["store-numeric-again"]), ("bulk_only", NEW_STORE_NAMES)])
+def test_store_lut_mutant_is_caught(lut, applies):
+    """22. _lut_sent survives set_device_filter(False) / (True): the new table never receives the old numbers (applies where the
+    filter goes off and on again).  23. the numbers of new dictionary values are forwarded on a bulk attach only (everywhere)."""
+    vdb = load_package()
+    caught = {}
+    for name in NEW_STORE_NAMES:
+        t = new_store_trace(name)
+        try:
+            lc.run(t, lc.StoreSim(vdb, lc.RefIndex(t["metric"]), lut=lut), expected=lc.slots(name, t))
+        except lc.Mismatch as e:
+            caught[name] = str(e).split("\n")[0]
+    print(lut, caught)
+    assert sorted(caught) == sorted(applies), caught
+    assert all(any(w in v for w in ("'lt'", "'le'", "'gt'", "'ge'", "s_with_filters")) for v in caught.values()), caught
 
 
 def test_traces_are_plain_data_and_replay():
