@@ -81,7 +81,8 @@ void vdb_flat_destroy(vdb_flat_index *h);
  *
  * Not available on a sharded handle: the two-half / ticket forms of the device search (begin/finish, submit/wait),
  * vdb_flat_distances_batch, the range searches (vdb_flat_range_search_batch, vdb_flat_range_search_batch_device), the grouped
- * searches (vdb_flat_search_batch_grouped, vdb_flat_search_batch_grouped_filtered, vdb_flat_grouped_stats), the
+ * searches (vdb_flat_search_batch_grouped, vdb_flat_search_batch_grouped_filtered, vdb_flat_grouped_stats), the diverse
+ * top-k (vdb_flat_search_batch_mmr, vdb_flat_search_batch_mmr_filtered, vdb_flat_mmr_stats), the
  * vdb_flat_debug_* probes and vdb_flat_search_batch_sharded (that one is the process-per-GPU form of the same exchange,
  * vdb_shard.h); they return VDB_ERR_INVALID_ARGUMENT.
  */
@@ -555,6 +556,54 @@ int vdb_flat_recommend_batch_filtered(vdb_flat_index *h, const uint64_t *example
                                       const vdb_meta_mask *mask, size_t kstride,
                                       uint64_t *out_ids, float *out_dists, size_t *out_counts);
 int vdb_flat_recommend_stats(const vdb_flat_index *h, uint64_t out[4]);
+
+/*
+ * DIVERSE TOP-K (MAXIMAL MARGINAL RELEVANCE): k results that are not all the same thing (no reference counterpart; a caller would
+ * search at depth m, get_vector every candidate and run an O(k m dim) loop on the host).  A request is a query q, a count k, a
+ * candidate depth m and a trade-off lambda, 1 <= k <= m <= VDB_MMR_MAX_CANDIDATES, lambda an f32 in [0, 1].
+ *  1. Candidates: what vdb_flat_search_batch returns for q with depth m under the same mask -- (id_i, d_i), i = 0..c-1, ascending by
+ *     (distance, unsigned id), c = min(m, eligible rows); ids, order, distance bits and errors are the search's own.  The POSITION
+ *     i in this list is the tie-break of everything below.
+ *  2. Pair distance: D(i, j) is DistanceMetric::distance between the stored rows of candidates i and j in the reference's f32
+ *     operation order (the exact-order folds; the norms of Cosine are sqrt(sum x*x) in the order of vector.rs:35-37, recomputed
+ *     from the rows).  It is symmetric bit for bit under all three metrics.
+ *  3. Selection: mu = 1.0f - lambda, computed once on the host in f32.  Pick 1 is candidate 0, its score lambda * d_0 (one
+ *     multiply).  After pick s_t, IF another pick follows, D(i, s_t) is evaluated for every candidate i not yet picked, then
+ *     near_i = min(near_i, D(i, s_t)) (near_i starts at +inf), then score_i = lambda * d_i - mu * near_i: two multiplies and one
+ *     subtraction, each rounded on its own, never contracted.  The next pick is the unpicked candidate with the smallest
+ *     (score is NaN, score, position): IEEE < compares the scores, so -0 equals +0, and a NaN score ranks after every number.
+ *     The selection stops after min(k, c) picks.
+ *  4. Outputs: out_ids / out_dists hold the picks in pick order, out_dists[t] the d of the pick in the bits of the search;
+ *     out_scores (may be NULL) the score each pick was chosen with; out_counts[b] = min(k_b, c_b).
+ *  5. ks: one k per query, or NULL for k.  The answer for k_b is the first k_b picks of the answer for any larger k at the same m
+ *     (greedy selection is prefix-stable) -- except for the NaN rule below, which covers only the pairs the k_b picks evaluate.
+ *  6. lambdas: one lambda per query, or NULL for lambda.
+ *  7. lambda = 1 returns the first k entries of the plain search, ids and distance bits, whenever the evaluated pair distances are
+ *     finite.
+ *  8. Errors, in this order.  An empty index or k = 0 (every k of ks) gives counts 0 before any other check.
+ *     VDB_ERR_INVALID_ARGUMENT before any device work: a null array; a NaN lambda or one outside [0, 1]; m = 0;
+ *     m > VDB_MMR_MAX_CANDIDATES; the largest k above m; a sharded handle (the candidates' rows live on several devices).  Then
+ *     everything the search at depth m reports.  Then VDB_ERR_NAN when an EVALUATED pair distance (item 3) is NaN for any query of
+ *     the batch.
+ *  9. Locking, tickets and flushing are those of vdb_flat_search_batch.  _filtered is the same call under a compiled mask.
+ * The selection runs where the rows are: the search's ids come down once, the host's id -> row map turns them into row numbers
+ * (under the handle's lock: none can be missing), nq x depth uint32 go up, and mmr_select_kernel (csrc/kernels_mmr.hip), one
+ * workgroup per query, runs the k_b dependent steps over rows that never leave HBM.  It evaluates the pairs of item 3 and no
+ * others: no m x m matrix exists anywhere.  The direct mapped-memory path of small indexes is not taken.
+ * vdb_flat_mmr_stats describes the last call on the handle: [0] queries, [1] the depth the search ran at, [2] candidates summed
+ * over the queries, [3] pair distances evaluated = sum_b sum_{t=1}^{count_b - 1} (c_b - t), [4] rows returned, [5] host ns spent
+ * turning candidate ids into device rows (download, map, upload), [6], [7] 0.
+ */
+#define VDB_MMR_MAX_CANDIDATES 1024
+int vdb_flat_search_batch_mmr(vdb_flat_index *h, const float *queries, size_t nq, size_t dim, const size_t *ks, size_t k,
+                              size_t candidates, const float *lambdas, float lambda,
+                              const uint64_t *id_mask, size_t mask_bits, size_t kstride,
+                              uint64_t *out_ids, float *out_dists, float *out_scores, size_t *out_counts);
+int vdb_flat_search_batch_mmr_filtered(vdb_flat_index *h, const float *queries, size_t nq, size_t dim, const size_t *ks, size_t k,
+                                       size_t candidates, const float *lambdas, float lambda,
+                                       const vdb_meta_mask *mask, size_t kstride,
+                                       uint64_t *out_ids, float *out_dists, float *out_scores, size_t *out_counts);
+int vdb_flat_mmr_stats(const vdb_flat_index *h, uint64_t out[8]);
 
 /*
  * ONE NEAREST ROW PER GROUP: the k nearest documents, videos, products of a store of chunked items, each represented by its nearest

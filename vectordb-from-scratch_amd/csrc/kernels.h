@@ -644,4 +644,20 @@ struct StrikeSetParams {
 };
 void launch_strike_set(const StrikeSetParams& p, uint32_t nq, hipStream_t s);
 
+// ---------------------------------------------------------------- diverse top-k: MMR over the candidates (kernels_mmr.hip)
+constexpr uint32_t MMR_MAX_CANDIDATES = 1024;                              // entries of one candidate list (VDB_MMR_MAX_CANDIDATES)
+// Query b's candidates: ids / dists / cand_rows [b * stride ..], min(counts[b], stride) entries ascending by (distance, id);
+// cand_rows holds the device row of every entry (< n_rows; an entry at or above it ends the query with status bit 1 and count 0).
+// The greedy selection of include/vdb_flat.h "DIVERSE TOP-K" with ks[b] picks, lambda[b] and mu[b] writes the picks in pick order to
+// out_ids / out_dists / out_scores [b * kout ..] (ks[b] <= kout) and out_counts[b] = min(ks[b], candidates).  A NaN among the
+// evaluated pair distances sets status bit 0.  stride <= MMR_MAX_CANDIDATES.
+struct MmrParams {
+    const float* rows; uint32_t ld, dim, n_rows; int metric;
+    const uint64_t* ids; const float* dists; const uint32_t* counts; const uint32_t* cand_rows; uint32_t stride;
+    const uint32_t* ks; const float* lambda; const float* mu;
+    uint64_t* out_ids; float* out_dists; float* out_scores; uint32_t* out_counts; uint32_t kout;
+    uint32_t* status;                                                      // [1], zeroed by the caller
+};
+void launch_mmr_select(const MmrParams& p, uint32_t nq, hipStream_t s);
+
 }  // namespace vdb

@@ -620,6 +620,67 @@ int vdbi::strike_copy_out(Index* H, const HostSearch& r, StrikeBufs B, const vdb
     return VDB_OK;
 }
 
+static_assert(vdb::MMR_MAX_CANDIDATES == VDB_MMR_MAX_CANDIDATES, "the kernel's LDS arrays and the public limit");
+// The second half of a diverse top-k call (r.mmr), on s behind the device search that left the candidate lists `found` at depth
+// found.stride: the ids come down, the host's id -> row map names their device rows (the handle is locked and flushed: a candidate
+// cannot be missing), the rows go up beside k | lambda | mu of every query in ONE copy, mmr_select_kernel picks at most kcut per
+// query, and the picks leave through the copy-out every host-pointer search shares.
+static int mmr_copy_out(vdb_flat_index* ix, const HostSearch& r, const Lists& found, size_t kcut, hipStream_t s) {
+    const size_t nq = r.nq, stride = found.stride, n = nq * stride;
+    MmrWs& W = ix->cur->w_mmr;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> ids(n);
+    std::vector<uint32_t> cnt(nq);
+    HIP_TRY(hipMemcpyAsync(cnt.data(), found.counts, nq * 4, hipMemcpyDeviceToHost, s));
+    if (n) HIP_TRY(hipMemcpyAsync(ids.data(), found.ids, n * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    // k [nq] | lambda [nq] | mu [nq] | device rows [nq][stride]
+    const size_t o_l = nq, o_m = 2 * nq, o_row = 3 * nq, words = o_row + n;
+    std::vector<uint32_t> meta(words, 0xffffffffu);
+    uint64_t cands = 0, pairs = 0;
+    for (size_t b = 0; b < nq; ++b) {
+        const size_t c = std::min<size_t>(cnt[b], stride), kq = std::min(r.ks ? r.ks[b] : r.k, kcut), count = std::min(kq, c);
+        const float lambda = r.mmr->lambdas ? r.mmr->lambdas[b] : r.mmr->lambda, mu = 1.0f - lambda;   // f32, once, here
+        meta[b] = (uint32_t)kq;
+        memcpy(&meta[o_l + b], &lambda, 4);
+        memcpy(&meta[o_m + b], &mu, 4);
+        for (size_t i = 0; i < c; ++i) {
+            const uint64_t id = ids[b * stride + i];
+            auto it = ix->id2row.find(id);
+            if (it == ix->id2row.end() || it->second >= ix->n_uploaded)
+                return fail(VDB_ERR_DEVICE, "internal error: candidate %llu has no row on the device", (unsigned long long)id);
+            meta[o_row + b * stride + i] = it->second;
+        }
+        cands += c;
+        for (size_t t = 1; t < count; ++t) pairs += c - t;             // the pairs the contract evaluates
+    }
+    int rc;
+    const size_t no = nq * std::max<size_t>(kcut, 1);
+    if ((rc = W.meta.ensure(words))) return rc;
+    if ((rc = W.outi.ensure(no)) || (rc = W.outd.ensure(no)) || (rc = W.outs.ensure(no))) return rc;
+    if ((rc = W.outc.ensure(nq)) || (rc = W.stat.ensure(1))) return rc;
+    HIP_TRY(hipMemcpyAsync(W.meta.p, meta.data(), words * 4, hipMemcpyHostToDevice, s));   // (pageable: the copy has left `meta` when this returns)
+    const uint64_t ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+    HIP_TRY(hipMemsetAsync(W.stat.p, 0, 4, s));
+    vdb::MmrParams mp{};
+    mp.rows = ix->d_rows; mp.ld = ix->ld; mp.dim = ix->dim; mp.n_rows = ix->n_uploaded; mp.metric = ix->metric;
+    mp.ids = found.ids; mp.dists = found.dists; mp.counts = found.counts; mp.cand_rows = W.meta.p + o_row; mp.stride = (uint32_t)stride;
+    mp.ks = W.meta.p; mp.lambda = reinterpret_cast<const float*>(W.meta.p + o_l); mp.mu = reinterpret_cast<const float*>(W.meta.p + o_m);
+    mp.out_ids = W.outi.p; mp.out_dists = W.outd.p; mp.out_scores = W.outs.p; mp.out_counts = W.outc.p; mp.kout = (uint32_t)kcut;
+    mp.status = W.stat.p;
+    vdb::launch_mmr_select(mp, (uint32_t)nq, s);
+    HIP_TRY(hipGetLastError());
+    uint32_t status = 0;                                           // valid after the copy-out's synchronisation
+    HIP_TRY(hipMemcpyAsync(&status, W.stat.p, 4, hipMemcpyDeviceToHost, s));
+    size_t total = 0;
+    if ((rc = copy_out(Lists{W.outi.p, W.outd.p, W.outc.p, nullptr, kcut, W.outs.p}, r, s, &total))) return rc;
+    if (status & 2u) return fail(VDB_ERR_DEVICE, "internal error: a candidate row beyond the device store");
+    const uint64_t st[8] = {nq, stride, cands, pairs, total, ns, 0, 0};
+    memcpy(ix->mmr_stats, st, sizeof(st));
+    if (status & 1u) return fail_nan();
+    return VDB_OK;
+}
+
 vdbi::MaskSrc vdbi::mask_src(const HostSearch& r) {
     return MaskSrc{r.id_mask, r.mask_bits, r.cm ? r.cm->d_words.p : nullptr, r.cm ? (hipEvent_t)r.cm->done : nullptr, r.dm};
 }
@@ -639,6 +700,8 @@ static int compiled_mask_check(const vdb_meta_mask* cm, int dev) {
 // r.rec (vdb_flat_recommend_batch; `by` is then rec->ids): the queries are FOLDS of stored vectors.  All examples resolve to device
 // rows as by-id's queries do, the fold kernel writes the query block straight from d_rows, the search runs with as many results
 // more as the longest request has examples, and the set strike removes every example from its request's list.
+// r.mmr (vdb_flat_search_batch_mmr, checked by mmr_check): the search runs at the candidate depth instead of k, and mmr_copy_out
+// re-ranks its lists on the device before the copy-out; k is the number of picks.
 static int search_batch_host(vdb_flat_index* ix, HostSearch r) {
     return guarded([&]() -> int {
     const size_t nq = r.nq;
@@ -661,6 +724,7 @@ static int search_batch_host(vdb_flat_index* ix, HostSearch r) {
     if ((rc = set_device(ix))) return rc;
     if (rec) memset(ix->recommend_stats, 0, sizeof(ix->recommend_stats));
     else if (by) memset(ix->by_id_stats, 0, sizeof(ix->by_id_stats));
+    if (r.mmr) memset(ix->mmr_stats, 0, sizeof(ix->mmr_stats));
     if (nq == 0) return VDB_OK;
     size_t dim = r.dim;
     std::vector<uint32_t> self_rows;
@@ -676,10 +740,11 @@ static int search_batch_host(vdb_flat_index* ix, HostSearch r) {
     size_t kdev = std::min(kmax, std::max<size_t>(len, 1));
     const size_t kcut = kdev;                                      // by id: what is left of a list after the strike, at most
     if (by) kdev = std::min(kdev + (rec ? rec->mmax : 1), len);    // (k was clamped to len first: k = SIZE_MAX cannot wrap)
+    if (r.mmr) kdev = std::min(r.mmr->candidates, std::max<size_t>(len, 1));   // the search runs at the candidate depth; kcut picks leave
     hipStream_t s = ix->stream;
     // Small index, a few queries (BASELINE configs[0]: Index::search itself, one query): queries and results go through MAPPED
     // host memory -- the two kernels of the direct path read and write it in place, nothing is copied by the runtime
-    if (direct_eligible(ix, ix->n_rows(), nq, kdev) && ix->misfits.empty() && dim == ix->dim && !r.id_mask && !r.cm && !r.dm && !by) {
+    if (direct_eligible(ix, ix->n_rows(), nq, kdev) && ix->misfits.empty() && dim == ix->dim && !r.id_mask && !r.cm && !r.dm && !by && !r.mmr) {
         const size_t qb = nq * dim * sizeof(float), ib = nq * kdev * sizeof(uint64_t), db = nq * kdev * sizeof(float), cb = nq * sizeof(uint32_t);
         const size_t o_i = (qb + 15) & ~(size_t)15, o_d = o_i + ib, o_c = o_d + ((db + 15) & ~(size_t)15);
         if ((rc = ensure_host_io(ix, o_c + cb))) return rc;
@@ -718,6 +783,7 @@ static int search_batch_host(vdb_flat_index* ix, HostSearch r) {
     if ((rc = search_device(ix, W->w_qin.p, nq, dim, kdev, d_mask, r.mask_bits, W->w_outi.p, W->w_outd.p, W->w_outc.p, nullptr))) return rc;
     const Lists found{W->w_outi.p, W->w_outd.p, W->w_outc.p, nullptr, kdev};
     if (by) return strike_copy_out(ix, r, strike, rl, found, kcut, s);
+    if (r.mmr) return mmr_copy_out(ix, r, found, kcut, s);
     return copy_out(found, r, s);
     });
 }
@@ -800,6 +866,65 @@ int vdb_flat_recommend_batch_filtered(vdb_flat_index* ix, const uint64_t* exampl
 int vdb_flat_recommend_stats(const vdb_flat_index* ix, uint64_t out[4]) {
     if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
     memcpy(out, ix->recommend_stats, sizeof(ix->recommend_stats));
+    return VDB_OK;
+}
+
+// ---- diverse top-k (no reference counterpart; search_batch_host with r.mmr)
+// The checks of include/vdb_flat.h "DIVERSE TOP-K" item 8, in its order, before any lock or device work.  *done: the call is
+// answered (an empty index, or no query asks for a row).
+static int mmr_check(const vdb_flat_index* ix, const HostSearch& r, const MmrReq& m, bool* done) {
+    *done = false;
+    if (!ix || (r.nq && !r.counts)) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (r.nq == 0) return VDB_OK;
+    size_t kmax = r.ks ? 0 : r.k;
+    for (size_t b = 0; r.ks && b < r.nq; ++b) kmax = std::max(kmax, r.ks[b]);
+    if (kmax == 0 || vdb_flat_len(ix) == 0) {
+        for (size_t b = 0; b < r.nq; ++b) r.counts[b] = 0;
+        *done = true;
+        return VDB_OK;
+    }
+    if (!r.queries || !r.ids || !r.dists) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    for (size_t b = 0; b < (m.lambdas ? r.nq : 1); ++b) {
+        const float l = m.lambdas ? m.lambdas[b] : m.lambda;
+        if (!(l >= 0.0f && l <= 1.0f)) return fail(VDB_ERR_INVALID_ARGUMENT, "lambda %g is not within [0, 1]", (double)l);
+    }
+    if (m.candidates == 0) return fail(VDB_ERR_INVALID_ARGUMENT, "candidates is 0");
+    if (m.candidates > VDB_MMR_MAX_CANDIDATES) return fail(VDB_ERR_INVALID_ARGUMENT, "%zu candidates, more than %d", m.candidates, VDB_MMR_MAX_CANDIDATES);
+    if (kmax > m.candidates) return fail(VDB_ERR_INVALID_ARGUMENT, "the largest k %zu is above the %zu candidates", kmax, m.candidates);
+    if (ix->multi) return refuse_multi("vdb_flat_search_batch_mmr");
+    return VDB_OK;
+}
+
+static int search_mmr_host(vdb_flat_index* ix, HostSearch r, MmrReq m, float* out_scores) {
+    r.scores = out_scores; r.mmr = &m;
+    bool done = false;
+    int rc = guarded([&]() -> int { return mmr_check(ix, r, m, &done); });
+    if (rc || done || r.nq == 0) {
+        if (!rc && ix && !ix->multi) { std::lock_guard<std::mutex> g(ix->mu); memset(ix->mmr_stats, 0, sizeof(ix->mmr_stats)); ix->mmr_stats[0] = r.nq; }
+        return rc;
+    }
+    return search_batch_host(ix, r);
+}
+
+int vdb_flat_search_batch_mmr(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k,
+                              size_t candidates, const float* lambdas, float lambda, const uint64_t* id_mask, size_t mask_bits,
+                              size_t kstride, uint64_t* out_ids, float* out_dists, float* out_scores, size_t* out_counts) {
+    return search_mmr_host(ix, under(host_search(queries, nq, dim, ks, k, kstride, out_ids, out_dists, out_counts), id_mask, mask_bits),
+                           MmrReq{candidates, lambdas, lambda}, out_scores);
+}
+
+int vdb_flat_search_batch_mmr_filtered(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k,
+                                       size_t candidates, const float* lambdas, float lambda, const vdb_meta_mask* mask, size_t kstride,
+                                       uint64_t* out_ids, float* out_dists, float* out_scores, size_t* out_counts) {
+    if (!mask) return fail(VDB_ERR_INVALID_ARGUMENT, "null mask");
+    return search_mmr_host(ix, under(host_search(queries, nq, dim, ks, k, kstride, out_ids, out_dists, out_counts), mask),
+                           MmrReq{candidates, lambdas, lambda}, out_scores);
+}
+
+int vdb_flat_mmr_stats(const vdb_flat_index* ix, uint64_t out[8]) {
+    if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (ix->multi) return refuse_multi("vdb_flat_mmr_stats");
+    memcpy(out, ix->mmr_stats, sizeof(ix->mmr_stats));
     return VDB_OK;
 }
 

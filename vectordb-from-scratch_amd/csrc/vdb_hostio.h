@@ -14,10 +14,12 @@
 namespace vdbi {
 
 // A batch as the caller shaped it: nq queries, k results each (ks[b] where ks is given), and where the answers go -- list b at
-// ids[b * kstride], dists[b * kstride] (and codes, where the search has them and the caller wants them), its length in counts[b].
+// ids[b * kstride], dists[b * kstride] (and codes or scores, where the search has them and the caller wants them), its length in
+// counts[b].
 struct Batch {
     size_t nq = 0; const size_t* ks = nullptr; size_t k = 0, kstride = 0;
     uint64_t* ids = nullptr; float* dists = nullptr; int32_t* codes = nullptr; size_t* counts = nullptr;
+    float* scores = nullptr;
 };
 
 // *kmax = the largest k of the batch; refuses a stride below it, then missing output arrays.
@@ -62,10 +64,11 @@ inline int stage_mask(DevBuf<uint64_t>& buf, const MaskSrc& m, hipStream_t s, co
 }
 
 // The lists of a finished search, in host-readable memory or on the device: list b at ids[b * stride], counts[b] entries of it
-// valid (a count above the stride means the stride).  codes may be null.
+// valid (a count above the stride means the stride).  codes and scores may be null.
 struct Lists {
     const uint64_t* ids = nullptr; const float* dists = nullptr; const uint32_t* counts = nullptr; const int32_t* codes = nullptr;
     size_t stride = 0;
+    const float* scores = nullptr;
 };
 
 // Host arrays to the caller's arrays; no runtime call.  Returns the number of entries written.
@@ -80,6 +83,7 @@ inline size_t emit_lists(const Lists& h, const Batch& b) {
             b.ids[q * b.kstride + i] = h.ids[q * h.stride + i];
             b.dists[q * b.kstride + i] = h.dists[q * h.stride + i];
             if (h.codes && b.codes) b.codes[q * b.kstride + i] = h.codes[q * h.stride + i];
+            if (h.scores && b.scores) b.scores[q * b.kstride + i] = h.scores[q * h.stride + i];
         }
     }
     return total;
@@ -93,14 +97,16 @@ inline int copy_out(const Lists& d, const Batch& b, hipStream_t s, size_t* total
     std::vector<uint64_t> ids(n);
     std::vector<float> ds(n);
     std::vector<int32_t> cs(d.codes ? n : 0);
+    std::vector<float> sc(d.scores && b.scores ? n : 0);
     if (b.nq) HIP_TRY(hipMemcpyAsync(cnt.data(), d.counts, b.nq * 4, hipMemcpyDeviceToHost, s));
     if (n) {
         HIP_TRY(hipMemcpyAsync(ids.data(), d.ids, n * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(ds.data(), d.dists, n * 4, hipMemcpyDeviceToHost, s));
         if (!cs.empty()) HIP_TRY(hipMemcpyAsync(cs.data(), d.codes, n * 4, hipMemcpyDeviceToHost, s));
+        if (!sc.empty()) HIP_TRY(hipMemcpyAsync(sc.data(), d.scores, n * 4, hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(hipStreamSynchronize(s));
-    const size_t t = emit_lists(Lists{ids.data(), ds.data(), cnt.data(), cs.empty() ? nullptr : cs.data(), d.stride}, b);
+    const size_t t = emit_lists(Lists{ids.data(), ds.data(), cnt.data(), cs.empty() ? nullptr : cs.data(), d.stride, sc.empty() ? nullptr : sc.data()}, b);
     if (total) *total = t;
     return VDB_OK;
 }

@@ -63,12 +63,26 @@ struct RecommendReq {
     size_t total = 0, mmax = 0;                                   // offsets[nq]; the longest request (recommend_check)
 };
 
+// A diverse top-k request (vdb_flat_search_batch_mmr) as the caller passed it, checked by mmr_check: the candidate
+// depth m and one lambda per query or the scalar (the scores go to Batch::scores, which may be null).
+struct MmrReq {
+    size_t candidates; const float* lambdas; float lambda;
+};
+// What one such call owns on the device beside the search workspace: k | lambda | mu per query and the candidates' device rows in
+// one upload; the picks; the NaN-pair status word.
+struct MmrWs {
+    vdbi::DevBuf<uint32_t> meta, outc, stat;
+    vdbi::DevBuf<uint64_t> outi; vdbi::DevBuf<float> outd, outs;
+};
+
 // A host-pointer batch search as its entry point received it (the extern "C" shims fill it): the batch and its outputs (Batch),
 // the queries -- vectors [nq][dim], or the stored vectors of `by` (then queries is null and dim unused), or folds of stored
-// vectors (rec, checked by recommend_check; by is then rec->ids) -- and the id mask in the form it came in.
+// vectors (rec, checked by recommend_check; by is then rec->ids) -- and the id mask in the form it came in.  mmr: the lists of the
+// search at depth mmr->candidates are re-ranked on the device before the copy-out (k is then the number of picks).
 struct HostSearch : vdbi::Batch {
     const float* queries = nullptr; size_t dim = 0;
     const uint64_t* by = nullptr; const RecommendReq* rec = nullptr;
+    const MmrReq* mmr = nullptr;
     const uint64_t* id_mask = nullptr; size_t mask_bits = 0;      // mask_bits bits in host memory
     const struct vdb_meta_mask* cm = nullptr;                     // a compiled mask (vdb_meta.h); mask_bits becomes its size
     const uint64_t* dm = nullptr;                                 // mask_bits bits already on the device (vdb_internal::search_batch_device_mask)
@@ -83,6 +97,7 @@ struct Workspace {
     vdbi::DevBuf<float> w_radii; vdbi::DevBuf<uint64_t> w_totals; // range search, host-pointer form: radii in, totals out
     vdbi::DevBuf<uint32_t> w_selfrow, w_bystat; vdbi::DevBuf<uint64_t> w_selfid;   // search by stored id: device rows and ids of the queries, struck | cut counters
     RecommendWs w_rec;                                            // recommend: the requests' lists
+    MmrWs w_mmr;                                                  // diverse top-k: per-query parameters, candidate rows, picks
     vdbi::DevBuf<uint16_t> w_qb;                                  // bf16 copy of the padded queries (screening tier)
     // compact block of the queries the screening tier could not certify (re-run by the f32 tier)
     vdbi::DevBuf<float> w2_qp, w2_qnorm, w2_thr, w2_outd, w2_qerr, w2_qg;
@@ -215,6 +230,7 @@ struct vdb_flat_index {
     uint64_t range_stats[8] = {0};                          // vdb_flat_range_stats: counters of the last range search
     uint64_t by_id_stats[4] = {0};                          // vdb_flat_by_id_stats: counters of the last search by stored id (also on a sharded parent)
     uint64_t recommend_stats[4] = {0};                      // vdb_flat_recommend_stats: counters of the last recommend call (also on a sharded parent)
+    uint64_t mmr_stats[8] = {0};                            // vdb_flat_mmr_stats: counters of the last diverse top-k call
     uint64_t distinct_stats[8] = {0};                       // vdb_flat_distinct_stats: counters of the last search by group (also on a sharded parent)
     DistinctWs dws;                                         // its device buffers (a sharded parent's live on devices[0])
     uint64_t grouped_stats[8] = {0};                        // vdb_flat_grouped_stats: counters of the last grouped search

@@ -161,6 +161,20 @@ public:
         if (codes) codes->assign(cs.begin(), cs.begin() + (ptrdiff_t)cnt);
         return out;
     }
+    // no reference counterpart: k rows near q and apart from each other (maximal marginal relevance over the `candidates` nearest
+    // rows, include/vdb_flat.h "DIVERSE TOP-K"), in pick order.  scores (may be null) receives the score each pick was chosen with.
+    std::vector<Neighbor> search_mmr(const Vector& q, size_t k, size_t candidates, float lambda, const uint64_t* id_mask = nullptr,
+                                     size_t mask_bits = 0, std::vector<float>* scores = nullptr) const {
+        std::vector<uint64_t> ids(std::max<size_t>(k, 1));
+        std::vector<float> ds(ids.size()), sc(ids.size());
+        size_t cnt = 0;
+        check(vdb_flat_search_batch_mmr(h_, q.as_slice().data(), 1, q.dimension(), nullptr, k, candidates, nullptr, lambda, id_mask, mask_bits,
+                                        ids.size(), ids.data(), ds.data(), sc.data(), &cnt));
+        std::vector<Neighbor> out;
+        for (size_t i = 0; i < cnt; ++i) out.emplace_back((size_t)ids[i], ds[i]);
+        if (scores) scores->assign(sc.begin(), sc.begin() + (ptrdiff_t)cnt);
+        return out;
+    }
     DistanceMetric metric() const override { return metric_; }
     size_t len() const override { return vdb_flat_len(h_); }
     void add_bulk(const float* rows, size_t n, size_t dim, uint64_t first_id) {

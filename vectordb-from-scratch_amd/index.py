@@ -412,6 +412,62 @@ class GpuFlatIndex(Index):
             _raise(rc)
         return [int(x) for x in out]
 
+    # ---- diverse top-k, MMR on the device (include/vdb_flat.h vdb_flat_search_batch_mmr; no reference counterpart)
+    def search_batch_mmr(self, queries, k, candidates, lam, id_mask=None, mask_bits=0, compiled_mask=None, ks=None):
+        """k results that are not all the same thing: the `candidates` nearest rows of each query (what search_batch_arrays
+        returns at that depth) are re-ranked greedily on the device -- pick 1 is the nearest, every later pick minimises
+        lam * d - (1 - lam) * (distance to the nearest row already picked), ties by position in the candidate list
+        (include/vdb_flat.h has the exact arithmetic).  lam is a scalar or one value per query, within [0, 1]; lam = 1 is the
+        plain search.  ks: one k per query instead of k.  1 <= k <= candidates <= 1024.  Returns (ids u64 [nq, kmax],
+        dists f32 [nq, kmax] -- the query distance of each pick --, scores f32 [nq, kmax], counts [nq]), in pick order."""
+        if compiled_mask is not None and id_mask is not None:
+            raise ValueError("pass id_mask or compiled_mask, not both")
+        qs = np.ascontiguousarray(queries, dtype=np.float32)
+        nq, dim = qs.shape
+        if ks is None:
+            ks_ptr, kscalar, kmax = None, int(k), int(k)
+        else:
+            ksa = np.ascontiguousarray(ks, dtype=np.uintp)
+            if ksa.shape != (nq,):
+                raise ValueError(f"ks must hold one value per query ({nq}), not {ksa.shape}")
+            ks_ptr = ksa.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t))
+            kscalar, kmax = 0, int(ksa.max()) if ksa.size else 0
+        if np.isscalar(lam):
+            lam_ptr, lscalar = None, float(lam)
+        else:
+            lams = np.ascontiguousarray(lam, dtype=np.float32)
+            if lams.shape != (nq,):
+                raise ValueError(f"lam must be a scalar or hold one value per query ({nq}), not {lams.shape}")
+            lam_ptr, lscalar = _fp(lams), 0.0
+        kstride = max(kmax, 1)
+        out_ids = np.zeros((nq, kstride), dtype=np.uint64)
+        out_d = np.zeros((nq, kstride), dtype=np.float32)
+        out_s = np.zeros((nq, kstride), dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uintp)
+        head = (self._h, _fp(qs), nq, dim, ks_ptr, kscalar, int(candidates), lam_ptr, lscalar)
+        tail = (kstride, _u64p(out_ids), _fp(out_d), _fp(out_s), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)))
+        if compiled_mask is not None:
+            rc = self._L.vdb_flat_search_batch_mmr_filtered(*head, compiled_mask.handle, *tail)
+        else:
+            mask_ptr = None
+            if id_mask is not None:
+                m = np.ascontiguousarray(id_mask, dtype=np.uint64)
+                mask_ptr = _u64p(m)
+            rc = self._L.vdb_flat_search_batch_mmr(*head, mask_ptr, int(mask_bits), *tail)
+        if rc:
+            _raise(rc)
+        return out_ids, out_d, out_s, counts
+
+    def mmr_stats(self):
+        """The last search_batch_mmr: [0] queries, [1] the depth the search ran at, [2] candidates summed over the queries,
+        [3] pair distances evaluated (sum over the queries of sum_{t=1}^{count-1} (c - t)), [4] rows returned, [5] host ns
+        spent turning candidate ids into device rows, [6], [7] 0."""
+        out = (ctypes.c_uint64 * 8)()
+        rc = self._L.vdb_flat_mmr_stats(self._h, out)
+        if rc:
+            _raise(rc)
+        return [int(x) for x in out]
+
     # ---- one nearest row per group (include/vdb_flat.h vdb_flat_search_batch_distinct; no reference counterpart)
     def search_batch_distinct(self, queries, k, table, slot, id_mask=None, mask_bits=0, compiled_mask=None):
         """The k nearest GROUPS, each represented by its nearest row: the full ranking of the eligible rows walked from the

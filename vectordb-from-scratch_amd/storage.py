@@ -732,6 +732,38 @@ class VectorStore:
             out_ids, dists, counts = self._index.recommend_batch(pos, neg, int(k), id_mask=mask, mask_bits=bits)
         return [self._map([(int(out_ids[b, i]), dists[b, i]) for i in range(int(counts[b]))]) for b in range(len(pos))]
 
+    # ---- "k results that are not all the same thing" (GpuFlatIndex.search_batch_mmr; no reference counterpart)
+    def search_mmr(self, query, k, lam=0.5, candidates=None, flt=None):
+        """k stored vectors near `query` and apart from each other (maximal marginal relevance), in pick order: the nearest
+        first, then whichever of the `candidates` nearest rows minimises lam * distance - (1 - lam) * (distance to the nearest
+        row already picked)."""
+        return self.search_mmr_batch([query], k, lam, candidates, flt)[0]
+
+    def search_mmr_batch(self, queries, k, lam=0.5, candidates=None, flt=None):
+        """search_mmr for several queries in one device call.  candidates defaults to min(max(4 k, 32), 1024).  flt is a
+        PRE-filter exactly as in search_similar_batch: the candidates are the nearest rows that pass it."""
+        if not isinstance(self._index, GpuFlatIndex):
+            raise ValueError("search_mmr needs a GpuFlatIndex")
+        queries = list(queries)
+        if not queries or self.is_empty():
+            return [[] for _ in queries]
+        for q in queries:
+            self._check_dim(q)
+        k = int(k)
+        if candidates is None:
+            candidates = min(max(4 * k, 32), 1024)
+        qs = np.stack([q.data for q in queries]).astype(np.float32, copy=False)
+        cm = self.compile_filter_device(flt) if flt is not None and self._table is not None else None
+        if cm is not None:
+            try:
+                out_ids, dists, _, counts = self._index.search_batch_mmr(qs, k, int(candidates), lam, compiled_mask=cm)
+            finally:
+                cm.release()
+        else:
+            mask, bits = self.compile_filter(flt) if flt is not None else (None, 0)
+            out_ids, dists, _, counts = self._index.search_batch_mmr(qs, k, int(candidates), lam, id_mask=mask, mask_bits=bits)
+        return [self._map([(int(out_ids[b, i]), dists[b, i]) for i in range(int(counts[b]))]) for b in range(len(queries))]
+
     # ---- "the k nearest documents" (GpuFlatIndex.search_batch_distinct; no reference counterpart)
     def search_distinct(self, query, k, field, flt=None):
         """The k nearest GROUPS of rows that share a value of metadata field `field`, each represented by its nearest row,
