@@ -137,6 +137,13 @@ int vdb_hnsw_entry_point(const vdb_hnsw_index *h, uint64_t *id, size_t *max_leve
  * HOST-traversed search_batch, [3] its distances, [4] queries answered by the device-resident search, [5] queries whose
  * device walk overflowed its LDS structures and that the host traversal re-ran. */
 int vdb_hnsw_stats(const vdb_hnsw_index *h, uint64_t out[6]);
+/* How the device mirror of the graph was kept up to date, since creation: [0] full rebuilds, of which [1] were forced by a
+ * mutation (the first upload, a vdb_hnsw_remove, an id added again), [2] happened because a node id did not fit the capacity of
+ * the last rebuild and [3] because the pool of upper-layer lists did not -- when several hold at once the rebuild counts for the
+ * first of them in this order, so [1] + [2] + [3] = [0]; [4] incremental syncs that launched the scatter kernel, [5] node records
+ * they scattered; [6] the mirror's capacity in node ids and [7] in pooled upper lists, as of the last rebuild (n + n / 4 + 1024 of
+ * what it held, or what a bulk insert reserved).  Changes nothing; tests use it to see which path a sync took and why. */
+int vdb_hnsw_mirror_stats(const vdb_hnsw_index *h, uint64_t out[8]);
 
 /* How bulk inserts (vdb_hnsw_add_bulk, 32 vectors or more) get their distances.  1 (default): FRONTIER ONLY -- a device walk per
  * insert evaluates what search_layer asks for (graph.rs:155, :182) on the graph as it was 64 + (its position in its block of

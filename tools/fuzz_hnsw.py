@@ -6,6 +6,12 @@ name an id twice; the product's graph must equal the CPU restatement's (same see
 (ids, order, distance bits) -- through the device-resident search.
 
     python tools/fuzz_hnsw.py [--cases N] [--seed S]
+
+--lifecycle runs random schedules of tests/hnsw_lifecycle.py instead (mutations and reads interleaved, every walk on the device
+and on the host route, vdb_hnsw_mirror_stats against the model after every read) and shrinks a failing one to a literal trace:
+
+    python tools/fuzz_hnsw.py --lifecycle [--cases N] [--seed S]
+    python tools/fuzz_hnsw.py --lifecycle --mutants        (no GPU: which pinned schedule catches which mutant, at which step)
 """
 import argparse
 import os
@@ -20,11 +26,50 @@ from bench import load_package  # noqa: E402
 import oracle  # noqa: E402
 
 
+def lifecycle(a):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hnsw_lifecycle as hl
+    if a.mutants:
+        for name in hl.PINNED:
+            trace, caught = hl.pinned(name), []
+            hl.run(trace, hl.MirrorRef(trace), expected=hl.slots(name))
+            for mutant in hl.MUTANTS:
+                try:
+                    hl.run(trace, mutant(trace), expected=hl.slots(name), counters=False)
+                except hl.Mismatch as e:
+                    step = int(str(e).split("step ")[1].split(" ")[0])
+                    caught.append(f"{mutant.__name__} (step {step}, {trace['ops'][step][0]})")
+            print(f"[{name}] {len(trace['ops'])} ops: " + (", ".join(caught) or "none"), flush=True)
+        return
+    vdb = load_package()
+    vdb.build()
+    rng = np.random.default_rng(a.seed)
+    t0 = time.time()
+    for case in range(a.cases):
+        seed, metric = int(rng.integers(1, 1 << 30)), int(rng.integers(0, 3))
+        d, m, base = int(rng.choice([8, 16, 33])), int(rng.choice([4, 6, 16])), int(rng.integers(300, 1501))
+        trace = hl.schedule(seed, metric, d, m, base)
+        try:
+            model, stats, walked = hl.run_gpu(vdb, trace)
+        except hl.Mismatch as e:
+            print(f"FAIL case {case}: {str(e).splitlines()[0]}", flush=True)
+            small = hl.shrink_gpu(vdb, trace, log=print)
+            print(f"shrunk: TRACE = {small!r}", flush=True)
+            sys.exit(1)
+        print(f"ok   case {case}: seed={seed} metric={metric} d={d} m={m} base={base} ops={len(trace['ops'])} device walks {walked} "
+              f"mirror_stats {stats}", flush=True)
+    print(f"ALL {a.cases} HNSW LIFECYCLE CASES OK in {time.time() - t0:.0f} s", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", type=int, default=40)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--lifecycle", action="store_true", help="random lifecycle schedules (tests/hnsw_lifecycle.py) instead")
+    ap.add_argument("--mutants", action="store_true", help="with --lifecycle, on the CPU: the pinned schedules against the mutants")
     a = ap.parse_args()
+    if a.lifecycle:
+        return lifecycle(a)
     vdb = load_package()
     vdb.build()
     rng = np.random.default_rng(a.seed)

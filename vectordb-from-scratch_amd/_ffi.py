@@ -30,7 +30,7 @@ SYMBOLS = [
     "vdb_hnsw_create", "vdb_hnsw_destroy", "vdb_hnsw_add", "vdb_hnsw_add_bulk", "vdb_hnsw_remove", "vdb_hnsw_search_batch", "vdb_hnsw_search_batch_masked",
     "vdb_hnsw_len", "vdb_hnsw_metric", "vdb_hnsw_get_vector", "vdb_hnsw_neighbors", "vdb_hnsw_node_level",
     "vdb_hnsw_entry_point", "vdb_hnsw_stats", "vdb_hnsw_set_traversal", "vdb_hnsw_set_build", "vdb_hnsw_build_stats", "vdb_hnsw_build_times", "vdb_hnsw_set_filter_scan",
-    "vdb_hnsw_search_batch_filtered", "vdb_hnsw_debug_present_mask",
+    "vdb_hnsw_search_batch_filtered", "vdb_hnsw_debug_present_mask", "vdb_hnsw_mirror_stats",
     # include/vdb_shard.h
     "vdb_shard_unique_id", "vdb_shard_group_create", "vdb_shard_group_destroy", "vdb_shard_group_rank", "vdb_shard_group_world",
     "vdb_shard_range", "vdb_flat_search_batch_sharded", "vdb_shard_group_last_stats",
@@ -207,6 +207,7 @@ def lib():
     L.vdb_hnsw_node_level.restype = c.c_long
     L.vdb_hnsw_entry_point.argtypes = [vp, u64p, szp]
     L.vdb_hnsw_stats.argtypes = [vp, u64p]
+    L.vdb_hnsw_mirror_stats.argtypes = [vp, u64p]
     L.vdb_hnsw_set_traversal.argtypes = [vp, c.c_int, sz]
     L.vdb_hnsw_set_filter_scan.argtypes = [vp, sz]
     L.vdb_hnsw_set_build.argtypes = [vp, c.c_int]

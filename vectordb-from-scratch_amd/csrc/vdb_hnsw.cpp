@@ -166,6 +166,10 @@ struct vdb_hnsw_index {
     uint32_t cap_ids = 0, cap_upper = 0, n_upper_used = 0;
     std::vector<uint32_t> h_up_off; std::vector<uint8_t> dirty_flag; std::vector<uint32_t> dirty;
     bool mirror_full = true;                                      // the next sync rebuilds the whole mirror
+    // vdb_hnsw_mirror_stats: [0..5]; full_cause = why mirror_full is set (1: a mutation or the first upload, 2 / 3: the bulk
+    // path's capacity check found the batch's ids / upper lists beyond the mirror), the index of the counter the rebuild goes to
+    uint64_t mstats[6] = {0};
+    uint32_t full_cause = 1;
     vdbi::HostBuf<uint32_t> h_stage;                              // mapped staging of the scatter records
     // speculative insert walks: per walk of a chunk its query row / level (host -> device) and its record (device -> host), mapped
     vdbi::HostBuf<uint32_t> h_wq;                                 // [2][WALKS]: rows, levels
@@ -491,7 +495,7 @@ int readd_row(Graph* g, uint64_t id, const float* v, size_t dim, long level_in) 
     const uint32_t row = vdb_internal::row_of(g->flat, id);
     if (row == 0xffffffffu) return vdb_internal::set_error(VDB_ERR_INVALID_ARGUMENT, "row was not stored");
     const size_t level = level_in >= 0 ? std::min<size_t>((size_t)level_in, g->max_layers - 1) : level_from_unit(g, next_unit(g));
-    g->mirror_full = true;
+    g->mirror_full = true; g->full_cause = 1;
     if (id < g->h_up_off.size()) g->h_up_off[id] = 0xffffffffu;
     std::vector<uint32_t> ra, rb;
     std::vector<float*> slot;
@@ -616,7 +620,7 @@ int vdb_hnsw_remove(vdb_hnsw_index* g, uint64_t id) {             // graph.rs:34
     std::lock_guard<std::mutex> lk(g->mu);
     if (!g->node(id)) return VDB_OK;
     g->graph_version++;
-    g->mirror_full = true;                                         // lists that still name the node need its row cleared: rebuilt as a whole
+    g->mirror_full = true; g->full_cause = 1;                      // lists that still name the node need its row cleared: rebuilt as a whole
     Node gone = std::move(g->nodes[id]);
     g->nodes[id] = Node();
     if (id < g->row_of_id.size()) g->row_of_id[id] = 0xffffffffu;
@@ -769,13 +773,19 @@ int sync_mirror(vdb_hnsw_index* g, hipStream_t s, size_t reserve_ids, size_t res
     const uint32_t stride0 = (uint32_t)g->m_max0, strideU = (uint32_t)g->m;
     auto row_now = [&](uint64_t x) -> uint32_t { const Node* t = g->node(x); return t ? t->row : 0xffffffffu; };
     // upper-list offsets of nodes that do not have one yet (new nodes of level >= 1)
-    bool full = g->mirror_full || !g->d_row_of || n > g->cap_ids || stride0 != g->stride0 || strideU != g->strideU;
+    // why a rebuild, for vdb_hnsw_mirror_stats -- the first cause that holds: 1 forced by a mutation (or nothing uploaded yet),
+    // 2 an id beyond cap_ids, 3 the upper-list pool beyond cap_upper
+    uint32_t cause = 0;
+    if (!g->d_row_of || stride0 != g->stride0 || strideU != g->strideU) cause = 1;
+    else if (g->mirror_full) cause = g->full_cause;
+    else if (n > g->cap_ids) cause = 2;
+    bool full = cause != 0;
     if (!full) {
         if (g->h_up_off.size() < n) g->h_up_off.resize(n, 0xffffffffu);
         for (uint32_t id : g->dirty) {
             const Node& nd = g->nodes[id];
             if (!nd.present || nd.level == 0 || g->h_up_off[id] != 0xffffffffu) continue;
-            if ((size_t)g->n_upper_used + nd.level > g->cap_upper) { full = true; break; }
+            if ((size_t)g->n_upper_used + nd.level > g->cap_upper) { full = true; cause = 3; break; }
             g->h_up_off[id] = g->n_upper_used;
             g->n_upper_used += nd.level;
         }
@@ -820,12 +830,13 @@ int sync_mirror(vdb_hnsw_index* g, hipStream_t s, size_t reserve_ids, size_t res
         }
         // the scatter kernel writes where the records say: nothing is launched unless every node id is inside the mirror's id
         // arrays and every upper-list slot inside the slots handed out so far (the next sync rebuilds the mirror as a whole)
-        if (bad) { g->mirror_full = true; return vdb_internal::set_error(VDB_ERR_DEVICE, "internal error: a mirror record lies outside the mirror"); }
+        if (bad) { g->mirror_full = true; g->full_cause = 1; return vdb_internal::set_error(VDB_ERR_DEVICE, "internal error: a mirror record lies outside the mirror"); }
         vdb::HnswScatterParams sp{g->h_stage.d, (uint32_t)g->dirty.size(), g->h_stage.d + g->dirty.size() * w0, cU,
                                   g->d_row_of, g->d_level, g->d_up_off, g->d_nbr0, g->d_nbr0_row, stride0, g->d_nbrU, g->d_nbrU_row, strideU};
         vdb::launch_hnsw_scatter(sp, s);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(s));                               // the staging memory is reused by the next sync
+        g->mstats[4]++; g->mstats[5] += g->dirty.size();
         g->dirty.clear();
         g->mirror_ids = n;
         g->mirror_version = g->graph_version;
@@ -855,6 +866,7 @@ int sync_mirror(vdb_hnsw_index* g, hipStream_t s, size_t reserve_ids, size_t res
         off += nd.level;
     }
     g->n_upper_used = off;
+    if (!g->mirror_full) g->full_cause = cause;                         // (a rebuild that fails below is due again, for the same reason)
     // built in locals and swapped in, together with the capacities and strides that describe it, once every array is there: a
     // failure leaves the old mirror whole (and due for this rebuild again: h_up_off already describes the new one)
     g->mirror_full = true;
@@ -878,6 +890,8 @@ int sync_mirror(vdb_hnsw_index* g, hipStream_t s, size_t reserve_ids, size_t res
     g->mirror_ids = n; g->stride0 = stride0; g->strideU = strideU; g->max_list = std::max(stride0, strideU);
     g->mirror_version = g->graph_version;
     g->mirror_full = false;
+    g->mstats[0]++; g->mstats[cause]++;
+    g->full_cause = 1;
     for (uint32_t id : g->dirty) if (id < g->dirty_flag.size()) g->dirty_flag[id] = 0;
     g->dirty.clear();
     return VDB_OK;
@@ -933,7 +947,10 @@ int build_speculative(Graph* g, const uint64_t* ids, uint64_t first_id, size_t n
     for (size_t i = 0; i < n; ++i) { max_id = std::max<size_t>(max_id, ids ? ids[i] : first_id + i); up_need += lev[i]; }
     size_t up_have = 0;
     for (const Node& nd : g->nodes) if (nd.present) up_have += nd.level;
-    if (max_id + 1 > g->cap_ids || up_have + up_need > g->cap_upper) g->mirror_full = true;
+    if (!g->mirror_full && g->d_row_of && (max_id + 1 > g->cap_ids || up_have + up_need > g->cap_upper)) {
+        g->full_cause = max_id + 1 > g->cap_ids ? 2 : 3;
+        g->mirror_full = true;
+    }
     constexpr uint32_t TAB = 32768;                                 // hash slots of an insert's record (at most REC_CAP entries)
     std::vector<uint32_t> tab_row(TAB), fetch_miss_idx, miss_a, miss_b;
     std::vector<float> tab_d(TAB), win, miss_d;
@@ -1433,6 +1450,15 @@ int vdb_hnsw_build_times(const vdb_hnsw_index* g, double out[4]) {
     return guarded([&]() -> int {
     if (!g || !out) return vdb_internal::set_error(VDB_ERR_INVALID_ARGUMENT, "null argument");
     memcpy(out, g->btimes, sizeof(g->btimes));
+    return VDB_OK;
+    });
+}
+int vdb_hnsw_mirror_stats(const vdb_hnsw_index* g, uint64_t out[8]) {
+    return guarded([&]() -> int {
+    if (!g || !out) return vdb_internal::set_error(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    memcpy(out, g->mstats, sizeof(g->mstats));
+    out[6] = g->cap_ids;
+    out[7] = g->cap_upper;
     return VDB_OK;
     });
 }

@@ -69,6 +69,10 @@ class GpuHnswIndex(Index):
         if rows.shape[0] == 0:
             return
         rc = self._L.vdb_hnsw_add_bulk(self._h, _u64p(ids), 0, _fp(rows), rows.shape[0], rows.shape[1])
+        if self._vectors:                                        # an id add() stored and this batch replaced: get_vector reads the index
+            cached = np.fromiter(self._vectors, dtype=np.uint64, count=len(self._vectors))
+            for i in cached[np.isin(cached, ids)]:
+                del self._vectors[int(i)]
         if rc:
             _raise(rc)
 
@@ -194,6 +198,14 @@ class GpuHnswIndex(Index):
         self._L.vdb_hnsw_stats(self._h, out)
         return dict(zip(["gpu_distances", "gpu_launches", "last_search_rounds", "last_search_distances", "device_queries",
                          "host_redone"], [int(v) for v in out]))
+
+    def mirror_stats(self):
+        """How the device mirror of the graph was kept up to date (vdb_hnsw_mirror_stats): full rebuilds and why, incremental
+        syncs and the node records they scattered, and the mirror's two capacities."""
+        out = (ctypes.c_uint64 * 8)()
+        self._L.vdb_hnsw_mirror_stats(self._h, out)
+        return dict(zip(["rebuilds", "rebuilds_mutation", "rebuilds_id_capacity", "rebuilds_upper_capacity", "scatters",
+                         "scattered_nodes", "cap_ids", "cap_upper"], [int(v) for v in out]))
 
     def set_build(self, frontier_only=True):
         """Bulk inserts: True (default) = device walks evaluate only what search_layer asks for, the host replays the inserts in
