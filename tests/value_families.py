@@ -1,4 +1,6 @@
-"""Value families for the tests at the edges of f32 (tests/test_value_edges_cpu.py, tests/test_gpu_value_edges.py).
+"""Value families for the tests at the edges of f32 (tests/test_value_edges_cpu.py, tests/test_gpu_value_edges.py, and, for the
+reads by stored id, recommend, one row per group, a filter per query and MMR, tests/test_gpu_value_edges_reads.py: the additions
+at the end of this file).
 
 Each family is a function (rng, n, d, nq, metric) -> rows f32[n, d], queries f32[nq, d]; ids are the row numbers.  What the
 ORACLE's answer contains for each is stated here and pinned, shape by shape, by tests/test_value_edges_cpu.py; the GPU tests
@@ -378,3 +380,167 @@ def merge_parts(W, B, k, seed):
             o = merge_order(ids[p, b], d[p, b])
             ids[p, b], d[p, b] = ids[p, b][o], d[p, b][o]
     return ids, d, counts
+
+
+# ------------------------------------------------------------------ reads whose QUERY is built from stored rows (by id, recommend)
+# A stored row that becomes a query brings its +-inf, 3e19 or 1e-23 to the query side.  inf_tail in its plain form then puts +inf
+# against +inf in one column of nearly every pair (inf - inf under Euclid, and a query that is no longer positive under Dot): those
+# stay as ERROR cases; the row-safe form (frac=0.10, what make_hnsw uses) is the one that is answered.  tests/test_value_edges_cpu.py
+# pins, id by id, what the oracle answers.
+ROW_QUERY_CASES = ([(f, m, {"frac": 0.10} if f == "inf_tail" else {}) for f, m in CASES]
+                   + [("inf_tail", m, {}) for m in (EUCLID, DOT)])
+ROW_QUERY_IDS = ["%s%s-m%d" % (f, "" if f != "inf_tail" else ("-rowsafe" if kw else "-plain"), m) for f, m, kw in ROW_QUERY_CASES]
+READ_SHAPES = ("direct", "tiered")                                 # every read kind; by id and recommend also run "screened"
+N_SEEDED = 40
+
+
+def by_id_ids(n):
+    """The stored ids the by-id tests ask about: the low ids every family keeps inside its widest tie group, the rows
+    cos_den_clamp makes special, two of short_mask, and 40 seeded live ones."""
+    fixed = [1, 3, 4, 6, 7, 8, 9, n // 2, n // 2 + 1, n - 5]
+    live = np.setdiff1d(np.arange(n), np.concatenate([dead_rows(n), fixed]))
+    more = np.random.default_rng([20291, n]).choice(live, N_SEEDED, replace=False)
+    return np.concatenate([fixed, np.sort(more)]).astype(np.int64)
+
+
+def row_requests(n, count=12):
+    """`count` seeded recommend requests over live rows: positives of length 1, 2, 5, 9 (in turn), 0 - 2 negatives."""
+    rng = np.random.default_rng([20292, n])
+    live = np.setdiff1d(np.arange(n), dead_rows(n))
+    reqs = []
+    for b in range(count):
+        e = [int(x) for x in rng.choice(live, (1, 2, 5, 9)[b % 4] + (b // 4) % 3, replace=False)]
+        cut = (1, 2, 5, 9)[b % 4]
+        reqs.append((tuple(e[:cut]), tuple(e[cut:])))
+    reqs[3] = (reqs[3][0][:8] + (1,), reqs[3][1])                  # a row of every family's tie group among nine positives
+    return tuple(reqs)
+
+
+# ------------------------------------------------------------------ the recommend fold at the edges of f32
+FOLD_N = 64
+FOLD_COLS = {"subnormal": 0, "zero": 1, "overflow": 2, "inf_minus_inf": 3, "fltmax": 4, "cancel": 5}
+FOLD_FIRST_TAME = 6                                                # columns 6 .. d-1 are gaussian in every ordinary row
+FOLD_REQUESTS = (                                                  # (name, positives, negatives)
+    ("subnormal_5", (8, 9, 10, 11, 12), ()),                      # sp = a multiple of 2^-149 near 2^-128; sp * 0.2f rounds inside the subnormal range
+    ("subnormal_9_2", (8, 9, 10, 11, 12, 13, 14, 15, 16), (44, 45)),
+    ("cancel_to_plus_zero", (19,), (20,)),                         # equal rows: ap - an = +0.0 in every element
+    ("minus_zero", (17,), (18,)),                                  # -0.0 + (-0.0 - +0.0) = -0.0
+    ("overflow_mid_fold", (22, 23, 24, 25, 46), ()),               # 2e38 + 2e38 = inf, then -2e38, -2e38: the average is finite, the fold is inf
+    ("inf_minus_inf", (26, 27), (28, 29)),                         # ap = an = inf: NaN, an error under every metric
+    ("fltmax_times_rp", (30, 31, 47), ()),                         # FLT_MAX * fl(1 / 3)
+    ("cosine_norm_underflows", (32, 33), ()),                      # 1e-25 everywhere, +1 and -1 cancel: not all zero, norm 0
+    ("tame_9_5", (48, 49, 50, 51, 52, 53, 54, 55, 56), (57, 58, 59, 60, 61)),
+    ("tame_2_9", (62, 48, ), (49, 50, 51, 52, 53, 54, 55, 56, 57)),
+    ("tame_1_2", (58,), (59, 60)),
+    ("tame_5_1", (34, 62, 3, 37, 35), (39,)),                      # rows of all three shards of a sharded handle, not in their order
+)
+# what the oracle answers for the folds (pinned by tests/test_value_edges_cpu.py): request name -> {metric: error}
+FOLD_ERRORS = {
+    "inf_minus_inf": {EUCLID: "NanDistance", COSINE: "NanDistance", DOT: "NanDistance"},
+    "cosine_norm_underflows": {COSINE: "InvalidVector"},
+    "overflow_mid_fold": {COSINE: "NanDistance"},                  # the norm of the fold is inf and so is its dot with every row: inf / inf
+    "fltmax_times_rp": {COSINE: "NanDistance"},                    # likewise against the FLT_MAX row itself
+}
+
+
+def fold_edges(d):
+    """(rows f32[64, d], requests): a hand-built block for the recommend fold (include/vdb_flat.h: a left fold from the first row,
+    one multiply by fl(1 / n), ap + (ap - an)).  Every phenomenon lives in a column of its own (FOLD_COLS), so that no distance
+    becomes NaN unless the request is an intended error (FOLD_ERRORS); the rows dead_rows(64) tombstones hold nothing special.
+      column 0   rows 8 .. 16 hold (2^19 + odd) * 2^-149: subnormal, their sums and averages stay subnormal.  Rows 40 .. 43 hold
+                 +-2^127 there and point along the fold of rows 8 .. 16 elsewhere: under Dot they lead its list and
+                 subnormal * 2^127 is an ordinary number, so a flushed fold changes their distance bits.
+      column 1   row 17 holds -0.0, row 18 +0.0
+      column 2   1.0 in every row (the fold of "overflow_mid_fold" is +inf there: inf * 0 must not arise), 1e-25 in rows 32, 33;
+                 rows 22, 23 hold 2e38 and rows 24, 25 -2e38
+      column 3   rows 26 .. 29 hold 3e38: two of them fold to inf on either side
+      column 4   row 30 holds FLT_MAX
+      rows 19, 20 are equal; rows 32, 33 hold 1e-25 everywhere but +1 / -1 in column 5."""
+    assert d >= 32
+    key = ("fold_edges", d)
+    if key not in _CACHE:
+        rng = np.random.default_rng([20293, d])
+        rows = _gauss(rng, FOLD_N, d)
+        c = FOLD_COLS
+        rows[:, :FOLD_FIRST_TAME] = 0.0
+        rows[:, c["overflow"]] = 1.0
+        sub = np.arange(8, 17)
+        rows[sub, c["subnormal"]] = ((2 ** 19 + 2 * np.arange(9) + 1) * 2.0 ** -149).astype(F32)
+        lead = np.arange(40, 44)
+        rows[lead] = F32(2.0) * rows[sub].mean(0, dtype=F32) + F32(0.05) * _gauss(rng, 4, d)
+        rows[lead, :FOLD_FIRST_TAME] = 0.0
+        rows[lead, c["overflow"]] = 1.0
+        rows[lead, c["subnormal"]] = np.array([1, -1, 1, -1], dtype=F32) * F32(2.0 ** 127)
+        rows[17, c["zero"]] = F32(-0.0)
+        rows[20] = rows[19]
+        rows[[22, 23], c["overflow"]] = F32(2e38)
+        rows[[24, 25], c["overflow"]] = F32(-2e38)
+        rows[26:30, c["inf_minus_inf"]] = F32(3e38)
+        rows[30, c["fltmax"]] = np.finfo(F32).max
+        rows[[32, 33]] = F32(1e-25)
+        rows[32, c["cancel"]], rows[33, c["cancel"]] = F32(1.0), F32(-1.0)
+        used = np.concatenate([lead] + [np.array(p + n) for _, p, n in FOLD_REQUESTS])
+        assert not np.isin(dead_rows(FOLD_N), used).any()
+        rows = np.ascontiguousarray(rows, dtype=F32)
+        rows.setflags(write=False)
+        _CACHE[key] = rows
+    return _CACHE[key], tuple((p, n) for _, p, n in FOLD_REQUESTS)
+
+
+# ------------------------------------------------------------------ one row per group: codes that need stage A, B and C
+DISTINCT_KS = {"A": 3, "B": 8, "C": 16}
+DISTINCT_GIANT = 7
+
+
+def distinct_codes(family, metric, n, d, nq, **kw):
+    """i32[n]: a code column laid along the ORACLE's ranking of query 0 over the live rows (rank position p), the giant_codes idea
+    of distinct_data: the rows at p = 3 .. 199 and 210 .. 1499 share one code.  Where the family's tie group leads the ranking
+    these are its lowest ids, and the group's representative is decided by id alone.  p = 0, 2 and 200 .. 209 have codes of their
+    own, p = 1 has none (-1: a group of its own); behind p = 1500 a row has code 100 + p % 500, every 97th none.  Query 0 then
+    sees 4 groups in its first 32 / 64 ranks and 14 in its first 1024: k = 3 ends in stage A, k = 8 in stage B, k = 16 in stage C
+    (distinct_data.stage_of; tests/test_value_edges_cpu.py asserts it).  Dead rows keep code -1."""
+    key = ("distinct_codes", family, metric, n, d, nq, tuple(sorted(kw.items())))
+    if key not in _CACHE:
+        import oracle
+        rows, q = make(family, n, d, nq, metric, **kw)
+        oi, _ = oracle.flat_search(metric, rows, q[0], n, live=live_bytes(n))
+        p = np.arange(len(oi))
+        c = (100 + p % 500).astype(np.int32)
+        c[p % 97 == 0] = -1
+        c[:1500] = DISTINCT_GIANT
+        c[[0, 2]] = [10, 12]
+        c[1] = -1
+        c[200:210] = 20 + np.arange(10)
+        codes = np.full(n, -1, dtype=np.int32)
+        codes[oi.astype(np.int64)] = c
+        codes.setflags(write=False)
+        _CACHE[key] = codes
+    return _CACHE[key]
+
+
+# ------------------------------------------------------------------ one batch, a filter per query: five bindings
+GROUP_NONE = 0xFFFFFFFF
+GROUP_HOLDS_HIDDEN = 0                                             # with hide=False only this mask (and no mask at all) admits HIDDEN(n)
+
+
+def group_masks(n, hide=True):
+    """(on bool[4, n], words u64[4, (n + 63) // 64], binding): masks 0 .. 3 = about half the ids, about 1 %, short_mask, nothing;
+    binding(nq) = u32[nq] binds the queries round-robin to 0, 1, 2, 3, GROUP_NONE.  With hide=False the row HIDDEN(n) is eligible
+    under mask 0 alone (and for the unfiltered queries, to whom every live row is)."""
+    ons = [id_mask(n, 0.5, 7, hide=hide)[0], id_mask(n, 0.01, 7)[0], short_mask(n)[0], np.zeros(n, dtype=bool)]
+    on = np.stack(ons)
+    assert not on[1:, HIDDEN(n)].any() and on[0, HIDDEN(n)] == (not hide)
+    words = np.zeros((4, (n + 63) // 64), dtype=np.uint64)
+    for g in range(4):
+        m = np.packbits(on[g].astype(np.uint8), bitorder="little")
+        words[g].view(np.uint8)[:m.size] = m
+
+    def binding(nq):
+        return np.array([(0, 1, 2, 3, GROUP_NONE)[b % 5] for b in range(nq)], dtype=np.uint32)
+    return on, words, binding
+
+
+def group_queries(q):
+    """the grouped batch of a shape: its queries, repeated until every one of the five bindings has at least two"""
+    reps = max(1, -(-10 // len(q)))
+    return np.ascontiguousarray(np.concatenate([q] * reps)) if reps > 1 else q
