@@ -306,6 +306,24 @@ int vdb_flat_set_screen(vdb_flat_index *h, int mode);
  * No reference counterpart; results are identical either way, bit for bit. */
 int vdb_flat_set_wide(vdb_flat_index *h, int on);
 
+/* The layout of the stored rows (no reference counterpart; results are identical in every mode, bit for bit).  An index
+ * whose rows have a pitch of a multiple of 64 floats may keep every row SPLIT in place into its bf16 piece and its low
+ * halves -- same address, same bytes, no extra memory -- so that the screening tier's filter pass streams 2 bytes per
+ * element instead of 4.  Only that pass and its re-ranks read split rows; every other reader or writer of the rows
+ * (the f32 and exact tiers, range, by-id, distinct, grouped, recommend, MMR, sparse, get_vector, adds, compaction, ...)
+ * first converts the store back, which costs a pass over it.  Rows holding an inf or NaN element stay plain f32.
+ *  0: never convert;
+ *  1 (default): adaptive -- after a run of screened searches of at most 256 queries with nothing else in between, the
+ *     next one converts first (never while another search of the handle is in flight);
+ *  2: convert before the next such search.
+ * On a sharded handle the mode goes to every shard; each shard decides for itself.
+ * vdb_flat_layout: out[0] = 0 plain f32 rows, 1 split rows (a sharded handle: 1 only if every shard is split);
+ * out[1] = conversions so far, both directions (summed over the shards).
+ * vdb_flat_debug_set_split_after (tests): the length of the run in mode 1 (0 = the default). */
+int vdb_flat_set_split(vdb_flat_index *h, int mode);
+int vdb_flat_layout(vdb_flat_index *h, uint64_t out[2]);
+int vdb_flat_debug_set_split_after(vdb_flat_index *h, size_t searches);
+
 /* The screening tier's LARGE-k range (no reference counterpart; results are identical either way, bit for bit):
  *  1 (default): 112 < k <= 1024 is served by the bf16 screening pass too -- a deeper filter threshold, up to 2048
  *     candidates per query, and the certified re-rank of kernels_aux.hip (rerank_large_kernel) -- on indexes of at least

@@ -15,7 +15,7 @@ SYMBOLS = [
     "vdb_flat_create", "vdb_flat_destroy", "vdb_flat_create_sharded", "vdb_flat_shards", "vdb_flat_shard_len", "vdb_flat_set_exchange", "vdb_flat_shard_stats", "vdb_flat_add", "vdb_flat_add_bulk", "vdb_flat_add_bulk_device",
     "vdb_flat_load_vector_file", "vdb_flat_remove", "vdb_flat_get_vector", "vdb_flat_len", "vdb_flat_metric", "vdb_flat_dim",
     "vdb_flat_reserve", "vdb_flat_flush", "vdb_flat_compact", "vdb_flat_set_auto_compact", "vdb_flat_store_stats", "vdb_flat_search", "vdb_flat_search_batch",
-    "vdb_flat_search_batch_device", "vdb_flat_search_batch_device_begin", "vdb_flat_search_batch_device_finish", "vdb_flat_search_batch_device_submit", "vdb_flat_search_batch_device_wait", "vdb_flat_distances_batch", "vdb_merge_topk_device", "vdb_merge_topk_packed_device", "vdb_flat_set_profile", "vdb_flat_last_stats", "vdb_flat_last_stats_ex", "vdb_flat_set_screen", "vdb_flat_set_wide", "vdb_flat_set_large_k", "vdb_flat_large_k_min_rows", "vdb_flat_set_shadow", "vdb_flat_set_sample_cache", "vdb_flat_set_tiers", "vdb_flat_debug_screen_scores", "vdb_flat_debug_rows", "vdb_flat_debug_row_info", "vdb_flat_debug_last_thresholds", "vdb_flat_debug_cert_probe", "vdb_flat_debug_compact_plan", "vdb_flat_debug_set_compact_bounce", "vdb_last_error",
+    "vdb_flat_search_batch_device", "vdb_flat_search_batch_device_begin", "vdb_flat_search_batch_device_finish", "vdb_flat_search_batch_device_submit", "vdb_flat_search_batch_device_wait", "vdb_flat_distances_batch", "vdb_merge_topk_device", "vdb_merge_topk_packed_device", "vdb_flat_set_profile", "vdb_flat_last_stats", "vdb_flat_last_stats_ex", "vdb_flat_set_screen", "vdb_flat_set_wide", "vdb_flat_set_split", "vdb_flat_layout", "vdb_flat_debug_set_split_after", "vdb_flat_set_large_k", "vdb_flat_large_k_min_rows", "vdb_flat_set_shadow", "vdb_flat_set_sample_cache", "vdb_flat_set_tiers", "vdb_flat_debug_screen_scores", "vdb_flat_debug_rows", "vdb_flat_debug_row_info", "vdb_flat_debug_last_thresholds", "vdb_flat_debug_cert_probe", "vdb_flat_debug_compact_plan", "vdb_flat_debug_set_compact_bounce", "vdb_last_error",
     "vdb_flat_range_search_batch", "vdb_flat_range_search_batch_device", "vdb_flat_range_stats",
     "vdb_flat_search_batch_by_id", "vdb_flat_search_batch_by_id_filtered", "vdb_flat_by_id_stats",
     "vdb_flat_recommend_batch", "vdb_flat_recommend_batch_filtered", "vdb_flat_recommend_stats",
@@ -124,6 +124,9 @@ def lib():
     L.vdb_flat_last_stats_ex.argtypes = [vp, u64p, sz]
     L.vdb_flat_set_screen.argtypes = [vp, c.c_int]
     L.vdb_flat_set_wide.argtypes = [vp, c.c_int]
+    L.vdb_flat_set_split.argtypes = [vp, c.c_int]
+    L.vdb_flat_layout.argtypes = [vp, u64p]
+    L.vdb_flat_debug_set_split_after.argtypes = [vp, sz]
     L.vdb_flat_set_large_k.argtypes = [vp, c.c_int]
     L.vdb_flat_set_sparse_filter.argtypes = [vp, c.c_int]
     L.vdb_flat_sparse_stats.argtypes = [vp, u64p]

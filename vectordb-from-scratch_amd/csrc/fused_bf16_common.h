@@ -45,6 +45,17 @@ __device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
     f32x2 v = {a, b};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));   // v_cvt_pk_bf16_f32 (RNE)
 }
+// THE SPLIT LAYOUT'S ROUNDING (row_split.h).  Over a store in the SPLIT layout kernels_fused_s16.hip reads the hi word of an
+// element in the place of pk_bf16's result: hi = upper16(x) + bit 15 of x, the element rounded to bf16 HALF UP IN MAGNITUDE.
+// It equals the RNE value except where the low half is exactly 0x8000 (a tie), and there it is the other neighbour of the
+// tie, so |x - hi| <= half a bf16 ulp of x for every finite x, exactly the bound RNE gives -- and where RNE overflows to
+// +-inf so does hi (upper 0x7f7f, lo >= 0x8000), nowhere else.  Every constant of the certificate (vdb_cert.cpp) and every
+// per-row margin and error maximum of launch_row_stats is derived from that half-ulp bound per element (|e_d| <= 2^-9 |d|
+// relative, |x - bf16(x)| absolute as an UPPER bound on what a reader may see), never from the direction of a tie: a tie's
+// two neighbours are equally far away, so the stored |x - bf16(x)| is the same number for both.  They stay valid unchanged.
+// The scores of a tie element differ between the layouts; the results do not, because scores only rank (THE METHOD above).
+// The compact sample copy keeps RNE values: any threshold is valid for the filter, it only has to let enough rows pass.
+// Non-finite elements never reach the hi plane: the forward conversion reports them and the index stays F32.
 __device__ __forceinline__ bf16x8 cvt8(const float4& lo, const float4& hi) {
     u32x4 r = {pk_bf16(lo.x, lo.y), pk_bf16(lo.z, lo.w), pk_bf16(hi.x, hi.y), pk_bf16(hi.z, hi.w)};
     return __builtin_bit_cast(bf16x8, r);

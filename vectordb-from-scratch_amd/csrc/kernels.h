@@ -2,6 +2,8 @@
 // and the host-side index (vdb_flat.cpp).  gfx950 (MI355X) only.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "row_split.h"
 #include <stddef.h>
 #include <stdint.h>
 
@@ -81,6 +83,9 @@ void launch_row_stats(const RowStatsParams& p, hipStream_t s);
 void launch_rows_to_bf16(const float* rows, uint16_t* rows16, uint32_t ld, uint32_t row_begin, uint32_t row_end, hipStream_t s);
 // compact bf16 copy of the S = 2^shift sample rows of the screening tier: out[j] = bf16(rows[screen_sample_row(j)]), j < S
 void launch_sample_to_bf16(const float* rows, uint32_t ld, uint32_t n_rows, uint32_t n_sample, uint32_t shift, uint16_t* out, hipStream_t s);
+// kernels_split.hip: rows [0, n_rows) converted in place between the F32 and the SPLIT layout (row_split.h; ld a multiple of 32,
+// at most 16384).  forward: *nonfinite is OR-ed with 1 if any element has an all-ones exponent (the caller zeroes it first).
+void launch_row_split(float* rows, uint32_t ld, uint32_t n_rows, bool forward, uint32_t* nonfinite, uint32_t n_cu, hipStream_t s);
 
 // count live rows whose norm is exactly zero (Cosine: distance.rs:51-55)
 void launch_count_zero_live(const float* nd, const uint32_t* livemask, uint32_t n_rows,
@@ -224,6 +229,8 @@ __host__ __device__ inline uint32_t screen_sample_row(uint32_t j, uint32_t n_sam
 struct FusedBf16Params {
     const float* rows; uint32_t ld; uint32_t n_rows;
     const uint16_t* rows16;                            // bf16 shadow of `rows`, same pitch (kernels_fused_s16.hip; null unless vdb_flat_set_shadow and ld % 64 == 0)
+    uint32_t rows16_pitch;                             // 16-bit words between two rows of rows16; 0 = ld (the shadow, the sample copy).  2 * ld: rows16 is the
+                                                       // store itself in the SPLIT layout (row_split.h) and the kernel streams the hi piece of every row
     const uint16_t* qb;                                // [256][ld] bf16 queries of this pass (zero padded)
     const float* alpha; const float* beta;
     // non-null (Dot / Euclid): the kernels rank by the LOWER-BOUND score  fma(-qg[q], margin[row], fma(dot, alpha, beta)),
@@ -310,6 +317,8 @@ struct RerankParams {
                                                        // LOWER-BOUND scores of FusedBf16Params::margin -- every row-dependent
                                                        // error term is already inside them
     uint32_t lds_row_stride, lds_chunk;                // filled by launch_rerank
+    uint32_t split;                                    // 1: `rows` is in the SPLIT layout (row_split.h; ld % 64 == 0): launch_rerank, _rerank_all, _rerank_large and
+                                                       // _rerank_all_large stage the hi and the lo piece of a slice and rebuild each f32 in the fold
 };
 void launch_rerank(const RerankParams& p, uint32_t nq, hipStream_t s);
 // the large-k re-rank of the screening tier: 112 < k <= 1024, up to 2048 candidates per query (kernels_aux.hip)

@@ -702,6 +702,9 @@ void launch_cert_probe(const RerankParams& p, const uint32_t* qi, const float* T
 constexpr uint32_t RR_MAX = 512;        // candidates per query at most (= RR_THREADS: one thread per candidate)
 constexpr uint32_t RR_THREADS = 512;
 
+// SPLIT: p.rows is in the SPLIT layout (row_split.h); an instance of its own, so that the f32-row instance is compiled as if the
+// other did not exist
+template <bool SPLIT>
 __global__ __launch_bounds__(RR_THREADS) void rerank_kernel(RerankParams p) {
     extern __shared__ __attribute__((aligned(16))) float sRows[];   // query row + `chunk` candidate rows
     __shared__ uint32_t sDist[RR_MAX];    // ordered exact distance
@@ -744,6 +747,7 @@ __global__ __launch_bounds__(RR_THREADS) void rerank_kernel(RerankParams p) {
     __syncthreads();
     const uint32_t nwaves = RR_THREADS / 64;
     const float qn_f = p.qnorm[q];
+    constexpr bool split = SPLIT;
     VDB_STAMP(1)
 
     uint32_t processed = 0;
@@ -798,21 +802,22 @@ __global__ __launch_bounds__(RR_THREADS) void rerank_kernel(RerankParams p) {
             float acc = 0.0f;
             for (uint32_t k0 = 0; n && k0 < dimp; k0 += W) {
                 const uint32_t wlen = dimp - k0 < W ? dimp - k0 : W;           // floats of this slice (a multiple of 4)
-                const uint32_t vpr = wlen / 4, bpr = (vpr + 63) / 64;
+                const uint32_t bpr = slice_pieces(wlen, split);
                 // stage the slice by LDS-DMA (global_load_lds_dwordx4: 1 KB of a row per wave instruction, no VGPR round
-                // trip), every piece in flight at once; the barrier's vmcnt(0) waits for them
+                // trip), every piece in flight at once; the barrier's vmcnt(0) waits for them.  SPLIT layout: the slice's hi
+                // piece and its lo piece, the same bytes in all
                 for (uint32_t u = wv; u < n * bpr; u += nwaves) {
-                    const uint32_t r = u / bpr, b = u % bpr, c4 = b * 64 + lane;
+                    const uint32_t r = u / bpr, b = u % bpr;
                     const uint32_t row = sRowIdx[processed + r];
-                    if (row != 0xffffffffu && c4 < vpr)
-                        __builtin_amdgcn_global_load_lds((rr_glb_t)(p.rows + (size_t)row * p.ld + k0 + 4 * c4),
-                                                         (rr_lds_t)(sR + (size_t)r * Wp + 256 * b), 16, 0, 0);
+                    if (row != 0xffffffffu) stage_slice_piece(p.rows, p.ld, row, k0, wlen, split, b, lane, sR + (size_t)r * Wp);
                 }
                 __syncthreads();
                 if (myrow != 0xffffffffu) {
                     const uint32_t flen = (k0 + wlen > p.dim) ? p.dim - k0 : wlen;   // the fold stops at dim, not at the padding
-                    acc = p.metric == EUCLID ? fold_sqdiff_part(sQ + k0, sR + (size_t)tid * Wp, flen, acc)
-                                             : fold_dot_part(sQ + k0, sR + (size_t)tid * Wp, flen, acc);
+                    const float* xs = sR + (size_t)tid * Wp;
+                    if (split) acc = p.metric == EUCLID ? fold_sqdiff_part_split(sQ + k0, xs, (wlen + 7u) & ~7u, flen, acc)
+                                                        : fold_dot_part_split(sQ + k0, xs, (wlen + 7u) & ~7u, flen, acc);
+                    else acc = p.metric == EUCLID ? fold_sqdiff_part(sQ + k0, xs, flen, acc) : fold_dot_part(sQ + k0, xs, flen, acc);
                 }
                 __syncthreads();
             }
@@ -938,6 +943,7 @@ __global__ __launch_bounds__(RR_THREADS) void rerank_kernel(RerankParams p) {
 // in behind them and the area cut back to k.  The list is complete by construction (every row whose score is at or
 // below the cut passed the filter), so the result is exact unless the list was truncated upstream.
 // ---------------------------------------------------------------------------------------------
+template <bool SPLIT>
 __global__ __launch_bounds__(RR_THREADS) void rerank_all_kernel(RerankParams p) {
     extern __shared__ __attribute__((aligned(16))) float sRows[];
     constexpr uint32_t AREA = 256;                                // k <= 112 plus a chunk of <= 64
@@ -965,7 +971,7 @@ __global__ __launch_bounds__(RR_THREADS) void rerank_all_kernel(RerankParams p) 
         float dist;
         uint32_t row;
         const bool have = stage_chunk_distances<RR_THREADS>(cand + c0, nthis, p.rows, p.ld, p.dim, p.n_rows, p.rowmask, p.nd, p.metric, qn_f,
-                                                            sQ, sR, ldp, sRowIdx, &sNanKey, &dist, &row);
+                                                            sQ, sR, ldp, sRowIdx, &sNanKey, &dist, &row, SPLIT);
         if (tid < nthis) {
             uint32_t od = 0xffffffffu;
             uint64_t id = ~0ull;
@@ -1005,12 +1011,13 @@ __global__ __launch_bounds__(RR_THREADS) void rerank_all_kernel(RerankParams p) 
 void launch_rerank_all(const RerankParams& p, uint32_t nq, hipStream_t s) {
     if (!nq) return;
     RerankParams q = p;
-    q.lds_row_stride = rerank_row_stride(p.dim);
+    q.lds_row_stride = rerank_row_stride(p.split ? (p.dim + 7u) & ~7u : p.dim);   // SPLIT: both pieces of a row in whole 16 bytes
     uint32_t chunk = (uint32_t)std::min<size_t>(64, (150 * 1024) / ((size_t)q.lds_row_stride * 4));
     chunk = chunk > 1 ? chunk - 1 : 1;
     q.lds_chunk = chunk;
     size_t lds = (size_t)(chunk + 1) * q.lds_row_stride * 4;
-    hipLaunchKernelGGL(rerank_all_kernel, dim3(nq), dim3(RR_THREADS), lds, s, q);
+    if (q.split) hipLaunchKernelGGL(rerank_all_kernel<true>, dim3(nq), dim3(RR_THREADS), lds, s, q);
+    else hipLaunchKernelGGL(rerank_all_kernel<false>, dim3(nq), dim3(RR_THREADS), lds, s, q);
 }
 
 void launch_rerank(const RerankParams& p, uint32_t nq, hipStream_t s) {
@@ -1025,7 +1032,8 @@ void launch_rerank(const RerankParams& p, uint32_t nq, hipStream_t s) {
     const size_t avail = (size_t)150 * 1024 / 4 - q.lds_row_stride;            // dim <= 16384: at least 21 K floats = 512 rows of 40
     q.lds_chunk = (uint32_t)avail;
     size_t lds = ((size_t)q.lds_row_stride + q.lds_chunk) * 4;
-    hipLaunchKernelGGL(rerank_kernel, dim3(nq), dim3(RR_THREADS), lds, s, q);
+    if (q.split) hipLaunchKernelGGL(rerank_kernel<true>, dim3(nq), dim3(RR_THREADS), lds, s, q);
+    else hipLaunchKernelGGL(rerank_kernel<false>, dim3(nq), dim3(RR_THREADS), lds, s, q);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1043,7 +1051,7 @@ constexpr uint32_t RL_AREA = 2048;                                // best k (<= 
 // ALL = true is the EXHAUSTIVE form (the re-threshold pass at large k, launch_rerank_all_large): the same sweep over every key of
 // the list in one round, in any order; a key whose row is out of range or masked out is skipped, no certificate is evaluated
 // (the list is complete by construction: cert = 1 unless a NaN score was seen; a truncated list is flagged by the select).
-template <bool ALL>
+template <bool ALL, bool SPLIT>
 __device__ __forceinline__ void rerank_large_body(const RerankParams& p) {
     extern __shared__ __attribute__((aligned(16))) float sRows[];   // query row + slice area of one sweep
     __shared__ uint32_t sDist[RL_AREA];
@@ -1067,6 +1075,7 @@ __device__ __forceinline__ void rerank_large_body(const RerankParams& p) {
     __syncthreads();
     const uint32_t nwaves = RL_THREADS / 64;
     const float qn_f = p.qnorm[q];
+    constexpr bool split = SPLIT;
 
     uint32_t processed = 0, nbest = 0;                            // candidates re-ranked; pairs held in [0, nbest)
     uint32_t target = cnt < p.kp_first ? cnt : p.kp_first;
@@ -1097,19 +1106,19 @@ __device__ __forceinline__ void rerank_large_body(const RerankParams& p) {
             float acc = 0.0f;
             for (uint32_t k0 = 0; k0 < dimp; k0 += W) {
                 const uint32_t wlen = dimp - k0 < W ? dimp - k0 : W;
-                const uint32_t vpr = wlen / 4, bpr = (vpr + 63) / 64;
+                const uint32_t bpr = slice_pieces(wlen, split);
                 for (uint32_t u = wv; u < n * bpr; u += nwaves) {
-                    const uint32_t r = u / bpr, b = u % bpr, c4 = b * 64 + lane;
+                    const uint32_t r = u / bpr, b = u % bpr;
                     const uint32_t row = sRowIdx[r];
-                    if (row != 0xffffffffu && c4 < vpr)
-                        __builtin_amdgcn_global_load_lds((rr_glb_t)(p.rows + (size_t)row * p.ld + k0 + 4 * c4),
-                                                         (rr_lds_t)(sR + (size_t)r * Wp + 256 * b), 16, 0, 0);
+                    if (row != 0xffffffffu) stage_slice_piece(p.rows, p.ld, row, k0, wlen, split, b, lane, sR + (size_t)r * Wp);
                 }
                 __syncthreads();
                 if (myrow != 0xffffffffu) {
                     const uint32_t flen = (k0 + wlen > p.dim) ? p.dim - k0 : wlen;
-                    acc = p.metric == EUCLID ? fold_sqdiff_part(sQ + k0, sR + (size_t)tid * Wp, flen, acc)
-                                             : fold_dot_part(sQ + k0, sR + (size_t)tid * Wp, flen, acc);
+                    const float* xs = sR + (size_t)tid * Wp;
+                    if (split) acc = p.metric == EUCLID ? fold_sqdiff_part_split(sQ + k0, xs, (wlen + 7u) & ~7u, flen, acc)
+                                                        : fold_dot_part_split(sQ + k0, xs, (wlen + 7u) & ~7u, flen, acc);
+                    else acc = p.metric == EUCLID ? fold_sqdiff_part(sQ + k0, xs, flen, acc) : fold_dot_part(sQ + k0, xs, flen, acc);
                 }
                 __syncthreads();
             }
@@ -1201,8 +1210,8 @@ __device__ __forceinline__ void rerank_large_body(const RerankParams& p) {
         }
     }
 }
-__global__ __launch_bounds__(RL_THREADS) void rerank_large_kernel(RerankParams p) { rerank_large_body<false>(p); }
-__global__ __launch_bounds__(RL_THREADS) void rerank_all_large_kernel(RerankParams p) { rerank_large_body<true>(p); }
+template <bool SPLIT> __global__ __launch_bounds__(RL_THREADS) void rerank_large_kernel(RerankParams p) { rerank_large_body<false, SPLIT>(p); }
+template <bool SPLIT> __global__ __launch_bounds__(RL_THREADS) void rerank_all_large_kernel(RerankParams p) { rerank_large_body<true, SPLIT>(p); }
 void launch_rerank_large(const RerankParams& p, uint32_t nq, hipStream_t s) {
     if (!nq || p.k == 0 || p.k > RL_KMAX) return;
     RerankParams q = p;
@@ -1215,7 +1224,8 @@ void launch_rerank_large(const RerankParams& p, uint32_t nq, hipStream_t s) {
     const size_t avail = (size_t)128 * 1024 / 4 - q.lds_row_stride;
     q.lds_chunk = (uint32_t)avail;
     const size_t lds = ((size_t)q.lds_row_stride + q.lds_chunk) * 4;
-    hipLaunchKernelGGL(rerank_large_kernel, dim3(nq), dim3(RL_THREADS), lds, s, q);
+    if (q.split) hipLaunchKernelGGL(rerank_large_kernel<true>, dim3(nq), dim3(RL_THREADS), lds, s, q);
+    else hipLaunchKernelGGL(rerank_large_kernel<false>, dim3(nq), dim3(RL_THREADS), lds, s, q);
 }
 // the exhaustive form (the re-threshold pass): every key of the list in ONE round, the same LDS plan
 void launch_rerank_all_large(const RerankParams& p, uint32_t nq, hipStream_t s) {
@@ -1227,7 +1237,8 @@ void launch_rerank_all_large(const RerankParams& p, uint32_t nq, hipStream_t s) 
     q.lds_row_stride = dimp + 4;
     q.lds_chunk = (uint32_t)((size_t)128 * 1024 / 4 - q.lds_row_stride);
     const size_t lds = ((size_t)q.lds_row_stride + q.lds_chunk) * 4;
-    hipLaunchKernelGGL(rerank_all_large_kernel, dim3(nq), dim3(RL_THREADS), lds, s, q);
+    if (q.split) hipLaunchKernelGGL(rerank_all_large_kernel<true>, dim3(nq), dim3(RL_THREADS), lds, s, q);
+    else hipLaunchKernelGGL(rerank_all_large_kernel<false>, dim3(nq), dim3(RL_THREADS), lds, s, q);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -3,6 +3,7 @@
 // cut.  Every includer is built with -ffp-contract=off: each multiply and add below rounds on its own.
 #pragma once
 #include "kernels.h"
+#include "row_split.h"
 
 #pragma clang fp contract(off)
 
@@ -133,6 +134,97 @@ __device__ __forceinline__ float fold_sqdiff_part(const float* __restrict__ q, c
     for (; i < d; ++i) { float t = __fsub_rn(q[i], x[i]); s = __fadd_rn(s, __fmul_rn(t, t)); }
     return s;
 }
+// The same two folds over a slice of a row of the SPLIT layout (row_split.h) as the re-rank kernels stage it: xs holds the 16-bit
+// hi words of the slice's n8 elements (n8 a multiple of 8: whole 16-byte pieces) and behind them their lo words.  Each f32 is
+// rebuilt from its two halves, two elements per 32-bit word pair, and folded exactly as above: the same values in the same
+// order, so the sums are those of the F32 layout bit for bit.
+__device__ __forceinline__ void split_join16(const uint32_t* __restrict__ hi, const uint32_t* __restrict__ lo, float4 (&b)[4]) {
+    uint4 h[2], l[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) { h[u] = *reinterpret_cast<const uint4*>(hi + 4 * u); l[u] = *reinterpret_cast<const uint4*>(lo + 4 * u); }
+    const uint32_t hw[8] = {h[0].x, h[0].y, h[0].z, h[0].w, h[1].x, h[1].y, h[1].z, h[1].w};
+    const uint32_t lw[8] = {l[0].x, l[0].y, l[0].z, l[0].w, l[1].x, l[1].y, l[1].z, l[1].w};
+    uint32_t e[16];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) split_join2(hw[u], lw[u], &e[2 * u], &e[2 * u + 1]);
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+        b[u] = float4{__uint_as_float(e[4 * u]), __uint_as_float(e[4 * u + 1]), __uint_as_float(e[4 * u + 2]), __uint_as_float(e[4 * u + 3])};
+}
+__device__ __forceinline__ float split_elem(const float* xs, uint32_t n8, uint32_t i) {
+    const uint16_t* w = reinterpret_cast<const uint16_t*>(xs);
+    return __uint_as_float(split_join(w[i], w[n8 + i]));
+}
+__device__ __forceinline__ float fold_dot_part_split(const float* __restrict__ q, const float* __restrict__ xs, uint32_t n8, uint32_t d, float s) {
+    const uint32_t* hi = reinterpret_cast<const uint32_t*>(xs);
+    const uint32_t* lo = hi + n8 / 2;
+    uint32_t i = 0;
+    for (; i + 16 <= d; i += 16) {
+        float4 a[4], b[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) a[u] = *reinterpret_cast<const float4*>(q + i + 4 * u);
+        split_join16(hi + i / 2, lo + i / 2, b);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const vdb_f2 p01 = vdb_f2{a[u].x, a[u].y} * vdb_f2{b[u].x, b[u].y};
+            const vdb_f2 p23 = vdb_f2{a[u].z, a[u].w} * vdb_f2{b[u].z, b[u].w};
+            s = __fadd_rn(s, p01.x);
+            s = __fadd_rn(s, p01.y);
+            s = __fadd_rn(s, p23.x);
+            s = __fadd_rn(s, p23.y);
+        }
+    }
+    for (; i < d; ++i) s = __fadd_rn(s, __fmul_rn(q[i], split_elem(xs, n8, i)));
+    return s;
+}
+__device__ __forceinline__ float fold_sqdiff_part_split(const float* __restrict__ q, const float* __restrict__ xs, uint32_t n8, uint32_t d, float s) {
+    const uint32_t* hi = reinterpret_cast<const uint32_t*>(xs);
+    const uint32_t* lo = hi + n8 / 2;
+    uint32_t i = 0;
+    for (; i + 16 <= d; i += 16) {
+        float4 a[4], b[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) a[u] = *reinterpret_cast<const float4*>(q + i + 4 * u);
+        split_join16(hi + i / 2, lo + i / 2, b);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const vdb_f2 t01 = vdb_f2{a[u].x, a[u].y} - vdb_f2{b[u].x, b[u].y};
+            const vdb_f2 t23 = vdb_f2{a[u].z, a[u].w} - vdb_f2{b[u].z, b[u].w};
+            const vdb_f2 p01 = t01 * t01, p23 = t23 * t23;
+            s = __fadd_rn(s, p01.x);
+            s = __fadd_rn(s, p01.y);
+            s = __fadd_rn(s, p23.x);
+            s = __fadd_rn(s, p23.y);
+        }
+    }
+    for (; i < d; ++i) { float t = __fsub_rn(q[i], split_elem(xs, n8, i)); s = __fadd_rn(s, __fmul_rn(t, t)); }
+    return s;
+}
+// A K slice [k0, k0 + wlen) of candidate row `row` into LDS at dst, by the 64 lanes of a wave, piece b of 64 x 16 bytes
+// (global_load_lds: lane L lands at dst + 256 b floats + 16 L bytes).  F32: the wlen floats (wlen a multiple of 4).  SPLIT
+// (ld % 64 == 0): the slice's hi piece, then its lo piece, each rounded up to whole 16 bytes -- n8 = (wlen + 7) & ~7 elements,
+// the same byte count; the fold is then fold_*_part_split(.., n8, ..).  k0 is a multiple of 16 in both.
+typedef __attribute__((address_space(3))) void* rr_lds_t;
+typedef const __attribute__((address_space(1))) void* rr_glb_t;
+__device__ __forceinline__ uint32_t slice_pieces(uint32_t wlen, bool split) {
+    const uint32_t vpr = split ? ((wlen + 7u) & ~7u) / 4 : wlen / 4;
+    return (vpr + 63) / 64;
+}
+__device__ __forceinline__ void stage_slice_piece(const float* __restrict__ rows, uint32_t ld, uint32_t row, uint32_t k0, uint32_t wlen, bool split,
+                                                  uint32_t b, uint32_t lane, float* dst) {
+    const uint32_t c4 = b * 64 + lane;
+    if (!split) {
+        if (c4 < wlen / 4)
+            __builtin_amdgcn_global_load_lds((rr_glb_t)(rows + (size_t)row * ld + k0 + 4 * c4), (rr_lds_t)(dst + 256 * b), 16, 0, 0);
+        return;
+    }
+    const uint32_t nch = ((wlen + 7u) & ~7u) / 8;                       // 16-byte pieces of each half
+    if (c4 < 2 * nch) {
+        const char* base = reinterpret_cast<const char*>(rows + (size_t)row * ld);
+        const char* src = c4 < nch ? base + 2 * (size_t)k0 + 16 * c4 : base + 2 * (size_t)ld + 2 * (size_t)k0 + 16 * (c4 - nch);
+        __builtin_amdgcn_global_load_lds((rr_glb_t)src, (rr_lds_t)(dst + 256 * b), 16, 0, 0);
+    }
+}
 // the distance from the finished fold (s = sum of squared differences under Euclid, the dot product otherwise)
 __device__ __forceinline__ float distance_from_fold(int metric, float s, float qn, float xn) {
     if (metric == EUCLID) return __builtin_sqrtf(s);
@@ -217,8 +309,6 @@ __device__ __forceinline__ void fold_multi(int metric, const float* x, uint32_t 
 // What the exhaustive re-ranks share (rerank_all_kernel, rerank_large_body, range_rerank_kernel): the LDS plan of a staged row,
 // the staging of a chunk of candidate rows with their exact distances, and the sort of (ordered distance, id) pairs.
 // ---------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void* rr_lds_t;
-typedef const __attribute__((address_space(1))) void* rr_glb_t;
 constexpr uint32_t NO_ROW = 0xffffffffu;                          // sRowIdx entry of a key that is skipped
 
 // floats between two rows staged in LDS: the padded dimension, plus 4 where it is a multiple of 8 (bank spread of the float4 reads)
@@ -237,9 +327,10 @@ template <uint32_t THREADS>
 __device__ __forceinline__ bool stage_chunk_distances(const uint64_t* __restrict__ keys, uint32_t nthis, const float* __restrict__ rows,
                                                       uint32_t ld, uint32_t dim, uint32_t n_rows, const uint32_t* __restrict__ rowmask,
                                                       const float* __restrict__ nd, int metric, float qn, const float* sQ, float* sR,
-                                                      uint32_t ldp, uint32_t* sRowIdx, uint32_t* sNanKey, float* dist, uint32_t* row_out) {
+                                                      uint32_t ldp, uint32_t* sRowIdx, uint32_t* sNanKey, float* dist, uint32_t* row_out,
+                                                      bool split = false) {
     const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const uint32_t vpr = ((dim + 3) & ~3u) / 4, bpr = (vpr + 63) / 64;
+    const uint32_t dimp = (dim + 3) & ~3u, bpr = slice_pieces(dimp, split);
     if (tid < nthis) {
         const uint64_t key = keys[tid];
         const uint32_t row = (uint32_t)key;
@@ -249,16 +340,20 @@ __device__ __forceinline__ bool stage_chunk_distances(const uint64_t* __restrict
     }
     __syncthreads();
     for (uint32_t u = wv; u < nthis * bpr; u += THREADS / 64) {
-        const uint32_t r = u / bpr, b = u % bpr, c4 = b * 64 + lane;
+        const uint32_t r = u / bpr, b = u % bpr;
         const uint32_t row = sRowIdx[r];
-        if (row != NO_ROW && c4 < vpr)
-            __builtin_amdgcn_global_load_lds((rr_glb_t)(rows + (size_t)row * ld + 4 * c4), (rr_lds_t)(sR + (size_t)r * ldp + 256 * b), 16, 0, 0);
+        if (row != NO_ROW) stage_slice_piece(rows, ld, row, 0, dimp, split, b, lane, sR + (size_t)r * ldp);
     }
     __syncthreads();
     if (tid >= nthis) return false;
     const uint32_t row = sRowIdx[tid];
     if (row == NO_ROW) return false;
-    *dist = exact_distance(metric, sQ, sR + (size_t)tid * ldp, dim, qn, nd[row]);
+    if (split) {                                                    // (SPLIT: the caller's ldp holds (dimp + 7) & ~7 floats)
+        const float* xs = sR + (size_t)tid * ldp;
+        const uint32_t n8 = (dimp + 7u) & ~7u;
+        const float f = metric == EUCLID ? fold_sqdiff_part_split(sQ, xs, n8, dim, 0.0f) : fold_dot_part_split(sQ, xs, n8, dim, 0.0f);
+        *dist = distance_from_fold(metric, f, qn, nd[row]);
+    } else *dist = exact_distance(metric, sQ, sR + (size_t)tid * ldp, dim, qn, nd[row]);
     *row_out = row;
     return true;
 }

@@ -71,7 +71,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     const uint32_t c = lane & 31, h = lane >> 5;
     const uint32_t ld = p.ld;                                           // elements; a multiple of 64 (host checks)
     const uint32_t KH = ld / 32;                                        // half-stages per tile (even)
-    const uint32_t rowb = ld * 2;                                       // bytes per shadow row
+    // bytes between two rows: 2 ld over the shadow and the sample copy, 4 ld over the store in the SPLIT layout, whose rows
+    // begin with their hi piece (row_split.h).  The pitch enters the per-lane offsets and the tile jump, nothing in the loop.
+    const uint32_t rowb = (!SAMPLE && p.rows16_pitch ? p.rows16_pitch : ld) * 2;
 
     // ---- the rows this workgroup covers: whole tiles dealt round-robin, as in the f32-row kernel (same sub-pools, same keys)
     const uint32_t nblk = ((SAMPLE ? p.n_sample : p.n_rows) + TR - 1) / TR;

@@ -189,7 +189,7 @@ int vdb_flat_add_bulk_device(vdb_flat_index* ix, const uint64_t* ids, uint64_t f
     uint32_t first = ix->n_rows();
     if ((rc = grow(ix, first + (uint32_t)n))) return rc;
     hipStream_t s = ix->stream;
-    HIP_TRY(hipMemcpy2DAsync(ix->d_rows + (size_t)first * ix->ld, (size_t)ix->ld * 4, d_rows, dim * 4, dim * 4, n,
+    HIP_TRY(hipMemcpy2DAsync(rows_mut(ix) + (size_t)first * ix->ld, (size_t)ix->ld * 4, d_rows, dim * 4, dim * 4, n,
                              hipMemcpyDeviceToDevice, s));
     ix->row_ids.reserve(first + n);
     ix->id2row.reserve(first + n);
@@ -209,10 +209,10 @@ int vdb_flat_add_bulk_device(vdb_flat_index* ix, const uint64_t* ids, uint64_t f
     }
     HIP_TRY(hipMemcpyAsync(ix->d_row_ids + first, ix->row_ids.data() + first, n * 8, hipMemcpyHostToDevice, s));
     const MarginPlan mp = margin_plan(ix);
-    vdb::RowStatsParams rp{ix->d_rows, ix->ld, ix->dim, first, first + (uint32_t)n, ix->metric, ix->d_nd,
+    vdb::RowStatsParams rp{rows_f32(ix), ix->ld, ix->dim, first, first + (uint32_t)n, ix->metric, ix->d_nd,
                            ix->d_alpha, ix->d_beta, ix->d_scalars, ix->d_margin, mp.m_e, mp.m_n, mp.m_b, mp.beta_shrink};
     vdb::launch_row_stats(rp, s);
-    if (ix->d_rows16) vdb::launch_rows_to_bf16(ix->d_rows, ix->d_rows16, ix->ld, first, first + (uint32_t)n, s);
+    if (ix->d_rows16) vdb::launch_rows_to_bf16(rows_f32(ix), ix->d_rows16, ix->ld, first, first + (uint32_t)n, s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
     ix->n_uploaded = first + (uint32_t)n;
@@ -291,7 +291,7 @@ int vdb_flat_get_vector(vdb_flat_index* ix, uint64_t id, float* out, size_t cap,
     if (row >= ix->n_uploaded) {
         memcpy(out, ix->pending.data() + (size_t)(row - ix->n_uploaded) * ix->ld, ncopy * sizeof(float));
     } else {
-        HIP_TRY(hipMemcpy(out, ix->d_rows + (size_t)row * ix->ld, ncopy * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out, rows_f32(ix) + (size_t)row * ix->ld, ncopy * sizeof(float), hipMemcpyDeviceToHost));
     }
     return VDB_OK;
     });
@@ -663,7 +663,7 @@ static int mmr_copy_out(vdb_flat_index* ix, const HostSearch& r, const Lists& fo
     const uint64_t ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
     HIP_TRY(hipMemsetAsync(W.stat.p, 0, 4, s));
     vdb::MmrParams mp{};
-    mp.rows = ix->d_rows; mp.ld = ix->ld; mp.dim = ix->dim; mp.n_rows = ix->n_uploaded; mp.metric = ix->metric;
+    mp.rows = rows_f32(ix); mp.ld = ix->ld; mp.dim = ix->dim; mp.n_rows = ix->n_uploaded; mp.metric = ix->metric;
     mp.ids = found.ids; mp.dists = found.dists; mp.counts = found.counts; mp.cand_rows = W.meta.p + o_row; mp.stride = (uint32_t)stride;
     mp.ks = W.meta.p; mp.lambda = reinterpret_cast<const float*>(W.meta.p + o_l); mp.mu = reinterpret_cast<const float*>(W.meta.p + o_m);
     mp.out_ids = W.outi.p; mp.out_dists = W.outd.p; mp.out_scores = W.outs.p; mp.out_counts = W.outc.p; mp.kout = (uint32_t)kcut;
@@ -768,14 +768,14 @@ static int search_batch_host(vdb_flat_index* ix, HostSearch r) {
     if (rec) {
         // only the lists go up; the fold reads the examples where they are stored
         if ((rc = recommend_stage(W->w_rec, *rec, nq, self_rows.data(), s, &rl))) return rc;
-        vdb::launch_fold_examples(ix->d_rows, ix->ld, ix->dim, ix->n_uploaded, rl, (uint32_t)nq, W->w_qin.p, s);
+        vdb::launch_fold_examples(rows_f32(ix), ix->ld, ix->dim, ix->n_uploaded, rl, (uint32_t)nq, W->w_qin.p, s);
         HIP_TRY(hipGetLastError());
     } else if (by) {
         // only the row numbers and the ids go up; the vectors never leave HBM
         if ((rc = W->w_selfrow.ensure(nq))) return rc;
         HIP_TRY(hipMemcpyAsync(W->w_selfrow.p, self_rows.data(), nq * 4, hipMemcpyHostToDevice, s));
         if ((rc = strike_stage(strike, r, s))) return rc;
-        vdb::launch_gather_rows(ix->d_rows, ix->ld, ix->dim, ix->n_uploaded, W->w_selfrow.p, (uint32_t)nq, W->w_qin.p, s);
+        vdb::launch_gather_rows(rows_f32(ix), ix->ld, ix->dim, ix->n_uploaded, W->w_selfrow.p, (uint32_t)nq, W->w_qin.p, s);
         HIP_TRY(hipGetLastError());
     } else if (dim) HIP_TRY(hipMemcpyAsync(W->w_qin.p, r.queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
     const uint64_t* d_mask;
@@ -1275,7 +1275,7 @@ int vdb_flat_distances_batch(vdb_flat_index* ix, const float* queries, size_t nq
     vdb::QueryPrepParams qp{ix->cur->w_qin.p, (uint32_t)dim, nq32, ix->cur->w_qp.p, ld, bp, ix->cur->w_qnorm.p, ix->cur->w_thr.p, vdb::EUCLID,
                             ix->cur->w_flags.p, nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr};   // metric EUCLID here: zero norms are judged per PAIR below
     vdb::launch_query_prep(qp, s);
-    vdb::PairDistParams pp{ix->d_rows, ld, (uint32_t)dim, ix->cur->w_qp.p, ix->cur->w_qnorm.p, ix->d_nd, ix->cur->w_rowmask.p + total,
+    vdb::PairDistParams pp{rows_f32(ix), ld, (uint32_t)dim, ix->cur->w_qp.p, ix->cur->w_qnorm.p, ix->d_nd, ix->cur->w_rowmask.p + total,
                            ix->cur->w_rowmask.p, (uint32_t)total, ix->metric, ix->cur->w_outd.p, ix->cur->w_flags.p};
     vdb::launch_pair_distances(pp, s);
     HIP_TRY(hipGetLastError());
@@ -1384,7 +1384,7 @@ int vdb_flat_debug_screen_scores(vdb_flat_index* ix, const float* queries, size_
         vdb::QueryPrepParams qp2{ix->cur->w_qin.p, (uint32_t)dim, (uint32_t)nq, ix->cur->w_qp.p, ld, SUPER, ix->cur->w_qnorm.p, ix->cur->w_thr.p, vdb::EUCLID,
                                  ix->cur->w_flags.p, nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr};
         vdb::launch_query_prep(qp2, s);
-        vdb::DenseParams dp{ix->d_rows, ld, n, ix->cur->w_qp.p, round_up((uint32_t)nq, 32), ix->d_alpha, ix->d_beta, ix->d_live, n, ix->cur->w_dense.p, n};
+        vdb::DenseParams dp{rows_f32(ix), ld, n, ix->cur->w_qp.p, round_up((uint32_t)nq, 32), ix->d_alpha, ix->d_beta, ix->d_live, n, ix->cur->w_dense.p, n};
         vdb::launch_dense_scores(dp, s);
         HIP_TRY(hipGetLastError());
         std::vector<uint64_t> keys((size_t)nq * n);
@@ -1418,7 +1418,7 @@ int vdb_flat_debug_screen_scores(vdb_flat_index* ix, const float* queries, size_
     HIP_TRY(hipMemcpyAsync(ix->cur->w_thr.p, thr.data(), nq * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(ix->cur->w_dbg.p, 0xff, nq * (size_t)n * 4, s));            // NaN pattern = no key for this (query, row)
     vdb::FusedBf16Params fp{};
-    fp.rows = ix->d_rows; fp.ld = ld; fp.n_rows = n; fp.qb = ix->cur->w_qb.p; fp.alpha = ix->d_alpha; fp.beta = ix->d_beta;
+    fp.rows = rows_f32(ix); fp.ld = ld; fp.n_rows = n; fp.qb = ix->cur->w_qb.p; fp.alpha = ix->d_alpha; fp.beta = ix->d_beta;
     fp.margin = lb ? ix->d_margin : nullptr; fp.qg = lb ? ix->cur->w_qg.p : nullptr;
     fp.rowmask = ix->d_live; fp.thr = ix->cur->w_thr.p; fp.pool = ix->cur->w_pool.p; fp.pool_cnt = ix->cur->w_subcnt.p; fp.capl = capl; fp.n_wg = n_wg;
     fp.scalars = ix->d_scalars; fp.qmax_bits = ix->cur->w_flags.p + 2;
@@ -1551,7 +1551,7 @@ int vdb_flat_set_shadow(vdb_flat_index* ix, int on) {
         DevBuf<uint16_t> r16;
         HIP_TRY(r16.alloc((size_t)ix->cap_rows * ix->ld));
         hipError_t e = hipMemsetAsync(r16, 0, (size_t)ix->cap_rows * ix->ld * 2, ix->stream);
-        if (e == hipSuccess) { vdb::launch_rows_to_bf16(ix->d_rows, r16, ix->ld, 0, ix->n_uploaded, ix->stream); e = hipGetLastError(); }
+        if (e == hipSuccess) { vdb::launch_rows_to_bf16(rows_f32(ix), r16, ix->ld, 0, ix->n_uploaded, ix->stream); e = hipGetLastError(); }
         if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);
         if (e != hipSuccess) return fail(VDB_ERR_DEVICE, "building the bf16 shadow failed: %s", hipGetErrorString(e));
         ix->d_rows16 = std::move(r16);                                   // only a COMPLETE shadow is ever visible to a search
@@ -1587,6 +1587,49 @@ int vdb_flat_set_wide(vdb_flat_index* ix, int on) {
     if (ix->multi) return multi_for_each(ix, [on](vdb_flat_index* c) { return vdb_flat_set_wide(c, on); });
     std::lock_guard<std::mutex> g(ix->mu);
     ix->wide = on != 0;
+    return VDB_OK;
+    });
+}
+
+int vdb_flat_set_split(vdb_flat_index* ix, int mode) {
+    return guarded([&]() -> int {
+    if (!ix || mode < 0 || mode > 2) return fail(VDB_ERR_INVALID_ARGUMENT, "mode must be 0, 1 or 2");
+    if (ix->multi) return multi_for_each(ix, [mode](vdb_flat_index* c) { return vdb_flat_set_split(c, mode); });
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->split_mode = mode;
+    ix->split_streak = 0;
+    return VDB_OK;
+    });
+}
+
+int vdb_flat_layout(vdb_flat_index* ix, uint64_t out[2]) {
+    return guarded([&]() -> int {
+    if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (ix->multi) {
+        uint64_t all = 1, conv = 0;
+        int rc = multi_for_each(ix, [&](vdb_flat_index* c) {
+            uint64_t o[2] = {0, 0};
+            int r = vdb_flat_layout(c, o);
+            all &= o[0]; conv += o[1];
+            return r;
+        });
+        out[0] = all; out[1] = conv;
+        return rc;
+    }
+    std::lock_guard<std::mutex> g(ix->mu);
+    out[0] = ix->layout == vdb::LAYOUT_SPLIT ? 1u : 0u;
+    out[1] = ix->split_conversions;
+    return VDB_OK;
+    });
+}
+
+int vdb_flat_debug_set_split_after(vdb_flat_index* ix, size_t searches) {
+    return guarded([&]() -> int {
+    if (!ix || searches > 0xffffffffull) return fail(VDB_ERR_INVALID_ARGUMENT, "bad argument");
+    if (ix->multi) return multi_for_each(ix, [searches](vdb_flat_index* c) { return vdb_flat_debug_set_split_after(c, searches); });
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->split_after = searches ? (uint32_t)searches : SPLIT_AFTER;
+    ix->split_streak = 0;
     return VDB_OK;
     });
 }
@@ -1752,7 +1795,7 @@ static int run_pair_eval(vdb_flat_index* ix, int mode, const uint32_t* a, const 
         memcpy(ix->h_pairs + n, b, n * sizeof(uint32_t));
     }
     vdb::PairEvalParams pp{};
-    pp.rows = ix->d_rows; pp.ld = ix->ld; pp.dim = ix->dim; pp.nd = ix->d_nd; pp.qp = ix->cur->w_qp.p; pp.qnorm = ix->cur->w_qnorm.p;
+    pp.rows = rows_f32(ix); pp.ld = ix->ld; pp.dim = ix->dim; pp.nd = ix->d_nd; pp.qp = ix->cur->w_qp.p; pp.qnorm = ix->cur->w_qnorm.p;
     pp.a = d_pairs; pp.b = d_pairs + n; pp.n = (uint32_t)n; pp.q0 = q0; pp.mode = mode; pp.metric = ix->metric;
     pp.mark = ZERO_NORM_MARK; pp.out = d_out;
     // A SMALL request (an HNSW insert's misses: a dozen pairs) is waited for by watching the mapped result buffer instead of
@@ -1801,7 +1844,7 @@ int device_view(vdb_flat_index* ix, DeviceView* out) {
     int rc;
     if ((rc = set_device(ix))) return rc;
     if ((rc = ix->cur->w_flags.ensure(4))) return rc;
-    out->rows = ix->d_rows; out->ld = ix->ld; out->dim = ix->dim; out->nd = ix->d_nd; out->qp = ix->cur->w_qp.p; out->qnorm = ix->cur->w_qnorm.p;
+    out->rows = rows_f32(ix); out->ld = ix->ld; out->dim = ix->dim; out->nd = ix->d_nd; out->qp = ix->cur->w_qp.p; out->qnorm = ix->cur->w_qnorm.p;
     out->metric = ix->metric; out->stream = (void*)ix->stream; out->status = ix->cur->w_flags.p;
     return VDB_OK;
 }

@@ -48,6 +48,10 @@ constexpr uint32_t SMALL_N = 16384;     // at or below: dense scores of every ro
 constexpr uint32_t SUPER = 256;         // queries per pipeline pass
 constexpr uint32_t MAX_SELECT = 2048;   // select kernel capacity (kk)
 constexpr uint32_t DIRECT_MAX_Q = 8;    // the direct exact path of small indexes takes batches up to this many queries
+// vdb_flat_set_split mode 1: eligible screened searches in a row before the next one converts the rows to the SPLIT layout.  From
+// the measured conversion times against the step time they buy back: the worst alternating workload -- SPLIT_AFTER
+// searches, one f32 reader -- loses at most 10 %.
+constexpr uint32_t SPLIT_AFTER = 64;
 constexpr uint32_t SPARSE_MAX_E = 131072;   // sparse-filter route: eligible rows at most (one pass's key buffer: 256 x 131072 x 8 B = 256 MiB)
 
 }  // namespace vdbi
@@ -198,7 +202,18 @@ struct vdb_flat_index {
     bool sample_cache = true;
     vdbi::DevBuf<uint16_t> d_rows16;      // opt-in bf16 shadow of d_rows [cap_rows][ld] (vdb_flat_set_shadow), else null
     bool shadow = false;
-    vdbi::DevBuf<float> d_rows, d_nd, d_alpha, d_beta;
+    // The rows [cap_rows][ld], in the layout `layout` names (row_split.h): plain f32 rows, or every row split in place into its
+    // bf16 piece and its low halves, which the screening tier's filter pass (launch_filter_pass) and its re-ranks read at 2 bytes
+    // per element.  Only those read d_rows_store as it lies (screen_params, rerank_params); EVERY other reader and every writer
+    // asks rows_f32(ix) / rows_mut(ix), which convert back first.
+    vdbi::DevBuf<float> d_rows_store, d_nd, d_alpha, d_beta;
+    int layout = 0;                                         // vdb::LAYOUT_F32 / LAYOUT_SPLIT
+    int split_mode = 1;                                     // vdb_flat_set_split: 0 never, 1 adaptive (default), 2 before the next eligible search
+    uint32_t split_after = vdbi::SPLIT_AFTER;               // adaptive: eligible searches in a row before the next one converts
+    uint32_t split_streak = 0;                              // ... counted so far; any rows_f32 / rows_mut call resets it
+    bool split_refused = false;                             // the rows hold a non-finite element: F32 until they change (rows_mut)
+    uint64_t split_conversions = 0;                         // conversions so far, both directions
+    vdbi::DevBuf<uint32_t> d_split_flag;                    // the forward conversion's non-finite report
     vdbi::DevBuf<float> d_margin;         // [cap] per-row error margin of the screening tier's lower-bound scores (Dot / Euclid; null under Cosine)
     vdbi::DevBuf<uint64_t> d_row_ids; vdbi::DevBuf<uint32_t> d_live, d_scalars;  // [0]=nd2max bits [1]=zero count [2],[3]=max bf16 rounding error of a row (abs^2, rel^2)
     uint32_t cap_rows = 0;
@@ -253,6 +268,15 @@ inline int set_device(const Index* ix) {
 }
 
 // ---- vdb_store.cpp: the device row store
+// The rows as plain f32 (null before the first row): converts a SPLIT store back first -- every stream of the device waited for,
+// so no kernel enqueued earlier still reads the other layout -- and resets the adaptive counter.  The caller holds the handle
+// mutex.  rows_mut: for a caller that changes rows; also forgets that the old rows held a non-finite element.  A conversion
+// that fails leaves the store unusable (store_broken: every later call is refused).
+float* rows_f32(Index* ix);
+float* rows_mut(Index* ix);
+// F32 -> SPLIT now (the caller has checked that nobody reads the rows: handle mutex held, other workspace idle).  A store with a
+// non-finite element is converted straight back and remembered (split_refused).
+int rows_to_split(Index* ix);
 int grow(Index* ix, uint32_t need_rows);
 void free_store(Index* ix);
 void reset_rows(Index* ix);

@@ -703,7 +703,7 @@ int multi_search_by_id(vdb_flat_index* P, const HostSearch& r) {
         if (!r) {
             hipError_t e = hipMemcpyAsync(p.d_grow.p, rows_g[g].data(), n_g * 4, hipMemcpyHostToDevice, p.stream);
             if (e == hipSuccess) {
-                vdb::launch_gather_rows(c->d_rows, c->ld, c->dim, c->n_uploaded, p.d_grow.p, (uint32_t)n_g, at_home ? stage : p.d_gq.p, p.stream);
+                vdb::launch_gather_rows(rows_f32(c), c->ld, c->dim, c->n_uploaded, p.d_grow.p, (uint32_t)n_g, at_home ? stage : p.d_gq.p, p.stream);
                 e = hipGetLastError();
             }
             if (e == hipSuccess && !at_home) e = hipMemcpyPeerAsync(stage, M->home, p.d_gq.p, M->dev[g], n_g * dim * 4, p.stream);

@@ -11,10 +11,17 @@
 namespace vdbi {
 
 // The filter pass of the screening tier: over the bf16 shadow rows when the index keeps them (vdb_flat_set_shadow) and the
-// row pitch allows whole 128-byte row requests, else over the f32 rows.  Same scores either way, bit for bit.
+// row pitch allows whole 128-byte row requests, else over the f32 rows.  Same scores either way, bit for bit.  A store in the
+// SPLIT layout (row_split.h) is its own shadow: the same kernel streams the hi piece of every row at the store's pitch (scores
+// differ from the other two only where an element lies exactly between two bf16 values, fused_bf16_common.h; results never).
 bool shadow_usable(const Index* ix) { return ix->d_rows16 && ix->ld % 64 == 0; }
 void launch_filter_pass(Index* ix, vdb::FusedBf16Params& fp, hipStream_t s) {
     if (shadow_usable(ix)) { fp.rows16 = ix->d_rows16; vdb::launch_fused_s16(fp, s); return; }
+    if (ix->layout == vdb::LAYOUT_SPLIT) {
+        fp.rows16 = reinterpret_cast<const uint16_t*>(ix->d_rows_store.p); fp.rows16_pitch = 2 * ix->ld;
+        vdb::launch_fused_s16(fp, s);
+        return;
+    }
 #ifdef VDB_DIAG
     if (!ix->kn.fused_pipe) { vdb::launch_fused_bf16(fp, s); return; }
 #endif
@@ -31,7 +38,7 @@ static uint32_t screen_grid(const Index* ix, uint32_t tile_rows) {
 static vdb::FusedBf16Params screen_params(const Index* ix, const Workspace* W, const uint32_t* d_rowmask, const uint32_t* d_status,
                                           uint32_t capl, uint32_t n_wg) {
     vdb::FusedBf16Params fp{};
-    fp.rows = ix->d_rows; fp.ld = ix->ld; fp.n_rows = ix->n_uploaded;
+    fp.rows = ix->d_rows_store; fp.ld = ix->ld; fp.n_rows = ix->n_uploaded;      // (in the layout of the moment: launch_filter_pass)
     fp.alpha = ix->d_alpha; fp.beta = ix->d_beta; fp.rowmask = d_rowmask ? d_rowmask : ix->d_live;
     fp.margin = ix->d_margin;
     fp.pool = W->w_pool.p; fp.pool_cnt = W->w_subcnt.p; fp.capl = capl; fp.n_wg = n_wg;
@@ -47,7 +54,8 @@ static void screen_queries(vdb::FusedBf16Params& fp, const Index* ix, const uint
 static vdb::RerankParams rerank_params(const Index* ix, const uint32_t* d_rowmask, uint32_t* d_status, size_t k, const uint64_t* cand,
                                        uint32_t kp, const uint32_t* cand_cnt) {
     vdb::RerankParams rp{};
-    rp.rows = ix->d_rows; rp.ld = ix->ld; rp.dim = ix->dim; rp.n_rows = ix->n_uploaded;
+    rp.rows = ix->d_rows_store; rp.split = ix->layout == vdb::LAYOUT_SPLIT ? 1u : 0u;
+    rp.ld = ix->ld; rp.dim = ix->dim; rp.n_rows = ix->n_uploaded;
     rp.nd = ix->d_nd; rp.row_ids = ix->d_row_ids; rp.rowmask = d_rowmask;
     rp.cand = cand; rp.cand_stride = kp; rp.cand_cnt = cand_cnt; rp.kp = kp;
     rp.metric = ix->metric; rp.k = (uint32_t)k; rp.nd2max_bits = ix->d_scalars;
@@ -112,7 +120,7 @@ int exact_one(Index* ix, hipStream_t s, uint32_t q, size_t k, const uint32_t* d_
     if ((rc = ix->cur->w_exact.ensure(n))) return rc;
     if ((rc = ix->cur->w_exsel.ensure(MAX_SELECT + 8))) return rc;
     if ((rc = ix->cur->w_cnt.ensure(4 * SUPER + 16))) return rc;
-    vdb::ExactScanParams ep{ix->d_rows, ix->ld, ix->dim, n, ix->cur->w_qp.p + (size_t)q * ix->ld, ix->cur->w_qnorm.p + q, ix->d_nd,
+    vdb::ExactScanParams ep{rows_f32(ix), ix->ld, ix->dim, n, ix->cur->w_qp.p + (size_t)q * ix->ld, ix->cur->w_qnorm.p + q, ix->d_nd,
                             d_rowmask, ix->ids_monotone ? nullptr : ix->d_idrank.p, ix->metric, ix->cur->w_exact.p,
                             ix->cur->w_flags.p};
     vdb::launch_exact_scan(ep, s);
@@ -157,7 +165,7 @@ static int bounded_scan_queries(Index* ix, hipStream_t s, const std::vector<uint
         const uint32_t nqf = (uint32_t)std::min<size_t>(8, todo.size() - g0);
         HIP_TRY(hipMemsetAsync(d_cnt8, 0, 16 * 4, s));
         vdb::BoundedScanParams ep{};
-        ep.rows = ix->d_rows; ep.ld = ix->ld; ep.dim = ix->dim; ep.n_rows = n; ep.qp = W->w_qp.p; ep.qnorm = W->w_qnorm.p;
+        ep.rows = rows_f32(ix); ep.ld = ix->ld; ep.dim = ix->dim; ep.n_rows = n; ep.qp = W->w_qp.p; ep.qnorm = W->w_qnorm.p;
         ep.nd = ix->d_nd; ep.rowmask = d_rowmask; ep.idrank = ix->ids_monotone ? nullptr : ix->d_idrank.p;
         ep.metric = ix->metric; ep.nqf = nqf;
         for (uint32_t j = 0; j < nqf; ++j) ep.qidx[j] = todo[g0 + j];
@@ -196,6 +204,7 @@ int pass_f32(Index* ix, hipStream_t s, const float* qp, const float* qnorm, floa
     int rc;
     const uint32_t n = ix->n_uploaded, ld = ix->ld;
     const bool small = n <= SMALL_N;
+    (void)rows_f32(ix);                                              // this tier reads f32 rows, its re-rank included
     // Threshold sample size S: the fused pass keeps about n*kp/S keys per query, spread over 512 private
     // sub-pools of 64 slots and gathered into 16384 LDS slots by the select.  S is chosen so that this
     // expectation stays near 8000 or below (mean sub-pool fill <= 16), and the sample costs <= ~3 % of the
@@ -231,7 +240,7 @@ int pass_f32(Index* ix, hipStream_t s, const float* qp, const float* qnorm, floa
         const uint32_t n_super = (tiles + nqt - 1) / nqt;          // workgroups along the query axis (1 or 2)
         const float* qp0 = qp + (size_t)q0 * ld;
 
-        vdb::DenseParams dp{ix->d_rows, ld, n, qp0, round_up(nb, 32), ix->d_alpha, ix->d_beta, d_rowmask, S,
+        vdb::DenseParams dp{rows_f32(ix), ld, n, qp0, round_up(nb, 32), ix->d_alpha, ix->d_beta, d_rowmask, S,
                             ix->cur->w_dense.p, S};
         vdb::launch_dense_scores(dp, s);
 
@@ -247,7 +256,7 @@ int pass_f32(Index* ix, hipStream_t s, const float* qp, const float* qnorm, floa
             vdb::launch_select(sp, nb, s);
             const uint32_t n_wg = std::min<uint32_t>((nqt == 8 ? 1u : 2u) * (uint32_t)ix->n_cu / n_super, (n + 31) / 32);
             const uint32_t n_sub = vdb::fused_subpools_per_query(nqt, n_wg);
-            vdb::FusedParams fp{ix->d_rows, ld, n, qp, q0, ix->d_alpha, ix->d_beta, d_rowmask ? d_rowmask : ix->d_live,
+            vdb::FusedParams fp{rows_f32(ix), ld, n, qp, q0, ix->d_alpha, ix->d_beta, d_rowmask ? d_rowmask : ix->d_live,
                                 thr, ix->cur->w_pool.p - (size_t)q0 * n_sub * capl,
                                 ix->cur->w_subcnt.p - (size_t)q0 * n_sub, capl, n_wg,
                                 ix->kn.fused_ablate};
@@ -310,10 +319,19 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
     // counts and keys, never empty slots, so the capacity costs address space only (0.5 GB of workspace at 1M rows).
     const uint32_t capl = 256;
     const uint32_t n_wg = screen_grid(ix, vdb::fused_bf16_tile_rows());
+    // ---- the layout of the rows.  A search can run over SPLIT rows if the filter pass may use the shadow-row
+    // kernel at the store's pitch (ld % 64, no shadow of its own, the production kernel) and the sample pass has its compact
+    // copy: that copy is made from f32 rows, so a stale one sends the rows back to F32 first.  A batch above 256 queries on a
+    // SPLIT index runs as 256-query passes of that kernel (the wide kernel reads f32 rows), as over the shadow.
+    Workspace* const other_ws = (ix->cur == &ix->wsv[0]) ? &ix->wsv[1] : &ix->wsv[0];
+    const bool split_able = ix->split_mode != 0 && !shadow_usable(ix) && ld % 64 == 0 && ix->sample_cache && !ix->kn.sample_block &&
+                            ix->kn.fused_pipe && !ix->kn.bf16_ablate;
+    if (ix->layout == vdb::LAYOUT_SPLIT && (!split_able || ix->sample16_n != n || ix->sample16_S != S)) (void)rows_f32(ix);
+    const bool go_split = ix->layout == vdb::LAYOUT_SPLIT;
     // Batches above 256 queries: the WIDE filter kernel (kernels_fused_bf16w.hip, 128 rows x 512 queries per workgroup) serves
     // two 256-query blocks per fetch of the rows -- BASELINE config 3 (B = 1024) reads its shard twice per batch instead of
     // four times.  Not over the opt-in bf16 shadow rows (their kernel has the one shape); vdb_flat_set_wide(h, 0) turns it off.
-    const bool use_wide = ix->wide && nq > SUPER && !shadow_usable(ix)
+    const bool use_wide = ix->wide && nq > SUPER && !shadow_usable(ix) && !go_split
 #ifdef VDB_DIAG
                           && ix->kn.fused_pipe
 #endif
@@ -355,12 +373,21 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
                 if (ix->d_sample16.alloc(need) != hipSuccess) { (void)hipGetLastError(); sample_copy = false; }   // no memory for the optional copy: f32 gather
             }
             if (sample_copy) {
-                vdb::launch_sample_to_bf16(ix->d_rows, ld, n, S, pl.shift, ix->d_sample16, s);
+                vdb::launch_sample_to_bf16(rows_f32(ix), ld, n, S, pl.shift, ix->d_sample16, s);
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(hipStreamSynchronize(s));                    // once per change of the rows: later searches on OTHER streams read it
                 ix->sample16_n = n; ix->sample16_S = S;
             }
         }
+    }
+    // the adaptive rule: consecutive searches that could run over SPLIT rows are counted (rows_f32 and every mutation reset the
+    // count); after split_after of them the next one converts first -- under the handle mutex, and only while no other search of
+    // this handle is in flight (its kernels read the rows), else not this time.  Mode 2 converts before the next such search.
+    if (split_able && sample_copy && nq <= SUPER) {
+        if (!go_split && !ix->split_refused && !other_ws->busy && (ix->split_mode == 2 || ix->split_streak >= ix->split_after)) {
+            if ((rc = rows_to_split(ix))) return rc;
+        }
+        ++ix->split_streak;
     }
     if (alt) {                                                   // the other stream starts behind query_prep and the row mask
         if ((rc = ix->ev_pass[0].create(hipEventDisableTiming)) || (rc = ix->ev_pass[1].create(hipEventDisableTiming))) return rc;
@@ -589,7 +616,7 @@ static int search_direct(Index* ix, hipStream_t s, const float* d_q, uint32_t nq
         HIP_TRY(hipMemsetAsync(W->w_dstat.p, 0, 16, s));
         W->dstat_ready = true;
     }
-    vdb::SmallScanParams sp{ix->d_rows, ix->ld, ix->dim, n, d_q, nq, ix->d_nd, d_rowmask, ix->ids_monotone ? nullptr : ix->d_idrank.p,
+    vdb::SmallScanParams sp{rows_f32(ix), ix->ld, ix->dim, n, d_q, nq, ix->d_nd, d_rowmask, ix->ids_monotone ? nullptr : ix->d_idrank.p,
                             ix->metric, W->w_exact.p, n_keys, keep, W->w_dstat.p};
     vdb::launch_small_scan(sp, s);
     vdb::SelectParams mp{};
@@ -682,7 +709,7 @@ static int search_sparse(Index* ix, hipStream_t s, const float* d_q, uint32_t nq
         if ((rc = W->w_cnt.ensure(4 * SUPER + 16))) return rc;
         for (uint32_t q0 = 0; q0 < nq; q0 += SUPER) {              // passes of SUPER queries: the key buffer stays bounded
             const uint32_t nb = std::min(SUPER, nq - q0);
-            vdb::SparseScanParams sp{ix->d_rows, ld, ix->dim, n, W->w_elig.p, E, W->w_qp.p + (size_t)q0 * ld, W->w_qnorm.p + q0, nb,
+            vdb::SparseScanParams sp{rows_f32(ix), ld, ix->dim, n, W->w_elig.p, E, W->w_qp.p + (size_t)q0 * ld, W->w_qnorm.p + q0, nb,
                                      ix->d_nd, ix->ids_monotone ? nullptr : ix->d_idrank.p, ix->metric, W->w_exact.p, stride, d_status};
             vdb::launch_sparse_scan(sp, s);
             vdb::SelectParams mp{};
@@ -1030,6 +1057,7 @@ static int range_search_run(Index* ix, const float* d_q, size_t nq, size_t dim, 
 
     const uint32_t n = ix->n_uploaded, ld = ix->ld, nq32 = (uint32_t)nq, bp_all = round_up(nq32, SUPER);
     const uint32_t mr = (uint32_t)max_results;
+    (void)rows_f32(ix);                                            // both routes read f32 rows (range_rerank_kernel, the range scan)
     const bool screened = ix->screen && n >= BF16_MIN_ROWS;
     constexpr uint32_t KMAX = MAX_SELECT;                          // keys evaluated per query at most (select capacity)
 
@@ -1096,7 +1124,7 @@ static int range_search_run(Index* ix, const float* d_q, size_t nq, size_t dim, 
             mp.ovf = d_ovf + q0; mp.summary = nullptr; mp.flag_truncation = 1;
             vdb::launch_select(mp, nb, s);
             vdb::RangeRerankParams rp{};
-            rp.rows = ix->d_rows; rp.ld = ld; rp.dim = ix->dim; rp.n_rows = n;
+            rp.rows = rows_f32(ix); rp.ld = ld; rp.dim = ix->dim; rp.n_rows = n;
             rp.qp = W->w_qp.p + (size_t)q0 * ld; rp.qnorm = W->w_qnorm.p + q0; rp.nd = ix->d_nd;
             rp.row_ids = ix->d_row_ids; rp.rowmask = d_rowmask;
             rp.cand = W->w2_cand.p; rp.cand_stride = KMAX; rp.cand_cnt = d_cand_cnt;
@@ -1453,7 +1481,7 @@ int search_grouped(Index* ix, hipStream_t s, const GroupedArgs& a) {
         vdb::launch_gather_queries(W->w_qp.p, W->w_qnorm.p, ld, d_perm, ns, ns, W->w2_qp.p, W->w2_qnorm.p, W->w2_thr.p, s);
         for (const GroupPass& P : plan.passes) {
             vdb::GroupedScanParams gp{};
-            gp.scan = vdb::SparseScanParams{ix->d_rows, ld, ix->dim, n, G.lists.p, (uint32_t)lists_len, W->w2_qp.p + (size_t)P.q0 * ld,
+            gp.scan = vdb::SparseScanParams{rows_f32(ix), ld, ix->dim, n, G.lists.p, (uint32_t)lists_len, W->w2_qp.p + (size_t)P.q0 * ld,
                                             W->w2_qnorm.p + P.q0, P.nq, ix->d_nd, ix->ids_monotone ? nullptr : ix->d_idrank.p, ix->metric,
                                             W->w_exact.p, P.stride, d_status};
             gp.tiles = d_tiles + 4 * (size_t)P.tile0; gp.n_tiles = P.n_tiles; gp.glist = d_glist; gp.n_groups = (uint32_t)R; gp.q_base = P.q0;

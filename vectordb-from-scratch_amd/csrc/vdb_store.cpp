@@ -14,6 +14,59 @@
 
 namespace vdbi {
 
+// ------------------------------------------------------------------ the layout of the rows (row_split.h)
+// One conversion of rows [0, n_uploaded), in place, on the handle's stream, with the whole device waited for before it (whatever
+// was enqueued against the old layout, on any stream, has run) and the stream after it (whoever is enqueued next, on any stream,
+// sees the new one).  The zero rows behind n_uploaded are the same in both layouts.
+static int convert_rows(Index* ix, bool forward) {
+    int prev = 0;
+    HIP_TRY(hipGetDevice(&prev));
+    if (prev != ix->device) HIP_TRY(hipSetDevice(ix->device));
+    auto run = [&]() -> int {
+        HIP_TRY(hipDeviceSynchronize());
+        hipStream_t s = ix->stream;
+        if (forward) {
+            int rc = ix->d_split_flag.ensure(1);
+            if (rc) return rc;
+            HIP_TRY(hipMemsetAsync(ix->d_split_flag.p, 0, 4, s));
+        }
+        vdb::launch_row_split(ix->d_rows_store, ix->ld, ix->n_uploaded, forward, ix->d_split_flag.p, (uint32_t)ix->n_cu, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));
+        return VDB_OK;
+    };
+    const int rc = run();
+    if (prev != ix->device) (void)hipSetDevice(prev);
+    if (rc) { ix->store_broken = true; return rc; }                      // rows may be half converted: nothing is served from this handle any more
+    ix->layout = forward ? vdb::LAYOUT_SPLIT : vdb::LAYOUT_F32;
+    ++ix->split_conversions;
+    return VDB_OK;
+}
+
+float* rows_f32(Index* ix) {
+    ix->split_streak = 0;
+    if (ix->layout == vdb::LAYOUT_SPLIT) (void)convert_rows(ix, false);
+    return ix->d_rows_store;
+}
+float* rows_mut(Index* ix) {
+    ix->split_refused = false;
+    return rows_f32(ix);
+}
+
+int rows_to_split(Index* ix) {
+    if (ix->layout == vdb::LAYOUT_SPLIT || ix->split_refused || !ix->d_rows_store || !ix->n_uploaded) return VDB_OK;
+    if (ix->ld % 64 != 0 || ix->ld > 16384) return VDB_OK;
+    int rc = convert_rows(ix, true);
+    if (rc) return rc;
+    uint32_t nonfinite = 0;
+    HIP_TRY(hipMemcpy(&nonfinite, ix->d_split_flag.p, 4, hipMemcpyDeviceToHost));
+    if (nonfinite) {                                                     // inf / NaN elements keep the f32-row kernel's behaviour
+        ix->split_refused = true;
+        return convert_rows(ix, false);
+    }
+    return VDB_OK;
+}
+
 // ------------------------------------------------------------------ device store management
 // Re-allocates the store with room for `cap` rows (>= n_uploaded) and carries the uploaded rows over; old and new exist at once.
 static int resize_store(Index* ix, uint32_t cap) {
@@ -32,14 +85,15 @@ static int resize_store(Index* ix, uint32_t cap) {
     HIP_TRY(lv.alloc((size_t)cap / 32));
     hipStream_t s = ix->stream;
     uint32_t old = ix->n_uploaded;
+    const float* old_rows = rows_f32(ix);                                // the new store is F32 like the one it replaces
     if (ix->shadow) {
         HIP_TRY(r16.alloc((size_t)cap * ix->ld));
         if (old && ix->d_rows16) HIP_TRY(hipMemcpyAsync(r16, ix->d_rows16, (size_t)old * ix->ld * 2, hipMemcpyDeviceToDevice, s));
-        else if (old) vdb::launch_rows_to_bf16(ix->d_rows, r16, ix->ld, 0, old, s);     // no shadow yet: from the f32 rows, never left unset
+        else if (old) vdb::launch_rows_to_bf16(old_rows, r16, ix->ld, 0, old, s);     // no shadow yet: from the f32 rows, never left unset
         HIP_TRY(hipMemsetAsync((char*)r16.p + (size_t)old * ix->ld * 2, 0, (size_t)(cap - old) * ix->ld * 2, s));
     }
     if (old) {
-        HIP_TRY(hipMemcpyAsync(rows, ix->d_rows, (size_t)old * row_bytes, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(rows, old_rows, (size_t)old * row_bytes, hipMemcpyDeviceToDevice, s));
         HIP_TRY(hipMemcpyAsync(nd, ix->d_nd, (size_t)old * 4, hipMemcpyDeviceToDevice, s));
         HIP_TRY(hipMemcpyAsync(al, ix->d_alpha, (size_t)old * 4, hipMemcpyDeviceToDevice, s));
         HIP_TRY(hipMemcpyAsync(be, ix->d_beta, (size_t)old * 4, hipMemcpyDeviceToDevice, s));
@@ -53,7 +107,7 @@ static int resize_store(Index* ix, uint32_t cap) {
     HIP_TRY(hipStreamSynchronize(s));
     ix->d_rows16 = std::move(r16);
     ix->d_margin = std::move(mg);
-    ix->d_rows = std::move(rows); ix->d_nd = std::move(nd); ix->d_alpha = std::move(al); ix->d_beta = std::move(be);
+    ix->d_rows_store = std::move(rows); ix->d_nd = std::move(nd); ix->d_alpha = std::move(al); ix->d_beta = std::move(be);
     ix->d_row_ids = std::move(ids); ix->d_live = std::move(lv);
     ix->cap_rows = cap;
     ix->live_dirty = true;
@@ -67,7 +121,8 @@ int grow(Index* ix, uint32_t need_rows) {
 }
 
 void free_store(Index* ix) {
-    ix->d_rows.release(); ix->d_nd.release(); ix->d_alpha.release(); ix->d_beta.release(); ix->d_margin.release();
+    ix->d_rows_store.release(); ix->layout = vdb::LAYOUT_F32; ix->split_streak = 0; ix->split_refused = false;
+    ix->d_nd.release(); ix->d_alpha.release(); ix->d_beta.release(); ix->d_margin.release();
     ix->d_row_ids.release(); ix->d_live.release();
     ix->d_rows16.release();
     ix->d_sample16.release(); ix->sample16_n = ix->sample16_S = 0;
@@ -96,6 +151,7 @@ void kill_row(Index* ix, uint32_t row) {
     --ix->n_live;
     ix->live_dirty = true;
     ix->zero_valid = false;
+    ix->split_streak = 0;                                                // a mutation: the adaptive layout rule starts counting again
 }
 
 // Appends one primary-dimension row to the host staging area.
@@ -173,15 +229,16 @@ static int flush_upload(Index* ix) {
         int rc = grow(ix, n);
         if (rc) return rc;
         uint32_t first = ix->n_uploaded, cnt = n - first;
-        HIP_TRY(hipMemcpyAsync(ix->d_rows + (size_t)first * ix->ld, ix->pending.data(),
+        float* d_rows = rows_mut(ix);                                    // appends go to f32 rows
+        HIP_TRY(hipMemcpyAsync(d_rows + (size_t)first * ix->ld, ix->pending.data(),
                                (size_t)cnt * ix->ld * sizeof(float), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(ix->d_row_ids + first, ix->row_ids.data() + first, (size_t)cnt * 8,
                                hipMemcpyHostToDevice, s));
         const MarginPlan mp = margin_plan(ix);
-        vdb::RowStatsParams rp{ix->d_rows, ix->ld, ix->dim, first, n, ix->metric, ix->d_nd, ix->d_alpha,
+        vdb::RowStatsParams rp{d_rows, ix->ld, ix->dim, first, n, ix->metric, ix->d_nd, ix->d_alpha,
                                ix->d_beta, ix->d_scalars, ix->d_margin, mp.m_e, mp.m_n, mp.m_b, mp.beta_shrink};
         vdb::launch_row_stats(rp, s);
-        if (ix->d_rows16) vdb::launch_rows_to_bf16(ix->d_rows, ix->d_rows16, ix->ld, first, n, s);
+        if (ix->d_rows16) vdb::launch_rows_to_bf16(d_rows, ix->d_rows16, ix->ld, first, n, s);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(s));   // pending is host memory about to be released
         ix->pending.clear();
@@ -240,7 +297,7 @@ void compact_plan(const uint32_t* live, uint32_t n_rows, uint32_t bounce_rows, s
 void store_stats(const Index* ix, uint64_t out[8]) {
     const uint64_t cap = ix->cap_rows;
     out[0] = ix->n_rows(); out[1] = ix->n_live; out[2] = cap;
-    out[3] = ix->d_rows ? cap * ((uint64_t)ix->ld * 4 + 3 * 4 + (ix->d_margin ? 4 : 0) + 8) + cap / 8 + (ix->d_rows16 ? cap * ix->ld * 2 : 0) : 0;
+    out[3] = ix->d_rows_store ? cap * ((uint64_t)ix->ld * 4 + 3 * 4 + (ix->d_margin ? 4 : 0) + 8) + cap / 8 + (ix->d_rows16 ? cap * ix->ld * 2 : 0) : 0;
     out[4] = ix->n_compactions; out[5] = ix->rows_reclaimed; out[6] = ix->last_compact_ns;
     // [7]: the last compaction's device part (bits 0-39, ns: plan uploaded .. last row moved and the stream synchronised) and its
     // chunk counts, saturating at 4095 (bits 40-51 through the bounce buffer, bits 52-63 moved directly)
@@ -255,7 +312,8 @@ int compact_store(Index* ix, bool shrink, size_t* out_reclaimed) {
     const auto t0 = std::chrono::steady_clock::now();
     hipStream_t s = ix->stream;
     const uint32_t n = ix->n_uploaded, n_live = ix->n_live, ld = ix->ld;
-    if (n > n_live) {                                   // (n_live > 0: removing the last row resets the store)
+    if (n > n_live) {
+        float* const d_rows = rows_mut(ix);                              // rows move as f32 rows                                   // (n_live > 0: removing the last row resets the store)
         std::vector<uint32_t> prefix;
         std::vector<CompactChunk> plan;
         const bool shadow = ix->d_rows16 != nullptr;
@@ -287,11 +345,11 @@ int compact_store(Index* ix, bool shrink, size_t* out_reclaimed) {
                 const uint32_t cnt = prefix[(c.b + 31) / 32] - prefix[c.a / 32];
                 // source: the store, rows [a, b)
                 mp.live = ix->d_live; mp.prefix = d_prefix; mp.row_begin = c.a; mp.row_end = c.b;
-                mp.src_rows = ix->d_rows; mp.src_rows16 = ix->d_rows16; mp.src_nd = ix->d_nd; mp.src_alpha = ix->d_alpha; mp.src_beta = ix->d_beta;
+                mp.src_rows = d_rows; mp.src_rows16 = ix->d_rows16; mp.src_nd = ix->d_nd; mp.src_alpha = ix->d_alpha; mp.src_beta = ix->d_beta;
                 mp.src_margin = ix->d_margin; mp.src_ids = ix->d_row_ids;
                 if (c.mode == 0) {
                     mp.dst_sub = 0;
-                    mp.dst_rows = ix->d_rows; mp.dst_rows16 = ix->d_rows16; mp.dst_nd = ix->d_nd; mp.dst_alpha = ix->d_alpha; mp.dst_beta = ix->d_beta;
+                    mp.dst_rows = d_rows; mp.dst_rows16 = ix->d_rows16; mp.dst_nd = ix->d_nd; mp.dst_alpha = ix->d_alpha; mp.dst_beta = ix->d_beta;
                     mp.dst_margin = ix->d_margin; mp.dst_ids = ix->d_row_ids;
                     moved = true;
                     vdb::launch_compact_move(mp, (uint32_t)ix->n_cu, s);
@@ -304,7 +362,7 @@ int compact_store(Index* ix, bool shrink, size_t* out_reclaimed) {
                     mp.live = nullptr; mp.prefix = nullptr; mp.row_begin = 0; mp.row_end = cnt; mp.dst_sub = 0;
                     mp.src_rows = b_rows; mp.src_rows16 = shadow ? b_rows16 : nullptr; mp.src_nd = b_nd; mp.src_alpha = b_alpha; mp.src_beta = b_beta;
                     mp.src_margin = ix->d_margin ? b_margin : nullptr; mp.src_ids = b_ids;
-                    mp.dst_rows = ix->d_rows + (size_t)c.dst * ld; mp.dst_rows16 = shadow ? ix->d_rows16 + (size_t)c.dst * ld : nullptr;
+                    mp.dst_rows = d_rows + (size_t)c.dst * ld; mp.dst_rows16 = shadow ? ix->d_rows16 + (size_t)c.dst * ld : nullptr;
                     mp.dst_nd = ix->d_nd + c.dst; mp.dst_alpha = ix->d_alpha + c.dst; mp.dst_beta = ix->d_beta + c.dst;
                     mp.dst_margin = ix->d_margin ? ix->d_margin + c.dst : nullptr; mp.dst_ids = ix->d_row_ids + c.dst;
                     moved = true;
@@ -314,7 +372,7 @@ int compact_store(Index* ix, bool shrink, size_t* out_reclaimed) {
             }
             // the freed tail reads as zero again (padding columns of later adds, rows staged past the last one by ragged tiles)
             moved = true;
-            if ((e = hipMemsetAsync(ix->d_rows + (size_t)n_live * ld, 0, (size_t)(n - n_live) * ld * 4, s)) != hipSuccess) return e;
+            if ((e = hipMemsetAsync(d_rows + (size_t)n_live * ld, 0, (size_t)(n - n_live) * ld * 4, s)) != hipSuccess) return e;
             if (ix->d_margin && (e = hipMemsetAsync(ix->d_margin + n_live, 0, (size_t)(n - n_live) * 4, s)) != hipSuccess) return e;
             if (shadow && (e = hipMemsetAsync(ix->d_rows16 + (size_t)n_live * ld, 0, (size_t)(n - n_live) * ld * 2, s)) != hipSuccess) return e;
             if ((e = hipMemsetAsync(ix->d_live, 0, (size_t)ix->cap_rows / 8, s)) != hipSuccess) return e;

@@ -825,6 +825,28 @@ class GpuFlatIndex(Index):
         if rc:
             _raise(rc)
 
+    def set_split(self, mode=1):
+        """The layout of the stored rows: 0 never split, 1 adaptive (default), 2 split before the next eligible screened search.
+        Split rows let the screening pass stream 2 bytes per element; every other reader converts them back first.  Results
+        are identical in every mode."""
+        rc = self._L.vdb_flat_set_split(self._h, int(mode))
+        if rc:
+            _raise(rc)
+
+    def layout(self):
+        """(layout, conversions): 0 = plain f32 rows, 1 = split rows; conversions so far in both directions."""
+        out = (ctypes.c_uint64 * 2)()
+        rc = self._L.vdb_flat_layout(self._h, out)
+        if rc:
+            _raise(rc)
+        return int(out[0]), int(out[1])
+
+    def debug_set_split_after(self, searches):
+        """Test hook: the run of eligible searches after which mode 1 converts (0 = the default)."""
+        rc = self._L.vdb_flat_debug_set_split_after(self._h, int(searches))
+        if rc:
+            _raise(rc)
+
     def set_wide(self, on=True):
         """Batches above 256 queries: 512 queries per fetch of the rows (default) or 256.  Results are identical."""
         rc = self._L.vdb_flat_set_wide(self._h, 1 if on else 0)
