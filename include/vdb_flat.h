@@ -664,6 +664,65 @@ int vdb_flat_distinct_stats(const vdb_flat_index *h, uint64_t out[8]);
 size_t vdb_flat_distinct_depth(size_t k, size_t len, int stage);
 
 /*
+ * THE K NEAREST GROUPS WITH UP TO G ROWS OF EACH: the three best chunks of each of the ten nearest documents, the best offers per
+ * product -- what other vector stores call "search groups" (a group-by field, a limit, a group size).  No reference counterpart,
+ * and no deeper plain search answers it: the 2nd and 3rd best row of a group are ordinary rows anywhere in the ranking.  One
+ * sentence defines the call: for query q, count k, size g = group_size, column `slot` of `table` and an optional id mask, the
+ * GROUPS are the first k entries of what vdb_flat_search_batch_distinct returns under the same arguments (ids, order, codes,
+ * count), and the MEMBERS of a group with code c >= 0 are the first min(g, E) rows of the full ranking of the eligible rows --
+ * vdb_flat_search_batch with k = len under that mask, ascending by (distance, unsigned id) -- restricted to the rows whose code
+ * is c, E being the number of eligible rows with that code.
+ *  - A row with code -1 is its own group with one member, itself; a row without the field, or with an id at or beyond the column's
+ *    length, reads as -1, exactly as vdb_flat_search_batch_distinct reads it.
+ *  - Outputs: group j of query b has its members at out_ids / out_dists [(b * kstride + j) * group_size ..], their number in
+ *    out_sizes[b * kstride + j], its code in out_codes[b * kstride + j] (out_codes may be NULL); out_counts[b] is the number of
+ *    groups.  Member 0 of every group is the group's representative: the id and the distance bits vdb_flat_search_batch_distinct
+ *    returns.  On success only the first out_sizes slots of the first out_counts groups are meaningful, the others unspecified.
+ *  - All distance bits are the search's own (the reference's f32 operation order); +-inf distances are ordinary members; no id
+ *    value is a flag.  group_size = 1 gives vdb_flat_search_batch_distinct's answer bit for bit, with every size 1.
+ *  - ks: the answer for k_b is the first k_b groups of the answer for max(ks).
+ * How it runs (csrc/kernels_per_group.hip): the search by group runs and leaves its answers on the device; the
+ * codes come down in one copy and the host sorts them into the table of wanted codes (vdb_flat_debug_per_group_plan); one pass
+ * over the rows -- id, live bit, mask bit and code, 12 bytes per row -- counts every wanted code's eligible rows, a host prefix sum
+ * and a second pass write the member lists; one workgroup per (query, group) pair then walks its list in chunks staged through
+ * LDS, evaluates every row with the reference's arithmetic and keeps the best g by (distance, id).  A code with more than 131072
+ * eligible rows (a capacity limit, that of the sparse and grouped routes) is answered by one ordinary search of its queries at
+ * depth g under the mask "caller's mask AND code == c"; results are identical either way.  Nothing survives the call: no list can
+ * go stale after an add, a remove, a compaction or a column write.  The first member of every filled group is compared with the
+ * representative on the device; a difference is VDB_ERR_DEVICE "internal error".
+ * Errors, in this order: an empty index or k = 0 gives counts 0 before any other check; VDB_ERR_INVALID_ARGUMENT before any device
+ * work for group_size = 0 or above VDB_PER_GROUP_MAX_SIZE, a NULL out_sizes, out_ids or out_dists, everything
+ * vdb_flat_search_batch_distinct refuses, and a sharded handle (the member rows live on several devices; the message says so);
+ * then every error of the search by group; a NaN distance met while the members are ranked gives VDB_ERR_NAN.  On any error
+ * nothing is written to the outputs.  Locking, flushing, tickets, the table's lock and stream ordering are those of
+ * vdb_flat_search_batch_distinct, whose counters (vdb_flat_distinct_stats) describe the first step of this call as well.
+ * vdb_flat_per_group_stats describes the last call: [0] queries, [1] groups returned, [2] pairs filled by the member scan, [3] pairs
+ * answered by a giant's masked search, [4] distinct wanted codes, [5] member rows listed (the lengths of the lists, summed),
+ * [6] pair distances evaluated by the fill, [7] representative mismatches (always 0).
+ * vdb_flat_debug_per_group_plan needs no handle and no device: the host plan for the answers' codes [nq][kmax] and kept counts
+ * [nq] (clamped to kmax, and to ks[b] where ks is given).  wanted receives the distinct codes >= 0 of the counted entries,
+ * ascending (at most cap are written); index [nq][kmax] receives the place of every counted entry's code in that table,
+ * 0xffffffff for an entry with code -1 or beyond its count.  wanted and index may be NULL.  Returns the number of wanted codes,
+ * (size_t)-1 for a NULL input or kmax above 1024.
+ * vdb_flat_debug_set_per_group_scan_cap (tests): the longest list the fill takes on this handle, in rows (0 = the default 131072,
+ * which is also the maximum); lower, small indexes take the giants' route.
+ */
+#define VDB_PER_GROUP_MAX_SIZE 32
+int vdb_flat_search_batch_per_group(vdb_flat_index *h, const float *queries, size_t nq, size_t dim, const size_t *ks, size_t k,
+                                    size_t group_size, vdb_meta_table *table, uint32_t slot, const uint64_t *id_mask,
+                                    size_t mask_bits, size_t kstride, uint64_t *out_ids /* [nq][kstride][group_size] */,
+                                    float *out_dists /* same shape */, int32_t *out_codes /* [nq][kstride], may be NULL */,
+                                    uint32_t *out_sizes /* [nq][kstride] */, size_t *out_counts /* [nq] */);
+int vdb_flat_search_batch_per_group_filtered(vdb_flat_index *h, const float *queries, size_t nq, size_t dim, const size_t *ks,
+                                             size_t k, size_t group_size, vdb_meta_table *table, uint32_t slot,
+                                             const vdb_meta_mask *mask, size_t kstride, uint64_t *out_ids, float *out_dists,
+                                             int32_t *out_codes, uint32_t *out_sizes, size_t *out_counts);
+int vdb_flat_per_group_stats(const vdb_flat_index *h, uint64_t out[8]);
+size_t vdb_flat_debug_per_group_plan(const int32_t *codes, const uint32_t *kept, const size_t *ks, size_t nq, size_t kmax,
+                                     int32_t *wanted, size_t cap, uint32_t *index);
+int vdb_flat_debug_set_per_group_scan_cap(vdb_flat_index *h, size_t rows);
+
+/*
  * ONE BATCH, A FILTER PER QUERY (no reference counterpart: search_batch_with_filter, src/storage.rs:313-322, takes one filter for
  * the batch, while every request of POST /search carries its own, routes.rs:30-35).  One sentence defines the call: the answer for
  * query b is what vdb_flat_search_batch returns for that query ALONE with k_b under mask group_of[b] -- under no mask for

@@ -22,6 +22,8 @@ SYMBOLS = [
     "vdb_flat_search_batch_mmr", "vdb_flat_search_batch_mmr_filtered", "vdb_flat_mmr_stats",
     "vdb_flat_search_batch_distinct", "vdb_flat_search_batch_distinct_filtered", "vdb_flat_distinct_stats", "vdb_flat_distinct_depth",
     "vdb_flat_search_batch_grouped", "vdb_flat_search_batch_grouped_filtered", "vdb_flat_grouped_stats", "vdb_flat_debug_group_plan",
+    "vdb_flat_search_batch_per_group", "vdb_flat_search_batch_per_group_filtered", "vdb_flat_per_group_stats", "vdb_flat_debug_per_group_plan",
+    "vdb_flat_debug_set_per_group_scan_cap",
     "vdb_flat_set_sparse_filter", "vdb_flat_sparse_stats", "vdb_flat_sparse_limit", "vdb_flat_debug_eligible_rows", "vdb_flat_debug_sparse_tile_rows", "vdb_flat_debug_sparse_tile_queries",
     "vdb_meta_create", "vdb_meta_destroy", "vdb_meta_set_codes", "vdb_meta_set_present", "vdb_meta_set_numbers", "vdb_meta_compile", "vdb_meta_compile_num", "vdb_meta_mask_ptr", "vdb_meta_mask_bits",
     "vdb_meta_mask_count", "vdb_meta_mask_wait_on", "vdb_meta_mask_release", "vdb_flat_search_batch_filtered",
@@ -188,6 +190,12 @@ def lib():
     L.vdb_flat_grouped_stats.argtypes = [vp, u64p]
     L.vdb_flat_debug_group_plan.argtypes = [u32p, sz, u32p, sz, u32p, u32p, sz]
     L.vdb_flat_debug_group_plan.restype = sz
+    L.vdb_flat_search_batch_per_group.argtypes = [vp, fp, sz, sz, szp, sz, sz, vp, c.c_uint32, u64p, sz, sz, u64p, fp, i32p, u32p, szp]
+    L.vdb_flat_search_batch_per_group_filtered.argtypes = [vp, fp, sz, sz, szp, sz, sz, vp, c.c_uint32, vp, sz, u64p, fp, i32p, u32p, szp]
+    L.vdb_flat_per_group_stats.argtypes = [vp, u64p]
+    L.vdb_flat_debug_per_group_plan.argtypes = [i32p, u32p, szp, sz, sz, i32p, sz, u32p]
+    L.vdb_flat_debug_per_group_plan.restype = sz
+    L.vdb_flat_debug_set_per_group_scan_cap.argtypes = [vp, sz]
     L.vdb_last_error.argtypes = [c.c_char_p, sz, szp, szp]
     L.vdb_last_error.restype = None
     L.vdb_hnsw_create.argtypes = [c.c_int, sz, sz, sz, u64, c.c_int, c.POINTER(vp)]

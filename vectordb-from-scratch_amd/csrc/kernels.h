@@ -630,6 +630,60 @@ struct ExcludeGroupsParams {
 };
 void launch_exclude_groups(const ExcludeGroupsParams& p, uint32_t n_cu, hipStream_t s);
 
+// ---------------------------------------------------------------- up to g rows of each of the k nearest groups (kernels_per_group.hip)
+constexpr uint32_t PER_GROUP_MAX_SIZE = 32;                                // members of one group at most (VDB_PER_GROUP_MAX_SIZE)
+// One pass over the device rows [0, n_rows).  A row belongs to the list of wanted code wanted[u] (ascending, distinct, >= 0) when
+// it is live (live null: every row), its id is admitted by mask (null: every id; else id < mask_bits and the bit set), id <
+// codes_len and codes[id] == wanted[u].  COUNT: counts[u] += 1.  SCATTER: the row takes place cursor[u]++ of its list and, when
+// that is below lens[u], is written as the candidate key (1 << 32) | row to list[offs[u] + place] (below list_cap); lens[u] = 0
+// lists nothing.  counts and cursor are zeroed by the caller.
+struct PerGroupListParams {
+    const uint64_t* row_ids; const uint32_t* live; uint32_t n_rows;
+    const uint64_t* mask; uint64_t mask_bits;
+    const int32_t* codes; uint64_t codes_len;
+    const int32_t* wanted; uint32_t n_wanted;
+    uint32_t* counts;
+    const uint32_t* offs; const uint32_t* lens; uint32_t* cursor; uint64_t* list; uint64_t list_cap;
+};
+void launch_per_group_list(const PerGroupListParams& p, bool scatter, uint32_t n_cu, hipStream_t s);
+// Pair (b, j), slot = b * kmax + j, of the answers rep_ids / rep_dists [nq][kmax] with kept[b] groups: out_ids / out_dists
+// [slot * g ..] = the representative and padding (~0, NaN), out_sizes[slot] = 1 for j < kept[b]; padding and 0 otherwise.
+struct PerGroupInitParams {
+    const uint64_t* rep_ids; const float* rep_dists; const uint32_t* kept; uint32_t nq, kmax, g;
+    uint64_t* out_ids; float* out_dists; uint32_t* out_sizes;
+};
+void launch_per_group_init(const PerGroupInitParams& p, hipStream_t s);
+// Workgroup i fills pair slot pairs[2 i] (< nq * kmax) from the list of wanted code pairs[2 i + 1] (< n_wanted): the best
+// min(g, valid rows) of list[offs[u] .. + lens[u]) for query slot / kmax (q: [nq][dim], the rows' dimension) ascending by
+// (distance, id) to out_ids / out_dists [slot * g ..], the rest of the g slots padded, the number to out_sizes[slot].
+// status[0] |= ST_NAN for a NaN distance; status[1] += 1 when member 0 is not the representative (id and distance bits).
+struct PerGroupFillParams {
+    const float* rows; uint32_t ld, dim, n_rows; const float* nd; const uint64_t* row_ids; int metric;
+    const float* q; uint32_t nq, kmax, g;
+    const uint32_t* pairs; const uint32_t* offs; const uint32_t* lens; uint32_t n_wanted; const uint64_t* list; uint64_t list_cap;
+    const uint64_t* rep_ids; const float* rep_dists;
+    uint64_t* out_ids; float* out_dists; uint32_t* out_sizes;
+    uint32_t* status;                                                      // [2], zeroed by the caller
+    uint32_t lds_row_stride, lds_chunk;                                    // set by the launcher
+};
+void launch_per_group_fill(const PerGroupFillParams& p, uint32_t n_pairs, hipStream_t s);
+// mask[0, ceil(bits / 64)) = src (all ones when null) over [0, bits) AND "id < codes_len and codes[id] == code"
+struct PerGroupCodeMaskParams {
+    const uint64_t* src; uint64_t bits; uint64_t* mask;
+    const int32_t* codes; uint64_t codes_len; int32_t code;
+};
+void launch_per_group_code_mask(const PerGroupCodeMaskParams& p, uint32_t n_cu, hipStream_t s);
+// Result list i of a search -- ids / dists [i * stride ..], counts[i] entries -- becomes the members of pair slot dest[i]: the
+// first min(counts[i], stride, g), the rest padded; status[1] += 1 when member 0 is not the representative.
+struct PerGroupPlaceParams {
+    const uint64_t* ids; const float* dists; const uint32_t* counts; uint32_t stride;
+    const uint32_t* dest; uint32_t nq, kmax, g;
+    const uint64_t* rep_ids; const float* rep_dists;
+    uint64_t* out_ids; float* out_dists; uint32_t* out_sizes;
+    uint32_t* status;
+};
+void launch_per_group_place(const PerGroupPlaceParams& p, uint32_t n_lists, hipStream_t s);
+
 // ---------------------------------------------------------------- recommend from stored examples (kernels_recommend.hip)
 constexpr uint32_t RECOMMEND_MAX_EXAMPLES = 64;                            // per request, positives + negatives (VDB_RECOMMEND_MAX_EXAMPLES)
 // The requests of one call on the device: request b owns entries [offs[b], offs[b + 1]) of rows / ids, the first n_pos[b] of

@@ -936,7 +936,8 @@ size_t vdb_flat_distinct_depth(size_t k, size_t len, int stage) {
     return 0;
 }
 
-static int search_distinct_host(vdb_flat_index* ix, HostSearch r, vdb_meta_table* table, uint32_t slot) {
+// pg: the call is vdb_flat_search_batch_per_group -- the same checks, locks and flushes, then per_group_drive
+static int search_distinct_host(vdb_flat_index* ix, HostSearch r, vdb_meta_table* table, uint32_t slot, const PerGroupOut* pg = nullptr) {
     return guarded([&]() -> int {
     const size_t nq = r.nq, dim = r.dim;
     if (!ix || (nq && (!r.queries || !r.counts))) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
@@ -947,6 +948,10 @@ static int search_distinct_host(vdb_flat_index* ix, HostSearch r, vdb_meta_table
     if (!ix->multi && in_flight(ix)) return refuse_in_flight();
     memset(ix->distinct_stats, 0, sizeof(ix->distinct_stats));
     ix->distinct_stats[0] = nq;
+    if (pg) {
+        memset(ix->per_group_stats, 0, sizeof(ix->per_group_stats));
+        ix->per_group_stats[0] = nq;
+    }
     if (nq == 0) return VDB_OK;
     const int dev = ix->multi ? multi_home(ix) : ix->device;
     const size_t len = ix->multi ? multi_len(ix) : ix->n_live + ix->misfits.size();
@@ -955,6 +960,11 @@ static int search_distinct_host(vdb_flat_index* ix, HostSearch r, vdb_meta_table
         return VDB_OK;
     }
     // every refusal below comes before any device search
+    if (pg) {
+        if (pg->g == 0 || pg->g > VDB_PER_GROUP_MAX_SIZE)
+            return fail(VDB_ERR_INVALID_ARGUMENT, "group_size %zu outside [1, %d]", pg->g, VDB_PER_GROUP_MAX_SIZE);
+        if (!pg->sizes) return fail(VDB_ERR_INVALID_ARGUMENT, "null out_sizes");
+    }
     int tdev = 0;
     if ((rc = meta_column_check(table, slot, &tdev))) return rc;
     if (kmax > vdb::DISTINCT_MAX_LIST) return fail(VDB_ERR_INVALID_ARGUMENT, "a search by group returns at most %u rows per query, not %zu", vdb::DISTINCT_MAX_LIST, kmax);
@@ -965,6 +975,8 @@ static int search_distinct_host(vdb_flat_index* ix, HostSearch r, vdb_meta_table
         if ((rc = compiled_mask_check(r.cm, dev))) return rc;
         r.mask_bits = r.cm->bits;
     }
+    // (the member rows of a sharded handle live on several devices: the limit vdb_flat_search_batch_mmr has)
+    if (pg && ix->multi) return fail(VDB_ERR_INVALID_ARGUMENT, "vdb_flat_search_batch_per_group is not available on a sharded handle (vdb_flat_create_sharded)");
     if (nq > 0x3fffffffull) return fail(VDB_ERR_INVALID_ARGUMENT, "batch too large");
     HIP_TRY(hipSetDevice(dev));
     // staged adds first, then the table's staged column writes; the handle's stream waits for those by an event
@@ -983,7 +995,7 @@ static int search_distinct_host(vdb_flat_index* ix, HostSearch r, vdb_meta_table
         search = [&](const float* d_q, size_t n, size_t depth, const uint64_t* d_mask, size_t bits, uint64_t* oi, float* od, uint32_t* oc) {
             return search_device(ix, d_q, n, dim, depth, d_mask, bits, oi, od, oc, nullptr);
         };
-    return distinct_drive(ix, s, search, a);
+    return pg ? per_group_drive(ix, s, search, a, *pg) : distinct_drive(ix, s, search, a);
     });
 }
 
@@ -1008,6 +1020,62 @@ int vdb_flat_distinct_stats(const vdb_flat_index* ix, uint64_t out[8]) {
     if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
     memcpy(out, ix->distinct_stats, sizeof(ix->distinct_stats));
     return VDB_OK;
+}
+
+// ---- up to g rows of each of the k nearest groups (no reference counterpart; vdb_search.cpp per_group_drive)
+int vdb_flat_search_batch_per_group(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k,
+                                    size_t group_size, vdb_meta_table* table, uint32_t slot, const uint64_t* id_mask, size_t mask_bits,
+                                    size_t kstride, uint64_t* out_ids, float* out_dists, int32_t* out_codes, uint32_t* out_sizes,
+                                    size_t* out_counts) {
+    HostSearch r = under(host_search(queries, nq, dim, ks, k, kstride, out_ids, out_dists, out_counts), id_mask, mask_bits);
+    r.codes = out_codes;
+    const PerGroupOut pg{group_size, out_sizes};
+    return search_distinct_host(ix, r, table, slot, &pg);
+}
+
+int vdb_flat_search_batch_per_group_filtered(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks, size_t k,
+                                             size_t group_size, vdb_meta_table* table, uint32_t slot, const vdb_meta_mask* mask,
+                                             size_t kstride, uint64_t* out_ids, float* out_dists, int32_t* out_codes, uint32_t* out_sizes,
+                                             size_t* out_counts) {
+    if (!mask) return fail(VDB_ERR_INVALID_ARGUMENT, "null mask");
+    HostSearch r = under(host_search(queries, nq, dim, ks, k, kstride, out_ids, out_dists, out_counts), mask);
+    r.codes = out_codes;
+    const PerGroupOut pg{group_size, out_sizes};
+    return search_distinct_host(ix, r, table, slot, &pg);
+}
+
+int vdb_flat_per_group_stats(const vdb_flat_index* ix, uint64_t out[8]) {
+    if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (ix->multi) return refuse_multi("vdb_flat_per_group_stats");
+    memcpy(out, ix->per_group_stats, sizeof(ix->per_group_stats));
+    return VDB_OK;
+}
+
+size_t vdb_flat_debug_per_group_plan(const int32_t* codes, const uint32_t* kept, const size_t* ks, size_t nq, size_t kmax, int32_t* wanted,
+                                     size_t cap, uint32_t* index) {
+    size_t n = 0;
+    (void)guarded([&]() -> int {
+    if ((nq && !kept) || (nq && kmax && !codes) || nq > 0x3fffffffull || kmax > vdb::DISTINCT_MAX_LIST) { n = ~(size_t)0; return VDB_OK; }
+    std::vector<int32_t> w;
+    std::vector<uint32_t> at;
+    per_group_plan(codes, kept, ks, nq, kmax, &w, &at);
+    n = w.size();
+    for (size_t i = 0; wanted && i < std::min(n, cap); ++i) wanted[i] = w[i];
+    for (size_t i = 0; index && i < nq * kmax; ++i) index[i] = at[i];
+    return VDB_OK;
+    });
+    return n;
+}
+
+int vdb_flat_debug_set_per_group_scan_cap(vdb_flat_index* ix, size_t rows) {
+    return guarded([&]() -> int {
+    if (!ix) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (ix->multi) return refuse_multi("vdb_flat_debug_set_per_group_scan_cap");
+    if (rows > SPARSE_MAX_E) return fail(VDB_ERR_INVALID_ARGUMENT, "a scan cap of %zu rows is above the capacity %u", rows, SPARSE_MAX_E);
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->per_group_scan_cap = (uint32_t)rows;
+    return VDB_OK;
+    });
 }
 
 }  // extern "C"

@@ -140,6 +140,16 @@ struct DistinctWs {
     vdbi::DevBuf<uint32_t> lc, kept, complete, sel;               // list counts | rows per answer | completeness flags | the incomplete queries
 };
 
+// What one search per group owns on the device beside DistinctWs (vdb_search.cpp per_group_drive): the table of
+// wanted codes, their counters, the plan (offsets | lengths | cursors), the member lists, the pairs of the fill, the members and
+// sizes of every pair, the status words, and -- only when a giant is searched -- its mask, query block and result lists.
+struct PerGroupWs {
+    vdbi::DevBuf<int32_t> wanted;
+    vdbi::DevBuf<uint32_t> cnt, plan, pairs, sizes, stat, sel, dest, gc;
+    vdbi::DevBuf<uint64_t> list, oi, gmask, gi;
+    vdbi::DevBuf<float> od, gq, gd;
+};
+
 // What one grouped search owns on the device (vdb_search.cpp search_grouped) beside the search workspace: the
 // caller's queries and masks, the row masks and lists of all groups, the plan, and the results -- permuted as the passes emit
 // them (s*) and in the caller's order (o*).
@@ -248,6 +258,9 @@ struct vdb_flat_index {
     uint64_t mmr_stats[8] = {0};                            // vdb_flat_mmr_stats: counters of the last diverse top-k call
     uint64_t distinct_stats[8] = {0};                       // vdb_flat_distinct_stats: counters of the last search by group (also on a sharded parent)
     DistinctWs dws;                                         // its device buffers (a sharded parent's live on devices[0])
+    uint64_t per_group_stats[8] = {0};                      // vdb_flat_per_group_stats: counters of the last search per group
+    PerGroupWs pgw;                                         // its device buffers
+    uint32_t per_group_scan_cap = 0;                        // vdb_flat_debug_set_per_group_scan_cap (tests): rows of a list the fill takes, 0 = SPARSE_MAX_E
     uint64_t grouped_stats[8] = {0};                        // vdb_flat_grouped_stats: counters of the last grouped search
     GroupedWs gws;                                          // its device buffers
     uint64_t id_bound = 0;                                  // 1 + the largest id ever added (saturating), raised at add time only: never lowered by a remove
@@ -355,6 +368,19 @@ struct DistinctArgs {
 using DistinctSearch = std::function<int(const float* d_q, size_t nq, size_t depth, const uint64_t* d_mask, size_t mask_bits,
                                          uint64_t* d_ids, float* d_dists, uint32_t* d_counts)>;
 int distinct_drive(Index* H, hipStream_t s, const DistinctSearch& search, const DistinctArgs& a);
+// The driver without its copy-out: the answers (ids, distances, codes [nq][kmax], kept [nq]) are left in H->dws (ai, ad, ac, kept),
+// enqueued on s; *d_mask, if given, receives the staged mask the searches ran under (a.r.mask_bits bits; null: none).
+int distinct_groups(Index* H, hipStream_t s, const DistinctSearch& search, const DistinctArgs& a, const uint64_t** d_mask = nullptr);
+
+// Up to g rows of each of the k nearest groups (vdb_flat_search_batch_per_group); plain handles only.
+// The caller's arrays beside those of a.r (ids and dists are then [nq][kstride][g]); sizes is [nq][kstride].
+struct PerGroupOut { size_t g; uint32_t* sizes; };
+int per_group_drive(Index* ix, hipStream_t s, const DistinctSearch& search, const DistinctArgs& a, const PerGroupOut& o);
+// The host plan: the wanted codes -- the codes >= 0 among the first min(kept[b], kmax, ks[b] if given) entries of every row of
+// codes [nq][kmax] -- ascending and distinct in *wanted, and in (*index)[b * kmax + j] the place of each such entry's code in
+// it (0xffffffff for every other entry).
+void per_group_plan(const int32_t* codes, const uint32_t* kept, const size_t* ks, size_t nq, size_t kmax, std::vector<int32_t>* wanted,
+                    std::vector<uint32_t>* index);
 
 // One batch, a filter per query (vdb_flat_search_batch_grouped).  The plan is host arithmetic alone: the
 // permutation that makes every group's queries contiguous (scanned groups first, then the groups nothing is eligible for, the

@@ -1227,6 +1227,17 @@ int refuse_in_flight() { return fail(VDB_ERR_INVALID_ARGUMENT, "a submitted sear
 // One host read of the flags per stage and per round; ids, distances and codes stay on the device until the end.
 // ---------------------------------------------------------------------------------------------
 int distinct_drive(Index* H, hipStream_t s, const DistinctSearch& search, const DistinctArgs& a) {
+    int rc;
+    if ((rc = distinct_groups(H, s, search, a))) return rc;
+    // ---- the answers come down (a kept count is clamped to the answers' stride)
+    DistinctWs& W = H->dws;
+    size_t emitted = 0;
+    if ((rc = copy_out(Lists{W.ai.p, W.ad.p, W.kept.p, W.ac.p, a.kmax}, a.r, s, &emitted))) return rc;
+    H->distinct_stats[7] += emitted;
+    return VDB_OK;
+}
+
+int distinct_groups(Index* H, hipStream_t s, const DistinctSearch& search, const DistinctArgs& a, const uint64_t** d_mask_out) {
     DistinctWs& W = H->dws;
     uint64_t* st = H->distinct_stats;
     const size_t nq = a.r.nq, dim = a.r.dim, kmax = a.kmax;
@@ -1241,6 +1252,7 @@ int distinct_drive(Index* H, hipStream_t s, const DistinctSearch& search, const 
     const uint64_t* d_mask;
     const size_t mask_bits = a.r.mask_bits;
     if ((rc = stage_mask(W.mask_in, mask_src(a.r), s, &d_mask))) return rc;
+    if (d_mask_out) *d_mask_out = d_mask;
     vdb::DistinctFirstParams fp{};
     fp.ids = W.li.p; fp.dists = W.ld.p; fp.counts = W.lc.p;
     fp.codes = a.d_codes; fp.codes_len = a.codes_len; fp.n_answers = (uint32_t)nq; fp.k = (uint32_t)kmax; fp.kstride = (uint32_t)kmax;
@@ -1306,11 +1318,180 @@ int distinct_drive(Index* H, hipStream_t s, const DistinctSearch& search, const 
             ++st[3];
         }
     }
+    return VDB_OK;
+}
 
-    // ---- the answers come down (a kept count is clamped to the answers' stride)
-    size_t emitted = 0;
-    if ((rc = copy_out(Lists{W.ai.p, W.ad.p, W.kept.p, W.ac.p, kmax}, a.r, s, &emitted))) return rc;
-    st[7] += emitted;
+// ---------------------------------------------------------------------------------------------
+// Up to g rows of each of the k nearest groups (vdb_flat_search_batch_per_group).  The groups are the search by
+// group's answers, left on the device; the members of a group with code c >= 0 are the first g rows of the full ranking whose
+// code is c, so only the rows of the wanted codes are ever ranked:
+//   1  distinct_groups; the codes and kept counts come down, the host sorts them into the table of wanted codes (per_group_plan)
+//   2  one pass over the rows counts every wanted code's members, a host prefix sum, a second pass writes the member lists
+//   3  a giant -- a code with more members than the fill takes -- gets the mask "caller's mask AND code == c" and one ordinary
+//      search of the queries that want it, at depth g
+//   4  every other pair with a code gets a workgroup of per_group_fill_kernel; pairs without a code keep the representative
+//   5  one copy-out.  Nothing is written to the caller's arrays before every check has passed.
+// Nothing survives the call: no list can go stale after an add, a remove, a compaction or a column write.
+// ---------------------------------------------------------------------------------------------
+void per_group_plan(const int32_t* codes, const uint32_t* kept, const size_t* ks, size_t nq, size_t kmax, std::vector<int32_t>* wanted,
+                    std::vector<uint32_t>* index) {
+    wanted->clear();
+    index->assign(nq * kmax, 0xffffffffu);
+    auto groups_of = [&](size_t b) { return std::min(std::min<size_t>(kept[b], kmax), ks ? ks[b] : kmax); };
+    for (size_t b = 0; b < nq; ++b)
+        for (size_t j = 0, c = groups_of(b); j < c; ++j)
+            if (codes[b * kmax + j] >= 0) wanted->push_back(codes[b * kmax + j]);
+    std::sort(wanted->begin(), wanted->end());
+    wanted->erase(std::unique(wanted->begin(), wanted->end()), wanted->end());
+    for (size_t b = 0; b < nq; ++b)
+        for (size_t j = 0, c = groups_of(b); j < c; ++j) {
+            const int32_t code = codes[b * kmax + j];
+            if (code >= 0) (*index)[b * kmax + j] = (uint32_t)(std::lower_bound(wanted->begin(), wanted->end(), code) - wanted->begin());
+        }
+}
+
+int per_group_drive(Index* ix, hipStream_t s, const DistinctSearch& search, const DistinctArgs& a, const PerGroupOut& o) {
+    DistinctWs& W = ix->dws;
+    PerGroupWs& G = ix->pgw;
+    uint64_t* st = ix->per_group_stats;
+    const size_t nq = a.r.nq, dim = a.r.dim, kmax = a.kmax, g = o.g, slots = nq * kmax;
+    int rc;
+    const uint64_t* d_mask = nullptr;
+    if ((rc = distinct_groups(ix, s, search, a, &d_mask))) return rc;
+
+    // ---- the plan
+    std::vector<int32_t> h_codes(slots), wanted;
+    std::vector<uint32_t> h_kept(nq), index, pairs, plan;
+    // (the uploads below read host vectors of this frame: no return, early ones included, leaves one in flight)
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
+    HIP_TRY(hipMemcpyAsync(h_codes.data(), W.ac.p, slots * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_kept.data(), W.kept.p, nq * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    per_group_plan(h_codes.data(), h_kept.data(), a.r.ks, nq, kmax, &wanted, &index);
+    const size_t U = wanted.size();
+    st[4] = U;
+
+    // ---- every pair starts as its representative alone
+    if ((rc = G.oi.ensure(slots * g)) || (rc = G.od.ensure(slots * g)) || (rc = G.sizes.ensure(slots)) || (rc = G.stat.ensure(2))) return rc;
+    HIP_TRY(hipMemsetAsync(G.stat.p, 0, 8, s));
+    vdb::launch_per_group_init(vdb::PerGroupInitParams{W.ai.p, W.ad.p, W.kept.p, (uint32_t)nq, (uint32_t)kmax, (uint32_t)g, G.oi.p, G.od.p, G.sizes.p}, s);
+    HIP_TRY(hipGetLastError());
+
+    if (g > 1 && U) {
+        // ---- member lists: count, prefix sum on the host, scatter
+        const uint32_t n = ix->n_uploaded;
+        const uint32_t cap = ix->per_group_scan_cap ? ix->per_group_scan_cap : SPARSE_MAX_E;
+        if ((rc = G.wanted.ensure(U)) || (rc = G.cnt.ensure(U)) || (rc = G.plan.ensure(3 * U)) || (rc = G.list.ensure(std::max<size_t>(n, 1)))) return rc;
+        HIP_TRY(hipMemcpyAsync(G.wanted.p, wanted.data(), U * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(G.cnt.p, 0, U * 4, s));
+        vdb::PerGroupListParams lp{};
+        lp.row_ids = ix->d_row_ids; lp.live = (ix->n_live == n) ? nullptr : ix->d_live.p; lp.n_rows = n;
+        lp.mask = d_mask; lp.mask_bits = a.r.mask_bits;
+        lp.codes = a.d_codes; lp.codes_len = a.codes_len;
+        lp.wanted = G.wanted.p; lp.n_wanted = (uint32_t)U; lp.counts = G.cnt.p;
+        lp.offs = G.plan.p; lp.lens = G.plan.p + U; lp.cursor = G.plan.p + 2 * U; lp.list = G.list.p; lp.list_cap = n;
+        vdb::launch_per_group_list(lp, false, a.n_cu, s);
+        HIP_TRY(hipGetLastError());
+        std::vector<uint32_t> count(U);
+        plan.assign(3 * U, 0);
+        HIP_TRY(hipMemcpyAsync(count.data(), G.cnt.p, U * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        uint64_t listed = 0;
+        for (size_t u = 0; u < U; ++u) {
+            const uint32_t e = std::min(count[u], n);                      // (a count read from the device: clamped)
+            const uint32_t len = (e > cap || listed + e > n) ? 0 : e;      // a giant is not listed
+            plan[u] = (uint32_t)listed; plan[U + u] = len;
+            listed += len;
+        }
+        st[5] = listed;
+        HIP_TRY(hipMemcpyAsync(G.plan.p, plan.data(), 3 * U * 4, hipMemcpyHostToDevice, s));
+        if (listed) {
+            vdb::launch_per_group_list(lp, true, a.n_cu, s);
+            HIP_TRY(hipGetLastError());
+        }
+
+        // ---- the pairs: those of a listed code for the fill, those of a giant by code
+        std::vector<std::vector<uint32_t>> giant(U);
+        for (size_t slot = 0; slot < slots; ++slot) {
+            const uint32_t u = index[slot];
+            if (u == 0xffffffffu) continue;
+            if (plan[U + u]) { pairs.push_back((uint32_t)slot); pairs.push_back(u); st[6] += plan[U + u]; }
+            else { giant[u].push_back((uint32_t)slot); ++st[3]; }
+        }
+        st[2] = pairs.size() / 2;
+
+        // ---- giants: one masked search per code, at depth g
+        if (st[3]) {
+            const uint64_t xbits = std::min<uint64_t>(d_mask ? (uint64_t)a.r.mask_bits : a.id_bound, a.codes_len);
+            const size_t depth = std::min(g, a.len);
+            if ((rc = G.gmask.ensure(std::max<size_t>((xbits + 63) / 64, 1)))) return rc;
+            for (size_t u = 0; u < U; ++u) {
+                const size_t m = giant[u].size();
+                if (!m) continue;
+                std::vector<uint32_t> sel(m);
+                for (size_t i = 0; i < m; ++i) sel[i] = giant[u][i] / (uint32_t)kmax;
+                if ((rc = G.sel.ensure(m)) || (rc = G.dest.ensure(m)) || (rc = G.gq.ensure(m * std::max<size_t>(dim, 1))) || (rc = G.gi.ensure(m * depth)) ||
+                    (rc = G.gd.ensure(m * depth)) || (rc = G.gc.ensure(m)))
+                    return rc;
+                HIP_TRY(hipMemcpyAsync(G.sel.p, sel.data(), m * 4, hipMemcpyHostToDevice, s));
+                HIP_TRY(hipMemcpyAsync(G.dest.p, giant[u].data(), m * 4, hipMemcpyHostToDevice, s));
+                vdb::launch_per_group_code_mask(vdb::PerGroupCodeMaskParams{d_mask, xbits, G.gmask.p, a.d_codes, a.codes_len, wanted[u]}, a.n_cu, s);
+                vdb::launch_gather_rows(W.q.p, (uint32_t)dim, (uint32_t)dim, (uint32_t)nq, G.sel.p, (uint32_t)m, G.gq.p, s);
+                HIP_TRY(hipGetLastError());
+                if ((rc = search(G.gq.p, m, depth, G.gmask.p, (size_t)xbits, G.gi.p, G.gd.p, G.gc.p))) {
+                    (void)hipStreamSynchronize(s);                         // (sel is a host vector of this frame)
+                    return rc;
+                }
+                vdb::launch_per_group_place(vdb::PerGroupPlaceParams{G.gi.p, G.gd.p, G.gc.p, (uint32_t)depth, G.dest.p, (uint32_t)nq, (uint32_t)kmax, (uint32_t)g,
+                                                                     W.ai.p, W.ad.p, G.oi.p, G.od.p, G.sizes.p, G.stat.p}, (uint32_t)m, s);
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipStreamSynchronize(s));                          // (sel and the next round's buffers)
+            }
+        }
+
+        // ---- the fill reads plain f32 rows, as every non-screening reader does
+        if (!pairs.empty()) {
+            const float* rows = rows_f32(ix);
+            if (!rows) return fail(VDB_ERR_DEVICE, "internal error: no rows to rank");
+            if ((rc = G.pairs.ensure(pairs.size()))) return rc;
+            HIP_TRY(hipMemcpyAsync(G.pairs.p, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice, s));
+            vdb::PerGroupFillParams fp{};
+            fp.rows = rows; fp.ld = ix->ld; fp.dim = ix->dim; fp.n_rows = n; fp.nd = ix->d_nd; fp.row_ids = ix->d_row_ids; fp.metric = ix->metric;
+            fp.q = W.q.p; fp.nq = (uint32_t)nq; fp.kmax = (uint32_t)kmax; fp.g = (uint32_t)g;
+            fp.pairs = G.pairs.p; fp.offs = G.plan.p; fp.lens = G.plan.p + U; fp.n_wanted = (uint32_t)U; fp.list = G.list.p; fp.list_cap = n;
+            fp.rep_ids = W.ai.p; fp.rep_dists = W.ad.p;
+            fp.out_ids = G.oi.p; fp.out_dists = G.od.p; fp.out_sizes = G.sizes.p; fp.status = G.stat.p;
+            vdb::launch_per_group_fill(fp, (uint32_t)(pairs.size() / 2), s);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+
+    // ---- one copy-out; nothing reaches the caller's arrays before the status words are read
+    std::vector<uint64_t> h_ids(slots * g);
+    std::vector<float> h_dists(slots * g);
+    std::vector<uint32_t> h_sizes(slots);
+    uint32_t h_stat[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(h_ids.data(), G.oi.p, slots * g * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_dists.data(), G.od.p, slots * g * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_sizes.data(), G.sizes.p, slots * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_stat, G.stat.p, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h_stat[0] & vdb::ST_NAN) return fail_nan();
+    st[7] = h_stat[1];
+    if (h_stat[1]) return fail(VDB_ERR_DEVICE, "internal error: the first member of %u groups is not the group's representative", h_stat[1]);
+    const Batch& r = a.r;
+    for (size_t b = 0; b < nq; ++b) {
+        const size_t c = std::min(std::min<size_t>(h_kept[b], kmax), r.ks ? r.ks[b] : r.k);
+        r.counts[b] = c;
+        st[1] += c;
+        for (size_t j = 0; j < c; ++j) {
+            const size_t from = b * kmax + j, to = b * r.kstride + j;
+            const size_t size = std::min<size_t>(h_sizes[from], g);
+            o.sizes[to] = (uint32_t)size;
+            if (r.codes) r.codes[to] = h_codes[from];
+            for (size_t m = 0; m < size; ++m) { r.ids[to * g + m] = h_ids[from * g + m]; r.dists[to * g + m] = h_dists[from * g + m]; }
+        }
+    }
     return VDB_OK;
 }
 

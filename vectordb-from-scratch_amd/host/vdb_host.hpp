@@ -161,6 +161,26 @@ public:
         if (codes) codes->assign(cs.begin(), cs.begin() + (ptrdiff_t)cnt);
         return out;
     }
+    // no reference counterpart: the k nearest GROUPS (search_distinct's answer) with up to group_size rows of each -- the first rows of
+    // the full ranking whose code in column `slot` of `table` is the group's; a row with code -1 is its own group of one.  Member 0
+    // of every group is its representative.  codes (may be null) receives the group code of every returned group.
+    std::vector<std::vector<Neighbor>> search_per_group(const Vector& q, size_t k, size_t group_size, vdb_meta_table* table, uint32_t slot,
+                                                        const uint64_t* id_mask = nullptr, size_t mask_bits = 0,
+                                                        std::vector<int32_t>* codes = nullptr) const {
+        const size_t stride = std::max<size_t>(k, 1), g = std::max<size_t>(group_size, 1);
+        std::vector<uint64_t> ids(stride * g);
+        std::vector<float> ds(ids.size());
+        std::vector<int32_t> cs(stride);
+        std::vector<uint32_t> sizes(stride);
+        size_t cnt = 0;
+        check(vdb_flat_search_batch_per_group(h_, q.as_slice().data(), 1, q.dimension(), nullptr, k, group_size, table, slot, id_mask, mask_bits,
+                                              stride, ids.data(), ds.data(), cs.data(), sizes.data(), &cnt));
+        std::vector<std::vector<Neighbor>> out(cnt);
+        for (size_t j = 0; j < cnt; ++j)
+            for (size_t m = 0; m < sizes[j]; ++m) out[j].emplace_back((size_t)ids[j * g + m], ds[j * g + m]);
+        if (codes) codes->assign(cs.begin(), cs.begin() + (ptrdiff_t)cnt);
+        return out;
+    }
     // no reference counterpart: k rows near q and apart from each other (maximal marginal relevance over the `candidates` nearest
     // rows, include/vdb_flat.h "DIVERSE TOP-K"), in pick order.  scores (may be null) receives the score each pick was chosen with.
     std::vector<Neighbor> search_mmr(const Vector& q, size_t k, size_t candidates, float lambda, const uint64_t* id_mask = nullptr,

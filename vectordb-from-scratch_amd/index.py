@@ -524,6 +524,92 @@ class GpuFlatIndex(Index):
         """Rows per query the stage-A (0) / stage-B (1) search of search_batch_distinct asks for; needs no device."""
         return int(_ffi.lib().vdb_flat_distinct_depth(int(k), int(length), int(stage)))
 
+    # ---- up to g rows of each of the k nearest groups (include/vdb_flat.h vdb_flat_search_batch_per_group; no reference counterpart)
+    PER_GROUP_MAX_SIZE = 32
+
+    def search_batch_per_group(self, queries, k, group_size, table, slot, id_mask=None, mask_bits=0, compiled_mask=None):
+        """The k nearest GROUPS (search_batch_distinct's answer under the same arguments) with up to group_size rows of each:
+        the members of a group with code c >= 0 are the first group_size rows of the full ranking of the eligible rows whose
+        code in column `slot` of `table` is c; a row with code -1 is its own group of one.  Member 0 of every group is its
+        representative.  Exact.  k an int or a per-query array.  Returns (ids [nq, k, g], dists [nq, k, g], codes [nq, k],
+        sizes [nq, k], counts [nq]); only the first sizes[b, j] members of the first counts[b] groups are meaningful."""
+        if compiled_mask is not None and id_mask is not None:
+            raise ValueError("pass id_mask or compiled_mask, not both")
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2:
+            raise ValueError("queries must be a 2-d array")
+        nq, dim = q.shape
+        if np.isscalar(k):
+            ks_ptr, kscalar, kmax = None, int(k), int(k)
+        else:
+            ks = np.ascontiguousarray(k, dtype=np.uintp)
+            if ks.shape != (nq,):
+                raise ValueError(f"k must be a scalar or hold one value per query ({nq}), not {ks.shape}")
+            ks_ptr = ks.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t))
+            kscalar, kmax = 0, int(ks.max()) if ks.size else 0
+        g = int(group_size)
+        kstride, gdim = max(kmax, 1), max(g, 1)
+        out_ids = np.zeros((nq, kstride, gdim), dtype=np.uint64)
+        out_d = np.zeros((nq, kstride, gdim), dtype=np.float32)
+        out_c = np.full((nq, kstride), -1, dtype=np.int32)
+        sizes = np.zeros((nq, kstride), dtype=np.uint32)
+        counts = np.zeros(nq, dtype=np.uintp)
+        tail = (kstride, _u64p(out_ids), _fp(out_d), out_c.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)))
+        head = (self._h, _fp(q), nq, dim, ks_ptr, kscalar, g, table._t if table is not None else None, int(slot))
+        if compiled_mask is not None:
+            rc = self._L.vdb_flat_search_batch_per_group_filtered(*head, compiled_mask.handle, *tail)
+        else:
+            mask_ptr = None
+            if id_mask is not None:
+                m = np.ascontiguousarray(id_mask, dtype=np.uint64)
+                mask_ptr = _u64p(m)
+            rc = self._L.vdb_flat_search_batch_per_group(*head, mask_ptr, int(mask_bits), *tail)
+        if rc:
+            _raise(rc)
+        return out_ids, out_d, out_c, sizes, counts
+
+    def per_group_stats(self):
+        """The last search_batch_per_group: [0] queries, [1] groups returned, [2] pairs filled by the member scan, [3] pairs answered
+        by a giant's masked search, [4] distinct wanted codes, [5] member rows listed, [6] pair distances evaluated by the fill,
+        [7] representative mismatches (always 0)."""
+        out = (ctypes.c_uint64 * 8)()
+        rc = self._L.vdb_flat_per_group_stats(self._h, out)
+        if rc:
+            _raise(rc)
+        return [int(x) for x in out]
+
+    @staticmethod
+    def debug_per_group_plan(codes, kept, ks=None):
+        """The host plan of search_batch_per_group for the answers' codes [nq, kmax] and kept counts [nq] (ks: a per-query k);
+        needs no device.  Returns (wanted i32 [U] ascending, index u32 [nq, kmax]: the place of every counted entry's code in
+        wanted, 0xffffffff for the others), or None for kmax above 1024."""
+        cd = np.ascontiguousarray(codes, dtype=np.int32)
+        kp = np.ascontiguousarray(kept, dtype=np.uint32).reshape(-1)
+        if cd.ndim != 2 or cd.shape[0] != kp.size:
+            raise ValueError("codes must be [nq, kmax] and kept [nq]")
+        nq, kmax = cd.shape
+        i32p, u32p, szp = (ctypes.POINTER(t) for t in (ctypes.c_int32, ctypes.c_uint32, ctypes.c_size_t))
+        ksp = None
+        if ks is not None:
+            ks = np.ascontiguousarray(ks, dtype=np.uintp)
+            ksp = ks.ctypes.data_as(szp)
+        L = _ffi.lib()
+        args = (cd.ctypes.data_as(i32p), kp.ctypes.data_as(u32p), ksp, nq, kmax)
+        n = L.vdb_flat_debug_per_group_plan(*args, None, 0, None)
+        if n == ctypes.c_size_t(-1).value:
+            return None
+        wanted = np.zeros(n, dtype=np.int32)
+        index = np.zeros((nq, kmax), dtype=np.uint32)
+        L.vdb_flat_debug_per_group_plan(*args, wanted.ctypes.data_as(i32p), n, index.ctypes.data_as(u32p))
+        return wanted, index
+
+    def debug_set_per_group_scan_cap(self, rows):
+        """tests: the longest member list search_batch_per_group's fill takes, in rows (0 = the default, 131072)"""
+        rc = self._L.vdb_flat_debug_set_per_group_scan_cap(self._h, int(rows))
+        if rc:
+            _raise(rc)
+
     # ---- one batch, a filter per query (include/vdb_flat.h vdb_flat_search_batch_grouped; no reference counterpart)
     def search_batch_grouped(self, queries, k, group_of, id_masks=None, mask_bits=0, compiled_masks=None, ks=None):
         """One batch, a filter per query: the answer for query b is what search_batch_arrays returns for that query alone under

@@ -797,6 +797,58 @@ class VectorStore:
                 cm.release()
         return [self._map([(int(out_ids[b, i]), dists[b, i]) for i in range(int(counts[b]))]) for b in range(len(queries))]
 
+    # ---- "the best passages of the k nearest documents" (GpuFlatIndex.search_batch_per_group; no reference counterpart)
+    def search_groups(self, query, k, field, group_size, flt=None):
+        """The k nearest GROUPS of rows that share a value of metadata field `field`, nearest first, each with its up to
+        group_size nearest rows: a list of (field value, [SearchResult, ...]).  A row without the field is its own group
+        (value None, one member)."""
+        return self.search_groups_batch([query], k, field, group_size, flt)[0]
+
+    def search_groups_batch(self, queries, k, field, group_size, flt=None):
+        """search_groups for several queries in one device call.  flt is a PRE-filter.  With the device filter on
+        (set_device_filter(True)) the field's resident column is read and flt is compiled on the device when it fits the
+        program limits, as search_distinct_batch does; with it off the field's column is sent up for this call alone and flt
+        is compiled by compile_filter.  A field no row has leaves every row its own group: the plain search."""
+        if not isinstance(self._index, GpuFlatIndex):
+            raise ValueError("search_groups needs a GpuFlatIndex")
+        group_size = int(group_size)
+        if not 1 <= group_size <= GpuFlatIndex.PER_GROUP_MAX_SIZE:
+            raise ValueError(f"group_size must lie in [1, {GpuFlatIndex.PER_GROUP_MAX_SIZE}]")
+        queries = list(queries)
+        if self.is_empty() or not queries:
+            return [[] for _ in queries]
+        for q in queries:
+            self._check_dim(q)
+        qs = np.stack([q.data for q in queries]).astype(np.float32)
+        cm = self.compile_filter_device(flt) if flt is not None and self._table is not None else None
+        mask, bits = self.compile_filter(flt) if flt is not None and cm is None else (None, 0)
+        col, own = self._cols.get(field), None
+        try:
+            if col is None:
+                out_ids, dists, counts = self._index.search_batch_arrays(qs, int(k), id_mask=mask, mask_bits=bits, compiled_mask=cm)
+                return [[(None, self._map([(int(out_ids[b, i]), dists[b, i])])) for i in range(int(counts[b]))] for b in range(len(queries))]
+            table, slot = self._table, self._slots[field]
+            if table is None:
+                table = own = MetaTable(self._index._device)
+                own.set_codes(0, 0, col.view(max(self._next_id, 1)))
+                slot = 0
+            out_ids, dists, codes, sizes, counts = self._index.search_batch_per_group(qs, int(k), group_size, table, slot, id_mask=mask,
+                                                                                      mask_bits=bits, compiled_mask=cm)
+        finally:
+            if cm is not None:
+                cm.release()
+            if own is not None:
+                own.close()
+        out = []
+        for b in range(len(queries)):
+            groups = []
+            for j in range(int(counts[b])):
+                c = int(codes[b, j])
+                members = self._map([(int(out_ids[b, j, m]), dists[b, j, m]) for m in range(int(sizes[b, j]))])
+                groups.append((col.values[c] if c >= 0 else None, members))
+            out.append(groups)
+        return out
+
     def search_batch_prefiltered(self, queries, flt):
         if self.is_empty():
             return [[] for _ in queries]
