@@ -34,10 +34,12 @@ constexpr int MT = 4, QT = 4;                    // MFMA tiles per wave: 4 x 32 
 
 // The 256 accumulators of a wave live in a[0:255], named BY HAND.  Left to hipcc, a 4 x 4 block of f32x16 accumulators
 // that fills the AccVGPR file exactly is allocated with copies through VGPRs and scratch spills inside the stage loop (a
-// scratch reload is a vector-memory operation: it drains the DMA pipeline).  So the MFMAs, the zeroing and the epilogue's
-// reads are inline asm on fixed AccVGPRs -- accumulator (i, j) is a[16 (4 i + j) .. +15] -- and the compiler allocates
-// nothing but the 256 architectural VGPRs.  Inline asm is opaque to the hazard recognizer: the waits between an MFMA
-// and the first VALU access to its result are placed by hand (s_nop before the epilogue and after the zeroing).
+// scratch reload is a vector-memory operation: it drains the DMA pipeline).  So the MFMAs and the epilogue's reads are
+// inline asm on fixed AccVGPRs -- accumulator (i, j) is a[16 (4 i + j) .. +15] -- and the compiler allocates nothing
+// but the 256 architectural VGPRs.  Nothing ever zeroes an accumulator: the first k-step of a tile issues its MFMAs
+// with the inline constant 0 as C (VDB_MFMA4Z), the same accumulation from +0.0 as into a zeroed register.  Inline asm
+// is opaque to the hazard recognizer: the waits between an MFMA and the first VALU access to its result are placed by
+// hand (s_nop before the epilogue).
 #define VDB_ALL_AGPRS "a0","a1","a2","a3","a4","a5","a6","a7","a8","a9","a10","a11","a12","a13","a14","a15","a16","a17","a18","a19","a20","a21","a22","a23","a24","a25","a26","a27","a28","a29","a30","a31","a32","a33","a34","a35","a36","a37","a38","a39","a40","a41","a42","a43","a44","a45","a46","a47","a48","a49","a50","a51","a52","a53","a54","a55","a56","a57","a58","a59","a60","a61","a62","a63","a64","a65","a66","a67","a68","a69","a70","a71","a72","a73","a74","a75","a76","a77","a78","a79","a80","a81","a82","a83","a84","a85","a86","a87","a88","a89","a90","a91","a92","a93","a94","a95","a96","a97","a98","a99","a100","a101","a102","a103","a104","a105","a106","a107","a108","a109","a110","a111","a112","a113","a114","a115","a116","a117","a118","a119","a120","a121","a122","a123","a124","a125","a126","a127","a128","a129","a130","a131","a132","a133","a134","a135","a136","a137","a138","a139","a140","a141","a142","a143","a144","a145","a146","a147","a148","a149","a150","a151","a152","a153","a154","a155","a156","a157","a158","a159","a160","a161","a162","a163","a164","a165","a166","a167","a168","a169","a170","a171","a172","a173","a174","a175","a176","a177","a178","a179","a180","a181","a182","a183","a184","a185","a186","a187","a188","a189","a190","a191","a192","a193","a194","a195","a196","a197","a198","a199","a200","a201","a202","a203","a204","a205","a206","a207","a208","a209","a210","a211","a212","a213","a214","a215","a216","a217","a218","a219","a220","a221","a222","a223","a224","a225","a226","a227","a228","a229","a230","a231","a232","a233","a234","a235","a236","a237","a238","a239","a240","a241","a242","a243","a244","a245","a246","a247","a248","a249","a250","a251","a252","a253","a254","a255"
 #define VDB_MFMA(I, J, FA, FB)                                                                         \
     asm volatile("v_mfma_f32_32x32x16_bf16 a[%2:%3], %0, %1, a[%2:%3]"                               \
@@ -45,11 +47,6 @@ constexpr int MT = 4, QT = 4;                    // MFMA tiles per wave: 4 x 32 
 // (the AccVGPR clobber list on a READ keeps hipcc from parking values in "free" AccVGPRs across it -- it has no other way to
 // know that a[0:255] are taken; the Makefile checks the generated code for compiler-made AccVGPR accesses and scratch)
 #define VDB_ACC_READ(DST, I, J, R) asm volatile("v_accvgpr_read_b32 %0, a[%1]" : "=v"(DST) : "n"(16 * (4 * (I) + (J)) + (R)) : VDB_ALL_AGPRS)
-#define VDB_Z1(N) asm volatile("v_accvgpr_write_b32 a[%0], 0" :: "n"(N) : VDB_ALL_AGPRS);
-#define VDB_Z4(N) VDB_Z1(N) VDB_Z1((N) + 1) VDB_Z1((N) + 2) VDB_Z1((N) + 3)
-#define VDB_Z16(N) VDB_Z4(N) VDB_Z4((N) + 4) VDB_Z4((N) + 8) VDB_Z4((N) + 12)
-#define VDB_Z64(N) VDB_Z16(N) VDB_Z16((N) + 16) VDB_Z16((N) + 32) VDB_Z16((N) + 48)
-#define VDB_ZERO_ACC { VDB_Z64(0) VDB_Z64(64) VDB_Z64(128) VDB_Z64(192) asm volatile("s_nop 7" ::: "memory"); }
 }  // namespace
 
 // SAMPLE = true: the sample pass over the COMPACT bf16 copy of the sample rows (p.rows16 = that copy, sample j at row j: the
@@ -159,6 +156,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                  :: "v"(FA), "v"(FB[0]), "v"(FB[1]), "v"(FB[2]), "v"(FB[3]),                          \
                     "n"(64 * (I)), "n"(64 * (I) + 15), "n"(64 * (I) + 16), "n"(64 * (I) + 31), "n"(64 * (I) + 32), "n"(64 * (I) + 47), \
                     "n"(64 * (I) + 48), "n"(64 * (I) + 63) : VDB_ALL_AGPRS)
+    // the same four with C = 0: the first k-step of a tile (the accumulate chain that follows takes D whole as C: no wait state)
+#define VDB_MFMA4Z(I, FA, FB)                                                                          \
+    asm volatile("v_mfma_f32_32x32x16_bf16 a[%5:%6], %0, %1, 0\n\tv_mfma_f32_32x32x16_bf16 a[%7:%8], %0, %2, 0\n\t" \
+                 "v_mfma_f32_32x32x16_bf16 a[%9:%10], %0, %3, 0\n\tv_mfma_f32_32x32x16_bf16 a[%11:%12], %0, %4, 0" \
+                 :: "v"(FA), "v"(FB[0]), "v"(FB[1]), "v"(FB[2]), "v"(FB[3]),                          \
+                    "n"(64 * (I)), "n"(64 * (I) + 15), "n"(64 * (I) + 16), "n"(64 * (I) + 31), "n"(64 * (I) + 32), "n"(64 * (I) + 47), \
+                    "n"(64 * (I) + 48), "n"(64 * (I) + 63) : VDB_ALL_AGPRS)
     // row constants of a tile, one tile ahead (4 bytes per lane): wave w fetches those of tile rows 64w..64w+63
     auto issue_consts = [&](uint32_t t) {
         const uint32_t par = t & 1u;
@@ -173,8 +177,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     if (MARGIN) {
         if (tid < TQ) { float g = p.qg[tid]; asm volatile("" : "+v"(g)); sG[tid] = g; }
     }
-
-    VDB_ZERO_ACC
 
     // fragment read offsets.  Row fragment of k-step t of half hf: chunk 4 hf + 2 t + h; query fragment: chunk 2 t + h
     const uint32_t swa = (c >> 1) & 7, swb = (c >> 2) & 3;
@@ -217,12 +219,16 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         // ---- k-step 0: 16 MFMAs, the eight fragment reads of k-step 1 between them
 #pragma unroll
         for (int j = 0; j < QT; ++j) fb1[j] = VDB_RD(qcur + offB[1] + j * 32 * B_ROWB);
-#define VDB_K0_ROW(I)                                                                                  \
+#define VDB_K0_ROW(I, MF)                                                                              \
         fa1[I] = VDB_RD(rcur + offA[HF][1] + (I) * 32 * A_ROWB);                                       \
         __builtin_amdgcn_sched_barrier(0);                                                             \
-        VDB_MFMA4(I, fa0[I], fb0);                                                                     \
+        MF(I, fa0[I], fb0);                                                                            \
         __builtin_amdgcn_sched_barrier(0);
-        VDB_K0_ROW(0) VDB_K0_ROW(1) VDB_K0_ROW(2) VDB_K0_ROW(3)
+        if (HF == 0 && ks == 0) {                                       // a tile starts (wave-uniform): C = 0, nothing is zeroed
+            VDB_K0_ROW(0, VDB_MFMA4Z) VDB_K0_ROW(1, VDB_MFMA4Z) VDB_K0_ROW(2, VDB_MFMA4Z) VDB_K0_ROW(3, VDB_MFMA4Z)
+        } else {
+            VDB_K0_ROW(0, VDB_MFMA4) VDB_K0_ROW(1, VDB_MFMA4) VDB_K0_ROW(2, VDB_MFMA4) VDB_K0_ROW(3, VDB_MFMA4)
+        }
 #undef VDB_K0_ROW
         // ---- publish the next half-stage, free the images of this one
         if (consts_in_window) {                                         // + the 3 (4) constant fetches of the tile start
@@ -321,6 +327,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 #pragma unroll
             for (int j = 0; j < QT; ++j) best[j] = __uint_as_float(0x7f800000u);
             asm volatile("s_nop 7" ::: "memory");                       // the last MFMA of the k-step wrote a[240:255]; they are read last
+            // ORDER: sub-tile by sub-tile -- I, J, then the four groups of (I, J) -- with alpha and beta of row block I read ONCE,
+            // in front of its four sub-tiles, and held in 32 registers.  With one wave on the SIMD every LDS read in front of
+            // a group is a wait that nothing hides: 4 of them per tile this way, 16 with the groups outermost, 64 when every
+            // group re-reads (measured: +27 us per C2 launch).  Sub-tile (3, 3), which the last MFMAs of the tile wrote, is
+            // still read last.  (Issuing the NEXT tile's first MFMAs from here, each behind the last read of its sub-tile,
+            // was measured and taken out again: DESIGN.md 4.3.)
 #define VDB_EPI_J(I, G4, J, NN)                                                                        \
     {                                                                                                  \
         float p0_, p1_, p2_, p3_;                              /* four reads in ONE asm: hipcc puts an s_nop behind every inline asm */ \
@@ -328,6 +340,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                      : "=v"(p0_), "=v"(p1_), "=v"(p2_), "=v"(p3_)                                      \
                      : "n"(16 * (4 * (I) + (J)) + 4 * (G4)), "n"(16 * (4 * (I) + (J)) + 4 * (G4) + 1), \
                        "n"(16 * (4 * (I) + (J)) + 4 * (G4) + 2), "n"(16 * (4 * (I) + (J)) + 4 * (G4) + 3) : VDB_ALL_AGPRS); \
+        const float4 a4 = a4_[G4], b4 = b4_[G4];                                                       \
+        const f32x2 al01 = {a4.x, a4.y}, al23 = {a4.z, a4.w}, be01 = {b4.x, b4.y}, be23 = {b4.z, b4.w}; \
+        const uint32_t rt0 = rowt + 8 * (G4);                                                          \
         const f32x2 p01 = {p0_, p1_}, p23 = {p2_, p3_};                                                \
         const f32x2 s01 = __builtin_elementwise_fma(p01, al01, be01), s23 = __builtin_elementwise_fma(p23, al23, be23); \
         const float s0 = s01.x, s1 = s01.y, s2 = s23.x, s3 = s23.y;                                    \
@@ -350,26 +365,27 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
             VDB_APPEND(s0, s1, s2, s3, vbits >> (8 * (G4)), tp, thr[J], ng[J], mg, (I) * 32 + 8 * (G4) + 4 * h, pool[J], pcnt[J], tr0 + rt0) \
         }                                                                                              \
     }
-#define VDB_EPI_G(I, G4, NN)                                                                           \
+#define VDB_EPI_IJ(I, J, NN)                                                                           \
     {                                                                                                  \
-        const float4 a4 = *reinterpret_cast<const float4*>(al + (I) * 32 + 8 * (G4));                  \
-        const float4 b4 = *reinterpret_cast<const float4*>(be + (I) * 32 + 8 * (G4));                  \
-        const f32x2 al01 = {a4.x, a4.y}, al23 = {a4.z, a4.w}, be01 = {b4.x, b4.y}, be23 = {b4.z, b4.w}; \
-        const uint32_t rt0 = rowt + 8 * (G4);                                                          \
-        VDB_EPI_J(I, G4, 0, NN) __builtin_amdgcn_sched_barrier(0); VDB_EPI_J(I, G4, 1, NN) __builtin_amdgcn_sched_barrier(0);    \
-        VDB_EPI_J(I, G4, 2, NN) __builtin_amdgcn_sched_barrier(0); VDB_EPI_J(I, G4, 3, NN) __builtin_amdgcn_sched_barrier(0);    \
+        VDB_EPI_J(I, 0, J, NN) __builtin_amdgcn_sched_barrier(0); VDB_EPI_J(I, 1, J, NN) __builtin_amdgcn_sched_barrier(0);      \
+        VDB_EPI_J(I, 2, J, NN) __builtin_amdgcn_sched_barrier(0); VDB_EPI_J(I, 3, J, NN) __builtin_amdgcn_sched_barrier(0);      \
     }
 #define VDB_EPI_I(I, NN)                                                                               \
     {                                                                                                  \
         const uint32_t vbits = (uint32_t)(val[(I) >> 1] >> (32 * ((I) & 1) + 4 * h));                  \
         const uint32_t rowt = wr * 128 + (I) * 32 + 4 * h;              /* tile-row of element (g = 0, e = 0) */ \
-        VDB_EPI_G(I, 0, NN) VDB_EPI_G(I, 1, NN) VDB_EPI_G(I, 2, NN) VDB_EPI_G(I, 3, NN)                \
+        float4 a4_[4], b4_[4];                                          /* alpha, beta of the row block: held across J */ \
+        _Pragma("unroll") for (int g_ = 0; g_ < 4; ++g_) {                                             \
+            a4_[g_] = *reinterpret_cast<const float4*>(al + (I) * 32 + 8 * g_);                        \
+            b4_[g_] = *reinterpret_cast<const float4*>(be + (I) * 32 + 8 * g_);                        \
+        }                                                                                              \
+        VDB_EPI_IJ(I, 0, NN) VDB_EPI_IJ(I, 1, NN) VDB_EPI_IJ(I, 2, NN) VDB_EPI_IJ(I, 3, NN)            \
     }
             // two copies of the scoring code, chosen once per tile: with the NaN test per group and without it
             if (no_nan) { VDB_EPI_I(0, 1) VDB_EPI_I(1, 1) VDB_EPI_I(2, 1) VDB_EPI_I(3, 1) }
             else { VDB_EPI_I(0, 0) VDB_EPI_I(1, 0) VDB_EPI_I(2, 0) VDB_EPI_I(3, 0) }
 #undef VDB_EPI_I
-#undef VDB_EPI_G
+#undef VDB_EPI_IJ
 #undef VDB_EPI_J
             if (SAMPLE) {
                 // one group minimum per (tile, row half, lane half) and query; the key's low word only has to make the keys of
@@ -379,7 +395,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                 for (int j = 0; j < QT; ++j)
                     p.minkeys[(size_t)q_of[j] * p.minkey_stride + g] = best[j] < __uint_as_float(0x7f800000u) ? make_key(best[j], g) : EMPTY_KEY;
             }
-            VDB_ZERO_ACC
         }
         ++ks;
         if (ks == KH) { ks = 0; ++tile; }
@@ -399,6 +414,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 #undef VDB_DMA_SV
 #undef VDB_MFMA_DMA
 #undef VDB_MFMA4
+#undef VDB_MFMA4Z
 #undef VDB_ISSUE_R
 #undef VDB_ISSUE_Q
 #undef VDB_RD
