@@ -1426,6 +1426,10 @@ def resolve(trace, op, log):
         return [("add", (int(id), log.rows[at[-1]].copy() if len(at) else v))]
     if kind == "zero":
         return [("add", (int(op[1]), np.zeros(d, dtype=F32)))]
+    if kind == "inf":                                                # one infinite element: the forward conversion of the rows refuses it
+        v = vectors(seed, op[2], 1, d)[0]
+        v[3] = np.inf
+        return [("add", (int(op[1]), v))]
     if kind == "misfit":
         return [("add", (int(op[1]), np.ones(int(op[2]), dtype=F32)))]
     if kind in ("bulk", "reset"):
@@ -2495,7 +2499,7 @@ class GpuIndexAdapter(EngineErrors):
         self.ix = vdb.GpuFlatIndex(vdb.DistanceMetric(metric), keep_host_copy=False, devices=devices)
         self.table = vdb.MetaTable(0)
         self.id_bound = 0
-        self.settings = dict(shadow=0, tiers=0, sparse_filter=0, screen=1, large_k=1, sample_cache=1)
+        self.settings = dict(shadow=0, tiers=0, sparse_filter=0, screen=1, large_k=1, sample_cache=1, split=1, split_after=0)
         self.seen = Counter()
         self.route, self.raw = None, None
         self._compactions, self._cap = 0, 0
@@ -2558,12 +2562,22 @@ class GpuIndexAdapter(EngineErrors):
         {"shadow": lambda: ix.set_shadow(bool(value)), "sample_cache": lambda: ix.set_sample_cache(bool(value)),
          "screen": lambda: ix.set_screen(int(value)), "tiers": lambda: ix.set_tiers(int(value)),
          "sparse_filter": lambda: ix.set_sparse_filter(int(value)), "large_k": lambda: ix.set_large_k(bool(value)),
-         "bounce": lambda: ix.debug_set_compact_bounce(int(value))}[name]()
+         "bounce": lambda: ix.debug_set_compact_bounce(int(value)), "split": lambda: ix.set_split(int(value)),
+         "split_after": lambda: ix.debug_set_split_after(int(value))}[name]()
         self.settings[name] = int(value)
 
     def flush(self):
         self.ix.flush()
         self._after_write()
+
+    def layout(self):
+        """(layout, conversions so far) of the rows: DESIGN.md 4.3"""
+        return self.ix.layout()
+
+    def handed_over(self):
+        """did the last search hand a query to the f32 tier or the exact scan (they read f32 rows: a SPLIT store converts back)"""
+        st = self.ix.last_stats()
+        return bool(st["f32_tier_queries"] or st["exact_queries"])
 
     # -- reads
     def _masked(self, mask, call):
@@ -2790,3 +2804,373 @@ class GpuStoreAdapter(EngineErrors):
         out = [self._out(r) for r in self._read(lambda: self.store.search_distinct_batch(qs, k, StoreSim.GROUP_FIELD, flt_of(self.vdb, spec)))]
         self.seen["distinct"] += 1
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- the SPLIT row layout
+# after a run of eligible searches an index rewrites its rows in place into their bf16 pieces and low halves; the
+# filter pass and the four re-ranks read them as they lie, every other reader (rows_f32) and every mutation (rows_mut) converts
+# back first.  A reader that forgets raises nothing.  Three schedules of 75 000 rows with the shadow off (SPLIT_PINNED) interleave
+# all nine read kinds with every mutation; LayoutChecked wraps an adapter, follows the rule through every call (LayoutTracker over
+# split_schedule.Rule) and compares layout() = (layout, conversions so far) after EVERY step.  SplitRefIndex is the reference
+# adapter with that rule inside and three mutants of its own.
+from split_schedule import RUN as SPLIT_RUN, Rule as SplitRule, split_hi, split_join, split_lo
+
+LAYOUT_F32, LAYOUT_SPLIT = 0, 1
+SPLIT_ROWS = 75_000
+PROFILES["split64"] = dict(d=64, d2=64, zero=False, misfit=False)
+PROFILES["split40"] = dict(d=40, d2=40, zero=False, misfit=False)
+SPLIT_PINNED = (                                                     # name, seed, profile, metric, vdb_flat_set_split at the start, what
+    ("split-adaptive-euclid", 91, "split64", EUCLID, 1, "the adaptive rule with a run of 2: every f32 reader and every mutation starts the count again"),
+    ("split-mode2-cosine", 92, "split40", COSINE, 2, "d = 40 (a pitch of 64 floats), converted before every eligible search"),
+    ("split-off-then-on-dot", 93, "split64", DOT, 0, "mode 0 through all nine read kinds (never converts), then mode 2"),
+)
+SPLIT_MODES = {0: 0, 1: "adaptive", 2: 2}
+
+
+def split_schedule(seed, profile, metric, first_mode):
+    g = _Gen9(seed, profile, metric)
+    e, k, d = g.emit, g.k, g.p["d"]
+
+    def searches(m=SPLIT_RUN + 1):                                   # enough eligible searches in a row for either rule to convert
+        for _ in range(m):
+            e(("search", 8, 10, k(), None))
+
+    def nine():
+        e(("search", 8, 10, k(), None))
+        e(("search", 1, 113, k(), None))                             # the large-k re-rank (from 73 200 rows)
+        e(("masked", 8, 10, k(), ("host", k(), 0.5)))
+        e(("numeric", 8, 10, k(), ("numeric", "ge", k())))
+        e(("by_id", 8, 10, k(), False, None))
+        e(("recommend", 4, 10, k(), False, None))
+        e(("distinct", 4, 10, k(), None))
+        e(("grouped", 8, 10, k(), 3, "host", k()))
+        e(("range", 4, k(), 40, 256, None))
+        e(("set", "sparse_filter", 1))
+        e(("sparse", 8, 10, k(), ("host", k(), SPARSE_SHARE)))
+        e(("set", "sparse_filter", 0))
+    e(("set", "split", first_mode))
+    e(("set", "split_after", SPLIT_RUN))
+    g.bulk(900, d)
+    e(("codes", 0, 80_000, k(), 30))
+    e(("numbers", 0, 30, k()))
+    for n in (30_000, SPLIT_ROWS - 30_900):                          # growth across re-allocations, across the floor of 65 536 rows
+        g.bulk(n)
+        e(("search", 1, 10, k(), None))
+    if first_mode == 0:
+        nine()
+        e(("set", "split", 2))
+    searches()
+    nine()
+    # ---- add (staged while the rows are SPLIT under either rule), upsert, remove
+    searches()
+    e(("add", g.fresh_ids(1), k(), -1))
+    searches()
+    e(("recommend", 4, 10, k(), False, None))                        # (each of the two straight after a run of searches: over SPLIT rows
+    searches()                                                       # under the adaptive rule too)
+    e(("by_id", 8, 10, k(), False, None))
+    e(("upsert", g.live_id(), k(), -1))
+    searches()
+    e(("grouped", 8, 10, k(), 3, "host", k()))
+    e(("distinct", 4, 10, k(), None))
+    e(("remove", g.live_id()))
+    searches()
+    e(("range", 4, k(), 40, 256, None))
+    e(("masked", 8, 10, k(), ("host", k(), 0.5)))
+    # ---- compact; a shrinking compaction and a refill to the same row count (which re-allocates)
+    e(("remove_many", 200, k()))
+    e(("compact",))
+    searches()
+    nine()
+    n = g.m.n_rows()
+    e(("remove_many", 900, k()))
+    e(("compact_shrink",))
+    g.bulk(n - g.m.n_rows())
+    searches()
+    e(("by_id", 8, 10, k(), False, None))
+    e(("numeric", 8, 10, k(), ("numeric", "lt", k())))
+    # ---- below 65 536 rows and back
+    e(("remove_many", g.m.n_live() - 60_000, k()))
+    e(("compact",))
+    e(("search", 8, 10, k(), None))
+    e(("recommend", 4, 10, k(), False, None))
+    g.bulk(SPLIT_ROWS - g.m.n_rows())
+    searches()
+    # ---- a non-finite row arrives late and is removed: a tombstone still stored -- the conversion walks the rows, not the live bits
+    bad = g.fresh_ids(1)
+    e(("inf", bad, k()))
+    e(("remove", bad))
+    searches(SPLIT_RUN + 2)                                          # refused, and not tried again
+    e(("grouped", 8, 10, k(), 3, "host", k()))
+    e(("compact",))                                                  # the rows change: tried again, and this time it holds
+    searches()
+    nine()
+    searches()
+    return g.trace
+
+
+def split_pinned(name):
+    for n, seed, profile, metric, mode, _ in SPLIT_PINNED:
+        if n == name:
+            return split_schedule(seed, profile, metric, mode)
+    raise KeyError(name)
+
+
+class LayoutTracker:
+    """split_schedule.Rule driven by the calls of the adapter interface.  The facts a prediction may take from the read itself
+    (certification is data-dependent): whether the last search handed a query to the f32 tier or the exact scan, the stages of a
+    distinct read, the counters of a grouped read.  Holds for the schedules above: depths of at most 58 or above 112, fewer than
+    262 144 rows (one sample size), the sparse filter 0 or 1, no shadow, no automatic compaction."""
+
+    def __init__(self):
+        self.rule = SplitRule("adaptive", 0)
+        self.live, self.bad_live, self.settings = set(), set(), dict(split=1, sparse_filter=0)
+
+    def expect(self):
+        return self.rule.expect()
+
+    # -- mutations
+    def add(self, id, v):
+        self.add_bulk(np.asarray(v, dtype=F32)[None, :], [id])
+
+    def add_bulk(self, rows, ids):
+        ids = [int(i) for i in np.asarray(ids, dtype=U64)]
+        bad = [i for i, r in zip(ids, np.asarray(rows, dtype=F32)) if not np.isfinite(r).all()]
+        self.rule.add(len(ids), overwrites=len(self.live.intersection(ids)), bad=bool(bad))
+        self.live.update(ids)
+        self.bad_live.update(bad)
+
+    def remove(self, ids):
+        ids = {int(i) for i in np.atleast_1d(np.asarray(ids, dtype=U64))} & self.live
+        if ids:
+            self.rule.remove(len(ids))
+        self.live -= ids
+        self.bad_live -= ids
+        assert self.live, "a store emptied by removes starts over: not in these schedules"
+
+    def compact(self, shrink=False):
+        self.rule.compact(shrink, bad_left=bool(self.bad_live))
+
+    def set(self, name, value):
+        assert name not in ("shadow", "screen", "large_k", "sample_cache") and (name != "sparse_filter" or value in (0, 1)), (name, value)
+        self.settings[name] = int(value)
+        if name == "split":
+            self.rule.mode, self.rule.streak = SPLIT_MODES[int(value)], 0
+        if name == "split_after":
+            assert int(value) == SPLIT_RUN
+            self.rule.streak = 0
+
+    def flush(self):
+        self.rule.flush()
+
+    # -- reads
+    def _search(self, nq, k, masked, handed_over, by_id=False):
+        r = self.rule
+        r.flush()
+        if by_id:
+            r.reader()                                               # the gather / the fold reads the stored rows
+        if masked and self.settings["sparse_filter"]:
+            return r.reader()                                        # the sparse route: an exact scan of the eligible rows
+        assert k <= 58 or k > 112, k
+        if k > 112 and r.n >= r.floor and r.n < 240 * (k + 192):
+            return r.reader()                                        # large k below its row floor: the exact scan
+        r.search(nq, handed_over=handed_over)
+
+    @staticmethod
+    def _kmax(ks):
+        return int(ks) if np.isscalar(ks) else max(int(x) for x in ks)
+
+    def search(self, got, facts, q, ks, mask=None):
+        self._search(len(q), self._kmax(ks), mask is not None, facts["handed_over"])
+
+    def range(self, got, facts, q, radii, max_results, mask=None):
+        self.rule.flush()
+        self.rule.reader()
+
+    def by_id(self, got, facts, ids, ks, mask=None):
+        self._search(len(ids), self._kmax(ks) + 1, mask is not None, facts["handed_over"], by_id=True)
+
+    def recommend(self, got, facts, pos, neg, ks, mask=None):
+        m = max(len(p) + len(n) for p, n in zip(pos, neg))
+        self._search(len(pos), self._kmax(ks) + m, mask is not None, facts["handed_over"], by_id=True)
+
+    def distinct(self, got, facts, q, ks, mask=None):
+        a, b, c = got["stages"]
+        # stage A at depth 40; a query it leaves open goes on at depth 1024, which these row counts answer by the exact scan
+        self._search(len(q), 40, mask is not None, facts["handed_over"] or a < len(q))
+
+    def grouped(self, got, facts, q, ks, group_of, masks):
+        _, _, n_scan, n_over, n_none, _ = got["gstats"]
+        assert not n_over
+        self.rule.flush()
+        if n_scan:
+            self.rule.reader()                                       # the grouped scan reads f32 rows
+        if n_none:
+            self._search(n_none, self._kmax(ks), False, facts["handed_over"])
+
+
+TRACKED = ("add", "add_bulk", "remove", "compact", "set", "flush")
+TRACKED_READS = ("search", "range", "by_id", "recommend", "distinct", "grouped")
+
+
+class LayoutChecked:
+    """An adapter behind a LayoutTracker: every call goes through, and layout() must read what the rule predicts after it."""
+
+    def __init__(self, inner):
+        self.inner, self.tracker, self.steps = inner, LayoutTracker(), 0
+        self.vdb, self.sharded = getattr(inner, "vdb", None), False
+
+    def __getattr__(self, name):
+        call = getattr(self.inner, name)
+        if name not in TRACKED + TRACKED_READS:
+            return call
+
+        def tracked(*args):
+            got = call(*args)
+            if name in TRACKED:
+                getattr(self.tracker, name)(*args)
+            else:
+                getattr(self.tracker, name)(got, dict(handed_over=self.inner.handed_over()), *args)
+            self.steps += 1
+            seen, want = self.inner.layout(), self.tracker.expect()
+            if seen != want:
+                raise Mismatch(f"layout after {name} (call {self.steps}): {seen}, predicted {want}; rule {vars(self.tracker.rule)}")
+            return got
+        return tracked
+
+
+def garble_as_split_bytes(v, ld):
+    """a row's SPLIT bytes taken as ld floats: what a reader sees that forgets rows_f32()"""
+    bits = np.zeros(ld, dtype=np.uint32)
+    bits[:v.size] = np.asarray(v, dtype=F32).view(np.uint32)
+    return np.concatenate([split_hi(bits), split_lo(bits)]).view(np.uint32).view(F32)[:v.size].copy()
+
+
+def garble_as_joined_f32(v, ld):
+    """an f32 row written into SPLIT rows and then "converted back": its words joined as if they were the two planes"""
+    row = np.zeros(ld, dtype=F32)
+    row[:v.size] = v
+    w = row.view(np.uint16)
+    return split_join(w[:ld], w[ld:]).view(F32)[:v.size].copy()
+
+
+SPLIT_MUTANTS = ("gather_takes_bytes", "fold_takes_bytes", "append_into_split", "refusal_forgotten")
+
+
+class SplitRefIndex(RefIndex):
+    """The reference adapter with the layout rule inside (a LayoutTracker of its own: layout() is what the engine's would be).
+    mutant: the by-id gather / every example of a recommend fold but the first reads the bytes as they lie while the rows are SPLIT;
+    an append is written into SPLIT rows and the store then converted back; a refusal is forgotten after a search."""
+
+    def __init__(self, metric, mutant=None):
+        super().__init__(metric)
+        assert mutant in (None,) + SPLIT_MUTANTS
+        self.mutant, self.own, self.split_at_read, self.reading = mutant, LayoutTracker(), False, None
+
+    def layout(self):
+        return self.own.expect()
+
+    def handed_over(self):
+        return False
+
+    def knn(self, rows, ids, q, k):
+        try:
+            return super().knn(rows, ids, q, k)
+        except oracle.OracleError:                                   # (bytes taken as floats may hold a NaN: the engine would fail the search)
+            raise Predicted("NanDistance")
+
+    @property
+    def ld(self):
+        return (self.d + 31) // 32 * 32
+
+    def stored(self, rows, first):
+        if self.mutant == "append_into_split" and self.own.rule.layout == LAYOUT_SPLIT:
+            return np.stack([garble_as_joined_f32(r, (rows.shape[1] + 31) // 32 * 32) for r in rows])
+        return rows
+
+    def uploaded(self):
+        super().uploaded()
+        self.own.rule.flush()
+        self.split_at_read = self.own.rule.layout == LAYOUT_SPLIT     # what a gather that does not convert back would find
+
+    def example_of(self, id, position):
+        v = self.vector_of(id)
+        takes = (self.mutant == "gather_takes_bytes" and self.reading == "by_id") or \
+                (self.mutant == "fold_takes_bytes" and self.reading == "recommend" and position)
+        return garble_as_split_bytes(v, self.ld) if takes and self.split_at_read else v
+
+    def by_id(self, ids, ks, mask=None):
+        self.reading = "by_id"
+        if self.mutant != "gather_takes_bytes":
+            return self._read("by_id", ids, ks, mask)
+        ids = np.asarray(ids, dtype=U64)                             # RefIndex.by_id with the gather through example_of
+        self.refusal("by_id", ids)
+        self.uploaded()
+        rows, bids = self.block(mask)
+        out, struck, cut = [], 0, 0
+        for b, own in enumerate(ids):
+            kb = k_of(ks, b)
+            oi, od = self.knn(rows, bids, self.example_of(own, 0), kb + 1)
+            oi, od, hit, _cut = bd.strike(oi, od, own, kb)
+            struck, cut = struck + bool(hit), cut + bool(_cut)
+            out.append((oi, od.view(np.uint32)))
+        got = {"lists": out, "struck": struck, "cut": cut} if np.isscalar(ks) else {"lists": out}
+        self.own.by_id(got, dict(handed_over=False), ids, ks, mask)
+        return got
+
+    def _read(self, name, *args):
+        self.reading = name
+        got = getattr(RefIndex, name)(self, *args)
+        if name == "distinct":                                       # (the reference adapter names no stages: every query ends in stage A here or not)
+            got = dict(got, stages=self.model_stages(*args))
+        getattr(self.own, name)(got, dict(handed_over=False), *args)
+        if self.mutant == "refusal_forgotten":
+            self.own.rule.refused = False
+        return got
+
+    def model_stages(self, q, ks, mask=None):
+        rows, ids = self.block(mask)
+        a = 0
+        for b in range(len(q)):
+            rank = self.knn(rows, ids, q[b], len(rows))
+            a += dd.stage_of(rank, self.codes_seen(), k_of(ks, b), self.n_live()) == "A"
+        return [a, len(q) - a, 0]
+
+    def search(self, *a):
+        return self._read("search", *a)
+
+    def range(self, *a):
+        return self._read("range", *a)
+
+    def distinct(self, *a):
+        return self._read("distinct", *a)
+
+    def grouped(self, *a):
+        return self._read("grouped", *a)
+
+    def recommend(self, *a):
+        return self._read("recommend", *a)
+
+    # -- mutations
+    def add(self, id, v):
+        super().add(id, v)
+        self.own.add(id, v)
+
+    def add_bulk(self, rows, ids):
+        super().add_bulk(rows, ids)
+        self.own.add_bulk(rows, ids)
+
+    def remove(self, ids):
+        super().remove(ids)
+        self.own.remove(ids)
+
+    def compact(self, shrink=False):
+        out = super().compact(shrink)
+        self.own.compact(shrink)
+        return out
+
+    def set(self, name, value):
+        self.own.set(name, value)
+
+    def flush(self):
+        super().flush()
+        self.own.flush()

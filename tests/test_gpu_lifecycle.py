@@ -238,3 +238,33 @@ def test_store_lifecycle(vdb, name):
     assert seen["compactions"] > 0, seen
     assert all(kinds[(k, False)] > 0 for k in lc.STORE_READS), kinds
     assert any(e for (_, e) in kinds), kinds                                                   # a predicted error was met
+
+
+# ------------------------------------------------------------------ the SPLIT row layout (lifecycle.SPLIT_PINNED)
+SPLIT_NAMES = [p[0] for p in lc.SPLIT_PINNED]
+
+
+@pytest.mark.parametrize("name", SPLIT_NAMES)
+def test_split_lifecycle(vdb, name):
+    """75 000 rows with the shadow off, all nine read kinds between add, upsert, remove, compact, a shrinking compaction refilled
+    to the same row count, growth across re-allocations, a fall below 65 536 rows and back, a late non-finite row: every read
+    against the model, and layout() = (layout, conversions) against the rule of DESIGN 4.3 after EVERY call
+    (lifecycle.LayoutChecked; the only facts it takes from the engine are the read's own counters)."""
+    t = lc.split_pinned(name)
+    ad = lc.GpuIndexAdapter(vdb, t["metric"])
+    checked = lc.LayoutChecked(ad)
+    try:
+        lc.run(t, checked, expected=lc.slots(name, t))
+    finally:
+        ad.close()
+    rule, seen = checked.tracker.rule, ad.seen
+    print(name, vars(rule), dict(seen))
+    # conversions in both directions, a refusal, and a retry that holds: the schedule ends on SPLIT rows
+    assert rule.forward >= 5 and rule.back >= 5 and rule.refusals == 1 and rule.expect()[0] == lc.LAYOUT_SPLIT, vars(rule)
+    assert ad.ix.layout() == rule.expect()
+    assert seen["route_bf16"] >= 20 and seen["bf16_large_k"] >= 2 and seen["bf16_shadow_rows"] == 0, seen
+    assert seen["sparse_route"] >= 2 and seen["range_screened"] + seen["range_exact"] + seen["range_dense"] >= 12, seen
+    assert seen["distinct_a"] > 0 and seen["grouped_scan"] > 0 and seen["grouped_unfiltered"] > 0 and seen["recommend_examples"] > 0, seen
+    # (two re-allocations of a store that holds rows: 30 900 -> 75 000 and the refill after the shrinking compaction; the first
+    # upload of 30 900 staged rows allocates, it does not grow)
+    assert seen["numeric_compiles"] >= 3 and seen["grown"] >= 2 and seen["shrunk"] >= 1 and seen["compactions"] >= 4, seen

@@ -242,7 +242,7 @@ def test_wide_batches_on_the_screening_tier(vdb, family, metric):
 
 
 # ------------------------------------------------------------------ large k
-LARGE_K_CASES = [c for c in vf.CASES if c[0] in ("inf_tail", "overflow", "subnormal", "nan_hidden", "cos_den_zero", "tame")]
+LARGE_K_CASES = [c for c in vf.CASES if c[0] in ("inf_tail", "overflow", "bf16_edge", "subnormal", "nan_hidden", "cos_den_zero", "tame")]
 
 
 @pytest.mark.parametrize("family,metric", LARGE_K_CASES, ids=["%s-m%d" % c for c in LARGE_K_CASES])

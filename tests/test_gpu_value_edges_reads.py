@@ -405,7 +405,7 @@ def test_mmr(vdb, family, metric, shape):
     if failed:
         w1, g1 = mmr_round(vdb, ix, case, shape, qsel, 1, ver.MMR_M, 0.5, live, "plain")
         assert g1 is not None and ix.mmr_stats()[3] == 0
-    assert failed == ((family, metric) in (("inf_tail", vf.EUCLID), ("inf_tail", vf.DOT), ("overflow", vf.COSINE)))
+    assert failed == ((family, metric) in (("inf_tail", vf.EUCLID), ("inf_tail", vf.DOT), ("overflow", vf.COSINE), ("bf16_edge", vf.COSINE)))
     # under the half mask, with the compiled twin
     on, words, compiled = half_mask(vdb, n)
     want, got = mmr_round(vdb, ix, case, shape, qsel, ver.MMR_K, ver.MMR_M, 0.5, live & on, "half", stored=live, id_mask=words, mask_bits=n)

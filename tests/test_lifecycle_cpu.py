@@ -416,3 +416,52 @@ def test_a_failure_names_its_trace_and_shrinks():
         lc.run(small, lc.ByIdGathersOldRow(t["metric"]))
     lc.run(small, lc.RefIndex(t["metric"]))
     assert lc.shrink(literal, lambda: lc.RefIndex(t["metric"])) is None
+
+
+# ------------------------------------------------------------------ the SPLIT row layout (lifecycle.SPLIT_PINNED)
+SPLIT_NAMES = [p[0] for p in lc.SPLIT_PINNED]
+_SPLIT = {}
+
+
+def split_trace(name):
+    if name not in _SPLIT:
+        _SPLIT[name] = lc.split_pinned(name)
+    return _SPLIT[name]
+
+
+def test_the_split_schedules_do_not_move_the_others():
+    assert lc.pinned(NAMES[0]) == trace_of(NAMES[0]) and lc.split_pinned(SPLIT_NAMES[0]) == split_trace(SPLIT_NAMES[0])
+
+
+@pytest.mark.parametrize("name", SPLIT_NAMES)
+def test_split_reference_passes(name):
+    """the reference adapter with the layout rule inside, behind LayoutChecked: every read equals the model, the layouts agree
+    after every call, and the schedule holds what the issue asks of it"""
+    t = split_trace(name)
+    ad = lc.LayoutChecked(lc.SplitRefIndex(t["metric"]))
+    sizes = []
+    m = lc.run(t, ad, expected=lc.slots(name, t), on_read=lambda step, op, model, args, got: sizes.append(model.n_rows()))
+    rule = ad.tracker.rule
+    assert rule.forward >= 5 and rule.back >= 5 and rule.refusals == 1 and rule.expect()[0] == lc.LAYOUT_SPLIT, vars(rule)
+    kinds = Counter(op[0] for op in t["ops"])
+    assert all(kinds[r] >= 3 for r in lc.READS9), kinds
+    assert all(kinds[x] >= 1 for x in ("add", "upsert", "remove", "remove_many", "compact", "compact_shrink", "bulk", "inf")), kinds
+    assert max(sizes) >= 240 * (113 + 192) and min(s for s in sizes[8:]) < lc.BF16_MIN_ROWS <= sizes[-1] and len(t["ops"]) <= 130
+    assert ("set", "shadow", 1) not in t["ops"] and t["ops"][0][:2] == ("set", "split") and t["ops"][1] == ("set", "split_after", 2)
+    assert m.counts["doublings"] >= 3 and m.counts["shrinks"] >= 1
+
+
+@pytest.mark.parametrize("mutant", lc.SPLIT_MUTANTS)
+def test_split_mutant_is_caught(mutant):
+    """a by-id gather / a recommend fold that sees the bytes as they lie while the rows are SPLIT, an append written into SPLIT
+    rows and then converted back, a refusal forgotten after a search: each falls on every one of the three schedules"""
+    caught = {}
+    for name in SPLIT_NAMES:
+        t = split_trace(name)
+        try:
+            lc.run(t, lc.LayoutChecked(lc.SplitRefIndex(t["metric"], mutant=mutant)), expected=lc.slots(name, t))
+        except lc.Mismatch as e:
+            caught[name] = str(e).split("\n")[0]
+    print(mutant, caught)
+    assert set(caught) == set(SPLIT_NAMES), (mutant, caught)
+    assert all(("layout after" in v) == (mutant == "refusal_forgotten") for v in caught.values()), caught

@@ -18,7 +18,9 @@ def _shapes():
     L = load_package()._ffi.lib()
     out = [(name,) + s[:3] + (k,) for name, s in vf.SHAPES.items() for k in s[3]]
     n, d, nq, ks = vf.large_k_shape(L.vdb_flat_large_k_min_rows(vf.K_LARGE))
-    return out + [("large_k", n, d, nq, ks[0])]
+    out.append(("large_k", n, d, nq, ks[0]))
+    n, d, nq, ks = vf.large_k_split_shape(L.vdb_flat_large_k_min_rows(vf.K_LARGE))     # tests/test_gpu_value_edges_split.py
+    return out + [("large_k_split", n, d, nq, ks[0])]
 
 
 SHAPES = _shapes()
@@ -71,6 +73,61 @@ def claim_overflow(metric, rows, q, k, live):
             r = int(np.nonzero(big)[0][-1])
             assert np.isposinf(oracle.distance(metric, q[b], rows[r])) and np.isposinf(oracle.distance(metric, q[b], rows[1]))
         assert ids_decide(bits, k) or (metric == vf.EUCLID and b > 0)
+
+
+def split_hi(bits):
+    """the hi word of the SPLIT layout (csrc/row_split.h): the upper half plus bit 15, modulo 2^16"""
+    bits = np.asarray(bits, dtype=np.uint32)
+    return ((bits >> 16) + ((bits >> 15) & 1)) & 0xffff
+
+
+def bf16_rne(bits):
+    """the bf16 word of a finite f32 by round-to-nearest-even"""
+    bits = np.asarray(bits, dtype=np.uint64)
+    return ((bits + 0x7fff + ((bits >> 16) & 1)) >> 16) & 0xffff
+
+
+def claim_bf16_edge(metric, rows, q, k, live):
+    col = rows.view(np.uint32)[:, 0]
+    mag = col & 0x7fffffff
+    alive = live != 0
+    assert np.isfinite(rows).all() and np.isfinite(q).all() and (q[:, 0] > 0).all() and (q[:, 0] < 1).all()
+    for pat in vf.BF16_EDGE_BITS:                                             # every pattern in a live row, the large ones with both signs
+        assert (alive & (col == pat)).any() and (pat not in vf.BF16_EDGE_LARGE or (alive & (col == pat | 0x80000000)).any()), hex(pat)
+    large = np.isin(mag, vf.BF16_EDGE_LARGE)
+    assert not np.isin(rows.view(np.uint32)[:, 1:] & 0x7fffffff, vf.BF16_EDGE_LARGE).any()       # column 0 alone
+    special = np.isin(mag, vf.BF16_EDGE_BITS)
+    assert abs(int(special.sum()) - max(rows.shape[0] // 100, 160)) <= 1
+    assert ((rows.view(np.uint32)[special, 1:] & 0xffff) == 0x8000).all()      # ordinary ties everywhere else in a special row
+    top_row = alive & (col == vf.BF16_EDGE_LARGE[2])
+    for b in vf.checked_queries(q.shape[0]):
+        oi, od, bits = top(metric, rows, q[b], k, live)                       # (asserts that no distance is NaN)
+        at = oi.astype(np.int64)
+        if metric == vf.EUCLID:                                               # the square of a large element overflows: +inf away
+            assert np.isfinite(od).all() and not large[at].any()
+            assert all(np.isposinf(oracle.distance(metric, q[b], rows[r])) for r in np.nonzero(large)[0][:12])
+        elif metric == vf.DOT:                                                # finite products: +FLT_MAX first, one distance, ids decide
+            lead = alive & large & (rows[:, 0] > 0)
+            m, mc = min(k + 1, int(lead.sum())), min(k + 1, int(top_row.sum()))
+            assert np.isfinite(od).all() and (od[:m] < -1e38).all() and lead[at[:m]].all() and (od[m:] > -1e38).all()
+            assert len(set(bits[:mc].tolist())) == 1 and np.array_equal(oi[:mc], lowest_live(top_row, live, mc)) and int(oi[0]) == 1
+            assert int(top_row.sum()) > 12 and (mc < k + 1 or ids_decide(bits, k))
+        else:                                                                 # the row norm is inf, the dot finite: exactly 1.0
+            assert (od == 1.0).all() and np.array_equal(oi, lowest_live(large, live, k + 1)) and int(oi[0]) == 1 and ids_decide(bits, k)
+            assert np.isinf(oracle.norm(rows[1])) and np.isfinite(np.float32(rows[1, 0]) * q[b, 0])
+
+
+def test_bf16_edge_patterns_in_the_hi_plane():
+    """What the screening tier reads for each pattern of bf16_edge: the hi word of the SPLIT layout equals the round-to-nearest-even
+    bf16 word for all of them but the two ties, where it is the other neighbour; the tie below FLT_MAX and FLT_MAX itself -- finite
+    elements, which the forward conversion accepts -- read as the bf16 infinity in both."""
+    pats = np.array(vf.BF16_EDGE_BITS, dtype=np.uint32)
+    assert split_hi(pats).tolist() == [0x7f7f, 0x7f80, 0x7f80, 0x0000, 0x0001, 0x0080]
+    assert bf16_rne(pats).tolist() == [0x7f7f, 0x7f80, 0x7f80, 0x0000, 0x0000, 0x0080]
+    assert split_hi(pats | 0x80000000).tolist() == [0xff7f, 0xff80, 0xff80, 0x8000, 0x8001, 0x8080]
+    assert np.isfinite(pats.view(np.float32)).all() and ((pats & 0x7f800000) != 0x7f800000).all()
+    tie = np.uint32(0x3f808000)                                               # an ordinary tie: half up in magnitude against ties-to-even
+    assert split_hi(tie) == 0x3f81 and bf16_rne(tie) == 0x3f80
 
 
 def claim_subnormal(metric, rows, q, k, live):
@@ -181,7 +238,7 @@ def claim_tame(metric, rows, q, k, live):
 
 
 CLAIMS = {
-    "inf_tail": claim_inf_tail, "overflow": claim_overflow, "subnormal": claim_subnormal, "cos_den_tiny": claim_cos_den_tiny,
+    "inf_tail": claim_inf_tail, "overflow": claim_overflow, "bf16_edge": claim_bf16_edge, "subnormal": claim_subnormal, "cos_den_tiny": claim_cos_den_tiny,
     "cos_den_clamp": claim_cos_den_clamp, "dot_zero": claim_dot_zero, "tame": claim_tame,
     "cos_den_zero": lambda *a: claim_hidden_error(*a, code=oracle.ERR_INVALID_VECTOR),
     "nan_hidden": lambda *a: claim_hidden_error(*a, code=oracle.ERR_NAN),
@@ -309,6 +366,9 @@ def test_by_id_which_stored_rows_the_oracle_answers_as_queries(case, shape):
     elif (family, metric) == ("overflow", vf.COSINE):              # a row whose norm is inf: inf / inf against itself and its like
         big = {int(r) for r in ids if np.isinf(oracle.norm(rows[r]))}
         assert big and big <= refused and 12 <= len(refused) <= 20 and len(good) >= 30
+    elif (family, metric) == ("bf16_edge", vf.COSINE):             # likewise, and only there: every other row stays below 1 in column 0
+        big = {int(r) for r in ids if np.isinf(oracle.norm(rows[r]))}
+        assert {1, 3, 4, 6, 7} <= big and refused == big and len(good) >= 40
     else:
         assert not refused, bad
     if family == "inf_tail" and kw and metric == vf.DOT:
@@ -443,7 +503,7 @@ def test_row_requests_cover_the_lengths_and_both_outcomes():
             refused[name] = len(bad)
             if case[0] == "inf_tail" and not case[2]:
                 assert len(bad) == 12 and all(e == "NanDistance" for _, e in bad)
-            elif (case[0], case[1]) in (("overflow", vf.COSINE), ("overflow", vf.DOT)) or case[0] == "inf_tail":
+            elif (case[0], case[1]) in (("overflow", vf.COSINE), ("overflow", vf.DOT), ("bf16_edge", vf.COSINE)) or case[0] == "inf_tail":
                 assert 1 <= len(good) and all(e == "NanDistance" for _, e in bad)
             elif case[0] == "cos_den_clamp":                       # multiples of one direction can cancel exactly: the all-zero fold
                 assert len(bad) <= 2 and all(e == "InvalidVector" for _, e in bad)
@@ -492,7 +552,7 @@ def test_mmr_outcome_classes_are_the_pinned_ones():
     tests/value_edge_reads.py from the model)."""
     got, pinned = ver.mmr_classes(), ver.golden_mmr_classes()
     assert got == pinned, [k for k in got if got[k] != pinned.get(k)]
-    allowed = {"inf_tail-m0", "inf_tail-m2", "overflow-m1"}
+    allowed = {"inf_tail-m0", "inf_tail-m2", "overflow-m1", "bf16_edge-m1"}
     errors = {k.split("/")[0] for k, v in got.items() if any(c["nan_pair"] for c in v)}
     assert errors == allowed
     for name in allowed:                                           # ... and there EVERY checked query evaluates one

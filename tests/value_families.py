@@ -15,6 +15,13 @@ mask always excludes (masked_out) serve all of them: the lowest ids of a tie gro
             tame query's top-k) and for EVERY row under query 0: one tie group, ids decide.  Dot (all signs equal where it
             counts): -inf first, ids decide.  Cosine: the row norm is inf and the dot finite, sim = 0, the distance exactly
             1.0; the tame rows point away from the queries (distance > 1), so the top-k is the 1.0 group, ids decide.
+  bf16_edge (all metrics)   finite elements whose bf16 piece is not: about 1 % of the rows (at least 160) hold in column 0 one of
+            +-0x7f7f7fff (the bf16 piece stays finite), +-0x7f7f8000 (the tie) and +-0x7f7fffff (both round to the bf16 infinity,
+            by round-to-nearest-even and in the hi word of the SPLIT layout alike), or 0x00007fff, 0x00008000, 0x007f8000 (the bf16
+            piece is 0, the smallest subnormal, the smallest normal number); their other elements are ordinary ties.  Euclid: such a
+            row is +inf away (the square overflows), the top-k is tame.  Dot: the products stay finite, the rows with +FLT_MAX lead
+            with one distance near -2.5e38, ids decide, then the two patterns next to the tie.  Cosine: the row norm is inf and the
+            dot finite, the distance exactly 1.0, the tame rows point away: the 1.0 group, ids decide.  No NaN, no error.
   subnormal (Euclid, Dot)   Euclid: half the rows are small integers times 1e-23, half gaussian (times 3).  Even queries are tiny too:
             sums of squares are 0 or subnormal (the square root of a subnormal is a small normal number), many exact 0.0.
             Odd queries are gaussian: q - x == q for every tiny row, one tie group of n / 2 rows at the normal distance
@@ -139,6 +146,40 @@ def overflow(rng, n, d, nq, metric):
             rows[:, :4] = np.abs(rows[:, :4])          # row against row (a graph build) too: no +inf and -inf in one fold
         else:                                          # every row is tame there: every difference squares to inf
             q[0, d - 4:] = rng.uniform(2.5e19, 3.5e19, 4).astype(F32)
+    return rows, q
+
+
+# the magnitudes bf16_edge puts into column 0, as f32 bit patterns, and what the hi word of the SPLIT layout (upper half + bit 15)
+# and round-to-nearest-even make of each
+BF16_EDGE_BITS = (0x7f7f7fff,                                      # the last pattern below the tie: hi = 0x7f7f, finite
+                  0x7f7f8000,                                      # the tie: hi = 0x7f80, the bf16 infinity, for a finite element
+                  0x7f7fffff,                                      # FLT_MAX: hi = 0x7f80
+                  0x00007fff,                                      # a subnormal below half the smallest bf16 subnormal: hi = 0
+                  0x00008000,                                      # the tie above it: hi = 0x0001, the smallest bf16 subnormal
+                  0x007f8000)                                      # the largest f32 subnormals round up to hi = 0x0080, a normal number
+BF16_EDGE_LARGE = BF16_EDGE_BITS[:3]
+
+
+def bf16_edge(rng, n, d, nq, metric):
+    """Finite elements at the two ends of what a bf16 word can hold.  About 1 % of the rows (at least 160, rows 0 .. 7 among them)
+    are special: column 0 holds one of BF16_EDGE_BITS -- the three large ones with both signs, nine patterns in turn, rows 1, 3,
+    4, 6 and 7 all +FLT_MAX -- and every other element of a special row is an ordinary tie (low half 0x8000).  Only column 0 is
+    large and the queries are positive and below 1 there, so a product with it stays finite and no fold meets inf - inf."""
+    assert d >= 8
+    rows, q = _gauss(rng, n, d), _gauss(rng, nq, d)
+    if metric == COSINE:                               # tame rows point away from every query: distance > 1 (as in `overflow`)
+        rows, q = -np.abs(rows) - F32(0.1), np.abs(q) + F32(0.1)
+        rows[:, 0] = -rng.uniform(0.1, 0.9, n).astype(F32)         # ... and stay below 1 in column 0: a stored row that becomes a
+    sp = _spread(rng, n, _n_special(n))                            #     query has a finite product with every large element
+    bits = rows.view(np.uint32)
+    ties = (bits[sp] & np.uint32(0xffff0000)) | np.uint32(0x8000)
+    a, b, c = (np.uint32(x) for x in BF16_EDGE_LARGE)
+    neg = np.uint32(0x80000000)
+    turn = np.array([a, a | neg, b, b | neg, c, c | neg] + list(BF16_EDGE_BITS[3:]), dtype=np.uint32)
+    ties[:, 0] = turn[np.arange(sp.size) % turn.size]
+    ties[:8, 0] = [a, c, b, c, c, c | neg, c, c]
+    bits[sp] = ties
+    q[:, 0] = rng.uniform(0.25, 0.5, nq).astype(F32) if metric == COSINE else rng.uniform(0.5, 1.0, nq).astype(F32)
     return rows, q
 
 
@@ -272,6 +313,7 @@ ALL = (EUCLID, COSINE, DOT)
 FAMILIES = {                                                       # name: (generator, metrics, the oracle's error while HIDDEN is alive)
     "inf_tail": (inf_tail, (EUCLID, DOT), None),
     "overflow": (overflow, ALL, None),
+    "bf16_edge": (bf16_edge, ALL, None),
     "subnormal": (subnormal, (EUCLID, DOT), None),
     "cos_den_tiny": (cos_den_tiny, (COSINE,), None),
     "cos_den_clamp": (cos_den_clamp, (COSINE,), None),
@@ -331,6 +373,12 @@ SHAPES = {
 def large_k_shape(min_rows):
     """min_rows = vdb_flat_large_k_min_rows(K_LARGE), rounded up to whole 512-row blocks."""
     return ((int(min_rows) + 511) // 512 * 512, 32, 8, (K_LARGE,))
+
+
+def large_k_split_shape(min_rows):
+    """the large-k shape at d = 64: a row pitch of 32 floats cannot take the SPLIT layout (ld % 64), one of 64 can"""
+    n, _, nq, ks = large_k_shape(min_rows)
+    return (n, 64, nq, ks)
 
 
 def checked_queries(nq):

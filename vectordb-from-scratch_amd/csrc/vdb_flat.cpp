@@ -1674,10 +1674,12 @@ int vdb_flat_layout(vdb_flat_index* ix, uint64_t out[2]) {
     return guarded([&]() -> int {
     if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
     if (ix->multi) {
+        std::mutex m;                                               // (the shards answer on their own threads)
         uint64_t all = 1, conv = 0;
         int rc = multi_for_each(ix, [&](vdb_flat_index* c) {
             uint64_t o[2] = {0, 0};
             int r = vdb_flat_layout(c, o);
+            std::lock_guard<std::mutex> g(m);
             all &= o[0]; conv += o[1];
             return r;
         });
