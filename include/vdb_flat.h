@@ -810,11 +810,23 @@ int vdb_flat_set_tiers(vdb_flat_index *h, unsigned flags);
  *
  * vdb_flat_debug_screen_scores: runs query preparation and the PRODUCTION filter kernel over every live row with
  * thresholds that let everything pass, and returns the ranking score of every (query, row) pair:
- *   out_scores [nq][rows uploaded] f32 (the NaN pattern 0xffffffff = no key: tombstoned row); nq <= 256;
+ *   out_scores [nq][rows uploaded] f32 (the NaN pattern 0xffffffff = no key: tombstoned row); nq <= 256 (512 with VDB_DEBUG_SCORES_WIDE);
  *   raw = 0: the scores the tier ranks by (Dot / Euclid: lower-bound scores, score - g_q * margin_row);
  *   raw = 1: the plain scores fma(acc, alpha, beta) (under Dot: -acc, the raw MFMA accumulator);
  *   raw = 2: the f32 MFMA TIER's scores (v_mfma_f32_32x32x2_f32; dense_scores_kernel over every row, bit-identical to the
  *            fused f32 kernel's); a following cert_probe then evaluates the f32 tier's certificate (eps_coef only);
+ *   raw | VDB_DEBUG_SCORES_SPLIT (with raw 0 or 1): the scores a search over SPLIT rows ranks by.  An F32 store is converted first
+ *            (whatever vdb_flat_set_split says; the adaptive run of mode 1 is neither fed nor reset; vdb_flat_layout counts the
+ *            conversion) and stays SPLIT; the filter pass reads the store as it lies.  VDB_ERR_INVALID_ARGUMENT, the rows left as
+ *            they were, when the store cannot be SPLIT (pitch not a multiple of 64 or above 16384, no rows), when the index keeps
+ *            a usable bf16 shadow (the filter pass would read that), or with raw 2 (the f32 tier reads f32 rows).  Rows with a
+ *            non-finite element: refused as well, after the one attempt a search would make (forward, found out, straight back).
+ *            Without the bit a SPLIT store is converted back first;
+ *   raw | VDB_DEBUG_SCORES_WIDE (with raw 0 or 1): the WIDE filter kernel (512 queries per fetch of the rows, batches above 256
+ *            queries) over f32 rows, launched as a search launches it: 256 < nq <= 512, the two 256-query blocks' pools turned
+ *            into their halves of the dump.  VDB_ERR_INVALID_ARGUMENT with nq <= 256 (no search runs it there), with a usable
+ *            shadow, with raw 2 or together with VDB_DEBUG_SCORES_SPLIT; VDB_ERR_DEVICE if a sub-pool counted more keys than it
+ *            holds (the dump would have holes);
  *   out_qinfo [nq][4]: exact-order |q|, the bound on |q - bf16(q)|, g_q, 0;
  *   out_consts [8]: eps_coef, c_acc, kappa, max |d|, max |d - bf16(d)|, max |d - bf16(d)|/|d|, 1 if lower-bound scores, ld.
  * vdb_flat_debug_rows: number of device rows.  vdb_flat_debug_row_info: out [rows][4] = exact-order |d|, alpha, beta, margin (0 under Cosine).
@@ -822,6 +834,8 @@ int vdb_flat_set_tiers(vdb_flat_index *h, unsigned flags);
  *   qi[i] of the last debug_screen_scores call, unexamined-row score bound T[i] and k-th exact distance ek[i].
  *   Soundness means: probe(T = score of row r, ek = exact distance of row r) is 0 for EVERY pair.
  */
+#define VDB_DEBUG_SCORES_SPLIT 4 /* OR-ed into raw: over SPLIT rows */
+#define VDB_DEBUG_SCORES_WIDE 8  /* OR-ed into raw: the 512-query kernel */
 int vdb_flat_debug_screen_scores(vdb_flat_index *h, const float *queries, size_t nq, size_t dim, int raw,
                                  float *out_scores, float *out_qinfo, double *out_consts);
 size_t vdb_flat_debug_rows(const vdb_flat_index *h); /* device rows incl. tombstoned ones (row i = i-th row added since the last reset or vdb_flat_compact: a compaction renumbers the rows) */

@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 import oracle
+from certificate_data import bf16_rne, exact_distances, make_case
 from conftest import ROOT, load_package
 
 pytestmark = pytest.mark.gpu
@@ -40,82 +41,36 @@ def vdb():
             json.dump(MARGINS, f, indent=1, sort_keys=True)
 
 
-def bf16_rne(x):
-    """RNE rounding of f32 to bf16 (what v_cvt_pk_bf16_f32 keeps), as f32."""
-    b = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
-    r = ((b + 0x7FFF + ((b >> 16) & 1)) >> 16) << 16
-    return (r & 0xFFFFFFFF).astype(np.uint32).view(np.float32).reshape(np.shape(x))
-
-
-def make_case(kind, metric, rng):
-    """(rows, queries): adversarial for the error bound."""
-    if kind == "cancel":
-        # heavy cancellation: alternating signs, every dot product is a difference of two large nearly equal sums
-        n, d, nq = 66_000, 96, 48
-        base = rng.random((n, d), dtype=np.float32) + 0.5
-        sign = np.where(np.arange(d) % 2 == 0, 1.0, -1.0).astype(np.float32)
-        rows = base * sign
-        q = (rng.random((nq, d), dtype=np.float32) + 0.5) * sign * np.where(rng.random((nq, 1)) < 0.5, 1, -1).astype(np.float32)
-        q[: nq // 2] = np.abs(q[: nq // 2])                      # these cancel against the rows' signs
-    elif kind == "scales":
-        # magnitudes from 1e-21 to 1e+17 between rows AND inside a row (1e18 squared times the dimension overflows f32)
-        n, d, nq = 66_100, 64, 48
-        top = 17.0                                               # |d|^2 (and Euclid's |d|^2 + 2|q||d|) must stay finite in f32
-        rexp = rng.uniform(-18, top, (n, 1))
-        rows = (rng.standard_normal((n, d)) * 10.0 ** (rexp + rng.uniform(-3, 0, (n, d)))).astype(np.float32)
-        qexp = rng.uniform(-18, top, (nq, 1))
-        q = (rng.standard_normal((nq, d)) * 10.0 ** (qexp + rng.uniform(-3, 0, (nq, d)))).astype(np.float32)
-    elif kind == "dim16384":
-        n, d, nq = 1_500, 16384, 8
-        rows = rng.standard_normal((n, d)).astype(np.float32)
-        q = rng.standard_normal((nq, d)).astype(np.float32)
-        q[0] = rows[7] + 1e-4 * rng.standard_normal(d).astype(np.float32)
-    elif kind == "bf16ties":
-        # clusters whose bf16 images collide: perturbations far below the bf16 resolution of the values
-        n, d, nq = 65_800, 128, 32
-        centres = rng.standard_normal((n // 200 + 1, d)).astype(np.float32)
-        rows = (centres[np.arange(n) // 200] * (1.0 + 2e-5 * rng.standard_normal((n, d)))).astype(np.float32)
-        q = (centres[rng.integers(0, centres.shape[0], nq)] * (1.0 + 1e-5 * rng.standard_normal((nq, d)))).astype(np.float32)
-    elif kind == "subnormal":
-        # f32 subnormals (below 1.18e-38) and values whose products underflow
-        n, d, nq = 65_700, 40, 24
-        rows = (rng.standard_normal((n, d)) * 10.0 ** rng.uniform(-41, -17, (n, 1))).astype(np.float32)
-        q = (rng.standard_normal((nq, d)) * 10.0 ** rng.uniform(-24, -15, (nq, 1))).astype(np.float32)
-        q[::2] = (rng.standard_normal((nq // 2, d)) * 10.0 ** rng.uniform(-6, 2, (nq // 2, 1))).astype(np.float32)   # ordinary queries against tiny rows
-        rows[:8] = (rng.standard_normal((8, d)) * 1e-3).astype(np.float32)   # a few ordinary rows keep Cosine defined
-    else:
-        raise ValueError(kind)
-    if metric == 1:
-        rows[np.linalg.norm(rows.astype(np.float64), axis=1) == 0] = 1.0
-        bad = ~np.isfinite(np.linalg.norm(rows.astype(np.float64), axis=1).astype(np.float32)) | \
-            (np.sqrt((rows.astype(np.float32) ** 2).sum(1)) == 0)
-        rows[bad] = 1.0                                         # a zero (or f32-underflowing) norm fails every Cosine search
-        qb = np.sqrt((q.astype(np.float32) ** 2).sum(1)) == 0
-        q[qb] = 1.0
-    return rows, q
-
-
-def exact_distances(metric, rows, q):
-    """Oracle distances of every row (f32 bits of the reference's arithmetic), as [n] f32, via one full-k search."""
-    n = rows.shape[0]
-    ids, d = oracle.flat_search(metric, rows, q, n)
-    out = np.empty(n, dtype=np.float32)
-    out[ids.astype(np.int64)] = d
-    return out
-
-
 @pytest.mark.parametrize("kind", ["cancel", "scales", "dim16384", "bf16ties", "subnormal"])
 @pytest.mark.parametrize("metric", [0, 1, 2])
 def test_score_error_stays_inside_the_certified_bound(vdb, metric, kind):
     rng = np.random.default_rng(zlib.crc32(f"{metric}/{kind}".encode()))
     rows, q = make_case(kind, metric, rng)
-    n, dim = rows.shape
-    nq = q.shape[0]
     ix = vdb.GpuFlatIndex(vdb.DistanceMetric(metric), keep_host_copy=False)
     ix.add_bulk(rows)
-    s_raw, qinfo, c = ix.debug_screen_scores(q, raw=True)
-    s_lb, qinfo2, c2 = ix.debug_screen_scores(q, raw=False)                      # leaves the prepared queries for the probes
+    bound_checks(ix, metric, kind, rows, q, f"{['euclid', 'cosine', 'dot'][metric]}/{kind}")
+
+
+def bound_checks(ix, metric, kind, rows, q, key, split=False, wide=False, round_rows=bf16_rne, dist_of=None, live=None):
+    """Checks (A), (B) and (C) of this file's docstring on the scores of one dump, recorded under MARGINS[key]; returns
+    (raw scores, lower-bound scores).  split / wide: the dump's kernel (debug_screen_scores); round_rows: the rounding that
+    kernel reads the rows in ((C)'s operands; the queries are RNE everywhere); dist_of(b): query b's oracle distances, for
+    callers that share them between dumps; live: bool [n], the rows that are not tombstoned (default: all)."""
+    n, dim = rows.shape
+    nq = q.shape[0]
+    if dist_of is None:
+        dist_of = lambda b, all_rows=rows: exact_distances(metric, all_rows, q[b])
+    s_raw, qinfo, c = ix.debug_screen_scores(q, raw=True, split=split, wide=wide)
+    s_lb, qinfo2, c2 = ix.debug_screen_scores(q, raw=False, split=split, wide=wide)   # leaves the prepared queries for the probes
+    if live is not None:                               # a tombstone has no key: checked, then left out of everything below
+        assert np.isnan(s_raw[:, ~live]).all() and np.isnan(s_lb[:, ~live]).all(), "a tombstoned row got a key"
+        full_raw, full_lb = s_raw, s_lb
+        rows, s_raw, s_lb = rows[live], s_raw[:, live], s_lb[:, live]
+        n, dist_all = rows.shape[0], dist_of
+        dist_of = lambda b: dist_all(b)[live]
     info = ix.debug_row_info().astype(np.float64)
+    if live is not None:
+        info = info[live]
     nd, margin = info[:, 0], info[:, 3]
     assert s_raw.shape == (nq, n) and np.array_equal(qinfo, qinfo2)
     assert c2["lower_bound_scores"] == (0.0 if metric == 1 else 1.0)
@@ -127,9 +82,9 @@ def test_score_error_stays_inside_the_certified_bound(vdb, metric, kind):
     TINY = 2.0 ** -40
     nd_pos_min = float(nd[nd > 0].min())
     uncertifiable = 0
-    D16 = bf16_rne(q).astype(np.float64) @ bf16_rne(rows).astype(np.float64).T   # [nq, n]
+    D16 = bf16_rne(q).astype(np.float64) @ round_rows(rows).astype(np.float64).T if metric == 2 else None   # [nq, n]
     for b in range(nq):
-        dist = exact_distances(metric, rows, q[b])
+        dist = dist_of(b)
         assert np.isfinite(dist).all(), "test data must give finite distances"
         qn, eq, g = (float(x) for x in qinfo[b, :3])
         # ---- (A) the production certification function on (own score, own distance)
@@ -169,13 +124,14 @@ def test_score_error_stays_inside_the_certified_bound(vdb, metric, kind):
             den = c_acc * qn_true[b] * nd_true + floor          # (products that underflow f32 are covered by the absolute floor)
             okc = den > 0
             worst["C_ratio"] = max(worst["C_ratio"], float(np.max(np.abs(acc - D16[b])[okc] / den[okc])))
-    MARGINS[f"{['euclid', 'cosine', 'dot'][metric]}/{kind}"] = {**worst, "queries_outside_the_certifiable_domain": uncertifiable, "rows": n, "dim": dim, "queries": nq, "eps_coef": eps, "c_acc": c_acc}
+    MARGINS[key] = {**worst, "queries_outside_the_certifiable_domain": uncertifiable, "rows": n, "dim": dim, "queries": nq, "eps_coef": eps, "c_acc": c_acc}
     print(f"\n[certificate] metric={metric} {kind}: worst error/budget = {worst['B_ratio']:.4f}"
           + (f", worst MFMA accumulation error / (c_acc |q||d|) = {worst['C_ratio']:.4f}" if metric == 2 else ""))
     if kind in ("cancel", "dim16384", "bf16ties"):
         assert uncertifiable == 0
     assert worst["B_ratio"] <= 1.0, worst
     assert worst["C_ratio"] <= 1.0, worst
+    return (full_raw, full_lb) if live is not None else (s_raw, s_lb)
 
 
 @pytest.mark.parametrize("kind", ["cancel", "scales", "bf16ties"])

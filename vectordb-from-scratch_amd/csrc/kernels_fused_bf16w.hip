@@ -13,9 +13,10 @@
 //
 // The 512 queries are two consecutive 256-query blocks of the search (query_prep's image layout is [block][K stage][256 x 64 B],
 // so a wave's query piece is still 1 KB of contiguous memory); their candidate pools are the two blocks' ordinary
-// workgroup-major pools (FusedBf16Params::pool_block_stride), of which this kernel fills sub-pools 0 and 1 (lane halves) and
-// zeroes the counts of 2 and 3, so the select's gather, the re-rank and everything downstream are the 256-query code unchanged.
-// Scores are bit-identical to the other filter kernels' (same operands, same MFMA order per accumulator).
+// workgroup-major pools (FusedBf16Params::pool_block_stride), of which this kernel fills all four sub-pools (r = 2 * row half +
+// lane half, 32 rows of a 128-row tile each), so the select's gather, the re-rank and everything downstream are the 256-query
+// code unchanged.  Scores are bit-identical to the other filter kernels' (same operands, same MFMA order per accumulator):
+// tests/test_gpu_certificate_layouts.py compares every (query, row) score through vdb_flat_debug_screen_scores.
 #include "fused_bf16_common.h"
 
 namespace vdb {

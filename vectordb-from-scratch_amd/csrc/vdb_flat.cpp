@@ -1409,7 +1409,13 @@ int vdb_flat_debug_screen_scores(vdb_flat_index* ix, const float* queries, size_
     return guarded([&]() -> int {
     if (ix && ix->multi) return refuse_multi("vdb_flat_debug_screen_scores");
     if (!ix || !queries || !out_scores || !nq) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
-    if (nq > SUPER) return fail(VDB_ERR_INVALID_ARGUMENT, "at most %u queries per call", SUPER);
+    if (raw < 0 || (raw & ~(3 | VDB_DEBUG_SCORES_SPLIT | VDB_DEBUG_SCORES_WIDE))) return fail(VDB_ERR_INVALID_ARGUMENT, "unknown bits in raw");
+    const bool over_split = (raw & VDB_DEBUG_SCORES_SPLIT) != 0, wide = (raw & VDB_DEBUG_SCORES_WIDE) != 0;
+    raw &= 3;
+    if (over_split && wide) return fail(VDB_ERR_INVALID_ARGUMENT, "the wide kernel reads f32 rows: not over SPLIT rows");
+    if ((over_split || wide) && raw == 2) return fail(VDB_ERR_INVALID_ARGUMENT, "the f32 tier reads f32 rows and has one kernel");
+    if (wide && nq <= SUPER) return fail(VDB_ERR_INVALID_ARGUMENT, "the wide kernel serves batches above %u queries only", SUPER);
+    if (nq > (wide ? 2 * SUPER : SUPER)) return fail(VDB_ERR_INVALID_ARGUMENT, "at most %u queries per call", wide ? 2 * SUPER : SUPER);
     std::lock_guard<std::mutex> g(ix->mu);
     if (in_flight(ix)) return refuse_in_flight();
     int rc;
@@ -1419,25 +1425,41 @@ int vdb_flat_debug_screen_scores(vdb_flat_index* ix, const float* queries, size_
     if (!n) return fail(VDB_ERR_INVALID_ARGUMENT, "empty index");
     if (ix->dim != dim) return fail_dim(dim, ix->dim);
     if (!ix->misfits.empty()) return fail(VDB_ERR_INVALID_ARGUMENT, "rows of another dimension are stored");
+    // what the two kernels need, asked BEFORE anything touches the rows: a refused call leaves them in the layout they had
+    if ((over_split || wide) && shadow_usable(ix)) return fail(VDB_ERR_INVALID_ARGUMENT, "the filter pass of this index runs over its bf16 shadow");
+    if (over_split && (ld % 64 != 0 || ld > 16384)) return fail(VDB_ERR_INVALID_ARGUMENT, "rows of pitch %u cannot be SPLIT", ld);
+    if (over_split && !ix->d_rows_store) return fail(VDB_ERR_INVALID_ARGUMENT, "empty store");
+    if (over_split && ix->split_refused) return fail(VDB_ERR_INVALID_ARGUMENT, "the rows hold a non-finite element and stay F32");
     hipStream_t s = ix->stream;
-    const uint32_t tile = vdb::fused_bf16_tile_rows();
+    // the dense dump needs every row of a workgroup's range in its sub-pools (none "counted, not stored"): a sub-pool takes a
+    // quarter of a 256-row tile; of the wide kernel's 128-row tile a quarter as well (32 rows) -- sized here for 64, a whole row
+    // half, which holds however the kernel deals a row half to its two lane halves; the counts are checked after the launch
+    const uint32_t tile = wide ? vdb::fused_bf16w_tile_rows() : vdb::fused_bf16_tile_rows();
     const uint32_t nblk = (n + tile - 1) / tile;
     const uint32_t n_wg = std::min<uint32_t>((uint32_t)ix->n_cu, nblk);
     const uint32_t n_sub = vdb::fused_bf16_subpools_per_query(n_wg);
-    const uint32_t capl = 64u * ((nblk + n_wg - 1) / n_wg);            // every row of a workgroup's range fits its sub-pools
-    const size_t pool_keys = (size_t)SUPER * n_sub * capl;
+    const uint32_t capl = 64u * ((nblk + n_wg - 1) / n_wg);
+    const uint32_t n_blocks = wide ? 2u : 1u, nqp = n_blocks * SUPER;
+    const size_t pool_block = (size_t)SUPER * n_sub * capl, cnt_block = (size_t)SUPER * n_sub;   // the production strides (pass_bf16)
+    const size_t pool_keys = n_blocks * pool_block;
     if (pool_keys * 8 > ((size_t)6 << 30)) return fail(VDB_ERR_INVALID_ARGUMENT, "index too large for the score dump");
     if ((rc = ix->cur->w_qin.ensure(nq * dim))) return rc;
-    if ((rc = ix->cur->w_qp.ensure((size_t)SUPER * ld))) return rc;
-    if ((rc = ix->cur->w_qnorm.ensure(SUPER))) return rc;
-    if ((rc = ix->cur->w_thr.ensure(SUPER))) return rc;
-    if ((rc = ix->cur->w_qb.ensure((size_t)SUPER * ld))) return rc;
-    if ((rc = ix->cur->w_qerr.ensure(SUPER))) return rc;
-    if ((rc = ix->cur->w_qg.ensure(SUPER))) return rc;
-    if ((rc = ix->cur->w_flags.ensure(4 + 3 * (size_t)SUPER))) return rc;
+    if ((rc = ix->cur->w_qp.ensure((size_t)nqp * ld))) return rc;
+    if ((rc = ix->cur->w_qnorm.ensure(nqp))) return rc;
+    if ((rc = ix->cur->w_thr.ensure(nqp))) return rc;
+    if ((rc = ix->cur->w_qb.ensure((size_t)nqp * ld))) return rc;
+    if ((rc = ix->cur->w_qerr.ensure(nqp))) return rc;
+    if ((rc = ix->cur->w_qg.ensure(nqp))) return rc;
+    if ((rc = ix->cur->w_flags.ensure(4 + 3 * (size_t)nqp))) return rc;
     if ((rc = ix->cur->w_pool.ensure(pool_keys))) return rc;
-    if ((rc = ix->cur->w_subcnt.ensure((size_t)SUPER * n_sub))) return rc;
+    if ((rc = ix->cur->w_subcnt.ensure(n_blocks * cnt_block))) return rc;
     if ((rc = ix->cur->w_dbg.ensure(nq * (size_t)n))) return rc;
+    // raw | VDB_DEBUG_SCORES_SPLIT: the store goes SPLIT (whatever split_mode says; the adaptive run is neither fed nor reset)
+    // and stays so.  A non-finite element sends it straight back, as in a search (rows_to_split), and the call is refused.
+    if (over_split) {
+        if ((rc = rows_to_split(ix))) return rc;
+        if (ix->layout != vdb::LAYOUT_SPLIT) return fail(VDB_ERR_INVALID_ARGUMENT, "the rows hold a non-finite element and stay F32");
+    }
     ix->cur->status_dirty = true;
     HIP_TRY(hipMemsetAsync(ix->cur->w_flags.p, 0, 16, s));
     HIP_TRY(hipMemcpyAsync(ix->cur->w_qin.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
@@ -1478,7 +1500,7 @@ int vdb_flat_debug_screen_scores(vdb_flat_index* ix, const float* queries, size_
         return VDB_OK;
     }
     ix->cur->dbg_f32 = false;
-    vdb::QueryPrepParams qp{ix->cur->w_qin.p, (uint32_t)dim, (uint32_t)nq, ix->cur->w_qp.p, ld, SUPER, ix->cur->w_qnorm.p, ix->cur->w_thr.p, vdb::EUCLID,
+    vdb::QueryPrepParams qp{ix->cur->w_qin.p, (uint32_t)dim, (uint32_t)nq, ix->cur->w_qp.p, ld, nqp, ix->cur->w_qnorm.p, ix->cur->w_thr.p, vdb::EUCLID,
                             ix->cur->w_flags.p, ix->cur->w_qb.p, ix->cur->w_qerr.p, ix->d_margin ? ix->cur->w_qg.p : nullptr, margin_plan(ix).kappa,
                             nullptr, nullptr};
     vdb::launch_query_prep(qp, s);
@@ -1486,12 +1508,26 @@ int vdb_flat_debug_screen_scores(vdb_flat_index* ix, const float* queries, size_
     HIP_TRY(hipMemcpyAsync(ix->cur->w_thr.p, thr.data(), nq * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(ix->cur->w_dbg.p, 0xff, nq * (size_t)n * 4, s));            // NaN pattern = no key for this (query, row)
     vdb::FusedBf16Params fp{};
-    fp.rows = rows_f32(ix); fp.ld = ld; fp.n_rows = n; fp.qb = ix->cur->w_qb.p; fp.alpha = ix->d_alpha; fp.beta = ix->d_beta;
+    fp.rows = over_split ? ix->d_rows_store.p : rows_f32(ix);                     // (SPLIT: as the store lies; launch_filter_pass reads its hi pieces)
+    fp.ld = ld; fp.n_rows = n; fp.qb = ix->cur->w_qb.p; fp.alpha = ix->d_alpha; fp.beta = ix->d_beta;
     fp.margin = lb ? ix->d_margin : nullptr; fp.qg = lb ? ix->cur->w_qg.p : nullptr;
     fp.rowmask = ix->d_live; fp.thr = ix->cur->w_thr.p; fp.pool = ix->cur->w_pool.p; fp.pool_cnt = ix->cur->w_subcnt.p; fp.capl = capl; fp.n_wg = n_wg;
     fp.scalars = ix->d_scalars; fp.qmax_bits = ix->cur->w_flags.p + 2;
-    launch_filter_pass(ix, fp, s);                                                // the PRODUCTION filter pass (shadow rows if enabled)
-    vdb::launch_pool_to_dense(ix->cur->w_pool.p, ix->cur->w_subcnt.p, n_sub, capl, (uint32_t)nq, n, ix->cur->w_dbg.p, s);
+    if (wide) {                                                                   // the launch of pass_bf16's wide pass
+        fp.pool_block_stride = pool_block; fp.cnt_block_stride = cnt_block;
+        vdb::launch_fused_bf16w(fp, s);
+        HIP_TRY(hipGetLastError());
+        std::vector<uint32_t> cnts(n_blocks * cnt_block);                         // a dump with holes is no dump
+        HIP_TRY(hipMemcpyAsync(cnts.data(), ix->cur->w_subcnt.p, cnts.size() * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (uint32_t c : cnts)
+            if (c > capl) return fail(VDB_ERR_DEVICE, "a sub-pool of the wide kernel counted %u keys, room for %u", c, capl);
+    } else launch_filter_pass(ix, fp, s);                                         // the PRODUCTION filter pass (shadow rows if enabled)
+    for (uint32_t b = 0; b < n_blocks; ++b) {
+        const uint32_t nb = std::min<uint32_t>(SUPER, (uint32_t)nq - b * SUPER);
+        vdb::launch_pool_to_dense(ix->cur->w_pool.p + b * pool_block, ix->cur->w_subcnt.p + b * cnt_block, n_sub, capl, nb, n,
+                                  ix->cur->w_dbg.p + (size_t)b * SUPER * n, s);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_scores, ix->cur->w_dbg.p, nq * (size_t)n * 4, hipMemcpyDeviceToHost, s));
     std::vector<float> qn(nq), qe(nq), qg(nq, 0.0f);
