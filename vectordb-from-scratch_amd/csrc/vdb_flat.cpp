@@ -104,7 +104,6 @@ int vdb_flat_create(int metric, int device, vdb_flat_index** out) {
     if ((rc = ix->d_scalars.ensure(8))) return rc;
     HIP_TRY(hipMemset(ix->d_scalars, 0, 32));
     ix->wsv.reset(new Workspace[2]);
-    ix->cur = &ix->wsv[0];
     ix->wsv[0].stream = ix->stream;
     ix->wsv[1].stream = ix->stream_alt;
     *out = ix.release();
@@ -409,7 +408,10 @@ int vdb_flat_search_batch_device(vdb_flat_index* ix, const float* d_queries, siz
         return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
     if (ix->multi) return multi_search_device(ix, d_queries, nq, dim, k, d_id_mask, mask_bits, d_out_ids, d_out_dists, d_out_counts, (hipStream_t)stream);
     std::lock_guard<std::mutex> g(ix->mu);
-    return search_device(ix, d_queries, nq, dim, k, d_id_mask, mask_bits, d_out_ids, d_out_dists, d_out_counts,
+    Workspace* W;
+    int rc = idle_workspace(ix, &W);
+    if (rc) return rc;
+    return search_device(ix, *W, d_queries, nq, dim, k, d_id_mask, mask_bits, d_out_ids, d_out_dists, d_out_counts,
                          (hipStream_t)stream);
     });
 }
@@ -424,16 +426,16 @@ int vdb_flat_search_batch_device_begin(vdb_flat_index* ix, const float* d_querie
     ix->mu.lock();
     if (ix->begin_locked) { ix->mu.unlock(); return fail(VDB_ERR_INVALID_ARGUMENT, "a search is already pending on this handle"); }
     if (in_flight(ix)) { ix->mu.unlock(); return refuse_in_flight(); }
-    ix->cur = &ix->wsv[0];
+    Workspace& W = ix->wsv[0];                                   // (nothing is in flight; _finish takes the same one)
     // (the handle is locked by hand here: an exception must not skip the unlock below)
-    int rc = guarded([&]() -> int { return search_part1(ix, d_queries, nq, dim, k, d_id_mask, mask_bits, d_out_ids, d_out_dists, d_out_counts, (hipStream_t)stream, true); });
+    int rc = guarded([&]() -> int { return search_part1(ix, W, d_queries, nq, dim, k, d_id_mask, mask_bits, d_out_ids, d_out_dists, d_out_counts, (hipStream_t)stream, true); });
     if (rc == VDB_OK && d_code) {
         hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
         // (a forced hand-over to the slower tiers -- vdb_flat_set_tiers, tests -- rewrites the outputs in _finish whatever the
         // first tier certified: the word says "pending" then, so that a caller exchanging partial results exchanges again)
-        if (ix->cur->ctx.pending && (ix->tiers & (VDB_TIERS_FORCE_EXACT | VDB_TIERS_FORCE_F32 | VDB_TIERS_FORCE_RETHRESHOLD))) {
+        if (W.ctx.pending && (ix->tiers & (VDB_TIERS_FORCE_EXACT | VDB_TIERS_FORCE_F32 | VDB_TIERS_FORCE_RETHRESHOLD))) {
             if (hipMemsetD32Async((hipDeviceptr_t)d_code, VDB_PENDING_HOST, 1, s) != hipSuccess) rc = fail(VDB_ERR_DEVICE, "hipMemsetD32Async failed");
-        } else if (ix->cur->ctx.pending) vdb::launch_write_code(ix->cur->w_flags.p, d_code, s);
+        } else if (W.ctx.pending) vdb::launch_write_code(SearchFlags(W.w_flags.p, W.ctx.nq32).status, d_code, s);
         else if (hipMemsetAsync(d_code, 0, 4, s) != hipSuccess) rc = fail(VDB_ERR_DEVICE, "hipMemsetAsync failed");
     }
     if (rc == VDB_OK && !stream) {
@@ -444,8 +446,8 @@ int vdb_flat_search_batch_device_begin(vdb_flat_index* ix, const float* d_querie
             rc = fail(VDB_ERR_DEVICE, "stream ordering failed");
     }
     if (rc) {
-        if (ix->cur->ctx.pending) (void)hipStreamSynchronize(ix->cur->ctx.s);
-        ix->cur->ctx.pending = false; ix->mu.unlock(); return rc;
+        if (W.ctx.pending) (void)hipStreamSynchronize(W.ctx.s);
+        W.ctx.pending = false; ix->mu.unlock(); return rc;
     }
     ix->begin_locked = true;                                   // released by vdb_flat_search_batch_device_finish (same thread)
     return VDB_OK;
@@ -457,9 +459,10 @@ int vdb_flat_search_batch_device_finish(vdb_flat_index* ix, int* changed) {
     if (!ix) return fail(VDB_ERR_INVALID_ARGUMENT, "null handle");
     if (ix->multi) return refuse_multi("vdb_flat_search_batch_device_finish");
     if (!ix->begin_locked) return fail(VDB_ERR_INVALID_ARGUMENT, "no search pending on this handle");
-    int rc = guarded([&]() -> int { return search_part2(ix, changed); });
-    publish_stats(ix);
-    ix->cur->ctx.pending = false;
+    Workspace& W = ix->wsv[0];                                   // (the one _begin took)
+    int rc = guarded([&]() -> int { return search_part2(ix, W, changed); });
+    publish_stats(ix, W);
+    W.ctx.pending = false;
     ix->begin_locked = false;
     ix->mu.unlock();
     return rc;
@@ -479,19 +482,17 @@ int vdb_flat_search_batch_device_submit(vdb_flat_index* ix, const float* d_queri
     if (ix->profile) return fail(VDB_ERR_INVALID_ARGUMENT, "kernel profiling synchronises inside the search: not available for submitted searches");
     int slot = !ix->wsv[0].busy ? 0 : (!ix->wsv[1].busy ? 1 : -1);
     if (slot < 0) return fail(VDB_ERR_INVALID_ARGUMENT, "two searches are already in flight on this handle");
-    ix->cur = &ix->wsv[slot];
-    // (an exception must not leave ix->cur pointing at the ticket's workspace)
-    int rc = guarded([&]() -> int { return search_part1(ix, d_queries, nq, dim, k, d_id_mask, mask_bits, d_out_ids, d_out_dists, d_out_counts, (hipStream_t)stream); });
+    Workspace& W = ix->wsv[slot];
+    int rc = guarded([&]() -> int { return search_part1(ix, W, d_queries, nq, dim, k, d_id_mask, mask_bits, d_out_ids, d_out_dists, d_out_counts, (hipStream_t)stream); });
     if (rc) {
         // part 1 may have failed AFTER kernels were enqueued (a later allocation, a launch error): they could still write the
         // caller's buffers after this return -- wait for them, as _begin does
-        hipStream_t s = stream ? (hipStream_t)stream : ix->cur->stream;
+        hipStream_t s = stream ? (hipStream_t)stream : W.stream;
         if (s) (void)hipStreamSynchronize(s);
         if (ix->wsv[slot ^ 1].stream && !ix->wsv[slot ^ 1].busy) (void)hipStreamSynchronize(ix->wsv[slot ^ 1].stream);   // alternating passes of a large batch
-        ix->cur->ctx.pending = false; ix->cur = &ix->wsv[0]; return rc;
+        W.ctx.pending = false; return rc;
     }
-    ix->cur->busy = true;                       // (a search part 1 answered completely has pending = false: wait() returns at once)
-    ix->cur = &ix->wsv[0];
+    W.busy = true;                              // (a search part 1 answered completely has pending = false: wait() returns at once)
     *ticket = slot;
     return VDB_OK;
     });
@@ -505,14 +506,13 @@ int vdb_flat_search_batch_device_wait(vdb_flat_index* ix, int ticket) {
     if (!ix->wsv[ticket].busy) return fail(VDB_ERR_INVALID_ARGUMENT, "no submitted search behind this ticket");
     int rc = set_device(ix);
     if (rc) return rc;
-    ix->cur = &ix->wsv[ticket];
+    Workspace& W = ix->wsv[ticket];
     // (whatever part 2 does -- an exception from its host vectors included -- the ticket is retired: a workspace left busy
     // would refuse add / remove / flush on the handle for ever)
-    rc = guarded([&]() -> int { return search_part2(ix, nullptr); });
-    publish_stats(ix);
-    ix->cur->ctx.pending = false;
-    ix->cur->busy = false;
-    ix->cur = &ix->wsv[0];
+    rc = guarded([&]() -> int { return search_part2(ix, W, nullptr); });
+    publish_stats(ix, W);
+    W.ctx.pending = false;
+    W.busy = false;
     return rc;
     });
 }
@@ -625,9 +625,8 @@ static_assert(vdb::MMR_MAX_CANDIDATES == VDB_MMR_MAX_CANDIDATES, "the kernel's L
 // found.stride: the ids come down, the host's id -> row map names their device rows (the handle is locked and flushed: a candidate
 // cannot be missing), the rows go up beside k | lambda | mu of every query in ONE copy, mmr_select_kernel picks at most kcut per
 // query, and the picks leave through the copy-out every host-pointer search shares.
-static int mmr_copy_out(vdb_flat_index* ix, const HostSearch& r, const Lists& found, size_t kcut, hipStream_t s) {
+static int mmr_copy_out(vdb_flat_index* ix, MmrWs& W, const HostSearch& r, const Lists& found, size_t kcut, hipStream_t s) {
     const size_t nq = r.nq, stride = found.stride, n = nq * stride;
-    MmrWs& W = ix->cur->w_mmr;
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<uint64_t> ids(n);
     std::vector<uint32_t> cnt(nq);
@@ -742,48 +741,46 @@ static int search_batch_host(vdb_flat_index* ix, HostSearch r) {
     if (by) kdev = std::min(kdev + (rec ? rec->mmax : 1), len);    // (k was clamped to len first: k = SIZE_MAX cannot wrap)
     if (r.mmr) kdev = std::min(r.mmr->candidates, std::max<size_t>(len, 1));   // the search runs at the candidate depth; kcut picks leave
     hipStream_t s = ix->stream;
+    Workspace& W = ix->wsv[0];                                     // (nothing is in flight: staged into and searched in the first workspace)
     // Small index, a few queries (BASELINE configs[0]: Index::search itself, one query): queries and results go through MAPPED
     // host memory -- the two kernels of the direct path read and write it in place, nothing is copied by the runtime
     if (direct_eligible(ix, ix->n_rows(), nq, kdev) && ix->misfits.empty() && dim == ix->dim && !r.id_mask && !r.cm && !r.dm && !by && !r.mmr) {
         const size_t qb = nq * dim * sizeof(float), ib = nq * kdev * sizeof(uint64_t), db = nq * kdev * sizeof(float), cb = nq * sizeof(uint32_t);
         const size_t o_i = (qb + 15) & ~(size_t)15, o_d = o_i + ib, o_c = o_d + ((db + 15) & ~(size_t)15);
-        if ((rc = ensure_host_io(ix, o_c + cb))) return rc;
-        Workspace* W = ix->cur;
-        memcpy(W->h_io, r.queries, qb);
-        rc = search_device(ix, reinterpret_cast<const float*>(W->h_io.d), nq, dim, kdev, nullptr, 0, reinterpret_cast<uint64_t*>(W->h_io.d + o_i),
-                           reinterpret_cast<float*>(W->h_io.d + o_d), reinterpret_cast<uint32_t*>(W->h_io.d + o_c), nullptr);
+        if ((rc = ensure_host_io(W, o_c + cb))) return rc;
+        memcpy(W.h_io, r.queries, qb);
+        rc = search_device(ix, W, reinterpret_cast<const float*>(W.h_io.d), nq, dim, kdev, nullptr, 0, reinterpret_cast<uint64_t*>(W.h_io.d + o_i),
+                           reinterpret_cast<float*>(W.h_io.d + o_d), reinterpret_cast<uint32_t*>(W.h_io.d + o_c), nullptr);
         if (rc) return rc;
-        W = &ix->wsv[0];                                           // (search_device leaves ix->cur at workspace 0, the one it used)
-        emit_lists(Lists{reinterpret_cast<const uint64_t*>(W->h_io + o_i), reinterpret_cast<const float*>(W->h_io + o_d),
-                         reinterpret_cast<const uint32_t*>(W->h_io + o_c), nullptr, kdev}, r);
+        emit_lists(Lists{reinterpret_cast<const uint64_t*>(W.h_io + o_i), reinterpret_cast<const float*>(W.h_io + o_d),
+                         reinterpret_cast<const uint32_t*>(W.h_io + o_c), nullptr, kdev}, r);
         return VDB_OK;
     }
-    Workspace* W = ix->cur;
-    if ((rc = W->w_qin.ensure(nq * std::max<size_t>(dim, 1)))) return rc;
-    if ((rc = W->w_outi.ensure(nq * std::max<size_t>(kdev, 1)))) return rc;
-    if ((rc = W->w_outd.ensure(nq * std::max<size_t>(kdev, 1)))) return rc;
-    if ((rc = W->w_outc.ensure(nq))) return rc;
+    if ((rc = W.w_qin.ensure(nq * std::max<size_t>(dim, 1)))) return rc;
+    if ((rc = W.w_outi.ensure(nq * std::max<size_t>(kdev, 1)))) return rc;
+    if ((rc = W.w_outd.ensure(nq * std::max<size_t>(kdev, 1)))) return rc;
+    if ((rc = W.w_outc.ensure(nq))) return rc;
     vdb::RecommendLists rl{};
-    const StrikeBufs strike{W->w_selfid, W->w_bystat, W->w_rec};
+    const StrikeBufs strike{W.w_selfid, W.w_bystat, W.w_rec};
     if (rec) {
         // only the lists go up; the fold reads the examples where they are stored
-        if ((rc = recommend_stage(W->w_rec, *rec, nq, self_rows.data(), s, &rl))) return rc;
-        vdb::launch_fold_examples(rows_f32(ix), ix->ld, ix->dim, ix->n_uploaded, rl, (uint32_t)nq, W->w_qin.p, s);
+        if ((rc = recommend_stage(W.w_rec, *rec, nq, self_rows.data(), s, &rl))) return rc;
+        vdb::launch_fold_examples(rows_f32(ix), ix->ld, ix->dim, ix->n_uploaded, rl, (uint32_t)nq, W.w_qin.p, s);
         HIP_TRY(hipGetLastError());
     } else if (by) {
         // only the row numbers and the ids go up; the vectors never leave HBM
-        if ((rc = W->w_selfrow.ensure(nq))) return rc;
-        HIP_TRY(hipMemcpyAsync(W->w_selfrow.p, self_rows.data(), nq * 4, hipMemcpyHostToDevice, s));
+        if ((rc = W.w_selfrow.ensure(nq))) return rc;
+        HIP_TRY(hipMemcpyAsync(W.w_selfrow.p, self_rows.data(), nq * 4, hipMemcpyHostToDevice, s));
         if ((rc = strike_stage(strike, r, s))) return rc;
-        vdb::launch_gather_rows(rows_f32(ix), ix->ld, ix->dim, ix->n_uploaded, W->w_selfrow.p, (uint32_t)nq, W->w_qin.p, s);
+        vdb::launch_gather_rows(rows_f32(ix), ix->ld, ix->dim, ix->n_uploaded, W.w_selfrow.p, (uint32_t)nq, W.w_qin.p, s);
         HIP_TRY(hipGetLastError());
-    } else if (dim) HIP_TRY(hipMemcpyAsync(W->w_qin.p, r.queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
+    } else if (dim) HIP_TRY(hipMemcpyAsync(W.w_qin.p, r.queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
     const uint64_t* d_mask;
-    if ((rc = stage_mask(W->w_mask_ids, mask_src(r), s, &d_mask))) return rc;
-    if ((rc = search_device(ix, W->w_qin.p, nq, dim, kdev, d_mask, r.mask_bits, W->w_outi.p, W->w_outd.p, W->w_outc.p, nullptr))) return rc;
-    const Lists found{W->w_outi.p, W->w_outd.p, W->w_outc.p, nullptr, kdev};
+    if ((rc = stage_mask(W.w_mask_ids, mask_src(r), s, &d_mask))) return rc;
+    if ((rc = search_device(ix, W, W.w_qin.p, nq, dim, kdev, d_mask, r.mask_bits, W.w_outi.p, W.w_outd.p, W.w_outc.p, nullptr))) return rc;
+    const Lists found{W.w_outi.p, W.w_outd.p, W.w_outc.p, nullptr, kdev};
     if (by) return strike_copy_out(ix, r, strike, rl, found, kcut, s);
-    if (r.mmr) return mmr_copy_out(ix, r, found, kcut, s);
+    if (r.mmr) return mmr_copy_out(ix, W.w_mmr, r, found, kcut, s);
     return copy_out(found, r, s);
     });
 }
@@ -993,7 +990,7 @@ static int search_distinct_host(vdb_flat_index* ix, HostSearch r, vdb_meta_table
         };
     else
         search = [&](const float* d_q, size_t n, size_t depth, const uint64_t* d_mask, size_t bits, uint64_t* oi, float* od, uint32_t* oc) {
-            return search_device(ix, d_q, n, dim, depth, d_mask, bits, oi, od, oc, nullptr);
+            return search_device(ix, ix->wsv[0], d_q, n, dim, depth, d_mask, bits, oi, od, oc, nullptr);   // (nothing is in flight)
         };
     return pg ? per_group_drive(ix, s, search, a, *pg) : distinct_drive(ix, s, search, a);
     });
@@ -1124,7 +1121,6 @@ static int search_grouped_host(vdb_flat_index* ix, const char* what, const HostS
     if (nq > 0x3fffffffull) return fail(VDB_ERR_INVALID_ARGUMENT, "batch too large");
     ix->grouped_stats[1] = R;
     if ((rc = set_device(ix))) return rc;
-    ix->cur = &ix->wsv[0];
     if ((rc = flush(ix))) return rc;                               // staged adds first
     const size_t kdev = std::min(kmax, std::max<size_t>(len, 1));  // Index::search returns at most len results
     hipStream_t s = ix->stream;
@@ -1151,7 +1147,7 @@ static int search_grouped_host(vdb_flat_index* ix, const char* what, const HostS
     }
     if (R) HIP_TRY(hipMemcpyAsync(G.desc.p, desc.data(), R * sizeof(vdb::GroupedMask), hipMemcpyHostToDevice, s));
     GroupedArgs a{G.q.p, nq, dim, kdev, slot.data(), G.desc.p, desc.data(), R, G.oi.p, G.od.p, G.oc.p};
-    if ((rc = search_grouped(ix, s, a))) {
+    if ((rc = search_grouped(ix, ix->wsv[0], s, a))) {                // (nothing is in flight: the first workspace)
         (void)hipStreamSynchronize(s);                             // (desc and the plan are host vectors of this frame)
         return rc;
     }
@@ -1310,6 +1306,7 @@ int vdb_flat_distances_batch(vdb_flat_index* ix, const float* queries, size_t nq
     if (in_flight(ix)) return refuse_in_flight();
     int rc = set_device(ix);
     if (rc) return rc;
+    Workspace& W = ix->wsv[0];                                     // (nothing is in flight: the first workspace)
     if ((rc = flush(ix))) return rc;
     if (total == 0) return VDB_OK;
     if (total > 0xfffffff0ull || nq > 0x7fffffffull) return fail(VDB_ERR_INVALID_ARGUMENT, "too many pairs");
@@ -1329,27 +1326,27 @@ int vdb_flat_distances_batch(vdb_flat_index* ix, const float* queries, size_t nq
             prow[i] = it == ix->id2row.end() ? 0xffffffffu : it->second;
             pq[i] = q;
         }
-    if ((rc = ix->cur->w_qin.ensure(nq * dim))) return rc;
-    if ((rc = ix->cur->w_qp.ensure((size_t)bp * ld))) return rc;
-    if ((rc = ix->cur->w_qnorm.ensure(bp))) return rc;
-    if ((rc = ix->cur->w_thr.ensure(bp))) return rc;
-    if ((rc = ix->cur->w_flags.ensure(4))) return rc;
-    if ((rc = ix->cur->w_rowmask.ensure(2 * total))) return rc;      // pair_row | pair_query
-    if ((rc = ix->cur->w_outd.ensure(total))) return rc;
-    HIP_TRY(hipMemsetAsync(ix->cur->w_flags.p, 0, 16, s));
-    HIP_TRY(hipMemcpyAsync(ix->cur->w_qin.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(ix->cur->w_rowmask.p, prow.data(), total * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(ix->cur->w_rowmask.p + total, pq.data(), total * 4, hipMemcpyHostToDevice, s));
-    vdb::QueryPrepParams qp{ix->cur->w_qin.p, (uint32_t)dim, nq32, ix->cur->w_qp.p, ld, bp, ix->cur->w_qnorm.p, ix->cur->w_thr.p, vdb::EUCLID,
-                            ix->cur->w_flags.p, nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr};   // metric EUCLID here: zero norms are judged per PAIR below
+    if ((rc = W.w_qin.ensure(nq * dim))) return rc;
+    if ((rc = W.w_qp.ensure((size_t)bp * ld))) return rc;
+    if ((rc = W.w_qnorm.ensure(bp))) return rc;
+    if ((rc = W.w_thr.ensure(bp))) return rc;
+    if ((rc = W.w_flags.ensure(4))) return rc;
+    if ((rc = W.w_rowmask.ensure(2 * total))) return rc;      // pair_row | pair_query
+    if ((rc = W.w_outd.ensure(total))) return rc;
+    HIP_TRY(hipMemsetAsync(W.w_flags.p, 0, 16, s));
+    HIP_TRY(hipMemcpyAsync(W.w_qin.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(W.w_rowmask.p, prow.data(), total * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(W.w_rowmask.p + total, pq.data(), total * 4, hipMemcpyHostToDevice, s));
+    vdb::QueryPrepParams qp{W.w_qin.p, (uint32_t)dim, nq32, W.w_qp.p, ld, bp, W.w_qnorm.p, W.w_thr.p, vdb::EUCLID,
+                            W.w_flags.p, nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr};   // metric EUCLID here: zero norms are judged per PAIR below
     vdb::launch_query_prep(qp, s);
-    vdb::PairDistParams pp{rows_f32(ix), ld, (uint32_t)dim, ix->cur->w_qp.p, ix->cur->w_qnorm.p, ix->d_nd, ix->cur->w_rowmask.p + total,
-                           ix->cur->w_rowmask.p, (uint32_t)total, ix->metric, ix->cur->w_outd.p, ix->cur->w_flags.p};
+    vdb::PairDistParams pp{rows_f32(ix), ld, (uint32_t)dim, W.w_qp.p, W.w_qnorm.p, ix->d_nd, W.w_rowmask.p + total,
+                           W.w_rowmask.p, (uint32_t)total, ix->metric, W.w_outd.p, W.w_flags.p};
     vdb::launch_pair_distances(pp, s);
     HIP_TRY(hipGetLastError());
     uint32_t st = 0;
-    HIP_TRY(hipMemcpyAsync(out_dists, ix->cur->w_outd.p, total * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&st, ix->cur->w_flags.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_dists, W.w_outd.p, total * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&st, W.w_flags.p, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (st & vdb::ST_ZERO_QUERY)
         return fail_zero_vector();
@@ -1398,7 +1395,9 @@ int vdb_flat_last_stats(const vdb_flat_index* ix, uint64_t out[8]) {
 int vdb_flat_last_stats_ex(const vdb_flat_index* ix, uint64_t* out, size_t n) {
     return guarded([&]() -> int {
     if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
-    for (size_t i = 0; i < n; ++i) out[i] = i < 16 ? (ix->multi ? ix->stats[i] : ix->cur->stats[i]) : 0;
+    // (a plain handle: the first workspace's counters, not the published copy vdb_flat_last_stats reads -- the two differ only
+    // after the wait for ticket 1 was the last thing to finish)
+    for (size_t i = 0; i < n; ++i) out[i] = i < STAT_COUNT ? (ix->multi ? ix->stats[i] : ix->wsv[0].stats[i]) : 0;
     return VDB_OK;
     });
 }
@@ -1420,6 +1419,7 @@ int vdb_flat_debug_screen_scores(vdb_flat_index* ix, const float* queries, size_
     if (in_flight(ix)) return refuse_in_flight();
     int rc;
     if ((rc = set_device(ix))) return rc;
+    Workspace& W = ix->wsv[0];                                     // (nothing is in flight: the first workspace)
     if ((rc = flush(ix))) return rc;
     const uint32_t n = ix->n_uploaded, ld = ix->ld;
     if (!n) return fail(VDB_ERR_INVALID_ARGUMENT, "empty index");
@@ -1443,45 +1443,45 @@ int vdb_flat_debug_screen_scores(vdb_flat_index* ix, const float* queries, size_
     const size_t pool_block = (size_t)SUPER * n_sub * capl, cnt_block = (size_t)SUPER * n_sub;   // the production strides (pass_bf16)
     const size_t pool_keys = n_blocks * pool_block;
     if (pool_keys * 8 > ((size_t)6 << 30)) return fail(VDB_ERR_INVALID_ARGUMENT, "index too large for the score dump");
-    if ((rc = ix->cur->w_qin.ensure(nq * dim))) return rc;
-    if ((rc = ix->cur->w_qp.ensure((size_t)nqp * ld))) return rc;
-    if ((rc = ix->cur->w_qnorm.ensure(nqp))) return rc;
-    if ((rc = ix->cur->w_thr.ensure(nqp))) return rc;
-    if ((rc = ix->cur->w_qb.ensure((size_t)nqp * ld))) return rc;
-    if ((rc = ix->cur->w_qerr.ensure(nqp))) return rc;
-    if ((rc = ix->cur->w_qg.ensure(nqp))) return rc;
-    if ((rc = ix->cur->w_flags.ensure(4 + 3 * (size_t)nqp))) return rc;
-    if ((rc = ix->cur->w_pool.ensure(pool_keys))) return rc;
-    if ((rc = ix->cur->w_subcnt.ensure(n_blocks * cnt_block))) return rc;
-    if ((rc = ix->cur->w_dbg.ensure(nq * (size_t)n))) return rc;
+    if ((rc = W.w_qin.ensure(nq * dim))) return rc;
+    if ((rc = W.w_qp.ensure((size_t)nqp * ld))) return rc;
+    if ((rc = W.w_qnorm.ensure(nqp))) return rc;
+    if ((rc = W.w_thr.ensure(nqp))) return rc;
+    if ((rc = W.w_qb.ensure((size_t)nqp * ld))) return rc;
+    if ((rc = W.w_qerr.ensure(nqp))) return rc;
+    if ((rc = W.w_qg.ensure(nqp))) return rc;
+    if ((rc = W.w_flags.ensure(SearchFlags::words(nqp)))) return rc;
+    if ((rc = W.w_pool.ensure(pool_keys))) return rc;
+    if ((rc = W.w_subcnt.ensure(n_blocks * cnt_block))) return rc;
+    if ((rc = W.w_dbg.ensure(nq * (size_t)n))) return rc;
     // raw | VDB_DEBUG_SCORES_SPLIT: the store goes SPLIT (whatever split_mode says; the adaptive run is neither fed nor reset)
     // and stays so.  A non-finite element sends it straight back, as in a search (rows_to_split), and the call is refused.
     if (over_split) {
         if ((rc = rows_to_split(ix))) return rc;
         if (ix->layout != vdb::LAYOUT_SPLIT) return fail(VDB_ERR_INVALID_ARGUMENT, "the rows hold a non-finite element and stay F32");
     }
-    ix->cur->status_dirty = true;
-    HIP_TRY(hipMemsetAsync(ix->cur->w_flags.p, 0, 16, s));
-    HIP_TRY(hipMemcpyAsync(ix->cur->w_qin.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
+    W.status_dirty = true;
+    HIP_TRY(hipMemsetAsync(W.w_flags.p, 0, 16, s));
+    HIP_TRY(hipMemcpyAsync(W.w_qin.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
     const bool lb = ix->d_margin && raw == 0;
     if (raw == 2) {
         // the f32 MFMA tier's scores: dense_scores_kernel over EVERY row -- the production kernel of indexes up to 16384 rows,
         // and bit-identical to the fused f32 kernel's scores by construction (same K order, same score expression)
         if ((size_t)nq * n > ((size_t)1 << 28)) return fail(VDB_ERR_INVALID_ARGUMENT, "index too large for the f32-tier score dump");
-        if ((rc = ix->cur->w_dense.ensure((size_t)SUPER * n))) return rc;
-        HIP_TRY(hipMemcpyAsync(ix->cur->w_qin.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemsetAsync(ix->cur->w_flags.p, 0, 16, s));
-        vdb::QueryPrepParams qp2{ix->cur->w_qin.p, (uint32_t)dim, (uint32_t)nq, ix->cur->w_qp.p, ld, SUPER, ix->cur->w_qnorm.p, ix->cur->w_thr.p, vdb::EUCLID,
-                                 ix->cur->w_flags.p, nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr};
+        if ((rc = W.w_dense.ensure((size_t)SUPER * n))) return rc;
+        HIP_TRY(hipMemcpyAsync(W.w_qin.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(W.w_flags.p, 0, 16, s));
+        vdb::QueryPrepParams qp2{W.w_qin.p, (uint32_t)dim, (uint32_t)nq, W.w_qp.p, ld, SUPER, W.w_qnorm.p, W.w_thr.p, vdb::EUCLID,
+                                 W.w_flags.p, nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr};
         vdb::launch_query_prep(qp2, s);
-        vdb::DenseParams dp{rows_f32(ix), ld, n, ix->cur->w_qp.p, round_up((uint32_t)nq, 32), ix->d_alpha, ix->d_beta, ix->d_live, n, ix->cur->w_dense.p, n};
+        vdb::DenseParams dp{rows_f32(ix), ld, n, W.w_qp.p, round_up((uint32_t)nq, 32), ix->d_alpha, ix->d_beta, ix->d_live, n, W.w_dense.p, n};
         vdb::launch_dense_scores(dp, s);
         HIP_TRY(hipGetLastError());
         std::vector<uint64_t> keys((size_t)nq * n);
         std::vector<float> qn2(nq);
         uint32_t sc2[8] = {0};
-        HIP_TRY(hipMemcpyAsync(keys.data(), ix->cur->w_dense.p, keys.size() * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(qn2.data(), ix->cur->w_qnorm.p, nq * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(keys.data(), W.w_dense.p, keys.size() * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(qn2.data(), W.w_qnorm.p, nq * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(sc2, ix->d_scalars, 32, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         for (size_t i = 0; i < keys.size(); ++i) {
@@ -1496,45 +1496,45 @@ int vdb_flat_debug_screen_scores(vdb_flat_index* ix, const float* queries, size_
             out_consts[0] = eps_coef(ix); out_consts[1] = 0.0; out_consts[2] = 0.0; out_consts[3] = std::sqrt(f(sc2[0]));
             out_consts[4] = 0.0; out_consts[5] = 0.0; out_consts[6] = 0.0; out_consts[7] = (double)ld;
         }
-        ix->cur->dbg_nq = (uint32_t)nq; ix->cur->dbg_lb = false; ix->cur->dbg_f32 = true;
+        W.dbg_nq = (uint32_t)nq; W.dbg_lb = false; W.dbg_f32 = true;
         return VDB_OK;
     }
-    ix->cur->dbg_f32 = false;
-    vdb::QueryPrepParams qp{ix->cur->w_qin.p, (uint32_t)dim, (uint32_t)nq, ix->cur->w_qp.p, ld, nqp, ix->cur->w_qnorm.p, ix->cur->w_thr.p, vdb::EUCLID,
-                            ix->cur->w_flags.p, ix->cur->w_qb.p, ix->cur->w_qerr.p, ix->d_margin ? ix->cur->w_qg.p : nullptr, margin_plan(ix).kappa,
+    W.dbg_f32 = false;
+    vdb::QueryPrepParams qp{W.w_qin.p, (uint32_t)dim, (uint32_t)nq, W.w_qp.p, ld, nqp, W.w_qnorm.p, W.w_thr.p, vdb::EUCLID,
+                            W.w_flags.p, W.w_qb.p, W.w_qerr.p, ix->d_margin ? W.w_qg.p : nullptr, margin_plan(ix).kappa,
                             nullptr, nullptr};
     vdb::launch_query_prep(qp, s);
     std::vector<float> thr(nq, std::numeric_limits<float>::infinity());            // everything passes; padding queries keep -inf
-    HIP_TRY(hipMemcpyAsync(ix->cur->w_thr.p, thr.data(), nq * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(ix->cur->w_dbg.p, 0xff, nq * (size_t)n * 4, s));            // NaN pattern = no key for this (query, row)
+    HIP_TRY(hipMemcpyAsync(W.w_thr.p, thr.data(), nq * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(W.w_dbg.p, 0xff, nq * (size_t)n * 4, s));            // NaN pattern = no key for this (query, row)
     vdb::FusedBf16Params fp{};
     fp.rows = over_split ? ix->d_rows_store.p : rows_f32(ix);                     // (SPLIT: as the store lies; launch_filter_pass reads its hi pieces)
-    fp.ld = ld; fp.n_rows = n; fp.qb = ix->cur->w_qb.p; fp.alpha = ix->d_alpha; fp.beta = ix->d_beta;
-    fp.margin = lb ? ix->d_margin : nullptr; fp.qg = lb ? ix->cur->w_qg.p : nullptr;
-    fp.rowmask = ix->d_live; fp.thr = ix->cur->w_thr.p; fp.pool = ix->cur->w_pool.p; fp.pool_cnt = ix->cur->w_subcnt.p; fp.capl = capl; fp.n_wg = n_wg;
-    fp.scalars = ix->d_scalars; fp.qmax_bits = ix->cur->w_flags.p + 2;
+    fp.ld = ld; fp.n_rows = n; fp.qb = W.w_qb.p; fp.alpha = ix->d_alpha; fp.beta = ix->d_beta;
+    fp.margin = lb ? ix->d_margin : nullptr; fp.qg = lb ? W.w_qg.p : nullptr;
+    fp.rowmask = ix->d_live; fp.thr = W.w_thr.p; fp.pool = W.w_pool.p; fp.pool_cnt = W.w_subcnt.p; fp.capl = capl; fp.n_wg = n_wg;
+    fp.scalars = ix->d_scalars; fp.qmax_bits = status_qmax(W.w_flags.p);
     if (wide) {                                                                   // the launch of pass_bf16's wide pass
         fp.pool_block_stride = pool_block; fp.cnt_block_stride = cnt_block;
         vdb::launch_fused_bf16w(fp, s);
         HIP_TRY(hipGetLastError());
         std::vector<uint32_t> cnts(n_blocks * cnt_block);                         // a dump with holes is no dump
-        HIP_TRY(hipMemcpyAsync(cnts.data(), ix->cur->w_subcnt.p, cnts.size() * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(cnts.data(), W.w_subcnt.p, cnts.size() * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         for (uint32_t c : cnts)
             if (c > capl) return fail(VDB_ERR_DEVICE, "a sub-pool of the wide kernel counted %u keys, room for %u", c, capl);
     } else launch_filter_pass(ix, fp, s);                                         // the PRODUCTION filter pass (shadow rows if enabled)
     for (uint32_t b = 0; b < n_blocks; ++b) {
         const uint32_t nb = std::min<uint32_t>(SUPER, (uint32_t)nq - b * SUPER);
-        vdb::launch_pool_to_dense(ix->cur->w_pool.p + b * pool_block, ix->cur->w_subcnt.p + b * cnt_block, n_sub, capl, nb, n,
-                                  ix->cur->w_dbg.p + (size_t)b * SUPER * n, s);
+        vdb::launch_pool_to_dense(W.w_pool.p + b * pool_block, W.w_subcnt.p + b * cnt_block, n_sub, capl, nb, n,
+                                  W.w_dbg.p + (size_t)b * SUPER * n, s);
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out_scores, ix->cur->w_dbg.p, nq * (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_scores, W.w_dbg.p, nq * (size_t)n * 4, hipMemcpyDeviceToHost, s));
     std::vector<float> qn(nq), qe(nq), qg(nq, 0.0f);
     uint32_t sc[8] = {0};
-    HIP_TRY(hipMemcpyAsync(qn.data(), ix->cur->w_qnorm.p, nq * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(qe.data(), ix->cur->w_qerr.p, nq * 4, hipMemcpyDeviceToHost, s));
-    if (ix->d_margin) HIP_TRY(hipMemcpyAsync(qg.data(), ix->cur->w_qg.p, nq * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(qn.data(), W.w_qnorm.p, nq * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(qe.data(), W.w_qerr.p, nq * 4, hipMemcpyDeviceToHost, s));
+    if (ix->d_margin) HIP_TRY(hipMemcpyAsync(qg.data(), W.w_qg.p, nq * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(sc, ix->d_scalars, 32, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (out_qinfo)
@@ -1546,7 +1546,7 @@ int vdb_flat_debug_screen_scores(vdb_flat_index* ix, const float* queries, size_
         out_consts[3] = std::sqrt(f(sc[0])); out_consts[4] = std::sqrt(f(sc[2])); out_consts[5] = std::sqrt(f(sc[3]));   // max |d|, max |e_d|, max |e_d|/|d|
         out_consts[6] = lb ? 1.0 : 0.0; out_consts[7] = (double)ld;
     }
-    ix->cur->dbg_nq = (uint32_t)nq; ix->cur->dbg_lb = lb;
+    W.dbg_nq = (uint32_t)nq; W.dbg_lb = lb;
     return VDB_OK;
     });
 }
@@ -1561,8 +1561,9 @@ int vdb_flat_debug_last_thresholds(vdb_flat_index* ix, float* out, size_t nq) {
     if (in_flight(ix)) return refuse_in_flight();
     int rc;
     if ((rc = set_device(ix))) return rc;
-    if (nq > ix->cur->w_thr.n) return fail(VDB_ERR_INVALID_ARGUMENT, "more queries than the last search prepared");
-    HIP_TRY(hipMemcpy(out, ix->cur->w_thr.p, nq * 4, hipMemcpyDeviceToHost));
+    Workspace& W = ix->wsv[0];                                     // (nothing is in flight: the first workspace)
+    if (nq > W.w_thr.n) return fail(VDB_ERR_INVALID_ARGUMENT, "more queries than the last search prepared");
+    HIP_TRY(hipMemcpy(out, W.w_thr.p, nq * 4, hipMemcpyDeviceToHost));
     return VDB_OK;
     });
 }
@@ -1597,11 +1598,12 @@ int vdb_flat_debug_cert_probe(vdb_flat_index* ix, const uint32_t* qi, const floa
     if (in_flight(ix)) return refuse_in_flight();
     int rc;
     if ((rc = set_device(ix))) return rc;
-    if (!ix->cur->dbg_nq) return fail(VDB_ERR_INVALID_ARGUMENT, "call vdb_flat_debug_screen_scores first");
+    Workspace& W = ix->wsv[0];                                     // (nothing is in flight: the first workspace)
+    if (!W.dbg_nq) return fail(VDB_ERR_INVALID_ARGUMENT, "call vdb_flat_debug_screen_scores first");
     if (n == 0) return VDB_OK;
     if (n > 0x7fffffffull) return fail(VDB_ERR_INVALID_ARGUMENT, "too many probes");
     for (size_t i = 0; i < n; ++i)
-        if (qi[i] >= ix->cur->dbg_nq) return fail(VDB_ERR_INVALID_ARGUMENT, "query index %u out of range", qi[i]);
+        if (qi[i] >= W.dbg_nq) return fail(VDB_ERR_INVALID_ARGUMENT, "query index %u out of range", qi[i]);
     hipStream_t s = ix->stream;
     DevBuf<uint32_t> d_qi, d_out; DevBuf<float> d_T, d_ek;
     auto done = [&](int r) { d_qi.release(); d_out.release(); d_T.release(); d_ek.release(); return r; };
@@ -1611,8 +1613,8 @@ int vdb_flat_debug_cert_probe(vdb_flat_index* ix, const uint32_t* qi, const floa
         return done(fail(VDB_ERR_DEVICE, "copy failed"));
     // the same parameter block the screening tier's re-rank gets (pass_bf16)
     vdb::RerankParams rp{};
-    rp.metric = ix->metric; rp.eps_coef = eps_coef(ix); rp.nd2max_bits = ix->d_scalars; rp.qnorm = ix->cur->w_qnorm.p; rp.ld = ix->ld;
-    rp.qerr = ix->cur->dbg_f32 ? nullptr : ix->cur->w_qerr.p; rp.c_acc = c_acc_bf16(ix); rp.lb_scores = ix->cur->dbg_lb ? 1u : 0u;   // dbg_f32: the f32 tier's parameter block (pass_f32)
+    rp.metric = ix->metric; rp.eps_coef = eps_coef(ix); rp.nd2max_bits = ix->d_scalars; rp.qnorm = W.w_qnorm.p; rp.ld = ix->ld;
+    rp.qerr = W.dbg_f32 ? nullptr : W.w_qerr.p; rp.c_acc = c_acc_bf16(ix); rp.lb_scores = W.dbg_lb ? 1u : 0u;   // dbg_f32: the f32 tier's parameter block (pass_f32)
     vdb::launch_cert_probe(rp, d_qi.p, d_T.p, d_ek.p, (uint32_t)n, d_out.p, s);
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(out, d_out.p, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
@@ -1797,6 +1799,7 @@ int vdb_flat_debug_eligible_rows(vdb_flat_index* ix, const uint64_t* id_mask, si
     if (in_flight(ix)) return refuse_in_flight();
     int rc;
     if ((rc = set_device(ix))) return rc;
+    Workspace& W = ix->wsv[0];                                     // (nothing is in flight: the first workspace)
     if ((rc = flush(ix))) return rc;
     *count = 0;
     const uint32_t n = ix->n_uploaded;
@@ -1808,17 +1811,17 @@ int vdb_flat_debug_eligible_rows(vdb_flat_index* ix, const uint64_t* id_mask, si
     const bool on_device = hipPointerGetAttributes(&at, id_mask) == hipSuccess && at.type == hipMemoryTypeDevice;
     if (!on_device) {
         (void)hipGetLastError();
-        if ((rc = stage_mask(ix->cur->w_mask_ids, MaskSrc{id_mask, mask_bits}, s, &d_mask))) return rc;
+        if ((rc = stage_mask(W.w_mask_ids, MaskSrc{id_mask, mask_bits}, s, &d_mask))) return rc;
     }
-    if ((rc = ix->cur->w_rowmask.ensure((n + 31) / 32))) return rc;
-    vdb::launch_build_rowmask(ix->d_row_ids, (ix->n_live == n) ? nullptr : ix->d_live, d_mask, mask_bits, n, ix->cur->w_rowmask.p, s);
+    if ((rc = W.w_rowmask.ensure((n + 31) / 32))) return rc;
+    vdb::launch_build_rowmask(ix->d_row_ids, (ix->n_live == n) ? nullptr : ix->d_live, d_mask, mask_bits, n, W.w_rowmask.p, s);
     uint32_t E = 0;
-    if ((rc = eligible_count(ix, s, ix->cur->w_rowmask.p, &E))) return rc;
+    if ((rc = eligible_count(ix, W, s, W.w_rowmask.p, &E))) return rc;
     *count = E;
     if (!E) return VDB_OK;
-    if ((rc = eligible_list(ix, s, ix->cur->w_rowmask.p, E))) return rc;
+    if ((rc = eligible_list(ix, W, s, W.w_rowmask.p, E))) return rc;
     const size_t take = std::min<size_t>(cap, E);
-    if (take) HIP_TRY(hipMemcpyAsync(out, ix->cur->w_elig.p, take * 4, hipMemcpyDeviceToHost, s));
+    if (take) HIP_TRY(hipMemcpyAsync(out, W.w_elig.p, take * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return VDB_OK;
     });
@@ -1863,6 +1866,7 @@ int pairs_begin(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim)
     if (in_flight(ix)) return fail(VDB_ERR_INVALID_ARGUMENT, "a submitted search is still in flight on this handle");
     int rc;
     if ((rc = set_device(ix))) return rc;
+    Workspace& W = ix->wsv[0];                                     // (nothing is in flight: the first workspace)
     if ((rc = flush(ix))) return rc;
     ix->pairs_nq = 0;
     if (nq == 0) return VDB_OK;
@@ -1871,14 +1875,14 @@ int pairs_begin(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim)
     const uint32_t ld = ix->ld ? ix->ld : round_up((uint32_t)dim, vdb::KSTAGE);
     const uint32_t bp = round_up((uint32_t)nq, SUPER);
     hipStream_t s = ix->stream;
-    if ((rc = ix->cur->w_qin.ensure(nq * dim))) return rc;
-    if ((rc = ix->cur->w_qp.ensure((size_t)bp * ld))) return rc;
-    if ((rc = ix->cur->w_qnorm.ensure(bp))) return rc;
-    if ((rc = ix->cur->w_thr.ensure(bp))) return rc;
-    if ((rc = ix->cur->w_flags.ensure(4))) return rc;
-    HIP_TRY(hipMemcpyAsync(ix->cur->w_qin.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
-    vdb::QueryPrepParams qp{ix->cur->w_qin.p, (uint32_t)dim, (uint32_t)nq, ix->cur->w_qp.p, ld, bp, ix->cur->w_qnorm.p, ix->cur->w_thr.p, vdb::EUCLID,
-                            ix->cur->w_flags.p, nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr};   // metric EUCLID: zero norms are judged per pair
+    if ((rc = W.w_qin.ensure(nq * dim))) return rc;
+    if ((rc = W.w_qp.ensure((size_t)bp * ld))) return rc;
+    if ((rc = W.w_qnorm.ensure(bp))) return rc;
+    if ((rc = W.w_thr.ensure(bp))) return rc;
+    if ((rc = W.w_flags.ensure(4))) return rc;
+    HIP_TRY(hipMemcpyAsync(W.w_qin.p, queries, nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
+    vdb::QueryPrepParams qp{W.w_qin.p, (uint32_t)dim, (uint32_t)nq, W.w_qp.p, ld, bp, W.w_qnorm.p, W.w_thr.p, vdb::EUCLID,
+                            W.w_flags.p, nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr};   // metric EUCLID: zero norms are judged per pair
     vdb::launch_query_prep(qp, s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
@@ -1891,6 +1895,7 @@ static int run_pair_eval(vdb_flat_index* ix, int mode, const uint32_t* a, const 
     if (in_flight(ix)) return fail(VDB_ERR_INVALID_ARGUMENT, "a submitted search is still in flight on this handle");
     int rc;
     if ((rc = set_device(ix))) return rc;
+    Workspace& W = ix->wsv[0];                                     // (nothing is in flight: the first workspace)
     if (n == 0) return VDB_OK;
     if (n > 0xfffffff0ull) return fail(VDB_ERR_INVALID_ARGUMENT, "too many pairs");
     if (mode == 1 && (rc = flush(ix))) return rc;
@@ -1901,7 +1906,7 @@ static int run_pair_eval(vdb_flat_index* ix, int mode, const uint32_t* a, const 
         memcpy(ix->h_pairs + n, b, n * sizeof(uint32_t));
     }
     vdb::PairEvalParams pp{};
-    pp.rows = rows_f32(ix); pp.ld = ix->ld; pp.dim = ix->dim; pp.nd = ix->d_nd; pp.qp = ix->cur->w_qp.p; pp.qnorm = ix->cur->w_qnorm.p;
+    pp.rows = rows_f32(ix); pp.ld = ix->ld; pp.dim = ix->dim; pp.nd = ix->d_nd; pp.qp = W.w_qp.p; pp.qnorm = W.w_qnorm.p;
     pp.a = d_pairs; pp.b = d_pairs + n; pp.n = (uint32_t)n; pp.q0 = q0; pp.mode = mode; pp.metric = ix->metric;
     pp.mark = ZERO_NORM_MARK; pp.out = d_out;
     // A SMALL request (an HNSW insert's misses: a dozen pairs) is waited for by watching the mapped result buffer instead of
@@ -1949,9 +1954,10 @@ int device_view(vdb_flat_index* ix, DeviceView* out) {
     std::lock_guard<std::mutex> g(ix->mu);
     int rc;
     if ((rc = set_device(ix))) return rc;
-    if ((rc = ix->cur->w_flags.ensure(4))) return rc;
-    out->rows = rows_f32(ix); out->ld = ix->ld; out->dim = ix->dim; out->nd = ix->d_nd; out->qp = ix->cur->w_qp.p; out->qnorm = ix->cur->w_qnorm.p;
-    out->metric = ix->metric; out->stream = (void*)ix->stream; out->status = ix->cur->w_flags.p;
+    Workspace& W = ix->wsv[0];
+    if ((rc = W.w_flags.ensure(4))) return rc;
+    out->rows = rows_f32(ix); out->ld = ix->ld; out->dim = ix->dim; out->nd = ix->d_nd; out->qp = W.w_qp.p; out->qnorm = W.w_qnorm.p;
+    out->metric = ix->metric; out->stream = (void*)ix->stream; out->status = W.w_flags.p;
     return VDB_OK;
 }
 int search_batch_device_mask(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, size_t k, const uint64_t* d_mask,

@@ -3,6 +3,7 @@
 //   vdb_store.cpp    the device-resident mirror of FlatIndex's rows (src/flat_index.rs:12-50): staging, upload, tombstones
 //   vdb_cert.cpp     the coefficients of the "certified top-k" bounds and the tier plans
 //   vdb_search.cpp   the tier scheduler: screening pass, re-threshold pass, f32 MFMA tier, exact scan
+//   vdb_flags.h      the flag blocks of a search by name and the tier hand-over decided from them (no HIP: tested on the CPU)
 //   vdb_multi.cpp    ONE index over several GPUs in one process (vdb_flat_create_sharded)
 // vdb_hostio.h holds the steps every host-pointer batch search shares (shape check, mask staging, copy-out); HostSearch below is
 // the request those entry points hand on.
@@ -25,6 +26,7 @@
 #include "../../include/vdb_flat.h"
 #include "kernels.h"
 #include "vdb_device.h"
+#include "vdb_flags.h"
 #include "vdb_hostio.h"
 #include "vdb_internal.h"
 
@@ -53,6 +55,28 @@ constexpr uint32_t DIRECT_MAX_Q = 8;    // the direct exact path of small indexe
 // searches, one f32 reader -- loses at most 10 %.
 constexpr uint32_t SPLIT_AFTER = 64;
 constexpr uint32_t SPARSE_MAX_E = 131072;   // sparse-filter route: eligible rows at most (one pass's key buffer: 256 x 131072 x 8 B = 256 MiB)
+
+// The slots of Workspace::stats / vdb_flat_index::stats: what vdb_flat_last_stats_ex reports (include/vdb_flat.h says what each means)
+enum SearchStat {
+    STAT_MFMA = 0,          // queries answered by the MFMA path
+    STAT_EXACT,             // queries re-done by the exact-scan fallback (or answered by an exact route)
+    STAT_OVERFLOW,          // candidate-pool overflows
+    STAT_ROWS_SCANNED,      // rows scanned by the fused kernel
+    STAT_SAMPLE,            // sample rows used for the thresholds
+    STAT_KP,                // k' (candidates kept per query)
+    STAT_UNCERTIFIED,       // uncertified queries
+    STAT_KERNEL_NS,         // fused-kernel time of the search, ns (profiling on)
+    STAT_SCREENED,          // 1 when the bf16 screening tier answered the batch first
+    STAT_TO_F32,            // queries the screening tier handed to the f32 MFMA tier
+    STAT_ENQUEUED_NS,       // host clock of the call, ns: first tier enqueued
+    STAT_FLAGS_NS,          // ... its flags on the host
+    STAT_TOTAL_NS,          // ... return
+    STAT_RETHRESHOLD,       // queries answered by the re-threshold pass
+    STAT_SHADOW,            // 1 when the screening pass read the bf16 shadow rows
+    STAT_DIAG,              // 1 in the diagnostics build with a knob set
+    STAT_COUNT
+};
+static_assert(STAT_COUNT == 16, "vdb_flat_last_stats_ex reports sixteen counters");
 
 }  // namespace vdbi
 
@@ -126,7 +150,7 @@ struct Workspace {
         uint64_t* d_out_ids = nullptr; float* d_out_dists = nullptr; uint32_t* d_out_counts = nullptr;
         std::chrono::steady_clock::time_point t_entry;
     } ctx;
-    uint64_t stats[16] = {0};
+    uint64_t stats[vdbi::STAT_COUNT] = {0};
     hipStream_t stream = nullptr;                           // this context's stream, owned by the handle (used when the caller passes none)
     bool busy = false;                                      // submitted, not yet waited for
 };
@@ -236,8 +260,8 @@ struct vdb_flat_index {
     vdbi::DevBuf<uint32_t> d_idrank, d_rank2row; bool rank_valid = false;
 
     // search workspace: everything one search in flight owns.  Two of them, so that two batches can be in flight on two
-    // streams (vdb_flat_search_batch_device_submit / _wait); every synchronous entry point uses the first.
-    struct Workspace* cur = nullptr;                        // the context the search code below works in (set under the handle mutex)
+    // streams (vdb_flat_search_batch_device_submit / _wait).  An entry point picks one under the handle mutex (idle_workspace; the
+    // first when nothing may be in flight) and passes it down: the search code holds no "current" workspace.
     std::unique_ptr<Workspace[]> wsv;                       // [2]
     // mapped host memory for the pair hooks (vdb_internal.h): the kernel reads the pairs and writes the distances in place
     vdbi::HostBuf<uint32_t> h_pairs; vdbi::HostBuf<float> h_pout;
@@ -248,7 +272,7 @@ struct vdb_flat_index {
     int screen = 1;                                         // 1: bf16 screening tier first (default), 0: f32 MFMA tier only
     bool wide = true;                                       // batches above 256 queries: the 512-query filter kernel (vdb_flat_set_wide)
     bool large_k = true;                                    // 112 < k <= 1024 on the screening tier (vdb_flat_set_large_k)
-    uint64_t stats[16] = {0};                               // counters of the last COMPLETED search (copied from its context)
+    uint64_t stats[vdbi::STAT_COUNT] = {0};                 // counters of the last COMPLETED search (copied from its workspace: publish_stats)
     // vdb_flat_set_sparse_filter: 0 never (default), 1 always, 2 automatic -- masked searches scan only the eligible rows (search_sparse)
     int sparse_mode = 0;
     uint64_t sparse_last = 0, sparse_E = 0, sparse_count = 0;  // vdb_flat_sparse_stats [0] [1] [2]
@@ -322,19 +346,23 @@ uint32_t pick_kp(size_t k);
 // ---- vdb_search.cpp: the tier scheduler
 bool shadow_usable(const Index* ix);
 void launch_filter_pass(Index* ix, vdb::FusedBf16Params& fp, hipStream_t s);
-int search_part1(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, const uint64_t* d_idmask,
+// Every function below that needs a workspace takes it from its caller.  idle_workspace: the one no submitted search is using, or
+// the refusal when two are in flight; other_workspace: the handle's second one, seen from W.
+int idle_workspace(Index* ix, Workspace** W);
+Workspace& other_workspace(Index* ix, Workspace& W);
+int search_part1(Index* ix, Workspace& W, const float* d_q, size_t nq, size_t dim, size_t k, const uint64_t* d_idmask,
                  size_t mask_bits, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                  hipStream_t user_stream, bool allow_alt = false);
-int search_part2(Index* ix, int* changed);
+int search_part2(Index* ix, Workspace& W, int* changed);
 bool direct_eligible(const Index* ix, size_t n_rows, size_t nq, size_t k);
 size_t sparse_limit(size_t n_rows, size_t ld, size_t dim, size_t nq);
-int eligible_count(Index* ix, hipStream_t s, const uint32_t* d_rowmask, uint32_t* out_E);
-int eligible_list(Index* ix, hipStream_t s, const uint32_t* d_rowmask, uint32_t E);
-int ensure_host_io(Index* ix, size_t bytes);
-void publish_stats(Index* ix);
+int eligible_count(Index* ix, Workspace& W, hipStream_t s, const uint32_t* d_rowmask, uint32_t* out_E);
+int eligible_list(Index* ix, Workspace& W, hipStream_t s, const uint32_t* d_rowmask, uint32_t E);
+int ensure_host_io(Workspace& W, size_t bytes);
+void publish_stats(Index* ix, const Workspace& W);
 bool in_flight(const Index* ix);
 int refuse_in_flight();
-int search_device(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, const uint64_t* d_idmask,
+int search_device(Index* ix, Workspace& W, const float* d_q, size_t nq, size_t dim, size_t k, const uint64_t* d_idmask,
                   size_t mask_bits, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                   hipStream_t user_stream);
 // what search_part1 answers for a query of `dim` elements before any device work: VDB_OK, or the dimension error of the first
@@ -402,7 +430,7 @@ struct GroupedArgs {
     const uint32_t* slot; const vdb::GroupedMask* d_desc; const vdb::GroupedMask* h_desc; size_t n_ref;
     uint64_t* d_out_ids; float* d_out_dists; uint32_t* d_out_counts;
 };
-int search_grouped(Index* ix, hipStream_t s, const GroupedArgs& a);
+int search_grouped(Index* ix, Workspace& W, hipStream_t s, const GroupedArgs& a);
 
 // ---- vdb_multi.cpp: one index over several GPUs in one process (the parent handle dispatches here)
 int multi_create(int metric, const int* devices, size_t n, vdb_flat_index** out);

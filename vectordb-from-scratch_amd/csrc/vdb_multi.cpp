@@ -153,7 +153,9 @@ struct vdb_multi {
     // search by stored id: the shards' gathered blocks side by side, each query's place in them, the query ids, struck | cut counters
     vdbi::DevBuf<float> w_gstage; vdbi::DevBuf<uint32_t> w_place, w_bystat; vdbi::DevBuf<uint64_t> w_selfid;
     RecommendWs w_rec;                                          // recommend: the requests' lists; their row numbers are places in w_gstage
-    uint64_t stats[8] = {0};
+    // vdb_flat_shard_stats: exchanges performed, shards, exchange mode, RCCL ranks, host clock of the call, ... until every first tier was enqueued
+    enum { SH_EXCHANGES, SH_SHARDS, SH_MODE, SH_RANKS, SH_TOTAL_NS, SH_ENQUEUED_NS, SH_COUNT = 8 };
+    uint64_t stats[SH_COUNT] = {0};
     vdbi::Gang gang;
 };
 
@@ -245,7 +247,7 @@ int exchange(vdb_multi* M, size_t words, size_t nq, size_t k, uint64_t* d_out_id
     HIP_TRY(hipMemcpyAsync(M->h_status, M->d_status, 4, hipMemcpyDeviceToHost, s0));
     HIP_TRY(hipStreamSynchronize(s0));
     *worst = *M->h_status;
-    M->stats[0]++;
+    M->stats[vdb_multi::SH_EXCHANGES]++;
     return VDB_OK;
 }
 
@@ -438,8 +440,8 @@ int search_locked(vdb_flat_index* P, const float* d_q, size_t nq, size_t dim, si
                   uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, hipStream_t user_stream) {
     vdb_multi* M = P->multi;
     const uint64_t t0 = now_ns();
-    M->stats[0] = 0; M->stats[1] = (uint64_t)M->G; M->stats[2] = (uint64_t)M->exchange; M->stats[3] = 0;
-    auto done = [&](int rc) { M->stats[4] = now_ns() - t0; return rc; };
+    M->stats[vdb_multi::SH_EXCHANGES] = 0; M->stats[vdb_multi::SH_SHARDS] = (uint64_t)M->G; M->stats[vdb_multi::SH_MODE] = (uint64_t)M->exchange; M->stats[vdb_multi::SH_RANKS] = 0;
+    auto done = [&](int rc) { M->stats[vdb_multi::SH_TOTAL_NS] = now_ns() - t0; return rc; };
     if (nq == 0) return done(VDB_OK);
     HIP_TRY(hipSetDevice(M->home));
     // the caller's queries may have been produced on its stream: wait for it on the host (cheap when it is idle), so that
@@ -452,7 +454,7 @@ int search_locked(vdb_flat_index* P, const float* d_q, size_t nq, size_t dim, si
         return done(VDB_OK);
     }
     if (nq > 0x3fffffffull) return done(fail(VDB_ERR_INVALID_ARGUMENT, "batch too large"));
-    if (M->exchange == VDB_EXCHANGE_RCCL) { int rc = ensure_comms(M); if (rc) return done(rc); M->stats[3] = (uint64_t)M->comm_world; }
+    if (M->exchange == VDB_EXCHANGE_RCCL) { int rc = ensure_comms(M); if (rc) return done(rc); M->stats[vdb_multi::SH_RANKS] = (uint64_t)M->comm_world; }
     const size_t nk = nq * k;
     size_t words = nq * (3 * k + 1) + 1;
     words += words & 1;
@@ -521,7 +523,7 @@ int search_locked(vdb_flat_index* P, const float* d_q, size_t nq, size_t dim, si
         }
         send(g);
     });
-    M->stats[5] = now_ns() - t0;
+    M->stats[vdb_multi::SH_ENQUEUED_NS] = now_ns() - t0;
 
     // ---- exchange 1
     uint32_t worst = 0;
@@ -551,14 +553,14 @@ int search_locked(vdb_flat_index* P, const float* d_q, size_t nq, size_t dim, si
     // aggregate counters of the children (vdb_flat_last_stats_ex of the parent)
     memset(P->stats, 0, sizeof(P->stats));
     for (auto* c : M->sh) {
-        uint64_t st[16];
-        vdb_flat_last_stats_ex(c, st, 16);
-        for (int i : {0, 1, 2, 3, 6, 9, 13}) P->stats[i] += st[i];
-        for (int i : {4, 5, 7}) P->stats[i] = std::max(P->stats[i], st[i]);
-        for (int i : {8, 14, 15}) P->stats[i] |= st[i];
+        uint64_t st[STAT_COUNT];
+        vdb_flat_last_stats_ex(c, st, STAT_COUNT);
+        for (int i : {STAT_MFMA, STAT_EXACT, STAT_OVERFLOW, STAT_ROWS_SCANNED, STAT_UNCERTIFIED, STAT_TO_F32, STAT_RETHRESHOLD}) P->stats[i] += st[i];
+        for (int i : {STAT_SAMPLE, STAT_KP, STAT_KERNEL_NS}) P->stats[i] = std::max(P->stats[i], st[i]);
+        for (int i : {STAT_SCREENED, STAT_SHADOW, STAT_DIAG}) P->stats[i] |= st[i];
     }
-    P->stats[10] = M->stats[5];
-    P->stats[12] = now_ns() - t0;
+    P->stats[STAT_ENQUEUED_NS] = M->stats[vdb_multi::SH_ENQUEUED_NS];
+    P->stats[STAT_TOTAL_NS] = now_ns() - t0;
     int erc = first_error(M);
     if (erc) return done(erc);
     if (worst != 0) return done(fail(VDB_ERR_DEVICE, "sharded search ended with status %u and no failing shard", worst));

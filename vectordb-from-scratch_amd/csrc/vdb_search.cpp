@@ -35,14 +35,14 @@ static uint32_t screen_grid(const Index* ix, uint32_t tile_rows) {
 }
 // A screening launch: everything that comes from the index and the pass-local workspace W.  The caller adds the query
 // block (screen_queries) and what its pass differs in.
-static vdb::FusedBf16Params screen_params(const Index* ix, const Workspace* W, const uint32_t* d_rowmask, const uint32_t* d_status,
+static vdb::FusedBf16Params screen_params(const Index* ix, const Workspace& W, const uint32_t* d_rowmask, uint32_t* d_status,
                                           uint32_t capl, uint32_t n_wg) {
     vdb::FusedBf16Params fp{};
     fp.rows = ix->d_rows_store; fp.ld = ix->ld; fp.n_rows = ix->n_uploaded;      // (in the layout of the moment: launch_filter_pass)
     fp.alpha = ix->d_alpha; fp.beta = ix->d_beta; fp.rowmask = d_rowmask ? d_rowmask : ix->d_live;
     fp.margin = ix->d_margin;
-    fp.pool = W->w_pool.p; fp.pool_cnt = W->w_subcnt.p; fp.capl = capl; fp.n_wg = n_wg;
-    fp.scalars = ix->d_scalars; fp.qmax_bits = d_status + 2;
+    fp.pool = W.w_pool.p; fp.pool_cnt = W.w_subcnt.p; fp.capl = capl; fp.n_wg = n_wg;
+    fp.scalars = ix->d_scalars; fp.qmax_bits = status_qmax(d_status);
     return fp;
 }
 // ... its queries: the 256-query block (512 for the wide kernel) that starts at q0 of the bf16 images / g_q / thresholds
@@ -70,30 +70,111 @@ static void rerank_io(vdb::RerankParams& rp, const Index* ix, const float* qp, c
     rp.out_counts = out_counts + q0; rp.cert = cert + q0;
 }
 
+// ------------------------------------------------------------------ steps shared by the routes
+// The eligibility mask of a search: tombstones, optionally AND the caller's id filter (built into W.w_rowmask on s).  Null: every row.
+static int eligibility_mask(Index* ix, Workspace& W, hipStream_t s, const uint64_t* d_idmask, size_t mask_bits, const uint32_t** out) {
+    int rc;
+    const uint32_t n = ix->n_uploaded;
+    *out = (ix->n_live == n) ? nullptr : ix->d_live.p;
+    if (d_idmask) {
+        if ((rc = W.w_rowmask.ensure((n + 31) / 32))) return rc;
+        vdb::launch_build_rowmask(ix->d_row_ids, *out, d_idmask, mask_bits, n, W.w_rowmask.p, s);
+        *out = W.w_rowmask.p;
+    }
+    return VDB_OK;
+}
+
+// What a search of a non-empty store checks before any device work, in the order its errors win: the dimension, a live zero-norm
+// row under Cosine, the batch size (the caller's verdict: the limits differ per entry point), the dimension limit.
+static int pre_device_checks(Index* ix, size_t dim, bool batch_too_large) {
+    int rc;
+    if ((rc = query_dim_check(ix, dim))) return rc;
+    if (ix->metric == vdb::COSINE) {
+        if ((rc = ensure_zero_count(ix))) return rc;
+        if (ix->zero_live) return fail_zero_vector();   // distance.rs:51-55 aborts the whole search (flat_index.rs:57-60)
+    }
+    if (batch_too_large) return fail(VDB_ERR_INVALID_ARGUMENT, "batch too large");
+    if (ix->dim > 16384) return fail(VDB_ERR_INVALID_ARGUMENT, "dimension %u exceeds the supported 16384", ix->dim);
+    return VDB_OK;
+}
+
+// A select in EMIT mode -- the k smallest keys written as final ids, distances and counts -- through W's sort area: everything
+// but the keys (keys / stride / counts / n_fixed / cap) and the output slice (emit_ids / emit_dists / emit_counts).
+static vdb::SelectParams emit_select_params(const Index* ix, Workspace& W, size_t k) {
+    vdb::SelectParams mp{};
+    mp.kk = (uint32_t)k; mp.out_keys = W.w_exsel.p; mp.out_stride = MAX_SELECT; mp.out_cnt = W.w_cnt.p;
+    mp.emit_stride = (uint32_t)k;
+    mp.emit_rank2row = ix->ids_monotone ? nullptr : ix->d_rank2row.p; mp.emit_row_ids = ix->d_row_ids;
+    return mp;
+}
+
+// The queries of an exact route (sparse, grouped): the zero-padded block and the exact-order norms in W, the status block cleared
+// in front; query_prep raises ST_ZERO_QUERY.  No bf16 image and no per-query flags.
+static int prep_exact_queries(Index* ix, Workspace& W, hipStream_t s, const float* d_q, uint32_t nq, size_t dim) {
+    int rc;
+    const uint32_t ld = ix->ld, bp_all = round_up(nq, SUPER);
+    if ((rc = W.w_qp.ensure((size_t)bp_all * ld)) || (rc = W.w_qnorm.ensure(bp_all)) || (rc = W.w_thr.ensure(bp_all)) ||
+        (rc = W.w_flags.ensure(SearchFlags::words(nq))))
+        return rc;
+    uint32_t* d_status = SearchFlags(W.w_flags.p, nq).status;
+    HIP_TRY(hipMemsetAsync(d_status, 0, STATUS_BYTES, s));
+    W.status_dirty = true;                                         // (the tiers' bookkeeping: the block is cleared again before its next use)
+    vdb::QueryPrepParams qp{d_q, (uint32_t)dim, nq, W.w_qp.p, ld, bp_all, W.w_qnorm.p, W.w_thr.p, ix->metric, d_status,
+                            nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr};
+    vdb::launch_query_prep(qp, s);
+    return VDB_OK;
+}
+
+// The cut pass (re-threshold pass, screened range search): the filter pass of one block of up to SUPER queries whose thresholds are
+// score cuts, then the select of EVERY key that passed -- up to CUT_KMAX per query, truncation flagged in d_ovf -- into W.w2_cand
+// (counts: cand_counts(W)).  cut_pass_setup: the grid and the buffers, once per call.
+constexpr uint32_t CUT_KMAX = MAX_SELECT, CUT_CAPL = 256;
+struct CutGrid { uint32_t n_wg, n_sub; };
+static uint32_t* cand_counts(Workspace& W) { return W.w_cnt.p + 2 * SUPER; }
+static int cut_pass_setup(const Index* ix, Workspace& W, CutGrid* g) {
+    int rc;
+    g->n_wg = screen_grid(ix, vdb::fused_bf16_tile_rows());
+    g->n_sub = vdb::fused_bf16_subpools_per_query(g->n_wg);
+    if ((rc = W.w2_cand.ensure((size_t)SUPER * CUT_KMAX))) return rc;
+    if ((rc = W.w_pool.ensure((size_t)SUPER * g->n_sub * CUT_CAPL))) return rc;
+    return W.w_subcnt.ensure((size_t)SUPER * g->n_sub);
+}
+static void cut_pass(Index* ix, Workspace& W, hipStream_t s, const CutGrid& g, const uint32_t* d_rowmask, uint32_t* d_status,
+                     const uint16_t* qb, const float* qg, const float* thr, uint32_t q0, uint32_t nb, uint32_t* d_ovf) {
+    vdb::FusedBf16Params fp = screen_params(ix, W, d_rowmask, d_status, CUT_CAPL, g.n_wg);
+    screen_queries(fp, ix, qb, qg, thr, q0);
+    launch_filter_pass(ix, fp, s);
+    vdb::SelectParams mp{};
+    mp.keys = W.w_pool.p; mp.sub_counts = W.w_subcnt.p; mp.n_sub = g.n_sub; mp.capl = CUT_CAPL; mp.wg_major = 1;
+    mp.kk = CUT_KMAX; mp.out_keys = W.w2_cand.p; mp.out_stride = CUT_KMAX; mp.out_cnt = cand_counts(W);
+    mp.ovf = d_ovf + q0; mp.summary = nullptr; mp.flag_truncation = 1;
+    vdb::launch_select(mp, nb, s);
+}
+
 // The compact re-run block of the queries `todo` (batch indices) that a tier could not certify: the w2_* buffers for
 // them, the index list on the device, their padded rows and norms gathered (thresholds: -inf in the padding).
-static int gather_compact(Index* ix, hipStream_t s, const std::vector<uint32_t>& todo, size_t k, bool zero_flags) {
+static int gather_compact(Index* ix, Workspace& W, hipStream_t s, const std::vector<uint32_t>& todo, size_t k, bool zero_flags) {
     int rc;
-    Workspace* W = ix->cur;
+    
     const uint32_t nf = (uint32_t)todo.size(), nfp = round_up(nf, SUPER), ld = ix->ld;
-    if ((rc = W->w2_qp.ensure((size_t)nfp * ld))) return rc;
-    if ((rc = W->w2_qnorm.ensure(nfp))) return rc;
-    if ((rc = W->w2_thr.ensure(nfp))) return rc;
-    if ((rc = W->w2_outi.ensure((size_t)nf * k))) return rc;
-    if ((rc = W->w2_outd.ensure((size_t)nf * k))) return rc;
-    if ((rc = W->w2_outc.ensure(nf))) return rc;
-    if ((rc = W->w2_flags.ensure(2 * (size_t)nf))) return rc;
-    if ((rc = W->w2_qidx.ensure(nf))) return rc;
-    HIP_TRY(hipMemcpyAsync(W->w2_qidx.p, todo.data(), (size_t)nf * 4, hipMemcpyHostToDevice, s));
-    if (zero_flags) HIP_TRY(hipMemsetAsync(W->w2_flags.p, 0, 2 * (size_t)nf * 4, s));
-    vdb::launch_gather_queries(W->w_qp.p, W->w_qnorm.p, ld, W->w2_qidx.p, nf, nfp, W->w2_qp.p, W->w2_qnorm.p, W->w2_thr.p, s);
+    if ((rc = W.w2_qp.ensure((size_t)nfp * ld))) return rc;
+    if ((rc = W.w2_qnorm.ensure(nfp))) return rc;
+    if ((rc = W.w2_thr.ensure(nfp))) return rc;
+    if ((rc = W.w2_outi.ensure((size_t)nf * k))) return rc;
+    if ((rc = W.w2_outd.ensure((size_t)nf * k))) return rc;
+    if ((rc = W.w2_outc.ensure(nf))) return rc;
+    if ((rc = W.w2_flags.ensure(2 * (size_t)nf))) return rc;
+    if ((rc = W.w2_qidx.ensure(nf))) return rc;
+    HIP_TRY(hipMemcpyAsync(W.w2_qidx.p, todo.data(), (size_t)nf * 4, hipMemcpyHostToDevice, s));
+    if (zero_flags) HIP_TRY(hipMemsetAsync(W.w2_flags.p, 0, 2 * (size_t)nf * 4, s));
+    vdb::launch_gather_queries(W.w_qp.p, W.w_qnorm.p, ld, W.w2_qidx.p, nf, nfp, W.w2_qp.p, W.w2_qnorm.p, W.w2_thr.p, s);
     return VDB_OK;
 }
 
 // diagnostics (kn.rr_depth): the re-rank depth each query of the block ended at and its phase stamps, printed
-static int dump_rerank_depth(Workspace* W, hipStream_t s, uint32_t nb, uint32_t kp_first) {
+static int dump_rerank_depth(Workspace& W, hipStream_t s, uint32_t nb, uint32_t kp_first) {
     std::vector<uint32_t> dep((size_t)SUPER * 17);
-    HIP_TRY(hipMemcpyAsync(dep.data(), W->w_depth.p, dep.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(dep.data(), W.w_depth.p, dep.size() * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     // phase stamps (s_memrealtime, 100 MHz): 0 start, 1 query row in LDS, 2 round 1 staged+folded, 3 sorted, 4 depth decided, 5 last round folded, 6 end
     const uint64_t* st64 = reinterpret_cast<const uint64_t*>(dep.data() + SUPER);
@@ -112,31 +193,31 @@ static int dump_rerank_depth(Workspace* W, hipStream_t s, uint32_t nb, uint32_t 
 }
 
 // ------------------------------------------------------------------ exact path for one query
-int exact_one(Index* ix, hipStream_t s, uint32_t q, size_t k, const uint32_t* d_rowmask, uint64_t* d_out_ids,
+int exact_one(Index* ix, Workspace& W, hipStream_t s, uint32_t q, size_t k, const uint32_t* d_rowmask, uint64_t* d_out_ids,
               float* d_out_dists, uint32_t* d_out_count) {
     int rc;
     uint32_t n = ix->n_uploaded;
     if ((rc = ensure_ranks(ix))) return rc;
-    if ((rc = ix->cur->w_exact.ensure(n))) return rc;
-    if ((rc = ix->cur->w_exsel.ensure(MAX_SELECT + 8))) return rc;
-    if ((rc = ix->cur->w_cnt.ensure(4 * SUPER + 16))) return rc;
-    vdb::ExactScanParams ep{rows_f32(ix), ix->ld, ix->dim, n, ix->cur->w_qp.p + (size_t)q * ix->ld, ix->cur->w_qnorm.p + q, ix->d_nd,
-                            d_rowmask, ix->ids_monotone ? nullptr : ix->d_idrank.p, ix->metric, ix->cur->w_exact.p,
-                            ix->cur->w_flags.p};
+    if ((rc = W.w_exact.ensure(n))) return rc;
+    if ((rc = W.w_exsel.ensure(MAX_SELECT + 8))) return rc;
+    if ((rc = W.w_cnt.ensure(4 * SUPER + 16))) return rc;
+    vdb::ExactScanParams ep{rows_f32(ix), ix->ld, ix->dim, n, W.w_qp.p + (size_t)q * ix->ld, W.w_qnorm.p + q, ix->d_nd,
+                            d_rowmask, ix->ids_monotone ? nullptr : ix->d_idrank.p, ix->metric, W.w_exact.p,
+                            W.w_flags.p};
     vdb::launch_exact_scan(ep, s);
-    uint32_t* cnt = ix->cur->w_cnt.p + 4 * SUPER;
-    uint64_t* last = ix->cur->w_exsel.p + MAX_SELECT;      // largest key emitted so far (one u64 after the sort area)
+    uint32_t* cnt = W.w_cnt.p + 4 * SUPER;
+    uint64_t* last = W.w_exsel.p + MAX_SELECT;      // largest key emitted so far (one u64 after the sort area)
     // k may be as large as the index: emit in chunks of MAX_SELECT, each chunk = the smallest keys
     // strictly above the previous chunk's last key
     for (size_t done = 0; done < k; done += MAX_SELECT) {
         uint32_t kk = (uint32_t)std::min<size_t>(MAX_SELECT, k - done);
         vdb::SelectParams sp{};
-        sp.keys = ix->cur->w_exact.p; sp.stride = 0; sp.counts = nullptr; sp.n_fixed = n; sp.cap = n;
-        sp.kk = kk; sp.out_keys = ix->cur->w_exsel.p; sp.out_stride = MAX_SELECT; sp.out_cnt = cnt;
+        sp.keys = W.w_exact.p; sp.stride = 0; sp.counts = nullptr; sp.n_fixed = n; sp.cap = n;
+        sp.kk = kk; sp.out_keys = W.w_exsel.p; sp.out_stride = MAX_SELECT; sp.out_cnt = cnt;
         sp.out_thr = nullptr; sp.ovf = nullptr;
         sp.lo_excl = done ? last : nullptr; sp.out_last = last;
         vdb::launch_select(sp, 1, s);
-        vdb::EmitParams em{ix->cur->w_exsel.p, MAX_SELECT, cnt, ix->ids_monotone ? nullptr : ix->d_rank2row.p,
+        vdb::EmitParams em{W.w_exsel.p, MAX_SELECT, cnt, ix->ids_monotone ? nullptr : ix->d_rank2row.p,
                            ix->d_row_ids, d_out_ids + done, d_out_dists + done, d_out_count, kk, done ? 1u : 0u, n};
         vdb::launch_emit(em, s);
     }
@@ -151,36 +232,36 @@ int exact_one(Index* ix, hipStream_t s, uint32_t q, size_t k, const uint32_t* d_
 // d_out_*[q * kk ..], the survivor count to d_out_totals[q] if given.  `dense` receives the queries with more survivors than
 // the key buffer holds (e.g. every row ties with the bound): their outputs are not valid, the caller runs exact_one for them.
 constexpr uint32_t SCAN_CAP = 32768;                               // keys per query of a bounded pass
-static int bounded_scan_queries(Index* ix, hipStream_t s, const std::vector<uint32_t>& todo, uint32_t kk, const float* d_radii,
+static int bounded_scan_queries(Index* ix, Workspace& W, hipStream_t s, const std::vector<uint32_t>& todo, uint32_t kk, const float* d_radii,
                                 const uint32_t* d_rowmask, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                                 uint64_t* d_out_totals, uint32_t* d_status, std::vector<uint32_t>& dense) {
     int rc;
-    Workspace* W = ix->cur;
+    
     const uint32_t n = ix->n_uploaded;
     if ((rc = ensure_ranks(ix))) return rc;
-    if ((rc = W->w_exact.ensure(std::max<size_t>((size_t)8 * SCAN_CAP, n)))) return rc;
-    if ((rc = W->w_exsel.ensure((size_t)8 * MAX_SELECT + 8))) return rc;
-    uint32_t* d_cnt8 = W->w_cnt.p + 3 * SUPER;                     // [8] survivors per query, [8..16) select counts
+    if ((rc = W.w_exact.ensure(std::max<size_t>((size_t)8 * SCAN_CAP, n)))) return rc;
+    if ((rc = W.w_exsel.ensure((size_t)8 * MAX_SELECT + 8))) return rc;
+    uint32_t* d_cnt8 = W.w_cnt.p + 3 * SUPER;                     // [8] survivors per query, [8..16) select counts
     for (size_t g0 = 0; g0 < todo.size(); g0 += 8) {
         const uint32_t nqf = (uint32_t)std::min<size_t>(8, todo.size() - g0);
         HIP_TRY(hipMemsetAsync(d_cnt8, 0, 16 * 4, s));
         vdb::BoundedScanParams ep{};
-        ep.rows = rows_f32(ix); ep.ld = ix->ld; ep.dim = ix->dim; ep.n_rows = n; ep.qp = W->w_qp.p; ep.qnorm = W->w_qnorm.p;
+        ep.rows = rows_f32(ix); ep.ld = ix->ld; ep.dim = ix->dim; ep.n_rows = n; ep.qp = W.w_qp.p; ep.qnorm = W.w_qnorm.p;
         ep.nd = ix->d_nd; ep.rowmask = d_rowmask; ep.idrank = ix->ids_monotone ? nullptr : ix->d_idrank.p;
         ep.metric = ix->metric; ep.nqf = nqf;
         for (uint32_t j = 0; j < nqf; ++j) ep.qidx[j] = todo[g0 + j];
         if (d_radii) ep.radii = d_radii;
         else { ep.prev_dists = d_out_dists; ep.prev_counts = d_out_counts; ep.k = kk; }
-        ep.keys = W->w_exact.p; ep.cap = SCAN_CAP; ep.cnt = d_cnt8; ep.status = d_status;
+        ep.keys = W.w_exact.p; ep.cap = SCAN_CAP; ep.cnt = d_cnt8; ep.status = d_status;
         vdb::launch_bounded_scan(ep, s);
         uint32_t h_cnt[8];
         HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt8, nqf * 4, hipMemcpyDeviceToHost, s));
         vdb::SelectParams sp{};
-        sp.keys = W->w_exact.p; sp.stride = SCAN_CAP; sp.counts = d_cnt8; sp.n_fixed = 0; sp.cap = SCAN_CAP; sp.kk = kk;
-        sp.out_keys = W->w_exsel.p; sp.out_stride = MAX_SELECT; sp.out_cnt = d_cnt8 + 8;
+        sp.keys = W.w_exact.p; sp.stride = SCAN_CAP; sp.counts = d_cnt8; sp.n_fixed = 0; sp.cap = SCAN_CAP; sp.kk = kk;
+        sp.out_keys = W.w_exsel.p; sp.out_stride = MAX_SELECT; sp.out_cnt = d_cnt8 + 8;
         vdb::launch_select(sp, nqf, s);
         vdb::EmitMultiParams em{};
-        em.keys = W->w_exsel.p; em.key_stride = MAX_SELECT; em.cnt = d_cnt8 + 8;
+        em.keys = W.w_exsel.p; em.key_stride = MAX_SELECT; em.cnt = d_cnt8 + 8;
         em.survivors = d_cnt8; em.out_totals = d_out_totals;
         em.rank2row = ix->ids_monotone ? nullptr : ix->d_rank2row.p; em.row_ids = ix->d_row_ids; em.n_rows = n;
         em.out_ids = d_out_ids; em.out_dists = d_out_dists; em.out_count = d_out_counts; em.k = kk; em.nqf = nqf;
@@ -198,9 +279,10 @@ static int bounded_scan_queries(Index* ix, hipStream_t s, const std::vector<uint
 // Runs the f32 pipeline for the nq queries whose padded rows start at qp (stride ld; the block
 // must be readable and zero up to a multiple of 256 rows, thr = -inf in the padding), writing results for query j
 // at out_*[j*k ..] and the certification / pool-overflow flags at d_cert[j] / d_ovf[j].
-int pass_f32(Index* ix, hipStream_t s, const float* qp, const float* qnorm, float* thr, uint32_t nq, size_t k, uint32_t kp,
+// first_tier: no screening tier ran in front, so the sample, k' and the profiled kernel time the counters report are this tier's.
+int pass_f32(Index* ix, Workspace& W, hipStream_t s, const float* qp, const float* qnorm, float* thr, uint32_t nq, size_t k, uint32_t kp,
              const uint32_t* d_rowmask, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_cert,
-             uint32_t* d_ovf, uint32_t* d_status) {
+             uint32_t* d_ovf, uint32_t* d_status, bool first_tier) {
     int rc;
     const uint32_t n = ix->n_uploaded, ld = ix->ld;
     const bool small = n <= SMALL_N;
@@ -219,16 +301,16 @@ int pass_f32(Index* ix, hipStream_t s, const float* qp, const float* qnorm, floa
     const uint32_t capl = 64;
     // sub-pools in one pass = queries * row ranges * row parts * 2 = 512 * n_cu for every kernel shape
     const size_t pass_subs = 512u * (size_t)ix->n_cu;
-    if ((rc = ix->cur->w_dense.ensure((size_t)SUPER * S))) return rc;
-    if ((rc = ix->cur->w_cand.ensure((size_t)SUPER * kp))) return rc;
+    if ((rc = W.w_dense.ensure((size_t)SUPER * S))) return rc;
+    if ((rc = W.w_cand.ensure((size_t)SUPER * kp))) return rc;
     if (!small) {
-        if ((rc = ix->cur->w_samp.ensure((size_t)SUPER * kp))) return rc;
-        if ((rc = ix->cur->w_pool.ensure(pass_subs * capl))) return rc;
-        if ((rc = ix->cur->w_subcnt.ensure(pass_subs))) return rc;
+        if ((rc = W.w_samp.ensure((size_t)SUPER * kp))) return rc;
+        if ((rc = W.w_pool.ensure(pass_subs * capl))) return rc;
+        if ((rc = W.w_subcnt.ensure(pass_subs))) return rc;
     }
-    uint32_t* d_cnt_a = ix->cur->w_cnt.p;               // sample select counts
-    uint32_t* d_cand_cnt = ix->cur->w_cnt.p + 2 * SUPER;
-    if (!ix->cur->stats[8]) { ix->cur->stats[4] = S; ix->cur->stats[5] = kp; }
+    uint32_t* d_cnt_a = W.w_cnt.p;               // sample select counts
+    uint32_t* d_cand_cnt = W.w_cnt.p + 2 * SUPER;
+    if (first_tier) { W.stats[STAT_SAMPLE] = S; W.stats[STAT_KP] = kp; }
     const float eps = eps_coef(ix);
 
     for (uint32_t q0 = 0; q0 < nq; q0 += SUPER) {
@@ -241,26 +323,26 @@ int pass_f32(Index* ix, hipStream_t s, const float* qp, const float* qnorm, floa
         const float* qp0 = qp + (size_t)q0 * ld;
 
         vdb::DenseParams dp{rows_f32(ix), ld, n, qp0, round_up(nb, 32), ix->d_alpha, ix->d_beta, d_rowmask, S,
-                            ix->cur->w_dense.p, S};
+                            W.w_dense.p, S};
         vdb::launch_dense_scores(dp, s);
 
         vdb::SelectParams sp{};
-        sp.keys = ix->cur->w_dense.p; sp.stride = S; sp.counts = nullptr; sp.n_fixed = S; sp.cap = S; sp.kk = kp;
+        sp.keys = W.w_dense.p; sp.stride = S; sp.counts = nullptr; sp.n_fixed = S; sp.cap = S; sp.kk = kp;
         sp.out_stride = kp;
         if (small) {
-            sp.out_keys = ix->cur->w_cand.p; sp.out_cnt = d_cand_cnt; sp.out_thr = nullptr; sp.ovf = nullptr;
+            sp.out_keys = W.w_cand.p; sp.out_cnt = d_cand_cnt; sp.out_thr = nullptr; sp.ovf = nullptr;
             vdb::launch_select(sp, nb, s);
         } else {
             // thresholds: the sample's kp-th score (padding queries were given -inf by query_prep)
-            sp.out_keys = ix->cur->w_samp.p; sp.out_cnt = d_cnt_a; sp.out_thr = thr + q0; sp.ovf = nullptr;
+            sp.out_keys = W.w_samp.p; sp.out_cnt = d_cnt_a; sp.out_thr = thr + q0; sp.ovf = nullptr;
             vdb::launch_select(sp, nb, s);
             const uint32_t n_wg = std::min<uint32_t>((nqt == 8 ? 1u : 2u) * (uint32_t)ix->n_cu / n_super, (n + 31) / 32);
             const uint32_t n_sub = vdb::fused_subpools_per_query(nqt, n_wg);
             vdb::FusedParams fp{rows_f32(ix), ld, n, qp, q0, ix->d_alpha, ix->d_beta, d_rowmask ? d_rowmask : ix->d_live,
-                                thr, ix->cur->w_pool.p - (size_t)q0 * n_sub * capl,
-                                ix->cur->w_subcnt.p - (size_t)q0 * n_sub, capl, n_wg,
+                                thr, W.w_pool.p - (size_t)q0 * n_sub * capl,
+                                W.w_subcnt.p - (size_t)q0 * n_sub, capl, n_wg,
                                 ix->kn.fused_ablate};
-            const bool prof = ix->profile && !ix->cur->stats[8];       // with the screening tier on, ITS kernel is the one timed
+            const bool prof = ix->profile && first_tier;          // with the screening tier on, ITS kernel is the one timed
             if (prof) HIP_TRY(hipEventRecord(ix->ev0, s));
             // 256-query passes: LDS-DMA staging, 3-image ring with the barrier in mid-stage; smaller batches: the
             // register-staged 128/64/32-query shapes.  (Diagnostics build: the 2-image and register-staged A/B variants.)
@@ -277,17 +359,17 @@ int pass_f32(Index* ix, hipStream_t s, const float* qp, const float* qnorm, floa
                 HIP_TRY(hipEventSynchronize(ix->ev1));
                 float ms = 0.f;
                 HIP_TRY(hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
-                ix->cur->stats[7] += (uint64_t)((double)ms * 1e6);
+                W.stats[STAT_KERNEL_NS] += (uint64_t)((double)ms * 1e6);
             }
-            ix->cur->stats[3] += n;
+            W.stats[STAT_ROWS_SCANNED] += n;
             vdb::SelectParams mp{};
-            mp.keys = ix->cur->w_pool.p; mp.stride = 0; mp.counts = nullptr; mp.n_fixed = 0; mp.cap = 0;
-            mp.sub_counts = ix->cur->w_subcnt.p; mp.n_sub = n_sub; mp.capl = capl;
-            mp.kk = kp; mp.out_keys = ix->cur->w_cand.p; mp.out_stride = kp; mp.out_cnt = d_cand_cnt;
-            mp.out_thr = nullptr; mp.ovf = d_ovf + q0; mp.summary = d_status + 1;
+            mp.keys = W.w_pool.p; mp.stride = 0; mp.counts = nullptr; mp.n_fixed = 0; mp.cap = 0;
+            mp.sub_counts = W.w_subcnt.p; mp.n_sub = n_sub; mp.capl = capl;
+            mp.kk = kp; mp.out_keys = W.w_cand.p; mp.out_stride = kp; mp.out_cnt = d_cand_cnt;
+            mp.out_thr = nullptr; mp.ovf = d_ovf + q0; mp.summary = status_summary(d_status);
             vdb::launch_select(mp, nb, s);
         }
-        vdb::RerankParams rp = rerank_params(ix, d_rowmask, d_status, k, ix->cur->w_cand.p, kp, d_cand_cnt);
+        vdb::RerankParams rp = rerank_params(ix, d_rowmask, d_status, k, W.w_cand.p, kp, d_cand_cnt);
         rerank_io(rp, ix, qp, qnorm, d_out_ids, d_out_dists, d_out_counts, d_cert, q0);
         rp.eps_coef = eps;
         rp.thr = small ? nullptr : thr + q0;
@@ -296,17 +378,12 @@ int pass_f32(Index* ix, hipStream_t s, const float* qp, const float* qnorm, floa
     return VDB_OK;
 }
 
-// VDB_TIERS_FORCE_RETHRESHOLD in effect: ignored together with FORCE_EXACT / FORCE_F32, and when the pass itself is switched off
-static bool force_rethreshold(const Index* ix) {
-    return (ix->tiers & VDB_TIERS_FORCE_RETHRESHOLD) &&
-           !(ix->tiers & (VDB_TIERS_FORCE_EXACT | VDB_TIERS_FORCE_F32 | VDB_TIERS_NO_RETHRESHOLD));
-}
-
 // ------------------------------------------------------------------ tier: bf16 screening + certified re-rank
 // Same structure, with the scores of the HBM-bound bf16 kernels (fused_bf16_common.h): group minima of a row
 // sample -> per-query threshold -> one pass over all rows keeping the keys under the threshold -> the kp smallest
-// keys -> exact re-rank, certified with the bf16 error bound.  Queries come from ix->cur->w_qp / w_qb / w_qnorm.
-int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& pl, const uint32_t* d_rowmask,
+// keys -> exact re-rank, certified with the bf16 error bound.  Queries come from W0.w_qp / w_qb / w_qnorm: W0 is the search's
+// workspace, W below the pass-local buffers of one pass (W0's, or the other workspace's for every second pass).
+int pass_bf16(Index* ix, Workspace& W0, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& pl, const uint32_t* d_rowmask,
               uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, uint32_t* d_cert, uint32_t* d_ovf,
               uint32_t* d_status, float* d_thr_next, bool allow_alt) {
     int rc;
@@ -323,7 +400,7 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
     // kernel at the store's pitch (ld % 64, no shadow of its own, the production kernel) and the sample pass has its compact
     // copy: that copy is made from f32 rows, so a stale one sends the rows back to F32 first.  A batch above 256 queries on a
     // SPLIT index runs as 256-query passes of that kernel (the wide kernel reads f32 rows), as over the shadow.
-    Workspace* const other_ws = (ix->cur == &ix->wsv[0]) ? &ix->wsv[1] : &ix->wsv[0];
+    Workspace& other = other_workspace(ix, W0);
     const bool split_able = ix->split_mode != 0 && !shadow_usable(ix) && ld % 64 == 0 && ix->sample_cache && !ix->kn.sample_block &&
                             ix->kn.fused_pipe && !ix->kn.bf16_ablate;
     if (ix->layout == vdb::LAYOUT_SPLIT && (!split_able || ix->sample16_n != n || ix->sample16_S != S)) (void)rows_f32(ix);
@@ -345,10 +422,9 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
     // arrays (queries, thresholds, flags, outputs) are indexed by q0 and shared; only the pass-local buffers are doubled.
     Workspace* alt = nullptr;
     if (allow_alt && nq > (use_wide ? 2 * SUPER : SUPER) && !ix->profile && !ix->kn.rr_depth) {
-        Workspace* o = (ix->cur == &ix->wsv[0]) ? &ix->wsv[1] : &ix->wsv[0];
-        if (!o->busy) alt = o;
+        if (!other.busy) alt = &other;
     }
-    Workspace* const Wv[2] = {ix->cur, alt ? alt : ix->cur};
+    Workspace* const Wv[2] = {&W0, alt ? alt : &W0};
     const hipStream_t Sv[2] = {s, alt ? alt->stream : s};
     for (int t = 0; t < (alt ? 2 : 1); ++t) {
         Workspace* w = Wv[t];
@@ -364,8 +440,7 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
     // so nobody else is reading it; with ANOTHER search in flight and a different key this one keeps the f32 gather)
     bool sample_copy = ix->sample_cache && ld % 64 == 0 && !ix->kn.sample_block;
     if (sample_copy && (ix->sample16_n != n || ix->sample16_S != S)) {
-        Workspace* o = (ix->cur == &ix->wsv[0]) ? &ix->wsv[1] : &ix->wsv[0];
-        if (o->busy) sample_copy = false;
+        if (other.busy) sample_copy = false;
         else {
             const size_t need = (size_t)S * ld;
             if (ix->d_sample16.n < need) {
@@ -384,7 +459,7 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
     // count); after split_after of them the next one converts first -- under the handle mutex, and only while no other search of
     // this handle is in flight (its kernels read the rows), else not this time.  Mode 2 converts before the next such search.
     if (split_able && sample_copy && nq <= SUPER) {
-        if (!go_split && !ix->split_refused && !other_ws->busy && (ix->split_mode == 2 || ix->split_streak >= ix->split_after)) {
+        if (!go_split && !ix->split_refused && !other.busy && (ix->split_mode == 2 || ix->split_streak >= ix->split_after)) {
             if ((rc = rows_to_split(ix))) return rc;
         }
         ++ix->split_streak;
@@ -394,32 +469,32 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
         HIP_TRY(hipEventRecord(ix->ev_pass[0], s));
         HIP_TRY(hipStreamWaitEvent(Sv[1], ix->ev_pass[0], 0));
     }
-    ix->cur->stats[4] = S;
+    W0.stats[STAT_SAMPLE] = S;
     const float eps = eps_coef(ix);
     // thresholds: sample pass + threshold select per 256-query block.  A batch of several passes computes ALL of them first, on the
     // caller's stream: left to their own pass, the second stream's small kernels queue up behind the first pass's filter kernel
     // (which owns every CU for a millisecond) and the second filter pass starts late.
     // a launch of this tier over pass-local buffers W: sample geometry and the diagnostics' ablation on top of screen_params
-    auto pass_params = [&](Workspace* W) {
+    auto pass_params = [&](Workspace& W) {
         vdb::FusedBf16Params fp = screen_params(ix, W, d_rowmask, d_status, capl, n_wg);
         fp.ablate = ix->kn.bf16_ablate;
         fp.n_sample = S; fp.sample_shift = pl.shift;
-        fp.sample_block = ix->kn.sample_block ? (n / (S / 256u)) : 0u; fp.minkeys = W->w_dense.p; fp.minkey_stride = M;
+        fp.sample_block = ix->kn.sample_block ? (n / (S / 256u)) : 0u; fp.minkeys = W.w_dense.p; fp.minkey_stride = M;
         return fp;
     };
-    auto thresholds_of = [&](Workspace* W, hipStream_t st, uint32_t qb0) {
+    auto thresholds_of = [&](Workspace& W, hipStream_t st, uint32_t qb0) {
         const uint32_t nb = std::min(SUPER, nq - qb0);
         vdb::FusedBf16Params fp = pass_params(W);
-        screen_queries(fp, ix, ix->cur->w_qb.p, ix->cur->w_qg.p, ix->cur->w_thr.p, qb0);
+        screen_queries(fp, ix, W0.w_qb.p, W0.w_qg.p, W0.w_thr.p, qb0);
         if (sample_copy) {
             vdb::FusedBf16Params sp16 = fp;
             sp16.rows16 = ix->d_sample16;
             vdb::launch_sample_s16(sp16, st);
         } else vdb::launch_sample_bf16(fp, st);
         vdb::SelectParams sp{};
-        sp.keys = W->w_dense.p; sp.stride = M; sp.counts = nullptr; sp.n_fixed = M; sp.cap = M; sp.kk = KT;
-        sp.out_stride = KT; sp.out_keys = W->w_samp.p; sp.out_cnt = W->w_cnt.p; sp.out_thr = ix->cur->w_thr.p + qb0; sp.ovf = nullptr;
-        if (ix->d_margin) { sp.shift_g = ix->cur->w_qg.p + qb0; sp.shift_m_bits = ix->d_scalars + 4; }   // plain-score sample -> lower-bound units
+        sp.keys = W.w_dense.p; sp.stride = M; sp.counts = nullptr; sp.n_fixed = M; sp.cap = M; sp.kk = KT;
+        sp.out_stride = KT; sp.out_keys = W.w_samp.p; sp.out_cnt = W.w_cnt.p; sp.out_thr = W0.w_thr.p + qb0; sp.ovf = nullptr;
+        if (ix->d_margin) { sp.shift_g = W0.w_qg.p + qb0; sp.shift_m_bits = ix->d_scalars + 4; }   // plain-score sample -> lower-bound units
         vdb::launch_thr_select(sp, nb, st);
     };
     // (measured at config 3's shape: four 256-query passes 3.26 -> 3.09 ms with the thresholds first; the two 512-query passes
@@ -427,22 +502,22 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
     const uint32_t n_passes = use_wide ? (nq + 2 * SUPER - 1) / (2 * SUPER) : (nq + SUPER - 1) / SUPER;
     const bool thr_first = alt != nullptr && n_passes > 2;
     if (thr_first) {
-        for (uint32_t qb0 = 0; qb0 < nq; qb0 += SUPER) thresholds_of(ix->cur, s, qb0);
+        for (uint32_t qb0 = 0; qb0 < nq; qb0 += SUPER) thresholds_of(W0, s, qb0);
         HIP_TRY(hipEventRecord(ix->ev_pass[0], s));               // (re-recorded: the other stream starts behind the thresholds)
         HIP_TRY(hipStreamWaitEvent(Sv[1], ix->ev_pass[0], 0));
     }
     for (uint32_t q0 = 0, pass = 0; q0 < nq; ++pass) {
         const bool wide = use_wide && nq - q0 > SUPER;            // two 256-query blocks share this pass's fetch of the rows
         const uint32_t n_blocks = wide ? 2u : 1u;
-        Workspace* const W = Wv[pass & 1];                        // pass-local buffers
+        Workspace& W = *Wv[pass & 1];                             // pass-local buffers
         const hipStream_t s = Sv[pass & 1];                       // (shadows the caller's stream inside the loop)
-        uint32_t* d_cand_cnt = W->w_cnt.p + 2 * SUPER;
+        uint32_t* d_cand_cnt = W.w_cnt.p + 2 * SUPER;
         vdb::FusedBf16Params fp = pass_params(W);
         // ---- thresholds of the pass's blocks (unless they were all computed up front)
         if (!thr_first)
             for (uint32_t b = 0; b < n_blocks; ++b) thresholds_of(W, s, q0 + b * SUPER);
         // ---- ONE pass over the rows for all of them
-        screen_queries(fp, ix, ix->cur->w_qb.p, ix->cur->w_qg.p, ix->cur->w_thr.p, q0);
+        screen_queries(fp, ix, W0.w_qb.p, W0.w_qg.p, W0.w_thr.p, q0);
         if (ix->profile) HIP_TRY(hipEventRecord(ix->ev0, s));
         if (wide) {
             fp.n_wg = n_wg_w; fp.pool_block_stride = pool_block; fp.cnt_block_stride = cnt_block;
@@ -453,7 +528,7 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
             HIP_TRY(hipEventSynchronize(ix->ev1));
             float ms = 0.f;
             HIP_TRY(hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
-            ix->cur->stats[7] += (uint64_t)((double)ms * 1e6);
+            W0.stats[STAT_KERNEL_NS] += (uint64_t)((double)ms * 1e6);
         }
 #ifdef VDB_DIAG
         // An ablated launch leaves wrong pools behind; if the step went on with them every query would fall through to the
@@ -463,36 +538,36 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
         if (fp.ablate) {
             fp.ablate = 0;
             if (wide) vdb::launch_fused_bf16w(fp, s); else launch_filter_pass(ix, fp, s);
-            ix->cur->stats[3] += n;
+            W0.stats[STAT_ROWS_SCANNED] += n;
         }
 #endif
-        ix->cur->stats[3] += n;
+        W0.stats[STAT_ROWS_SCANNED] += n;
 
         // ---- per block: the smallest pooled keys, then the exact re-rank
         for (uint32_t b = 0; b < n_blocks; ++b) {
             const uint32_t qb0 = q0 + b * SUPER, nb = std::min(SUPER, nq - qb0);
             vdb::SelectParams mp{};
-            mp.keys = W->w_pool.p + (size_t)b * pool_block; mp.stride = 0; mp.counts = nullptr; mp.n_fixed = 0; mp.cap = 0;
-            mp.sub_counts = W->w_subcnt.p + (size_t)b * cnt_block; mp.n_sub = vdb::fused_bf16_subpools_per_query(wide ? n_wg_w : n_wg);
+            mp.keys = W.w_pool.p + (size_t)b * pool_block; mp.stride = 0; mp.counts = nullptr; mp.n_fixed = 0; mp.cap = 0;
+            mp.sub_counts = W.w_subcnt.p + (size_t)b * cnt_block; mp.n_sub = vdb::fused_bf16_subpools_per_query(wide ? n_wg_w : n_wg);
             mp.capl = capl; mp.wg_major = 1;
-            mp.kk = kp; mp.out_keys = W->w_cand.p; mp.out_stride = kp; mp.out_cnt = d_cand_cnt;
-            mp.out_thr = nullptr; mp.ovf = d_ovf + qb0; mp.summary = d_status + 1;
+            mp.kk = kp; mp.out_keys = W.w_cand.p; mp.out_stride = kp; mp.out_cnt = d_cand_cnt;
+            mp.out_thr = nullptr; mp.ovf = d_ovf + qb0; mp.summary = status_summary(d_status);
             vdb::launch_select(mp, nb, s);
 
-            vdb::RerankParams rp = rerank_params(ix, d_rowmask, d_status, k, W->w_cand.p, kp, d_cand_cnt);
-            rerank_io(rp, ix, ix->cur->w_qp.p, ix->cur->w_qnorm.p, d_out_ids, d_out_dists, d_out_counts, d_cert, qb0);
+            vdb::RerankParams rp = rerank_params(ix, d_rowmask, d_status, k, W.w_cand.p, kp, d_cand_cnt);
+            rerank_io(rp, ix, W0.w_qp.p, W0.w_qnorm.p, d_out_ids, d_out_dists, d_out_counts, d_cert, qb0);
             rp.eps_coef = eps;
-            rp.thr = ix->cur->w_thr.p + qb0;
-            rp.qerr = ix->cur->w_qerr.p + qb0; rp.c_acc = c_acc_bf16(ix); rp.lb_scores = ix->d_margin ? 1u : 0u;
+            rp.thr = W0.w_thr.p + qb0;
+            rp.qerr = W0.w_qerr.p + qb0; rp.c_acc = c_acc_bf16(ix); rp.lb_scores = ix->d_margin ? 1u : 0u;
             rp.kp_first = round_up((uint32_t)k + 38u, 16u); rp.kp_step = 32;
             rp.thr_next = d_thr_next ? d_thr_next + qb0 : nullptr;
-            rp.cut_always = force_rethreshold(ix) ? 1u : 0u;
+            rp.cut_always = force_rethreshold(ix->tiers) ? 1u : 0u;
             // diagnostics build: the first re-rank round overridden, the depth each query ended at printed
             if (ix->kn.kp_first) rp.kp_first = ix->kn.kp_first;
             const bool dump_depth = ix->kn.rr_depth;
             if (dump_depth) {
-                if ((rc = W->w_depth.ensure(SUPER * 17))) return rc;      // depth[q], then 8 x 64-bit phase stamps per query
-                rp.depth = W->w_depth.p;
+                if ((rc = W.w_depth.ensure(SUPER * 17))) return rc;      // depth[q], then 8 x 64-bit phase stamps per query
+                rp.depth = W.w_depth.p;
             }
             if (pl.large) {
                 // 112 < k <= 1024: the large-k re-rank (first round k + k/8, at least k + 38; then as deep as the certificate asks)
@@ -520,50 +595,37 @@ int pass_bf16(Index* ix, hipStream_t s, uint32_t nq, size_t k, const Bf16Plan& p
 // form of the large-k re-rank above that (k <= 1024).  Exact by construction; a query whose list does not fit (pool overflow,
 // more than 2048 keys) keeps its flag and goes on to the next tier.
 // todo: batch indices; cuts: their score cuts.  On return flags2 (host) holds cert / overflow per compact query.
-int pass_rethreshold(Index* ix, hipStream_t s, const std::vector<uint32_t>& todo, const std::vector<float>& cuts, size_t k,
+int pass_rethreshold(Index* ix, Workspace& W, hipStream_t s, const std::vector<uint32_t>& todo, const std::vector<float>& cuts, size_t k,
                      const uint32_t* d_rowmask, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                      uint32_t* d_status, std::vector<uint32_t>& flags2) {
     int rc;
     const uint32_t n = ix->n_uploaded, ld = ix->ld;
     const uint32_t nf = (uint32_t)todo.size(), nfp = round_up(nf, SUPER);
-    constexpr uint32_t KMAX = 2048;                              // keys re-ranked per query at most (select capacity)
-    const uint32_t capl = 256;
-    const uint32_t n_wg = screen_grid(ix, vdb::fused_bf16_tile_rows());
-    const uint32_t n_sub = vdb::fused_bf16_subpools_per_query(n_wg);
-    if ((rc = ix->cur->w2_qerr.ensure(nfp))) return rc;
-    if ((rc = ix->cur->w2_qg.ensure(nfp))) return rc;
-    if ((rc = ix->cur->w2_qb.ensure((size_t)nfp * ld))) return rc;
-    if ((rc = ix->cur->w2_cand.ensure((size_t)SUPER * KMAX))) return rc;
-    if ((rc = ix->cur->w_pool.ensure((size_t)SUPER * n_sub * capl))) return rc;
-    if ((rc = ix->cur->w_subcnt.ensure((size_t)SUPER * n_sub))) return rc;
-    if ((rc = gather_compact(ix, s, todo, k, false))) return rc;             // (query_prep below zeroes the flags)
-    uint32_t* d_cert2 = ix->cur->w2_flags.p;
-    uint32_t* d_ovf2 = ix->cur->w2_flags.p + nf;
+    CutGrid grid;
+    if ((rc = W.w2_qerr.ensure(nfp))) return rc;
+    if ((rc = W.w2_qg.ensure(nfp))) return rc;
+    if ((rc = W.w2_qb.ensure((size_t)nfp * ld))) return rc;
+    if ((rc = cut_pass_setup(ix, W, &grid))) return rc;
+    if ((rc = gather_compact(ix, W, s, todo, k, false))) return rc;          // (query_prep below zeroes the flags)
+    uint32_t* d_cert2 = W.w2_flags.p;
+    uint32_t* d_ovf2 = W.w2_flags.p + nf;
     // bf16 image, |q - bf16(q)| and zeroed flags of the compact block (the rows are already padded: dim = ld)
-    vdb::QueryPrepParams qp{ix->cur->w2_qp.p, ld, nf, ix->cur->w2_qp.p, ld, nfp, ix->cur->w2_qnorm.p, ix->cur->w2_thr.p, vdb::EUCLID, d_status,
-                            ix->cur->w2_qb.p, ix->cur->w2_qerr.p, ix->d_margin ? ix->cur->w2_qg.p : nullptr, margin_plan(ix).kappa, d_cert2, d_ovf2};
+    vdb::QueryPrepParams qp{W.w2_qp.p, ld, nf, W.w2_qp.p, ld, nfp, W.w2_qnorm.p, W.w2_thr.p, vdb::EUCLID, d_status,
+                            W.w2_qb.p, W.w2_qerr.p, ix->d_margin ? W.w2_qg.p : nullptr, margin_plan(ix).kappa, d_cert2, d_ovf2};
     vdb::launch_query_prep(qp, s);
-    HIP_TRY(hipMemcpyAsync(ix->cur->w2_thr.p, cuts.data(), (size_t)nf * 4, hipMemcpyHostToDevice, s));   // padding queries keep -inf
-    uint32_t* d_cand_cnt = ix->cur->w_cnt.p + 2 * SUPER;
+    HIP_TRY(hipMemcpyAsync(W.w2_thr.p, cuts.data(), (size_t)nf * 4, hipMemcpyHostToDevice, s));   // padding queries keep -inf
     for (uint32_t q0 = 0; q0 < nf; q0 += SUPER) {
         const uint32_t nb = std::min(SUPER, nf - q0);
-        vdb::FusedBf16Params fp = screen_params(ix, ix->cur, d_rowmask, d_status, capl, n_wg);
-        screen_queries(fp, ix, ix->cur->w2_qb.p, ix->cur->w2_qg.p, ix->cur->w2_thr.p, q0);
-        launch_filter_pass(ix, fp, s);
-        ix->cur->stats[3] += n;
-        vdb::SelectParams mp{};
-        mp.keys = ix->cur->w_pool.p; mp.sub_counts = ix->cur->w_subcnt.p; mp.n_sub = n_sub; mp.capl = capl; mp.wg_major = 1;
-        mp.kk = KMAX; mp.out_keys = ix->cur->w2_cand.p; mp.out_stride = KMAX; mp.out_cnt = d_cand_cnt;
-        mp.ovf = d_ovf2 + q0; mp.summary = nullptr; mp.flag_truncation = 1;
-        vdb::launch_select(mp, nb, s);
-        vdb::RerankParams rp = rerank_params(ix, d_rowmask, d_status, k, ix->cur->w2_cand.p, KMAX, d_cand_cnt);
-        rerank_io(rp, ix, ix->cur->w2_qp.p, ix->cur->w2_qnorm.p, ix->cur->w2_outi.p, ix->cur->w2_outd.p, ix->cur->w2_outc.p, d_cert2, q0);
+        cut_pass(ix, W, s, grid, d_rowmask, d_status, W.w2_qb.p, W.w2_qg.p, W.w2_thr.p, q0, nb, d_ovf2);
+        W.stats[STAT_ROWS_SCANNED] += n;
+        vdb::RerankParams rp = rerank_params(ix, d_rowmask, d_status, k, W.w2_cand.p, CUT_KMAX, cand_counts(W));
+        rerank_io(rp, ix, W.w2_qp.p, W.w2_qnorm.p, W.w2_outi.p, W.w2_outd.p, W.w2_outc.p, d_cert2, q0);
         if (k <= BF16_MAX_K) vdb::launch_rerank_all(rp, nb, s);
         else vdb::launch_rerank_all_large(rp, nb, s);
     }
     HIP_TRY(hipGetLastError());
     flags2.assign(2 * (size_t)nf, 0u);
-    HIP_TRY(hipMemcpyAsync(flags2.data(), ix->cur->w2_flags.p, 2 * (size_t)nf * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(flags2.data(), W.w2_flags.p, 2 * (size_t)nf * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     // only the queries this pass answered completely are written back
     std::vector<uint32_t> good;
@@ -572,9 +634,9 @@ int pass_rethreshold(Index* ix, hipStream_t s, const std::vector<uint32_t>& todo
         // scatter compact results j -> batch position todo[j] (the scatter kernel walks a (source, destination) list)
         std::vector<uint32_t> src_dst(2 * good.size());
         for (size_t i = 0; i < good.size(); ++i) { src_dst[i] = good[i]; src_dst[good.size() + i] = todo[good[i]]; }
-        if ((rc = ix->cur->w2_qidx.ensure(2 * good.size()))) return rc;
-        HIP_TRY(hipMemcpyAsync(ix->cur->w2_qidx.p, src_dst.data(), src_dst.size() * 4, hipMemcpyHostToDevice, s));
-        vdb::launch_scatter_results_list(ix->cur->w2_outi.p, ix->cur->w2_outd.p, ix->cur->w2_outc.p, ix->cur->w2_qidx.p, ix->cur->w2_qidx.p + good.size(),
+        if ((rc = W.w2_qidx.ensure(2 * good.size()))) return rc;
+        HIP_TRY(hipMemcpyAsync(W.w2_qidx.p, src_dst.data(), src_dst.size() * 4, hipMemcpyHostToDevice, s));
+        vdb::launch_scatter_results_list(W.w2_outi.p, W.w2_outd.p, W.w2_outc.p, W.w2_qidx.p, W.w2_qidx.p + good.size(),
                                          (uint32_t)good.size(), (uint32_t)k, d_out_ids, d_out_dists, d_out_counts, s);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(s));
@@ -594,45 +656,43 @@ bool direct_eligible(const Index* ix, size_t n_rows, size_t nq, size_t k) {
     return !(ix->tiers & VDB_TIERS_NO_DIRECT) && n_rows > 0 && n_rows <= SMALL_N && nq > 0 && nq <= DIRECT_MAX_Q && k > 0 && k <= MAX_SELECT;
 }
 
-int ensure_host_io(Index* ix, size_t bytes) {
-    return ix->cur->h_io.ensure(std::max<size_t>(bytes, 1u << 16));
+int ensure_host_io(Workspace& W, size_t bytes) {
+    return W.h_io.ensure(std::max<size_t>(bytes, 1u << 16));
 }
 
-static int search_direct(Index* ix, hipStream_t s, const float* d_q, uint32_t nq, size_t k, const uint32_t* d_rowmask,
+static int search_direct(Index* ix, Workspace& W, hipStream_t s, const float* d_q, uint32_t nq, size_t k, const uint32_t* d_rowmask,
                          uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts) {
     int rc;
-    Workspace* W = ix->cur;
+    
     const uint32_t n = ix->n_uploaded;
     if ((rc = ensure_ranks(ix))) return rc;
     // every workgroup of the scan keeps its k smallest keys only (k < 256): the select ranks n/256 * k keys instead of n
     const uint32_t keep = k < 256 ? (uint32_t)k : 0u;
     const uint32_t n_keys = keep ? vdb::small_scan_groups(n) * keep : n;
-    if ((rc = W->w_exact.ensure((size_t)nq * std::max(n_keys, n)))) return rc;
-    if ((rc = W->w_exsel.ensure((size_t)nq * MAX_SELECT + 8))) return rc;
-    if ((rc = W->w_cnt.ensure(4 * SUPER + 16))) return rc;
-    if (!W->dstat_ready) {
-        if ((rc = W->w_dstat.ensure(4))) return rc;
-        if ((rc = W->h_dstat.ensure(16))) return rc;
-        HIP_TRY(hipMemsetAsync(W->w_dstat.p, 0, 16, s));
-        W->dstat_ready = true;
+    if ((rc = W.w_exact.ensure((size_t)nq * std::max(n_keys, n)))) return rc;
+    if ((rc = W.w_exsel.ensure((size_t)nq * MAX_SELECT + 8))) return rc;
+    if ((rc = W.w_cnt.ensure(4 * SUPER + 16))) return rc;
+    if (!W.dstat_ready) {
+        if ((rc = W.w_dstat.ensure(4))) return rc;
+        if ((rc = W.h_dstat.ensure(16))) return rc;
+        HIP_TRY(hipMemsetAsync(W.w_dstat.p, 0, 16, s));
+        W.dstat_ready = true;
     }
     vdb::SmallScanParams sp{rows_f32(ix), ix->ld, ix->dim, n, d_q, nq, ix->d_nd, d_rowmask, ix->ids_monotone ? nullptr : ix->d_idrank.p,
-                            ix->metric, W->w_exact.p, n_keys, keep, W->w_dstat.p};
+                            ix->metric, W.w_exact.p, n_keys, keep, W.w_dstat.p};
     vdb::launch_small_scan(sp, s);
-    vdb::SelectParams mp{};
-    mp.keys = W->w_exact.p; mp.stride = n_keys; mp.counts = nullptr; mp.n_fixed = n_keys; mp.cap = n_keys;
-    mp.kk = (uint32_t)k; mp.out_keys = W->w_exsel.p; mp.out_stride = MAX_SELECT; mp.out_cnt = W->w_cnt.p;
-    mp.emit_ids = d_out_ids; mp.emit_dists = d_out_dists; mp.emit_counts = d_out_counts; mp.emit_stride = (uint32_t)k;
-    mp.emit_rank2row = ix->ids_monotone ? nullptr : ix->d_rank2row.p; mp.emit_row_ids = ix->d_row_ids;
-    mp.emit_status_in = W->w_dstat.p; mp.emit_status = W->h_dstat.d;
+    vdb::SelectParams mp = emit_select_params(ix, W, k);
+    mp.keys = W.w_exact.p; mp.stride = n_keys; mp.counts = nullptr; mp.n_fixed = n_keys; mp.cap = n_keys;
+    mp.emit_ids = d_out_ids; mp.emit_dists = d_out_dists; mp.emit_counts = d_out_counts;
+    mp.emit_status_in = W.w_dstat.p; mp.emit_status = W.h_dstat.d;
     vdb::launch_select(mp, nq, s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
     uint32_t status = 0;
-    for (uint32_t q = 0; q < nq; ++q) status |= W->h_dstat[q];
-    ix->cur->stats[1] = nq;                                         // answered by an exact scan
+    for (uint32_t q = 0; q < nq; ++q) status |= W.h_dstat[q];
+    W.stats[STAT_EXACT] = nq;                                      // answered by an exact scan
     if (status) {                                                  // (rare: leave the device word clean for the next search)
-        HIP_TRY(hipMemsetAsync(W->w_dstat.p, 0, 16, s));
+        HIP_TRY(hipMemsetAsync(W.w_dstat.p, 0, 16, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
     if (status & vdb::ST_ZERO_QUERY) return fail_zero_vector();
@@ -659,11 +719,11 @@ size_t sparse_limit(size_t n_rows, size_t ld, size_t dim, size_t nq) {
 }
 
 // E = set bits of the row mask below n_uploaded, read back to the host (one synchronisation)
-int eligible_count(Index* ix, hipStream_t s, const uint32_t* d_rowmask, uint32_t* out_E) {
+int eligible_count(Index* ix, Workspace& W, hipStream_t s, const uint32_t* d_rowmask, uint32_t* out_E) {
     int rc;
     const uint32_t n = ix->n_uploaded, nb = vdb::sparse_list_blocks(n);
-    if ((rc = ix->cur->w_eligblk.ensure(2 * (size_t)nb + 4))) return rc;
-    uint32_t* blk = ix->cur->w_eligblk.p;
+    if ((rc = W.w_eligblk.ensure(2 * (size_t)nb + 4))) return rc;
+    uint32_t* blk = W.w_eligblk.p;
     vdb::launch_sparse_count(d_rowmask, n, blk, blk + nb, blk + 2 * (size_t)nb, s);
     HIP_TRY(hipGetLastError());
     uint32_t E = 0;
@@ -674,50 +734,39 @@ int eligible_count(Index* ix, hipStream_t s, const uint32_t* d_rowmask, uint32_t
     return VDB_OK;
 }
 // ... and the list itself, w_elig[0..E), from the block offsets eligible_count left behind
-int eligible_list(Index* ix, hipStream_t s, const uint32_t* d_rowmask, uint32_t E) {
+int eligible_list(Index* ix, Workspace& W, hipStream_t s, const uint32_t* d_rowmask, uint32_t E) {
     int rc;
     const uint32_t n = ix->n_uploaded, nb = vdb::sparse_list_blocks(n);
-    if ((rc = ix->cur->w_elig.ensure(std::max<size_t>(E, 1)))) return rc;
-    vdb::launch_sparse_scatter(d_rowmask, n, ix->cur->w_eligblk.p + nb, ix->cur->w_elig.p, E, s);
+    if ((rc = W.w_elig.ensure(std::max<size_t>(E, 1)))) return rc;
+    vdb::launch_sparse_scatter(d_rowmask, n, W.w_eligblk.p + nb, W.w_elig.p, E, s);
     HIP_TRY(hipGetLastError());
     return VDB_OK;
 }
 
-static int search_sparse(Index* ix, hipStream_t s, const float* d_q, uint32_t nq, size_t dim, size_t k, uint32_t E,
+static int search_sparse(Index* ix, Workspace& W, hipStream_t s, const float* d_q, uint32_t nq, size_t dim, size_t k, uint32_t E,
                          const uint32_t* d_rowmask, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts) {
     int rc;
-    Workspace* W = ix->cur;
-    const uint32_t n = ix->n_uploaded, ld = ix->ld, bp_all = round_up(nq, SUPER);
-    // queries: the zero-padded block and the exact-order norms; query_prep raises ST_ZERO_QUERY (also when nothing is eligible)
-    if ((rc = W->w_qp.ensure((size_t)bp_all * ld))) return rc;
-    if ((rc = W->w_qnorm.ensure(bp_all))) return rc;
-    if ((rc = W->w_thr.ensure(bp_all))) return rc;
-    if ((rc = W->w_flags.ensure(4 + 3 * (size_t)nq))) return rc;
-    uint32_t* d_status = W->w_flags.p;
-    HIP_TRY(hipMemsetAsync(d_status, 0, 16, s));
-    W->status_dirty = true;                                        // (the tiers' bookkeeping: the block is cleared again before its next use)
-    vdb::QueryPrepParams qp{d_q, (uint32_t)dim, nq, W->w_qp.p, ld, bp_all, W->w_qnorm.p, W->w_thr.p, ix->metric, d_status,
-                            nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr};
-    vdb::launch_query_prep(qp, s);
+    
+    const uint32_t n = ix->n_uploaded, ld = ix->ld;
+    // (ST_ZERO_QUERY is raised also when nothing is eligible)
+    if ((rc = prep_exact_queries(ix, W, s, d_q, nq, dim))) return rc;
+    uint32_t* d_status = SearchFlags(W.w_flags.p, nq).status;
     if (E == 0) HIP_TRY(hipMemsetAsync(d_out_counts, 0, (size_t)nq * 4, s));
     else {
         if ((rc = ensure_ranks(ix))) return rc;
-        if ((rc = eligible_list(ix, s, d_rowmask, E))) return rc;
+        if ((rc = eligible_list(ix, W, s, d_rowmask, E))) return rc;
         const uint32_t stride = round_up(E, vdb::SPARSE_TILE_R);
-        if ((rc = W->w_exact.ensure((size_t)std::min(nq, SUPER) * stride))) return rc;
-        if ((rc = W->w_exsel.ensure((size_t)SUPER * MAX_SELECT + 8))) return rc;
-        if ((rc = W->w_cnt.ensure(4 * SUPER + 16))) return rc;
+        if ((rc = W.w_exact.ensure((size_t)std::min(nq, SUPER) * stride))) return rc;
+        if ((rc = W.w_exsel.ensure((size_t)SUPER * MAX_SELECT + 8))) return rc;
+        if ((rc = W.w_cnt.ensure(4 * SUPER + 16))) return rc;
         for (uint32_t q0 = 0; q0 < nq; q0 += SUPER) {              // passes of SUPER queries: the key buffer stays bounded
             const uint32_t nb = std::min(SUPER, nq - q0);
-            vdb::SparseScanParams sp{rows_f32(ix), ld, ix->dim, n, W->w_elig.p, E, W->w_qp.p + (size_t)q0 * ld, W->w_qnorm.p + q0, nb,
-                                     ix->d_nd, ix->ids_monotone ? nullptr : ix->d_idrank.p, ix->metric, W->w_exact.p, stride, d_status};
+            vdb::SparseScanParams sp{rows_f32(ix), ld, ix->dim, n, W.w_elig.p, E, W.w_qp.p + (size_t)q0 * ld, W.w_qnorm.p + q0, nb,
+                                     ix->d_nd, ix->ids_monotone ? nullptr : ix->d_idrank.p, ix->metric, W.w_exact.p, stride, d_status};
             vdb::launch_sparse_scan(sp, s);
-            vdb::SelectParams mp{};
-            mp.keys = W->w_exact.p; mp.stride = stride; mp.counts = nullptr; mp.n_fixed = stride; mp.cap = stride;
-            mp.kk = (uint32_t)k; mp.out_keys = W->w_exsel.p; mp.out_stride = MAX_SELECT; mp.out_cnt = W->w_cnt.p;
+            vdb::SelectParams mp = emit_select_params(ix, W, k);
+            mp.keys = W.w_exact.p; mp.stride = stride; mp.counts = nullptr; mp.n_fixed = stride; mp.cap = stride;
             mp.emit_ids = d_out_ids + (size_t)q0 * k; mp.emit_dists = d_out_dists + (size_t)q0 * k; mp.emit_counts = d_out_counts + q0;
-            mp.emit_stride = (uint32_t)k;
-            mp.emit_rank2row = ix->ids_monotone ? nullptr : ix->d_rank2row.p; mp.emit_row_ids = ix->d_row_ids;
             vdb::launch_select(mp, nb, s);
         }
     }
@@ -725,7 +774,7 @@ static int search_sparse(Index* ix, hipStream_t s, const float* d_q, uint32_t nq
     uint32_t st[4] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(st, d_status, 16, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    W->stats[1] = nq;                                              // answered by an exact scan
+    W.stats[STAT_EXACT] = nq;                                      // answered by an exact scan
     ix->sparse_last = 1; ++ix->sparse_count;
     if (st[0] & vdb::ST_ZERO_QUERY) return fail_zero_vector();
     if (st[0] & vdb::ST_NAN) return fail_nan();
@@ -746,21 +795,21 @@ int query_dim_check(const Index* ix, size_t dim) {
 
 // Part 1: checks, workspace, and the FIRST tier enqueued on the stream -- no host synchronisation unless the search is
 // one of the cases answered completely here (empty store, k = 0, k too large for the MFMA tiers).
-int search_part1(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, const uint64_t* d_idmask,
+int search_part1(Index* ix, Workspace& W, const float* d_q, size_t nq, size_t dim, size_t k, const uint64_t* d_idmask,
                  size_t mask_bits, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                  hipStream_t user_stream, bool allow_alt) {
     int rc;
-    ix->cur->ctx.pending = false;
+    W.ctx.pending = false;
     ix->sparse_last = 0;
     if ((rc = set_device(ix))) return rc;
     if ((rc = flush(ix))) return rc;
     if (nq == 0) return VDB_OK;
     // all launches of this search go to the caller's stream when one is given (so that the caller's
     // events bracket them); the workspace is protected by the handle mutex and the final sync
-    hipStream_t s = user_stream ? user_stream : ix->cur->stream;
-    memset(ix->cur->stats, 0, sizeof(ix->cur->stats));
-    ix->cur->stats[14] = shadow_usable(ix) ? 1u : 0u;   // the screening pass reads the bf16 shadow rows
-    ix->cur->stats[15] = ix->kn.any ? 1u : 0u;          // diagnostics build with a knob set: the run is NOT covered by the exactness guarantee
+    hipStream_t s = user_stream ? user_stream : W.stream;
+    memset(W.stats, 0, sizeof(W.stats));
+    W.stats[STAT_SHADOW] = shadow_usable(ix) ? 1u : 0u;   // the screening pass reads the bf16 shadow rows
+    W.stats[STAT_DIAG] = ix->kn.any ? 1u : 0u;            // diagnostics build with a knob set: the run is NOT covered by the exactness guarantee
     const auto t_entry = std::chrono::steady_clock::now();
     auto since = [&]() { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_entry).count(); };
     size_t total_rows = ix->n_live + ix->misfits.size();
@@ -769,14 +818,7 @@ int search_part1(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, c
         HIP_TRY(hipStreamSynchronize(s));
         return VDB_OK;
     }
-    if ((rc = query_dim_check(ix, dim))) return rc;
-    if (ix->metric == vdb::COSINE) {
-        if ((rc = ensure_zero_count(ix))) return rc;
-        if (ix->zero_live)   // distance.rs:51-55 aborts the whole search (flat_index.rs:57-60)
-            return fail_zero_vector();
-    }
-    if (nq > 0x7fffffffull / 2 || k > 0x7fffffffull) return fail(VDB_ERR_INVALID_ARGUMENT, "batch too large");
-    if (ix->dim > 16384) return fail(VDB_ERR_INVALID_ARGUMENT, "dimension %u exceeds the supported 16384", ix->dim);
+    if ((rc = pre_device_checks(ix, dim, nq > 0x7fffffffull / 2 || k > 0x7fffffffull))) return rc;
 
     const uint32_t n = ix->n_uploaded;
     const uint32_t ld = ix->ld;
@@ -788,90 +830,82 @@ int search_part1(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, c
     // whenever the select can hold k and the list fits; mode 2 also asks the measured cost limit and leaves small indexes to the
     // direct path.  Answered completely here, like the direct path; otherwise the search goes on below as if nothing had happened.
     if (ix->sparse_mode && d_idmask) {
-        if ((rc = ix->cur->w_rowmask.ensure((n + 31) / 32))) return rc;
-        vdb::launch_build_rowmask(ix->d_row_ids, (ix->n_live == n) ? nullptr : ix->d_live, d_idmask, mask_bits, n, ix->cur->w_rowmask.p, s);
+        const uint32_t* d_rowmask;
+        if ((rc = eligibility_mask(ix, W, s, d_idmask, mask_bits, &d_rowmask))) return rc;
         uint32_t E = 0;
-        if ((rc = eligible_count(ix, s, ix->cur->w_rowmask.p, &E))) return rc;
+        if ((rc = eligible_count(ix, W, s, d_rowmask, &E))) return rc;
         ix->sparse_E = E;
         bool take = k <= MAX_SELECT && E <= SPARSE_MAX_E;
         if (ix->sparse_mode == 2) take = take && !direct_eligible(ix, n, nq, k) && E <= sparse_limit(n, ld, ix->dim, nq);
         if (take) {
-            rc = search_sparse(ix, s, d_q, nq32, dim, k, E, ix->cur->w_rowmask.p, d_out_ids, d_out_dists, d_out_counts);
-            ix->cur->stats[10] = ix->cur->stats[11] = ix->cur->stats[12] = since();
+            rc = search_sparse(ix, W, s, d_q, nq32, dim, k, E, d_rowmask, d_out_ids, d_out_dists, d_out_counts);
+            W.stats[STAT_ENQUEUED_NS] = W.stats[STAT_FLAGS_NS] = W.stats[STAT_TOTAL_NS] = since();
             return rc;
         }
     }
 
     // ---- small index, a few queries: the direct exact path (two kernels, answered completely here)
     if (direct_eligible(ix, n, nq, k)) {
-        const uint32_t* d_rowmask = (ix->n_live == n) ? nullptr : ix->d_live;
-        if (d_idmask) {
-            if ((rc = ix->cur->w_rowmask.ensure((n + 31) / 32))) return rc;
-            vdb::launch_build_rowmask(ix->d_row_ids, d_rowmask, d_idmask, mask_bits, n, ix->cur->w_rowmask.p, s);
-            d_rowmask = ix->cur->w_rowmask.p;
-        }
-        rc = search_direct(ix, s, d_q, nq32, k, d_rowmask, d_out_ids, d_out_dists, d_out_counts);
-        ix->cur->stats[10] = ix->cur->stats[11] = ix->cur->stats[12] = since();
+        const uint32_t* d_rowmask;
+        if ((rc = eligibility_mask(ix, W, s, d_idmask, mask_bits, &d_rowmask))) return rc;
+        rc = search_direct(ix, W, s, d_q, nq32, k, d_rowmask, d_out_ids, d_out_dists, d_out_counts);
+        W.stats[STAT_ENQUEUED_NS] = W.stats[STAT_FLAGS_NS] = W.stats[STAT_TOTAL_NS] = since();
         return rc;
     }
 
     // ---- workspace
-    if ((rc = ix->cur->w_qp.ensure((size_t)bp_all * ld))) return rc;
-    if ((rc = ix->cur->w_qnorm.ensure(bp_all))) return rc;
-    if ((rc = ix->cur->w_thr.ensure(bp_all))) return rc;
-    if ((rc = ix->cur->w_flags.ensure(4 + 3 * (size_t)nq32))) return rc;      // status block | cert | overflow | score cut per query
-    if ((rc = ix->cur->h_flags.ensure(4 + 3 * (size_t)nq32))) return rc;
-    uint32_t* d_status = ix->cur->w_flags.p;        // [0] status bits
-    uint32_t* d_cert = ix->cur->w_flags.p + 4;      // [nq]
-    uint32_t* d_ovf = d_cert + nq32;           // [nq]
+    if ((rc = W.w_qp.ensure((size_t)bp_all * ld))) return rc;
+    if ((rc = W.w_qnorm.ensure(bp_all))) return rc;
+    if ((rc = W.w_thr.ensure(bp_all))) return rc;
+    const size_t flag_words = SearchFlags::words(nq32);           // status block | cert | overflow | score cut per query
+    if ((rc = W.w_flags.ensure(flag_words))) return rc;
+    if ((rc = W.h_flags.ensure(flag_words))) return rc;
+    const SearchFlags df(W.w_flags.p, nq32);
+    uint32_t* const d_status = df.status;
     // the per-query flags are zeroed by query_prep; the 16-byte status block only needs a memset when the last
     // search left it set (or the buffer is new) -- one launch less at the head of every search
     const bool flags_by_prep = kp != 0 || (ix->screen && plan_bf16(ix, n, k).kp);
-    if (!flags_by_prep) HIP_TRY(hipMemsetAsync(ix->cur->w_flags.p, 0, (4 + 3 * (size_t)nq32) * 4, s));
-    else if (ix->cur->status_dirty || ix->cur->w_flags.p != ix->cur->status_buf) {
-        HIP_TRY(hipMemsetAsync(ix->cur->w_flags.p, 0, 16, s));
-        ix->cur->status_buf = ix->cur->w_flags.p;
+    if (!flags_by_prep) HIP_TRY(hipMemsetAsync(W.w_flags.p, 0, flag_words * 4, s));
+    else if (W.status_dirty || W.w_flags.p != W.status_buf) {
+        HIP_TRY(hipMemsetAsync(d_status, 0, STATUS_BYTES, s));
+        W.status_buf = W.w_flags.p;
     }
-    ix->cur->status_dirty = true;                               // until a clean status word has been read back
+    W.status_dirty = true;                               // until a clean status word has been read back
 
-    // ---- eligibility mask: tombstones, optionally AND the caller's id filter
-    const uint32_t* d_rowmask = (ix->n_live == n) ? nullptr : ix->d_live;
-    if (d_idmask) {
-        if ((rc = ix->cur->w_rowmask.ensure((n + 31) / 32))) return rc;
-        vdb::launch_build_rowmask(ix->d_row_ids, d_rowmask, d_idmask, mask_bits, n, ix->cur->w_rowmask.p, s);
-        d_rowmask = ix->cur->w_rowmask.p;
-    }
+    const uint32_t* d_rowmask;
+    if ((rc = eligibility_mask(ix, W, s, d_idmask, mask_bits, &d_rowmask))) return rc;
 
     // ---- queries: zero-padded copy + exact-order norms
     {
         uint16_t* qb = nullptr;
         if (ix->screen && plan_bf16(ix, n, k).kp) {
-            if ((rc = ix->cur->w_qb.ensure((size_t)bp_all * ld))) return rc;
-            if ((rc = ix->cur->w_qerr.ensure(bp_all))) return rc;
-            if ((rc = ix->cur->w_qg.ensure(bp_all))) return rc;
-            qb = ix->cur->w_qb.p;
+            if ((rc = W.w_qb.ensure((size_t)bp_all * ld))) return rc;
+            if ((rc = W.w_qerr.ensure(bp_all))) return rc;
+            if ((rc = W.w_qg.ensure(bp_all))) return rc;
+            qb = W.w_qb.p;
         }
-        vdb::QueryPrepParams qp{d_q, (uint32_t)dim, nq32, ix->cur->w_qp.p, ld, bp_all, ix->cur->w_qnorm.p, ix->cur->w_thr.p, ix->metric, d_status, qb,
-                                ix->cur->w_qerr.p, (qb && ix->d_margin) ? ix->cur->w_qg.p : nullptr, margin_plan(ix).kappa,
-                                flags_by_prep ? d_cert : nullptr, flags_by_prep ? d_ovf : nullptr};
+        vdb::QueryPrepParams qp{d_q, (uint32_t)dim, nq32, W.w_qp.p, ld, bp_all, W.w_qnorm.p, W.w_thr.p, ix->metric, d_status, qb,
+                                W.w_qerr.p, (qb && ix->d_margin) ? W.w_qg.p : nullptr, margin_plan(ix).kappa,
+                                flags_by_prep ? df.cert : nullptr, flags_by_prep ? df.ovf : nullptr};
         vdb::launch_query_prep(qp, s);
     }
 
     if (kp == 0 && !(ix->screen && plan_bf16(ix, n, k).kp)) {
         // large k: exact scan for every query
-        HIP_TRY(hipMemcpyAsync(ix->cur->h_flags, ix->cur->w_flags.p, 16, hipMemcpyDeviceToHost, s));
+        const SearchFlags hf(W.h_flags, nq32);
+        HIP_TRY(hipMemcpyAsync(hf.status, d_status, STATUS_BYTES, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        if (ix->cur->h_flags[0] & vdb::ST_ZERO_QUERY)
+        if (hf.status[0] & vdb::ST_ZERO_QUERY)
             return fail_zero_vector();
         for (uint32_t q = 0; q < nq32; ++q) {
-            if ((rc = exact_one(ix, s, q, k, d_rowmask, d_out_ids + (size_t)q * k, d_out_dists + (size_t)q * k,
+            if ((rc = exact_one(ix, W, s, q, k, d_rowmask, d_out_ids + (size_t)q * k, d_out_dists + (size_t)q * k,
                                 d_out_counts + q)))
                 return rc;
         }
-        ix->cur->stats[1] = nq32;
-        HIP_TRY(hipMemcpyAsync(ix->cur->h_flags, ix->cur->w_flags.p, 16, hipMemcpyDeviceToHost, s));
+        W.stats[STAT_EXACT] = nq32;
+        HIP_TRY(hipMemcpyAsync(hf.status, d_status, STATUS_BYTES, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        if (ix->cur->h_flags[0] & vdb::ST_NAN) return fail_nan();
+        if (hf.status[0] & vdb::ST_NAN) return fail_nan();
         return VDB_OK;
     }
 
@@ -879,22 +913,22 @@ int search_part1(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, c
     // are re-run as a compact block by the f32 MFMA tier; whatever that cannot certify goes to the exact scan.
     const Bf16Plan pl16 = ix->screen ? plan_bf16(ix, n, k) : Bf16Plan{};
     const uint32_t kp16 = pl16.kp;
-    if ((rc = ix->cur->w_cnt.ensure(4 * SUPER + 16))) return rc;
+    if ((rc = W.w_cnt.ensure(4 * SUPER + 16))) return rc;
     if (kp16) {
-        ix->cur->stats[8] = 1;
-        ix->cur->stats[5] = kp16;
-        if ((rc = pass_bf16(ix, s, nq32, k, pl16, d_rowmask, d_out_ids, d_out_dists, d_out_counts, d_cert, d_ovf, d_status,
-                            reinterpret_cast<float*>(d_ovf + nq32), allow_alt)))
+        W.stats[STAT_SCREENED] = 1;
+        W.stats[STAT_KP] = kp16;
+        if ((rc = pass_bf16(ix, W, s, nq32, k, pl16, d_rowmask, d_out_ids, d_out_dists, d_out_counts, df.cert, df.ovf, d_status,
+                            df.cut, allow_alt)))
             return rc;
     } else {
-        if ((rc = pass_f32(ix, s, ix->cur->w_qp.p, ix->cur->w_qnorm.p, ix->cur->w_thr.p, nq32, k, kp, d_rowmask, d_out_ids, d_out_dists,
-                           d_out_counts, d_cert, d_ovf, d_status)))
+        if ((rc = pass_f32(ix, W, s, W.w_qp.p, W.w_qnorm.p, W.w_thr.p, nq32, k, kp, d_rowmask, d_out_ids, d_out_dists,
+                           d_out_counts, df.cert, df.ovf, d_status, true)))
             return rc;
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(ix->cur->h_flags, ix->cur->w_flags.p, (4 + 3 * (size_t)nq32) * 4, hipMemcpyDeviceToHost, s));
-    ix->cur->stats[10] = since();                       // host time until everything of the first tier is enqueued, ns
-    Workspace::SearchCtx& c = ix->cur->ctx;
+    HIP_TRY(hipMemcpyAsync(W.h_flags, W.w_flags.p, flag_words * 4, hipMemcpyDeviceToHost, s));
+    W.stats[STAT_ENQUEUED_NS] = since();                      // host time until everything of the first tier is enqueued, ns
+    Workspace::SearchCtx& c = W.ctx;
     c.pending = true; c.nq32 = nq32; c.kp = kp; c.kp16 = kp16; c.k = k; c.s = s; c.d_rowmask = d_rowmask;
     c.d_out_ids = d_out_ids; c.d_out_dists = d_out_dists; c.d_out_counts = d_out_counts; c.t_entry = t_entry;
     return VDB_OK;
@@ -902,9 +936,9 @@ int search_part1(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, c
 
 // Part 2: wait for the first tier, read its flags, run the fallback tiers for the queries it could not certify.
 // *changed (may be null) tells whether outputs were rewritten after part 1's pass.
-int search_part2(Index* ix, int* changed) {
+int search_part2(Index* ix, Workspace& W, int* changed) {
     if (changed) *changed = 0;
-    Workspace::SearchCtx& c = ix->cur->ctx;
+    Workspace::SearchCtx& c = W.ctx;
     if (!c.pending) return VDB_OK;
     c.pending = false;
     int rc;
@@ -913,108 +947,80 @@ int search_part2(Index* ix, int* changed) {
     hipStream_t s = c.s;
     const uint32_t* d_rowmask = c.d_rowmask;
     uint64_t* d_out_ids = c.d_out_ids; float* d_out_dists = c.d_out_dists; uint32_t* d_out_counts = c.d_out_counts;
-    uint32_t* d_status = ix->cur->w_flags.p;
+    uint32_t* d_status = SearchFlags(W.w_flags.p, nq32).status;
+    const SearchFlags hf(W.h_flags, nq32);                        // the first tier's flags, once the stream has been waited for
     const auto t_entry = c.t_entry;
     auto since = [&]() { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_entry).count(); };
     HIP_TRY(hipStreamSynchronize(s));
-    ix->cur->stats[11] = since();                       // ... until the first tier's flags are on the host, ns
-    uint32_t status = ix->cur->h_flags[0];
+    W.stats[STAT_FLAGS_NS] = since();            // ... until the first tier's flags are on the host, ns
+    uint32_t status = hf.status[0];
     if (status & vdb::ST_ZERO_QUERY) return fail_zero_vector();
-    // vdb_flat_set_tiers: forced hand-over to the slower tiers (tests); every tier returns the same results
-    const bool force_exact = (ix->tiers & VDB_TIERS_FORCE_EXACT) != 0;
-    const bool force_f32 = (ix->tiers & VDB_TIERS_FORCE_F32) != 0;
-    const bool no_rethr = (ix->tiers & VDB_TIERS_NO_RETHRESHOLD) != 0;
-    const bool force_rethr = kp16 && force_rethreshold(ix);       // every query with a cut takes the re-threshold pass as well
+    // the hand-over (vdb_flags.h): who is settled, who takes the re-threshold pass.  vdb_flat_set_tiers forces it (tests); every
+    // tier returns the same results
+    TierTriage tri = tier_triage(hf.cert, hf.ovf, hf.cut, nq32, ix->tiers, kp16, kp);
+    W.stats[STAT_OVERFLOW] += tri.n_overflow;
+    W.stats[STAT_UNCERTIFIED] += tri.n_uncertified;
+    if (changed && !tri.todo.empty()) *changed = 1;
     std::vector<uint32_t> todo;
-    for (uint32_t q = 0; q < nq32; ++q) {
-        bool cert = ix->cur->h_flags[4 + q] != 0, ovf = ix->cur->h_flags[4 + nq32 + q] != 0;
-        if (ovf) ++ix->cur->stats[2];
-        if (!cert) ++ix->cur->stats[6];
-        if (cert && !ovf && !force_exact && !(kp16 && force_f32) && !force_rethr) continue;
-        todo.push_back(q);
-    }
-    if (changed && !todo.empty()) *changed = 1;
-    if (kp16 && !todo.empty() && !no_rethr && !force_exact && !force_f32) {
+    if (tri.rethreshold) {
         // ---- tier 0b: queries with a known score cut get one more HBM-bound pass with that cut as the threshold
-        const uint32_t* h_ovf = ix->cur->h_flags + 4 + nq32;
-        const float* h_cut = reinterpret_cast<const float*>(ix->cur->h_flags + 4 + 2 * (size_t)nq32);
-        std::vector<uint32_t> sel, rest;
-        std::vector<float> cuts;
-        for (uint32_t q : todo) {
-            const float c = h_cut[q];
-            if (!h_ovf[q] && c == c && std::isfinite(c)) { sel.push_back(q); cuts.push_back(c); }
-            else rest.push_back(q);
-        }
-        if (!sel.empty()) {
+        if (!tri.sel.empty()) {
             std::vector<uint32_t> fl;
-            if ((rc = pass_rethreshold(ix, s, sel, cuts, k, d_rowmask, d_out_ids, d_out_dists, d_out_counts, d_status, fl))) return rc;
-            const uint32_t nf = (uint32_t)sel.size();
-            for (uint32_t j = 0; j < nf; ++j) {
-                if (fl[j] && !fl[nf + j]) ++ix->cur->stats[13];
-                else { rest.push_back(sel[j]); if (fl[nf + j]) ++ix->cur->stats[2]; }
-            }
-            std::sort(rest.begin(), rest.end());
+            if ((rc = pass_rethreshold(ix, W, s, tri.sel, tri.cuts, k, d_rowmask, d_out_ids, d_out_dists, d_out_counts, d_status, fl))) return rc;
+            W.stats[STAT_RETHRESHOLD] += after_rethreshold(tri.sel, fl, tri.rest, &W.stats[STAT_OVERFLOW]);
         }
-        todo.swap(rest);
-    }
+        todo.swap(tri.rest);
+    } else todo.swap(tri.todo);
     if (kp16 && !todo.empty()) {
         // ---- second tier: the uncertified queries as one compact block through the f32 MFMA pipeline
         const uint32_t nf = (uint32_t)todo.size();
-        ix->cur->stats[9] = nf;
-        if ((rc = gather_compact(ix, s, todo, k, true))) return rc;
-        if (kp == 0) {
+        W.stats[STAT_TO_F32] = nf;
+        if ((rc = gather_compact(ix, W, s, todo, k, true))) return rc;
+        if (!tri.f32_tier) {
             // k too large for the f32 tier (the large-k screening tier's uncertified queries): straight to the exact scan (flags stay 0)
         } else {
-            if ((rc = pass_f32(ix, s, ix->cur->w2_qp.p, ix->cur->w2_qnorm.p, ix->cur->w2_thr.p, nf, k, kp, d_rowmask, ix->cur->w2_outi.p,
-                               ix->cur->w2_outd.p, ix->cur->w2_outc.p, ix->cur->w2_flags.p, ix->cur->w2_flags.p + nf, d_status)))
+            if ((rc = pass_f32(ix, W, s, W.w2_qp.p, W.w2_qnorm.p, W.w2_thr.p, nf, k, kp, d_rowmask, W.w2_outi.p,
+                               W.w2_outd.p, W.w2_outc.p, W.w2_flags.p, W.w2_flags.p + nf, d_status, false)))
                 return rc;
-            vdb::launch_scatter_results(ix->cur->w2_outi.p, ix->cur->w2_outd.p, ix->cur->w2_outc.p, ix->cur->w2_qidx.p, nf, (uint32_t)k,
+            vdb::launch_scatter_results(W.w2_outi.p, W.w2_outd.p, W.w2_outc.p, W.w2_qidx.p, nf, (uint32_t)k,
                                         d_out_ids, d_out_dists, d_out_counts, s);
         }
         HIP_TRY(hipGetLastError());
-        std::vector<uint32_t> f2(2 * (size_t)nf + 4);
-        HIP_TRY(hipMemcpyAsync(f2.data(), ix->cur->w2_flags.p, 2 * (size_t)nf * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(f2.data() + 2 * (size_t)nf, ix->cur->w_flags.p, 16, hipMemcpyDeviceToHost, s));
+        std::vector<uint32_t> f2(2 * (size_t)nf + STATUS_WORDS);   // cert | overflow of the compact block | the status block
+        HIP_TRY(hipMemcpyAsync(f2.data(), W.w2_flags.p, 2 * (size_t)nf * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(f2.data() + 2 * (size_t)nf, d_status, STATUS_BYTES, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         status |= f2[2 * (size_t)nf];
         if (status & vdb::ST_ZERO_QUERY)
             return fail_zero_vector();
-        std::vector<uint32_t> todo2;
-        for (uint32_t j = 0; j < nf; ++j) {
-            bool cert = f2[j] != 0, ovf = f2[nf + j] != 0;
-            if (ovf) ++ix->cur->stats[2];
-            if (cert && !ovf && !force_exact) continue;
-            todo2.push_back(todo[j]);
-        }
-        todo.swap(todo2);
+        todo = after_f32(todo, f2.data(), ix->tiers, &W.stats[STAT_OVERFLOW]);
     }
     // ---- exact fallback for the queries the MFMA tiers could not certify.  Up to 8 of them share one pass
     // over the rows; a row survives for a query only if its exact distance is <= the k-th exact distance
     // the re-rank already found (a valid upper bound), so each query is left with a handful of keys.
-    uint32_t n_fallback = 0;
-    n_fallback = (uint32_t)todo.size();
+    const uint32_t n_fallback = (uint32_t)todo.size();
     if (!todo.empty()) {
         std::vector<uint32_t> dense;                             // queries whose bounded pass overflowed
-        if ((rc = bounded_scan_queries(ix, s, todo, (uint32_t)k, nullptr, d_rowmask, d_out_ids, d_out_dists, d_out_counts, nullptr,
+        if ((rc = bounded_scan_queries(ix, W, s, todo, (uint32_t)k, nullptr, d_rowmask, d_out_ids, d_out_dists, d_out_counts, nullptr,
                                        d_status, dense)))
             return rc;
         for (uint32_t q : dense)
-            if ((rc = exact_one(ix, s, q, k, d_rowmask, d_out_ids + (size_t)q * k, d_out_dists + (size_t)q * k,
+            if ((rc = exact_one(ix, W, s, q, k, d_rowmask, d_out_ids + (size_t)q * k, d_out_dists + (size_t)q * k,
                                 d_out_counts + q)))
                 return rc;
     }
-    ix->cur->stats[12] = since();                       // whole call, ns
-    ix->cur->stats[0] = nq32 - n_fallback;
-    ix->cur->stats[1] = n_fallback;
+    W.stats[STAT_TOTAL_NS] = since();            // whole call, ns
+    W.stats[STAT_MFMA] = nq32 - n_fallback;
+    W.stats[STAT_EXACT] = n_fallback;
     uint32_t st2 = status;
     if (n_fallback) {
-        HIP_TRY(hipMemcpyAsync(ix->cur->h_flags, ix->cur->w_flags.p, 16, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(hf.status, d_status, STATUS_BYTES, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        st2 |= ix->cur->h_flags[0];
+        st2 |= hf.status[0];
     }
     // status bits, the summary word, or a query norm beyond the kernels' no-NaN domain (word 2 is a running maximum: tame
     // values may stay, a wild one must not outlive its search)
-    ix->cur->status_dirty = st2 != 0 || ix->cur->stats[6] != 0 || ix->cur->stats[2] != 0 || ix->cur->h_flags[2] > 0x53800000u;
+    W.status_dirty = st2 != 0 || W.stats[STAT_UNCERTIFIED] != 0 || W.stats[STAT_OVERFLOW] != 0 || *status_qmax(hf.status) > 0x53800000u;
     if (st2 & vdb::ST_NAN)
         return fail_nan();
     return VDB_OK;
@@ -1032,11 +1038,11 @@ int search_part2(Index* ix, int* changed) {
 //   3. dense fallback: more than 32768 survivors -> exact_one for the first max_results (all within the radius); the total is
 //      route 2's counter.
 // (the caller checked the radii: none is NaN)
-static int range_search_run(Index* ix, const float* d_q, size_t nq, size_t dim, const float* d_radii,
+static int range_search_run(Index* ix, Workspace& W, const float* d_q, size_t nq, size_t dim, const float* d_radii,
                             const uint64_t* d_idmask, size_t mask_bits, size_t max_results, uint64_t* d_out_ids, float* d_out_dists,
                             uint32_t* d_out_counts, uint64_t* d_out_totals, hipStream_t s, uint64_t* st) {
     int rc;
-    Workspace* W = ix->cur;
+    
     const size_t total_rows = ix->n_live + ix->misfits.size();
     if (total_rows == 0) {                                         // as the searches: an empty store answers before any check
         HIP_TRY(hipMemsetAsync(d_out_counts, 0, nq * 4, s));
@@ -1044,109 +1050,78 @@ static int range_search_run(Index* ix, const float* d_q, size_t nq, size_t dim, 
         HIP_TRY(hipStreamSynchronize(s));
         return VDB_OK;
     }
-    if (ix->n_live && ix->dim != dim) return fail_dim(dim, ix->dim);
-    for (auto& kv : ix->misfits)
-        if (kv.second.size() != dim) return fail_dim(dim, kv.second.size());
-    if (!ix->misfits.empty()) return fail(VDB_ERR_INVALID_ARGUMENT, "zero-dimensional vectors are not searchable");
-    if (ix->metric == vdb::COSINE) {
-        if ((rc = ensure_zero_count(ix))) return rc;
-        if (ix->zero_live) return fail_zero_vector();
-    }
-    if (nq > 0x7fffffffull / 2) return fail(VDB_ERR_INVALID_ARGUMENT, "batch too large");
-    if (ix->dim > 16384) return fail(VDB_ERR_INVALID_ARGUMENT, "dimension %u exceeds the supported 16384", ix->dim);
+    if ((rc = pre_device_checks(ix, dim, nq > 0x7fffffffull / 2))) return rc;
 
     const uint32_t n = ix->n_uploaded, ld = ix->ld, nq32 = (uint32_t)nq, bp_all = round_up(nq32, SUPER);
     const uint32_t mr = (uint32_t)max_results;
     (void)rows_f32(ix);                                            // both routes read f32 rows (range_rerank_kernel, the range scan)
     const bool screened = ix->screen && n >= BF16_MIN_ROWS;
-    constexpr uint32_t KMAX = MAX_SELECT;                          // keys evaluated per query at most (select capacity)
 
     // ---- workspace.  Flags: status block | overflow | no cut | complete | keys evaluated, per query; all zeroed here
-    if ((rc = W->w_qp.ensure((size_t)bp_all * ld))) return rc;
-    if ((rc = W->w_qnorm.ensure(bp_all))) return rc;
-    if ((rc = W->w_thr.ensure(bp_all))) return rc;
-    if ((rc = W->w_flags.ensure(4 + 4 * (size_t)nq32))) return rc;
-    if ((rc = W->w_cnt.ensure(4 * SUPER + 16))) return rc;
-    uint32_t* d_status = W->w_flags.p;
-    uint32_t* d_ovf = d_status + 4;
-    uint32_t* d_nocut = d_ovf + nq32;
-    uint32_t* d_complete = d_nocut + nq32;
-    uint32_t* d_nkeys = d_complete + nq32;
-    HIP_TRY(hipMemsetAsync(W->w_flags.p, 0, (4 + 4 * (size_t)nq32) * 4, s));
-    W->status_dirty = true;                                        // (the tiers' bookkeeping: the block is cleared again before its next use)
+    if ((rc = W.w_qp.ensure((size_t)bp_all * ld))) return rc;
+    if ((rc = W.w_qnorm.ensure(bp_all))) return rc;
+    if ((rc = W.w_thr.ensure(bp_all))) return rc;
+    if ((rc = W.w_flags.ensure(RangeFlags::words(nq32)))) return rc;
+    if ((rc = W.w_cnt.ensure(4 * SUPER + 16))) return rc;
+    const RangeFlags df(W.w_flags.p, nq32);
+    uint32_t* const d_status = df.status;
+    HIP_TRY(hipMemsetAsync(W.w_flags.p, 0, RangeFlags::words(nq32) * 4, s));
+    W.status_dirty = true;                                        // (the tiers' bookkeeping: the block is cleared again before its next use)
 
-    // ---- eligibility mask: tombstones, optionally AND the caller's id filter
-    const uint32_t* d_rowmask = (ix->n_live == n) ? nullptr : ix->d_live;
-    if (d_idmask) {
-        if ((rc = W->w_rowmask.ensure((n + 31) / 32))) return rc;
-        vdb::launch_build_rowmask(ix->d_row_ids, d_rowmask, d_idmask, mask_bits, n, W->w_rowmask.p, s);
-        d_rowmask = W->w_rowmask.p;
-    }
+    const uint32_t* d_rowmask;
+    if ((rc = eligibility_mask(ix, W, s, d_idmask, mask_bits, &d_rowmask))) return rc;
 
     // ---- queries: zero-padded copy, exact-order norms; for the screened route the bf16 image, |q - bf16(q)| and g_q as a search prepares them
     if (screened) {
-        if ((rc = W->w_qb.ensure((size_t)bp_all * ld))) return rc;
-        if ((rc = W->w_qerr.ensure(bp_all))) return rc;
-        if ((rc = W->w_qg.ensure(bp_all))) return rc;
+        if ((rc = W.w_qb.ensure((size_t)bp_all * ld))) return rc;
+        if ((rc = W.w_qerr.ensure(bp_all))) return rc;
+        if ((rc = W.w_qg.ensure(bp_all))) return rc;
     }
     {
-        vdb::QueryPrepParams qp{d_q, (uint32_t)dim, nq32, W->w_qp.p, ld, bp_all, W->w_qnorm.p, W->w_thr.p, ix->metric, d_status,
-                                screened ? W->w_qb.p : nullptr, W->w_qerr.p, (screened && ix->d_margin) ? W->w_qg.p : nullptr,
+        vdb::QueryPrepParams qp{d_q, (uint32_t)dim, nq32, W.w_qp.p, ld, bp_all, W.w_qnorm.p, W.w_thr.p, ix->metric, d_status,
+                                screened ? W.w_qb.p : nullptr, W.w_qerr.p, (screened && ix->d_margin) ? W.w_qg.p : nullptr,
                                 margin_plan(ix).kappa, nullptr, nullptr};
         vdb::launch_query_prep(qp, s);
     }
 
     std::vector<uint32_t> todo;                                    // batch indices for the exact range scan
     if (screened) {
-        const uint32_t capl = 256;
-        const uint32_t n_wg = screen_grid(ix, vdb::fused_bf16_tile_rows());
-        const uint32_t n_sub = vdb::fused_bf16_subpools_per_query(n_wg);
-        if ((rc = W->w2_cand.ensure((size_t)SUPER * KMAX))) return rc;
-        if ((rc = W->w_pool.ensure((size_t)SUPER * n_sub * capl))) return rc;
-        if ((rc = W->w_subcnt.ensure((size_t)SUPER * n_sub))) return rc;
+        CutGrid grid;
+        if ((rc = cut_pass_setup(ix, W, &grid))) return rc;
         // thresholds: score_cut(radius) from the constants the re-rank hands to score_cut (pass_bf16)
         vdb::RangeCutParams cp{};
-        cp.cert = rerank_params(ix, d_rowmask, d_status, mr, nullptr, KMAX, nullptr);
-        cp.cert.qnorm = W->w_qnorm.p; cp.cert.eps_coef = eps_coef(ix);
-        cp.cert.qerr = W->w_qerr.p; cp.cert.c_acc = c_acc_bf16(ix); cp.cert.lb_scores = ix->d_margin ? 1u : 0u;
-        cp.radii = d_radii; cp.nq = nq32; cp.thr = W->w_thr.p; cp.nocut = d_nocut;
+        cp.cert = rerank_params(ix, d_rowmask, d_status, mr, nullptr, CUT_KMAX, nullptr);
+        cp.cert.qnorm = W.w_qnorm.p; cp.cert.eps_coef = eps_coef(ix);
+        cp.cert.qerr = W.w_qerr.p; cp.cert.c_acc = c_acc_bf16(ix); cp.cert.lb_scores = ix->d_margin ? 1u : 0u;
+        cp.radii = d_radii; cp.nq = nq32; cp.thr = W.w_thr.p; cp.nocut = df.nocut;
         vdb::launch_range_cut(cp, s);
-        uint32_t* d_cand_cnt = W->w_cnt.p + 2 * SUPER;
         for (uint32_t q0 = 0; q0 < nq32; q0 += SUPER) {
             const uint32_t nb = std::min(SUPER, nq32 - q0);
-            vdb::FusedBf16Params fp = screen_params(ix, W, d_rowmask, d_status, capl, n_wg);
-            screen_queries(fp, ix, W->w_qb.p, W->w_qg.p, W->w_thr.p, q0);
-            launch_filter_pass(ix, fp, s);
+            cut_pass(ix, W, s, grid, d_rowmask, d_status, W.w_qb.p, W.w_qg.p, W.w_thr.p, q0, nb, df.ovf);
             st[3] += n;
-            vdb::SelectParams mp{};
-            mp.keys = W->w_pool.p; mp.sub_counts = W->w_subcnt.p; mp.n_sub = n_sub; mp.capl = capl; mp.wg_major = 1;
-            mp.kk = KMAX; mp.out_keys = W->w2_cand.p; mp.out_stride = KMAX; mp.out_cnt = d_cand_cnt;
-            mp.ovf = d_ovf + q0; mp.summary = nullptr; mp.flag_truncation = 1;
-            vdb::launch_select(mp, nb, s);
             vdb::RangeRerankParams rp{};
             rp.rows = rows_f32(ix); rp.ld = ld; rp.dim = ix->dim; rp.n_rows = n;
-            rp.qp = W->w_qp.p + (size_t)q0 * ld; rp.qnorm = W->w_qnorm.p + q0; rp.nd = ix->d_nd;
+            rp.qp = W.w_qp.p + (size_t)q0 * ld; rp.qnorm = W.w_qnorm.p + q0; rp.nd = ix->d_nd;
             rp.row_ids = ix->d_row_ids; rp.rowmask = d_rowmask;
-            rp.cand = W->w2_cand.p; rp.cand_stride = KMAX; rp.cand_cnt = d_cand_cnt;
+            rp.cand = W.w2_cand.p; rp.cand_stride = CUT_KMAX; rp.cand_cnt = cand_counts(W);
             rp.radii = d_radii + q0; rp.metric = ix->metric; rp.max_results = mr;
             rp.out_ids = d_out_ids + (size_t)q0 * mr; rp.out_dists = d_out_dists + (size_t)q0 * mr;
             rp.out_counts = d_out_counts + q0; rp.out_totals = d_out_totals ? d_out_totals + q0 : nullptr;
-            rp.complete = d_complete + q0; rp.n_keys = d_nkeys + q0; rp.status = d_status;
+            rp.complete = df.complete + q0; rp.n_keys = df.n_keys + q0; rp.status = d_status;
             vdb::launch_range_rerank(rp, nb, s);
         }
         HIP_TRY(hipGetLastError());
     }
-    std::vector<uint32_t> hf(4 + 4 * (size_t)nq32);
-    HIP_TRY(hipMemcpyAsync(hf.data(), W->w_flags.p, hf.size() * 4, hipMemcpyDeviceToHost, s));
+    std::vector<uint32_t> h_words(RangeFlags::words(nq32));
+    const RangeFlags hf(h_words.data(), nq32);
+    HIP_TRY(hipMemcpyAsync(h_words.data(), W.w_flags.p, h_words.size() * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (hf[0] & vdb::ST_ZERO_QUERY) return fail_zero_vector();
+    if (hf.status[0] & vdb::ST_ZERO_QUERY) return fail_zero_vector();
     if (screened) {
-        const uint32_t* ovf = hf.data() + 4; const uint32_t* nocut = ovf + nq32; const uint32_t* complete = nocut + nq32;
-        const uint32_t* nkeys = complete + nq32;
         for (uint32_t q = 0; q < nq32; ++q) {
-            if (nocut[q]) ++st[6];
-            else { if (ovf[q]) ++st[5]; st[4] += nkeys[q]; }
-            if (nocut[q] || ovf[q] || !complete[q]) todo.push_back(q);
+            if (hf.nocut[q]) ++st[6];
+            else { if (hf.ovf[q]) ++st[5]; st[4] += hf.n_keys[q]; }
+            if (hf.nocut[q] || hf.ovf[q] || !hf.complete[q]) todo.push_back(q);
         }
     } else {
         todo.resize(nq32);
@@ -1157,20 +1132,20 @@ static int range_search_run(Index* ix, const float* d_q, size_t nq, size_t dim, 
     uint32_t n_dense = 0;
     if (!todo.empty()) {
         std::vector<uint32_t> dense;
-        if ((rc = bounded_scan_queries(ix, s, todo, mr, d_radii, d_rowmask, d_out_ids, d_out_dists, d_out_counts, d_out_totals,
+        if ((rc = bounded_scan_queries(ix, W, s, todo, mr, d_radii, d_rowmask, d_out_ids, d_out_dists, d_out_counts, d_out_totals,
                                        d_status, dense)))
             return rc;
         // (every one of the first max_results <= 2048 lies within the radius: more than 32768 rows do)
         for (uint32_t q : dense)
-            if ((rc = exact_one(ix, s, q, mr, d_rowmask, d_out_ids + (size_t)q * mr, d_out_dists + (size_t)q * mr, d_out_counts + q)))
+            if ((rc = exact_one(ix, W, s, q, mr, d_rowmask, d_out_ids + (size_t)q * mr, d_out_dists + (size_t)q * mr, d_out_counts + q)))
                 return rc;
         n_dense = (uint32_t)dense.size();
     }
     st[0] = nq32 - todo.size(); st[1] = todo.size() - n_dense; st[2] = n_dense;
-    uint32_t status = hf[0];
+    uint32_t status = hf.status[0];
     if (!todo.empty()) {
-        uint32_t st4[4] = {0, 0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(st4, W->w_flags.p, 16, hipMemcpyDeviceToHost, s));
+        uint32_t st4[STATUS_WORDS] = {0, 0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(st4, d_status, STATUS_BYTES, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         status |= st4[0];
     }
@@ -1185,9 +1160,8 @@ int range_search_device(Index* ix, const float* d_q, size_t nq, size_t dim, cons
     int rc;
     if (max_results == 0 || max_results > MAX_SELECT)
         return fail(VDB_ERR_INVALID_ARGUMENT, "max_results %zu outside [1, %u]", max_results, MAX_SELECT);
-    // a synchronous call takes a context no submitted search is using, like search_device
-    Workspace* W = ix->wsv[0].busy ? &ix->wsv[1] : &ix->wsv[0];
-    if (W->busy) return fail(VDB_ERR_INVALID_ARGUMENT, "two submitted searches are in flight on this handle: wait for one first");
+    Workspace* W;
+    if ((rc = idle_workspace(ix, &W))) return rc;
     if ((rc = set_device(ix))) return rc;
     hipStream_t s = user_stream ? user_stream : W->stream;
     // the radii on the host: a NaN radius is refused before anything is launched
@@ -1198,17 +1172,23 @@ int range_search_device(Index* ix, const float* d_q, size_t nq, size_t dim, cons
     }
     for (size_t b = 0; b < nq; ++b)
         if (h_radii[b] != h_radii[b]) return fail(VDB_ERR_INVALID_ARGUMENT, "the radius of query %zu is NaN", b);
-    ix->cur = W;
     uint64_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     rc = flush(ix);
-    if (!rc && nq) rc = range_search_run(ix, d_q, nq, dim, d_radii, d_idmask, mask_bits, max_results, d_out_ids, d_out_dists,
+    if (!rc && nq) rc = range_search_run(ix, *W, d_q, nq, dim, d_radii, d_idmask, mask_bits, max_results, d_out_ids, d_out_dists,
                                          d_out_counts, d_out_totals, s, st);
     memcpy(ix->range_stats, st, sizeof(st));
-    ix->cur = &ix->wsv[0];
     return rc;
 }
 
-void publish_stats(Index* ix) { memcpy(ix->stats, ix->cur->stats, sizeof(ix->stats)); }
+void publish_stats(Index* ix, const Workspace& W) { memcpy(ix->stats, W.stats, sizeof(ix->stats)); }
+
+// A synchronous call takes the workspace no submitted search is using
+int idle_workspace(Index* ix, Workspace** W) {
+    *W = ix->wsv[0].busy ? &ix->wsv[1] : &ix->wsv[0];
+    if ((*W)->busy) return fail(VDB_ERR_INVALID_ARGUMENT, "two submitted searches are in flight on this handle: wait for one first");
+    return VDB_OK;
+}
+Workspace& other_workspace(Index* ix, Workspace& W) { return ix->wsv[&W == &ix->wsv[0] ? 1 : 0]; }
 
 // searches submitted and not yet waited for (vdb_flat_search_batch_device_submit): the row store must not change under them
 bool in_flight(const Index* ix) { return ix->wsv && (ix->wsv[0].busy || ix->wsv[1].busy); }
@@ -1495,19 +1475,16 @@ int per_group_drive(Index* ix, hipStream_t s, const DistinctSearch& search, cons
     return VDB_OK;
 }
 
-int search_device(Index* ix, const float* d_q, size_t nq, size_t dim, size_t k, const uint64_t* d_idmask,
+// A synchronous search in the workspace its entry point picked (idle_workspace, or the first when nothing may be in flight)
+int search_device(Index* ix, Workspace& W, const float* d_q, size_t nq, size_t dim, size_t k, const uint64_t* d_idmask,
                   size_t mask_bits, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                   hipStream_t user_stream) {
-    // a synchronous search takes a context no submitted search is using
-    ix->cur = ix->wsv[0].busy ? &ix->wsv[1] : &ix->wsv[0];
-    if (ix->cur->busy) return fail(VDB_ERR_INVALID_ARGUMENT, "two submitted searches are in flight on this handle: wait for one first");
     // (the other workspace may serve the alternating passes of a large batch: the handle mutex is held until part 2 is done,
     // so no submit can claim it meanwhile)
-    int rc = search_part1(ix, d_q, nq, dim, k, d_idmask, mask_bits, d_out_ids, d_out_dists, d_out_counts, user_stream, !in_flight(ix));
-    if (rc) { ix->cur->ctx.pending = false; publish_stats(ix); ix->cur = &ix->wsv[0]; return rc; }
-    rc = search_part2(ix, nullptr);
-    publish_stats(ix);
-    ix->cur = &ix->wsv[0];
+    int rc = search_part1(ix, W, d_q, nq, dim, k, d_idmask, mask_bits, d_out_ids, d_out_dists, d_out_counts, user_stream, !in_flight(ix));
+    if (rc) { W.ctx.pending = false; publish_stats(ix, W); return rc; }
+    rc = search_part2(ix, W, nullptr);
+    publish_stats(ix, W);
     return rc;
 }
 
@@ -1563,7 +1540,7 @@ bool group_plan(const uint32_t* group_of, size_t nq, const uint32_t* elig, size_
 }
 
 // an ordinary search of the queries `idx` (caller's indices) under one mask or none, its results put into their places
-static int grouped_ordinary(Index* ix, hipStream_t s, const GroupedArgs& a, const std::vector<uint32_t>& idx, const vdb::GroupedMask* mask) {
+static int grouped_ordinary(Index* ix, Workspace& W, hipStream_t s, const GroupedArgs& a, const std::vector<uint32_t>& idx, const vdb::GroupedMask* mask) {
     int rc;
     GroupedWs& G = ix->gws;
     const size_t m = idx.size(), k = a.k;
@@ -1574,43 +1551,29 @@ static int grouped_ordinary(Index* ix, hipStream_t s, const GroupedArgs& a, cons
     HIP_TRY(hipMemcpyAsync(G.sel.p, idx.data(), m * 4, hipMemcpyHostToDevice, s));
     vdb::launch_gather_rows(a.d_q, (uint32_t)a.dim, (uint32_t)a.dim, (uint32_t)a.nq, G.sel.p, (uint32_t)m, G.q2.p, s);
     HIP_TRY(hipGetLastError());
-    if ((rc = search_device(ix, G.q2.p, m, a.dim, k, mask ? mask->words : nullptr, mask ? (size_t)mask->bits : 0, G.si.p, G.sd.p, G.sc.p, nullptr)))
+    if ((rc = search_device(ix, W, G.q2.p, m, a.dim, k, mask ? mask->words : nullptr, mask ? (size_t)mask->bits : 0, G.si.p, G.sd.p, G.sc.p, nullptr)))
         return rc;
     vdb::launch_scatter_results(G.si.p, G.sd.p, G.sc.p, G.sel.p, (uint32_t)m, (uint32_t)k, a.d_out_ids, a.d_out_dists, a.d_out_counts, s);
     HIP_TRY(hipGetLastError());
     return VDB_OK;
 }
 
-int search_grouped(Index* ix, hipStream_t s, const GroupedArgs& a) {
+int search_grouped(Index* ix, Workspace& W, hipStream_t s, const GroupedArgs& a) {
     int rc;
     GroupedWs& G = ix->gws;
     uint64_t* st = ix->grouped_stats;
     const size_t nq = a.nq, k = a.k, R = a.n_ref;
     const uint32_t nq32 = (uint32_t)nq;
-    // the checks of a search, in its order (search_part1): dimension, a live zero-norm row under Cosine
-    if ((rc = query_dim_check(ix, a.dim))) return rc;
-    if (ix->metric == vdb::COSINE) {
-        if ((rc = ensure_zero_count(ix))) return rc;
-        if (ix->zero_live) return fail_zero_vector();
-    }
-    if (ix->dim > 16384) return fail(VDB_ERR_INVALID_ARGUMENT, "dimension %u exceeds the supported 16384", ix->dim);
-    ix->cur = &ix->wsv[0];
-    Workspace* W = ix->cur;
-    const uint32_t n = ix->n_uploaded, ld = ix->ld, bp_all = round_up(nq32, SUPER);
+    // the checks of a search, in its order (search_part1; the entry point has refused an oversized batch already)
+    if ((rc = pre_device_checks(ix, a.dim, false))) return rc;
+    const uint32_t n = ix->n_uploaded, ld = ix->ld;
     const uint32_t n_words = (n + 31) / 32, nb = vdb::sparse_list_blocks(n);
 
     // ---- row masks and counts of all referenced groups; the queries prepared (the whole batch: a zero-norm query anywhere fails
     // the call before any distance is looked at)
     HIP_TRY(hipMemsetAsync(a.d_out_counts, 0, nq * 4, s));
-    if ((rc = W->w_qp.ensure((size_t)bp_all * ld)) || (rc = W->w_qnorm.ensure(bp_all)) || (rc = W->w_thr.ensure(bp_all)) ||
-        (rc = W->w_flags.ensure(4 + 3 * (size_t)nq32)))
-        return rc;
-    uint32_t* d_status = W->w_flags.p;
-    HIP_TRY(hipMemsetAsync(d_status, 0, 16, s));
-    W->status_dirty = true;                                        // (the tiers' bookkeeping: the block is cleared again before its next use)
-    vdb::QueryPrepParams qp{a.d_q, (uint32_t)a.dim, nq32, W->w_qp.p, ld, bp_all, W->w_qnorm.p, W->w_thr.p, ix->metric, d_status,
-                            nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr};
-    vdb::launch_query_prep(qp, s);
+    if ((rc = prep_exact_queries(ix, W, s, a.d_q, nq32, a.dim))) return rc;
+    uint32_t* d_status = SearchFlags(W.w_flags.p, nq32).status;
     uint32_t* d_blk = nullptr;                                     // [R][nb] counts | [R][nb] offsets | [R] totals
     if (R) {
         if ((rc = G.rowmask.ensure(R * std::max<size_t>(n_words, 1))) || (rc = G.blk.ensure(2 * R * (size_t)nb + R))) return rc;
@@ -1650,35 +1613,32 @@ int search_grouped(Index* ix, hipStream_t s, const GroupedArgs& a) {
         size_t key_rows = 0;
         for (const GroupPass& P : plan.passes) key_rows = std::max(key_rows, (size_t)P.nq * P.stride);
         if ((rc = ensure_ranks(ix))) return rc;
-        if ((rc = G.plan.ensure(hp.size())) || (rc = G.lists.ensure(lists_len)) || (rc = W->w2_qp.ensure((size_t)ns * ld)) ||
-            (rc = W->w2_qnorm.ensure(ns)) || (rc = W->w2_thr.ensure(ns)) || (rc = G.si.ensure((size_t)ns * k)) || (rc = G.sd.ensure((size_t)ns * k)) ||
-            (rc = G.sc.ensure(ns)) || (rc = W->w_exact.ensure(key_rows)) || (rc = W->w_exsel.ensure((size_t)SUPER * MAX_SELECT + 8)) ||
-            (rc = W->w_cnt.ensure(4 * SUPER + 16)))
+        if ((rc = G.plan.ensure(hp.size())) || (rc = G.lists.ensure(lists_len)) || (rc = W.w2_qp.ensure((size_t)ns * ld)) ||
+            (rc = W.w2_qnorm.ensure(ns)) || (rc = W.w2_thr.ensure(ns)) || (rc = G.si.ensure((size_t)ns * k)) || (rc = G.sd.ensure((size_t)ns * k)) ||
+            (rc = G.sc.ensure(ns)) || (rc = W.w_exact.ensure(key_rows)) || (rc = W.w_exsel.ensure((size_t)SUPER * MAX_SELECT + 8)) ||
+            (rc = W.w_cnt.ensure(4 * SUPER + 16)))
             return rc;
         HIP_TRY(hipMemcpyAsync(G.plan.p, hp.data(), hp.size() * 4, hipMemcpyHostToDevice, s));
         const uint32_t* d_perm = G.plan.p; const uint32_t* d_kcnt = d_perm + ns; const uint32_t* d_glist = d_kcnt + ns;
         const uint32_t* d_tiles = d_glist + 2 * R;
         vdb::launch_grouped_scatter(G.rowmask.p, (uint32_t)R, n, d_blk + R * (size_t)nb, d_glist, G.lists.p, (uint32_t)lists_len, s);
-        vdb::launch_gather_queries(W->w_qp.p, W->w_qnorm.p, ld, d_perm, ns, ns, W->w2_qp.p, W->w2_qnorm.p, W->w2_thr.p, s);
+        vdb::launch_gather_queries(W.w_qp.p, W.w_qnorm.p, ld, d_perm, ns, ns, W.w2_qp.p, W.w2_qnorm.p, W.w2_thr.p, s);
         for (const GroupPass& P : plan.passes) {
             vdb::GroupedScanParams gp{};
-            gp.scan = vdb::SparseScanParams{rows_f32(ix), ld, ix->dim, n, G.lists.p, (uint32_t)lists_len, W->w2_qp.p + (size_t)P.q0 * ld,
-                                            W->w2_qnorm.p + P.q0, P.nq, ix->d_nd, ix->ids_monotone ? nullptr : ix->d_idrank.p, ix->metric,
-                                            W->w_exact.p, P.stride, d_status};
+            gp.scan = vdb::SparseScanParams{rows_f32(ix), ld, ix->dim, n, G.lists.p, (uint32_t)lists_len, W.w2_qp.p + (size_t)P.q0 * ld,
+                                            W.w2_qnorm.p + P.q0, P.nq, ix->d_nd, ix->ids_monotone ? nullptr : ix->d_idrank.p, ix->metric,
+                                            W.w_exact.p, P.stride, d_status};
             gp.tiles = d_tiles + 4 * (size_t)P.tile0; gp.n_tiles = P.n_tiles; gp.glist = d_glist; gp.n_groups = (uint32_t)R; gp.q_base = P.q0;
             vdb::launch_grouped_scan(gp, s);
-            vdb::SelectParams mp{};
-            mp.keys = W->w_exact.p; mp.stride = P.stride; mp.counts = d_kcnt + P.q0; mp.n_fixed = P.stride; mp.cap = P.stride;
-            mp.kk = (uint32_t)k; mp.out_keys = W->w_exsel.p; mp.out_stride = MAX_SELECT; mp.out_cnt = W->w_cnt.p;
+            vdb::SelectParams mp = emit_select_params(ix, W, k);
+            mp.keys = W.w_exact.p; mp.stride = P.stride; mp.counts = d_kcnt + P.q0; mp.n_fixed = P.stride; mp.cap = P.stride;
             mp.emit_ids = G.si.p + (size_t)P.q0 * k; mp.emit_dists = G.sd.p + (size_t)P.q0 * k; mp.emit_counts = G.sc.p + P.q0;
-            mp.emit_stride = (uint32_t)k;
-            mp.emit_rank2row = ix->ids_monotone ? nullptr : ix->d_rank2row.p; mp.emit_row_ids = ix->d_row_ids;
             vdb::launch_select(mp, P.nq, s);
         }
         vdb::launch_scatter_results(G.si.p, G.sd.p, G.sc.p, d_perm, ns, (uint32_t)k, a.d_out_ids, a.d_out_dists, a.d_out_counts, s);
         HIP_TRY(hipGetLastError());
-        uint32_t st4[4] = {0, 0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(st4, d_status, 16, hipMemcpyDeviceToHost, s));
+        uint32_t st4[STATUS_WORDS] = {0, 0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(st4, d_status, STATUS_BYTES, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         if (st4[0] & vdb::ST_NAN) return fail_nan();
     }
@@ -1690,10 +1650,10 @@ int search_grouped(Index* ix, hipStream_t s, const GroupedArgs& a) {
         const uint32_t g = a.slot[plan.perm[i]];
         idx.clear();
         for (; i < plan.n_scan + plan.n_empty + plan.n_over && a.slot[plan.perm[i]] == g; ++i) idx.push_back(plan.perm[i]);
-        if ((rc = grouped_ordinary(ix, s, a, idx, &a.h_desc[g]))) return rc;
+        if ((rc = grouped_ordinary(ix, W, s, a, idx, &a.h_desc[g]))) return rc;
     }
     idx.assign(plan.perm.begin() + (nq - plan.n_none), plan.perm.end());
-    if ((rc = grouped_ordinary(ix, s, a, idx, nullptr))) return rc;
+    if ((rc = grouped_ordinary(ix, W, s, a, idx, nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return VDB_OK;
 }
