@@ -576,6 +576,56 @@ int vdb_flat_recommend_batch_filtered(vdb_flat_index *h, const uint64_t *example
 int vdb_flat_recommend_stats(const vdb_flat_index *h, uint64_t out[4]);
 
 /*
+ * RECOMMEND BY BEST SCORE: nearest to ANY positive, vetoed by the negatives (no reference counterpart; a caller would search by id
+ * once per positive, get_vector every candidate and every negative, and fold on the host).  vdb_flat_recommend_batch answers "more
+ * like the centre of these"; this call scores every candidate against every example on its own.  Request b has positives
+ * p_1..p_np (np >= 1), negatives n_1..n_nn (nn >= 0), all stored ids, laid out as in vdb_flat_recommend_batch, and a count k_b.
+ * d(e, x) is the reference distance with the stored vector of example e as the query and row x as the row: exactly what
+ * vdb_flat_search_batch_by_id([e]) reports for x.
+ *  - Eligible rows: the live rows the optional mask admits, minus the SET of the request's example ids (64-bit equality).
+ *  - dp(x): dp = d(p_1, x); for i = 2..np: if d(p_i, x) < dp then dp = d(p_i, x).  A left fold in list order with the IEEE <: on
+ *    equal values, -0.0 and +0.0 included, the earlier positive's bits stay.
+ *  - Kept: x is kept iff nn == 0, or dp(x) < d(n_j, x) holds for every j.  A tie is a veto; a NaN d(n_j, x) is a veto.  The rule is
+ *    decided row by row and does not depend on the route the engine took.
+ *  - dn(x): for a kept row, the same left fold over the negatives; +inf when nn == 0.
+ *  - Result: the kept rows ascending by (dp, unsigned id), in the order the plain search gives equal distances (-0.0 in front of
+ *    +0.0), cut to min(k_b, len): out_ids, out_dists (dp, bit for bit), out_neg_dists (dn; may be NULL), out_counts.  Fewer than
+ *    k_b kept rows is a short list, not an error.  min(max k_b, len) may not exceed VDB_RECOMMEND_BEST_MAX_K.
+ * Consequences: one positive and no negatives is vdb_flat_search_batch_by_id bit for bit; an example the mask hides is still an
+ * example; the same id may repeat and may stand on both sides; no id value is a flag.
+ * Errors, in this order: (1) recommend's argument checks, before any device work, with the same limits; (2) staged writes are
+ * flushed; (3) VDB_ERR_NOT_FOUND and VDB_ERR_DIMENSION_MISMATCH as recommend; (4) under Cosine a zero-norm example, like any live
+ * zero-norm row, is VDB_ERR_INVALID_VECTOR; (5) a NaN d(p_i, x) at any live row the mask admits -- the examples included: they are
+ * struck afterwards -- is VDB_ERR_NAN, on every route.
+ * Not built, refused with VDB_ERR_INVALID_ARGUMENT where a caller can reach it: ranking the vetoed rows behind the kept ones,
+ * np = 0, sharded handles, device-pointer and ticket forms.
+ * How (csrc/kernels_recommend_best.hip): the positives of all requests are gathered into one query block on the
+ * device and ONE certified search ranks them at depth D.  A list with D entries ends at its frontier, F is the smallest frontier
+ * of a request, and an entry with d < F is settled: a row missing from list i has d(p_i, x) >= F, so the smallest distance seen
+ * for a settled row is its dp.  A merge kernel walks the settled entries in (dp, id) order, a veto kernel computes the exact
+ * d(n_j, x) for those rows, applies the kept rule and keeps the first k_b.  A request is answered when k_b rows were kept or
+ * nothing can lie behind its candidates; the others run again at depth min(len, 1024), and what is left gets ONE exact pass over
+ * the rows per request.  vdb_flat_recommend_best_depth(k, m, len, stage) is the depth of stage 0 -- min(len, min(1024,
+ * max(2 (k + m), 32))), k = min(max k_b, len), m = the longest request -- and of stage 1; 0 for any other stage.
+ * vdb_flat_recommend_best_stats describes the last call: [0] requests, [1] example rows, [2] requests answered at stage 0, [3] at
+ * stage 1, [4] by the exact scan, [5] the stage-0 depth, [6] list searches run (the sum of np over every stage a request went
+ * through), [7] 0.  vdb_flat_debug_set_recommend_best_route (tests): 0 automatic (lists first unless the stage-0 depth is the whole
+ * index), 1 lists first always, 2 the exact scan only; the answers are the same bits on every route.
+ */
+#define VDB_RECOMMEND_BEST_MAX_K 1024
+int vdb_flat_recommend_best_batch(vdb_flat_index *h, const uint64_t *example_ids, const size_t *offsets /* [nq + 1] */,
+                                  const uint32_t *n_pos /* [nq] */, size_t nq, const size_t *ks, size_t k,
+                                  const uint64_t *id_mask, size_t mask_bits, size_t kstride,
+                                  uint64_t *out_ids, float *out_dists, float *out_neg_dists, size_t *out_counts);
+int vdb_flat_recommend_best_batch_filtered(vdb_flat_index *h, const uint64_t *example_ids, const size_t *offsets /* [nq + 1] */,
+                                           const uint32_t *n_pos /* [nq] */, size_t nq, const size_t *ks, size_t k,
+                                           const vdb_meta_mask *mask, size_t kstride,
+                                           uint64_t *out_ids, float *out_dists, float *out_neg_dists, size_t *out_counts);
+int vdb_flat_recommend_best_stats(const vdb_flat_index *h, uint64_t out[8]);
+size_t vdb_flat_recommend_best_depth(size_t k, size_t m, size_t len, int stage);
+int vdb_flat_debug_set_recommend_best_route(vdb_flat_index *h, int mode);
+
+/*
  * DIVERSE TOP-K (MAXIMAL MARGINAL RELEVANCE): k results that are not all the same thing (no reference counterpart; a caller would
  * search at depth m, get_vector every candidate and run an O(k m dim) loop on the host).  A request is a query q, a count k, a
  * candidate depth m and a trade-off lambda, 1 <= k <= m <= VDB_MMR_MAX_CANDIDATES, lambda an f32 in [0, 1].

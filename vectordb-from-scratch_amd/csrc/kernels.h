@@ -723,4 +723,46 @@ struct MmrParams {
 };
 void launch_mmr_select(const MmrParams& p, uint32_t nq, hipStream_t s);
 
+// ---------------------------------------------------------------- recommend by best score (kernels_recommend_best.hip)
+constexpr uint32_t RB_MAX_ROWS = 1024;                                     // rows one walk of the lists hands to the veto (VDB_RECOMMEND_BEST_MAX_K)
+constexpr uint32_t RB_MAX_ENTRIES = 4096;                                  // list entries one walk sorts in LDS
+// The requests of one call on the device: request b owns entries [offs[b], offs[b + 1]) of rows / ids (at most
+// RECOMMEND_MAX_EXAMPLES), the first n_pos[b] >= 1 of them positives, the rest negatives; ks[b] rows are wanted.  rows: device
+// rows below the store's n_rows (the host resolved them).
+struct RbRequests {
+    const uint32_t* offs; const uint32_t* n_pos; const uint32_t* ks; const uint32_t* rows; const uint64_t* ids;
+};
+// Workgroup j merges the n_pos lists of request sel[j] (j itself without sel): lists list0[j] .. of ids / dists [list][depth],
+// counts[list] entries each, ascending (distance, id).  The candidates -- at most min(cand_stride, RB_MAX_ROWS) rows ascending by
+// (ordered dp, id), examples struck -- go to cand_ids / cand_dists [j * cand_stride ..], their number to cand_cnt[j]; open[j] = 1
+// when rows may exist behind them (a list came back full, or the walk was cut by either capacity).
+struct RbMergeParams {
+    RbRequests R; const uint32_t* sel; const uint32_t* list0;
+    const uint64_t* ids; const float* dists; const uint32_t* counts; uint32_t depth;
+    uint64_t* cand_ids; float* cand_dists; uint32_t* cand_cnt; uint32_t* open; uint32_t cand_stride;
+};
+void launch_rb_merge(const RbMergeParams& p, uint32_t n_req, hipStream_t s);
+// Workgroup j takes the candidates of request sel[j] in order: the kept rule against every negative's stored row, the dn fold, and
+// the first min(ks[b], kout) kept rows to out_ids / out_dists / out_neg [b * kout ..], their number to out_counts[b].
+// answered[j] (may be null) = 1 when that many were kept or open (may be null) says nothing lies behind the candidates.
+// row_ids / rank2row (null: rows are in id order) / live name the live row of an id; status bit 1: a candidate without one.
+struct RbVetoParams {
+    const float* rows; uint32_t ld, dim, n_rows; int metric; const float* nd;
+    const uint64_t* row_ids; const uint32_t* rank2row; const uint32_t* live;
+    RbRequests R; const uint32_t* sel;
+    const uint64_t* cand_ids; const float* cand_dists; const uint32_t* cand_cnt; const uint32_t* open; uint32_t cand_stride;
+    uint64_t* out_ids; float* out_dists; float* out_neg; uint32_t* out_counts; uint32_t kout;
+    uint32_t* answered; uint32_t* status;
+};
+void launch_rb_veto(const RbVetoParams& p, uint32_t n_req, hipStream_t s);
+// The exact scan: keys[y * key_stride + row] = (ordered dp, id rank) of every eligible row that request sel[y] keeps, EMPTY_KEY
+// for every other row below n_rows; ST_NAN into status for a NaN positive distance at an eligible row.
+struct RbScanParams {
+    const float* rows; uint32_t ld, dim, n_rows; int metric; const float* nd;
+    const uint32_t* rowmask; const uint32_t* idrank;                       // null: every row / ranks are rows
+    RbRequests R; const uint32_t* sel;
+    uint64_t* keys; size_t key_stride; uint32_t* status;
+};
+void launch_rb_scan(const RbScanParams& p, uint32_t n_req, hipStream_t s);
+
 }  // namespace vdb

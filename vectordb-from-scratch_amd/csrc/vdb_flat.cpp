@@ -866,6 +866,77 @@ int vdb_flat_recommend_stats(const vdb_flat_index* ix, uint64_t out[4]) {
     return VDB_OK;
 }
 
+// ---- recommend by best score (no reference counterpart; vdb_search.cpp recommend_best_drive)
+static_assert(vdb::RB_MAX_ROWS == VDB_RECOMMEND_BEST_MAX_K, "the walk's candidate list and the public limit");
+size_t vdb_flat_recommend_best_depth(size_t k, size_t m, size_t len, int stage) {
+    const size_t cap = vdb::RB_MAX_ROWS;
+    if (stage == 0) return std::min(len, std::min(cap, std::max(2 * (std::min(k, cap) + std::min(m, cap)), (size_t)32)));
+    if (stage == 1) return std::min(len, cap);
+    return 0;
+}
+
+// The front end of both forms: recommend's argument checks before any lock or device work, then the lock, the flush, the
+// examples' device rows (VDB_ERR_NOT_FOUND, VDB_ERR_DIMENSION_MISMATCH as recommend), then the driver.
+static int recommend_best_host(vdb_flat_index* ix, HostSearch r, RecommendReq rec, float* out_neg_dists) {
+    return guarded([&]() -> int {
+    const size_t nq = r.nq;
+    int rc;
+    if ((rc = recommend_check(&rec, nq))) return rc;
+    if (!ix || (nq && !r.counts)) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (ix->multi) return refuse_multi("vdb_flat_recommend_best_batch");
+    if (r.cm) {
+        if ((rc = compiled_mask_check(r.cm, ix->device))) return rc;
+        r.mask_bits = r.cm->bits;
+    }
+    size_t kmax;
+    if ((rc = batch_shape(r, &kmax))) return rc;
+    r.scores = out_neg_dists;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (in_flight(ix)) return refuse_in_flight();
+    if ((rc = set_device(ix))) return rc;
+    memset(ix->recommend_best_stats, 0, sizeof(ix->recommend_best_stats));
+    ix->recommend_best_stats[0] = nq; ix->recommend_best_stats[1] = rec.total;
+    if (nq == 0) return VDB_OK;
+    // staged adds and removes first: an id resolves to what the searches below see
+    if ((rc = flush(ix))) return rc;
+    std::vector<uint32_t> ex_rows;
+    if ((rc = resolve_query_ids(ix, rec.ids, rec.total, &ex_rows))) return rc;
+    return recommend_best_drive(ix, r, rec, ex_rows.data(), kmax);
+    });
+}
+
+int vdb_flat_recommend_best_batch(vdb_flat_index* ix, const uint64_t* example_ids, const size_t* offsets, const uint32_t* n_pos, size_t nq,
+                                  const size_t* ks, size_t k, const uint64_t* id_mask, size_t mask_bits, size_t kstride, uint64_t* out_ids,
+                                  float* out_dists, float* out_neg_dists, size_t* out_counts) {
+    return recommend_best_host(ix, under(host_search(nullptr, nq, 0, ks, k, kstride, out_ids, out_dists, out_counts), id_mask, mask_bits),
+                               RecommendReq{example_ids, offsets, n_pos}, out_neg_dists);
+}
+
+int vdb_flat_recommend_best_batch_filtered(vdb_flat_index* ix, const uint64_t* example_ids, const size_t* offsets, const uint32_t* n_pos,
+                                           size_t nq, const size_t* ks, size_t k, const vdb_meta_mask* mask, size_t kstride,
+                                           uint64_t* out_ids, float* out_dists, float* out_neg_dists, size_t* out_counts) {
+    if (!mask) return fail(VDB_ERR_INVALID_ARGUMENT, "null mask");
+    return recommend_best_host(ix, under(host_search(nullptr, nq, 0, ks, k, kstride, out_ids, out_dists, out_counts), mask),
+                               RecommendReq{example_ids, offsets, n_pos}, out_neg_dists);
+}
+
+int vdb_flat_recommend_best_stats(const vdb_flat_index* ix, uint64_t out[8]) {
+    if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (ix->multi) return refuse_multi("vdb_flat_recommend_best_stats");
+    memcpy(out, ix->recommend_best_stats, sizeof(ix->recommend_best_stats));
+    return VDB_OK;
+}
+
+int vdb_flat_debug_set_recommend_best_route(vdb_flat_index* ix, int mode) {
+    return guarded([&]() -> int {
+    if (!ix || mode < 0 || mode > 2) return fail(VDB_ERR_INVALID_ARGUMENT, "bad argument");
+    if (ix->multi) return refuse_multi("vdb_flat_debug_set_recommend_best_route");
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->rb_route = mode;
+    return VDB_OK;
+    });
+}
+
 // ---- diverse top-k (no reference counterpart; search_batch_host with r.mmr)
 // The checks of include/vdb_flat.h "DIVERSE TOP-K" item 8, in its order, before any lock or device work.  *done: the call is
 // answered (an empty index, or no query asks for a row).

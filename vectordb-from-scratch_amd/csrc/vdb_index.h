@@ -103,6 +103,15 @@ struct MmrWs {
     vdbi::DevBuf<uint64_t> outi; vdbi::DevBuf<float> outd, outs;
 };
 
+// What one recommend-by-best-score call owns on the device beside the search workspace (vdb_search.cpp recommend_best_drive,
+// DESIGN.md 4.17): the requests, the stage's selection (requests | first lists | positive rows), the gathered positives, the
+// ranked lists, the candidates of the walk or of the scan's select, the flags, and the answers.
+struct RecBestWs {
+    vdbi::DevBuf<uint32_t> meta, sel, lc, cc, open, answered, outc, stat;
+    vdbi::DevBuf<uint64_t> ids, li, ci, outi, mask_in;
+    vdbi::DevBuf<float> q, ld, cd, outd, outn;
+};
+
 // A host-pointer batch search as its entry point received it (the extern "C" shims fill it): the batch and its outputs (Batch),
 // the queries -- vectors [nq][dim], or the stored vectors of `by` (then queries is null and dim unused), or folds of stored
 // vectors (rec, checked by recommend_check; by is then rec->ids) -- and the id mask in the form it came in.  mmr: the lists of the
@@ -280,6 +289,9 @@ struct vdb_flat_index {
     uint64_t by_id_stats[4] = {0};                          // vdb_flat_by_id_stats: counters of the last search by stored id (also on a sharded parent)
     uint64_t recommend_stats[4] = {0};                      // vdb_flat_recommend_stats: counters of the last recommend call (also on a sharded parent)
     uint64_t mmr_stats[8] = {0};                            // vdb_flat_mmr_stats: counters of the last diverse top-k call
+    uint64_t recommend_best_stats[8] = {0};                 // vdb_flat_recommend_best_stats: counters of the last recommend-by-best-score call
+    RecBestWs rbw;                                          // its device buffers
+    int rb_route = 0;                                       // vdb_flat_debug_set_recommend_best_route (tests): 0 auto, 1 lists first, 2 scan only
     uint64_t distinct_stats[8] = {0};                       // vdb_flat_distinct_stats: counters of the last search by group (also on a sharded parent)
     DistinctWs dws;                                         // its device buffers (a sharded parent's live on devices[0])
     uint64_t per_group_stats[8] = {0};                      // vdb_flat_per_group_stats: counters of the last search per group
@@ -381,6 +393,10 @@ int strike_stage(StrikeBufs B, const HostSearch& r, hipStream_t s);
 int strike_copy_out(Index* H, const HostSearch& r, StrikeBufs B, const vdb::RecommendLists& L, const Lists& found, size_t kcut, hipStream_t s);
 // the mask of a request whose compiled mask, if any, has passed the device check
 MaskSrc mask_src(const HostSearch& r);
+// Recommend by best score (vdb_flat_recommend_best_batch) behind the entry point's checks, the flush and the
+// resolution of every example to its device row (ex_rows [rec.total]): the list stages, the exact scan for what they cannot
+// settle, the copy-out (dn goes to r.scores) and ix->recommend_best_stats.  kmax: the largest k of the batch.
+int recommend_best_drive(Index* ix, const HostSearch& r, const RecommendReq& rec, const uint32_t* ex_rows, size_t kmax);
 int range_search_device(Index* ix, const float* d_q, size_t nq, size_t dim, const float* d_radii, const uint64_t* d_idmask,
                         size_t mask_bits, size_t max_results, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                         uint64_t* d_out_totals, hipStream_t user_stream);

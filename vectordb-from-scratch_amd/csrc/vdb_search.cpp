@@ -1658,4 +1658,161 @@ int search_grouped(Index* ix, Workspace& W, hipStream_t s, const GroupedArgs& a)
     return VDB_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Recommend by best score (vdb_flat_recommend_best_batch).  The answer of a request is defined row by row (dp,
+// the kept rule, dn); the driver only decides how it gets there, and every way is exact:
+//   lists  the positives of the requests in hand become one query block (gathered on the device), ONE certified search ranks
+//          them at depth D, rb_merge_kernel walks each request's lists under the frontier proof, rb_veto_kernel applies the
+//          negatives and keeps the first k.  A request is answered when k rows were kept or nothing can lie behind its
+//          candidates.  Stage 0 runs at vdb_flat_recommend_best_depth(.., 0), stage 1 -- the unanswered requests only -- at
+//          (.., 1).
+//   scan   what is still unanswered: rb_scan_kernel writes one key per kept row, the full-scan select emits the first k, the
+//          same veto kernel adds dn.
+// One host read of the flags per list stage; ids and distances stay on the device until the copy-out.
+// ---------------------------------------------------------------------------------------------
+constexpr size_t RB_SCAN_KEYS = (size_t)1 << 25;                   // keys of one scan pass (256 MiB)
+
+int recommend_best_drive(Index* ix, const HostSearch& r, const RecommendReq& rec, const uint32_t* ex_rows, size_t kmax) {
+    RecBestWs& B = ix->rbw;
+    Workspace& W = ix->wsv[0];                                     // (nothing is in flight)
+    hipStream_t s = ix->stream;
+    uint64_t* st = ix->recommend_best_stats;
+    const size_t nq = r.nq, total = rec.total, dim = ix->dim;
+    const size_t len = ix->n_live + ix->misfits.size();
+    const size_t kcut = std::min(kmax, len);
+    int rc;
+    if (kcut == 0) {
+        for (size_t b = 0; b < nq; ++b) r.counts[b] = 0;
+        return VDB_OK;
+    }
+    if (kcut > vdb::RB_MAX_ROWS)
+        return fail(VDB_ERR_INVALID_ARGUMENT, "a recommend by best score returns at most %u rows per request, not %zu", vdb::RB_MAX_ROWS, kcut);
+    if ((rc = pre_device_checks(ix, dim, false))) return rc;
+    if ((rc = ensure_ranks(ix))) return rc;
+    const uint32_t n = ix->n_uploaded;
+    const size_t D0 = vdb_flat_recommend_best_depth(kcut, rec.mmax, len, 0), D1 = vdb_flat_recommend_best_depth(kcut, rec.mmax, len, 1);
+    st[5] = D0;
+
+    // ---- the requests go up: offsets [nq + 1] | n_pos [nq] | k [nq] | rows [total], and the ids
+    const size_t o_np = nq + 1, o_k = o_np + nq, o_row = o_k + nq, words = o_row + total;
+    std::vector<uint32_t> meta(words);
+    for (size_t b = 0; b <= nq; ++b) meta[b] = (uint32_t)rec.offsets[b];
+    for (size_t b = 0; b < nq; ++b) {
+        meta[o_np + b] = rec.n_pos[b];
+        meta[o_k + b] = (uint32_t)std::min(r.ks ? r.ks[b] : r.k, kcut);
+    }
+    memcpy(meta.data() + o_row, ex_rows, total * 4);
+    const size_t no = nq * kcut;
+    if ((rc = B.meta.ensure(words)) || (rc = B.ids.ensure(std::max<size_t>(total, 1))) || (rc = B.stat.ensure(2)) ||
+        (rc = B.outi.ensure(no)) || (rc = B.outd.ensure(no)) || (rc = B.outn.ensure(no)) || (rc = B.outc.ensure(nq)))
+        return rc;
+    // (the uploads below read host vectors of this frame: no return, early ones included, leaves one in flight)
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
+    HIP_TRY(hipMemcpyAsync(B.meta.p, meta.data(), words * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(B.ids.p, rec.ids, total * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(B.stat.p, 0, 8, s));
+    const vdb::RbRequests R{B.meta.p, B.meta.p + o_np, B.meta.p + o_k, B.meta.p + o_row, B.ids.p};
+    const uint64_t* d_mask;
+    if ((rc = stage_mask(B.mask_in, mask_src(r), s, &d_mask))) return rc;
+
+    auto veto_params = [&]() {
+        vdb::RbVetoParams vp{};
+        vp.rows = rows_f32(ix); vp.ld = ix->ld; vp.dim = ix->dim; vp.n_rows = n; vp.metric = ix->metric; vp.nd = ix->d_nd;
+        vp.row_ids = ix->d_row_ids; vp.rank2row = ix->ids_monotone ? nullptr : ix->d_rank2row.p; vp.live = ix->d_live;
+        vp.R = R; vp.cand_ids = B.ci.p; vp.cand_dists = B.cd.p; vp.cand_cnt = B.cc.p;
+        vp.out_ids = B.outi.p; vp.out_dists = B.outd.p; vp.out_neg = B.outn.p; vp.out_counts = B.outc.p; vp.kout = (uint32_t)kcut;
+        vp.status = B.stat.p + 1;
+        return vp;
+    };
+
+    // ---- a list stage for the requests `reqs` at depth D; *left receives those it could not answer
+    auto run_lists = [&](const std::vector<uint32_t>& reqs, size_t D, std::vector<uint32_t>* left) -> int {
+        const size_t nr = reqs.size();
+        // requests [nr] | first list [nr] | positive rows [nl]
+        std::vector<uint32_t> sel(2 * nr);
+        for (size_t j = 0; j < nr; ++j) {
+            const uint32_t b = reqs[j];
+            sel[j] = b;
+            sel[nr + j] = (uint32_t)(sel.size() - 2 * nr);
+            sel.insert(sel.end(), ex_rows + rec.offsets[b], ex_rows + rec.offsets[b] + rec.n_pos[b]);
+        }
+        const size_t nl = sel.size() - 2 * nr;
+        const size_t cs = vdb::RB_MAX_ROWS;
+        if ((rc = B.sel.ensure(sel.size())) || (rc = B.q.ensure(nl * std::max<size_t>(dim, 1))) || (rc = B.li.ensure(nl * D)) ||
+            (rc = B.ld.ensure(nl * D)) || (rc = B.lc.ensure(nl)) || (rc = B.ci.ensure(nr * cs)) || (rc = B.cd.ensure(nr * cs)) ||
+            (rc = B.cc.ensure(nr)) || (rc = B.open.ensure(nr)) || (rc = B.answered.ensure(nr)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(B.sel.p, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, s));
+        // only row numbers go up; the vectors never leave HBM
+        vdb::launch_gather_rows(rows_f32(ix), ix->ld, ix->dim, n, B.sel.p + 2 * nr, (uint32_t)nl, B.q.p, s);
+        HIP_TRY(hipGetLastError());
+        if ((rc = search_device(ix, W, B.q.p, nl, dim, D, d_mask, r.mask_bits, B.li.p, B.ld.p, B.lc.p, nullptr))) return rc;
+        st[6] += nl;
+        vdb::RbMergeParams mp{R, B.sel.p, B.sel.p + nr, B.li.p, B.ld.p, B.lc.p, (uint32_t)D, B.ci.p, B.cd.p, B.cc.p, B.open.p, (uint32_t)cs};
+        vdb::launch_rb_merge(mp, (uint32_t)nr, s);
+        vdb::RbVetoParams vp = veto_params();
+        vp.sel = B.sel.p; vp.open = B.open.p; vp.cand_stride = (uint32_t)cs; vp.answered = B.answered.p;
+        vdb::launch_rb_veto(vp, (uint32_t)nr, s);
+        HIP_TRY(hipGetLastError());
+        std::vector<uint32_t> flag(nr);
+        HIP_TRY(hipMemcpyAsync(flag.data(), B.answered.p, nr * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        left->clear();
+        for (size_t j = 0; j < nr; ++j) if (!flag[j]) left->push_back(reqs[j]);
+        return VDB_OK;
+    };
+
+    // ---- the exact scan for the requests `reqs`, as many per pass as the key buffer holds
+    auto run_scan = [&](const std::vector<uint32_t>& reqs) -> int {
+        const size_t nr = reqs.size();
+        const uint32_t* d_rowmask;
+        if ((rc = eligibility_mask(ix, W, s, d_mask, r.mask_bits, &d_rowmask))) return rc;
+        const size_t G = std::min<size_t>(std::min<size_t>(nr, SUPER), std::max<size_t>(RB_SCAN_KEYS / std::max<uint32_t>(n, 1), 1));
+        if ((rc = B.sel.ensure(nr)) || (rc = W.w_exact.ensure(G * n)) || (rc = W.w_exsel.ensure((size_t)SUPER * MAX_SELECT + 8)) ||
+            (rc = W.w_cnt.ensure(4 * SUPER + 16)) || (rc = B.ci.ensure(G * kcut)) || (rc = B.cd.ensure(G * kcut)) || (rc = B.cc.ensure(G)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(B.sel.p, reqs.data(), nr * 4, hipMemcpyHostToDevice, s));
+        for (size_t g0 = 0; g0 < nr; g0 += G) {
+            const uint32_t g = (uint32_t)std::min(G, nr - g0);
+            vdb::RbScanParams sp{rows_f32(ix), ix->ld, ix->dim, n, ix->metric, ix->d_nd, d_rowmask,
+                                 ix->ids_monotone ? nullptr : ix->d_idrank.p, R, B.sel.p + g0, W.w_exact.p, n, B.stat.p};
+            vdb::launch_rb_scan(sp, g, s);
+            vdb::SelectParams mp = emit_select_params(ix, W, kcut);
+            mp.keys = W.w_exact.p; mp.stride = n; mp.counts = nullptr; mp.n_fixed = n; mp.cap = n;
+            mp.emit_ids = B.ci.p; mp.emit_dists = B.cd.p; mp.emit_counts = B.cc.p;
+            vdb::launch_select(mp, g, s);
+            vdb::RbVetoParams vp = veto_params();
+            vp.sel = B.sel.p + g0; vp.open = nullptr; vp.cand_stride = (uint32_t)kcut; vp.answered = nullptr;
+            vdb::launch_rb_veto(vp, g, s);
+            HIP_TRY(hipGetLastError());
+        }
+        return VDB_OK;
+    };
+
+    std::vector<uint32_t> todo(nq), left;
+    for (size_t b = 0; b < nq; ++b) todo[b] = (uint32_t)b;
+    // (automatic: lists whose depth is the whole index are the expensive way to scan it)
+    const bool lists = ix->rb_route == 1 || (ix->rb_route == 0 && D0 < len);
+    if (lists) {
+        if ((rc = run_lists(todo, D0, &left))) return rc;
+        st[2] = todo.size() - left.size();
+        todo.swap(left);
+        if (!todo.empty() && D1 > D0) {
+            if ((rc = run_lists(todo, D1, &left))) return rc;
+            st[3] = todo.size() - left.size();
+            todo.swap(left);
+        }
+    }
+    if (!todo.empty()) {
+        if ((rc = run_scan(todo))) return rc;
+        st[4] = todo.size();
+    }
+    uint32_t status[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(status, B.stat.p, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (status[1] & 2u) return fail(VDB_ERR_DEVICE, "internal error: a candidate without a live row on the device");
+    if (status[0] & vdb::ST_NAN) return fail_nan();
+    return copy_out(Lists{B.outi.p, B.outd.p, B.outc.p, nullptr, kcut, B.outn.p}, r, s);
+}
+
 }  // namespace vdbi

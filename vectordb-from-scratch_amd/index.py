@@ -352,15 +352,9 @@ class GpuFlatIndex(Index):
             _raise(rc)
         return [int(x) for x in out]
 
-    # ---- recommend from positive and negative stored ids (include/vdb_flat.h vdb_flat_recommend_batch; no reference counterpart)
-    def recommend_batch(self, positive, negative, k, id_mask=None, mask_bits=0, compiled_mask=None):
-        """"More like these, less like those": request b is the average ap of the stored vectors positive[b] (at least one id)
-        and, when negative[b] is not empty, ap + (ap - an) with the average an of those; the answer is what
-        search_batch_arrays returns for that vector with k + the number of examples, every example removed, cut to k.  The
-        fold runs on the device in f32, left to right in list order (include/vdb_flat.h has the exact arithmetic); the
-        vectors never leave it.  positive, negative: sequences of id sequences of the same length (negative None: no
-        negatives at all); k an int or a per-request array.  Returns the arrays of search_batch_arrays.  An id that is not
-        stored raises VectorNotFound for the whole batch."""
+    def _recommend(self, best, positive, negative, k, id_mask, mask_bits, compiled_mask):
+        """what recommend_batch and recommend_best_batch share: the example lists as the C ABI takes them, the outputs (with the
+        negatives' distances for `best`), the call under either kind of mask, the errors"""
         if compiled_mask is not None and id_mask is not None:
             raise ValueError("pass id_mask or compiled_mask, not both")
         nq = len(positive)
@@ -385,23 +379,37 @@ class GpuFlatIndex(Index):
         kstride = max(kmax, 1)
         out_ids = np.zeros((nq, kstride), dtype=np.uint64)
         out_d = np.zeros((nq, kstride), dtype=np.float32)
+        out_n = np.zeros((nq, kstride), dtype=np.float32) if best else None
         counts = np.zeros(nq, dtype=np.uintp)
         szp = ctypes.POINTER(ctypes.c_size_t)
         head = (self._h, _u64p(ex), offsets.ctypes.data_as(szp), n_pos.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), nq, ks_ptr, kscalar)
-        tail = (kstride, _u64p(out_ids), _fp(out_d), counts.ctypes.data_as(szp))
+        tail = (kstride, _u64p(out_ids), _fp(out_d)) + ((_fp(out_n),) if best else ()) + (counts.ctypes.data_as(szp),)
+        plain, filtered = ((self._L.vdb_flat_recommend_best_batch, self._L.vdb_flat_recommend_best_batch_filtered) if best else
+                           (self._L.vdb_flat_recommend_batch, self._L.vdb_flat_recommend_batch_filtered))
         if compiled_mask is not None:
-            rc = self._L.vdb_flat_recommend_batch_filtered(*head, compiled_mask.handle, *tail)
+            rc = filtered(*head, compiled_mask.handle, *tail)
         else:
             mask_ptr = None
             if id_mask is not None:
                 m = np.ascontiguousarray(id_mask, dtype=np.uint64)
                 mask_ptr = _u64p(m)
-            rc = self._L.vdb_flat_recommend_batch(*head, mask_ptr, int(mask_bits), *tail)
+            rc = plain(*head, mask_ptr, int(mask_bits), *tail)
         if rc == _ffi.ERR_NOT_FOUND:
             raise VectorNotFound(int(_ffi.last_error()[0].rsplit(": ", 1)[-1]))
         if rc:
             _raise(rc)
-        return out_ids, out_d, counts
+        return (out_ids, out_d, out_n, counts) if best else (out_ids, out_d, counts)
+
+    # ---- recommend from positive and negative stored ids (include/vdb_flat.h vdb_flat_recommend_batch; no reference counterpart)
+    def recommend_batch(self, positive, negative, k, id_mask=None, mask_bits=0, compiled_mask=None):
+        """"More like these, less like those": request b is the average ap of the stored vectors positive[b] (at least one id)
+        and, when negative[b] is not empty, ap + (ap - an) with the average an of those; the answer is what
+        search_batch_arrays returns for that vector with k + the number of examples, every example removed, cut to k.  The
+        fold runs on the device in f32, left to right in list order (include/vdb_flat.h has the exact arithmetic); the
+        vectors never leave it.  positive, negative: sequences of id sequences of the same length (negative None: no
+        negatives at all); k an int or a per-request array.  Returns the arrays of search_batch_arrays.  An id that is not
+        stored raises VectorNotFound for the whole batch."""
+        return self._recommend(False, positive, negative, k, id_mask, mask_bits, compiled_mask)
 
     def recommend_stats(self):
         """The last recommend_batch: [0] requests, [1] example rows folded, [2] entries struck in total (those in front of the
@@ -411,6 +419,33 @@ class GpuFlatIndex(Index):
         if rc:
             _raise(rc)
         return [int(x) for x in out]
+
+    # ---- recommend by best score (include/vdb_flat.h vdb_flat_recommend_best_batch; no reference counterpart)
+    def recommend_best_batch(self, positive, negative, k, id_mask=None, mask_bits=0, compiled_mask=None):
+        """Nearest to ANY positive, vetoed by the negatives: every candidate row x is scored against every example on its own.
+        dp(x) is the smallest distance from a positive of the request to x (the distance search_batch_by_id reports), x is kept
+        when dp(x) is strictly below its distance from every negative, and the answer is the kept rows nearest first by
+        (dp, id), the examples themselves left out (include/vdb_flat.h has the exact rules).  positive, negative, k and the
+        masks as in recommend_batch.  Returns (ids u64 [nq, kmax], dists f32 [nq, kmax] -- dp --, neg_dists f32 [nq, kmax] --
+        the smallest distance from a negative, +inf without negatives --, counts [nq]).  An id that is not stored raises
+        VectorNotFound for the whole batch."""
+        return self._recommend(True, positive, negative, k, id_mask, mask_bits, compiled_mask)
+
+    def recommend_best_stats(self):
+        """The last recommend_best_batch: [0] requests, [1] example rows, [2] requests answered at list stage 0, [3] at list
+        stage 1, [4] by the exact scan, [5] the stage-0 depth, [6] list searches run (the positives of every stage a request
+        went through), [7] 0."""
+        out = (ctypes.c_uint64 * 8)()
+        rc = self._L.vdb_flat_recommend_best_stats(self._h, out)
+        if rc:
+            _raise(rc)
+        return [int(x) for x in out]
+
+    def debug_set_recommend_best_route(self, mode):
+        """Tests: 0 automatic, 1 the list stages first whatever the depth, 2 the exact scan only.  The answers are the same bits."""
+        rc = self._L.vdb_flat_debug_set_recommend_best_route(self._h, int(mode))
+        if rc:
+            _raise(rc)
 
     # ---- diverse top-k, MMR on the device (include/vdb_flat.h vdb_flat_search_batch_mmr; no reference counterpart)
     def search_batch_mmr(self, queries, k, candidates, lam, id_mask=None, mask_bits=0, compiled_mask=None, ks=None):

@@ -703,8 +703,14 @@ class VectorStore:
         """recommend for several (positive ids, negative ids) pairs in one device call; the vectors never leave the GPU.  An
         unknown id raises VectorNotFound.  flt is a PRE-filter, as in search_similar_batch: a filtered-out id may still be an
         example, it is simply in nobody's answer."""
+        return self._recommend_requests("recommend", requests, k, flt)
+
+    def _recommend_requests(self, what, requests, k, flt):
+        """recommend_batch and recommend_best_batch: the string ids to internal ids, the filter on its host or device path, the
+        index call `what`_batch, the (id, distance) lists back under the callers' ids"""
         if not isinstance(self._index, GpuFlatIndex):
-            raise ValueError("recommend needs a GpuFlatIndex")
+            raise ValueError(what + " needs a GpuFlatIndex")
+        call = getattr(self._index, what + "_batch")
 
         def internal(ids):
             out = []
@@ -724,13 +730,26 @@ class VectorStore:
         cm = self.compile_filter_device(flt) if flt is not None and self._table is not None else None
         if cm is not None:
             try:
-                out_ids, dists, counts = self._index.recommend_batch(pos, neg, int(k), compiled_mask=cm)
+                res = call(pos, neg, int(k), compiled_mask=cm)
             finally:
                 cm.release()
         else:
             mask, bits = self.compile_filter(flt) if flt is not None else (None, 0)
-            out_ids, dists, counts = self._index.recommend_batch(pos, neg, int(k), id_mask=mask, mask_bits=bits)
+            res = call(pos, neg, int(k), id_mask=mask, mask_bits=bits)
+        out_ids, dists, counts = res[0], res[1], res[-1]
         return [self._map([(int(out_ids[b, i]), dists[b, i]) for i in range(int(counts[b]))]) for b in range(len(pos))]
+
+    # ---- "near any of these, nearer to none of those" (GpuFlatIndex.recommend_best_batch; no reference counterpart)
+    def recommend_best(self, positive, negative, k, flt=None):
+        """The k stored vectors nearest to ANY of the stored vectors `positive`, each scored by its nearest positive and left
+        out when some vector of `negative` (may be empty) is at least as near; the examples themselves left out, nearest first."""
+        return self.recommend_best_batch([(positive, negative)], k, flt)[0]
+
+    def recommend_best_batch(self, requests, k, flt=None):
+        """recommend_best for several (positive ids, negative ids) pairs in one device call; the vectors never leave the GPU.
+        An unknown id raises VectorNotFound.  flt is a PRE-filter, as in recommend_batch: a filtered-out id may still be an
+        example."""
+        return self._recommend_requests("recommend_best", requests, k, flt)
 
     # ---- "k results that are not all the same thing" (GpuFlatIndex.search_batch_mmr; no reference counterpart)
     def search_mmr(self, query, k, lam=0.5, candidates=None, flt=None):
