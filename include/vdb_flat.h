@@ -598,7 +598,9 @@ int vdb_flat_recommend_stats(const vdb_flat_index *h, uint64_t out[4]);
  * zero-norm row, is VDB_ERR_INVALID_VECTOR; (5) a NaN d(p_i, x) at any live row the mask admits -- the examples included: they are
  * struck afterwards -- is VDB_ERR_NAN, on every route.
  * Not built, refused with VDB_ERR_INVALID_ARGUMENT where a caller can reach it: ranking the vetoed rows behind the kept ones,
- * np = 0, sharded handles, device-pointer and ticket forms.
+ * np = 0, sharded handles, device-pointer and ticket forms.  A sharded handle is refused among the checks of (1): before the
+ * flush and before any id is resolved, so also on an empty index and for an id that is not stored (unlike
+ * vdb_flat_search_batch_mmr and vdb_flat_search_batch_per_group, which answer an empty index with counts 0 first).
  * How (csrc/kernels_recommend_best.hip): the positives of all requests are gathered into one query block on the
  * device and ONE certified search ranks them at depth D.  A list with D entries ends at its frontier, F is the smallest frontier
  * of a request, and an entry with d < F is settled: a row missing from list i has d(p_i, x) >= F, so the smallest distance seen

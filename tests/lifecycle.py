@@ -28,15 +28,36 @@ older schedules are dealt from one rng stream each and must stay op for op what 
     MetaTable.set_numbers(0, first code, values): the LUT of column 0, absent at first, overwritten in crossing ranges, grown
     past its device capacity twice (Log.table_uploaded counts the regrows by vdb_meta.cpp's growth rule).
   * store level ("numeric": True in the trace): the fields ts and price, numeric filters in the pool, the reads s_recommend and
-    s_with_filters, the device filter switched off and on again."""
+    s_with_filters, the device filter switched off and on again.
+
+MMR, PER-GROUP AND RECOMMEND-BY-BEST READS have schedules of their own again (TWELVE_PINNED, large-twelve, TWELVE_STORE_PINNED;
+_Gen12, an rng stream of its own), for the same reason.
+  * mmr (B, k, query key, m, lambda key, mask): the model's candidates are Model.ranking at depth m, its picks mmr_data.select;
+    query 0 of every batch lies beside the row written last.  The reference adapter searches the survivors block at depth m,
+    builds the whole pair matrix and recomputes min-over-picked from it at every step.  Score bits and mmr_stats [0]-[4].
+  * per_group (B, k, query key, g, mask): per_group_data.expected / routes on the full rankings and self.codes; the reference
+    adapter is the host composition (its distinct answer, then one search with k = g of the eligible rows of every kept code).
+    Codes, sizes, members' ids and distance bits, per_group_stats [1]-[6] under the cap set by ("set", "pg_cap", 0 | 1024).
+  * best (B, k, example key, absent, mask): recommend_best_data's definition and lists_route under ("set", "rb_route", 0 | 1 | 2).
+    recommend_best_data caches by case name; a life changes the rows under one name, so its PURE parts were factored out: definition()
+    and lists_route() take tables=, and Model.best_tables gives them d(e, .) from Model.ranking, kept until the next mutation and
+    not by name.  The reference adapter ranks the survivors block per positive, takes vector_of(id) per candidate and negative
+    with oracle.distance, folds in numpy and sorts by (ordered dp, id).  dn bits and recommend_best_stats [0]-[6].
+  * the op ("near", id, key, of) appends a row beside a stored one (at right angles to it, 0.01 away): as a negative it vetoes
+    half of all rows, the nearest included, which no Gaussian row and no exact copy does; best_requests_of names it.
+  * the generator keeps the answers it needed for its caps; pinned() hands them to slots(), so the first run() does not repeat them.
+  * store level ("twelve": True): s_mmr, s_groups (a header ("#value", size) in front of every group's members), s_recommend_best."""
 from collections import Counter
 
 import numpy as np
 
 import by_id_data as bd
 import distinct_data as dd
+import mmr_data as md
 import oracle
+import per_group_data as pgd
 import range_data as rd
+import recommend_best_data as rbd
 import recommend_data as rcd
 
 F32, U64, I32 = np.float32, np.uint64, np.int32
@@ -53,6 +74,11 @@ SPARSE_SHARE = 0.02                    # eligible share of a "sparse" read's mas
 NEW_READS = ("grouped", "recommend", "numeric")
 READS9, MUTATIONS12 = READS + NEW_READS, MUTATIONS + ("numbers",)
 NUMERIC_CARRIERS = ("numeric", "masked", "by_id", "distinct", "grouped", "recommend")
+# the three composed reads that came after those (TWELVE_PINNED; _Gen12): MMR, per group, recommend by best score
+NEWER_READS = ("mmr", "per_group", "best")
+READS12 = READS9 + NEWER_READS
+MMR_MAX, BEST_MAX_K = 1024, 1024       # VDB_MMR_MAX_CANDIDATES, VDB_RECOMMEND_BEST_MAX_K
+PG_LOW_CAP = 1024                      # ("set", "pg_cap", 1024): member lists above it take the giants' route
 GROUP_NONE = 0xFFFFFFFF                # VDB_GROUP_NONE
 GROUPED_MAX_K = 2048                   # a grouped search with k (clamped to the live count) above: one ordinary masked search per group
 GROUPED_BIG_K = 2100
@@ -302,8 +328,11 @@ class Log:
             self.table_uploaded()
         return mask_ok(mask, self.codes, self.present, self.numbers_seen())
 
+    pg_cap = rb_route = 0                  # vdb_flat_debug_set_per_group_scan_cap (0: the default), ..._recommend_best_route
+
     def set(self, name, value):
-        pass
+        if name in ("pg_cap", "rb_route"):                             # handle state: it outlives every mutation
+            setattr(self, name, int(value))
 
     def flush(self):
         self.uploaded()
@@ -321,15 +350,20 @@ class Log:
         return self.metric == COSINE and self.ids.size and bool((self.alive & ~self.rows.any(axis=1)).any())
 
     def refusal(self, kind, ids=None):
-        if kind in ("range", "grouped") and self.sharded:
+        """The ORDER of the checks (include/vdb_flat.h): range, grouped and recommend by best score refuse a sharded handle before
+        anything else; MMR and per group answer an empty index with empty lists BEFORE they refuse one (mmr_check,
+        search_distinct_host); an absent example comes before the dimension mismatch and the zero-norm row."""
+        if kind in ("range", "grouped", "best") and self.sharded:
             raise Predicted("Refused")
-        if kind == "by_id":
+        if kind in ("by_id", "best"):
             live = set(self.ids[self.alive].tolist()) | set(self.misfits)
             for i in np.asarray(ids, dtype=U64).tolist():
                 if i not in live:
                     raise Predicted("VectorNotFound", int(i))
         if not self.ids.size and not self.misfits:
             return True                                                # an empty store answers every query with nothing
+        if kind in ("mmr", "per_group") and self.sharded:
+            raise Predicted("Refused")
         if self.misfits:
             raise Predicted("DimensionMismatch")
         if self.zero_live():
@@ -508,6 +542,88 @@ class Model(Log):
         k = int(ks) if np.isscalar(ks) else [int(x) for x in ks]
         st = rcd.stats(self.metric, self.rows, requests, k, self.n_live(), ids=self.ids, live=live)
         return {"lists": out, "rstats": st[1:4], "cut": cut}
+
+    # -- the three composed reads (NEWER_READS), each through the module that states its contract
+    def row_of_live(self):
+        """id -> row of the log, over the live rows"""
+        at = np.nonzero(self.alive)[0]
+        return dict(zip(self.ids[at].tolist(), at.tolist()))
+
+    def mmr(self, q, ks, m, lam, mask=None):
+        """include/vdb_flat.h "DIVERSE TOP-K": the candidates are the search at depth m under the mask, the picks mmr_data.select
+        over their stored rows.  mstats: mmr_stats [0]-[4].  moved: the queries whose picks are not the plain top-k (a cap).  The
+        schedules hold finite gaussian rows only: no pair and no score may be a NaN (the liberty of mmr_data.check is never taken)."""
+        empty = self.refusal("mmr")
+        self.uploaded()
+        nq = len(q)
+        if empty:
+            return {"lists": [(np.zeros(0, U64), np.zeros(0, np.uint32))] * nq, "scores": [np.zeros(0, np.uint32)] * nq, "mstats": [nq, 0, 0, 0, 0],
+                    "moved": 0}
+        live, at = self._live(mask), self.row_of_live()
+        out, scores, cands, pairs, moved = [], [], 0, 0, 0
+        for b in range(nq):
+            oi, od = self.ranking(q[b], live, min(int(m), self.n_rows()))
+            vecs = self.rows[[at[int(i)] for i in oi]] if len(oi) else self.rows[:0]
+            picks, sc, np_, nan = md.select(self.metric, vecs, od, k_of(ks, b), lam if np.isscalar(lam) else lam[b])
+            assert not nan and not np.isnan(sc).any() and not np.isnan(od).any(), "a NaN in a lifecycle schedule"
+            out.append((oi[picks], od[picks].view(np.uint32)))
+            scores.append(sc.view(np.uint32))
+            cands, pairs, moved = cands + len(oi), pairs + np_, moved + (list(picks) != list(range(len(picks))))
+        return {"lists": out, "scores": scores, "mstats": [nq, min(int(m), self.n_live()), cands, pairs, sum(len(l[0]) for l in out)], "moved": moved}
+
+    def per_group(self, q, ks, g, mask=None):
+        """per_group_data.expected over the full rankings (kept until the next mutation, as distinct's) and self.codes.  lists: the
+        representatives (what distinct answers); groups: per query [(code, member ids, member distance bits)]; pstats:
+        per_group_stats [1]-[6] by per_group_data.routes under the cap currently set; deep: the largest 0-based rank of a member."""
+        empty = self.refusal("per_group")
+        self.uploaded()
+        nq = len(q)
+        if empty:
+            return {"lists": [(np.zeros(0, U64), np.zeros(0, np.uint32))] * nq, "groups": [[]] * nq, "pstats": [0] * 6, "deep": -1}
+        live = self._live(mask)
+        ranks = [self.ranking(q[b], live) for b in range(nq)]
+        out, groups, deep = [], [], -1
+        for b, rank in enumerate(ranks):
+            ex = pgd.expected(rank, self.codes, k_of(ks, b), g)
+            groups.append([(c, ids, d.view(np.uint32)) for c, ids, d in ex])
+            out.append((np.array([ids[0] for _, ids, _ in ex], dtype=U64), np.array([d[0] for _, _, d in ex], dtype=F32).view(np.uint32)))
+            deep = max([deep] + [int(r[-1]) for r in pgd.member_ranks(rank, self.codes, k_of(ks, b), g)])
+        k = int(ks) if np.isscalar(ks) else [int(x) for x in ks]
+        return {"lists": out, "groups": groups, "pstats": pgd.routes(ranks, self.codes, k, int(g), cap=self.pg_cap or pgd.SCAN_CAP), "deep": deep}
+
+    def best_tables(self, key, metric, rows, req, ids, elig):
+        """recommend_best_data._tables without its cache by case name: d(e, .) from Model.ranking, kept until the next mutation"""
+        memo = self.__dict__.setdefault("_memo", {})
+
+        def table(e):
+            oi, od = self.ranking(self.rows[e], elig)
+            tkey = ("table", int(e), elig.tobytes())
+            if tkey not in memo:
+                at = np.nonzero(elig)[0]
+                order = np.argsort(self.ids[at], kind="stable")
+                t = np.full(len(rows), np.inf, dtype=F32)
+                t[at[order[np.searchsorted(self.ids[at][order], oi)]]] = od
+                memo[tkey] = t
+            return oi, od, memo[tkey]
+        return [table(e) for e in req[0]], [table(e)[2] for e in req[1]]
+
+    def best(self, pos, neg, ks, mask=None):
+        """recommend_best_data's definition (the dp fold, the strict veto, the dn fold, the order (ordered dp, id)) over the log
+        with live= and the mask's rows; dn: the dn bits; bstats: recommend_best_stats [0]-[6] by lists_route on the same rankings
+        under the route currently set; bstages: the stage every request ends at (not an engine output: the caps use it)."""
+        flat = np.array([i for p, n in zip(pos, neg) for i in list(p) + list(n)], dtype=U64)
+        self.refusal("best", flat)
+        self.uploaded()
+        at = self.row_of_live()
+        requests = [(tuple(at[int(i)] for i in p), tuple(at[int(i)] for i in n)) for p, n in zip(pos, neg)]
+        k = int(ks) if np.isscalar(ks) else [int(x) for x in ks]
+        kw = dict(ids=self.ids, live=self.alive.astype(np.uint8), mask=None if mask is None else self._live(mask), tables=self.best_tables)
+        want = rbd.definition(None, self.metric, self.rows, requests, k, **kw)
+        routed, stages, st = rbd.lists_route(None, self.metric, self.rows, requests, k, route=self.rb_route, **kw)
+        rbd.same(routed, want, "the routes restated against the definition")
+        assert not any(np.isnan(d).any() or np.isnan(n).any() for _, d, n in want), "a NaN in a lifecycle schedule"
+        return {"lists": [(i, d.view(np.uint32)) for i, d, _ in want], "dn": [n.view(np.uint32) for _, _, n in want], "bstats": [int(x) for x in st[:7]],
+                "bstages": list(stages)}
 
 
 def grouped_counters(ks, group_of, elig, n_live):
@@ -697,6 +813,235 @@ class RefIndex(Log):
             struck_total += int((hit & (np.cumsum(~hit) - ~hit < kcut)).sum())      # (the examples in front of the cut of the batch-wide list)
             out.append((oi[~hit][:k], od[~hit][:k].view(np.uint32)))
         return {"lists": out, "rstats": [len(flat), struck_total, min(kcut + mmax, self.n_live())]}
+
+    # -- MMR: its own depth-m search of the survivors block, the whole c x c pair matrix, and the greedy choice with min over
+    # the picked recomputed from the matrix at every step (the naive form, not select()'s incremental near)
+    def mmr_vectors(self, ids):
+        """the stored rows the candidate ids resolve to (hook of the MMR mutants)"""
+        return np.stack([self.vector_of(i) for i in ids])
+
+    def pair_matrix(self, vecs):
+        """D(i, j) for all i, j by oracle.distance; above 32 candidates (1024 x 1024 calls take 9 s) row i is one oracle search of
+        the candidate block with candidate i as the query, scattered back by position -- the same arithmetic"""
+        c = len(vecs)
+        D = np.zeros((c, c), dtype=F32)
+        if c <= 32:
+            for i in range(c):
+                for j in range(c):
+                    D[i, j] = md.pair_distance(self.metric, vecs[i], vecs[j])
+            return D
+        block = np.ascontiguousarray(vecs, dtype=F32)
+        for i in range(c):
+            oi, od = oracle.flat_search(self.metric, block, block[i], c)
+            D[i, oi.astype(np.int64)] = od
+        return D
+
+    def mmr(self, q, ks, m, lam, mask=None):
+        empty = self.refusal("mmr")
+        self.uploaded()
+        nq = len(q)
+        rows, ids = self.block(mask)
+        out, scores, cands, pairs = [], [], 0, 0
+        for b in range(nq):
+            if empty or not len(rows):
+                out.append((np.zeros(0, U64), np.zeros(0, np.uint32)))
+                scores.append(np.zeros(0, np.uint32))
+                continue
+            oi, od = self.knn(rows, ids, q[b], min(int(m), len(rows)))
+            c, count = len(oi), min(k_of(ks, b), len(oi))
+            l = F32(lam if np.isscalar(lam) else lam[b])
+            mu = F32(1) - l
+            D = self.pair_matrix(self.mmr_vectors(oi)) if count > 1 else None
+            picks, sc = [0], [F32(l * od[0])]
+            for t in range(1, count):
+                rest = np.array([i for i in range(c) if i not in picks])
+                near = D[np.ix_(rest, picks)].min(axis=1)
+                score = (l * od[rest]).astype(F32) - (mu * near).astype(F32)
+                j = int(np.argmin(score))                            # (the first of equal scores: the lower position)
+                picks.append(int(rest[j]))
+                sc.append(score[j])
+                pairs += len(rest)
+            out.append((oi[picks], od[picks].view(np.uint32)))
+            scores.append(np.asarray(sc, dtype=F32).view(np.uint32))
+            cands += c
+        depth = 0 if empty else min(int(m), self.n_live())
+        return {"lists": out, "scores": scores, "mstats": [nq, depth, cands, pairs, sum(len(l_[0]) for l_ in out)]}
+
+    # -- per group: the host composition -- its own distinct answer, then for every kept code c >= 0 one search with k = g of
+    # the survivors block cut down to the eligible rows with that code
+    def listing_codes(self):
+        """the code column as the member listing reads it (hook)"""
+        return self.codes_seen()
+
+    def listing_block(self, mask):
+        """(rows, ids) the member listing walks (hook)"""
+        return self.block(mask)
+
+    def giant_block(self, mask):
+        """(rows, ids) the masked search of a giant code runs over (hook)"""
+        return self.block(mask)
+
+    def per_group(self, q, ks, g, mask=None):
+        empty = self.refusal("per_group")
+        self.uploaded()
+        nq, g = len(q), int(g)
+        if empty:
+            return {"lists": [(np.zeros(0, U64), np.zeros(0, np.uint32))] * nq, "groups": [[]] * nq, "pstats": [0] * 6}
+        rows, ids = self.block(mask)
+        lrows, lids = self.listing_block(mask)
+        lcodes = dd.codes_of(lids, self.listing_codes())
+        cap = self.pg_cap or pgd.SCAN_CAP
+        out, groups, size, st = [], [], {}, dict(groups=0, filled=0, giant=0, evaluated=0)
+        for b in range(nq):
+            if not len(rows):
+                out.append((np.zeros(0, U64), np.zeros(0, np.uint32)))
+                groups.append([])
+                continue
+            ei, ed, ec = dd.expected(self.knn(rows, ids, q[b], len(rows)), self.codes_seen(), k_of(ks, b))
+            mine = []
+            for i, d, c in zip(ei, ed, ec):
+                if c < 0 or g == 1:
+                    mine.append((int(c), np.array([i], dtype=U64), np.array([d], dtype=F32).view(np.uint32)))
+                    if c >= 0:
+                        size[int(c)] = 0
+                    continue
+                e = size[int(c)] = int((lcodes == c).sum())
+                if e <= cap:
+                    sel, (brows, bids) = lcodes == c, (lrows, lids)
+                    st["filled"], st["evaluated"] = st["filled"] + 1, st["evaluated"] + e
+                else:
+                    brows, bids = self.giant_block(mask)
+                    sel = dd.codes_of(bids, self.listing_codes()) == c
+                    st["giant"] += 1
+                mi, md_ = self.knn(np.ascontiguousarray(brows[sel]), np.ascontiguousarray(bids[sel]), q[b], g) if sel.any() else (np.zeros(0, U64), np.zeros(0, F32))
+                mine.append((int(c), mi, md_.view(np.uint32)))
+            st["groups"] += len(mine)
+            groups.append(mine)
+            out.append((ei, ed.view(np.uint32)))
+        listed = 0 if g == 1 else sum(e for e in size.values() if e <= cap)
+        return {"lists": out, "groups": groups, "pstats": [st["groups"], st["filled"], st["giant"], len(size), listed, st["evaluated"]]}
+
+    # -- recommend by best score: the host composition -- one full-depth ranking of the survivors block per positive (by id: the
+    # query is vector_of), vector_of(id) per candidate and per negative with oracle.distance, the folds in numpy, the order
+    # (ordered dp, id).  The stages (for bstats) from the same rankings cut at the stage depths, by a walk of its own (candidates_at).
+    def veto_vector(self, id):
+        """the stored row a candidate id resolves to in the veto (hook)"""
+        return self.vector_of(id)
+
+    def stage_block(self, stage, mask):
+        """(rows, ids) the lists of stage 0 / 1 are searched over, and those the exact scan (stage 2) walks (hook)"""
+        return self.block(mask)
+
+    def route_seen(self):
+        return self.rb_route
+
+    WALK_ROWS, WALK_ENTRIES = 1024, 4096                             # DESIGN.md 4.17: the rows a request walks, the entries it merges
+
+    def candidates_at(self, lists, D, examples):
+        """The candidates of one request from its positives' lists cut at depth D, in the words of include/vdb_flat.h and
+        DESIGN.md 4.17 and in numpy (the model goes through recommend_best_data._walk, a loop over tuples): a list with D
+        entries ends at its frontier, F is the smallest frontier, an entry with d < F is settled; beyond WALK_ENTRIES settled
+        entries only those in front of the first entry past the capacity count; per id the smallest distance; the examples
+        struck; ascending by (dp, -0.0 in front of +0.0, id), WALK_ROWS rows at most.  Returns (ids, open): open when something
+        may lie behind the candidates -- a list that came back full, the capacity, the row limit."""
+        cut = [(oi[:D], od[:D]) for oi, od in lists]
+        fronts = [od[-1] for _, od in cut if len(od) == D]
+        is_open = bool(fronts)
+        ids = np.concatenate([oi for oi, _ in cut]) if cut else np.zeros(0, U64)
+        d = np.concatenate([od for _, od in cut]) if cut else np.zeros(0, F32)
+        which = np.concatenate([np.full(len(oi), i) for i, (oi, _) in enumerate(cut)]) if cut else np.zeros(0, int)
+        if fronts:
+            settled = d < min(fronts)
+            ids, d, which = ids[settled], d[settled], which[settled]
+        if len(d) > self.WALK_ENTRIES:
+            order = np.lexsort((which, ids, ~np.signbit(d), d))
+            at = order[self.WALK_ENTRIES]
+            front = (d < d[at]) | ((d == d[at]) & np.signbit(d) & ~np.signbit(d[at]))
+            ids, d, which, is_open = ids[front], d[front], which[front], True
+        first = np.lexsort((which, d, ids))                          # per id its smallest distance (of equal ones the earlier list's bits)
+        keep = first[np.concatenate([[True], ids[first][1:] != ids[first][:-1]])] if len(first) else first
+        ids, d = ids[keep], d[keep]
+        mine = ~np.isin(ids, np.array(sorted(examples), dtype=U64))
+        ids, d = ids[mine], d[mine]
+        order = np.lexsort((ids, ~np.signbit(d), d))
+        if len(order) > self.WALK_ROWS:
+            order, is_open = order[:self.WALK_ROWS], True
+        return ids[order].tolist(), is_open
+
+    def best(self, pos, neg, ks, mask=None):
+        flat = np.array([i for p, n in zip(pos, neg) for i in list(p) + list(n)], dtype=U64)
+        self.refusal("best", flat)
+        self.resolve_before_upload(flat)
+        self.uploaded()
+        nl = self.n_live()
+        kmax = int(ks) if np.isscalar(ks) else max(int(x) for x in ks)
+        kcut, mmax = min(kmax, nl), max(len(p) + len(n) for p, n in zip(pos, neg))
+        D0, D1 = min(nl, 1024, max(2 * (min(kcut, 1024) + min(mmax, 1024)), 32)), min(nl, 1024)   # (include/vdb_flat.h: the stage depths)
+        route = self.route_seen()
+        use_lists = route == rbd.LISTS or (route == rbd.AUTO and D0 < nl)
+        depths = ([D0] + ([D1] if D1 > D0 else [])) if use_lists else []
+        out, dns, stages, searches = [], [], [], 0
+        for b, (p, n) in enumerate(zip(pos, neg)):
+            kb = min(k_of(ks, b), kcut)
+            examples = {int(i) for i in list(p) + list(n)}
+            pvecs = [self.example_of(i, j) for j, i in enumerate(p)]
+            nvecs = [self.example_of(i, len(p) + j) for j, i in enumerate(n)]
+
+            def kept_of(cands, dp_of):
+                """walk (id, dp) candidates in order: the veto with oracle.distance per candidate and negative, until kb are kept"""
+                good = []
+                for x in cands:
+                    if len(good) == kb:
+                        break
+                    if not nvecs:
+                        good.append((x, dp_of[x], F32(np.inf)))
+                        continue
+                    v, dn = self.veto_vector(x), F32(np.inf)
+                    veto = False
+                    for j, nv in enumerate(nvecs):
+                        t = md.pair_distance(self.metric, nv, v)
+                        veto = veto or not dp_of[x] < t
+                        dn = t if j == 0 or t < dn else dn
+                    if not veto:
+                        good.append((x, dp_of[x], dn))
+                return good
+
+            def folded(rows, bids):
+                """dp per id of a block: a left fold of the positives' full rankings, and the ids by (ordered dp, id)"""
+                order = np.argsort(bids, kind="stable")
+                dp = None
+                lists = []
+                for v in pvecs:
+                    oi, od = self.knn(rows, bids, v, len(rows)) if len(rows) else (np.zeros(0, U64), np.zeros(0, F32))
+                    lists.append((oi, od))
+                    t = np.zeros(len(bids), dtype=F32)
+                    t[order[np.searchsorted(bids[order], oi)]] = od
+                    dp = t if dp is None else np.where(t < dp, t, dp)
+                return lists, dp
+
+            done = None
+            for stage, D in enumerate(depths):
+                searches += len(p)
+                rows, bids = self.stage_block(stage, mask)
+                lists, dp = folded(rows, bids)
+                walk, is_open = self.candidates_at(lists, D, examples)
+                dp_of = dict(zip(bids.tolist(), dp))
+                good = kept_of(walk, dp_of)
+                if len(good) >= kb or not is_open:
+                    done = (stage, good)
+                    break
+            if done is None:
+                rows, bids = self.stage_block(rbd.STAGE_SCAN, mask)
+                _, dp = folded(rows, bids)
+                cand = ~np.isin(bids, np.array(sorted(examples), dtype=U64))
+                o = np.lexsort((bids[cand], ~np.signbit(dp[cand]), dp[cand]))          # (dp ascending, -0.0 in front of +0.0, then the id)
+                done = (rbd.STAGE_SCAN, kept_of(bids[cand][o].tolist(), dict(zip(bids.tolist(), dp))))
+            stages.append(done[0])
+            good = done[1][:kb]
+            out.append((np.array([x for x, _, _ in good], dtype=U64), np.array([d for _, d, _ in good], dtype=F32).view(np.uint32)))
+            dns.append(np.array([t for _, _, t in good], dtype=F32).view(np.uint32))
+        st = [len(pos), len(flat), stages.count(0), stages.count(1), stages.count(rbd.STAGE_SCAN), D0, searches]
+        return {"lists": out, "dn": dns, "bstats": st}
 
 
 # ---------------------------------------------------------------------------------------------------------------- mutants
@@ -1034,6 +1379,151 @@ INDEX_MUTANTS = {1: LostRemove, 2: StagedInvisibleOnce, 3: IdsNotMoved, 4: GrowF
                  12: RefillKeepsNorms}
 
 
+# -- the mutants of the three composed reads: one stale-state defect each, on the state those reads lean on
+class BestVetoStaleRanks(RefIndex):
+    """24. recommend by best: the veto resolves a candidate id through the id-order table (d_rank2row), and an add does not clear
+    rank_valid -- the table is the one built before the adds since the last compaction, so an id added (or written again) since
+    then resolves to the row of its lower neighbour in id order (or to its own old row)"""
+
+    table = None
+
+    def on_compact(self, shrink):
+        self.table = None
+
+    def on_reset(self):
+        self.table = None
+
+    def veto_vector(self, id):
+        if self.table is None:
+            at = np.nonzero(self.alive)[0]
+            order = np.argsort(self.ids[at], kind="stable")
+            self.table = (self.ids[at][order], at[order])
+        tids, trows = self.table
+        j = max(int(np.searchsorted(tids, U64(id), side="right")) - 1, 0)
+        return self.rows[min(int(trows[j]), self.n_rows() - 1)]
+
+
+class BestVetoFirstRow(RefIndex):
+    """25. recommend by best: among the rows that carry a candidate's id the veto takes the FIRST one, not the live one -- after a
+    re-add or an upsert dn and the veto come from the superseded vector (until a compaction drops it)"""
+
+    def veto_vector(self, id):
+        return self.rows[np.nonzero(self.ids == U64(id))[0][0]]
+
+
+class BestResolvesEarly(RecommendResolvesEarly):
+    """26. recommend by best: the examples' rows are resolved (id2row) BEFORE the flush -- and the compaction inside it -- of the
+    same read: every example is whatever sits at its old row number (the analogue of 16)"""
+
+
+class BestScanForgetsLive(RefIndex):
+    """27. recommend by best: the exact scan's own eligibility mask is the caller's mask alone, without the live bits -- a
+    removed row is scored, kept and returned by a request that ends in the scan (until a compaction drops it)"""
+
+    def stage_block(self, stage, mask):
+        if stage != rbd.STAGE_SCAN:
+            return self.block(mask)
+        rows, ids, alive = self.seen()
+        ok = self.ok_by_id(mask)
+        keep = np.ones(len(ids), dtype=bool) if ok is None else ok_of_ids(ok, ids)
+        return np.ascontiguousarray(rows[keep]), np.ascontiguousarray(ids[keep])
+
+    def veto_vector(self, id):
+        return self.rows[np.nonzero(self.ids == U64(id))[0][-1]]
+
+
+class BestStageOneUnmasked(RefIndex):
+    """28. recommend by best: the second list search (depth 1024) runs without the caller's mask, which was staged for the first"""
+
+    def stage_block(self, stage, mask):
+        return self.block(None if stage == 1 else mask)
+
+
+class MmrRowsOneCompactionOld(RefIndex):
+    """29. MMR: the host's id -> row map is not rebuilt by a compaction (only by adds and removes) -- the pair distances are read
+    from the rows the candidates had BEFORE the rows moved; ids and query distances still look right"""
+
+    snap = None
+
+    def on_compact(self, shrink):
+        if self.snap is None:
+            self.snap = (self.ids.copy(), self.alive.copy())
+
+    def _kill(self, ids):
+        self.snap = None
+        super()._kill(ids)
+
+    def mmr_vectors(self, ids):
+        if self.snap is None:
+            return super().mmr_vectors(ids)
+        sids, salive = self.snap
+        return np.stack([self.rows[min(int(np.nonzero(salive & (sids == U64(i)))[0][-1]), self.n_rows() - 1)] for i in ids])
+
+
+class MmrPairsOldRow(ByIdGathersOldRow):
+    """30. MMR: the pair distances of an upserted id use its superseded row (the search itself, and search by id, are right)"""
+
+    def vector_of(self, id):
+        return RefIndex.vector_of(self, id)
+
+    def mmr_vectors(self, ids):
+        return np.stack([self.before.get(int(i), RefIndex.vector_of(self, i)) for i in ids])
+
+
+class PerGroupStaleColumn(RefIndex):
+    """31. per group: the member listing reads the code column as of the PREVIOUS upload (a distinct or per-group read): a
+    set_codes since then reaches the search by group, not the listing"""
+
+    column = None
+
+    def listing_codes(self):
+        return self.codes if self.column is None else self.column
+
+    def distinct(self, *a, **kw):
+        try:
+            return super().distinct(*a, **kw)
+        finally:
+            self.column = self.codes.copy()
+
+    def per_group(self, *a, **kw):
+        try:
+            return super().per_group(*a, **kw)
+        finally:
+            self.column = self.codes.copy()
+
+
+class PerGroupListsTombstones(RefIndex):
+    """32. per group: the member listing forgets the live bit -- a removed row of a wanted code is listed, ranked and returned
+    (until a compaction drops it)"""
+
+    def listing_block(self, mask):
+        rows, ids, alive = self.seen()
+        ok = self.ok_by_id(mask)
+        keep = np.ones(len(ids), dtype=bool) if ok is None else ok_of_ids(ok, ids)
+        return np.ascontiguousarray(rows[keep]), np.ascontiguousarray(ids[keep])
+
+
+class GiantsDropMask(RefIndex):
+    """33. per group: the giants' route searches under "code == c" alone and drops the caller's mask"""
+
+    def giant_block(self, mask):
+        return self.block(None)
+
+
+class SwitchesRevertOnGrow(RefIndex):
+    """34. the two debug switches live in the store's header: a re-allocation (a capacity doubling) puts debug_set_per_group_scan_cap
+    and debug_set_recommend_best_route back to their defaults -- the answers stay, the counters show another route"""
+
+    def on_grow(self):
+        if self.cap:
+            self.pg_cap = self.rb_route = 0
+
+
+TWELVE_INDEX_MUTANTS = {24: BestVetoStaleRanks, 25: BestVetoFirstRow, 26: BestResolvesEarly, 27: BestScanForgetsLive, 28: BestStageOneUnmasked,
+                        29: MmrRowsOneCompactionOld, 30: MmrPairsOldRow, 31: PerGroupStaleColumn, 32: PerGroupListsTombstones,
+                        33: GiantsDropMask, 34: SwitchesRevertOnGrow}
+
+
 # ---------------------------------------------------------------------------------------------------------------- the store
 def flt_of(vdb, spec):
     """a filter as plain data -> MetadataFilter: ("eq" | "ne", field, value), ("exists", field), ("and" | "or", [specs]),
@@ -1212,15 +1702,50 @@ class StoreSim:
             neg.append([self.entries[s][0] for s in n])
         return self._named(self._pre(lambda p_, n_, k_, m_: self.index.recommend(p_, n_, k_, m_), pos, neg, int(k), spec=spec)["lists"])
 
+    # -- the three composed reads (store schedules with "twelve": True)
+    def search_mmr(self, q, k, lam, m, spec):
+        """VectorStore.search_mmr: the index's MMR under the pre-filter; the store returns ids and query distances, no scores"""
+        if self._empty():
+            return []
+        got = self._pre(lambda q_, k_, m_, l_, mk: self.index.mmr(q_, k_, m_, l_, mk), q[None, :], int(k), int(m), float(lam), spec=spec)
+        named = self._named(got["lists"])[0]
+        if "moved" not in got:
+            return named
+        return {"lists": [([s for s, _ in named], [b for _, b in named])], "moved": got["moved"]}   # (the model's: as_answer's form, and the cap's figure)
+
+    def search_groups(self, q, k, g, spec):
+        """VectorStore.search_groups over GROUP_FIELD: [(field value or None, members)] flattened to one list -- a header
+        ("#value", size) in front of every group's (name, distance bits) entries -- so that diff() compares values, sizes and members"""
+        if self._empty():
+            return []
+        value = {c: v for v, c in self.group_code.items()}
+        got = self._pre(lambda q_, k_, g_, mk: self.index.per_group(q_, k_, g_, mk), q[None, :], int(k), int(g), spec=spec)["groups"][0]
+        out = []
+        for code, ids, bits in got:
+            out.append((f"#{value.get(int(code))}", len(ids)))
+            out.extend(self._named([(ids, bits)])[0])
+        return out
+
+    def recommend_best_batch(self, requests, k, spec):
+        pos, neg = [], []
+        for p, n in requests:
+            for sid in list(p) + list(n):
+                if sid not in self.entries:
+                    raise Predicted("VectorNotFound", sid)
+            pos.append([self.entries[s][0] for s in p])
+            neg.append([self.entries[s][0] for s in n])
+        return self._named(self._pre(lambda p_, n_, k_, m_: self.index.best(p_, n_, k_, m_), pos, neg, int(k), spec=spec)["lists"])
+
 
 # ---------------------------------------------------------------------------------------------------------------- the runner
 READ_OPS = READS
 STORE_READS = ("s_search", "s_with_filter", "s_prefiltered", "s_within", "s_similar", "s_distinct")
 NEW_STORE_READS = ("s_recommend", "s_with_filters")                 # (schedules with "numeric": True only)
+NEWER_STORE_READS = ("s_mmr", "s_groups", "s_recommend_best")       # (schedules with "twelve": True only)
 
 
 def is_read(op):
-    return op[0] in READ_OPS or op[0] in NEW_READS or op[0] in STORE_READS or op[0] in NEW_STORE_READS
+    return op[0] in READ_OPS or op[0] in NEW_READS or op[0] in NEWER_READS or op[0] in STORE_READS or op[0] in NEW_STORE_READS or op[0] in NEWER_STORE_READS
 
 
 def queries(seed, key, log, B, d):
@@ -1308,7 +1833,88 @@ def materialise(trace, op, model):
         _, B, k, ekey, absent, m = op
         pos, neg = requests_of(seed, ekey, model, B, absent)
         return "recommend", (pos, neg, ks_of(k), mask_of(seed, m, model))
+    if kind == "mmr":
+        _, B, k, qkey, m, lkey, mask = op
+        q = queries(seed, qkey, model, B, d)
+        if model.n_live() and model.d == d:                          # query 0 lies next to the row written last: it is candidate 0 and pick 1
+            q[0] = model.rows[np.nonzero(model.alive)[0][-1]] + F32(0.05) * q[0]
+            if model.metric == COSINE and not q[0].any():
+                q[0] = F32(1.0)
+        return "mmr", (q, ks_of(k), int(m), lambdas_of(seed, lkey, B), mask_of(seed, mask, model))
+    if kind == "per_group":
+        _, B, k, qkey, g, mask = op
+        return "per_group", (queries(seed, qkey, model, B, d), ks_of(k), int(g), mask_of(seed, mask, model))
+    if kind == "best":
+        _, B, k, ekey, absent, mask = op
+        pos, neg = best_requests_of(seed, ekey, model, B, absent)
+        return "best", (pos, neg, ks_of(k), mask_of(seed, mask, model))
     raise ValueError(kind)
+
+
+LAMBDAS = (0.0, 0.3, 0.5, 0.7, 1.0)
+
+
+def lambdas_of(seed, lkey, B):
+    """the trade-off of an MMR read: one f32 for the batch (keys 0..4 name LAMBDAS outright), or one per query"""
+    if 0 <= int(lkey) < len(LAMBDAS):
+        return float(LAMBDAS[int(lkey)])
+    rng = rng_of(seed, lkey, 14)
+    if rng.random() < 0.5 or B == 1:
+        return float(rng.choice(LAMBDAS[:4]))
+    return np.array(rng.choice(LAMBDAS, B), dtype=F32)
+
+
+def best_requests_of(seed, ekey, log, B, absent):
+    """(positives, negatives) of a recommend-by-best read: per request 1 to 4 positives and 0 to 2 negatives from the live ids, half
+    of them among the 48 ids written last, an id repeated or put on both sides one time in five.  Request 0 always has two
+    positives or more and a negative.  When the row written last lies beside another live row x without being its copy (the op
+    "near"), request 0 is ([x, x], [the id written last -- and the one before it, if that lies beside x too]): such negatives veto
+    half or more of all rows, the nearest included, which is what sends a request on to list stage 1.  Else, when another live
+    row holds the very bits of the row written last (an add or an upsert that copies a stored row, a duplicate of a bulk), that
+    row's id is the first positive of request 0 -- the id written last is then the nearest candidate of a request with a
+    negative, and the veto has to resolve it to its row.  `absent` puts a removed (or never stored) id at a random place."""
+    rng = rng_of(seed, ekey, 15)
+    live = log.live_ids()
+    last = log.ids[log.alive][-48:]
+
+    def draw(n):
+        if not live.size:
+            return [0] * n
+        ids = live[rng.integers(0, live.size, n)]
+        recent = rng.random(n) < 0.5
+        ids[recent] = last[rng.integers(0, last.size, n)][recent]
+        return [int(i) for i in ids]
+    reqs = []
+    for b in range(B):
+        npos, nneg = int(rng.integers(1, 5)), int(rng.integers(0, 3))
+        if b == 0:
+            npos, nneg = max(npos, 2), max(nneg, 1)
+        p, n = draw(npos), draw(nneg)
+        if rng.random() < 0.2:
+            side = n if n and rng.random() < 0.5 else p
+            side[int(rng.integers(0, len(side)))] = p[int(rng.integers(0, len(p)))]
+        reqs.append([p, n])
+    if live.size:
+        at = np.nonzero(log.alive)[0]
+        twin = at[:-1][(log.rows[at[:-1]] == log.rows[at[-1]]).all(axis=1)]
+        gap = ((log.rows[at[:-1]].astype(np.float64) - log.rows[at[-1]]) ** 2).sum(axis=1) if at.size > 1 else np.zeros(0)
+        beside = at[:-1][(gap > 0) & (gap < 1.0)]
+        if beside.size:
+            x, vetoes = int(log.ids[beside[0]]), [int(log.ids[at[-1]])]
+            if at.size > 2 and at[-2] != beside[0] and 0 < ((log.rows[at[-2]].astype(np.float64) - log.rows[beside[0]]) ** 2).sum() < 1.0:
+                vetoes.append(int(log.ids[at[-2]]))
+            reqs[0] = [[x, x], vetoes]
+        elif twin.size:
+            x, newest = int(log.ids[twin[0]]), int(log.ids[at[-1]])
+            other = [int(i) for i in live[:3] if int(i) not in (x, newest)][:1]
+            reqs[0][0][0] = x
+            reqs[0] = [[x if i == newest else i for i in reqs[0][0]], [i for i in reqs[0][1] if i not in (x, newest)] or other]
+    if absent or not live.size:
+        gone = np.setdiff1d(log.ids, live)
+        b = int(rng.integers(0, B))
+        side = reqs[b][int(rng.integers(0, 2)) if reqs[b][1] else 0]
+        side[int(rng.integers(0, len(side)))] = int(gone[int(rng.integers(0, gone.size))]) if gone.size else ID_LIMIT - 1
+    return [p for p, _ in reqs], [n for _, n in reqs]
 
 
 def grouped_masks(seed, gkey, log, B, G, form):
@@ -1408,7 +2014,19 @@ def diff(want, got):
         for b, (w, g) in enumerate(zip(want["codes"], got["codes"])):
             if not np.array_equal(w, g):
                 return f"query {b}: group codes {g}, expected {w}"
-    for key in ("struck", "cut", "stages", "gstats", "rstats"):      # the engine's own counters of the read, where both sides have them
+    for key in ("scores", "dn"):                                     # MMR's score bits, the dn bits of recommend by best score
+        if key in want and key in got:
+            for b, (w, g) in enumerate(zip(want[key], got[key])):
+                if not np.array_equal(w, g):
+                    return f"query {b}: {key} bits {[hex(int(x)) for x in g]}, expected {[hex(int(x)) for x in w]}"
+    if "groups" in want and "groups" in got:                         # per group: the codes, the sizes, every member's id and distance bits
+        for b, (w, g) in enumerate(zip(want["groups"], got["groups"])):
+            if len(w) != len(g):
+                return f"query {b}: {len(g)} groups, expected {len(w)}"
+            for j, ((wc, wi, wd), (gc, gi, gd)) in enumerate(zip(w, g)):
+                if int(wc) != int(gc) or not np.array_equal(wi, gi) or not np.array_equal(wd, gd):
+                    return f"query {b}, group {j}: code {int(gc)} members {list(map(int, gi))} bits {[hex(int(x)) for x in gd]}, expected code {int(wc)} members {list(map(int, wi))} bits {[hex(int(x)) for x in wd]}"
+    for key in ("struck", "cut", "stages", "gstats", "rstats", "mstats", "pstats", "bstats"):   # the engine's own counters of the read, where both sides have them
         if key in want and key in got and want[key] != got[key]:
             return f"{key} {got[key]}, expected {want[key]}"
     return None
@@ -1424,6 +2042,12 @@ def resolve(trace, op, log):
         v = vectors(seed, key, 1, d)[0]
         at = np.nonzero(log.alive & (log.ids == U64(dup_of)))[0] if dup_of >= 0 else ()
         return [("add", (int(id), log.rows[at[-1]].copy() if len(at) else v))]
+    if kind == "near":                                               # a row beside a stored one: as a negative it vetoes about half of ALL rows,
+        _, id, key, of = op                                          # the nearest included (best_requests_of) -- a copy would veto every row
+        at = np.nonzero(log.alive & (log.ids == U64(of)))[0]
+        x, step = log.rows[at[-1]].astype(np.float64), vectors(seed, key, 1, d)[0].astype(np.float64)
+        step -= (step @ x) / max(x @ x, 1e-30) * x                   # (at right angles to the row: the half of the rows it vetoes is a fair one)
+        return [("add", (int(id), (x + 0.01 * step).astype(F32)))]
     if kind == "zero":
         return [("add", (int(op[1]), np.zeros(d, dtype=F32)))]
     if kind == "inf":                                                # one infinite element: the forward conversion of the rows refuses it
@@ -1493,7 +2117,9 @@ def run(trace, adapter, expected=None, on_read=None):
         else:
             if expected is not None and expected[step] is not None:
                 name, args, want = expected[step]
-                if "error" not in want and not (name in ("range", "grouped") and log.sharded):
+                if log.sharded and name in NEWER_READS:              # refused -- or, by MMR and per group, an empty index answered first
+                    want = capture(lambda: getattr(model, name)(*args))
+                elif "error" not in want and not (name in ("range", "grouped") and log.sharded):
                     log.uploaded()                                   # (a refused read uploads nothing: as on the uncached path)
             else:
                 name, args = materialise_store(trace, op, model) if store else materialise(trace, op, model)
@@ -1647,6 +2273,23 @@ def materialise_store(trace, op, model):
         pool = [NUMERIC_STORE_FILTERS[int(i)] for i in rng.integers(0, len(NUMERIC_STORE_FILTERS), 3)]
         specs = [None if rng.random() < 0.25 else pool[int(rng.integers(0, 3))] for _ in range(B)]
         return "search_batch_with_filters", (queries(seed, qkey, log, B, d), ks_of(k), specs)
+    if kind == "s_mmr":
+        _, k, qkey, lkey, m, spec = op
+        return "search_mmr", (queries(seed, qkey, log, 1, d)[0], int(k), float(LAMBDAS[int(lkey)]), int(m), spec)
+    if kind == "s_groups":
+        _, k, qkey, g, spec = op
+        return "search_groups", (queries(seed, qkey, log, 1, d)[0], int(k), int(g), spec)
+    if kind == "s_recommend_best":
+        _, B, k, rkey, spec, absent = op
+        rng = rng_of(seed, rkey, 16)
+        names = sorted(model.entries)
+        pick = lambda n: [names[int(i)] for i in rng.integers(0, len(names), n)] if names else ["doc0"] * n
+        reqs = [(pick(int(rng.integers(1, 4))), pick(int(rng.integers(0, 3)))) for _ in range(B)]
+        if names:                                                    # request 0: two positives, one of them on both sides -- a veto that bites
+            reqs[0] = (reqs[0][0][:1] + pick(1), reqs[0][0][:1])
+        if absent or not names:
+            reqs[int(rng.integers(0, B))][0][0] = "nobody"
+        return "recommend_best_batch", (reqs, int(k), spec)
     if kind == "s_recommend":
         _, B, k, rkey, spec, absent = op
         rng = rng_of(seed, rkey, 13)
@@ -2269,8 +2912,352 @@ class _Gen9(_Gen):
         return self.trace
 
 
+# ---------------------------------------------------------------------------------------------------------------- MMR, per group, recommend by best
+# Schedules of their own once more (TWELVE_PINNED), a generator class beside _Gen9 with an rng stream of its own: the 19 + 9 + 3
+# older traces stay op for op what they are.  The trace key "twelve" marks a schedule that holds the three kinds.
+PROFILES["twelve"] = dict(d=64, d2=40, zero=True, misfit=False)
+PROFILES["twelve-auto"] = dict(d=40, d2=64, zero=True, misfit=True, auto=0.3)
+
+TWELVE_PINNED = (
+    ("twelve-euclid", 101, "twelve", EUCLID, "all twelve read kinds, both debug switches set mutations before they are read; d = 64, reset to d = 40"),
+    ("twelve-cosine", 102, "twelve", COSINE, "the same with the zero-norm episode: the three composed reads fail while the row lives"),
+    ("twelve-dot", 103, "twelve", DOT, "the same under Dot"),
+    ("twelve-auto-euclid", 111, "twelve-auto", EUCLID, "d = 40 (ragged against the row pitch), reset to d = 64, auto-compaction on: the reads compact before they resolve ids; a misfit episode"),
+    ("twelve-auto-cosine", 112, "twelve-auto", COSINE, "auto-compaction with both error episodes"),
+    ("twelve-auto-dot", 113, "twelve-auto", DOT, "auto-compaction under Dot"),
+)
+BEST_KS = (1, 10, 113, 300)
+
+
+class _Gen12(_Gen9):
+    def __init__(self, seed, profile, metric):
+        super().__init__(seed, profile, metric)
+        self.trace["twelve"] = True
+        self.rng = np.random.default_rng([int(seed), 96])
+        self.kept, self.answers = None, {}
+
+    topping_up = False
+
+    def draw_B(self):
+        return int(self.rng.choice((1, 8))) if self.topping_up else super().draw_B()
+
+    def answer(self, op):
+        """the model's answer to a read op that is not emitted yet (the caps on the inputs are conditions on it).  The answer
+        to the op that IS emitted next is kept: pinned() hands it to slots(), so that the first run() does not compute it again.
+        Asked of a COPY of the model (the arrays are shared: a read replaces them, it never writes into them): the read's flush
+        and its auto-compaction must not have happened when a redrawn op is materialised, or a replay of the printed trace,
+        which materialises before the read, would see other arguments."""
+        import copy
+        trial = copy.copy(self.m)
+        trial.counts, trial._memo = dict(self.m.counts), {}
+        name, args = materialise(self.trace, op, trial)
+        want = capture(lambda: getattr(trial, name)(*args))
+        self.kept = (op, name, args, want)
+        return want
+
+    def emit(self, op):
+        if is_read(op) and self.kept is not None and self.kept[0] is op:
+            self.answers[len(self.trace["ops"])] = self.kept[1:]
+        self.kept = None
+        super().emit(op)
+
+    def read(self, kind=None, absent=False):
+        if kind is None:                                             # a new kind this mutation has not been followed by yet; the least used one
+            after = self.last_mut
+            want = [r for r in NEWER_READS if after and (after, r) not in self.pairs]
+            least = min(self.used[r] for r in READS12)
+            want = [r for r in want if self.used[r] <= least + 2]    # (no kind runs away)
+            kind = min(want or READS12, key=lambda r: (self.used[r], READS12.index(r)))
+        if kind not in NEWER_READS:
+            return super().read(kind, absent)
+        return getattr(self, "read_" + kind)(absent=absent) if kind == "best" else getattr(self, "read_" + kind)()
+
+    def mask12(self, none=0.6):
+        return self.draw_mask9(self.last_mut == "numbers", none)
+
+    def read_mmr(self, B=None, k=None, m=None, lkey=None, mask=False):
+        """B * k * m stays small (the model's selection is a Python loop over the pairs: 12 us each).  A key is redrawn until, with some
+        lambda < 1 and k > 1, a query's picks are not the plain top-k."""
+        rng = self.rng
+        B = B or self.draw_B()
+        m = m or int(rng.choice((8, 40, 200)))
+        per_query = k is None and rng.random() < 0.2
+        if k is None:
+            k = int(rng.choice([x for x in (3, 10, 113) if x <= m]))   # (k = 1 cannot move a pick: per-query k holds it)
+        while B > 1 and B * k * m > 1600:
+            B = {40: 9, 9: 8, 8: 1}[B]
+        if B * k * m > 1600 and m < MMR_MAX:
+            k = 10
+        if per_query and B > 1:
+            k = tuple(int(x) for x in rng.choice([x for x in (1, 3, 10) if x <= min(m, k)], B))
+        mask = self.mask12() if mask is False else mask
+        for attempt in range(2):                                     # (the second with lambda = 0: nothing but the distance between the picks)
+            op = ("mmr", B, k, self.k(), m, 0 if attempt == 1 else 1000 + self.k() if lkey is None else lkey, mask)
+            got = self.answer(op)
+            if "error" in got or got["moved"] or k == 1 or lkey == 4:    # (k = 1 and lambda = 1 cannot move a pick)
+                break
+        self.emit(op)
+
+    def read_per_group(self, B=None, k=None, g=None, mask=False, deep=False):
+        """a key is redrawn until some group has two members or more (g > 1); deep: until a member lies beyond rank 1024"""
+        rng = self.rng
+        B = B or min(self.draw_B(), 9 if self.m.n_rows() < 5000 else 4)   # (every query is a full ranking of the rows, and a walk over its groups)
+        k = k or self.draw_k(B)
+        g = g or int(rng.choice((1, 2, 3, 8, 32), p=(0.1, 0.25, 0.35, 0.2, 0.1)))
+        mask = self.mask12() if mask is False else mask
+        for _ in range(12):
+            op = ("per_group", B, k, self.k(), g, mask)
+            got = self.answer(op)
+            if "error" in got or g == 1 or (got["deep"] >= 1024 if deep else any(len(ids) > 1 for grp in got["groups"] for _, ids, _ in grp)):
+                break
+        self.emit(op)
+
+    def read_best(self, B=None, k=None, mask=False, absent=False, stage=None):
+        """a key is redrawn until at most a quarter of the requests come back empty -- and, with stage, one ends at that stage"""
+        rng = self.rng
+        B = B or min(self.draw_B(), 8 if self.m.n_rows() < 5000 else 4)   # (every example is a full ranking of the rows in the model)
+        if k is None:
+            k = tuple(int(x) for x in rng.choice(BEST_KS[:3], B)) if B > 1 and rng.random() < 0.15 else int(rng.choice(BEST_KS, p=(0.15, 0.45, 0.25, 0.15)))
+        mask = self.mask12() if mask is False else mask
+        for _ in range(12):
+            op = ("best", B, k, self.k(), bool(absent), mask)
+            got = self.answer(op)
+            if "error" in got or (4 * sum(1 for l in got["lists"] if not len(l[0])) <= B and (stage is None or stage in got["bstages"])):
+                break
+        assert stage is None or "error" in got or stage in got["bstages"], (op, got["bstages"])
+        self.emit(op)
+
+    def near(self, n):
+        """n rows beside one stored row: the negatives of the next best read's request 0 (best_requests_of)"""
+        x = self.live_id()
+        for _ in range(n):
+            self.emit(("near", self.fresh_ids(1), self.k(), x))
+
+    def copy_of(self, kind):
+        """an add, an upsert or a re-add whose vector is a copy of another stored row: the next best read names that row"""
+        live = self.m.live_ids()
+        x = int(live[int(self.rng.integers(0, live.size))])
+        if kind == "add":
+            return self.emit(("add", self.fresh_ids(1), self.k(), x))
+        i = self.dead_id() if kind == "readd" else None
+        if i is None:
+            kind, i = "upsert", int(live[(int(np.searchsorted(live, x)) + 1) % live.size])
+        self.emit((kind, i, self.k(), x))
+
+    def mix(self, steps, kinds=None):
+        kinds = kinds or ("add", "add", "upsert", "upsert", "readd", "remove", "remove", "remove_absent", "bulk", "compact",
+                          "compact_shrink", "auto_compact", "codes", "codes", "numbers")
+        for _ in range(steps):
+            r = self.rng.random()
+            if r < 0.1:
+                self.toggle()
+                continue
+            self.turn += 1
+            missing = [m for m in kinds if any((m, rd_) not in self.pairs for rd_ in NEWER_READS)]
+            kind = missing[self.turn % len(missing)] if missing and r < 0.75 else str(self.rng.choice(kinds))
+            self.mutate(kind)
+            self.read()
+            if self.rng.random() < 0.2:
+                self.read()
+
+    def codes_few(self):
+        """six codes over every id: above 1024 rows each from about 8000 rows on -- giants under ("set", "pg_cap", 1024)"""
+        self.emit(("codes", 0, self.m.id_bound, self.k(), 6))
+
+    def codes_many(self):
+        """about two rows per code: the second member of a group lies anywhere in the ranking"""
+        self.emit(("codes", 0, self.m.id_bound, self.k(), max(self.groups, self.m.n_live() // 2)))
+
+    def build(self):
+        p, rng, e, k = self.p, self.rng, self.emit, self.k
+        e(("set", "sparse_filter", int(rng.choice((1, 2)))))
+        e(("set", "shadow", 1))
+        e(("set", "bounce", 64))
+        self.bulk(int(rng.integers(1100, 1400)), p["d"])
+        e(("codes", 0, 3000, k(), self.groups))
+        self.mutate("numbers")
+        # ---- MMR: every stored row a candidate (m = 1024, B = 1); the row written last is candidate 0 of query 0 -- an upsert,
+        # then removes and a compaction, each straight in front of an MMR read
+        self.read_mmr(B=1, k=3, m=1024, lkey=2, mask=None)
+        self.mutate("upsert")
+        self.read_mmr(B=4, k=10, m=40, lkey=2, mask=None)
+        e(("remove_many", 60, k()))
+        e(("compact",))
+        self.read_mmr(B=4, k=10, m=40, lkey=1, mask=None)
+        # ---- per group: lists under the default cap; the whole column rewritten between two reads; tombstones of wanted codes
+        self.mutate("numbers")
+        self.read_per_group(B=4, k=10, g=3, mask=None)
+        e(("codes", 0, self.m.id_bound, k(), self.groups))
+        self.read_per_group(B=4, k=10, g=3, mask=None)
+        e(("remove_many", 60, k()))
+        self.read_per_group(B=9, k=113, g=3, mask=None)
+        # ---- recommend by best: the veto resolves the id written last -- behind a non-monotone add, an upsert and a re-add that
+        # copy a stored row (the next read names that row); the scan over tombstones; stage 1 under a mask
+        e(("compact",))
+        self.mutate("numbers")
+        self.read_best(B=4, k=10, mask=None)
+        self.copy_of("add")
+        self.read_best(B=4, k=10, mask=None)
+        self.copy_of("upsert")
+        self.read_best(B=4, k=10, mask=None)
+        e(("remove_many", 60, k()))
+        self.copy_of("readd")
+        self.read_best(B=4, k=113, mask=None)
+        self.near(1)
+        self.read_best(B=4, k=BEST_MAX_K, mask=None, stage=rbd.STAGE_SCAN)   # the 1024 nearest hold fewer than 1024 kept rows: the scan, dead rows in the store
+        self.near(2)
+        self.read_best(B=4, k=113, mask=("host", k(), 0.5), stage=1)
+        # ---- the switches are set here and read mutations later: forced lists, the low cap
+        e(("set", "rb_route", 1))
+        e(("set", "pg_cap", PG_LOW_CAP))
+        for kind in NEWER_READS[:2]:                                 # (ids to re-add are rare later: a compaction forgets them; best had its re-add above)
+            self.mutate("readd")
+            self.read(kind)
+        self.mix(1)
+        if p.get("auto"):
+            e(("auto_compact", p["auto"]))
+            self.read()
+        # grow through the doublings (the switches must survive the re-allocations); few codes: giants under the low cap
+        for n in (1300, 2500, 4500):
+            self.mutate("remove")
+            self.bulk(n)
+            self.read()
+            self.mix(1)
+        self.codes_few()
+        self.read_per_group(B=4, k=10, g=3, mask=None)                          # giants (above 1024 rows a code): the low cap across the re-allocations
+        self.codes_few()                                             # (the same six codes under another key: giants stay giants)
+        self.read_best(B=2, k=10, mask=None)                                    # route 1 since the start
+        e(("set", "rb_route", 2))
+        e(("set", "shadow", 1))
+        self.bulk(SMALL_N - 300 - self.m.n_rows())
+        self.mutate("add")
+        self.read_best(B=2, k=10, mask=None)                                    # route 2 across a re-allocation
+        self.read_per_group(B=2, k=10, g=8, mask=("host", k(), 0.9))            # giants under the caller's mask
+        e(("set", "rb_route", 0))
+        self.bulk(1000)                                              # across SMALL_N upward
+        self.mutate("add")
+        self.read_mmr(B=1, k=3, m=1024, lkey=3, mask=None)
+        self.codes_many()
+        e(("set", "pg_cap", 0))
+        self.read_per_group(B=4, k=10, g=3, mask=None, deep=True)
+        e(("codes", 0, self.m.id_bound, k(), self.groups))          # (back to codes the LUT has numbers for: a numeric mask admits rows again)
+        self.read("mmr")
+        self.mix(1)
+        # back down: most rows go, rows are staged, the compaction takes them along
+        e(("auto_compact", 0.0))
+        self.read("per_group")
+        e(("set", "bounce", 64))
+        e(("remove_many", self.m.n_live() - 2600, k()))
+        self.read()
+        self.mutate("add")
+        self.mutate("upsert")
+        e(("compact",))
+        self.read_mmr(B=4, k=10, m=40, lkey=2, mask=None)
+        e(("compact_shrink",))
+        self.read("per_group")
+        self.mix(1)
+        # the row count collides
+        e(("compact",))
+        self.read()
+        n = self.m.n_rows()
+        e(("remove_many", 700, k()))
+        e(("set", "bounce", 0))
+        e(("compact_shrink",))
+        self.bulk(n - self.m.n_rows())
+        self.read()
+        self.read("mmr")
+        self.mix(1)
+        # auto-compaction inside the read: the ids resolve to the rows AFTER it
+        for kind in NEWER_READS:
+            e(("auto_compact", p.get("auto") or 0.25))
+            e(("remove_many", int(self.m.n_live() * 0.4), k()))
+            if kind == "best":
+                self.read_best(B=4, k=10, mask=None)
+            else:
+                self.read(kind)
+        if not p.get("auto"):
+            e(("auto_compact", 0.0))
+        if p["zero"] and self.trace["metric"] == COSINE:
+            z = self.fresh_ids(1)
+            e(("zero", z))
+            for kind in NEWER_READS:
+                self.read(kind)
+            e(("remove", z))
+            self.read()                                              # (answers again; whichever kind is behind -- the top-up counts it)
+        if p["misfit"]:
+            z = self.fresh_ids(1)
+            e(("misfit", z, p["d"] + 3))
+            for kind in NEWER_READS:
+                self.read(kind)
+            e(("remove", z))
+            self.read()
+        self.read("best", absent=True)
+        self.mix(1)
+        # everything goes; the refill has another dimension
+        e(("remove_many", max(0, self.m.n_live() - 300), k()))
+        n = int(rng.integers(1100, 1300))
+        e(("codes", 0, self.next_id + n, k(), self.groups))
+        e(("reset", n, p["d2"], self.fresh_ids(n), 1, k(), 0.15))
+        self.read(NEWER_READS[self.trace["seed"] % 3])              # (the pinned seeds take every new kind here)
+        self.read_mmr(B=1, k=3, m=1024, lkey=2, mask=None)
+        self.mix(1)
+        # what the draws left out -- a third of the pairs per schedule, by its seed: the six pinned ones hold every pair twice over
+        for i, (m, r) in enumerate([(m, r) for m in MUTATIONS12 for r in NEWER_READS if m != "reset"]):
+            if i % 3 == self.trace["seed"] % 3 and (m, r) not in self.pairs and self.used[r] < 16:   # (at 8 % a kind, a read of the most frequent kind costs eight others)
+                self.mutate(m)
+                self.read(r)
+        # the older cap stays: no read kind below 8 % of the reads (twelve kinds: at most 12 % for the most frequent one).  Here,
+        # where the index is smallest, and with the read behind the last bulk counted in
+        self.topping_up = True                                       # (batches of 1 and 8 from here on: these reads are there for their count)
+        while min(self.used[r] for r in READS12) < 0.08 * (sum(self.used.values()) + 2):
+            self.read(min(READS12, key=lambda r: (self.used[r], READS12.index(r))))
+        self.bulk(1500)
+        self.read()
+        return self.trace
+
+
+LARGE_TWELVE = ("large-twelve", 121, EUCLID, "75 000 rows of d = 64: the searches inside the three composed reads run on the bf16 screening tier, "
+                "before and after a compaction and a shrinking compaction refilled to the same row count")
+
+
+def large_twelve_schedule(seed=LARGE_TWELVE[1], metric=LARGE_TWELVE[2]):
+    """at most 40 ops, small batches (in the model every ranking walks 75 000 rows); about two rows per code, so that stage A of
+    the search by group completes every query at its depth of 40 -- a deeper stage would leave the screening tier at this size"""
+    g = _Gen12(seed, "twelve", metric)
+    g.trace["profile"] = "large-twelve"
+    e, k = g.emit, g.k
+
+    def reads(deep=False):
+        g.read_mmr(B=2, k=10, m=40, lkey=2, mask=None)
+        g.read_per_group(B=2, k=10, g=3, mask=None, deep=deep)
+        g.read_best(B=2, k=10, mask=None)
+    e(("set", "shadow", 1))
+    e(("set", "sparse_filter", 1))
+    g.bulk(900, 64)
+    for n in (30_000, LARGE_ROWS - 30_900):
+        g.bulk(n)
+        e(("search", 1, 10, k(), None))
+    e(("codes", 0, g.m.id_bound, k(), LARGE_ROWS // 2))
+    g.mutate("add")
+    reads(deep=True)                                                 # (a member beyond rank 1024 of the full ranking)
+    g.read_mmr(B=1, k=3, m=1024, lkey=2, mask=None)                  # depth 1024 needs 240 (1024 + 192) rows for the tier: this one is an exact scan
+    g.copy_of("upsert")
+    reads()
+    e(("remove_many", 900, k()))
+    e(("compact",))
+    reads()
+    n = g.m.n_rows()
+    e(("remove_many", 900, k()))
+    e(("compact_shrink",))
+    g.bulk(n - g.m.n_rows())
+    reads()
+    return g
+
+
 def schedule(seed, profile, metric=EUCLID):
     """a trace of about 200 ops: see _Gen.build for the phases, PROFILES for what differs between profiles"""
+    if profile in ("twelve", "twelve-auto"):
+        return _Gen12(seed, profile, metric).build()
     return (_Gen9 if profile in ("nine", "nine-auto") else _Gen)(seed, profile, metric).build()
 
 
@@ -2284,6 +3271,13 @@ def pinned(name):
     for n, seed, profile, metric, _ in NEW_PINNED:
         if n == name:
             return _Gen9(seed, profile, metric).build()
+    for n, seed, profile, metric, _ in TWELVE_PINNED + (LARGE_TWELVE[:2] + ("large-twelve",) + LARGE_TWELVE[2:],):
+        if n == name:
+            g = large_twelve_schedule(seed, metric) if profile == "large-twelve" else _Gen12(seed, profile, metric)
+            trace = g.trace if profile == "large-twelve" else g.build()
+            if name not in _SLOTS:                                   # the answers the generator had to compute anyway
+                _SLOTS[name] = [g.answers.get(step) for step in range(len(trace["ops"]))]
+            return trace
     raise KeyError(name)
 
 
@@ -2299,6 +3293,10 @@ NEW_STORE_PINNED = (
     ("store-numeric-late", 56, COSINE, dict(table_at="mid", auto=0.4), "numeric fields, device filter mid-life, auto-compaction"),
     ("store-numeric-again", 57, DOT, dict(table_at="start", auto=0.0, again=True), "device filter on, off mid-life and on again: the new table takes every number"),
 )
+TWELVE_STORE_PINNED = (
+    ("store-twelve-early", 58, EUCLID, dict(table_at="start", auto=0.0), "MMR, groups and recommend by best through the store, device filter from the start"),
+    ("store-twelve-late", 59, COSINE, dict(table_at="mid", auto=0.4), "the same with the device filter switched on mid-life and auto-compaction"),
+)
 STORE_FILTERS = (("eq", "par", "1"), ("ne", "par", "0"), ("exists", "grp"), ("and", [("exists", "grp"), ("ne", "ver", "2")]),
                  ("or", [("eq", "par", "2"), ("eq", "grp", "g3")]), ("eq", "grp", "g5"))
 
@@ -2308,7 +3306,7 @@ NUMERIC_STORE_FILTERS = STORE_FILTERS + (
     ("gt", "ts", "-inf"), ("le", "price", 3.5))
 
 
-def store_schedule(seed, metric, table_at="mid", auto=0.0, steps=110, numeric=False, again=False):
+def store_schedule(seed, metric, table_at="mid", auto=0.0, steps=110, numeric=False, again=False, twelve=False):
     """numeric: the schedules of the numeric fields (doc_fields: ts, price), the filter pool NUMERIC_STORE_FILTERS and the two
     store reads s_recommend and s_with_filters; again: the device filter goes off and on again at two thirds of the life.
     Without them the trace is, draw for draw, the one STORE_PINNED was dealt."""
@@ -2318,6 +3316,9 @@ def store_schedule(seed, metric, table_at="mid", auto=0.0, steps=110, numeric=Fa
     READS_, FILTERS_ = (STORE_READS + NEW_STORE_READS, NUMERIC_STORE_FILTERS) if numeric else (STORE_READS, STORE_FILTERS)
     if numeric:
         trace["numeric"] = True
+    if twelve:                                                       # (the schedules of s_mmr, s_groups and s_recommend_best: rows carry duplicates already)
+        trace["twelve"] = True
+        READS_ = READS_ + NEWER_STORE_READS
     ops = trace["ops"]
     docs, gone, key = set(), set(), [0]
 
@@ -2347,6 +3348,13 @@ def store_schedule(seed, metric, table_at="mid", auto=0.0, steps=110, numeric=Fa
         elif kind == "s_with_filters":
             B = int(rng.choice(BATCHES))
             ops.append((kind, B, tuple(int(x) for x in rng.choice(KS[:3], B)) if rng.random() < 0.5 else kk, k(), k()))
+        elif kind == "s_mmr":
+            m = int(rng.choice((8, 40, 200)))
+            ops.append((kind, min(max(kk, 3), 10, m), k(), int(rng.integers(0, 4)), m, flt()))
+        elif kind == "s_groups":
+            ops.append((kind, min(max(kk, 3), 10), k(), int(rng.choice((1, 2, 3, 8), p=(0.1, 0.3, 0.4, 0.2))), flt()))
+        elif kind == "s_recommend_best":
+            ops.append((kind, int(rng.choice((1, 4, 8))), max(kk, 10), k(), flt(), bool(rng.random() < 0.1)))
         else:
             ops.append((kind, int(rng.choice((1, 8, 9))), kk, k(), flt()))
 
@@ -2415,6 +3423,9 @@ def store_pinned(name):
     for n, seed, metric, kw, _ in NEW_STORE_PINNED:
         if n == name:
             return store_schedule(seed, metric, numeric=True, **kw)
+    for n, seed, metric, kw, _ in TWELVE_STORE_PINNED:
+        if n == name:
+            return store_schedule(seed, metric, numeric=True, twelve=True, **kw)
     raise KeyError(name)
 
 
@@ -2422,7 +3433,7 @@ def store_pinned(name):
 def read_begins(trace, op, model):
     """What every read does to the model's state, without the oracle: True when the model refuses it (then nothing is uploaded,
     exactly as Model.search & co. raise before they upload), else the staged rows are uploaded and auto-compaction may run."""
-    if op[0] == "grouped" and model.sharded:
+    if op[0] in ("grouped", "best") and model.sharded:
         return True
     if (op[5] != "host") if op[0] == "grouped" else (op[0] != "range" and op[-1] is not None and op[-1][0] in ("compiled", "numeric")):
         model.table_uploaded()                                       # (the mask is compiled before the read is called)
@@ -2430,6 +3441,9 @@ def read_begins(trace, op, model):
         ids = materialise(trace, op, model)[1][0] if op[0] == "by_id" else None
         if op[0] == "recommend":
             pos, neg = requests_of(trace["seed"], op[3], model, op[1], op[4])
+            ids = [i for p, n in zip(pos, neg) for i in p + n]
+        if op[0] == "best":
+            pos, neg = best_requests_of(trace["seed"], op[3], model, op[1], op[4])
             ids = [i for p, n in zip(pos, neg) for i in p + n]
         model.refusal({"masked": "search", "sparse": "search", "numeric": "search", "recommend": "by_id"}.get(op[0], op[0]), ids)
     except Predicted:
@@ -2461,7 +3475,11 @@ _SLOTS = {}
 
 
 def slots(name, trace):
-    """the `expected` list of run() for a pinned trace: computed by the first run, shared by every later one"""
+    """the `expected` list of run() for a pinned trace: computed by the first run, shared by every later one.  For the
+    TWELVE_PINNED schedules and large-twelve, pinned() has put the answers in that _Gen12 computed while it built the trace
+    (_Gen12.answer / emit: kept by identity of the op it emits next) -- hidden state that ties a trace to its answers by NAME.
+    tests/test_lifecycle_cpu.py::test_twelve_traces_are_plain_data_and_replay is the guard: it replays one whole printed trace
+    without them and compares name, arguments and answer of every kept slot."""
     return _SLOTS.setdefault(name, [None] * len(trace["ops"]))
 
 
@@ -2499,7 +3517,7 @@ class GpuIndexAdapter(EngineErrors):
         self.ix = vdb.GpuFlatIndex(vdb.DistanceMetric(metric), keep_host_copy=False, devices=devices)
         self.table = vdb.MetaTable(0)
         self.id_bound = 0
-        self.settings = dict(shadow=0, tiers=0, sparse_filter=0, screen=1, large_k=1, sample_cache=1, split=1, split_after=0)
+        self.settings = dict(shadow=0, tiers=0, sparse_filter=0, screen=1, large_k=1, sample_cache=1, split=1, split_after=0, pg_cap=0, rb_route=0)
         self.seen = Counter()
         self.route, self.raw = None, None
         self._compactions, self._cap = 0, 0
@@ -2559,7 +3577,11 @@ class GpuIndexAdapter(EngineErrors):
 
     def set(self, name, value):
         ix = self.ix
-        {"shadow": lambda: ix.set_shadow(bool(value)), "sample_cache": lambda: ix.set_sample_cache(bool(value)),
+        if self.sharded and name in ("pg_cap", "rb_route"):          # (a sharded handle refuses the two reads and their switches alike)
+            self.settings[name] = int(value)
+            return
+        {"pg_cap": lambda: ix.debug_set_per_group_scan_cap(int(value)), "rb_route": lambda: ix.debug_set_recommend_best_route(int(value)),
+         "shadow": lambda: ix.set_shadow(bool(value)), "sample_cache": lambda: ix.set_sample_cache(bool(value)),
          "screen": lambda: ix.set_screen(int(value)), "tiers": lambda: ix.set_tiers(int(value)),
          "sparse_filter": lambda: ix.set_sparse_filter(int(value)), "large_k": lambda: ix.set_large_k(bool(value)),
          "bounce": lambda: ix.debug_set_compact_bounce(int(value)), "split": lambda: ix.set_split(int(value)),
@@ -2611,6 +3633,8 @@ class GpuIndexAdapter(EngineErrors):
     def twin(self, model):
         """a fresh index bulk-loaded with the model's survivors and a fresh table with its codes, presence bits and numbers"""
         t = GpuIndexAdapter(self.vdb, model.metric)
+        for name in ("pg_cap", "rb_route"):                          # (the twin's counters are compared too: it takes the same routes)
+            t.set(name, self.settings[name])
         rows, ids = model.survivors()
         t.add_bulk(rows, ids)
         t.set_codes(0, model.codes[:max(model.col_len, 1)])
@@ -2643,6 +3667,44 @@ class GpuIndexAdapter(EngineErrors):
         self.seen["recommend_examples"] += st[1]
         self.seen["recommend_struck"] += st[2]
         return {"lists": lists_of(gi, gd, gc), "rstats": st[1:4]}
+
+    def mmr(self, q, ks, m, lam, mask=None):
+        k, kw = (int(ks), {}) if np.isscalar(ks) else (0, {"ks": ks})
+        gi, gd, gs, gc = self._read(lambda: self._masked(mask, lambda **mk: self.ix.search_batch_mmr(q, k, int(m), lam, **kw, **mk)))
+        out = {"lists": lists_of(gi, gd, gc), "scores": [np.array(gs[b, :int(c)], dtype=F32).view(np.uint32) for b, c in enumerate(gc)]}
+        self.seen["bf16_in_mmr"] += self._screened()
+        if not self.sharded:                                         # (a sharded handle answers an empty index and keeps no counters)
+            st = self.ix.mmr_stats()
+            self.seen["mmr_pairs"] += st[3]
+            self.seen["mmr_candidates"] += st[2]
+            out["mstats"] = st[:5]
+        return out
+
+    def per_group(self, q, ks, g, mask=None):
+        gi, gd, gcodes, gsizes, gc = self._read(lambda: self._masked(mask, lambda **mk: self.ix.search_batch_per_group(q, ks, int(g), self.table, 0, **mk)))
+        groups = [[(int(gcodes[b, j]), np.array(gi[b, j, :int(gsizes[b, j])], dtype=U64), np.array(gd[b, j, :int(gsizes[b, j])], dtype=F32).view(np.uint32))
+                   for j in range(int(c))] for b, c in enumerate(gc)]
+        out = {"lists": [(np.array([ids[0] for _, ids, _ in grp], dtype=U64), np.array([d[0] for _, _, d in grp], dtype=np.uint32)) for grp in groups],
+               "groups": groups}
+        self.seen["bf16_in_per_group"] += self._screened()
+        if not self.sharded:
+            st = self.ix.per_group_stats()
+            for j, key in ((2, "per_group_filled"), (3, "per_group_giants"), (5, "per_group_listed")):
+                self.seen[key] += st[j]
+            out["pstats"] = st[1:7]
+        return out
+
+    def best(self, pos, neg, ks, mask=None):
+        gi, gd, gn, gc = self._read(lambda: self._masked(mask, lambda **mk: self.ix.recommend_best_batch(pos, neg, ks, **mk)))
+        st = self.ix.recommend_best_stats()
+        for j, key in ((2, "best_stage0"), (3, "best_stage1"), (4, "best_scan"), (6, "best_list_searches")):
+            self.seen[key] += st[j]
+        self.seen["bf16_in_best"] += self._screened()
+        return {"lists": lists_of(gi, gd, gc), "dn": [np.array(gn[b, :int(c)], dtype=F32).view(np.uint32) for b, c in enumerate(gc)], "bstats": st[:7]}
+
+    def _screened(self):
+        """did the last search of the handle run on the bf16 screening tier (the engine's own flag)"""
+        return 0 if self.sharded else int(bool(self.ix.last_stats()["bf16_screen"]))
 
     def _read(self, call):
         try:
@@ -2803,6 +3865,30 @@ class GpuStoreAdapter(EngineErrors):
         qs = [self.vdb.Vector(x) for x in q]
         out = [self._out(r) for r in self._read(lambda: self.store.search_distinct_batch(qs, k, StoreSim.GROUP_FIELD, flt_of(self.vdb, spec)))]
         self.seen["distinct"] += 1
+        return out
+
+    def search_mmr(self, q, k, lam, m, spec):
+        out = self._out(self._read(lambda: self.store.search_mmr(self.vdb.Vector(q), k, lam, m, flt_of(self.vdb, spec))))
+        self.seen["mmr_pairs"] += self.store.index().mmr_stats()[3] if out else 0
+        return out
+
+    def search_groups(self, q, k, g, spec):
+        got = self._read(lambda: self.store.search_groups(self.vdb.Vector(q), k, StoreSim.GROUP_FIELD, g, flt_of(self.vdb, spec)))
+        out = []
+        for value, members in got:
+            out.append((f"#{value}", len(members)))
+            out.extend(self._out(members))
+        if out:
+            st = self.store.index().per_group_stats()
+            self.seen["per_group_filled"] += st[2]
+            self.seen["per_group_groups"] += st[1]
+        return out
+
+    def recommend_best_batch(self, requests, k, spec):
+        out = [self._out(r) for r in self._read(lambda: self.store.recommend_best_batch(requests, k, flt_of(self.vdb, spec)))]
+        st = self.store.index().recommend_best_stats()
+        self.seen["best_stage0"] += st[2]
+        self.seen["best_later"] += st[3] + st[4]
         return out
 
 

@@ -149,13 +149,15 @@ def _elig(live, mask):
     return e
 
 
-def definition(key, metric, rows, requests, k, ids=None, live=None, mask=None):
-    """per request (ids, dp, dn).  live: the stored rows (len counts them); mask: the rows the caller's mask admits"""
+def definition(key, metric, rows, requests, k, ids=None, live=None, mask=None, tables=None):
+    """per request (ids, dp, dn).  live: the stored rows (len counts them); mask: the rows the caller's mask admits.  tables: what
+    gives d(e, .) in place of _tables -- same arguments, same result, NOT cached by case name (tests/lifecycle.py: a life of the
+    index changes the rows under one name, so its model passes rankings of its own, kept until the next mutation)"""
     elig = _elig(live, mask)
     ks, _ = _ks(requests, k, n_live_of(rows, live))
     out = []
     for req, kb in zip(requests, ks):
-        pt, nt = _tables(key, metric, rows, req, ids, elig)
+        pt, nt = (tables or _tables)(key, metric, rows, req, ids, elig)
         own, dp, dn, kept = _row_facts(rows, req, ids, elig, pt, nt)
         out.append(_answer(own, dp, dn, np.nonzero(kept)[0], kb))
     return out
@@ -197,8 +199,8 @@ def _walk(req, own_of, pt, D):
     return [x for _, x in walk], is_open
 
 
-def lists_route(key, metric, rows, requests, k, ids=None, live=None, mask=None, route=AUTO):
-    """(answers, stages, stats): the engine's routes restated on the oracle's rankings"""
+def lists_route(key, metric, rows, requests, k, ids=None, live=None, mask=None, route=AUTO, tables=None):
+    """(answers, stages, stats): the engine's routes restated on the oracle's rankings (tables: as in definition())"""
     n = len(rows)
     elig = _elig(live, mask)
     nl = n_live_of(rows, live)
@@ -211,7 +213,7 @@ def lists_route(key, metric, rows, requests, k, ids=None, live=None, mask=None, 
     depths = ([D0] + ([D1] if D1 > D0 else [])) if use_lists else []
     answers, stages, searches = [], [], 0
     for req, kb in zip(requests, ks):
-        pt, nt = _tables(key, metric, rows, req, ids, elig)
+        pt, nt = (tables or _tables)(key, metric, rows, req, ids, elig)
         own_, dp, dn, kept = _row_facts(rows, req, ids, elig, pt, nt)
         done = None
         for stage, D in enumerate(depths):

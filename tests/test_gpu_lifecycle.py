@@ -25,7 +25,14 @@ Grouped, recommend and numeric-filter reads (lifecycle.NEW_PINNED, NEW_STORE_PIN
 kinds through a plain handle (grouped_stats [0]-[5] and recommend_stats [1]-[3] compared with the model read by read; the
 grouped scan, the per-group fallback of k > 2048, unfiltered queries, folded examples, struck entries and numeric compiles
 must all have been counted; twins with a fresh MetaTable on every fourth grouped / recommend read) and through a sharded
-handle (every grouped read refused), three store schedules with numeric fields.  E_g > 131072 is out of reach at 20 000 rows."""
+handle (every grouped read refused), three store schedules with numeric fields.  E_g > 131072 is out of reach at 20 000 rows.
+
+MMR, per-group and recommend-by-best reads (lifecycle.TWELVE_PINNED, large-twelve, TWELVE_STORE_PINNED): six index schedules of
+all twelve read kinds through a plain handle -- MMR's score bits, the groups' codes, sizes and members, the dn bits, and
+mmr_stats [0]-[4], per_group_stats [1]-[6], recommend_best_stats [0]-[6] compared read by read; the counters must show MMR
+pairs, member lists filled and giants searched, best answered at list stage 0, at stage 1 and by the exact scan; a twin on every
+fourth read of each kind -- and through a sharded handle (all three refused, after the empty-index answer where the header puts
+it first); one 75 000-row schedule whose inner searches run on the bf16 tier; two store schedules."""
 import numpy as np
 import pytest
 
@@ -39,6 +46,8 @@ LARGE_NAMES = [p[0] for p in lc.LARGE_PINNED]
 STORE_NAMES = [p[0] for p in lc.STORE_PINNED]
 NEW_NAMES = [p[0] for p in lc.NEW_PINNED]
 NEW_STORE_NAMES = [p[0] for p in lc.NEW_STORE_PINNED]
+TWELVE_NAMES = [p[0] for p in lc.TWELVE_PINNED]
+TWELVE_STORE_NAMES = [p[0] for p in lc.TWELVE_STORE_PINNED]
 _TRACES = {}
 
 
@@ -51,7 +60,7 @@ def vdb():
 
 def trace_of(name):
     if name not in _TRACES:
-        _TRACES[name] = lc.store_pinned(name) if name in STORE_NAMES else lc.pinned(name)
+        _TRACES[name] = lc.store_pinned(name) if name in STORE_NAMES + TWELVE_STORE_NAMES else lc.pinned(name)
     return _TRACES[name]
 
 
@@ -201,6 +210,110 @@ def test_sharded_lifecycle_nine(vdb, name):
     assert meant[("grouped", "answered")] == 0 and seen["grouped_scan"] + seen["grouped_fallback"] == 0, (seen, meant)
     assert meant[("recommend", "answered")] > 0 and meant[("numeric", "answered")] > 0 and meant["numeric_answered"] > 0, meant
     assert seen["recommend_examples"] > 0 and seen["recommend_struck"] > 0 and seen["numeric_compiles"] > 0, seen
+
+
+def life12(vdb, name, devices=None, trace=None):
+    """one schedule of the twelve read kinds (lifecycle.TWELVE_PINNED) through an index adapter: every read against the model --
+    for the three composed reads the lists, MMR's score bits, the groups' codes, sizes and members, the dn bits, and
+    mmr_stats [0]-[4], per_group_stats [1]-[6], recommend_best_stats [0]-[6] (lifecycle.diff).  On a plain handle every fourth
+    read of each of the three kinds is made again on a twin -- a fresh index bulk-loaded with the survivors, a fresh MetaTable,
+    the two debug switches as they stand -- and the two answers, counters included, are compared."""
+    t = trace or trace_of(name)
+    ad = lc.GpuIndexAdapter(vdb, t["metric"], devices=devices)
+    meant, nth = lc.Counter(), lc.Counter()
+
+    def on_read(step, op, model, args, got):
+        if "error" in got:
+            meant[(op[0], got["error"][0])] += 1
+            return
+        meant[(op[0], "answered")] += 1
+        meant[(op[0], "rows")] += sum(len(l[0]) for l in got["lists"])
+        if op[0] in lc.NEWER_READS and not ad.sharded:
+            nth[op[0]] += 1
+            if nth[op[0]] % 4 == 0:
+                twin = ad.twin(model)
+                try:
+                    again = getattr(twin, op[0])(*args)
+                finally:
+                    twin.close()
+                what = lc.diff(got, again)
+                assert what is None, (name, step, op, "the twin answers otherwise", what)
+                meant["twins_" + op[0]] += 1
+    try:
+        model = lc.run(t, ad, expected=lc.slots(name, t), on_read=on_read)
+    finally:
+        ad.close()
+    print(name, "sharded" if devices else "plain", dict(ad.seen), dict(meant), model.counts)
+    return ad.seen, meant, model
+
+
+@pytest.mark.parametrize("name", TWELVE_NAMES)
+def test_index_lifecycle_twelve(vdb, name):
+    """MMR, per-group and recommend-by-best reads in a long life of the index: the row written last is a candidate behind every
+    kind of write, compactions by hand and inside the read, doublings with both debug switches set, a reset to another
+    dimension, the zero-norm and misfit episodes.  The engine's own counters must show the routes: MMR pairs, member lists
+    filled and giants searched, best answered at list stage 0, at stage 1 and by the exact scan."""
+    seen, meant, model = life12(vdb, name)
+    assert seen["mmr_pairs"] > 0 and seen["mmr_candidates"] > 0, seen
+    assert seen["per_group_filled"] > 0 and seen["per_group_giants"] > 0 and seen["per_group_listed"] > 0, seen
+    assert seen["best_stage0"] > 0 and seen["best_stage1"] > 0 and seen["best_scan"] > 0 and seen["best_list_searches"] > 0, seen
+    assert all(meant["twins_" + kind] >= 1 for kind in lc.NEWER_READS), meant
+    assert all(meant[(kind, "answered")] > 0 and meant[(kind, "rows")] > 0 for kind in lc.READS12), meant
+    t = trace_of(name)
+    for kind in lc.NEWER_READS:
+        if t["metric"] == lc.COSINE:
+            assert meant[(kind, "InvalidVector")] >= 1, (kind, meant)
+        if any(op[0] == "misfit" for op in t["ops"]):
+            assert meant[(kind, "DimensionMismatch")] >= 1, (kind, meant)
+    assert meant[("best", "VectorNotFound")] >= 1, meant
+
+
+@pytest.mark.parametrize("name", TWELVE_NAMES)
+def test_sharded_lifecycle_twelve(vdb, name):
+    """the same schedules through one sharded handle: recommend by best refuses it before anything else, MMR and per group
+    answer an empty index first and refuse it otherwise (these schedules never read an empty index: every read of the three is
+    refused); the nine older kinds behave as before -- range and grouped refused, the others answered"""
+    seen, meant, model = life12(vdb, name, devices=[0, 0, 0])
+    t = trace_of(name)
+    for kind in lc.NEWER_READS + ("range", "grouped"):
+        assert meant[(kind, "Refused")] == sum(1 for op in t["ops"] if op[0] == kind) > 0, (kind, meant)
+        assert meant[(kind, "answered")] == 0, (kind, meant)
+    assert seen["mmr_pairs"] + seen["per_group_filled"] + seen["per_group_giants"] + seen["best_list_searches"] == 0, seen
+    for kind in ("search", "masked", "sparse", "by_id", "distinct", "recommend", "numeric"):
+        assert meant[(kind, "answered")] > 0, (kind, meant)
+
+
+def test_large_lifecycle_twelve(vdb):
+    """75 000 rows of d = 64: MMR's candidate search, the search by group inside per group and the list searches of recommend
+    by best run on the bf16 screening tier -- the engine's own last_stats()["bf16_screen"] after every such read -- before
+    and after a compaction and a shrinking compaction refilled to the same row count; one MMR read at m = 1024 with B = 1, whose
+    depth leaves the tier at this size"""
+    seen, meant, model = life12(vdb, "large-twelve")
+    for kind in lc.NEWER_READS:                                      # four rounds of reads, each on the tier
+        assert meant[(kind, "answered")] == 4 + (kind == "mmr") and seen["bf16_in_" + kind] == 4, (kind, seen, meant)
+    # (the fifth MMR read is the one at m = 1024, B = 1: depth 1024 needs 240 (1024 + 192) = 291 840 rows for the tier -- an exact scan here)
+    assert seen["mmr_pairs"] > 0 and seen["per_group_filled"] > 0 and seen["best_stage0"] > 0 and seen["best_list_searches"] > 0, seen
+    assert seen["compactions"] >= 2 and seen["shrunk"] >= 1 and seen["grown_with_shadow"] >= 2, seen
+
+
+@pytest.mark.parametrize("name", TWELVE_STORE_NAMES)
+def test_store_lifecycle_twelve(vdb, name):
+    """VectorStore.search_mmr, search_groups and recommend_best_batch beside the eight older store reads, with upserts, filters
+    from the pool, the device filter from the start (early) or switched on mid-life (late: search_groups then sends the field's
+    column up for the call alone, before), auto-compaction in the late one"""
+    t = trace_of(name)
+    ad = lc.GpuStoreAdapter(vdb, t["metric"], auto_compact=t["auto"])
+    kinds = lc.Counter()
+    try:
+        lc.run(t, ad, expected=lc.slots(name, t), on_read=lambda step, op, model, args, got: kinds.update([(op[0], "error" in got)]))
+    finally:
+        ad.close()
+    print(name, dict(ad.seen), dict(kinds))
+    seen = ad.seen
+    assert all(kinds[(k, False)] > 0 for k in lc.STORE_READS + lc.NEW_STORE_READS + lc.NEWER_STORE_READS), kinds
+    assert any(e for (_, e) in kinds), kinds                                                   # a predicted error was met
+    assert seen["mmr_pairs"] > 0 and seen["per_group_filled"] > 0 and seen["per_group_groups"] > 0 and seen["best_stage0"] > 0, seen
+    assert seen["prefiltered_compiled"] > 0 and seen["compactions"] > 0, seen
 
 
 @pytest.mark.parametrize("name", NEW_STORE_NAMES)

@@ -14,9 +14,15 @@ every new index schedule and 22 / 23 on the store schedules they apply to, every
 read kinds with all twelve mutations, (numbers, r) for every r that can carry a numeric mask, two LUT regrows per schedule,
 and the caps: the old three, at most a quarter of the grouped per-query answers empty, 80 % of the numeric masks keeping
 5-95 % of the live rows, every recommend read striking or cutting an entry.  (A sharded handle refuses every grouped read too:
-with the range reads that is about a fifth of the reads of these schedules.)"""
+with the range reads that is about a fifth of the reads of these schedules.)
+
+The MMR, per-group and recommend-by-best reads (TWELVE_PINNED, large-twelve, TWELVE_STORE_PINNED) get them once more at the end
+of the file: the 19 + 9 + 3 older traces have not moved, the reference adapter passes with all three counter vectors, the
+sharded reference refuses what the model says, mutants 24-34 fall on all six index schedules, a failing trace shrinks to at
+most eight ops, every (mutation, first read) pair of the three kinds, and their caps with the model alone."""
 from collections import Counter
 
+import numpy as np
 import pytest
 
 import lifecycle as lc
@@ -195,6 +201,14 @@ OLD_DIGESTS = {
     "store-euclid-early": "65aa23185b83342d",
 }
 NEW_NAMES = [p[0] for p in lc.NEW_PINNED]
+# the 9 + 3 schedules that came with the grouped / recommend / numeric reads and with the SPLIT layout: digests computed with the
+# generator of the commit before MMR, per group and recommend by best became read kinds (lifecycle.TWELVE_PINNED)
+NINE_DIGESTS = {
+    "nine-euclid": "12397159a246d068", "nine-cosine": "e3c076a8a95bf529", "nine-dot": "3824bc828f55e8b1",
+    "nine-auto-euclid": "8a375c4f6d468b01", "nine-auto-cosine": "83c43e4baaacb552", "nine-auto-dot": "6b687f90ba5fb2af",
+    "store-numeric-early": "2fcaa6ee9548e37d", "store-numeric-late": "b073d66ac77e74be", "store-numeric-again": "a21f2b5f01728d1c",
+    "split-adaptive-euclid": "b7a12e67c50c653b", "split-mode2-cosine": "a7de658198423643", "split-off-then-on-dot": "2624a8bd8d719f87",
+}
 
 
 def test_the_old_schedules_do_not_move():
@@ -202,6 +216,16 @@ def test_the_old_schedules_do_not_move():
     assert sorted(OLD_DIGESTS) == sorted(NAMES + LARGE_NAMES + STORE_NAMES) and len(OLD_DIGESTS) == 19
     got = {name: hashlib.sha256(repr(trace_of(name)).encode()).hexdigest()[:16] for name in OLD_DIGESTS}
     assert got == OLD_DIGESTS, {n: d for n, d in got.items() if d != OLD_DIGESTS[n]}
+    nine = {p[0]: lc.pinned(p[0]) for p in lc.NEW_PINNED}
+    nine.update({p[0]: lc.store_pinned(p[0]) for p in lc.NEW_STORE_PINNED})
+    nine.update({p[0]: lc.split_pinned(p[0]) for p in lc.SPLIT_PINNED})
+    assert sorted(nine) == sorted(NINE_DIGESTS) and len(NINE_DIGESTS) == 12
+    got = {name: hashlib.sha256(repr(t).encode()).hexdigest()[:16] for name, t in nine.items()}
+    assert got == NINE_DIGESTS, {n: d for n, d in got.items() if d != NINE_DIGESTS[n]}
+    assert lc.READS9 == lc.READS + ("grouped", "recommend", "numeric") and lc.MUTATIONS12 == lc.MUTATIONS + ("numbers",)
+    assert lc.READS12 == lc.READS9 + ("mmr", "per_group", "best")
+    assert not any(op[0] in lc.NEWER_READS + lc.NEWER_STORE_READS + ("near",) or op[:2] in (("set", "pg_cap"), ("set", "rb_route"))
+                   for t in list(nine.values()) + [trace_of(n) for n in OLD_DIGESTS] for op in t["ops"])
     assert lc.READS == ("search", "masked", "sparse", "range", "by_id", "distinct") and len(lc.STORE_READS) == 6 and len(lc.STORE_FILTERS) == 6
     assert not any(op[0] in lc.NEW_READS or op[0] == "numbers" for n in NAMES + LARGE_NAMES for op in trace_of(n)["ops"])
 
@@ -465,3 +489,283 @@ def test_split_mutant_is_caught(mutant):
     print(mutant, caught)
     assert set(caught) == set(SPLIT_NAMES), (mutant, caught)
     assert all(("layout after" in v) == (mutant == "refusal_forgotten") for v in caught.values()), caught
+
+
+# ------------------------------------------------------------------ MMR, per-group and recommend-by-best reads (lifecycle.TWELVE_PINNED)
+# The same proofs for the three composed reads: six index schedules, one short large one, two store schedules; mutants 24-34.
+TWELVE_NAMES = [p[0] for p in lc.TWELVE_PINNED]
+TWELVE_STORE_NAMES = [p[0] for p in lc.TWELVE_STORE_PINNED]
+
+
+def twelve_trace(name):
+    if name not in _TRACES:
+        _TRACES[name] = lc.store_pinned(name) if name in TWELVE_STORE_NAMES else lc.pinned(name)
+    return _TRACES[name]
+
+
+def caught12(make, names):
+    out = {}
+    for name in names:
+        t = twelve_trace(name)
+        try:
+            lc.run(t, make(t), expected=lc.slots(name, t))
+        except lc.Mismatch as e:
+            out[name] = str(e).split("\n")[0]
+    return out
+
+
+def reference_run12(name):
+    """one index schedule against the reference adapter; what the caps need, counted from the MODEL's answers kept in slots()"""
+    t = twelve_trace(name)
+    empty, seen, sizes = [], Counter(), []
+    stages, routes, caps_set = Counter(), set(), set()
+
+    def answered(step, op, model, args, got):
+        sizes.append((op[0], model.n_rows()))
+        if "error" in got:
+            return
+        if not any(len(l[0]) for l in got["lists"]):
+            empty.append((step, op))
+        want = lc.slots(name, t)[step][2]
+        if op[0] == "mmr":
+            lam = args[3]
+            seen["mmr_diverse"] += bool(np.min(lam) < 1)
+            seen["mmr_moved"] += bool(np.min(lam) < 1 and want["moved"])
+            seen["mmr_all_rows"] += len(args[0]) == 1 and args[2] == lc.MMR_MAX and want["mstats"][2] == lc.MMR_MAX
+            seen["mmr_pairs"] += want["mstats"][3]
+            assert not any(np.isnan(sc.view(np.float32)).any() for sc in want["scores"])
+        elif op[0] == "per_group":
+            seen["pg_reads"] += 1
+            seen["pg_with_members"] += any(len(ids) > 1 for grp in want["groups"] for _, ids, _ in grp)
+            seen["pg_deep"] += want["deep"] >= 1024
+            seen["pg_filled"] += want["pstats"][1]
+            seen["pg_giants_low_cap"] += want["pstats"][2] if model.pg_cap == lc.PG_LOW_CAP else 0
+            caps_set.add(model.pg_cap)
+        elif op[0] == "best":
+            seen["best_requests"] += len(want["lists"])
+            seen["best_empty"] += sum(1 for l in want["lists"] if not len(l[0]))
+            assert any(len(p) >= 2 and len(n) >= 1 for p, n in zip(args[0], args[1])), (step, op)
+            routes.add(model.rb_route)
+            if model.rb_route == 0:
+                stages.update(want["bstages"])
+            seen["best_list_searches"] += want["bstats"][6]
+    lc.run(t, lc.RefIndex(t["metric"]), expected=lc.slots(name, t), on_read=answered)
+    print(name, dict(seen), dict(stages), routes, caps_set)
+    assert not empty, empty                                          # every answered read returns a row
+    # the caps the issue words for EVERY schedule
+    assert seen["mmr_diverse"] >= 4 and 2 * seen["mmr_moved"] >= seen["mmr_diverse"] and seen["mmr_all_rows"] >= 1 and seen["mmr_pairs"] > 0, seen
+    assert 5 * seen["pg_with_members"] >= 4 * seen["pg_reads"] and seen["pg_deep"] >= 1 and seen["pg_filled"] > 0, seen
+    assert 4 * seen["best_empty"] <= seen["best_requests"] and seen["best_list_searches"] > 0, seen
+    return t, seen, stages, routes, caps_set, sizes
+
+
+@pytest.mark.parametrize("name", TWELVE_NAMES)
+def test_reference_adapter_passes_the_twelve_read_kinds(name):
+    """The reference adapter -- the naive greedy choice over the whole pair matrix, the host compositions of per group and of
+    recommend by best -- passes: lists, score bits, group codes, sizes and members, dn bits and all three counter vectors.  The
+    caps hold WITH THE MODEL ALONE (the answers kept in slots()), so that a passing GPU run cannot be vacuous: those of every
+    schedule in reference_run12, here those of every INDEX schedule."""
+    t, seen, stages, routes, caps_set, sizes = reference_run12(name)
+    assert seen["mmr_diverse"] >= 6, seen
+    assert seen["pg_giants_low_cap"] > 0 and caps_set == {0, lc.PG_LOW_CAP}, (seen, caps_set)
+    assert stages[0] > 0 and stages[1] > 0 and stages[2] > 0 and routes == {0, 1, 2}, (stages, routes)
+
+
+def test_the_large_twelve_schedule():
+    """75 000 rows of d = 64, at most 40 ops, all three kinds before and after a compaction and a shrinking compaction refilled
+    to the same row count (that the searches inside run on the bf16 screening tier is the engine's word: the GPU test), the
+    MMR read at m = 1024 with B = 1, a per-group member beyond rank 1024, and the caps of every schedule with the model alone"""
+    t, seen, stages, routes, caps_set, sizes = reference_run12("large-twelve")
+    assert t["d"] == 64 and len(t["ops"]) <= 40 and all(n >= lc.BF16_MIN_ROWS for kind, n in sizes if kind in lc.NEWER_READS), sizes
+    kinds = [op[0] for op in t["ops"]]
+    for kind in lc.NEWER_READS:
+        at = [i for i, op in enumerate(t["ops"]) if op[0] == kind and not (kind == "mmr" and op[4] == lc.MMR_MAX)]
+        assert len(at) == 4 and at[1] < kinds.index("compact") < at[2] < kinds.index("compact_shrink") < at[3], (kind, at)
+    assert [op[1:3] + op[4:5] for op in t["ops"] if op[0] == "mmr" and op[4] == lc.MMR_MAX] == [(1, 3, lc.MMR_MAX)]
+    assert lc.LARGE_ROWS <= max(n for _, n in sizes) <= lc.LARGE_ROWS + 4           # (the single add and the upsert append a row each)
+    c = lc.coverage(t)                                               # (of the old three: no error read at all; four read kinds, so no 8 % rule)
+    assert c["errors"] == 0 and set(c["reads"]) == set(lc.NEWER_READS) | {"search"}, c
+
+
+@pytest.mark.parametrize("name", TWELVE_NAMES[:2] + TWELVE_NAMES[3:4])          # (the fourth holds the misfit episode)
+def test_reference_adapter_refuses_the_three_when_sharded(name):
+    """the sharded reference refuses exactly the reads the model says: range, grouped and every read of the three new kinds
+    (no read of these schedules meets an empty index, which MMR and per group would answer first)"""
+    t = twelve_trace(name)
+    seen = Counter()
+    lc.run(t, lc.RefIndex(t["metric"], sharded=True), expected=lc.slots(name, t), on_read=lambda s, op, m, a, got: seen.update([(op[0], "error" in got)]))
+    for kind in ("range", "grouped") + lc.NEWER_READS:
+        assert seen[(kind, True)] == sum(1 for op in t["ops"] if op[0] == kind) > 0 and not seen[(kind, False)], (kind, seen)
+    assert all(seen[(kind, False)] > 0 for kind in ("search", "masked", "by_id", "distinct", "recommend", "numeric")), seen
+
+
+def test_the_order_of_the_checks_on_an_empty_or_sharded_index():
+    """MMR and per group answer an EMPTY index with empty lists before they refuse a sharded handle; recommend by best refuses
+    the sharded handle first (and names an absent example before the dimension mismatch and the zero-norm row on a plain one)"""
+    q = np.ones((2, 8), dtype=np.float32)
+    for cls in (lc.Model, lc.RefIndex):
+        sharded = cls(lc.COSINE, sharded=True)
+        assert [len(l[0]) for l in sharded.mmr(q, 3, 8, 0.5)["lists"]] == [0, 0] and sharded.per_group(q, 3, 2)["groups"] == [[], []]
+        assert lc.capture(lambda: sharded.best([[5]], [[]], 3)) == {"error": ("Refused", None)}
+        sharded.add_bulk(np.ones((4, 8), dtype=np.float32), np.arange(4))
+        for call in (lambda: sharded.mmr(q, 3, 8, 0.5), lambda: sharded.per_group(q, 3, 2), lambda: sharded.best([[1]], [[]], 3)):
+            assert lc.capture(call) == {"error": ("Refused", None)}
+        plain = cls(lc.COSINE)
+        assert lc.capture(lambda: plain.best([[5]], [[]], 3)) == {"error": ("VectorNotFound", 5)}
+        plain.add_bulk(np.ones((4, 8), dtype=np.float32), np.arange(4))
+        plain.add(9, np.zeros(8, dtype=np.float32))
+        plain.add(10, np.ones(5, dtype=np.float32))
+        assert lc.capture(lambda: plain.best([[1, 7]], [[6]], 3)) == {"error": ("VectorNotFound", 7)}
+        assert lc.capture(lambda: plain.best([[1]], [[]], 3)) == {"error": ("DimensionMismatch", None)}
+        plain.remove([10])
+        for call in (lambda: plain.mmr(q, 3, 8, 0.5), lambda: plain.per_group(q, 3, 2), lambda: plain.best([[1]], [[]], 3)):
+            assert lc.capture(call) == {"error": ("InvalidVector", None)}
+
+
+MUTANT_KIND = {24: "best", 25: "best", 26: "best", 27: "best", 28: "best", 29: "mmr", 30: "mmr", 31: "per_group", 32: "per_group", 33: "per_group"}
+
+
+@pytest.mark.parametrize("number", sorted(lc.TWELVE_INDEX_MUTANTS))
+def test_twelve_index_mutant_is_caught(number):
+    """every mutant falls on EVERY one of the six schedules, on a read of the kind whose state it spoils (34, the switches that
+    revert at a re-allocation, on the counters of a per-group or a best read)"""
+    mutant = lc.TWELVE_INDEX_MUTANTS[number]
+    caught = caught12(lambda t: mutant(t["metric"]), TWELVE_NAMES)
+    print(number, mutant.__name__, len(caught), "of", len(TWELVE_NAMES), caught)
+    assert sorted(caught) == sorted(TWELVE_NAMES), sorted(set(TWELVE_NAMES) - set(caught))
+    if number in MUTANT_KIND:
+        assert all(f"('{MUTANT_KIND[number]}'," in v for v in caught.values()), caught
+    else:
+        assert all(("pstats" in v or "bstats" in v) for v in caught.values()), caught
+    assert len(lc.TWELVE_INDEX_MUTANTS) >= 9 and min(lc.TWELVE_INDEX_MUTANTS) == 24
+    assert all(sum(1 for k in MUTANT_KIND.values() if k == kind) >= 2 for kind in lc.NEWER_READS)
+
+
+@pytest.mark.parametrize("number", [25, 30, 31])
+def test_a_twelve_failure_shrinks(number):
+    """a failing trace of a new mutant (one per kind) shrinks to at most eight ops that still fail it and pass the reference"""
+    t = twelve_trace(TWELVE_NAMES[0])
+    make = lambda: lc.TWELVE_INDEX_MUTANTS[number](t["metric"])
+    small = lc.shrink(t, make)
+    assert small is not None and len(small["ops"]) <= 8, small and small["ops"]
+    assert small["ops"][-1][0] == MUTANT_KIND[number]
+    with pytest.raises(lc.Mismatch):
+        lc.run(small, make())
+    lc.run(small, lc.RefIndex(t["metric"]))
+
+
+def test_coverage_sizes_and_caps_of_the_twelve_read_kinds():
+    covs = {name: lc.coverage(twelve_trace(name)) for name in TWELVE_NAMES}
+    pairs = set().union(*(c["pairs"] for c in covs.values()))
+    missing = [(m, r) for m in lc.MUTATIONS12 for r in lc.NEWER_READS if (m, r) not in pairs]
+    assert not missing, missing
+    for name, c in covs.items():
+        t = twelve_trace(name)
+        n, ops = c["counts"], t["ops"]
+        assert n["up"] >= 1 and n["down"] >= 1, (name, n)
+        assert n["doublings"] >= 3 and n["shrinks"] >= 1 and n["dim_resets"] >= 1, (name, n)
+        assert n["auto_compactions"] >= 1 and n["compact_with_staged"] >= 1, (name, n)
+        assert 150 <= len(ops) <= 300 and t["twelve"] is True, (name, len(ops))
+        assert {op[0] for op in ops if not lc.is_read(op)} >= set(lc.MUTATIONS12) - {"remove_absent"} | {"near"}, name
+        reads = Counter(c["reads"])
+        total = sum(reads.values())
+        assert c["errors"] <= 0.15 * total, (name, c["errors"], total)
+        assert set(reads) == set(lc.READS12) and min(reads.values()) >= 0.08 * total, (name, reads)   # (the older cap, as it stands)
+        m = lc.Model(t["metric"])
+        peak, low, dims = 0, 10 ** 9, set()
+        since = {}                                                   # switch -> counted mutations since it was set
+        used = set()
+        for op in ops:
+            if lc.is_read(op):
+                peak, low = max(peak, m.n_rows()), min(low, m.n_live())
+                dims.add(m.d)
+                for sw, kind in (("pg_cap", "per_group"), ("rb_route", "best")):
+                    if op[0] == kind and sw in since and since[sw][1] >= 2:
+                        used.add((sw, since[sw][0]))
+                m.uploaded()
+            else:
+                lc.apply_mutation(t, op, m)
+                if op[0] == "set" and op[1] in ("pg_cap", "rb_route"):
+                    since[op[1]] = [op[2], 0]
+                elif op[0] in lc.MUTATIONS12 or op[0] == "remove_many":
+                    for v in since.values():
+                        v[1] += 1
+        assert lc.SMALL_N < peak <= 20_000 and low <= 1300, (name, peak, low)
+        assert dims == {40, 64}, (name, dims)
+        # both values of pg_cap and all three of rb_route, each read two mutations or more after it was set
+        assert used == {("pg_cap", 0), ("pg_cap", lc.PG_LOW_CAP), ("rb_route", 0), ("rb_route", 1), ("rb_route", 2)}, (name, used)
+        assert any(op[0] == "best" and op[4] for op in ops), name                               # an absent example: VectorNotFound
+        codes = [i for i, op in enumerate(ops) if op[0] == "codes"]
+        grouped_reads = [i for i, op in enumerate(ops) if op[0] in ("distinct", "per_group")]
+        assert any(a < c_ < b for a in grouped_reads for b in grouped_reads for c_ in codes if c_ > 100), name   # set_codes late, between two such reads
+    cosine = [p[0] for p in lc.TWELVE_PINNED if p[3] == lc.COSINE]
+    assert cosine and all(any(op[0] == "zero" for op in twelve_trace(n)["ops"]) for n in cosine)
+    assert any(op[0] == "misfit" for n in TWELVE_NAMES for op in twelve_trace(n)["ops"])
+    assert {p[2] for p in lc.TWELVE_PINNED} == {"twelve", "twelve-auto"} and {lc.PROFILES[p]["d"] for p in ("twelve", "twelve-auto")} == {40, 64}
+
+
+@pytest.mark.parametrize("name", TWELVE_STORE_NAMES)
+def test_store_reference_passes_with_the_three_reads(name):
+    """StoreSim over RefIndex passes the two store schedules of s_mmr, s_groups and s_recommend_best (with upserts, the filter
+    pool, the device filter from the start and switched on mid-life, auto-compaction in one): every kind keeps its share,
+    every answered read returns a row; a group header carries the field value and the size"""
+    import ast
+    vdb = load_package()
+    t = twelve_trace(name)
+    assert ast.literal_eval(repr(t)) == t and t["twelve"] is True and t["numeric"] is True
+    empty, kinds, groups = [], Counter(), Counter()
+
+    def answered(step, op, model, args, got):
+        kinds[op[0]] += 1
+        if "error" in got:
+            return
+        if not any(len(l[0]) for l in got["lists"]):
+            empty.append((step, op))
+        want = lc.slots(name, t)[step][2]                            # the MODEL's answer: the caps are conditions on it alone
+        if op[0] == "s_groups":
+            sizes = [b for s, b in want if str(s).startswith("#")]
+            groups["reads"] += 1
+            groups["reads_with_members"] += any(x > 1 for x in sizes)
+            groups["none"] += sum(1 for s, _ in want if s == "#None")
+        elif op[0] == "s_mmr":
+            groups["mmr_diverse"] += args[2] < 1
+            groups["mmr_moved"] += bool(args[2] < 1 and want["moved"])
+        elif op[0] == "s_recommend_best":
+            groups["best_requests"] += len(want)
+            groups["best_empty"] += sum(1 for l in want if not l)
+            assert any(len(p) >= 2 and len(n) >= 1 for p, n in args[0]), (step, op)
+    lc.run(t, lc.StoreSim(vdb, lc.RefIndex(t["metric"])), expected=lc.slots(name, t), on_read=answered)
+    print(name, dict(kinds), dict(groups))
+    assert not empty, empty
+    assert set(kinds) == set(lc.STORE_READS + lc.NEW_STORE_READS + lc.NEWER_STORE_READS) and min(kinds.values()) >= 0.08 * sum(kinds.values()), kinds
+    assert 5 * groups["reads_with_members"] >= 4 * groups["reads"] and groups["none"] > 0, groups
+    assert groups["mmr_diverse"] >= 6 and 2 * groups["mmr_moved"] >= groups["mmr_diverse"], groups
+    assert 4 * groups["best_empty"] <= groups["best_requests"], groups
+    switches = [op[2] for op in t["ops"] if op[:2] == ("set", "device_filter")]
+    assert switches == [1] and (t["ops"][0][:2] == ("set", "device_filter")) == (name == "store-twelve-early")
+    assert (t["auto"] > 0) == (name == "store-twelve-late") and sum(1 for op in t["ops"] if op[0] == "s_insert") >= 40
+
+
+def test_store_mutant_is_caught_by_the_three_reads():
+    """11 (the presence bit of a superseded internal id stays set) falls on both new store schedules"""
+    vdb = load_package()
+    caught = caught12(lambda t: lc.StoreSim(vdb, lc.RefIndex(t["metric"]), stale_presence=True), TWELVE_STORE_NAMES)
+    print(caught)
+    assert sorted(caught) == sorted(TWELVE_STORE_NAMES), caught
+
+
+def test_twelve_traces_are_plain_data_and_replay():
+    import ast
+    name = TWELVE_NAMES[3]
+    t = twelve_trace(name)
+    again = ast.literal_eval(repr(t))
+    assert again == t and lc.pinned(name) == t                      # printed, parsed back, generated twice: the same trace
+    kept = lc.slots(name, t)
+    fresh = [None] * len(t["ops"])
+    lc.run(again, lc.RefIndex(t["metric"]), expected=fresh)          # the WHOLE printed trace, without the answers the generator kept
+    compared = 0
+    for step, (a, b) in enumerate(zip(kept, fresh)):                 # what the generator kept is what a replay materialises and computes:
+        if a is not None and b is not None:                          # auto-compaction inside a redrawn read included (on from about op 60)
+            assert a[0] == b[0] and repr(a[1]) == repr(b[1]) and lc.diff(a[2], b[2]) is None and lc.diff(b[2], a[2]) is None, step
+            compared += 1
+    assert compared >= 30 and t["profile"] == "twelve-auto", compared

@@ -5,10 +5,13 @@ pinned ones of tests/test_gpu_lifecycle.py, every read compared bit for bit with
 trace, shrinks it (ops are dropped greedily while the failure persists) and prints the shrunk trace as a literal that
 lifecycle.run() replays; the exit status is then non-zero.
 
-    python tools/fuzz_lifecycle.py [--cases N] [--seed S] [--store] [--sharded] [--large]
+    python tools/fuzz_lifecycle.py [--cases N] [--seed S] [--store] [--sharded] [--large] [--twelve]
 
 --store drives VectorStore with store-level schedules, --sharded one sharded handle over three shards on device 0, --large draws the
-short 75 000-row schedules that reach the bf16 screening tier and the screened range route.
+short 75 000-row schedules that reach the bf16 screening tier and the screened range route.  --twelve draws the schedules of the
+MMR, per-group and recommend-by-best reads instead: the profiles "twelve" and "twelve-auto" (all twelve read kinds, the two debug
+switches), with --store the store schedules that hold search_mmr, search_groups and recommend_best_batch (and the numeric fields),
+with --large the 75 000-row twelve-kind schedule.  Without --twelve a seed names the case it always named.
 """
 import argparse
 import os
@@ -29,18 +32,23 @@ def main():
     ap.add_argument("--store", action="store_true")
     ap.add_argument("--sharded", action="store_true")
     ap.add_argument("--large", action="store_true")
+    ap.add_argument("--twelve", action="store_true")
     args = ap.parse_args()
     vdb = load_package()
     vdb.build()
-    profiles = sorted(lc.PROFILES)
+    profiles = ["twelve", "twelve-auto"] if args.twelve else sorted(p for p in lc.PROFILES if not p.startswith("twelve"))
     t0, reads = time.time(), 0
     for case in range(args.cases):
         seed, metric = args.seed + case, case % 3
         if args.store:
-            trace = lc.store_schedule(seed, metric, table_at=("mid", "start")[case % 2], auto=(0.0, 0.4)[(case // 2) % 2])
+            trace = lc.store_schedule(seed, metric, table_at=("mid", "start")[case % 2], auto=(0.0, 0.4)[(case // 2) % 2],
+                                      numeric=args.twelve, twelve=args.twelve)
             make = lambda: lc.GpuStoreAdapter(vdb, metric, auto_compact=trace["auto"])   # noqa: E731
         else:
-            trace = lc.large_schedule(seed, metric) if args.large else lc.schedule(seed, profiles[(case // 3) % len(profiles)], metric)
+            if args.large:
+                trace = lc.large_twelve_schedule(seed, metric).trace if args.twelve else lc.large_schedule(seed, metric)
+            else:
+                trace = lc.schedule(seed, profiles[(case // 3) % len(profiles)], metric)
             make = lambda: lc.GpuIndexAdapter(vdb, metric, devices=[0, 0, 0] if args.sharded else None)   # noqa: E731
         made = []
 
