@@ -628,6 +628,64 @@ size_t vdb_flat_recommend_best_depth(size_t k, size_t m, size_t len, int stage);
 int vdb_flat_debug_set_recommend_best_route(vdb_flat_index *h, int mode);
 
 /*
+ * DISCOVERY SEARCH: a target ranked inside context pairs (no reference counterpart; a caller would download the distance columns
+ * of 2P + 1 stored vectors over the whole store and fold them on the host).  Request b has a target t, pairs (p_1, n_1) ..
+ * (p_P, n_P), 0 <= P <= VDB_DISCOVER_MAX_PAIRS, all stored ids, and a count k_b.  pair_ids holds p_1 n_1 p_2 n_2 ... of every
+ * request side by side; request b owns pairs [offsets[b], offsets[b + 1]).  d(e, x) is the reference distance with the stored
+ * vector of e as the query and row x as the row: exactly what vdb_flat_search_batch_by_id([e]) reports for x.
+ *  - Eligible rows: the live rows the optional mask admits, minus the SET {t, p_i, n_i} (64-bit equality).  An example the mask
+ *    hides is still an example; ids may repeat and may stand on both sides of a pair; no id value is a flag.
+ *  - rank(x): the number of pairs i with d(p_i, x) < d(n_i, x) under the IEEE <.  A tie is "not satisfied"; a NaN on either side
+ *    is "not satisfied" (so a pair whose two ids are equal never is).  The rule is decided row by row and does not depend on
+ *    the route the engine took.
+ *  - Result: the eligible rows by (rank descending, d(t, x) ascending in the order the plain search gives equal distances --
+ *    -0.0 in front of +0.0 --, unsigned id ascending), cut to min(k_b, len): out_ids, out_dists (d(t, x), bit for bit), out_ranks
+ *    (may be NULL), out_counts.  Fewer than k_b eligible rows is a short list, not an error.  min(max k_b, len) may not exceed
+ *    VDB_DISCOVER_MAX_K.
+ * Consequences: P = 0 is vdb_flat_search_batch_by_id bit for bit; with t = p, one pair (p, n) and k = len the rank-1 prefix of
+ * the answer is vdb_flat_recommend_best_batch([p], [n]) with k = len, ids and dp bits.
+ * Errors, in this order: (1) the argument checks, before any device work: NULL arguments, offsets that do not start at 0 or
+ * decrease, more than VDB_DISCOVER_MAX_PAIRS pairs in a request, the stride, the k limit, and a sharded handle -- refused with
+ * VDB_ERR_INVALID_ARGUMENT before the flush and before any id is resolved; (2) staged writes are flushed; (3) VDB_ERR_NOT_FOUND
+ * and VDB_ERR_DIMENSION_MISMATCH as recommend, over the ids in the order t_b, p_1, n_1, ... request by request; (4) under Cosine a
+ * zero-norm example (the target included), like any live zero-norm row, is VDB_ERR_INVALID_VECTOR; (5) a NaN d(t, x) at any live
+ * row the mask admits -- the examples included: they are struck afterwards -- is VDB_ERR_NAN, on every route.  A NaN d(p_i, x) or
+ * d(n_i, x) is no error: the pair is not satisfied.
+ * Not built: a raw-vector target, context-only search without a target, sharded handles (refused as in (1)), device-pointer
+ * and ticket forms, HNSW.
+ * How (csrc/kernels_discover.hip): the targets of all requests are gathered into one query block on the device
+ * and ONE certified search ranks the store for each at depth D; the examples are struck.  What is left is the front of the
+ * ranking of the eligible rows by (d(t, x), id): a row outside it sorts behind its last entry.  A kernel finds every candidate's
+ * device row, computes the exact d(p_i, x), d(n_i, x) from the stored rows and counts.  A request is answered when k_b candidates
+ * have rank P (the first k_b of them are the answer: nothing outside has a higher rank or sorts in front) or when the list is
+ * complete -- the search returned fewer rows than D, or D is the whole index --: then the answer is the list's stable sort by rank
+ * descending.  The others run again at depth min(len, 1024), and what is left gets ONE exact pass over the rows per request
+ * (the rows are read as f32: a SPLIT store converts back first), keyed (P - rank, d(t, x), id rank) in 5 + 32 + 27 bits for the
+ * full-scan select; a store of 2^27 rows or more is refused there with VDB_ERR_INVALID_ARGUMENT rather than answered wrongly.
+ * vdb_flat_discover_depth(k, P, len, stage) is the search depth D of stage 0 -- min(len, min(1024, max(2 k 2^P' + 2 P' + 1, 64))),
+ * k = min(max k_b, len), P' = min(the most pairs of any request, 10): a pair of unrelated examples is satisfied by about half of
+ * the rows, so the depth has room for twice the k rows of rank P at that rate and for the examples -- and of stage 1; 0 for any
+ * other stage.  vdb_flat_discover_stats describes the last call: [0] requests, [1] example rows (targets included), [2]
+ * requests answered at stage 0, [3] at stage 1, [4] by the exact scan, [5] the stage-0 depth, [6] list searches run (one per
+ * request and stage it went through), [7] 0.  vdb_flat_debug_set_discover_route (tests): 0 automatic (lists first unless the
+ * stage-0 depth is the whole index), 1 lists first always, 2 the exact scan only; the answers are the same bits on every route.
+ */
+#define VDB_DISCOVER_MAX_PAIRS 16
+#define VDB_DISCOVER_MAX_K 1024
+int vdb_flat_discover_batch(vdb_flat_index *h, const uint64_t *target_ids /* [nq] */,
+                            const uint64_t *pair_ids /* p_1 n_1 p_2 n_2 ..., 2 * offsets[nq] ids */,
+                            const size_t *offsets /* [nq + 1], in pairs */, size_t nq, const size_t *ks, size_t k,
+                            const uint64_t *id_mask, size_t mask_bits, size_t kstride,
+                            uint64_t *out_ids, float *out_dists, uint32_t *out_ranks, size_t *out_counts);
+int vdb_flat_discover_batch_filtered(vdb_flat_index *h, const uint64_t *target_ids /* [nq] */, const uint64_t *pair_ids,
+                                     const size_t *offsets /* [nq + 1], in pairs */, size_t nq, const size_t *ks, size_t k,
+                                     const vdb_meta_mask *mask, size_t kstride,
+                                     uint64_t *out_ids, float *out_dists, uint32_t *out_ranks, size_t *out_counts);
+int vdb_flat_discover_stats(const vdb_flat_index *h, uint64_t out[8]);
+size_t vdb_flat_discover_depth(size_t k, size_t P, size_t len, int stage);
+int vdb_flat_debug_set_discover_route(vdb_flat_index *h, int mode);
+
+/*
  * DIVERSE TOP-K (MAXIMAL MARGINAL RELEVANCE): k results that are not all the same thing (no reference counterpart; a caller would
  * search at depth m, get_vector every candidate and run an O(k m dim) loop on the host).  A request is a query q, a count k, a
  * candidate depth m and a trade-off lambda, 1 <= k <= m <= VDB_MMR_MAX_CANDIDATES, lambda an f32 in [0, 1].

@@ -21,6 +21,7 @@ SYMBOLS = [
     "vdb_flat_recommend_batch", "vdb_flat_recommend_batch_filtered", "vdb_flat_recommend_stats",
     "vdb_flat_recommend_best_batch", "vdb_flat_recommend_best_batch_filtered", "vdb_flat_recommend_best_stats", "vdb_flat_recommend_best_depth",
     "vdb_flat_debug_set_recommend_best_route",
+    "vdb_flat_discover_batch", "vdb_flat_discover_batch_filtered", "vdb_flat_discover_stats", "vdb_flat_discover_depth", "vdb_flat_debug_set_discover_route",
     "vdb_flat_search_batch_mmr", "vdb_flat_search_batch_mmr_filtered", "vdb_flat_mmr_stats",
     "vdb_flat_search_batch_distinct", "vdb_flat_search_batch_distinct_filtered", "vdb_flat_distinct_stats", "vdb_flat_distinct_depth",
     "vdb_flat_search_batch_grouped", "vdb_flat_search_batch_grouped_filtered", "vdb_flat_grouped_stats", "vdb_flat_debug_group_plan",
@@ -184,6 +185,12 @@ def lib():
     L.vdb_flat_recommend_best_depth.argtypes = [sz, sz, sz, c.c_int]
     L.vdb_flat_recommend_best_depth.restype = sz
     L.vdb_flat_debug_set_recommend_best_route.argtypes = [vp, c.c_int]
+    L.vdb_flat_discover_batch.argtypes = [vp, u64p, u64p, szp, sz, szp, sz, u64p, sz, sz, u64p, fp, c.POINTER(c.c_uint32), szp]
+    L.vdb_flat_discover_batch_filtered.argtypes = [vp, u64p, u64p, szp, sz, szp, sz, vp, sz, u64p, fp, c.POINTER(c.c_uint32), szp]
+    L.vdb_flat_discover_stats.argtypes = [vp, u64p]
+    L.vdb_flat_discover_depth.argtypes = [sz, sz, sz, c.c_int]
+    L.vdb_flat_discover_depth.restype = sz
+    L.vdb_flat_debug_set_discover_route.argtypes = [vp, c.c_int]
     L.vdb_flat_search_batch_mmr.argtypes = [vp, fp, sz, sz, szp, sz, sz, fp, c.c_float, u64p, sz, sz, u64p, fp, fp, szp]
     L.vdb_flat_search_batch_mmr_filtered.argtypes = [vp, fp, sz, sz, szp, sz, sz, fp, c.c_float, vp, sz, u64p, fp, fp, szp]
     L.vdb_flat_mmr_stats.argtypes = [vp, u64p]

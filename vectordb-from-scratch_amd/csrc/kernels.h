@@ -765,4 +765,51 @@ struct RbScanParams {
 };
 void launch_rb_scan(const RbScanParams& p, uint32_t n_req, hipStream_t s);
 
+// ---------------------------------------------------------------- discovery search (kernels_discover.hip)
+constexpr uint32_t DISCOVER_MAX_PAIRS = 16;                                // (positive, negative) pairs of one request (VDB_DISCOVER_MAX_PAIRS)
+constexpr uint32_t DISCOVER_MAX_LIST = 1024;                               // candidates of one list stage, and rows of one answer (VDB_DISCOVER_MAX_K)
+// the scan's key: (P - rank) above the ordered d(t, x) above the id rank -- 5 + 32 + 27 bits
+constexpr uint32_t DISCOVER_KEY_ID_BITS = 27, DISCOVER_KEY_LEVEL_SHIFT = 59;
+// The requests of one call on the device: request b owns entries [offs[b], offs[b + 1]) of rows / ids -- the target, then
+// p_1 n_1 p_2 n_2 ..., 2P + 1 entries with P <= DISCOVER_MAX_PAIRS; ks[b] rows are wanted.  rows: device rows below the store's
+// n_rows (the host resolved them).
+struct DiscoverRequests {
+    const uint32_t* offs; const uint32_t* ks; const uint32_t* rows; const uint64_t* ids;
+};
+// Workgroup j takes the candidates of request sel[j] (j itself without sel): cand_ids / cand_dists [j * cand_stride ..], cand_cnt[j]
+// of them (at most DISCOVER_MAX_LIST), ascending by (d(t, x), id), the examples struck.  raw_cnt[j] is what the search at `depth`
+// returned before the strike: the list is complete when that is below depth, or when exhaustive says the depth covered every row.
+// answered[j] = 1 when ks[b] candidates have rank P or the list is complete; only then the first min(ks[b], kout) candidates by
+// (rank descending, list order) go to out_ids / out_dists / out_ranks [b * kout ..] and their number to out_counts[b].
+// row_ids / rank2row (null: rows are in id order) / live name the live row of an id; status bit 1: a candidate without one.
+struct DiscoverRankParams {
+    const float* rows; uint32_t ld, dim, n_rows; int metric; const float* nd;
+    const uint64_t* row_ids; const uint32_t* rank2row; const uint32_t* live;
+    DiscoverRequests R; const uint32_t* sel;
+    const uint64_t* cand_ids; const float* cand_dists; const uint32_t* cand_cnt; const uint32_t* raw_cnt; uint32_t cand_stride, depth, exhaustive;
+    uint64_t* out_ids; float* out_dists; uint32_t* out_ranks; uint32_t* out_counts; uint32_t kout;
+    uint32_t* answered; uint32_t* status;
+};
+void launch_discover_rank(const DiscoverRankParams& p, uint32_t n_req, hipStream_t s);
+// The exact scan: keys[y * key_stride + row] = ((P - rank) << 59 | ordered d(t, row) << 27 | id rank) of every eligible row of
+// request sel[y] that is none of its examples, EMPTY_KEY for every other row below n_rows (n_rows < 2^27); ST_NAN into status for
+// a NaN d(t, row) at an eligible row, the examples included.
+struct DiscoverScanParams {
+    const float* rows; uint32_t ld, dim, n_rows; int metric; const float* nd;
+    const uint32_t* rowmask; const uint32_t* idrank;                       // null: every row / ranks are rows
+    DiscoverRequests R; const uint32_t* sel;
+    uint64_t* keys; size_t key_stride; uint32_t* status;
+};
+void launch_discover_scan(const DiscoverScanParams& p, uint32_t n_req, hipStream_t s);
+// The first min(key_cnt[y], ks[b], kout) of the ascending keys [y * key_stride ..] of request b = sel[y], taken apart into
+// out_ids / out_dists / out_ranks [b * kout ..]; their number to out_counts[b].  status bit 1: a key that names no row.
+struct DiscoverEmitParams {
+    const uint64_t* keys; const uint32_t* key_cnt; uint32_t key_stride;
+    DiscoverRequests R; const uint32_t* sel;
+    const uint32_t* rank2row; const uint64_t* row_ids; uint32_t n_rows;
+    uint64_t* out_ids; float* out_dists; uint32_t* out_ranks; uint32_t* out_counts; uint32_t kout;
+    uint32_t* status;
+};
+void launch_discover_emit(const DiscoverEmitParams& p, uint32_t n_req, hipStream_t s);
+
 }  // namespace vdb

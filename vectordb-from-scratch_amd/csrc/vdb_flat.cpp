@@ -937,6 +937,109 @@ int vdb_flat_debug_set_recommend_best_route(vdb_flat_index* ix, int mode) {
     });
 }
 
+// ---- discovery search (no reference counterpart; vdb_search.cpp discover_drive)
+static_assert(vdb::DISCOVER_MAX_LIST == VDB_DISCOVER_MAX_K && vdb::DISCOVER_MAX_PAIRS == VDB_DISCOVER_MAX_PAIRS, "the kernels' LDS arrays and the public limits");
+constexpr size_t DISCOVER_DEPTH_MAX_SHIFT = 10;                    // 2 k 2^10 is beyond the cap for every k >= 1
+size_t vdb_flat_discover_depth(size_t k, size_t P, size_t len, int stage) {
+    const size_t cap = vdb::DISCOVER_MAX_LIST;
+    // (a pair of unrelated examples is satisfied by about half of the rows, so about 2^-P of a list has rank P: room for twice
+    // the k_b rows the answered rule waits for, and for the examples the strike removes)
+    const size_t Pc = std::min(P, (size_t)DISCOVER_DEPTH_MAX_SHIFT);
+    if (stage == 0) return std::min(len, std::min(cap, std::max(((2 * std::min(k, cap)) << Pc) + 2 * Pc + 1, (size_t)64)));
+    if (stage == 1) return std::min(len, cap);
+    return 0;
+}
+
+// The argument checks of vdb_flat_discover_batch that need no handle, before any lock or device work; fills r->pairs and r->pmax.
+static int discover_check(DiscoverReq* r, size_t nq) {
+    r->pairs = r->pmax = 0;
+    if (nq == 0) return VDB_OK;
+    if (!r->targets || !r->offsets) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (r->offsets[0] != 0) return fail(VDB_ERR_INVALID_ARGUMENT, "offsets[0] is %zu, not 0", r->offsets[0]);
+    for (size_t b = 0; b < nq; ++b) {
+        if (r->offsets[b + 1] < r->offsets[b]) return fail(VDB_ERR_INVALID_ARGUMENT, "offsets decrease at request %zu", b);
+        const size_t P = r->offsets[b + 1] - r->offsets[b];
+        if (P > VDB_DISCOVER_MAX_PAIRS) return fail(VDB_ERR_INVALID_ARGUMENT, "request %zu has %zu pairs, more than %d", b, P, VDB_DISCOVER_MAX_PAIRS);
+        r->pmax = std::max(r->pmax, P);
+    }
+    r->pairs = r->offsets[nq];
+    if (nq > ((size_t)1 << 20)) return fail(VDB_ERR_INVALID_ARGUMENT, "%zu requests in one call, more than 2^20", nq);
+    if (r->pairs && !r->pair_ids) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    return VDB_OK;
+}
+
+// The front end of both forms: the argument checks before any lock or device work, then the lock, the k limit, the flush, the
+// examples' device rows (VDB_ERR_NOT_FOUND, VDB_ERR_DIMENSION_MISMATCH as recommend), then the driver.
+static int discover_host(vdb_flat_index* ix, HostSearch r, DiscoverReq req, uint32_t* out_ranks) {
+    return guarded([&]() -> int {
+    const size_t nq = r.nq;
+    int rc;
+    if ((rc = discover_check(&req, nq))) return rc;
+    if (!ix || (nq && !r.counts)) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (ix->multi) return refuse_multi("vdb_flat_discover_batch");
+    if (r.cm) {
+        if ((rc = compiled_mask_check(r.cm, ix->device))) return rc;
+        r.mask_bits = r.cm->bits;
+    }
+    size_t kmax;
+    if ((rc = batch_shape(r, &kmax))) return rc;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (in_flight(ix)) return refuse_in_flight();
+    // (staged adds and removes are counted already: the flush below does not change len)
+    const size_t kcut = std::min(kmax, (size_t)ix->n_live + ix->misfits.size());
+    if (kcut > VDB_DISCOVER_MAX_K)
+        return fail(VDB_ERR_INVALID_ARGUMENT, "a discovery search returns at most %d rows per request, not %zu", VDB_DISCOVER_MAX_K, kcut);
+    if ((rc = set_device(ix))) return rc;
+    memset(ix->discover_stats, 0, sizeof(ix->discover_stats));
+    ix->discover_stats[0] = nq; ix->discover_stats[1] = nq + 2 * req.pairs;
+    if (nq == 0) return VDB_OK;
+    // staged adds and removes first: an id resolves to what the searches below see
+    if ((rc = flush(ix))) return rc;
+    // the examples of every request side by side: the target, then p_1 n_1 p_2 n_2 ...
+    std::vector<uint64_t> ex_ids;
+    ex_ids.reserve(nq + 2 * req.pairs);
+    for (size_t b = 0; b < nq; ++b) {
+        ex_ids.push_back(req.targets[b]);
+        ex_ids.insert(ex_ids.end(), req.pair_ids + 2 * req.offsets[b], req.pair_ids + 2 * req.offsets[b + 1]);
+    }
+    std::vector<uint32_t> ex_rows;
+    if ((rc = resolve_query_ids(ix, ex_ids.data(), ex_ids.size(), &ex_rows))) return rc;
+    return discover_drive(ix, r, req, ex_ids.data(), ex_rows.data(), kcut, out_ranks);
+    });
+}
+
+int vdb_flat_discover_batch(vdb_flat_index* ix, const uint64_t* target_ids, const uint64_t* pair_ids, const size_t* offsets, size_t nq,
+                            const size_t* ks, size_t k, const uint64_t* id_mask, size_t mask_bits, size_t kstride, uint64_t* out_ids,
+                            float* out_dists, uint32_t* out_ranks, size_t* out_counts) {
+    return discover_host(ix, under(host_search(nullptr, nq, 0, ks, k, kstride, out_ids, out_dists, out_counts), id_mask, mask_bits),
+                         DiscoverReq{target_ids, pair_ids, offsets}, out_ranks);
+}
+
+int vdb_flat_discover_batch_filtered(vdb_flat_index* ix, const uint64_t* target_ids, const uint64_t* pair_ids, const size_t* offsets,
+                                     size_t nq, const size_t* ks, size_t k, const vdb_meta_mask* mask, size_t kstride, uint64_t* out_ids,
+                                     float* out_dists, uint32_t* out_ranks, size_t* out_counts) {
+    if (!mask) return fail(VDB_ERR_INVALID_ARGUMENT, "null mask");
+    return discover_host(ix, under(host_search(nullptr, nq, 0, ks, k, kstride, out_ids, out_dists, out_counts), mask),
+                         DiscoverReq{target_ids, pair_ids, offsets}, out_ranks);
+}
+
+int vdb_flat_discover_stats(const vdb_flat_index* ix, uint64_t out[8]) {
+    if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (ix->multi) return refuse_multi("vdb_flat_discover_stats");
+    memcpy(out, ix->discover_stats, sizeof(ix->discover_stats));
+    return VDB_OK;
+}
+
+int vdb_flat_debug_set_discover_route(vdb_flat_index* ix, int mode) {
+    return guarded([&]() -> int {
+    if (!ix || mode < 0 || mode > 2) return fail(VDB_ERR_INVALID_ARGUMENT, "bad argument");
+    if (ix->multi) return refuse_multi("vdb_flat_debug_set_discover_route");
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->discover_route = mode;
+    return VDB_OK;
+    });
+}
+
 // ---- diverse top-k (no reference counterpart; search_batch_host with r.mmr)
 // The checks of include/vdb_flat.h "DIVERSE TOP-K" item 8, in its order, before any lock or device work.  *done: the call is
 // answered (an empty index, or no query asks for a row).

@@ -112,6 +112,22 @@ struct RecBestWs {
     vdbi::DevBuf<float> q, ld, cd, outd, outn;
 };
 
+// What one discovery search owns on the device beside the search workspace (vdb_search.cpp discover_drive): the
+// requests, the stage's selection (requests | target rows | offsets of the stage's example sets) and those sets' ids, the
+// gathered targets, the ranked lists with their counts before and after the strike, the scan's key counts, the flags, the
+// status words, and the answers.
+struct DiscoverWs {
+    vdbi::DevBuf<uint32_t> meta, sel, lc, raw, answered, outc, outr, stat, struck;
+    vdbi::DevBuf<uint64_t> ids, sids, li, outi, mask_in;
+    vdbi::DevBuf<float> q, ld, outd;
+};
+// A discovery request as the caller passed it, checked by discover_check: request b has the target targets[b] and the pairs
+// [offsets[b], offsets[b + 1]) of pair_ids (two ids each).
+struct DiscoverReq {
+    const uint64_t* targets; const uint64_t* pair_ids; const size_t* offsets;
+    size_t pairs = 0, pmax = 0;                                   // offsets[nq]; the most pairs of a request (discover_check)
+};
+
 // A host-pointer batch search as its entry point received it (the extern "C" shims fill it): the batch and its outputs (Batch),
 // the queries -- vectors [nq][dim], or the stored vectors of `by` (then queries is null and dim unused), or folds of stored
 // vectors (rec, checked by recommend_check; by is then rec->ids) -- and the id mask in the form it came in.  mmr: the lists of the
@@ -292,6 +308,9 @@ struct vdb_flat_index {
     uint64_t recommend_best_stats[8] = {0};                 // vdb_flat_recommend_best_stats: counters of the last recommend-by-best-score call
     RecBestWs rbw;                                          // its device buffers
     int rb_route = 0;                                       // vdb_flat_debug_set_recommend_best_route (tests): 0 auto, 1 lists first, 2 scan only
+    uint64_t discover_stats[8] = {0};                       // vdb_flat_discover_stats: counters of the last discovery search
+    DiscoverWs dcw;                                         // its device buffers
+    int discover_route = 0;                                 // vdb_flat_debug_set_discover_route (tests): 0 auto, 1 lists first, 2 scan only
     uint64_t distinct_stats[8] = {0};                       // vdb_flat_distinct_stats: counters of the last search by group (also on a sharded parent)
     DistinctWs dws;                                         // its device buffers (a sharded parent's live on devices[0])
     uint64_t per_group_stats[8] = {0};                      // vdb_flat_per_group_stats: counters of the last search per group
@@ -397,6 +416,12 @@ MaskSrc mask_src(const HostSearch& r);
 // resolution of every example to its device row (ex_rows [rec.total]): the list stages, the exact scan for what they cannot
 // settle, the copy-out (dn goes to r.scores) and ix->recommend_best_stats.  kmax: the largest k of the batch.
 int recommend_best_drive(Index* ix, const HostSearch& r, const RecommendReq& rec, const uint32_t* ex_rows, size_t kmax);
+// Discovery search (vdb_flat_discover_batch) behind the entry point's checks, the flush and the resolution of
+// every example to its device row: ex_ids / ex_rows hold, request by request, the target and then p_1 n_1 p_2 n_2 ...
+// (2 P_b + 1 entries; nq + 2 req.pairs in all).  The list stages, the exact scan for what they cannot settle, the copy-out (the
+// ranks go to out_ranks, which may be null) and ix->discover_stats.  kcut = min(the largest k of the batch, len) > 0.
+int discover_drive(Index* ix, const HostSearch& r, const DiscoverReq& req, const uint64_t* ex_ids, const uint32_t* ex_rows, size_t kcut,
+                   uint32_t* out_ranks);
 int range_search_device(Index* ix, const float* d_q, size_t nq, size_t dim, const float* d_radii, const uint64_t* d_idmask,
                         size_t mask_bits, size_t max_results, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                         uint64_t* d_out_totals, hipStream_t user_stream);

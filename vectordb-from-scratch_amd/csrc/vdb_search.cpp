@@ -1815,4 +1815,162 @@ int recommend_best_drive(Index* ix, const HostSearch& r, const RecommendReq& rec
     return copy_out(Lists{B.outi.p, B.outd.p, B.outc.p, nullptr, kcut, B.outn.p}, r, s);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Discovery search (vdb_flat_discover_batch).  The answer of a request is defined row by row (rank, d(t, x));
+// the driver only decides how it gets there, and every way is exact:
+//   lists  the targets of the requests in hand become one query block (gathered on the device), ONE certified search ranks
+//          the store for each at depth D, the set strike removes every request's examples, discover_rank_kernel counts the
+//          satisfied pairs of every candidate and writes the answer of a request that has k rows of rank P or a complete
+//          list.  Stage 0 runs at vdb_flat_discover_depth(.., 0), stage 1 -- the unanswered requests only -- at (.., 1).
+//   scan   what is still unanswered: discover_scan_kernel writes one key per eligible row, the full-scan select sorts the first
+//          k, discover_emit_kernel takes them apart.
+// One host read of the flags per list stage; ids and distances stay on the device until the copy-out.
+// ---------------------------------------------------------------------------------------------
+int discover_drive(Index* ix, const HostSearch& r, const DiscoverReq& req, const uint64_t* ex_ids, const uint32_t* ex_rows, size_t kcut,
+                   uint32_t* out_ranks) {
+    DiscoverWs& B = ix->dcw;
+    Workspace& W = ix->wsv[0];                                     // (nothing is in flight)
+    hipStream_t s = ix->stream;
+    uint64_t* st = ix->discover_stats;
+    const size_t nq = r.nq, total = nq + 2 * req.pairs, dim = ix->dim;
+    const size_t len = ix->n_live + ix->misfits.size();
+    int rc;
+    if (kcut == 0) {
+        for (size_t b = 0; b < nq; ++b) r.counts[b] = 0;
+        return VDB_OK;
+    }
+    if ((rc = pre_device_checks(ix, dim, false))) return rc;
+    if ((rc = ensure_ranks(ix))) return rc;
+    const uint32_t n = ix->n_uploaded;
+    const size_t D0 = vdb_flat_discover_depth(kcut, req.pmax, len, 0), D1 = vdb_flat_discover_depth(kcut, req.pmax, len, 1);
+    st[5] = D0;
+
+    // ---- the requests go up: offsets [nq + 1] | k [nq] | rows [total], and the ids
+    const size_t o_k = nq + 1, o_row = o_k + nq, words = o_row + total;
+    std::vector<uint32_t> meta(words);
+    for (size_t b = 0; b <= nq; ++b) meta[b] = (uint32_t)(b + 2 * req.offsets[b]);
+    for (size_t b = 0; b < nq; ++b) meta[o_k + b] = (uint32_t)std::min(r.ks ? r.ks[b] : r.k, kcut);
+    memcpy(meta.data() + o_row, ex_rows, total * 4);
+    const size_t no = nq * kcut;
+    if ((rc = B.meta.ensure(words)) || (rc = B.ids.ensure(total)) || (rc = B.stat.ensure(2)) || (rc = B.outi.ensure(no)) ||
+        (rc = B.outd.ensure(no)) || (rc = B.outr.ensure(no)) || (rc = B.outc.ensure(nq)))
+        return rc;
+    // (the uploads below read host vectors of this frame: no return, early ones included, leaves one in flight)
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
+    HIP_TRY(hipMemcpyAsync(B.meta.p, meta.data(), words * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(B.ids.p, ex_ids, total * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(B.stat.p, 0, 8, s));
+    const vdb::DiscoverRequests R{B.meta.p, B.meta.p + o_k, B.meta.p + o_row, B.ids.p};
+    const uint64_t* d_mask;
+    if ((rc = stage_mask(B.mask_in, mask_src(r), s, &d_mask))) return rc;
+    const uint32_t* d_rank2row = ix->ids_monotone ? nullptr : ix->d_rank2row.p;
+
+    // ---- a list stage for the requests `reqs` at depth D; *left receives those it could not answer
+    auto run_lists = [&](const std::vector<uint32_t>& reqs, size_t D, std::vector<uint32_t>* left) -> int {
+        const size_t nr = reqs.size();
+        // requests [nr] | target rows [nr] | offsets of the stage's example sets [nr + 1]; the ids of those sets
+        std::vector<uint32_t> sel(3 * nr + 1);
+        std::vector<uint64_t> sids;
+        for (size_t j = 0; j < nr; ++j) {
+            const uint32_t b = reqs[j];
+            sel[j] = b;
+            sel[nr + j] = ex_rows[meta[b]];
+            sel[2 * nr + j] = (uint32_t)sids.size();
+            sids.insert(sids.end(), ex_ids + meta[b], ex_ids + meta[b + 1]);
+        }
+        sel[3 * nr] = (uint32_t)sids.size();
+        if ((rc = B.sel.ensure(sel.size())) || (rc = B.sids.ensure(sids.size())) || (rc = B.q.ensure(nr * std::max<size_t>(dim, 1))) ||
+            (rc = B.li.ensure(nr * D)) || (rc = B.ld.ensure(nr * D)) || (rc = B.lc.ensure(nr)) || (rc = B.raw.ensure(nr)) ||
+            (rc = B.answered.ensure(nr)) || (rc = B.struck.ensure(1)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(B.sel.p, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(B.sids.p, sids.data(), sids.size() * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(B.struck.p, 0, 4, s));
+        // only row numbers go up; the vectors never leave HBM
+        vdb::launch_gather_rows(rows_f32(ix), ix->ld, ix->dim, n, B.sel.p + nr, (uint32_t)nr, B.q.p, s);
+        HIP_TRY(hipGetLastError());
+        if ((rc = search_device(ix, W, B.q.p, nr, dim, D, d_mask, r.mask_bits, B.li.p, B.ld.p, B.lc.p, nullptr))) return rc;
+        st[6] += nr;
+        // (the strike rewrites the counts: whether a list came back full is read from this copy)
+        HIP_TRY(hipMemcpyAsync(B.raw.p, B.lc.p, nr * 4, hipMemcpyDeviceToDevice, s));
+        vdb::StrikeSetParams sp{B.li.p, B.ld.p, B.lc.p, (uint32_t)D, B.sel.p + 2 * nr, B.sids.p, (uint32_t)D, B.struck.p};
+        vdb::launch_strike_set(sp, (uint32_t)nr, s);
+        vdb::DiscoverRankParams rp{};
+        rp.rows = rows_f32(ix); rp.ld = ix->ld; rp.dim = ix->dim; rp.n_rows = n; rp.metric = ix->metric; rp.nd = ix->d_nd;
+        rp.row_ids = ix->d_row_ids; rp.rank2row = d_rank2row; rp.live = ix->d_live;
+        rp.R = R; rp.sel = B.sel.p;
+        rp.cand_ids = B.li.p; rp.cand_dists = B.ld.p; rp.cand_cnt = B.lc.p; rp.raw_cnt = B.raw.p;
+        rp.cand_stride = (uint32_t)D; rp.depth = (uint32_t)D; rp.exhaustive = D >= len ? 1u : 0u;
+        rp.out_ids = B.outi.p; rp.out_dists = B.outd.p; rp.out_ranks = B.outr.p; rp.out_counts = B.outc.p; rp.kout = (uint32_t)kcut;
+        rp.answered = B.answered.p; rp.status = B.stat.p + 1;
+        vdb::launch_discover_rank(rp, (uint32_t)nr, s);
+        HIP_TRY(hipGetLastError());
+        std::vector<uint32_t> flag(nr);
+        HIP_TRY(hipMemcpyAsync(flag.data(), B.answered.p, nr * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        left->clear();
+        for (size_t j = 0; j < nr; ++j) if (!flag[j]) left->push_back(reqs[j]);
+        return VDB_OK;
+    };
+
+    // ---- the exact scan for the requests `reqs`, as many per pass as the key buffer holds
+    auto run_scan = [&](const std::vector<uint32_t>& reqs) -> int {
+        const size_t nr = reqs.size();
+        if (n >> vdb::DISCOVER_KEY_ID_BITS)
+            return fail(VDB_ERR_INVALID_ARGUMENT, "the exact scan of a discovery search keys at most 2^%u - 1 rows, the store holds %u",
+                        vdb::DISCOVER_KEY_ID_BITS, n);
+        const uint32_t* d_rowmask;
+        if ((rc = eligibility_mask(ix, W, s, d_mask, r.mask_bits, &d_rowmask))) return rc;
+        const size_t G = std::min<size_t>(std::min<size_t>(nr, SUPER), std::max<size_t>(RB_SCAN_KEYS / std::max<uint32_t>(n, 1), 1));
+        if ((rc = B.sel.ensure(nr)) || (rc = W.w_exact.ensure(G * n)) || (rc = W.w_exsel.ensure((size_t)SUPER * MAX_SELECT + 8)) ||
+            (rc = W.w_cnt.ensure(4 * SUPER + 16)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(B.sel.p, reqs.data(), nr * 4, hipMemcpyHostToDevice, s));
+        for (size_t g0 = 0; g0 < nr; g0 += G) {
+            const uint32_t g = (uint32_t)std::min(G, nr - g0);
+            vdb::DiscoverScanParams sp{rows_f32(ix), ix->ld, ix->dim, n, ix->metric, ix->d_nd, d_rowmask,
+                                       ix->ids_monotone ? nullptr : ix->d_idrank.p, R, B.sel.p + g0, W.w_exact.p, n, B.stat.p};
+            vdb::launch_discover_scan(sp, g, s);
+            // (the keys are no (distance, id rank) pairs: the select only sorts them, discover_emit_kernel reads them)
+            vdb::SelectParams mp{};
+            mp.kk = (uint32_t)kcut; mp.out_keys = W.w_exsel.p; mp.out_stride = MAX_SELECT; mp.out_cnt = W.w_cnt.p;
+            mp.keys = W.w_exact.p; mp.stride = n; mp.counts = nullptr; mp.n_fixed = n; mp.cap = n;
+            vdb::launch_select(mp, g, s);
+            vdb::DiscoverEmitParams ep{W.w_exsel.p, W.w_cnt.p, MAX_SELECT, R, B.sel.p + g0, d_rank2row, ix->d_row_ids, n,
+                                       B.outi.p, B.outd.p, B.outr.p, B.outc.p, (uint32_t)kcut, B.stat.p + 1};
+            vdb::launch_discover_emit(ep, g, s);
+            HIP_TRY(hipGetLastError());
+        }
+        return VDB_OK;
+    };
+
+    std::vector<uint32_t> todo(nq), left;
+    for (size_t b = 0; b < nq; ++b) todo[b] = (uint32_t)b;
+    // (automatic: a list whose depth is the whole index is the expensive way to scan it)
+    const bool lists = ix->discover_route == 1 || (ix->discover_route == 0 && D0 < len);
+    if (lists) {
+        if ((rc = run_lists(todo, D0, &left))) return rc;
+        st[2] = todo.size() - left.size();
+        todo.swap(left);
+        if (!todo.empty() && D1 > D0) {
+            if ((rc = run_lists(todo, D1, &left))) return rc;
+            st[3] = todo.size() - left.size();
+            todo.swap(left);
+        }
+    }
+    if (!todo.empty()) {
+        if ((rc = run_scan(todo))) return rc;
+        st[4] = todo.size();
+    }
+    uint32_t status[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(status, B.stat.p, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (status[1] & 2u) return fail(VDB_ERR_DEVICE, "internal error: a candidate without a live row on the device");
+    if (status[0] & vdb::ST_NAN) return fail_nan();
+    // (the ranks travel in the copy-out's 32-bit column: the same bits, read back as uint32_t)
+    Batch out = r;
+    out.codes = reinterpret_cast<int32_t*>(out_ranks);
+    return copy_out(Lists{B.outi.p, B.outd.p, B.outc.p, reinterpret_cast<const int32_t*>(B.outr.p), kcut}, out, s);
+}
+
 }  // namespace vdbi

@@ -447,6 +447,72 @@ class GpuFlatIndex(Index):
         if rc:
             _raise(rc)
 
+    # ---- discovery search (include/vdb_flat.h vdb_flat_discover_batch; no reference counterpart)
+    def discover_batch(self, targets, pairs, k, id_mask=None, mask_bits=0, compiled_mask=None, want_ranks=True):
+        """A target ranked inside context pairs: request b has the stored id targets[b] and the (positive id, negative id) pairs
+        pairs[b] (at most 16, may be empty).  rank(x) counts the pairs whose positive is strictly nearer to row x than their
+        negative (the distances search_batch_by_id reports), and the answer is the rows by (rank descending, distance from the
+        target ascending, id), the target and every pair id left out (include/vdb_flat.h has the exact rules).  k an int or a
+        per-request array; the masks as in recommend_batch.  Returns (ids u64 [nq, kmax], dists f32 [nq, kmax] -- from the
+        target --, ranks u32 [nq, kmax] or None without want_ranks, counts [nq]).  An id that is not stored raises VectorNotFound
+        for the whole batch."""
+        if compiled_mask is not None and id_mask is not None:
+            raise ValueError("pass id_mask or compiled_mask, not both")
+        tg = np.ascontiguousarray(targets, dtype=np.uint64).reshape(-1)
+        nq = tg.size
+        if len(pairs) != nq:
+            raise ValueError(f"{nq} targets but {len(pairs)} pair lists")
+        pl = [np.asarray(p, dtype=np.uint64).reshape(-1, 2) for p in pairs]
+        flat = np.ascontiguousarray(np.concatenate([p.reshape(-1) for p in pl] + [np.zeros(0, dtype=np.uint64)]))
+        offsets = np.zeros(nq + 1, dtype=np.uintp)
+        offsets[1:] = np.cumsum([p.shape[0] for p in pl], dtype=np.uintp)
+        if np.isscalar(k):
+            ks_ptr, kscalar, kmax = None, int(k), int(k)
+        else:
+            ks = np.ascontiguousarray(k, dtype=np.uintp)
+            if ks.shape != (nq,):
+                raise ValueError(f"k must be a scalar or hold one value per request ({nq}), not {ks.shape}")
+            ks_ptr = ks.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t))
+            kscalar, kmax = 0, int(ks.max()) if ks.size else 0
+        kstride = max(kmax, 1)
+        out_ids = np.zeros((nq, kstride), dtype=np.uint64)
+        out_d = np.zeros((nq, kstride), dtype=np.float32)
+        out_r = np.zeros((nq, kstride), dtype=np.uint32) if want_ranks else None
+        counts = np.zeros(nq, dtype=np.uintp)
+        szp = ctypes.POINTER(ctypes.c_size_t)
+        head = (self._h, _u64p(tg), _u64p(flat), offsets.ctypes.data_as(szp), nq, ks_ptr, kscalar)
+        tail = (kstride, _u64p(out_ids), _fp(out_d), out_r.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if want_ranks else None,
+                counts.ctypes.data_as(szp))
+        if compiled_mask is not None:
+            rc = self._L.vdb_flat_discover_batch_filtered(*head, compiled_mask.handle, *tail)
+        else:
+            mask_ptr = None
+            if id_mask is not None:
+                m = np.ascontiguousarray(id_mask, dtype=np.uint64)
+                mask_ptr = _u64p(m)
+            rc = self._L.vdb_flat_discover_batch(*head, mask_ptr, int(mask_bits), *tail)
+        if rc == _ffi.ERR_NOT_FOUND:
+            raise VectorNotFound(int(_ffi.last_error()[0].rsplit(": ", 1)[-1]))
+        if rc:
+            _raise(rc)
+        return out_ids, out_d, out_r, counts
+
+    def discover_stats(self):
+        """The last discover_batch: [0] requests, [1] example rows (targets included), [2] requests answered at list stage 0,
+        [3] at list stage 1, [4] by the exact scan, [5] the stage-0 depth, [6] list searches run (one per request and stage it
+        went through), [7] 0."""
+        out = (ctypes.c_uint64 * 8)()
+        rc = self._L.vdb_flat_discover_stats(self._h, out)
+        if rc:
+            _raise(rc)
+        return [int(x) for x in out]
+
+    def debug_set_discover_route(self, mode):
+        """Tests: 0 automatic, 1 the list stages first whatever the depth, 2 the exact scan only.  The answers are the same bits."""
+        rc = self._L.vdb_flat_debug_set_discover_route(self._h, int(mode))
+        if rc:
+            _raise(rc)
+
     # ---- diverse top-k, MMR on the device (include/vdb_flat.h vdb_flat_search_batch_mmr; no reference counterpart)
     def search_batch_mmr(self, queries, k, candidates, lam, id_mask=None, mask_bits=0, compiled_mask=None, ks=None):
         """k results that are not all the same thing: the `candidates` nearest rows of each query (what search_batch_arrays

@@ -751,6 +751,43 @@ class VectorStore:
         example."""
         return self._recommend_requests("recommend_best", requests, k, flt)
 
+    # ---- "like this item, on the side of what I liked" (GpuFlatIndex.discover_batch; no reference counterpart)
+    def discover(self, target, pairs, k, flt=None):
+        """The k stored vectors ranked first by how many of the (positive id, negative id) `pairs` they satisfy -- nearer to the
+        positive than to the negative -- then by distance to the stored vector `target`; the target and the pair ids themselves
+        left out.  Returns (results, ranks): the SearchResults with the distance from the target, and the satisfied pairs of each."""
+        return self.discover_batch([(target, pairs)], k, flt)[0]
+
+    def discover_batch(self, requests, k, flt=None):
+        """discover for several (target id, pairs) requests in one device call; the vectors never leave the GPU.  An unknown id
+        raises VectorNotFound.  flt is a PRE-filter, as in recommend_batch: a filtered-out id may still be an example."""
+        if not isinstance(self._index, GpuFlatIndex):
+            raise ValueError("discover needs a GpuFlatIndex")
+
+        def internal(id):
+            i = self._internal_of(id)
+            if i is None:
+                raise VectorNotFound(id)
+            return i
+
+        targets, pairs = [], []
+        for t, ps in requests:
+            targets.append(internal(t))
+            pairs.append([(internal(p), internal(n)) for p, n in ps])
+        if not targets:
+            return []
+        cm = self.compile_filter_device(flt) if flt is not None and self._table is not None else None
+        if cm is not None:
+            try:
+                out_ids, dists, ranks, counts = self._index.discover_batch(targets, pairs, int(k), compiled_mask=cm)
+            finally:
+                cm.release()
+        else:
+            mask, bits = self.compile_filter(flt) if flt is not None else (None, 0)
+            out_ids, dists, ranks, counts = self._index.discover_batch(targets, pairs, int(k), id_mask=mask, mask_bits=bits)
+        return [(self._map([(int(out_ids[b, i]), dists[b, i]) for i in range(int(counts[b]))]), [int(x) for x in ranks[b, :int(counts[b])]])
+                for b in range(len(targets))]
+
     # ---- "k results that are not all the same thing" (GpuFlatIndex.search_batch_mmr; no reference counterpart)
     def search_mmr(self, query, k, lam=0.5, candidates=None, flt=None):
         """k stored vectors near `query` and apart from each other (maximal marginal relevance), in pick order: the nearest
