@@ -686,6 +686,57 @@ size_t vdb_flat_discover_depth(size_t k, size_t P, size_t len, int stage);
 int vdb_flat_debug_set_discover_route(vdb_flat_index *h, int mode);
 
 /*
+ * LATE-INTERACTION SEARCH (MaxSim) over multi-vector documents (no reference counterpart; a caller would download one distance
+ * column per token over the whole store and take segment minima and sums on the host).  Query b is T_b token vectors, 1 <= T_b <=
+ * VDB_MAXSIM_MAX_TOKENS: tokens [sum T_b][dim] side by side, query b owns tokens [offsets[b], offsets[b + 1]).  The rows are
+ * grouped into documents by column `slot` of `table`, as in vdb_flat_search_batch_distinct; n_codes bounds the codes the column
+ * may hold (a dictionary's size).
+ *  - d(t, x) is the distance vdb_flat_search_batch reports for token t as the query and row x, bit for bit.
+ *  - A row is ELIGIBLE when it is live, the optional mask admits it, and its code c in the column is >= 0.  A row with code -1, or
+ *    with an id at or beyond the column's length, is NOT a document here -- unlike the search by group, where such a row is its
+ *    own group: the score table below has a slot per code and no room for a million one-row documents.  A caller who wants them
+ *    gives them a field.
+ *  - A DOCUMENT is a code with at least one eligible row.  m(t, c) = the minimum of d(t, x) over the eligible rows x with code c,
+ *    by the index's ordered-f32 comparison (-0.0 in front of +0.0).
+ *  - score(c) = ((m(t_1, c) + m(t_2, c)) + m(t_3, c)) + ...: an f32 left fold in token order that starts FROM the first term, one
+ *    rounding per add.  T_b = 1 returns m(t_1, c)'s own bits: with one token and every row coded, the call is
+ *    vdb_flat_search_batch_distinct, codes and distance bits.
+ *  - Result: the documents by (ordered score ascending, code ascending), cut to min(k_b, documents): out_codes, out_scores
+ *    [nq][kstride], out_counts.  The answer for k_b is the first k_b entries of the answer for max k_b <= VDB_MAXSIM_MAX_K.
+ *    +inf and -inf scores are ordinary.
+ * Errors, in this order, (1) to (7) before any device work: (1) an empty index, nq = 0 or max k_b = 0: counts 0, VDB_OK; (2) NULL
+ * arguments, a stride below max k_b, offsets that do not start at 0 or decrease; (3) a T_b of 0 or above VDB_MAXSIM_MAX_TOKENS;
+ * (4) n_codes = 0 (or above 2^31); (5) everything vdb_flat_search_batch_distinct refuses -- the table, the slot, max k_b above
+ * VDB_MAXSIM_MAX_K, a table on another device, an id ever at or above 2^32, a compiled mask on another device; (6) a sharded
+ * handle; (7) VDB_ERR_DIMENSION_MISMATCH.  Then staged writes are flushed, and: a live zero-norm row, or a zero-norm token, under
+ * Cosine is VDB_ERR_INVALID_VECTOR; a code >= n_codes met at a live admitted row is VDB_ERR_INVALID_ARGUMENT; a NaN d(t, x) at an
+ * eligible row, or a NaN score (+inf and -inf meeting in the sum), is VDB_ERR_NAN.  On any error nothing is written.  Locking,
+ * flushing, the table's lock and the stream ordering are those of vdb_flat_search_batch_distinct.
+ * Not built: a bf16 / MFMA screening pass with a certificate per (token, document), sharded handles (refused as in (6)), HNSW
+ * stores, device-pointer and ticket forms, stored ids as tokens, the best row per token, the C++ host mirror.
+ * How (csrc/kernels_maxsim.hip): one thread per row reads its row once per query and folds it against all T_b
+ * tokens in that pass (32 accumulator chains in registers, the token elements through scalar loads); the ordered distances go
+ * into table[query][code][token] by an integer atomic minimum, one per run of neighbouring rows of one document; a second kernel
+ * folds every touched code's minima into the key (ordered score, code), the radix select sorts the first max k_b and a last
+ * kernel takes them apart.  The table takes n_codes x 32 x 4 bytes per query and the keys n_codes x 8: the queries go through in
+ * chunks that keep both under 256 MiB (vdb_flat_debug_set_maxsim_table_cap lowers that, for tests: 0 restores it).
+ * vdb_flat_maxsim_stats describes the last call: [0] queries, [1] tokens, [2] chunks, [3] eligible rows scanned, summed over the
+ * queries, [4] documents seen, summed over the queries, [5] documents returned, [6] [7] 0.
+ */
+#define VDB_MAXSIM_MAX_TOKENS 32
+#define VDB_MAXSIM_MAX_K 1024
+int vdb_flat_search_batch_maxsim(vdb_flat_index *h, const float *tokens /* [offsets[nq]][dim] */, const size_t *offsets /* [nq + 1] */,
+                                 size_t nq, size_t dim, const size_t *ks, size_t k, vdb_meta_table *table, uint32_t slot,
+                                 size_t n_codes, const uint64_t *id_mask, size_t mask_bits, size_t kstride,
+                                 int32_t *out_codes, float *out_scores, size_t *out_counts);
+int vdb_flat_search_batch_maxsim_filtered(vdb_flat_index *h, const float *tokens, const size_t *offsets /* [nq + 1] */,
+                                          size_t nq, size_t dim, const size_t *ks, size_t k, vdb_meta_table *table, uint32_t slot,
+                                          size_t n_codes, const vdb_meta_mask *mask, size_t kstride,
+                                          int32_t *out_codes, float *out_scores, size_t *out_counts);
+int vdb_flat_maxsim_stats(const vdb_flat_index *h, uint64_t out[8]);
+int vdb_flat_debug_set_maxsim_table_cap(vdb_flat_index *h, size_t bytes);
+
+/*
  * DIVERSE TOP-K (MAXIMAL MARGINAL RELEVANCE): k results that are not all the same thing (no reference counterpart; a caller would
  * search at depth m, get_vector every candidate and run an O(k m dim) loop on the host).  A request is a query q, a count k, a
  * candidate depth m and a trade-off lambda, 1 <= k <= m <= VDB_MMR_MAX_CANDIDATES, lambda an f32 in [0, 1].

@@ -812,4 +812,35 @@ struct DiscoverEmitParams {
 };
 void launch_discover_emit(const DiscoverEmitParams& p, uint32_t n_req, hipStream_t s);
 
+// ---------------------------------------------------------------- late-interaction (MaxSim) search (kernels_maxsim.hip)
+constexpr uint32_t MAXSIM_MAX_TOKENS = 32;                                 // tokens of one query, and the token stride of the table (VDB_MAXSIM_MAX_TOKENS)
+// Query q0 + y of the call owns tokens [offs[q0 + y], offs[q0 + y + 1]) -- at most MAXSIM_MAX_TOKENS -- of the prepared block qp
+// (rows of ld floats, zero padded) with the exact-order norms qnorm.  A row is eligible when rowmask admits it (null: every row
+// below n_rows), its id lies below codes_len and its code c = codes[id] is >= 0; a code >= n_codes sets bit 0 of status[3] and
+// the row is left out.  table[(y * n_codes + c) * MAXSIM_MAX_TOKENS + t] takes the atomicMin of the ordered d(token t, row); the
+// caller fills it with ones.  status[0] |= ST_NAN for a NaN distance at an eligible row; *rows_scanned += the eligible rows, by
+// the workgroups of y = 0 only.
+struct MaxsimScanParams {
+    const float* rows; uint32_t ld, dim, n_rows; int metric; const float* nd;
+    const uint32_t* rowmask; const uint64_t* row_ids; const int32_t* codes; uint64_t codes_len; uint32_t n_codes;
+    const float* qp; const float* qnorm; const uint32_t* offs; uint32_t q0;
+    uint32_t* table; uint32_t* status; unsigned long long* rows_scanned;
+};
+void launch_maxsim_scan(const MaxsimScanParams& p, uint32_t n_queries, hipStream_t s);
+// keys[y * n_codes + c] = ordered(score) << 32 | c for every code whose token 0 entry was reached, EMPTY_KEY for every other;
+// score = the f32 left fold of the query's minima in token order, from the first.  status[0] |= ST_NAN for a NaN score;
+// *docs_seen += the keys that are not empty.
+struct MaxsimFoldParams {
+    const uint32_t* table; uint32_t n_codes; const uint32_t* offs; uint32_t q0;
+    uint64_t* keys; uint32_t* status; unsigned long long* docs_seen;
+};
+void launch_maxsim_fold(const MaxsimFoldParams& p, uint32_t n_queries, hipStream_t s);
+// The first min(key_cnt[y], ks[b], kout) of the ascending keys [y * key_stride ..] of query b = q0 + y, taken apart into
+// out_codes / out_scores [b * kout ..]; their number to out_counts[b].  status[3] bit 1: an empty key among them.
+struct MaxsimEmitParams {
+    const uint64_t* keys; const uint32_t* key_cnt; uint32_t key_stride; const uint32_t* ks; uint32_t q0;
+    int32_t* out_codes; float* out_scores; uint32_t* out_counts; uint32_t kout; uint32_t* status;
+};
+void launch_maxsim_emit(const MaxsimEmitParams& p, uint32_t n_queries, hipStream_t s);
+
 }  // namespace vdb

@@ -1040,6 +1040,112 @@ int vdb_flat_debug_set_discover_route(vdb_flat_index* ix, int mode) {
     });
 }
 
+// ---- late-interaction (MaxSim) search (no reference counterpart; vdb_search.cpp maxsim_drive)
+static_assert(vdb::MAXSIM_MAX_TOKENS == VDB_MAXSIM_MAX_TOKENS, "the table's token stride and the public limit");
+static_assert(VDB_MAXSIM_MAX_K <= MAX_SELECT, "the select holds the largest answer");
+
+// Checks (2) to (4) of include/vdb_flat.h "LATE-INTERACTION SEARCH", which need no handle; fills r->total.
+static int maxsim_check(const HostSearch& r, MaxsimReq* q, size_t kmax) {
+    if (!q->tokens || !q->offsets || !q->out_codes || !q->out_scores) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (kmax > r.kstride) return fail(VDB_ERR_INVALID_ARGUMENT, "kstride %zu smaller than the largest k %zu", r.kstride, kmax);
+    if (q->offsets[0] != 0) return fail(VDB_ERR_INVALID_ARGUMENT, "offsets[0] is %zu, not 0", q->offsets[0]);
+    for (size_t b = 0; b < r.nq; ++b)
+        if (q->offsets[b + 1] < q->offsets[b]) return fail(VDB_ERR_INVALID_ARGUMENT, "offsets decrease at query %zu", b);
+    for (size_t b = 0; b < r.nq; ++b) {
+        const size_t T = q->offsets[b + 1] - q->offsets[b];
+        if (T == 0 || T > VDB_MAXSIM_MAX_TOKENS)
+            return fail(VDB_ERR_INVALID_ARGUMENT, "query %zu has %zu tokens, outside [1, %d]", b, T, VDB_MAXSIM_MAX_TOKENS);
+    }
+    q->total = q->offsets[r.nq];
+    if (q->n_codes == 0 || q->n_codes > ((size_t)1 << 31)) return fail(VDB_ERR_INVALID_ARGUMENT, "n_codes %zu outside [1, 2^31]", q->n_codes);
+    return VDB_OK;
+}
+
+// The front end of both forms, in the order of the contract: the answered cases, the handle-free checks, then everything
+// vdb_flat_search_batch_distinct refuses, the sharded refusal and the dimension -- all before the flush and any device work.
+static int maxsim_host(vdb_flat_index* ix, HostSearch r, MaxsimReq req, vdb_meta_table* table, uint32_t slot) {
+    return guarded([&]() -> int {
+    const size_t nq = r.nq;
+    int rc;
+    if (nq && !r.counts) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    std::unique_lock<std::mutex> g;
+    size_t len = 1;                                                // (without a handle the checks below still answer in their order)
+    if (ix) {
+        g = std::unique_lock<std::mutex>(ix->mu);
+        if (!ix->multi && in_flight(ix)) return refuse_in_flight();
+        memset(ix->maxsim_stats, 0, sizeof(ix->maxsim_stats));
+        len = ix->multi ? multi_len(ix) : ix->n_live + ix->misfits.size();
+    }
+    size_t kmax = r.ks ? 0 : r.k;
+    for (size_t b = 0; r.ks && b < nq; ++b) kmax = std::max(kmax, r.ks[b]);
+    if (nq == 0 || len == 0 || kmax == 0) {                        // (1): answered, whatever else was passed
+        if (!ix) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+        for (size_t b = 0; b < nq; ++b) r.counts[b] = 0;
+        ix->maxsim_stats[0] = nq;
+        return VDB_OK;
+    }
+    if ((rc = maxsim_check(r, &req, kmax))) return rc;             // (2) (3) (4)
+    if (!ix) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    ix->maxsim_stats[0] = nq; ix->maxsim_stats[1] = req.total;
+    // (5) what the search by group refuses
+    const int dev = ix->multi ? multi_home(ix) : ix->device;
+    int tdev = 0;
+    if ((rc = meta_column_check(table, slot, &tdev))) return rc;
+    if (kmax > VDB_MAXSIM_MAX_K) return fail(VDB_ERR_INVALID_ARGUMENT, "a late-interaction search returns at most %d documents per query, not %zu", VDB_MAXSIM_MAX_K, kmax);
+    if (tdev != dev) return fail(VDB_ERR_INVALID_ARGUMENT, "the metadata table lives on device %d, the index on device %d", tdev, dev);
+    const uint64_t id_bound = ix->multi ? multi_id_bound(ix) : ix->id_bound;
+    if (id_bound > (1ull << 32)) return fail(VDB_ERR_INVALID_ARGUMENT, "the index has held an id at or above 2^32: a metadata table cannot describe it");
+    if (r.cm) {
+        if ((rc = compiled_mask_check(r.cm, dev))) return rc;
+        r.mask_bits = r.cm->bits;
+    }
+    if (nq > 0x3fffffffull) return fail(VDB_ERR_INVALID_ARGUMENT, "batch too large");
+    if (ix->multi) return refuse_multi("vdb_flat_search_batch_maxsim");   // (6)
+    if ((rc = query_dim_check(ix, req.dim))) return rc;            // (7)
+    if ((rc = set_device(ix))) return rc;
+    // staged adds first, then the table's staged column writes; the handle's stream waits for those by an event
+    if ((rc = flush(ix))) return rc;
+    MetaColumn col;
+    if ((rc = meta_column_acquire(table, slot, ix->stream, &col))) return rc;
+    struct Release { vdb_meta_table* t; ~Release() { meta_column_release(t); } } release{table};
+    return maxsim_drive(ix, r, req, col.d_codes, col.len, kmax);
+    });
+}
+
+int vdb_flat_search_batch_maxsim(vdb_flat_index* ix, const float* tokens, const size_t* offsets, size_t nq, size_t dim, const size_t* ks,
+                                 size_t k, vdb_meta_table* table, uint32_t slot, size_t n_codes, const uint64_t* id_mask, size_t mask_bits,
+                                 size_t kstride, int32_t* out_codes, float* out_scores, size_t* out_counts) {
+    return maxsim_host(ix, under(host_search(nullptr, nq, dim, ks, k, kstride, nullptr, nullptr, out_counts), id_mask, mask_bits),
+                       MaxsimReq{tokens, offsets, dim, n_codes, out_codes, out_scores}, table, slot);
+}
+
+int vdb_flat_search_batch_maxsim_filtered(vdb_flat_index* ix, const float* tokens, const size_t* offsets, size_t nq, size_t dim,
+                                          const size_t* ks, size_t k, vdb_meta_table* table, uint32_t slot, size_t n_codes,
+                                          const vdb_meta_mask* mask, size_t kstride, int32_t* out_codes, float* out_scores,
+                                          size_t* out_counts) {
+    if (!mask) return fail(VDB_ERR_INVALID_ARGUMENT, "null mask");
+    return maxsim_host(ix, under(host_search(nullptr, nq, dim, ks, k, kstride, nullptr, nullptr, out_counts), mask),
+                       MaxsimReq{tokens, offsets, dim, n_codes, out_codes, out_scores}, table, slot);
+}
+
+int vdb_flat_maxsim_stats(const vdb_flat_index* ix, uint64_t out[8]) {
+    if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (ix->multi) return refuse_multi("vdb_flat_maxsim_stats");
+    memcpy(out, ix->maxsim_stats, sizeof(ix->maxsim_stats));
+    return VDB_OK;
+}
+
+int vdb_flat_debug_set_maxsim_table_cap(vdb_flat_index* ix, size_t bytes) {
+    return guarded([&]() -> int {
+    if (!ix) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (ix->multi) return refuse_multi("vdb_flat_debug_set_maxsim_table_cap");
+    if (bytes > MAXSIM_TABLE_CAP) return fail(VDB_ERR_INVALID_ARGUMENT, "a cap of %zu bytes is above the default %zu: the setter only lowers it", bytes, MAXSIM_TABLE_CAP);
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->maxsim_table_cap = bytes;
+    return VDB_OK;
+    });
+}
+
 // ---- diverse top-k (no reference counterpart; search_batch_host with r.mmr)
 // The checks of include/vdb_flat.h "DIVERSE TOP-K" item 8, in its order, before any lock or device work.  *done: the call is
 // answered (an empty index, or no query asks for a row).

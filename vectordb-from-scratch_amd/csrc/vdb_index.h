@@ -128,6 +128,23 @@ struct DiscoverReq {
     size_t pairs = 0, pmax = 0;                                   // offsets[nq]; the most pairs of a request (discover_check)
 };
 
+// What one late-interaction search owns on the device beside the search workspace (vdb_search.cpp maxsim_drive):
+// the tokens as they came in, offsets [nq + 1] | k [nq], the table of minima and the key blocks of one chunk of queries, the
+// counters (eligible rows, documents seen), and the answers.
+struct MaxsimWs {
+    vdbi::DevBuf<float> q, outs;
+    vdbi::DevBuf<uint32_t> meta, table, outc;
+    vdbi::DevBuf<int32_t> outcodes;
+    vdbi::DevBuf<uint64_t> keys, ctr, mask_in;
+};
+// A late-interaction request as the caller passed it, checked by maxsim_check: query b owns tokens [offsets[b], offsets[b + 1])
+// of tokens [total][dim]; the answers go to out_codes / out_scores [nq][kstride] and the batch's counts.
+struct MaxsimReq {
+    const float* tokens; const size_t* offsets; size_t dim, n_codes;
+    int32_t* out_codes; float* out_scores;
+    size_t total = 0;                                             // offsets[nq] (maxsim_check)
+};
+
 // A host-pointer batch search as its entry point received it (the extern "C" shims fill it): the batch and its outputs (Batch),
 // the queries -- vectors [nq][dim], or the stored vectors of `by` (then queries is null and dim unused), or folds of stored
 // vectors (rec, checked by recommend_check; by is then rec->ids) -- and the id mask in the form it came in.  mmr: the lists of the
@@ -311,6 +328,9 @@ struct vdb_flat_index {
     uint64_t discover_stats[8] = {0};                       // vdb_flat_discover_stats: counters of the last discovery search
     DiscoverWs dcw;                                         // its device buffers
     int discover_route = 0;                                 // vdb_flat_debug_set_discover_route (tests): 0 auto, 1 lists first, 2 scan only
+    uint64_t maxsim_stats[8] = {0};                         // vdb_flat_maxsim_stats: counters of the last late-interaction search
+    MaxsimWs msw;                                           // its device buffers
+    size_t maxsim_table_cap = 0;                            // vdb_flat_debug_set_maxsim_table_cap (tests): bytes of table and keys per chunk, 0 = MAXSIM_TABLE_CAP
     uint64_t distinct_stats[8] = {0};                       // vdb_flat_distinct_stats: counters of the last search by group (also on a sharded parent)
     DistinctWs dws;                                         // its device buffers (a sharded parent's live on devices[0])
     uint64_t per_group_stats[8] = {0};                      // vdb_flat_per_group_stats: counters of the last search per group
@@ -422,6 +442,11 @@ int recommend_best_drive(Index* ix, const HostSearch& r, const RecommendReq& rec
 // ranks go to out_ranks, which may be null) and ix->discover_stats.  kcut = min(the largest k of the batch, len) > 0.
 int discover_drive(Index* ix, const HostSearch& r, const DiscoverReq& req, const uint64_t* ex_ids, const uint32_t* ex_rows, size_t kcut,
                    uint32_t* out_ranks);
+// Late-interaction search (vdb_flat_search_batch_maxsim) behind the entry point's checks, the flush and the
+// column's lock: d_codes [codes_len] is the column by id.  The token preparation, the chunks of queries (memset, scan, fold,
+// select, emit), one status read, the copy-out and ix->maxsim_stats.  kmax = the largest k of the batch, in [1, 1024].
+constexpr size_t MAXSIM_TABLE_CAP = (size_t)256 << 20;            // bytes of table and keys of one chunk (DESIGN.md 4.19 says why)
+int maxsim_drive(Index* ix, const HostSearch& r, const MaxsimReq& req, const int32_t* d_codes, size_t codes_len, size_t kmax);
 int range_search_device(Index* ix, const float* d_q, size_t nq, size_t dim, const float* d_radii, const uint64_t* d_idmask,
                         size_t mask_bits, size_t max_results, uint64_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                         uint64_t* d_out_totals, hipStream_t user_stream);

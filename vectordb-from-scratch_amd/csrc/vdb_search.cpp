@@ -1973,4 +1973,103 @@ int discover_drive(Index* ix, const HostSearch& r, const DiscoverReq& req, const
     return copy_out(Lists{B.outi.p, B.outd.p, B.outc.p, reinterpret_cast<const int32_t*>(B.outr.p), kcut}, out, s);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Late-interaction search (vdb_flat_search_batch_maxsim).  All tokens of the call are prepared as one query
+// block (zero padded, exact-order norms, ST_ZERO_QUERY under Cosine).  The queries then go through in CHUNKS whose table of
+// minima (n_codes x 32 words a query) and key blocks (n_codes keys a query) stay under the cap: per chunk one memset of the
+// table to ones, one scan of the rows, one fold into keys, one select, one emit.  The status words and the two counters come
+// down once, behind the last chunk; nothing reaches the caller's arrays before they are read.
+// ---------------------------------------------------------------------------------------------
+int maxsim_drive(Index* ix, const HostSearch& r, const MaxsimReq& req, const int32_t* d_codes, size_t codes_len, size_t kmax) {
+    MaxsimWs& B = ix->msw;
+    Workspace& W = ix->wsv[0];                                     // (nothing is in flight)
+    hipStream_t s = ix->stream;
+    uint64_t* st = ix->maxsim_stats;
+    const size_t nq = r.nq, total = req.total, dim = req.dim, n_codes = req.n_codes;
+    int rc;
+    if ((rc = pre_device_checks(ix, dim, total > 0x3fffffffull))) return rc;
+    const uint32_t n = ix->n_uploaded;
+
+    // ---- how many queries one chunk holds: table and keys under the cap, the select's sort area, the grid's y range
+    const size_t per_query = n_codes * (vdb::MAXSIM_MAX_TOKENS * 4 + 8);
+    const size_t cap = ix->maxsim_table_cap ? ix->maxsim_table_cap : MAXSIM_TABLE_CAP;
+    const size_t G = std::min<size_t>(std::min<size_t>(nq, SUPER), std::max<size_t>(cap / per_query, 1));
+
+    // ---- the tokens, offsets [nq + 1] | k [nq]
+    std::vector<uint32_t> meta(2 * nq + 1);
+    for (size_t b = 0; b <= nq; ++b) meta[b] = (uint32_t)req.offsets[b];
+    for (size_t b = 0; b < nq; ++b) meta[nq + 1 + b] = (uint32_t)std::min(r.ks ? r.ks[b] : r.k, kmax);
+    if ((rc = B.q.ensure(total * std::max<size_t>(dim, 1))) || (rc = B.meta.ensure(meta.size())) || (rc = B.ctr.ensure(2)) ||
+        (rc = B.table.ensure(G * n_codes * vdb::MAXSIM_MAX_TOKENS)) || (rc = B.keys.ensure(G * n_codes)) ||
+        (rc = B.outcodes.ensure(nq * kmax)) || (rc = B.outs.ensure(nq * kmax)) || (rc = B.outc.ensure(nq)) ||
+        (rc = W.w_exsel.ensure((size_t)SUPER * MAX_SELECT + 8)) || (rc = W.w_cnt.ensure(4 * SUPER + 16)))
+        return rc;
+    // (the uploads below read host memory of this frame: no return, early ones included, leaves one in flight)
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
+    HIP_TRY(hipMemcpyAsync(B.q.p, req.tokens, total * dim * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(B.meta.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(B.ctr.p, 0, 16, s));
+    if ((rc = prep_exact_queries(ix, W, s, B.q.p, (uint32_t)total, dim))) return rc;
+    uint32_t* d_status = SearchFlags(W.w_flags.p, total).status;
+    const uint64_t* d_mask;
+    if ((rc = stage_mask(B.mask_in, mask_src(r), s, &d_mask))) return rc;
+    const uint32_t* d_rowmask;
+    if ((rc = eligibility_mask(ix, W, s, d_mask, r.mask_bits, &d_rowmask))) return rc;
+    const float* rows = rows_f32(ix);                              // (a SPLIT store converts back: DESIGN.md 4.3)
+    if (!rows && n) return fail(VDB_ERR_DEVICE, "the row store is unusable");
+    unsigned long long* ctr = reinterpret_cast<unsigned long long*>(B.ctr.p);
+
+    size_t chunks = 0;
+    for (size_t q0 = 0; q0 < nq; q0 += G, ++chunks) {
+        const uint32_t g = (uint32_t)std::min(G, nq - q0);
+        HIP_TRY(hipMemsetAsync(B.table.p, 0xff, (size_t)g * n_codes * vdb::MAXSIM_MAX_TOKENS * 4, s));
+        vdb::MaxsimScanParams sp{rows, ix->ld, ix->dim, n, ix->metric, ix->d_nd, d_rowmask, ix->d_row_ids, d_codes, codes_len,
+                                 (uint32_t)n_codes, W.w_qp.p, W.w_qnorm.p, B.meta.p, (uint32_t)q0, B.table.p, d_status, ctr};
+        vdb::launch_maxsim_scan(sp, g, s);
+        vdb::launch_maxsim_fold(vdb::MaxsimFoldParams{B.table.p, (uint32_t)n_codes, B.meta.p, (uint32_t)q0, B.keys.p, d_status, ctr + 1}, g, s);
+        // (the keys are (score, code) pairs, no (distance, id rank) pairs: the select only sorts them, maxsim_emit_kernel reads them)
+        vdb::SelectParams mp{};
+        mp.kk = (uint32_t)kmax; mp.out_keys = W.w_exsel.p; mp.out_stride = MAX_SELECT; mp.out_cnt = W.w_cnt.p;
+        mp.keys = B.keys.p; mp.stride = n_codes; mp.counts = nullptr; mp.n_fixed = (uint32_t)n_codes; mp.cap = (uint32_t)n_codes;
+        vdb::launch_select(mp, g, s);
+        vdb::MaxsimEmitParams ep{W.w_exsel.p, W.w_cnt.p, MAX_SELECT, B.meta.p + nq + 1, (uint32_t)q0,
+                                 B.outcodes.p, B.outs.p, B.outc.p, (uint32_t)kmax, d_status};
+        vdb::launch_maxsim_emit(ep, g, s);
+        HIP_TRY(hipGetLastError());
+    }
+
+    // ---- one read of the status words and the counters
+    uint32_t status[4] = {0, 0, 0, 0};
+    uint64_t counters[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(status, d_status, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(counters, B.ctr.p, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (status[0] & vdb::ST_ZERO_QUERY) return fail_zero_vector();
+    if (status[3] & 1u) return fail(VDB_ERR_INVALID_ARGUMENT, "the column holds a code at or above n_codes = %zu", n_codes);
+    if (status[0] & vdb::ST_NAN) return fail_nan();
+    if (status[3] & 2u) return fail(VDB_ERR_DEVICE, "internal error: an empty key among the selected documents");
+
+    // ---- the copy-out: per-query k is a prefix of the answer for the largest k
+    std::vector<uint32_t> cnt(nq);
+    std::vector<int32_t> codes(nq * kmax);
+    std::vector<float> scores(nq * kmax);
+    HIP_TRY(hipMemcpyAsync(cnt.data(), B.outc.p, nq * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(codes.data(), B.outcodes.p, nq * kmax * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(scores.data(), B.outs.p, nq * kmax * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    uint64_t returned = 0;
+    for (size_t b = 0; b < nq; ++b) {
+        const size_t c = std::min<size_t>(cnt[b], meta[nq + 1 + b]);
+        for (size_t i = 0; i < c; ++i) {
+            req.out_codes[b * r.kstride + i] = codes[b * kmax + i];
+            req.out_scores[b * r.kstride + i] = scores[b * kmax + i];
+        }
+        r.counts[b] = c;
+        returned += c;
+    }
+    // (the scan counts the eligible rows once per chunk, in its y = 0 workgroups: every query of the call scanned as many)
+    st[2] = chunks; st[3] = chunks ? counters[0] / chunks * nq : 0; st[4] = counters[1]; st[5] = returned;
+    return VDB_OK;
+}
+
 }  // namespace vdbi

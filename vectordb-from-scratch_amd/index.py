@@ -513,6 +513,69 @@ class GpuFlatIndex(Index):
         if rc:
             _raise(rc)
 
+    # ---- late-interaction (MaxSim) search (include/vdb_flat.h vdb_flat_search_batch_maxsim; no reference counterpart)
+    MAXSIM_MAX_TOKENS = 32
+
+    def search_batch_maxsim(self, token_lists, k, table, slot, n_codes, id_mask=None, mask_bits=0, compiled_mask=None):
+        """The k best DOCUMENTS of multi-vector queries: token_lists[b] is the [T_b, dim] block of query b's token vectors
+        (1 <= T_b <= 32), a document is a code >= 0 of column `slot` of `table` (a MetaTable) with at least one live, admitted
+        row, and its score is the f32 sum over the tokens, in order, of the document's nearest row to that token (the distances
+        search_batch_arrays reports).  Rows without a code are left out.  n_codes bounds the column's codes.  k an int or a
+        per-query array; the masks as in search_batch_distinct.  Returns (codes i32 [nq, kmax], scores f32 [nq, kmax], counts),
+        best (lowest) score first, ties to the lower code."""
+        if compiled_mask is not None and id_mask is not None:
+            raise ValueError("pass id_mask or compiled_mask, not both")
+        blocks = [np.ascontiguousarray(t, dtype=np.float32) for t in token_lists]
+        nq = len(blocks)
+        if any(t.ndim != 2 for t in blocks) or len({t.shape[1] for t in blocks}) > 1:
+            raise ValueError("every query is a 2-d block of token vectors of one dimension")
+        dim = blocks[0].shape[1] if blocks else 0
+        tokens = np.ascontiguousarray(np.concatenate(blocks)) if blocks else np.zeros((0, 0), dtype=np.float32)
+        offsets = np.zeros(nq + 1, dtype=np.uintp)
+        offsets[1:] = np.cumsum([t.shape[0] for t in blocks], dtype=np.uintp)
+        if np.isscalar(k):
+            ks_ptr, kscalar, kmax = None, int(k), int(k)
+        else:
+            ks = np.ascontiguousarray(k, dtype=np.uintp)
+            if ks.shape != (nq,):
+                raise ValueError(f"k must be a scalar or hold one value per query ({nq}), not {ks.shape}")
+            ks_ptr = ks.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t))
+            kscalar, kmax = 0, int(ks.max()) if ks.size else 0
+        kstride = max(kmax, 1)
+        out_c = np.full((nq, kstride), -1, dtype=np.int32)
+        out_s = np.zeros((nq, kstride), dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uintp)
+        szp = ctypes.POINTER(ctypes.c_size_t)
+        head = (self._h, _fp(tokens), offsets.ctypes.data_as(szp), nq, dim, ks_ptr, kscalar, table._t if table is not None else None,
+                int(slot), int(n_codes))
+        tail = (kstride, out_c.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fp(out_s), counts.ctypes.data_as(szp))
+        if compiled_mask is not None:
+            rc = self._L.vdb_flat_search_batch_maxsim_filtered(*head, compiled_mask.handle, *tail)
+        else:
+            mask_ptr = None
+            if id_mask is not None:
+                m = np.ascontiguousarray(id_mask, dtype=np.uint64)
+                mask_ptr = _u64p(m)
+            rc = self._L.vdb_flat_search_batch_maxsim(*head, mask_ptr, int(mask_bits), *tail)
+        if rc:
+            _raise(rc)
+        return out_c, out_s, counts
+
+    def maxsim_stats(self):
+        """The last search_batch_maxsim: [0] queries, [1] tokens, [2] chunks of queries, [3] eligible rows scanned, summed over
+        the queries, [4] documents seen, summed over the queries, [5] documents returned, [6], [7] 0."""
+        out = (ctypes.c_uint64 * 8)()
+        rc = self._L.vdb_flat_maxsim_stats(self._h, out)
+        if rc:
+            _raise(rc)
+        return [int(x) for x in out]
+
+    def debug_set_maxsim_table_cap(self, nbytes):
+        """Tests: the bytes of score table and keys one chunk of queries may take (0: the default, 256 MiB).  Same answers."""
+        rc = self._L.vdb_flat_debug_set_maxsim_table_cap(self._h, int(nbytes))
+        if rc:
+            _raise(rc)
+
     # ---- diverse top-k, MMR on the device (include/vdb_flat.h vdb_flat_search_batch_mmr; no reference counterpart)
     def search_batch_mmr(self, queries, k, candidates, lam, id_mask=None, mask_bits=0, compiled_mask=None, ks=None):
         """k results that are not all the same thing: the `candidates` nearest rows of each query (what search_batch_arrays

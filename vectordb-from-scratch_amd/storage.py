@@ -853,6 +853,50 @@ class VectorStore:
                 cm.release()
         return [self._map([(int(out_ids[b, i]), dists[b, i]) for i in range(int(counts[b]))]) for b in range(len(queries))]
 
+    # ---- "the k best documents for a multi-vector query" (GpuFlatIndex.search_batch_maxsim; no reference counterpart)
+    def search_late_interaction(self, query_tokens, k, field, flt=None):
+        """Late interaction (MaxSim, the scoring of ColBERT-style models): the rows that share a value of metadata field `field`
+        are one document, its score is the sum over the query's token vectors of the distance of the document's nearest row to
+        that token, and the k documents with the lowest score come back as (field value, score) pairs, best first.  Rows without
+        the field belong to no document."""
+        return self.search_late_interaction_batch([query_tokens], k, field, flt)[0]
+
+    def search_late_interaction_batch(self, queries, k, field, flt=None):
+        """search_late_interaction for several queries (each a list of Vectors, at most 32) in one device call.  flt is a
+        PRE-filter on the rows.  With the device filter on the field's resident column is read and flt is compiled on the
+        device when it fits the program limits; with it off the column is sent up for this call alone and flt is compiled by
+        compile_filter -- as search_groups_batch does."""
+        if not isinstance(self._index, GpuFlatIndex):
+            raise ValueError("search_late_interaction needs a GpuFlatIndex")
+        queries = [list(q) for q in queries]
+        for q in queries:
+            if not 1 <= len(q) <= GpuFlatIndex.MAXSIM_MAX_TOKENS:
+                raise ValueError(f"a query has between 1 and {GpuFlatIndex.MAXSIM_MAX_TOKENS} token vectors")
+        col = self._cols.get(field)
+        if self.is_empty() or not queries or col is None or not col.values:
+            return [[] for _ in queries]
+        for q in queries:
+            for t in q:
+                self._check_dim(t)
+        blocks = [np.stack([t.data for t in q]).astype(np.float32) for q in queries]
+        cm = self.compile_filter_device(flt) if flt is not None and self._table is not None else None
+        mask, bits = self.compile_filter(flt) if flt is not None and cm is None else (None, 0)
+        own = None
+        try:
+            table, slot = self._table, self._slots.get(field, 0)
+            if table is None:
+                table = own = MetaTable(self._index._device)
+                own.set_codes(0, 0, col.view(max(self._next_id, 1)))
+                slot = 0
+            codes, scores, counts = self._index.search_batch_maxsim(blocks, int(k), table, slot, len(col.values), id_mask=mask,
+                                                                    mask_bits=bits, compiled_mask=cm)
+        finally:
+            if cm is not None:
+                cm.release()
+            if own is not None:
+                own.close()
+        return [[(col.values[int(codes[b, i])], float(scores[b, i])) for i in range(int(counts[b]))] for b in range(len(queries))]
+
     # ---- "the best passages of the k nearest documents" (GpuFlatIndex.search_batch_per_group; no reference counterpart)
     def search_groups(self, query, k, field, group_size, flt=None):
         """The k nearest GROUPS of rows that share a value of metadata field `field`, nearest first, each with its up to
