@@ -712,7 +712,7 @@ int vdb_flat_debug_set_discover_route(vdb_flat_index *h, int mode);
  * Cosine is VDB_ERR_INVALID_VECTOR; a code >= n_codes met at a live admitted row is VDB_ERR_INVALID_ARGUMENT; a NaN d(t, x) at an
  * eligible row, or a NaN score (+inf and -inf meeting in the sum), is VDB_ERR_NAN.  On any error nothing is written.  Locking,
  * flushing, the table's lock and the stream ordering are those of vdb_flat_search_batch_distinct.
- * Not built: a bf16 / MFMA screening pass with a certificate per (token, document), sharded handles (refused as in (6)), HNSW
+ * Not built: sharded handles (refused as in (6)), HNSW
  * stores, device-pointer and ticket forms, stored ids as tokens, the best row per token, the C++ host mirror.
  * How (csrc/kernels_maxsim.hip): one thread per row reads its row once per query and folds it against all T_b
  * tokens in that pass (32 accumulator chains in registers, the token elements through scalar loads); the ordered distances go
@@ -722,6 +722,17 @@ int vdb_flat_debug_set_discover_route(vdb_flat_index *h, int mode);
  * chunks that keep both under 256 MiB (vdb_flat_debug_set_maxsim_table_cap lowers that, for tests: 0 restores it).
  * vdb_flat_maxsim_stats describes the last call: [0] queries, [1] tokens, [2] chunks, [3] eligible rows scanned, summed over the
  * queries, [4] documents seen, summed over the queries, [5] documents returned, [6] [7] 0.
+ * THE SCREENED ROUTE, vdb_flat_set_maxsim_screen(h, 1) (0, the default, is the route above, untouched): the same answer bit for
+ * bit -- codes, score bits, counts, errors -- by another plan (csrc/kernels_maxsim_screen.hip).  The bf16 matrix
+ * cores rank every (token, row) pair, the screening tier's certificate turns the smallest ranking score of a (token, document)
+ * into a lower bound of m(t, c), their f32 left fold L(c) is a lower bound of score(c), and the exact scan folds only the rows of
+ * the k documents with the smallest L and then of every document with L(c) <= e_k, the k-th exact score so far.  A query with a
+ * token whose norm lies outside [2^-40, 2^40], or that meets a row norm above 2^40 or a ranking score that is not finite at an
+ * eligible row, or any query of an index that holds a tiny-norm row under Cosine, is NOT SCREENED: the exact scan folds all its
+ * rows, as above.  Then vdb_flat_maxsim_stats: [3] the rows the exact scans folded, summed over the queries, [6] the queries
+ * answered by the screened route, [7] the documents re-scored exactly, summed over the screened queries.  Sharded handles, HNSW
+ * stores and a SPLIT store behave as above.  vdb_flat_debug_maxsim_lower_bounds (tests): L(q, c) of the last screened call,
+ * [nq][n_codes], NaN for a code without a document and for a query that was not screened.
  */
 #define VDB_MAXSIM_MAX_TOKENS 32
 #define VDB_MAXSIM_MAX_K 1024
@@ -735,6 +746,8 @@ int vdb_flat_search_batch_maxsim_filtered(vdb_flat_index *h, const float *tokens
                                           int32_t *out_codes, float *out_scores, size_t *out_counts);
 int vdb_flat_maxsim_stats(const vdb_flat_index *h, uint64_t out[8]);
 int vdb_flat_debug_set_maxsim_table_cap(vdb_flat_index *h, size_t bytes);
+int vdb_flat_set_maxsim_screen(vdb_flat_index *h, int on);
+int vdb_flat_debug_maxsim_lower_bounds(vdb_flat_index *h, float *out /* [nq][n_codes] */, size_t nq, size_t n_codes);
 
 /*
  * DIVERSE TOP-K (MAXIMAL MARGINAL RELEVANCE): k results that are not all the same thing (no reference counterpart; a caller would

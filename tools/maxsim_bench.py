@@ -17,8 +17,15 @@ identical: codes, score bits and counts.  Per query of the maxsim arm the file a
 contract) over the time against 39.3 T operations/s (256 CUs x 64 lanes x 2.4 GHz), and says which of the two floors is higher.
 A record, not a bar: no pass / fail time is attached.
 
+--screen-out FILE runs the SCREENED route instead (vdb_flat_set_maxsim_screen, DESIGN.md 4.19 "screened route"): at both shapes
+and on two kinds of data -- the uniform i.i.d. rows above, and documents that are clusters (a gaussian centre per document, its 16
+rows 0.1 gaussian around it, every query's tokens around the centre of one document) -- the exact arm (switch off: the parent
+commit's code, the yardstick) and the screened arm alternate on one handle; the file holds each arm's time per call, the
+screened arm's stats [6] (queries screened) and [7] (documents re-scored, summed over the queries) and the documents.  The
+answers must be identical.
+
     python tools/maxsim_bench.py [--rows N] [--queries B] [--tokens T] [--k K] [--rounds R] [--composed-queries C]
-                                 [--out profiles/maxsim_bench.json]"""
+                                 [--out profiles/maxsim_bench.json] [--screen-out profiles/maxsim_screen_bench.json]"""
 import argparse
 import json
 import os
@@ -141,6 +148,57 @@ def shape(vdb, a, metric, name, d):
     return doc
 
 
+def screen_shape(vdb, a, metric, name, d, data):
+    dev = torch.device("cuda", 0)
+    n, B, T, k = a.rows // PER_DOC * PER_DOC, a.queries, a.tokens, a.k
+    n_docs = n // PER_DOC
+    g = torch.Generator(device=dev).manual_seed(31)
+    ix = vdb.GpuFlatIndex(metric, keep_host_copy=False)
+    rng = np.random.default_rng(37)
+    if data == "clustered":
+        centres = torch.randn((n_docs, d), device=dev, generator=g, dtype=torch.float32)
+        toks = [np.ascontiguousarray(centres[int(c)].cpu().numpy() + 0.1 * rng.standard_normal((T, d)), dtype=F32) for c in rng.integers(0, n_docs, B)]
+    else:
+        toks = [np.ascontiguousarray(x) for x in rng.random((B, T, d), dtype=F32)]
+    chunk = 125_000 // PER_DOC * PER_DOC
+    for r0 in range(0, n, chunk):
+        m = min(chunk, n - r0)
+        if data == "clustered":
+            rows = centres[r0 // PER_DOC:(r0 + m) // PER_DOC].repeat_interleave(PER_DOC, dim=0) + 0.1 * torch.randn((m, d), device=dev, generator=g, dtype=torch.float32)
+        else:
+            rows = torch.rand((m, d), device=dev, generator=g, dtype=torch.float32)
+        ix.add_bulk_device(rows.data_ptr(), m, d, first_id=r0)
+        torch.cuda.synchronize()
+    ix.flush()
+    del rows
+    table = vdb.MetaTable(0)
+    table.set_codes(0, 0, (np.arange(n) // PER_DOC).astype(I32))
+
+    def call(on):
+        ix.set_maxsim_screen(on)
+        t0 = time.perf_counter()
+        res = ix.search_batch_maxsim(toks, k, table, 0, n_docs)
+        return (time.perf_counter() - t0) * 1e3, res, ix.maxsim_stats()
+
+    before = clocks()
+    for _ in range(a.warmup):
+        call(False), call(True)
+    te, ts = [], []
+    for _ in range(a.rounds):
+        t, re_, _ = call(False)
+        te.append(t)
+        t, rs, st = call(True)
+        ts.append(t)
+    for x, y in zip(re_, rs):
+        assert np.array_equal(np.asarray(x).view(U32) if x.dtype == F32 else x, np.asarray(y).view(U32) if y.dtype == F32 else y)
+    table.close()
+    return {"shape": name, "data": data, "rows": n, "dim": d, "metric": name.split()[-1], "queries": B, "tokens_per_query": T, "k": k,
+            "rows_per_document": PER_DOC, "documents": n_docs, "rounds": a.rounds, "warmup": a.warmup, "clocks_before": before, "clocks_after": clocks(),
+            "exact_ms": summary(te), "screened_ms": summary(ts), "screened_over_exact": round(med(ts) / med(te), 3),
+            "queries_screened": st[6], "documents_rescored": st[7], "documents_rescored_per_query": round(st[7] / max(st[6], 1), 1),
+            "rows_folded_exactly": st[3], "answers_identical": True}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -152,9 +210,18 @@ def main():
     ap.add_argument("--composed-rounds", type=int, default=1)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default="")
+    ap.add_argument("--screen-out", default="")
     a = ap.parse_args()
     vdb = load_package()
     vdb.build()
+    if a.screen_out:
+        doc = {"tool": "tools/maxsim_bench.py --screen-out",
+               "shapes": [screen_shape(vdb, a, m, name, d, data) for data in ("iid", "clustered")
+                          for m, name, d in ((vdb.DistanceMetric.DotProduct, "1M x 128 dot", 128), (vdb.DistanceMetric.Cosine, "1M x 768 cosine", 768))]}
+        with open(a.screen_out, "w") as f:
+            f.write(json.dumps(doc, indent=1) + "\n")
+        print(json.dumps(doc))
+        return
     doc = {"tool": "tools/maxsim_bench.py",
            "shapes": [shape(vdb, a, vdb.DistanceMetric.DotProduct, "1M x 128 dot", 128), shape(vdb, a, vdb.DistanceMetric.Cosine, "1M x 768 cosine", 768)]}
     if a.out:

@@ -23,6 +23,7 @@ SYMBOLS = [
     "vdb_flat_debug_set_recommend_best_route",
     "vdb_flat_discover_batch", "vdb_flat_discover_batch_filtered", "vdb_flat_discover_stats", "vdb_flat_discover_depth", "vdb_flat_debug_set_discover_route",
     "vdb_flat_search_batch_maxsim", "vdb_flat_search_batch_maxsim_filtered", "vdb_flat_maxsim_stats", "vdb_flat_debug_set_maxsim_table_cap",
+    "vdb_flat_set_maxsim_screen", "vdb_flat_debug_maxsim_lower_bounds",
     "vdb_flat_search_batch_mmr", "vdb_flat_search_batch_mmr_filtered", "vdb_flat_mmr_stats",
     "vdb_flat_search_batch_distinct", "vdb_flat_search_batch_distinct_filtered", "vdb_flat_distinct_stats", "vdb_flat_distinct_depth",
     "vdb_flat_search_batch_grouped", "vdb_flat_search_batch_grouped_filtered", "vdb_flat_grouped_stats", "vdb_flat_debug_group_plan",
@@ -196,6 +197,8 @@ def lib():
     L.vdb_flat_search_batch_maxsim_filtered.argtypes = [vp, fp, szp, sz, sz, szp, sz, vp, c.c_uint32, sz, vp, sz, c.POINTER(c.c_int32), fp, szp]
     L.vdb_flat_maxsim_stats.argtypes = [vp, u64p]
     L.vdb_flat_debug_set_maxsim_table_cap.argtypes = [vp, sz]
+    L.vdb_flat_set_maxsim_screen.argtypes = [vp, c.c_int]
+    L.vdb_flat_debug_maxsim_lower_bounds.argtypes = [vp, fp, sz, sz]
     L.vdb_flat_search_batch_mmr.argtypes = [vp, fp, sz, sz, szp, sz, sz, fp, c.c_float, u64p, sz, sz, u64p, fp, fp, szp]
     L.vdb_flat_search_batch_mmr_filtered.argtypes = [vp, fp, sz, sz, szp, sz, sz, fp, c.c_float, vp, sz, u64p, fp, fp, szp]
     L.vdb_flat_mmr_stats.argtypes = [vp, u64p]

@@ -843,4 +843,54 @@ struct MaxsimEmitParams {
 };
 void launch_maxsim_emit(const MaxsimEmitParams& p, uint32_t n_queries, hipStream_t s);
 
+// ---- the SCREENED route (vdb_flat_set_maxsim_screen, kernels_maxsim_screen.hip, DESIGN.md 4.19 "screened route")
+// The candidate instance of the scan: the same kernel body, but a row is folded only when bit `code` of marked[y * mark_words ..]
+// is set; *rows_scanned += the rows folded, by every y.  The table is NOT reset between two candidate scans of a chunk.
+void launch_maxsim_scan_marked(const MaxsimScanParams& p, const uint32_t* marked, uint32_t mark_words, uint32_t n_queries, hipStream_t s);
+// The certificate constants of one token (CertConsts of kernels_exact.h, in a form the host can size): ok = 0 when the token
+// cannot be certified -- its query is then not screened.
+struct MaxsimTokenCert { double a, b, tslack, lhs_scale; uint32_t square, ok; };
+// One thread per token of the call: cert[t] = cert_consts(cert_in, t, qnorm[t]), ok also cleared for a norm above 2^40 or NaN;
+// a token that is not ok sets unscreened[colmap[t] >> 8].  cert_in carries metric, ld, eps_coef, nd2max_bits, qerr, c_acc, lb_scores.
+struct MaxsimCertParams {
+    RerankParams cert_in; const float* qnorm; const uint32_t* colmap; uint32_t n_tokens, n_queries;
+    MaxsimTokenCert* cert; uint32_t* unscreened;
+};
+void launch_maxsim_cert(const MaxsimCertParams& p, hipStream_t s);
+// The screening pass: ranking scores of a tile of 128 rows against 256 token COLUMNS (one image pass of the bf16 block query_prep
+// wrote: qb, with qg under Dot / Euclid) on v_mfma_f32_32x32x16_bf16, the LOWER-BOUND score fma(-qg, margin, fma(acc, alpha,
+// beta)) when margin is not null.  Column t of the call belongs to query colmap[t] >> 8, token slot colmap[t] & 255 (all ones:
+// unused); only queries [q0, q0 + nq) are served.  table[((q - q0) * n_codes + c) * 32 + slot] takes the atomicMin of the ordered
+// score over the eligible rows (the rule of MaxsimScanParams), one atomic per run of equal codes inside a half tile of 64 rows.
+// A score that is not finite at an eligible row, or a row norm above 2^40, sets unscreened[q] and enters the table as 0.
+struct MaxsimScreenParams {
+    const float* rows; uint32_t ld, n_rows; const float* nd; const float* alpha; const float* beta; const float* margin;
+    const uint32_t* rowmask; const uint64_t* row_ids; const int32_t* codes; uint64_t codes_len; uint32_t n_codes;
+    const uint16_t* qb; const float* qg; const uint32_t* colmap;
+    uint32_t pass0, q0, nq;
+    uint32_t* table; uint32_t* unscreened; uint32_t* status;
+};
+void launch_maxsim_screen(const MaxsimScreenParams& p, uint32_t n_pass, hipStream_t s);
+// One thread per (query y, code c): lb[(q0 + y) * n_codes + c] = ordered L(c), the f32 left fold in token order of the per-token
+// lower bounds cert_lower_bound(cert[token], table entry) -- all ones for a code without an eligible row -- and keys[y * n_codes
+// + c] = L << 32 | c (EMPTY_KEY for no document).  A NaN L counts as -inf.  *docs_seen += the documents.
+struct MaxsimBoundParams {
+    const uint32_t* table; uint32_t n_codes; const uint32_t* offs; uint32_t q0; const MaxsimTokenCert* cert; int metric;
+    uint32_t* lb; uint64_t* keys; unsigned long long* docs_seen;
+};
+void launch_maxsim_bound(const MaxsimBoundParams& p, uint32_t n_queries, hipStream_t s);
+// The candidate bitmaps, marked[y * mark_words + (c >> 5)] bit c & 31.  sel / sel_cnt: the select's ascending keys and counts
+// (stride sel_stride), kk the call's largest k.
+//   round 1: the codes of the first min(sel_cnt[y], kk) keys (the kk smallest lower bounds); every word all ones for an
+//            unscreened query.  The caller zeroes the bitmap first.
+//   round 2: sel holds EXACT keys; e_k = the score word of key kk - 1 (all ones with fewer than kk keys); a code is marked when
+//            it is a document, lb <= e_k as ordered integers, and round 1 did not mark it.  Nothing for an unscreened query.
+// *rescored += the marked documents of screened queries.
+struct MaxsimMarkParams {
+    const uint64_t* sel; const uint32_t* sel_cnt; uint32_t sel_stride, kk;
+    const uint32_t* lb; uint32_t n_codes, q0; const uint32_t* unscreened;
+    uint32_t* marked; uint32_t mark_words; unsigned long long* rescored;
+};
+void launch_maxsim_mark(const MaxsimMarkParams& p, int round, uint32_t n_queries, hipStream_t s);
+
 }  // namespace vdb

@@ -445,6 +445,23 @@ __device__ __forceinline__ bool cert_test(const RerankParams& p, uint32_t q, flo
     return cert_eval(cert_consts(p, q, qn), T, ek);
 }
 
+// The certificate read the other way (late-interaction screening): every row of a set has ranking score >= s.
+// cert_eval(c, s, ek) holds exactly for the ek with lhs(ek) < B := a + b (s - |s| tslack), and each such ek lies strictly below
+// the exact distance of every row of the set; so that distance is at least the supremum of those ek: B itself, or under Euclid
+// sqrt(B / lhs_scale) (0 for B <= 0: the reference's distance is a square root).  Cosine's distance is 1 - clamp(sim), never
+// above 2.  Plain f64, then rounded towards -inf to f32: a smaller bound is safe.  NaN in, NaN out.
+__device__ __forceinline__ float cert_lower_bound(const CertConsts& c, int metric, float s) {
+    double B = c.a + c.b * ((double)s - fabs((double)s) * c.tslack);
+    if (c.square) B = B > 0.0 ? sqrt(B / c.lhs_scale) * (1.0 - 1.0e-15) : 0.0;   // (the f64 sqrt and division: an ulp each)
+    if (metric == COSINE && B > 2.0) B = 2.0;
+    float f = (float)B;
+    if ((double)f > B) {
+        if (f == 0.0f) f = __uint_as_float(0x80000001u);
+        else f = __uint_as_float(__float_as_uint(f) + (f > 0.0f ? (uint32_t)-1 : 1u));
+    }
+    return f;
+}
+
 // The inverse of cert_test: the smallest score T* such that cert_test(T) holds for every T > T*.  Every row whose
 // ranking score exceeds it is PROVEN to lie beyond the k-th exact distance ek, so a filter pass with T* (rounded up) as
 // its threshold keeps every row that can still matter (the "re-threshold" pass of vdb_flat.cpp).

@@ -13,6 +13,8 @@
 //     lane of its run), after which the LAST lane of a run holds the run's minima and is the only one that issues atomics.  A
 //     document of 16 adjacent rows then costs one atomic per token, not 16; a store of one-row documents skips the step.  The
 //     table is the same with or without it.  Lanes without an eligible row read no row; they stay in the wave for the shuffles.
+//     maxsim_scan_marked_kernel is the same body for the screened route (kernels_maxsim_screen.hip): a row takes part only when
+//     its code's bit is set in the query's candidate bitmap, and the rows folded are counted for every query.
 //   - maxsim_fold_kernel: one thread per (query, code).  An entry whose token 0 is untouched (all ones: no distance maps there,
 //     a NaN raises ST_NAN in the scan) is no document and gives EMPTY_KEY; else the T minima are folded left in token order and
 //     the key is ordered(score) << 32 | code: ascending keys are the answer's order, ties go to the lower code.
@@ -35,7 +37,9 @@ __device__ __forceinline__ uint32_t ms_uniform(uint32_t v) { return (uint32_t)__
 // ---------------------------------------------------------------------------------------------
 // the row scan
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(MS_THREADS) void maxsim_scan_kernel(MaxsimScanParams p) {
+// (CAND: the candidate instance of the screened route -- a row takes part only when its code's bit is set in the query's bitmap)
+template <bool CAND>
+__device__ __forceinline__ void maxsim_scan_body(const MaxsimScanParams& p, const uint32_t* marked, uint32_t mark_words) {
     const uint32_t row = blockIdx.x * MS_THREADS + threadIdx.x, lane = threadIdx.x & 63u, y = blockIdx.y;
     const uint32_t t0 = ms_uniform(p.offs[p.q0 + y]);
     const uint32_t T0 = ms_uniform(p.offs[p.q0 + y + 1]) - t0;
@@ -54,6 +58,7 @@ __global__ __launch_bounds__(MS_THREADS) void maxsim_scan_kernel(MaxsimScanParam
             }
         }
     }
+    if (CAND && code != MS_NO_CODE && !((marked[(size_t)y * mark_words + (code >> 5)] >> (code & 31u)) & 1u)) code = MS_NO_CODE;
     const bool mine = code != MS_NO_CODE;
     const unsigned long long active = __ballot(mine);
     // (every atomic of this kernel stands BEHIND the fold: a store in front of it would make the token loads vector loads)
@@ -85,7 +90,7 @@ __global__ __launch_bounds__(MS_THREADS) void maxsim_scan_kernel(MaxsimScanParam
     }
     if (nan) atomicOr(p.status, ST_NAN);
     if (beyond) atomicOr(p.status + 3, 1u);
-    if (y == 0 && lane == 0) atomicAdd(p.rows_scanned, (unsigned long long)__popcll(active));
+    if ((CAND || y == 0) && lane == 0) atomicAdd(p.rows_scanned, (unsigned long long)__popcll(active));
 
     // ---- one set of minima per run of equal codes: a segmented prefix minimum, lane by lane towards the run's last lane
     const uint32_t before = __shfl_up(code, 1u);
@@ -109,6 +114,17 @@ __global__ __launch_bounds__(MS_THREADS) void maxsim_scan_kernel(MaxsimScanParam
         for (int j = 0; j < (int)MAXSIM_MAX_TOKENS; ++j)
             if (j < (int)T) atomicMin(e + j, o[j]);
     }
+}
+
+__global__ __launch_bounds__(MS_THREADS) void maxsim_scan_kernel(MaxsimScanParams p) { maxsim_scan_body<false>(p, nullptr, 0); }
+__global__ __launch_bounds__(MS_THREADS) void maxsim_scan_marked_kernel(MaxsimScanParams p, const uint32_t* marked, uint32_t mark_words) {
+    maxsim_scan_body<true>(p, marked, mark_words);
+}
+
+void launch_maxsim_scan_marked(const MaxsimScanParams& p, const uint32_t* marked, uint32_t mark_words, uint32_t n_queries, hipStream_t s) {
+    if (!p.n_rows || !n_queries) return;
+    hipLaunchKernelGGL(maxsim_scan_marked_kernel, dim3((p.n_rows + MS_THREADS - 1) / MS_THREADS, n_queries), dim3(MS_THREADS), 0, s, p,
+                       marked, mark_words);
 }
 
 void launch_maxsim_scan(const MaxsimScanParams& p, uint32_t n_queries, hipStream_t s) {

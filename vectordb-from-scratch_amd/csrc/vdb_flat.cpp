@@ -1146,6 +1146,36 @@ int vdb_flat_debug_set_maxsim_table_cap(vdb_flat_index* ix, size_t bytes) {
     });
 }
 
+int vdb_flat_set_maxsim_screen(vdb_flat_index* ix, int on) {
+    return guarded([&]() -> int {
+    if (!ix) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (ix->multi) return refuse_multi("vdb_flat_set_maxsim_screen");
+    if (on != 0 && on != 1) return fail(VDB_ERR_INVALID_ARGUMENT, "the screen switch is 0 or 1, not %d", on);
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->maxsim_screen = on;
+    return VDB_OK;
+    });
+}
+
+int vdb_flat_debug_maxsim_lower_bounds(vdb_flat_index* ix, float* out, size_t nq, size_t n_codes) {
+    return guarded([&]() -> int {
+    if (!ix || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (ix->multi) return refuse_multi("vdb_flat_debug_maxsim_lower_bounds");
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (in_flight(ix)) return refuse_in_flight();
+    if (!ix->maxsim_lb_codes || nq != ix->maxsim_unscreened.size() || n_codes != ix->maxsim_lb_codes)
+        return fail(VDB_ERR_INVALID_ARGUMENT, "the last late-interaction search left no lower bounds of %zu queries x %zu codes", nq, n_codes);
+    int rc;
+    if ((rc = set_device(ix))) return rc;
+    std::vector<uint32_t> lb(nq * n_codes);
+    HIP_TRY(hipMemcpy(lb.data(), ix->msw.lb.p, lb.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t b = 0; b < nq; ++b)
+        for (size_t c = 0; c < n_codes; ++c)               // (all ones, "no document", reads back as a NaN; so does an unscreened query)
+            out[b * n_codes + c] = vdb::ordered_to_f32(ix->maxsim_unscreened[b] ? 0xffffffffu : lb[b * n_codes + c]);
+    return VDB_OK;
+    });
+}
+
 // ---- diverse top-k (no reference counterpart; search_batch_host with r.mmr)
 // The checks of include/vdb_flat.h "DIVERSE TOP-K" item 8, in its order, before any lock or device work.  *done: the call is
 // answered (an empty index, or no query asks for a row).

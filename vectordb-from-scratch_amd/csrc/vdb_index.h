@@ -136,6 +136,10 @@ struct MaxsimWs {
     vdbi::DevBuf<uint32_t> meta, table, outc;
     vdbi::DevBuf<int32_t> outcodes;
     vdbi::DevBuf<uint64_t> keys, ctr, mask_in;
+    // the screened route: column -> (query, token slot), the per-query "not screened" flags, the lower bounds L(q, c) of the whole
+    // call (ordered), the candidate bitmaps of one chunk, the certificate constants per token
+    vdbi::DevBuf<uint32_t> colmap, unscreened, lb, marked;
+    vdbi::DevBuf<vdb::MaxsimTokenCert> cert;
 };
 // A late-interaction request as the caller passed it, checked by maxsim_check: query b owns tokens [offsets[b], offsets[b + 1])
 // of tokens [total][dim]; the answers go to out_codes / out_scores [nq][kstride] and the batch's counts.
@@ -330,6 +334,9 @@ struct vdb_flat_index {
     int discover_route = 0;                                 // vdb_flat_debug_set_discover_route (tests): 0 auto, 1 lists first, 2 scan only
     uint64_t maxsim_stats[8] = {0};                         // vdb_flat_maxsim_stats: counters of the last late-interaction search
     MaxsimWs msw;                                           // its device buffers
+    int maxsim_screen = 0;                                  // vdb_flat_set_maxsim_screen: 1 = the screened route
+    std::vector<uint32_t> maxsim_unscreened;                // the last screened call: per query, 1 = answered by the plain scan
+    size_t maxsim_lb_codes = 0;                             // ... and its n_codes: msw.lb holds [maxsim_unscreened.size()][maxsim_lb_codes] bounds; 0 = none
     size_t maxsim_table_cap = 0;                            // vdb_flat_debug_set_maxsim_table_cap (tests): bytes of table and keys per chunk, 0 = MAXSIM_TABLE_CAP
     uint64_t distinct_stats[8] = {0};                       // vdb_flat_distinct_stats: counters of the last search by group (also on a sharded parent)
     DistinctWs dws;                                         // its device buffers (a sharded parent's live on devices[0])

@@ -109,18 +109,21 @@ static vdb::SelectParams emit_select_params(const Index* ix, Workspace& W, size_
 }
 
 // The queries of an exact route (sparse, grouped): the zero-padded block and the exact-order norms in W, the status block cleared
-// in front; query_prep raises ST_ZERO_QUERY.  No bf16 image and no per-query flags.
-static int prep_exact_queries(Index* ix, Workspace& W, hipStream_t s, const float* d_q, uint32_t nq, size_t dim) {
+// in front; query_prep raises ST_ZERO_QUERY.  No per-query flags; bf16 (the screened late-interaction route): also the bf16 image
+// with |q - bf16(q)| and, where the rows carry margins, g_q, as the screening tier prepares them.
+static int prep_exact_queries(Index* ix, Workspace& W, hipStream_t s, const float* d_q, uint32_t nq, size_t dim, bool bf16 = false) {
     int rc;
     const uint32_t ld = ix->ld, bp_all = round_up(nq, SUPER);
     if ((rc = W.w_qp.ensure((size_t)bp_all * ld)) || (rc = W.w_qnorm.ensure(bp_all)) || (rc = W.w_thr.ensure(bp_all)) ||
         (rc = W.w_flags.ensure(SearchFlags::words(nq))))
         return rc;
+    if (bf16 && ((rc = W.w_qb.ensure((size_t)bp_all * ld)) || (rc = W.w_qerr.ensure(bp_all)) || (rc = W.w_qg.ensure(bp_all)))) return rc;
     uint32_t* d_status = SearchFlags(W.w_flags.p, nq).status;
     HIP_TRY(hipMemsetAsync(d_status, 0, STATUS_BYTES, s));
     W.status_dirty = true;                                         // (the tiers' bookkeeping: the block is cleared again before its next use)
     vdb::QueryPrepParams qp{d_q, (uint32_t)dim, nq, W.w_qp.p, ld, bp_all, W.w_qnorm.p, W.w_thr.p, ix->metric, d_status,
                             nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr};
+    if (bf16) { qp.qb = W.w_qb.p; qp.qerr = W.w_qerr.p; qp.qg = ix->d_margin ? W.w_qg.p : nullptr; qp.kappa = margin_plan(ix).kappa; }
     vdb::launch_query_prep(qp, s);
     return VDB_OK;
 }
@@ -1991,7 +1994,11 @@ int maxsim_drive(Index* ix, const HostSearch& r, const MaxsimReq& req, const int
     const uint32_t n = ix->n_uploaded;
 
     // ---- how many queries one chunk holds: table and keys under the cap, the select's sort area, the grid's y range
-    const size_t per_query = n_codes * (vdb::MAXSIM_MAX_TOKENS * 4 + 8);
+    // (the screened route folds its ranking table into per-document bounds and then reuses the table for the exact minima: one
+    // table, plus a candidate bitmap of a bit per code)
+    const bool screen = ix->maxsim_screen != 0 && n > 0;
+    const size_t mark_words = (n_codes + 31) / 32;
+    const size_t per_query = n_codes * (vdb::MAXSIM_MAX_TOKENS * 4 + 8) + (screen ? mark_words * 4 : 0);
     const size_t cap = ix->maxsim_table_cap ? ix->maxsim_table_cap : MAXSIM_TABLE_CAP;
     const size_t G = std::min<size_t>(std::min<size_t>(nq, SUPER), std::max<size_t>(cap / per_query, 1));
 
@@ -1999,7 +2006,17 @@ int maxsim_drive(Index* ix, const HostSearch& r, const MaxsimReq& req, const int
     std::vector<uint32_t> meta(2 * nq + 1);
     for (size_t b = 0; b <= nq; ++b) meta[b] = (uint32_t)req.offsets[b];
     for (size_t b = 0; b < nq; ++b) meta[nq + 1 + b] = (uint32_t)std::min(r.ks ? r.ks[b] : r.k, kmax);
-    if ((rc = B.q.ensure(total * std::max<size_t>(dim, 1))) || (rc = B.meta.ensure(meta.size())) || (rc = B.ctr.ensure(2)) ||
+    ix->maxsim_lb_codes = 0;
+    const size_t tok_pad = round_up((uint32_t)total, SUPER);
+    std::vector<uint32_t> colmap(screen ? tok_pad : 0, 0xffffffffu);
+    if (screen) {
+        for (size_t b = 0; b < nq; ++b)
+            for (size_t t = req.offsets[b]; t < req.offsets[b + 1]; ++t) colmap[t] = (uint32_t)(b << 8 | (t - req.offsets[b]));
+        if ((rc = B.colmap.ensure(tok_pad)) || (rc = B.unscreened.ensure(nq)) || (rc = B.lb.ensure(nq * n_codes)) ||
+            (rc = B.marked.ensure(G * mark_words)) || (rc = B.cert.ensure(total)))
+            return rc;
+    }
+    if ((rc = B.q.ensure(total * std::max<size_t>(dim, 1))) || (rc = B.meta.ensure(meta.size())) || (rc = B.ctr.ensure(4)) ||
         (rc = B.table.ensure(G * n_codes * vdb::MAXSIM_MAX_TOKENS)) || (rc = B.keys.ensure(G * n_codes)) ||
         (rc = B.outcodes.ensure(nq * kmax)) || (rc = B.outs.ensure(nq * kmax)) || (rc = B.outc.ensure(nq)) ||
         (rc = W.w_exsel.ensure((size_t)SUPER * MAX_SELECT + 8)) || (rc = W.w_cnt.ensure(4 * SUPER + 16)))
@@ -2008,8 +2025,8 @@ int maxsim_drive(Index* ix, const HostSearch& r, const MaxsimReq& req, const int
     struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
     HIP_TRY(hipMemcpyAsync(B.q.p, req.tokens, total * dim * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(B.meta.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(B.ctr.p, 0, 16, s));
-    if ((rc = prep_exact_queries(ix, W, s, B.q.p, (uint32_t)total, dim))) return rc;
+    HIP_TRY(hipMemsetAsync(B.ctr.p, 0, 32, s));
+    if ((rc = prep_exact_queries(ix, W, s, B.q.p, (uint32_t)total, dim, screen))) return rc;
     uint32_t* d_status = SearchFlags(W.w_flags.p, total).status;
     const uint64_t* d_mask;
     if ((rc = stage_mask(B.mask_in, mask_src(r), s, &d_mask))) return rc;
@@ -2019,18 +2036,56 @@ int maxsim_drive(Index* ix, const HostSearch& r, const MaxsimReq& req, const int
     if (!rows && n) return fail(VDB_ERR_DEVICE, "the row store is unusable");
     unsigned long long* ctr = reinterpret_cast<unsigned long long*>(B.ctr.p);
 
+    if (screen) {
+        // the column map, the flags, and the certificate constants of every token: a token that cannot be certified (a norm below
+        // 2^-40 or above 2^40, a tiny-norm row under Cosine) marks its query "not screened"
+        HIP_TRY(hipMemcpyAsync(B.colmap.p, colmap.data(), tok_pad * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(B.unscreened.p, 0, nq * 4, s));
+        vdb::MaxsimCertParams cp{};
+        cp.cert_in.metric = ix->metric; cp.cert_in.ld = ix->ld; cp.cert_in.eps_coef = eps_coef(ix); cp.cert_in.nd2max_bits = ix->d_scalars;
+        cp.cert_in.qerr = W.w_qerr.p; cp.cert_in.c_acc = c_acc_bf16(ix); cp.cert_in.lb_scores = ix->d_margin ? 1u : 0u;
+        cp.qnorm = W.w_qnorm.p; cp.colmap = B.colmap.p; cp.n_tokens = (uint32_t)total; cp.n_queries = (uint32_t)nq;
+        cp.cert = B.cert.p; cp.unscreened = B.unscreened.p;
+        vdb::launch_maxsim_cert(cp, s);
+    }
+
     size_t chunks = 0;
     for (size_t q0 = 0; q0 < nq; q0 += G, ++chunks) {
         const uint32_t g = (uint32_t)std::min(G, nq - q0);
-        HIP_TRY(hipMemsetAsync(B.table.p, 0xff, (size_t)g * n_codes * vdb::MAXSIM_MAX_TOKENS * 4, s));
+        const size_t table_bytes = (size_t)g * n_codes * vdb::MAXSIM_MAX_TOKENS * 4;
+        HIP_TRY(hipMemsetAsync(B.table.p, 0xff, table_bytes, s));
         vdb::MaxsimScanParams sp{rows, ix->ld, ix->dim, n, ix->metric, ix->d_nd, d_rowmask, ix->d_row_ids, d_codes, codes_len,
                                  (uint32_t)n_codes, W.w_qp.p, W.w_qnorm.p, B.meta.p, (uint32_t)q0, B.table.p, d_status, ctr};
-        vdb::launch_maxsim_scan(sp, g, s);
-        vdb::launch_maxsim_fold(vdb::MaxsimFoldParams{B.table.p, (uint32_t)n_codes, B.meta.p, (uint32_t)q0, B.keys.p, d_status, ctr + 1}, g, s);
         // (the keys are (score, code) pairs, no (distance, id rank) pairs: the select only sorts them, maxsim_emit_kernel reads them)
         vdb::SelectParams mp{};
         mp.kk = (uint32_t)kmax; mp.out_keys = W.w_exsel.p; mp.out_stride = MAX_SELECT; mp.out_cnt = W.w_cnt.p;
         mp.keys = B.keys.p; mp.stride = n_codes; mp.counts = nullptr; mp.n_fixed = (uint32_t)n_codes; mp.cap = (uint32_t)n_codes;
+        if (!screen) {
+            vdb::launch_maxsim_scan(sp, g, s);
+            vdb::launch_maxsim_fold(vdb::MaxsimFoldParams{B.table.p, (uint32_t)n_codes, B.meta.p, (uint32_t)q0, B.keys.p, d_status, ctr + 1}, g, s);
+        } else {
+            // the ranking pass over the 256-column passes that hold the chunk's tokens, the bounds L(q, c), the k smallest of them
+            const uint32_t pass0 = meta[q0] >> 8, pass1 = (meta[q0 + g] - 1) >> 8;
+            vdb::MaxsimScreenParams kp{rows, ix->ld, n, ix->d_nd, ix->d_alpha, ix->d_beta, ix->d_margin, d_rowmask, ix->d_row_ids, d_codes,
+                                       codes_len, (uint32_t)n_codes, W.w_qb.p, ix->d_margin ? W.w_qg.p : nullptr, B.colmap.p,
+                                       pass0, (uint32_t)q0, g, B.table.p, B.unscreened.p, d_status};
+            vdb::launch_maxsim_screen(kp, pass1 - pass0 + 1, s);
+            vdb::launch_maxsim_bound(vdb::MaxsimBoundParams{B.table.p, (uint32_t)n_codes, B.meta.p, (uint32_t)q0, B.cert.p, ix->metric,
+                                                            B.lb.p, B.keys.p, ctr + 1}, g, s);
+            vdb::launch_select(mp, g, s);
+            // round 1: the exact scores of those k documents (of every document, for a query that is not screened) give e_k;
+            // round 2: every other document with L <= e_k.  The exact table is not reset in between: minima are idempotent.
+            vdb::MaxsimMarkParams kp2{W.w_exsel.p, W.w_cnt.p, MAX_SELECT, (uint32_t)kmax, B.lb.p, (uint32_t)n_codes, (uint32_t)q0,
+                                      B.unscreened.p, B.marked.p, (uint32_t)mark_words, ctr + 2};
+            HIP_TRY(hipMemsetAsync(B.marked.p, 0, (size_t)g * mark_words * 4, s));
+            HIP_TRY(hipMemsetAsync(B.table.p, 0xff, table_bytes, s));
+            for (int round = 1; round <= 2; ++round) {
+                vdb::launch_maxsim_mark(kp2, round, g, s);
+                vdb::launch_maxsim_scan_marked(sp, B.marked.p, (uint32_t)mark_words, g, s);
+                vdb::launch_maxsim_fold(vdb::MaxsimFoldParams{B.table.p, (uint32_t)n_codes, B.meta.p, (uint32_t)q0, B.keys.p, d_status, ctr + 3}, g, s);
+                if (round == 1) vdb::launch_select(mp, g, s);
+            }
+        }
         vdb::launch_select(mp, g, s);
         vdb::MaxsimEmitParams ep{W.w_exsel.p, W.w_cnt.p, MAX_SELECT, B.meta.p + nq + 1, (uint32_t)q0,
                                  B.outcodes.p, B.outs.p, B.outc.p, (uint32_t)kmax, d_status};
@@ -2040,9 +2095,11 @@ int maxsim_drive(Index* ix, const HostSearch& r, const MaxsimReq& req, const int
 
     // ---- one read of the status words and the counters
     uint32_t status[4] = {0, 0, 0, 0};
-    uint64_t counters[2] = {0, 0};
+    uint64_t counters[4] = {0, 0, 0, 0};
+    std::vector<uint32_t> unscreened(screen ? nq : 0);
     HIP_TRY(hipMemcpyAsync(status, d_status, 16, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(counters, B.ctr.p, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(counters, B.ctr.p, 32, hipMemcpyDeviceToHost, s));
+    if (screen) HIP_TRY(hipMemcpyAsync(unscreened.data(), B.unscreened.p, nq * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (status[0] & vdb::ST_ZERO_QUERY) return fail_zero_vector();
     if (status[3] & 1u) return fail(VDB_ERR_INVALID_ARGUMENT, "the column holds a code at or above n_codes = %zu", n_codes);
@@ -2069,6 +2126,13 @@ int maxsim_drive(Index* ix, const HostSearch& r, const MaxsimReq& req, const int
     }
     // (the scan counts the eligible rows once per chunk, in its y = 0 workgroups: every query of the call scanned as many)
     st[2] = chunks; st[3] = chunks ? counters[0] / chunks * nq : 0; st[4] = counters[1]; st[5] = returned;
+    if (screen) {
+        // (the candidate scans count the rows they fold, per query)
+        st[3] = counters[0]; st[7] = counters[2];
+        for (size_t b = 0; b < nq; ++b) st[6] += unscreened[b] ? 0 : 1;
+        ix->maxsim_unscreened.swap(unscreened);
+        ix->maxsim_lb_codes = n_codes;
+    }
     return VDB_OK;
 }
 

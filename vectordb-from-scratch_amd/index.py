@@ -563,12 +563,30 @@ class GpuFlatIndex(Index):
 
     def maxsim_stats(self):
         """The last search_batch_maxsim: [0] queries, [1] tokens, [2] chunks of queries, [3] eligible rows scanned, summed over
-        the queries, [4] documents seen, summed over the queries, [5] documents returned, [6], [7] 0."""
+        the queries, [4] documents seen, summed over the queries, [5] documents returned, [6], [7] 0.  After set_maxsim_screen(True):
+        [3] the rows the exact scans folded, [6] the queries the screened route answered, [7] the documents it re-scored."""
         out = (ctypes.c_uint64 * 8)()
         rc = self._L.vdb_flat_maxsim_stats(self._h, out)
         if rc:
             _raise(rc)
         return [int(x) for x in out]
+
+    def set_maxsim_screen(self, on):
+        """True: search_batch_maxsim ranks on the bf16 matrix cores and folds exactly only the documents a certified lower bound
+        cannot exclude -- the same answer, bit for bit.  maxsim_stats then reports [3] the rows folded exactly, [6] the queries
+        the screened route answered, [7] the documents it re-scored.  False (the default): the plain scan."""
+        rc = self._L.vdb_flat_set_maxsim_screen(self._h, 1 if on else 0)
+        if rc:
+            _raise(rc)
+
+    def debug_maxsim_lower_bounds(self, nq, n_codes):
+        """Tests: the lower bounds L(q, c) of the last screened search_batch_maxsim, f32 [nq, n_codes]; NaN where code c is no
+        document and for a query that was not screened."""
+        out = np.zeros((int(nq), int(n_codes)), dtype=np.float32)
+        rc = self._L.vdb_flat_debug_maxsim_lower_bounds(self._h, _fp(out), int(nq), int(n_codes))
+        if rc:
+            _raise(rc)
+        return out
 
     def debug_set_maxsim_table_cap(self, nbytes):
         """Tests: the bytes of score table and keys one chunk of queries may take (0: the default, 256 MiB).  Same answers."""

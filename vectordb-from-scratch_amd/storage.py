@@ -861,6 +861,13 @@ class VectorStore:
         the field belong to no document."""
         return self.search_late_interaction_batch([query_tokens], k, field, flt)[0]
 
+    def set_late_interaction_screen(self, on):
+        """True: late-interaction searches rank on the bf16 matrix cores first and score exactly only the documents that can
+        still reach the top k (GpuFlatIndex.set_maxsim_screen); the answers do not change."""
+        if not isinstance(self._index, GpuFlatIndex):
+            raise ValueError("search_late_interaction needs a GpuFlatIndex")
+        self._index.set_maxsim_screen(on)
+
     def search_late_interaction_batch(self, queries, k, field, flt=None):
         """search_late_interaction for several queries (each a list of Vectors, at most 32) in one device call.  flt is a
         PRE-filter on the rows.  With the device filter on the field's resident column is read and flt is compiled on the
