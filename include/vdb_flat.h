@@ -750,6 +750,63 @@ int vdb_flat_set_maxsim_screen(vdb_flat_index *h, int on);
 int vdb_flat_debug_maxsim_lower_bounds(vdb_flat_index *h, float *out /* [nq][n_codes] */, size_t nq, size_t n_codes);
 
 /*
+ * SPARSE VECTORS: an index of its own for SPLADE / BM25-style weights, the sparse side of a hybrid retrieval (no reference
+ * counterpart; the dense kernels need strided f32 rows, and a densified 30k-dimension row costs 120 KB).  "spv" and not "sparse":
+ * vdb_flat_set_sparse_filter is the sparse-FILTER route of the dense index.
+ *
+ * Definition (what the device is held to, bit for bit):
+ *  - A sparse vector is a set of (index u32, value f32) pairs with unique indices below 2^24, in any order: the host sorts every
+ *    vector ascending by index on entry; a repeated index or an index >= 2^24 is VDB_ERR_INVALID_ARGUMENT.  Explicit zeros are
+ *    stored and count as overlap.
+ *  - For a query q and a stored vector x let S be the indices they share, ascending.  S empty: x is NOT A CANDIDATE and is never
+ *    returned, however large k is.  Else  s = 0.0f; for d in S: s = s + (q_d * x_d)  -- one rounded multiply, then one rounded
+ *    add, in ascending d -- and the distance is -s, as DistanceMetric::DotProduct (src/distance.rs:31).
+ *  - The answer is the k_b candidates with the smallest (distance, id), ids as unsigned 64-bit, ordered as vdb_flat_search_batch
+ *    orders them under VDB_METRIC_DOT (-0.0 in front of +0.0); out_counts[b] = min(k_b, eligible candidates).
+ *  - id_mask / mask_bits as in vdb_flat_search_batch; removed ids are gone; an id that is added again keeps only its last vector.
+ *    Mask and tombstones apply BEFORE top-k.  A NaN score at an eligible candidate (inf - inf, 0 * inf) fails the call with
+ *    VDB_ERR_NAN; +inf and -inf scores are ordinary.
+ *  - ks, k, kstride and the output arrays are those of vdb_flat_search_batch, max k_b <= VDB_SPV_MAX_K.  Query b owns the pairs
+ *    [q_offsets[b], q_offsets[b + 1]) of q_indices / q_values, at most VDB_SPV_MAX_QUERY_NNZ of them (more are refused).  An empty
+ *    index, a query without pairs, k_b = 0: count 0.
+ * vdb_spv_add_bulk: row i owns the pairs [offsets[i], offsets[i + 1]); an existing id is overwritten; everything is checked
+ * before anything is stored.  vdb_spv_remove: an absent id is VDB_OK.  vdb_spv_len: live rows.  Mutations are externally
+ * serialised against searches by the caller's write lock, like vdb_flat_add; searches on one handle serialise themselves.
+ * How (csrc/kernels_spv.hip): the rows are kept as CSR in append order with a live bitmap; the id -> row map
+ * stays on the host.  vdb_spv_flush after a mutation (the next search does it otherwise) rebuilds the INVERTED FILE on the device
+ * from the live rows: histogram of the indices, exclusive scan, scatter of (row, value) postings.  A search runs one workgroup of
+ * 1024 threads per query: it walks the query's dimensions in ascending order, the threads striding over each posting list and
+ * adding into acc[row] with a barrier between dimensions (so every row's fold is the ascending fold above); a second walk over
+ * the same lists takes each touched accumulator out with an atomic exchange -- which leaves it clean for the next query --, tests
+ * liveness and mask, and offers (-s, id) to an exact top-k select in LDS.  An accumulator slot is 4 bytes per stored row (dead
+ * ones included); a batch runs in chunks of min(nq, cap / (4 rows)) queries, cap = 256 MiB (vdb_spv_debug_set_workspace_cap
+ * lowers it, for tests: 0 restores it).
+ * vdb_spv_stats: [0] rows stored, live + dead  [1] dead rows  [2] stored non-zeros, dead rows included  [3] vocabulary bound
+ * (1 + the largest index ever stored)  [4] rebuilds of the inverted file  [5] list entries walked by the last search (each entry
+ * once: the sum of the queried lists' lengths)  [6] candidates offered to the select by the last search  [7] its chunks.
+ * Not built: sharded handles; reclaiming dead rows (they stay until the caller builds a new index); HNSW stores; queries with
+ * more than VDB_SPV_MAX_QUERY_NNZ pairs; rows and non-zeros are both below 2^32, dead ones included.
+ */
+#define VDB_SPV_MAX_K 1024
+#define VDB_SPV_MAX_QUERY_NNZ 1024
+typedef struct vdb_spv_index vdb_spv_index;
+int vdb_spv_create(int device, vdb_spv_index **out);
+void vdb_spv_destroy(vdb_spv_index *h);
+int vdb_spv_add_bulk(vdb_spv_index *h, const uint64_t *ids, const size_t *offsets /* [n + 1] */, const uint32_t *indices,
+                     const float *values, size_t n);
+int vdb_spv_remove(vdb_spv_index *h, uint64_t id);
+size_t vdb_spv_len(const vdb_spv_index *h);
+int vdb_spv_flush(vdb_spv_index *h);
+int vdb_spv_search_batch(vdb_spv_index *h, const size_t *q_offsets /* [nq + 1] */, const uint32_t *q_indices, const float *q_values,
+                         size_t nq, const size_t *ks, size_t k, const uint64_t *id_mask, size_t mask_bits, size_t kstride,
+                         uint64_t *out_ids, float *out_dists, size_t *out_counts);
+int vdb_spv_search_batch_filtered(vdb_spv_index *h, const size_t *q_offsets /* [nq + 1] */, const uint32_t *q_indices,
+                                  const float *q_values, size_t nq, const size_t *ks, size_t k, const vdb_meta_mask *mask,
+                                  size_t kstride, uint64_t *out_ids, float *out_dists, size_t *out_counts);
+int vdb_spv_stats(const vdb_spv_index *h, uint64_t out[8]);
+int vdb_spv_debug_set_workspace_cap(vdb_spv_index *h, size_t bytes);
+
+/*
  * DIVERSE TOP-K (MAXIMAL MARGINAL RELEVANCE): k results that are not all the same thing (no reference counterpart; a caller would
  * search at depth m, get_vector every candidate and run an O(k m dim) loop on the host).  A request is a query q, a count k, a
  * candidate depth m and a trade-off lambda, 1 <= k <= m <= VDB_MMR_MAX_CANDIDATES, lambda an f32 in [0, 1].

@@ -24,6 +24,8 @@ SYMBOLS = [
     "vdb_flat_discover_batch", "vdb_flat_discover_batch_filtered", "vdb_flat_discover_stats", "vdb_flat_discover_depth", "vdb_flat_debug_set_discover_route",
     "vdb_flat_search_batch_maxsim", "vdb_flat_search_batch_maxsim_filtered", "vdb_flat_maxsim_stats", "vdb_flat_debug_set_maxsim_table_cap",
     "vdb_flat_set_maxsim_screen", "vdb_flat_debug_maxsim_lower_bounds",
+    "vdb_spv_create", "vdb_spv_destroy", "vdb_spv_add_bulk", "vdb_spv_remove", "vdb_spv_len", "vdb_spv_flush", "vdb_spv_search_batch",
+    "vdb_spv_search_batch_filtered", "vdb_spv_stats", "vdb_spv_debug_set_workspace_cap",
     "vdb_flat_search_batch_mmr", "vdb_flat_search_batch_mmr_filtered", "vdb_flat_mmr_stats",
     "vdb_flat_search_batch_distinct", "vdb_flat_search_batch_distinct_filtered", "vdb_flat_distinct_stats", "vdb_flat_distinct_depth",
     "vdb_flat_search_batch_grouped", "vdb_flat_search_batch_grouped_filtered", "vdb_flat_grouped_stats", "vdb_flat_debug_group_plan",
@@ -199,6 +201,18 @@ def lib():
     L.vdb_flat_debug_set_maxsim_table_cap.argtypes = [vp, sz]
     L.vdb_flat_set_maxsim_screen.argtypes = [vp, c.c_int]
     L.vdb_flat_debug_maxsim_lower_bounds.argtypes = [vp, fp, sz, sz]
+    L.vdb_spv_create.argtypes = [c.c_int, c.POINTER(vp)]
+    L.vdb_spv_destroy.argtypes = [vp]
+    L.vdb_spv_destroy.restype = None
+    L.vdb_spv_add_bulk.argtypes = [vp, u64p, szp, u32p, fp, sz]
+    L.vdb_spv_remove.argtypes = [vp, u64]
+    L.vdb_spv_len.argtypes = [vp]
+    L.vdb_spv_len.restype = sz
+    L.vdb_spv_flush.argtypes = [vp]
+    L.vdb_spv_search_batch.argtypes = [vp, szp, u32p, fp, sz, szp, sz, u64p, sz, sz, u64p, fp, szp]
+    L.vdb_spv_search_batch_filtered.argtypes = [vp, szp, u32p, fp, sz, szp, sz, vp, sz, u64p, fp, szp]
+    L.vdb_spv_stats.argtypes = [vp, u64p]
+    L.vdb_spv_debug_set_workspace_cap.argtypes = [vp, sz]
     L.vdb_flat_search_batch_mmr.argtypes = [vp, fp, sz, sz, szp, sz, sz, fp, c.c_float, u64p, sz, sz, u64p, fp, fp, szp]
     L.vdb_flat_search_batch_mmr_filtered.argtypes = [vp, fp, sz, sz, szp, sz, sz, fp, c.c_float, vp, sz, u64p, fp, fp, szp]
     L.vdb_flat_mmr_stats.argtypes = [vp, u64p]

@@ -1,0 +1,52 @@
+// kernels_spv.h -- parameter blocks and launchers of the sparse-VECTOR index (kernels_spv.hip, vdb_spv.cpp).
+// "spv", not "sparse": kernels_sparse.hip is the sparse-FILTER route of the dense index.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <stddef.h>
+#include <stdint.h>
+
+namespace vdb {
+
+constexpr uint32_t SPV_MAX_INDEX = 1u << 24;        // indices are below this
+constexpr uint32_t SPV_MAX_QUERY_NNZ = 1024;        // non-zeros of one query (its table lives in LDS)
+constexpr uint32_t SPV_MAX_K = 1024;
+constexpr uint32_t SPV_THREADS = 1024;              // one workgroup per query
+constexpr uint32_t SPV_SELECT_CAP = 4096;           // keys of the select buffer (LDS); pruned to k when a round of 1024 may not fit
+// An accumulator nobody has added to.  A NaN pattern no fold can produce: every NaN a fold yields is stored as 0x7fc00000.
+constexpr uint32_t SPV_UNTOUCHED = 0x7fffbeefu;
+
+struct SpvEntry { uint32_t row; float val; };       // one posting: the row and its weight in the list's dimension
+
+// words[i] = value, i < n
+void launch_spv_fill(uint32_t* words, size_t n, uint32_t value, hipStream_t s);
+
+// The inverted file from the CSR rows, live rows only.  The host guarantees: row_ptr is monotone with row_ptr[n_rows] entries in
+// idx / val, every idx[e] < vocab, and the number of entries of live rows is below 2^32.
+struct SpvBuildParams {
+    const uint32_t* row_ptr; const uint32_t* idx; const float* val; const uint32_t* live; uint32_t n_rows;
+    uint32_t vocab;
+    uint32_t* counts;                                  // [vocab]: zero before the histogram; the scan leaves it zero for the scatter's cursors
+    uint32_t* list_ptr;                                // [vocab + 1]
+    SpvEntry* entries;                                 // [list_ptr[vocab]]
+};
+void launch_spv_histogram(const SpvBuildParams& p, hipStream_t s);
+void launch_spv_scan(const SpvBuildParams& p, hipStream_t s);
+void launch_spv_scatter(const SpvBuildParams& p, hipStream_t s);
+
+// One workgroup per query y < nq of a chunk (query b = q0 + y of the batch): fold, emit, select.
+struct SpvSearchParams {
+    const uint32_t* q_off; const uint32_t* q_idx; const float* q_val;   // the batch's queries, CSR, indices ascending; q_off[nq_batch + 1]
+    const uint32_t* ks; uint32_t q0;                   // k of query b (<= SPV_MAX_K, <= kout)
+    const uint32_t* list_ptr; uint32_t vocab; const SpvEntry* entries;
+    float* acc; uint32_t n_rows;                       // acc[y * n_rows + row]: SPV_UNTOUCHED on entry and on exit
+    const uint32_t* live; const uint64_t* row_ids; const uint32_t* rank;   // by row; rank = position of the row's id among the live ids
+    const uint64_t* sorted_ids;                        // by rank
+    const uint64_t* id_mask; uint64_t mask_bits;       // may be null
+    uint64_t* out_ids; float* out_dists; uint32_t* out_counts; uint32_t kout;   // [nq_batch][kout]
+    uint32_t* status;                                  // |= ST_NAN: a NaN score in an eligible row
+    unsigned long long* counters;                      // [0] += list entries walked (once per entry), [1] += candidates offered to the select
+};
+void launch_spv_search(const SpvSearchParams& p, uint32_t nq, hipStream_t s);
+
+}  // namespace vdb

@@ -12,6 +12,7 @@ import numpy as np
 from .error import DimensionMismatch, VectorNotFound
 from .hnsw import GpuHnswIndex
 from .index import GROUP_NONE, GpuFlatIndex, Index, MetaTable
+from .sparse_index import GpuSparseIndex, rrf_fuse
 from .vector import DistanceMetric, Vector
 
 
@@ -135,6 +136,7 @@ class BatchInsertItem:                               # storage.rs:74-79
     id: str
     vector: Vector
     metadata: Metadata = field(default_factory=Metadata)
+    sparse: tuple = None                             # (indices, values): the row's sparse vector (VectorStore.enable_sparse)
 
 
 class _Column:
@@ -224,6 +226,7 @@ class VectorStore:
         self._slots = {}
         self._table = None
         self._lut_sent = {}                              # field -> dictionary codes whose numbers the table has (MetaTable.set_numbers)
+        self._sparse = None                              # enable_sparse: a GpuSparseIndex keyed by the same internal ids
 
     @classmethod
     def with_index(cls, index):                      # storage.rs:118-127
@@ -233,8 +236,19 @@ class VectorStore:
     def insert(self, id, vector):                    # storage.rs:130-132
         self.insert_with_metadata(id, vector, Metadata())
 
-    def insert_with_metadata(self, id, vector, metadata):   # storage.rs:135-172
+    def enable_sparse(self):
+        """Keep a sparse vector beside the dense one (GpuSparseIndex on the index's GPU, keyed by the same internal id, so every
+        mask of compile_filter applies to it unchanged): insert_with_metadata(..., sparse=(indices, values)), search_sparse,
+        search_hybrid.  Flat stores only."""
+        if not isinstance(self._index, GpuFlatIndex):
+            raise ValueError("sparse vectors need a GpuFlatIndex")
+        if self._sparse is None:
+            self._sparse = GpuSparseIndex(self._index._device)
+
+    def insert_with_metadata(self, id, vector, metadata, sparse=None):   # storage.rs:135-172
         id = str(id)
+        if sparse is not None and self._sparse is None:
+            raise ValueError("enable_sparse() first")
         dim = vector.dimension()
         if self._dimension is not None:
             if dim != self._dimension:
@@ -246,11 +260,15 @@ class VectorStore:
             old = self._bulk_internal(id)                # an id that names a bulk-attached row: the insert replaces that row
         if old is not None:
             self._index.remove(old)
+            if self._sparse is not None:
+                self._sparse.remove(old)
             self._metadata.pop(old, None)
             self._internal_to_id.pop(old, None)
         internal = self._next_id
         self._next_id += 1
         self._index.add(internal, vector)
+        if sparse is not None:
+            self._sparse.add(internal, sparse[0], sparse[1])
         self._id_to_internal[id] = internal
         self._internal_to_id[internal] = id
         self._metadata[internal] = metadata
@@ -266,7 +284,7 @@ class VectorStore:
 
     def insert_batch(self, items):                   # storage.rs:293-298
         for it in items:
-            self.insert_with_metadata(it.id, it.vector, it.metadata)
+            self.insert_with_metadata(it.id, it.vector, it.metadata, sparse=it.sparse)
 
     def delete(self, id):                            # storage.rs:175-192
         internal = self._id_to_internal.pop(id, None)
@@ -280,6 +298,8 @@ class VectorStore:
         self._internal_to_id.pop(internal, None)
         self._metadata.pop(internal, None)
         self._index.remove(internal)
+        if self._sparse is not None:
+            self._sparse.remove(internal)
         self._mark_present(internal, False)
         return v
 
@@ -647,6 +667,54 @@ class VectorStore:
             return None
         prog, consts = prog
         return self._table.compile(prog, max(self._next_id, 1), consts if consts else None)
+
+    # ---- sparse and hybrid retrieval (GpuSparseIndex; no reference counterpart)
+    def _masked(self, flt, call):
+        """call(id_mask, mask_bits, compiled_mask) under flt as a PRE-filter: compiled on the device when the device filter is on
+        and the filter fits its program limits, by compile_filter otherwise"""
+        if flt is None:
+            return call(None, 0, None)
+        cm = self.compile_filter_device(flt) if self._table is not None else None
+        if cm is None:
+            mask, bits = self.compile_filter(flt)
+            return call(mask, bits, None)
+        try:
+            return call(None, 0, cm)
+        finally:
+            cm.release()
+
+    def _sparse_lists(self, queries, k, flt):
+        if self._sparse is None:
+            raise ValueError("enable_sparse() first")
+        ids, dists, counts = self._masked(flt, lambda m, b, cm: self._sparse.search_batch_arrays(queries, int(k), id_mask=m, mask_bits=b,
+                                                                                                  compiled_mask=cm))
+        return [[(int(ids[q, i]), dists[q, i]) for i in range(int(counts[q]))] for q in range(len(queries))]
+
+    def search_sparse(self, query, k, flt=None):
+        """The k rows whose sparse vector scores highest against query = (indices, values), as SearchResults with distance =
+        -score, best first; rows that share no index with the query are never returned.  flt is a PRE-filter."""
+        return self.search_sparse_batch([query], k, flt)[0]
+
+    def search_sparse_batch(self, queries, k, flt=None):
+        queries = list(queries)
+        if not queries:
+            return []
+        return [self._map(r) for r in self._sparse_lists(queries, k, flt)]
+
+    def search_hybrid(self, dense_query, sparse_query, k, flt=None, depth=None):
+        """Hybrid retrieval: the dense search and the sparse search both run at `depth` (default max(k, 100), at most 1024) under
+        the same pre-filter, and their rankings are fused by reciprocal rank -- 1 / (60 + rank) summed over the two lists in
+        f64, ties by internal id (rrf_fuse; O(depth) work, on the host on purpose).  Returns [(id, fused score), ...], best first."""
+        depth = max(int(k), 100) if depth is None else int(depth)
+        if self._sparse is None:
+            raise ValueError("enable_sparse() first")
+        if self.is_empty():
+            return []
+        self._check_dim(dense_query)
+        dense = self._masked(flt, lambda m, b, cm: self._index.search_batch([(dense_query, depth)], id_mask=m, mask_bits=b, compiled_mask=cm))[0]
+        sparse = self._sparse_lists([sparse_query], depth, flt)[0]
+        fused = rrf_fuse([[i for i, _ in dense], [i for i, _ in sparse]], k)
+        return [(r.id, s) for i, s in fused for r in self._map([(i, s)])]
 
     # ---- exact range search (GpuFlatIndex.range_search_batch; no reference counterpart)
     def search_within(self, query, radius, limit, flt=None):
