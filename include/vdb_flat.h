@@ -781,6 +781,16 @@ int vdb_flat_debug_maxsim_lower_bounds(vdb_flat_index *h, float *out /* [nq][n_c
  * liveness and mask, and offers (-s, id) to an exact top-k select in LDS.  An accumulator slot is 4 bytes per stored row (dead
  * ones included); a batch runs in chunks of min(nq, cap / (4 rows)) queries, cap = 256 MiB (vdb_spv_debug_set_workspace_cap
  * lowers it, for tests: 0 restores it).
+ * vdb_spv_set_route: HOW a search scores; the answers are the same to the bit.  0 (the default): the inverted-file walk above,
+ * the right tool for queries off the head of the word distribution.  1: the ROW-MAJOR route (csrc/kernels_spv_rows.hip, DESIGN.md
+ * 4.20.1) for batches whose queries hold the frequent words, where the walk makes every query visit a large part of the store:
+ * the CSR rows are read once per tile of 64 queries -- a lane is a query, a row's entries arrive in ascending index order, so the
+ * fold is the definition's --, against a dense table of the batch's distinct dimensions; its work depends on the store's size
+ * and the number of queries, not on how frequent the query words are.  2: per call, the row-major route when the inverted
+ * route's counted work exceeds vdb_spv_route_rho() times the row-major route's.  Any other mode is VDB_ERR_INVALID_ARGUMENT.
+ * vdb_spv_route_stats, of the last search: [0] the route taken (0 / 1)  [1] row passes launched (0 on route 0)  [2] the inverted
+ * route's counted work: the sum over queries and queried indices of the live list length  [3] the row-major route's: live
+ * non-zeros times the number of 64-query tiles.  vdb_spv_stats [5] - [7] are the same numbers on both routes.
  * vdb_spv_stats: [0] rows stored, live + dead  [1] dead rows  [2] stored non-zeros, dead rows included  [3] vocabulary bound
  * (1 + the largest index ever stored)  [4] rebuilds of the inverted file  [5] list entries walked by the last search (each entry
  * once: the sum of the queried lists' lengths)  [6] candidates offered to the select by the last search  [7] its chunks.
@@ -805,6 +815,9 @@ int vdb_spv_search_batch_filtered(vdb_spv_index *h, const size_t *q_offsets /* [
                                   size_t kstride, uint64_t *out_ids, float *out_dists, size_t *out_counts);
 int vdb_spv_stats(const vdb_spv_index *h, uint64_t out[8]);
 int vdb_spv_debug_set_workspace_cap(vdb_spv_index *h, size_t bytes);
+int vdb_spv_set_route(vdb_spv_index *h, int mode);
+int vdb_spv_route_stats(const vdb_spv_index *h, uint64_t out[4]);
+double vdb_spv_route_rho(void);
 
 /*
  * DIVERSE TOP-K (MAXIMAL MARGINAL RELEVANCE): k results that are not all the same thing (no reference counterpart; a caller would

@@ -2,7 +2,13 @@
 """Sparse-vector search (GpuSparseIndex) at a SPLADE-like shape, against the best composition available without it: a torch
 CSR x dense-query product on the same GPU plus topk -- or, where this ROCm build of torch cannot do that, a numpy pass over the
 CSR arrays on the host, measured on two queries and labelled per query.  Warm-up, then the two alternate; median, min and max of
-each are recorded.  Writes one JSON object to --out and prints it."""
+each are recorded.  Writes one JSON object to --out and prints it.
+
+--route 0 | 1 | 2 measures that route of the index (vdb_spv_set_route) as before; --route both alternates route 0, route 1 and the
+baseline in one process, once per --query-min-rank R given (query indices drawn from the words of frequency rank >= R only: 0 is
+the Zipf workload, 1000 one off the head of the distribution), records both routes' counted work, interpolates in log space the
+ratio of the two counts at which the routes' times cross (rho) when two workloads fall on either side of it, and adds k = 1024
+and a half-selective id mask on the first workload."""
 import argparse
 import importlib.util
 import json
@@ -37,6 +43,39 @@ def zipf_rows(rng, n, vocab, draws, cdf):
     return offs, idx, rng.random(idx.size, dtype=np.float32) + np.float32(0.05)
 
 
+def zipf_queries(rng, n, vocab, draws, min_rank):
+    w = 1.0 / np.arange(1, vocab + 1, dtype=np.float64)
+    w[:min_rank] = 0.0
+    return zipf_rows(rng, n, vocab, draws, np.cumsum(w / w.sum()).astype(np.float32))
+
+
+def both_routes(ix, queries, k, rounds, base=None, **mask):
+    """route 0, route 1 (and the baseline) alternating -> {"route0": spread, "route1": spread, "baseline": spread, work counts}"""
+    def run(route):
+        ix.set_route(route)
+        t0 = time.perf_counter()
+        r = ix.search_batch_arrays(queries, k, **mask)
+        return (time.perf_counter() - t0) * 1e3, r
+    for route in (0, 1, 0, 1):
+        run(route)
+    t = {0: [], 1: [], "base": []}
+    for _ in range(rounds):
+        for route in (0, 1):
+            ms, r = run(route)
+            t[route].append(ms)
+            if route == 0:
+                r0, st0 = r, ix.stats()
+        if base is not None:
+            t["base"].append(base()[0])
+    rs, st1 = ix.route_stats(), ix.stats()
+    rec = {"route0": spread(t[0]), "route1": spread(t[1]), "work_inverted": rs["work_inverted"], "work_rows": rs["work_rows"],
+           "passes": rs["passes"], "chunks": st1["chunks"], "entries_walked_per_query": st1["entries_walked"] / len(queries),
+           "answers_and_counters_equal": bool(all(np.array_equal(a, b) for a, b in zip(r0, r)) and st0 == st1)}
+    if base is not None:
+        rec["baseline"] = spread(t["base"])
+    return rec
+
+
 def spread(ms):
     return {"median_ms": float(np.median(ms)), "min_ms": float(min(ms)), "max_ms": float(max(ms)), "runs": len(ms)}
 
@@ -50,6 +89,8 @@ def main():
     ap.add_argument("--queries", type=int, default=256)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--route", default="0", choices=["0", "1", "2", "both"])
+    ap.add_argument("--query-min-rank", type=int, nargs="+", default=[0])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "spv_bench.json"))
     a = ap.parse_args()
     vdb = load_package()
@@ -59,11 +100,13 @@ def main():
     cdf = np.cumsum(w / w.sum()).astype(np.float32)
     t = time.perf_counter()
     offs, idx, val = zipf_rows(rng, a.rows, a.vocab, a.row_draws, cdf)
-    qoffs, qidx, qval = zipf_rows(rng, a.queries, a.vocab, a.query_draws, cdf)
+    qoffs, qidx, qval = zipf_queries(rng, a.queries, a.vocab, a.query_draws, a.query_min_rank[0])
     print(f"data: {idx.size} non-zeros in {a.rows} rows, {qidx.size} in {a.queries} queries, {time.perf_counter() - t:.1f} s", flush=True)
     queries = [(qidx[qoffs[b]:qoffs[b + 1]], qval[qoffs[b]:qoffs[b + 1]]) for b in range(a.queries)]
     ids = np.arange(a.rows, dtype=np.uint64)
     ix = vdb.GpuSparseIndex()
+    if a.route != "both":
+        ix.set_route(int(a.route))
     t = time.perf_counter()
     ix.add_csr(ids, offs, idx, val)
     t_add = time.perf_counter() - t
@@ -118,6 +161,33 @@ def main():
             return (time.perf_counter() - t0) * 1e3 / base_scale, (np.array(out), None)
         base_label = "numpy pass over the CSR arrays on the host, PER QUERY (two queries measured)"
 
+    if a.route == "both":
+        rec = {"shape": {"rows": a.rows, "vocab": a.vocab, "nnz": int(idx.size), "queries": a.queries, "k": a.k, "rounds": a.rounds},
+               "baseline_is": base_label, "workloads": []}
+        for i, rank in enumerate(a.query_min_rank):
+            if i:
+                qoffs, qidx, qval = zipf_queries(rng, a.queries, a.vocab, a.query_draws, rank)
+                queries = [(qidx[qoffs[b]:qoffs[b + 1]], qval[qoffs[b]:qoffs[b + 1]]) for b in range(a.queries)]
+            w = dict(query_min_rank=rank, mean_nnz_per_query=qidx.size / a.queries,
+                     **both_routes(ix, queries, a.k, a.rounds, base if i == 0 and base_scale == 1 else None))
+            w["log_work_ratio"] = float(np.log(w["work_inverted"] / w["work_rows"]))
+            w["log_time_ratio"] = float(np.log(w["route0"]["median_ms"] / w["route1"]["median_ms"]))
+            rec["workloads"].append(w)
+            print(json.dumps(w), flush=True)
+            if i == 0:
+                first = queries
+        pts = sorted((w["log_work_ratio"], w["log_time_ratio"]) for w in rec["workloads"])
+        for (x0, y0), (x1, y1) in zip(pts, pts[1:]):
+            if y0 < 0 <= y1:                             # route 0 faster at x0, route 1 at x1: the times cross between them
+                rec["rho"] = float(np.exp(x0 - y0 * (x1 - x0) / (y1 - y0)))
+        rec["k_1024"] = both_routes(ix, first, 1024, 3)
+        half = np.full((a.rows + 63) // 64, 0x5555555555555555, dtype=np.uint64)
+        rec["masked_half"] = both_routes(ix, first, a.k, 3, id_mask=half, mask_bits=a.rows)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(rec, f, indent=1)
+        print(json.dumps(rec))
+        return
     ours()
     ours()
     base()
@@ -131,6 +201,7 @@ def main():
     nb = r_base[0].shape[0]
     same = [len(set(r_ours[0][b].tolist()) & set(r_base[0][b].tolist())) for b in range(nb)]
     rec = {
+        "route": int(a.route),
         "shape": {"rows": a.rows, "vocab": a.vocab, "nnz": int(idx.size), "mean_nnz_per_row": idx.size / a.rows, "queries": a.queries,
                   "mean_nnz_per_query": qidx.size / a.queries, "k": a.k, "index_distribution": "Zipf, exponent 1, rows and queries alike"},
         "search_batch": spread(t_ours),

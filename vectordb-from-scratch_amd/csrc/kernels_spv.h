@@ -49,4 +49,33 @@ struct SpvSearchParams {
 };
 void launch_spv_search(const SpvSearchParams& p, uint32_t nq, hipStream_t s);
 
+// ---------------------------------------------------------------- the row-major route (kernels_spv_rows.hip)
+// A PASS serves the queries [qa, qa + nq) of a batch, nq <= 64 * tiles: every CSR row is read once per tile of 64 queries.
+constexpr uint32_t SPV_ROWS_TILE = 64;              // queries per tile (a lane is a query), and rows per row tile
+constexpr uint32_t SPV_NO_SLOT = 0xffffffffu;       // dim_slot of a dimension no query of the pass holds
+// A table cell of a (dimension, query) pair the query does not hold.  A NaN pattern no query value is stored as: every NaN
+// value goes into the table as 0x7fc00000 (any NaN factor makes the score NaN, and a NaN score has one pattern already).
+constexpr uint32_t SPV_ABSENT = 0x7fa5ab5eu;
+constexpr size_t SPV_ROWS_TABLE_BYTES = 32u << 20;  // the table budget of a pass (one tile always fits: 65536 * 64 * 4 B)
+
+struct SpvRowsParams {
+    // the pass's queries: q_slot[pair] = the rank of the pair's dimension among the pass's distinct dimensions below vocab
+    // (udims[n_u], ascending), SPV_NO_SLOT for a dimension at or above vocab
+    const uint32_t* q_off; const float* q_val; const uint32_t* q_slot; uint32_t qa, nq, tiles;
+    const uint32_t* udims; uint32_t n_u;
+    uint32_t* dim_slot;                                // [vocab]: SPV_NO_SLOT on entry and on exit of a pass
+    uint32_t* table;                                   // [(n_u + 1)][tiles * 64] f32 bits; row n_u stays SPV_ABSENT everywhere
+    const uint32_t* row_ptr; const uint32_t* idx; const float* val; const uint32_t* live; uint32_t n_rows;
+    float* acc;                                        // acc[y * n_rows + row], y < nq: SPV_UNTOUCHED on entry and after the emit
+    // the emit (SpvSearchParams' fields of the same names)
+    const uint32_t* ks; const uint64_t* row_ids; const uint32_t* rank; const uint64_t* sorted_ids;
+    const uint64_t* id_mask; uint64_t mask_bits;
+    uint64_t* out_ids; float* out_dists; uint32_t* out_counts; uint32_t kout;
+    uint32_t* status; unsigned long long* counters;    // [0] += fold steps (= list entries the inverted route walks), [1] += offers
+};
+void launch_spv_rows_slots(const SpvRowsParams& p, bool set, hipStream_t s);   // dim_slot[udims[u]] = set ? u : SPV_NO_SLOT
+void launch_spv_rows_table(const SpvRowsParams& p, hipStream_t s);             // the table: SPV_ABSENT, then the pairs
+void launch_spv_rows_fold(const SpvRowsParams& p, hipStream_t s);
+void launch_spv_rows_emit(const SpvRowsParams& p, hipStream_t s);
+
 }  // namespace vdb

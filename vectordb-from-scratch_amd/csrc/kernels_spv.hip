@@ -19,6 +19,7 @@
 // Compiled without packed-f32 instructions (Makefile); -ffp-contract=off keeps the multiply and the add apart.
 #include "kernels.h"
 #include "kernels_spv.h"
+#include "kernels_spv_select.h"
 
 namespace vdb {
 
@@ -84,35 +85,6 @@ __global__ __launch_bounds__(BUILD_THREADS) void spv_scatter_kernel(SpvBuildPara
     }
 }
 
-// Sorts s_keys[0, n) ascending (unique keys), keeps the kq smallest; returns how many are kept.  Called by the whole workgroup.
-__device__ uint32_t spv_prune(uint64_t* s_keys, uint32_t* s_cnt, uint64_t* s_thr, uint32_t kq) {
-    const uint32_t tid = threadIdx.x;
-    __syncthreads();                                   // every push of the rounds before is in the buffer
-    const uint32_t n = *s_cnt;
-    uint32_t P = 2;
-    while (P < n) P <<= 1;
-    for (uint32_t i = n + tid; i < P; i += SPV_THREADS) s_keys[i] = EMPTY_KEY;
-    __syncthreads();
-    for (uint32_t k2 = 2; k2 <= P; k2 <<= 1)
-        for (uint32_t j = k2 >> 1; j > 0; j >>= 1) {
-            for (uint32_t i = tid; i < P; i += SPV_THREADS) {
-                const uint32_t o = i ^ j;
-                if (o > i) {
-                    const uint64_t x = s_keys[i], y = s_keys[o];
-                    if ((x > y) == ((i & k2) == 0)) { s_keys[i] = y; s_keys[o] = x; }
-                }
-            }
-            __syncthreads();
-        }
-    const uint32_t keep = min(n, kq);
-    if (tid == 0) {
-        *s_cnt = keep;
-        *s_thr = (kq && n >= kq) ? s_keys[kq - 1] : EMPTY_KEY;
-    }
-    __syncthreads();
-    return keep;
-}
-
 __global__ __launch_bounds__(SPV_THREADS) void spv_search_kernel(SpvSearchParams p) {
     __shared__ float s_val[SPV_MAX_QUERY_NNZ];
     __shared__ uint32_t s_ptr[SPV_MAX_QUERY_NNZ], s_len[SPV_MAX_QUERY_NNZ];
@@ -176,7 +148,7 @@ __global__ __launch_bounds__(SPV_THREADS) void spv_search_kernel(SpvSearchParams
                         if (s != s) s_nan = 1;
                         if (kq) {
                             const uint64_t key = make_key(-s, p.rank[row]);
-                            if (key < s_thr) s_keys[atomicAdd(&s_cnt, 1u)] = key;   // below bound <= SPV_SELECT_CAP
+                            spv_offer(s_keys, &s_cnt, &s_thr, key);            // below bound <= SPV_SELECT_CAP
                         }
                     }
                 }

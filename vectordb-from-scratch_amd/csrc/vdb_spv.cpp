@@ -1,10 +1,13 @@
 // vdb_spv.cpp -- the sparse-VECTOR index (include/vdb_flat.h "Sparse vectors"): CSR rows in append order with a
 // live bitmap and the id -> row map on the host, the inverted file rebuilt on the device by the flush after a mutation, and the
-// batch search that runs kernels_spv.hip one workgroup per query over a workspace of accumulator slots.
+// batch search that runs kernels_spv.hip one workgroup per query over a workspace of accumulator slots -- or, on the row-major route
+// (vdb_spv_set_route), kernels_spv_rows.hip over the CSR rows themselves, in passes of query tiles.
 //
 // What the kernels may assume is checked HERE, before anything reaches the device: every stored index is below 2^24 and below
 // `vocab`, row_ptr is monotone and ends at the number of stored entries (below 2^32), every query has at most 1024 ascending
-// indices.  The scatter and the two list walks have no other guard.
+// indices.  The scatter and the two list walks have no other guard.  The row-major route adds: every pair's table slot is below
+// the pass's count of distinct dimensions, those dimensions are below `vocab` = the size dim_slot is filled to, the table holds
+// one row more than that count, and a pass's queries lie inside one chunk of accumulator slots.
 #include <limits>
 
 #include "kernels_spv.h"
@@ -36,6 +39,12 @@ struct vdb_spv_index {
     DevBuf<uint32_t> d_qoff, d_qidx, d_ks, d_out_counts, d_flags;   // d_flags: [0] status, [2..5] the two 64-bit counters
     DevBuf<uint64_t> d_mask, d_out_ids;
     uint64_t rebuilds = 0, last_walked = 0, last_offered = 0, last_chunks = 0;
+    // the row-major route
+    int route = 0;                                                  // 0 inverted walk, 1 row-major, 2 by counted work
+    std::vector<uint32_t> live_df;                                  // [vocab]: live rows that hold the index (the live list length)
+    DevBuf<uint32_t> d_dim_slot, d_table, d_qslot, d_udims;
+    bool slots_clean = false;                                       // d_dim_slot is SPV_NO_SLOT up to its size
+    uint64_t last_route = 0, last_passes = 0, last_work_inv = 0, last_work_rows = 0;
 
     static constexpr size_t DEFAULT_CAP = 256u << 20;
 };
@@ -43,6 +52,9 @@ struct vdb_spv_index {
 namespace {
 
 constexpr uint64_t MAX_ENTRIES = 0xffffffffull;                     // row_ptr and list_ptr are 32-bit
+// Automatic route: row-major when the inverted route's counted work exceeds this many times the row-major route's (DESIGN.md
+// 4.20.1 "Measured": where the two routes' times cross, interpolated between two measured workloads).
+constexpr double ROUTE_RHO = 0.46;
 
 // One vector's pairs, sorted ascending by index into (oi, ov); refuses an index at or above 2^24 and a repeated index.
 int sorted_pairs(const uint32_t* in_i, const float* in_v, size_t n, const char* what, size_t which, std::vector<uint32_t>& oi,
@@ -70,6 +82,7 @@ int check_offsets(const size_t* off, size_t n, const char* what) {
 void kill_row(vdb_spv_index* h, uint32_t row) {
     h->live[row >> 5] &= ~(1u << (row & 31));
     h->live_nnz -= h->row_ptr[row + 1] - h->row_ptr[row];
+    for (uint32_t e = h->row_ptr[row]; e < h->row_ptr[row + 1]; ++e) --h->live_df[h->idx[e]];
     h->dirty = true;
 }
 
@@ -122,6 +135,42 @@ int flush_locked(vdb_spv_index* h) {
     return VDB_OK;
 }
 
+// The row-major route's plan of a batch: inside every chunk of `slots` queries, tiles of 64 queries are taken into one pass for
+// as long as |U| * 64 * tiles * 4 B stays within the table budget (U = the distinct dimensions below vocab the pass's queries
+// hold; one tile always fits: at most 64 * 1024 dimensions).  qslot[pair] = the rank of the pair's dimension in its pass's U.
+struct RowPass { uint32_t qa, nq, tiles, y0, u_off, n_u; };          // y0: the first query's accumulator slot inside its chunk
+
+void plan_row_passes(const std::vector<uint32_t>& qoff, const std::vector<uint32_t>& qidx, uint32_t vocab, size_t nq, size_t slots,
+                     std::vector<RowPass>& passes, std::vector<uint32_t>& qslot, std::vector<uint32_t>& udims) {
+    constexpr size_t T = vdb::SPV_ROWS_TILE;
+    qslot.assign(qidx.size(), vdb::SPV_NO_SLOT);
+    std::vector<uint32_t> U, cand;
+    for (size_t c0 = 0; c0 < nq; c0 += slots) {
+        const size_t c1 = std::min(c0 + slots, nq);
+        for (size_t a = c0; a < c1;) {
+            size_t b = a;
+            U.clear();
+            while (b < c1) {
+                const size_t nb = std::min(b + T, c1);
+                cand = U;
+                for (uint32_t i = qoff[b]; i < qoff[nb]; ++i)
+                    if (qidx[i] < vocab) cand.push_back(qidx[i]);
+                std::sort(cand.begin(), cand.end());
+                cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
+                if (b > a && cand.size() * T * ((nb - a + T - 1) / T) * 4 > vdb::SPV_ROWS_TABLE_BYTES) break;
+                U.swap(cand);
+                b = nb;
+            }
+            for (uint32_t i = qoff[a]; i < qoff[b]; ++i)
+                if (qidx[i] < vocab) qslot[i] = (uint32_t)(std::lower_bound(U.begin(), U.end(), qidx[i]) - U.begin());
+            passes.push_back({(uint32_t)a, (uint32_t)(b - a), (uint32_t)((b - a + T - 1) / T), (uint32_t)(a - c0), (uint32_t)udims.size(),
+                              (uint32_t)U.size()});
+            udims.insert(udims.end(), U.begin(), U.end());
+            a = b;
+        }
+    }
+}
+
 int search(vdb_spv_index* h, const size_t* q_offsets, const uint32_t* q_indices, const float* q_values, size_t nq, const size_t* ks,
            size_t k, const MaskSrc& mask, size_t kstride, uint64_t* out_ids, float* out_dists, size_t* out_counts) {
     if (!h) return fail(VDB_ERR_INVALID_ARGUMENT, "null handle");
@@ -152,6 +201,12 @@ int search(vdb_spv_index* h, const size_t* q_offsets, const uint32_t* q_indices,
     std::lock_guard<std::mutex> g(h->mu);
     if ((rc = flush_locked(h))) return rc;
     h->last_walked = h->last_offered = h->last_chunks = 0;
+    // the two routes' counted work: the live lengths of the queried lists; the live non-zeros once per tile of 64 queries
+    h->last_route = h->last_passes = h->last_work_inv = 0;
+    for (uint32_t d : qidx)
+        if (d < h->vocab) h->last_work_inv += h->live_df[d];
+    h->last_work_rows = h->live_nnz * ((nq + vdb::SPV_ROWS_TILE - 1) / vdb::SPV_ROWS_TILE);
+    const bool by_rows = h->route == 1 || (h->route == 2 && (double)h->last_work_inv > ROUTE_RHO * (double)h->last_work_rows);
     if (h->row_of.empty() || kmax == 0 || q_nnz == 0) {             // nothing can be a candidate
         for (size_t i = 0; i < nq; ++i) out_counts[i] = 0;
         return VDB_OK;
@@ -182,10 +237,46 @@ int search(vdb_spv_index* h, const size_t* q_offsets, const uint32_t* q_indices,
     p.id_mask = d_mask; p.mask_bits = mask.bits;
     p.out_ids = h->d_out_ids; p.out_dists = h->d_out_dists; p.out_counts = h->d_out_counts; p.kout = (uint32_t)kmax;
     p.status = h->d_flags; p.counters = reinterpret_cast<unsigned long long*>(h->d_flags.p + 2);
-    for (size_t q0 = 0; q0 < nq; q0 += slots) {
-        p.q0 = (uint32_t)q0;
-        vdb::launch_spv_search(p, (uint32_t)std::min(slots, nq - q0), s);
-        ++h->last_chunks;
+    std::vector<RowPass> passes;
+    std::vector<uint32_t> qslot, udims;                             // (read by their copies until the stream is synchronised)
+    if (by_rows) {
+        plan_row_passes(qoff, qidx, h->vocab, nq, slots, passes, qslot, udims);
+        size_t table = 0;
+        for (const RowPass& a : passes) table = std::max(table, ((size_t)a.n_u + 1) * a.tiles * vdb::SPV_ROWS_TILE);
+        udims.push_back(0);                                         // (never empty: upload_tail allocates)
+        if ((rc = upload_tail(h->d_qslot, qslot, 0, s)) || (rc = upload_tail(h->d_udims, udims, 0, s)) || (rc = h->d_table.ensure(table)))
+            return rc;
+        if (!h->slots_clean || h->d_dim_slot.n < h->vocab) {        // a wider vocabulary, or a search that failed half-way
+            if ((rc = h->d_dim_slot.ensure(h->vocab))) return rc;
+            vdb::launch_spv_fill(h->d_dim_slot, h->d_dim_slot.n, vdb::SPV_NO_SLOT, s);
+        }
+        h->slots_clean = false;
+        vdb::SpvRowsParams r{};
+        r.q_off = h->d_qoff; r.q_val = h->d_qval; r.q_slot = h->d_qslot;
+        r.dim_slot = h->d_dim_slot; r.table = h->d_table;
+        r.row_ptr = h->d_row_ptr; r.idx = h->d_idx; r.val = h->d_val; r.live = h->d_live; r.n_rows = n_rows;
+        r.ks = h->d_ks; r.row_ids = h->d_ids; r.rank = h->d_rank; r.sorted_ids = h->d_sorted;
+        r.id_mask = d_mask; r.mask_bits = mask.bits;
+        r.out_ids = h->d_out_ids; r.out_dists = h->d_out_dists; r.out_counts = h->d_out_counts; r.kout = (uint32_t)kmax;
+        r.status = p.status; r.counters = p.counters;
+        for (const RowPass& a : passes) {
+            r.qa = a.qa; r.nq = a.nq; r.tiles = a.tiles; r.udims = h->d_udims.p + a.u_off; r.n_u = a.n_u;
+            r.acc = h->d_acc.p + (size_t)a.y0 * n_rows;             // a.y0 + a.nq <= slots: the plan keeps a pass inside one chunk
+            vdb::launch_spv_rows_slots(r, true, s);
+            vdb::launch_spv_rows_table(r, s);
+            vdb::launch_spv_rows_fold(r, s);
+            vdb::launch_spv_rows_emit(r, s);
+            vdb::launch_spv_rows_slots(r, false, s);
+        }
+        h->last_route = 1;
+        h->last_passes = passes.size();
+        h->last_chunks = (nq + slots - 1) / slots;
+    } else {
+        for (size_t q0 = 0; q0 < nq; q0 += slots) {
+            p.q0 = (uint32_t)q0;
+            vdb::launch_spv_search(p, (uint32_t)std::min(slots, nq - q0), s);
+            ++h->last_chunks;
+        }
     }
     HIP_TRY(hipGetLastError());
     uint32_t flags[8] = {0};
@@ -193,6 +284,7 @@ int search(vdb_spv_index* h, const size_t* q_offsets, const uint32_t* q_indices,
     Lists d;
     d.ids = h->d_out_ids; d.dists = h->d_out_dists; d.counts = h->d_out_counts; d.stride = kmax;
     if ((rc = copy_out(d, b, s))) return rc;                        // synchronises s: flags are here, too
+    if (by_rows) h->slots_clean = true;                             // every pass has put SPV_NO_SLOT back
     memcpy(&h->last_walked, flags + 2, 8);
     memcpy(&h->last_offered, flags + 4, 8);
     if (flags[0] & vdb::ST_NAN) return fail_nan();
@@ -264,6 +356,8 @@ int vdb_spv_add_bulk(vdb_spv_index* h, const uint64_t* ids, const size_t* offset
         h->row_of[ids[i]] = row;
         h->live_nnz += len;
         if (len) h->vocab = std::max(h->vocab, ni[at + len - 1] + 1);
+        if (h->live_df.size() < h->vocab) h->live_df.resize(h->vocab, 0);
+        for (size_t j = at; j < at + len; ++j) ++h->live_df[ni[j]];
         at += len;
     }
     h->dirty = true;
@@ -329,6 +423,25 @@ int vdb_spv_stats(const vdb_spv_index* h, uint64_t out[8]) {
     out[7] = h->last_chunks;
     return VDB_OK;
 }
+
+int vdb_spv_set_route(vdb_spv_index* h, int mode) {
+    if (!h) return fail(VDB_ERR_INVALID_ARGUMENT, "null handle");
+    if (mode < 0 || mode > 2) return fail(VDB_ERR_INVALID_ARGUMENT, "route %d: 0 (inverted file), 1 (row-major) or 2 (automatic)", mode);
+    std::lock_guard<std::mutex> g(h->mu);
+    h->route = mode;
+    return VDB_OK;
+}
+
+int vdb_spv_route_stats(const vdb_spv_index* h, uint64_t out[4]) {
+    if (!h || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    out[0] = h->last_route;
+    out[1] = h->last_passes;
+    out[2] = h->last_work_inv;
+    out[3] = h->last_work_rows;
+    return VDB_OK;
+}
+
+double vdb_spv_route_rho(void) { return ROUTE_RHO; }
 
 int vdb_spv_debug_set_workspace_cap(vdb_spv_index* h, size_t bytes) {
     if (!h) return fail(VDB_ERR_INVALID_ARGUMENT, "null handle");

@@ -142,6 +142,24 @@ class GpuSparseIndex:
         names = ("rows", "dead_rows", "nnz", "vocab", "rebuilds", "entries_walked", "candidates", "chunks")
         return dict(zip(names, (int(x) for x in out)))
 
+    def set_route(self, mode):
+        """How searches score: 0 the inverted-file walk (default), 1 the row-major route (batches that hold the frequent words),
+        2 whichever has less counted work (route_stats; the factor is route_rho()).  The answers are the same to the bit."""
+        rc = self._L.vdb_spv_set_route(self._h, int(mode))
+        if rc:
+            _raise(rc)
+
+    def route_stats(self):
+        """of the last search: the route taken, its row passes, and the counted work of either route"""
+        out = (ctypes.c_uint64 * 4)()
+        rc = self._L.vdb_spv_route_stats(self._h, out)
+        if rc:
+            _raise(rc)
+        return dict(zip(("route", "passes", "work_inverted", "work_rows"), (int(x) for x in out)))
+
+    def route_rho(self):
+        return float(self._L.vdb_spv_route_rho())
+
     def debug_set_workspace_cap(self, nbytes):
         """Lower the accumulator workspace (tests: several chunks on a small index); 0 restores 256 MiB."""
         rc = self._L.vdb_spv_debug_set_workspace_cap(self._h, int(nbytes))

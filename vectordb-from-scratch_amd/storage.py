@@ -245,6 +245,13 @@ class VectorStore:
         if self._sparse is None:
             self._sparse = GpuSparseIndex(self._index._device)
 
+    def set_sparse_route(self, mode):
+        """How search_sparse / search_hybrid score (GpuSparseIndex.set_route): 0 the inverted-file walk, 1 the row-major route,
+        2 automatic.  The answers do not change."""
+        if self._sparse is None:
+            raise ValueError("enable_sparse() first")
+        self._sparse.set_route(mode)
+
     def insert_with_metadata(self, id, vector, metadata, sparse=None):   # storage.rs:135-172
         id = str(id)
         if sparse is not None and self._sparse is None:
