@@ -25,28 +25,6 @@ namespace vdb {
 constexpr uint32_t DISC_THREADS = 256, DISC_WAVES = DISC_THREADS / 64;
 constexpr uint32_t DISC_NO_RANK = 0xffu;                                   // rank byte of a candidate without a live row
 
-// the first `nthis` of eight example rows as wave-uniform values (the row numbers live in memory every lane reads alike)
-__device__ __forceinline__ void disc_rows8(const uint32_t* src, uint32_t nthis, uint32_t (&q8)[8]) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) q8[j] = j < (int)nthis ? (uint32_t)__builtin_amdgcn_readfirstlane((int)src[j]) : 0u;
-}
-
-// the live device row that holds `id`: binary search in id order, then along the rows of that id
-__device__ __forceinline__ uint32_t disc_row_of(const DiscoverRankParams& p, uint64_t id) {
-    uint32_t lo = 0, hi = p.n_rows;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        const uint32_t r = p.rank2row ? p.rank2row[mid] : mid;
-        if (r < p.n_rows && p.row_ids[r] < id) lo = mid + 1; else hi = mid;
-    }
-    for (; lo < p.n_rows; ++lo) {
-        const uint32_t r = p.rank2row ? p.rank2row[lo] : lo;
-        if (r >= p.n_rows || p.row_ids[r] != id) break;
-        if ((p.live[r >> 5] >> (r & 31)) & 1u) return r;
-    }
-    return NO_ROW;
-}
-
 // ---------------------------------------------------------------------------------------------
 // the list route: ranks of the candidates, the answered rule, the answer
 // ---------------------------------------------------------------------------------------------
@@ -75,7 +53,7 @@ __global__ __launch_bounds__(DISC_THREADS) void discover_rank_kernel(DiscoverRan
     for (uint32_t base = 0; base < count; base += DISC_THREADS) {
         const uint32_t i = base + tid;
         if (i >= count) continue;
-        const uint32_t row = disc_row_of(p, ids[i]);
+        const uint32_t row = live_row_of(p.row_ids, p.rank2row, p.live, p.n_rows, ids[i]);
         if (row == NO_ROW) { atomicOr(p.status, 2u); sRank[i] = (uint8_t)DISC_NO_RANK; continue; }
         const float* x = p.rows + (size_t)row * p.ld;
         const float xn = p.nd[row];
@@ -84,7 +62,7 @@ __global__ __launch_bounds__(DISC_THREADS) void discover_rank_kernel(DiscoverRan
         for (uint32_t c = 0; c < ne; c += 8) {
             const uint32_t nthis = ne - c < 8 ? ne - c : 8;
             uint32_t q8[8];
-            disc_rows8(sEx + c, nthis, q8);
+            uniform_rows8(sEx + c, nthis, q8);
             float s[8];
             fold_multi<8>(p.metric, x, p.dim, p.rows, p.ld, q8, nthis, s);
 #pragma unroll
@@ -156,7 +134,7 @@ __global__ __launch_bounds__(DISC_THREADS) void discover_scan_kernel(DiscoverSca
     for (uint32_t c = 0; c < m; c += 8) {
         const uint32_t nthis = m - c < 8 ? m - c : 8;
         uint32_t q8[8];
-        disc_rows8(p.R.rows + o0 + c, nthis, q8);
+        uniform_rows8(p.R.rows + o0 + c, nthis, q8);
         float s[8];
         fold_multi<8>(p.metric, x, p.dim, p.rows, p.ld, q8, nthis, s);
 #pragma unroll

@@ -305,11 +305,40 @@ __device__ __forceinline__ void fold_multi(int metric, const float* x, uint32_t 
     for (int j = 0; j < NQ; ++j) s[j] = acc[j];
 }
 
+// What the searches by stored examples feed it with (kernels_recommend_best.hip, kernels_discover.hip): the first `nthis` of eight
+// example rows as wave-uniform values (the row numbers live in memory every lane reads alike).
+__device__ __forceinline__ void uniform_rows8(const uint32_t* src, uint32_t nthis, uint32_t (&q8)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) q8[j] = j < (int)nthis ? (uint32_t)__builtin_amdgcn_readfirstlane((int)src[j]) : 0u;
+}
+
+constexpr uint32_t NO_ROW = 0xffffffffu;                          // no row: an id without a live one, an sRowIdx entry of a skipped key
+
+// The live device row that holds `id`, or NO_ROW: binary search in id order (rank2row null: the rows are in id order), then along
+// the rows of that id.
+// (The four arguments are members of the caller's kernel parameters and come by reference, as they did inside the params struct:
+// taken by value, rb_veto_kernel compiles to another block layout of its last lines -- same registers, seven instructions fewer,
+// not the code that was measured.  By reference both callers compile to what they were, instruction for instruction.)
+__device__ __forceinline__ uint32_t live_row_of(const uint64_t* const& row_ids, const uint32_t* const& rank2row, const uint32_t* const& live,
+                                                const uint32_t& n_rows, uint64_t id) {
+    uint32_t lo = 0, hi = n_rows;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        const uint32_t r = rank2row ? rank2row[mid] : mid;
+        if (r < n_rows && row_ids[r] < id) lo = mid + 1; else hi = mid;
+    }
+    for (; lo < n_rows; ++lo) {
+        const uint32_t r = rank2row ? rank2row[lo] : lo;
+        if (r >= n_rows || row_ids[r] != id) break;
+        if ((live[r >> 5] >> (r & 31)) & 1u) return r;
+    }
+    return NO_ROW;
+}
+
 // ---------------------------------------------------------------------------------------------
 // What the exhaustive re-ranks share (rerank_all_kernel, rerank_large_body, range_rerank_kernel): the LDS plan of a staged row,
 // the staging of a chunk of candidate rows with their exact distances, and the sort of (ordered distance, id) pairs.
 // ---------------------------------------------------------------------------------------------
-constexpr uint32_t NO_ROW = 0xffffffffu;                          // sRowIdx entry of a key that is skipped
 
 // floats between two rows staged in LDS: the padded dimension, plus 4 where it is a multiple of 8 (bank spread of the float4 reads)
 __host__ __device__ inline uint32_t rerank_row_stride(uint32_t dim) {

@@ -31,12 +31,6 @@ constexpr uint32_t RB_THREADS = 256, RB_WAVES = RB_THREADS / 64;
 constexpr uint32_t RB_DEAD = 0xffu;                                        // list byte of an entry that left the walk
 constexpr float RB_INF = __builtin_huge_valf();
 
-// the first `nthis` of eight example rows as wave-uniform values (the row numbers live in memory every lane reads alike)
-__device__ __forceinline__ void rb_rows8(const uint32_t* src, uint32_t nthis, uint32_t (&q8)[8]) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) q8[j] = j < (int)nthis ? (uint32_t)__builtin_amdgcn_readfirstlane((int)src[j]) : 0u;
-}
-
 // ---------------------------------------------------------------------------------------------
 // the exact scan
 // ---------------------------------------------------------------------------------------------
@@ -55,7 +49,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_scan_kernel(RbScanParams p) {
     for (uint32_t c = 0; c < m; c += 8) {
         const uint32_t nthis = m - c < 8 ? m - c : 8;
         uint32_t q8[8];
-        rb_rows8(p.R.rows + o0 + c, nthis, q8);
+        uniform_rows8(p.R.rows + o0 + c, nthis, q8);
         float s[8];
         fold_multi<8>(p.metric, x, p.dim, p.rows, p.ld, q8, nthis, s);
 #pragma unroll
@@ -245,22 +239,6 @@ void launch_rb_merge(const RbMergeParams& p, uint32_t n_req, hipStream_t s) {
 // ---------------------------------------------------------------------------------------------
 // the veto
 // ---------------------------------------------------------------------------------------------
-// the live device row that holds `id`: binary search in id order, then along the rows of that id
-__device__ __forceinline__ uint32_t rb_row_of(const RbVetoParams& p, uint64_t id) {
-    uint32_t lo = 0, hi = p.n_rows;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        const uint32_t r = p.rank2row ? p.rank2row[mid] : mid;
-        if (r < p.n_rows && p.row_ids[r] < id) lo = mid + 1; else hi = mid;
-    }
-    for (; lo < p.n_rows; ++lo) {
-        const uint32_t r = p.rank2row ? p.rank2row[lo] : lo;
-        if (r >= p.n_rows || p.row_ids[r] != id) break;
-        if ((p.live[r >> 5] >> (r & 31)) & 1u) return r;
-    }
-    return NO_ROW;
-}
-
 __global__ __launch_bounds__(RB_THREADS) void rb_veto_kernel(RbVetoParams p) {
     __shared__ uint32_t sNeg[RECOMMEND_MAX_EXAMPLES + 8];
     __shared__ uint32_t sWave[RB_WAVES];
@@ -289,7 +267,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_veto_kernel(RbVetoParams p) {
         uint32_t row = NO_ROW;
         if (i < count) {
             id = ids[i]; dp = dps[i];
-            row = rb_row_of(p, id);
+            row = live_row_of(p.row_ids, p.rank2row, p.live, p.n_rows, id);
             if (row == NO_ROW) atomicOr(p.status, 2u);
         }
         bool keep = row != NO_ROW;
@@ -299,7 +277,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_veto_kernel(RbVetoParams p) {
             for (uint32_t c = 0; c < nn; c += 8) {
                 const uint32_t nthis = nn - c < 8 ? nn - c : 8;
                 uint32_t q8[8];
-                rb_rows8(sNeg + c, nthis, q8);
+                uniform_rows8(sNeg + c, nthis, q8);
                 float s[8];
                 fold_multi<8>(p.metric, x, p.dim, p.rows, p.ld, q8, nthis, s);
 #pragma unroll

@@ -135,6 +135,13 @@ struct Stream {
     }
 };
 
+// Waits for a stream when the scope ends, by whichever return: for a function whose uploads or kernels use memory of its frame.
+// Owns nothing.
+struct Drain {
+    hipStream_t s;
+    ~Drain() { (void)hipStreamSynchronize(s); }
+};
+
 struct Event {
     hipEvent_t e = nullptr;
     Event() = default;

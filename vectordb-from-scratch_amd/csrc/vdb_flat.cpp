@@ -803,6 +803,39 @@ static HostSearch of_ids(HostSearch r, const uint64_t* ids, const RecommendReq* 
     return r;
 }
 
+// The front end of the staged searches by stored examples (recommend by best score, discovery), both forms, behind the feature's
+// handle-free argument checks: the handle, the sharded refusal under `name`, the mask and the batch shape; then the lock,
+// limit(kmax) -- the feature's own refusal --, the device, stats = {nq, n_examples, 0 ...}, and an empty batch is answered; then
+// the flush, the n_examples ids as examples() lays them out, their device rows (VDB_ERR_NOT_FOUND, VDB_ERR_DIMENSION_MISMATCH as
+// recommend), and drive(ex_rows, kmax).
+template <class Limit, class Examples, class Drive>
+static int example_search_host(vdb_flat_index* ix, HostSearch& r, const char* name, uint64_t (vdb_flat_index::*stats)[8], size_t n_examples,
+                               Limit&& limit, Examples&& examples, Drive&& drive) {
+    const size_t nq = r.nq;
+    int rc;
+    if (!ix || (nq && !r.counts)) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    if (ix->multi) return refuse_multi(name);
+    if (r.cm) {
+        if ((rc = compiled_mask_check(r.cm, ix->device))) return rc;
+        r.mask_bits = r.cm->bits;
+    }
+    size_t kmax;
+    if ((rc = batch_shape(r, &kmax))) return rc;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (in_flight(ix)) return refuse_in_flight();
+    if ((rc = limit(kmax))) return rc;
+    if ((rc = set_device(ix))) return rc;
+    uint64_t* st = ix->*stats;
+    memset(st, 0, sizeof(ix->*stats));
+    st[0] = nq; st[1] = n_examples;
+    if (nq == 0) return VDB_OK;
+    // staged adds and removes first: an id resolves to what the searches below see
+    if ((rc = flush(ix))) return rc;
+    std::vector<uint32_t> ex_rows;
+    if ((rc = resolve_query_ids(ix, examples(), n_examples, &ex_rows))) return rc;
+    return drive(ex_rows.data(), kmax);
+}
+
 extern "C" {
 
 int vdb_flat_search_batch(vdb_flat_index* ix, const float* queries, size_t nq, size_t dim, const size_t* ks,
@@ -875,33 +908,16 @@ size_t vdb_flat_recommend_best_depth(size_t k, size_t m, size_t len, int stage) 
     return 0;
 }
 
-// The front end of both forms: recommend's argument checks before any lock or device work, then the lock, the flush, the
-// examples' device rows (VDB_ERR_NOT_FOUND, VDB_ERR_DIMENSION_MISMATCH as recommend), then the driver.
+// (the front end of both forms is example_search_host, behind recommend's argument checks)
 static int recommend_best_host(vdb_flat_index* ix, HostSearch r, RecommendReq rec, float* out_neg_dists) {
     return guarded([&]() -> int {
-    const size_t nq = r.nq;
     int rc;
-    if ((rc = recommend_check(&rec, nq))) return rc;
-    if (!ix || (nq && !r.counts)) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
-    if (ix->multi) return refuse_multi("vdb_flat_recommend_best_batch");
-    if (r.cm) {
-        if ((rc = compiled_mask_check(r.cm, ix->device))) return rc;
-        r.mask_bits = r.cm->bits;
-    }
-    size_t kmax;
-    if ((rc = batch_shape(r, &kmax))) return rc;
+    if ((rc = recommend_check(&rec, r.nq))) return rc;
     r.scores = out_neg_dists;
-    std::lock_guard<std::mutex> g(ix->mu);
-    if (in_flight(ix)) return refuse_in_flight();
-    if ((rc = set_device(ix))) return rc;
-    memset(ix->recommend_best_stats, 0, sizeof(ix->recommend_best_stats));
-    ix->recommend_best_stats[0] = nq; ix->recommend_best_stats[1] = rec.total;
-    if (nq == 0) return VDB_OK;
-    // staged adds and removes first: an id resolves to what the searches below see
-    if ((rc = flush(ix))) return rc;
-    std::vector<uint32_t> ex_rows;
-    if ((rc = resolve_query_ids(ix, rec.ids, rec.total, &ex_rows))) return rc;
-    return recommend_best_drive(ix, r, rec, ex_rows.data(), kmax);
+    return example_search_host(ix, r, "vdb_flat_recommend_best_batch", &vdb_flat_index::recommend_best_stats, rec.total,
+        [](size_t) -> int { return VDB_OK; },                      // (its k limit comes behind the ids: recommend_best_drive)
+        [&]() { return rec.ids; },
+        [&](const uint32_t* ex_rows, size_t kmax) { return recommend_best_drive(ix, r, rec, ex_rows, kmax); });
     });
 }
 
@@ -968,43 +984,32 @@ static int discover_check(DiscoverReq* r, size_t nq) {
     return VDB_OK;
 }
 
-// The front end of both forms: the argument checks before any lock or device work, then the lock, the k limit, the flush, the
-// examples' device rows (VDB_ERR_NOT_FOUND, VDB_ERR_DIMENSION_MISMATCH as recommend), then the driver.
+// (the front end of both forms is example_search_host, behind discover_check; the k limit is taken under the lock)
 static int discover_host(vdb_flat_index* ix, HostSearch r, DiscoverReq req, uint32_t* out_ranks) {
     return guarded([&]() -> int {
     const size_t nq = r.nq;
     int rc;
     if ((rc = discover_check(&req, nq))) return rc;
-    if (!ix || (nq && !r.counts)) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
-    if (ix->multi) return refuse_multi("vdb_flat_discover_batch");
-    if (r.cm) {
-        if ((rc = compiled_mask_check(r.cm, ix->device))) return rc;
-        r.mask_bits = r.cm->bits;
-    }
-    size_t kmax;
-    if ((rc = batch_shape(r, &kmax))) return rc;
-    std::lock_guard<std::mutex> g(ix->mu);
-    if (in_flight(ix)) return refuse_in_flight();
-    // (staged adds and removes are counted already: the flush below does not change len)
-    const size_t kcut = std::min(kmax, (size_t)ix->n_live + ix->misfits.size());
-    if (kcut > VDB_DISCOVER_MAX_K)
-        return fail(VDB_ERR_INVALID_ARGUMENT, "a discovery search returns at most %d rows per request, not %zu", VDB_DISCOVER_MAX_K, kcut);
-    if ((rc = set_device(ix))) return rc;
-    memset(ix->discover_stats, 0, sizeof(ix->discover_stats));
-    ix->discover_stats[0] = nq; ix->discover_stats[1] = nq + 2 * req.pairs;
-    if (nq == 0) return VDB_OK;
-    // staged adds and removes first: an id resolves to what the searches below see
-    if ((rc = flush(ix))) return rc;
-    // the examples of every request side by side: the target, then p_1 n_1 p_2 n_2 ...
+    size_t kcut = 0;
     std::vector<uint64_t> ex_ids;
-    ex_ids.reserve(nq + 2 * req.pairs);
-    for (size_t b = 0; b < nq; ++b) {
-        ex_ids.push_back(req.targets[b]);
-        ex_ids.insert(ex_ids.end(), req.pair_ids + 2 * req.offsets[b], req.pair_ids + 2 * req.offsets[b + 1]);
-    }
-    std::vector<uint32_t> ex_rows;
-    if ((rc = resolve_query_ids(ix, ex_ids.data(), ex_ids.size(), &ex_rows))) return rc;
-    return discover_drive(ix, r, req, ex_ids.data(), ex_rows.data(), kcut, out_ranks);
+    return example_search_host(ix, r, "vdb_flat_discover_batch", &vdb_flat_index::discover_stats, nq + 2 * req.pairs,
+        [&](size_t kmax) -> int {
+            // (staged adds and removes are counted already: the flush does not change len)
+            kcut = std::min(kmax, (size_t)ix->n_live + ix->misfits.size());
+            if (kcut > VDB_DISCOVER_MAX_K)
+                return fail(VDB_ERR_INVALID_ARGUMENT, "a discovery search returns at most %d rows per request, not %zu", VDB_DISCOVER_MAX_K, kcut);
+            return VDB_OK;
+        },
+        [&]() {
+            // the examples of every request side by side: the target, then p_1 n_1 p_2 n_2 ...
+            ex_ids.reserve(nq + 2 * req.pairs);
+            for (size_t b = 0; b < nq; ++b) {
+                ex_ids.push_back(req.targets[b]);
+                ex_ids.insert(ex_ids.end(), req.pair_ids + 2 * req.offsets[b], req.pair_ids + 2 * req.offsets[b + 1]);
+            }
+            return ex_ids.data();
+        },
+        [&](const uint32_t* ex_rows, size_t) { return discover_drive(ix, r, req, ex_ids.data(), ex_rows, kcut, out_ranks); });
     });
 }
 

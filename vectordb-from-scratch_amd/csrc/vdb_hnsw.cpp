@@ -975,7 +975,7 @@ int build_speculative(Graph* g, const uint64_t* ids, uint64_t first_id, size_t n
         if (!B.dense) for (size_t i = 0; i < nc; ++i) B.pos[id_of(c0 + i)] = (uint32_t)i;
     };
     // no walk may be in flight when this function returns: it writes the mapped records and reads the mirror
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{sw};
+    const vdbi::Drain drain{sw};
     bool walked[2] = {false, false};                               // did the block of this parity get a walk launch (a graph existed)?
     auto launch_walks = [&](size_t b) -> int {                     // the mirror is up to date and no walk is in flight
         const size_t c0 = b * WALKS, nc = std::min<size_t>(WALKS, n - c0);

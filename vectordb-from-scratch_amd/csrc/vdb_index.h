@@ -103,23 +103,26 @@ struct MmrWs {
     vdbi::DevBuf<uint64_t> outi; vdbi::DevBuf<float> outd, outs;
 };
 
-// What one recommend-by-best-score call owns on the device beside the search workspace (vdb_search.cpp recommend_best_drive,
-// DESIGN.md 4.17): the requests, the stage's selection (requests | first lists | positive rows), the gathered positives, the
-// ranked lists, the candidates of the walk or of the scan's select, the flags, and the answers.
-struct RecBestWs {
-    vdbi::DevBuf<uint32_t> meta, sel, lc, cc, open, answered, outc, stat;
-    vdbi::DevBuf<uint64_t> ids, li, ci, outi, mask_in;
-    vdbi::DevBuf<float> q, ld, cd, outd, outn;
-};
-
-// What one discovery search owns on the device beside the search workspace (vdb_search.cpp discover_drive): the
-// requests, the stage's selection (requests | target rows | offsets of the stage's example sets) and those sets' ids, the
-// gathered targets, the ranked lists with their counts before and after the strike, the scan's key counts, the flags, the
-// status words, and the answers.
-struct DiscoverWs {
-    vdbi::DevBuf<uint32_t> meta, sel, lc, raw, answered, outc, outr, stat, struck;
-    vdbi::DevBuf<uint64_t> ids, sids, li, outi, mask_in;
+// What one staged search by stored examples owns on the device beside the search workspace (vdb_search.cpp, DESIGN.md 4.17 "The
+// staged driver"): the requests and their ids, the stage's selection, the gathered query rows, the ranked lists, the answered
+// flags, the status words, the staged mask, and the answers.  Each of the two searches keeps its own instance on the handle.
+struct StagedWs {
+    vdbi::DevBuf<uint32_t> meta, sel, lc, answered, outc, stat;
+    vdbi::DevBuf<uint64_t> ids, li, outi, mask_in;
     vdbi::DevBuf<float> q, ld, outd;
+};
+// Recommend by best score (recommend_best_drive) adds the candidates of the walk or of the scan's select with
+// their open flags, and the negatives' distances of the answers; its selection is requests | first lists | positive rows.
+struct RecBestWs : StagedWs {
+    vdbi::DevBuf<uint32_t> cc, open;
+    vdbi::DevBuf<uint64_t> ci;
+    vdbi::DevBuf<float> cd, outn;
+};
+// Discovery (discover_drive) adds the ids of the stage's example sets, the list counts before the strike, the
+// struck counter, and the ranks of the answers; its selection is requests | target rows | offsets of the stage's example sets.
+struct DiscoverWs : StagedWs {
+    vdbi::DevBuf<uint32_t> raw, outr, struck;
+    vdbi::DevBuf<uint64_t> sids;
 };
 // A discovery request as the caller passed it, checked by discover_check: request b has the target targets[b] and the pairs
 // [offsets[b], offsets[b + 1]) of pair_ids (two ids each).

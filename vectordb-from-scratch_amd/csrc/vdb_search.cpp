@@ -7,6 +7,7 @@
 #include <limits>
 
 #include "vdb_index.h"
+#include "vdb_stages.h"
 
 namespace vdbi {
 
@@ -95,6 +96,17 @@ static int pre_device_checks(Index* ix, size_t dim, bool batch_too_large) {
     }
     if (batch_too_large) return fail(VDB_ERR_INVALID_ARGUMENT, "batch too large");
     if (ix->dim > 16384) return fail(VDB_ERR_INVALID_ARGUMENT, "dimension %u exceeds the supported 16384", ix->dim);
+    return VDB_OK;
+}
+
+// After a stage that left one flag per request on the device (d_flags[j] belongs to reqs[j]): the one host read of the stage.
+// *left receives the requests whose flag is zero.
+static int read_unanswered(hipStream_t s, const uint32_t* d_flags, const std::vector<uint32_t>& reqs, std::vector<uint32_t>* left) {
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> flag(reqs.size());
+    HIP_TRY(hipMemcpyAsync(flag.data(), d_flags, flag.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *left = unanswered(reqs, flag.data());
     return VDB_OK;
 }
 
@@ -1240,16 +1252,10 @@ int distinct_groups(Index* H, hipStream_t s, const DistinctSearch& search, const
     fp.ids = W.li.p; fp.dists = W.ld.p; fp.counts = W.lc.p;
     fp.codes = a.d_codes; fp.codes_len = a.codes_len; fp.n_answers = (uint32_t)nq; fp.k = (uint32_t)kmax; fp.kstride = (uint32_t)kmax;
     fp.out_ids = W.ai.p; fp.out_dists = W.ad.p; fp.out_codes = W.ac.p; fp.kept = W.kept.p; fp.complete = W.complete.p;
-    std::vector<uint32_t> flag(nq), pending;
+    std::vector<uint32_t> all(nq), pending;
+    for (size_t b = 0; b < nq; ++b) all[b] = (uint32_t)b;
     // the incomplete queries after a collapse (one host read of the flags)
-    auto read_pending = [&]() -> int {
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(flag.data(), W.complete.p, nq * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        pending.clear();
-        for (size_t b = 0; b < nq; ++b) if (!flag[b]) pending.push_back((uint32_t)b);
-        return VDB_OK;
-    };
+    auto read_pending = [&]() -> int { return read_unanswered(s, W.complete.p, all, &pending); };
 
     // ---- stage A
     if ((rc = search(W.q.p, nq, dA, d_mask, mask_bits, W.li.p, W.ld.p, W.lc.p))) return rc;
@@ -1346,7 +1352,7 @@ int per_group_drive(Index* ix, hipStream_t s, const DistinctSearch& search, cons
     std::vector<int32_t> h_codes(slots), wanted;
     std::vector<uint32_t> h_kept(nq), index, pairs, plan;
     // (the uploads below read host vectors of this frame: no return, early ones included, leaves one in flight)
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
+    const Drain drain{s};
     HIP_TRY(hipMemcpyAsync(h_codes.data(), W.ac.p, slots * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(h_kept.data(), W.kept.p, nq * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -1662,19 +1668,81 @@ int search_grouped(Index* ix, Workspace& W, hipStream_t s, const GroupedArgs& a)
 }
 
 // ---------------------------------------------------------------------------------------------
-// Recommend by best score (vdb_flat_recommend_best_batch).  The answer of a request is defined row by row (dp,
-// the kept rule, dn); the driver only decides how it gets there, and every way is exact:
-//   lists  the positives of the requests in hand become one query block (gathered on the device), ONE certified search ranks
-//          them at depth D, rb_merge_kernel walks each request's lists under the frontier proof, rb_veto_kernel applies the
-//          negatives and keeps the first k.  A request is answered when k rows were kept or nothing can lie behind its
-//          candidates.  Stage 0 runs at vdb_flat_recommend_best_depth(.., 0), stage 1 -- the unanswered requests only -- at
-//          (.., 1).
-//   scan   what is still unanswered: rb_scan_kernel writes one key per kept row, the full-scan select emits the first k, the
-//          same veto kernel adds dn.
-// One host read of the flags per list stage; ids and distances stay on the device until the copy-out.
+// The staged searches by stored examples: recommend by best score and discovery (DESIGN.md 4.17 "The staged driver").  The answer
+// of a request is defined row by row; a driver only decides how it gets there, and every way is exact.  The ladder is
+// run_stages (vdb_stages.h): list stages for the requests in hand -- ONE certified search at depth D over a query block gathered
+// on the device, then the feature's own kernels, which flag the requests they could answer -- and the exact scan for what is
+// left.  One host read of the flags per list stage; ids and distances stay on the device until the copy-out.  Each driver
+// keeps its stage bodies; the steps around them are the functions below.
 // ---------------------------------------------------------------------------------------------
-constexpr size_t RB_SCAN_KEYS = (size_t)1 << 25;                   // keys of one scan pass (256 MiB)
+// The first steps: nothing can come back (kcut == 0: every count is 0, *none is set), else the checks of a search of a non-empty
+// store and the id ranks.
+static int staged_begin(Index* ix, const HostSearch& r, size_t kcut, bool* none) {
+    *none = kcut == 0;
+    if (*none) {
+        for (size_t b = 0; b < r.nq; ++b) r.counts[b] = 0;
+        return VDB_OK;
+    }
+    int rc;
+    if ((rc = pre_device_checks(ix, ix->dim, false))) return rc;
+    return ensure_ranks(ix);
+}
 
+// The requests go up: the packed meta words and the example ids; room for nq x kcut answers, the status words cleared, the mask
+// staged.  The uploads read host memory of the caller's frame: the caller holds a Drain.
+static int staged_upload(StagedWs& B, const HostSearch& r, hipStream_t s, const std::vector<uint32_t>& meta, const uint64_t* ids, size_t total,
+                         size_t kcut, const uint64_t** d_mask) {
+    const size_t no = r.nq * kcut;
+    int rc;
+    if ((rc = B.meta.ensure(meta.size())) || (rc = B.ids.ensure(std::max<size_t>(total, 1))) || (rc = B.stat.ensure(2)) ||
+        (rc = B.outi.ensure(no)) || (rc = B.outd.ensure(no)) || (rc = B.outc.ensure(r.nq)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(B.meta.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(B.ids.p, ids, total * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(B.stat.p, 0, 8, s));
+    return stage_mask(B.mask_in, mask_src(r), s, d_mask);
+}
+
+// The exact scan for the requests `reqs`, as many per pass as the key buffer holds: the eligibility mask, the key buffer and the
+// select's areas, the requests into `sel`, then pass(d_rowmask, g0, g) for requests [g0, g0 + g) of sel.
+template <class Pass>
+static int staged_scan(Index* ix, Workspace& W, hipStream_t s, const uint64_t* d_mask, size_t mask_bits, DevBuf<uint32_t>& sel,
+                       const std::vector<uint32_t>& reqs, Pass&& pass) {
+    const size_t nr = reqs.size();
+    const uint32_t n = ix->n_uploaded;
+    const uint32_t* d_rowmask;
+    int rc;
+    if ((rc = eligibility_mask(ix, W, s, d_mask, mask_bits, &d_rowmask))) return rc;
+    const size_t G = scan_pass_width(nr, n, SUPER);
+    if ((rc = sel.ensure(nr)) || (rc = W.w_exact.ensure(G * n)) || (rc = W.w_exsel.ensure((size_t)SUPER * MAX_SELECT + 8)) ||
+        (rc = W.w_cnt.ensure(4 * SUPER + 16)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(sel.p, reqs.data(), nr * 4, hipMemcpyHostToDevice, s));
+    for (size_t g0 = 0; g0 < nr; g0 += G) {
+        pass(d_rowmask, g0, (uint32_t)std::min(G, nr - g0));
+        HIP_TRY(hipGetLastError());
+    }
+    return VDB_OK;
+}
+
+// The last step before the copy-out: the two status words of the call (stat[0] the ST_* bits, stat[1] bit 1 a candidate without
+// a live row).
+static int staged_status(hipStream_t s, const uint32_t* d_stat) {
+    uint32_t status[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(status, d_stat, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (status[1] & 2u) return fail(VDB_ERR_DEVICE, "internal error: a candidate without a live row on the device");
+    if (status[0] & vdb::ST_NAN) return fail_nan();
+    return VDB_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Recommend by best score (vdb_flat_recommend_best_batch): dp, the kept rule, dn.
+//   lists  the query block is the positives of the requests in hand; rb_merge_kernel walks each request's lists under the
+//          frontier proof, rb_veto_kernel applies the negatives and keeps the first k.  A request is answered when k rows were
+//          kept or nothing can lie behind its candidates.  Depths: vdb_flat_recommend_best_depth(.., 0) and (.., 1).
+//   scan   rb_scan_kernel writes one key per kept row, the full-scan select emits the first k, the same veto kernel adds dn.
+// ---------------------------------------------------------------------------------------------
 int recommend_best_drive(Index* ix, const HostSearch& r, const RecommendReq& rec, const uint32_t* ex_rows, size_t kmax) {
     RecBestWs& B = ix->rbw;
     Workspace& W = ix->wsv[0];                                     // (nothing is in flight)
@@ -1684,39 +1752,29 @@ int recommend_best_drive(Index* ix, const HostSearch& r, const RecommendReq& rec
     const size_t len = ix->n_live + ix->misfits.size();
     const size_t kcut = std::min(kmax, len);
     int rc;
-    if (kcut == 0) {
-        for (size_t b = 0; b < nq; ++b) r.counts[b] = 0;
-        return VDB_OK;
-    }
+    bool none;
     if (kcut > vdb::RB_MAX_ROWS)
         return fail(VDB_ERR_INVALID_ARGUMENT, "a recommend by best score returns at most %u rows per request, not %zu", vdb::RB_MAX_ROWS, kcut);
-    if ((rc = pre_device_checks(ix, dim, false))) return rc;
-    if ((rc = ensure_ranks(ix))) return rc;
+    if ((rc = staged_begin(ix, r, kcut, &none)) || none) return rc;
     const uint32_t n = ix->n_uploaded;
     const size_t D0 = vdb_flat_recommend_best_depth(kcut, rec.mmax, len, 0), D1 = vdb_flat_recommend_best_depth(kcut, rec.mmax, len, 1);
     st[5] = D0;
 
-    // ---- the requests go up: offsets [nq + 1] | n_pos [nq] | k [nq] | rows [total], and the ids
-    const size_t o_np = nq + 1, o_k = o_np + nq, o_row = o_k + nq, words = o_row + total;
-    std::vector<uint32_t> meta(words);
+    // ---- the requests: offsets [nq + 1] | n_pos [nq] | k [nq] | rows [total], and the ids
+    const size_t o_np = nq + 1, o_k = o_np + nq, o_row = o_k + nq;
+    std::vector<uint32_t> meta(o_row + total);
     for (size_t b = 0; b <= nq; ++b) meta[b] = (uint32_t)rec.offsets[b];
     for (size_t b = 0; b < nq; ++b) {
         meta[o_np + b] = rec.n_pos[b];
         meta[o_k + b] = (uint32_t)std::min(r.ks ? r.ks[b] : r.k, kcut);
     }
     memcpy(meta.data() + o_row, ex_rows, total * 4);
-    const size_t no = nq * kcut;
-    if ((rc = B.meta.ensure(words)) || (rc = B.ids.ensure(std::max<size_t>(total, 1))) || (rc = B.stat.ensure(2)) ||
-        (rc = B.outi.ensure(no)) || (rc = B.outd.ensure(no)) || (rc = B.outn.ensure(no)) || (rc = B.outc.ensure(nq)))
-        return rc;
-    // (the uploads below read host vectors of this frame: no return, early ones included, leaves one in flight)
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
-    HIP_TRY(hipMemcpyAsync(B.meta.p, meta.data(), words * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(B.ids.p, rec.ids, total * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(B.stat.p, 0, 8, s));
-    const vdb::RbRequests R{B.meta.p, B.meta.p + o_np, B.meta.p + o_k, B.meta.p + o_row, B.ids.p};
+    if ((rc = B.outn.ensure(nq * kcut))) return rc;
+    // (the uploads read host vectors of this frame: no return, early ones included, leaves one in flight)
+    const Drain drain{s};
     const uint64_t* d_mask;
-    if ((rc = stage_mask(B.mask_in, mask_src(r), s, &d_mask))) return rc;
+    if ((rc = staged_upload(B, r, s, meta, rec.ids, total, kcut, &d_mask))) return rc;
+    const vdb::RbRequests R{B.meta.p, B.meta.p + o_np, B.meta.p + o_k, B.meta.p + o_row, B.ids.p};
 
     auto veto_params = [&]() {
         vdb::RbVetoParams vp{};
@@ -1756,27 +1814,14 @@ int recommend_best_drive(Index* ix, const HostSearch& r, const RecommendReq& rec
         vdb::RbVetoParams vp = veto_params();
         vp.sel = B.sel.p; vp.open = B.open.p; vp.cand_stride = (uint32_t)cs; vp.answered = B.answered.p;
         vdb::launch_rb_veto(vp, (uint32_t)nr, s);
-        HIP_TRY(hipGetLastError());
-        std::vector<uint32_t> flag(nr);
-        HIP_TRY(hipMemcpyAsync(flag.data(), B.answered.p, nr * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        left->clear();
-        for (size_t j = 0; j < nr; ++j) if (!flag[j]) left->push_back(reqs[j]);
-        return VDB_OK;
+        return read_unanswered(s, B.answered.p, reqs, left);
     };
 
-    // ---- the exact scan for the requests `reqs`, as many per pass as the key buffer holds
+    // ---- the exact scan for the requests `reqs`: the select's answers are the veto's candidates
     auto run_scan = [&](const std::vector<uint32_t>& reqs) -> int {
-        const size_t nr = reqs.size();
-        const uint32_t* d_rowmask;
-        if ((rc = eligibility_mask(ix, W, s, d_mask, r.mask_bits, &d_rowmask))) return rc;
-        const size_t G = std::min<size_t>(std::min<size_t>(nr, SUPER), std::max<size_t>(RB_SCAN_KEYS / std::max<uint32_t>(n, 1), 1));
-        if ((rc = B.sel.ensure(nr)) || (rc = W.w_exact.ensure(G * n)) || (rc = W.w_exsel.ensure((size_t)SUPER * MAX_SELECT + 8)) ||
-            (rc = W.w_cnt.ensure(4 * SUPER + 16)) || (rc = B.ci.ensure(G * kcut)) || (rc = B.cd.ensure(G * kcut)) || (rc = B.cc.ensure(G)))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(B.sel.p, reqs.data(), nr * 4, hipMemcpyHostToDevice, s));
-        for (size_t g0 = 0; g0 < nr; g0 += G) {
-            const uint32_t g = (uint32_t)std::min(G, nr - g0);
+        const size_t G = scan_pass_width(reqs.size(), n, SUPER);
+        if ((rc = B.ci.ensure(G * kcut)) || (rc = B.cd.ensure(G * kcut)) || (rc = B.cc.ensure(G))) return rc;
+        return staged_scan(ix, W, s, d_mask, r.mask_bits, B.sel, reqs, [&](const uint32_t* d_rowmask, size_t g0, uint32_t g) {
             vdb::RbScanParams sp{rows_f32(ix), ix->ld, ix->dim, n, ix->metric, ix->d_nd, d_rowmask,
                                  ix->ids_monotone ? nullptr : ix->d_idrank.p, R, B.sel.p + g0, W.w_exact.p, n, B.stat.p};
             vdb::launch_rb_scan(sp, g, s);
@@ -1787,47 +1832,21 @@ int recommend_best_drive(Index* ix, const HostSearch& r, const RecommendReq& rec
             vdb::RbVetoParams vp = veto_params();
             vp.sel = B.sel.p + g0; vp.open = nullptr; vp.cand_stride = (uint32_t)kcut; vp.answered = nullptr;
             vdb::launch_rb_veto(vp, g, s);
-            HIP_TRY(hipGetLastError());
-        }
-        return VDB_OK;
+        });
     };
 
-    std::vector<uint32_t> todo(nq), left;
-    for (size_t b = 0; b < nq; ++b) todo[b] = (uint32_t)b;
-    // (automatic: lists whose depth is the whole index are the expensive way to scan it)
-    const bool lists = ix->rb_route == 1 || (ix->rb_route == 0 && D0 < len);
-    if (lists) {
-        if ((rc = run_lists(todo, D0, &left))) return rc;
-        st[2] = todo.size() - left.size();
-        todo.swap(left);
-        if (!todo.empty() && D1 > D0) {
-            if ((rc = run_lists(todo, D1, &left))) return rc;
-            st[3] = todo.size() - left.size();
-            todo.swap(left);
-        }
-    }
-    if (!todo.empty()) {
-        if ((rc = run_scan(todo))) return rc;
-        st[4] = todo.size();
-    }
-    uint32_t status[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(status, B.stat.p, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (status[1] & 2u) return fail(VDB_ERR_DEVICE, "internal error: a candidate without a live row on the device");
-    if (status[0] & vdb::ST_NAN) return fail_nan();
+    if ((rc = run_stages(nq, D0, D1, len, ix->rb_route, st, run_lists, run_scan))) return rc;
+    if ((rc = staged_status(s, B.stat.p))) return rc;
     return copy_out(Lists{B.outi.p, B.outd.p, B.outc.p, nullptr, kcut, B.outn.p}, r, s);
 }
 
 // ---------------------------------------------------------------------------------------------
-// Discovery search (vdb_flat_discover_batch).  The answer of a request is defined row by row (rank, d(t, x));
-// the driver only decides how it gets there, and every way is exact:
-//   lists  the targets of the requests in hand become one query block (gathered on the device), ONE certified search ranks
-//          the store for each at depth D, the set strike removes every request's examples, discover_rank_kernel counts the
-//          satisfied pairs of every candidate and writes the answer of a request that has k rows of rank P or a complete
-//          list.  Stage 0 runs at vdb_flat_discover_depth(.., 0), stage 1 -- the unanswered requests only -- at (.., 1).
-//   scan   what is still unanswered: discover_scan_kernel writes one key per eligible row, the full-scan select sorts the first
-//          k, discover_emit_kernel takes them apart.
-// One host read of the flags per list stage; ids and distances stay on the device until the copy-out.
+// Discovery search (vdb_flat_discover_batch): rank, d(t, x).
+//   lists  the query block is the targets of the requests in hand; the set strike removes every request's examples,
+//          discover_rank_kernel counts the satisfied pairs of every candidate and writes the answer of a request that has k rows
+//          of rank P or a complete list.  Depths: vdb_flat_discover_depth(.., 0) and (.., 1).
+//   scan   discover_scan_kernel writes one key per eligible row, the full-scan select sorts the first k, discover_emit_kernel
+//          takes them apart.
 // ---------------------------------------------------------------------------------------------
 int discover_drive(Index* ix, const HostSearch& r, const DiscoverReq& req, const uint64_t* ex_ids, const uint32_t* ex_rows, size_t kcut,
                    uint32_t* out_ranks) {
@@ -1838,34 +1857,24 @@ int discover_drive(Index* ix, const HostSearch& r, const DiscoverReq& req, const
     const size_t nq = r.nq, total = nq + 2 * req.pairs, dim = ix->dim;
     const size_t len = ix->n_live + ix->misfits.size();
     int rc;
-    if (kcut == 0) {
-        for (size_t b = 0; b < nq; ++b) r.counts[b] = 0;
-        return VDB_OK;
-    }
-    if ((rc = pre_device_checks(ix, dim, false))) return rc;
-    if ((rc = ensure_ranks(ix))) return rc;
+    bool none;
+    if ((rc = staged_begin(ix, r, kcut, &none)) || none) return rc;
     const uint32_t n = ix->n_uploaded;
     const size_t D0 = vdb_flat_discover_depth(kcut, req.pmax, len, 0), D1 = vdb_flat_discover_depth(kcut, req.pmax, len, 1);
     st[5] = D0;
 
-    // ---- the requests go up: offsets [nq + 1] | k [nq] | rows [total], and the ids
-    const size_t o_k = nq + 1, o_row = o_k + nq, words = o_row + total;
-    std::vector<uint32_t> meta(words);
+    // ---- the requests: offsets [nq + 1] | k [nq] | rows [total], and the ids
+    const size_t o_k = nq + 1, o_row = o_k + nq;
+    std::vector<uint32_t> meta(o_row + total);
     for (size_t b = 0; b <= nq; ++b) meta[b] = (uint32_t)(b + 2 * req.offsets[b]);
     for (size_t b = 0; b < nq; ++b) meta[o_k + b] = (uint32_t)std::min(r.ks ? r.ks[b] : r.k, kcut);
     memcpy(meta.data() + o_row, ex_rows, total * 4);
-    const size_t no = nq * kcut;
-    if ((rc = B.meta.ensure(words)) || (rc = B.ids.ensure(total)) || (rc = B.stat.ensure(2)) || (rc = B.outi.ensure(no)) ||
-        (rc = B.outd.ensure(no)) || (rc = B.outr.ensure(no)) || (rc = B.outc.ensure(nq)))
-        return rc;
-    // (the uploads below read host vectors of this frame: no return, early ones included, leaves one in flight)
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
-    HIP_TRY(hipMemcpyAsync(B.meta.p, meta.data(), words * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(B.ids.p, ex_ids, total * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(B.stat.p, 0, 8, s));
-    const vdb::DiscoverRequests R{B.meta.p, B.meta.p + o_k, B.meta.p + o_row, B.ids.p};
+    if ((rc = B.outr.ensure(nq * kcut))) return rc;
+    // (the uploads read host vectors of this frame: no return, early ones included, leaves one in flight)
+    const Drain drain{s};
     const uint64_t* d_mask;
-    if ((rc = stage_mask(B.mask_in, mask_src(r), s, &d_mask))) return rc;
+    if ((rc = staged_upload(B, r, s, meta, ex_ids, total, kcut, &d_mask))) return rc;
+    const vdb::DiscoverRequests R{B.meta.p, B.meta.p + o_k, B.meta.p + o_row, B.ids.p};
     const uint32_t* d_rank2row = ix->ids_monotone ? nullptr : ix->d_rank2row.p;
 
     // ---- a list stage for the requests `reqs` at depth D; *left receives those it could not answer
@@ -1907,30 +1916,15 @@ int discover_drive(Index* ix, const HostSearch& r, const DiscoverReq& req, const
         rp.out_ids = B.outi.p; rp.out_dists = B.outd.p; rp.out_ranks = B.outr.p; rp.out_counts = B.outc.p; rp.kout = (uint32_t)kcut;
         rp.answered = B.answered.p; rp.status = B.stat.p + 1;
         vdb::launch_discover_rank(rp, (uint32_t)nr, s);
-        HIP_TRY(hipGetLastError());
-        std::vector<uint32_t> flag(nr);
-        HIP_TRY(hipMemcpyAsync(flag.data(), B.answered.p, nr * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        left->clear();
-        for (size_t j = 0; j < nr; ++j) if (!flag[j]) left->push_back(reqs[j]);
-        return VDB_OK;
+        return read_unanswered(s, B.answered.p, reqs, left);
     };
 
-    // ---- the exact scan for the requests `reqs`, as many per pass as the key buffer holds
+    // ---- the exact scan for the requests `reqs`
     auto run_scan = [&](const std::vector<uint32_t>& reqs) -> int {
-        const size_t nr = reqs.size();
         if (n >> vdb::DISCOVER_KEY_ID_BITS)
             return fail(VDB_ERR_INVALID_ARGUMENT, "the exact scan of a discovery search keys at most 2^%u - 1 rows, the store holds %u",
                         vdb::DISCOVER_KEY_ID_BITS, n);
-        const uint32_t* d_rowmask;
-        if ((rc = eligibility_mask(ix, W, s, d_mask, r.mask_bits, &d_rowmask))) return rc;
-        const size_t G = std::min<size_t>(std::min<size_t>(nr, SUPER), std::max<size_t>(RB_SCAN_KEYS / std::max<uint32_t>(n, 1), 1));
-        if ((rc = B.sel.ensure(nr)) || (rc = W.w_exact.ensure(G * n)) || (rc = W.w_exsel.ensure((size_t)SUPER * MAX_SELECT + 8)) ||
-            (rc = W.w_cnt.ensure(4 * SUPER + 16)))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(B.sel.p, reqs.data(), nr * 4, hipMemcpyHostToDevice, s));
-        for (size_t g0 = 0; g0 < nr; g0 += G) {
-            const uint32_t g = (uint32_t)std::min(G, nr - g0);
+        return staged_scan(ix, W, s, d_mask, r.mask_bits, B.sel, reqs, [&](const uint32_t* d_rowmask, size_t g0, uint32_t g) {
             vdb::DiscoverScanParams sp{rows_f32(ix), ix->ld, ix->dim, n, ix->metric, ix->d_nd, d_rowmask,
                                        ix->ids_monotone ? nullptr : ix->d_idrank.p, R, B.sel.p + g0, W.w_exact.p, n, B.stat.p};
             vdb::launch_discover_scan(sp, g, s);
@@ -1942,34 +1936,11 @@ int discover_drive(Index* ix, const HostSearch& r, const DiscoverReq& req, const
             vdb::DiscoverEmitParams ep{W.w_exsel.p, W.w_cnt.p, MAX_SELECT, R, B.sel.p + g0, d_rank2row, ix->d_row_ids, n,
                                        B.outi.p, B.outd.p, B.outr.p, B.outc.p, (uint32_t)kcut, B.stat.p + 1};
             vdb::launch_discover_emit(ep, g, s);
-            HIP_TRY(hipGetLastError());
-        }
-        return VDB_OK;
+        });
     };
 
-    std::vector<uint32_t> todo(nq), left;
-    for (size_t b = 0; b < nq; ++b) todo[b] = (uint32_t)b;
-    // (automatic: a list whose depth is the whole index is the expensive way to scan it)
-    const bool lists = ix->discover_route == 1 || (ix->discover_route == 0 && D0 < len);
-    if (lists) {
-        if ((rc = run_lists(todo, D0, &left))) return rc;
-        st[2] = todo.size() - left.size();
-        todo.swap(left);
-        if (!todo.empty() && D1 > D0) {
-            if ((rc = run_lists(todo, D1, &left))) return rc;
-            st[3] = todo.size() - left.size();
-            todo.swap(left);
-        }
-    }
-    if (!todo.empty()) {
-        if ((rc = run_scan(todo))) return rc;
-        st[4] = todo.size();
-    }
-    uint32_t status[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(status, B.stat.p, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (status[1] & 2u) return fail(VDB_ERR_DEVICE, "internal error: a candidate without a live row on the device");
-    if (status[0] & vdb::ST_NAN) return fail_nan();
+    if ((rc = run_stages(nq, D0, D1, len, ix->discover_route, st, run_lists, run_scan))) return rc;
+    if ((rc = staged_status(s, B.stat.p))) return rc;
     // (the ranks travel in the copy-out's 32-bit column: the same bits, read back as uint32_t)
     Batch out = r;
     out.codes = reinterpret_cast<int32_t*>(out_ranks);
@@ -2022,7 +1993,7 @@ int maxsim_drive(Index* ix, const HostSearch& r, const MaxsimReq& req, const int
         (rc = W.w_exsel.ensure((size_t)SUPER * MAX_SELECT + 8)) || (rc = W.w_cnt.ensure(4 * SUPER + 16)))
         return rc;
     // (the uploads below read host memory of this frame: no return, early ones included, leaves one in flight)
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
+    const Drain drain{s};
     HIP_TRY(hipMemcpyAsync(B.q.p, req.tokens, total * dim * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(B.meta.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(B.ctr.p, 0, 32, s));
