@@ -791,6 +791,19 @@ int vdb_flat_debug_maxsim_lower_bounds(vdb_flat_index *h, float *out /* [nq][n_c
  * vdb_spv_route_stats, of the last search: [0] the route taken (0 / 1)  [1] row passes launched (0 on route 0)  [2] the inverted
  * route's counted work: the sum over queries and queried indices of the live list length  [3] the row-major route's: live
  * non-zeros times the number of 64-query tiles.  vdb_spv_stats [5] - [7] are the same numbers on both routes.
+ * vdb_spv_set_segmented: HOW the inverted route walks; the answers are the same to the bit.  0 (the default): one workgroup per
+ * query, as above.  A power of two R in [64, VDB_SPV_SEG_ROWS_MAX]: the SEGMENTED walk (csrc/kernels_spv_seg.hip, DESIGN.md
+ * 4.20.2) for requests of a few queries, which one workgroup each cannot spread over the device.  The rows are cut into segments
+ * of R consecutive CSR rows and the inverted file is ordered by (index, segment), still one contiguous list per index; one
+ * workgroup serves one (query, segment) pair with the segment's accumulators in LDS -- the same ascending fold, a linear emit
+ * with no second walk and no global accumulator --, and one workgroup per query merges the segments' partial top-k lists (keys
+ * are unique: the merge is exact).  Wherever route 0 would run (mode 0, or mode 2 choosing it) the segmented walk runs instead,
+ * if the store has at least two segments (and at most 2^21), an index, and a sub-list table of vocab * segments + 1 words within
+ * 2^26; else the file is built and walked as without the option, which is no error.  vdb_spv_route_stats [0] stays 0 for it, and
+ * vdb_spv_stats [5] - [7] are the one-workgroup walk's numbers.  Changing the value makes an inverted file in place stale: the
+ * next flush or search rebuilds it (vdb_spv_stats [4]).  Any other value is VDB_ERR_INVALID_ARGUMENT.
+ * vdb_spv_segment_stats, of the last search: [0] 1 if the segmented walk ran  [1] its segments  [2] rows per segment  [3] the
+ * (query, segment) workgroups that found at least one posting.
  * vdb_spv_stats: [0] rows stored, live + dead  [1] dead rows  [2] stored non-zeros, dead rows included  [3] vocabulary bound
  * (1 + the largest index ever stored)  [4] rebuilds of the inverted file  [5] list entries walked by the last search (each entry
  * once: the sum of the queried lists' lengths)  [6] candidates offered to the select by the last search  [7] its chunks.
@@ -818,6 +831,9 @@ int vdb_spv_debug_set_workspace_cap(vdb_spv_index *h, size_t bytes);
 int vdb_spv_set_route(vdb_spv_index *h, int mode);
 int vdb_spv_route_stats(const vdb_spv_index *h, uint64_t out[4]);
 double vdb_spv_route_rho(void);
+#define VDB_SPV_SEG_ROWS_MAX 16384
+int vdb_spv_set_segmented(vdb_spv_index *h, size_t rows_per_segment);
+int vdb_spv_segment_stats(const vdb_spv_index *h, uint64_t out[4]);
 
 /*
  * DIVERSE TOP-K (MAXIMAL MARGINAL RELEVANCE): k results that are not all the same thing (no reference counterpart; a caller would

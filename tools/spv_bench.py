@@ -8,7 +8,11 @@ each are recorded.  Writes one JSON object to --out and prints it.
 baseline in one process, once per --query-min-rank R given (query indices drawn from the words of frequency rank >= R only: 0 is
 the Zipf workload, 1000 one off the head of the distribution), records both routes' counted work, interpolates in log space the
 ratio of the two counts at which the routes' times cross (rho) when two workloads fall on either side of it, and adds k = 1024
-and a half-selective id mask on the first workload."""
+and a half-selective id mask on the first workload.
+
+--segmented measures the segmented inverted walk (vdb_spv_set_segmented) at 4096, 8192 and 16384 rows per segment against the
+one-workgroup walk, route 1 and the baseline, alternating, at 1, 4, 16 and 256 queries of every --query-min-rank, and the flush
+times with the option off and on."""
 import argparse
 import importlib.util
 import json
@@ -76,6 +80,69 @@ def both_routes(ix, queries, k, rounds, base=None, **mask):
     return rec
 
 
+SEG_ROWS, SEG_BATCHES = (4096, 8192, 16384), (1, 4, 16, 256)
+
+
+def segmented_arms(vdb, a, ids, offs, idx, val, rng):
+    """--segmented: the one-workgroup walk, the segmented walk at each of SEG_ROWS rows per segment (a handle each: a change of the
+    setting rebuilds the file), route 1 and torch.sparse.mm + topk, alternating in one process, per query set (--query-min-rank)
+    and batch size; and the flush times with the option off and on.  The arms' answers must be equal."""
+    arms, rec = {}, {"shape": {"rows": a.rows, "vocab": a.vocab, "nnz": int(idx.size), "k": a.k, "rounds": a.rounds}, "flush": {}, "runs": []}
+    for name, R in [("old_walk", 0)] + [("segmented_%d" % R, R) for R in SEG_ROWS]:
+        ix = arms[name] = vdb.GpuSparseIndex()
+        ix.set_segmented(R)
+        ix.add_csr(ids, offs, idx, val)
+        t0 = time.perf_counter()
+        ix.flush()
+        t1 = time.perf_counter()
+        ix.remove(a.rows - 1)
+        t2 = time.perf_counter()
+        ix.flush()
+        rec["flush"][name] = {"first_flush_s": t1 - t0, "flush_after_one_remove_s": time.perf_counter() - t2}
+    arms["route1"] = arms["old_walk"]                    # the same handle: the route is set per call
+    print(json.dumps(rec["flush"]), flush=True)
+    import torch
+    dev, live = torch.device("cuda:0"), a.rows - 1
+    csr = torch.sparse_csr_tensor(torch.from_numpy(offs[:live + 1].astype(np.int64)), torch.from_numpy(idx[:offs[live]].astype(np.int64)),
+                                  torch.from_numpy(val[:offs[live]]), size=(live, a.vocab), device=dev)
+
+    def call(name, queries, qd):
+        t0 = time.perf_counter()
+        if name == "torch":
+            top = torch.topk(torch.sparse.mm(csr, qd.to(dev)).t(), a.k, dim=1)
+            r = (top.indices.cpu().numpy().astype(np.uint64),)
+        else:
+            arms[name].set_route(1 if name == "route1" else 0)
+            r = arms[name].search_batch_arrays(queries, a.k)   # ends in a stream synchronise and the copy of the answers
+        return (time.perf_counter() - t0) * 1e3, r
+
+    for rank in a.query_min_rank:
+        qoffs, qidx, qval = zipf_queries(rng, max(SEG_BATCHES), a.vocab, a.query_draws, rank)
+        for nq in SEG_BATCHES:
+            queries = [(qidx[qoffs[b]:qoffs[b + 1]], qval[qoffs[b]:qoffs[b + 1]]) for b in range(nq)]
+            qd = np.zeros((a.vocab, nq), dtype=np.float32)
+            for b, (qi, qv) in enumerate(queries):
+                qd[qi, b] = qv
+            qd = torch.from_numpy(qd)
+            names = list(arms) + ["torch"]
+            for _ in range(2):
+                for name in names:
+                    call(name, queries, qd)
+            t, last = {name: [] for name in names}, {}
+            for _ in range(a.rounds):
+                for name in names:
+                    ms, last[name] = call(name, queries, qd)
+                    t[name].append(ms)
+            ref = last["old_walk"]
+            run = {"query_min_rank": rank, "queries": nq, "times": {name: spread(t[name]) for name in names},
+                   "answers_equal": bool(all(np.array_equal(x.view(np.uint8), y.view(np.uint8)) for name in arms for x, y in zip(ref, last[name]))),
+                   "torch_mean_shared_ids_of_k": float(np.mean([np.isin(last["torch"][0][b], ref[0][b]).sum() for b in range(nq)])),
+                   "segments": {name: arms[name].segment_stats() for name in arms if name.startswith("segmented")}}
+            rec["runs"].append(run)
+            print(json.dumps(run), flush=True)
+    return rec
+
+
 def spread(ms):
     return {"median_ms": float(np.median(ms)), "min_ms": float(min(ms)), "max_ms": float(max(ms)), "runs": len(ms)}
 
@@ -91,6 +158,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--route", default="0", choices=["0", "1", "2", "both"])
     ap.add_argument("--query-min-rank", type=int, nargs="+", default=[0])
+    ap.add_argument("--segmented", action="store_true", help="the arms of vdb_spv_set_segmented (segmented_arms)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "spv_bench.json"))
     a = ap.parse_args()
     vdb = load_package()
@@ -104,6 +172,12 @@ def main():
     print(f"data: {idx.size} non-zeros in {a.rows} rows, {qidx.size} in {a.queries} queries, {time.perf_counter() - t:.1f} s", flush=True)
     queries = [(qidx[qoffs[b]:qoffs[b + 1]], qval[qoffs[b]:qoffs[b + 1]]) for b in range(a.queries)]
     ids = np.arange(a.rows, dtype=np.uint64)
+    if a.segmented:
+        rec = segmented_arms(vdb, a, ids, offs, idx, val, rng)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(rec, f, indent=1)
+        return
     ix = vdb.GpuSparseIndex()
     if a.route != "both":
         ix.set_route(int(a.route))

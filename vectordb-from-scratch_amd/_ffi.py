@@ -26,6 +26,7 @@ SYMBOLS = [
     "vdb_flat_set_maxsim_screen", "vdb_flat_debug_maxsim_lower_bounds",
     "vdb_spv_create", "vdb_spv_destroy", "vdb_spv_add_bulk", "vdb_spv_remove", "vdb_spv_len", "vdb_spv_flush", "vdb_spv_search_batch",
     "vdb_spv_search_batch_filtered", "vdb_spv_stats", "vdb_spv_debug_set_workspace_cap", "vdb_spv_set_route", "vdb_spv_route_stats", "vdb_spv_route_rho",
+    "vdb_spv_set_segmented", "vdb_spv_segment_stats",
     "vdb_flat_search_batch_mmr", "vdb_flat_search_batch_mmr_filtered", "vdb_flat_mmr_stats",
     "vdb_flat_search_batch_distinct", "vdb_flat_search_batch_distinct_filtered", "vdb_flat_distinct_stats", "vdb_flat_distinct_depth",
     "vdb_flat_search_batch_grouped", "vdb_flat_search_batch_grouped_filtered", "vdb_flat_grouped_stats", "vdb_flat_debug_group_plan",
@@ -217,6 +218,8 @@ def lib():
     L.vdb_spv_route_stats.argtypes = [vp, u64p]
     L.vdb_spv_route_rho.argtypes = []
     L.vdb_spv_route_rho.restype = c.c_double
+    L.vdb_spv_set_segmented.argtypes = [vp, sz]
+    L.vdb_spv_segment_stats.argtypes = [vp, u64p]
     L.vdb_flat_search_batch_mmr.argtypes = [vp, fp, sz, sz, szp, sz, sz, fp, c.c_float, u64p, sz, sz, u64p, fp, fp, szp]
     L.vdb_flat_search_batch_mmr_filtered.argtypes = [vp, fp, sz, sz, szp, sz, sz, fp, c.c_float, vp, sz, u64p, fp, fp, szp]
     L.vdb_flat_mmr_stats.argtypes = [vp, u64p]

@@ -23,12 +23,15 @@ void launch_spv_fill(uint32_t* words, size_t n, uint32_t value, hipStream_t s);
 
 // The inverted file from the CSR rows, live rows only.  The host guarantees: row_ptr is monotone with row_ptr[n_rows] entries in
 // idx / val, every idx[e] < vocab, and the number of entries of live rows is below 2^32.
+// With segs > 1 (the segmented file below) the histogram and the scatter key an entry by index * segs + (row >> seg_shift), and
+// counts / list_ptr are the caller's tables over vocab * segs keys.
 struct SpvBuildParams {
     const uint32_t* row_ptr; const uint32_t* idx; const float* val; const uint32_t* live; uint32_t n_rows;
     uint32_t vocab;
     uint32_t* counts;                                  // [vocab]: zero before the histogram; the scan leaves it zero for the scatter's cursors
     uint32_t* list_ptr;                                // [vocab + 1]
     SpvEntry* entries;                                 // [list_ptr[vocab]]
+    uint32_t segs, seg_shift;                          // 0 or 1 segment: keyed by the index alone
 };
 void launch_spv_histogram(const SpvBuildParams& p, hipStream_t s);
 void launch_spv_scan(const SpvBuildParams& p, hipStream_t s);
@@ -77,5 +80,29 @@ void launch_spv_rows_slots(const SpvRowsParams& p, bool set, hipStream_t s);   /
 void launch_spv_rows_table(const SpvRowsParams& p, hipStream_t s);             // the table: SPV_ABSENT, then the pairs
 void launch_spv_rows_fold(const SpvRowsParams& p, hipStream_t s);
 void launch_spv_rows_emit(const SpvRowsParams& p, hipStream_t s);
+
+// ---------------------------------------------------------------- the segmented inverted walk (kernels_spv_seg.hip)
+// The rows are cut into `segs` segments of seg_rows = 1 << seg_shift consecutive rows, and the postings are ordered by the key
+// (index, segment): sub_ptr[index * segs + segment] is where that segment's slice of the index's list starts, so that
+// list_ptr[index] = sub_ptr[index * segs] and the lists stay what the one-workgroup walk reads.
+constexpr uint32_t SPV_SEG_ROWS_MIN = 64, SPV_SEG_ROWS_MAX = 16384;   // rows per segment: a power of two (the accumulators: 4 B each in LDS)
+constexpr uint64_t SPV_SEG_TABLE_MAX = 1ull << 26;                    // words of sub_ptr; a larger table is not built (the file stays unsegmented)
+constexpr uint32_t SPV_SEG_SCAN_TILE = 4096;                          // keys per workgroup of the scan
+
+// sub_ptr[n_keys + 1] = the exclusive scan of counts[n_keys], which is left zero (the scatter's cursors), by
+// ceil(n_keys / SPV_SEG_SCAN_TILE) workgroups; tiles[2 * that + 1] is scratch.  n_keys > 0.
+void launch_spv_seg_scan(uint32_t* counts, uint32_t* sub_ptr, uint32_t n_keys, uint32_t* tiles, hipStream_t s);
+// list_ptr[d] = sub_ptr[d * segs], d <= vocab
+void launch_spv_seg_lists(const uint32_t* sub_ptr, uint32_t segs, uint32_t vocab, uint32_t* list_ptr, hipStream_t s);
+
+// One workgroup per (segment, query y < nq of a launch; query b = q.q0 + y of the batch): fold into LDS, emit, select; then one
+// workgroup per query merges the segments' partial lists.  q.acc is not used.
+struct SpvSegParams {
+    SpvSearchParams q;
+    const uint32_t* sub_ptr; uint32_t segs, seg_shift;
+    uint64_t* part; uint32_t* part_cnt;                // part[(y * segs + segment) * q.kout + i], i < part_cnt[y * segs + segment] <= k of the query
+};                                                     // q.counters[2] += the workgroups that met a posting
+void launch_spv_seg_score(const SpvSegParams& p, uint32_t nq, hipStream_t s);
+void launch_spv_seg_merge(const SpvSegParams& p, uint32_t nq, hipStream_t s);
 
 }  // namespace vdb

@@ -34,6 +34,10 @@ __global__ __launch_bounds__(256) void spv_fill_kernel(uint32_t* __restrict__ wo
 }
 
 __device__ inline bool live_row(const uint32_t* live, uint32_t row) { return (live[row >> 5] >> (row & 31)) & 1u; }
+// the list an entry goes to: its index, or (index, segment of the row) in a segmented file
+__device__ inline uint32_t list_key(const SpvBuildParams& p, uint32_t d, uint32_t row) {
+    return p.segs > 1 ? d * p.segs + (row >> p.seg_shift) : d;
+}
 
 // one wave per row: its lanes stride over the row's entries
 __global__ __launch_bounds__(BUILD_THREADS) void spv_histogram_kernel(SpvBuildParams p) {
@@ -41,7 +45,7 @@ __global__ __launch_bounds__(BUILD_THREADS) void spv_histogram_kernel(SpvBuildPa
     for (uint32_t row = blockIdx.x * (BUILD_THREADS / WAVE) + threadIdx.x / WAVE; row < p.n_rows; row += waves) {
         if (!live_row(p.live, row)) continue;
         const uint32_t e1 = p.row_ptr[row + 1];
-        for (uint32_t e = p.row_ptr[row] + lane; e < e1; e += WAVE) atomicAdd(&p.counts[p.idx[e]], 1u);
+        for (uint32_t e = p.row_ptr[row] + lane; e < e1; e += WAVE) atomicAdd(&p.counts[list_key(p, p.idx[e], row)], 1u);
     }
 }
 
@@ -77,7 +81,7 @@ __global__ __launch_bounds__(BUILD_THREADS) void spv_scatter_kernel(SpvBuildPara
         if (!live_row(p.live, row)) continue;
         const uint32_t e1 = p.row_ptr[row + 1];
         for (uint32_t e = p.row_ptr[row] + lane; e < e1; e += WAVE) {
-            const uint32_t d = p.idx[e];
+            const uint32_t d = list_key(p, p.idx[e], row);
             // below list_ptr[d + 1]: the histogram counted exactly the entries that come here
             const uint32_t slot = p.list_ptr[d] + atomicAdd(&p.counts[d], 1u);
             p.entries[slot] = SpvEntry{row, p.val[e]};

@@ -7,7 +7,9 @@
 // `vocab`, row_ptr is monotone and ends at the number of stored entries (below 2^32), every query has at most 1024 ascending
 // indices.  The scatter and the two list walks have no other guard.  The row-major route adds: every pair's table slot is below
 // the pass's count of distinct dimensions, those dimensions are below `vocab` = the size dim_slot is filled to, the table holds
-// one row more than that count, and a pass's queries lie inside one chunk of accumulator slots.
+// one row more than that count, and a pass's queries lie inside one chunk of accumulator slots.  The segmented walk
+// (vdb_spv_set_segmented) adds: the file in place was built with the segment size the launch names, its segments
+// cover the stored rows, its sub-list table has vocab * segments + 1 words, and a launch's partial lists fit their workspace.
 #include <limits>
 
 #include "kernels_spv.h"
@@ -36,7 +38,7 @@ struct vdb_spv_index {
     // the workspace of a search
     size_t cap = DEFAULT_CAP;
     DevBuf<float> d_acc, d_qval, d_out_dists;
-    DevBuf<uint32_t> d_qoff, d_qidx, d_ks, d_out_counts, d_flags;   // d_flags: [0] status, [2..5] the two 64-bit counters
+    DevBuf<uint32_t> d_qoff, d_qidx, d_ks, d_out_counts, d_flags;   // d_flags: [0] status, [2..7] the three 64-bit counters
     DevBuf<uint64_t> d_mask, d_out_ids;
     uint64_t rebuilds = 0, last_walked = 0, last_offered = 0, last_chunks = 0;
     // the row-major route
@@ -45,6 +47,12 @@ struct vdb_spv_index {
     DevBuf<uint32_t> d_dim_slot, d_table, d_qslot, d_udims;
     bool slots_clean = false;                                       // d_dim_slot is SPV_NO_SLOT up to its size
     uint64_t last_route = 0, last_passes = 0, last_work_inv = 0, last_work_rows = 0;
+    // the segmented walk
+    uint32_t seg_rows = 0;                                          // what vdb_spv_set_segmented asked for; 0: off
+    uint32_t file_segs = 0, file_shift = 0;                         // the file in place: its segments (0: not segmented) of 1 << file_shift rows
+    DevBuf<uint32_t> d_sub_ptr, d_tiles, d_part_cnt;
+    DevBuf<uint64_t> d_part;
+    uint64_t last_seg[4] = {0, 0, 0, 0};
 
     static constexpr size_t DEFAULT_CAP = 256u << 20;
 };
@@ -55,6 +63,8 @@ constexpr uint64_t MAX_ENTRIES = 0xffffffffull;                     // row_ptr a
 // Automatic route: row-major when the inverted route's counted work exceeds this many times the row-major route's (DESIGN.md
 // 4.20.1 "Measured": where the two routes' times cross, interpolated between two measured workloads).
 constexpr double ROUTE_RHO = 0.46;
+// A launch of the segmented walk has one workgroup of 1024 threads per segment along x: below 2^32 threads.
+constexpr uint64_t SEG_MAX_SEGS = 1u << 21;
 
 // One vector's pairs, sorted ascending by index into (oi, ov); refuses an index at or above 2^24 and a repeated index.
 int sorted_pairs(const uint32_t* in_i, const float* in_v, size_t n, const char* what, size_t which, std::vector<uint32_t>& oi,
@@ -118,19 +128,39 @@ int flush_locked(vdb_spv_index* h) {
     std::vector<uint64_t> sorted(by_id.size());
     for (size_t r = 0; r < by_id.size(); ++r) { sorted[r] = by_id[r].first; rank[by_id[r].second] = (uint32_t)r; }
     if ((rc = upload_tail(h->d_rank, rank, 0, s)) || (rc = upload_tail(h->d_sorted, sorted, 0, s))) return rc;
-    if ((rc = h->d_counts.ensure(std::max<size_t>(h->vocab, 1))) || (rc = h->d_list_ptr.ensure((size_t)h->vocab + 1)) ||
+    // segmented: at least two segments, and a sub-list table within its cap -- else the file is built as without the option
+    uint32_t segs = 0, shift = 0;
+    if (h->seg_rows && h->vocab) {
+        const uint64_t want = ((uint64_t)n_rows + h->seg_rows - 1) / h->seg_rows;
+        if (want >= 2 && want <= SEG_MAX_SEGS && (uint64_t)h->vocab * want + 1 <= vdb::SPV_SEG_TABLE_MAX) {
+            segs = (uint32_t)want;
+            while ((1u << shift) < h->seg_rows) ++shift;
+        }
+    }
+    const size_t n_keys = segs ? (size_t)h->vocab * segs : h->vocab;
+    const size_t n_tiles = (n_keys + vdb::SPV_SEG_SCAN_TILE - 1) / vdb::SPV_SEG_SCAN_TILE;
+    if ((rc = h->d_counts.ensure(std::max<size_t>(n_keys, 1))) || (rc = h->d_list_ptr.ensure((size_t)h->vocab + 1)) ||
         (rc = h->d_entries.ensure(std::max<uint64_t>(h->live_nnz, 1))))
         return rc;
-    vdb::SpvBuildParams p{h->d_row_ptr, h->d_idx, h->d_val, h->d_live, n_rows, h->vocab, h->d_counts, h->d_list_ptr, h->d_entries};
-    vdb::launch_spv_fill(h->d_counts, h->vocab, 0, s);
+    if (segs && ((rc = h->d_sub_ptr.ensure(n_keys + 1)) || (rc = h->d_tiles.ensure(2 * n_tiles + 1)))) return rc;
+    vdb::SpvBuildParams p{h->d_row_ptr, h->d_idx, h->d_val, h->d_live, n_rows, h->vocab, h->d_counts, segs ? h->d_sub_ptr : h->d_list_ptr,
+                          h->d_entries, segs, shift};
+    vdb::launch_spv_fill(h->d_counts, n_keys, 0, s);
     vdb::launch_spv_histogram(p, s);
-    vdb::launch_spv_scan(p, s);
+    if (segs) {                                                     // (n_keys > 0: no store without an index is segmented)
+        vdb::launch_spv_seg_scan(h->d_counts, h->d_sub_ptr, (uint32_t)n_keys, h->d_tiles, s);
+        vdb::launch_spv_seg_lists(h->d_sub_ptr, segs, h->vocab, h->d_list_ptr, s);
+    } else {
+        vdb::launch_spv_scan(p, s);
+    }
     vdb::launch_spv_scatter(p, s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));                               // (rank and sorted are read by the copies until here)
     h->up_rows = h->ids.size();
     h->up_nnz = h->idx.size();
     h->dirty = false;
+    h->file_segs = segs;
+    h->file_shift = shift;
     ++h->rebuilds;
     return VDB_OK;
 }
@@ -207,6 +237,8 @@ int search(vdb_spv_index* h, const size_t* q_offsets, const uint32_t* q_indices,
         if (d < h->vocab) h->last_work_inv += h->live_df[d];
     h->last_work_rows = h->live_nnz * ((nq + vdb::SPV_ROWS_TILE - 1) / vdb::SPV_ROWS_TILE);
     const bool by_rows = h->route == 1 || (h->route == 2 && (double)h->last_work_inv > ROUTE_RHO * (double)h->last_work_rows);
+    const bool by_segs = !by_rows && h->file_segs;                  // the inverted route over a segmented file: the segmented walk
+    h->last_seg[0] = h->last_seg[1] = h->last_seg[2] = h->last_seg[3] = 0;
     if (h->row_of.empty() || kmax == 0 || q_nnz == 0) {             // nothing can be a candidate
         for (size_t i = 0; i < nq; ++i) out_counts[i] = 0;
         return VDB_OK;
@@ -224,7 +256,7 @@ int search(vdb_spv_index* h, const size_t* q_offsets, const uint32_t* q_indices,
         return rc;
     // the accumulator slots: as many queries at once as the cap allows, at least one
     const size_t slots = std::min<size_t>(nq, std::max<size_t>(h->cap / (4 * (size_t)n_rows), 1));
-    if (h->d_acc.n < slots * n_rows) {
+    if (!by_segs && h->d_acc.n < slots * n_rows) {                  // (the segmented walk's accumulators are in LDS; its chunks stay these)
         if ((rc = h->d_acc.ensure(slots * n_rows))) return rc;
         vdb::launch_spv_fill(reinterpret_cast<uint32_t*>(h->d_acc.p), h->d_acc.n, vdb::SPV_UNTOUCHED, s);   // every search leaves them so
     }
@@ -271,6 +303,27 @@ int search(vdb_spv_index* h, const size_t* q_offsets, const uint32_t* q_indices,
         h->last_route = 1;
         h->last_passes = passes.size();
         h->last_chunks = (nq + slots - 1) / slots;
+    } else if (by_segs) {
+        // the partial lists, segs * kmax keys per query: a chunk is split further where they would exceed the cap (one query always runs)
+        const size_t per_query = (size_t)h->file_segs * kmax;
+        const size_t step = std::min<size_t>({slots, std::max<size_t>(h->cap / (8 * per_query), 1), 65535});   // (grid y)
+        if ((rc = h->d_part.ensure(step * per_query)) || (rc = h->d_part_cnt.ensure(step * h->file_segs))) return rc;
+        vdb::SpvSegParams g{};
+        g.q = p;
+        g.sub_ptr = h->d_sub_ptr; g.segs = h->file_segs; g.seg_shift = h->file_shift;
+        g.part = h->d_part; g.part_cnt = h->d_part_cnt;
+        for (size_t q0 = 0; q0 < nq; q0 += slots) {
+            const size_t q1 = std::min(q0 + slots, nq);
+            for (size_t a = q0; a < q1; a += step) {
+                g.q.q0 = (uint32_t)a;
+                vdb::launch_spv_seg_score(g, (uint32_t)std::min(step, q1 - a), s);
+                vdb::launch_spv_seg_merge(g, (uint32_t)std::min(step, q1 - a), s);
+            }
+            ++h->last_chunks;
+        }
+        h->last_seg[0] = 1;
+        h->last_seg[1] = h->file_segs;
+        h->last_seg[2] = 1ull << h->file_shift;
     } else {
         for (size_t q0 = 0; q0 < nq; q0 += slots) {
             p.q0 = (uint32_t)q0;
@@ -287,6 +340,7 @@ int search(vdb_spv_index* h, const size_t* q_offsets, const uint32_t* q_indices,
     if (by_rows) h->slots_clean = true;                             // every pass has put SPV_NO_SLOT back
     memcpy(&h->last_walked, flags + 2, 8);
     memcpy(&h->last_offered, flags + 4, 8);
+    memcpy(&h->last_seg[3], flags + 6, 8);                          // (zero on the other routes)
     if (flags[0] & vdb::ST_NAN) return fail_nan();
     return VDB_OK;
 }
@@ -442,6 +496,24 @@ int vdb_spv_route_stats(const vdb_spv_index* h, uint64_t out[4]) {
 }
 
 double vdb_spv_route_rho(void) { return ROUTE_RHO; }
+
+int vdb_spv_set_segmented(vdb_spv_index* h, size_t rows_per_segment) {
+    if (!h) return fail(VDB_ERR_INVALID_ARGUMENT, "null handle");
+    const size_t r = rows_per_segment;
+    if (r && (r < vdb::SPV_SEG_ROWS_MIN || r > vdb::SPV_SEG_ROWS_MAX || (r & (r - 1))))
+        return fail(VDB_ERR_INVALID_ARGUMENT, "rows per segment %zu: 0 (off) or a power of two in [%u, %u]", r, vdb::SPV_SEG_ROWS_MIN,
+                    vdb::SPV_SEG_ROWS_MAX);
+    std::lock_guard<std::mutex> g(h->mu);
+    if (r != h->seg_rows && h->rebuilds) h->dirty = true;           // the file in place has the other order: the next flush rebuilds it
+    h->seg_rows = (uint32_t)r;
+    return VDB_OK;
+}
+
+int vdb_spv_segment_stats(const vdb_spv_index* h, uint64_t out[4]) {
+    if (!h || !out) return fail(VDB_ERR_INVALID_ARGUMENT, "null argument");
+    for (int i = 0; i < 4; ++i) out[i] = h->last_seg[i];
+    return VDB_OK;
+}
 
 int vdb_spv_debug_set_workspace_cap(vdb_spv_index* h, size_t bytes) {
     if (!h) return fail(VDB_ERR_INVALID_ARGUMENT, "null handle");

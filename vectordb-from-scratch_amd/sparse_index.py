@@ -9,6 +9,7 @@ from . import _ffi
 from .index import _fp, _raise, _u64p
 
 MAX_K, MAX_QUERY_NNZ = 1024, 1024
+SEG_ROWS_MAX, SEG_ROWS = 16384, 8192                     # GpuSparseIndex.set_segmented: the largest segment; the default (DESIGN.md 4.20.2 "Measured")
 RRF_K = 60
 
 
@@ -159,6 +160,23 @@ class GpuSparseIndex:
 
     def route_rho(self):
         return float(self._L.vdb_spv_route_rho())
+
+    def set_segmented(self, rows=SEG_ROWS):
+        """How the inverted route walks: 0 one workgroup per query (default); a power of two in [64, 16384] one workgroup per
+        (query, segment of that many rows) with the accumulators in LDS, for requests of a few queries (segment_stats says whether
+        it ran: a store needs two segments).  The answers are the same to the bit; a change rebuilds the inverted file."""
+        rc = self._L.vdb_spv_set_segmented(self._h, int(rows))
+        if rc:
+            _raise(rc)
+
+    def segment_stats(self):
+        """of the last search: whether the segmented walk ran, its segments, rows per segment, and the (query, segment) workgroups
+        that found a posting"""
+        out = (ctypes.c_uint64 * 4)()
+        rc = self._L.vdb_spv_segment_stats(self._h, out)
+        if rc:
+            _raise(rc)
+        return dict(zip(("segmented", "segments", "rows_per_segment", "workgroups"), (int(x) for x in out)))
 
     def debug_set_workspace_cap(self, nbytes):
         """Lower the accumulator workspace (tests: several chunks on a small index); 0 restores 256 MiB."""

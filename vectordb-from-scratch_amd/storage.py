@@ -252,6 +252,13 @@ class VectorStore:
             raise ValueError("enable_sparse() first")
         self._sparse.set_route(mode)
 
+    def set_sparse_segmented(self, rows):
+        """How the inverted route of search_sparse / search_hybrid walks (GpuSparseIndex.set_segmented): 0 one workgroup per query,
+        a power of two in [64, 16384] one per (query, segment of that many rows).  The answers do not change."""
+        if self._sparse is None:
+            raise ValueError("enable_sparse() first")
+        self._sparse.set_segmented(rows)
+
     def insert_with_metadata(self, id, vector, metadata, sparse=None):   # storage.rs:135-172
         id = str(id)
         if sparse is not None and self._sparse is None:
