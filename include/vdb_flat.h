@@ -836,6 +836,62 @@ int vdb_spv_set_segmented(vdb_spv_index *h, size_t rows_per_segment);
 int vdb_spv_segment_stats(const vdb_spv_index *h, uint64_t out[4]);
 
 /*
+ * INT8 VECTORS: an index of its own for embeddings that arrive as signed 8-bit integers (no reference counterpart).  Widened to
+ * f32 they would cost four times the HBM and the whole certified pipeline, to reproduce integer sums that were exact to begin
+ * with; here the int8 matrix instructions of gfx950 accumulate them in i32 without rounding, and one pass over 1 B/element rows
+ * gives the answer itself.
+ *
+ * Definition (what the device is held to, bit for bit):
+ *  - A row and a query are dim signed 8-bit integers, 1 <= dim <= VDB_I8_MAX_DIM, the full range -128..127.  dim is fixed by the
+ *    first add; a later row or query of another dim is VDB_ERR_DIMENSION_MISMATCH.
+ *  - Three integer sums, exact:  s = sum q_i x_i,  nq = sum q_i^2,  nx = sum x_i^2.  |s| <= 2^28 and e = nq + nx - 2 s satisfies
+ *    0 <= e < 2^31: i32 holds every one of them.
+ *  - The distance is f32, a chain of single correctly rounded IEEE operations, never contracted:
+ *      VDB_METRIC_DOT        d = -(float)s               (s == 0 gives -0.0f)
+ *      VDB_METRIC_EUCLIDEAN  d = sqrtf((float)e)
+ *      VDB_METRIC_COSINE     sim = (float)s / (sqrtf((float)nq) * sqrtf((float)nx)), clamped to [-1, 1];  d = 1.0f - sim
+ *                            (the shape of src/distance.rs:47-64).  A live zero-norm row fails the call with
+ *                            VDB_ERR_INVALID_VECTOR, masked or not, and so does a zero-norm query anywhere in the batch, as on the
+ *                            dense index -- once the index holds a live row and some k_b > 0.
+ *    No NaN can arise.
+ *  - The answer is the k_b live, mask-eligible rows with the smallest (d as f32, id as unsigned 64-bit), ordered that way (-0.0
+ *    in front of +0.0); out_counts[b] = min(k_b, eligible).  ks, k, kstride, id_mask / mask_bits, the compiled vdb_meta_mask form
+ *    and the output arrays are those of vdb_spv_search_batch / _filtered; max k_b <= VDB_I8_MAX_K.  An empty index or k_b = 0:
+ *    count 0.
+ * vdb_i8_add_bulk: rows [n][dim]; an existing id is overwritten, only its last vector counts.  vdb_i8_remove: an absent id is
+ * VDB_OK.  vdb_i8_len: live rows.  Tombstones and the mask apply BEFORE top-k.  Mutations are externally serialised against
+ * searches by the caller's write lock, like vdb_flat_add; searches on one handle serialise themselves.
+ * How (csrc/kernels_i8.hip): the rows lie in HBM at ld = dim rounded up to 64 bytes, zero-padded, with an i32
+ * norm per row computed on the device as the rows arrive, the u64 id, its 32-bit rank among the live ids, and a live bitmap; the
+ * host keeps the id -> row map and NO copy of the rows.  vdb_i8_flush after a mutation (the next search does it otherwise) sends
+ * ids, ranks and live bits up and, under Cosine, counts the live zero-norm rows in one reduction kernel.  A search launches one
+ * workgroup per (segment of R consecutive rows, tile of QT queries): the query tile in LDS, the rows streamed from HBM straight
+ * into the operand registers of v_mfma_i32_16x16x64_i8, the distance, key, live bit, mask and a threshold select per query in
+ * the epilogue; then one workgroup per query merges the segments' partial lists (keys are unique: the merge is exact).
+ * vdb_i8_stats: [0] rows stored, live + dead  [1] dead rows  [2] dim  [3] ld; of the last search: [4] row segments  [5] (segment,
+ * query tile) workgroups launched  [6] keys that reached the merge; [7] QT << 32 | R of this build (QT: the tile of a search
+ * whose largest k is at most 128; above, 16 queries share a workgroup).
+ * Not built: reclaiming dead rows (they stay until the caller builds a new index); sharded handles; HNSW stores; uint8, binary
+ * and mixed int8 x f32 searches; by-id, recommend, MMR and the other composed reads.  Rows are below 2^32, dead ones included.
+ */
+#define VDB_I8_MAX_DIM 16384
+#define VDB_I8_MAX_K 1024
+typedef struct vdb_i8_index vdb_i8_index;
+int vdb_i8_create(int metric, int device, vdb_i8_index **out);
+void vdb_i8_destroy(vdb_i8_index *h);
+int vdb_i8_add_bulk(vdb_i8_index *h, const uint64_t *ids, const int8_t *rows /* [n][dim] */, size_t n, size_t dim);
+int vdb_i8_remove(vdb_i8_index *h, uint64_t id);
+size_t vdb_i8_len(const vdb_i8_index *h);
+int vdb_i8_flush(vdb_i8_index *h);
+int vdb_i8_search_batch(vdb_i8_index *h, const int8_t *queries /* [nq][dim] */, size_t nq, size_t dim, const size_t *ks, size_t k,
+                        const uint64_t *id_mask, size_t mask_bits, size_t kstride, uint64_t *out_ids, float *out_dists,
+                        size_t *out_counts);
+int vdb_i8_search_batch_filtered(vdb_i8_index *h, const int8_t *queries /* [nq][dim] */, size_t nq, size_t dim, const size_t *ks,
+                                 size_t k, const vdb_meta_mask *mask, size_t kstride, uint64_t *out_ids, float *out_dists,
+                                 size_t *out_counts);
+int vdb_i8_stats(const vdb_i8_index *h, uint64_t out[8]);
+
+/*
  * DIVERSE TOP-K (MAXIMAL MARGINAL RELEVANCE): k results that are not all the same thing (no reference counterpart; a caller would
  * search at depth m, get_vector every candidate and run an O(k m dim) loop on the host).  A request is a query q, a count k, a
  * candidate depth m and a trade-off lambda, 1 <= k <= m <= VDB_MMR_MAX_CANDIDATES, lambda an f32 in [0, 1].

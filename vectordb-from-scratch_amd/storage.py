@@ -12,6 +12,7 @@ import numpy as np
 from .error import DimensionMismatch, VectorNotFound
 from .hnsw import GpuHnswIndex
 from .index import GROUP_NONE, GpuFlatIndex, Index, MetaTable
+from .int8_index import GpuInt8Index
 from .sparse_index import GpuSparseIndex, rrf_fuse
 from .vector import DistanceMetric, Vector
 
@@ -137,6 +138,7 @@ class BatchInsertItem:                               # storage.rs:74-79
     vector: Vector
     metadata: Metadata = field(default_factory=Metadata)
     sparse: tuple = None                             # (indices, values): the row's sparse vector (VectorStore.enable_sparse)
+    int8: object = None                              # np.int8 [dim]: the row's int8 vector (VectorStore.enable_int8)
 
 
 class _Column:
@@ -227,6 +229,7 @@ class VectorStore:
         self._table = None
         self._lut_sent = {}                              # field -> dictionary codes whose numbers the table has (MetaTable.set_numbers)
         self._sparse = None                              # enable_sparse: a GpuSparseIndex keyed by the same internal ids
+        self._int8 = None                                # enable_int8: a GpuInt8Index keyed by the same internal ids
 
     @classmethod
     def with_index(cls, index):                      # storage.rs:118-127
@@ -259,10 +262,21 @@ class VectorStore:
             raise ValueError("enable_sparse() first")
         self._sparse.set_segmented(rows)
 
-    def insert_with_metadata(self, id, vector, metadata, sparse=None):   # storage.rs:135-172
+    def enable_int8(self, metric=None):
+        """Keep an int8 vector beside the dense one (GpuInt8Index on the index's GPU, keyed by the same internal id, so every
+        mask of compile_filter applies to it unchanged): insert_with_metadata(..., int8=row), search_int8.  metric: the store's
+        own by default.  Flat stores only."""
+        if not isinstance(self._index, GpuFlatIndex):
+            raise ValueError("int8 vectors need a GpuFlatIndex")
+        if self._int8 is None:
+            self._int8 = GpuInt8Index(self._index.metric() if metric is None else DistanceMetric(metric), self._index._device)
+
+    def insert_with_metadata(self, id, vector, metadata, sparse=None, int8=None):   # storage.rs:135-172
         id = str(id)
         if sparse is not None and self._sparse is None:
             raise ValueError("enable_sparse() first")
+        if int8 is not None and self._int8 is None:
+            raise ValueError("enable_int8() first")
         dim = vector.dimension()
         if self._dimension is not None:
             if dim != self._dimension:
@@ -276,6 +290,8 @@ class VectorStore:
             self._index.remove(old)
             if self._sparse is not None:
                 self._sparse.remove(old)
+            if self._int8 is not None:
+                self._int8.remove(old)
             self._metadata.pop(old, None)
             self._internal_to_id.pop(old, None)
         internal = self._next_id
@@ -283,6 +299,8 @@ class VectorStore:
         self._index.add(internal, vector)
         if sparse is not None:
             self._sparse.add(internal, sparse[0], sparse[1])
+        if int8 is not None:
+            self._int8.add(internal, int8)
         self._id_to_internal[id] = internal
         self._internal_to_id[internal] = id
         self._metadata[internal] = metadata
@@ -298,7 +316,7 @@ class VectorStore:
 
     def insert_batch(self, items):                   # storage.rs:293-298
         for it in items:
-            self.insert_with_metadata(it.id, it.vector, it.metadata, sparse=it.sparse)
+            self.insert_with_metadata(it.id, it.vector, it.metadata, sparse=it.sparse, int8=it.int8)
 
     def delete(self, id):                            # storage.rs:175-192
         internal = self._id_to_internal.pop(id, None)
@@ -314,6 +332,8 @@ class VectorStore:
         self._index.remove(internal)
         if self._sparse is not None:
             self._sparse.remove(internal)
+        if self._int8 is not None:
+            self._int8.remove(internal)
         self._mark_present(internal, False)
         return v
 
@@ -714,6 +734,18 @@ class VectorStore:
         if not queries:
             return []
         return [self._map(r) for r in self._sparse_lists(queries, k, flt)]
+
+    def search_int8(self, query, k, flt=None):
+        """The k rows whose int8 vector is nearest to query (np.int8 [dim]) under the metric of enable_int8, as SearchResults,
+        best first.  flt is a PRE-filter."""
+        return self.search_int8_batch(np.asarray(query).reshape(1, -1), k, flt)[0]
+
+    def search_int8_batch(self, queries, k, flt=None):
+        if self._int8 is None:
+            raise ValueError("enable_int8() first")
+        ids, dists, counts = self._masked(flt, lambda m, b, cm: self._int8.search_batch_arrays(queries, int(k), id_mask=m, mask_bits=b,
+                                                                                               compiled_mask=cm))
+        return [self._map([(int(ids[q, i]), dists[q, i]) for i in range(int(counts[q]))]) for q in range(ids.shape[0])]
 
     def search_hybrid(self, dense_query, sparse_query, k, flt=None, depth=None):
         """Hybrid retrieval: the dense search and the sparse search both run at `depth` (default max(k, 100), at most 1024) under
