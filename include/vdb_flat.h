@@ -871,8 +871,9 @@ int vdb_spv_segment_stats(const vdb_spv_index *h, uint64_t out[4]);
  * vdb_i8_stats: [0] rows stored, live + dead  [1] dead rows  [2] dim  [3] ld; of the last search: [4] row segments  [5] (segment,
  * query tile) workgroups launched  [6] keys that reached the merge; [7] QT << 32 | R of this build (QT: the tile of a search
  * whose largest k is at most 128; above, 16 queries share a workgroup).
- * Not built: reclaiming dead rows (they stay until the caller builds a new index); sharded handles; HNSW stores; uint8, binary
- * and mixed int8 x f32 searches; by-id, recommend, MMR and the other composed reads.  Rows are below 2^32, dead ones included.
+ * Not built: reclaiming dead rows (they stay until the caller builds a new index); sharded handles; HNSW stores; uint8 and
+ * mixed int8 x f32 searches (binary vectors have an index of their own, below); by-id, recommend, MMR and the other composed
+ * reads.  Rows are below 2^32, dead ones included.
  */
 #define VDB_I8_MAX_DIM 16384
 #define VDB_I8_MAX_K 1024
@@ -890,6 +891,60 @@ int vdb_i8_search_batch_filtered(vdb_i8_index *h, const int8_t *queries /* [nq][
                                  size_t k, const vdb_meta_mask *mask, size_t kstride, uint64_t *out_ids, float *out_dists,
                                  size_t *out_counts);
 int vdb_i8_stats(const vdb_i8_index *h, uint64_t out[8]);
+
+/*
+ * BINARY VECTORS: an index of its own for 1-bit embeddings and fingerprints under Hamming or Jaccard / Tanimoto distance (no
+ * reference counterpart).  Widened to int8 they would cost 8 times the HBM, to f32 32 times and the whole certified pipeline, to
+ * get back integer counts that were exact to begin with; here the rows stay packed at 1 bit per element, are widened to 0/1
+ * bytes in registers and counted on the int8 matrix instructions of gfx950, and one pass gives the answer itself.
+ *
+ * Definition (what the device is held to, bit for bit):
+ *  - A row and a query are dim bits, dim a multiple of 8 and 8 <= dim <= VDB_BIN_MAX_DIM, passed packed as dim / 8 bytes.  The
+ *    bit order within a byte is the caller's, the same for rows and queries; nothing depends on it.  dim is fixed by the first
+ *    add; a later row or query of another dim is VDB_ERR_DIMENSION_MISMATCH, a dim outside the range VDB_ERR_INVALID_ARGUMENT
+ *    before anything is stored.
+ *  - Exact integers:  nq = popcount(q),  nx = popcount(x),  a = popcount(q & x),  h = popcount(q ^ x) = nq + nx - 2 a,
+ *    u = popcount(q | x) = nq + nx - a; all at most 32768.
+ *  - The distance is f32, single correctly rounded IEEE operations, never contracted:
+ *      VDB_BIN_HAMMING  d = (float)h
+ *      VDB_BIN_JACCARD  d = (u == 0) ? 0.0f : 1.0f - (float)a / (float)u
+ *    No NaN, no -0.0 and no error case can arise.
+ *  - The answer is the k_b live, mask-eligible rows with the smallest (d as f32, id as unsigned 64-bit), ordered that way;
+ *    out_counts[b] = min(k_b, eligible).  ks, k, kstride, id_mask / mask_bits, the compiled vdb_meta_mask form and the output
+ *    arrays are those of the int8 index's batch searches; max k_b <= VDB_BIN_MAX_K.  An empty index or k_b = 0: count 0.
+ *    Hamming distances tie massively: the id tie-break is the normal case here.
+ * Overwrite (the last vector of an id counts), tombstones, "mask before top-k", the locking contract and "no host copy of the
+ * rows" are as on the int8 index.
+ * How (csrc/kernels_bin.hip): packed rows in HBM at a stride of whole 64-byte chunks, zero-padded, with an i32
+ * popcount per row computed on the device as the rows arrive.  A search widens the batch's queries once, then launches one
+ * workgroup per (segment of R consecutive rows, tile of QT queries); every workgroup of a launch shares one proven threshold
+ * per query in HBM, tests its integer sums against it in registers and forms keys for the survivors only; one workgroup per
+ * query merges the partial lists.  The lists are the exact top-k whatever the timing; the work done is not:
+ * the stats of the last search: [0] rows stored, live + dead  [1] dead rows  [2] dim in bits  [3] row stride in bytes  [4] row
+ * segments  [5] (segment, query tile) workgroups launched  [6] keys that reached the merge -- TIMING-DEPENDENT, it varies from
+ * call to call with the order in which workgroups publish their thresholds; [7] QT << 32 | R of this build (QT: the tile of a
+ * search whose largest k is at most 128; above, 16 queries share a workgroup).
+ * Not built: compaction (dead rows stay until the caller builds a new index); sharded handles; HNSW stores; by-id, recommend,
+ * MMR and the other composed reads; dim that is not a multiple of 8.  Rows are below 2^32, dead ones included.
+ */
+#define VDB_BIN_HAMMING 0
+#define VDB_BIN_JACCARD 1
+#define VDB_BIN_MAX_DIM 32768
+#define VDB_BIN_MAX_K 1024
+typedef struct vdb_bin_index vdb_bin_index;
+int vdb_bin_create(int metric, int device, vdb_bin_index **out);
+void vdb_bin_destroy(vdb_bin_index *h);
+int vdb_bin_add_bulk(vdb_bin_index *h, const uint64_t *ids, const uint8_t *rows /* [n][dim / 8] */, size_t n, size_t dim /* bits */);
+int vdb_bin_remove(vdb_bin_index *h, uint64_t id);
+size_t vdb_bin_len(const vdb_bin_index *h);
+int vdb_bin_flush(vdb_bin_index *h);
+int vdb_bin_search_batch(vdb_bin_index *h, const uint8_t *queries /* [nq][dim / 8] */, size_t nq, size_t dim, const size_t *ks,
+                         size_t k, const uint64_t *id_mask, size_t mask_bits, size_t kstride, uint64_t *out_ids, float *out_dists,
+                         size_t *out_counts);
+int vdb_bin_search_batch_filtered(vdb_bin_index *h, const uint8_t *queries /* [nq][dim / 8] */, size_t nq, size_t dim,
+                                  const size_t *ks, size_t k, const vdb_meta_mask *mask, size_t kstride, uint64_t *out_ids,
+                                  float *out_dists, size_t *out_counts);
+int vdb_bin_stats(const vdb_bin_index *h, uint64_t out[8]);
 
 /*
  * DIVERSE TOP-K (MAXIMAL MARGINAL RELEVANCE): k results that are not all the same thing (no reference counterpart; a caller would

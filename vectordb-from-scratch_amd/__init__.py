@@ -11,11 +11,12 @@ from .error import (DimensionMismatch, IndexError_, InvalidVector, NanDistance, 
                     VectorNotFound)
 from .index import CompiledMask, GpuFlatIndex, Index, MetaTable
 from .hnsw import GpuHnswIndex, HnswParams
+from .binary_index import BinaryMetric, GpuBinaryIndex
 from .int8_index import GpuInt8Index
 from .sparse_index import GpuSparseIndex
 from .storage import BatchInsertItem, Metadata, MetadataFilter, SearchResult, VectorStore, num
 from .vector import DistanceMetric, Vector
 
-__all__ = ["build", "GpuFlatIndex", "MetaTable", "CompiledMask", "GpuHnswIndex", "HnswParams", "GpuSparseIndex", "GpuInt8Index", "Index", "VectorStore", "Vector", "DistanceMetric", "Metadata",
+__all__ = ["build", "GpuFlatIndex", "MetaTable", "CompiledMask", "GpuHnswIndex", "HnswParams", "GpuSparseIndex", "GpuInt8Index", "GpuBinaryIndex", "BinaryMetric", "Index", "VectorStore", "Vector", "DistanceMetric", "Metadata",
            "MetadataFilter", "num", "SearchResult", "BatchInsertItem", "VectorDbError", "DimensionMismatch",
            "InvalidVector", "VectorNotFound", "IndexError_", "NanDistance"]

@@ -29,6 +29,8 @@ SYMBOLS = [
     "vdb_spv_set_segmented", "vdb_spv_segment_stats",
     "vdb_i8_create", "vdb_i8_destroy", "vdb_i8_add_bulk", "vdb_i8_remove", "vdb_i8_len", "vdb_i8_flush", "vdb_i8_search_batch",
     "vdb_i8_search_batch_filtered", "vdb_i8_stats",
+    "vdb_bin_create", "vdb_bin_destroy", "vdb_bin_add_bulk", "vdb_bin_remove", "vdb_bin_len", "vdb_bin_flush", "vdb_bin_search_batch",
+    "vdb_bin_search_batch_filtered", "vdb_bin_stats",
     "vdb_flat_search_batch_mmr", "vdb_flat_search_batch_mmr_filtered", "vdb_flat_mmr_stats",
     "vdb_flat_search_batch_distinct", "vdb_flat_search_batch_distinct_filtered", "vdb_flat_distinct_stats", "vdb_flat_distinct_depth",
     "vdb_flat_search_batch_grouped", "vdb_flat_search_batch_grouped_filtered", "vdb_flat_grouped_stats", "vdb_flat_debug_group_plan",
@@ -234,6 +236,18 @@ def lib():
     L.vdb_i8_search_batch.argtypes = [vp, i8p, sz, sz, szp, sz, u64p, sz, sz, u64p, fp, szp]
     L.vdb_i8_search_batch_filtered.argtypes = [vp, i8p, sz, sz, szp, sz, vp, sz, u64p, fp, szp]
     L.vdb_i8_stats.argtypes = [vp, u64p]
+    u8p = c.POINTER(c.c_uint8)
+    L.vdb_bin_create.argtypes = [c.c_int, c.c_int, c.POINTER(vp)]
+    L.vdb_bin_destroy.argtypes = [vp]
+    L.vdb_bin_destroy.restype = None
+    L.vdb_bin_add_bulk.argtypes = [vp, u64p, u8p, sz, sz]
+    L.vdb_bin_remove.argtypes = [vp, u64]
+    L.vdb_bin_len.argtypes = [vp]
+    L.vdb_bin_len.restype = sz
+    L.vdb_bin_flush.argtypes = [vp]
+    L.vdb_bin_search_batch.argtypes = [vp, u8p, sz, sz, szp, sz, u64p, sz, sz, u64p, fp, szp]
+    L.vdb_bin_search_batch_filtered.argtypes = [vp, u8p, sz, sz, szp, sz, vp, sz, u64p, fp, szp]
+    L.vdb_bin_stats.argtypes = [vp, u64p]
     L.vdb_flat_search_batch_mmr.argtypes = [vp, fp, sz, sz, szp, sz, sz, fp, c.c_float, u64p, sz, sz, u64p, fp, fp, szp]
     L.vdb_flat_search_batch_mmr_filtered.argtypes = [vp, fp, sz, sz, szp, sz, sz, fp, c.c_float, vp, sz, u64p, fp, fp, szp]
     L.vdb_flat_mmr_stats.argtypes = [vp, u64p]

@@ -12,6 +12,7 @@ import numpy as np
 from .error import DimensionMismatch, VectorNotFound
 from .hnsw import GpuHnswIndex
 from .index import GROUP_NONE, GpuFlatIndex, Index, MetaTable
+from .binary_index import BinaryMetric, GpuBinaryIndex
 from .int8_index import GpuInt8Index
 from .sparse_index import GpuSparseIndex, rrf_fuse
 from .vector import DistanceMetric, Vector
@@ -139,6 +140,7 @@ class BatchInsertItem:                               # storage.rs:74-79
     metadata: Metadata = field(default_factory=Metadata)
     sparse: tuple = None                             # (indices, values): the row's sparse vector (VectorStore.enable_sparse)
     int8: object = None                              # np.int8 [dim]: the row's int8 vector (VectorStore.enable_int8)
+    binary: object = None                            # np.uint8 [dim / 8]: the row's packed binary vector (VectorStore.enable_binary)
 
 
 class _Column:
@@ -230,6 +232,7 @@ class VectorStore:
         self._lut_sent = {}                              # field -> dictionary codes whose numbers the table has (MetaTable.set_numbers)
         self._sparse = None                              # enable_sparse: a GpuSparseIndex keyed by the same internal ids
         self._int8 = None                                # enable_int8: a GpuInt8Index keyed by the same internal ids
+        self._binary = None                              # enable_binary: a GpuBinaryIndex keyed by the same internal ids
 
     @classmethod
     def with_index(cls, index):                      # storage.rs:118-127
@@ -271,12 +274,23 @@ class VectorStore:
         if self._int8 is None:
             self._int8 = GpuInt8Index(self._index.metric() if metric is None else DistanceMetric(metric), self._index._device)
 
-    def insert_with_metadata(self, id, vector, metadata, sparse=None, int8=None):   # storage.rs:135-172
+    def enable_binary(self, metric):
+        """Keep a packed binary vector beside the dense one (GpuBinaryIndex on the index's GPU, keyed by the same internal id, so
+        every mask of compile_filter applies to it unchanged): insert_with_metadata(..., binary=row), search_binary.  metric: a
+        BinaryMetric.  Flat stores only."""
+        if not isinstance(self._index, GpuFlatIndex):
+            raise ValueError("binary vectors need a GpuFlatIndex")
+        if self._binary is None:
+            self._binary = GpuBinaryIndex(BinaryMetric(metric), self._index._device)
+
+    def insert_with_metadata(self, id, vector, metadata, sparse=None, int8=None, binary=None):   # storage.rs:135-172
         id = str(id)
         if sparse is not None and self._sparse is None:
             raise ValueError("enable_sparse() first")
         if int8 is not None and self._int8 is None:
             raise ValueError("enable_int8() first")
+        if binary is not None and self._binary is None:
+            raise ValueError("enable_binary() first")
         dim = vector.dimension()
         if self._dimension is not None:
             if dim != self._dimension:
@@ -292,6 +306,8 @@ class VectorStore:
                 self._sparse.remove(old)
             if self._int8 is not None:
                 self._int8.remove(old)
+            if self._binary is not None:
+                self._binary.remove(old)
             self._metadata.pop(old, None)
             self._internal_to_id.pop(old, None)
         internal = self._next_id
@@ -301,6 +317,8 @@ class VectorStore:
             self._sparse.add(internal, sparse[0], sparse[1])
         if int8 is not None:
             self._int8.add(internal, int8)
+        if binary is not None:
+            self._binary.add(internal, binary)
         self._id_to_internal[id] = internal
         self._internal_to_id[internal] = id
         self._metadata[internal] = metadata
@@ -316,7 +334,7 @@ class VectorStore:
 
     def insert_batch(self, items):                   # storage.rs:293-298
         for it in items:
-            self.insert_with_metadata(it.id, it.vector, it.metadata, sparse=it.sparse, int8=it.int8)
+            self.insert_with_metadata(it.id, it.vector, it.metadata, sparse=it.sparse, int8=it.int8, binary=it.binary)
 
     def delete(self, id):                            # storage.rs:175-192
         internal = self._id_to_internal.pop(id, None)
@@ -334,6 +352,8 @@ class VectorStore:
             self._sparse.remove(internal)
         if self._int8 is not None:
             self._int8.remove(internal)
+        if self._binary is not None:
+            self._binary.remove(internal)
         self._mark_present(internal, False)
         return v
 
@@ -745,6 +765,18 @@ class VectorStore:
             raise ValueError("enable_int8() first")
         ids, dists, counts = self._masked(flt, lambda m, b, cm: self._int8.search_batch_arrays(queries, int(k), id_mask=m, mask_bits=b,
                                                                                                compiled_mask=cm))
+        return [self._map([(int(ids[q, i]), dists[q, i]) for i in range(int(counts[q]))]) for q in range(ids.shape[0])]
+
+    def search_binary(self, query, k, flt=None):
+        """The k rows whose binary vector is nearest to query (np.uint8 [dim / 8], packed) under the metric of enable_binary, as
+        SearchResults, best first.  flt is a PRE-filter."""
+        return self.search_binary_batch(np.asarray(query).reshape(1, -1), k, flt)[0]
+
+    def search_binary_batch(self, queries, k, flt=None):
+        if self._binary is None:
+            raise ValueError("enable_binary() first")
+        ids, dists, counts = self._masked(flt, lambda m, b, cm: self._binary.search_batch_arrays(queries, int(k), id_mask=m, mask_bits=b,
+                                                                                                 compiled_mask=cm))
         return [self._map([(int(ids[q, i]), dists[q, i]) for i in range(int(counts[q]))]) for q in range(ids.shape[0])]
 
     def search_hybrid(self, dense_query, sparse_query, k, flt=None, depth=None):
